@@ -8,6 +8,7 @@ A "step" is ONE ADMM iteration (one call of Optimization3D_multi::optimization_d
 reference) over the whole fleet.  The timed region is exactly K iterations starting from the initial
 trajectory (init_variable), cloud + BVH + state already resident in HBM, no host read-back inside.
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the roofline and cpu_baseline objects).
+--dump-outputs DIR writes the state after the last timed step as DIR/<name>.npy (seeded scenes: the same inputs on every run).
 """
 import argparse
 import importlib
@@ -274,6 +275,25 @@ def states_equal(a, b, u0=0, u1=None):
     return all(np.array_equal(a[k][u0:u1], b[k][u0:u1]) for k in STATE_KEYS)
 
 
+DUMP_LIMIT = 64 << 20   # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(outdir, st):
+    """--dump-outputs DIR: the state arrays the timed path's caller receives after its last step, one DIR/<name>.npy each (float64, as the
+    library returns them).  A set larger than DUMP_LIMIT keeps a fixed, seeded sample of the robots (the same rows on every run; their
+    indices in DIR/robot_index.npy)."""
+    os.makedirs(outdir, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(st[k], dtype=np.float64) for k in STATE_KEYS}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT:
+        U = arrs["spline"].shape[0]
+        keep = np.sort(np.random.default_rng(0).choice(U, max(1, U * DUMP_LIMIT // total), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+        np.save(os.path.join(outdir, "robot_index.npy"), keep.astype(np.float64))
+    for k, a in arrs.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 def bench_group(pkg, scene, devices, args):
     """K iterations through tj_group (one process, one host thread per rank inside the library).  Same top-level keys as the
     single-GPU line; `roofline` / `cpu_baseline` are null here (they are N = 1 objects, see the default run).
@@ -347,6 +367,8 @@ def bench_group(pkg, scene, devices, args):
         import hashlib
         stt = grp.get_state()
         check = hashlib.sha256(np.ascontiguousarray(stt["spline"]).tobytes() + np.ascontiguousarray(stt["piece_time"]).tobytes()).hexdigest()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, grp.get_state())
     ex_us = [float(x) for x in grp.profile_exchange(50)] if multi else [0.0] * 5
     grp.close()
     # the same schedule on ONE rank through the same entry point: what the phase schedule itself costs without any exchange
@@ -403,7 +425,11 @@ def main():
                                                           "collectives), e.g. 0,1,2,3 -- entries may repeat (0,0 = two ranks on one GPU).  `--gpus N` without torchrun selects devices 0..N-1")
     ap.add_argument("--validate-iters", type=int, default=8, help="multi-GPU runs: iterations of the untimed self-validation (sharded state == one-rank state, bitwise) that precedes the timing")
     ap.add_argument("--state-checksum", action="store_true", help="each rank also prints 'CHECK <rank> <sha256 of its owned robots\' final control points and piece times>'")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the state the timed path computed in its last step as DIR/<name>.npy "
+                                                                          "(float64; sharded runs: the robots rank 0 owns) -- to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     pkg = importlib.import_module("traj-opt-admm_amd")
     sc = pkg.scenes
@@ -600,6 +626,11 @@ def main():
     if st["order_unresolved"]:
         raise SystemExit(f"inter-robot CCD clamp: {st['order_unresolved']} segments whose pair order could not be replayed in the reference's tree order")
 
+    if not sharded and st["iters"] != K:
+        raise SystemExit(f"the timed window ran {st['iters']} iterations, --steps asked for {K}")
+    if args.dump_outputs and rank == 0:
+        u0, u1 = rank * scene["U"] // world, (rank + 1) * scene["U"] // world
+        dump_outputs(args.dump_outputs, {k: v[u0:u1] for k, v in slv.get_state().items()})
     if args.state_checksum:
         import hashlib
         stt = slv.get_state()

@@ -245,7 +245,7 @@ def test_coupled_chain_with_cache_units_changes_no_bit(pkg, scenes, monkeypatch)
     scene = dict(scenes.crossing(12, 4000, seed=23, name="crossing-U12-coupled"), mode=2)
     monkeypatch.delenv("TJ_COUPLED_UNITS", raising=False)
     # the default since the second half of round 5: the Newton solve on a second queue next to k_grad (one gate launch more per iteration) -- same bits as the one-queue chain
-    monkeypatch.delenv("TJ_XS_ASYNC", raising=False)
+    monkeypatch.setenv("TJ_XS_ASYNC", "1")   # explicit: the default takes the second queue only where the process's hardware-queue budget allows (GPU_MAX_HW_QUEUES)
     e = pkg.Solver(scene, stop=0.0)
     l0 = e.launch_count(); e.iterate(12); le = e.launch_count() - l0
     se, te = e.get_state(), e.stats()

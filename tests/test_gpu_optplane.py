@@ -309,7 +309,11 @@ def test_asynchronous_plane_refinement_changes_no_bit(pkg, scenes, monkeypatch, 
     scene = {"scn_b": scenes.scn_b, "scn_c": scenes.scn_c}[scene_name]()
     for k in ("TJ_KEEP_ASYNC", "TJ_XS_ASYNC"):
         monkeypatch.delenv(k, raising=False)
+    # the refinement's queue is requested explicitly (the default takes it only where the process's hardware-queue budget, GPU_MAX_HW_QUEUES - 1 per device, allows),
+    # and the Newton solve stays on the chain's queue in both runs so that the context needs no more than two queues
+    monkeypatch.setenv("TJ_XS_ASYNC", "0")
     n_it = 40
+    monkeypatch.setenv("TJ_KEEP_ASYNC", "1")
     a = pkg.Solver(scene, stop=0.0, optimal_plane=1)
     l0 = a.launch_count(); a.iterate_async(n_it); a.sync(); la = a.launch_count() - l0
     sa, ta = a.get_state(), a.stats(); on_a, cd_a = a.get_pair_cache()

@@ -1153,9 +1153,9 @@ int tj_set_state(tj_ctx* c, int u, const double* spline, const double* p_slack, 
   return TJ_OK;
 }
 
-int tj_iterate_async(tj_ctx* c, int n_iters) {
-  if (!c || n_iters < 0) return TJ_ERR_INVALID;
-  if (!ready(c)) return TJ_ERR_INVALID;
+namespace {
+// the parts of tj_iterate_async (also used by the lockstep enqueue of the ranks of a group that share a device, tj_group.h)
+int iterate_async_prologue(tj_ctx* c, int n_iters) {
   if (c->heal && n_iters > 0 && (c->xs_two_queues || c->keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
     if (c->snap_iters == 0 && !c->heal_busy) {
       if (!c->begin_folded) c->snap_in_begin = true;   // the batch's first launch is k_begin: the snapshot rides in it
@@ -1164,13 +1164,39 @@ int tj_iterate_async(tj_ctx* c, int n_iters) {
     if (!c->heal_busy) c->snap_iters += n_iters;
   }
   if (n_iters > 0) { int r = ensure_hull_cache(c); if (r) return r; }
-  // inside a batch the begin work of iteration i+1 rides on iteration i's k_linesearch (not in coupled mode, whose line search
-  // is several kernels, and not in the captured-graph replay, which is one fixed iteration)
-  // (coupled mode: only where the whole search is ONE launch whose last block commits -- lsc_wide, one context)
-  const bool chain = !c->use_graph && (c->d.mode != TJ_MODE_MULTI_COUPLED || (c->lsc_wide && c->d.u1 - c->d.u0 == c->d.U));
+  return TJ_OK;
+}
+
+// inside a batch the begin work of iteration i+1 rides on iteration i's k_linesearch (not in coupled mode, whose line search
+// is several kernels, and not in the captured-graph replay, which is one fixed iteration)
+// (coupled mode: only where the whole search is ONE launch whose last block commits -- lsc_wide, one context)
+bool iterate_async_chain(const tj_ctx* c) {
+  return !c->use_graph && (c->d.mode != TJ_MODE_MULTI_COUPLED || (c->lsc_wide && c->d.u1 - c->d.u0 == c->d.U));
+}
+
+// chain position of iteration i of a batch of n (clears begin_folded: the fold it reports is consumed here)
+int iterate_async_pos(tj_ctx* c, bool chain, int i, int n) {
+  const int pos = chain ? (((i > 0 || c->begin_folded) ? 1 : 0) | (i + 1 < n ? 2 : 0)) : 0;
+  c->begin_folded = false;
+  return pos;
+}
+
+// part of an eager iteration: kernels [k0, k1) of the stream order (enqueue_iteration is all of them)
+int enqueue_iteration_part(tj_ctx* c, int chain_pos, int k0, int k1) {
+  for (int k = k0; k < k1; k++) launch_kernel(c, k, c->stream, 0, true, false, chain_pos);
+  HIPCHK(c, hipGetLastError());
+  c->maybe_deferred = true;
+  return TJ_OK;
+}
+}  // namespace
+
+int tj_iterate_async(tj_ctx* c, int n_iters) {
+  if (!c || n_iters < 0) return TJ_ERR_INVALID;
+  if (!ready(c)) return TJ_ERR_INVALID;
+  { int r = iterate_async_prologue(c, n_iters); if (r) return r; }
+  const bool chain = iterate_async_chain(c);
   for (int i = 0; i < n_iters; i++) {
-    const int pos = chain ? (((i > 0 || c->begin_folded) ? 1 : 0) | (i + 1 < n_iters ? 2 : 0)) : 0;
-    c->begin_folded = false;
+    const int pos = iterate_async_pos(c, chain, i, n_iters);
     int r = launch_graph_or_eager(c, 3, pos); if (r) return r;
   }
   c->iters_enqueued += n_iters;

@@ -255,6 +255,37 @@ int group_rank_loop(tj_group* g, int r, int n_iters, bool careful = false, long*
   return TJ_OK;
 }
 
+// Direct exchange, ranks that share a device: HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues per device and lets further streams share them, and a
+// shared queue starts its kernels one after another in submission order.  A kernel that waits for a peer's push must then never be submitted ahead of the kernel that
+// pushes: with three ranks on a device of two queues a rank's k_front / k_ccd waited at the head of a queue for a peer whose producer stood behind it, until the 2 s limit.
+// So one host thread enqueues the batch for all ranks, iteration by iteration and part by part, every rank's part before any rank's next part: k_begin (pushes the
+// control points at a batch's start), k_hullinfo .. k_xsolve (k_front waits for the control points, k_xsolve pushes the direction records), k_ccd .. k_linesearch (k_ccd
+// waits for the direction records, k_linesearch pushes the control points of the next iteration) -- every wait stands behind its producers in whatever queue they share.
+// Same kernels and chain positions per rank as tj_iterate_async; only the host's interleaving differs.
+int group_direct_lockstep(tj_group* g, int n_iters, std::vector<int>& rc) {
+  std::vector<bool> chain(g->n);
+  for (int r = 0; r < g->n; r++) {
+    tj_ctx* c = g->ctx[r];
+    if (hipSetDevice(g->dev[r]) != hipSuccess) { c->err = "hipSetDevice failed"; return rc[r] = TJ_ERR_DEVICE; }
+    if (!ready(c)) return rc[r] = TJ_ERR_INVALID;
+    if ((rc[r] = iterate_async_prologue(c, n_iters))) return rc[r];
+    chain[r] = iterate_async_chain(c);
+  }
+  for (int i = 0; i < n_iters; i++) {
+    std::vector<int> pos(g->n);
+    static const int cut[4] = {0, K_HULLINFO, K_CCD_PREP, K_COUNT};
+    for (int part = 0; part < 3; part++)
+      for (int r = 0; r < g->n; r++) {
+        tj_ctx* c = g->ctx[r];
+        if (hipSetDevice(g->dev[r]) != hipSuccess) { c->err = "hipSetDevice failed"; return rc[r] = TJ_ERR_DEVICE; }
+        if (part == 0) pos[r] = iterate_async_pos(c, chain[r], i, n_iters);
+        if ((rc[r] = enqueue_iteration_part(c, pos[r], cut[part], cut[part + 1]))) return rc[r];
+      }
+  }
+  for (int r = 0; r < g->n; r++) g->ctx[r]->iters_enqueued += n_iters;
+  return TJ_OK;
+}
+
 int group_fail(tj_group* g, int rc, const std::string& m) { g->err = m; return rc; }
 thread_local std::string g_group_create_err;   // why this thread's last tj_group_create failed (there is no group to ask then)
 
@@ -461,8 +492,12 @@ int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, 
       if (int fr = flush_deferred(c)) return group_fail(g, fr, tj_last_error(c));   // (the update the previous batch still owes belongs to the state)
       hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(c->snap_n, 1)), dim3(256), 0, c->stream, c->snap_tab, c->snap_n, 0, c->d.ctl, c->ctl_snap);
     }
+  // direct exchange with ranks sharing a device: enqueued in lockstep by this thread (group_direct_lockstep), unless a rank replays a captured graph (TJ_USE_GRAPH=1)
+  const bool lockstep = g->n > 1 && !g->distinct && g->transport == TJ_TRANSPORT_FLAG && g->ctx[0]->d.xch &&
+                        std::none_of(g->ctx.begin(), g->ctx.end(), [](tj_ctx* c) { return c->use_graph; });
   auto run_batch = [&](bool careful, std::vector<long>* extra) {
-    if (g->n == 1) rc[0] = group_rank_loop(g, 0, n_iters, careful, extra ? &(*extra)[0] : nullptr);
+    if (lockstep && !careful) { if (group_direct_lockstep(g, n_iters, rc)) g->abort_flag.store(1); }
+    else if (g->n == 1) rc[0] = group_rank_loop(g, 0, n_iters, careful, extra ? &(*extra)[0] : nullptr);
     else {
       std::vector<std::thread> th;
       for (int r = 0; r < g->n; r++) th.emplace_back([g, r, n_iters, &rc, careful, extra]() { rc[r] = group_rank_loop(g, r, n_iters, careful, extra ? &(*extra)[r] : nullptr); if (rc[r]) g->abort_flag.store(1); });

@@ -39,7 +39,7 @@ def test_coupled_stages_teacher_forced_vs_reference(pkg, scenes):
 
 @pytest.mark.parametrize("name", ["hard_coupled", "scn_b_coupled"])
 def test_coupled_iterations_vs_oracle_live(pkg, scenes, name):
-    """every iteration of a longer run, each started from the oracle's state, through the hipGraph path"""
+    """every iteration of a longer run, each started from the oracle's state, through the iteration chain"""
     from oracle.pyoracle import Engine
     scene = scene_by_name(scenes, name)
     o = Engine("port", scene)

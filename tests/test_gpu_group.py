@@ -536,9 +536,7 @@ def test_coupled_search_in_one_launch_changes_no_bit(pkg, scenes, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"TJ_CCD_LEAN": "0"}, {"TJ_CCD_LEAN": "1"}, {"TJ_GRAD_FOLD": "0"}, {"TJ_GRAD_NPL": "8"}, {"TJ_SPLIT_UNIONS": "1"},
-                                 {"TJ_USE_GRAPH": "1"}, {"TJ_PAIR_ROWS": "4"}, {"TJ_N_SOLVE": "96"}, {"TJ_N_SOLVE": "96", "TJ_HS_MIN": "1"}, {"TJ_SEQ_FOLD": "0"}, {"TJ_LS_FAST": "0"}, {"TJ_GRAD_BALANCE": "1"}, {"TJ_LS_HELP": "1"}, {"TJ_LS_HELP": "2"}, {"TJ_LS_HELP": "3"}, {"TJ_LS_HELP_MUTE": "1"}, {"TJ_HS_BUDGET": "1", "TJ_HS_MIN": "2"}, {"TJ_HS_BUDGET": "40", "TJ_HS_MIN": "1"}, {"TJ_BVH_SKIP": "1"}, {"TJ_BVH_SKIP": "0"}, {"TJ_MID_ORDER": "1"}, {"TJ_XS_ASYNC": "0"}, {"TJ_XS_ONE_QUEUE": "1"},
-                                 {"TJ_XS_ASYNC": "0", "TJ_SPLIT_UNIONS": "1"}, {"TJ_XS_ASYNC": "0", "TJ_CCD_LEAN": "0"}],
+@pytest.mark.parametrize("env", [{"TJ_CCD_LEAN": "1"}, {"TJ_GRAD_FOLD": "0"}, {"TJ_GRAD_NPL": "8"}, {"TJ_PAIR_ROWS": "4"}, {"TJ_N_SOLVE": "96"}, {"TJ_N_SOLVE": "96", "TJ_HS_MIN": "1"}, {"TJ_SEQ_FOLD": "0"}, {"TJ_LS_FAST": "0"}, {"TJ_GRAD_BALANCE": "1"}, {"TJ_LS_HELP": "1"}, {"TJ_LS_HELP": "2"}, {"TJ_LS_HELP": "3"}, {"TJ_LS_HELP_MUTE": "1"}, {"TJ_HS_BUDGET": "1", "TJ_HS_MIN": "2"}, {"TJ_HS_BUDGET": "40", "TJ_HS_MIN": "1"}, {"TJ_BVH_SKIP": "1"}, {"TJ_BVH_SKIP": "0"}, {"TJ_MID_ORDER": "1"}, {"TJ_XS_ASYNC": "0"}, {"TJ_XS_ONE_QUEUE": "1"}],
                          ids=lambda e: "+".join(f"{k}={v}" for k, v in e.items()))
 def test_launch_shape_switches_change_no_bit(pkg, scenes, monkeypatch, env):
     """The launch-shape switches of tj_create select other builds / groupings of the same arithmetic: the state

@@ -519,7 +519,7 @@ def test_sharded_equals_unsharded(pkg, scenes):
 
 
 def test_full_size_scn_c_teacher_forced_vs_oracle(pkg, scenes):
-    """BASELINE config 4 size (64 UAVs, 100k points): whole iterations through the hipGraph path, each started from the
+    """BASELINE config 4 size (64 UAVs, 100k points): whole iterations through the iteration chain, each started from the
     CPU oracle's state.  (Free-running end-to-end parity is meaningless on this scene: the reference's own 1-ulp
     envelope is 1e-2)"""
     from oracle.pyoracle import Engine

@@ -283,8 +283,6 @@ struct Dev {
   // 1 KB of stamps + 2 KB of speculative planes per segment: 16.8 MB per launch at 256 robots).  A superset is enough: the stamp still decides.
   unsigned long long* pairbits;
   __device__ __forceinline__ void pair_mark(int tr, int a, int b) const { atomicOr(&pairbits[((size_t)tr * U + a) * ((U + 63) >> 6) + (b >> 6)], 1ull << (b & 63)); }
-  int* ccd_found;                  // [64] obstacle primitives the CCD stage found inside swept boxes, cumulative, spread over 64 counters (block & 63) so that no
-                                   // address is hot; the host sums them when it reads the control block and picks k_ccd's build from the rate
   int pair_rows;                   // rows per tile of the robot-pair broad phase (kernels_pairs.h)
   int mid_order;      // k_mid's grid: 0 slack | pair waves | obstacle solves; 1 (hundreds of robots) pair waves | obstacle solves | slack (kernels_step.h; TJ_MID_ORDER)
   const int* xs_gather;   // k_xsolve's overlap-add as a table (tj_create): [n*n][2] piece-block entries per entry of the reduced system, then [n][2] for the gradient; -1 none, -2 every piece (time entry)

@@ -5,9 +5,8 @@
 // (Optimization3D_multi.h:29-118) / Optimization3D_admm::optimization (Optimization3D_admm.h:29-67),
 // enqueued with plain launches and no host synchronisation inside or between iterations: a linear chain on the context's
 // stream, plus -- one context -- the Newton solve on a second stream next to the gradient kernel (Dev::xs_async, dev_common.h)
-// and, inside a batch, the NEXT iteration's k_front on that stream next to the line search (Dev::fa; TJ_USE_GRAPH=1 replays a
-// captured hipGraph of the one-queue chain instead).  A wait between the queues that runs out is healed, not reported (heal_check).  The stop test of the mains
-// runs on the device (begin_body), so a converged problem turns the remaining launches into early-exit kernels.
+// and, inside a batch, the NEXT iteration's k_front on that stream next to the line search (Dev::fa).  A wait between the queues
+// that runs out is healed, not reported (heal_check).  The stop test of the mains runs on the device (begin_body), so a converged problem turns the remaining launches into early-exit kernels.
 //
 // There is deliberately no CPU path in this file: every entry point either runs HIP kernels or
 // fails with TJ_ERR_DEVICE.
@@ -46,7 +45,7 @@ struct tj_ctx {
   Dev d;
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  bool maybe_deferred = false;                    // a graph iteration ran since the last flush
+  bool maybe_deferred = false;                    // an iteration chain ran since the last flush
   std::vector<void*> allocs;
   std::string err;
   bool have_cloud = false, have_state = false;
@@ -66,7 +65,6 @@ struct tj_ctx {
   bool heal = false, heal_busy = false, snap_in_begin = false; long long snap_iters = 0; int async_fallbacks = 0, xs_fault = 0;
   SnapRegion* snap_tab = nullptr; int snap_n = 0; Ctl* ctl_snap = nullptr;
   bool fa_mid_ok = false, fa_mid_now = false;   // Dev::fa_mid: k_front's whole grid is resident at once next to one k_linesearch block (tj_create) / the k_mid about to be enqueued waits for k_front itself
-  bool use_graph = false;    // TJ_USE_GRAPH=1: replay a captured hipGraph per iteration instead of plain launches
   bool hull_valid = false;   // Dev::fuse: the hull cache matches the control points (else k_hullinfo runs before the next iteration)
   bool ccd_valid = false;    // Dev::fuse: the swept-hull cache of the owned robots matches their direction records (k_xsolve's tail wrote it; tj_set_direction / tj_set_state clear it)
   long long launches = 0;    // kernels enqueued by the iteration schedules so far (tj_launch_count)
@@ -77,20 +75,11 @@ struct tj_ctx {
   XchPeers* xch_table = nullptr;
   bool xf_used[2] = {false, false};   // the cache units of k_front [0] / k_ccd [1] have counted themselves done since the last begin: a repeat of that launch before the next begin first zeroes the counters
   bool xch_wait_kernel = false;   // direct exchange, wait mode 0: a one-wave k_xch_wait launch in front of k_front / k_ccd
-  // graph of one full iteration
-  // hipGraphs: [0..2] the three phases of a sharded iteration, [3] one full iteration
-  hipGraph_t graph[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipGraphExec_t gexec[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool graph_ok[4] = {false, false, false, false};
-  bool graph_failed[4] = {false, false, false, false};
   size_t lds_grad = 0, lds_xs = 0, lds_xs2 = 0, lds_ls = 0, lds_seq = 0;
   bool lsc_wide = false;     // coupled mode: k_ls_coupled evaluates all LSC_ROUNDS rounds in one launch (kernels_ls.h)
   int lsc_base = 0;          // coupled mode, sharded context that follows the Armijo search (Dev::lsc_follow): first round of the table the next phases 4 / 5 evaluate and decide (0 at every iteration's start)
-  bool ccd_lean = true;        // which build of k_ccd the chain launches (kernels_step.h); re-decided whenever the control block is read
-  unsigned ccd_found_seen = 0; long long iters_enqueued = 0, iters_seen = 0;
   bool grad_fold = true;       // k_grad compacts its own segments (one launch less); TJ_GRAD_FOLD=0 keeps k_sep_self_compact + the 192-thread k_grad
   int n_solve_env = 0;         // TJ_N_SOLVE: pair-solve waves of k_mid (launch-shape switch)
-  bool split_unions = false;   // k_front / k_ccd as two launches each (hundreds of robots), see launch_kernel
   LsLayout lsl;
   // cloud-dependent allocations (rebuilt by tj_set_cloud)
   std::vector<void*> cloud_allocs;
@@ -148,14 +137,6 @@ int upload(tj_ctx* c, const void* dst, const void* src, size_t bytes) {
   return TJ_OK;
 }
 
-void drop_graph(tj_ctx* c) {
-  for (int i = 0; i < 4; i++) {
-    if (c->gexec[i]) { hipGraphExecDestroy(c->gexec[i]); c->gexec[i] = nullptr; }
-    if (c->graph[i]) { hipGraphDestroy(c->graph[i]); c->graph[i] = nullptr; }
-    c->graph_ok[i] = false; c->graph_failed[i] = false;
-  }
-}
-
 // every kernel the iteration schedules enqueue is counted (tj_launch_count: launches per iteration of a schedule, bench.py / tests)
 #define TJ_LAUNCH(...) do { c->launches++; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
@@ -164,23 +145,29 @@ const char* const kKernelNames[K_COUNT] = {"k_begin", "k_hullinfo", "k_front", "
                                            "k_grad", "k_xsolve", "k_xsolve_c2", "k_ccd_prep", "k_ccd", "k_ccd_obs", "k_ccd_self_pairs", "k_ccd_self_seq",
                                            "k_linesearch", "k_ls_coupled", "k_ls_commit", "k_slack"};
 
+// the schedule a launch belongs to:
+//   Stage: the stage API (tj_run_stage) and the host's one-off launches -- every stage as its own kernels.
+//   Chain: the single-context iteration, a linear chain on one queue in which independent stages share a launch (union kernels
+//          k_front / k_mid / k_ccd instead of their constituents), the slack/dual update is the deferred one inside k_mid, and --
+//          except in coupled mode -- the hull cache comes from k_linesearch (Dev::fuse); the asynchronous schedules (second and
+//          third queue) belong to it alone.
+//   Phase: the phases of a sharded iteration (enqueue_body): union kernels as well, on the context's queue only.
+enum class Sched { Stage, Chain, Phase };
+
 // launch exactly one kernel (returns false for kernels that do not exist in this mode / schedule).
-// in_graph: the launch belongs to the single-GPU iteration graph, a linear chain on one queue in which independent
-// stages share a launch (union kernels k_front / k_mid / k_ccd instead of their constituents), the slack/dual update
-// is the deferred one inside k_mid, and -- except in coupled mode -- the hull cache comes from k_linesearch (Dev::fuse).
-// chain_pos (single-GPU chain only): 0 = an iteration on its own (k_begin launched, k_linesearch plain); bit 1 = this iteration's
+// chain_pos (chains only): 0 = an iteration on its own (k_begin launched, k_linesearch plain); bit 1 = this iteration's
 // begin work was done by the previous iteration's k_linesearch (no k_begin launch); bit 2 = this iteration's k_linesearch also
 // does the next iteration's begin work.
-bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bool in_graph = false, bool in_phase = false, int chain_pos = 0) {
+bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos = 0) {
   Dev d_ = c->d;
-  if (!in_graph) d_.xs_async = 0;   // the asynchronous solve's tickets and flags belong to the single-GPU chain (begin -> k_grad -> k_xsolve -> k_ccd, every iteration); stage API and phases: plain
+  if (sched != Sched::Chain) d_.xs_async = 0;   // the asynchronous solve's tickets and flags belong to the single-GPU chain (begin -> k_grad -> k_xsolve -> k_ccd, every iteration); stage API and phases: plain
   d_.xs_seq = 0; d_.keep_seq = 0;
-  const bool keep2q = in_graph && c->keep_two_queues && !c->xs_same_queue_now && !c->use_graph;
+  const bool keep2q = sched == Sched::Chain && c->keep_two_queues && !c->xs_same_queue_now;
   if (!keep2q) d_.keep_async = 0;
-  if (kid == K_GRAD && d_.xs_async && c->xs_two_queues && !c->xs_same_queue_now && !c->use_graph) d_.xs_seq = ++c->xs_seq;   // this k_grad opens the gate of its k_xsolve
+  if (kid == K_GRAD && d_.xs_async && c->xs_two_queues && !c->xs_same_queue_now) d_.xs_seq = ++c->xs_seq;   // this k_grad opens the gate of its k_xsolve
   d_.fa_seq = 0; d_.fa_mid = 0; d_.fa_units = 0;
-  if (!in_graph) d_.fa = 0;   // (the context switch belongs to the single-GPU chain like xs_async; fa contexts are never sharded, and the stage API rebuilds the hull cache itself)
-  const bool fa2q = in_graph && d_.fa && c->xs_two_queues && !c->xs_same_queue_now && !c->use_graph;
+  if (sched != Sched::Chain) d_.fa = 0;   // (the context switch belongs to the single-GPU chain like xs_async; fa contexts are never sharded, and the stage API rebuilds the hull cache itself)
+  const bool fa2q = sched == Sched::Chain && d_.fa && c->xs_two_queues && !c->xs_same_queue_now;
   const Dev& d = d_;
   const int owned = d.u1 - d.u0;
   const bool multi = d.mode >= 1, coupled = d.mode == 2, tri = d.prim == 3;
@@ -196,7 +183,7 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
   const int n_rows = multi ? d.S * pair_units(d.U, d.pair_rows) : 0;   // one wave per (segment, tile of pair_rows lower robots x 64 partners)
   const int n_xf = d.xf_units();   // sharded contexts: one wave per (foreign robot, segment) at the head of k_front / k_ccd (kernels_step.h); coupled chain: per (robot, segment)
   const int n_ccd = owned * d.S + n_rows, n_front = n_ccd + n_xf + (d.spec ? SPEC_CAP : 0) + (d.grad_bal ? (owned * d.P + 63) / 64 : 0);
-  const bool chained = in_graph || in_phase;          // an iteration chain (one context, or the phases of a sharded schedule) as opposed to the stage API
+  const bool chained = sched != Sched::Stage;          // an iteration chain (one context, or the phases of a sharded schedule) as opposed to the stage API
   const int n_mid_slack = owned * d.P;
   d_.fa_nfront = n_front; d_.fa_nls = coupled ? owned * LSC_ROUNDS : owned * d.ls_help;
   switch (kid) {
@@ -205,14 +192,7 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
       else TJ_LAUNCH(k_begin, dim3(1), dim3(256), 0, s, d, nullptr, 0, nullptr);
       c->xf_used[0] = c->xf_used[1] = false; return true;
     case K_HULLINFO: if ((chained && (d.fuse || d.xf_all)) || !multi) return false; TJ_LAUNCH(k_hullinfo, dim3(d.U * d.S), dim3(64), 0, s, d); return true;  // unfused sharded phases (coupled mode): always (all robots, after the gather)
-    case K_FRONT: if (!in_graph && !in_phase) return false;
-      if (c->split_unions && multi) {
-        // hundreds of robots: the union is bound by how many one-wave blocks are resident (LDS of the BVH frontier: 14 per CU), and
-        // the pair rows need none of that LDS -- two launches, the second one at full occupancy, beat one boundary saved
-        if (owned * d.S > 0) { if (tri) TJ_LAUNCH((k_obs_query<3>), dim3(owned * d.S), dim3(64), 0, s, d); else TJ_LAUNCH((k_obs_query<1>), dim3(owned * d.S), dim3(64), 0, s, d); }
-        TJ_LAUNCH(k_sep_self_rows, dim3(n_rows), dim3(64), 0, s, d);
-        return true;
-      }
+    case K_FRONT: if (!chained) return false;
       if (d.xf) { if (c->xf_used[0]) (void)hipMemsetAsync(d.xf_seg, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[0] = true; }
       if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 0);   // ranks sharing a device: the wait for the peers' control points is a launch of its own
       if (keep2q) d_.keep_seq = ++c->keep_seq;   // this k_front opens the gate of the iteration's plane refinement (third queue)
@@ -223,7 +203,7 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
         if (tri) TJ_LAUNCH((k_front<3, true>), dim3(n_front), dim3(64), 0, c->stream2, d); else TJ_LAUNCH((k_front<1, true>), dim3(n_front), dim3(64), 0, c->stream2, d);
         return true;
       }
-      d_.fa_units = (in_graph && c->hull_from_units) ? 1 : 0;   // (the k_linesearch before it published no hull cache: one-queue emulation of the asynchronous front)
+      d_.fa_units = (sched == Sched::Chain && c->hull_from_units) ? 1 : 0;   // (the k_linesearch before it published no hull cache: one-queue emulation of the asynchronous front)
       if (tri) TJ_LAUNCH((k_front<3>), dim3(n_front), dim3(64), 0, s, d); else TJ_LAUNCH((k_front<1>), dim3(n_front), dim3(64), 0, s, d);
       if (keep2q) {
         d_.keep_seq = 0;
@@ -231,15 +211,15 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
         TJ_LAUNCH(k_keep, dim3(d.keep_waves), dim3(64), 0, c->stream3, d, 2);
       }
       return true;
-    case K_SEP_OBS: if (in_graph || in_phase) return false;  // stage API and sharded phase 0
+    case K_SEP_OBS: if (chained) return false;  // stage API only
       if (tri) TJ_LAUNCH((k_obs_query<3>), dim3(owned * d.S), dim3(64), 0, s, d); else TJ_LAUNCH((k_obs_query<1>), dim3(owned * d.S), dim3(64), 0, s, d);
       return true;
-    case K_OBS_SOLVE: if (in_graph || !n_obs_solve) return false;
+    case K_OBS_SOLVE: if (sched == Sched::Chain || !n_obs_solve) return false;
       if (tri) TJ_LAUNCH((k_obs_solve<3>), dim3(n_obs_solve), dim3(64), 0, s, d); else TJ_LAUNCH((k_obs_solve<1>), dim3(n_obs_solve), dim3(64), 0, s, d);
       return true;
-    case K_SEP_SELF_ROWS: if (in_graph || in_phase || !multi) return false; TJ_LAUNCH(k_sep_self_rows, dim3(n_rows), dim3(64), 0, s, d); return true;
-    case K_MID: if (!in_graph && !in_phase) return false;
-      if (in_graph && c->fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
+    case K_SEP_SELF_ROWS: if (chained || !multi) return false; TJ_LAUNCH(k_sep_self_rows, dim3(n_rows), dim3(64), 0, s, d); return true;
+    case K_MID: if (!chained) return false;
+      if (sched == Sched::Chain && c->fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
         c->fa_mid_now = false;
         d_.fa_seq = c->fa_seq; d_.fa_mid = 1;
         if (tri) TJ_LAUNCH((k_mid<3, true>), dim3(1 + n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve); else TJ_LAUNCH((k_mid<1, true>), dim3(1 + n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve);
@@ -247,21 +227,21 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
       }
       if (tri) TJ_LAUNCH((k_mid<3>), dim3(n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve); else TJ_LAUNCH((k_mid<1>), dim3(n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve);
       return true;
-    case K_SEP_SELF_SOLVE: if (in_graph || !n_solve) return false; TJ_LAUNCH(k_sep_self_solve, dim3(n_solve), dim3(64), 0, s, d); return true;
+    case K_SEP_SELF_SOLVE: if (sched == Sched::Chain || !n_solve) return false; TJ_LAUNCH(k_sep_self_solve, dim3(n_solve), dim3(64), 0, s, d); return true;
     case K_KEEP:  // "optimal_plane":1 only; single UAV: a wave per segment, multi UAV: lanes over the switched-on pair slots
       if (!d.optimal_plane || (multi ? false : d.N == 0)) return false;
       TJ_LAUNCH(k_keep, dim3(multi ? 1024 : owned * d.S), dim3(64), 0, s, d, keep2q ? 1 : 0); return true;   // (asynchronous refinement: the new pairs only)
-    case K_SEP_SELF_COMPACT: if ((in_graph || in_phase) && c->grad_fold) return false;   // iteration chains (single GPU and sharded phases): folded into k_grad
+    case K_SEP_SELF_COMPACT: if (chained && c->grad_fold) return false;   // iteration chains (single GPU and sharded phases): folded into k_grad
       TJ_LAUNCH(k_sep_self_compact, dim3(owned * d.S), dim3(64), 0, s, d); return true;
     case K_GRAD:
-      if ((in_graph || in_phase) && c->grad_fold) TJ_LAUNCH((k_grad<true>), dim3(owned * d.P), dim3(GRAD_FOLD_THREADS), c->lds_grad + grad_fold_extra_doubles(d.res) * sizeof(double), s, d);
+      if (chained && c->grad_fold) TJ_LAUNCH((k_grad<true>), dim3(owned * d.P), dim3(GRAD_FOLD_THREADS), c->lds_grad + grad_fold_extra_doubles(d.res) * sizeof(double), s, d);
       else TJ_LAUNCH((k_grad<false>), dim3(owned * d.P), dim3(GRAD_THREADS), c->lds_grad, s, d);
       return true;
     case K_XSOLVE: {
       Dev dx = d;
       if (!chained) dx.c2_fold = 0;   // (the stage API's solve is followed by k_xsolve_c2)
       const Dev& d = dx;
-      if (c->xs_seq_gated != c->xs_seq) {   // asynchronous solve: on the second queue, behind a gate that this iteration's k_grad opens (profiling, graphs: it simply follows k_grad on this queue)
+      if (c->xs_seq_gated != c->xs_seq) {   // asynchronous solve: on the second queue, behind a gate that this iteration's k_grad opens (profiling: it simply follows k_grad on this queue)
         c->xs_seq_gated = c->xs_seq;
         s = c->stream2;
         TJ_LAUNCH(k_xs_gate, dim3(1), dim3(64), 0, s, d, c->xs_seq, (c->xs_fault > 0 && c->xs_seq == c->xs_fault) ? 1 : 0);
@@ -287,31 +267,25 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
       if (chained && d.xf) { if (owned > 0) TJ_LAUNCH(k_ccd_prep, dim3(owned * d.S), dim3(64), 0, s, d, d.u0); }   // (the other ranks' robots: k_ccd's foreign units)
       else TJ_LAUNCH(k_ccd_prep, dim3(d.U * d.S), dim3(64), 0, s, d, 0);
       return true;
-    case K_CCD: if (!in_graph && !in_phase) return false;
-      if (c->split_unions && multi) {
-        if (owned * d.S > 0) { if (tri) TJ_LAUNCH((k_ccd_obs<3>), dim3(owned * d.S), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd_obs<1>), dim3(owned * d.S), dim3(64), 0, s, d); }
-        TJ_LAUNCH(k_ccd_self_pairs, dim3(n_rows), dim3(64), 0, s, d);
-        return true;
-      }
+    case K_CCD: if (!chained) return false;
       if (d.xf) { if (c->xf_used[1]) (void)hipMemsetAsync(d.xf_seg + (size_t)d.S * XF_SEG_STRIDE, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[1] = true; }
       if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 1);   // ranks sharing a device: the wait for the peers' direction records is a launch of its own
       {
         const int g = n_ccd + n_xf + (d.seq_fold ? 1 : 0);   // + the finisher of the folded pair replay (kernels_step.h)
-        if (c->ccd_lean) { if (tri) TJ_LAUNCH((k_ccd_lean<3>), dim3(g), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd_lean<1>), dim3(g), dim3(64), 0, s, d); }
-        else { if (tri) TJ_LAUNCH((k_ccd<3>), dim3(g), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd<1>), dim3(g), dim3(64), 0, s, d); }
+        if (tri) TJ_LAUNCH((k_ccd_lean<3>), dim3(g), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd_lean<1>), dim3(g), dim3(64), 0, s, d);
       }
       return true;
-    case K_CCD_OBS: if (in_graph) return false;
+    case K_CCD_OBS: if (sched == Sched::Chain) return false;
       if (tri) TJ_LAUNCH((k_ccd_obs<3>), dim3(owned * d.S), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd_obs<1>), dim3(owned * d.S), dim3(64), 0, s, d);
       return true;
-    case K_CCD_SELF_PAIRS: if (in_graph || !multi) return false; TJ_LAUNCH(k_ccd_self_pairs, dim3(n_rows), dim3(64), 0, s, d); return true;
+    case K_CCD_SELF_PAIRS: if (sched == Sched::Chain || !multi) return false; TJ_LAUNCH(k_ccd_self_pairs, dim3(n_rows), dim3(64), 0, s, d); return true;
     case K_CCD_SELF_SEQ:
-      if ((in_graph || in_phase) && d.seq_fold && !(c->split_unions && multi)) return false;   // the last block of k_ccd has done it
-      if (!multi && in_graph) return false;   // single UAV: no pairs to replay, and k_xsolve has left gnorm = |g| itself -- one launch less in the chain
+      if (chained && d.seq_fold) return false;   // the last block of k_ccd has done it
+      if (!multi && sched == Sched::Chain) return false;   // single UAV: no pairs to replay, and k_xsolve has left gnorm = |g| itself -- one launch less in the chain
       TJ_LAUNCH(k_ccd_self_seq, dim3(1), dim3(64), c->lds_seq, s, d); return true;
     case K_LINESEARCH: if (!coupled) { c->hull_from_units = false;
       if (fa2q && (chain_pos & 2)) { d_.fa_seq = ++c->fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->fa_armed = true; c->hull_from_units = true; }
-      else if (in_graph && d_.fa && c->fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
+      else if (sched == Sched::Chain && d_.fa && c->fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
       TJ_LAUNCH(k_linesearch, dim3(owned * d.ls_help), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, (chain_pos & 2) ? 1 : 0); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // (its last block runs begin_body)
       return !coupled;
     // coupled mode ("decouple":0): evaluation rounds of the summed-energy Armijo search, commit
@@ -325,25 +299,25 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, int slack_deferred = 0, bo
       }
       return coupled;
     case K_LS_COMMIT: if (coupled && !(c->lsc_wide && owned == d.U)) TJ_LAUNCH(k_ls_commit, dim3(owned), dim3(64), 0, s, d, (owned != d.U && d.lsc_follow) ? c->lsc_base : 0); return coupled;   // (one context, all rounds in one launch: its last block commits)
-    case K_SLACK: if (in_graph) return false; TJ_LAUNCH(k_slack, dim3(owned * d.P), dim3(64), 0, s, d, slack_deferred); return true;
+    case K_SLACK: if (sched == Sched::Chain) return false; TJ_LAUNCH(k_slack, dim3(owned * d.P), dim3(64), 0, s, d, 0); return true;
   }
   return false;
 }
 
 // enqueue one stage (= one or more kernels) on a stream
-int enqueue_stage(tj_ctx* c, int stage, hipStream_t s = nullptr, bool in_graph = false) {
+int enqueue_stage(tj_ctx* c, int stage, hipStream_t s = nullptr) {
   if (!s) s = c->stream;
   switch (stage) {
-    case TJ_STAGE_BEGIN: launch_kernel(c, K_BEGIN, s); break;
-    case TJ_STAGE_PLANES_OBS: launch_kernel(c, K_SEP_OBS, s); launch_kernel(c, K_OBS_SOLVE, s); if (c->d.mode == 0) launch_kernel(c, K_KEEP, s); launch_kernel(c, K_SEP_SELF_COMPACT, s); break;
-    case TJ_STAGE_PLANES_SELF: launch_kernel(c, K_HULLINFO, s); launch_kernel(c, K_SEP_SELF_ROWS, s); launch_kernel(c, K_SEP_SELF_SOLVE, s); launch_kernel(c, K_KEEP, s); launch_kernel(c, K_SEP_SELF_COMPACT, s); break;
-    case TJ_STAGE_GRAD: launch_kernel(c, K_GRAD, s); break;
-    case TJ_STAGE_XSOLVE: launch_kernel(c, K_XSOLVE, s); launch_kernel(c, K_XSOLVE_C2, s); break;
-    case TJ_STAGE_CCD_PREP: launch_kernel(c, K_CCD_PREP, s); break;
-    case TJ_STAGE_CCD_OBS: launch_kernel(c, K_CCD_OBS, s); break;
-    case TJ_STAGE_CCD_SELF: launch_kernel(c, K_CCD_SELF_PAIRS, s); launch_kernel(c, K_CCD_SELF_SEQ, s); break;
-    case TJ_STAGE_LINESEARCH: launch_kernel(c, K_LINESEARCH, s); launch_kernel(c, K_LS_COUPLED, s); launch_kernel(c, K_LS_COMMIT, s); break;
-    case TJ_STAGE_SLACK: launch_kernel(c, K_SLACK, s, 0); break;
+    case TJ_STAGE_BEGIN: launch_kernel(c, K_BEGIN, s, Sched::Stage); break;
+    case TJ_STAGE_PLANES_OBS: launch_kernel(c, K_SEP_OBS, s, Sched::Stage); launch_kernel(c, K_OBS_SOLVE, s, Sched::Stage); if (c->d.mode == 0) launch_kernel(c, K_KEEP, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_COMPACT, s, Sched::Stage); break;
+    case TJ_STAGE_PLANES_SELF: launch_kernel(c, K_HULLINFO, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_ROWS, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_SOLVE, s, Sched::Stage); launch_kernel(c, K_KEEP, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_COMPACT, s, Sched::Stage); break;
+    case TJ_STAGE_GRAD: launch_kernel(c, K_GRAD, s, Sched::Stage); break;
+    case TJ_STAGE_XSOLVE: launch_kernel(c, K_XSOLVE, s, Sched::Stage); launch_kernel(c, K_XSOLVE_C2, s, Sched::Stage); break;
+    case TJ_STAGE_CCD_PREP: launch_kernel(c, K_CCD_PREP, s, Sched::Stage); break;
+    case TJ_STAGE_CCD_OBS: launch_kernel(c, K_CCD_OBS, s, Sched::Stage); break;
+    case TJ_STAGE_CCD_SELF: launch_kernel(c, K_CCD_SELF_PAIRS, s, Sched::Stage); launch_kernel(c, K_CCD_SELF_SEQ, s, Sched::Stage); break;
+    case TJ_STAGE_LINESEARCH: launch_kernel(c, K_LINESEARCH, s, Sched::Stage); launch_kernel(c, K_LS_COUPLED, s, Sched::Stage); launch_kernel(c, K_LS_COMMIT, s, Sched::Stage); break;
+    case TJ_STAGE_SLACK: launch_kernel(c, K_SLACK, s, Sched::Stage); break;
     case TJ_STAGE_END: hipLaunchKernelGGL(k_end, dim3(1), dim3(1), 0, s, c->d); break;
     default: c->err = "unknown stage"; return TJ_ERR_INVALID;
   }
@@ -351,16 +325,17 @@ int enqueue_stage(tj_ctx* c, int stage, hipStream_t s = nullptr, bool in_graph =
   return TJ_OK;
 }
 
-// One iteration of the single-GPU schedule: a LINEAR chain on one stream / hardware queue (captured into the hipGraph)
+// One iteration of the single-GPU schedule (Sched::Chain): a LINEAR chain on one stream / hardware queue
 //   begin -> [hullinfo] -> front{obstacle planes | pair rows} -> mid{slack+dual of the PREVIOUS iteration | pair solves}
 //         -> compact -> grad -> xsolve [-> xsolve_c2] -> ccd_prep -> ccd{obstacle CCD | pair CCD selection} -> seq -> line search
 // Same-queue successors start back to back, so concurrency between independent stages comes from sharing a launch
 // (union kernels), not from parallel streams.  The plane builders only read control points, which the previous line
 // search already committed, so that iteration's slack/dual update (touches z, Lambda, t_z, tau only) is deferred into
 // k_mid; flush_deferred() pays the last one before anything on the host looks at the state.  The iteration counter is
-// committed by the next k_begin.
+// committed by the next k_begin.  Plain launches: the host enqueues far ahead of the device, and a hipGraph replay of the
+// same chain measured 4 us slower per iteration.
 int enqueue_iteration(tj_ctx* c, int chain_pos = 0) {
-  for (int k = 0; k < K_COUNT; k++) launch_kernel(c, k, c->stream, 0, true, false, chain_pos);
+  for (int k = 0; k < K_COUNT; k++) launch_kernel(c, k, c->stream, Sched::Chain, chain_pos);
   HIPCHK(c, hipGetLastError());
   c->maybe_deferred = true;
   return TJ_OK;
@@ -374,7 +349,7 @@ int flush_deferred(tj_ctx* c) {
   const Dev& d = c->d;
   TJ_LAUNCH(k_flush, dim3(1), dim3(1), 0, c->stream, d, c->begin_folded ? 1 : 0);   // (a begin folded into the last line search whose iteration was never enqueued is taken back)
   c->begin_folded = false;
-  launch_kernel(c, K_SLACK, c->stream, 1);
+  TJ_LAUNCH(k_slack, dim3((d.u1 - d.u0) * d.P), dim3(64), 0, c->stream, d, 1);   // (deferred: pays the update only where Ctl::slack_now says one is owed)
   HIPCHK(c, hipGetLastError());
   c->maybe_deferred = false;
   return TJ_OK;
@@ -398,14 +373,12 @@ int heal_check(tj_ctx* c, int err_known);
     if ((c)->snap_iters > 0 && !(c)->heal_busy) { int hr_ = heal_check(c, -1); if (hr_) return hr_; } \
   } while (0)
 
-// Work of graph slot `which`: 0,1,2 = the phases of a sharded iteration (split at the two all-gathers), 3 = one full
-// iteration.  The phases are linear chains on the context's stream as well and reuse the union kernels where the
+// Phase `which` of a sharded iteration (Sched::Phase), split at the all-gathers.  The phases are linear chains on the context's stream as well and reuse the union kernels where the
 // stages they join fall into the same phase (k_mid, k_ccd); the slack/dual update is the deferred one inside k_mid.
 //   phase 0: begin (stop test)                                                            -> all-gather control points
 //   phase 1: hull cache (ALL robots), k_front {obstacle query | pair rows}, k_mid, compaction, gradient, Newton solve -> all-gather directions
 //   phase 2: swept-hull cache (ALL robots), k_ccd, sequential pair clamp + gnorm, line search
-int enqueue_body(tj_ctx* c, int which, int chain_pos = 0, bool whole_iteration = false) {
-  if (whole_iteration) return enqueue_iteration(c, chain_pos);
+int enqueue_body(tj_ctx* c, int which, int chain_pos = 0) {
   hipStream_t m = c->stream;
   // decoupled / single: 3 phases.  coupled ("decouple":0): 6 phases -- the arrowhead system, the shared CCD step and the
   // Armijo test on the summed energy each need something from every robot (tj_iterate_phase, trajadmm.h)
@@ -423,7 +396,7 @@ int enqueue_body(tj_ctx* c, int which, int chain_pos = 0, bool whole_iteration =
     case 5: list = pc5; n = 1; break;
   }
   if (which == 1 && c->d.fuse) { int hr = ensure_hull_cache(c); if (hr) return hr; }   // fused phases: k_linesearch keeps the owned robots' hull cache; after a host write it is rebuilt once
-  for (int i = 0; i < n; i++) launch_kernel(c, list[i], m, 0, false, true, chain_pos);
+  for (int i = 0; i < n; i++) launch_kernel(c, list[i], m, Sched::Phase, chain_pos);
   HIPCHK(c, hipGetLastError());
   // this iteration's slack/dual update is owed to the next k_mid (or the flush) -- in a followed coupled search only once the search is over (tj_coupled_search_pending says so):
   // a flush between two tables of candidates would pay the update on the uncommitted control net
@@ -431,63 +404,15 @@ int enqueue_body(tj_ctx* c, int which, int chain_pos = 0, bool whole_iteration =
   return TJ_OK;
 }
 
-// Capture the body once into a hipGraph and replay it; fall back to eager launches if capture is
-// not possible on this stream.
-int launch_graph_or_eager(tj_ctx* c, int which, int chain_pos = 0) {
-  // Default: plain launches.  The iteration is a linear chain on one queue and the host enqueues far ahead of the device
-  // (10 launches ~ 35 us of host time per ~200 us iteration), so consecutive kernels already start back to back; a
-  // hipGraph replay of the same chain measured 4 us SLOWER per iteration (~8 us between consecutive graph launches),
-  // and ten iterations per graph 6 us slower still.  TJ_USE_GRAPH=1 selects the captured-graph replay.
-  if (!c->use_graph) {
-    int r = enqueue_body(c, which, chain_pos, which == 3);
-    if (r == TJ_OK && which >= 3) c->maybe_deferred = true;
-    return r;
-  }
-
-  if (!c->graph_ok[which] && !c->graph_failed[which]) {
-    hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-      int r = enqueue_body(c, which, 0, which == 3);
-      hipGraph_t g = nullptr;
-      e = hipStreamEndCapture(c->stream, &g);
-      if (r == TJ_OK && e == hipSuccess && g && hipGraphInstantiate(&c->gexec[which], g, nullptr, nullptr, 0) == hipSuccess) { c->graph[which] = g; c->graph_ok[which] = true; }
-      else { if (g) hipGraphDestroy(g); (void)hipGetLastError(); c->graph_failed[which] = true; }
-    } else { (void)hipGetLastError(); c->graph_failed[which] = true; }
-  }
-  if (c->graph_ok[which]) {
-    HIPCHK(c, hipGraphLaunch(c->gexec[which], c->stream));
-    if (which == 3) c->maybe_deferred = true;  // a replayed iteration leaves its slack/dual update owed
-    return TJ_OK;
-  }
-  return enqueue_body(c, which, 0, which == 3);
-}
-
-// obstacle-CCD candidates per iteration since the last look -> build of k_ccd for what comes next (kernels_step.h)
-void choose_builds(tj_ctx* c, const int* found64) {
-  unsigned tot = 0;
-  for (int i = 0; i < 64; i++) tot += (unsigned)found64[i];
-  const long long di = c->iters_enqueued - c->iters_seen;
-  // (rounds 2 - 4 picked the per-lane build of k_ccd where many candidates reach the GJK; since the lean build takes them cooperatively (round 5: no spills) it is the
-  //  faster one on every scene measured -- hard 8-robot fleet 43.4 -> 34.3 us, 64 robots through 1 M points 31.3 -> 29.5, SCN-A 17.4 -> 16.6 -- and stays selected;
-  //  TJ_CCD_LEAN=0 launches the per-lane build)
-  (void)di; (void)tot;
-  c->ccd_found_seen = tot; c->iters_seen = c->iters_enqueued;
-}
-
 int check_device_errors(tj_ctx* c, Ctl* out = nullptr) {
-  Ctl h; int found64[64];
+  Ctl h;
   const int fb0 = c->async_fallbacks;
   { int fr_ = flush_deferred(c); if (fr_) return fr_; }   // (in front of the copies: they are to see the state behind the last slack / dual update)
   HIPCHK(c, hipMemcpyAsync(&h, c->d.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(found64, c->d.ccd_found, sizeof(found64), hipMemcpyDeviceToHost, c->stream));
   QUIESCE_NOHEAL(c);
   if (c->snap_iters > 0 && !c->heal_busy) { int hr_ = heal_check(c, h.error); if (hr_) return hr_; }   // (the error word has come with the control block: no extra read-back)
-  if (c->async_fallbacks != fb0) {   // the batch was run again on one queue (heal_check): what was copied above belongs to the abandoned attempt
-    HIPCHK(c, hipMemcpy(&h, c->d.ctl, sizeof(Ctl), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(found64, c->d.ccd_found, sizeof(found64), hipMemcpyDeviceToHost));
-  }
+  if (c->async_fallbacks != fb0) HIPCHK(c, hipMemcpy(&h, c->d.ctl, sizeof(Ctl), hipMemcpyDeviceToHost));   // the batch was run again on one queue (heal_check): what was copied above belongs to the abandoned attempt
   if (out) *out = h;
-  choose_builds(c, found64);
   if (h.error & ERR_PEER_TIMEOUT) { c->err = "tj_group: a peer rank's slice did not arrive within 2 s (flag transport); the group must be re-initialised"; return TJ_ERR_DEVICE; }
   if (h.error & (ERR_PLANE_OVERFLOW | ERR_FRONT_OVERFLOW | ERR_PAIR_OVERFLOW)) {
     c->err = "device list overflow (error bits " + std::to_string(h.error) + "): raise cap_obs/cap_self/cap_pairs";
@@ -508,11 +433,11 @@ int check_device_errors(tj_ctx* c, Ctl* out = nullptr) {
   return TJ_OK;
 }
 
-// Dev::fuse: the iteration graph has no k_hullinfo (k_linesearch leaves the next iteration's hull cache); after the
+// Dev::fuse: the iteration chain has no k_hullinfo (k_linesearch leaves the next iteration's hull cache); after the
 // control points were set from the host the cache is rebuilt once here.
 int ensure_hull_cache(tj_ctx* c) {
   if (!c->d.fuse || c->hull_valid) return TJ_OK;
-  launch_kernel(c, K_HULLINFO, c->stream);
+  launch_kernel(c, K_HULLINFO, c->stream, Sched::Stage);
   HIPCHK(c, hipGetLastError());
   c->hull_valid = true; c->hull_from_units = false;
   return TJ_OK;
@@ -610,15 +535,13 @@ int tj_create(const tj_params* p, tj_ctx** out) {
   Dev& d = c->d;
   memset(&d, 0, sizeof(d));
   d.mode = p->mode; d.U = p->uav_num; d.P = p->piece_num; d.res = p->res; d.S = d.P * d.res; d.T = 3 * d.P + 3; d.N = 0; d.prim = 1;
-  c->use_graph = tune("USE_GRAPH") != nullptr;
   // the fused chain (k_linesearch leaves the hull cache, k_xsolve's tail the swept-hull cache) -- sharded contexts too since round 5: the other ranks' robots
   // are handled by foreign units inside k_front / k_ccd (Dev::xf).  Coupled mode keeps its own kernels (and, sharded, k_hullinfo / k_ccd_prep for all robots).
-  const bool split_env = tune("SPLIT_UNIONS") && atoi(tune("SPLIT_UNIONS")) != 0;
-  d.fuse = (p->mode != TJ_MODE_MULTI_COUPLED && !(p->world > 1 && split_env)) ? 1 : 0;
+  d.fuse = p->mode != TJ_MODE_MULTI_COUPLED ? 1 : 0;
   d.rank = p->rank; d.world = p->world;
   d.xf = (p->world > 1 && d.fuse && p->mode == TJ_MODE_MULTI_DECOUPLE) ? 1 : 0;
   // coupled mode, one context: every robot's cache records by units inside k_front / k_ccd (two launches less per iteration; TJ_COUPLED_UNITS=0: k_hullinfo / k_ccd_prep)
-  if (p->mode == TJ_MODE_MULTI_COUPLED && p->world == 1 && !split_env && !(tune("COUPLED_UNITS") && atoi(tune("COUPLED_UNITS")) == 0)) { d.xf = 1; d.xf_all = 1; }
+  if (p->mode == TJ_MODE_MULTI_COUPLED && p->world == 1 && !(tune("COUPLED_UNITS") && atoi(tune("COUPLED_UNITS")) == 0)) { d.xf = 1; d.xf_all = 1; }
   d.u0 = (int)((long long)p->rank * d.U / p->world); d.u1 = (int)((long long)(p->rank + 1) * d.U / p->world);
   d.lambda = p->lambda; d.margin = p->margin; d.offset = p->offset; d.mu = p->mu; d.vel_limit = p->vel_limit; d.acc_limit = p->acc_limit;
   d.ks = p->ks; d.kt = p->kt; d.stop = p->stop;
@@ -650,8 +573,6 @@ int tj_create(const tj_params* p, tj_ctx** out) {
   d.seq_tree = (d.mode == TJ_MODE_MULTI_DECOUPLE && seq_lds_bytes(d.U, d.S, true) <= lds_max) ? 1 : 0;
   if (tune("NO_SEQ_TREE")) d.seq_tree = 0;  // test hook: behave like a fleet too large for the LDS-resident tree
   c->lds_seq = seq_lds_bytes(d.U, d.S, d.seq_tree != 0);
-  c->split_unions = false;
-  if (const char* e = tune("CCD_LEAN")) c->ccd_lean = atoi(e) != 0;
   // hundreds of robots: the 512-thread folded k_grad is limited to ~2 workgroups per CU by wave slots; the 192-thread one (5 per CU)
   // plus a separate compaction launch is faster once there are more pieces than that (SCN-D: k_grad 109 -> 72 + 14 us)
   c->grad_fold = (d.u1 - d.u0) * d.P <= 512;
@@ -666,14 +587,13 @@ int tj_create(const tj_params* p, tj_ctx** out) {
   if (const char* e = tune("PAIR_LPW")) { const int r = atoi(e); if (r == 8 || r == 16 || r == 32 || r == 64) d.pair_lpw = r; }   // launch-shape switch (same bits)
   d.pair_pass_on = 1;
   if (const char* e = tune("PAIR_PASS_ON")) d.pair_pass_on = atoi(e) != 0;
-  if (const char* e = tune("SPLIT_UNIONS")) c->split_unions = atoi(e) != 0;
   // GJK head start for last iteration's slow robot pairs (kernels_pairs.h: spec_pair_body); TJ_PAIR_HEAD_START=0 switches it off (test hook: same bits)
-  d.spec = (d.mode >= 1 && !d.optimal_plane && !c->split_unions) ? 1 : 0;
+  d.spec = (d.mode >= 1 && !d.optimal_plane) ? 1 : 0;
   if (const char* e = tune("PAIR_HEAD_START")) d.spec = d.spec && atoi(e) != 0;
   // k_ccd's last block finishes with the sequential pair replay + gnorm (kernels_step.h): decoupled mode, when the replay's small
   // arrays fit k_ccd's static LDS buffer with room for at least 256 acting-pair keys (the value is that capacity)
   d.seq_fold = 0;
-  if ((d.mode == TJ_MODE_MULTI_DECOUPLE || (d.mode == TJ_MODE_MULTI_COUPLED && p->world == 1)) && !c->split_unions) {   // (coupled: one context only -- a sharded one exports its obstacle-CCD exponents from k_ccd_self_seq)
+  if (d.mode == TJ_MODE_MULTI_DECOUPLE || (d.mode == TJ_MODE_MULTI_COUPLED && p->world == 1)) {   // (coupled: one context only -- a sharded one exports its obstacle-CCD exponents from k_ccd_self_seq)
     const size_t buf = sizeof(double) * (size_t)(CCD_LDS_DOUBLES > PAIR_LDS_DOUBLES ? CCD_LDS_DOUBLES : PAIR_LDS_DOUBLES);
     int cap = 4096;
     while (cap >= 256 && seq_fold_lds_bytes(d.U, cap) > buf) cap >>= 1;
@@ -741,7 +661,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
     // claim their streams (main + second + third) out of a per-device budget of GPU_MAX_HW_QUEUES - 1 (the null stream has one); a context that does not fit keeps the one-queue
     // chain (same bits).  An explicit TJ_XS_ASYNC=1 / TJ_KEEP_ASYNC=1 overrides; self-healing stays the net under it.
     {
-      const bool want_keep = d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !c->split_unions && !(counters_on && !tune("KEEP_ASYNC")) && !(tune("KEEP_ASYNC") && atoi(tune("KEEP_ASYNC")) == 0);
+      const bool want_keep = d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !(counters_on && !tune("KEEP_ASYNC")) && !(tune("KEEP_ASYNC") && atoi(tune("KEEP_ASYNC")) == 0);
       const int need = 1 + (d.xs_async ? 1 : 0) + (want_keep ? 1 : 0);
       const bool forced = (tune("XS_ASYNC") && atoi(tune("XS_ASYNC")) != 0) || (tune("KEEP_ASYNC") && atoi(tune("KEEP_ASYNC")) != 0);
       if (need > 1) {
@@ -757,7 +677,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
       c->xs_two_queues = ok && tune("XS_ONE_QUEUE") == nullptr;
     }
     // asynchronous plane refinement ("optimal_plane":1, multi-UAV decoupled mode, one context; TJ_KEEP_ASYNC=0: k_keep stays one launch between k_mid and k_grad -- same bits)
-    d.keep_async = (d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !c->split_unions && !c->hwq_refused) ? 1 : 0;
+    d.keep_async = (d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !c->hwq_refused) ? 1 : 0;
     if (counters_on && !tune("KEEP_ASYNC")) d.keep_async = 0;
     if (const char* e = tune("KEEP_ASYNC")) d.keep_async = d.keep_async && atoi(e) != 0;
     d.keep_waves = 1024;
@@ -776,7 +696,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
     if (const char* e = tune("LS_HELP_MUTE")) d.ls_help_mute = atoi(e) != 0;                          // test hook (same bits): the helpers never post, the primaries time out
     // asynchronous front (dev_common.h, Dev::fa): one context, decoupled mode, the asynchronous solve's second queue, and a k_linesearch grid that is resident all at once
     // (one block per compute unit at most -- the residency gate's premise).  TJ_FRONT_ASYNC=0: k_linesearch publishes the hull cache and k_front follows it on the chain's queue (same bits)
-    d.fa = (d.xs_async && p->world == 1 && !d.optimal_plane && !c->split_unions && !c->use_graph &&
+    d.fa = (d.xs_async && p->world == 1 && !d.optimal_plane &&
             (p->mode != TJ_MODE_MULTI_COUPLED ? (d.fuse && owned * d.ls_help <= d.num_cu) : (c->lsc_wide && d.xf_all && owned * LSC_ROUNDS <= d.num_cu))) ? 1 : 0;   // (coupled: the one-launch search, whose last block commits every robot)
     if (const char* e = tune("FRONT_ASYNC")) d.fa = d.fa && atoi(e) != 0;
     c->fa_emulate = tune("FRONT_ASYNC_ONE_QUEUE") && atoi(tune("FRONT_ASYNC_ONE_QUEUE")) != 0;   // the asynchronous front's data flow (k_front's units form the records, k_linesearch publishes none) on the chain's queue: counter passes
@@ -861,7 +781,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
       (r = dalloc(c, &d.seg_stats, U * S * 6)) || (r = dalloc(c, &d.pair_stats, U * S * 2)) || (r = dalloc(c, &d.blk_stats, U * P + U)) ||
       (r = dalloc(c, &d.hullinfo, U * S * HULL_STRIDE)) || (r = dalloc(c, &d.hbox, S * 6 * U)) || (r = dalloc(c, &d.cbox, S * 6 * U)) || (r = dalloc(c, &d.pairplane, d.mode >= 1 ? S * U * U * 4 : 1)) ||
       (r = dalloc(c, &d.pairstamp, d.mode >= 1 ? S * U * U : 1)) || (r = dalloc(c, &d.pairbits, d.mode >= 1 ? S * U * ((U + 63) / 64) : 1)) ||
-      (r = dalloc(c, &d.pair_work, 3 * (size_t)d.cap_work)) || (r = dalloc(c, &d.pair_work_n, (size_t)d.S + 1)) || (r = dalloc(c, &d.pair_ovf, 4)) || (r = dalloc(c, &d.seq_gmem_d, seq_fold_gmem_doubles(d.U))) || (r = dalloc(c, &d.seq_gmem_i, seq_fold_gmem_ints(d.U))) || (r = dalloc(c, &d.spec_n, 2)) || (r = dalloc(c, &d.spec_list, 2 * SPEC_CAP)) || (r = dalloc(c, &d.spec_tag, SPEC_CAP)) || (r = dalloc(c, &d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES)) || (r = dalloc(c, &d.spec_sti, SPEC_CAP * SPEC_STATE_INTS)) || (r = dalloc(c, &d.pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX)) || (r = dalloc(c, &d.ccd_found, 64)) || (r = dalloc(c, &d.ctl, 1)) ||
+      (r = dalloc(c, &d.pair_work, 3 * (size_t)d.cap_work)) || (r = dalloc(c, &d.pair_work_n, (size_t)d.S + 1)) || (r = dalloc(c, &d.pair_ovf, 4)) || (r = dalloc(c, &d.seq_gmem_d, seq_fold_gmem_doubles(d.U))) || (r = dalloc(c, &d.seq_gmem_i, seq_fold_gmem_ints(d.U))) || (r = dalloc(c, &d.spec_n, 2)) || (r = dalloc(c, &d.spec_list, 2 * SPEC_CAP)) || (r = dalloc(c, &d.spec_tag, SPEC_CAP)) || (r = dalloc(c, &d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES)) || (r = dalloc(c, &d.spec_sti, SPEC_CAP * SPEC_STATE_INTS)) || (r = dalloc(c, &d.pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX)) || (r = dalloc(c, &d.ctl, 1)) ||
       (r = dalloc(c, &d.ocand, U * S * d.cap_obs)) || (r = dalloc(c, &d.ocand_n, U * S)) || (r = dalloc(c, &d.ohull, U * S * 18)) ||
       (r = dalloc(c, &d.obs_work, 2 * U * S * d.cap_obs)) || (r = dalloc(c, &d.obs_work_n, 1)) ||
       (r = dalloc(c, &d.oraw, U * S * d.cap_obs * 4)) || (r = dalloc(c, &d.ostamp, U * S * d.cap_obs)) ||
@@ -879,7 +799,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
     if (const char* e = tune("XS_FAULT")) c->xs_fault = atoi(e);   // test hook: the n-th gate of the asynchronous solve reports a time-out
     std::vector<std::pair<void*, size_t>> reg = {
       {d.spline, U * 3 * T * 8}, {d.p_slack, U * 18 * P * 8}, {d.p_lambda, U * 18 * P * 8}, {d.t_slack, U * P * 8}, {d.t_lambda, U * P * 8}, {d.piece_time, U * 8},
-      {d.xdir, U * d.xs * 8}, {d.ls_hist, U * 4}, {d.step_out, U * 8}, {d.seg_stats, U * S * 6 * 8}, {d.pair_stats, U * S * 2 * 8}, {d.blk_stats, (U * P + U) * 8}, {d.ccd_found, 64 * 4}};
+      {d.xdir, U * d.xs * 8}, {d.ls_hist, U * 4}, {d.step_out, U * 8}, {d.seg_stats, U * S * 6 * 8}, {d.pair_stats, U * S * 2 * 8}, {d.blk_stats, (U * P + U) * 8}};
     if (d.optimal_plane) {
       const bool m0 = d.mode == 0;
       if (m0) { reg.push_back({d.kobs_id, U * S * d.cap_obs * 4}); reg.push_back({d.kobs_n, U * S * 4}); reg.push_back({d.kobs_cd, U * S * d.cap_obs * 32}); }
@@ -902,7 +822,6 @@ int tj_create(const tj_params* p, tj_ctx** out) {
 
 void tj_destroy(tj_ctx* c) {
   if (!c) return;
-  drop_graph(c);
   if (c->hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->hwq_claim); c->hwq_claim = 0; }
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -946,7 +865,6 @@ int set_obstacles(tj_ctx* c, const double* verts, int n, int prim) {
   if (n > 0) { int cnt = (n + 7) / 8, off = 0; for (;;) { lvl_off.push_back(off); lvl_n.push_back(cnt); off += cnt; if (cnt <= 64) break; cnt = (cnt + 7) / 8; } }
   if ((int)lvl_n.size() > MAX_LEVELS) { c->err = "too many obstacle primitives for MAX_LEVELS"; return TJ_ERR_UNSUPPORTED; }
   QUIESCE(c);
-  drop_graph(c);
   c->have_cloud = false;
   d.N = 0; d.nlevels = 0; if (!tune("BVH_SKIP")) d.bvh_skip = 0; d.px = d.py = d.pz = d.tri = nullptr; d.boxes = d.leafbox = nullptr;
   for (void* p : c->cloud_allocs) hipFree(p);
@@ -1168,10 +1086,9 @@ int iterate_async_prologue(tj_ctx* c, int n_iters) {
 }
 
 // inside a batch the begin work of iteration i+1 rides on iteration i's k_linesearch (not in coupled mode, whose line search
-// is several kernels, and not in the captured-graph replay, which is one fixed iteration)
-// (coupled mode: only where the whole search is ONE launch whose last block commits -- lsc_wide, one context)
+// is several kernels -- except where the whole search is ONE launch whose last block commits: lsc_wide, one context)
 bool iterate_async_chain(const tj_ctx* c) {
-  return !c->use_graph && (c->d.mode != TJ_MODE_MULTI_COUPLED || (c->lsc_wide && c->d.u1 - c->d.u0 == c->d.U));
+  return c->d.mode != TJ_MODE_MULTI_COUPLED || (c->lsc_wide && c->d.u1 - c->d.u0 == c->d.U);
 }
 
 // chain position of iteration i of a batch of n (clears begin_folded: the fold it reports is consumed here)
@@ -1181,9 +1098,9 @@ int iterate_async_pos(tj_ctx* c, bool chain, int i, int n) {
   return pos;
 }
 
-// part of an eager iteration: kernels [k0, k1) of the stream order (enqueue_iteration is all of them)
+// part of an iteration: kernels [k0, k1) of the stream order (enqueue_iteration is all of them)
 int enqueue_iteration_part(tj_ctx* c, int chain_pos, int k0, int k1) {
-  for (int k = k0; k < k1; k++) launch_kernel(c, k, c->stream, 0, true, false, chain_pos);
+  for (int k = k0; k < k1; k++) launch_kernel(c, k, c->stream, Sched::Chain, chain_pos);
   HIPCHK(c, hipGetLastError());
   c->maybe_deferred = true;
   return TJ_OK;
@@ -1197,9 +1114,8 @@ int tj_iterate_async(tj_ctx* c, int n_iters) {
   const bool chain = iterate_async_chain(c);
   for (int i = 0; i < n_iters; i++) {
     const int pos = iterate_async_pos(c, chain, i, n_iters);
-    int r = launch_graph_or_eager(c, 3, pos); if (r) return r;
+    int r = enqueue_iteration(c, pos); if (r) return r;
   }
-  c->iters_enqueued += n_iters;
   return TJ_OK;
 }
 
@@ -1215,7 +1131,6 @@ void* tj_stream(tj_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int tj_set_stream(tj_ctx* c, void* hip_stream) {
   if (!c) return TJ_ERR_INVALID;
   QUIESCE(c);
-  drop_graph(c);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   c->stream = (hipStream_t)hip_stream;
   c->own_stream = false;
@@ -1236,7 +1151,7 @@ int tj_profile_kernels(tj_ctx* c, int n_iters, double* ms, int* launches) {
     HIPCHK(c, hipEventRecord(e[0], c->stream));
     const int pos = (c->d.mode != TJ_MODE_MULTI_COUPLED) ? ((it > 0 ? 1 : 0) | (it + 1 < n_iters ? 2 : 0)) : 0;
     for (int k = 0; k < K_COUNT; k++) {
-      if (launch_kernel(c, k, c->stream, 0, true, false, pos)) ran[k]++;
+      if (launch_kernel(c, k, c->stream, Sched::Chain, pos)) ran[k]++;
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipEventRecord(e[k + 1], c->stream));
     }
@@ -1299,7 +1214,7 @@ int tj_iterate_phase_chained(tj_ctx* c, int phase, int more) {
     if (phase == 0) { pos = c->begin_folded ? 1 : 0; c->begin_folded = false; }
     if (phase == 2 && more) { pos = 2; c->begin_folded = true; }
   }
-  if (phase == 0) { c->iters_enqueued += 1; c->lsc_base = 0; }
+  if (phase == 0) c->lsc_base = 0;
   return enqueue_body(c, phase, pos);
 }
 
@@ -1985,7 +1900,6 @@ int tj_xch_enable(tj_ctx* c, int on, int wait_mode) {
   Dev& d = c->d;
   if (on && (!d.xp || !c->xch_block)) { c->err = "tj_xch_enable: tj_xch_attach has not been called"; return TJ_ERR_INVALID; }
   QUIESCE(c);
-  drop_graph(c);
   d.xch = on ? 1 : 0; d.xch_poll = (on && wait_mode == 1) ? 1 : 0; c->xch_wait_kernel = on && wait_mode == 0;
   return TJ_OK;
 }

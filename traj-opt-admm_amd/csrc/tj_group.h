@@ -282,7 +282,6 @@ int group_direct_lockstep(tj_group* g, int n_iters, std::vector<int>& rc) {
         if ((rc[r] = enqueue_iteration_part(c, pos[r], cut[part], cut[part + 1]))) return rc[r];
       }
   }
-  for (int r = 0; r < g->n; r++) g->ctx[r]->iters_enqueued += n_iters;
   return TJ_OK;
 }
 
@@ -492,9 +491,8 @@ int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, 
       if (int fr = flush_deferred(c)) return group_fail(g, fr, tj_last_error(c));   // (the update the previous batch still owes belongs to the state)
       hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(c->snap_n, 1)), dim3(256), 0, c->stream, c->snap_tab, c->snap_n, 0, c->d.ctl, c->ctl_snap);
     }
-  // direct exchange with ranks sharing a device: enqueued in lockstep by this thread (group_direct_lockstep), unless a rank replays a captured graph (TJ_USE_GRAPH=1)
-  const bool lockstep = g->n > 1 && !g->distinct && g->transport == TJ_TRANSPORT_FLAG && g->ctx[0]->d.xch &&
-                        std::none_of(g->ctx.begin(), g->ctx.end(), [](tj_ctx* c) { return c->use_graph; });
+  // direct exchange with ranks sharing a device: enqueued in lockstep by this thread (group_direct_lockstep)
+  const bool lockstep = g->n > 1 && !g->distinct && g->transport == TJ_TRANSPORT_FLAG && g->ctx[0]->d.xch;
   auto run_batch = [&](bool careful, std::vector<long>* extra) {
     if (lockstep && !careful) { if (group_direct_lockstep(g, n_iters, rc)) g->abort_flag.store(1); }
     else if (g->n == 1) rc[0] = group_rank_loop(g, 0, n_iters, careful, extra ? &(*extra)[0] : nullptr);

@@ -401,6 +401,33 @@ def test_cross_queue_timeout_heals_itself(pkg, scenes, monkeypatch, scene_name, 
     s.close()
 
 
+
+@pytest.mark.gpu
+def test_cross_queue_timeout_heals_a_batch_that_starts_folded(pkg, scenes, monkeypatch):
+    """A batch whose first iteration was already begun by the line search of the phase before it (iterate_phase(2, more=1)) heals like any other: the checkpoint is
+    taken in a launch of its own together with the host's begin_folded flag, and restoring it takes that fold back as a flush does, so the run enqueued again counts
+    the begun iteration once.  The phases open no gate of the asynchronous solve, so TJ_XS_FAULT=3 falls on the third iteration of the batch."""
+    for k in ("TJ_XS_ASYNC", "TJ_XS_ONE_QUEUE", "TJ_FRONT_ASYNC", "TJ_HEAL", "TJ_XS_FAULT", "TJ_KEEP_ASYNC"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("TJ_XS_ASYNC", "1")   # (explicit: see test_asynchronous_newton_solve_changes_no_bit)
+    scene = scenes.scn_b()
+    def run():
+        s = pkg.Solver(scene, stop=0.0)
+        s.iterate_phase(0); s.iterate_phase(1); s.iterate_phase(2, more=1)
+        s.iterate_async(8); s.sync()
+        st, ts = s.get_state(), s.stats()
+        s.close()
+        return st, ts
+    sa, ta = run()
+    monkeypatch.setenv("TJ_XS_FAULT", "3")
+    sb, tb = run()
+    assert ta["async_fallbacks"] == 0 and tb["async_fallbacks"] == 1, (ta["async_fallbacks"], tb["async_fallbacks"])
+    assert ta["error_bits"] == 0 and tb["error_bits"] == 0, (ta["error_bits"], tb["error_bits"])
+    assert ta["iters"] == tb["iters"], (ta["iters"], tb["iters"])
+    for n in sa:
+        assert np.array_equal(sa[n], sb[n]), f"{n}: the healed run differs from the undisturbed one"
+
+
 _SHARE_CODE = r"""
 import sys, os, importlib, time
 import numpy as np

@@ -192,12 +192,14 @@ struct Dev {
   __host__ __device__ int* xs_ticket(int u) const { return xs_sync + (size_t)u * 32; }
   __host__ __device__ int* xs_flag(int u) const { return xs_sync + ((size_t)U + u) * 32; }
   __host__ __device__ int* xs_done() const { return xs_sync + (size_t)2 * U * 32; }
+  __host__ __device__ static size_t xs_sync_ints(int U_) { return ((size_t)2 * U_ + 2) * 32; }
   // "optimal_plane":1, multi-UAV, one context: the refinement of the planes stored before this iteration (k_keep part 2) needs nothing of this iteration's broad
   // phase -- only the committed control points -- and is as long as its slowest plane (tens of Newton rounds).  It runs on a THIRD queue from the start of the
   // iteration (gate: k_front's first block has started), next to k_front and k_mid; k_grad (its compaction reads the planes) waits for the waves' sixteen completion
   // counters.  keep_sync: ints [16][32] counters (zeroed by begin_body) | [32] go word.
   int keep_async, keep_seq, keep_waves; int* keep_sync;
   __host__ __device__ int* keep_go() const { return keep_sync + 16 * 32; }
+  __host__ __device__ static size_t keep_sync_ints() { return 17 * 32; }
   // ASYNCHRONOUS FRONT (round 6; one context, all three modes, every block of the line-search kernel resident at once): inside a batch the NEXT iteration's k_front
   // runs on the second hardware queue next to this iteration's k_linesearch (coupled mode: the one-launch k_ls_coupled).  Its launch is held back by a one-wave gate
   // (k_fa_gate) until every block of the line search has started (residency counters: all of them are resident then, so a k_front block that sleeps on a flag can never

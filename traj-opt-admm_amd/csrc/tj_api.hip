@@ -15,7 +15,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <strings.h>
-#include <cstring>
 #include <string>
 #include <vector>
 #include "../../include/trajadmm.h"
@@ -40,6 +39,19 @@ using namespace tj;
 static std::atomic<int> g_async_queues[64];
 static int hw_queue_budget() { const char* e = getenv("GPU_MAX_HW_QUEUES"); const int n = e ? atoi(e) : 4; return std::max(n, 2) - 1; }
 
+// The cross-queue schedule of one context: the asynchronous Newton solve (Dev::xs_async) and front (Dev::fa) on stream2, the asynchronous plane refinement (Dev::keep_async) on
+// stream3.  Each pairing has a host counter that must match a monotonic word on the device: xs_seq <-> Dev::xs_go (k_grad opens the gate of its k_xsolve; xs_seq_gated: the last
+// pairing a gate was launched for), keep_seq <-> Dev::keep_go (k_front opens the refinement's gate), fa_seq <-> Dev::fa_sync (k_linesearch(i) <-> k_front(i + 1)).  restart_pairings resets both.
+struct CrossQueue {
+  hipStream_t stream2 = nullptr, stream3 = nullptr; int xs_seq = 0, xs_seq_gated = 0, keep_seq = 0, fa_seq = 0;
+  bool xs_two_queues = false, keep_two_queues = false, xs_same_queue_now = false;   // stream2 / stream3 in use (heal_check latches both off for good) / tj_profile_kernels: one queue
+  bool fa_armed = false, fa_mid_now = false, hull_from_units = false;   // the last k_linesearch enqueued belongs to pairing fa_seq (the next k_front goes to stream2 behind k_fa_gate) / the k_mid about to be enqueued waits for k_front itself (Dev::fa_mid) / the last k_linesearch published no hull cache (the next k_front forms the records)
+  int hwq_claim = 0, xs_fault = 0;   // hardware queues claimed out of the process's budget for contexts that sleep across queues (tj_create) / test hook TJ_XS_FAULT: the n-th gate reports a time-out
+};
+// The checkpoint a batch can be restored from (heal_check; the careful re-run of a coupled sharded group, tj_group_iterate), touched by checkpoint_take / _restore / _drop
+// only.  Device half: the regions of `tab` and the control block, copied to an arena of tj_create (in_begin: taken by the next k_begin).  Host half: the flags that describe it.
+struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bool in_begin = false; bool begin_folded = false, maybe_deferred = false; int lsc_base = 0; };
+
 struct tj_ctx {
   tj_params prm;
   Dev d;
@@ -49,22 +61,10 @@ struct tj_ctx {
   std::vector<void*> allocs;
   std::string err;
   bool have_cloud = false, have_state = false;
-  // asynchronous Newton solve (Dev::xs_async): k_xsolve goes to a second hardware queue, behind a one-wave gate kernel that the iteration's k_grad opens (xs_seq: the
-  // sequence number of that pairing; xs_seq_gated: the last one a gate was launched for; xs_same_queue_now: tj_profile_kernels keeps everything on one queue)
-  hipStream_t stream3 = nullptr; int keep_seq = 0; bool keep_two_queues = false;   // asynchronous plane refinement (Dev::keep_async)
-  hipStream_t stream2 = nullptr; int xs_seq = 0, xs_seq_gated = 0; bool xs_two_queues = false, xs_same_queue_now = false;
-  // asynchronous front (Dev::fa): fa_seq = pairings k_linesearch(i) <-> k_front(i + 1) launched so far (the device's words are monotonic in it); fa_armed: the last
-  // k_linesearch enqueued belongs to pairing fa_seq and the k_front that follows goes to the second queue behind k_fa_gate
-  int fa_seq = 0; bool fa_armed = false;
-  int hwq_claim = 0; bool hwq_refused = false;   // hardware queues this context claimed out of the process's budget for contexts that sleep across queues (tj_create)
-  bool hull_from_units = false, fa_emulate = false;   // the last k_linesearch enqueued published no hull cache (the next k_front forms the records in its units) / TJ_FRONT_ASYNC_ONE_QUEUE=1: the schedule's data flow on one queue
-  // Self-healing of the cross-queue schedules: a wait between the queues that runs out (ERR_XS_TIMEOUT -- in practice a GPU shared with another process, whose time slices
-  // keep one of the queues off the hardware) must not fail a run.  The first tj_iterate_async after a point at which the host has looked at the device takes a snapshot of the
-  // state (one launch); when the host next looks and finds the bit, it latches every two-queue schedule off, restores the snapshot, enqueues the same iterations again on
-  // the one queue and counts the incident (tj_stats.async_fallbacks).  TJ_HEAL=0: off (the bit is reported as TJ_ERR_NO_PROGRESS, as in round 5).
-  bool heal = false, heal_busy = false, snap_in_begin = false; long long snap_iters = 0; int async_fallbacks = 0, xs_fault = 0;
-  SnapRegion* snap_tab = nullptr; int snap_n = 0; Ctl* ctl_snap = nullptr;
-  bool fa_mid_ok = false, fa_mid_now = false;   // Dev::fa_mid: k_front's whole grid is resident at once next to one k_linesearch block (tj_create) / the k_mid about to be enqueued waits for k_front itself
+  CrossQueue xq; bool hwq_refused = false, fa_emulate = false, fa_mid_ok = false;   // (tj_create) no room in the queue budget / TJ_FRONT_ASYNC_ONE_QUEUE=1 / Dev::fa_mid: k_front's grid is resident next to one k_linesearch block
+  // Self-healing (heal_check): a wait between the queues that runs out (ERR_XS_TIMEOUT -- in practice a GPU shared with another process) must not fail a run.  snap_iters:
+  // iterations enqueued since the first tj_iterate_async after a host look took the checkpoint.  TJ_HEAL=0: off (the bit is reported as TJ_ERR_NO_PROGRESS, as in round 5).
+  bool heal = false, heal_busy = false; long long snap_iters = 0; int async_fallbacks = 0; Checkpoint ck;
   bool hull_valid = false;   // Dev::fuse: the hull cache matches the control points (else k_hullinfo runs before the next iteration)
   bool ccd_valid = false;    // Dev::fuse: the swept-hull cache of the owned robots matches their direction records (k_xsolve's tail wrote it; tj_set_direction / tj_set_state clear it)
   long long launches = 0;    // kernels enqueued by the iteration schedules so far (tj_launch_count)
@@ -162,12 +162,12 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
   Dev d_ = c->d;
   if (sched != Sched::Chain) d_.xs_async = 0;   // the asynchronous solve's tickets and flags belong to the single-GPU chain (begin -> k_grad -> k_xsolve -> k_ccd, every iteration); stage API and phases: plain
   d_.xs_seq = 0; d_.keep_seq = 0;
-  const bool keep2q = sched == Sched::Chain && c->keep_two_queues && !c->xs_same_queue_now;
+  const bool keep2q = sched == Sched::Chain && c->xq.keep_two_queues && !c->xq.xs_same_queue_now;
   if (!keep2q) d_.keep_async = 0;
-  if (kid == K_GRAD && d_.xs_async && c->xs_two_queues && !c->xs_same_queue_now) d_.xs_seq = ++c->xs_seq;   // this k_grad opens the gate of its k_xsolve
+  if (kid == K_GRAD && d_.xs_async && c->xq.xs_two_queues && !c->xq.xs_same_queue_now) d_.xs_seq = ++c->xq.xs_seq;   // this k_grad opens the gate of its k_xsolve
   d_.fa_seq = 0; d_.fa_mid = 0; d_.fa_units = 0;
   if (sched != Sched::Chain) d_.fa = 0;   // (the context switch belongs to the single-GPU chain like xs_async; fa contexts are never sharded, and the stage API rebuilds the hull cache itself)
-  const bool fa2q = sched == Sched::Chain && d_.fa && c->xs_two_queues && !c->xs_same_queue_now;
+  const bool fa2q = sched == Sched::Chain && d_.fa && c->xq.xs_two_queues && !c->xq.xs_same_queue_now;
   const Dev& d = d_;
   const int owned = d.u1 - d.u0;
   const bool multi = d.mode >= 1, coupled = d.mode == 2, tri = d.prim == 3;
@@ -188,27 +188,27 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
   d_.fa_nfront = n_front; d_.fa_nls = coupled ? owned * LSC_ROUNDS : owned * d.ls_help;
   switch (kid) {
     case K_BEGIN: if (chain_pos & 1) return false;
-      if (c->snap_in_begin) { c->snap_in_begin = false; TJ_LAUNCH(k_begin, dim3(1 + 128), dim3(256), 0, s, d, c->snap_tab, c->snap_n, c->ctl_snap); }   // (self-healing: the batch's snapshot rides in this launch)
+      if (c->ck.in_begin) { c->ck.in_begin = false; TJ_LAUNCH(k_begin, dim3(1 + 128), dim3(256), 0, s, d, c->ck.tab, c->ck.n, c->ck.ctl); }   // (checkpoint_take: the device half rides in this launch)
       else TJ_LAUNCH(k_begin, dim3(1), dim3(256), 0, s, d, nullptr, 0, nullptr);
       c->xf_used[0] = c->xf_used[1] = false; return true;
     case K_HULLINFO: if ((chained && (d.fuse || d.xf_all)) || !multi) return false; TJ_LAUNCH(k_hullinfo, dim3(d.U * d.S), dim3(64), 0, s, d); return true;  // unfused sharded phases (coupled mode): always (all robots, after the gather)
     case K_FRONT: if (!chained) return false;
       if (d.xf) { if (c->xf_used[0]) (void)hipMemsetAsync(d.xf_seg, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[0] = true; }
       if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 0);   // ranks sharing a device: the wait for the peers' control points is a launch of its own
-      if (keep2q) d_.keep_seq = ++c->keep_seq;   // this k_front opens the gate of the iteration's plane refinement (third queue)
-      if (c->fa_armed && fa2q && (chain_pos & 1)) {   // asynchronous front: on the second queue, next to the k_linesearch just enqueued (pairing fa_seq), behind the residency gate
-        c->fa_armed = false;
-        d_.fa_seq = c->fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->fa_mid_now = c->fa_mid_ok;
-        TJ_LAUNCH(k_fa_gate, dim3(1), dim3(64), 0, c->stream2, d, (int)((unsigned)c->fa_seq * (unsigned)d.fa_nls));
-        if (tri) TJ_LAUNCH((k_front<3, true>), dim3(n_front), dim3(64), 0, c->stream2, d); else TJ_LAUNCH((k_front<1, true>), dim3(n_front), dim3(64), 0, c->stream2, d);
+      if (keep2q) d_.keep_seq = ++c->xq.keep_seq;   // this k_front opens the gate of the iteration's plane refinement (third queue)
+      if (c->xq.fa_armed && fa2q && (chain_pos & 1)) {   // asynchronous front: on the second queue, next to the k_linesearch just enqueued (pairing fa_seq), behind the residency gate
+        c->xq.fa_armed = false;
+        d_.fa_seq = c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->xq.fa_mid_now = c->fa_mid_ok;
+        TJ_LAUNCH(k_fa_gate, dim3(1), dim3(64), 0, c->xq.stream2, d, (int)((unsigned)c->xq.fa_seq * (unsigned)d.fa_nls));
+        if (tri) TJ_LAUNCH((k_front<3, true>), dim3(n_front), dim3(64), 0, c->xq.stream2, d); else TJ_LAUNCH((k_front<1, true>), dim3(n_front), dim3(64), 0, c->xq.stream2, d);
         return true;
       }
-      d_.fa_units = (sched == Sched::Chain && c->hull_from_units) ? 1 : 0;   // (the k_linesearch before it published no hull cache: one-queue emulation of the asynchronous front)
+      d_.fa_units = (sched == Sched::Chain && c->xq.hull_from_units) ? 1 : 0;   // (the k_linesearch before it published no hull cache: one-queue emulation of the asynchronous front)
       if (tri) TJ_LAUNCH((k_front<3>), dim3(n_front), dim3(64), 0, s, d); else TJ_LAUNCH((k_front<1>), dim3(n_front), dim3(64), 0, s, d);
       if (keep2q) {
         d_.keep_seq = 0;
-        TJ_LAUNCH(k_keep_gate, dim3(1), dim3(64), 0, c->stream3, d, c->keep_seq);
-        TJ_LAUNCH(k_keep, dim3(d.keep_waves), dim3(64), 0, c->stream3, d, 2);
+        TJ_LAUNCH(k_keep_gate, dim3(1), dim3(64), 0, c->xq.stream3, d, c->xq.keep_seq);
+        TJ_LAUNCH(k_keep, dim3(d.keep_waves), dim3(64), 0, c->xq.stream3, d, 2);
       }
       return true;
     case K_SEP_OBS: if (chained) return false;  // stage API only
@@ -219,9 +219,9 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       return true;
     case K_SEP_SELF_ROWS: if (chained || !multi) return false; TJ_LAUNCH(k_sep_self_rows, dim3(n_rows), dim3(64), 0, s, d); return true;
     case K_MID: if (!chained) return false;
-      if (sched == Sched::Chain && c->fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
-        c->fa_mid_now = false;
-        d_.fa_seq = c->fa_seq; d_.fa_mid = 1;
+      if (sched == Sched::Chain && c->xq.fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
+        c->xq.fa_mid_now = false;
+        d_.fa_seq = c->xq.fa_seq; d_.fa_mid = 1;
         if (tri) TJ_LAUNCH((k_mid<3, true>), dim3(1 + n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve); else TJ_LAUNCH((k_mid<1, true>), dim3(1 + n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve);
         return true;
       }
@@ -241,10 +241,10 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       Dev dx = d;
       if (!chained) dx.c2_fold = 0;   // (the stage API's solve is followed by k_xsolve_c2)
       const Dev& d = dx;
-      if (c->xs_seq_gated != c->xs_seq) {   // asynchronous solve: on the second queue, behind a gate that this iteration's k_grad opens (profiling: it simply follows k_grad on this queue)
-        c->xs_seq_gated = c->xs_seq;
-        s = c->stream2;
-        TJ_LAUNCH(k_xs_gate, dim3(1), dim3(64), 0, s, d, c->xs_seq, (c->xs_fault > 0 && c->xs_seq == c->xs_fault) ? 1 : 0);
+      if (c->xq.xs_seq_gated != c->xq.xs_seq) {   // asynchronous solve: on the second queue, behind a gate that this iteration's k_grad opens (profiling: it simply follows k_grad on this queue)
+        c->xq.xs_seq_gated = c->xq.xs_seq;
+        s = c->xq.stream2;
+        TJ_LAUNCH(k_xs_gate, dim3(1), dim3(64), 0, s, d, c->xq.xs_seq, (c->xq.xs_fault > 0 && c->xq.xs_seq == c->xq.xs_fault) ? 1 : 0);
       }
       if (d.xs_band) TJ_LAUNCH(k_xsolve_band, dim3(owned), dim3(XB_THREADS), c->lds_xs, s, d);
       else switch (9 * d.P - 2) {   // the register factorisation is inlined per size (kernels_newton.h); 61 rows and the LDS forms: the generic kernel
@@ -283,17 +283,17 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       if (chained && d.seq_fold) return false;   // the last block of k_ccd has done it
       if (!multi && sched == Sched::Chain) return false;   // single UAV: no pairs to replay, and k_xsolve has left gnorm = |g| itself -- one launch less in the chain
       TJ_LAUNCH(k_ccd_self_seq, dim3(1), dim3(64), c->lds_seq, s, d); return true;
-    case K_LINESEARCH: if (!coupled) { c->hull_from_units = false;
-      if (fa2q && (chain_pos & 2)) { d_.fa_seq = ++c->fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->fa_armed = true; c->hull_from_units = true; }
-      else if (sched == Sched::Chain && d_.fa && c->fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
+    case K_LINESEARCH: if (!coupled) { c->xq.hull_from_units = false;
+      if (fa2q && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; c->xq.hull_from_units = true; }
+      else if (sched == Sched::Chain && d_.fa && c->fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->xq.hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
       TJ_LAUNCH(k_linesearch, dim3(owned * d.ls_help), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, (chain_pos & 2) ? 1 : 0); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // (its last block runs begin_body)
       return !coupled;
     // coupled mode ("decouple":0): evaluation rounds of the summed-energy Armijo search, commit
     case K_LS_COUPLED:
       if (coupled) {
         const int base = (owned != d.U && d.lsc_follow) ? c->lsc_base : 0;   // (a followed search of a sharded context: the rounds beyond the first table)
-        c->hull_from_units = false;
-        if (fa2q && c->lsc_wide && owned == d.U && (chain_pos & 2)) { d_.fa_seq = ++c->fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->fa_armed = true; }   // asynchronous front: the next k_front runs next to this launch
+        c->xq.hull_from_units = false;
+        if (fa2q && c->lsc_wide && owned == d.U && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; }   // asynchronous front: the next k_front runs next to this launch
         if (c->lsc_wide) { TJ_LAUNCH(k_ls_coupled, dim3(owned * LSC_ROUNDS), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, 0, LSC_ROUNDS, (chain_pos & 2) ? 1 : 0, base); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // all rounds at once, one block per (robot, round)
         else for (int r = 0; r < LSC_ROUNDS; r++) TJ_LAUNCH(k_ls_coupled, dim3(owned), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, r, 1, 0, base);
       }
@@ -334,8 +334,9 @@ int enqueue_stage(tj_ctx* c, int stage, hipStream_t s = nullptr) {
 // k_mid; flush_deferred() pays the last one before anything on the host looks at the state.  The iteration counter is
 // committed by the next k_begin.  Plain launches: the host enqueues far ahead of the device, and a hipGraph replay of the
 // same chain measured 4 us slower per iteration.
-int enqueue_iteration(tj_ctx* c, int chain_pos = 0) {
-  for (int k = 0; k < K_COUNT; k++) launch_kernel(c, k, c->stream, Sched::Chain, chain_pos);
+// (k0, k1: only kernels [k0, k1) of the stream order -- the lockstep enqueue of ranks that share a device, tj_group.h)
+int enqueue_iteration(tj_ctx* c, int chain_pos = 0, int k0 = 0, int k1 = K_COUNT) {
+  for (int k = k0; k < k1; k++) launch_kernel(c, k, c->stream, Sched::Chain, chain_pos);
   HIPCHK(c, hipGetLastError());
   c->maybe_deferred = true;
   return TJ_OK;
@@ -355,15 +356,14 @@ int flush_deferred(tj_ctx* c) {
   return TJ_OK;
 }
 
-int heal_check(tj_ctx* c, int err_known);
 // drain: pay a deferred slack/dual update, then wait for every queue of the context
 #define QUIESCE_NOHEAL(c)                                       \
   do {                                                          \
     int qr_ = flush_deferred(c);                                \
     if (qr_) return qr_;                                        \
     HIPCHK(c, hipStreamSynchronize((c)->stream));               \
-    if ((c)->stream2) HIPCHK(c, hipStreamSynchronize((c)->stream2)); \
-    if ((c)->stream3) HIPCHK(c, hipStreamSynchronize((c)->stream3)); \
+    if ((c)->xq.stream2) HIPCHK(c, hipStreamSynchronize((c)->xq.stream2)); \
+    if ((c)->xq.stream3) HIPCHK(c, hipStreamSynchronize((c)->xq.stream3)); \
   } while (0)
 // every host-visible read or write of solver state first drains the context -- and, where a batch ran on several queues, looks whether it has to be run again (heal_check:
 // one 4-byte read-back; tj_sync alone does not look -- whoever reads a result afterwards does; tj_iterate uses the control block it reads anyway)
@@ -372,6 +372,51 @@ int heal_check(tj_ctx* c, int err_known);
     QUIESCE_NOHEAL(c);                                          \
     if ((c)->snap_iters > 0 && !(c)->heal_busy) { int hr_ = heal_check(c, -1); if (hr_) return hr_; } \
   } while (0)
+
+// Restart the pairings of the cross-queue schedule (CrossQueue): device words and host counters together, every queue drained.  keep_go (tj_init_state): the go words
+// xs_go / keep_go and their counters go on counting (nothing is in flight: they still match); the words in front of xs_go and fa_sync restart (begin_body zeroes keep_sync's counters).
+int restart_pairings(tj_ctx* c, bool keep_go) {
+  HIPCHK(c, hipMemsetAsync(c->d.xs_sync, 0, (keep_go ? (size_t)(c->d.xs_go() - c->d.xs_sync) : Dev::xs_sync_ints(c->d.U)) * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d.fa_sync, 0, Dev::fa_sync_ints(c->d.U) * sizeof(int), c->stream)); c->xq.fa_seq = 0; c->xq.fa_armed = c->xq.fa_mid_now = false;
+  if (!keep_go) { HIPCHK(c, hipMemsetAsync(c->d.keep_sync, 0, Dev::keep_sync_ints() * sizeof(int), c->stream)); c->xq.xs_seq = c->xq.xs_seq_gated = c->xq.keep_seq = 0; }
+  return TJ_OK;
+}
+// Checkpoint take: the host half now, the device half in the next k_begin (in_begin: the batch starts with one -- no begin folded) or in a k_snapshot launch now.
+int checkpoint_take(tj_ctx* c, bool in_begin) {
+  Checkpoint& k = c->ck;
+  k.in_begin = in_begin; k.begin_folded = c->begin_folded; k.maybe_deferred = c->maybe_deferred; k.lsc_base = c->lsc_base;
+  if (!in_begin) { hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(k.n, 1)), dim3(256), 0, c->stream, k.tab, k.n, 0, c->d.ctl, k.ctl); HIPCHK(c, hipGetLastError()); }
+  return TJ_OK;
+}
+// Restore: both halves back (the control block keeps the abandoned run's epoch: k_snapshot), the caches outside the checkpoint stale.  What a folded begin zeroed (work
+// lists, begin_body) is not in the checkpoint: such a fold is taken back as by any flush, so the next iteration starts with its own k_begin and counts the begun one once.
+int checkpoint_restore(tj_ctx* c) {
+  const Checkpoint& k = c->ck;
+  hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(k.n, 1)), dim3(256), 0, c->stream, k.tab, k.n, 1, c->d.ctl, k.ctl); HIPCHK(c, hipGetLastError());
+  c->begin_folded = k.begin_folded; c->maybe_deferred = k.maybe_deferred; c->lsc_base = k.lsc_base; c->hull_valid = c->ccd_valid = c->xf_used[0] = c->xf_used[1] = false;
+  return c->begin_folded ? flush_deferred(c) : TJ_OK;
+}
+void checkpoint_drop(tj_ctx* c) { c->ck.in_begin = false; }
+
+// Self-healing (tj_ctx): the batch enqueued since the checkpoint is through.  No incident: drop the checkpoint.  ERR_XS_TIMEOUT: latch one queue (release the queue
+// claim, clear the two-queue flags, restart the pairings), restore the checkpoint, enqueue the same iterations again and drain.
+int heal_check(tj_ctx* c, int err_known) {
+  int err = err_known;
+  if (err < 0) HIPCHK(c, hipMemcpy(&err, &c->d.ctl->error, sizeof(int), hipMemcpyDeviceToHost));   // (every queue has drained: QUIESCE)
+  const long long n = c->snap_iters; c->snap_iters = 0;
+  if (!(err & ERR_XS_TIMEOUT)) { checkpoint_drop(c); return TJ_OK; }
+  struct Busy { tj_ctx* c; ~Busy() { c->heal_busy = false; } } busy{c}; c->heal_busy = true;   // (reset on every exit)
+  c->async_fallbacks++;
+  if (c->xq.hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->xq.hwq_claim); c->xq.hwq_claim = 0; }   // (the budget is free for another context)
+  c->xq.xs_two_queues = c->xq.keep_two_queues = false; c->xq.xs_fault = 0;   // (the tickets / flags of the asynchronous solve work on one queue as well: TJ_XS_ONE_QUEUE's schedule)
+  int r = restart_pairings(c, false);
+  if (r || (r = checkpoint_restore(c))) return r;
+  checkpoint_drop(c);   // (the run enqueued again stays on one queue: nothing of it is healed)
+  HIPCHK(c, hipMemsetAsync(c->d.xf_seg, 0, (size_t)2 * c->d.S * XF_SEG_STRIDE * sizeof(int), c->stream)); HIPCHK(c, hipMemsetAsync(c->d.spec_n, 0, 8, c->stream));   // (spec_n: head-start lists of the abandoned iterations, launch shape only)
+  if ((r = tj_iterate_async(c, (int)n))) return r;
+  QUIESCE_NOHEAL(c);
+  return TJ_OK;
+}
 
 // Phase `which` of a sharded iteration (Sched::Phase), split at the all-gathers.  The phases are linear chains on the context's stream as well and reuse the union kernels where the
 // stages they join fall into the same phase (k_mid, k_ccd); the slack/dual update is the deferred one inside k_mid.
@@ -439,38 +484,8 @@ int ensure_hull_cache(tj_ctx* c) {
   if (!c->d.fuse || c->hull_valid) return TJ_OK;
   launch_kernel(c, K_HULLINFO, c->stream, Sched::Stage);
   HIPCHK(c, hipGetLastError());
-  c->hull_valid = true; c->hull_from_units = false;
+  c->hull_valid = true; c->xq.hull_from_units = false;
   return TJ_OK;
-}
-
-// The batch enqueued since the last snapshot is through (every queue drained).  No incident: forget the snapshot.  ERR_XS_TIMEOUT: one queue from now on, the snapshot's
-// state back in place, the same iterations again.
-int heal_check(tj_ctx* c, int err_known) {
-  int err = err_known;
-  if (err < 0) HIPCHK(c, hipMemcpy(&err, &c->d.ctl->error, sizeof(int), hipMemcpyDeviceToHost));   // (every queue has drained: QUIESCE)
-  const long long n = c->snap_iters;
-  c->snap_iters = 0;
-  if (!(err & ERR_XS_TIMEOUT)) return TJ_OK;
-  c->heal_busy = true;
-  c->async_fallbacks++;
-  if (c->hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->hwq_claim); c->hwq_claim = 0; }   // (one queue from now on: the budget is free for another context)
-  c->xs_two_queues = false; c->keep_two_queues = false; c->fa_armed = false; c->fa_mid_now = false; c->xs_fault = 0;   // (the tickets / flags of the asynchronous solve work on one queue as well: TJ_XS_ONE_QUEUE's schedule)
-  Dev& d = c->d;
-  hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(c->snap_n, 1)), dim3(256), 0, c->stream, c->snap_tab, c->snap_n, 1, d.ctl, c->ctl_snap);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(d.xs_sync, 0, ((size_t)2 * d.U + 2) * 32 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(d.fa_sync, 0, Dev::fa_sync_ints(d.U) * sizeof(int), c->stream)); c->fa_seq = 0;
-  HIPCHK(c, hipMemsetAsync(d.keep_sync, 0, 17 * 32 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(d.xf_seg, 0, (size_t)2 * d.S * XF_SEG_STRIDE * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(d.spec_n, 0, 8, c->stream));   // (head-start lists of the abandoned iterations: launch shape only, dropped)
-  c->hull_valid = false; c->ccd_valid = false; c->begin_folded = false; c->maybe_deferred = false;   // (what the snapshot's control block owes is owed again: the next k_mid / flush pays it)
-  c->xs_seq = c->xs_seq_gated = 0; c->keep_seq = 0;
-  int r = tj_iterate_async(c, (int)n);
-  if (r == TJ_OK) r = flush_deferred(c);
-  if (r == TJ_OK) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2)); if (c->stream3) HIPCHK(c, hipStreamSynchronize(c->stream3)); }
-  c->snap_iters = 0;
-  c->heal_busy = false;
-  return r;
 }
 
 bool ready(tj_ctx* c) {
@@ -668,13 +683,13 @@ int tj_create(const tj_params* p, tj_ctx** out) {
         std::atomic<int>& g = g_async_queues[std::min(std::max(p->device, 0), 63)];
         const int had = g.fetch_add(need);
         if (had + need > hw_queue_budget() && !forced) { g.fetch_sub(need); d.xs_async = 0; c->hwq_refused = true; }
-        else c->hwq_claim = need;
+        else c->xq.hwq_claim = need;
       }
     }
     if (d.xs_async) {
-      const bool ok = hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) == hipSuccess;
-      if (!ok) { (void)hipGetLastError(); c->stream2 = nullptr; }   // (the tickets and flags work on one queue as well)
-      c->xs_two_queues = ok && tune("XS_ONE_QUEUE") == nullptr;
+      const bool ok = hipStreamCreateWithFlags(&c->xq.stream2, hipStreamNonBlocking) == hipSuccess;
+      if (!ok) { (void)hipGetLastError(); c->xq.stream2 = nullptr; }   // (the tickets and flags work on one queue as well)
+      c->xq.xs_two_queues = ok && tune("XS_ONE_QUEUE") == nullptr;
     }
     // asynchronous plane refinement ("optimal_plane":1, multi-UAV decoupled mode, one context; TJ_KEEP_ASYNC=0: k_keep stays one launch between k_mid and k_grad -- same bits)
     d.keep_async = (d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !c->hwq_refused) ? 1 : 0;
@@ -682,8 +697,8 @@ int tj_create(const tj_params* p, tj_ctx** out) {
     if (const char* e = tune("KEEP_ASYNC")) d.keep_async = d.keep_async && atoi(e) != 0;
     d.keep_waves = 1024;
     if (d.keep_async) {
-      if (hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) == hipSuccess) c->keep_two_queues = true;
-      else { (void)hipGetLastError(); c->stream3 = nullptr; d.keep_async = 0; }
+      if (hipStreamCreateWithFlags(&c->xq.stream3, hipStreamNonBlocking) == hipSuccess) c->xq.keep_two_queues = true;
+      else { (void)hipGetLastError(); c->xq.stream3 = nullptr; d.keep_async = 0; }
     }
     if (const char* e = tune("GRAD_BALANCE")) d.grad_bal = (atoi(e) != 0 && owned * d.P <= 65536) ? 1 : 0;   // launch-shape switch (same bits)
     d.ls_help = (d.ls_fast && p->mode != TJ_MODE_MULTI_COUPLED) ? std::max(1, std::min(LS_HELP_MAX, prop.multiProcessorCount / owned)) : 1;
@@ -787,7 +802,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
       (r = dalloc(c, &d.oraw, U * S * d.cap_obs * 4)) || (r = dalloc(c, &d.ostamp, U * S * d.cap_obs)) ||
       (r = dalloc(c, &d.grad_scr, (size_t)(d.u1 - d.u0) * P * 16 * (size_t)(d.cap_obs + d.cap_self))) ||
       (r = dalloc(c, &d.xs_scr, d.xs_band ? (size_t)(d.u1 - d.u0) * ((size_t)n * n + 4 * n) : 1)) ||
-      (r = dalloc(c, &d.xf_seg, 2 * S * XF_SEG_STRIDE)) || (r = dalloc(c, &d.xs_sync, (2 * U + 2) * 32)) || (r = dalloc(c, &d.keep_sync, 17 * 32)) || (r = dalloc(c, &d.fa_sync, Dev::fa_sync_ints(d.U)))) return r;
+      (r = dalloc(c, &d.xf_seg, 2 * S * XF_SEG_STRIDE)) || (r = dalloc(c, &d.xs_sync, Dev::xs_sync_ints(U))) || (r = dalloc(c, &d.keep_sync, Dev::keep_sync_ints())) || (r = dalloc(c, &d.fa_sync, Dev::fa_sync_ints(d.U)))) return r;
   if (d.optimal_plane) {
     const bool m0 = d.mode == 0;
     if ((r = dalloc(c, &d.kobs_id, m0 ? U * S * d.cap_obs : 1)) || (r = dalloc(c, &d.kobs_n, U * S)) || (r = dalloc(c, &d.kobs_cd, m0 ? U * S * d.cap_obs * 4 : 1)) ||
@@ -796,7 +811,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
   }
   {   // self-healing: what a batch's first state consists of (everything an iteration reads that an earlier iteration wrote and that is not rebuilt or re-stamped anyway)
     c->heal = !(tune("HEAL") && atoi(tune("HEAL")) == 0);
-    if (const char* e = tune("XS_FAULT")) c->xs_fault = atoi(e);   // test hook: the n-th gate of the asynchronous solve reports a time-out
+    if (const char* e = tune("XS_FAULT")) c->xq.xs_fault = atoi(e);   // test hook: the n-th gate of the asynchronous solve reports a time-out
     std::vector<std::pair<void*, size_t>> reg = {
       {d.spline, U * 3 * T * 8}, {d.p_slack, U * 18 * P * 8}, {d.p_lambda, U * 18 * P * 8}, {d.t_slack, U * P * 8}, {d.t_lambda, U * P * 8}, {d.piece_time, U * 8},
       {d.xdir, U * d.xs * 8}, {d.ls_hist, U * 4}, {d.step_out, U * 8}, {d.seg_stats, U * S * 6 * 8}, {d.pair_stats, U * S * 2 * 8}, {d.blk_stats, (U * P + U) * 8}};
@@ -811,8 +826,8 @@ int tj_create(const tj_params* p, tj_ctx** out) {
       if ((r = dalloc(c, &snap, (pr.second + 15) / 16 * 16))) return r;
       tab.push_back(SnapRegion{(char*)pr.first, snap, (unsigned long long)pr.second});
     }
-    c->snap_n = (int)tab.size();
-    if ((r = dalloc(c, &c->snap_tab, tab.size())) || (r = dalloc(c, &c->ctl_snap, 1)) || (r = upload(c, c->snap_tab, tab.data(), tab.size() * sizeof(SnapRegion)))) return r;
+    c->ck.n = (int)tab.size();
+    if ((r = dalloc(c, &c->ck.tab, tab.size())) || (r = dalloc(c, &c->ck.ctl, 1)) || (r = upload(c, c->ck.tab, tab.data(), tab.size() * sizeof(SnapRegion)))) return r;
   }
   if (d.mode == TJ_MODE_MULTI_COUPLED &&
       ((r = dalloc(c, &d.xL, U * (d.xs_band ? (size_t)(n - 1) * BAND_BS + n : (size_t)n * n))) || (r = dalloc(c, &d.xy, U * (size_t)n)) || (r = dalloc(c, &d.xg, U * (size_t)n)) ||
@@ -822,10 +837,10 @@ int tj_create(const tj_params* p, tj_ctx** out) {
 
 void tj_destroy(tj_ctx* c) {
   if (!c) return;
-  if (c->hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->hwq_claim); c->hwq_claim = 0; }
+  if (c->xq.hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->xq.hwq_claim); c->xq.hwq_claim = 0; }
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
-  if (c->stream3) { (void)hipStreamSynchronize(c->stream3); (void)hipStreamDestroy(c->stream3); }
+  if (c->xq.stream2) { (void)hipStreamSynchronize(c->xq.stream2); (void)hipStreamDestroy(c->xq.stream2); }
+  if (c->xq.stream3) { (void)hipStreamSynchronize(c->xq.stream3); (void)hipStreamDestroy(c->xq.stream3); }
   for (void* p : c->xch_ipc_opened) (void)hipIpcCloseMemHandle(p);
   if (c->xch_block) (void)hipFree(c->xch_block);
   for (void* p : c->allocs) hipFree(p);
@@ -1002,8 +1017,7 @@ int tj_init_state(tj_ctx* c, const double* wp, double pt0) {
   // tj_group_init_state does; processes use their collective's barrier)
   if (c->xch_block) HIPCHK(c, hipMemsetAsync(d.xcnt, 0, 2 * XCH_MAX * sizeof(unsigned long long), c->stream));
   if (d.xf) HIPCHK(c, hipMemsetAsync(d.xf_seg, 0, (size_t)2 * d.S * XF_SEG_STRIDE * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(d.xs_sync, 0, ((size_t)2 * d.U + 1) * 32 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(d.fa_sync, 0, Dev::fa_sync_ints(d.U) * sizeof(int), c->stream)); c->fa_seq = 0; c->fa_armed = false;   // (the words are monotonic in the pairing number, which restarts here)
+  if ((r = restart_pairings(c, true))) return r;
   Ctl h;
   memset(&h, 0, sizeof(h));
   h.gnorm = 1.0;  // Main/multiPathPlanning3D.cpp:594
@@ -1074,11 +1088,8 @@ int tj_set_state(tj_ctx* c, int u, const double* spline, const double* p_slack, 
 namespace {
 // the parts of tj_iterate_async (also used by the lockstep enqueue of the ranks of a group that share a device, tj_group.h)
 int iterate_async_prologue(tj_ctx* c, int n_iters) {
-  if (c->heal && n_iters > 0 && (c->xs_two_queues || c->keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
-    if (c->snap_iters == 0 && !c->heal_busy) {
-      if (!c->begin_folded) c->snap_in_begin = true;   // the batch's first launch is k_begin: the snapshot rides in it
-      else { hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(c->snap_n, 1)), dim3(256), 0, c->stream, c->snap_tab, c->snap_n, 0, c->d.ctl, c->ctl_snap); HIPCHK(c, hipGetLastError()); }
-    }
+  if (c->heal && n_iters > 0 && (c->xq.xs_two_queues || c->xq.keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
+    if (c->snap_iters == 0 && !c->heal_busy) { int r = checkpoint_take(c, !c->begin_folded); if (r) return r; }   // (no begin folded: the batch's first launch is k_begin)
     if (!c->heal_busy) c->snap_iters += n_iters;
   }
   if (n_iters > 0) { int r = ensure_hull_cache(c); if (r) return r; }
@@ -1097,14 +1108,6 @@ int iterate_async_pos(tj_ctx* c, bool chain, int i, int n) {
   c->begin_folded = false;
   return pos;
 }
-
-// part of an iteration: kernels [k0, k1) of the stream order (enqueue_iteration is all of them)
-int enqueue_iteration_part(tj_ctx* c, int chain_pos, int k0, int k1) {
-  for (int k = k0; k < k1; k++) launch_kernel(c, k, c->stream, Sched::Chain, chain_pos);
-  HIPCHK(c, hipGetLastError());
-  c->maybe_deferred = true;
-  return TJ_OK;
-}
 }  // namespace
 
 int tj_iterate_async(tj_ctx* c, int n_iters) {
@@ -1112,16 +1115,13 @@ int tj_iterate_async(tj_ctx* c, int n_iters) {
   if (!ready(c)) return TJ_ERR_INVALID;
   { int r = iterate_async_prologue(c, n_iters); if (r) return r; }
   const bool chain = iterate_async_chain(c);
-  for (int i = 0; i < n_iters; i++) {
-    const int pos = iterate_async_pos(c, chain, i, n_iters);
-    int r = enqueue_iteration(c, pos); if (r) return r;
-  }
+  for (int i = 0; i < n_iters; i++)
+    if (int r = enqueue_iteration(c, iterate_async_pos(c, chain, i, n_iters))) return r;
   return TJ_OK;
 }
 
 int tj_sync(tj_ctx* c) {
   if (!c) return TJ_ERR_INVALID;
-  { int r = flush_deferred(c); if (r) return r; }
   QUIESCE_NOHEAL(c);   // (no read-back here: a batch that has to be run again -- heal_check -- is noticed by the next call that reads a result or the statistics)
   return TJ_OK;
 }
@@ -1145,7 +1145,7 @@ int tj_profile_kernels(tj_ctx* c, int n_iters, double* ms, int* launches) {
   std::vector<hipEvent_t> ev((size_t)n_iters * (K_COUNT + 1));
   for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
   std::vector<int> ran(K_COUNT, 0);
-  c->xs_same_queue_now = true;   // per-kernel events on one queue: the asynchronous solve follows k_grad there (its own time is then what the events show)
+  c->xq.xs_same_queue_now = true;   // per-kernel events on one queue: the asynchronous solve follows k_grad there (its own time is then what the events show)
   for (int it = 0; it < n_iters; it++) {
     hipEvent_t* e = &ev[(size_t)it * (K_COUNT + 1)];
     HIPCHK(c, hipEventRecord(e[0], c->stream));
@@ -1156,7 +1156,7 @@ int tj_profile_kernels(tj_ctx* c, int n_iters, double* ms, int* launches) {
       HIPCHK(c, hipEventRecord(e[k + 1], c->stream));
     }
   }
-  c->xs_same_queue_now = false;
+  c->xq.xs_same_queue_now = false;
   if (n_iters > 0) c->maybe_deferred = true;  // the last iteration's slack/dual update is still owed (paid by the flush below)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < K_COUNT; k++) ms[k] = 0;

@@ -279,7 +279,7 @@ int group_direct_lockstep(tj_group* g, int n_iters, std::vector<int>& rc) {
         tj_ctx* c = g->ctx[r];
         if (hipSetDevice(g->dev[r]) != hipSuccess) { c->err = "hipSetDevice failed"; return rc[r] = TJ_ERR_DEVICE; }
         if (part == 0) pos[r] = iterate_async_pos(c, chain[r], i, n_iters);
-        if ((rc[r] = enqueue_iteration_part(c, pos[r], cut[part], cut[part + 1]))) return rc[r];
+        if ((rc[r] = enqueue_iteration(c, pos[r], cut[part], cut[part + 1]))) return rc[r];
       }
   }
   return TJ_OK;
@@ -484,12 +484,12 @@ int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, 
   g->abort_flag.store(0);
   std::vector<int> rc(g->n, TJ_OK);
   const bool cpl_sharded = g->n > 1 && g->ctx[0]->d.mode == TJ_MODE_MULTI_COUPLED;
-  if (cpl_sharded)   // the state the batch starts from: a search that leaves the exchanged candidates (error bit 32) is followed in a second, careful run of the batch (below)
+  if (cpl_sharded)   // checkpoint of the state the batch starts from: a search that leaves the exchanged candidates (error bit 32) is followed in a second, careful run of the batch (below)
     for (int r = 0; r < g->n; r++) {
       tj_ctx* c = g->ctx[r];
       if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
-      if (int fr = flush_deferred(c)) return group_fail(g, fr, tj_last_error(c));   // (the update the previous batch still owes belongs to the state)
-      hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(c->snap_n, 1)), dim3(256), 0, c->stream, c->snap_tab, c->snap_n, 0, c->d.ctl, c->ctl_snap);
+      int fr = flush_deferred(c);   // (the update the previous batch still owes belongs to the state)
+      if (fr || (fr = checkpoint_take(c, false))) return group_fail(g, fr, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
     }
   // direct exchange with ranks sharing a device: enqueued in lockstep by this thread (group_direct_lockstep)
   const bool lockstep = g->n > 1 && !g->distinct && g->transport == TJ_TRANSPORT_FLAG && g->ctx[0]->d.xch;
@@ -518,8 +518,7 @@ int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, 
       for (int r = 0; r < g->n; r++) {
         tj_ctx* c = g->ctx[r];
         (void)hipSetDevice(g->dev[r]);
-        hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(c->snap_n, 1)), dim3(256), 0, c->stream, c->snap_tab, c->snap_n, 1, c->d.ctl, c->ctl_snap);
-        c->hull_valid = false; c->ccd_valid = false; c->maybe_deferred = false; c->begin_folded = false;
+        if (int e = checkpoint_restore(c)) { g->poisoned = true; return group_fail(g, e, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c)); }   // (the ranks no longer start from one state)
         tj_set_coupled_follow(c, 1);
       }
       std::vector<long> extra(g->n, 0);

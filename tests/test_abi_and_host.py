@@ -201,7 +201,7 @@ def test_hot_kernels_use_no_scratch_memory(pkg, tmp_path):
 
 
 def _disassemble(pkg, tmp_path):
-    """{kernel symbol: [(mnemonic, operand text)]} of the gfx950 code object inside the shipped library"""
+    """{symbol: [(address, mnemonic, operand text)]} of the gfx950 code object inside the shipped library"""
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     if not os.path.exists(objdump):
         pytest.skip("LLVM binutils of the ROCm image not found")
@@ -217,43 +217,73 @@ def _disassemble(pkg, tmp_path):
         if m:
             cur = m.group(1); body[cur] = []
         elif cur and line.strip():
-            text = line.split("//")[0].strip()
-            if text:
+            text, _, comment = line.partition("//")
+            a = re.match(r"\s*([0-9A-Fa-f]+):", comment)   # the instruction's address (lines without one: padding)
+            if text.strip() and a:
                 parts = text.split(None, 1)
-                body[cur].append((parts[0], parts[1] if len(parts) > 1 else ""))
+                body[cur].append((int(a.group(1), 16), parts[0], parts[1].strip() if len(parts) > 1 else ""))
     return body
+
+
+def _region(k, ins, at, i, end):
+    """indices of the instructions of the marked region that starts at ins[i], followed along the control flow -- fall-through and branch targets
+    (next instruction + 4 * simm16) -- up to the end marker (an immediate of `end`).  Layout order is not control flow: the compiler places unrelated
+    blocks between a region's markers.  s_endpgm or an indirect branch / call inside a region, or a region that never reaches its end, fails."""
+    seen, todo, ends = set(), [i + 1], 0
+    while todo:
+        j = todo.pop()
+        if j in seen:
+            continue
+        assert j < len(ins), f"{k}: a marked region runs off the end of the function"
+        a, m, ops = ins[j]
+        if m == "s_nop" and ops in end:
+            ends += 1
+            continue
+        seen.add(j)
+        assert not m.startswith(("s_endpgm", "s_setpc", "s_swappc", "s_call", "s_rfe")), f"{k}: {m} inside a marked region"
+        if m.startswith(("s_branch", "s_cbranch_")):
+            imm = int(ops.split()[0])
+            imm -= 65536 if imm >= 32768 else 0
+            assert a + 4 + 4 * imm in at, f"{k}: branch out of the function inside a marked region: {m} {ops}"
+            todo.append(at[a + 4 + 4 * imm])
+            if m == "s_branch":
+                continue
+        todo.append(j + 1)
+    assert ends, f"{k}: a marked region ({ins[i][2]}) that never reaches its end marker"
+    return sorted(seen)
 
 
 def test_signalling_sites_keep_their_order(pkg, tmp_path):
     """Every cross-block / cross-queue protocol of the library ("Synchronisation protocols") rests on one idiom: records out with write-through
     stores, `s_waitcnt vmcnt(0)` (+ a barrier where several waves stored), THEN the signal -- a relaxed atomic; the consumer polls the word and reads afterwards.  Relaxed
     atomics promise no such order in the HIP memory model; the instruction stream does.  This test reads the shipped code object and fails if a compiler change takes the
-    order away.  The sites carry `s_nop` immediates no compiler emits (dev_common.h: sig_acked 0x2a1 / sig_sent 0x2a2, wait_begin 0x2b1 / wait_end 0x2b2, and 0x2c1 / 0x2c2
-    around "the DONE word is performed before the commit stores" in k_linesearch):
+    order away.  The sites carry `s_nop` immediates no compiler emits (dev_common.h: sig_acked 0x2a1 / sig_sent 0x2a2, poll_until 0x2b1 / 0x2b2, and 0x2c1 / 0x2c2
+    around "the DONE word is performed before the commit stores" in k_linesearch).  Every function of the code object is walked, and every marked region is followed
+    along its control flow (_region), not its layout:
       * right behind 0x2a1 stands the full `s_waitcnt vmcnt(0) ...`; from there to 0x2a2 there is no memory write but the signal itself -- a 32-bit or 64-bit atomic, or
         a single 32-bit write-through store, or ONE 64-bit write-through store on its own (a head-start entry's tag); record stores are 64 bits wide and come in
         numbers: one sunk below the wait would show here;
-      * the first memory instruction behind 0x2b1 is the poll itself, a 32- or 64-bit load past the caches (sc1) -- a record load hoisted to the head of the wait would
-        stand there instead (the block layout between the loop's markers is not its control flow, so the loop body is not scanned further);
+      * between 0x2b1 and 0x2b2 (a wait) every vector memory instruction is a poll -- a load past the caches (sc1) -- or the `buffer_inv` right behind an acquire
+        poll; there is no store and no atomic (what a site does on a time-out comes after the wait) and no LDS access but a cross-lane permute;
       * between 0x2c1 and 0x2c2 stand the wait and the barrier and no store at all."""
     body = _disassemble(pkg, tmp_path)
-    chain = [k for k in body if re.search(r"tj\d+(k_grad|k_xsolve|k_linesearch|k_front|k_mid|k_ccd_lean|k_ccd|k_keep|k_begin|k_xs_gate|k_fa_gate|k_keep_gate|k_ls_coupled)(I|E)", k)]
-    assert len(chain) >= 12, sorted(body)[:5]
-    n_sig = n_wait = n_word = 0
+    assert len(body) >= 60 and sum(m == "s_endpgm" for ins in body.values() for _, m, _ in ins) >= 50, sorted(body)[:5]   # (parsed into mnemonics)
+    mem = ("global_", "flat_", "buffer_", "scratch_")
     writes = ("global_store", "flat_store", "scratch_store", "buffer_store", "global_atomic", "flat_atomic", "buffer_atomic")
-    for k in chain:
-        ins = body[k]
-        assert any(m == "s_endpgm" for m, _ in ins) and any(m.startswith("global_load") for m, _ in ins), f"disassembly of {k} not parsed into mnemonics"
-        i = 0
-        while i < len(ins):
-            m, ops = ins[i]
-            if m == "s_nop" and ops.strip() in ("0x2a1", "673"):
+    lds_ok = ("ds_bpermute_b32", "ds_permute_b32", "ds_swizzle_b32")
+    n_sig = n_wait = n_word = 0
+    waits = {}   # function -> checked waits
+    for k, ins in body.items():
+        at = {a: j for j, (a, _, _) in enumerate(ins)}
+        for i, (_, m, ops) in enumerate(ins):
+            if m != "s_nop":
+                continue
+            if ops in ("0x2a1", "673"):
                 n_sig += 1
-                assert ins[i + 1][0] == "s_waitcnt" and "vmcnt(0)" in ins[i + 1][1], f"{k}: no s_waitcnt vmcnt(0) right behind the 'acknowledged' marker: {ins[i + 1]}"
-                j = i + 2
+                assert ins[i + 1][1] == "s_waitcnt" and "vmcnt(0)" in ins[i + 1][2], f"{k}: no s_waitcnt vmcnt(0) right behind the 'acknowledged' marker: {ins[i + 1]}"
                 wide = other = 0
-                while j < len(ins) and not (ins[j][0] == "s_nop" and ins[j][1].strip() in ("0x2a2", "674")) and ins[j][0] != "s_endpgm":
-                    mm, oo = ins[j]
+                for j in _region(k, ins, at, i, ("0x2a2", "674")):
+                    _, mm, oo = ins[j]
                     if mm.startswith(writes):
                         if mm == "global_store_dwordx2" and "sc1" in oo:
                             wide += 1      # a 64-bit word that IS the signal (a head-start entry's tag); allowed only alone
@@ -261,32 +291,62 @@ def test_signalling_sites_keep_their_order(pkg, tmp_path):
                             other += 1
                             is_signal = "atomic" in mm or (mm == "global_store_dword" and "sc1" in oo)
                             assert is_signal, f"{k}: a store between 'acknowledged' and the signal: {mm} {oo}"
-                    j += 1
                 assert wide == 0 or (wide == 1 and other == 0), f"{k}: 64-bit stores between 'acknowledged' and the signal ({wide} of them, {other} other writes): a record store sunk below the wait?"
-                assert j < len(ins) and ins[j][0] == "s_nop", f"{k}: 'acknowledged' marker without a 'sent' marker behind it"
-                i = j
-            elif m == "s_nop" and ops.strip() in ("0x2b1", "689"):
+            elif ops in ("0x2b1", "689"):
                 n_wait += 1
-                j = i + 1
-                while not ins[j][0].startswith(("global_", "flat_", "buffer_", "scratch_")):   # the first memory instruction behind the marker, in layout order, is the poll
-                    assert ins[j][0] != "s_endpgm", f"{k}: a wait without a poll"
-                    j += 1
-                assert ins[j][0] in ("global_load_dword", "global_load_dwordx2") and "sc1" in ins[j][1], f"{k}: the first memory access of a wait is not a poll past the caches: {ins[j]}"
-            elif m == "s_nop" and ops.strip() in ("0x2c1", "705"):
+                polls = 0
+                for j in _region(k, ins, at, i, ("0x2b2", "690")):
+                    _, mm, oo = ins[j]
+                    if mm == "buffer_inv":
+                        p = j - 1
+                        while ins[p][1] == "s_waitcnt":
+                            p -= 1
+                        assert ins[p][1].startswith("global_load") and "sc1" in ins[p][2], f"{k}: a cache invalidation inside a wait that is not an acquire poll's: {ins[p]}"
+                    elif mm.startswith(mem):
+                        assert not mm.startswith(writes), f"{k}: a store or atomic inside a wait (a time-out action belongs behind 0x2b2): {mm} {oo}"
+                        assert mm.startswith("global_load") and "sc1" in oo, f"{k}: a memory access inside a wait that is not a poll past the caches: {mm} {oo}"
+                        polls += 1
+                    assert not mm.startswith("ds_") or mm in lds_ok, f"{k}: an LDS access inside a wait: {mm} {oo}"
+                assert polls, f"{k}: a wait without a poll"
+                waits[k] = waits.get(k, 0) + 1
+            elif ops in ("0x2c1", "705"):
                 n_word += 1
-                j = i + 1
                 seen_wait = seen_barrier = False
-                while not (ins[j][0] == "s_nop" and ins[j][1].strip() in ("0x2c2", "706")):
-                    mm, oo = ins[j]
+                for j in _region(k, ins, at, i, ("0x2c2", "706")):
+                    _, mm, oo = ins[j]
                     seen_wait |= mm == "s_waitcnt" and "vmcnt(0)" in oo
                     seen_barrier |= mm == "s_barrier"
                     assert not mm.startswith(writes), f"{k}: a memory write between the DONE word's wait and the commit: {mm} {oo}"
-                    j += 1
                 assert seen_wait and seen_barrier, f"{k}: the DONE word's wait / barrier is gone"
-                i = j
-            i += 1
-    # the sites exist (a refactoring that drops the markers must not turn this test into a no-op): producers in k_grad, k_xsolve, k_linesearch, k_front, k_ccd, k_keep, k_mid's watcher, ...
-    assert n_sig >= 20 and n_wait >= 20 and n_word >= 1, (n_sig, n_wait, n_word)
+    # the sites exist (a refactoring that drops the markers must not turn this test into a no-op): producers in k_grad, k_xsolve, k_linesearch, k_front, k_ccd, k_keep,
+    # k_mid's watcher, ...; waits in every kernel that polls, the gates and the group exchange among them
+    assert n_sig >= 64 and n_wait >= 82 and n_word >= 1, (n_sig, n_wait, n_word)
+    for name in ("k_keep_gate", "k_xch_wait", "k_group_wait_unpack", "k_ls_coupled", "k_linesearch"):
+        assert any(re.search(rf"tj\d+{name}(I|E)", k) for k in waits), f"no checked wait in {name}"
+
+
+def test_every_consumer_waits_through_poll_until():
+    """A cross-block wait is written once (dev_common.h: poll_until, with the markers the ISA test checks inside it).  A hand-written poll loop in csrc/ would
+    escape that test, so: s_sleep stands only in poll_until, in group_barrier (an LDS barrier among the waves of one block) and in the TJ_LS_HELP_LATE delay
+    (a test hook), and only poll_until compares the wall clock with a deadline."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "traj-opt-admm_amd", "csrc")
+    sleeps, deadlines = [], []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".h", ".hip", ".cpp")):
+            continue
+        fn = None
+        lines = open(os.path.join(csrc, f)).read().splitlines()
+        for n, line in enumerate(lines):
+            m = re.search(r"__(?:device|global)__\b.*?\b(\w+)\s*\(", line)
+            if m:
+                fn = m.group(1)
+            if "__builtin_amdgcn_s_sleep" in line:
+                sleeps.append((f, "TJ_LS_HELP_LATE" if "ls_help_late" in lines[n - 1] + line else fn))
+            if re.search(r"wall_clock64\(\)\s*>", line):
+                deadlines.append((f, fn))
+    assert sorted(sleeps) == [("dev_common.h", "poll_until"), ("dev_linalg.h", "group_barrier"), ("kernels_ls.h", "TJ_LS_HELP_LATE")], sleeps
+    assert deadlines == [("dev_common.h", "poll_until")], deadlines
 
 
 def test_every_environment_switch_is_documented():

@@ -360,15 +360,38 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 // ACKNOWLEDGED (`s_waitcnt vmcnt(0)`: the counter is per wave; a barrier hands it to the other waves of a block) and only then issues the signal -- a relaxed atomic on a word
 // of its own cache line.  CONSUMER: polls the word with a relaxed atomic load (`global_load ... sc1`) and reads the records afterwards, either past the caches (sc1 loads) or
 // from lines its XCD's L2 cannot hold yet.  No fence instruction on either side (a release is `buffer_wbl2`: it writes back the whole L2 of the XCD, measured +14 us when
-// every block of a large grid does it).  What the HIP memory model does not promise for relaxed atomics the ISA does; so that a compiler change cannot silently take it
-// away, the sites are marked with `s_nop` immediates no compiler emits and tests/test_abi_and_host.py::test_signalling_sites_keep_their_order checks, in the disassembly of
-// the shipped code object, that between "acknowledged" (0x2a1 + the s_waitcnt) and "sent" (0x2a2) there is no store but the signal itself, and that a wait loop (0x2b1 ...
-// 0x2b2) contains no load that is not a poll.
+// every block of a large grid does it).  Every consumer waits through poll_until (below); every producer brackets its signal with sig_acked / sig_sent.  What the HIP memory
+// model does not promise for relaxed atomics the ISA does; so that a compiler change cannot silently take it away, the sites are marked with `s_nop` immediates no compiler
+// emits and tests/test_abi_and_host.py::test_signalling_sites_keep_their_order walks, in the disassembly of every kernel of the shipped code object, each marked region along
+// its control flow: between "acknowledged" (0x2a1 + the s_waitcnt) and "sent" (0x2a2) there is no store but the signal itself, and a wait (0x2b1 ... 0x2b2) holds no memory
+// access but the poll -- no record load, no store, no atomic (what a site does on a time-out comes after 0x2b2).
 #define TJ_MARK_(imm) asm volatile("s_nop " #imm ::: "memory")
 __device__ __forceinline__ void sig_acked() { TJ_MARK_(0x2a1); __builtin_amdgcn_s_waitcnt(0); asm volatile("" ::: "memory"); }   // every store this wave has issued is acknowledged
 __device__ __forceinline__ void sig_sent() { TJ_MARK_(0x2a2); }                                                                   // the signal has been issued
-__device__ __forceinline__ void wait_begin() { TJ_MARK_(0x2b1); }
-__device__ __forceinline__ void wait_end() { TJ_MARK_(0x2b2); }
+// Limits of the waits, in ticks of the 100 MHz wall clock: a logic error or a lost peer must not hang the device.  2 s where the producer runs on another queue or
+// device (a GPU shared with another process may leave that queue off the hardware for whole time slices: 5 ms was too short), 5 ms (+ 1 us per block / wave of a
+// large launch: a profiler or a shared GPU stretches it) where it is a block of the same launch, 10 us where the waiter can go on without the signal.
+constexpr long long WAIT_2S = 200000000ll, WAIT_5MS = 500000ll, WAIT_10US = 1000ll, WAIT_SLACK = 100ll;
+// THE wait.  Polls once; after a failed poll it reads the clock (t_end == 0: the limit starts now; a caller may share one t_end over several waits) and loops
+// sleep (none for SLEEP == 0), poll, deadline.  `poll` is the loop's only memory access -- an sc1 load of the signal word(s) -- and its result is wave-uniform.
+// Returns whether the poll succeeded; what a site does on a time-out (error bits, counters, fallback values) it does after the call, outside the marked region.
+template <int SLEEP, class Poll>
+__device__ __forceinline__ bool poll_until(Poll&& poll, long long& t_end, long long ticks) {
+  TJ_MARK_(0x2b1);
+  bool ok = poll();
+  if (!ok) {
+    if (t_end == 0) t_end = wall_clock64() + ticks;
+    for (;;) {
+      if constexpr (SLEEP > 0) __builtin_amdgcn_s_sleep(SLEEP);
+      if ((ok = poll())) break;
+      if (wall_clock64() > t_end) break;
+    }
+  }
+  TJ_MARK_(0x2b2);
+  return ok;
+}
+template <int SLEEP, class Poll>
+__device__ __forceinline__ bool poll_until(Poll&& poll, long long ticks) { long long t_end = 0; return poll_until<SLEEP>(poll, t_end, ticks); }
 __device__ __forceinline__ unsigned long long ballot(bool p) { return __ballot(p); }
 __device__ __forceinline__ int prefix_count(unsigned long long m) { return __popcll(m & ((1ull << lane_id()) - 1ull)); }
 
@@ -411,121 +434,59 @@ __device__ __forceinline__ void xch_push_robot(const Dev& D, int kind, int u, in
 }
 
 // ---- consumer side ----
-constexpr long long XCH_TIMEOUT_TICKS = 200000000ll;   // 2 s of the 100 MHz wall clock: a lost peer must not hang the device
+__device__ __forceinline__ void wait_failed(const Dev& D, int bits) { if (lane_id() == 0) atomicOr(&D.ctl->error, bits); }
 // All `need` robots of rank r have pushed their slice of kind k for the launch that is running?  (Every rank pushes once per iteration, so the rounds
-// THIS rank has pushed -- final when the kernel started -- are the rounds it may expect of a peer.)  Wave-uniform; false = timed out (error bit set).
-__device__ __forceinline__ bool xch_wait_owner(const Dev& D, int kind, int r) {
+// THIS rank has pushed -- final when the kernel started -- are the rounds it may expect of a peer.)  One wave.
+__device__ __forceinline__ void xch_wait_owner(const Dev& D, int kind, int r) {
   const unsigned long long need = (unsigned long long)(D.ctl->xpush[kind] / (D.u1 - D.u0)) * (unsigned long long)D.owned_by(r);
   const unsigned long long* w = D.xcnt + kind * XCH_MAX + r;
-  wait_begin();
-  bool ok = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= need;
-  if (!ok) {
-    const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;
-    for (;;) {
-      __builtin_amdgcn_s_sleep(4);
-      if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= need) { ok = true; break; }
-      if (wall_clock64() > t_end) { atomicOr(&D.ctl->error, ERR_PEER_TIMEOUT); break; }
-    }
-  }
-  wait_end();
-  return ok;
+  if (!poll_until<4>([&] { return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) >= need; }, WAIT_2S)) wait_failed(D, ERR_PEER_TIMEOUT);
 }
 // Foreign-robot units (kernels_step.h) leave their records with write-through stores, wait for the acknowledgements and count themselves done; the pair
 // tiles of the same launch -- later in the grid, so every unit is resident or finished when a tile starts -- wait for the count.  Records are line
 // aligned (HULL_INFO_STRIDE, CCD_STRIDE), so what a tile then loads cannot have been fetched by its XCD's L2 earlier in the launch.
 __device__ __forceinline__ void xf_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double xf_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void xf_store_i(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int xf_load_i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int* xf_word(const Dev& D, int kind, int tr) { return D.xf_seg + ((size_t)kind * D.S + tr) * XF_SEG_STRIDE; }
 __device__ __forceinline__ void xf_signal(const Dev& D, int kind, int tr) {
   sig_acked();
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(xf_word(D, kind, tr), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   sig_sent();
 }
-// every foreign unit of segment tr has left its record?  one wave; uniform
-__device__ __forceinline__ bool xf_wait_seg(const Dev& D, int kind, int tr) {
+// every foreign unit of segment tr has left its record?  One wave.  (Direct exchange or an asynchronous solve: the units themselves may wait 2 s.)
+__device__ __forceinline__ void xf_wait_seg(const Dev& D, int kind, int tr) {
   const int want = D.xf_want();
   const int* w = xf_word(D, kind, tr);
-  wait_begin();
-  bool ok = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
-  if (!ok) {
-    const long long t_end = wall_clock64() + ((D.xch || D.xs_async) ? XCH_TIMEOUT_TICKS + 10000000ll : 500000ll + 100ll * gridDim.x);   // (direct exchange: the units themselves may wait 2 s for a peer)
-    for (;;) {
-      __builtin_amdgcn_s_sleep(2);
-      if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) { ok = true; break; }
-      if (wall_clock64() > t_end) { if ((threadIdx.x & 63) == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_PASS_TIMEOUT); break; }
-    }
-  }
-  wait_end();
-  return ok;
+  const long long lim = (D.xch || D.xs_async) ? WAIT_2S + WAIT_2S / 20 : WAIT_5MS + WAIT_SLACK * gridDim.x;   // (2.1 s)
+  if (!poll_until<2>([&] { return xf_load_i(w) >= want; }, lim)) wait_failed(D, ERR_LOOP_CAP | ERR_PASS_TIMEOUT);
 }
-
-// asynchronous Newton solve (Dev::xs_async): wait until word *w has reached `want`.  One wave, uniform; false = timed out (error bit set).
+// asynchronous Newton solve (Dev::xs_async): word *w has reached `want`.  One wave.
 template <int SLEEP = 2>
-__device__ __forceinline__ bool xs_wait(const Dev& D, const int* w, int want) {
-  wait_begin();
-  bool ok = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
-  if (!ok) {
-    const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;   // 2 s: a logic error must not hang the device -- but a GPU shared with another process may leave the
-                                                                  // other queue of this context off the hardware for whole time slices (5 ms was too short for that)
-    for (;;) {
-      __builtin_amdgcn_s_sleep(SLEEP);
-      if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) { ok = true; break; }
-      if (wall_clock64() > t_end) { if ((threadIdx.x & 63) == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); break; }
-    }
-  }
-  wait_end();
-  return ok;
+__device__ __forceinline__ void xs_wait(const Dev& D, const int* w, int want) {
+  if (!poll_until<SLEEP>([&] { return xf_load_i(w) >= want; }, WAIT_2S)) wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
 }
-// asynchronous plane refinement (Dev::keep_async): every wave of the refinement launch (third queue) has left its planes?  Called by all threads of a block; uniform.
+// poll of sixteen counters, `stride` ints apart (one wave; lanes 0..15 load): their sum, wave-uniform
+__device__ __forceinline__ int sum16(const int* base, int stride = 32) {
+  int v = lane_id() < 16 ? xf_load_i(base + (size_t)lane_id() * stride) : 0;
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return __shfl(v, 0);
+}
+// asynchronous plane refinement (Dev::keep_async): every wave of the refinement launch (third queue) has left its planes?  Called by all threads of a block.
+// (2 s: a refinement of thousands of rounds is legitimate -- the reference spins on such planes as well.)
 __device__ __forceinline__ void keep_wait(const Dev& D) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;   // 2 s (a refinement of thousands of rounds is legitimate: the reference spins on such planes as well)
-    wait_begin();
-    for (;;) {
-      int v = lane < 16 ? __hip_atomic_load(D.keep_sync + lane * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      v = __shfl(v, 0);
-      if (v >= D.keep_waves) break;
-      if (wall_clock64() > t_end) { if (lane == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); break; }
-      __builtin_amdgcn_s_sleep(8);
-    }
-    wait_end();
-  }
+  if (threadIdx.x < 64 && !poll_until<8>([&] { return sum16(D.keep_sync) >= D.keep_waves; }, WAIT_2S)) wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
   __syncthreads();
   asm volatile("" ::: "memory");
 }
-// asynchronous front (Dev::fa_seq): the sixteen words at `base` (a 128-byte line each) sum to at least `want`?  One wave, uniform; false = timed out (error bit set).
-__device__ __forceinline__ bool fa_wait16(const Dev& D, const int* base, int want) {
-  const int lane = threadIdx.x & 63;
-  const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;
-  bool ok = false;
-  wait_begin();
-  for (;;) {
-    int v = lane < 16 ? __hip_atomic_load(base + (size_t)lane * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    v = __shfl(v, 0);
-    if (v - want >= 0) { ok = true; break; }
-    if (wall_clock64() > t_end) { if (lane == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); break; }
-    __builtin_amdgcn_s_sleep(4);
-  }
-  wait_end();
-  return ok;
+// asynchronous front (Dev::fa_seq): the sixteen words at `base` (a 128-byte line each) sum to at least `want` (wrap-safe)?  One wave.
+__device__ __forceinline__ void fa_wait16(const Dev& D, const int* base, int want) {
+  if (!poll_until<4>([&] { return sum16(base) - want >= 0; }, WAIT_2S)) wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
 }
 // ... one word has reached `want` (a robot's commit flag)
-__device__ __forceinline__ bool fa_wait_flag(const Dev& D, const int* w, int want) {
-  wait_begin();
-  bool ok = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want >= 0;
-  if (!ok) {
-    const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;
-    for (;;) {
-      __builtin_amdgcn_s_sleep(4);
-      if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want >= 0) { ok = true; break; }
-      if (wall_clock64() > t_end) { if ((threadIdx.x & 63) == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); break; }
-    }
-  }
-  wait_end();
-  return ok;
+__device__ __forceinline__ void fa_wait_flag(const Dev& D, const int* w, int want) {
+  if (!poll_until<4>([&] { return xf_load_i(w) - want >= 0; }, WAIT_2S)) wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
 }
 // a block's stores (write-through) have been acknowledged -> it counts itself on one of sixteen words (fire and forget)
 __device__ __forceinline__ void fa_count(int* w) {
@@ -533,8 +494,6 @@ __device__ __forceinline__ void fa_count(int* w) {
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(w, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   sig_sent();
 }
-__device__ __forceinline__ void xf_store_i(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int xf_load_i(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // a value that a kernel running at the same time on the other queue will read: written through when the solve is asynchronous
 __device__ __forceinline__ void xs_out(bool wt, double* p, double v) { if (wt) xf_store(p, v); else *p = v; }
 

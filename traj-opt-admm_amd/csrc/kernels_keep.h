@@ -24,12 +24,7 @@ namespace tj {
 // part: 0 = everything (the one-queue chain, the stage API), 1 = new pairs only, 2 = the planes stored before this iteration only (asynchronous refinement, Dev::keep_async:
 // launched on a queue of its own at the start of the iteration; its planes go out written through, every wave counts itself done)
 __global__ __launch_bounds__(64) void k_keep_gate(Dev D, int seq) {
-  const int* w = D.keep_go();
-  const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;   // 2 s
-  while (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq < 0) {
-    if (wall_clock64() > t_end) { if (threadIdx.x == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); break; }
-    __builtin_amdgcn_s_sleep(16);
-  }
+  if (!poll_until<16>([&] { return xf_load_i(D.keep_go()) - seq >= 0; }, WAIT_2S)) wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
 }
 __global__ __launch_bounds__(64) void k_keep(Dev D, int part) {
   const bool wt = part == 2;

@@ -631,15 +631,10 @@ __global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, in
         // The word permits round sr + 1 as soon as the primary's own two candidates of round sr have failed -- before it has read our posts: that
         // evaluation runs ahead of the decision and is left at its barrier if the search ends meanwhile (x_energy_team: abort_word).
         if (tid == 0) {
-          const long long t_end = wall_clock64() + 500000;   // 5 ms: a logic error must not hang the device
-          int leave = 0;
-          for (;;) {
-            const unsigned long long w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((unsigned)(w >> 32) == epoch) { if ((unsigned)w == LS_WORD_DONE) { leave = 1; break; } if ((unsigned)w > (unsigned)sr) break; }
-            if (wall_clock64() > t_end) { leave = 1; atomicAdd(&D.ctl->ls_helper_timeouts, 1); break; }
-            __builtin_amdgcn_s_sleep(1);
-          }
-          s_flag = leave;
+          unsigned long long w = 0;   // (LS_WORD_DONE > every super-round)
+          const bool ok = poll_until<1>([&] { w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)(w >> 32) == epoch && (unsigned)w > (unsigned)sr; }, WAIT_5MS);
+          if (!ok) atomicAdd(&D.ctl->ls_helper_timeouts, 1);
+          s_flag = !ok || (unsigned)w == LS_WORD_DONE;
         }
         __syncthreads();
         if (s_flag) break;
@@ -654,16 +649,13 @@ __global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, in
         if (acc_k < 0 && H > 1) {
           // Our own two failed: PERMIT round sr + 1 at once (word = sr + 1) -- the helpers start it while we look at their posts of this round; if one of those
           // passes, they leave mid-evaluation.  (The set round sr + 1 posts into was emptied at the end of round sr - 2: long performed, the wait is free.)
-          __builtin_amdgcn_s_waitcnt(0);
+          sig_acked();
           if (tid == 0) __hip_atomic_store(word, ((unsigned long long)epoch << 32) | (unsigned)(sr + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          sig_sent();
           double v = 0.0;
-          const long long t_end = wall_clock64() + 1000;   // 10 us
-          for (;;) {
-            const bool mine = tid >= 2 && tid < 2 * H;
-            if (mine) v = __hip_atomic_load(tab + set + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__ballot(mine && (unsigned long long)__double_as_longlong(v) == LS_TAB_EMPTY) == 0ull) break;
-            if (wall_clock64() > t_end) { giveup = 1; if (tid == 0) atomicAdd(&D.ctl->ls_giveups, 1); break; }
-          }
+          const bool mine = tid >= 2 && tid < 2 * H;
+          auto all_posted = [&] { if (mine) v = __hip_atomic_load(tab + set + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return ballot(mine && (unsigned long long)__double_as_longlong(v) == LS_TAB_EMPTY) == 0ull; };
+          if (!poll_until<0>(all_posted, WAIT_10US)) { giveup = 1; if (tid == 0) atomicAdd(&D.ctl->ls_giveups, 1); }
           if (!giveup) {
             double st = res[LS_GROUPS + 1];
             for (int l = 2; l < 2 * H; l++) {
@@ -787,8 +779,8 @@ __global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, in
   // there waits for it (inside a batch only: the first iteration of a batch is fed by k_begin, which pushes whatever the state is then)
   if (D.xch && begin_next) xch_push_robot<false>(D, 0, u, 3 * T, sm + L.gnet + (size_t)wg * 3 * T, 3 * T, tid, LS_THREADS);
 ticket:
-  if (h > 0 && begin_next) sig_acked();   // a helper's posts are performed before its ticket: begin_body's reset of the table cannot be overtaken by them
   if (begin_next) {
+    if (h > 0) sig_acked();   // a helper's posts are performed before its ticket: begin_body's reset of the table cannot be overtaken by them
     // No fence: nothing another block of THIS kernel writes is read here (gnorm and the counters come from earlier kernels;
     // what begin_body resets was consumed by every block before its ticket), and what is written here is read by later
     // kernels only.  The agent-scope atomic alone orders the tickets.  (An agent-scope release here would write back the
@@ -1010,10 +1002,11 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_coupled(Dev D, LsLayout L, in
   }
   if (!one_ctx) return;
   // the stores were performed before this wave arrives at the barrier; then the block's ticket
-  __builtin_amdgcn_s_waitcnt(0);
   __shared__ int s_last;
+  sig_acked();
   __syncthreads();
   if (tid == 0) s_last = atomicAdd(&D.ctl->ls_ticket, 1) == (int)gridDim.x - 1;
+  sig_sent();
   __syncthreads();
   if (!s_last) return;
   if (tid == 0) D.ctl->ls_ticket = 0;

@@ -617,18 +617,10 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
       // robot order, its pivot, the back substitution, the direction record.  Same operations in the same order, hence the same bits (TJ_C2_FOLD=0: the separate launch).
       double* oc = D.xcorner + (size_t)u * 4;
       if (tid == 0) { xf_store(oc, L[m * n + m]); xf_store(oc + 1, x0[m]); xf_store(oc + 2, g0[m]); xf_store(oc + 3, 0.0); }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0);
-      asm volatile("" ::: "memory");
+      sig_acked();
       if (tid == 0) __hip_atomic_fetch_add(&D.ctl->c2_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      {
-        const long long t_end = wall_clock64() + 500000;   // 5 ms: a logic error must not hang the device
-        while (__hip_atomic_load(&D.ctl->c2_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < D.U) {
-          if (wall_clock64() > t_end) { if (tid == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_PASS_TIMEOUT); break; }
-          __builtin_amdgcn_s_sleep(2);
-        }
-        asm volatile("" ::: "memory");
-      }
+      sig_sent();
+      if (!poll_until<2>([&] { return xf_load_i(&D.ctl->c2_cnt) >= D.U; }, WAIT_5MS)) wait_failed(D, ERR_LOOP_CAP | ERR_PASS_TIMEOUT);
       double* s_cstage = scr; double* s_red = scr + 64;   // (the scratch of the solve, >= 96 doubles and idle here: static arrays would push the 88-row system over the LDS limit)
       {
         double acc = 0;
@@ -743,14 +735,7 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
 // asynchronous solve: the gate in front of k_xsolve on the second queue (one wave, no LDS: it may sit there through the rest of the previous iteration)
 __global__ __launch_bounds__(64) void k_xs_gate(Dev D, int seq, int fault = 0) {
   if (fault) { if (threadIdx.x == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); return; }   // test hook (TJ_XS_FAULT): as if the wait below had run out
-  const int* w = D.xs_go();
-  const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;   // 2 s
-  wait_begin();
-  while (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq < 0) {
-    if (wall_clock64() > t_end) { if (threadIdx.x == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); break; }
-    __builtin_amdgcn_s_sleep(16);
-  }
-  wait_end();
+  if (!poll_until<16>([&] { return xf_load_i(D.xs_go()) - seq >= 0; }, WAIT_2S)) wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
 }
 
 // NREG = n when the system fits one row per lane (n = 9P-2 <= 61, P <= 7: the register factorisation inlined, size known at

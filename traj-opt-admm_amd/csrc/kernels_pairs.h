@@ -332,17 +332,10 @@ __device__ __forceinline__ void sep_self_solve_body(const Dev& D, int bid, int n
     const int epoch_now = D.ctl->epoch;
     if (head_start && bid < min(nwaves / 2, SPEC_CAP)) {
       unsigned long long tg = 0;
-      wait_begin();
-      {
-        const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;
-        for (;;) {
-          tg = __hip_atomic_load(D.spec_tag + bid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((int)(tg >> 32) == epoch_now) break;
-          if (wall_clock64() > t_end) { if (lane == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_XS_TIMEOUT); tg = ((unsigned long long)(unsigned)epoch_now << 32) | SPEC_KEY_NONE; break; }
-          __builtin_amdgcn_s_sleep(4);
-        }
+      if (!poll_until<4>([&] { tg = __hip_atomic_load(D.spec_tag + bid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (int)(tg >> 32) == epoch_now; }, WAIT_2S)) {
+        wait_failed(D, ERR_LOOP_CAP | ERR_XS_TIMEOUT);
+        tg = ((unsigned long long)(unsigned)epoch_now << 32) | SPEC_KEY_NONE;
       }
-      wait_end();
       const unsigned key = (unsigned)tg;
       const int tr = (int)(key & 0x1ff), p0 = (int)((key >> 9) & 0x7ff), q = (int)((key >> 20) & 0x7ff);
       if (key != SPEC_KEY_NONE && tr < D.S && p0 < D.U && q < D.U) {
@@ -394,17 +387,13 @@ __device__ __forceinline__ void sep_self_solve_body(const Dev& D, int bid, int n
     if (pass_on && bid >= np) {   // ---- consumer: the long solves, one per wave ----
       if (bid - np >= nc) return;
       TJ_TIC(D, K_SEP_SELF_SOLVE, 0);
-      const long long t_end = wall_clock64() + 500000 + 100ll * nwaves;   // 5 ms + 1 us per launched wave (a profiler or a shared GPU stretches a large launch): a logic error must not hang the device
+      long long t_end = 0;   // one deadline for every entry of this wave: 5 ms + 1 us per launched wave
       for (int i = bid - np;; i += nc) {
         unsigned long long e = 0;
-        bool have = false;
         if (i >= D.cap_work + PAIR_CONSUMERS_MAX) return;
-        for (;;) {
-          e = __hip_atomic_load(&D.pair_ovf_list[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((int)(e >> 32) == epoch) { have = true; break; }
-          if (wall_clock64() > t_end) { if (lane == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_PASS_TIMEOUT); break; }
-          __builtin_amdgcn_s_sleep(16);
-        }
+        const bool have = poll_until<16>([&] { e = __hip_atomic_load(&D.pair_ovf_list[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (int)(e >> 32) == epoch; },
+                                         t_end, WAIT_5MS + WAIT_SLACK * nwaves);
+        if (!have) wait_failed(D, ERR_LOOP_CAP | ERR_PASS_TIMEOUT);
         if (!have || (e & PAIR_OVF_STOP)) { TJ_TIC(D, K_SEP_SELF_SOLVE, 2); return; }
         if (i == bid - np) TJ_TIC(D, K_SEP_SELF_SOLVE, 1);
         const int tr = (int)(e & 0x1ff), p0 = (int)((e >> 9) & 0x7ff), q = (int)((e >> 20) & 0x7ff);   // 9 + 11 + 11 bits, bit 31 = PAIR_OVF_STOP

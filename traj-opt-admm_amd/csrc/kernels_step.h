@@ -213,13 +213,7 @@ __global__ __launch_bounds__(64) void k_xch_wait(Dev D, int kind) {
   if (done) return;
   const unsigned long long need = mine ? (unsigned long long)(pushed / (D.u1 - D.u0)) * (unsigned long long)D.owned_by(lane) : 0ull;
   if (ballot(got < need) == 0ull) return;
-  const long long t_end = wall_clock64() + XCH_TIMEOUT_TICKS;
-  for (;;) {
-    __builtin_amdgcn_s_sleep(4);
-    if (mine) got = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (ballot(got < need) == 0ull) return;
-    if (wall_clock64() > t_end) { if (lane == 0) atomicOr(&D.ctl->error, ERR_PEER_TIMEOUT); return; }
-  }
+  if (!poll_until<4>([&] { if (mine) got = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return ballot(got < need) == 0ull; }, WAIT_2S)) wait_failed(D, ERR_PEER_TIMEOUT);
 }
 
 constexpr int CCD_LDS_DOUBLES = 294 + (2 * FRONT_CAP + 128) / 2;   // info[146] kax[147] | fa fb cand
@@ -921,26 +915,15 @@ __device__ __forceinline__ void ccd_union_body(const Dev& D) {
     }
     __syncthreads();
   }
-  int any_act = 0;
-  {
-    const long long t_end = wall_clock64() + (D.xs_async ? XCH_TIMEOUT_TICKS : 500000 + 100ll * gridDim.x);   // 5 ms + 1 us per block of the launch: a logic error must not hang the device
-                                                                                                                // (asynchronous solve: the tiles themselves wait for units that wait for the other queue -- 2 s, like them)
-    for (;;) {
-      int v = lane < 16 ? __hip_atomic_load(&D.ctl->ccd_sub[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      v = __shfl(v, 0);
-      if ((v & 0xffff) == n_t) {
-        any_act = v >> 16;
-        // every selection block of THIS launch is in: take exactly what was observed back out, so that a launch that is repeated without a begin in between
-        // (tj_iterate_phase on the CCD phase twice, a re-run after an error) starts from zero instead of finding the counters full.  Not after a
-        // time-out: late blocks may still be adding (the next begin_body zeroes the words anyway).
-        if (lane < 16) { const int mine = __hip_atomic_load(&D.ctl->ccd_sub[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (mine) atomicSub(&D.ctl->ccd_sub[lane], mine); }
-        break;
-      }
-      if (wall_clock64() > t_end) { if (lane == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_PASS_TIMEOUT); break; }
-      __builtin_amdgcn_s_sleep(8);
-    }
-  }
+  int any_act = 0, v = 0;
+  // 5 ms + 1 us per block of the launch (asynchronous solve: the tiles themselves wait for units that wait for the other queue -- 2 s, like them)
+  if (poll_until<8>([&] { v = sum16(D.ctl->ccd_sub, 1); return (v & 0xffff) == n_t; }, D.xs_async ? WAIT_2S : WAIT_5MS + WAIT_SLACK * gridDim.x)) {
+    any_act = v >> 16;
+    // every selection block of THIS launch is in: take exactly what was observed back out, so that a launch that is repeated without a begin in between
+    // (tj_iterate_phase on the CCD phase twice, a re-run after an error) starts from zero instead of finding the counters full.  Not after a
+    // time-out: late blocks may still be adding (the next begin_body zeroes the words anyway).
+    if (lane < 16) { const int mine = xf_load_i(&D.ctl->ccd_sub[lane]); if (mine) atomicSub(&D.ctl->ccd_sub[lane], mine); }
+  } else wait_failed(D, ERR_LOOP_CAP | ERR_PASS_TIMEOUT);
   if (any_act > 0) ccd_self_seq_body<true>(D, M, false);   // (reads the pairs' count and keys with agent-scope loads)
   TJ_TIC(D, K_CCD, 2);
 }

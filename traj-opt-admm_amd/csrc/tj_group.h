@@ -65,18 +65,13 @@ __global__ __launch_bounds__(GROUP_FLAG_THREADS) void k_group_push_flag(const do
   __syncthreads();
   if ((int)threadIdx.x < n_peers) __hip_atomic_store(dst.flag[threadIdx.x], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-constexpr long long GROUP_FLAG_TIMEOUT_TICKS = 200000000ll;   // 2 s of the 100 MHz wall clock: a lost peer must not hang the device
-// flags: this rank's words, one per peer (already offset to the exchange's kind and parity)
+// flags: this rank's words, one per peer (already offset to the exchange's kind and parity).  Wave 0 waits for every peer's flag (lane p: peer p), the block behind it.
 __global__ __launch_bounds__(GROUP_FLAG_THREADS) void k_group_wait_unpack(double* dst, const double* rx, GroupPeers mine, int n_peers, unsigned long long seq, size_t own_off, size_t own_count, size_t total, Ctl* ctl) {
   __shared__ int s_lost;
-  if (threadIdx.x == 0) s_lost = 0;
-  __syncthreads();
-  if ((int)threadIdx.x < n_peers) {
-    const long long t_end = wall_clock64() + GROUP_FLAG_TIMEOUT_TICKS;
-    while (__hip_atomic_load(mine.flag[threadIdx.x], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
-      if (wall_clock64() > t_end) { atomicOr(&ctl->error, ERR_PEER_TIMEOUT); s_lost = 1; break; }
-      __builtin_amdgcn_s_sleep(8);
-    }
+  if (threadIdx.x < 64) {
+    const unsigned long long* f = (int)threadIdx.x < n_peers ? mine.flag[threadIdx.x] : nullptr;
+    const bool ok = poll_until<8>([&] { return ballot(f && __hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) == 0ull; }, WAIT_2S);
+    if (threadIdx.x == 0) { s_lost = !ok; if (!ok) atomicOr(&ctl->error, ERR_PEER_TIMEOUT); }
   }
   __syncthreads();
   if (s_lost) return;   // a peer's slice never arrived: leave the buffer as it is (the error bit fails the batch) rather than unpack stale data

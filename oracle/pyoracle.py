@@ -212,11 +212,11 @@ class Engine:
 class Prims:
     """Stateless known-answer primitives (GJK, k-DOP, planes, pair order, LLT)."""
 
-    def __init__(self, kind):
+    def __init__(self, kind, params=None):
         self.lib = C.CDLL(_PATHS[kind]); self.px = _PREFIX[kind]
         # both libraries keep parameters (offset, margin, k-DOP axes) in process-wide state that a
-        # setup call initialises with the shipped 3D.json values
-        Engine(kind, _dummy_scene())
+        # setup call initialises: the shipped 3D.json values, updated by `params`
+        Engine(kind, _dummy_scene(), params)
 
     def _f(self, name, restype=C.c_int):
         f = getattr(self.lib, self.px + name); f.restype = restype; return f

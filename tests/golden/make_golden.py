@@ -122,11 +122,12 @@ def make_prims():
     np.savez_compressed(os.path.join(HERE, "prims_kat.npz"), **d)
 
 
-def make_stages(name, scene, iters, keep, with_canon=True):
+def make_stages(name, scene, iters, keep, with_canon=True, params=None):
     """Per-iteration intermediates of the reference's own stage sequence, starting each kept
     iteration from the reference's state (so consumers can teacher-force).  with_canon=False leaves out the
-    order-free copy of the plane lists (large scenes: consumers sort `planes_raw` themselves)."""
-    e = Engine("ref", scene)
+    order-free copy of the plane lists (large scenes: consumers sort `planes_raw` themselves).  params: 3D.json
+    values other than the shipped ones (recorded, with the twin check, in the file)."""
+    e = Engine("ref", scene, params)
     rec = {"cloud_sum": np.array([scene["cloud"].sum(), np.abs(scene["cloud"]).sum()]), "waypoints": scene["waypoints"]}
     for it in range(iters):
         pre = e.get_state()
@@ -149,6 +150,9 @@ def make_stages(name, scene, iters, keep, with_canon=True):
             rec[k + "mid_spline"] = mid["spline"]; rec[k + "mid_piece_time"] = mid["piece_time"]
             for n_, v in post.items(): rec[k + "post_" + n_] = v
     rec["kept"] = np.array(sorted(keep))
+    if params is not None:
+        rec["params"] = param_array(scene, params)
+        rec.update(twin_check(scene, params, rec))
     np.savez_compressed(os.path.join(HERE, f"stages_{name}.npz"), **rec)
 
 
@@ -191,10 +195,10 @@ def coupled(scene):
     return sc
 
 
-def make_stages_coupled(name, scene, iters, keep):
+def make_stages_coupled(name, scene, iters, keep, params=None):
     """Coupled mode: planes, then update_spline (one reference function: arrowhead Newton system, CCD clamps,
     Armijo on the summed energy), then the slack/dual update."""
-    e = Engine("ref", scene)
+    e = Engine("ref", scene, params)
     rec = {"cloud_sum": np.array([scene["cloud"].sum(), np.abs(scene["cloud"]).sum()]), "waypoints": scene["waypoints"]}
     for it in range(iters):
         pre = e.get_state()
@@ -212,17 +216,20 @@ def make_stages_coupled(name, scene, iters, keep):
             rec[k + "mid_spline"] = mid["spline"]; rec[k + "mid_piece_time"] = mid["piece_time"]
             for n_, v in post.items(): rec[k + "post_" + n_] = v
     rec["kept"] = np.array(sorted(keep))
+    if params is not None:
+        rec["params"] = param_array(scene, params)
+        rec.update(twin_check(scene, params, rec))
     np.savez_compressed(os.path.join(HERE, f"stages_{name}.npz"), **rec)
 
 
-def make_e2e(name, scene, max_iter=200, stop=1e-2):
+def make_e2e(name, scene, max_iter=200, stop=1e-2, params=None):
     """The unmodified reference to the mains' stop test: final state, and Energy_admm::spline_energy of every robot at the final
     state against the separating planes OF that state (the iteration's own plane lists are locals of optimization_decouple; the
     stage entry rebuilds them).  A second run with the way points moved by ONE ULP records how far the reference moves its own
     final control points (`spline_env`) and energies (`energy_env`): the floor under any end-to-end tolerance."""
     def run(pert):
         sc = dict(scene); sc["waypoints"] = scene["waypoints"] * (1.0 + pert)
-        e = Engine("ref", sc)
+        e = Engine("ref", sc, params)
         gn = []
         for it in range(max_iter):
             g = e.iterate(); gn.append(g)
@@ -233,7 +240,8 @@ def make_e2e(name, scene, max_iter=200, stop=1e-2):
         return gn, st, np.array([e.spline_energy(u) for u in range(scene["U"])])
     gn, st, energy = run(0.0)
     _, st_p, energy_p = run(2.3e-16)
-    np.savez_compressed(os.path.join(HERE, f"e2e_{name}.npz"), gnorm_hist=np.array(gn), iters=np.array(len(gn)), final_energy=energy,
+    extra = {} if params is None else {"params": param_array(scene, params)}
+    np.savez_compressed(os.path.join(HERE, f"e2e_{name}.npz"), **extra, gnorm_hist=np.array(gn), iters=np.array(len(gn)), final_energy=energy,
                         energy_env=np.array(np.max(np.abs(energy_p - energy) / np.abs(energy))),
                         spline_env=np.array(np.max(np.abs(st_p["spline"] - st["spline"])) / np.max(np.abs(st["spline"]))),
                         cloud_sum=np.array([scene["cloud"].sum(), np.abs(scene["cloud"]).sum()]), **{"final_" + k: v for k, v in st.items()})
@@ -474,6 +482,37 @@ def _flat_obs_cache(cache):
     return n, ids.astype(np.int32), cd
 
 
+def make_optplane_stages(name, scene, iters, keep, params=None):
+    """`optimal_plane:1`: the reference's plane stage with its persistent tables before / after, at kept iterations"""
+    e = Engine("ref", scene, params); e.set_optimal_plane(True)
+    rec = {"cloud_sum": np.array([scene["cloud"].sum(), np.abs(scene["cloud"]).sum()])}
+    for it in range(iters):
+        pre = e.get_state()
+        pre_cache = e.get_obs_cache() if scene["mode"] == 0 else e.get_pair_cache()
+        counts, planes = e.stage_planes()
+        post_cache = e.get_obs_cache() if scene["mode"] == 0 else e.get_pair_cache()
+        if scene["mode"] == 2:
+            e.stage_update_spline()
+        else:
+            e.stage_direction(); e.stage_steps(); e.stage_linesearch()
+        e.stage_slack()
+        e.iters += 1
+        if it in keep:
+            k = f"it{it}_"
+            for n_, v in pre.items(): rec[k + "pre_" + n_] = v
+            rec[k + "counts"] = counts; rec[k + "planes"] = canon(counts, planes)
+            for tag, cache in (("pre", pre_cache), ("post", post_cache)):
+                if scene["mode"] == 0:
+                    n, ids, cd = _flat_obs_cache(cache)
+                    rec[k + tag + "_cache_n"] = n; rec[k + tag + "_cache_ids"] = ids; rec[k + tag + "_cache_cd"] = cd
+                else:
+                    rec[k + tag + "_cache_on"] = cache[0]; rec[k + tag + "_cache_cd"] = cache[1]
+    rec["kept"] = np.array(sorted(keep))
+    if params is not None:
+        rec["params"] = param_array(scene, params)
+    np.savez_compressed(os.path.join(HERE, f"optplane_stages_{name}.npz"), **rec)
+
+
 def make_optplane():
     """`optimal_plane:1`: known answers of Optimal_plane::optimal_cd / self_optimal_cd, the persistent tables and the
     plane lists of the reference's plane stage at kept iterations (teacher-forcing data), and converged runs."""
@@ -510,31 +549,7 @@ def make_optplane():
 
     for name, scene, iters, keep in (("tiny_single", pkg_scenes.tiny(0, n_points=3000), 12, {0, 1, 4, 8, 11}), ("tiny_multi", pkg_scenes.tiny(1), 10, {0, 1, 3, 6, 9}),
                                      ("tiny_multi_coupled", coupled(pkg_scenes.tiny(1)), 8, {0, 1, 4, 7})):
-        e = Engine("ref", scene); e.set_optimal_plane(True)
-        rec = {"cloud_sum": np.array([scene["cloud"].sum(), np.abs(scene["cloud"]).sum()])}
-        for it in range(iters):
-            pre = e.get_state()
-            pre_cache = e.get_obs_cache() if scene["mode"] == 0 else e.get_pair_cache()
-            counts, planes = e.stage_planes()
-            post_cache = e.get_obs_cache() if scene["mode"] == 0 else e.get_pair_cache()
-            if scene["mode"] == 2:
-                e.stage_update_spline()
-            else:
-                e.stage_direction(); e.stage_steps(); e.stage_linesearch()
-            e.stage_slack()
-            e.iters += 1
-            if it in keep:
-                k = f"it{it}_"
-                for n_, v in pre.items(): rec[k + "pre_" + n_] = v
-                rec[k + "counts"] = counts; rec[k + "planes"] = canon(counts, planes)
-                for tag, cache in (("pre", pre_cache), ("post", post_cache)):
-                    if scene["mode"] == 0:
-                        n, ids, cd = _flat_obs_cache(cache)
-                        rec[k + tag + "_cache_n"] = n; rec[k + tag + "_cache_ids"] = ids; rec[k + tag + "_cache_cd"] = cd
-                    else:
-                        rec[k + tag + "_cache_on"] = cache[0]; rec[k + tag + "_cache_cd"] = cache[1]
-        rec["kept"] = np.array(sorted(keep))
-        np.savez_compressed(os.path.join(HERE, f"optplane_stages_{name}.npz"), **rec)
+        make_optplane_stages(name, scene, iters, keep)
 
     for name, scene in (("tiny_single", pkg_scenes.tiny(0, n_points=3000)), ("tiny_multi", pkg_scenes.tiny(1))):
         e = Engine("ref", scene); e.set_optimal_plane(True)
@@ -604,7 +619,160 @@ def make_coupled_long():
     np.savez_compressed(os.path.join(HERE, "coupled_long_kat.npz"), **rec)
 
 
+# ---- non-default 3D.json values -----------------------------------------------------------------------------------------------
+# The shipped values pair up (margin == offset, vel_limit == acc_limit, kt == 1, lambda == 1/mu), so a kernel that swaps or drops
+# one of them computes the same numbers.  A and B break every pair, in opposite directions where there is one; with piece_time0 = 20
+# the solver shortens the pieces until velocity and acceleration records enter the barrier range in the later kept iterations (the
+# twin check below records that they do).  tests/test_oracle_params.py holds the same two dicts and checks them against every file.
+PARAMS_A = dict(res=8, lam=20.0, margin=0.14, offset=0.06, mu=0.25, vel_limit=1.2, acc_limit=2.5, kt=2.5, piece_time0=20.0, stop=1e-2)
+PARAMS_B = dict(res=8, lam=4.0, margin=0.06, offset=0.115, mu=0.05, vel_limit=0.9, acc_limit=0.8, kt=0.4, piece_time0=20.0, stop=1e-2)
+PARAM_FIELDS = ("lam", "margin", "offset", "mu", "vel_limit", "acc_limit", "ks", "kt", "piece_time0", "res")
+TWIN_SCALED = ("lam", "margin", "offset", "mu", "vel_limit", "acc_limit", "kt")
+TWIN_OUTPUTS = ("planes", "gn", "direction", "steps", "armijo", "mid", "post")
+STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
+
+
+def param_array(scene, params):
+    p = dict(pkg_scenes.DEFAULT_PARAMS); p.update(params); p["ks"] = scene["ks"]
+    return np.array([float(p[k]) for k in PARAM_FIELDS])
+
+
+def twin_variants(params):
+    """the parameter sets a swapped, inverted, dropped or slightly wrong kernel argument would amount to"""
+    p = dict(params)
+    out = [("swap_margin_offset", dict(p, margin=p["offset"], offset=p["margin"])),
+           ("swap_vel_acc", dict(p, vel_limit=p["acc_limit"], acc_limit=p["vel_limit"])),
+           ("lam_mu_inverse", dict(p, lam=1.0 / p["mu"], mu=1.0 / p["lam"])),
+           ("kt_one", dict(p, kt=1.0))]
+    for k in TWIN_SCALED:
+        out.append((f"scale_{k}", dict(p, **{k: p[k] * (1.0 + 1e-3)})))
+    return out
+
+
+def twin_check(scene, params, rec):
+    """Runs the unmodified reference under every twin variant on the fixture's kept iterations, teacher-forced the way the tests
+    feed a solver (pre state in; the fixture's mid state into the slack update), and records per variant and output the largest
+    difference from the fixture, normalised as the tests normalise it: planes (abs, inf when the counts differ), gn (rel. to
+    max(1, |gn|); coupled: gnorm), direction (abs, with t_direction), steps (abs, both CCD clamps), armijo (abs; decoupled only),
+    mid (abs, control points and piece_time after the update), post (rel. to max(1, |x|), every state array)."""
+    names, diffs = [], []
+    for name, vp in twin_variants(params):
+        e = Engine("ref", scene, vp)
+        worst = dict.fromkeys(TWIN_OUTPUTS, 0.0)
+        if scene["mode"] == 2:
+            worst["direction"] = worst["steps"] = worst["armijo"] = np.nan
+        elif scene["mode"] == 0:
+            worst["armijo"] = np.nan
+
+        def upd(o, v):     # a NaN where the fixture has a number fails every bar: recorded as inf
+            worst[o] = max(worst[o], np.inf if np.isnan(v) else float(v))
+        for it in rec["kept"]:
+            k = f"it{it}_"
+            e.set_state({n: rec[k + "pre_" + n] for n in STATE})
+            counts, planes = e.stage_planes()
+            want = rec[k + "planes"] if k + "planes" in rec else canon(rec[k + "counts"], rec[k + "planes_raw"])
+            if np.array_equal(counts, rec[k + "counts"]):
+                got = canon(counts, planes)
+                upd("planes", np.max(np.where(np.isnan(got) & np.isnan(want), 0.0, np.abs(got - want)), initial=0.0))
+            else:
+                upd("planes", np.inf)
+            if scene["mode"] == 2:
+                gnorm, _ = e.stage_update_spline()
+                upd("gn", abs(gnorm - rec[k + "gnorm"]) / max(1.0, float(rec[k + "gnorm"])))
+            else:
+                d = e.stage_direction()
+                upd("gn", np.max(np.abs(d["gn"] - rec[k + "gn"])) / max(1.0, np.abs(rec[k + "gn"]).max()))
+                upd("direction", max(np.max(np.abs(d["direction"] - rec[k + "direction"])), np.max(np.abs(d["t_direction"] - rec[k + "t_direction"]))))
+                a, b = e.stage_steps()
+                upd("steps", max(np.max(np.abs(a - rec[k + "step_self"])), np.max(np.abs(b - rec[k + "step_pos"]))))
+                arm = e.stage_linesearch()
+                if scene["mode"] == 1:
+                    upd("armijo", np.max(np.abs(arm - rec[k + "step_armijo"])))
+            st = e.get_state()
+            upd("mid", max(np.max(np.abs(st["spline"] - rec[k + "mid_spline"])), np.max(np.abs(st["piece_time"] - rec[k + "mid_piece_time"]))))
+            e.set_state({n: (rec[k + "mid_" + n] if n in ("spline", "piece_time") else rec[k + "pre_" + n]) for n in STATE})
+            e.stage_slack()
+            st = e.get_state()
+            for n in STATE:
+                upd("post", np.max(np.abs(st[n] - rec[k + "post_" + n])) / max(1.0, np.abs(rec[k + "post_" + n]).max()))
+        names.append(name); diffs.append([worst[o] for o in TWIN_OUTPUTS])
+    return {"twin_names": np.array(names), "twin_outputs": np.array(TWIN_OUTPUTS), "twin_diff": np.array(diffs)}
+
+
+def params_kat_edges(scene, seed):
+    """seeded straight edges through the `hard` scene's volume and 12 prior edges near its robot layer (shared with the tests)"""
+    rng = np.random.default_rng(seed)
+    n = 3000
+    a = rng.uniform(-4.5, 4.5, size=(n, 3)); a[:, 2] = rng.uniform(-0.7, 1.2, size=n)
+    b = a + rng.normal(size=(n, 3)) * rng.uniform(0.02, 1.5, size=(n, 1))
+    prior = np.concatenate([rng.uniform(-3, 3, size=(12, 3)), rng.uniform(-3, 3, size=(12, 3))], axis=1)
+    prior[:, 2] = prior[:, 5] = rng.uniform(0, 0.5, size=12)
+    return np.concatenate([a, b], axis=1), prior
+
+
+def make_prims_params():
+    """Known answers of the parameter-dependent primitives under A and B: the pair plane with the offset Newton (plane_self, refine),
+    Optimal_plane::optimal_cd / self_optimal_cd, and the planner's motion validator at d = offset + margin/2 on the `hard` scene"""
+    rec = {}
+    for tag, params in (("A", PARAMS_A), ("B", PARAMS_B)):
+        off, mar = params["offset"], params["margin"]
+        rng = np.random.default_rng(20261016 + ord(tag))
+        pr = Prims("ref", params)
+        P, Q, ps = [], [], []
+        for i in range(600):          # hull pairs inside and around the pair barrier's range offset + 2 margin
+            a = rand_hull(rng)
+            gap = rng.uniform(0.5 * off, off + 3 * mar)
+            dirn = rng.normal(0, 1, 3); dirn /= np.linalg.norm(dirn)
+            far = a[np.argmax(a @ dirn)]
+            b = rand_hull(rng, centre=far + dirn * (gap + 0.35))
+            ok, cd = pr.plane_self(a, b, off + 2 * mar, refine=True)
+            P.append(a); Q.append(b); ps.append(np.concatenate([[float(ok)], cd if ok else np.zeros(4)]))
+        rec[f"{tag}_P"] = np.array(P); rec[f"{tag}_Q"] = np.array(Q); rec[f"{tag}_plane_self"] = np.array(ps)
+        P_o, q_o, in_o, out_o, P_s, Q_s, in_s, out_s = [], [], [], [], [], [], [], []
+        while len(P_o) < 200:         # as make_optplane, at this set's distances
+            ctr = rng.normal(size=3); Ph = ctr + 0.3 * rng.normal(size=(6, 3))
+            dirn = rng.normal(size=3); dirn /= np.linalg.norm(dirn)
+            q = ctr + dirn * (0.9 + rng.random() * 0.3)
+            ok, cd = pr.plane_obs(Ph, q, off + mar + 5.0)
+            out = pr.optimal_cd(Ph, q, cd) if ok else None
+            if ok and np.isfinite(out).all():
+                P_o.append(Ph); q_o.append(q); in_o.append(cd); out_o.append(out)
+        while len(P_s) < 200:
+            ctr = rng.normal(size=3); Ph = ctr + 0.3 * rng.normal(size=(6, 3))
+            dirn = rng.normal(size=3); dirn /= np.linalg.norm(dirn)
+            Qh = ctr + dirn * (1.2 + rng.random() * 0.3) + 0.3 * rng.normal(size=(6, 3))
+            ok, cd = pr.plane_self(Ph, Qh, off + 2 * mar + 5.0, refine=False)
+            out = pr.self_optimal_cd(Ph, Qh, cd) if ok else None
+            if ok and np.isfinite(out).all():
+                P_s.append(Ph); Q_s.append(Qh); in_s.append(cd); out_s.append(out)
+        rec.update({f"{tag}_P_obs": np.array(P_o), f"{tag}_q_obs": np.array(q_o), f"{tag}_in_obs": np.array(in_o), f"{tag}_out_obs": np.array(out_o),
+                    f"{tag}_P_self": np.array(P_s), f"{tag}_Q_self": np.array(Q_s), f"{tag}_in_self": np.array(in_s), f"{tag}_out_self": np.array(out_s)})
+        scene = pkg_scenes.hard()
+        edges, prior = params_kat_edges(scene, 7 + ord(tag))
+        e = Engine("ref", scene, params)
+        rec[f"{tag}_edges"] = edges; rec[f"{tag}_prior"] = prior
+        rec[f"{tag}_hit_cloud"] = e.edge_collision(edges); rec[f"{tag}_hit_all"] = e.edge_collision(edges, prior)
+        rec[f"{tag}_params"] = param_array(scene, params)
+        rec["cloud_sum"] = np.array([scene["cloud"].sum(), np.abs(scene["cloud"]).sum()])
+    np.savez_compressed(os.path.join(HERE, "prims_params_kat.npz"), **rec)
+
+
+def make_params():
+    """every fixture at the non-default sets A and B (tests/test_oracle_params.py, tests/test_gpu_params.py)"""
+    for tag, params, iters, keep in (("A", PARAMS_A, 8, {0, 3, 5, 7}), ("B", PARAMS_B, 10, {0, 4, 7, 9})):
+        make_stages(f"hard_params{tag}", pkg_scenes.hard(), iters, keep, params=params)
+        make_stages(f"hard_single_params{tag}", hard_single(), iters, keep, params=params)
+        make_stages_coupled(f"hard_coupled_params{tag}", coupled(pkg_scenes.hard()), iters, keep, params=params)
+    make_optplane_stages("tiny_multi_paramsA", pkg_scenes.tiny(1), 8, {0, 1, 4, 7}, params=PARAMS_A)
+    make_optplane_stages("tiny_single_paramsA", pkg_scenes.tiny(0, n_points=3000), 8, {0, 1, 4, 7}, params=PARAMS_A)
+    make_prims_params()
+    make_e2e("scn_b_paramsA", pkg_scenes.scn_b(), params=PARAMS_A)
+
+
 if __name__ == "__main__":
+    if "--params-only" in sys.argv:
+        make_params()
+        sys.exit(0)
     if "--coupled-long-only" in sys.argv:
         make_coupled_long()
         sys.exit(0)

@@ -15,7 +15,11 @@ def test_coupled_stages_teacher_forced_vs_reference(pkg, scenes):
     g = gold("stages_hard_coupled.npz")
     scene = scene_by_name(scenes, "hard_coupled")
     check_scene_matches_fixture(scene, g)
-    s = pkg.Solver(scene, stop=0.0)
+    _coupled_teacher_forced(pkg, scene, g)
+
+
+def _coupled_teacher_forced(pkg, scene, g, params=None):
+    s = pkg.Solver(scene, params=params, stop=0.0)
     for it in g["kept"]:
         k = f"it{it}_"
         s.set_state({n: g[k + "pre_" + n] for n in STATE})

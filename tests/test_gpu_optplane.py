@@ -86,7 +86,11 @@ def test_device_plane_refinement_known_answers(katsolver):
 def test_persistent_plane_stage_teacher_forced_vs_reference(pkg, scenes, name):
     g = gold(f"optplane_stages_{name}.npz"); scene = _scene(scenes, name)
     check_scene_matches_fixture(scene, g)
-    s = pkg.Solver(scene, stop=0.0, optimal_plane=1)
+    _persistent_plane_stage(pkg, scene, g, name)
+
+
+def _persistent_plane_stage(pkg, scene, g, name, params=None):
+    s = pkg.Solver(scene, params=params, stop=0.0, optimal_plane=1)
     diffs = []   # every refined plane entry's distance from the reference's, all kept iterations
     for it in g["kept"]:
         k = f"it{it}_"

@@ -127,10 +127,10 @@ def test_device_llt_and_min_eigenvalue(katsolver):
     assert (np.abs(out[:, 1] - g["min_eig"]) <= 1e-12 * np.maximum(1.0, scale)).all()
 
 
-def _teacher_forced(pkg, scene, g, tol_dir=1e-11):
+def _teacher_forced(pkg, scene, g, tol_dir=1e-11, params=None):
     """tolerances = ~10x the largest difference observed against the reference's vectors (TJ_PRINT_OBSERVED=1 prints them:
     direction 1.5e-12 on tiny / SCN-C and 1.6e-11 on the ill-conditioned `hard` scene, |g| 5e-15 relative, slack/dual 7e-14)"""
-    s = pkg.Solver(scene, stop=0.0)
+    s = pkg.Solver(scene, params=params, stop=0.0)
     seen = dict(planes=0.0, direction=0.0, mid=0.0, gn=0.0, post=0.0)   # largest differences met (TJ_PRINT_OBSERVED=1 prints them)
     for it in g["kept"]:
         k = f"it{it}_"

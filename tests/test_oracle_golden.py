@@ -82,7 +82,12 @@ def test_stages_teacher_forced(scenes, name):
     g = gold(f"stages_{name}.npz")
     scene = scene_by_name(scenes, name)
     check_scene_matches_fixture(scene, g)
-    e = Engine("port", scene)
+    port_teacher_forced(scene, g)
+
+
+def port_teacher_forced(scene, g, params=None):
+    """the port through the kept iterations of a decoupled / single-UAV stage fixture, each stage started from the reference's state"""
+    e = Engine("port", scene, params)
     for it in g["kept"]:
         k = f"it{it}_"
         e.set_state({n: g[k + "pre_" + n] for n in ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")})
@@ -336,7 +341,11 @@ def test_coupled_stages_teacher_forced(scenes):
     g = gold("stages_hard_coupled.npz")
     scene = scene_by_name(scenes, "hard_coupled")
     check_scene_matches_fixture(scene, g)
-    e = Engine("port", scene)
+    port_coupled_teacher_forced(scene, g)
+
+
+def port_coupled_teacher_forced(scene, g, params=None):
+    e = Engine("port", scene, params)
     for it in g["kept"]:
         k = f"it{it}_"
         e.set_state({n: g[k + "pre_" + n] for n in STATE})

@@ -41,10 +41,15 @@ def test_oracle_plane_refinement_known_answers_bit_exact():
 
 @pytest.mark.parametrize("name", ["tiny_single", "tiny_multi", "tiny_multi_coupled"])
 def test_oracle_persistent_plane_stage_bit_exact(scenes, name):
-    from oracle.pyoracle import Engine
     g = gold(f"optplane_stages_{name}.npz"); scene = _scene(scenes, name)
     check_scene_matches_fixture(scene, g)
-    e = Engine("port", scene); e.set_optimal_plane(True)
+    port_persistent_plane_stage(scene, g)
+
+
+def port_persistent_plane_stage(scene, g, params=None):
+    """the port's plane stage with its persistent tables, bit for bit, through the kept iterations of an optplane_stages fixture"""
+    from oracle.pyoracle import Engine
+    e = Engine("port", scene, params); e.set_optimal_plane(True)
     for it in g["kept"]:
         k = f"it{it}_"
         e.set_state({n: g[k + "pre_" + n] for n in STATE})

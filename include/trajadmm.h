@@ -181,6 +181,37 @@ int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_ar
  * separating planes of the last iteration (the lists the last tj_iterate built): energy[uav_num], robots of other ranks 0.
  * The value the line search calls E(x); the mains do not print it, parity tests compare it with the reference's. */
 int tj_get_energy(tj_ctx* c, double* energy);
+/* ---- tj_audit: is the trajectory the context holds collision-free and inside its limits?  A read-only query on the device
+ * (csrc/kernels_audit.h); the reference never reports these numbers.  For every OWNED robot (robots of other ranks: all-zero records):
+ *   obs_clearance   min over the robot's S segments and ALL obstacle primitives (points of tj_set_cloud, triangles of tj_set_mesh) of the GJK
+ *                   distance |v| between the segment's 6-point hull and the primitive -- the quantity Separate::opengjk (Separate.h:107-151) and
+ *                   the CCD clamp (Step.h:83-97) compare with their ranges -- searched up to `range`: min(range, exact minimum), never a sample.
+ *                   obs_segment / obs_index: where it is attained (index as given to tj_set_cloud / face index of tj_set_mesh; equal distances:
+ *                   the smallest (segment, index)); -1, -1 and obs_clearance == range when nothing is closer than range.  0.0 = a hull touches.
+ *   pair_clearance  min over segments tr and robots q != u of the GJK distance between the hulls of (u, tr) and (q, tr): the SAME-SEGMENT pairing
+ *                   of separate_self / self_step (Optimization3D_multi.h:246-259, Step.h:196-208).  Decoupled robots carry their own piece_time,
+ *                   so this is the solver's own pairing, not a distance at equal flight times.  pair_segment / pair_robot as above (smallest
+ *                   (segment, q)); single-UAV mode: range, -1, -1.  A sharded context (world > 1) reads the other ranks' control points as its
+ *                   last exchange left them; tj_group_audit reads every robot's from its owner.
+ *   speed, accel    max over segments and j of |order (P[j+1] - P[j])| / (weight piece_time) and
+ *                   |order (order - 1) (P[j+2] - 2 P[j+1] + P[j])| / (weight^2 piece_time^2): what bound_energy subtracts from vel_limit / acc_limit
+ *                   (Energy_admm.h:131-165), in the line search's association; speed_segment / accel_segment: where (the smallest on ties).
+ *   duration        piece_num * piece_time, log_data's "ccd time".
+ *   flags           TJ_AUDIT_OBS_CONTACT obs_clearance <= offset, TJ_AUDIT_PAIR_CONTACT pair_clearance <= offset (the reference's CCD treats such a
+ *                   state as in contact), TJ_AUDIT_SPEED speed >= vel_limit, TJ_AUDIT_ACCEL accel >= acc_limit (bound_energy returns infinity).
+ * range <= 0: the solver's own plane range offset + 2 * margin.  seg_obs / seg_pair (may be NULL): the per-segment minima [uav_num][S] (range where
+ * nothing is closer; rows of other ranks 0).  Valid any time after tj_init_state -- straight after it included, and without obstacles.  Changes no
+ * solver state, statistics or launch count.  A walk whose frontier overflows is TJ_ERR_CAPACITY (lower `range`), never a smaller answer. */
+enum { TJ_AUDIT_OBS_CONTACT = 1, TJ_AUDIT_PAIR_CONTACT = 2, TJ_AUDIT_SPEED = 4, TJ_AUDIT_ACCEL = 8 };
+typedef struct tj_audit_robot {
+  double obs_clearance;  int obs_segment, obs_index;
+  double pair_clearance; int pair_segment, pair_robot;
+  double speed, accel;   int speed_segment, accel_segment;
+  double duration;
+  int flags, reserved;
+} tj_audit_robot;
+int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);
+int tj_audit_record_size(void);   /* sizeof(tj_audit_robot), for bindings that mirror the record */
 /* teacher forcing of the CCD / line-search stages: overwrite robot u's search direction record (direction T x 3 column-major) */
 int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_direction, double wolfe, double gn);
 
@@ -332,6 +363,7 @@ int tj_group_set_mesh(tj_group* g, const double* vertices, int n_vertices, const
 int tj_group_init_state(tj_group* g, const double* waypoints, double piece_time0);
 int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, int* converged);   /* like tj_iterate */
 int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, double* p_lambda, double* t_slack, double* t_lambda, double* piece_time);   /* from u's owner */
+int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);   /* tj_audit of every robot by its owner, against every robot's control points as its owner holds them: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */
 /* event-timed cost of one exchange of each buffer kind (microseconds, slowest rank's average over `reps`): us[5], kinds 2..4

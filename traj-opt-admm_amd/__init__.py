@@ -30,6 +30,7 @@ EXPORTS = [
     "tj_group_create", "tj_group_destroy", "tj_group_size", "tj_group_ctx", "tj_group_last_error", "tj_group_set_cloud", "tj_group_set_mesh",
     "tj_group_transport", "tj_group_set_transport", "tj_group_profile_exchange", "tj_rccl_available", "tj_group_rccl_ranks",
     "tj_group_init_state", "tj_group_iterate", "tj_group_get_state",
+    "tj_audit", "tj_audit_record_size", "tj_group_audit",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -48,6 +49,30 @@ class TjStats(C.Structure):
                                              "planes_self", "energy_evals", "pair_tests", "llt_fail_piece", "llt_fail_robot", "newton_iters", "pair_solves")] + \
                [("order_ambiguous", C.c_int), ("error_bits", C.c_int), ("order_unresolved", C.c_int), ("head_starts", C.c_int), ("gjk_max_sum", C.c_ulonglong),
                 ("ls_giveups", C.c_int), ("ls_helper_timeouts", C.c_int), ("async_fallbacks", C.c_int)]
+
+
+class TjAuditRobot(C.Structure):
+    """mirror of tj_audit_robot (include/trajadmm.h); tj_audit_record_size() is its sizeof on the C side"""
+    _fields_ = [("obs_clearance", C.c_double), ("obs_segment", C.c_int), ("obs_index", C.c_int),
+                ("pair_clearance", C.c_double), ("pair_segment", C.c_int), ("pair_robot", C.c_int),
+                ("speed", C.c_double), ("accel", C.c_double), ("speed_segment", C.c_int), ("accel_segment", C.c_int),
+                ("duration", C.c_double), ("flags", C.c_int), ("reserved", C.c_int)]
+
+
+AUDIT_FLAGS = dict(obs_contact=1, pair_contact=2, speed=4, accel=8)
+
+
+def _audit(call, U, S, range, per_segment):
+    """shared by Solver.audit / Group.audit: call(range, records, seg_obs, seg_pair) -> dict of numpy arrays [U] (+ [U][S])"""
+    rec = (TjAuditRobot * U)()
+    so = np.zeros((U, S)) if per_segment else None
+    sp = np.zeros((U, S)) if per_segment else None
+    call(C.c_double(0.0 if range is None else float(range)), rec, _d(so) if per_segment else None, _d(sp) if per_segment else None)
+    out = {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32)
+           for n, t in TjAuditRobot._fields_ if n != "reserved"}
+    if per_segment:
+        out["seg_obs"], out["seg_pair"] = so, sp
+    return out
 
 
 class TrajAdmmError(RuntimeError):
@@ -454,6 +479,12 @@ class Solver:
         self._check(self.lib.tj_get_energy(self._ctx, _d(e)))
         return e
 
+    def audit(self, range=None, per_segment=False):
+        """tj_audit: per robot obstacle / robot-pair clearance (GJK hull distances up to `range`; None = offset + 2 * margin) with where they
+        are attained, peak speed / acceleration against the limits, duration and the flag word (AUDIT_FLAGS); robots of other ranks are zero.
+        per_segment=True adds seg_obs / seg_pair [U][S].  Read-only, valid straight after construction."""
+        return _audit(lambda r, rec, so, sp: self._check(self.lib.tj_audit(self._ctx, r, rec, so, sp)), self.U, self.S, range, per_segment)
+
     def build_info(self):
         ms, dev = C.c_double(), C.c_int()
         self._check(self.lib.tj_get_build_info(self._ctx, C.byref(ms), C.byref(dev)))
@@ -559,6 +590,10 @@ class Group:
                                                     _d(st["t_slack"][u]), _d(st["t_lambda"][u]), C.byref(pt)))
             st["piece_time"][u] = pt.value
         return st
+
+    def audit(self, range=None, per_segment=False):
+        """tj_group_audit: Solver.audit of every robot from the rank that owns it (bitwise one context's)"""
+        return _audit(lambda r, rec, so, sp: self._check(self.lib.tj_group_audit(self._g, r, rec, so, sp)), self.U, self.S, range, per_segment)
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

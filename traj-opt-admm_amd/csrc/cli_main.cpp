@@ -13,6 +13,8 @@
 // --batch N iterations per device batch (the stop test runs on the device before every iteration),
 // --triangles (or the optional key "triangles":1 in 3D.json): obstacles are the TRIANGLES of the OBJ (`f` lines, tj_set_mesh)
 // instead of its vertices as a point cloud.
+// --audit [RANGE]: after the run (and after the "ccd len:" lines) one line per robot from tj_audit / tj_group_audit -- obstacle and robot-pair clearance
+// (searched up to RANGE; default offset + 2 * margin), peak speed and acceleration, duration, flag word.  The result file is unchanged.
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
 #include <chrono>
@@ -27,9 +29,10 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
+  bool audit = false; double audit_range = 0;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -38,6 +41,7 @@ int main(int argc, char** argv) {
     else if (a == "--dump-state" && i + 1 < argc) dump = argv[++i];
     else if (a == "--sample-traj" && i + 1 < argc) sample_file = argv[++i];
     else if (a == "--triangles") triangles = true;
+    else if (a == "--audit") { audit = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_range = atof(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -150,6 +154,17 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k + 2 < smp.size(); k += 3) sf << u << " " << (k / 3) * dt << " " << smp[k] << " " << smp[k + 1] << " " << smp[k + 2] << "\n";
       }
       (void)whole_len;
+    }
+    if (audit) {
+      std::vector<tj_audit_robot> rec(U);
+      chk(group ? tj_group_audit(grp, audit_range, rec.data(), nullptr, nullptr) : tj_audit(ctx, audit_range, rec.data(), nullptr, nullptr), "tj_audit");
+      std::cout.precision(17);
+      for (int u = 0; u < U; u++) {
+        const tj_audit_robot& r = rec[u];
+        std::cout << "audit uav " << u << " obs " << r.obs_clearance << " seg " << r.obs_segment << " id " << r.obs_index << " pair " << r.pair_clearance << " seg " << r.pair_segment
+                  << " uav " << r.pair_robot << " speed " << r.speed << " seg " << r.speed_segment << " accel " << r.accel << " seg " << r.accel_segment << " time " << r.duration
+                  << " flags " << r.flags << std::endl;
+      }
     }
     if (!dump.empty()) {
       std::ofstream df(dump);

@@ -31,6 +31,7 @@
 #endif
 #include "kernels_plan.h"
 #include "kernels_bvh.h"
+#include "kernels_audit.h"
 
 using namespace tj;
 
@@ -87,6 +88,9 @@ struct tj_ctx {
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
+  // tj_audit's own buffers, allocated by its first call (kernels_audit.h): rows [U][S], records [U], a control block for the walk's overflow bit, the control nets a group
+  // hands in; audit_order (sorted primitive -> caller's index) belongs to the obstacle set and goes with it (cloud_allocs)
+  AuditArgs audit{}; tj_audit_robot* audit_out = nullptr; Ctl* audit_ctl = nullptr; double* audit_net = nullptr; int* audit_order = nullptr;
 };
 
 // EVERY environment switch of the library is read through this one function (tj_group.h included): TJ_TUNE="KEY=value,KEY=value" or, equivalently, TJ_KEY=value
@@ -885,6 +889,7 @@ int set_obstacles(tj_ctx* c, const double* verts, int n, int prim) {
   for (void* p : c->cloud_allocs) hipFree(p);
   c->cloud_allocs.clear();
   c->cloud_order.clear();
+  c->audit_order = nullptr;
   if (n > 0) {
     for (int k = 0; k < 3; k++) { c->cloud_lo[k] = INFINITY; c->cloud_hi[k] = -INFINITY; }
     for (size_t i = 0; i < (size_t)n * prim; i++) for (int k = 0; k < 3; k++) { c->cloud_lo[k] = std::min(c->cloud_lo[k], verts[3 * i + k]); c->cloud_hi[k] = std::max(c->cloud_hi[k], verts[3 * i + k]); }
@@ -1375,6 +1380,51 @@ int tj_get_energy(tj_ctx* c, double* energy) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return TJ_OK;
 }
+
+namespace {
+// tj_audit / tj_group_audit.  net_host: every robot's control points [U][3][T] as the caller assembled them (a group: from the owners), or null = the context's own.
+int audit_run(tj_ctx* c, double range, const double* net_host, tj_audit_robot* out, double* seg_obs, double* seg_pair) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  const Dev& d = c->d;
+  const size_t rows = (size_t)d.U * d.S, net_n = (size_t)d.U * 3 * d.T;
+  QUIESCE(c);
+  int r;
+  if (!c->audit_out) {
+    AuditArgs& a = c->audit;
+    if ((r = dalloc(c, &a.row_obs, rows)) || (r = dalloc(c, &a.row_pair, rows)) || (r = dalloc(c, &a.row_speed, rows)) || (r = dalloc(c, &a.row_accel, rows)) ||
+        (r = dalloc(c, &a.row_prim, rows)) || (r = dalloc(c, &a.row_q, rows)) || (r = dalloc(c, &c->audit_ctl, 1)) || (r = dalloc(c, &c->audit_net, net_n)) || (r = dalloc(c, &c->audit_out, d.U))) return r;
+  }
+  if (d.N > 0 && !c->audit_order) {
+    if ((r = dalloc(c, &c->audit_order, d.N, &c->cloud_allocs)) || (r = upload(c, c->audit_order, c->cloud_order.data(), (size_t)d.N * 4))) return r;
+  }
+  if (net_host && (r = upload(c, c->audit_net, net_host, net_n * 8))) return r;
+  AuditArgs a = c->audit;
+  a.net = net_host ? c->audit_net : d.spline; a.order = c->audit_order; a.range = range > 0 ? range : d.offset + 2 * d.margin;
+  Dev da = d; da.ctl = c->audit_ctl;   // (the walk reports a frontier overflow through Dev::ctl: the audit's own block, never the solver's)
+  const int owned = d.u1 - d.u0;
+  HIPCHK(c, hipMemsetAsync(c->audit_ctl, 0, sizeof(Ctl), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->audit_out, 0, (size_t)d.U * sizeof(tj_audit_robot), c->stream));
+  if (seg_obs || seg_pair) { HIPCHK(c, hipMemsetAsync(a.row_obs, 0, rows * 8, c->stream)); HIPCHK(c, hipMemsetAsync(a.row_pair, 0, rows * 8, c->stream)); }
+  if (owned > 0) {   // plain launches: not part of the iteration schedules, not counted by tj_launch_count
+    if (d.prim == 3) hipLaunchKernelGGL(k_audit<3>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+    else hipLaunchKernelGGL(k_audit<1>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+    hipLaunchKernelGGL(k_audit_reduce, dim3(owned), dim3(64), 0, c->stream, da, a, c->audit_out);
+  }
+  HIPCHK(c, hipGetLastError());
+  int err = 0;
+  HIPCHK(c, hipMemcpyAsync(&err, &c->audit_ctl->error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->audit_out, (size_t)d.U * sizeof(tj_audit_robot), hipMemcpyDeviceToHost, c->stream));
+  if (seg_obs) HIPCHK(c, hipMemcpyAsync(seg_obs, a.row_obs, rows * 8, hipMemcpyDeviceToHost, c->stream));
+  if (seg_pair) HIPCHK(c, hipMemcpyAsync(seg_pair, a.row_pair, rows * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (err & ERR_FRONT_OVERFLOW) { c->err = "tj_audit: the BVH frontier of a segment overflowed at this range (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one hull): lower `range`"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+}  // namespace
+
+int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) { return audit_run(c, range, nullptr, out, seg_obs, seg_pair); }
+int tj_audit_record_size(void) { return (int)sizeof(tj_audit_robot); }
 
 int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_armijo) {
   if (!c) return TJ_ERR_INVALID;

@@ -601,4 +601,29 @@ int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, doub
   return group_fail(g, TJ_ERR_INVALID, "tj_group_get_state: no such robot");
 }
 
+// tj_audit of every robot by the rank that owns it.  A rank holds the OTHER ranks' control points as its last exchange left them -- one line search behind the owners after a
+// batch --, so every robot's control points are first read from its owner and handed to every rank's audit: the records are bitwise those of one context.
+int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) {
+  if (!g || !out) return TJ_ERR_INVALID;
+  GROUP_LIVE(g);
+  const Dev& d0 = g->ctx[0]->d;
+  const int U = d0.U, S = d0.S, T = d0.T;
+  std::vector<double> net((size_t)U * 3 * T);
+  for (int u = 0; u < U; u++) { const int rc = tj_group_get_state(g, u, &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, nullptr); if (rc < 0) return rc; }
+  std::vector<tj_audit_robot> part(U);
+  std::vector<double> so(seg_obs ? (size_t)U * S : 0), sp(seg_pair ? (size_t)U * S : 0);
+  for (int r = 0; r < g->n; r++) {
+    tj_ctx* c = g->ctx[r];
+    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
+    const int rc = audit_run(c, range, g->n > 1 ? net.data() : nullptr, part.data(), seg_obs ? so.data() : nullptr, seg_pair ? sp.data() : nullptr);
+    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
+    for (int u = c->d.u0; u < c->d.u1; u++) {
+      out[u] = part[u];
+      if (seg_obs) std::copy(so.begin() + (size_t)u * S, so.begin() + (size_t)(u + 1) * S, seg_obs + (size_t)u * S);
+      if (seg_pair) std::copy(sp.begin() + (size_t)u * S, sp.begin() + (size_t)(u + 1) * S, seg_pair + (size_t)u * S);
+    }
+  }
+  return TJ_OK;
+}
+
 }  // extern "C"

@@ -197,9 +197,14 @@ int tj_get_energy(tj_ctx* c, double* energy);
  *                   |order (order - 1) (P[j+2] - 2 P[j+1] + P[j])| / (weight^2 piece_time^2): what bound_energy subtracts from vel_limit / acc_limit
  *                   (Energy_admm.h:131-165), in the line search's association; speed_segment / accel_segment: where (the smallest on ties).
  *   duration        piece_num * piece_time, log_data's "ccd time".
- *   flags           TJ_AUDIT_OBS_CONTACT obs_clearance <= offset, TJ_AUDIT_PAIR_CONTACT pair_clearance <= offset (the reference's CCD treats such a
- *                   state as in contact), TJ_AUDIT_SPEED speed >= vel_limit, TJ_AUDIT_ACCEL accel >= acc_limit (bound_energy returns infinity).
- * range <= 0: the solver's own plane range offset + 2 * margin.  seg_obs / seg_pair (may be NULL): the per-segment minima [uav_num][S] (range where
+ *   flags           TJ_AUDIT_OBS_CONTACT a primitive was found (obs_index >= 0) and obs_clearance <= offset, TJ_AUDIT_PAIR_CONTACT a robot was found
+ *                   (pair_robot >= 0) and pair_clearance <= offset (the reference's CCD treats such a state as in contact), TJ_AUDIT_SPEED
+ *                   speed >= vel_limit, TJ_AUDIT_ACCEL accel >= acc_limit (bound_energy returns infinity).  A contact flag always names what is in
+ *                   contact: with range < offset a robot alone in empty space reports obs_clearance == range, index -1 and NO contact, while a
+ *                   primitive closer than that range still sets the flag.
+ * range <= 0 or NaN: the solver's own plane range offset + 2 * margin.  range = +infinity is valid (every primitive is a candidate; the capacity
+ * limit below applies, so it suits small obstacle sets) and reports what any range beyond the largest distance reports, with `range` itself
+ * (infinity) where there is no obstacle or no other robot.  seg_obs / seg_pair (may be NULL): the per-segment minima [uav_num][S] (range where
  * nothing is closer; rows of other ranks 0).  Valid any time after tj_init_state -- straight after it included, and without obstacles.  Changes no
  * solver state, statistics or launch count.  A walk whose frontier overflows is TJ_ERR_CAPACITY (lower `range`), never a smaller answer. */
 enum { TJ_AUDIT_OBS_CONTACT = 1, TJ_AUDIT_PAIR_CONTACT = 2, TJ_AUDIT_SPEED = 4, TJ_AUDIT_ACCEL = 8 };

@@ -1,83 +1,26 @@
 """GPU (-m gpu): tj_audit -- obstacle / robot-pair clearance, dynamic limits, duration of the state the solver holds.
 
-Expected values: oracle.pyoracle.Prims.gjk (the reference's own openGJK where oracle/_ref/libref.so is present, else the port, which is
-pinned to it bit for bit) applied to hulls this file forms itself from host_tables with the ascending six-term sum, over EVERY primitive whose
-point (or whose triangle's box) lies within `range` of the hull's box -- a numpy prefilter with the device's comparison, nothing sampled.
-Distances and limits are compared with == on the doubles: same inputs, same expressions (no FMA contraction on either side)."""
+Expected values come from tests/audit_ref.py: oracle.pyoracle.Prims.gjk (the reference's own openGJK where oracle/_ref/libref.so is present, else
+the port, which is pinned to it bit for bit) applied to hulls formed from host_tables with the ascending six-term sum, over EVERY primitive and
+every other robot -- no box filter, nothing sampled (tests/test_audit_ref.py shows on the CPU that the filtered form agrees).  Distances and
+limits are compared with == on the doubles: same inputs, same expressions (no FMA contraction on either side).  The truth tests compare with an
+exact distance that shares nothing with GJK, at the bars measured in tests/test_audit_ref.py."""
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
 
+import audit_ref as R
+from conftest import ROOT
+from audit_ref import brute_obs, brute_pair, hulls_of, limits_of, norm3, prims, robot_min
+from test_audit_ref import GJK_BAR
+from test_oracle_params import PARAM_SETS
+
 pytestmark = pytest.mark.gpu
 STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
-
-
-def prims():
-    from oracle.pyoracle import Prims, available
-    return Prims("ref" if available("ref") else "port")
-
-
-def norm3(v):
-    """dev_common.h norm3: sqrt(x*x + y*y + z*z), left to right"""
-    return float(np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
-
-
-def hulls_of(pkg, spline, P, res):
-    """[U][S][6][3]: hull_entry's sum -- acc = 0, acc += basis[tr][j][k] * net[3 * piece + k][a] for k = 0..5"""
-    basis = pkg.host_tables(P, res)[2]
-    U, S = spline.shape[0], P * res
-    H = np.zeros((U, S, 6, 3))
-    for tr in range(S):
-        sp = tr // res
-        for k in range(6):
-            H[:, tr] += basis[tr][None, :, k, None] * spline[:, None, :, 3 * sp + k]
-    return H
-
-
-def brute_obs(pr, H, prims_xyz, rng):
-    """prims_xyz [N][3] points or [N][3][3] triangles -> (d[U][S], id[U][S]); id -1 and d = rng where nothing is closer"""
-    U, S = H.shape[:2]
-    tri = prims_xyz.ndim == 3
-    plo = prims_xyz.min(axis=1) if tri else prims_xyz
-    phi = prims_xyz.max(axis=1) if tri else prims_xyz
-    d = np.full((U, S), rng); ids = np.full((U, S), -1, dtype=np.int64)
-    for u in range(U):
-        for tr in range(S):
-            lo, hi = H[u, tr].min(axis=0), H[u, tr].max(axis=0)
-            near = np.flatnonzero(~((phi + rng < lo) | (plo > hi + rng)).any(axis=1))   # box_hit's comparison (kernels_sep.h)
-            for i in near:
-                x = norm3(pr.gjk(H[u, tr], prims_xyz[i].reshape(-1, 3)))
-                if x < rng and (x < d[u, tr] or (x == d[u, tr] and i < ids[u, tr])):
-                    d[u, tr], ids[u, tr] = x, i
-    return d, ids
-
-
-def brute_pair(pr, H, rng):
-    U, S = H.shape[:2]
-    d = np.full((U, S), rng); ids = np.full((U, S), -1, dtype=np.int64)
-    for u in range(U):
-        for tr in range(S):
-            for q in range(U):
-                if q == u:
-                    continue
-                a, b = (u, q) if u < q else (q, u)   # plane_pair: the lower robot index is body 1
-                x = norm3(pr.gjk(H[a, tr], H[b, tr]))
-                if x < rng and x < d[u, tr]:
-                    d[u, tr], ids[u, tr] = x, q
-    return d, ids
-
-
-def robot_min(d, ids, rng):
-    """(value, segment, index) per robot: smallest (segment, index) among equal distances"""
-    out = []
-    for u in range(d.shape[0]):
-        best = (rng, -1, -1)
-        for tr in range(d.shape[1]):
-            if ids[u, tr] >= 0 and d[u, tr] < best[0]:
-                best = (d[u, tr], tr, int(ids[u, tr]))
-        out.append(best)
-    return out
+DEFAULT_RANGE = 0.1 + 2 * 0.1   # offset + 2 * margin at the shipped values, in the library's association (0.30000000000000004)
 
 
 def check_clearances(pkg, slv, scene, rng, multi=True):
@@ -87,7 +30,7 @@ def check_clearances(pkg, slv, scene, rng, multi=True):
     H = hulls_of(pkg, slv.get_state()["spline"], slv.P, slv.res)
     pr = prims()
     xyz = scene["tris"] if scene.get("tris") is not None else scene["cloud"]
-    d, ids = brute_obs(pr, H, np.asarray(xyz, dtype=np.float64), r)
+    d, ids = brute_obs(pr, H, np.asarray(xyz, dtype=np.float64), r, prefilter=False)
     assert np.array_equal(a["seg_obs"], d)
     for u, (v, tr, i) in enumerate(robot_min(d, ids, r)):
         assert (a["obs_clearance"][u], a["obs_segment"][u], a["obs_index"][u]) == (v, tr, i), u
@@ -139,34 +82,6 @@ def test_triangles(pkg, scenes):
     slv.close()
 
 
-def limits_of(pkg, st, P, res):
-    """Energy_admm.h:131-165 in the line search's association (kernels_ls.h): per robot (speed, segment, accel, segment, duration)"""
-    H = hulls_of(pkg, st["spline"], P, res)
-    out = []
-    for u in range(H.shape[0]):
-        pt = st["piece_time"][u]
-        sp, ss, ac, acs = -1.0, -1, -1.0, -1
-        for tr in range(P * res):
-            k = tr % res
-            w = (k + 1) / float(res) - k / float(res)   # the table value (seg_weight), not 1 / res
-            Pp = H[u, tr]
-            for b in range(5):
-                v = 5 * (Pp[b + 1] - Pp[b])
-                x = norm3(v) / (w * pt)
-                if x > sp:
-                    sp, ss = x, tr
-            for j in range(4):
-                v = 20 * (Pp[j + 2] - 2 * Pp[j + 1] + Pp[j])
-                x = norm3(v) / (w * w * pt * pt)
-                if x > ac:
-                    ac, acs = x, tr
-        dur = 0.0
-        for _ in range(P):
-            dur += 1.0 * pt
-        out.append((sp, ss, ac, acs, dur))
-    return out
-
-
 def test_limits_and_what_the_solver_maintains(pkg, scenes):
     """speed / accel / duration equal the numpy restatement at the start and after 10 iterations of hard().  After those 10 iterations every speed < vel_limit and
     accel < acc_limit (bound_energy is infinite otherwise, so the line search never accepts such a state) and every clearance > offset (what the CCD clamp maintains:
@@ -199,7 +114,9 @@ def test_start_in_collision_is_reported(pkg, scenes):
     scene["cloud"] = cloud
     slv = pkg.Solver(scene, stop=0.0)
     a = slv.audit()
-    assert a["obs_clearance"][1] == 0.0 and a["obs_index"][1] == 123 and a["obs_segment"][1] in (16, 17)   # (the vertex is shared with the end of segment 16)
+    d16, d17 = (norm3(prims().gjk(H[1, tr], cloud[123:124])) for tr in (16, 17))   # (the vertex is shared with the end of segment 16)
+    assert min(d16, d17) == 0.0
+    assert a["obs_clearance"][1] == 0.0 and a["obs_index"][1] == 123 and a["obs_segment"][1] == (16 if d16 <= d17 else 17)   # equal values: the smallest segment
     assert a["flags"][1] & pkg.AUDIT_FLAGS["obs_contact"]
     assert a["obs_clearance"][1] == norm3(prims().gjk(H[1, a["obs_segment"][1]], cloud[123:124]))
     assert not (a["flags"][0] & pkg.AUDIT_FLAGS["obs_contact"])
@@ -273,3 +190,382 @@ def test_bad_arguments(pkg, scenes):
     assert all(r.obs_index == -1 and abs(r.obs_clearance - 0.3) < 1e-15 for r in rec)
     assert lib.tj_audit(None, C.c_double(0.0), rec, None, None) == -1
     lib.tj_destroy(ctx)
+
+
+# ---- sizes, tables, flags, ties, truth, errors (the shapes the tests above never reach) ----------------------------------------------------
+
+def check_records(a, want_rows, kind, rng):
+    d, ids = want_rows
+    assert np.array_equal(a["seg_" + kind], d), kind
+    names = ("obs_clearance", "obs_segment", "obs_index") if kind == "obs" else ("pair_clearance", "pair_segment", "pair_robot")
+    for u, rec in enumerate(robot_min(d, ids, rng)):
+        assert tuple(a[n][u] for n in names) == rec, (kind, u)
+
+
+def check_limits(pkg, slv, a):
+    for u, (sp, ss, ac, acs, dur) in enumerate(limits_of(pkg, slv.get_state(), slv.P, slv.res)):
+        assert (a["speed"][u], a["speed_segment"][u], a["accel"][u], a["accel_segment"][u], a["duration"][u]) == (sp, ss, ac, acs, dur), u
+
+
+def expected_flags(pkg, p, a_rows_obs, a_rows_pair, lim, rng, multi=True):
+    """the header's flag word from the brute force and the restated limits: offset for both contacts, vel_limit for speed, acc_limit for accel"""
+    F = pkg.AUDIT_FLAGS
+    out = []
+    ro, rp = robot_min(*a_rows_obs, rng), robot_min(*a_rows_pair, rng) if multi else None
+    for u in range(len(lim)):
+        f = F["obs_contact"] if ro[u][2] >= 0 and ro[u][0] <= p["offset"] else 0
+        if multi and rp[u][2] >= 0 and rp[u][0] <= p["offset"]:
+            f |= F["pair_contact"]
+        f |= (F["speed"] if lim[u][0] >= p["vel_limit"] else 0) | (F["accel"] if lim[u][2] >= p["acc_limit"] else 0)
+        out.append(f)
+    return np.array(out)
+
+
+@pytest.mark.parametrize("U", [64, 65, 70, 130])
+def test_fleet_sizes_beyond_one_pair_batch(pkg, scenes, U):
+    """k_audit's partner loop takes 64 robots per pass: a full single batch, a second batch of one robot, a partly filled one, three batches;
+    qr == u in a later batch, the LDS tile reused.  crossing() stacks the fleet 0.25 apart, so at the start every inner robot is equidistant from
+    both neighbours (checked on the CPU in tests/test_audit_ref.py): the smaller robot index is expected.  U = 130 also through a group of three
+    ranks on one device (44 + 43 + 43 robots: owners in different batches) == one context."""
+    scene = scenes.crossing(U, 600, seed=5)
+    slv = pkg.Solver(scene, stop=0.0)
+    grp = pkg.Group(scene, [0, 0, 0], stop=0.0) if U == 130 else None
+    pr = prims()
+    for it in (0, 3):
+        if it:
+            slv.iterate(it)
+            if grp:
+                grp.iterate(it)
+        st = slv.get_state()
+        assert R.valid_state(st, U)
+        d, ids = R.all_pair(pr, hulls_of(pkg, st["spline"], slv.P, slv.res))
+        if it == 0:
+            assert np.sum(ids[1:U - 1, 20] == np.arange(0, U - 2)) > U // 2   # the tie between u - 1 and u + 1 goes to u - 1
+        for rng in (None, 1.0):
+            r = DEFAULT_RANGE if rng is None else rng
+            a = slv.audit(range=rng, per_segment=True)
+            check_records(a, R.cap(d, ids, r), "pair", r)
+            if grp:
+                g = grp.audit(range=rng, per_segment=True)
+                for k in a:
+                    assert np.array_equal(a[k], g[k]), (it, rng, k)
+    if grp:
+        grp.close()
+    slv.close()
+
+
+@pytest.mark.parametrize("P,res", [(9, 8), (12, 8), (20, 8), (3, 15), (3, 16), (2, 16)])
+def test_segment_counts_and_tables(pkg, scenes, P, res):
+    """S = 72, 96, 160 rows per robot (k_audit_reduce's lanes hold two or three rows each), res 15 / 16 (seg_weight and basis away from 1/8): the
+    scene construction of test_piece_counts_and_resolutions_vs_oracle, state from the CPU engine after 3 iterations"""
+    scene = dict(scenes.hard(4, 3000, pieces=P))
+    params = {"res": res}
+    slv = pkg.Solver(scene, params, stop=0.0)
+    st = R.port_state(scene, 3, params)
+    assert R.valid_state(st, 4)
+    slv.set_state(st)
+    pr = prims()
+    H = hulls_of(pkg, st["spline"], P, res)
+    rows_o, rows_p = R.all_obs(pr, H, scene["cloud"]), R.all_pair(pr, H)
+    for rng in (None, 1.0):
+        r = DEFAULT_RANGE if rng is None else rng
+        a = slv.audit(range=rng, per_segment=True)
+        check_records(a, R.cap(*rows_o, r), "obs", r)
+        check_records(a, R.cap(*rows_p, r), "pair", r)
+        check_limits(pkg, slv, a)
+    slv.close()
+
+
+def test_equal_minima_64_segments_apart_and_a_minimum_beyond_segment_64(pkg, scenes):
+    """S = 96 (tests/audit_ref.py equal_minima_scene): robot 1 has |v| == 0.0 in segments 9, 10, 73 and 74 -- rows 9 and 73 sit in the same lane of
+    the reduction: segment 9 is expected; robot 2's minimum lies in segment 79, a lane's second row"""
+    scene, st, d, ids = R.equal_minima_scene(pkg, scenes)
+    slv = pkg.Solver(scene, stop=0.0)
+    slv.set_state(st)   # the very state the hulls were formed from
+    a = slv.audit(per_segment=True)
+    check_records(a, R.cap(d, ids, DEFAULT_RANGE), "obs", DEFAULT_RANGE)
+    assert (a["obs_segment"][1], a["obs_index"][1], a["obs_segment"][2], a["obs_index"][2]) == (9, 1500, 79, 2200)
+    slv.close()
+
+
+@pytest.mark.parametrize("tag", ["A", "B"])
+def test_flags_and_default_range_at_sets_a_and_b(pkg, scenes, tag):
+    """margin != offset and vel_limit != acc_limit (tests/test_oracle_params.py): the default range is offset + 2 * margin, contacts compare with
+    offset, speed with vel_limit, accel with acc_limit.  Constructed states (tests/audit_ref.py threshold_scene, limit_piece_times; their
+    preconditions run on the CPU in tests/test_audit_ref.py too) sit BETWEEN the values a swapped comparison would use, then below and above both;
+    every one of the four flags is seen set and seen clear on the robot built for it, the other robots' words as the brute force says."""
+    p = R.params_of(pkg, PARAM_SETS[tag])
+    F = pkg.AUDIT_FLAGS
+    rng = R.default_range(p)
+    seen_set, seen_clear = set(), set()
+    for gap, contact, between in R.threshold_gaps(p):
+        scene, st, rows_o, rows_p = R.threshold_scene(pkg, scenes, PARAM_SETS[tag], gap, contact, between)
+        rows_o, rows_p = R.cap(*rows_o, rng), R.cap(*rows_p, rng)
+        slv = pkg.Solver(scene, PARAM_SETS[tag], stop=0.0)
+        for pt in R.limit_piece_times(pkg, st, 2, p) if between else [st["piece_time"][2]]:   # robot 2's piece_time scaled: speed ~ 1 / pt, accel ~ 1 / pt^2
+            s2 = R.scaled_time_state(st, 2, pt)
+            assert R.valid_state(s2, 4)
+            slv.set_state(s2)
+            a = slv.audit(per_segment=True)                                  # range 0: the default
+            check_records(a, rows_o, "obs", rng)
+            check_records(a, rows_p, "pair", rng)
+            check_limits(pkg, slv, a)
+            exp = expected_flags(pkg, p, rows_o, rows_p, limits_of(pkg, s2, 5, 8), rng)
+            assert np.array_equal(a["flags"], exp), (gap, pt, a["flags"], exp)
+            assert bool(exp[3] & F["obs_contact"]) == contact and bool(exp[0] & F["pair_contact"]) == contact == bool(exp[1] & F["pair_contact"])
+            for n in F:
+                for u in range(4):
+                    (seen_set if a["flags"][u] & F[n] else seen_clear).add((n, u))
+        slv.close()
+    for n, u in (("obs_contact", 3), ("pair_contact", 0), ("pair_contact", 1), ("speed", 2), ("accel", 2)):
+        assert (n, u) in seen_set and (n, u) in seen_clear, (n, u)
+
+
+def test_every_flag_is_seen_set_at_the_shipped_values(pkg, scenes):
+    """PAIR_CONTACT names both robots; SPEED and ACCEL alone and together; at the defaults (offset 0.1, limits 2)"""
+    p = R.params_of(pkg)
+    F = pkg.AUDIT_FLAGS
+    scene, st = R.overlap_state(pkg, scenes, gap=0.05)
+    slv = pkg.Solver(scene, stop=0.0)
+    H = hulls_of(pkg, st["spline"], 5, 8)
+    pr = prims()
+    rows_o, rows_p = R.cap(*R.all_obs(pr, H, scene["cloud"]), DEFAULT_RANGE), R.cap(*R.all_pair(pr, H), DEFAULT_RANGE)
+    for want in (set(), {"speed"}, {"accel"}, {"speed", "accel"}):
+        pt = R.piece_time_for(pkg, st, 5, 8, 3, p, want)
+        if pt is None:
+            continue
+        s2 = R.scaled_time_state(st, 3, pt)
+        slv.set_state(s2)
+        a = slv.audit()
+        exp = expected_flags(pkg, p, rows_o, rows_p, limits_of(pkg, s2, 5, 8), DEFAULT_RANGE)
+        assert np.array_equal(a["flags"], exp), (want, a["flags"], exp)
+        assert exp[0] & F["pair_contact"] and exp[1] & F["pair_contact"] and (a["pair_robot"][0], a["pair_robot"][1]) == (1, 0)
+        assert not exp[2] & F["pair_contact"]
+    slv.close()
+
+
+@pytest.mark.parametrize("kind", ["twin", "tris"])
+@pytest.mark.parametrize("i,j", [(40, 555), (555, 40)])
+def test_equal_distances_report_the_callers_smaller_index(pkg, scenes, kind, i, j):
+    """two primitives at bit-equal distance (the same point / the same triangle at two indices of the caller's list): obs_index is min(i, j)
+    whatever order the BVH's sort gave them -- A.order undoes the sort"""
+    tiny = scenes.tiny(mode=1)
+    st = R.port_state(tiny, 0)
+    H = hulls_of(pkg, st["spline"], 5, 8)
+    scene = R.tie_scene(scenes, H, 1, 20, i, j, kind)
+    v, tr, k = R.tie_precondition(prims(), H, 1, scene, i, j)
+    slv = pkg.Solver(scene, stop=0.0)
+    slv.set_state(st)   # the very state the hulls above were formed from
+    a = slv.audit()
+    assert (a["obs_clearance"][1], a["obs_segment"][1], a["obs_index"][1]) == (v, tr, min(i, j))
+    slv.close()
+
+
+def nearest_exact(H, X, u, seg, idx, value, bar):
+    """the record names a primitive whose EXACT distance is `value` within `bar`, and no primitive is exactly closer by more than `bar`"""
+    X = np.asarray(X, dtype=np.float64)
+    e = R.exact_distance(H[u, seg], X[idx])
+    assert abs(value - e) <= bar, (u, seg, idx, value, e)
+    tri = X.ndim == 3
+    plo, phi = (X.min(axis=1), X.max(axis=1)) if tri else (X, X)
+    m = value + 1e-9
+    for tr in range(H.shape[1]):
+        lo, hi = H[u, tr].min(axis=0), H[u, tr].max(axis=0)
+        for i in np.flatnonzero(~((phi + m < lo) | (plo > hi + m)).any(axis=1)):
+            assert R.exact_distance(H[u, tr], X[i]) >= value - bar, (u, tr, i)
+
+
+@pytest.mark.parametrize("name", ["hard10", "tiny_tri", "contact", "overlap"])
+def test_clearances_are_distances(pkg, scenes, name):
+    """the reported clearance against an exact Euclidean distance that shares nothing with GJK (tests/audit_ref.py exact_distance), at the bars
+    measured on the CPU per class (tests/test_audit_ref.py GJK_BAR): cloud points, hull pairs and a point on a face at rounding level; triangles, a
+    point on a vertex and a point inside a solid hull are the stated limits of openGJK's stopping rule (4.5e-13, 1e-5, 5.3e-7 seen)"""
+    if name == "hard10":
+        scene = scenes.hard(); slv = pkg.Solver(scene, stop=0.0); slv.iterate(10); X, kind = scene["cloud"], "point"
+    elif name == "tiny_tri":
+        scene = scenes.triangulate(scenes.tiny(mode=1)); slv = pkg.Solver(scene, stop=0.0); slv.iterate(3); X, kind = scene["tris"], "triangle"
+    elif name == "contact":
+        scene, st, cases = R.contact_cases(pkg, scenes); slv = pkg.Solver(scene, stop=0.0); slv.set_state(st); X, kind = scene["cloud"], None
+    else:
+        scene, st = R.overlap_state(pkg, scenes); slv = pkg.Solver(scene, stop=0.0); slv.set_state(st); X, kind = scene["cloud"], "point"
+    a = slv.audit(range=1.0)
+    H = hulls_of(pkg, slv.get_state()["spline"], slv.P, slv.res)
+    for u in range(slv.U):
+        assert a["obs_index"][u] >= 0 and a["pair_robot"][u] >= 0
+        bar = GJK_BAR[kind or next(k for cu, _, _, k in cases if cu == u)]   # contact scene: one constructed case per robot, each at its own bar
+        nearest_exact(H, X, u, a["obs_segment"][u], a["obs_index"][u], a["obs_clearance"][u], bar)
+        seg, q = a["pair_segment"][u], a["pair_robot"][u]
+        assert abs(a["pair_clearance"][u] - R.exact_distance(H[u, seg], H[q, seg])) <= GJK_BAR["pair"], (u, seg, q)
+    if name == "contact":
+        for u, tr, i, k in cases:
+            assert a["obs_index"][u] == i and a["obs_clearance"][u] <= GJK_BAR[k] and a["flags"][u] & pkg.AUDIT_FLAGS["obs_contact"]
+    if name == "overlap":
+        assert a["pair_clearance"][0] <= 1e-3 + 1e-15 and a["flags"][0] & a["flags"][1] & pkg.AUDIT_FLAGS["pair_contact"]
+    slv.close()
+
+
+def test_frontier_overflow_is_an_error_and_leaves_everything_usable(pkg, scenes):
+    """SCN-B (20 000 points = 2 500 leaf boxes > FRONT_CAP = 1 024) at range 100: every leaf is within range of every hull, the walk cannot hold them:
+    TJ_ERR_CAPACITY -- never a smaller answer; the solver's own error bits, its state and the next audit are untouched, and the iterations
+    after it are those of a solver that never audited.  One call."""
+    scene = scenes.scn_b()
+    slv = pkg.Solver(scene, stop=0.0); ref = pkg.Solver(scene, stop=0.0)
+    slv.iterate(2); ref.iterate(2)
+    before, st0 = slv.audit(per_segment=True), slv.get_state()
+    with pytest.raises(pkg.TrajAdmmError) as ei:
+        slv.audit(range=100.0)
+    assert "-3" in str(ei.value) and "range" in str(ei.value)
+    assert slv.stats()["error_bits"] == 0
+    st1 = slv.get_state()
+    for n in STATE:
+        assert np.array_equal(st0[n], st1[n]), n
+    after = slv.audit(per_segment=True)
+    for k in before:
+        assert np.array_equal(before[k], after[k]), k
+    slv.iterate(2); ref.iterate(2)
+    sa, sb = slv.get_state(), ref.get_state()
+    for n in STATE:
+        assert np.array_equal(sa[n], sb[n]), n
+    slv.close(); ref.close()
+
+
+def test_replaced_obstacle_set(pkg, scenes):
+    """audit, tj_set_cloud with a permuted shorter cloud, audit: the caller-index table belongs to the obstacle set and goes with it; then tj_set_mesh"""
+    scene = scenes.tiny(mode=1)
+    slv = pkg.Solver(scene, stop=0.0)
+    slv.iterate(3)
+    st = slv.get_state()
+    first = slv.audit(range=1.0)
+    perm = np.random.default_rng(8).permutation(600)[:437]
+    cloud2 = np.ascontiguousarray(scene["cloud"][perm])
+    slv._check(slv.lib.tj_set_cloud(slv._ctx, cloud2.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(437)))
+    scene2 = dict(scene, cloud=cloud2)
+    fresh = pkg.Solver(scene2, stop=0.0); fresh.set_state(st)
+    a, b = slv.audit(range=1.0, per_segment=True), fresh.audit(range=1.0, per_segment=True)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    for u in range(slv.U):   # a robot whose nearest point was kept meets it again under its new index
+        if first["obs_index"][u] >= 0 and first["obs_index"][u] in perm:
+            assert a["obs_index"][u] >= 0 and perm[a["obs_index"][u]] == first["obs_index"][u] and a["obs_clearance"][u] == first["obs_clearance"][u], u
+    H = hulls_of(pkg, st["spline"], 5, 8)
+    check_records(a, brute_obs(prims(), H, cloud2, 1.0, prefilter=False), "obs", 1.0)
+    fresh.close()
+    tris = scenes.triangulate(scene2)["tris"][::-1][:300]
+    verts = np.ascontiguousarray(tris, dtype=np.float64).reshape(-1, 3)
+    faces = np.arange(900, dtype=np.int32).reshape(-1, 3)
+    slv._check(slv.lib.tj_set_mesh(slv._ctx, verts.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(900), faces.ctypes.data_as(C.POINTER(C.c_int)), C.c_int(300)))
+    a = slv.audit(range=1.0, per_segment=True)
+    check_records(a, brute_obs(prims(), H, np.ascontiguousarray(tris), 1.0, prefilter=False), "obs", 1.0)
+    slv.close()
+
+
+@pytest.mark.parametrize("name", ["tiny_multi_optplane", "tiny_single_optplane", "hard_coupled"])
+def test_other_modes_on_one_context(pkg, scenes, name):
+    """optimal_plane = 1 (multi and single UAV) and the coupled mode (one shared piece_time) on ONE context, initial state and after 3 iterations"""
+    from conftest import scene_by_name
+    if name == "hard_coupled":
+        scene, caps = scene_by_name(scenes, name), {}
+    else:
+        scene, caps = scene_by_name(scenes, name[:-len("_optplane")]), dict(optimal_plane=1)
+    slv = pkg.Solver(scene, stop=0.0, **caps)
+    multi = scene["mode"] != 0
+    for it in (0, 3):
+        if it:
+            slv.iterate(it)
+        a = check_clearances(pkg, slv, scene, None if it else 1.0, multi=multi)
+        check_limits(pkg, slv, a)
+    if name == "hard_coupled":
+        assert len(set(slv.get_state()["piece_time"])) == 1
+    slv.close()
+
+
+def test_range_corner_values(pkg, scenes):
+    """range below offset: a robot with nothing within range reports range, -1 and NO contact (a contact names what is in contact), a robot with a
+    primitive within that range still reports it; +infinity == any range beyond the largest distance; NaN == the default"""
+    F = pkg.AUDIT_FLAGS
+    scene, st, H = R.range_corner_scene(pkg, scenes)
+    cloud = scene["cloud"]
+    slv = pkg.Solver(scene, stop=0.0)
+    slv.set_state(st)   # the very state the hulls above were formed from
+    a = slv.audit(range=0.05, per_segment=True)
+    check_records(a, brute_obs(prims(), H, cloud, 0.05, prefilter=False), "obs", 0.05)
+    assert a["obs_index"][1] == 123 and a["obs_clearance"][1] < 0.05 and a["flags"][1] & F["obs_contact"]
+    for u in (0, 2):
+        assert (a["obs_clearance"][u], a["obs_index"][u], a["obs_segment"][u]) == (0.05, -1, -1) and not a["flags"][u] & F["obs_contact"]
+    assert np.all(a["pair_clearance"] == 0.05) and np.all(a["pair_robot"] == -1) and not np.any(a["flags"] & F["pair_contact"])
+    x, y = slv.audit(range=100.0, per_segment=True), slv.audit(range=float("inf"), per_segment=True)
+    for k in x:
+        assert np.array_equal(x[k], y[k]), k
+    x, y = slv.audit(range=None, per_segment=True), slv.audit(range=float("nan"), per_segment=True)
+    for k in x:
+        assert np.array_equal(x[k], y[k]), k
+    slv.close()
+    empty = pkg.Solver(dict(scenes.tiny(mode=0), cloud=np.zeros((0, 3))), stop=0.0)   # no obstacle, no other robot: +inf reports `range` itself
+    a = empty.audit(range=float("inf"), per_segment=True)
+    assert a["obs_clearance"][0] == np.inf == a["pair_clearance"][0] and (a["obs_index"][0], a["obs_segment"][0], a["pair_robot"][0]) == (-1, -1, -1)
+    assert np.all(a["seg_obs"] == np.inf) and np.all(a["seg_pair"] == np.inf) and a["flags"][0] & 3 == 0 and np.isfinite(a["speed"][0])
+    empty.close()
+
+
+def parse_audit_lines(stdout):
+    """'audit uav U obs X seg N id N pair X seg N uav N speed X seg N accel X seg N time X flags N' -> list of dicts in the record's names"""
+    names = ("obs_clearance", "obs_segment", "obs_index", "pair_clearance", "pair_segment", "pair_robot", "speed", "speed_segment", "accel",
+             "accel_segment", "duration", "flags")
+    out = []
+    for line in stdout.split("\n"):
+        if line.startswith("audit uav "):
+            w = line.split()
+            assert len(w) == 27 and int(w[2]) == len(out), line
+            out.append({n: (float if n in ("obs_clearance", "pair_clearance", "speed", "accel", "duration") else int)(w[4 + 2 * k]) for k, n in enumerate(names)})
+    return out
+
+
+def load_dump(path, st):
+    """--dump-state file -> the solver state `st` with its control points and piece_time replaced (17 digits: the exact doubles)"""
+    lines = open(path).read().strip().split("\n")
+    U, P = int(lines[0].split()[1]), int(lines[0].split()[3])
+    T = 3 * P + 3
+    out = {k: v.copy() for k, v in st.items()}
+    for u in range(U):
+        blk = lines[1 + u * (T + 1):1 + (u + 1) * (T + 1)]
+        assert blk[0].split()[:2] == ["uav", str(u)]
+        out["piece_time"][u] = float(blk[0].split()[3])
+        out["spline"][u] = np.array([[float(x) for x in l.split()] for l in blk[1:]]).T
+    return out
+
+
+@pytest.mark.parametrize("multi", [False, True])
+def test_command_line_audit(pkg, scenes, tmp_path, multi):
+    """--audit and --audit 1.0 on both mains (and through a two-rank group on the multi-UAV one): every printed field equals the library's audit
+    of the dumped state -- doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly"""
+    import torch
+    scene = scenes.tiny(mode=1) if multi else scenes.tiny(0, n_points=3000)
+    mesh = "x.obj"
+    scenes.write_reference_files(scene, str(tmp_path), mesh)
+    os.makedirs(tmp_path / "Config_File", exist_ok=True)
+    (tmp_path / "Config_File" / "3D.json").write_text(
+        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
+        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D" if multi else "admmPathPlanning3D")
+    two = ["--gpus", "2"] if torch.cuda.device_count() >= 2 else ["--devices", "0,0"]   # two ranks either way: tj_group_audit
+    slv = pkg.Solver(scene, stop=0.0)
+    dumps = []
+    for audit_args, rng in ((["--audit"], None), (["--audit", "1.0"], 1.0)):
+        for extra in ([], two) if multi else ([],):
+            r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + audit_args + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
+            assert r.returncode in (0, 2), r.stderr          # 2: not converged after 6 iterations, the audit is printed all the same
+            got = parse_audit_lines(r.stdout)
+            assert len(got) == scene["U"], r.stdout[-2000:]
+            dumps.append(open(tmp_path / "state.txt").read())
+            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
+            a = slv.audit(range=rng)
+            for u, rec in enumerate(got):
+                for n, v in rec.items():
+                    if isinstance(v, int):
+                        assert v == a[n][u], (audit_args, extra, u, n, v, a[n][u])
+                    else:
+                        assert abs(v - a[n][u]) <= 1e-6 * abs(a[n][u]), (audit_args, extra, u, n, v, a[n][u])
+            if not multi:
+                assert all(rec["pair_robot"] == -1 and rec["pair_clearance"] == (DEFAULT_RANGE if rng is None else rng) for rec in got)
+    assert len(set(dumps)) == 1                                # the audit and the group change nothing of the run
+    slv.close()

@@ -157,7 +157,8 @@ __global__ __launch_bounds__(64) void k_audit_reduce(Dev D, AuditArgs A, tj_audi
     r.pair_clearance = pd; r.pair_segment = pq < 0 ? -1 : ps; r.pair_robot = pq;
     r.speed = -nsp; r.accel = -nac; r.speed_segment = ss; r.accel_segment = as;
     r.duration = dur;
-    r.flags = (od <= D.offset ? TJ_AUDIT_OBS_CONTACT : 0) | (D.multi() && pd <= D.offset ? TJ_AUDIT_PAIR_CONTACT : 0) |
+    // a contact names what is in contact: with range <= offset and nothing found, od == range <= offset is the search limit, not a clearance
+    r.flags = (oi >= 0 && od <= D.offset ? TJ_AUDIT_OBS_CONTACT : 0) | (pq >= 0 && pd <= D.offset ? TJ_AUDIT_PAIR_CONTACT : 0) |
               (-nsp >= D.vel_limit ? TJ_AUDIT_SPEED : 0) | (-nac >= D.acc_limit ? TJ_AUDIT_ACCEL : 0);
     r.reserved = 0;
     out[u] = r;

@@ -190,7 +190,7 @@ int tj_get_energy(tj_ctx* c, double* energy);
  *                   the smallest (segment, index)); -1, -1 and obs_clearance == range when nothing is closer than range.  0.0 = a hull touches.
  *   pair_clearance  min over segments tr and robots q != u of the GJK distance between the hulls of (u, tr) and (q, tr): the SAME-SEGMENT pairing
  *                   of separate_self / self_step (Optimization3D_multi.h:246-259, Step.h:196-208).  Decoupled robots carry their own piece_time,
- *                   so this is the solver's own pairing, not a distance at equal flight times.  pair_segment / pair_robot as above (smallest
+ *                   so this is the solver's own pairing, not a distance at equal flight times (that is tj_audit_timed, below).  pair_segment / pair_robot as above (smallest
  *                   (segment, q)); single-UAV mode: range, -1, -1.  A sharded context (world > 1) reads the other ranks' control points as its
  *                   last exchange left them; tj_group_audit reads every robot's from its owner.
  *   speed, accel    max over segments and j of |order (P[j+1] - P[j])| / (weight piece_time) and
@@ -217,6 +217,42 @@ typedef struct tj_audit_robot {
 } tj_audit_robot;
 int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);
 int tj_audit_record_size(void);   /* sizeof(tj_audit_robot), for bindings that mirror the record */
+/* ---- tj_audit_timed: how close do two robots get AT THE SAME FLIGHT TIME?  The distance at equal flight times that pair_clearance above is not
+ * (csrc/kernels_audit_timed.h; read-only like tj_audit).  Time is log_data's (Main/multiPathPlanning3D.cpp:31-60): t = sigma * piece_time of the robot,
+ * sigma in [0, piece_num]; a robot that has arrived (t > piece_num * piece_time) stays at its last control point.  For every OWNED robot u, every segment
+ * tr, every other robot q: the segment's window of time is split into 2^levels equal sub-windows, each cut further at q's segment boundaries and at q's
+ * arrival; on every resulting window W both flown quintics are restricted to W (de Casteljau) and d_i = a_i - b_i, the Bezier net of p_u(t) - p_q(t) over
+ * W, gives
+ *   lo(W) = GJK distance of conv{d_0..d_5} from the origin: the curve lies in its hull, no separation on W is smaller (as exact as the GJK: DESIGN.md 3c)
+ *   hi(W) = min(|d_0|, |d_5|): the separation at W's start / end, attained at a known time.
+ *   timed_lo <= the minimum separation of u from any other robot over u's flight <= timed_hi     (both capped: min(range, ...))
+ *   timed_robot / timed_segment / timed_time   partner, u's segment and the real time of the timed_hi sample; lo_robot / lo_segment: where timed_lo is attained.
+ *                   -1 (time -1.0) and the value `range` where nothing is closer than range.  Equal values: the smallest (segment, partner, window).
+ *   levels          the level used.
+ *   flags           TJ_AUDIT_TIMED_CONTACT a partner was found and timed_hi <= offset: the two ARE within offset at timed_time; TJ_AUDIT_TIMED_CLEAR
+ *                   timed_lo > offset: separation certified.  Neither: undecided at this level -- raise `levels` (the bracket narrows by about 4x per
+ *                   level from level 2 on; 7x and 2.4x over the first two steps, table below).  Single-UAV mode: range, -1, -1 and CLEAR.
+ * range <= 0: offset + 2 * margin; +infinity is valid.  levels 0..6; < 0: the default TJ_AUDIT_TIMED_LEVELS.  levels > 6, or a NaN range: TJ_ERR_INVALID.
+ * The default is the smallest level at which timed_hi - timed_lo < offset / 10 (contact decided to a tenth of the contact distance) for every robot with a
+ * partner in range on the final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz and e2e_scn_b_coupled.npz (measured by tests/audit_timed_ref.py, the
+ * numpy restatement; largest width over the three states per level):
+ *   level   0        1        2        3        4        5        6
+ *   width   1.98e-2  2.78e-3  1.16e-3  3.18e-4  8.18e-5  1.83e-5  4.73e-6      (offset / 10 = 1e-2: level 1)
+ * seg_lo / seg_hi (may be NULL): per-segment values [uav_num][S] (range where nothing is closer; rows of other ranks 0).  Records of other ranks' robots are
+ * all zero.  A plain SHARDED context (world > 1) does not hold the other ranks' piece_time as their owners have it and returns TJ_ERR_UNSUPPORTED rather than
+ * answer from stale values: use tj_group_audit_timed, which reads every robot's control points and piece_time from its owner.  Fixed number of launches
+ * (two kernels), no host loop over pairs.  Changes no solver state, statistics or launch count. */
+#define TJ_AUDIT_TIMED_LEVELS 1
+#define TJ_AUDIT_TIMED_CONTACT 1
+#define TJ_AUDIT_TIMED_CLEAR 2
+typedef struct tj_audit_timed_robot {
+  double timed_lo, timed_hi, timed_time;
+  int timed_robot, timed_segment;
+  int lo_robot, lo_segment;
+  int levels, flags;
+} tj_audit_timed_robot;
+int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);
+int tj_audit_timed_record_size(void);   /* sizeof(tj_audit_timed_robot) */
 /* teacher forcing of the CCD / line-search stages: overwrite robot u's search direction record (direction T x 3 column-major) */
 int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_direction, double wolfe, double gn);
 
@@ -369,6 +405,7 @@ int tj_group_init_state(tj_group* g, const double* waypoints, double piece_time0
 int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, int* converged);   /* like tj_iterate */
 int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, double* p_lambda, double* t_slack, double* t_lambda, double* piece_time);   /* from u's owner */
 int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);   /* tj_audit of every robot by its owner, against every robot's control points as its owner holds them: bitwise one context's */
+int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);   /* tj_audit_timed of every robot by its owner; every robot's control points AND piece_time are read from its owner: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */
 /* event-timed cost of one exchange of each buffer kind (microseconds, slowest rank's average over `reps`): us[5], kinds 2..4

@@ -31,6 +31,7 @@ EXPORTS = [
     "tj_group_transport", "tj_group_set_transport", "tj_group_profile_exchange", "tj_rccl_available", "tj_group_rccl_ranks",
     "tj_group_init_state", "tj_group_iterate", "tj_group_get_state",
     "tj_audit", "tj_audit_record_size", "tj_group_audit",
+    "tj_audit_timed", "tj_audit_timed_record_size", "tj_group_audit_timed",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -72,6 +73,30 @@ def _audit(call, U, S, range, per_segment):
            for n, t in TjAuditRobot._fields_ if n != "reserved"}
     if per_segment:
         out["seg_obs"], out["seg_pair"] = so, sp
+    return out
+
+
+class TjAuditTimedRobot(C.Structure):
+    """mirror of tj_audit_timed_robot (include/trajadmm.h); tj_audit_timed_record_size() is its sizeof on the C side"""
+    _fields_ = [("timed_lo", C.c_double), ("timed_hi", C.c_double), ("timed_time", C.c_double),
+                ("timed_robot", C.c_int), ("timed_segment", C.c_int), ("lo_robot", C.c_int), ("lo_segment", C.c_int),
+                ("levels", C.c_int), ("flags", C.c_int)]
+
+
+AUDIT_TIMED_FLAGS = dict(contact=1, clear=2)
+AUDIT_TIMED_LEVELS = 1   # TJ_AUDIT_TIMED_LEVELS: what levels=None selects
+
+
+def _audit_timed(call, U, S, range, levels, per_segment):
+    """shared by Solver.audit_timed / Group.audit_timed: call(range, levels, records, seg_lo, seg_hi) -> dict of numpy arrays [U] (+ [U][S])"""
+    rec = (TjAuditTimedRobot * U)()
+    sl = np.zeros((U, S)) if per_segment else None
+    sh = np.zeros((U, S)) if per_segment else None
+    call(C.c_double(0.0 if range is None else float(range)), C.c_int(-1 if levels is None else int(levels)), rec,
+         _d(sl) if per_segment else None, _d(sh) if per_segment else None)
+    out = {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjAuditTimedRobot._fields_}
+    if per_segment:
+        out["seg_lo"], out["seg_hi"] = sl, sh
     return out
 
 
@@ -485,6 +510,14 @@ class Solver:
         per_segment=True adds seg_obs / seg_pair [U][S].  Read-only, valid straight after construction."""
         return _audit(lambda r, rec, so, sp: self._check(self.lib.tj_audit(self._ctx, r, rec, so, sp)), self.U, self.S, range, per_segment)
 
+    def audit_timed(self, range=None, levels=None, per_segment=False):
+        """tj_audit_timed: per robot the bracket timed_lo <= closest approach to any other robot AT EQUAL FLIGHT TIMES <= timed_hi (searched up to
+        `range`; None = offset + 2 * margin), the partner / own segment / real time of the timed_hi sample, where timed_lo is attained, the level
+        used (levels 0..6: 2^levels sub-windows per segment; None = AUDIT_TIMED_LEVELS) and the flag word (AUDIT_TIMED_FLAGS: contact certain /
+        separation certified / neither = raise levels).  per_segment=True adds seg_lo / seg_hi [U][S].  Read-only.  A sharded context raises
+        (TJ_ERR_UNSUPPORTED): Group.audit_timed reads every robot's piece_time from its owner."""
+        return _audit_timed(lambda r, l, rec, sl, sh: self._check(self.lib.tj_audit_timed(self._ctx, r, l, rec, sl, sh)), self.U, self.S, range, levels, per_segment)
+
     def build_info(self):
         ms, dev = C.c_double(), C.c_int()
         self._check(self.lib.tj_get_build_info(self._ctx, C.byref(ms), C.byref(dev)))
@@ -594,6 +627,10 @@ class Group:
     def audit(self, range=None, per_segment=False):
         """tj_group_audit: Solver.audit of every robot from the rank that owns it (bitwise one context's)"""
         return _audit(lambda r, rec, so, sp: self._check(self.lib.tj_group_audit(self._g, r, rec, so, sp)), self.U, self.S, range, per_segment)
+
+    def audit_timed(self, range=None, levels=None, per_segment=False):
+        """tj_group_audit_timed: Solver.audit_timed of every robot from the rank that owns it (bitwise one context's)"""
+        return _audit_timed(lambda r, l, rec, sl, sh: self._check(self.lib.tj_group_audit_timed(self._g, r, l, rec, sl, sh)), self.U, self.S, range, levels, per_segment)
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

@@ -15,6 +15,8 @@
 // instead of its vertices as a point cloud.
 // --audit [RANGE]: after the run (and after the "ccd len:" lines) one line per robot from tj_audit / tj_group_audit -- obstacle and robot-pair clearance
 // (searched up to RANGE; default offset + 2 * margin), peak speed and acceleration, duration, flag word.  The result file is unchanged.
+// --audit-timed [LEVELS]: after the --audit lines one line per robot from tj_audit_timed / tj_group_audit_timed -- the bracket of the closest approach to another robot at
+// equal flight times (default range; LEVELS 0..6, default the library's), the partner / segment / time of its upper end, where its lower end lies, level, flag word.
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
 #include <chrono>
@@ -29,10 +31,11 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
+  bool audit_timed = false; int audit_levels = -1;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -42,6 +45,7 @@ int main(int argc, char** argv) {
     else if (a == "--sample-traj" && i + 1 < argc) sample_file = argv[++i];
     else if (a == "--triangles") triangles = true;
     else if (a == "--audit") { audit = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_range = atof(argv[++i]); }
+    else if (a == "--audit-timed") { audit_timed = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_levels = atoi(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -164,6 +168,16 @@ int main(int argc, char** argv) {
         std::cout << "audit uav " << u << " obs " << r.obs_clearance << " seg " << r.obs_segment << " id " << r.obs_index << " pair " << r.pair_clearance << " seg " << r.pair_segment
                   << " uav " << r.pair_robot << " speed " << r.speed << " seg " << r.speed_segment << " accel " << r.accel << " seg " << r.accel_segment << " time " << r.duration
                   << " flags " << r.flags << std::endl;
+      }
+    }
+    if (audit_timed) {
+      std::vector<tj_audit_timed_robot> rec(U);
+      chk(group ? tj_group_audit_timed(grp, 0.0, audit_levels, rec.data(), nullptr, nullptr) : tj_audit_timed(ctx, 0.0, audit_levels, rec.data(), nullptr, nullptr), "tj_audit_timed");
+      std::cout.precision(17);
+      for (int u = 0; u < U; u++) {
+        const tj_audit_timed_robot& r = rec[u];
+        std::cout << "audit-timed uav " << u << " lo " << r.timed_lo << " uav " << r.lo_robot << " seg " << r.lo_segment << " hi " << r.timed_hi << " uav " << r.timed_robot
+                  << " seg " << r.timed_segment << " time " << r.timed_time << " levels " << r.levels << " flags " << r.flags << std::endl;
       }
     }
     if (!dump.empty()) {

@@ -5,7 +5,7 @@
 //                        (Separate.h:107-151) and the CCD clamp (Step.h:83-97) compare with their ranges;
 //   robot-pair clearance the same between the hulls of two robots on the SAME segment index, the pairing of separate_self / self_step
 //                        (Optimization3D_multi.h:246-259, Step.h:196-208).  Decoupled robots carry their own piece_time, so equal segment
-//                        indices are not equal flight times: this is the solver's own notion of "the pair", not a continuous-time distance;
+//                        indices are not equal flight times: this is the solver's own notion of "the pair", not a continuous-time distance (kernels_audit_timed.h is);
 //   speed / acceleration the two quantities bound_energy subtracts from vel_limit / acc_limit (Energy_admm.h:131-165), in the expressions and
 //                        the association of the line search (kernels_ls.h x_energy_group).
 //

@@ -1,0 +1,190 @@
+// kernels_audit_timed.h -- tj_audit_timed: how close do two robots get at EQUAL FLIGHT TIMES, with a certificate.
+//
+// tj_audit's pair_clearance is the solver's own pairing (equal segment indices: separate_self / self_step, Optimization3D_multi.h:246-259, Step.h:196-208).
+// Decoupled robots carry their own piece_time, so equal indices are not equal times.  Here both robots are looked at in real time, with log_data's conventions
+// (Main/multiPathPlanning3D.cpp:31-60): t = sigma * piece_time, sigma in [0, P] the piece parameter, time_weight == 1; segment tr of robot u is sigma in
+// [tr / res, (tr + 1) / res] and its hull (hull_entry's sums) is the Bezier net of the flown quintic there; after P * piece_time_q robot q has arrived and
+// stays at its last control point (a one-point body).
+//
+// For an owned robot u, its segment tr, a partner q != u and the level L (0..6):
+//   the segment's window of time [T0, T1] = [tr / res, (tr + 1) / res] * piece_time_u is split into 2^L equal sub-windows; each is cut at q's segment boundaries
+//   (j / res) * piece_time_q and at q's arrival, so that a window W = [ca, cb] lies in ONE segment of u and ONE segment of q (or in q's hover);
+//   both quintics are restricted to W by blossoming (bez_restrict: b_i = the blossom with 5 - i arguments at W's start and i at its end, de Casteljau steps
+//   (1 - s) * x + s * y); d_i = a_i - b_i is the Bezier net of p_u(t) - p_q(t) over W;
+//   lo(W) = |gjk(conv{d_0..d_5}, {0})|: the curve lies in its hull, so no separation on W is smaller (up to GJK's stopping rule);
+//   hi(W) = min(|d_0|, |d_5|): the end points lie on the curve, a separation attained at W's start / end.
+// Per (robot, segment) the minima of lo and hi over partners and windows, capped at `range`; ties keep the smallest (partner, sub-window, cut).
+//
+// Exactness of the skip: a window is not evaluated when the boxes of the two RAW segment hulls are further apart than `range` on an axis -- both restricted
+// nets lie in their raw hulls, so |d| >= hull distance >= box gap > range on the whole window, and neither minimum (both capped at `range`) can change.  Same
+// rounding guard as k_audit's pair loop.
+//
+//   k_audit_timed         one wave per (owned robot, segment).  Lane = (partner of the pass, sub-window): 64 >> L partners per pass, 2^L sub-windows each, so level 6
+//                         is one partner per pass and one sub-window per lane.  A lane walks the cuts of its sub-window (usually one or two), forms q's raw hull in its
+//                         column of an LDS tile (stride 64 doubles: lane-consecutive, conflict-free), restricts both nets in registers, writes d to its column of a
+//                         second tile and runs the per-lane GJK against the origin.  Lanes keep their own running minima (strict comparisons, ascending order); one
+//                         total-order reduction (value, partner * 64 + sub-window) at the end.  No float atomics: the result is a function of the state alone.
+//   k_audit_timed_reduce  one wave per owned robot: its S rows -> the record.
+// Read-only: the kernels write the audit's own buffers only (no tj_stats counter, no launch count).
+#pragma once
+#include "kernels_audit.h"
+
+namespace tj {
+
+struct AuditTimedArgs {
+  const double* net;   // [U][3][T] control nets: the solver's own, or the copy a group assembled from the owners
+  const double* pt;    // [U] piece_time of every robot: the solver's own, or the group's copy
+  double range;
+  int levels;
+  double *row_lo, *row_hi, *row_time;   // [U][S]
+  int *row_qlo, *row_qhi;               // [U][S] partner of the row's lo / hi, -1: nothing closer than range
+};
+
+// the Bezier net of a quintic restricted to [sa, sb] of its parameter: o[i] = blossom(sa x (5 - i), sb x i).  Row s of the triangle (s steps at sa) has 6 - s points; 5 - s
+// steps at sb take it to o[5 - s].  sa = 0, sb = 1 returns p bit for bit (1 * x + 0 * y).
+__device__ __forceinline__ void bez_restrict(const double (&p)[6], double sa, double sb, double (&o)[6]) {
+  const double ua = 1 - sa, ub = 1 - sb;
+  double r[6];
+#pragma unroll
+  for (int m = 0; m < 6; m++) r[m] = p[m];
+#pragma unroll
+  for (int s = 0; s <= 5; s++) {
+    double t[6];
+#pragma unroll
+    for (int m = 0; m <= 5 - s; m++) t[m] = r[m];
+#pragma unroll
+    for (int k = 5 - s; k > 0; k--)
+#pragma unroll
+      for (int m = 0; m < k; m++) t[m] = ub * t[m] + sb * t[m + 1];
+    o[5 - s] = t[0];
+#pragma unroll
+    for (int m = 0; m < 5 - s; m++) r[m] = ua * r[m] + sa * r[m + 1];
+  }
+}
+
+__device__ __forceinline__ double clamp01(double x) { return fmin(fmax(x, 0.0), 1.0); }
+
+// audit_argmin with a double and an int travelling along
+__device__ __forceinline__ void audit_argmin_t(double& d, int& key, double& aux, int& iaux) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double d2 = __shfl_xor(d, off), a2 = __shfl_xor(aux, off); const int k2 = __shfl_xor(key, off), i2 = __shfl_xor(iaux, off);
+    if (d2 < d || (d2 == d && k2 < key)) { d = d2; key = k2; aux = a2; iaux = i2; }
+  }
+}
+
+__global__ __launch_bounds__(64) void k_audit_timed(Dev D, AuditTimedArgs A) {
+  const int lane = lane_id(), S = D.S, U = D.U;
+  const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
+  __shared__ double P[18], tq[18 * 64], td[18 * 64];
+  if (lane < 18) P[lane] = hull_entry(D, A.net + (size_t)u * 3 * D.T, tr, lane / 3, lane % 3);
+  __syncthreads();
+  double blo[3], bhi[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    blo[k] = lo; bhi[k] = hi;
+  }
+  const double range = A.range, res = (double)D.res, ptu = A.pt[u];
+  const int L = A.levels, N = 1 << L, per = 64 >> L, w = lane & (N - 1), ql = lane >> L;
+  const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
+  const double t0 = ((tr + w / (double)N) / res) * ptu, t1 = ((tr + (w + 1) / (double)N) / res) * ptu;   // (the last sub-window ends at T1u bit for bit)
+  double* cq = tq + lane; double* cd = td + lane;   // this lane's columns
+
+  double dlo = range, dhi = range, thi = 0.0; int klo = INT_MAX, khi = INT_MAX;
+  if (D.multi()) {
+    for (int base = 0; base < U; base += per) {
+      const int q = base + ql;
+      if (q >= U || q == u) continue;
+      const double ptq = A.pt[q];
+      const double* nq = A.net + (size_t)q * 3 * D.T;
+      // q's segment at t0: T(j) <= t0 < T(j + 1) in the very expressions the cuts use (the quotient only proposes); j == S: q has arrived
+      const double g = floor((t0 / ptq) * res);
+      int j = g >= (double)S ? S : (g > 0.0 ? (int)g : 0);
+      while (j > 0 && (j / res) * ptq > t0) j--;
+      while (j < S && ((j + 1) / res) * ptq <= t0) j++;
+      do {
+        const bool hover = j >= S;
+        const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
+        const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
+        if (hover) {
+#pragma unroll
+          for (int k = 0; k < 3; k++) { const double v = hull_entry(D, nq, S - 1, 5, k); for (int i = 0; i < 6; i++) cq[(3 * i + k) * 64] = v; }
+        } else {
+          for (int e = 0; e < 18; e++) cq[e * 64] = hull_entry(D, nq, j, e / 3, e % 3);
+        }
+        bool near = true;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          double lo = INFINITY, hi = -INFINITY;
+          for (int i = 0; i < 6; i++) { const double v = cq[(3 * i + k) * 64]; if (v < lo) lo = v; if (v > hi) hi = v; }
+          const double gap = fmax(lo - bhi[k], blo[k] - hi);
+          near = near && !(gap > range * 1.000001 + 1e-9);
+        }
+        if (near) {
+          const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
+          const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+            double a[6], b[6], oa[6], ob[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) { a[i] = P[3 * i + k]; b[i] = cq[(3 * i + k) * 64]; }
+            bez_restrict(a, sa, sb, oa);
+            if (hover) {
+#pragma unroll
+              for (int i = 0; i < 6; i++) ob[i] = b[i];
+            } else {
+              bez_restrict(b, ra, rb, ob);
+            }
+#pragma unroll
+            for (int i = 0; i < 6; i++) cd[(3 * i + k) * 64] = oa[i] - ob[i];
+          }
+          const V3 v = gjk(BodyHullS{cd, 64}, BodyPoint{V3{0.0, 0.0, 0.0}});
+          const double lo = norm3(v.x, v.y, v.z);
+          const double h0 = norm3(cd[0], cd[64], cd[128]), h5 = norm3(cd[15 * 64], cd[16 * 64], cd[17 * 64]);
+          const bool first = h0 <= h5;
+          const double hi = first ? h0 : h5;
+          if (lo < range && lo < dlo) { dlo = lo; klo = q * 64 + w; }
+          if (hi < range && hi < dhi) { dhi = hi; khi = q * 64 + w; thi = first ? ca : cb; }
+        }
+        j++;
+      } while (j <= S && (j / res) * ptq < t1);
+    }
+    int unused = 0;
+    audit_argmin(dlo, klo, unused);
+    audit_argmin_t(dhi, khi, thi, unused);
+  }
+  if (lane == 0) {
+    const size_t row = (size_t)u * S + tr;
+    A.row_lo[row] = dlo; A.row_qlo[row] = klo == INT_MAX ? -1 : klo >> 6;
+    A.row_hi[row] = dhi; A.row_qhi[row] = khi == INT_MAX ? -1 : khi >> 6;
+    A.row_time[row] = khi == INT_MAX ? -1.0 : thi;
+  }
+}
+
+// the S rows of an owned robot -> its record; equal values keep the smaller segment
+__global__ __launch_bounds__(64) void k_audit_timed_reduce(Dev D, AuditTimedArgs A, tj_audit_timed_robot* out) {
+  const int lane = lane_id(), S = D.S, u = D.u0 + blockIdx.x;
+  double dlo = A.range, dhi = A.range, thi = -1.0;
+  int slo = INT_MAX, qlo = -1, shi = INT_MAX, qhi = -1;
+  for (int tr = lane; tr < S; tr += 64) {   // ascending segments per lane: a strict comparison keeps the first
+    const size_t r = (size_t)u * S + tr;
+    { const double d = A.row_lo[r]; const int i = A.row_qlo[r]; if (i >= 0 && d < dlo) { dlo = d; slo = tr; qlo = i; } }
+    { const double d = A.row_hi[r]; const int i = A.row_qhi[r]; if (i >= 0 && d < dhi) { dhi = d; shi = tr; qhi = i; thi = A.row_time[r]; } }
+  }
+  audit_argmin(dlo, slo, qlo);
+  audit_argmin_t(dhi, shi, thi, qhi);
+  if (lane == 0) {
+    tj_audit_timed_robot r;
+    r.timed_lo = dlo; r.timed_hi = dhi; r.timed_time = qhi < 0 ? -1.0 : thi;
+    r.timed_robot = qhi; r.timed_segment = qhi < 0 ? -1 : shi;
+    r.lo_robot = qlo; r.lo_segment = qlo < 0 ? -1 : slo;
+    r.levels = A.levels;
+    // CONTACT names its partner (as tj_audit's contacts do); CLEAR is a statement about the lower bound alone.  One UAV: nothing to be near.
+    r.flags = !D.multi() ? TJ_AUDIT_TIMED_CLEAR : ((qhi >= 0 && dhi <= D.offset ? TJ_AUDIT_TIMED_CONTACT : 0) | (dlo > D.offset ? TJ_AUDIT_TIMED_CLEAR : 0));
+    out[u] = r;
+  }
+}
+
+}  // namespace tj

@@ -32,6 +32,7 @@
 #include "kernels_plan.h"
 #include "kernels_bvh.h"
 #include "kernels_audit.h"
+#include "kernels_audit_timed.h"
 
 using namespace tj;
 
@@ -90,6 +91,8 @@ struct tj_ctx {
   int bvh_on_device = 0;
   // tj_audit's own buffers, allocated by its first call (kernels_audit.h): rows [U][S], records [U], a control block for the walk's overflow bit, the control nets a group
   // hands in; audit_order (sorted primitive -> caller's index) belongs to the obstacle set and goes with it (cloud_allocs)
+  // tj_audit_timed's own (kernels_audit_timed.h): rows, records, the control nets and piece times a group hands in
+  AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr; double* timed_net = nullptr; double* timed_pt = nullptr;
   AuditArgs audit{}; tj_audit_robot* audit_out = nullptr; Ctl* audit_ctl = nullptr; double* audit_net = nullptr; int* audit_order = nullptr;
 };
 
@@ -1425,6 +1428,50 @@ int audit_run(tj_ctx* c, double range, const double* net_host, tj_audit_robot* o
 
 int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) { return audit_run(c, range, nullptr, out, seg_obs, seg_pair); }
 int tj_audit_record_size(void) { return (int)sizeof(tj_audit_robot); }
+
+namespace {
+// tj_audit_timed / tj_group_audit_timed.  net_host [U][3][T] and pt_host [U]: every robot's control points and piece_time as a group read them from the owners, or null = the context's own.
+int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, tj_audit_timed_robot* out, double* seg_lo, double* seg_hi) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  if (range != range) { c->err = "tj_audit_timed: range is NaN"; return TJ_ERR_INVALID; }
+  if (levels > 6) { c->err = "tj_audit_timed: levels must be 0..6 (or negative for the default): one segment's sub-windows are one wave wide"; return TJ_ERR_INVALID; }
+  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  const Dev& d = c->d;
+  if (d.multi() && d.world > 1 && !(net_host && pt_host)) {
+    c->err = "tj_audit_timed: a sharded context does not hold the other ranks' piece_time as their owners have it; use tj_group_audit_timed";
+    return TJ_ERR_UNSUPPORTED;
+  }
+  const size_t rows = (size_t)d.U * d.S, net_n = (size_t)d.U * 3 * d.T;
+  QUIESCE(c);
+  int r;
+  if (!c->timed_out) {   // first call (or one whose allocations failed partway: what it got is kept, only the missing buffers are allocated)
+    AuditTimedArgs& a = c->timed;
+    if ((!a.row_lo && (r = dalloc(c, &a.row_lo, rows))) || (!a.row_hi && (r = dalloc(c, &a.row_hi, rows))) || (!a.row_time && (r = dalloc(c, &a.row_time, rows))) ||
+        (!a.row_qlo && (r = dalloc(c, &a.row_qlo, rows))) || (!a.row_qhi && (r = dalloc(c, &a.row_qhi, rows))) || (!c->timed_net && (r = dalloc(c, &c->timed_net, net_n))) ||
+        (!c->timed_pt && (r = dalloc(c, &c->timed_pt, d.U))) || (r = dalloc(c, &c->timed_out, d.U))) return r;
+  }
+  if (net_host && ((r = upload(c, c->timed_net, net_host, net_n * 8)) || (r = upload(c, c->timed_pt, pt_host, (size_t)d.U * 8)))) return r;
+  AuditTimedArgs a = c->timed;
+  a.net = net_host ? c->timed_net : d.spline; a.pt = net_host ? c->timed_pt : d.piece_time;
+  a.range = range > 0 ? range : d.offset + 2 * d.margin; a.levels = levels < 0 ? TJ_AUDIT_TIMED_LEVELS : levels;
+  const int owned = d.u1 - d.u0;
+  HIPCHK(c, hipMemsetAsync(c->timed_out, 0, (size_t)d.U * sizeof(tj_audit_timed_robot), c->stream));
+  if (seg_lo || seg_hi) { HIPCHK(c, hipMemsetAsync(a.row_lo, 0, rows * 8, c->stream)); HIPCHK(c, hipMemsetAsync(a.row_hi, 0, rows * 8, c->stream)); }
+  if (owned > 0) {   // two plain launches whatever the fleet's size: not part of the iteration schedules, not counted by tj_launch_count
+    hipLaunchKernelGGL(k_audit_timed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_audit_timed_reduce, dim3(owned), dim3(64), 0, c->stream, d, a, c->timed_out);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->timed_out, (size_t)d.U * sizeof(tj_audit_timed_robot), hipMemcpyDeviceToHost, c->stream));
+  if (seg_lo) HIPCHK(c, hipMemcpyAsync(seg_lo, a.row_lo, rows * 8, hipMemcpyDeviceToHost, c->stream));
+  if (seg_hi) HIPCHK(c, hipMemcpyAsync(seg_hi, a.row_hi, rows * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return TJ_OK;
+}
+}  // namespace
+
+int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi) { return audit_timed_run(c, range, levels, nullptr, nullptr, records, seg_lo, seg_hi); }
+int tj_audit_timed_record_size(void) { return (int)sizeof(tj_audit_timed_robot); }
 
 int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_armijo) {
   if (!c) return TJ_ERR_INVALID;

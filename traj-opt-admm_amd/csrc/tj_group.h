@@ -626,4 +626,30 @@ int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_o
   return TJ_OK;
 }
 
+// tj_audit_timed of every robot by the rank that owns it.  Like tj_group_audit every robot's control points are read from its owner -- and so is its piece_time, which a rank
+// holds for its own robots only: the records are bitwise those of one context.
+int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* out, double* seg_lo, double* seg_hi) {
+  if (!g || !out) return TJ_ERR_INVALID;
+  GROUP_LIVE(g);
+  const Dev& d0 = g->ctx[0]->d;
+  const int U = d0.U, S = d0.S, T = d0.T;
+  std::vector<double> net((size_t)U * 3 * T), pt(U);
+  for (int u = 0; u < U; u++) { const int rc = tj_group_get_state(g, u, &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, &pt[u]); if (rc < 0) return rc; }
+  std::vector<tj_audit_timed_robot> part(U);
+  std::vector<double> sl(seg_lo ? (size_t)U * S : 0), sh(seg_hi ? (size_t)U * S : 0);
+  for (int r = 0; r < g->n; r++) {
+    tj_ctx* c = g->ctx[r];
+    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
+    const bool own = g->n == 1;
+    const int rc = audit_timed_run(c, range, levels, own ? nullptr : net.data(), own ? nullptr : pt.data(), part.data(), seg_lo ? sl.data() : nullptr, seg_hi ? sh.data() : nullptr);
+    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
+    for (int u = c->d.u0; u < c->d.u1; u++) {
+      out[u] = part[u];
+      if (seg_lo) std::copy(sl.begin() + (size_t)u * S, sl.begin() + (size_t)(u + 1) * S, seg_lo + (size_t)u * S);
+      if (seg_hi) std::copy(sh.begin() + (size_t)u * S, sh.begin() + (size_t)(u + 1) * S, seg_hi + (size_t)u * S);
+    }
+  }
+  return TJ_OK;
+}
+
 }  // extern "C"

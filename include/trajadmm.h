@@ -231,7 +231,8 @@ int tj_audit_record_size(void);   /* sizeof(tj_audit_robot), for bindings that m
  *   levels          the level used.
  *   flags           TJ_AUDIT_TIMED_CONTACT a partner was found and timed_hi <= offset: the two ARE within offset at timed_time; TJ_AUDIT_TIMED_CLEAR
  *                   timed_lo > offset: separation certified.  Neither: undecided at this level -- raise `levels` (the bracket narrows by about 4x per
- *                   level from level 2 on; 7x and 2.4x over the first two steps, table below).  Single-UAV mode: range, -1, -1 and CLEAR.
+ *                   level from level 2 on; 7x and 2.4x over the first two steps, table below), or, beyond level 6 and for the separation itself rather than a
+ *                   bracket, call tj_closest_approach (below).  Single-UAV mode: range, -1, -1 and CLEAR.
  * range <= 0: offset + 2 * margin; +infinity is valid.  levels 0..6; < 0: the default TJ_AUDIT_TIMED_LEVELS.  levels > 6, or a NaN range: TJ_ERR_INVALID.
  * The default is the smallest level at which timed_hi - timed_lo < offset / 10 (contact decided to a tenth of the contact distance) for every robot with a
  * partner in range on the final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz and e2e_scn_b_coupled.npz (measured by tests/audit_timed_ref.py, the
@@ -253,6 +254,59 @@ typedef struct tj_audit_timed_robot {
 } tj_audit_timed_robot;
 int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);
 int tj_audit_timed_record_size(void);   /* sizeof(tj_audit_timed_robot) */
+/* ---- tj_closest_approach: the closest approach of every robot to another robot AT THE SAME FLIGHT TIME, its time and its partner, converged to a tolerance
+ * the caller names (csrc/kernels_closest.h; read-only like tj_audit_timed).  tj_audit_timed's bracket comes from a uniform split and ends at level 6 (4.73e-6
+ * above); here the same certified bounds drive a branch and bound that halves only the windows that can still hold the minimum.  Time, hover after arrival,
+ * hull formation, the cuts at the partner's segment boundaries, the restriction of both nets and the box skip are tj_audit_timed's, unchanged.  For every
+ * OWNED robot u:
+ *   seeds    the windows tj_audit_timed evaluates at levels = 0, each (u's segment tr, partner q, q's segment j or its hover, [ca, cb]) with the same box
+ *            prefilter against `range`; hi(W) and the time of the hi sample as above; lo(W) as above where the GJK's v separates the origin from the hull
+ *            (v . d_i > 0 for all six points), 0 where it does not (see the stated limit).  best = the smallest hi < range, equal values ordered by
+ *            (segment, partner, time).  The live set is {W : lo(W) < range and lo(W) < best.hi}.
+ *   round d  = 1, 2, ..: every live window is halved at cm = 0.5 * (ca + cb); if cm == ca or cm == cb it cannot be split and stays in the set as terminal
+ *            (counted in lo, halved no more).  Both children are evaluated by restricting the RAW segment hulls of u and q to the child (the parent's net is
+ *            never restricted: rounding does not accumulate with depth).  best is updated over all children of the round, in the order (hi, segment,
+ *            partner, time); then the live set becomes the children and terminals with lo < best.hi -- strict, against the round's final best, so the SET
+ *            does not depend on the order of evaluation.
+ *   bracket  lo = min(best.hi, min of lo over the live set), hi = best.hi.  Sound: a dropped window had lo >= best.hi at that time, and best.hi only falls.
+ *   stop     hi - lo <= tol (CONVERGED) | the live set is empty (CONVERGED) | every live window is terminal | d == max_depth | the live set after a round,
+ *            or after the seeding, holds more than max_windows (TRUNCATED: the record is that of the last completed round -- for the seeds the levels = 0
+ *            bracket with depth 0; `windows` counts the work of the overflowing round too).  Overflow is a property of the set's size: deterministic.
+ *   lo <= the minimum separation of u from any other robot over u's flight <= hi; hi is attained at `time` against `robot`, in u's segment `segment`;
+ *   -1, -1 (time -1.0, lo == hi == range) when nothing is closer than range.  depth: rounds of halving completed.  windows: windows evaluated for this robot
+ *   (seeds + 2 per halved window): the work done.
+ * range as tj_audit_timed (<= 0: offset + 2 * margin; +infinity valid).  tol < 0: TJ_CLOSEST_TOL; 0 is valid and means "until nothing can be split or
+ * dropped".  max_depth < 0: TJ_CLOSEST_MAX_DEPTH; above it TJ_ERR_INVALID (40 = a 52-bit mantissa, less 9 bits for a time of up to 512 segment lengths, with a
+ * margin of 3).  max_windows <= 0: TJ_CLOSEST_FRONTIER; above it TJ_ERR_INVALID.  NaN range or tol: TJ_ERR_INVALID.  Single-UAV mode: range, range, -1.0,
+ * -1, -1, depth 0, CLEAR | CONVERGED.  A plain SHARDED context (world > 1) returns TJ_ERR_UNSUPPORTED like tj_audit_timed; tj_group_closest_approach reads every
+ * robot's control points and piece_time from its owner.  Records of other ranks' robots are all zero.  Four launches whatever the fleet's size and the depth,
+ * no host loop over rounds, pairs or robots.  Changes no solver state, statistics or launch count.
+ * STATED LIMIT: DESIGN.md 3c's contact floor -- the GJK reports up to ~1e-5 instead of 0 for an origin inside the hull -- would put lo ABOVE the truth where
+ * the true separation is below that floor.  So the GJK's value counts as a lower bound only with its own certificate, a separating plane; a window without one
+ * counts lo = 0 and is never dropped, only halved: in contact lo = 0 and the search runs until hi <= tol, the windows are terminal or max_depth.  At depth 0
+ * lo is tj_audit_timed's min(timed_lo, timed_hi) unless such a window is live.  hi, time and the CONTACT flag involve no GJK: hi is attained.
+ * The default tolerance is measured (tests/closest_ref.py default_tolerance, the restatement): tol = 0 and max_depth = 40 at the default range on the final
+ * states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz and e2e_scn_b_coupled.npz; per depth the largest hi - lo over the robots with a partner in range:
+ *   depth   0        1        2        3        4        5        6        7        8        9        10       11       12       13       14       15       16       17
+ *   width   1.98e-2  2.78e-3  1.16e-3  3.19e-4  8.18e-5  1.83e-5  4.73e-6  1.35e-6  2.64e-7  6.58e-8  1.68e-8  4.10e-9  1.24e-9  3.28e-10 7.95e-11 1.18e-11 2.50e-12 0
+ * The floor is the first depth after which the width no longer shrinks by at least 2x.  Here it shrinks all the way: at depth 17 every live set has emptied
+ * (hi == lo), so the floor is the last positive width, 2.50e-12 at depth 16 (the counted rounding slack of tests/audit_timed_ref.py is 1.5e-11 at S = 40), and
+ * TJ_CLOSEST_TOL is the smallest power of ten >= 10 x that. */
+#define TJ_CLOSEST_CONTACT   1   /* a partner was found and hi <= offset: the two ARE within offset at `time` */
+#define TJ_CLOSEST_CLEAR     2   /* lo > offset: separation certified */
+#define TJ_CLOSEST_CONVERGED 4   /* hi - lo <= tol, or nothing was left that could hold a smaller separation */
+#define TJ_CLOSEST_TRUNCATED 8   /* the live set outgrew max_windows: the bracket of the last completed round is returned */
+#define TJ_CLOSEST_MAX_DEPTH 40
+#define TJ_CLOSEST_FRONTIER  4096
+#define TJ_CLOSEST_TOL 1e-10
+typedef struct tj_closest_robot {
+  double lo, hi, time;     /* lo <= min separation of u from any other robot over u's flight <= hi; hi is attained at `time` */
+  int robot, segment;      /* partner and u's segment of the hi sample; -1, -1 (time -1.0, lo == hi == range) when nothing is closer than range */
+  int depth, flags;        /* rounds of halving completed */
+  int windows, reserved;   /* windows evaluated for this robot (seeds + 2 per halved window): the work done */
+} tj_closest_robot;
+int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);
+int tj_closest_record_size(void);   /* sizeof(tj_closest_robot) */
 /* teacher forcing of the CCD / line-search stages: overwrite robot u's search direction record (direction T x 3 column-major) */
 int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_direction, double wolfe, double gn);
 
@@ -406,6 +460,7 @@ int tj_group_iterate(tj_group* g, int n_iters, double* gnorm, int* iters_total, 
 int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, double* p_lambda, double* t_slack, double* t_lambda, double* piece_time);   /* from u's owner */
 int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);   /* tj_audit of every robot by its owner, against every robot's control points as its owner holds them: bitwise one context's */
 int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);   /* tj_audit_timed of every robot by its owner; every robot's control points AND piece_time are read from its owner: bitwise one context's */
+int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);   /* tj_closest_approach of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */
 /* event-timed cost of one exchange of each buffer kind (microseconds, slowest rank's average over `reps`): us[5], kinds 2..4

@@ -32,6 +32,7 @@ EXPORTS = [
     "tj_group_init_state", "tj_group_iterate", "tj_group_get_state",
     "tj_audit", "tj_audit_record_size", "tj_group_audit",
     "tj_audit_timed", "tj_audit_timed_record_size", "tj_group_audit_timed",
+    "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -98,6 +99,26 @@ def _audit_timed(call, U, S, range, levels, per_segment):
     if per_segment:
         out["seg_lo"], out["seg_hi"] = sl, sh
     return out
+
+
+class TjClosestRobot(C.Structure):
+    """mirror of tj_closest_robot (include/trajadmm.h); tj_closest_record_size() is its sizeof on the C side"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("time", C.c_double), ("robot", C.c_int), ("segment", C.c_int),
+                ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int), ("reserved", C.c_int)]
+
+
+CLOSEST_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8)
+CLOSEST_TOL = 1e-10        # TJ_CLOSEST_TOL: what tol=None selects
+CLOSEST_MAX_DEPTH = 40     # TJ_CLOSEST_MAX_DEPTH
+CLOSEST_FRONTIER = 4096    # TJ_CLOSEST_FRONTIER
+
+
+def _closest(call, U, range, tol, max_depth, max_windows):
+    """shared by Solver.closest_approach / Group.closest_approach: call(range, tol, max_depth, max_windows, records) -> dict of numpy arrays [U]"""
+    rec = (TjClosestRobot * U)()
+    call(C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
+         C.c_int(0 if max_windows is None else int(max_windows)), rec)
+    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjClosestRobot._fields_ if n != "reserved"}
 
 
 class TrajAdmmError(RuntimeError):
@@ -518,6 +539,13 @@ class Solver:
         (TJ_ERR_UNSUPPORTED): Group.audit_timed reads every robot's piece_time from its owner."""
         return _audit_timed(lambda r, l, rec, sl, sh: self._check(self.lib.tj_audit_timed(self._ctx, r, l, rec, sl, sh)), self.U, self.S, range, levels, per_segment)
 
+    def closest_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
+        """tj_closest_approach: per robot lo <= closest approach to any other robot AT EQUAL FLIGHT TIMES <= hi, converged to `tol` (None: CLOSEST_TOL) by a
+        branch and bound over tj_audit_timed's windows; `time`, `robot`, `segment` of the hi sample (-1 where nothing is closer than `range`), `depth` rounds,
+        `windows` evaluated, `flags` (CLOSEST_FLAGS).  Dict of numpy arrays [U].  Read-only.  A sharded solver (world > 1) raises (TJ_ERR_UNSUPPORTED):
+        Group.closest_approach reads every robot's piece_time from its owner."""
+        return _closest(lambda r, t, d, w, rec: self._check(self.lib.tj_closest_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+
     def build_info(self):
         ms, dev = C.c_double(), C.c_int()
         self._check(self.lib.tj_get_build_info(self._ctx, C.byref(ms), C.byref(dev)))
@@ -631,6 +659,10 @@ class Group:
     def audit_timed(self, range=None, levels=None, per_segment=False):
         """tj_group_audit_timed: Solver.audit_timed of every robot from the rank that owns it (bitwise one context's)"""
         return _audit_timed(lambda r, l, rec, sl, sh: self._check(self.lib.tj_group_audit_timed(self._g, r, l, rec, sl, sh)), self.U, self.S, range, levels, per_segment)
+
+    def closest_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_closest_approach: Solver.closest_approach of every robot from the rank that owns it (bitwise one context's)"""
+        return _closest(lambda r, t, d, w, rec: self._check(self.lib.tj_group_closest_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

@@ -17,6 +17,9 @@
 // (searched up to RANGE; default offset + 2 * margin), peak speed and acceleration, duration, flag word.  The result file is unchanged.
 // --audit-timed [LEVELS]: after the --audit lines one line per robot from tj_audit_timed / tj_group_audit_timed -- the bracket of the closest approach to another robot at
 // equal flight times (default range; LEVELS 0..6, default the library's), the partner / segment / time of its upper end, where its lower end lies, level, flag word.
+// --closest-approach [TOL]: after the --audit-timed lines one line per robot from tj_closest_approach / tj_group_closest_approach -- the closest approach to another robot at
+// equal flight times converged to TOL (default the library's; default range), its partner / segment / time, rounds, windows evaluated, flag word -- and a fleet summary
+// (smallest hi, who, when, any contact).
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
 #include <chrono>
@@ -31,11 +34,12 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
   bool audit_timed = false; int audit_levels = -1;
+  bool closest = false; double closest_tol = -1;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -46,6 +50,7 @@ int main(int argc, char** argv) {
     else if (a == "--triangles") triangles = true;
     else if (a == "--audit") { audit = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_range = atof(argv[++i]); }
     else if (a == "--audit-timed") { audit_timed = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_levels = atoi(argv[++i]); }
+    else if (a == "--closest-approach") { closest = true; if (i + 1 < argc && argv[i + 1][0] != '-') closest_tol = atof(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -179,6 +184,21 @@ int main(int argc, char** argv) {
         std::cout << "audit-timed uav " << u << " lo " << r.timed_lo << " uav " << r.lo_robot << " seg " << r.lo_segment << " hi " << r.timed_hi << " uav " << r.timed_robot
                   << " seg " << r.timed_segment << " time " << r.timed_time << " levels " << r.levels << " flags " << r.flags << std::endl;
       }
+    }
+    if (closest) {
+      std::vector<tj_closest_robot> rec(U);
+      chk(group ? tj_group_closest_approach(grp, 0.0, closest_tol, -1, 0, rec.data()) : tj_closest_approach(ctx, 0.0, closest_tol, -1, 0, rec.data()), "tj_closest_approach");
+      std::cout.precision(17);
+      int who = -1, contact = 0;
+      for (int u = 0; u < U; u++) {
+        const tj_closest_robot& r = rec[u];
+        std::cout << "closest uav " << u << " lo " << r.lo << " hi " << r.hi << " uav " << r.robot << " seg " << r.segment << " time " << r.time << " depth " << r.depth
+                  << " windows " << r.windows << " flags " << r.flags << std::endl;
+        if (r.robot >= 0 && (who < 0 || r.hi < rec[who].hi)) who = u;
+        contact |= r.flags & TJ_CLOSEST_CONTACT;
+      }
+      if (who < 0) std::cout << "closest fleet none contact 0" << std::endl;
+      else std::cout << "closest fleet hi " << rec[who].hi << " uav " << who << " uav " << rec[who].robot << " time " << rec[who].time << " contact " << contact << std::endl;
     }
     if (!dump.empty()) {
       std::ofstream df(dump);

@@ -73,6 +73,71 @@ __device__ __forceinline__ void audit_argmin_t(double& d, int& key, double& aux,
   }
 }
 
+// ---- the pieces of one window, shared with kernels_closest.h (one set of source expressions: the two kernels' windows carry the same bits) ----
+// q's segment at t0: T(j) <= t0 < T(j + 1) in the very expressions the cuts use (the quotient only proposes); j == S: q has arrived
+__device__ __forceinline__ int timed_first_segment(double t0, double ptq, double res, int S) {
+  const double g = floor((t0 / ptq) * res);
+  int j = g >= (double)S ? S : (g > 0.0 ? (int)g : 0);
+  while (j > 0 && (j / res) * ptq > t0) j--;
+  while (j < S && ((j + 1) / res) * ptq <= t0) j++;
+  return j;
+}
+
+// q's raw hull of segment j (hover: six times its last control point) into a lane's column of a tile of stride ST
+template <int ST>
+__device__ __forceinline__ void timed_partner_fill(const Dev& D, const double* nq, int j, bool hover, double* cq) {
+  if (hover) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { const double v = hull_entry(D, nq, D.S - 1, 5, k); for (int i = 0; i < 6; i++) cq[(3 * i + k) * ST] = v; }
+  } else {
+    for (int e = 0; e < 18; e++) cq[e * ST] = hull_entry(D, nq, j, e / 3, e % 3);
+  }
+}
+
+// the same, and whether its box is within `range` of the box [blo, bhi] of u's raw hull (the skip of the header comment)
+__device__ __forceinline__ bool timed_partner_hull(const Dev& D, const double* nq, int j, bool hover, double* cq, const double (&blo)[3], const double (&bhi)[3], double range) {
+  timed_partner_fill<64>(D, nq, j, hover, cq);
+  bool near = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int i = 0; i < 6; i++) { const double v = cq[(3 * i + k) * 64]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    const double gap = fmax(lo - bhi[k], blo[k] - hi);
+    near = near && !(gap > range * 1.000001 + 1e-9);
+  }
+  return near;
+}
+
+// one window: u's raw hull pa (stride SP) restricted to [sa, sb], q's raw hull cq (stride SQ) to [ra, rb] (hover: as it is), the difference net to the column cd
+// (stride SQ); lo = its hull's GJK distance from the origin, h0 / h5 = |d_0| / |d_5|; sep (kernels_closest.h): whether the GJK's v is a separating direction
+template <int SP, int SQ>
+__device__ __forceinline__ void timed_window(const double* pa, const double* cq, double* cd, bool hover, double sa, double sb, double ra, double rb, double& lo, double& h0, double& h5, bool* sep = nullptr) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double a[6], b[6], oa[6], ob[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { a[i] = pa[(3 * i + k) * SP]; b[i] = cq[(3 * i + k) * SQ]; }
+    bez_restrict(a, sa, sb, oa);
+    if (hover) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) ob[i] = b[i];
+    } else {
+      bez_restrict(b, ra, rb, ob);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) cd[(3 * i + k) * SQ] = oa[i] - ob[i];
+  }
+  const V3 v = gjk(BodyHullS{cd, SQ}, BodyPoint{V3{0.0, 0.0, 0.0}});
+  lo = norm3(v.x, v.y, v.z);
+  h0 = norm3(cd[0], cd[SQ], cd[2 * SQ]); h5 = norm3(cd[15 * SQ], cd[16 * SQ], cd[17 * SQ]);
+  if (sep) {   // does v separate the origin from the hull (v . d_i > 0 for all six points)?  Only there is |v| a lower bound at rounding level
+    double m = INFINITY;
+#pragma unroll
+    for (int i = 0; i < 6; i++) m = fmin(m, v.x * cd[(3 * i) * SQ] + v.y * cd[(3 * i + 1) * SQ] + v.z * cd[(3 * i + 2) * SQ]);
+    *sep = m > 0.0;
+  }
+}
+
 __global__ __launch_bounds__(64) void k_audit_timed(Dev D, AuditTimedArgs A) {
   const int lane = lane_id(), S = D.S, U = D.U;
   const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
@@ -99,50 +164,16 @@ __global__ __launch_bounds__(64) void k_audit_timed(Dev D, AuditTimedArgs A) {
       if (q >= U || q == u) continue;
       const double ptq = A.pt[q];
       const double* nq = A.net + (size_t)q * 3 * D.T;
-      // q's segment at t0: T(j) <= t0 < T(j + 1) in the very expressions the cuts use (the quotient only proposes); j == S: q has arrived
-      const double g = floor((t0 / ptq) * res);
-      int j = g >= (double)S ? S : (g > 0.0 ? (int)g : 0);
-      while (j > 0 && (j / res) * ptq > t0) j--;
-      while (j < S && ((j + 1) / res) * ptq <= t0) j++;
+      int j = timed_first_segment(t0, ptq, res, S);
       do {
         const bool hover = j >= S;
         const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
         const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
-        if (hover) {
-#pragma unroll
-          for (int k = 0; k < 3; k++) { const double v = hull_entry(D, nq, S - 1, 5, k); for (int i = 0; i < 6; i++) cq[(3 * i + k) * 64] = v; }
-        } else {
-          for (int e = 0; e < 18; e++) cq[e * 64] = hull_entry(D, nq, j, e / 3, e % 3);
-        }
-        bool near = true;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          double lo = INFINITY, hi = -INFINITY;
-          for (int i = 0; i < 6; i++) { const double v = cq[(3 * i + k) * 64]; if (v < lo) lo = v; if (v > hi) hi = v; }
-          const double gap = fmax(lo - bhi[k], blo[k] - hi);
-          near = near && !(gap > range * 1.000001 + 1e-9);
-        }
-        if (near) {
+        if (timed_partner_hull(D, nq, j, hover, cq, blo, bhi, range)) {
           const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
           const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            double a[6], b[6], oa[6], ob[6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { a[i] = P[3 * i + k]; b[i] = cq[(3 * i + k) * 64]; }
-            bez_restrict(a, sa, sb, oa);
-            if (hover) {
-#pragma unroll
-              for (int i = 0; i < 6; i++) ob[i] = b[i];
-            } else {
-              bez_restrict(b, ra, rb, ob);
-            }
-#pragma unroll
-            for (int i = 0; i < 6; i++) cd[(3 * i + k) * 64] = oa[i] - ob[i];
-          }
-          const V3 v = gjk(BodyHullS{cd, 64}, BodyPoint{V3{0.0, 0.0, 0.0}});
-          const double lo = norm3(v.x, v.y, v.z);
-          const double h0 = norm3(cd[0], cd[64], cd[128]), h5 = norm3(cd[15 * 64], cd[16 * 64], cd[17 * 64]);
+          double lo, h0, h5;
+          timed_window<1, 64>(P, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5);
           const bool first = h0 <= h5;
           const double hi = first ? h0 : h5;
           if (lo < range && lo < dlo) { dlo = lo; klo = q * 64 + w; }

@@ -1,0 +1,208 @@
+// kernels_closest.h -- tj_closest_approach: every robot's closest approach to another robot at EQUAL FLIGHT TIMES, converged to a tolerance.
+//
+// tj_audit_timed brackets the separation with a UNIFORM split of every segment's window of time (2^levels parts, levels <= 6).  Here the same certified
+// bounds drive a branch and bound: a window W has lo(W) (GJK distance of the difference net's hull from the origin: nothing on W is closer) and hi(W) (an end
+// point: a separation attained at a known time).  lo counts only where the GJK's v SEPARATES the origin from the hull (v . d_i > 0 for all six points); without
+// that certificate the origin may be inside, where the GJK stops at up to ~1e-5 instead of 0, and lo(W) = 0.  A window whose lo is not below the smallest hi found so far cannot hold the minimum and is dropped; the
+// others are halved.  Time, hover, hull formation, the cuts at the partner's segment boundaries, the restriction of both nets and the box skip are
+// kernels_audit_timed.h's (timed_first_segment, timed_window: the same source expressions).  The definition (include/trajadmm.h), per owned robot u:
+//   seeds    the windows (tr, q, j, ca, cb) k_audit_timed evaluates at levels = 0.  best = the smallest hi < range, ties by (segment, partner, time);
+//            live = {lo < range and lo < best.hi}
+//   round d  every live window is halved at cm = 0.5 * (ca + cb); cm == ca or cm == cb: it stays in the set as terminal.  Both children are evaluated by
+//            restricting the RAW segment hulls (never the parent's net: rounding does not grow with depth).  best over (best, children of the round) in the
+//            order (hi, segment, partner, time); then live = the children and terminals with lo < best.hi -- compared with the round's FINAL best, so the
+//            set does not depend on the order of evaluation
+//   bracket  lo_u = min(best.hi, min lo over live), hi_u = best.hi
+//   stop     hi_u - lo_u <= tol | live empty | every live window terminal | d == max_depth | more than max_windows live (TRUNCATED: the record of the last
+//            completed round is returned; `windows` counts the overflowing round's work too)
+//
+// Four launches whatever the fleet's size and the depth:
+//   k_audit_timed (levels 0), k_audit_timed_reduce   the level-0 bracket per robot: best (hi, segment, partner, time) and the smallest lo
+//   k_closest_seed     one wave per (owned robot, segment), k_audit_timed's walk at level 0 (lane = partner of the pass).  A lane whose window has
+//                      lo < best.hi appends it to the robot's list with one integer atomic on the robot's counter (append order is free: nothing
+//                      downstream depends on it; the windows below best.hi are a handful per robot, so there is nothing for a ballot to save).  The
+//                      number of windows evaluated is summed over the wave and added once.
+//   k_closest_refine   one workgroup of CL_THREADS per owned robot runs ALL rounds.  Lanes take the CHILDREN of the live list strided (item 2 p + c =
+//                      child c of window p): the raw hulls of (u, tr) and (q, j) into the lane's columns of two LDS tiles, timed_window, lo to the robot's
+//                      klo slice.  A total-order reduction (hi, segment, partner, time) over the workgroup gives the round's best; a second pass over the
+//                      same items keeps lo < best.hi and appends to the other half of the ping-pong list (integer LDS counter), reducing min lo and "all
+//                      terminal" on the way.  The lists live in the robot's slice of a global buffer allocated on the first call (40-byte records; a
+//                      live list is a few windows, read once per round: L2 traffic, no LDS staging).  No workgroup waits on another; no polling, no
+//                      cross-queue word, nothing of the iteration's scratch.
+// Read-only: the kernels write the query's own buffers only (no tj_stats counter, no launch count).
+#pragma once
+#include "kernels_audit_timed.h"
+
+namespace tj {
+
+constexpr int CL_THREADS = 128;   // two waves: the per-lane GJK's registers and three 18-row tiles of 128 columns = 54 KB of LDS
+
+struct ClosestWin { double ca, cb, lo; int tr, q, j, term; };   // one live window: [ca, cb] in segment tr of u and segment j of q (j == S: q hovers)
+
+struct ClosestArgs {
+  const double* net;   // [U][3][T]
+  const double* pt;    // [U]
+  double range, tol;
+  int max_depth, max_windows;
+  const tj_audit_timed_robot* seed;   // [U] the level-0 bracket
+  ClosestWin* list;    // [U][2][TJ_CLOSEST_FRONTIER] ping-pong live lists
+  double* klo;         // [U][2 * TJ_CLOSEST_FRONTIER] lo of the round's children
+  int* count;          // [U][3]: live windows after seeding (may exceed max_windows: overflow), windows evaluated by the seeding, 1 = a live seed has no certificate (lo 0)
+};
+
+__global__ __launch_bounds__(64) void k_closest_seed(Dev D, ClosestArgs A) {
+  const int lane = lane_id(), S = D.S, U = D.U;
+  const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
+  __shared__ double P[18], tq[18 * 64], td[18 * 64];
+  if (lane < 18) P[lane] = hull_entry(D, A.net + (size_t)u * 3 * D.T, tr, lane / 3, lane % 3);
+  __syncthreads();
+  double blo[3], bhi[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    blo[k] = lo; bhi[k] = hi;
+  }
+  const double range = A.range, res = (double)D.res, ptu = A.pt[u], besthi = A.seed[u].timed_hi;
+  const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
+  const double t0 = ((tr + 0 / (double)1) / res) * ptu, t1 = ((tr + (0 + 1) / (double)1) / res) * ptu;   // k_audit_timed's sub-window 0 of 1
+  double* cq = tq + lane; double* cd = td + lane;
+  ClosestWin* list = A.list + (size_t)u * 2 * TJ_CLOSEST_FRONTIER;
+  int nev = 0;
+  for (int base = 0; base < U; base += 64) {
+    const int q = base + lane;
+    if (q >= U || q == u) continue;
+    const double ptq = A.pt[q];
+    const double* nq = A.net + (size_t)q * 3 * D.T;
+    int j = timed_first_segment(t0, ptq, res, S);
+    do {
+      const bool hover = j >= S;
+      const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
+      const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
+      if (timed_partner_hull(D, nq, j, hover, cq, blo, bhi, range)) {
+        const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
+        const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+        double lo, h0, h5; bool sep;
+        timed_window<1, 64>(P, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
+        if (!sep) lo = 0.0;
+        nev++;
+        if (lo < range && lo < besthi) {
+          if (!sep) atomicOr(&A.count[3 * u + 2], 1);
+          const int at = atomicAdd(&A.count[3 * u], 1);
+          if (at < A.max_windows) list[at] = ClosestWin{ca, cb, lo, tr, q, j, 0};
+        }
+      }
+      j++;
+    } while (j <= S && (j / res) * ptq < t1);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) nev += __shfl_xor(nev, off);
+  if (lane == 0 && nev) atomicAdd(&A.count[3 * u + 1], nev);
+}
+
+// the smallest (hi, segment, partner, time) in lexicographic order
+struct ClosestBest { double hi, time; int seg, q; };
+__device__ __forceinline__ bool closest_before(const ClosestBest& a, const ClosestBest& b) {
+  if (a.hi != b.hi) return a.hi < b.hi;
+  if (a.seg != b.seg) return a.seg < b.seg;
+  if (a.q != b.q) return a.q < b.q;
+  return a.time < b.time;
+}
+
+__global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArgs A, tj_closest_robot* out) {
+  constexpr int NW = CL_THREADS / 64;
+  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S, u = D.u0 + blockIdx.x;
+  __shared__ double tp[18 * CL_THREADS], tq[18 * CL_THREADS], td[18 * CL_THREADS];
+  __shared__ ClosestBest wbest[NW];
+  __shared__ double wlo[NW];
+  __shared__ int wev[NW], wterm[NW], kept;
+  const tj_audit_timed_robot seed = A.seed[u];
+  const double range = A.range, res = (double)D.res, ptu = A.pt[u];
+  const int maxw = A.max_windows;
+  const double* nu = A.net + (size_t)u * 3 * D.T;
+  ClosestWin* cur = A.list + (size_t)u * 2 * TJ_CLOSEST_FRONTIER; ClosestWin* nxt = cur + TJ_CLOSEST_FRONTIER;
+  double* klo = A.klo + (size_t)u * 2 * TJ_CLOSEST_FRONTIER;
+  double* cp = tp + tid; double* cq = tq + tid; double* cd = td + tid;
+
+  // the committed record: the level-0 bracket (every thread holds the same values)
+  ClosestBest best{seed.timed_hi, seed.timed_time, seed.timed_robot < 0 ? INT_MAX : seed.timed_segment, seed.timed_robot < 0 ? INT_MAX : seed.timed_robot};
+  double lo_u = A.count[3 * u + 2] ? 0.0 : fmin(seed.timed_lo, seed.timed_hi);   // min(best.hi, min lo over the live seeds): tj_audit_timed's, unless a live seed counts 0
+  int n = A.count[3 * u], windows = A.count[3 * u + 1], depth = 0;
+  bool truncated = n > maxw, terminal = false;   // terminal: every live window is
+  if (D.multi()) {
+    while (!truncated && !(best.hi - lo_u <= A.tol) && n > 0 && !terminal && depth < A.max_depth) {
+      // ---- pass 1: the children, one per lane ----
+      ClosestBest mine{range, 0.0, INT_MAX, INT_MAX};
+      int nev = 0;
+      for (int i = tid; i < 2 * n; i += CL_THREADS) {
+        const ClosestWin w = cur[i >> 1];
+        const int c = i & 1;
+        const double cm = 0.5 * (w.ca + w.cb);
+        if (w.term || cm == w.ca || cm == w.cb) { klo[i] = c ? INFINITY : w.lo; continue; }
+        const double ca = c ? cm : w.ca, cb = c ? w.cb : cm;
+        const bool hover = w.j >= S;
+        const double ptq = A.pt[w.q];
+        const double T0u = (w.tr / res) * ptu, T1u = ((w.tr + 1) / res) * ptu, lenu = T1u - T0u;
+        const double Tj = (w.j / res) * ptq, Tj1 = ((w.j + 1) / res) * ptq;
+        for (int e = 0; e < 18; e++) cp[e * CL_THREADS] = hull_entry(D, nu, w.tr, e / 3, e % 3);
+        timed_partner_fill<CL_THREADS>(D, A.net + (size_t)w.q * 3 * D.T, w.j, hover, cq);
+        const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
+        const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+        double lo, h0, h5; bool sep;
+        timed_window<CL_THREADS, CL_THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
+        if (!sep) lo = 0.0;
+        nev++;
+        klo[i] = lo;
+        const bool first = h0 <= h5;
+        const ClosestBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
+        if (b.hi < range && closest_before(b, mine)) mine = b;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const ClosestBest o{__shfl_xor(mine.hi, off), __shfl_xor(mine.time, off), __shfl_xor(mine.seg, off), __shfl_xor(mine.q, off)};
+        if (closest_before(o, mine)) mine = o;
+        nev += __shfl_xor(nev, off);
+      }
+      if (lane == 0) { wbest[wave] = mine; wev[wave] = nev; }
+      if (tid == 0) kept = 0;
+      __syncthreads();   // (also: every klo of the round is written)
+      ClosestBest cand = best;
+      for (int k = 0; k < NW; k++) { if (closest_before(wbest[k], cand)) cand = wbest[k]; windows += wev[k]; }
+      // ---- pass 2: keep what can still hold something below the round's best ----
+      double mlo = INFINITY; int allterm = 1;
+      for (int i = tid; i < 2 * n; i += CL_THREADS) {
+        const ClosestWin w = cur[i >> 1];
+        const int c = i & 1;
+        const double cm = 0.5 * (w.ca + w.cb), lo = klo[i];
+        const bool term = w.term || cm == w.ca || cm == w.cb;
+        if ((term && c) || !(lo < cand.hi)) continue;
+        mlo = fmin(mlo, lo); allterm &= term ? 1 : 0;
+        const int at = atomicAdd(&kept, 1);
+        if (at < maxw) nxt[at] = term ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0};
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) { mlo = fmin(mlo, __shfl_xor(mlo, off)); allterm &= __shfl_xor(allterm, off); }
+      if (lane == 0) { wlo[wave] = mlo; wterm[wave] = allterm; }
+      __syncthreads();   // (also: the new list is written, `kept` is final)
+      const int m = kept;
+      for (int k = 0; k < NW; k++) { mlo = fmin(mlo, wlo[k]); allterm &= wterm[k]; }
+      __syncthreads();   // everyone has read the round's words before the next round writes them
+      if (m > maxw) { truncated = true; break; }
+      best = cand; lo_u = fmin(best.hi, mlo); n = m; terminal = m > 0 && allterm; depth++;
+      ClosestWin* t = cur; cur = nxt; nxt = t;
+    }
+  }
+  if (tid == 0) {
+    tj_closest_robot r;
+    const bool found = best.q != INT_MAX;
+    r.lo = lo_u; r.hi = best.hi; r.time = found ? best.time : -1.0;
+    r.robot = found ? best.q : -1; r.segment = found ? best.seg : -1;
+    r.depth = depth; r.windows = windows; r.reserved = 0;
+    r.flags = !D.multi() ? (TJ_CLOSEST_CLEAR | TJ_CLOSEST_CONVERGED)
+                         : ((found && best.hi <= D.offset ? TJ_CLOSEST_CONTACT : 0) | (lo_u > D.offset ? TJ_CLOSEST_CLEAR : 0) |
+                            (best.hi - lo_u <= A.tol || (n == 0 && !truncated) ? TJ_CLOSEST_CONVERGED : 0) | (truncated ? TJ_CLOSEST_TRUNCATED : 0));
+    out[u] = r;
+  }
+}
+
+}  // namespace tj

@@ -33,6 +33,7 @@
 #include "kernels_bvh.h"
 #include "kernels_audit.h"
 #include "kernels_audit_timed.h"
+#include "kernels_closest.h"
 
 using namespace tj;
 
@@ -93,6 +94,8 @@ struct tj_ctx {
   // hands in; audit_order (sorted primitive -> caller's index) belongs to the obstacle set and goes with it (cloud_allocs)
   // tj_audit_timed's own (kernels_audit_timed.h): rows, records, the control nets and piece times a group hands in
   AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr; double* timed_net = nullptr; double* timed_pt = nullptr;
+  // tj_closest_approach's own (kernels_closest.h): the live lists, the children's lower bounds, the counters, the records
+  ClosestArgs closest{}; tj_closest_robot* closest_out = nullptr;
   AuditArgs audit{}; tj_audit_robot* audit_out = nullptr; Ctl* audit_ctl = nullptr; double* audit_net = nullptr; int* audit_order = nullptr;
 };
 
@@ -1430,6 +1433,23 @@ int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, doub
 int tj_audit_record_size(void) { return (int)sizeof(tj_audit_robot); }
 
 namespace {
+// the buffers and arguments of k_audit_timed (tj_audit_timed, and the level-0 seed bound of tj_closest_approach); the caller has quiesced the context
+int timed_setup(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, AuditTimedArgs& out) {
+  const Dev& d = c->d;
+  const size_t rows = (size_t)d.U * d.S, net_n = (size_t)d.U * 3 * d.T;
+  int r;
+  if (!c->timed_out) {   // first call (or one whose allocations failed partway: what it got is kept, only the missing buffers are allocated)
+    AuditTimedArgs& a = c->timed;
+    if ((!a.row_lo && (r = dalloc(c, &a.row_lo, rows))) || (!a.row_hi && (r = dalloc(c, &a.row_hi, rows))) || (!a.row_time && (r = dalloc(c, &a.row_time, rows))) ||
+        (!a.row_qlo && (r = dalloc(c, &a.row_qlo, rows))) || (!a.row_qhi && (r = dalloc(c, &a.row_qhi, rows))) || (!c->timed_net && (r = dalloc(c, &c->timed_net, net_n))) ||
+        (!c->timed_pt && (r = dalloc(c, &c->timed_pt, d.U))) || (r = dalloc(c, &c->timed_out, d.U))) return r;
+  }
+  if (net_host && ((r = upload(c, c->timed_net, net_host, net_n * 8)) || (r = upload(c, c->timed_pt, pt_host, (size_t)d.U * 8)))) return r;
+  out = c->timed;
+  out.net = net_host ? c->timed_net : d.spline; out.pt = net_host ? c->timed_pt : d.piece_time;
+  out.range = range > 0 ? range : d.offset + 2 * d.margin; out.levels = levels;
+  return TJ_OK;
+}
 // tj_audit_timed / tj_group_audit_timed.  net_host [U][3][T] and pt_host [U]: every robot's control points and piece_time as a group read them from the owners, or null = the context's own.
 int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, tj_audit_timed_robot* out, double* seg_lo, double* seg_hi) {
   if (!c || !out) return TJ_ERR_INVALID;
@@ -1441,19 +1461,11 @@ int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host,
     c->err = "tj_audit_timed: a sharded context does not hold the other ranks' piece_time as their owners have it; use tj_group_audit_timed";
     return TJ_ERR_UNSUPPORTED;
   }
-  const size_t rows = (size_t)d.U * d.S, net_n = (size_t)d.U * 3 * d.T;
+  const size_t rows = (size_t)d.U * d.S;
   QUIESCE(c);
-  int r;
-  if (!c->timed_out) {   // first call (or one whose allocations failed partway: what it got is kept, only the missing buffers are allocated)
-    AuditTimedArgs& a = c->timed;
-    if ((!a.row_lo && (r = dalloc(c, &a.row_lo, rows))) || (!a.row_hi && (r = dalloc(c, &a.row_hi, rows))) || (!a.row_time && (r = dalloc(c, &a.row_time, rows))) ||
-        (!a.row_qlo && (r = dalloc(c, &a.row_qlo, rows))) || (!a.row_qhi && (r = dalloc(c, &a.row_qhi, rows))) || (!c->timed_net && (r = dalloc(c, &c->timed_net, net_n))) ||
-        (!c->timed_pt && (r = dalloc(c, &c->timed_pt, d.U))) || (r = dalloc(c, &c->timed_out, d.U))) return r;
-  }
-  if (net_host && ((r = upload(c, c->timed_net, net_host, net_n * 8)) || (r = upload(c, c->timed_pt, pt_host, (size_t)d.U * 8)))) return r;
-  AuditTimedArgs a = c->timed;
-  a.net = net_host ? c->timed_net : d.spline; a.pt = net_host ? c->timed_pt : d.piece_time;
-  a.range = range > 0 ? range : d.offset + 2 * d.margin; a.levels = levels < 0 ? TJ_AUDIT_TIMED_LEVELS : levels;
+  AuditTimedArgs a;
+  int r = timed_setup(c, range, levels < 0 ? TJ_AUDIT_TIMED_LEVELS : levels, net_host, pt_host, a);
+  if (r) return r;
   const int owned = d.u1 - d.u0;
   HIPCHK(c, hipMemsetAsync(c->timed_out, 0, (size_t)d.U * sizeof(tj_audit_timed_robot), c->stream));
   if (seg_lo || seg_hi) { HIPCHK(c, hipMemsetAsync(a.row_lo, 0, rows * 8, c->stream)); HIPCHK(c, hipMemsetAsync(a.row_hi, 0, rows * 8, c->stream)); }
@@ -1472,6 +1484,52 @@ int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host,
 
 int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi) { return audit_timed_run(c, range, levels, nullptr, nullptr, records, seg_lo, seg_hi); }
 int tj_audit_timed_record_size(void) { return (int)sizeof(tj_audit_timed_robot); }
+
+namespace {
+// tj_closest_approach / tj_group_closest_approach.  net_host / pt_host as in audit_timed_run.
+int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_closest_robot* out) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  if (range != range) { c->err = "tj_closest_approach: range is NaN"; return TJ_ERR_INVALID; }
+  if (tol != tol) { c->err = "tj_closest_approach: tol is NaN"; return TJ_ERR_INVALID; }
+  if (max_depth > TJ_CLOSEST_MAX_DEPTH) { c->err = "tj_closest_approach: max_depth must be 0.." + std::to_string(TJ_CLOSEST_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
+  if (max_windows > TJ_CLOSEST_FRONTIER) { c->err = "tj_closest_approach: max_windows must be 1.." + std::to_string(TJ_CLOSEST_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
+  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  const Dev& d = c->d;
+  if (d.multi() && d.world > 1 && !(net_host && pt_host)) {
+    c->err = "tj_closest_approach: a sharded context does not hold the other ranks' piece_time as their owners have it; use tj_group_closest_approach";
+    return TJ_ERR_UNSUPPORTED;
+  }
+  QUIESCE(c);
+  AuditTimedArgs t;
+  int r = timed_setup(c, range, 0, net_host, pt_host, t);
+  if (r) return r;
+  if (!c->closest_out) {   // first call (or one whose allocations failed partway)
+    ClosestArgs& a = c->closest;
+    if ((!a.list && (r = dalloc(c, &a.list, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER))) || (!a.klo && (r = dalloc(c, &a.klo, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER))) ||
+        (!a.count && (r = dalloc(c, &a.count, (size_t)d.U * 3))) || (r = dalloc(c, &c->closest_out, d.U))) return r;
+  }
+  ClosestArgs a = c->closest;
+  a.net = t.net; a.pt = t.pt; a.range = t.range; a.tol = tol < 0 ? TJ_CLOSEST_TOL : tol;
+  a.max_depth = max_depth < 0 ? TJ_CLOSEST_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_CLOSEST_FRONTIER : max_windows;
+  a.seed = c->timed_out;
+  const int owned = d.u1 - d.u0;
+  HIPCHK(c, hipMemsetAsync(c->closest_out, 0, (size_t)d.U * sizeof(tj_closest_robot), c->stream));
+  HIPCHK(c, hipMemsetAsync(a.count, 0, (size_t)d.U * 3 * sizeof(int), c->stream));
+  if (owned > 0) {   // four plain launches whatever the fleet's size and the depth: not part of the iteration schedules, not counted by tj_launch_count
+    hipLaunchKernelGGL(k_audit_timed, dim3(owned * d.S), dim3(64), 0, c->stream, d, t);
+    hipLaunchKernelGGL(k_audit_timed_reduce, dim3(owned), dim3(64), 0, c->stream, d, t, c->timed_out);
+    hipLaunchKernelGGL(k_closest_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_closest_refine, dim3(owned), dim3(CL_THREADS), 0, c->stream, d, a, c->closest_out);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->closest_out, (size_t)d.U * sizeof(tj_closest_robot), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return TJ_OK;
+}
+}  // namespace
+
+int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records) { return closest_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, records); }
+int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
 
 int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_armijo) {
   if (!c) return TJ_ERR_INVALID;

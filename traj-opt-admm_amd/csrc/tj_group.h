@@ -652,4 +652,24 @@ int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_r
   return TJ_OK;
 }
 
+// tj_closest_approach of every robot by the rank that owns it; control points and piece_time of every robot from its owner, as tj_group_audit_timed
+int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* out) {
+  if (!g || !out) return TJ_ERR_INVALID;
+  GROUP_LIVE(g);
+  const Dev& d0 = g->ctx[0]->d;
+  const int U = d0.U, T = d0.T;
+  std::vector<double> net((size_t)U * 3 * T), pt(U);
+  for (int u = 0; u < U; u++) { const int rc = tj_group_get_state(g, u, &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, &pt[u]); if (rc < 0) return rc; }
+  std::vector<tj_closest_robot> part(U);
+  for (int r = 0; r < g->n; r++) {
+    tj_ctx* c = g->ctx[r];
+    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
+    const bool own = g->n == 1;
+    const int rc = closest_run(c, range, tol, max_depth, max_windows, own ? nullptr : net.data(), own ? nullptr : pt.data(), part.data());
+    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
+    for (int u = c->d.u0; u < c->d.u1; u++) out[u] = part[u];
+  }
+  return TJ_OK;
+}
+
 }  // extern "C"

@@ -307,6 +307,69 @@ typedef struct tj_closest_robot {
 } tj_closest_robot;
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);
 int tj_closest_record_size(void);   /* sizeof(tj_closest_robot) */
+/* ---- tj_obstacle_approach: how close the FLOWN CURVE of every robot comes to an obstacle primitive, when, and to which one, converged to a tolerance the
+ * caller names (csrc/kernels_obstacle_approach.h; read-only like tj_audit).  tj_audit's obs_clearance is the distance of a segment's 6-point hull: what the
+ * solver constrains and the right certificate for a converged state, but only a lower bound on what the vehicle does, without a time, and on the GJK's
+ * contact floor wherever a primitive lies inside a hull -- which a control net that bulges at a corner (an init file, tj_plan_init's output, a
+ * state from tj_set_state) does around points the curve misses by more than `offset`.  Here the same hull bound drives tj_closest_approach's branch and
+ * bound.  Works in all three modes (single-UAV included), for clouds and meshes.  For every OWNED robot u:
+ *   item     (segment tr, primitive i, window [sa, sb] in [0, 1] of the segment's local parameter).  Windows are dyadic, so halving at 0.5 * (sa + sb) is
+ *            exact, and with max_depth <= 40 no window is ever unsplittable: there are no terminal items.  The real time of parameter s of segment tr is
+ *            ((tr + s) / res) * piece_time[u] -- log_data's sigma * piece_time; this expression is used wherever a time is formed.
+ *   net      b_0..b_5 = the segment's raw hull (hull_entry's sums) restricted to [sa, sb] by blossoming (bez_restrict), always from the RAW hull, never
+ *            from the parent's net: rounding does not accumulate with depth.  [0, 1] returns the raw hull bit for bit.
+ *   lo(W)    |v|, v = gjk(conv{b_0..b_5}, primitive) with the hull as body 1 and the primitive as body 2 (k_audit's order), where v SEPARATES them:
+ *            v . (b_i - p_j) > 0 for all six hull points and all vertices of the primitive, evaluated as (v.x * dx + v.y * dy) + v.z * dz.  Otherwise
+ *            lo(W) = 0, and the item is never dropped, only halved (tj_closest_approach's certificate and its reason: the GJK's contact floor).
+ *   hi(W)    the smaller of the distances of b_0 and b_5 -- points of the curve, at s = sa and s = sb -- from the primitive; b_0's on equality.  A cloud
+ *            point p: norm3(b - p).  A triangle: |gjk({b}, triangle)|, a point of the Minkowski difference: an upper bound on the true distance, attained to
+ *            the triangle figure of DESIGN.md 3c.  Equal values are ordered by (hi, segment, index, s), index = the caller's.
+ *   seeds    for every segment the primitives tj_audit's walk returns at m = range (the same predicate: the primitive's box within `range` of the hull's box
+ *            on every axis, touching counts; the 49-axis cull is not used, for 3c's reason), window [0, 1].  best = the smallest hi < range over all
+ *            seeds.  The live set is {W : lo(W) < range and lo(W) < best.hi}.
+ *   round d  = 1, 2, ..: every live item is halved; both children are evaluated; best is updated over all children of the round; then the live set
+ *            becomes the children with lo < best.hi -- strict, against the round's FINAL best, so the set, and with it every field of the record
+ *            (`windows` and `depth` included), does not depend on the order of evaluation.
+ *   bracket  lo = min(best.hi, min of lo over the live set), hi = best.hi.  Sound: a dropped item had lo >= best.hi at that time, and best.hi only falls.
+ *   stop     hi - lo <= tol (CONVERGED) | the live set is empty (CONVERGED) | d == max_depth | the live set after a round, or after the seeding, holds
+ *            more than max_windows (TRUNCATED: the record is that of the last completed round -- for the seeds their own bracket with depth 0;
+ *            `windows` counts the work of the overflowing round too).  Overflow is a property of the set's size: deterministic.
+ *   lo <= min over u's flight and all primitives of dist(p_u(t), primitive) <= hi; hi is attained at `time`, against primitive `index` (the point index
+ *   of tj_set_cloud / the face index of tj_set_mesh), in segment `segment`.  depth: rounds completed.  windows: items evaluated (seeds + 2 per halved item).
+ *   Nothing within range, an empty obstacle set, tj_set_cloud with n = 0: index -1, segment -1, time -1.0, lo == hi == range, depth 0, CLEAR | CONVERGED.
+ *   Flags against `offset`, tj_closest_approach's meanings; CLEAR is lo > offset, so a search limited to range <= offset that finds nothing certifies
+ *   nothing and does not set it (tj_audit's rule for its contact flag, mirrored) -- except where there are no obstacles at all.
+ * STATED LIMIT: a certified lo is the GJK's |v|, which its stop rule (|v|^2 - v . w <= 1e-10 |v|^2) leaves up to 1e-10 |v| above the hull's distance: that,
+ * relative, is how far lo may stand above the minimum.  hi, time and the CONTACT flag involve no GJK for a cloud (hi is attained); for a mesh hi carries it too.
+ * range <= 0: offset + 2 * margin; +infinity is valid.  tol < 0: TJ_OBSTACLE_TOL; 0 is valid.  max_depth < 0: TJ_OBSTACLE_MAX_DEPTH; above it
+ * TJ_ERR_INVALID.  max_windows <= 0: TJ_OBSTACLE_FRONTIER; above it TJ_ERR_INVALID.  NaN range or tol, records == NULL, a call before tj_init_state:
+ * TJ_ERR_INVALID.  A walk frontier beyond its capacity (FRONT_CAP boxes of 8 primitives near one hull): TJ_ERR_CAPACITY, never a smaller answer.  A plain
+ * SHARDED context (world > 1) answers for its owned robots -- its own state is current, and nothing of another robot is read; records of other ranks'
+ * robots are all zero.  tj_group_obstacle_approach assembles the owners' records: bitwise one context's.  THREE launches whatever the fleet's size, the
+ * number of primitives and the depth; no host loop over rounds or robots.  Changes no solver state, statistics or launch count.
+ * The defaults are measured (tests/obstacle_approach_ref.py default_tolerance, the restatement, on the CPU): tol = 0 and max_depth = 40 at the default range
+ * on the final states of tests/golden/e2e_scn_a.npz, e2e_scn_b.npz, e2e_scn_c3.npz and e2e_scn_b_coupled.npz with their scenes' clouds; per depth the largest
+ * hi - lo over the robots with a primitive in range:
+ *   depth   0        1        2        3        4        5        6        7        8        9        10       11       12       13       14       15       16       17       18       19
+ *   width   1.35e-2  8.51e-3  4.92e-3  9.91e-4  5.96e-4  1.90e-4  3.33e-5  1.20e-5  2.65e-6  1.96e-7  1.96e-7  2.14e-8  6.27e-9  2.35e-9  5.59e-10 1.40e-10 4.77e-11 8.14e-12 3.71e-13 0
+ * The width shrinks all the way: at depth 19 every live set has emptied (hi == lo), so the floor is the last positive width, 3.71e-13 at depth 18, and
+ * TJ_OBSTACLE_TOL is the smallest power of ten >= 10 x that.  The largest live set any robot of these runs holds at any depth is 9 items;
+ * TJ_OBSTACLE_FRONTIER is the next power of two >= 4 x that (real clouds are denser than the fixtures'), and at least 4096. */
+#define TJ_OBSTACLE_CONTACT   1   /* a primitive was found and hi <= offset: the curve IS within offset of primitive `index` at `time` */
+#define TJ_OBSTACLE_CLEAR     2   /* lo > offset: clearance of the flown curve certified */
+#define TJ_OBSTACLE_CONVERGED 4   /* hi - lo <= tol, or nothing was left that could hold a smaller distance */
+#define TJ_OBSTACLE_TRUNCATED 8   /* the live set outgrew max_windows: the bracket of the last completed round is returned */
+#define TJ_OBSTACLE_MAX_DEPTH 40
+#define TJ_OBSTACLE_FRONTIER  4096   /* measured maximum of the live set: 9 */
+#define TJ_OBSTACLE_TOL 1e-11
+typedef struct tj_obstacle_robot {
+  double lo, hi, time;     /* lo <= min over u's flight and all primitives of dist(p_u(t), primitive) <= hi; hi is attained at `time` */
+  int index, segment;      /* the primitive (caller's index) and u's segment of the hi sample; -1, -1 (time -1.0, lo == hi == range) when nothing is within range */
+  int depth, flags;        /* rounds of halving completed */
+  int windows, reserved;   /* items evaluated for this robot (seeds + 2 per halved item): the work done */
+} tj_obstacle_robot;
+int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);
+int tj_obstacle_record_size(void);   /* sizeof(tj_obstacle_robot) */
 /* teacher forcing of the CCD / line-search stages: overwrite robot u's search direction record (direction T x 3 column-major) */
 int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_direction, double wolfe, double gn);
 
@@ -461,6 +524,7 @@ int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, doub
 int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);   /* tj_audit of every robot by its owner, against every robot's control points as its owner holds them: bitwise one context's */
 int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);   /* tj_audit_timed of every robot by its owner; every robot's control points AND piece_time are read from its owner: bitwise one context's */
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);   /* tj_closest_approach of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
+int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */
 /* event-timed cost of one exchange of each buffer kind (microseconds, slowest rank's average over `reps`): us[5], kinds 2..4

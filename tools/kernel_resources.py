@@ -15,15 +15,21 @@ def resources(lib):
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], cwd=tmp, check=True, capture_output=True)
         cos = [f for f in os.listdir(tmp) if "amdgcn" in f]
         notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(tmp, cos[0])], check=True, capture_output=True, text=True).stdout
-    name, d = None, {}
-    for line in notes.splitlines():
-        m = re.search(r"\.name:\s+(\S+)", line)
+    # one entry per kernel under amdhsa.kernels: "  - .agpr_count: .." opens it, its own keys are indented by four (the keys of its .args entries by
+    # eight or more, their .name among them), and .name comes AFTER .agpr_count and .group_segment_fixed_size: collect the entry, then file it under its name
+    d, cur = {}, None
+    keys = ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count", "name")
+    for line in notes.splitlines() + ["  - .end: 0"]:
+        m = re.match(r"^  - \.(\w+):\s*(\S*)", line)
         if m:
-            name = m.group(1); d[name] = {}
-        for k in ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count"):
-            m = re.search(r"\." + k + r":\s+(\d+)", line)
-            if m and name:
-                d[name][k] = int(m.group(1))
+            if cur and "name" in cur:
+                name = cur.pop("name")
+                d[name] = {k: int(v) for k, v in cur.items()}
+            cur = {}
+        else:
+            m = re.match(r"^    \.(\w+):\s*(\S*)", line)
+        if m and cur is not None and m.group(1) in keys:
+            cur[m.group(1)] = m.group(2)
     return d
 
 

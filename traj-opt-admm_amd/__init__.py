@@ -33,6 +33,7 @@ EXPORTS = [
     "tj_audit", "tj_audit_record_size", "tj_group_audit",
     "tj_audit_timed", "tj_audit_timed_record_size", "tj_group_audit_timed",
     "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
+    "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -119,6 +120,26 @@ def _closest(call, U, range, tol, max_depth, max_windows):
     call(C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
          C.c_int(0 if max_windows is None else int(max_windows)), rec)
     return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjClosestRobot._fields_ if n != "reserved"}
+
+
+class TjObstacleRobot(C.Structure):
+    """mirror of tj_obstacle_robot (include/trajadmm.h); tj_obstacle_record_size() is its sizeof on the C side"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("time", C.c_double), ("index", C.c_int), ("segment", C.c_int),
+                ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int), ("reserved", C.c_int)]
+
+
+OBSTACLE_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8)
+OBSTACLE_TOL = 1e-11        # TJ_OBSTACLE_TOL: what tol=None selects
+OBSTACLE_MAX_DEPTH = 40     # TJ_OBSTACLE_MAX_DEPTH
+OBSTACLE_FRONTIER = 4096    # TJ_OBSTACLE_FRONTIER
+
+
+def _obstacle(call, U, range, tol, max_depth, max_windows):
+    """shared by Solver.obstacle_approach / Group.obstacle_approach: call(range, tol, max_depth, max_windows, records) -> dict of numpy arrays [U]"""
+    rec = (TjObstacleRobot * U)()
+    call(C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
+         C.c_int(0 if max_windows is None else int(max_windows)), rec)
+    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjObstacleRobot._fields_ if n != "reserved"}
 
 
 class TrajAdmmError(RuntimeError):
@@ -546,6 +567,13 @@ class Solver:
         Group.closest_approach reads every robot's piece_time from its owner."""
         return _closest(lambda r, t, d, w, rec: self._check(self.lib.tj_closest_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
+    def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
+        """tj_obstacle_approach: per robot lo <= closest approach of the FLOWN CURVE to any obstacle primitive <= hi, converged to `tol` (None: OBSTACLE_TOL)
+        by a branch and bound over windows of the segments' hulls; `time`, `index` (the caller's point / face index), `segment` of the hi sample (-1 where
+        nothing is within `range`), `depth` rounds, `windows` evaluated, `flags` (OBSTACLE_FLAGS).  Dict of numpy arrays [U].  Read-only.  All modes; a
+        sharded solver (world > 1) answers for its owned robots, the other records are zero."""
+        return _obstacle(lambda r, t, d, w, rec: self._check(self.lib.tj_obstacle_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+
     def build_info(self):
         ms, dev = C.c_double(), C.c_int()
         self._check(self.lib.tj_get_build_info(self._ctx, C.byref(ms), C.byref(dev)))
@@ -663,6 +691,10 @@ class Group:
     def closest_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_closest_approach: Solver.closest_approach of every robot from the rank that owns it (bitwise one context's)"""
         return _closest(lambda r, t, d, w, rec: self._check(self.lib.tj_group_closest_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+
+    def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""
+        return _obstacle(lambda r, t, d, w, rec: self._check(self.lib.tj_group_obstacle_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

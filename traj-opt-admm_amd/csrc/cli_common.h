@@ -172,4 +172,19 @@ inline void log_data(const double* spline, int P, const double* convert, double 
   }
 }
 
+// --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
+inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
+  std::cout.precision(17);
+  int who = -1, contact = 0;
+  for (size_t u = 0; u < rec.size(); u++) {
+    const tj_obstacle_robot& r = rec[u];
+    std::cout << "obstacle uav " << u << " lo " << r.lo << " hi " << r.hi << " id " << r.index << " seg " << r.segment << " time " << r.time << " depth " << r.depth
+              << " windows " << r.windows << " flags " << r.flags << std::endl;
+    if (r.index >= 0 && (who < 0 || r.hi < rec[who].hi)) who = (int)u;
+    contact |= r.flags & TJ_OBSTACLE_CONTACT;
+  }
+  if (who < 0) std::cout << "obstacle fleet none contact 0" << std::endl;
+  else std::cout << "obstacle fleet hi " << rec[who].hi << " uav " << who << " id " << rec[who].index << " time " << rec[who].time << " contact " << contact << std::endl;
+}
+
 }  // namespace tjcli

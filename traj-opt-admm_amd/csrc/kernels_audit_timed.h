@@ -73,6 +73,24 @@ __device__ __forceinline__ void audit_argmin_t(double& d, int& key, double& aux,
   }
 }
 
+// the certificate of a GJK result v = (nearest point of body 1) - (nearest point of body 2): v . (a_i - b_j) > 0 for every vertex pair, i.e. v is a separating
+// direction and |v| a lower bound on the distance at rounding level.  Without it the bodies may touch, where the GJK stops at up to ~1e-5 instead
+// of 0.  Shared by timed_window (body 2 = the origin: d - 0 is d, the bits of its first form) and kernels_obstacle_approach.h.
+template <class B1, class B2>
+__device__ __forceinline__ bool gjk_separates(const V3& v, const B1& b1, const B2& b2) {
+  double m = INFINITY;
+#pragma unroll
+  for (int i = 0; i < B1::N; i++) {
+    const V3 a = b1.get(i);
+#pragma unroll
+    for (int j = 0; j < B2::N; j++) {
+      const V3 b = b2.get(j);
+      m = fmin(m, v.x * (a.x - b.x) + v.y * (a.y - b.y) + v.z * (a.z - b.z));
+    }
+  }
+  return m > 0.0;
+}
+
 // ---- the pieces of one window, shared with kernels_closest.h (one set of source expressions: the two kernels' windows carry the same bits) ----
 // q's segment at t0: T(j) <= t0 < T(j + 1) in the very expressions the cuts use (the quotient only proposes); j == S: q has arrived
 __device__ __forceinline__ int timed_first_segment(double t0, double ptq, double res, int S) {
@@ -130,12 +148,8 @@ __device__ __forceinline__ void timed_window(const double* pa, const double* cq,
   const V3 v = gjk(BodyHullS{cd, SQ}, BodyPoint{V3{0.0, 0.0, 0.0}});
   lo = norm3(v.x, v.y, v.z);
   h0 = norm3(cd[0], cd[SQ], cd[2 * SQ]); h5 = norm3(cd[15 * SQ], cd[16 * SQ], cd[17 * SQ]);
-  if (sep) {   // does v separate the origin from the hull (v . d_i > 0 for all six points)?  Only there is |v| a lower bound at rounding level
-    double m = INFINITY;
-#pragma unroll
-    for (int i = 0; i < 6; i++) m = fmin(m, v.x * cd[(3 * i) * SQ] + v.y * cd[(3 * i + 1) * SQ] + v.z * cd[(3 * i + 2) * SQ]);
-    *sep = m > 0.0;
-  }
+  // does v separate the origin from the hull (v . d_i > 0 for all six points)?  Only there is |v| a lower bound at rounding level
+  if (sep) *sep = gjk_separates(v, BodyHullS{cd, SQ}, BodyPoint{V3{0.0, 0.0, 0.0}});
 }
 
 __global__ __launch_bounds__(64) void k_audit_timed(Dev D, AuditTimedArgs A) {

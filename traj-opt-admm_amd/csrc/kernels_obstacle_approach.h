@@ -1,0 +1,251 @@
+// kernels_obstacle_approach.h -- tj_obstacle_approach: how close the FLOWN CURVE of every robot comes to an obstacle primitive, when, and to which one.
+//
+// tj_audit's obs_clearance is the distance of a segment's 6-point HULL from the obstacles: what the solver constrains, a lower bound on what the vehicle does,
+// without a time, and on the GJK's contact floor wherever a primitive lies inside a hull the curve itself stays clear of (an init file, tj_plan_init's
+// output, a loaded state).  Here the hull bound drives tj_closest_approach's branch and bound (kernels_closest.h) over windows of ONE segment's parameter:
+// an item is (segment tr, primitive i, window [sa, sb] in [0, 1]); its net is the RAW hull (hull_entry's sums) restricted to the window by bez_restrict
+// (never the parent's net: rounding does not grow with depth; [0, 1] returns the raw hull bit for bit); lo(W) = |gjk(net's hull, primitive)| (hull = body 1, as
+// k_audit) where the GJK's v SEPARATES the two (gjk_separates: v . (b_i - p_j) > 0 for all six points and all vertices), 0 otherwise; hi(W) = the smaller of
+// b_0's and b_5's distance to the primitive, points of the curve at the window's ends: attained, at a known time.  Windows are dyadic: halving is exact, and
+// with max_depth <= 40 none is ever unsplittable.  The definition (include/trajadmm.h), per owned robot u:
+//   seeds    per segment the primitives k_audit's walk returns at m = range (the leaf predicate in fp64 on the primitives themselves), window [0, 1].
+//            best = the smallest hi < range, equal values ordered by (hi, segment, index, s); live = {lo < range and lo < best.hi}
+//   round d  every live item is halved at 0.5 * (sa + sb); both children are evaluated from the raw hull; best over (best, children of the round); then
+//            live = the children with lo < best.hi -- against the round's FINAL best, so the set does not depend on the order of evaluation
+//   bracket  lo_u = min(best.hi, min lo over live), hi_u = best.hi
+//   stop     hi_u - lo_u <= tol | live empty | d == max_depth | more than max_windows live (TRUNCATED: the record of the last completed round)
+//
+// THREE launches whatever the fleet's size, the number of primitives and the depth:
+//   k_obst_seed     one wave per (owned robot, segment): hull, BVH walk (bvh_query<1, PRIM> at m = range, the 49-axis cull is not used: DESIGN.md 3c), per
+//                   candidate and lane hi and its end; a total-order reduction over the wave gives the row's best; the candidates are counted once per wave.
+//   k_obst_append   the same walk again, now that every row of the robot is final: each wave reduces the robot's S rows to its best (S <= 504 records: less
+//                   than one step of the walk), then per candidate and lane the certified lo; an item with lo < best.hi is appended to the robot's list with
+//                   one integer atomic (append order is free: nothing downstream depends on it).  The row's smallest live lo goes to the row, so that the
+//                   seed bracket is exact even where the list overflows.
+//   k_obst_refine   one workgroup of OA_THREADS per owned robot runs ALL rounds over a ping-pong list in global memory (32-byte items + the children's lo):
+//                   lanes take the children strided, restrict the raw hull in registers into their column of one LDS tile, run the per-lane GJK; a
+//                   total-order reduction over the workgroup gives the round's best; a second pass keeps lo < best.hi (integer LDS counter).
+// No float atomics, no workgroup waits on another, no polling, no cross-queue word, nothing of the iteration's scratch.  Read-only: the kernels write the
+// query's own buffers only; the walk's overflow bit goes to a control block of the query's own (Dev::ctl of the COPY the kernels receive).
+#pragma once
+#include "kernels_closest.h"
+
+namespace tj {
+
+constexpr int OA_THREADS = 128;   // two waves: the per-lane GJK's registers, one 18-row tile of 128 columns
+
+struct ObstItem { double sa, sb, lo; int tr, pt; };   // window [sa, sb] of segment tr against the SORTED primitive pt
+struct ObstBest { double hi, s; int seg, idx; };      // idx: the caller's index; nothing found: hi = range, INT_MAX, INT_MAX
+
+struct ObstArgs {
+  const double* net;     // [U][3][T]
+  const double* pt;      // [U]
+  const int* order;      // sorted primitive -> index in the caller's obstacle list
+  double range, tol;
+  int max_depth, max_windows, cap;
+  ObstBest* row;         // [U][S] the best seed of the row
+  double* row_lo;        // [U][S] the smallest lo among the row's live seeds (INFINITY: none)
+  ObstBest* best;        // [U] the best seed of the robot
+  ObstItem* list;        // [owned][2][cap] ping-pong live lists
+  double* klo;           // [owned][2 * cap] lo of the round's children
+  int* count;            // [U][2]: live seeds (may exceed max_windows: overflow), seeds evaluated
+};
+
+// the smaller of two records in the order (hi, segment, index, s)
+__device__ __forceinline__ bool obst_before(const ObstBest& a, const ObstBest& b) {
+  if (a.hi != b.hi) return a.hi < b.hi;
+  if (a.seg != b.seg) return a.seg < b.seg;
+  if (a.idx != b.idx) return a.idx < b.idx;
+  return a.s < b.s;
+}
+__device__ __forceinline__ void obst_wave_best(ObstBest& m) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const ObstBest o{__shfl_xor(m.hi, off), __shfl_xor(m.s, off), __shfl_xor(m.seg, off), __shfl_xor(m.idx, off)};
+    if (obst_before(o, m)) m = o;
+  }
+}
+
+// distance of a point of the curve from a primitive: a cloud point directly; a triangle through the GJK of the one-point body (a point of the Minkowski
+// difference: an upper bound on the true distance, attained to the triangle figure of DESIGN.md 3c)
+template <int PRIM>
+__device__ __forceinline__ double obst_point_dist(const V3& b, const typename PrimOf<PRIM>::Body& prim) {
+  if constexpr (PRIM == 1) return norm3(b.x - prim.q.x, b.y - prim.q.y, b.z - prim.q.z);
+  else { const V3 v = gjk(BodyPoint{b}, prim); return norm3(v.x, v.y, v.z); }
+}
+
+// the unit's hull and its box
+__device__ __forceinline__ void obst_hull(const Dev& D, const double* net, int tr, double* P, QBox& q) {
+  const int lane = lane_id();
+  if (lane < 18) P[lane] = hull_entry(D, net, tr, lane / 3, lane % 3);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    q.lo[k] = lo; q.hi[k] = hi;
+  }
+}
+
+template <int PRIM>
+__global__ __launch_bounds__(64) void k_obst_seed(Dev D, ObstArgs A) {
+  const int lane = lane_id(), S = D.S;
+  const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
+  __shared__ double P[18];
+  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  QBox q;
+  obst_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
+  const double range = A.range;
+  ObstBest mine{range, 0.0, INT_MAX, INT_MAX};
+  int nev = 0;
+  bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
+    if (pt >= 0) {
+      const auto prim = PrimOf<PRIM>::load(D, pt);
+      const double h0 = obst_point_dist<PRIM>(V3{P[0], P[1], P[2]}, prim), h5 = obst_point_dist<PRIM>(V3{P[15], P[16], P[17]}, prim);
+      const bool first = h0 <= h5;
+      const ObstBest b{first ? h0 : h5, first ? 0.0 : 1.0, tr, A.order[pt]};
+      nev++;
+      if (b.hi < range && obst_before(b, mine)) mine = b;
+    }
+  });
+  obst_wave_best(mine);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) nev += __shfl_xor(nev, off);
+  if (lane == 0) {
+    A.row[(size_t)u * S + tr] = mine;
+    if (nev) atomicAdd(&A.count[2 * u + 1], nev);
+  }
+}
+
+template <int PRIM>
+__global__ __launch_bounds__(64) void k_obst_append(Dev D, ObstArgs A) {
+  const int lane = lane_id(), S = D.S;
+  const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
+  __shared__ double P[18];
+  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  QBox q;
+  obst_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
+  const double range = A.range;
+  ObstBest best{range, 0.0, INT_MAX, INT_MAX};
+  for (int r = lane; r < S; r += 64) { const ObstBest b = A.row[(size_t)u * S + r]; if (obst_before(b, best)) best = b; }
+  obst_wave_best(best);
+  if (tr == 0 && lane == 0) A.best[u] = best;
+  ObstItem* list = A.list + (size_t)ui * 2 * A.cap;
+  double mlo = INFINITY;
+  bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
+    if (pt >= 0) {
+      const auto prim = PrimOf<PRIM>::load(D, pt);
+      const BodyHull hull{P};
+      const V3 v = gjk(hull, prim);
+      double lo = norm3(v.x, v.y, v.z);
+      if (!gjk_separates(v, hull, prim)) lo = 0.0;
+      if (lo < range && lo < best.hi) {
+        mlo = fmin(mlo, lo);
+        const int at = atomicAdd(&A.count[2 * u], 1);
+        if (at < A.max_windows) list[at] = ObstItem{0.0, 1.0, lo, tr, pt};
+      }
+    }
+  });
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mlo = fmin(mlo, __shfl_xor(mlo, off));
+  if (lane == 0) A.row_lo[(size_t)u * S + tr] = mlo;
+}
+
+template <int PRIM>
+__global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, tj_obstacle_robot* out) {
+  constexpr int NW = OA_THREADS / 64;
+  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S, ui = blockIdx.x, u = D.u0 + ui;
+  __shared__ double td[18 * OA_THREADS];
+  __shared__ ObstBest wbest[NW];
+  __shared__ double wlo[NW];
+  __shared__ int kept;
+  const double range = A.range, res = (double)D.res, ptu = A.pt[u];
+  const int maxw = A.max_windows;
+  const double* nu = A.net + (size_t)u * 3 * D.T;
+  ObstItem* cur = A.list + (size_t)ui * 2 * A.cap; ObstItem* nxt = cur + A.cap;
+  double* klo = A.klo + (size_t)ui * 2 * A.cap;
+  double* cd = td + tid;
+
+  // the committed record: the seeds' bracket (every thread holds the same values)
+  ObstBest best = A.best[u];
+  double mlo = INFINITY;
+  for (int r = tid; r < S; r += OA_THREADS) mlo = fmin(mlo, A.row_lo[(size_t)u * S + r]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mlo = fmin(mlo, __shfl_xor(mlo, off));
+  if (lane == 0) wlo[wave] = mlo;
+  __syncthreads();
+  for (int k = 0; k < NW; k++) mlo = fmin(mlo, wlo[k]);
+  __syncthreads();
+  double lo_u = fmin(best.hi, mlo);
+  int n = A.count[2 * u], windows = A.count[2 * u + 1], depth = 0;
+  bool truncated = n > maxw;
+  while (!truncated && !(best.hi - lo_u <= A.tol) && n > 0 && depth < A.max_depth) {
+    // ---- pass 1: the children, one per lane ----
+    ObstBest mine{range, 0.0, INT_MAX, INT_MAX};
+    for (int i = tid; i < 2 * n; i += OA_THREADS) {
+      const ObstItem w = cur[i >> 1];
+      const int c = i & 1;
+      const double sm = 0.5 * (w.sa + w.sb), sa = c ? sm : w.sa, sb = c ? w.sb : sm;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        double a[6], o[6];
+#pragma unroll
+        for (int j = 0; j < 6; j++) a[j] = hull_entry(D, nu, w.tr, j, k);
+        bez_restrict(a, sa, sb, o);
+#pragma unroll
+        for (int j = 0; j < 6; j++) cd[(3 * j + k) * OA_THREADS] = o[j];
+      }
+      const auto prim = PrimOf<PRIM>::load(D, w.pt);
+      const BodyHullS hull{cd, OA_THREADS};
+      const V3 v = gjk(hull, prim);
+      double lo = norm3(v.x, v.y, v.z);
+      if (!gjk_separates(v, hull, prim)) lo = 0.0;
+      klo[i] = lo;
+      const double h0 = obst_point_dist<PRIM>(hull.get(0), prim), h5 = obst_point_dist<PRIM>(hull.get(5), prim);
+      const bool first = h0 <= h5;
+      const ObstBest b{first ? h0 : h5, first ? sa : sb, w.tr, A.order[w.pt]};
+      if (b.hi < range && obst_before(b, mine)) mine = b;
+    }
+    obst_wave_best(mine);
+    if (lane == 0) wbest[wave] = mine;
+    if (tid == 0) kept = 0;
+    __syncthreads();   // (also: every klo of the round is written)
+    ObstBest cand = best;
+    for (int k = 0; k < NW; k++) if (obst_before(wbest[k], cand)) cand = wbest[k];
+    windows += 2 * n;
+    // ---- pass 2: keep what can still hold something below the round's best ----
+    mlo = INFINITY;
+    for (int i = tid; i < 2 * n; i += OA_THREADS) {
+      const double lo = klo[i];
+      if (!(lo < cand.hi)) continue;
+      const ObstItem w = cur[i >> 1];
+      const int c = i & 1;
+      const double sm = 0.5 * (w.sa + w.sb);
+      mlo = fmin(mlo, lo);
+      const int at = atomicAdd(&kept, 1);
+      if (at < maxw) nxt[at] = ObstItem{c ? sm : w.sa, c ? w.sb : sm, lo, w.tr, w.pt};
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mlo = fmin(mlo, __shfl_xor(mlo, off));
+    if (lane == 0) wlo[wave] = mlo;
+    __syncthreads();   // (also: the new list is written, `kept` is final)
+    const int m = kept;
+    for (int k = 0; k < NW; k++) mlo = fmin(mlo, wlo[k]);
+    __syncthreads();   // everyone has read the round's words before the next round writes them
+    if (m > maxw) { truncated = true; break; }
+    best = cand; lo_u = fmin(best.hi, mlo); n = m; depth++;
+    ObstItem* t = cur; cur = nxt; nxt = t;
+  }
+  if (tid == 0) {
+    tj_obstacle_robot r;
+    const bool found = best.idx != INT_MAX;
+    r.lo = lo_u; r.hi = best.hi; r.time = found ? ((best.seg + best.s) / res) * ptu : -1.0;   // log_data's sigma * piece_time
+    r.index = found ? best.idx : -1; r.segment = found ? best.seg : -1;
+    r.depth = depth; r.windows = windows; r.reserved = 0;
+    r.flags = (found && best.hi <= D.offset ? TJ_OBSTACLE_CONTACT : 0) | (lo_u > D.offset || D.N == 0 ? TJ_OBSTACLE_CLEAR : 0) |
+              (best.hi - lo_u <= A.tol || (n == 0 && !truncated) ? TJ_OBSTACLE_CONVERGED : 0) | (truncated ? TJ_OBSTACLE_TRUNCATED : 0);
+    out[u] = r;
+  }
+}
+
+}  // namespace tj

@@ -34,6 +34,7 @@
 #include "kernels_audit.h"
 #include "kernels_audit_timed.h"
 #include "kernels_closest.h"
+#include "kernels_obstacle_approach.h"
 
 using namespace tj;
 
@@ -96,6 +97,8 @@ struct tj_ctx {
   AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr; double* timed_net = nullptr; double* timed_pt = nullptr;
   // tj_closest_approach's own (kernels_closest.h): the live lists, the children's lower bounds, the counters, the records
   ClosestArgs closest{}; tj_closest_robot* closest_out = nullptr;
+  // tj_obstacle_approach's own (kernels_obstacle_approach.h): rows, the live lists, the children's lower bounds, the counters, its control block, the records
+  ObstArgs obst{}; tj_obstacle_robot* obst_out = nullptr; Ctl* obst_ctl = nullptr;
   AuditArgs audit{}; tj_audit_robot* audit_out = nullptr; Ctl* audit_ctl = nullptr; double* audit_net = nullptr; int* audit_order = nullptr;
 };
 
@@ -1530,6 +1533,57 @@ int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_wind
 
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records) { return closest_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, records); }
 int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
+
+// tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
+int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  if (range != range) { c->err = "tj_obstacle_approach: range is NaN"; return TJ_ERR_INVALID; }
+  if (tol != tol) { c->err = "tj_obstacle_approach: tol is NaN"; return TJ_ERR_INVALID; }
+  if (max_depth > TJ_OBSTACLE_MAX_DEPTH) { c->err = "tj_obstacle_approach: max_depth must be 0.." + std::to_string(TJ_OBSTACLE_MAX_DEPTH) + " (or negative for the default): deeper windows are not dyadic in a double"; return TJ_ERR_INVALID; }
+  if (max_windows > TJ_OBSTACLE_FRONTIER) { c->err = "tj_obstacle_approach: max_windows must be 1.." + std::to_string(TJ_OBSTACLE_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
+  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  const Dev& d = c->d;
+  const int owned = d.u1 - d.u0;
+  const size_t rows = (size_t)d.U * d.S, items = (size_t)(owned > 0 ? owned : 1) * 2 * TJ_OBSTACLE_FRONTIER;
+  QUIESCE(c);
+  int r;
+  if (!c->obst_out) {   // first call (or one whose allocations failed partway: what it got is kept)
+    ObstArgs& a = c->obst;
+    if ((!a.row && (r = dalloc(c, &a.row, rows))) || (!a.row_lo && (r = dalloc(c, &a.row_lo, rows))) || (!a.best && (r = dalloc(c, &a.best, d.U))) ||
+        (!a.list && (r = dalloc(c, &a.list, items))) || (!a.klo && (r = dalloc(c, &a.klo, items))) || (!a.count && (r = dalloc(c, &a.count, (size_t)d.U * 2))) ||
+        (!c->obst_ctl && (r = dalloc(c, &c->obst_ctl, 1))) || (r = dalloc(c, &c->obst_out, d.U))) return r;
+  }
+  if (d.N > 0 && !c->audit_order) {   // sorted primitive -> caller's index: tj_audit's table, made by whichever of the two runs first
+    if ((r = dalloc(c, &c->audit_order, d.N, &c->cloud_allocs)) || (r = upload(c, c->audit_order, c->cloud_order.data(), (size_t)d.N * 4))) return r;
+  }
+  ObstArgs a = c->obst;
+  a.net = d.spline; a.pt = d.piece_time; a.order = c->audit_order;
+  a.range = range > 0 ? range : d.offset + 2 * d.margin; a.tol = tol < 0 ? TJ_OBSTACLE_TOL : tol;
+  a.max_depth = max_depth < 0 ? TJ_OBSTACLE_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_OBSTACLE_FRONTIER : max_windows; a.cap = TJ_OBSTACLE_FRONTIER;
+  Dev da = d; da.ctl = c->obst_ctl;   // (the walk reports a frontier overflow through Dev::ctl: the query's own block, never the solver's)
+  HIPCHK(c, hipMemsetAsync(c->obst_ctl, 0, sizeof(Ctl), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->obst_out, 0, (size_t)d.U * sizeof(tj_obstacle_robot), c->stream));
+  HIPCHK(c, hipMemsetAsync(a.count, 0, (size_t)d.U * 2 * sizeof(int), c->stream));
+  if (owned > 0) {   // three plain launches whatever the fleet's size, the number of primitives and the depth: not part of the iteration schedules, not counted by tj_launch_count
+    if (d.prim == 3) {
+      hipLaunchKernelGGL(k_obst_seed<3>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+      hipLaunchKernelGGL(k_obst_append<3>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+      hipLaunchKernelGGL(k_obst_refine<3>, dim3(owned), dim3(OA_THREADS), 0, c->stream, da, a, c->obst_out);
+    } else {
+      hipLaunchKernelGGL(k_obst_seed<1>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+      hipLaunchKernelGGL(k_obst_append<1>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+      hipLaunchKernelGGL(k_obst_refine<1>, dim3(owned), dim3(OA_THREADS), 0, c->stream, da, a, c->obst_out);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  int err = 0;
+  HIPCHK(c, hipMemcpyAsync(&err, &c->obst_ctl->error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->obst_out, (size_t)d.U * sizeof(tj_obstacle_robot), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (err & ERR_FRONT_OVERFLOW) { c->err = "tj_obstacle_approach: the BVH frontier of a segment overflowed at this range (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one hull): lower `range`"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+int tj_obstacle_record_size(void) { return (int)sizeof(tj_obstacle_robot); }
 
 int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_armijo) {
   if (!c) return TJ_ERR_INVALID;

@@ -672,4 +672,20 @@ int tj_group_closest_approach(tj_group* g, double range, double tol, int max_dep
   return TJ_OK;
 }
 
+// tj_obstacle_approach of every robot by the rank that owns it, from that rank's own state (nothing of another robot is read)
+int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
+  if (!g || !out) return TJ_ERR_INVALID;
+  GROUP_LIVE(g);
+  const int U = g->ctx[0]->d.U;
+  std::vector<tj_obstacle_robot> part(U);
+  for (int r = 0; r < g->n; r++) {
+    tj_ctx* c = g->ctx[r];
+    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
+    const int rc = tj_obstacle_approach(c, range, tol, max_depth, max_windows, part.data());
+    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
+    for (int u = c->d.u0; u < c->d.u1; u++) out[u] = part[u];
+  }
+  return TJ_OK;
+}
+
 }  // extern "C"

@@ -1,0 +1,31 @@
+"""The clock of the query timing scripts (audit_timing.py, closest_timing.py, obstacle_approach_timing.py): the 64-UAV SCN-C state after a number of iterations, and a
+hipEvent pair on the context's stream around a whole call (memsets, kernels, copies).  Run the scripts from the repository root on the GPU."""
+import ctypes as C, importlib, os, sys
+import numpy as np
+sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+pkg = importlib.import_module("traj-opt-admm_amd")
+from conftest import hip_runtime
+
+
+def scn_c_clock(iterations):
+    """-> (solver on SCN-C after `iterations`, timed(fn, reps, warm=3) -> (median, min, max) in milliseconds of `reps` calls after `warm` untimed ones)"""
+    hip = hip_runtime()
+    slv = pkg.Solver(pkg.scenes.scn_c(), stop=0.0)
+    slv.iterate(iterations)
+    stream = C.c_void_p(slv.stream())
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+
+    def timed(fn, reps, warm=3):
+        for _ in range(warm):
+            fn()
+        out = []
+        for _ in range(reps):
+            assert hip.hipEventRecord(e0, stream) == 0
+            fn()
+            assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
+            out.append(ms.value)
+        return float(np.median(out)), float(min(out)), float(max(out))
+    return slv, timed

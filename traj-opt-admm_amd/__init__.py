@@ -65,14 +65,18 @@ class TjAuditRobot(C.Structure):
 AUDIT_FLAGS = dict(obs_contact=1, pair_contact=2, speed=4, accel=8)
 
 
+def _records(struct, rec):
+    """an array of C records -> dict of numpy arrays, one per field (`reserved` is dropped)"""
+    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in struct._fields_ if n != "reserved"}
+
+
 def _audit(call, U, S, range, per_segment):
     """shared by Solver.audit / Group.audit: call(range, records, seg_obs, seg_pair) -> dict of numpy arrays [U] (+ [U][S])"""
     rec = (TjAuditRobot * U)()
     so = np.zeros((U, S)) if per_segment else None
     sp = np.zeros((U, S)) if per_segment else None
     call(C.c_double(0.0 if range is None else float(range)), rec, _d(so) if per_segment else None, _d(sp) if per_segment else None)
-    out = {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32)
-           for n, t in TjAuditRobot._fields_ if n != "reserved"}
+    out = _records(TjAuditRobot, rec)
     if per_segment:
         out["seg_obs"], out["seg_pair"] = so, sp
     return out
@@ -96,7 +100,7 @@ def _audit_timed(call, U, S, range, levels, per_segment):
     sh = np.zeros((U, S)) if per_segment else None
     call(C.c_double(0.0 if range is None else float(range)), C.c_int(-1 if levels is None else int(levels)), rec,
          _d(sl) if per_segment else None, _d(sh) if per_segment else None)
-    out = {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjAuditTimedRobot._fields_}
+    out = _records(TjAuditTimedRobot, rec)
     if per_segment:
         out["seg_lo"], out["seg_hi"] = sl, sh
     return out
@@ -114,12 +118,12 @@ CLOSEST_MAX_DEPTH = 40     # TJ_CLOSEST_MAX_DEPTH
 CLOSEST_FRONTIER = 4096    # TJ_CLOSEST_FRONTIER
 
 
-def _closest(call, U, range, tol, max_depth, max_windows):
-    """shared by Solver.closest_approach / Group.closest_approach: call(range, tol, max_depth, max_windows, records) -> dict of numpy arrays [U]"""
-    rec = (TjClosestRobot * U)()
+def _approach(struct, call, U, range, tol, max_depth, max_windows):
+    """shared by closest_approach / obstacle_approach of Solver and Group: call(range, tol, max_depth, max_windows, records) -> dict of numpy arrays [U]"""
+    rec = (struct * U)()
     call(C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
          C.c_int(0 if max_windows is None else int(max_windows)), rec)
-    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjClosestRobot._fields_ if n != "reserved"}
+    return _records(struct, rec)
 
 
 class TjObstacleRobot(C.Structure):
@@ -132,14 +136,6 @@ OBSTACLE_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8)
 OBSTACLE_TOL = 1e-11        # TJ_OBSTACLE_TOL: what tol=None selects
 OBSTACLE_MAX_DEPTH = 40     # TJ_OBSTACLE_MAX_DEPTH
 OBSTACLE_FRONTIER = 4096    # TJ_OBSTACLE_FRONTIER
-
-
-def _obstacle(call, U, range, tol, max_depth, max_windows):
-    """shared by Solver.obstacle_approach / Group.obstacle_approach: call(range, tol, max_depth, max_windows, records) -> dict of numpy arrays [U]"""
-    rec = (TjObstacleRobot * U)()
-    call(C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
-         C.c_int(0 if max_windows is None else int(max_windows)), rec)
-    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in TjObstacleRobot._fields_ if n != "reserved"}
 
 
 class TrajAdmmError(RuntimeError):
@@ -565,14 +561,14 @@ class Solver:
         branch and bound over tj_audit_timed's windows; `time`, `robot`, `segment` of the hi sample (-1 where nothing is closer than `range`), `depth` rounds,
         `windows` evaluated, `flags` (CLOSEST_FLAGS).  Dict of numpy arrays [U].  Read-only.  A sharded solver (world > 1) raises (TJ_ERR_UNSUPPORTED):
         Group.closest_approach reads every robot's piece_time from its owner."""
-        return _closest(lambda r, t, d, w, rec: self._check(self.lib.tj_closest_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+        return _approach(TjClosestRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_closest_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_obstacle_approach: per robot lo <= closest approach of the FLOWN CURVE to any obstacle primitive <= hi, converged to `tol` (None: OBSTACLE_TOL)
         by a branch and bound over windows of the segments' hulls; `time`, `index` (the caller's point / face index), `segment` of the hi sample (-1 where
         nothing is within `range`), `depth` rounds, `windows` evaluated, `flags` (OBSTACLE_FLAGS).  Dict of numpy arrays [U].  Read-only.  All modes; a
         sharded solver (world > 1) answers for its owned robots, the other records are zero."""
-        return _obstacle(lambda r, t, d, w, rec: self._check(self.lib.tj_obstacle_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+        return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_obstacle_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
     def build_info(self):
         ms, dev = C.c_double(), C.c_int()
@@ -690,11 +686,11 @@ class Group:
 
     def closest_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_closest_approach: Solver.closest_approach of every robot from the rank that owns it (bitwise one context's)"""
-        return _closest(lambda r, t, d, w, rec: self._check(self.lib.tj_group_closest_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+        return _approach(TjClosestRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_group_closest_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""
-        return _obstacle(lambda r, t, d, w, rec: self._check(self.lib.tj_group_obstacle_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+        return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_group_obstacle_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

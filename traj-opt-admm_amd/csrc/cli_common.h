@@ -172,6 +172,40 @@ inline void log_data(const double* spline, int P, const double* convert, double 
   }
 }
 
+// --audit, --audit-timed: one line per robot
+inline void print_audit(const std::vector<tj_audit_robot>& rec) {
+  std::cout.precision(17);
+  for (size_t u = 0; u < rec.size(); u++) {
+    const tj_audit_robot& r = rec[u];
+    std::cout << "audit uav " << u << " obs " << r.obs_clearance << " seg " << r.obs_segment << " id " << r.obs_index << " pair " << r.pair_clearance << " seg " << r.pair_segment
+              << " uav " << r.pair_robot << " speed " << r.speed << " seg " << r.speed_segment << " accel " << r.accel << " seg " << r.accel_segment << " time " << r.duration
+              << " flags " << r.flags << std::endl;
+  }
+}
+inline void print_audit_timed(const std::vector<tj_audit_timed_robot>& rec) {
+  std::cout.precision(17);
+  for (size_t u = 0; u < rec.size(); u++) {
+    const tj_audit_timed_robot& r = rec[u];
+    std::cout << "audit-timed uav " << u << " lo " << r.timed_lo << " uav " << r.lo_robot << " seg " << r.lo_segment << " hi " << r.timed_hi << " uav " << r.timed_robot
+              << " seg " << r.timed_segment << " time " << r.timed_time << " levels " << r.levels << " flags " << r.flags << std::endl;
+  }
+}
+
+// --closest-approach: one line per robot and the fleet's summary (the robot with the smallest attained separation)
+inline void print_closest_approach(const std::vector<tj_closest_robot>& rec) {
+  std::cout.precision(17);
+  int who = -1, contact = 0;
+  for (size_t u = 0; u < rec.size(); u++) {
+    const tj_closest_robot& r = rec[u];
+    std::cout << "closest uav " << u << " lo " << r.lo << " hi " << r.hi << " uav " << r.robot << " seg " << r.segment << " time " << r.time << " depth " << r.depth
+              << " windows " << r.windows << " flags " << r.flags << std::endl;
+    if (r.robot >= 0 && (who < 0 || r.hi < rec[who].hi)) who = (int)u;
+    contact |= r.flags & TJ_CLOSEST_CONTACT;
+  }
+  if (who < 0) std::cout << "closest fleet none contact 0" << std::endl;
+  else std::cout << "closest fleet hi " << rec[who].hi << " uav " << who << " uav " << rec[who].robot << " time " << rec[who].time << " contact " << contact << std::endl;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

@@ -172,38 +172,17 @@ int main(int argc, char** argv) {
     if (audit) {
       std::vector<tj_audit_robot> rec(U);
       chk(group ? tj_group_audit(grp, audit_range, rec.data(), nullptr, nullptr) : tj_audit(ctx, audit_range, rec.data(), nullptr, nullptr), "tj_audit");
-      std::cout.precision(17);
-      for (int u = 0; u < U; u++) {
-        const tj_audit_robot& r = rec[u];
-        std::cout << "audit uav " << u << " obs " << r.obs_clearance << " seg " << r.obs_segment << " id " << r.obs_index << " pair " << r.pair_clearance << " seg " << r.pair_segment
-                  << " uav " << r.pair_robot << " speed " << r.speed << " seg " << r.speed_segment << " accel " << r.accel << " seg " << r.accel_segment << " time " << r.duration
-                  << " flags " << r.flags << std::endl;
-      }
+      tjcli::print_audit(rec);
     }
     if (audit_timed) {
       std::vector<tj_audit_timed_robot> rec(U);
       chk(group ? tj_group_audit_timed(grp, 0.0, audit_levels, rec.data(), nullptr, nullptr) : tj_audit_timed(ctx, 0.0, audit_levels, rec.data(), nullptr, nullptr), "tj_audit_timed");
-      std::cout.precision(17);
-      for (int u = 0; u < U; u++) {
-        const tj_audit_timed_robot& r = rec[u];
-        std::cout << "audit-timed uav " << u << " lo " << r.timed_lo << " uav " << r.lo_robot << " seg " << r.lo_segment << " hi " << r.timed_hi << " uav " << r.timed_robot
-                  << " seg " << r.timed_segment << " time " << r.timed_time << " levels " << r.levels << " flags " << r.flags << std::endl;
-      }
+      tjcli::print_audit_timed(rec);
     }
     if (closest) {
       std::vector<tj_closest_robot> rec(U);
       chk(group ? tj_group_closest_approach(grp, 0.0, closest_tol, -1, 0, rec.data()) : tj_closest_approach(ctx, 0.0, closest_tol, -1, 0, rec.data()), "tj_closest_approach");
-      std::cout.precision(17);
-      int who = -1, contact = 0;
-      for (int u = 0; u < U; u++) {
-        const tj_closest_robot& r = rec[u];
-        std::cout << "closest uav " << u << " lo " << r.lo << " hi " << r.hi << " uav " << r.robot << " seg " << r.segment << " time " << r.time << " depth " << r.depth
-                  << " windows " << r.windows << " flags " << r.flags << std::endl;
-        if (r.robot >= 0 && (who < 0 || r.hi < rec[who].hi)) who = u;
-        contact |= r.flags & TJ_CLOSEST_CONTACT;
-      }
-      if (who < 0) std::cout << "closest fleet none contact 0" << std::endl;
-      else std::cout << "closest fleet hi " << rec[who].hi << " uav " << who << " uav " << rec[who].robot << " time " << rec[who].time << " contact " << contact << std::endl;
+      tjcli::print_closest_approach(rec);
     }
     if (obstacle) {
       std::vector<tj_obstacle_robot> rec(U);

@@ -13,17 +13,14 @@
 //                   bvh_query with m = range (a primitive closer than `range` to the hull has its box within `range` of the hull's box, so
 //                   min(range, min over candidates) is exact), per batch of up to 64 candidates one per-lane GJK each, then the robots
 //                   q != u of the same segment one per lane (lower robot index = body 1, as plane_pair), then the segment's 5 velocity
-//                   and 4 acceleration terms.  Minima are reduced across the wave with a total order (distance, index): no float atomics,
-//                   the result is a function of the state alone.
+//                   and 4 acceleration terms.  Minima are reduced across the wave with a total order (distance, index; dev_query.h).
 //   k_audit_reduce  one wave per owned robot: its S rows -> the robot's record.
 //
 // Read-only: the kernels write the audit's own buffers only.  The frontier arrays of the walk are the unit's own LDS (FRONT_CAP entries, as in every
-// other user of bvh_query); the overflow bit goes to a control block of the audit's own (Dev::ctl of the COPY the kernels receive), never to the
+// other user of bvh_query); the overflow bit goes to the queries' control block (Dev::ctl of the COPY the kernels receive: tj_api.hip), never to the
 // solver's.  No `visits` counter is passed: tj_stats does not move.
 #pragma once
-#include <limits.h>
-#include "../../include/trajadmm.h"
-#include "kernels_sep.h"
+#include "dev_query.h"
 
 namespace tj {
 
@@ -35,42 +32,19 @@ struct AuditArgs {
   int *row_prim, *row_q;                                 // [U][S] argmin primitive (caller's index) / robot, -1: nothing closer than range
 };
 
-// a 6-point hull behind a stride: the unit's own hull (LDS, stride 1) or a lane's column of the transposed partner tile (stride 64)
-struct BodyHullS {
-  const double* p; int st;
-  static constexpr int N = 6;
-  __device__ __forceinline__ V3 get(int i) const { return V3{p[(3 * i) * st], p[(3 * i + 1) * st], p[(3 * i + 2) * st]}; }
-};
-
-// minimum of (d, key) in lexicographic order over the wave, `aux` travels with it; every lane ends with the same triple
-__device__ __forceinline__ void audit_argmin(double& d, int& key, int& aux) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double d2 = __shfl_xor(d, off); const int k2 = __shfl_xor(key, off), a2 = __shfl_xor(aux, off);
-    if (d2 < d || (d2 == d && k2 < key)) { d = d2; key = k2; aux = a2; }
-  }
-}
-
 template <int PRIM>
 __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
   const int lane = lane_id(), S = D.S;
   const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
   __shared__ double P[18], tile[18 * 64];
   __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
-  if (lane < 18) P[lane] = hull_entry(D, A.net + (size_t)u * 3 * D.T, tr, lane / 3, lane % 3);
-  __syncthreads();
   QBox q;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    q.lo[k] = lo; q.hi[k] = hi;
-  }
+  query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
   const double range = A.range;
   const size_t row = (size_t)u * S + tr;
 
   // ---- obstacles: every primitive whose box is within `range` of the hull's box, one per lane ----
-  double od = range; int oi = INT_MAX, unused = 0;
+  double od = range; int oi = INT_MAX;
   bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
     if (pt >= 0) {
       const V3 v = gjk(BodyHull{P}, PrimOf<PRIM>::load(D, pt));
@@ -79,7 +53,7 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
       if (d < range && (d < od || (d == od && idx < oi))) { od = d; oi = idx; }
     }
   });
-  audit_argmin(od, oi, unused);
+  wave_argmin(od, oi);
 
   // ---- the other robots on this segment, one per lane ----
   double pd = range; int pq = INT_MAX;
@@ -91,15 +65,7 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
       if (live) {
         const double* nq = A.net + (size_t)qr * 3 * D.T;
         for (int e = 0; e < 18; e++) tile[e * 64 + lane] = hull_entry(D, nq, tr, e / 3, e % 3);
-        // Boxes further apart than `range` on an axis: the hulls are at least that far apart.  (Rounding is monotonic, so a true gap <= range never
-        // compares greater; the guard keeps a pair whose gap is within rounding of `range` in the GJK, whose |v| decides.)
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          double lo = INFINITY, hi = -INFINITY;
-          for (int j = 0; j < 6; j++) { const double v = tile[(3 * j + k) * 64 + lane]; if (v < lo) lo = v; if (v > hi) hi = v; }
-          const double gap = fmax(lo - q.hi[k], q.lo[k] - hi);
-          live = live && !(gap > range * 1.000001 + 1e-9);
-        }
+        live = box_near(tile + lane, 64, q, range);
       }
       if (live) {
         const BodyHullS own{P, 1}, oth{tile + lane, 64};
@@ -109,7 +75,7 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
         if (d < range && (d < pd || (d == pd && qr < pq))) { pd = d; pq = qr; }
       }
     }
-    audit_argmin(pd, pq, unused);
+    wave_argmin(pd, pq);
   }
 
   // ---- dynamic limits: the terms of kernels_ls.h x_energy_group (Energy_admm.h:131-165), weight = the segment's table value ----
@@ -139,7 +105,7 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
 __global__ __launch_bounds__(64) void k_audit_reduce(Dev D, AuditArgs A, tj_audit_robot* out) {
   const int lane = lane_id(), S = D.S, u = D.u0 + blockIdx.x;
   double od = A.range, pd = A.range, nsp = 1.0, nac = 1.0;   // nsp / nac: the negated maxima, so that one reduction serves all four
-  int os = INT_MAX, oi = -1, ps = INT_MAX, pq = -1, ss = INT_MAX, as = INT_MAX, unused = 0;
+  int os = INT_MAX, oi = -1, ps = INT_MAX, pq = -1, ss = INT_MAX, as = INT_MAX;
   for (int tr = lane; tr < S; tr += 64) {   // ascending segments per lane: a strict comparison keeps the first
     const size_t r = (size_t)u * S + tr;
     { const double d = A.row_obs[r]; const int i = A.row_prim[r]; if (i >= 0 && d < od) { od = d; os = tr; oi = i; } }
@@ -147,7 +113,7 @@ __global__ __launch_bounds__(64) void k_audit_reduce(Dev D, AuditArgs A, tj_audi
     { const double v = -A.row_speed[r]; if (v < nsp) { nsp = v; ss = tr; } }
     { const double v = -A.row_accel[r]; if (v < nac) { nac = v; as = tr; } }
   }
-  audit_argmin(od, os, oi); audit_argmin(pd, ps, pq); audit_argmin(nsp, ss, unused); audit_argmin(nac, as, unused);
+  wave_argmin(od, os, oi); wave_argmin(pd, ps, pq); wave_argmin(nsp, ss); wave_argmin(nac, as);
   if (lane == 0) {
     const double pt = D.piece_time[u];
     double dur = 0;

@@ -16,14 +16,14 @@
 // Per (robot, segment) the minima of lo and hi over partners and windows, capped at `range`; ties keep the smallest (partner, sub-window, cut).
 //
 // Exactness of the skip: a window is not evaluated when the boxes of the two RAW segment hulls are further apart than `range` on an axis -- both restricted
-// nets lie in their raw hulls, so |d| >= hull distance >= box gap > range on the whole window, and neither minimum (both capped at `range`) can change.  Same
-// rounding guard as k_audit's pair loop.
+// nets lie in their raw hulls, so |d| >= hull distance >= box gap > range on the whole window, and neither minimum (both capped at `range`) can change
+// (box_near, dev_query.h).
 //
 //   k_audit_timed         one wave per (owned robot, segment).  Lane = (partner of the pass, sub-window): 64 >> L partners per pass, 2^L sub-windows each, so level 6
 //                         is one partner per pass and one sub-window per lane.  A lane walks the cuts of its sub-window (usually one or two), forms q's raw hull in its
 //                         column of an LDS tile (stride 64 doubles: lane-consecutive, conflict-free), restricts both nets in registers, writes d to its column of a
-//                         second tile and runs the per-lane GJK against the origin.  Lanes keep their own running minima (strict comparisons, ascending order); one
-//                         total-order reduction (value, partner * 64 + sub-window) at the end.  No float atomics: the result is a function of the state alone.
+//                         second tile and runs the per-lane GJK against the origin (timed_walk).  Lanes keep their own running minima; one total-order reduction
+//                         (value, partner * 64 + sub-window) at the end (dev_query.h).
 //   k_audit_timed_reduce  one wave per owned robot: its S rows -> the record.
 // Read-only: the kernels write the audit's own buffers only (no tj_stats counter, no launch count).
 #pragma once
@@ -64,15 +64,6 @@ __device__ __forceinline__ void bez_restrict(const double (&p)[6], double sa, do
 
 __device__ __forceinline__ double clamp01(double x) { return fmin(fmax(x, 0.0), 1.0); }
 
-// audit_argmin with a double and an int travelling along
-__device__ __forceinline__ void audit_argmin_t(double& d, int& key, double& aux, int& iaux) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double d2 = __shfl_xor(d, off), a2 = __shfl_xor(aux, off); const int k2 = __shfl_xor(key, off), i2 = __shfl_xor(iaux, off);
-    if (d2 < d || (d2 == d && k2 < key)) { d = d2; key = k2; aux = a2; iaux = i2; }
-  }
-}
-
 // the certificate of a GJK result v = (nearest point of body 1) - (nearest point of body 2): v . (a_i - b_j) > 0 for every vertex pair, i.e. v is a separating
 // direction and |v| a lower bound on the distance at rounding level.  Without it the bodies may touch, where the GJK stops at up to ~1e-5 instead
 // of 0.  Shared by timed_window (body 2 = the origin: d - 0 is d, the bits of its first form) and kernels_obstacle_approach.h.
@@ -112,18 +103,10 @@ __device__ __forceinline__ void timed_partner_fill(const Dev& D, const double* n
   }
 }
 
-// the same, and whether its box is within `range` of the box [blo, bhi] of u's raw hull (the skip of the header comment)
-__device__ __forceinline__ bool timed_partner_hull(const Dev& D, const double* nq, int j, bool hover, double* cq, const double (&blo)[3], const double (&bhi)[3], double range) {
+// the same, and whether its box is within `range` of the box of u's raw hull (the skip of the header comment)
+__device__ __forceinline__ bool timed_partner_hull(const Dev& D, const double* nq, int j, bool hover, double* cq, const QBox& box, double range) {
   timed_partner_fill<64>(D, nq, j, hover, cq);
-  bool near = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int i = 0; i < 6; i++) { const double v = cq[(3 * i + k) * 64]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    const double gap = fmax(lo - bhi[k], blo[k] - hi);
-    near = near && !(gap > range * 1.000001 + 1e-9);
-  }
-  return near;
+  return box_near(cq, 64, box, range);
 }
 
 // one window: u's raw hull pa (stride SP) restricted to [sa, sb], q's raw hull cq (stride SQ) to [ra, rb] (hover: as it is), the difference net to the column cd
@@ -152,53 +135,57 @@ __device__ __forceinline__ void timed_window(const double* pa, const double* cq,
   if (sep) *sep = gjk_separates(v, BodyHullS{cd, SQ}, BodyPoint{V3{0.0, 0.0, 0.0}});
 }
 
-__global__ __launch_bounds__(64) void k_audit_timed(Dev D, AuditTimedArgs A) {
+// THE WALK of one wave over the partners and cuts of (u, tr) at level L, the single source of the windows' bits (k_audit_timed at the caller's level, k_closest_seed at level
+// 0): lane = (partner of the pass, sub-window), P / box the unit's hull and box (query_hull), cq / cd the lane's columns of two 18 x 64 tiles.  f(q, w, j, ca, cb, lo, h0, h5, sep)
+// is called once per evaluated window [ca, cb] of sub-window w against segment j of partner q (j == S: q hovers); sep is the GJK's certificate where CERT asks for it.
+template <bool CERT, class F>
+__device__ __forceinline__ void timed_walk(const Dev& D, const double* net, const double* pt, double range, int L, int u, int tr, const double* P, const QBox& box,
+                                           double* cq, double* cd, F&& f) {
   const int lane = lane_id(), S = D.S, U = D.U;
-  const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
-  __shared__ double P[18], tq[18 * 64], td[18 * 64];
-  if (lane < 18) P[lane] = hull_entry(D, A.net + (size_t)u * 3 * D.T, tr, lane / 3, lane % 3);
-  __syncthreads();
-  double blo[3], bhi[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    blo[k] = lo; bhi[k] = hi;
-  }
-  const double range = A.range, res = (double)D.res, ptu = A.pt[u];
-  const int L = A.levels, N = 1 << L, per = 64 >> L, w = lane & (N - 1), ql = lane >> L;
+  const double res = (double)D.res, ptu = pt[u];
+  const int N = 1 << L, per = 64 >> L, w = lane & (N - 1), ql = lane >> L;
   const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
   const double t0 = ((tr + w / (double)N) / res) * ptu, t1 = ((tr + (w + 1) / (double)N) / res) * ptu;   // (the last sub-window ends at T1u bit for bit)
-  double* cq = tq + lane; double* cd = td + lane;   // this lane's columns
+  for (int base = 0; base < U; base += per) {
+    const int q = base + ql;
+    if (q >= U || q == u) continue;
+    const double ptq = pt[q];
+    const double* nq = net + (size_t)q * 3 * D.T;
+    int j = timed_first_segment(t0, ptq, res, S);
+    do {
+      const bool hover = j >= S;
+      const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
+      const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
+      if (timed_partner_hull(D, nq, j, hover, cq, box, range)) {
+        const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
+        const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+        double lo, h0, h5; bool sep = true;
+        timed_window<1, 64>(P, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, CERT ? &sep : nullptr);
+        f(q, w, j, ca, cb, lo, h0, h5, sep);
+      }
+      j++;
+    } while (j <= S && (j / res) * ptq < t1);
+  }
+}
 
+__global__ __launch_bounds__(64) void k_audit_timed(Dev D, AuditTimedArgs A) {
+  const int lane = lane_id(), S = D.S;
+  const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
+  __shared__ double P[18], tq[18 * 64], td[18 * 64];
+  QBox box;
+  query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, box);
+  const double range = A.range;
   double dlo = range, dhi = range, thi = 0.0; int klo = INT_MAX, khi = INT_MAX;
   if (D.multi()) {
-    for (int base = 0; base < U; base += per) {
-      const int q = base + ql;
-      if (q >= U || q == u) continue;
-      const double ptq = A.pt[q];
-      const double* nq = A.net + (size_t)q * 3 * D.T;
-      int j = timed_first_segment(t0, ptq, res, S);
-      do {
-        const bool hover = j >= S;
-        const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
-        const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
-        if (timed_partner_hull(D, nq, j, hover, cq, blo, bhi, range)) {
-          const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-          const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
-          double lo, h0, h5;
-          timed_window<1, 64>(P, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5);
-          const bool first = h0 <= h5;
-          const double hi = first ? h0 : h5;
-          if (lo < range && lo < dlo) { dlo = lo; klo = q * 64 + w; }
-          if (hi < range && hi < dhi) { dhi = hi; khi = q * 64 + w; thi = first ? ca : cb; }
-        }
-        j++;
-      } while (j <= S && (j / res) * ptq < t1);
-    }
-    int unused = 0;
-    audit_argmin(dlo, klo, unused);
-    audit_argmin_t(dhi, khi, thi, unused);
+    // lanes keep their own running minima (strict comparisons, ascending order)
+    timed_walk<false>(D, A.net, A.pt, range, A.levels, u, tr, P, box, tq + lane, td + lane, [&](int q, int w, int, double ca, double cb, double lo, double h0, double h5, bool) {
+      const bool first = h0 <= h5;
+      const double hi = first ? h0 : h5;
+      if (lo < range && lo < dlo) { dlo = lo; klo = q * 64 + w; }
+      if (hi < range && hi < dhi) { dhi = hi; khi = q * 64 + w; thi = first ? ca : cb; }
+    });
+    wave_argmin(dlo, klo);
+    wave_argmin(dhi, khi, thi);
   }
   if (lane == 0) {
     const size_t row = (size_t)u * S + tr;
@@ -218,8 +205,8 @@ __global__ __launch_bounds__(64) void k_audit_timed_reduce(Dev D, AuditTimedArgs
     { const double d = A.row_lo[r]; const int i = A.row_qlo[r]; if (i >= 0 && d < dlo) { dlo = d; slo = tr; qlo = i; } }
     { const double d = A.row_hi[r]; const int i = A.row_qhi[r]; if (i >= 0 && d < dhi) { dhi = d; shi = tr; qhi = i; thi = A.row_time[r]; } }
   }
-  audit_argmin(dlo, slo, qlo);
-  audit_argmin_t(dhi, shi, thi, qhi);
+  wave_argmin(dlo, slo, qlo);
+  wave_argmin(dhi, shi, thi, qhi);
   if (lane == 0) {
     tj_audit_timed_robot r;
     r.timed_lo = dlo; r.timed_hi = dhi; r.timed_time = qhi < 0 ? -1.0 : thi;

@@ -5,7 +5,8 @@
 // point: a separation attained at a known time).  lo counts only where the GJK's v SEPARATES the origin from the hull (v . d_i > 0 for all six points); without
 // that certificate the origin may be inside, where the GJK stops at up to ~1e-5 instead of 0, and lo(W) = 0.  A window whose lo is not below the smallest hi found so far cannot hold the minimum and is dropped; the
 // others are halved.  Time, hover, hull formation, the cuts at the partner's segment boundaries, the restriction of both nets and the box skip are
-// kernels_audit_timed.h's (timed_first_segment, timed_window: the same source expressions).  The definition (include/trajadmm.h), per owned robot u:
+// kernels_audit_timed.h's (timed_walk for the seeds, timed_window for the children: one set of source expressions); the record QBest with its order
+// (hi, segment, partner, time) and the bounded append are dev_query.h's.  The definition (include/trajadmm.h), per owned robot u:
 //   seeds    the windows (tr, q, j, ca, cb) k_audit_timed evaluates at levels = 0.  best = the smallest hi < range, ties by (segment, partner, time);
 //            live = {lo < range and lo < best.hi}
 //   round d  every live window is halved at cm = 0.5 * (ca + cb); cm == ca or cm == cb: it stays in the set as terminal.  Both children are evaluated by
@@ -18,7 +19,7 @@
 //
 // Four launches whatever the fleet's size and the depth:
 //   k_audit_timed (levels 0), k_audit_timed_reduce   the level-0 bracket per robot: best (hi, segment, partner, time) and the smallest lo
-//   k_closest_seed     one wave per (owned robot, segment), k_audit_timed's walk at level 0 (lane = partner of the pass).  A lane whose window has
+//   k_closest_seed     one wave per (owned robot, segment), timed_walk at level 0 with the certificate (lane = partner of the pass).  A lane whose window has
 //                      lo < best.hi appends it to the robot's list with one integer atomic on the robot's counter (append order is free: nothing
 //                      downstream depends on it; the windows below best.hi are a handful per robot, so there is nothing for a ballot to save).  The
 //                      number of windows evaluated is summed over the wave and added once.
@@ -51,69 +52,31 @@ struct ClosestArgs {
 };
 
 __global__ __launch_bounds__(64) void k_closest_seed(Dev D, ClosestArgs A) {
-  const int lane = lane_id(), S = D.S, U = D.U;
+  const int lane = lane_id(), S = D.S;
   const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
   __shared__ double P[18], tq[18 * 64], td[18 * 64];
-  if (lane < 18) P[lane] = hull_entry(D, A.net + (size_t)u * 3 * D.T, tr, lane / 3, lane % 3);
-  __syncthreads();
-  double blo[3], bhi[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    blo[k] = lo; bhi[k] = hi;
-  }
-  const double range = A.range, res = (double)D.res, ptu = A.pt[u], besthi = A.seed[u].timed_hi;
-  const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
-  const double t0 = ((tr + 0 / (double)1) / res) * ptu, t1 = ((tr + (0 + 1) / (double)1) / res) * ptu;   // k_audit_timed's sub-window 0 of 1
-  double* cq = tq + lane; double* cd = td + lane;
+  QBox box;
+  query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, box);
+  const double range = A.range, besthi = A.seed[u].timed_hi;
   ClosestWin* list = A.list + (size_t)u * 2 * TJ_CLOSEST_FRONTIER;
   int nev = 0;
-  for (int base = 0; base < U; base += 64) {
-    const int q = base + lane;
-    if (q >= U || q == u) continue;
-    const double ptq = A.pt[q];
-    const double* nq = A.net + (size_t)q * 3 * D.T;
-    int j = timed_first_segment(t0, ptq, res, S);
-    do {
-      const bool hover = j >= S;
-      const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
-      const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
-      if (timed_partner_hull(D, nq, j, hover, cq, blo, bhi, range)) {
-        const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-        const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
-        double lo, h0, h5; bool sep;
-        timed_window<1, 64>(P, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
-        if (!sep) lo = 0.0;
-        nev++;
-        if (lo < range && lo < besthi) {
-          if (!sep) atomicOr(&A.count[3 * u + 2], 1);
-          const int at = atomicAdd(&A.count[3 * u], 1);
-          if (at < A.max_windows) list[at] = ClosestWin{ca, cb, lo, tr, q, j, 0};
-        }
-      }
-      j++;
-    } while (j <= S && (j / res) * ptq < t1);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) nev += __shfl_xor(nev, off);
+  timed_walk<true>(D, A.net, A.pt, range, 0, u, tr, P, box, tq + lane, td + lane, [&](int q, int, int j, double ca, double cb, double lo, double, double, bool sep) {
+    if (!sep) lo = 0.0;
+    nev++;
+    if (lo < range && lo < besthi) {
+      if (!sep) atomicOr(&A.count[3 * u + 2], 1);
+      bnb_keep(A.count[3 * u], list, A.max_windows, ClosestWin{ca, cb, lo, tr, q, j, 0});
+    }
+  });
+  nev = wave_sum(nev);
   if (lane == 0 && nev) atomicAdd(&A.count[3 * u + 1], nev);
-}
-
-// the smallest (hi, segment, partner, time) in lexicographic order
-struct ClosestBest { double hi, time; int seg, q; };
-__device__ __forceinline__ bool closest_before(const ClosestBest& a, const ClosestBest& b) {
-  if (a.hi != b.hi) return a.hi < b.hi;
-  if (a.seg != b.seg) return a.seg < b.seg;
-  if (a.q != b.q) return a.q < b.q;
-  return a.time < b.time;
 }
 
 __global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArgs A, tj_closest_robot* out) {
   constexpr int NW = CL_THREADS / 64;
   const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S, u = D.u0 + blockIdx.x;
   __shared__ double tp[18 * CL_THREADS], tq[18 * CL_THREADS], td[18 * CL_THREADS];
-  __shared__ ClosestBest wbest[NW];
+  __shared__ QBest wbest[NW];
   __shared__ double wlo[NW];
   __shared__ int wev[NW], wterm[NW], kept;
   const tj_audit_timed_robot seed = A.seed[u];
@@ -125,14 +88,14 @@ __global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArg
   double* cp = tp + tid; double* cq = tq + tid; double* cd = td + tid;
 
   // the committed record: the level-0 bracket (every thread holds the same values)
-  ClosestBest best{seed.timed_hi, seed.timed_time, seed.timed_robot < 0 ? INT_MAX : seed.timed_segment, seed.timed_robot < 0 ? INT_MAX : seed.timed_robot};
+  QBest best{seed.timed_hi, seed.timed_time, seed.timed_robot < 0 ? INT_MAX : seed.timed_segment, seed.timed_robot < 0 ? INT_MAX : seed.timed_robot};
   double lo_u = A.count[3 * u + 2] ? 0.0 : fmin(seed.timed_lo, seed.timed_hi);   // min(best.hi, min lo over the live seeds): tj_audit_timed's, unless a live seed counts 0
   int n = A.count[3 * u], windows = A.count[3 * u + 1], depth = 0;
   bool truncated = n > maxw, terminal = false;   // terminal: every live window is
   if (D.multi()) {
     while (!truncated && !(best.hi - lo_u <= A.tol) && n > 0 && !terminal && depth < A.max_depth) {
       // ---- pass 1: the children, one per lane ----
-      ClosestBest mine{range, 0.0, INT_MAX, INT_MAX};
+      QBest mine{range, 0.0, INT_MAX, INT_MAX};
       int nev = 0;
       for (int i = tid; i < 2 * n; i += CL_THREADS) {
         const ClosestWin w = cur[i >> 1];
@@ -154,20 +117,15 @@ __global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArg
         nev++;
         klo[i] = lo;
         const bool first = h0 <= h5;
-        const ClosestBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
-        if (b.hi < range && closest_before(b, mine)) mine = b;
+        const QBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
+        if (b.hi < range && before(b, mine)) mine = b;
       }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const ClosestBest o{__shfl_xor(mine.hi, off), __shfl_xor(mine.time, off), __shfl_xor(mine.seg, off), __shfl_xor(mine.q, off)};
-        if (closest_before(o, mine)) mine = o;
-        nev += __shfl_xor(nev, off);
-      }
+      wave_best(mine); nev = wave_sum(nev);
       if (lane == 0) { wbest[wave] = mine; wev[wave] = nev; }
       if (tid == 0) kept = 0;
       __syncthreads();   // (also: every klo of the round is written)
-      ClosestBest cand = best;
-      for (int k = 0; k < NW; k++) { if (closest_before(wbest[k], cand)) cand = wbest[k]; windows += wev[k]; }
+      QBest cand = best;
+      for (int k = 0; k < NW; k++) { if (before(wbest[k], cand)) cand = wbest[k]; windows += wev[k]; }
       // ---- pass 2: keep what can still hold something below the round's best ----
       double mlo = INFINITY; int allterm = 1;
       for (int i = tid; i < 2 * n; i += CL_THREADS) {
@@ -177,11 +135,11 @@ __global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArg
         const bool term = w.term || cm == w.ca || cm == w.cb;
         if ((term && c) || !(lo < cand.hi)) continue;
         mlo = fmin(mlo, lo); allterm &= term ? 1 : 0;
-        const int at = atomicAdd(&kept, 1);
-        if (at < maxw) nxt[at] = term ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0};
+        bnb_keep(kept, nxt, maxw, term ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0});
       }
+      mlo = wave_min(mlo);
 #pragma unroll
-      for (int off = 32; off > 0; off >>= 1) { mlo = fmin(mlo, __shfl_xor(mlo, off)); allterm &= __shfl_xor(allterm, off); }
+      for (int off = 32; off > 0; off >>= 1) allterm &= __shfl_xor(allterm, off);
       if (lane == 0) { wlo[wave] = mlo; wterm[wave] = allterm; }
       __syncthreads();   // (also: the new list is written, `kept` is final)
       const int m = kept;
@@ -194,9 +152,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArg
   }
   if (tid == 0) {
     tj_closest_robot r;
-    const bool found = best.q != INT_MAX;
-    r.lo = lo_u; r.hi = best.hi; r.time = found ? best.time : -1.0;
-    r.robot = found ? best.q : -1; r.segment = found ? best.seg : -1;
+    const bool found = best.id != INT_MAX;
+    r.lo = lo_u; r.hi = best.hi; r.time = found ? best.x : -1.0;
+    r.robot = found ? best.id : -1; r.segment = found ? best.seg : -1;
     r.depth = depth; r.windows = windows; r.reserved = 0;
     r.flags = !D.multi() ? (TJ_CLOSEST_CLEAR | TJ_CLOSEST_CONVERGED)
                          : ((found && best.hi <= D.offset ? TJ_CLOSEST_CONTACT : 0) | (lo_u > D.offset ? TJ_CLOSEST_CLEAR : 0) |

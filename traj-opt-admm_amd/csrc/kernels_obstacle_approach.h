@@ -9,7 +9,7 @@
 // b_0's and b_5's distance to the primitive, points of the curve at the window's ends: attained, at a known time.  Windows are dyadic: halving is exact, and
 // with max_depth <= 40 none is ever unsplittable.  The definition (include/trajadmm.h), per owned robot u:
 //   seeds    per segment the primitives k_audit's walk returns at m = range (the leaf predicate in fp64 on the primitives themselves), window [0, 1].
-//            best = the smallest hi < range, equal values ordered by (hi, segment, index, s); live = {lo < range and lo < best.hi}
+//            best = the smallest hi < range, equal values ordered by (hi, segment, index, s) (QBest, dev_query.h); live = {lo < range and lo < best.hi}
 //   round d  every live item is halved at 0.5 * (sa + sb); both children are evaluated from the raw hull; best over (best, children of the round); then
 //            live = the children with lo < best.hi -- against the round's FINAL best, so the set does not depend on the order of evaluation
 //   bracket  lo_u = min(best.hi, min lo over live), hi_u = best.hi
@@ -26,7 +26,8 @@
 //                   lanes take the children strided, restrict the raw hull in registers into their column of one LDS tile, run the per-lane GJK; a
 //                   total-order reduction over the workgroup gives the round's best; a second pass keeps lo < best.hi (integer LDS counter).
 // No float atomics, no workgroup waits on another, no polling, no cross-queue word, nothing of the iteration's scratch.  Read-only: the kernels write the
-// query's own buffers only; the walk's overflow bit goes to a control block of the query's own (Dev::ctl of the COPY the kernels receive).
+// query's own buffers only; the walk's overflow bit goes to the queries' control block, as k_audit's.  Hull and box, the record QBest with its order and the
+// bounded append are dev_query.h's.
 #pragma once
 #include "kernels_closest.h"
 
@@ -35,7 +36,6 @@ namespace tj {
 constexpr int OA_THREADS = 128;   // two waves: the per-lane GJK's registers, one 18-row tile of 128 columns
 
 struct ObstItem { double sa, sb, lo; int tr, pt; };   // window [sa, sb] of segment tr against the SORTED primitive pt
-struct ObstBest { double hi, s; int seg, idx; };      // idx: the caller's index; nothing found: hi = range, INT_MAX, INT_MAX
 
 struct ObstArgs {
   const double* net;     // [U][3][T]
@@ -43,28 +43,13 @@ struct ObstArgs {
   const int* order;      // sorted primitive -> index in the caller's obstacle list
   double range, tol;
   int max_depth, max_windows, cap;
-  ObstBest* row;         // [U][S] the best seed of the row
+  QBest* row;            // [U][S] the best seed of the row (x: the position s in the segment, id: the caller's index of the primitive)
   double* row_lo;        // [U][S] the smallest lo among the row's live seeds (INFINITY: none)
-  ObstBest* best;        // [U] the best seed of the robot
+  QBest* best;           // [U] the best seed of the robot
   ObstItem* list;        // [owned][2][cap] ping-pong live lists
   double* klo;           // [owned][2 * cap] lo of the round's children
   int* count;            // [U][2]: live seeds (may exceed max_windows: overflow), seeds evaluated
 };
-
-// the smaller of two records in the order (hi, segment, index, s)
-__device__ __forceinline__ bool obst_before(const ObstBest& a, const ObstBest& b) {
-  if (a.hi != b.hi) return a.hi < b.hi;
-  if (a.seg != b.seg) return a.seg < b.seg;
-  if (a.idx != b.idx) return a.idx < b.idx;
-  return a.s < b.s;
-}
-__device__ __forceinline__ void obst_wave_best(ObstBest& m) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const ObstBest o{__shfl_xor(m.hi, off), __shfl_xor(m.s, off), __shfl_xor(m.seg, off), __shfl_xor(m.idx, off)};
-    if (obst_before(o, m)) m = o;
-  }
-}
 
 // distance of a point of the curve from a primitive: a cloud point directly; a triangle through the GJK of the one-point body (a point of the Minkowski
 // difference: an upper bound on the true distance, attained to the triangle figure of DESIGN.md 3c)
@@ -74,19 +59,6 @@ __device__ __forceinline__ double obst_point_dist(const V3& b, const typename Pr
   else { const V3 v = gjk(BodyPoint{b}, prim); return norm3(v.x, v.y, v.z); }
 }
 
-// the unit's hull and its box
-__device__ __forceinline__ void obst_hull(const Dev& D, const double* net, int tr, double* P, QBox& q) {
-  const int lane = lane_id();
-  if (lane < 18) P[lane] = hull_entry(D, net, tr, lane / 3, lane % 3);
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    q.lo[k] = lo; q.hi[k] = hi;
-  }
-}
-
 template <int PRIM>
 __global__ __launch_bounds__(64) void k_obst_seed(Dev D, ObstArgs A) {
   const int lane = lane_id(), S = D.S;
@@ -94,23 +66,22 @@ __global__ __launch_bounds__(64) void k_obst_seed(Dev D, ObstArgs A) {
   __shared__ double P[18];
   __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
   QBox q;
-  obst_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
+  query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
   const double range = A.range;
-  ObstBest mine{range, 0.0, INT_MAX, INT_MAX};
+  QBest mine{range, 0.0, INT_MAX, INT_MAX};
   int nev = 0;
   bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
     if (pt >= 0) {
       const auto prim = PrimOf<PRIM>::load(D, pt);
       const double h0 = obst_point_dist<PRIM>(V3{P[0], P[1], P[2]}, prim), h5 = obst_point_dist<PRIM>(V3{P[15], P[16], P[17]}, prim);
       const bool first = h0 <= h5;
-      const ObstBest b{first ? h0 : h5, first ? 0.0 : 1.0, tr, A.order[pt]};
+      const QBest b{first ? h0 : h5, first ? 0.0 : 1.0, tr, A.order[pt]};
       nev++;
-      if (b.hi < range && obst_before(b, mine)) mine = b;
+      if (b.hi < range && before(b, mine)) mine = b;
     }
   });
-  obst_wave_best(mine);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) nev += __shfl_xor(nev, off);
+  wave_best(mine);
+  nev = wave_sum(nev);
   if (lane == 0) {
     A.row[(size_t)u * S + tr] = mine;
     if (nev) atomicAdd(&A.count[2 * u + 1], nev);
@@ -124,11 +95,11 @@ __global__ __launch_bounds__(64) void k_obst_append(Dev D, ObstArgs A) {
   __shared__ double P[18];
   __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
   QBox q;
-  obst_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
+  query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
   const double range = A.range;
-  ObstBest best{range, 0.0, INT_MAX, INT_MAX};
-  for (int r = lane; r < S; r += 64) { const ObstBest b = A.row[(size_t)u * S + r]; if (obst_before(b, best)) best = b; }
-  obst_wave_best(best);
+  QBest best{range, 0.0, INT_MAX, INT_MAX};
+  for (int r = lane; r < S; r += 64) { const QBest b = A.row[(size_t)u * S + r]; if (before(b, best)) best = b; }
+  wave_best(best);
   if (tr == 0 && lane == 0) A.best[u] = best;
   ObstItem* list = A.list + (size_t)ui * 2 * A.cap;
   double mlo = INFINITY;
@@ -141,13 +112,11 @@ __global__ __launch_bounds__(64) void k_obst_append(Dev D, ObstArgs A) {
       if (!gjk_separates(v, hull, prim)) lo = 0.0;
       if (lo < range && lo < best.hi) {
         mlo = fmin(mlo, lo);
-        const int at = atomicAdd(&A.count[2 * u], 1);
-        if (at < A.max_windows) list[at] = ObstItem{0.0, 1.0, lo, tr, pt};
+        bnb_keep(A.count[2 * u], list, A.max_windows, ObstItem{0.0, 1.0, lo, tr, pt});
       }
     }
   });
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mlo = fmin(mlo, __shfl_xor(mlo, off));
+  mlo = wave_min(mlo);
   if (lane == 0) A.row_lo[(size_t)u * S + tr] = mlo;
 }
 
@@ -156,7 +125,7 @@ __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, t
   constexpr int NW = OA_THREADS / 64;
   const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S, ui = blockIdx.x, u = D.u0 + ui;
   __shared__ double td[18 * OA_THREADS];
-  __shared__ ObstBest wbest[NW];
+  __shared__ QBest wbest[NW];
   __shared__ double wlo[NW];
   __shared__ int kept;
   const double range = A.range, res = (double)D.res, ptu = A.pt[u];
@@ -167,11 +136,10 @@ __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, t
   double* cd = td + tid;
 
   // the committed record: the seeds' bracket (every thread holds the same values)
-  ObstBest best = A.best[u];
+  QBest best = A.best[u];
   double mlo = INFINITY;
   for (int r = tid; r < S; r += OA_THREADS) mlo = fmin(mlo, A.row_lo[(size_t)u * S + r]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mlo = fmin(mlo, __shfl_xor(mlo, off));
+  mlo = wave_min(mlo);
   if (lane == 0) wlo[wave] = mlo;
   __syncthreads();
   for (int k = 0; k < NW; k++) mlo = fmin(mlo, wlo[k]);
@@ -181,7 +149,7 @@ __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, t
   bool truncated = n > maxw;
   while (!truncated && !(best.hi - lo_u <= A.tol) && n > 0 && depth < A.max_depth) {
     // ---- pass 1: the children, one per lane ----
-    ObstBest mine{range, 0.0, INT_MAX, INT_MAX};
+    QBest mine{range, 0.0, INT_MAX, INT_MAX};
     for (int i = tid; i < 2 * n; i += OA_THREADS) {
       const ObstItem w = cur[i >> 1];
       const int c = i & 1;
@@ -203,15 +171,15 @@ __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, t
       klo[i] = lo;
       const double h0 = obst_point_dist<PRIM>(hull.get(0), prim), h5 = obst_point_dist<PRIM>(hull.get(5), prim);
       const bool first = h0 <= h5;
-      const ObstBest b{first ? h0 : h5, first ? sa : sb, w.tr, A.order[w.pt]};
-      if (b.hi < range && obst_before(b, mine)) mine = b;
+      const QBest b{first ? h0 : h5, first ? sa : sb, w.tr, A.order[w.pt]};
+      if (b.hi < range && before(b, mine)) mine = b;
     }
-    obst_wave_best(mine);
+    wave_best(mine);
     if (lane == 0) wbest[wave] = mine;
     if (tid == 0) kept = 0;
     __syncthreads();   // (also: every klo of the round is written)
-    ObstBest cand = best;
-    for (int k = 0; k < NW; k++) if (obst_before(wbest[k], cand)) cand = wbest[k];
+    QBest cand = best;
+    for (int k = 0; k < NW; k++) if (before(wbest[k], cand)) cand = wbest[k];
     windows += 2 * n;
     // ---- pass 2: keep what can still hold something below the round's best ----
     mlo = INFINITY;
@@ -222,11 +190,9 @@ __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, t
       const int c = i & 1;
       const double sm = 0.5 * (w.sa + w.sb);
       mlo = fmin(mlo, lo);
-      const int at = atomicAdd(&kept, 1);
-      if (at < maxw) nxt[at] = ObstItem{c ? sm : w.sa, c ? w.sb : sm, lo, w.tr, w.pt};
+      bnb_keep(kept, nxt, maxw, ObstItem{c ? sm : w.sa, c ? w.sb : sm, lo, w.tr, w.pt});
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mlo = fmin(mlo, __shfl_xor(mlo, off));
+    mlo = wave_min(mlo);
     if (lane == 0) wlo[wave] = mlo;
     __syncthreads();   // (also: the new list is written, `kept` is final)
     const int m = kept;
@@ -238,9 +204,9 @@ __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, t
   }
   if (tid == 0) {
     tj_obstacle_robot r;
-    const bool found = best.idx != INT_MAX;
-    r.lo = lo_u; r.hi = best.hi; r.time = found ? ((best.seg + best.s) / res) * ptu : -1.0;   // log_data's sigma * piece_time
-    r.index = found ? best.idx : -1; r.segment = found ? best.seg : -1;
+    const bool found = best.id != INT_MAX;
+    r.lo = lo_u; r.hi = best.hi; r.time = found ? ((best.seg + best.x) / res) * ptu : -1.0;   // log_data's sigma * piece_time
+    r.index = found ? best.id : -1; r.segment = found ? best.seg : -1;
     r.depth = depth; r.windows = windows; r.reserved = 0;
     r.flags = (found && best.hi <= D.offset ? TJ_OBSTACLE_CONTACT : 0) | (lo_u > D.offset || D.N == 0 ? TJ_OBSTACLE_CLEAR : 0) |
               (best.hi - lo_u <= A.tol || (n == 0 && !truncated) ? TJ_OBSTACLE_CONVERGED : 0) | (truncated ? TJ_OBSTACLE_TRUNCATED : 0);

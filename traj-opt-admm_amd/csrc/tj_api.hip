@@ -91,15 +91,15 @@ struct tj_ctx {
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
-  // tj_audit's own buffers, allocated by its first call (kernels_audit.h): rows [U][S], records [U], a control block for the walk's overflow bit, the control nets a group
-  // hands in; audit_order (sorted primitive -> caller's index) belongs to the obstacle set and goes with it (cloud_allocs)
-  // tj_audit_timed's own (kernels_audit_timed.h): rows, records, the control nets and piece times a group hands in
-  AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr; double* timed_net = nullptr; double* timed_pt = nullptr;
-  // tj_closest_approach's own (kernels_closest.h): the live lists, the children's lower bounds, the counters, the records
+  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach): every buffer is allocated by the first call that needs it, and a call
+  // whose allocations failed partway keeps what it got (query_buf).  Each query ends in a stream synchronise, so no two are in flight on one context, and they share: q_ctl, the
+  // control block the BVH walk reports its overflow bit to (never the solver's); q_net [U][3][T] and q_pt [U], the staged copy of the control nets and piece times a group hands
+  // in; q_order (sorted primitive -> caller's index), which belongs to the obstacle set and goes with it (cloud_allocs).  Per query: its rows / lists / counters and its records.
+  Ctl* q_ctl = nullptr; double* q_net = nullptr; double* q_pt = nullptr; int* q_order = nullptr;
+  AuditArgs audit{}; tj_audit_robot* audit_out = nullptr;
+  AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr;
   ClosestArgs closest{}; tj_closest_robot* closest_out = nullptr;
-  // tj_obstacle_approach's own (kernels_obstacle_approach.h): rows, the live lists, the children's lower bounds, the counters, its control block, the records
-  ObstArgs obst{}; tj_obstacle_robot* obst_out = nullptr; Ctl* obst_ctl = nullptr;
-  AuditArgs audit{}; tj_audit_robot* audit_out = nullptr; Ctl* audit_ctl = nullptr; double* audit_net = nullptr; int* audit_order = nullptr;
+  ObstArgs obst{}; tj_obstacle_robot* obst_out = nullptr;
 };
 
 // EVERY environment switch of the library is read through this one function (tj_group.h included): TJ_TUNE="KEY=value,KEY=value" or, equivalently, TJ_KEY=value
@@ -147,6 +147,25 @@ int upload(tj_ctx* c, const void* dst, const void* src, size_t bytes) {
   // the host buffer may be reused as soon as this returns
   HIPCHK(c, hipMemcpyAsync((void*)dst, src, bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return TJ_OK;
+}
+
+// ---- the templates of the read-only queries' host path (further down, with the rest of it) ----
+// a buffer of the queries: allocated once; what an earlier call got before an allocation failed is kept, only the missing ones are retried
+template <class T>
+int query_buf(tj_ctx* c, T*& p, size_t n, std::vector<void*>* list = nullptr) { return p ? TJ_OK : dalloc(c, &p, n, list); }
+// the kernels templated on the primitive kind, each launch written once: f(std::integral_constant<int, PRIM>)
+template <class F>
+void with_prim(const Dev& d, F&& f) { if (d.prim == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 1>{}); }
+// the records of a query: zeroed before its launches (robots of other ranks stay zero), copied out after them; rows [U][S] likewise where the caller asked for them
+template <class T>
+int query_clear(tj_ctx* c, T* dev, size_t n, bool wanted = true) {
+  if (wanted) HIPCHK(c, hipMemsetAsync(dev, 0, n * sizeof(T), c->stream));
+  return TJ_OK;
+}
+template <class T>
+int query_fetch(tj_ctx* c, T* host, const T* dev, size_t n) {
+  if (host) HIPCHK(c, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
   return TJ_OK;
 }
 
@@ -898,7 +917,7 @@ int set_obstacles(tj_ctx* c, const double* verts, int n, int prim) {
   for (void* p : c->cloud_allocs) hipFree(p);
   c->cloud_allocs.clear();
   c->cloud_order.clear();
-  c->audit_order = nullptr;
+  c->q_order = nullptr;
   if (n > 0) {
     for (int k = 0; k < 3; k++) { c->cloud_lo[k] = INFINITY; c->cloud_hi[k] = -INFINITY; }
     for (size_t i = 0; i < (size_t)n * prim; i++) for (int k = 0; k < 3; k++) { c->cloud_lo[k] = std::min(c->cloud_lo[k], verts[3 * i + k]); c->cloud_hi[k] = std::max(c->cloud_hi[k], verts[3 * i + k]); }
@@ -1391,197 +1410,184 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }
 
 namespace {
-// tj_audit / tj_group_audit.  net_host: every robot's control points [U][3][T] as the caller assembled them (a group: from the owners), or null = the context's own.
+// ---- the read-only queries: one path for the four (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h) ----
+// The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
+// the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
+int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
+  if (v == v) return TJ_OK;
+  c->err = std::string(name) + ": " + what + " is NaN"; return TJ_ERR_INVALID;
+}
+// is there a state to look at, and (owners: the query reads every robot's piece_time) does a sharded context get the owners' values handed in
+int query_state(tj_ctx* c, const char* name, bool owners, bool handed_in) {
+  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  if (owners && c->d.multi() && c->d.world > 1 && !handed_in) {
+    c->err = std::string(name) + ": a sharded context does not hold the other ranks' piece_time as their owners have it; use tj_group_" + (name + 3);
+    return TJ_ERR_UNSUPPORTED;
+  }
+  return TJ_OK;
+}
+double query_range(const Dev& d, double range) { return range > 0 ? range : d.offset + 2 * d.margin; }
+// sorted primitive -> index in the caller's obstacle list, made by whichever query needs it first
+int ensure_order(tj_ctx* c) {
+  int r;
+  if (c->d.N > 0 && !c->q_order && ((r = dalloc(c, &c->q_order, c->d.N, &c->cloud_allocs)) || (r = upload(c, c->q_order, c->cloud_order.data(), (size_t)c->d.N * 4)))) return r;
+  return TJ_OK;
+}
+// what the kernels read as the fleet's control nets and piece times: the staged copy of what a group handed in, or the context's own
+int query_inputs(tj_ctx* c, const double* net_host, const double* pt_host, const double*& net, const double*& pt) {
+  const Dev& d = c->d;
+  const size_t net_n = (size_t)d.U * 3 * d.T;
+  int r;
+  if (net_host && ((r = query_buf(c, c->q_net, net_n)) || (r = upload(c, c->q_net, net_host, net_n * 8)))) return r;
+  if (pt_host && ((r = query_buf(c, c->q_pt, d.U)) || (r = upload(c, c->q_pt, pt_host, (size_t)d.U * 8)))) return r;
+  net = net_host ? c->q_net : d.spline; pt = pt_host ? c->q_pt : d.piece_time;
+  return TJ_OK;
+}
+// the Dev of a query that walks the BVH: the walk reports a frontier overflow through Dev::ctl -- the queries' own block, zeroed for this call, never the solver's
+int walk_dev(tj_ctx* c, Dev& da) {
+  int r = query_buf(c, c->q_ctl, 1);
+  if (r) return r;
+  HIPCHK(c, hipMemsetAsync(c->q_ctl, 0, sizeof(Ctl), c->stream));
+  da = c->d; da.ctl = c->q_ctl;
+  return TJ_OK;
+}
+// the end of every query: the records (and whatever else is queued) are waited for; walk != null: the query of that name walked the BVH, and its overflow bit is read back
+int query_finish(tj_ctx* c, const char* walk) {
+  int err = 0;
+  HIPCHK(c, hipGetLastError());
+  if (walk) HIPCHK(c, hipMemcpyAsync(&err, &c->q_ctl->error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (err & ERR_FRONT_OVERFLOW) { c->err = std::string(walk) + ": the BVH frontier of a segment overflowed at this range (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one hull): lower `range`"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+
 int audit_run(tj_ctx* c, double range, const double* net_host, tj_audit_robot* out, double* seg_obs, double* seg_pair) {
   if (!c || !out) return TJ_ERR_INVALID;
-  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  int r = query_state(c, "tj_audit", false, false);
+  if (r) return r;
   const Dev& d = c->d;
-  const size_t rows = (size_t)d.U * d.S, net_n = (size_t)d.U * 3 * d.T;
-  QUIESCE(c);
-  int r;
-  if (!c->audit_out) {
-    AuditArgs& a = c->audit;
-    if ((r = dalloc(c, &a.row_obs, rows)) || (r = dalloc(c, &a.row_pair, rows)) || (r = dalloc(c, &a.row_speed, rows)) || (r = dalloc(c, &a.row_accel, rows)) ||
-        (r = dalloc(c, &a.row_prim, rows)) || (r = dalloc(c, &a.row_q, rows)) || (r = dalloc(c, &c->audit_ctl, 1)) || (r = dalloc(c, &c->audit_net, net_n)) || (r = dalloc(c, &c->audit_out, d.U))) return r;
-  }
-  if (d.N > 0 && !c->audit_order) {
-    if ((r = dalloc(c, &c->audit_order, d.N, &c->cloud_allocs)) || (r = upload(c, c->audit_order, c->cloud_order.data(), (size_t)d.N * 4))) return r;
-  }
-  if (net_host && (r = upload(c, c->audit_net, net_host, net_n * 8))) return r;
-  AuditArgs a = c->audit;
-  a.net = net_host ? c->audit_net : d.spline; a.order = c->audit_order; a.range = range > 0 ? range : d.offset + 2 * d.margin;
-  Dev da = d; da.ctl = c->audit_ctl;   // (the walk reports a frontier overflow through Dev::ctl: the audit's own block, never the solver's)
+  const size_t rows = (size_t)d.U * d.S;
   const int owned = d.u1 - d.u0;
-  HIPCHK(c, hipMemsetAsync(c->audit_ctl, 0, sizeof(Ctl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->audit_out, 0, (size_t)d.U * sizeof(tj_audit_robot), c->stream));
-  if (seg_obs || seg_pair) { HIPCHK(c, hipMemsetAsync(a.row_obs, 0, rows * 8, c->stream)); HIPCHK(c, hipMemsetAsync(a.row_pair, 0, rows * 8, c->stream)); }
-  if (owned > 0) {   // plain launches: not part of the iteration schedules, not counted by tj_launch_count
-    if (d.prim == 3) hipLaunchKernelGGL(k_audit<3>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
-    else hipLaunchKernelGGL(k_audit<1>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+  QUIESCE(c);
+  AuditArgs& b = c->audit;
+  if ((r = query_buf(c, b.row_obs, rows)) || (r = query_buf(c, b.row_pair, rows)) || (r = query_buf(c, b.row_speed, rows)) || (r = query_buf(c, b.row_accel, rows)) ||
+      (r = query_buf(c, b.row_prim, rows)) || (r = query_buf(c, b.row_q, rows)) || (r = query_buf(c, c->audit_out, d.U)) || (r = ensure_order(c))) return r;
+  AuditArgs a = b;
+  const double* pt;
+  Dev da;
+  if ((r = query_inputs(c, net_host, nullptr, a.net, pt)) || (r = walk_dev(c, da))) return r;
+  a.order = c->q_order; a.range = query_range(d, range);
+  if ((r = query_clear(c, c->audit_out, d.U)) || (r = query_clear(c, a.row_obs, rows, seg_obs || seg_pair)) || (r = query_clear(c, a.row_pair, rows, seg_obs || seg_pair))) return r;
+  if (owned > 0) {   // plain launches (here and in the other queries): not part of the iteration schedules, not counted by tj_launch_count
+    with_prim(d, [&](auto prim) { hipLaunchKernelGGL(k_audit<decltype(prim)::value>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a); });
     hipLaunchKernelGGL(k_audit_reduce, dim3(owned), dim3(64), 0, c->stream, da, a, c->audit_out);
   }
-  HIPCHK(c, hipGetLastError());
-  int err = 0;
-  HIPCHK(c, hipMemcpyAsync(&err, &c->audit_ctl->error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out, c->audit_out, (size_t)d.U * sizeof(tj_audit_robot), hipMemcpyDeviceToHost, c->stream));
-  if (seg_obs) HIPCHK(c, hipMemcpyAsync(seg_obs, a.row_obs, rows * 8, hipMemcpyDeviceToHost, c->stream));
-  if (seg_pair) HIPCHK(c, hipMemcpyAsync(seg_pair, a.row_pair, rows * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (err & ERR_FRONT_OVERFLOW) { c->err = "tj_audit: the BVH frontier of a segment overflowed at this range (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one hull): lower `range`"; return TJ_ERR_CAPACITY; }
-  return TJ_OK;
+  if ((r = query_fetch(c, out, c->audit_out, d.U)) || (r = query_fetch(c, seg_obs, a.row_obs, rows)) || (r = query_fetch(c, seg_pair, a.row_pair, rows))) return r;
+  return query_finish(c, "tj_audit");
+}
+
+// the buffers and arguments of k_audit_timed (tj_audit_timed, and the level-0 seed bound of tj_closest_approach); the caller has quiesced the context
+int timed_setup(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, AuditTimedArgs& a) {
+  const Dev& d = c->d;
+  const size_t rows = (size_t)d.U * d.S;
+  AuditTimedArgs& b = c->timed;
+  int r;
+  if ((r = query_buf(c, b.row_lo, rows)) || (r = query_buf(c, b.row_hi, rows)) || (r = query_buf(c, b.row_time, rows)) || (r = query_buf(c, b.row_qlo, rows)) ||
+      (r = query_buf(c, b.row_qhi, rows)) || (r = query_buf(c, c->timed_out, d.U))) return r;
+  a = b;
+  a.range = query_range(d, range); a.levels = levels;
+  return query_inputs(c, net_host, pt_host, a.net, a.pt);
+}
+// k_audit_timed and its reduction: the two launches of tj_audit_timed, the first two of tj_closest_approach
+void timed_launch(tj_ctx* c, const AuditTimedArgs& a) {
+  const Dev& d = c->d;
+  hipLaunchKernelGGL(k_audit_timed, dim3((d.u1 - d.u0) * d.S), dim3(64), 0, c->stream, d, a);
+  hipLaunchKernelGGL(k_audit_timed_reduce, dim3(d.u1 - d.u0), dim3(64), 0, c->stream, d, a, c->timed_out);
+}
+
+int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, tj_audit_timed_robot* out, double* seg_lo, double* seg_hi) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  int r = query_nan(c, "tj_audit_timed", "range", range);
+  if (r) return r;
+  if (levels > 6) { c->err = "tj_audit_timed: levels must be 0..6 (or negative for the default): one segment's sub-windows are one wave wide"; return TJ_ERR_INVALID; }
+  if ((r = query_state(c, "tj_audit_timed", true, net_host && pt_host))) return r;
+  const Dev& d = c->d;
+  const size_t rows = (size_t)d.U * d.S;
+  QUIESCE(c);
+  AuditTimedArgs a;
+  if ((r = timed_setup(c, range, levels < 0 ? TJ_AUDIT_TIMED_LEVELS : levels, net_host, pt_host, a))) return r;
+  if ((r = query_clear(c, c->timed_out, d.U)) || (r = query_clear(c, a.row_lo, rows, seg_lo || seg_hi)) || (r = query_clear(c, a.row_hi, rows, seg_lo || seg_hi))) return r;
+  if (d.u1 > d.u0) timed_launch(c, a);   // two launches whatever the fleet's size
+  if ((r = query_fetch(c, out, c->timed_out, d.U)) || (r = query_fetch(c, seg_lo, a.row_lo, rows)) || (r = query_fetch(c, seg_hi, a.row_hi, rows))) return r;
+  return query_finish(c, nullptr);
+}
+
+int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_closest_robot* out) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  int r;
+  if ((r = query_nan(c, "tj_closest_approach", "range", range)) || (r = query_nan(c, "tj_closest_approach", "tol", tol))) return r;
+  if (max_depth > TJ_CLOSEST_MAX_DEPTH) { c->err = "tj_closest_approach: max_depth must be 0.." + std::to_string(TJ_CLOSEST_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
+  if (max_windows > TJ_CLOSEST_FRONTIER) { c->err = "tj_closest_approach: max_windows must be 1.." + std::to_string(TJ_CLOSEST_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
+  if ((r = query_state(c, "tj_closest_approach", true, net_host && pt_host))) return r;
+  const Dev& d = c->d;
+  const int owned = d.u1 - d.u0;
+  QUIESCE(c);
+  AuditTimedArgs t;
+  ClosestArgs& b = c->closest;
+  if ((r = timed_setup(c, range, 0, net_host, pt_host, t)) || (r = query_buf(c, b.list, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER)) || (r = query_buf(c, b.klo, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER)) ||
+      (r = query_buf(c, b.count, (size_t)d.U * 3)) || (r = query_buf(c, c->closest_out, d.U))) return r;
+  ClosestArgs a = b;
+  a.net = t.net; a.pt = t.pt; a.range = t.range; a.tol = tol < 0 ? TJ_CLOSEST_TOL : tol;
+  a.max_depth = max_depth < 0 ? TJ_CLOSEST_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_CLOSEST_FRONTIER : max_windows;
+  a.seed = c->timed_out;
+  if ((r = query_clear(c, c->closest_out, d.U)) || (r = query_clear(c, a.count, (size_t)d.U * 3))) return r;
+  if (owned > 0) {   // four launches whatever the fleet's size and the depth
+    timed_launch(c, t);
+    hipLaunchKernelGGL(k_closest_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_closest_refine, dim3(owned), dim3(CL_THREADS), 0, c->stream, d, a, c->closest_out);
+  }
+  if ((r = query_fetch(c, out, c->closest_out, d.U))) return r;
+  return query_finish(c, nullptr);
 }
 }  // namespace
 
 int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) { return audit_run(c, range, nullptr, out, seg_obs, seg_pair); }
 int tj_audit_record_size(void) { return (int)sizeof(tj_audit_robot); }
-
-namespace {
-// the buffers and arguments of k_audit_timed (tj_audit_timed, and the level-0 seed bound of tj_closest_approach); the caller has quiesced the context
-int timed_setup(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, AuditTimedArgs& out) {
-  const Dev& d = c->d;
-  const size_t rows = (size_t)d.U * d.S, net_n = (size_t)d.U * 3 * d.T;
-  int r;
-  if (!c->timed_out) {   // first call (or one whose allocations failed partway: what it got is kept, only the missing buffers are allocated)
-    AuditTimedArgs& a = c->timed;
-    if ((!a.row_lo && (r = dalloc(c, &a.row_lo, rows))) || (!a.row_hi && (r = dalloc(c, &a.row_hi, rows))) || (!a.row_time && (r = dalloc(c, &a.row_time, rows))) ||
-        (!a.row_qlo && (r = dalloc(c, &a.row_qlo, rows))) || (!a.row_qhi && (r = dalloc(c, &a.row_qhi, rows))) || (!c->timed_net && (r = dalloc(c, &c->timed_net, net_n))) ||
-        (!c->timed_pt && (r = dalloc(c, &c->timed_pt, d.U))) || (r = dalloc(c, &c->timed_out, d.U))) return r;
-  }
-  if (net_host && ((r = upload(c, c->timed_net, net_host, net_n * 8)) || (r = upload(c, c->timed_pt, pt_host, (size_t)d.U * 8)))) return r;
-  out = c->timed;
-  out.net = net_host ? c->timed_net : d.spline; out.pt = net_host ? c->timed_pt : d.piece_time;
-  out.range = range > 0 ? range : d.offset + 2 * d.margin; out.levels = levels;
-  return TJ_OK;
-}
-// tj_audit_timed / tj_group_audit_timed.  net_host [U][3][T] and pt_host [U]: every robot's control points and piece_time as a group read them from the owners, or null = the context's own.
-int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host, const double* pt_host, tj_audit_timed_robot* out, double* seg_lo, double* seg_hi) {
-  if (!c || !out) return TJ_ERR_INVALID;
-  if (range != range) { c->err = "tj_audit_timed: range is NaN"; return TJ_ERR_INVALID; }
-  if (levels > 6) { c->err = "tj_audit_timed: levels must be 0..6 (or negative for the default): one segment's sub-windows are one wave wide"; return TJ_ERR_INVALID; }
-  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
-  const Dev& d = c->d;
-  if (d.multi() && d.world > 1 && !(net_host && pt_host)) {
-    c->err = "tj_audit_timed: a sharded context does not hold the other ranks' piece_time as their owners have it; use tj_group_audit_timed";
-    return TJ_ERR_UNSUPPORTED;
-  }
-  const size_t rows = (size_t)d.U * d.S;
-  QUIESCE(c);
-  AuditTimedArgs a;
-  int r = timed_setup(c, range, levels < 0 ? TJ_AUDIT_TIMED_LEVELS : levels, net_host, pt_host, a);
-  if (r) return r;
-  const int owned = d.u1 - d.u0;
-  HIPCHK(c, hipMemsetAsync(c->timed_out, 0, (size_t)d.U * sizeof(tj_audit_timed_robot), c->stream));
-  if (seg_lo || seg_hi) { HIPCHK(c, hipMemsetAsync(a.row_lo, 0, rows * 8, c->stream)); HIPCHK(c, hipMemsetAsync(a.row_hi, 0, rows * 8, c->stream)); }
-  if (owned > 0) {   // two plain launches whatever the fleet's size: not part of the iteration schedules, not counted by tj_launch_count
-    hipLaunchKernelGGL(k_audit_timed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
-    hipLaunchKernelGGL(k_audit_timed_reduce, dim3(owned), dim3(64), 0, c->stream, d, a, c->timed_out);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->timed_out, (size_t)d.U * sizeof(tj_audit_timed_robot), hipMemcpyDeviceToHost, c->stream));
-  if (seg_lo) HIPCHK(c, hipMemcpyAsync(seg_lo, a.row_lo, rows * 8, hipMemcpyDeviceToHost, c->stream));
-  if (seg_hi) HIPCHK(c, hipMemcpyAsync(seg_hi, a.row_hi, rows * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TJ_OK;
-}
-}  // namespace
-
 int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi) { return audit_timed_run(c, range, levels, nullptr, nullptr, records, seg_lo, seg_hi); }
 int tj_audit_timed_record_size(void) { return (int)sizeof(tj_audit_timed_robot); }
-
-namespace {
-// tj_closest_approach / tj_group_closest_approach.  net_host / pt_host as in audit_timed_run.
-int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_closest_robot* out) {
-  if (!c || !out) return TJ_ERR_INVALID;
-  if (range != range) { c->err = "tj_closest_approach: range is NaN"; return TJ_ERR_INVALID; }
-  if (tol != tol) { c->err = "tj_closest_approach: tol is NaN"; return TJ_ERR_INVALID; }
-  if (max_depth > TJ_CLOSEST_MAX_DEPTH) { c->err = "tj_closest_approach: max_depth must be 0.." + std::to_string(TJ_CLOSEST_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
-  if (max_windows > TJ_CLOSEST_FRONTIER) { c->err = "tj_closest_approach: max_windows must be 1.." + std::to_string(TJ_CLOSEST_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
-  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
-  const Dev& d = c->d;
-  if (d.multi() && d.world > 1 && !(net_host && pt_host)) {
-    c->err = "tj_closest_approach: a sharded context does not hold the other ranks' piece_time as their owners have it; use tj_group_closest_approach";
-    return TJ_ERR_UNSUPPORTED;
-  }
-  QUIESCE(c);
-  AuditTimedArgs t;
-  int r = timed_setup(c, range, 0, net_host, pt_host, t);
-  if (r) return r;
-  if (!c->closest_out) {   // first call (or one whose allocations failed partway)
-    ClosestArgs& a = c->closest;
-    if ((!a.list && (r = dalloc(c, &a.list, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER))) || (!a.klo && (r = dalloc(c, &a.klo, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER))) ||
-        (!a.count && (r = dalloc(c, &a.count, (size_t)d.U * 3))) || (r = dalloc(c, &c->closest_out, d.U))) return r;
-  }
-  ClosestArgs a = c->closest;
-  a.net = t.net; a.pt = t.pt; a.range = t.range; a.tol = tol < 0 ? TJ_CLOSEST_TOL : tol;
-  a.max_depth = max_depth < 0 ? TJ_CLOSEST_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_CLOSEST_FRONTIER : max_windows;
-  a.seed = c->timed_out;
-  const int owned = d.u1 - d.u0;
-  HIPCHK(c, hipMemsetAsync(c->closest_out, 0, (size_t)d.U * sizeof(tj_closest_robot), c->stream));
-  HIPCHK(c, hipMemsetAsync(a.count, 0, (size_t)d.U * 3 * sizeof(int), c->stream));
-  if (owned > 0) {   // four plain launches whatever the fleet's size and the depth: not part of the iteration schedules, not counted by tj_launch_count
-    hipLaunchKernelGGL(k_audit_timed, dim3(owned * d.S), dim3(64), 0, c->stream, d, t);
-    hipLaunchKernelGGL(k_audit_timed_reduce, dim3(owned), dim3(64), 0, c->stream, d, t, c->timed_out);
-    hipLaunchKernelGGL(k_closest_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
-    hipLaunchKernelGGL(k_closest_refine, dim3(owned), dim3(CL_THREADS), 0, c->stream, d, a, c->closest_out);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->closest_out, (size_t)d.U * sizeof(tj_closest_robot), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return TJ_OK;
-}
-}  // namespace
-
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records) { return closest_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, records); }
 int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
 
 // tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
   if (!c || !out) return TJ_ERR_INVALID;
-  if (range != range) { c->err = "tj_obstacle_approach: range is NaN"; return TJ_ERR_INVALID; }
-  if (tol != tol) { c->err = "tj_obstacle_approach: tol is NaN"; return TJ_ERR_INVALID; }
+  int r;
+  if ((r = query_nan(c, "tj_obstacle_approach", "range", range)) || (r = query_nan(c, "tj_obstacle_approach", "tol", tol))) return r;
   if (max_depth > TJ_OBSTACLE_MAX_DEPTH) { c->err = "tj_obstacle_approach: max_depth must be 0.." + std::to_string(TJ_OBSTACLE_MAX_DEPTH) + " (or negative for the default): deeper windows are not dyadic in a double"; return TJ_ERR_INVALID; }
   if (max_windows > TJ_OBSTACLE_FRONTIER) { c->err = "tj_obstacle_approach: max_windows must be 1.." + std::to_string(TJ_OBSTACLE_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
-  if (!c->have_state) { c->err = "tj_init_state has not been called"; return TJ_ERR_INVALID; }
+  if ((r = query_state(c, "tj_obstacle_approach", false, false))) return r;
   const Dev& d = c->d;
   const int owned = d.u1 - d.u0;
   const size_t rows = (size_t)d.U * d.S, items = (size_t)(owned > 0 ? owned : 1) * 2 * TJ_OBSTACLE_FRONTIER;
   QUIESCE(c);
-  int r;
-  if (!c->obst_out) {   // first call (or one whose allocations failed partway: what it got is kept)
-    ObstArgs& a = c->obst;
-    if ((!a.row && (r = dalloc(c, &a.row, rows))) || (!a.row_lo && (r = dalloc(c, &a.row_lo, rows))) || (!a.best && (r = dalloc(c, &a.best, d.U))) ||
-        (!a.list && (r = dalloc(c, &a.list, items))) || (!a.klo && (r = dalloc(c, &a.klo, items))) || (!a.count && (r = dalloc(c, &a.count, (size_t)d.U * 2))) ||
-        (!c->obst_ctl && (r = dalloc(c, &c->obst_ctl, 1))) || (r = dalloc(c, &c->obst_out, d.U))) return r;
-  }
-  if (d.N > 0 && !c->audit_order) {   // sorted primitive -> caller's index: tj_audit's table, made by whichever of the two runs first
-    if ((r = dalloc(c, &c->audit_order, d.N, &c->cloud_allocs)) || (r = upload(c, c->audit_order, c->cloud_order.data(), (size_t)d.N * 4))) return r;
-  }
-  ObstArgs a = c->obst;
-  a.net = d.spline; a.pt = d.piece_time; a.order = c->audit_order;
-  a.range = range > 0 ? range : d.offset + 2 * d.margin; a.tol = tol < 0 ? TJ_OBSTACLE_TOL : tol;
+  ObstArgs& b = c->obst;
+  if ((r = query_buf(c, b.row, rows)) || (r = query_buf(c, b.row_lo, rows)) || (r = query_buf(c, b.best, d.U)) || (r = query_buf(c, b.list, items)) || (r = query_buf(c, b.klo, items)) ||
+      (r = query_buf(c, b.count, (size_t)d.U * 2)) || (r = query_buf(c, c->obst_out, d.U)) || (r = ensure_order(c))) return r;
+  ObstArgs a = b;
+  Dev da;
+  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = walk_dev(c, da))) return r;
+  a.order = c->q_order; a.range = query_range(d, range); a.tol = tol < 0 ? TJ_OBSTACLE_TOL : tol;
   a.max_depth = max_depth < 0 ? TJ_OBSTACLE_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_OBSTACLE_FRONTIER : max_windows; a.cap = TJ_OBSTACLE_FRONTIER;
-  Dev da = d; da.ctl = c->obst_ctl;   // (the walk reports a frontier overflow through Dev::ctl: the query's own block, never the solver's)
-  HIPCHK(c, hipMemsetAsync(c->obst_ctl, 0, sizeof(Ctl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->obst_out, 0, (size_t)d.U * sizeof(tj_obstacle_robot), c->stream));
-  HIPCHK(c, hipMemsetAsync(a.count, 0, (size_t)d.U * 2 * sizeof(int), c->stream));
-  if (owned > 0) {   // three plain launches whatever the fleet's size, the number of primitives and the depth: not part of the iteration schedules, not counted by tj_launch_count
-    if (d.prim == 3) {
-      hipLaunchKernelGGL(k_obst_seed<3>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
-      hipLaunchKernelGGL(k_obst_append<3>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
-      hipLaunchKernelGGL(k_obst_refine<3>, dim3(owned), dim3(OA_THREADS), 0, c->stream, da, a, c->obst_out);
-    } else {
-      hipLaunchKernelGGL(k_obst_seed<1>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
-      hipLaunchKernelGGL(k_obst_append<1>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
-      hipLaunchKernelGGL(k_obst_refine<1>, dim3(owned), dim3(OA_THREADS), 0, c->stream, da, a, c->obst_out);
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  int err = 0;
-  HIPCHK(c, hipMemcpyAsync(&err, &c->obst_ctl->error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out, c->obst_out, (size_t)d.U * sizeof(tj_obstacle_robot), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (err & ERR_FRONT_OVERFLOW) { c->err = "tj_obstacle_approach: the BVH frontier of a segment overflowed at this range (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one hull): lower `range`"; return TJ_ERR_CAPACITY; }
-  return TJ_OK;
+  if ((r = query_clear(c, c->obst_out, d.U)) || (r = query_clear(c, a.count, (size_t)d.U * 2))) return r;
+  if (owned > 0)   // three launches whatever the fleet's size, the number of primitives and the depth
+    with_prim(d, [&](auto prim) {
+      constexpr int PRIM = decltype(prim)::value;
+      hipLaunchKernelGGL(k_obst_seed<PRIM>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+      hipLaunchKernelGGL(k_obst_append<PRIM>, dim3(owned * d.S), dim3(64), 0, c->stream, da, a);
+      hipLaunchKernelGGL(k_obst_refine<PRIM>, dim3(owned), dim3(OA_THREADS), 0, c->stream, da, a, c->obst_out);
+    });
+  if ((r = query_fetch(c, out, c->obst_out, d.U))) return r;
+  return query_finish(c, "tj_obstacle_approach");
 }
 int tj_obstacle_record_size(void) { return (int)sizeof(tj_obstacle_robot); }
 

@@ -601,91 +601,65 @@ int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, doub
   return group_fail(g, TJ_ERR_INVALID, "tj_group_get_state: no such robot");
 }
 
-// tj_audit of every robot by the rank that owns it.  A rank holds the OTHER ranks' control points as its last exchange left them -- one line search behind the owners after a
-// batch --, so every robot's control points are first read from its owner and handed to every rank's audit: the records are bitwise those of one context.
+}  // extern "C" (a template cannot have C linkage)
+
+// A read-only query of every robot by the rank that owns it, the shape of the four tj_group_* queries below: gather, run on every rank, scatter.  A rank holds the OTHER ranks'
+// control points as its last exchange left them -- one line search behind the owners after a batch -- and a piece_time for its own robots only, so what the query reads of
+// other robots (nets: control points [U][3][T], pts: piece_time [U]) is first read from the owners and handed to every rank: the records are bitwise those of one context.
+// run(ctx, net or null, pt or null, part) -> rc; null = the context's own state, which with one rank is current.  rows: per-segment arrays [U][S] as (what run wrote, the
+// caller's) to scatter with the owned records, or null pairs.
+struct GroupRows { const double* part; double* out; };
+template <class Rec, class Run>
+int group_query(tj_group* g, bool nets, bool pts, Rec* out, GroupRows rows0, GroupRows rows1, Run&& run) {
+  if (!g || !out) return TJ_ERR_INVALID;
+  GROUP_LIVE(g);
+  const Dev& d0 = g->ctx[0]->d;
+  const int U = d0.U, S = d0.S, T = d0.T;
+  const bool staged = g->n > 1;
+  std::vector<double> net(nets && staged ? (size_t)U * 3 * T : 0), pt(pts && staged ? U : 0);
+  for (int u = 0; u < U && (!net.empty() || !pt.empty()); u++) {
+    const int rc = tj_group_get_state(g, u, net.empty() ? nullptr : &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, pt.empty() ? nullptr : &pt[u]);
+    if (rc < 0) return rc;
+  }
+  std::vector<Rec> part(U);
+  for (int r = 0; r < g->n; r++) {
+    tj_ctx* c = g->ctx[r];
+    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
+    const int rc = run(c, net.empty() ? nullptr : net.data(), pt.empty() ? nullptr : pt.data(), part.data());
+    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
+    for (int u = c->d.u0; u < c->d.u1; u++) {
+      out[u] = part[u];
+      for (const GroupRows& w : {rows0, rows1}) if (w.out) std::copy(w.part + (size_t)u * S, w.part + (size_t)(u + 1) * S, w.out + (size_t)u * S);
+    }
+  }
+  return TJ_OK;
+}
+// a scratch copy of a per-segment array the caller asked for (null: not asked for, nothing to scatter)
+static std::vector<double> group_rows(const tj_group* g, const double* wanted) { return std::vector<double>(g && wanted ? (size_t)g->ctx[0]->d.U * g->ctx[0]->d.S : 0); }
+
+extern "C" {
+
 int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) {
-  if (!g || !out) return TJ_ERR_INVALID;
-  GROUP_LIVE(g);
-  const Dev& d0 = g->ctx[0]->d;
-  const int U = d0.U, S = d0.S, T = d0.T;
-  std::vector<double> net((size_t)U * 3 * T);
-  for (int u = 0; u < U; u++) { const int rc = tj_group_get_state(g, u, &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, nullptr); if (rc < 0) return rc; }
-  std::vector<tj_audit_robot> part(U);
-  std::vector<double> so(seg_obs ? (size_t)U * S : 0), sp(seg_pair ? (size_t)U * S : 0);
-  for (int r = 0; r < g->n; r++) {
-    tj_ctx* c = g->ctx[r];
-    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
-    const int rc = audit_run(c, range, g->n > 1 ? net.data() : nullptr, part.data(), seg_obs ? so.data() : nullptr, seg_pair ? sp.data() : nullptr);
-    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
-    for (int u = c->d.u0; u < c->d.u1; u++) {
-      out[u] = part[u];
-      if (seg_obs) std::copy(so.begin() + (size_t)u * S, so.begin() + (size_t)(u + 1) * S, seg_obs + (size_t)u * S);
-      if (seg_pair) std::copy(sp.begin() + (size_t)u * S, sp.begin() + (size_t)(u + 1) * S, seg_pair + (size_t)u * S);
-    }
-  }
-  return TJ_OK;
+  std::vector<double> so = group_rows(g, seg_obs), sp = group_rows(g, seg_pair);
+  return group_query(g, true, false, out, {so.data(), seg_obs}, {sp.data(), seg_pair}, [&](tj_ctx* c, const double* net, const double*, tj_audit_robot* part) {
+    return audit_run(c, range, net, part, seg_obs ? so.data() : nullptr, seg_pair ? sp.data() : nullptr); });
 }
 
-// tj_audit_timed of every robot by the rank that owns it.  Like tj_group_audit every robot's control points are read from its owner -- and so is its piece_time, which a rank
-// holds for its own robots only: the records are bitwise those of one context.
 int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* out, double* seg_lo, double* seg_hi) {
-  if (!g || !out) return TJ_ERR_INVALID;
-  GROUP_LIVE(g);
-  const Dev& d0 = g->ctx[0]->d;
-  const int U = d0.U, S = d0.S, T = d0.T;
-  std::vector<double> net((size_t)U * 3 * T), pt(U);
-  for (int u = 0; u < U; u++) { const int rc = tj_group_get_state(g, u, &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, &pt[u]); if (rc < 0) return rc; }
-  std::vector<tj_audit_timed_robot> part(U);
-  std::vector<double> sl(seg_lo ? (size_t)U * S : 0), sh(seg_hi ? (size_t)U * S : 0);
-  for (int r = 0; r < g->n; r++) {
-    tj_ctx* c = g->ctx[r];
-    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
-    const bool own = g->n == 1;
-    const int rc = audit_timed_run(c, range, levels, own ? nullptr : net.data(), own ? nullptr : pt.data(), part.data(), seg_lo ? sl.data() : nullptr, seg_hi ? sh.data() : nullptr);
-    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
-    for (int u = c->d.u0; u < c->d.u1; u++) {
-      out[u] = part[u];
-      if (seg_lo) std::copy(sl.begin() + (size_t)u * S, sl.begin() + (size_t)(u + 1) * S, seg_lo + (size_t)u * S);
-      if (seg_hi) std::copy(sh.begin() + (size_t)u * S, sh.begin() + (size_t)(u + 1) * S, seg_hi + (size_t)u * S);
-    }
-  }
-  return TJ_OK;
+  std::vector<double> sl = group_rows(g, seg_lo), sh = group_rows(g, seg_hi);
+  return group_query(g, true, true, out, {sl.data(), seg_lo}, {sh.data(), seg_hi}, [&](tj_ctx* c, const double* net, const double* pt, tj_audit_timed_robot* part) {
+    return audit_timed_run(c, range, levels, net, pt, part, seg_lo ? sl.data() : nullptr, seg_hi ? sh.data() : nullptr); });
 }
 
-// tj_closest_approach of every robot by the rank that owns it; control points and piece_time of every robot from its owner, as tj_group_audit_timed
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* out) {
-  if (!g || !out) return TJ_ERR_INVALID;
-  GROUP_LIVE(g);
-  const Dev& d0 = g->ctx[0]->d;
-  const int U = d0.U, T = d0.T;
-  std::vector<double> net((size_t)U * 3 * T), pt(U);
-  for (int u = 0; u < U; u++) { const int rc = tj_group_get_state(g, u, &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, &pt[u]); if (rc < 0) return rc; }
-  std::vector<tj_closest_robot> part(U);
-  for (int r = 0; r < g->n; r++) {
-    tj_ctx* c = g->ctx[r];
-    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
-    const bool own = g->n == 1;
-    const int rc = closest_run(c, range, tol, max_depth, max_windows, own ? nullptr : net.data(), own ? nullptr : pt.data(), part.data());
-    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
-    for (int u = c->d.u0; u < c->d.u1; u++) out[u] = part[u];
-  }
-  return TJ_OK;
+  return group_query(g, true, true, out, {}, {}, [&](tj_ctx* c, const double* net, const double* pt, tj_closest_robot* part) {
+    return closest_run(c, range, tol, max_depth, max_windows, net, pt, part); });
 }
 
-// tj_obstacle_approach of every robot by the rank that owns it, from that rank's own state (nothing of another robot is read)
+// from every rank's own state: nothing of another robot is read
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
-  if (!g || !out) return TJ_ERR_INVALID;
-  GROUP_LIVE(g);
-  const int U = g->ctx[0]->d.U;
-  std::vector<tj_obstacle_robot> part(U);
-  for (int r = 0; r < g->n; r++) {
-    tj_ctx* c = g->ctx[r];
-    if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
-    const int rc = tj_obstacle_approach(c, range, tol, max_depth, max_windows, part.data());
-    if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
-    for (int u = c->d.u0; u < c->d.u1; u++) out[u] = part[u];
-  }
-  return TJ_OK;
+  return group_query(g, false, false, out, {}, {}, [&](tj_ctx* c, const double*, const double*, tj_obstacle_robot* part) {
+    return tj_obstacle_approach(c, range, tol, max_depth, max_windows, part); });
 }
 
 }  // extern "C"

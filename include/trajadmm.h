@@ -307,6 +307,62 @@ typedef struct tj_closest_robot {
 } tj_closest_robot;
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);
 int tj_closest_record_size(void);   /* sizeof(tj_closest_robot) */
+/* ---- tj_pair_approach: the conflict graph -- EVERY pair of robots that comes close at equal flight times, each with its own converged separation and time
+ * (csrc/kernels_pair_approach.h; read-only like tj_closest_approach).  tj_closest_approach returns one record per robot, its single worst partner, and prunes
+ * every other partner's windows against that partner's hi: the other separations are never computed.  Here the answer is per DIRECTED PAIR (u, q), u owned,
+ * q != u: how close does u come to q at equal flight times over u's flight.  Time, hover after arrival, hull formation, the cuts at q's segment boundaries,
+ * the restriction of both raw nets, the box prefilter against `range`, the certificate rule for lo and the order (hi, segment, partner, time) are
+ * tj_closest_approach's, unchanged.  For one directed pair:
+ *   seeds    the level-0 windows (tr, q, j, [ca, cb]) tj_audit_timed evaluates for u against this q and that pass the box prefilter.
+ *   listed   (u, q) is listed if and only if some seed has lo < range or hi < range.  A pair that is not listed is certified to be at least `range` apart over
+ *            u's flight and produces no row.
+ *   search   tj_closest_approach's seeds / round / bracket / stop with "the robot's windows" replaced by "the pair's windows": best = the pair's smallest
+ *            hi < range; live = {lo < range and lo < best.hi}; live windows are halved, children are evaluated from the RAW hulls and kept against the round's
+ *            FINAL pair best; terminal windows as there.  Stop: hi - lo <= tol | live empty | every live window terminal | max_depth | a live set of THIS PAIR
+ *            above max_windows (TRUNCATED: the record of the last completed round; `windows` counts the overflowing round too).  Every field is a function of
+ *            the state alone.
+ *   record   lo <= the minimum separation of `robot` from `partner` over robot's flight <= hi; hi is attained at `time` in robot's segment `segment`; segment
+ *            -1, time -1.0 and hi == range when no sample lies below range (the pair is listed for its lo).  Flags against `offset`, tj_closest_approach's
+ *            meanings and values.  (u, q) and (q, u) are two rows: u's flight and q's flight end at different times.
+ *   rows     sorted by (robot, partner) ascending; neither the order of evaluation nor that of any atomic append is visible in the output.
+ * *n is the number of listed pairs.  *n > cap: TJ_ERR_CAPACITY, the first `cap` rows in order have been written and *n says what to allocate; cap = 0 with
+ * rows == NULL is a valid count-only call.  range <= 0: offset + 2 * margin; +infinity is valid.  tol < 0: TJ_PAIR_TOL; 0 is valid.  max_depth < 0:
+ * TJ_PAIR_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0: TJ_PAIR_FRONTIER; above TJ_PAIR_MAX_WINDOWS TJ_ERR_INVALID.  NaN range or tol, n == NULL,
+ * cap < 0, rows == NULL with cap > 0, a call before tj_init_state: TJ_ERR_INVALID.  Single-UAV mode: *n = 0 and TJ_OK.  A plain SHARDED context (world > 1)
+ * returns TJ_ERR_UNSUPPORTED like tj_closest_approach; tj_group_pair_approach reads every robot's control points and piece_time from its owner and returns
+ * the owners' rows in (robot, partner) order, bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, and is a function of cap and max_windows (S = piece_num * res segments):
+ *   cap * (2 * max_windows * (40 + 8) + (2 * S + 2) * 48 + 16 + 48) bytes     (live lists and their children's lo, the pairs' level-0 seeds, counters and rows)
+ * plus the bitmask, owned * ceil(uav_num / 32) * 8 bytes (512 KB at 2048 robots).  A call whose figure exceeds TJ_PAIR_MAX_BYTES is refused up front with
+ * TJ_ERR_INVALID: lower cap (rows beyond it are counted, not lost) or max_windows.  At the defaults a row costs 10 144 bytes at S = 40.
+ * At most FOUR launches whatever the fleet's size, the number of pairs and the depth; no host loop over robots, pairs or rounds.  Changes no solver state,
+ * statistics or launch count.  tj_closest_approach's STATED LIMIT (a window without the GJK's certificate counts lo = 0) holds here per pair.
+ * The defaults are measured (tests/pair_approach_ref.py default_tolerance, the restatement, on the CPU): tol = 0 and max_depth = 40 at the default range on the
+ * final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz and e2e_scn_b_coupled.npz; per depth the largest hi - lo over the listed pairs:
+ *   depth   0        1        2        3        4        5        6        7        8        9        10       11       12       13       14       15       16       17
+ *   width   2.14e-2  3.61e-3  1.32e-3  3.19e-4  8.18e-5  1.83e-5  4.73e-6  1.35e-6  2.64e-7  6.58e-8  1.68e-8  4.10e-9  1.24e-9  3.28e-10 7.95e-11 1.18e-11 2.50e-12 0
+ * The width shrinks all the way: the floor is the last positive width, 2.50e-12 at depth 16, and TJ_PAIR_TOL is the smallest power of ten >= 10 x that.
+ *   state                 listed directed pairs   largest live set of any pair at any depth
+ *   e2e_scn_b (8 UAVs)    14                      2
+ *   e2e_scn_c3 (64 UAVs)  126                     2
+ *   e2e_scn_b_coupled     14                      2
+ * TJ_PAIR_FRONTIER is the next power of two >= 4 x the largest live set, and at least 64.  The listed pairs are what `cap` has to hold at the default range:
+ * about two per robot on a converged state (each robot's neighbours in both directions). */
+#define TJ_PAIR_CONTACT   1   /* hi < range was found and hi <= offset: the two ARE within offset at `time` */
+#define TJ_PAIR_CLEAR     2   /* lo > offset: separation of this pair certified over robot's flight */
+#define TJ_PAIR_CONVERGED 4   /* hi - lo <= tol, or nothing was left that could hold a smaller separation */
+#define TJ_PAIR_TRUNCATED 8   /* the pair's live set outgrew max_windows: the bracket of the last completed round is returned */
+#define TJ_PAIR_MAX_DEPTH 40
+#define TJ_PAIR_FRONTIER  64
+#define TJ_PAIR_MAX_WINDOWS 4096
+#define TJ_PAIR_MAX_BYTES (1ll << 31)
+#define TJ_PAIR_TOL 1e-10
+typedef struct tj_pair_record {
+  double lo, hi, time;            /* lo <= min separation of `robot` from `partner` over robot's flight <= hi */
+  int robot, partner, segment, depth, flags, windows;
+} tj_pair_record;
+int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);
+int tj_pair_record_size(void);   /* sizeof(tj_pair_record) */
 /* ---- tj_obstacle_approach: how close the FLOWN CURVE of every robot comes to an obstacle primitive, when, and to which one, converged to a tolerance the
  * caller names (csrc/kernels_obstacle_approach.h; read-only like tj_audit).  tj_audit's obs_clearance is the distance of a segment's 6-point hull: what the
  * solver constrains and the right certificate for a converged state, but only a lower bound on what the vehicle does, without a time, and on the GJK's
@@ -524,6 +580,7 @@ int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, doub
 int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair);   /* tj_audit of every robot by its owner, against every robot's control points as its owner holds them: bitwise one context's */
 int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);   /* tj_audit_timed of every robot by its owner; every robot's control points AND piece_time are read from its owner: bitwise one context's */
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);   /* tj_closest_approach of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
+int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);   /* tj_pair_approach of every robot by its owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */

@@ -34,6 +34,7 @@ EXPORTS = [
     "tj_audit_timed", "tj_audit_timed_record_size", "tj_group_audit_timed",
     "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
     "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
+    "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -136,6 +137,63 @@ OBSTACLE_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8)
 OBSTACLE_TOL = 1e-11        # TJ_OBSTACLE_TOL: what tol=None selects
 OBSTACLE_MAX_DEPTH = 40     # TJ_OBSTACLE_MAX_DEPTH
 OBSTACLE_FRONTIER = 4096    # TJ_OBSTACLE_FRONTIER
+
+
+class TjPairRecord(C.Structure):
+    """mirror of tj_pair_record (include/trajadmm.h); tj_pair_record_size() is its sizeof on the C side"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("time", C.c_double), ("robot", C.c_int), ("partner", C.c_int), ("segment", C.c_int),
+                ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int)]
+
+
+PAIR_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8)
+PAIR_TOL = 1e-10           # TJ_PAIR_TOL: what tol=None selects
+PAIR_MAX_DEPTH = 40        # TJ_PAIR_MAX_DEPTH
+PAIR_FRONTIER = 64         # TJ_PAIR_FRONTIER: what max_windows=None selects
+PAIR_MAX_WINDOWS = 4096    # TJ_PAIR_MAX_WINDOWS
+
+
+def merge_pairs(rows, rng, offset):
+    """the directed rows of pair_approach -> one row per unordered pair a < b (`robot` = a, `partner` = b) with a listed direction: lo = min, hi = min over
+    the two directions, a missing direction counting as `rng` (an unlisted direction is certified at least rng apart, so the merge is sound); `time`,
+    `segment` and `of` (whose flight the hi sample belongs to) from the direction with the smaller hi, on equality from (a, b); depth = max, windows = sum;
+    contact / truncated of either direction, clear / converged of both (a missing direction is converged, and clear iff rng > offset).  Pure numpy."""
+    u, q = rows["robot"].astype(np.int64), rows["partner"].astype(np.int64)
+    a, b = np.minimum(u, q), np.maximum(u, q)
+    span = int(b.max()) + 1 if len(b) else 1
+    key, ikey = np.unique(a * span + b, return_inverse=True)
+    n = len(key)
+    fwd, bwd = np.full(n, -1), np.full(n, -1)        # row index of (a, b) and of (b, a), -1: not listed
+    fwd[ikey[u < q]] = np.flatnonzero(u < q); bwd[ikey[u > q]] = np.flatnonzero(u > q)
+    either, both = PAIR_FLAGS["contact"] | PAIR_FLAGS["truncated"], PAIR_FLAGS["clear"] | PAIR_FLAGS["converged"]
+    absent = dict(lo=rng, hi=rng, depth=0, windows=0, flags=PAIR_FLAGS["converged"] | (PAIR_FLAGS["clear"] if rng > offset else 0))
+
+    def side(ix, name):
+        v = rows[name][np.maximum(ix, 0)] if len(rows[name]) else np.zeros(n, dtype=rows[name].dtype)
+        return np.where(ix >= 0, v, absent[name]) if name in absent else v
+
+    take_f = (fwd >= 0) & ((bwd < 0) | (side(fwd, "hi") <= side(bwd, "hi")))
+    src = np.where(take_f, fwd, bwd)
+    ff, fb = side(fwd, "flags").astype(np.int32), side(bwd, "flags").astype(np.int32)
+    return dict(robot=(key // span).astype(np.int32), partner=(key % span).astype(np.int32), lo=np.minimum(side(fwd, "lo"), side(bwd, "lo")),
+                hi=np.minimum(side(fwd, "hi"), side(bwd, "hi")), time=side(src, "time"), segment=side(src, "segment"),
+                of=np.where(take_f, key // span, key % span).astype(np.int32), depth=np.maximum(side(fwd, "depth"), side(bwd, "depth")).astype(np.int32),
+                windows=(side(fwd, "windows") + side(bwd, "windows")).astype(np.int32), flags=((ff | fb) & either) | (ff & fb & both))
+
+
+def _pair_approach(call, params, range, tol, max_depth, max_windows, symmetric):
+    """shared by Solver.pair_approach / Group.pair_approach: call(range, tol, max_depth, max_windows, rows, cap, n).  The count-only call first, then the rows."""
+    args = (C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
+            C.c_int(0 if max_windows is None else int(max_windows)))
+    n = C.c_int(0)
+    call(*args, None, C.c_int(0), C.byref(n))
+    rec = (TjPairRecord * max(n.value, 1))()
+    if n.value:
+        call(*args, rec, C.c_int(n.value), C.byref(n))
+    rows = _records(TjPairRecord, rec[:n.value])
+    if not symmetric:
+        return rows
+    rng = float(range) if range is not None and range > 0 else params["offset"] + 2 * params["margin"]
+    return merge_pairs(rows, rng, params["offset"])
 
 
 class TrajAdmmError(RuntimeError):
@@ -563,6 +621,14 @@ class Solver:
         Group.closest_approach reads every robot's piece_time from its owner."""
         return _approach(TjClosestRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_closest_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
+    def pair_approach(self, range=None, tol=None, max_depth=None, max_windows=None, symmetric=False):
+        """tj_pair_approach: one row per DIRECTED pair (robot, partner) that comes within `range` at equal flight times over robot's flight (an unlisted pair
+        is certified at least `range` apart): lo <= the pair's closest approach <= hi converged to `tol` (None: PAIR_TOL) by the pair's own branch and bound,
+        `time` / `segment` of the hi sample, `depth`, `windows`, `flags` (PAIR_FLAGS).  Dict of numpy arrays [n], sorted by (robot, partner).
+        symmetric=True: one row per unordered pair (merge_pairs).  Read-only.  A sharded solver (world > 1) raises: use Group.pair_approach."""
+        return _pair_approach(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_pair_approach(self._ctx, r, t, d, w, rows, cap, n)), self.params,
+                              range, tol, max_depth, max_windows, symmetric)
+
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_obstacle_approach: per robot lo <= closest approach of the FLOWN CURVE to any obstacle primitive <= hi, converged to `tol` (None: OBSTACLE_TOL)
         by a branch and bound over windows of the segments' hulls; `time`, `index` (the caller's point / face index), `segment` of the hi sample (-1 where
@@ -595,6 +661,7 @@ class Group:
         p = dict(scenes.DEFAULT_PARAMS)
         if params:
             p.update(params)
+        self.params = p
         self.mode, self.U, self.P = scene["mode"], scene["U"], scene["P"]
         self.res = p["res"]
         self.S, self.T = self.P * self.res, 3 * self.P + 3
@@ -687,6 +754,11 @@ class Group:
     def closest_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_closest_approach: Solver.closest_approach of every robot from the rank that owns it (bitwise one context's)"""
         return _approach(TjClosestRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_group_closest_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+
+    def pair_approach(self, range=None, tol=None, max_depth=None, max_windows=None, symmetric=False):
+        """tj_group_pair_approach: Solver.pair_approach from the ranks that own the robots, in (robot, partner) order (bitwise one context's)"""
+        return _pair_approach(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_group_pair_approach(self._g, r, t, d, w, rows, cap, n)), self.params,
+                              range, tol, max_depth, max_windows, symmetric)
 
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""

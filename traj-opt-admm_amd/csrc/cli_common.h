@@ -206,6 +206,28 @@ inline void print_closest_approach(const std::vector<tj_closest_robot>& rec) {
   else std::cout << "closest fleet hi " << rec[who].hi << " uav " << who << " uav " << rec[who].robot << " time " << rec[who].time << " contact " << contact << std::endl;
 }
 
+// --pair-approach: one line per listed directed pair, in the library's (robot, partner) order, and the counts of pairs in contact, undecided and certified clear
+inline void print_pair_approach(const std::vector<tj_pair_record>& rows) {
+  std::cout.precision(17);
+  int contact = 0, clear = 0;
+  for (const tj_pair_record& r : rows) {
+    std::cout << "pair uav " << r.robot << " uav " << r.partner << " lo " << r.lo << " hi " << r.hi << " seg " << r.segment << " time " << r.time << " depth " << r.depth
+              << " windows " << r.windows << " flags " << r.flags << std::endl;
+    contact += r.flags & TJ_PAIR_CONTACT ? 1 : 0;
+    clear += !(r.flags & TJ_PAIR_CONTACT) && (r.flags & TJ_PAIR_CLEAR) ? 1 : 0;
+  }
+  std::cout << "pair fleet listed " << rows.size() << " contact " << contact << " undecided " << rows.size() - contact - clear << " clear " << clear << std::endl;
+}
+// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle)
+template <class F>
+inline int pair_approach_rows(F&& f, double tol, std::vector<tj_pair_record>& rows) {
+  int n = 0;
+  const int rc = f(0.0, tol, -1, 0, nullptr, 0, &n);
+  if (rc < 0) return rc;
+  rows.resize(n);
+  return n ? f(0.0, tol, -1, 0, rows.data(), n, &n) : rc;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

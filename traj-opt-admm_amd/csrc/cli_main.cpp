@@ -23,6 +23,9 @@
 // --obstacle-approach [TOL]: after the --closest-approach lines one line per robot from tj_obstacle_approach / tj_group_obstacle_approach -- the flown curve's closest
 // approach to an obstacle primitive converged to TOL (default the library's; default range), the primitive / segment / time, rounds, items evaluated, flag word -- and a
 // fleet summary (smallest hi, who, which primitive, when, any contact).  Works in the single-UAV main too.
+// --pair-approach [TOL]: after the --obstacle-approach lines one line per LISTED directed robot pair from tj_pair_approach / tj_group_pair_approach, sorted by (robot,
+// partner) -- every pair that comes within the default range at equal flight times, its closest approach converged to TOL (default the library's), segment / time,
+// rounds, windows evaluated, flag word -- and the counts of pairs in contact, undecided and clear.
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
 #include <chrono>
@@ -37,13 +40,14 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
   bool audit_timed = false; int audit_levels = -1;
   bool closest = false; double closest_tol = -1;
   bool obstacle = false; double obstacle_tol = -1;
+  bool pairs = false; double pairs_tol = -1;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -56,6 +60,7 @@ int main(int argc, char** argv) {
     else if (a == "--audit-timed") { audit_timed = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_levels = atoi(argv[++i]); }
     else if (a == "--closest-approach") { closest = true; if (i + 1 < argc && argv[i + 1][0] != '-') closest_tol = atof(argv[++i]); }
     else if (a == "--obstacle-approach") { obstacle = true; if (i + 1 < argc && argv[i + 1][0] != '-') obstacle_tol = atof(argv[++i]); }
+    else if (a == "--pair-approach") { pairs = true; if (i + 1 < argc && argv[i + 1][0] != '-') pairs_tol = atof(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -188,6 +193,12 @@ int main(int argc, char** argv) {
       std::vector<tj_obstacle_robot> rec(U);
       chk(group ? tj_group_obstacle_approach(grp, 0.0, obstacle_tol, -1, 0, rec.data()) : tj_obstacle_approach(ctx, 0.0, obstacle_tol, -1, 0, rec.data()), "tj_obstacle_approach");
       tjcli::print_obstacle_approach(rec);
+    }
+    if (pairs) {
+      std::vector<tj_pair_record> rows;
+      chk(tjcli::pair_approach_rows([&](double r, double t, int d, int w, tj_pair_record* out, int cap, int* n) {
+            return group ? tj_group_pair_approach(grp, r, t, d, w, out, cap, n) : tj_pair_approach(ctx, r, t, d, w, out, cap, n); }, pairs_tol, rows), "tj_pair_approach");
+      tjcli::print_pair_approach(rows);
     }
     if (!dump.empty()) {
       std::ofstream df(dump);

@@ -23,7 +23,7 @@
 //                      lo < best.hi appends it to the robot's list with one integer atomic on the robot's counter (append order is free: nothing
 //                      downstream depends on it; the windows below best.hi are a handful per robot, so there is nothing for a ballot to save).  The
 //                      number of windows evaluated is summed over the wave and added once.
-//   k_closest_refine   one workgroup of CL_THREADS per owned robot runs ALL rounds.  Lanes take the CHILDREN of the live list strided (item 2 p + c =
+//   k_closest_refine   one workgroup of CL_THREADS per owned robot runs ALL rounds (closest_rounds, shared with kernels_pair_approach.h).  Lanes take the CHILDREN of the live list strided (item 2 p + c =
 //                      child c of window p): the raw hulls of (u, tr) and (q, j) into the lane's columns of two LDS tiles, timed_window, lo to the robot's
 //                      klo slice.  A total-order reduction (hi, segment, partner, time) over the workgroup gives the round's best; a second pass over the
 //                      same items keeps lo < best.hi and appends to the other half of the ping-pong list (integer LDS counter), reducing min lo and "all
@@ -72,84 +72,93 @@ __global__ __launch_bounds__(64) void k_closest_seed(Dev D, ClosestArgs A) {
   if (lane == 0 && nev) atomicAdd(&A.count[3 * u + 1], nev);
 }
 
-__global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArgs A, tj_closest_robot* out) {
-  constexpr int NW = CL_THREADS / 64;
-  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S, u = D.u0 + blockIdx.x;
-  __shared__ double tp[18 * CL_THREADS], tq[18 * CL_THREADS], td[18 * CL_THREADS];
+// ALL rounds of one search by a workgroup of THREADS threads (k_closest_refine: a robot's windows; kernels_pair_approach.h: one pair's): the two-pass round of the header
+// comment on the ping-pong lists cur / nxt (maxw items each) and klo (2 * maxw), from the committed record (best, lo_u, n live windows in cur, not truncated) to the one the
+// search ends on.  Every thread holds the same values on entry and on return.
+template <int THREADS>
+__device__ __forceinline__ void closest_rounds(const Dev& D, const double* net, const double* pt, int u, double range, double tol, int max_depth, int maxw,
+                                               ClosestWin* cur, ClosestWin* nxt, double* klo, QBest& best, double& lo_u, int& n, int& windows, int& depth, bool& truncated) {
+  constexpr int NW = THREADS / 64;
+  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S;
+  __shared__ double tp[18 * THREADS], tq[18 * THREADS], td[18 * THREADS];
   __shared__ QBest wbest[NW];
   __shared__ double wlo[NW];
   __shared__ int wev[NW], wterm[NW], kept;
-  const tj_audit_timed_robot seed = A.seed[u];
-  const double range = A.range, res = (double)D.res, ptu = A.pt[u];
-  const int maxw = A.max_windows;
-  const double* nu = A.net + (size_t)u * 3 * D.T;
-  ClosestWin* cur = A.list + (size_t)u * 2 * TJ_CLOSEST_FRONTIER; ClosestWin* nxt = cur + TJ_CLOSEST_FRONTIER;
-  double* klo = A.klo + (size_t)u * 2 * TJ_CLOSEST_FRONTIER;
+  const double res = (double)D.res, ptu = pt[u];
+  const double* nu = net + (size_t)u * 3 * D.T;
   double* cp = tp + tid; double* cq = tq + tid; double* cd = td + tid;
+  bool terminal = false;   // every live window is
+  while (!truncated && !(best.hi - lo_u <= tol) && n > 0 && !terminal && depth < max_depth) {
+    // ---- pass 1: the children, one per lane ----
+    QBest mine{range, 0.0, INT_MAX, INT_MAX};
+    int nev = 0;
+    for (int i = tid; i < 2 * n; i += THREADS) {
+      const ClosestWin w = cur[i >> 1];
+      const int c = i & 1;
+      const double cm = 0.5 * (w.ca + w.cb);
+      if (w.term || cm == w.ca || cm == w.cb) { klo[i] = c ? INFINITY : w.lo; continue; }
+      const double ca = c ? cm : w.ca, cb = c ? w.cb : cm;
+      const bool hover = w.j >= S;
+      const double ptq = pt[w.q];
+      const double T0u = (w.tr / res) * ptu, T1u = ((w.tr + 1) / res) * ptu, lenu = T1u - T0u;
+      const double Tj = (w.j / res) * ptq, Tj1 = ((w.j + 1) / res) * ptq;
+      for (int e = 0; e < 18; e++) cp[e * THREADS] = hull_entry(D, nu, w.tr, e / 3, e % 3);
+      timed_partner_fill<THREADS>(D, net + (size_t)w.q * 3 * D.T, w.j, hover, cq);
+      const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
+      const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+      double lo, h0, h5; bool sep;
+      timed_window<THREADS, THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
+      if (!sep) lo = 0.0;
+      nev++;
+      klo[i] = lo;
+      const bool first = h0 <= h5;
+      const QBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
+      if (b.hi < range && before(b, mine)) mine = b;
+    }
+    wave_best(mine); nev = wave_sum(nev);
+    if (lane == 0) { wbest[wave] = mine; wev[wave] = nev; }
+    if (tid == 0) kept = 0;
+    __syncthreads();   // (also: every klo of the round is written)
+    QBest cand = best;
+    for (int k = 0; k < NW; k++) { if (before(wbest[k], cand)) cand = wbest[k]; windows += wev[k]; }
+    // ---- pass 2: keep what can still hold something below the round's best ----
+    double mlo = INFINITY; int allterm = 1;
+    for (int i = tid; i < 2 * n; i += THREADS) {
+      const ClosestWin w = cur[i >> 1];
+      const int c = i & 1;
+      const double cm = 0.5 * (w.ca + w.cb), lo = klo[i];
+      const bool term = w.term || cm == w.ca || cm == w.cb;
+      if ((term && c) || !(lo < cand.hi)) continue;
+      mlo = fmin(mlo, lo); allterm &= term ? 1 : 0;
+      bnb_keep(kept, nxt, maxw, term ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0});
+    }
+    mlo = wave_min(mlo);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) allterm &= __shfl_xor(allterm, off);
+    if (lane == 0) { wlo[wave] = mlo; wterm[wave] = allterm; }
+    __syncthreads();   // (also: the new list is written, `kept` is final)
+    const int m = kept;
+    for (int k = 0; k < NW; k++) { mlo = fmin(mlo, wlo[k]); allterm &= wterm[k]; }
+    __syncthreads();   // everyone has read the round's words before the next round writes them
+    if (m > maxw) { truncated = true; break; }
+    best = cand; lo_u = fmin(best.hi, mlo); n = m; terminal = m > 0 && allterm; depth++;
+    ClosestWin* t = cur; cur = nxt; nxt = t;
+  }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArgs A, tj_closest_robot* out) {
+  const int tid = threadIdx.x, u = D.u0 + blockIdx.x;
+  const tj_audit_timed_robot seed = A.seed[u];
+  ClosestWin* cur = A.list + (size_t)u * 2 * TJ_CLOSEST_FRONTIER;
 
   // the committed record: the level-0 bracket (every thread holds the same values)
   QBest best{seed.timed_hi, seed.timed_time, seed.timed_robot < 0 ? INT_MAX : seed.timed_segment, seed.timed_robot < 0 ? INT_MAX : seed.timed_robot};
   double lo_u = A.count[3 * u + 2] ? 0.0 : fmin(seed.timed_lo, seed.timed_hi);   // min(best.hi, min lo over the live seeds): tj_audit_timed's, unless a live seed counts 0
   int n = A.count[3 * u], windows = A.count[3 * u + 1], depth = 0;
-  bool truncated = n > maxw, terminal = false;   // terminal: every live window is
-  if (D.multi()) {
-    while (!truncated && !(best.hi - lo_u <= A.tol) && n > 0 && !terminal && depth < A.max_depth) {
-      // ---- pass 1: the children, one per lane ----
-      QBest mine{range, 0.0, INT_MAX, INT_MAX};
-      int nev = 0;
-      for (int i = tid; i < 2 * n; i += CL_THREADS) {
-        const ClosestWin w = cur[i >> 1];
-        const int c = i & 1;
-        const double cm = 0.5 * (w.ca + w.cb);
-        if (w.term || cm == w.ca || cm == w.cb) { klo[i] = c ? INFINITY : w.lo; continue; }
-        const double ca = c ? cm : w.ca, cb = c ? w.cb : cm;
-        const bool hover = w.j >= S;
-        const double ptq = A.pt[w.q];
-        const double T0u = (w.tr / res) * ptu, T1u = ((w.tr + 1) / res) * ptu, lenu = T1u - T0u;
-        const double Tj = (w.j / res) * ptq, Tj1 = ((w.j + 1) / res) * ptq;
-        for (int e = 0; e < 18; e++) cp[e * CL_THREADS] = hull_entry(D, nu, w.tr, e / 3, e % 3);
-        timed_partner_fill<CL_THREADS>(D, A.net + (size_t)w.q * 3 * D.T, w.j, hover, cq);
-        const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-        const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
-        double lo, h0, h5; bool sep;
-        timed_window<CL_THREADS, CL_THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
-        if (!sep) lo = 0.0;
-        nev++;
-        klo[i] = lo;
-        const bool first = h0 <= h5;
-        const QBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
-        if (b.hi < range && before(b, mine)) mine = b;
-      }
-      wave_best(mine); nev = wave_sum(nev);
-      if (lane == 0) { wbest[wave] = mine; wev[wave] = nev; }
-      if (tid == 0) kept = 0;
-      __syncthreads();   // (also: every klo of the round is written)
-      QBest cand = best;
-      for (int k = 0; k < NW; k++) { if (before(wbest[k], cand)) cand = wbest[k]; windows += wev[k]; }
-      // ---- pass 2: keep what can still hold something below the round's best ----
-      double mlo = INFINITY; int allterm = 1;
-      for (int i = tid; i < 2 * n; i += CL_THREADS) {
-        const ClosestWin w = cur[i >> 1];
-        const int c = i & 1;
-        const double cm = 0.5 * (w.ca + w.cb), lo = klo[i];
-        const bool term = w.term || cm == w.ca || cm == w.cb;
-        if ((term && c) || !(lo < cand.hi)) continue;
-        mlo = fmin(mlo, lo); allterm &= term ? 1 : 0;
-        bnb_keep(kept, nxt, maxw, term ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0});
-      }
-      mlo = wave_min(mlo);
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) allterm &= __shfl_xor(allterm, off);
-      if (lane == 0) { wlo[wave] = mlo; wterm[wave] = allterm; }
-      __syncthreads();   // (also: the new list is written, `kept` is final)
-      const int m = kept;
-      for (int k = 0; k < NW; k++) { mlo = fmin(mlo, wlo[k]); allterm &= wterm[k]; }
-      __syncthreads();   // everyone has read the round's words before the next round writes them
-      if (m > maxw) { truncated = true; break; }
-      best = cand; lo_u = fmin(best.hi, mlo); n = m; terminal = m > 0 && allterm; depth++;
-      ClosestWin* t = cur; cur = nxt; nxt = t;
-    }
-  }
+  bool truncated = n > A.max_windows;
+  if (D.multi())
+    closest_rounds<CL_THREADS>(D, A.net, A.pt, u, A.range, A.tol, A.max_depth, A.max_windows, cur, cur + TJ_CLOSEST_FRONTIER, A.klo + (size_t)u * 2 * TJ_CLOSEST_FRONTIER,
+                               best, lo_u, n, windows, depth, truncated);
   if (tid == 0) {
     tj_closest_robot r;
     const bool found = best.id != INT_MAX;

@@ -35,6 +35,7 @@
 #include "kernels_audit_timed.h"
 #include "kernels_closest.h"
 #include "kernels_obstacle_approach.h"
+#include "kernels_pair_approach.h"
 
 using namespace tj;
 
@@ -100,6 +101,10 @@ struct tj_ctx {
   AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr;
   ClosestArgs closest{}; tj_closest_robot* closest_out = nullptr;
   ObstArgs obst{}; tj_obstacle_robot* obst_out = nullptr;
+  // tj_pair_approach: the bitmask, its offsets and n are the fleet's size (allocated once, as above); what is sized by the call's cap and max_windows grows with the
+  // largest call so far (pair_cap, pair_mw) and lives in pair_allocs
+  PairArgs pair{}; tj_pair_record* pair_out = nullptr;
+  std::vector<void*> pair_allocs; int pair_cap = -1, pair_mw = 0;
 };
 
 // EVERY environment switch of the library is read through this one function (tj_group.h included): TJ_TUNE="KEY=value,KEY=value" or, equivalently, TJ_KEY=value
@@ -877,6 +882,7 @@ void tj_destroy(tj_ctx* c) {
   if (c->xch_block) (void)hipFree(c->xch_block);
   for (void* p : c->allocs) hipFree(p);
   for (void* p : c->cloud_allocs) hipFree(p);
+  for (void* p : c->pair_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1410,7 +1416,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }
 
 namespace {
-// ---- the read-only queries: one path for the four (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h) ----
+// ---- the read-only queries: one path for the five (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1549,6 +1555,63 @@ int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_wind
   if ((r = query_fetch(c, out, c->closest_out, d.U))) return r;
   return query_finish(c, nullptr);
 }
+
+// device bytes of tj_pair_approach that depend on the call (include/trajadmm.h states the formula)
+size_t pair_bytes(const Dev& d, int cap, int mw) {
+  return (size_t)cap * ((size_t)2 * mw * (sizeof(ClosestWin) + sizeof(double)) + (size_t)(2 * d.S + 2) * sizeof(PairSeed) + 4 * sizeof(int) + sizeof(tj_pair_record));
+}
+
+int pair_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_pair_record* rows, int cap, int* n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int r;
+  if ((r = query_nan(c, "tj_pair_approach", "range", range)) || (r = query_nan(c, "tj_pair_approach", "tol", tol))) return r;
+  if (max_depth > TJ_PAIR_MAX_DEPTH) { c->err = "tj_pair_approach: max_depth must be 0.." + std::to_string(TJ_PAIR_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
+  if (max_windows > TJ_PAIR_MAX_WINDOWS) { c->err = "tj_pair_approach: max_windows must be 1.." + std::to_string(TJ_PAIR_MAX_WINDOWS) + " (or <= 0 for the default)"; return TJ_ERR_INVALID; }
+  const Dev& d = c->d;
+  const int mw = max_windows <= 0 ? TJ_PAIR_FRONTIER : max_windows;
+  if (pair_bytes(d, cap, mw) > (size_t)TJ_PAIR_MAX_BYTES) {
+    c->err = "tj_pair_approach: cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw) + " need " + std::to_string(pair_bytes(d, cap, mw)) + " bytes of device memory, more than TJ_PAIR_MAX_BYTES (" +
+             std::to_string((long long)TJ_PAIR_MAX_BYTES) + "): lower cap (rows beyond it are still counted) or max_windows";
+    return TJ_ERR_INVALID;
+  }
+  if ((r = query_state(c, "tj_pair_approach", true, net_host && pt_host))) return r;
+  *n = 0;
+  if (!d.multi()) return TJ_OK;   // one UAV: no pair
+  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
+  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
+  QUIESCE(c);
+  PairArgs& b = c->pair;
+  if ((r = query_buf(c, b.mask, mask_n)) || (r = query_buf(c, b.wordoff, mask_n)) || (r = query_buf(c, b.n, 1))) return r;
+  if (cap > c->pair_cap || mw > c->pair_mw) {   // grow: the context is quiet, nothing reads the old buffers
+    for (void* p : c->pair_allocs) hipFree(p);
+    c->pair_allocs.clear();
+    b.who = nullptr; b.count = nullptr; b.seeds = nullptr; b.list = nullptr; b.klo = nullptr; c->pair_out = nullptr;
+    const int gc = std::max(cap, c->pair_cap), gm = std::max(mw, c->pair_mw);
+    c->pair_cap = -1; c->pair_mw = 0;
+    std::vector<void*>* l = &c->pair_allocs;
+    if ((r = query_buf(c, b.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.count, (size_t)gc * 2, l)) || (r = query_buf(c, b.seeds, (size_t)gc * (2 * d.S + 2), l)) ||
+        (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, c->pair_out, gc, l))) return r;
+    c->pair_cap = gc; c->pair_mw = gm;
+  }
+  PairArgs a = b;
+  if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
+  a.range = query_range(d, range); a.tol = tol < 0 ? TJ_PAIR_TOL : tol;
+  a.max_depth = max_depth < 0 ? TJ_PAIR_MAX_DEPTH : max_depth; a.max_windows = mw; a.cap = cap;
+  a.words = words; a.seed_cap = 2 * d.S + 2;
+  if ((r = query_clear(c, a.mask, mask_n)) || (r = query_clear(c, a.n, 1)) || (r = query_clear(c, a.count, (size_t)cap * 2, cap > 0))) return r;
+  if (owned > 0) {   // two launches for the count, four for the rows, whatever the fleet's size, the number of pairs and the depth
+    hipLaunchKernelGGL(k_pair_mark, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, a);
+    if (cap > 0) {
+      hipLaunchKernelGGL(k_pair_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+      hipLaunchKernelGGL(k_pair_refine, dim3(cap), dim3(PA_THREADS), 0, c->stream, d, a, c->pair_out);
+    }
+  }
+  if ((r = query_fetch(c, n, a.n, 1)) || (r = query_finish(c, nullptr))) return r;
+  if ((r = query_fetch(c, rows, c->pair_out, std::min(cap, *n))) || (r = query_finish(c, nullptr))) return r;
+  if (*n > cap && rows) { c->err = "tj_pair_approach: " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
 }  // namespace
 
 int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) { return audit_run(c, range, nullptr, out, seg_obs, seg_pair); }
@@ -1557,6 +1620,8 @@ int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* re
 int tj_audit_timed_record_size(void) { return (int)sizeof(tj_audit_timed_robot); }
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records) { return closest_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, records); }
 int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
+int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return pair_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
+int tj_pair_record_size(void) { return (int)sizeof(tj_pair_record); }
 
 // tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {

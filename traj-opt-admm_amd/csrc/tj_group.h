@@ -609,30 +609,41 @@ int tj_group_get_state(tj_group* g, int u, double* spline, double* p_slack, doub
 // run(ctx, net or null, pt or null, part) -> rc; null = the context's own state, which with one rank is current.  rows: per-segment arrays [U][S] as (what run wrote, the
 // caller's) to scatter with the owned records, or null pairs.
 struct GroupRows { const double* part; double* out; };
-template <class Rec, class Run>
-int group_query(tj_group* g, bool nets, bool pts, Rec* out, GroupRows rows0, GroupRows rows1, Run&& run) {
-  if (!g || !out) return TJ_ERR_INVALID;
+// gather and run: each(rank, ctx, net or null, pt or null) -> rc, rank after rank, every rank's device current
+template <class Each>
+int group_each(tj_group* g, bool nets, bool pts, Each&& each) {
   GROUP_LIVE(g);
   const Dev& d0 = g->ctx[0]->d;
-  const int U = d0.U, S = d0.S, T = d0.T;
+  const int U = d0.U, T = d0.T;
   const bool staged = g->n > 1;
   std::vector<double> net(nets && staged ? (size_t)U * 3 * T : 0), pt(pts && staged ? U : 0);
   for (int u = 0; u < U && (!net.empty() || !pt.empty()); u++) {
     const int rc = tj_group_get_state(g, u, net.empty() ? nullptr : &net[(size_t)u * 3 * T], nullptr, nullptr, nullptr, nullptr, pt.empty() ? nullptr : &pt[u]);
     if (rc < 0) return rc;
   }
-  std::vector<Rec> part(U);
   for (int r = 0; r < g->n; r++) {
     tj_ctx* c = g->ctx[r];
     if (hipSetDevice(g->dev[r]) != hipSuccess) return group_fail(g, TJ_ERR_DEVICE, "hipSetDevice failed");
-    const int rc = run(c, net.empty() ? nullptr : net.data(), pt.empty() ? nullptr : pt.data(), part.data());
+    const int rc = each(r, c, net.empty() ? nullptr : net.data(), pt.empty() ? nullptr : pt.data());
     if (rc < 0) return group_fail(g, rc, std::string("rank ") + std::to_string(r) + ": " + tj_last_error(c));
+  }
+  return TJ_OK;
+}
+// scatter: one record per robot (and its rows) from the rank that owns it
+template <class Rec, class Run>
+int group_query(tj_group* g, bool nets, bool pts, Rec* out, GroupRows rows0, GroupRows rows1, Run&& run) {
+  if (!g || !out) return TJ_ERR_INVALID;
+  const int U = g->ctx[0]->d.U, S = g->ctx[0]->d.S;
+  std::vector<Rec> part(U);
+  return group_each(g, nets, pts, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    const int rc = run(c, net, pt, part.data());
+    if (rc < 0) return rc;
     for (int u = c->d.u0; u < c->d.u1; u++) {
       out[u] = part[u];
       for (const GroupRows& w : {rows0, rows1}) if (w.out) std::copy(w.part + (size_t)u * S, w.part + (size_t)(u + 1) * S, w.out + (size_t)u * S);
     }
-  }
-  return TJ_OK;
+    return (int)TJ_OK;
+  });
 }
 // a scratch copy of a per-segment array the caller asked for (null: not asked for, nothing to scatter)
 static std::vector<double> group_rows(const tj_group* g, const double* wanted) { return std::vector<double>(g && wanted ? (size_t)g->ctx[0]->d.U * g->ctx[0]->d.S : 0); }
@@ -654,6 +665,25 @@ int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_r
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* out) {
   return group_query(g, true, true, out, {}, {}, [&](tj_ctx* c, const double* net, const double* pt, tj_closest_robot* part) {
     return closest_run(c, range, tol, max_depth, max_windows, net, pt, part); });
+}
+
+// the ranks' lists one after the other: ownership is by contiguous robot blocks in rank order, so that is the (robot, partner) order.  A rank whose rows do not fit
+// writes the first that do and is counted in full; the ranks behind it only count.
+int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) {
+  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int total = 0;
+  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    const int room = std::max(0, cap - total);
+    int nr = 0;
+    const int e = pair_run(c, range, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, room, &nr);
+    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
+    total += nr;
+    return (int)TJ_OK;
+  });
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_pair_approach: " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
+  return TJ_OK;
 }
 
 // from every rank's own state: nothing of another robot is read

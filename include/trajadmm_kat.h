@@ -39,6 +39,15 @@ int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double*
 /* dense LLT failure test + smallest eigenvalue (Eigen LLT / SelfAdjointEigenSolver as used at Gradient_admm.h:38-53): out[nmat][2] */
 int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out);
 
+/* ---- the launch plan (csrc/host_plan.h) ------------------------------------------------------------
+ * A flat record of ints: the device facts the plan was decided on (PlanFacts), then every decision of the plan, the LDS byte counts, the queue
+ * request and the grid sizes (plan_record; the Python package names the entries: PLAN_FACTS, PLAN_FIELDS).
+ *   c != NULL: that context's own record (p and facts are ignored): the plan as tj_create made it, plus the live Dev -- not what a self-heal latched off since.
+ *   c == NULL: the pure planner on the caller's parameters and facts[] -- needs no device, like tj_host_tables; an unsupported shape gives its
+ *              TJ_ERR_* code in the record's `err` entry and the text in msg.
+ * Returns the number of ints written, 0 for bad arguments, -needed if cap is too small. */
+int tj_kat_plan(const tj_ctx* c, const tj_params* p, const int* facts, int* out, int cap, char* msg, int msg_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,7 +201,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_linalg"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_linalg", "tj_kat_plan"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -249,6 +249,30 @@ def host_tables(piece_num, res=8):
 
 def _i(a):
     return a.ctypes.data_as(_ip)
+
+
+# the launch plan's record (tj_kat_plan, csrc/host_plan.h: plan_record): the device facts, then the plan
+PLAN_FACTS = ("num_cu", "xsolve_ok", "xsolve_regs", "xsolve_lds", "grad_ok", "grad_regs", "grad_lds", "grad_fold_ok", "grad_fold_regs", "grad_fold_lds",
+              "front_ok", "front_regs", "front_lds", "counters_on", "claim_refused", "prim", "n_obs")
+PLAN_FIELDS = ("err", "mode", "U", "P", "res", "S", "T", "N", "prim", "u0", "u1", "rank", "world", "fuse", "xf", "xf_all", "cap_obs", "cap_self", "cap_pairs", "optimal_plane",
+               "pair_rows", "cap_work", "xs", "grad_npl", "xs_band", "seq_tree", "bvh_skip", "pair_prio", "mid_order", "pair_lpw", "pair_pass_on", "spec", "seq_fold", "spec_budget",
+               "spec_min", "ls_fast", "num_cu", "c2_fold", "grad_bal", "xs_async", "keep_async", "keep_waves", "ls_help", "ls_help_late", "ls_help_mute", "fa",
+               "grad_fold", "n_solve_env", "lsc_wide", "fa_emulate", "fa_mid_ok", "fa_mid_front", "hwq_refused", "queues", "forced", "xs_two_queues", "keep_two_queues", "heal", "xs_fault",
+               "lds_grad", "lds_xs", "lds_xs2", "lds_ls", "lds_seq", "lsl_total", "lsl_plane_cap", "lsl_affine", "lsl_groups",
+               "n_rows", "n_ccd", "n_xf", "n_front", "n_solve", "n_obs_solve", "n_mid_slack")
+
+
+def plan_record(params=None, facts=None, ctx=None):
+    """(facts, plan, message) of a context (ctx: its tj_ctx pointer) or -- no GPU needed -- of the pure planner on a TjParams and a dict of PLAN_FACTS."""
+    lib = load_library(kat=True)
+    f = np.array([facts[k] for k in PLAN_FACTS] if facts else [0] * len(PLAN_FACTS), dtype=np.int32)
+    out = np.zeros(len(PLAN_FACTS) + len(PLAN_FIELDS), dtype=np.int32)
+    msg = C.create_string_buffer(512)
+    n = lib.tj_kat_plan(ctx, C.byref(params) if params is not None else None, _i(f), _i(out), C.c_int(out.size), msg, C.c_int(512))
+    if n != out.size:
+        raise TrajAdmmError(f"tj_kat_plan returned {n}, the package knows {out.size} entries")
+    v = [int(x) for x in out]
+    return dict(zip(PLAN_FACTS, v)), dict(zip(PLAN_FIELDS, v[len(PLAN_FACTS):])), msg.value.decode()
 
 
 class Solver:

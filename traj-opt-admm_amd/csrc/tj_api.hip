@@ -16,6 +16,7 @@
 #include <cstring>
 #include <strings.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/trajadmm.h"
 #include "dev_common.h"
@@ -36,6 +37,7 @@
 #include "kernels_closest.h"
 #include "kernels_obstacle_approach.h"
 #include "kernels_pair_approach.h"
+#include "host_plan.h"
 
 using namespace tj;
 
@@ -43,6 +45,12 @@ using namespace tj;
 // streams claimed by the contexts of this process whose kernels sleep across queues, per device (tj_create)
 static std::atomic<int> g_async_queues[64];
 static int hw_queue_budget() { const char* e = getenv("GPU_MAX_HW_QUEUES"); const int n = e ? atoi(e) : 4; return std::max(n, 2) - 1; }
+// the budget's one door: n > 0 claims n queues of the device (false: no room and not forced -- nothing is taken), n < 0 hands them back
+static bool queue_budget(int device, int n, bool forced = true) {
+  std::atomic<int>& g = g_async_queues[std::min(std::max(device, 0), 63)];
+  if (g.fetch_add(n) + n > hw_queue_budget() && n > 0 && !forced) { g.fetch_sub(n); return false; }
+  return true;
+}
 
 // The cross-queue schedule of one context: the asynchronous Newton solve (Dev::xs_async) and front (Dev::fa) on stream2, the asynchronous plane refinement (Dev::keep_async) on
 // stream3.  Each pairing has a host counter that must match a monotonic word on the device: xs_seq <-> Dev::xs_go (k_grad opens the gate of its k_xsolve; xs_seq_gated: the last
@@ -66,10 +74,12 @@ struct tj_ctx {
   std::vector<void*> allocs;
   std::string err;
   bool have_cloud = false, have_state = false;
-  CrossQueue xq; bool hwq_refused = false, fa_emulate = false, fa_mid_ok = false;   // (tj_create) no room in the queue budget / TJ_FRONT_ASYNC_ONE_QUEUE=1 / Dev::fa_mid: k_front's grid is resident next to one k_linesearch block
+  CrossQueue xq;
+  HostPlan hp; PlanFacts facts{};   // the host half of the launch plan (host_plan.h; Dev holds the rest) and the device facts it was decided on.  The plan AS MADE by tj_create: the live
+                                    // queue state is xq's (xs_two_queues, keep_two_queues, xs_fault start as planned; heal_check clears them there only)
   // Self-healing (heal_check): a wait between the queues that runs out (ERR_XS_TIMEOUT -- in practice a GPU shared with another process) must not fail a run.  snap_iters:
   // iterations enqueued since the first tj_iterate_async after a host look took the checkpoint.  TJ_HEAL=0: off (the bit is reported as TJ_ERR_NO_PROGRESS, as in round 5).
-  bool heal = false, heal_busy = false; long long snap_iters = 0; int async_fallbacks = 0; Checkpoint ck;
+  bool heal_busy = false; long long snap_iters = 0; int async_fallbacks = 0; Checkpoint ck;
   bool hull_valid = false;   // Dev::fuse: the hull cache matches the control points (else k_hullinfo runs before the next iteration)
   bool ccd_valid = false;    // Dev::fuse: the swept-hull cache of the owned robots matches their direction records (k_xsolve's tail wrote it; tj_set_direction / tj_set_state clear it)
   long long launches = 0;    // kernels enqueued by the iteration schedules so far (tj_launch_count)
@@ -80,12 +90,7 @@ struct tj_ctx {
   XchPeers* xch_table = nullptr;
   bool xf_used[2] = {false, false};   // the cache units of k_front [0] / k_ccd [1] have counted themselves done since the last begin: a repeat of that launch before the next begin first zeroes the counters
   bool xch_wait_kernel = false;   // direct exchange, wait mode 0: a one-wave k_xch_wait launch in front of k_front / k_ccd
-  size_t lds_grad = 0, lds_xs = 0, lds_xs2 = 0, lds_ls = 0, lds_seq = 0;
-  bool lsc_wide = false;     // coupled mode: k_ls_coupled evaluates all LSC_ROUNDS rounds in one launch (kernels_ls.h)
   int lsc_base = 0;          // coupled mode, sharded context that follows the Armijo search (Dev::lsc_follow): first round of the table the next phases 4 / 5 evaluate and decide (0 at every iteration's start)
-  bool grad_fold = true;       // k_grad compacts its own segments (one launch less); TJ_GRAD_FOLD=0 keeps k_sep_self_compact + the 192-thread k_grad
-  int n_solve_env = 0;         // TJ_N_SOLVE: pair-solve waves of k_mid (launch-shape switch)
-  LsLayout lsl;
   // cloud-dependent allocations (rebuilt by tj_set_cloud)
   std::vector<void*> cloud_allocs;
   std::vector<int> cloud_order;   // sorted position -> index in the caller's cloud (ids of tj_get/set_obs_cache)
@@ -136,15 +141,16 @@ namespace {
     }                                                                                            \
   } while (0)
 
-template <class T>
-int dalloc(tj_ctx* c, T** p, size_t n, std::vector<void*>* list = nullptr) {
+int dalloc_bytes(tj_ctx* c, void** p, size_t bytes, std::vector<void*>* list = nullptr) {
   void* q = nullptr;
-  HIPCHK(c, hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  HIPCHK(c, hipMemsetAsync(q, 0, std::max<size_t>(n, 1) * sizeof(T), c->stream));  // ordered on the solver's stream like every kernel and copy that follows
+  HIPCHK(c, hipMalloc(&q, bytes));
+  HIPCHK(c, hipMemsetAsync(q, 0, bytes, c->stream));  // ordered on the solver's stream like every kernel and copy that follows
   (list ? *list : c->allocs).push_back(q);
-  *p = (T*)q;
+  *p = q;
   return TJ_OK;
 }
+template <class T>
+int dalloc(tj_ctx* c, T** p, size_t n, std::vector<void*>* list = nullptr) { return dalloc_bytes(c, (void**)p, std::max<size_t>(n, 1) * sizeof(T), list); }
 
 int upload(tj_ctx* c, const void* dst, const void* src, size_t bytes) {
   if (bytes == 0) return TJ_OK;
@@ -162,6 +168,16 @@ int query_buf(tj_ctx* c, T*& p, size_t n, std::vector<void*>* list = nullptr) { 
 // the kernels templated on the primitive kind, each launch written once: f(std::integral_constant<int, PRIM>)
 template <class F>
 void with_prim(const Dev& d, F&& f) { if (d.prim == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 1>{}); }
+// k_xsolve's register factorisation is inlined per size of the reduced system, 9P - 2 rows (kernels_newton.h); 61 rows -- the inlined form would spill -- and the
+// LDS forms: the generic kernel, which calls it out of line.  f(std::integral_constant<int, N>): the launch, the attribute query and the LDS attribute all choose here
+template <class F>
+void with_xsolve(int P, F&& f) {
+  switch (9 * P - 2) {
+    case 16: f(std::integral_constant<int, 16>{}); break; case 25: f(std::integral_constant<int, 25>{}); break; case 34: f(std::integral_constant<int, 34>{}); break;
+    case 43: f(std::integral_constant<int, 43>{}); break; case 52: f(std::integral_constant<int, 52>{}); break; default: f(std::integral_constant<int, 0>{}); break;
+  }
+}
+void release_queues(tj_ctx* c) { if (c->xq.hwq_claim) { queue_budget(c->prm.device, -c->xq.hwq_claim); c->xq.hwq_claim = 0; } }
 // the records of a query: zeroed before its launches (robots of other ranks stay zero), copied out after them; rows [U][S] likewise where the caller asked for them
 template <class T>
 int query_clear(tj_ctx* c, T* dev, size_t n, bool wanted = true) {
@@ -207,21 +223,11 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
   const bool fa2q = sched == Sched::Chain && d_.fa && c->xq.xs_two_queues && !c->xq.xs_same_queue_now;
   const Dev& d = d_;
   const int owned = d.u1 - d.u0;
-  const bool multi = d.mode >= 1, coupled = d.mode == 2, tri = d.prim == 3;
-  // Waves striding over the two device-built work lists.  k_mid holds ~1 wave per SIMD (VGPR bound), i.e. 1024 resident
-  // waves: a larger grid adds no parallelism, only dispatch time for blocks that find no work (measured: with
-  // 4096 + 1024 blocks the last ones started 50 us into a 60 us kernel).
-  // Large fleets (one pair per lane, long solves passed on to idle waves -- sep_self_solve_body): half as many waves again, they
-  // are the consumers of the passed-on pairs (SCN-D: k_mid 62 us with 1024, 58 with 1536, 62 with 2048).
-  // Small fleets (a wave per pair, two or three pairs per wave): 1 728 = what is left of k_mid's 2 048 resident waves beside SCN-C's
-  // 320 slack blocks (1 024: k_mid 31.5 us, 1 536: 28.2, 1 728: 27.6, 2 048: 27.6 before the static assignment; alike after it).
-  const int n_solve = (multi && !d.optimal_plane) ? std::min(d.cap_work, c->n_solve_env > 0 ? c->n_solve_env : (d.U >= 192 ? 1536 : 1728)) : 0;  // "optimal_plane":1 -- k_keep finds and refines the pair planes
-  const int n_obs_solve = d.N > 0 ? 1024 : 0;   // (512: SCN-E's k_mid 43.7 us, 1024: 38.3, 2048: 37.8; SCN-C indifferent)
-  const int n_rows = multi ? d.S * pair_units(d.U, d.pair_rows) : 0;   // one wave per (segment, tile of pair_rows lower robots x 64 partners)
-  const int n_xf = d.xf_units();   // sharded contexts: one wave per (foreign robot, segment) at the head of k_front / k_ccd (kernels_step.h); coupled chain: per (robot, segment)
-  const int n_ccd = owned * d.S + n_rows, n_front = n_ccd + n_xf + (d.spec ? SPEC_CAP : 0) + (d.grad_bal ? (owned * d.P + 63) / 64 : 0);
+  const bool multi = d.mode >= 1, coupled = d.mode == 2;
+  const Grids g = plan_grids(d, c->hp.n_solve_env);   // (of d as this launch sees it: the per-launch flags above count)
+  const int n_solve = g.n_solve, n_obs_solve = g.n_obs_solve, n_rows = g.n_rows, n_xf = g.n_xf, n_ccd = g.n_ccd, n_front = g.n_front;
   const bool chained = sched != Sched::Stage;          // an iteration chain (one context, or the phases of a sharded schedule) as opposed to the stage API
-  const int n_mid_slack = owned * d.P;
+  const int n_mid = g.n_mid_slack + n_solve + n_obs_solve;
   d_.fa_nfront = n_front; d_.fa_nls = coupled ? owned * LSC_ROUNDS : owned * d.ls_help;
   switch (kid) {
     case K_BEGIN: if (chain_pos & 1) return false;
@@ -235,13 +241,13 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       if (keep2q) d_.keep_seq = ++c->xq.keep_seq;   // this k_front opens the gate of the iteration's plane refinement (third queue)
       if (c->xq.fa_armed && fa2q && (chain_pos & 1)) {   // asynchronous front: on the second queue, next to the k_linesearch just enqueued (pairing fa_seq), behind the residency gate
         c->xq.fa_armed = false;
-        d_.fa_seq = c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->xq.fa_mid_now = c->fa_mid_ok;
+        d_.fa_seq = c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->hp.fa_mid_ok ? 1 : 0; c->xq.fa_mid_now = c->hp.fa_mid_ok;
         TJ_LAUNCH(k_fa_gate, dim3(1), dim3(64), 0, c->xq.stream2, d, (int)((unsigned)c->xq.fa_seq * (unsigned)d.fa_nls));
-        if (tri) TJ_LAUNCH((k_front<3, true>), dim3(n_front), dim3(64), 0, c->xq.stream2, d); else TJ_LAUNCH((k_front<1, true>), dim3(n_front), dim3(64), 0, c->xq.stream2, d);
+        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_front<decltype(prim)::value, true>), dim3(n_front), dim3(64), 0, c->xq.stream2, d); });
         return true;
       }
       d_.fa_units = (sched == Sched::Chain && c->xq.hull_from_units) ? 1 : 0;   // (the k_linesearch before it published no hull cache: one-queue emulation of the asynchronous front)
-      if (tri) TJ_LAUNCH((k_front<3>), dim3(n_front), dim3(64), 0, s, d); else TJ_LAUNCH((k_front<1>), dim3(n_front), dim3(64), 0, s, d);
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_front<decltype(prim)::value>), dim3(n_front), dim3(64), 0, s, d); });
       if (keep2q) {
         d_.keep_seq = 0;
         TJ_LAUNCH(k_keep_gate, dim3(1), dim3(64), 0, c->xq.stream3, d, c->xq.keep_seq);
@@ -249,30 +255,30 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       }
       return true;
     case K_SEP_OBS: if (chained) return false;  // stage API only
-      if (tri) TJ_LAUNCH((k_obs_query<3>), dim3(owned * d.S), dim3(64), 0, s, d); else TJ_LAUNCH((k_obs_query<1>), dim3(owned * d.S), dim3(64), 0, s, d);
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_obs_query<decltype(prim)::value>), dim3(owned * d.S), dim3(64), 0, s, d); });
       return true;
     case K_OBS_SOLVE: if (sched == Sched::Chain || !n_obs_solve) return false;
-      if (tri) TJ_LAUNCH((k_obs_solve<3>), dim3(n_obs_solve), dim3(64), 0, s, d); else TJ_LAUNCH((k_obs_solve<1>), dim3(n_obs_solve), dim3(64), 0, s, d);
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_obs_solve<decltype(prim)::value>), dim3(n_obs_solve), dim3(64), 0, s, d); });
       return true;
     case K_SEP_SELF_ROWS: if (chained || !multi) return false; TJ_LAUNCH(k_sep_self_rows, dim3(n_rows), dim3(64), 0, s, d); return true;
     case K_MID: if (!chained) return false;
       if (sched == Sched::Chain && c->xq.fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
         c->xq.fa_mid_now = false;
         d_.fa_seq = c->xq.fa_seq; d_.fa_mid = 1;
-        if (tri) TJ_LAUNCH((k_mid<3, true>), dim3(1 + n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve); else TJ_LAUNCH((k_mid<1, true>), dim3(1 + n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve);
+        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value, true>), dim3(1 + n_mid), dim3(64), 0, s, d, n_solve, n_obs_solve); });
         return true;
       }
-      if (tri) TJ_LAUNCH((k_mid<3>), dim3(n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve); else TJ_LAUNCH((k_mid<1>), dim3(n_mid_slack + n_solve + n_obs_solve), dim3(64), 0, s, d, n_solve, n_obs_solve);
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value>), dim3(n_mid), dim3(64), 0, s, d, n_solve, n_obs_solve); });
       return true;
     case K_SEP_SELF_SOLVE: if (sched == Sched::Chain || !n_solve) return false; TJ_LAUNCH(k_sep_self_solve, dim3(n_solve), dim3(64), 0, s, d); return true;
     case K_KEEP:  // "optimal_plane":1 only; single UAV: a wave per segment, multi UAV: lanes over the switched-on pair slots
       if (!d.optimal_plane || (multi ? false : d.N == 0)) return false;
       TJ_LAUNCH(k_keep, dim3(multi ? 1024 : owned * d.S), dim3(64), 0, s, d, keep2q ? 1 : 0); return true;   // (asynchronous refinement: the new pairs only)
-    case K_SEP_SELF_COMPACT: if (chained && c->grad_fold) return false;   // iteration chains (single GPU and sharded phases): folded into k_grad
+    case K_SEP_SELF_COMPACT: if (chained && c->hp.grad_fold) return false;   // iteration chains (single GPU and sharded phases): folded into k_grad
       TJ_LAUNCH(k_sep_self_compact, dim3(owned * d.S), dim3(64), 0, s, d); return true;
     case K_GRAD:
-      if (chained && c->grad_fold) TJ_LAUNCH((k_grad<true>), dim3(owned * d.P), dim3(GRAD_FOLD_THREADS), c->lds_grad + grad_fold_extra_doubles(d.res) * sizeof(double), s, d);
-      else TJ_LAUNCH((k_grad<false>), dim3(owned * d.P), dim3(GRAD_THREADS), c->lds_grad, s, d);
+      if (chained && c->hp.grad_fold) TJ_LAUNCH((k_grad<true>), dim3(owned * d.P), dim3(GRAD_FOLD_THREADS), c->hp.lds_grad_of(true, d.res), s, d);
+      else TJ_LAUNCH((k_grad<false>), dim3(owned * d.P), dim3(GRAD_THREADS), c->hp.lds_grad, s, d);
       return true;
     case K_XSOLVE: {
       Dev dx = d;
@@ -283,21 +289,14 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
         s = c->xq.stream2;
         TJ_LAUNCH(k_xs_gate, dim3(1), dim3(64), 0, s, d, c->xq.xs_seq, (c->xq.xs_fault > 0 && c->xq.xs_seq == c->xq.xs_fault) ? 1 : 0);
       }
-      if (d.xs_band) TJ_LAUNCH(k_xsolve_band, dim3(owned), dim3(XB_THREADS), c->lds_xs, s, d);
-      else switch (9 * d.P - 2) {   // the register factorisation is inlined per size (kernels_newton.h); 61 rows and the LDS forms: the generic kernel
-        case 16: TJ_LAUNCH((k_xsolve<16>), dim3(owned), dim3(XS_LOAD_THREADS), c->lds_xs, s, d); break;
-        case 25: TJ_LAUNCH((k_xsolve<25>), dim3(owned), dim3(XS_LOAD_THREADS), c->lds_xs, s, d); break;
-        case 34: TJ_LAUNCH((k_xsolve<34>), dim3(owned), dim3(XS_LOAD_THREADS), c->lds_xs, s, d); break;
-        case 43: TJ_LAUNCH((k_xsolve<43>), dim3(owned), dim3(XS_LOAD_THREADS), c->lds_xs, s, d); break;
-        case 52: TJ_LAUNCH((k_xsolve<52>), dim3(owned), dim3(XS_LOAD_THREADS), c->lds_xs, s, d); break;
-        default: TJ_LAUNCH((k_xsolve<0>), dim3(owned), dim3(XS_LOAD_THREADS), c->lds_xs, s, d); break;
-      }
+      if (d.xs_band) TJ_LAUNCH(k_xsolve_band, dim3(owned), dim3(XB_THREADS), c->hp.lds_xs, s, d);
+      else with_xsolve(d.P, [&](auto n) { TJ_LAUNCH((k_xsolve<decltype(n)::value>), dim3(owned), dim3(XS_LOAD_THREADS), c->hp.lds_xs, s, d); });
       if (chained && d.fuse && !d.xs_band) c->ccd_valid = true;   // its tail has left the owned robots' swept-hull cache
       return true;
     }
     case K_XSOLVE_C2:
       if (coupled && chained && d.c2_fold) return false;   // k_xsolve has finished the arrowhead solve itself
-      if (coupled) { if (d.xs_band) TJ_LAUNCH(k_xsolve_c2_band, dim3(owned), dim3(XS_THREADS), c->lds_xs2, s, d); else TJ_LAUNCH(k_xsolve_c2, dim3(owned), dim3(XS_THREADS), c->lds_xs2, s, d); }
+      if (coupled) { if (d.xs_band) TJ_LAUNCH(k_xsolve_c2_band, dim3(owned), dim3(XS_THREADS), c->hp.lds_xs2, s, d); else TJ_LAUNCH(k_xsolve_c2, dim3(owned), dim3(XS_THREADS), c->hp.lds_xs2, s, d); }
       return coupled;
     case K_CCD_PREP: if (chained && d.xf_all) return false;                                // coupled chain: k_ccd's units build every robot's record
       if (chained && d.fuse && !d.xs_band && c->ccd_valid) return false;  // fused chains: k_xsolve's tail leaves the swept-hull cache
@@ -308,34 +307,34 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       if (d.xf) { if (c->xf_used[1]) (void)hipMemsetAsync(d.xf_seg + (size_t)d.S * XF_SEG_STRIDE, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[1] = true; }
       if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 1);   // ranks sharing a device: the wait for the peers' direction records is a launch of its own
       {
-        const int g = n_ccd + n_xf + (d.seq_fold ? 1 : 0);   // + the finisher of the folded pair replay (kernels_step.h)
-        if (tri) TJ_LAUNCH((k_ccd_lean<3>), dim3(g), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd_lean<1>), dim3(g), dim3(64), 0, s, d);
+        const int n = n_ccd + n_xf + (d.seq_fold ? 1 : 0);   // + the finisher of the folded pair replay (kernels_step.h)
+        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_lean<decltype(prim)::value>), dim3(n), dim3(64), 0, s, d); });
       }
       return true;
     case K_CCD_OBS: if (sched == Sched::Chain) return false;
-      if (tri) TJ_LAUNCH((k_ccd_obs<3>), dim3(owned * d.S), dim3(64), 0, s, d); else TJ_LAUNCH((k_ccd_obs<1>), dim3(owned * d.S), dim3(64), 0, s, d);
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_obs<decltype(prim)::value>), dim3(owned * d.S), dim3(64), 0, s, d); });
       return true;
     case K_CCD_SELF_PAIRS: if (sched == Sched::Chain || !multi) return false; TJ_LAUNCH(k_ccd_self_pairs, dim3(n_rows), dim3(64), 0, s, d); return true;
     case K_CCD_SELF_SEQ:
       if (chained && d.seq_fold) return false;   // the last block of k_ccd has done it
       if (!multi && sched == Sched::Chain) return false;   // single UAV: no pairs to replay, and k_xsolve has left gnorm = |g| itself -- one launch less in the chain
-      TJ_LAUNCH(k_ccd_self_seq, dim3(1), dim3(64), c->lds_seq, s, d); return true;
+      TJ_LAUNCH(k_ccd_self_seq, dim3(1), dim3(64), c->hp.lds_seq, s, d); return true;
     case K_LINESEARCH: if (!coupled) { c->xq.hull_from_units = false;
-      if (fa2q && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; c->xq.hull_from_units = true; }
-      else if (sched == Sched::Chain && d_.fa && c->fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->xq.hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
-      TJ_LAUNCH(k_linesearch, dim3(owned * d.ls_help), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, (chain_pos & 2) ? 1 : 0); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // (its last block runs begin_body)
+      if (fa2q && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->hp.fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; c->xq.hull_from_units = true; }
+      else if (sched == Sched::Chain && d_.fa && c->hp.fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->xq.hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
+      TJ_LAUNCH(k_linesearch, dim3(owned * d.ls_help), dim3(LS_THREADS), c->hp.lds_ls, s, d, c->hp.lsl, (chain_pos & 2) ? 1 : 0); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // (its last block runs begin_body)
       return !coupled;
     // coupled mode ("decouple":0): evaluation rounds of the summed-energy Armijo search, commit
     case K_LS_COUPLED:
       if (coupled) {
         const int base = (owned != d.U && d.lsc_follow) ? c->lsc_base : 0;   // (a followed search of a sharded context: the rounds beyond the first table)
         c->xq.hull_from_units = false;
-        if (fa2q && c->lsc_wide && owned == d.U && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; }   // asynchronous front: the next k_front runs next to this launch
-        if (c->lsc_wide) { TJ_LAUNCH(k_ls_coupled, dim3(owned * LSC_ROUNDS), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, 0, LSC_ROUNDS, (chain_pos & 2) ? 1 : 0, base); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // all rounds at once, one block per (robot, round)
-        else for (int r = 0; r < LSC_ROUNDS; r++) TJ_LAUNCH(k_ls_coupled, dim3(owned), dim3(LS_THREADS), c->lds_ls, s, d, c->lsl, r, 1, 0, base);
+        if (fa2q && c->hp.lsc_wide && owned == d.U && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->hp.fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; }   // asynchronous front: the next k_front runs next to this launch
+        if (c->hp.lsc_wide) { TJ_LAUNCH(k_ls_coupled, dim3(owned * LSC_ROUNDS), dim3(LS_THREADS), c->hp.lds_ls, s, d, c->hp.lsl, 0, LSC_ROUNDS, (chain_pos & 2) ? 1 : 0, base); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // all rounds at once, one block per (robot, round)
+        else for (int r = 0; r < LSC_ROUNDS; r++) TJ_LAUNCH(k_ls_coupled, dim3(owned), dim3(LS_THREADS), c->hp.lds_ls, s, d, c->hp.lsl, r, 1, 0, base);
       }
       return coupled;
-    case K_LS_COMMIT: if (coupled && !(c->lsc_wide && owned == d.U)) TJ_LAUNCH(k_ls_commit, dim3(owned), dim3(64), 0, s, d, (owned != d.U && d.lsc_follow) ? c->lsc_base : 0); return coupled;   // (one context, all rounds in one launch: its last block commits)
+    case K_LS_COMMIT: if (coupled && !(c->hp.lsc_wide && owned == d.U)) TJ_LAUNCH(k_ls_commit, dim3(owned), dim3(64), 0, s, d, (owned != d.U && d.lsc_follow) ? c->lsc_base : 0); return coupled;   // (one context, all rounds in one launch: its last block commits)
     case K_SLACK: if (sched == Sched::Chain) return false; TJ_LAUNCH(k_slack, dim3(owned * d.P), dim3(64), 0, s, d, 0); return true;
   }
   return false;
@@ -444,7 +443,7 @@ int heal_check(tj_ctx* c, int err_known) {
   if (!(err & ERR_XS_TIMEOUT)) { checkpoint_drop(c); return TJ_OK; }
   struct Busy { tj_ctx* c; ~Busy() { c->heal_busy = false; } } busy{c}; c->heal_busy = true;   // (reset on every exit)
   c->async_fallbacks++;
-  if (c->xq.hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->xq.hwq_claim); c->xq.hwq_claim = 0; }   // (the budget is free for another context)
+  release_queues(c);   // (the budget is free for another context)
   c->xq.xs_two_queues = c->xq.keep_two_queues = false; c->xq.xs_fault = 0;   // (the tickets / flags of the asynchronous solve work on one queue as well: TJ_XS_ONE_QUEUE's schedule)
   int r = restart_pairings(c, false);
   if (r || (r = checkpoint_restore(c))) return r;
@@ -569,312 +568,190 @@ int tj_host_tables(int piece_num, int res, double* convert, double* mdyn, double
 
 const char* tj_last_error(const tj_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
+}  // extern "C"
+
+// ---- tj_create's steps ----
+namespace {
+
+const void* xsolve_fn(int P) { const void* f = nullptr; with_xsolve(P, [&](auto n) { f = (const void*)k_xsolve<decltype(n)::value>; }); return f; }
+
+KernelFact kernel_fact(const void* f) {
+  hipFuncAttributes a;
+  if (hipFuncGetAttributes(&a, f) != hipSuccess) { (void)hipGetLastError(); return KernelFact{0, 0, 0}; }
+  return KernelFact{1, a.numRegs, (int)a.sharedSizeBytes};
+}
+
+// what the planner is told about the device (host_plan.h: PlanFacts) -- every runtime query the plan depends on is made here
+int gather_facts(tj_ctx* c, PlanFacts& f) {
+  hipDeviceProp_t prop;
+  HIPCHK(c, hipGetDeviceProperties(&prop, c->prm.device));
+  f = PlanFacts{};
+  f.num_cu = prop.multiProcessorCount;
+  f.xsolve = kernel_fact(xsolve_fn(c->prm.piece_num));
+  f.grad[0] = kernel_fact((const void*)k_grad<false>); f.grad[1] = kernel_fact((const void*)k_grad<true>);
+  f.front = kernel_fact((const void*)k_front<1, true>);
+  const KernelFact f3 = kernel_fact((const void*)k_front<3, true>);
+  if (f.front.ok && f3.ok) { f.front.regs = std::max(f.front.regs, f3.regs); f.front.lds = std::max(f.front.lds, f3.lds); }
+  const char* cc = getenv("ROCPROF_COUNTER_COLLECTION");
+  f.counters_on = (cc && cc[0] && strcmp(cc, "0") != 0 && strcasecmp(cc, "false") != 0) ? 1 : 0;
+  f.prim = 1;
+  return TJ_OK;
+}
+
+// the dynamic LDS every kernel of the plan may ask for
+int set_lds_attributes(tj_ctx* c) {
+  const Dev& d = c->d; const HostPlan& h = c->hp;
+  auto set = [&](const void* f, size_t bytes) -> int { HIPCHK(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); return TJ_OK; };
+  int r;
+  if ((r = set((const void*)k_grad<true>, h.lds_grad_of(true, d.res))) || (r = set((const void*)k_grad<false>, h.lds_grad)) ||
+      (r = set(d.xs_band ? (const void*)k_xsolve_band : xsolve_fn(d.P), h.lds_xs)) ||
+      (r = set((const void*)k_linesearch, h.lds_ls)) || (r = set((const void*)k_ls_coupled, h.lds_ls)) ||
+      (r = set(d.xs_band ? (const void*)k_xsolve_c2_band : (const void*)k_xsolve_c2, h.lds_xs2)) || (r = set((const void*)k_ccd_self_seq, h.lds_seq))) return r;
+  return TJ_OK;
+}
+
+// k_xsolve's overlap-add as a table: per entry of the reduced system the (at most two) piece-block entries that cover it, in piece order; -2: the time-time entry (every piece)
+const char* build_xs_gather(int Pn, std::vector<int>& gt) {
+  const int m = 9 * Pn - 3, n = m + 1;
+  gt.assign((size_t)2 * n * n + 2 * n, -1);
+  auto cover = [&](int g, int& lo, int& hi) { if (g >= 0) { lo = std::max(lo, (g - 17 + 8) / 9); hi = std::min(hi, g / 9); } };
+  for (int idx = 0; idx < n * n; idx++) {
+    const int ra = idx / n, rb = idx % n, ga = ra == m ? -1 : ra + 6, gb = rb == m ? -1 : rb + 6;
+    if (ga < 0 && gb < 0) { gt[2 * (size_t)idx] = -2; continue; }
+    int lo = 0, hi = Pn - 1, k = 0;
+    cover(ga, lo, hi); cover(gb, lo, hi);
+    for (int sp = std::max(lo, 0); sp <= hi; sp++) {
+      const int a = ga < 0 ? 18 : ga - 9 * sp, b = gb < 0 ? 18 : gb - 9 * sp;
+      if (k < 2) gt[2 * (size_t)idx + k] = sp * 361 + a * 19 + b;
+      k++;
+    }
+    if (k > 2) return "internal: an entry of the reduced system is covered by more than two piece blocks";
+  }
+  for (int ra = 0; ra < n; ra++) {
+    const int ga = ra == m ? -1 : ra + 6;
+    if (ga < 0) { gt[(size_t)2 * n * n + 2 * ra] = -2; continue; }
+    int lo = 0, hi = Pn - 1, k = 0;
+    cover(ga, lo, hi);
+    for (int sp = std::max(lo, 0); sp <= hi; sp++) { if (k < 2) gt[(size_t)2 * n * n + 2 * ra + k] = sp * 19 + (ga - 9 * sp); k++; }
+    if (k > 2) return "internal: a row of the reduced system is covered by more than two piece blocks";
+  }
+  return nullptr;
+}
+
+// the constant tables of the kernels: built on the host, uploaded once
+int upload_tables(tj_ctx* c) {
+  Dev& d = c->d;
+  HostTables t;
+  build_tables(d.P, d.res, STEP_CAP, t);
+  std::vector<int> gt;
+  if (const char* bad = build_xs_gather(d.P, gt)) { c->err = bad; return TJ_ERR_INVALID; }
+  auto put = [&](auto*& dst, const auto* src, size_t n) {
+    std::remove_const_t<std::remove_reference_t<decltype(*dst)>>* q = nullptr;
+    int r = dalloc(c, &q, n);
+    if (!r) r = upload(c, q, src, n * sizeof(*q));
+    dst = q;
+    return r;
+  };
+  int r;
+  if ((r = put(d.basis, t.basis.data(), t.basis.size())) || (r = put(d.convert, t.convert.data(), t.convert.size())) || (r = put(d.mdyn, t.mdyn, 36)) ||
+      (r = put(d.kdop, t.kdop, 147)) || (r = put(d.pow08, t.pow08.data(), t.pow08.size())) || (r = put(d.xs_gather, gt.data(), gt.size()))) return r;
+  return TJ_OK;
+}
+
+// One device array of a context: where its pointer lives, its element count and size, and whether it is part of the checkpoint.  tj_create allocates from this
+// list and builds the checkpoint's region table from it, so no size is written twice.
+struct ArrayDecl { void** slot; size_t n, elem; bool snap; };
+template <class T>
+ArrayDecl arr(T*& p, size_t n, bool snap = false) { return ArrayDecl{(void**)&p, n, sizeof(T), snap}; }
+constexpr bool SNAP = true;   // self-healing: what a batch's first state consists of (everything an iteration reads that an earlier iteration wrote and that is not rebuilt or re-stamped anyway)
+
+std::vector<ArrayDecl> device_arrays(Dev& d) {
+  const size_t U = d.U, S = d.S, P = d.P, T = d.T, owned = d.u1 - d.u0, n = 9 * P - 2, co = d.cap_obs, cs = d.cap_self;
+  const bool multi = d.mode >= 1;
+  std::vector<ArrayDecl> a = {
+    arr(d.spline, U * 3 * T, SNAP), arr(d.p_slack, U * 18 * P, SNAP), arr(d.p_lambda, U * 18 * P, SNAP), arr(d.t_slack, U * P, SNAP), arr(d.t_lambda, U * P, SNAP), arr(d.piece_time, U, SNAP),
+    arr(d.oplanes, U * S * co * 4), arr(d.ocount, U * S), arr(d.splanes, U * S * cs * 4), arr(d.scount, U * S),
+    arr(d.lg, U * P * 19), arr(d.lh, U * P * 361), arr(d.xdir, U * d.xs, SNAP),
+    arr(d.k_obs, U), arr(d.k_self, U), arr(d.step_out, U, SNAP), arr(d.ls_hist, U, SNAP), arr(d.grad_cost, owned * P), arr(d.grad_perm, owned * P), arr(d.ls_tab, U * LS_TAB_STRIDE), arr(d.ls_word, U),
+    arr(d.ccdinfo, U * S * CCD_STRIDE), arr(d.pair_list, ACT_CAP),
+    arr(d.seg_stats, U * S * 6, SNAP), arr(d.pair_stats, U * S * 2, SNAP), arr(d.blk_stats, U * P + U, SNAP),
+    arr(d.hullinfo, U * S * HULL_STRIDE), arr(d.hbox, S * 6 * U), arr(d.cbox, S * 6 * U), arr(d.pairplane, multi ? S * U * U * 4 : 1),
+    arr(d.pairstamp, multi ? S * U * U : 1), arr(d.pairbits, multi ? S * U * ((U + 63) / 64) : 1),
+    arr(d.pair_work, 3 * (size_t)d.cap_work), arr(d.pair_work_n, S + 1), arr(d.pair_ovf, 4), arr(d.seq_gmem_d, seq_fold_gmem_doubles(d.U)), arr(d.seq_gmem_i, seq_fold_gmem_ints(d.U)),
+    arr(d.spec_n, 2), arr(d.spec_list, 2 * SPEC_CAP), arr(d.spec_tag, SPEC_CAP), arr(d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES), arr(d.spec_sti, SPEC_CAP * SPEC_STATE_INTS),
+    arr(d.pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX), arr(d.ctl, 1),
+    arr(d.ocand, U * S * co), arr(d.ocand_n, U * S), arr(d.ohull, U * S * 18),
+    arr(d.obs_work, 2 * U * S * co), arr(d.obs_work_n, 1), arr(d.oraw, U * S * co * 4), arr(d.ostamp, U * S * co),
+    arr(d.grad_scr, owned * P * 16 * (co + cs)), arr(d.xs_scr, d.xs_band ? owned * (n * n + 4 * n) : 1),
+    arr(d.xf_seg, 2 * S * XF_SEG_STRIDE), arr(d.xs_sync, Dev::xs_sync_ints(d.U)), arr(d.keep_sync, Dev::keep_sync_ints()), arr(d.fa_sync, Dev::fa_sync_ints(d.U))};
+#ifdef TJ_PHASE_TIMING
+  a.push_back(arr(d.dbg, (size_t)K_COUNT * TJ_TIC_BLOCKS * TJ_TIC_SLOTS));
+#endif
+  if (d.optimal_plane) {   // the planes that persist across iterations: obstacle lists (single UAV) or the dense pair table
+    const bool m0 = d.mode == 0;
+    a.insert(a.end(), {arr(d.kobs_id, m0 ? U * S * co : 1, m0), arr(d.kobs_n, U * S, m0), arr(d.kobs_cd, m0 ? U * S * co * 4 : 1, m0),
+                       arr(d.kpair_on, m0 ? 1 : S * U * U, !m0), arr(d.kpair_list, m0 ? 1 : S * U * U, !m0), arr(d.kpair_n, 2, !m0), arr(d.kpair_cd, m0 ? 1 : S * U * U * 4, !m0)});
+  }
+  if (d.mode == TJ_MODE_MULTI_COUPLED)
+    a.insert(a.end(), {arr(d.xL, U * (d.xs_band ? (n - 1) * BAND_BS + n : n * n)), arr(d.xy, U * n), arr(d.xg, U * n), arr(d.xcorner, U * 4), arr(d.k_obs_f, U), arr(d.ls_e, (size_t)LSC_ROUNDS * U * LS_GROUPS)});
+  return a;
+}
+
+// allocate the arrays and, for those of the checkpoint, an arena each and the region table k_snapshot walks
+int allocate_arrays(tj_ctx* c) {
+  const std::vector<ArrayDecl> arrays = device_arrays(c->d);
+  int r;
+  for (const ArrayDecl& a : arrays) if ((r = dalloc_bytes(c, a.slot, std::max<size_t>(a.n, 1) * a.elem))) return r;
+  std::vector<SnapRegion> tab;
+  for (const ArrayDecl& a : arrays) {
+    if (!a.snap) continue;
+    char* snap = nullptr;
+    if ((r = dalloc(c, &snap, (a.n * a.elem + 15) / 16 * 16))) return r;
+    tab.push_back(SnapRegion{(char*)*a.slot, snap, (unsigned long long)(a.n * a.elem)});
+  }
+  c->ck.n = (int)tab.size();
+  if ((r = dalloc(c, &c->ck.tab, tab.size())) || (r = dalloc(c, &c->ck.ctl, 1)) || (r = upload(c, c->ck.tab, tab.data(), tab.size() * sizeof(SnapRegion)))) return r;
+  return TJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// validate -> device and stream -> facts -> plan -> claim queues (refused: plan again) -> streams (missing: downgrade) -> LDS attributes -> tables -> arrays
 int tj_create(const tj_params* p, tj_ctx** out) {
   if (!p || !out) return TJ_ERR_INVALID;
   *out = nullptr;
   tj_ctx* c = new tj_ctx();
   *out = c;  // returned even on failure so the caller can read tj_last_error()
   c->prm = *p;
-  if (p->uav_num < 1 || p->piece_num < 2 || p->res < 1 || p->mode < 0 || p->mode > 2 || p->world < 1 || p->rank < 0 || p->rank >= p->world) {
-    c->err = "invalid tj_params (need uav_num>=1, piece_num>=2, res>=1, mode 0/1/2, 0<=rank<world)";
-    return TJ_ERR_INVALID;
-  }
-  if (p->mode == TJ_MODE_SINGLE && p->uav_num != 1) { c->err = "TJ_MODE_SINGLE requires uav_num == 1"; return TJ_ERR_INVALID; }
+  if (const char* bad = plan_check_params(p)) { c->err = bad; return TJ_ERR_INVALID; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { c->err = "no HIP device available (this library has no CPU fallback)"; return TJ_ERR_DEVICE; }
   HIPCHK(c, hipSetDevice(p->device));
   HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  Dev& d = c->d;
-  memset(&d, 0, sizeof(d));
-  d.mode = p->mode; d.U = p->uav_num; d.P = p->piece_num; d.res = p->res; d.S = d.P * d.res; d.T = 3 * d.P + 3; d.N = 0; d.prim = 1;
-  // the fused chain (k_linesearch leaves the hull cache, k_xsolve's tail the swept-hull cache) -- sharded contexts too since round 5: the other ranks' robots
-  // are handled by foreign units inside k_front / k_ccd (Dev::xf).  Coupled mode keeps its own kernels (and, sharded, k_hullinfo / k_ccd_prep for all robots).
-  d.fuse = p->mode != TJ_MODE_MULTI_COUPLED ? 1 : 0;
-  d.rank = p->rank; d.world = p->world;
-  d.xf = (p->world > 1 && d.fuse && p->mode == TJ_MODE_MULTI_DECOUPLE) ? 1 : 0;
-  // coupled mode, one context: every robot's cache records by units inside k_front / k_ccd (two launches less per iteration; TJ_COUPLED_UNITS=0: k_hullinfo / k_ccd_prep)
-  if (p->mode == TJ_MODE_MULTI_COUPLED && p->world == 1 && !(tune("COUPLED_UNITS") && atoi(tune("COUPLED_UNITS")) == 0)) { d.xf = 1; d.xf_all = 1; }
-  d.u0 = (int)((long long)p->rank * d.U / p->world); d.u1 = (int)((long long)(p->rank + 1) * d.U / p->world);
-  d.lambda = p->lambda; d.margin = p->margin; d.offset = p->offset; d.mu = p->mu; d.vel_limit = p->vel_limit; d.acc_limit = p->acc_limit;
-  d.ks = p->ks; d.kt = p->kt; d.stop = p->stop;
-  d.cap_obs = p->cap_obs > 0 ? p->cap_obs : 256;
-  d.cap_self = p->cap_self > 0 ? p->cap_self : std::max(1, std::min(d.U - 1, 64));  // neighbours within offset + 2 margin of ONE segment; k_grad's LDS grows with it
-  d.cap_pairs = p->cap_pairs > 0 ? p->cap_pairs : d.U;
-  d.optimal_plane = p->optimal_plane ? 1 : 0;
-  d.pair_rows = d.U <= 128 ? 8 : 16;   // tile height: 64 robots -- 8 rows: k_front 13.3 -> 12.5 us, k_ccd 9.6 -> 8.7 (with eight interval records in flight); 256 robots -- 16 rows (8: +1.3 us, 4: +13)
-  if (const char* e = tune("PAIR_ROWS")) { const int r = atoi(e); if (r == 2 || r == 4 || r == 8 || r == 16) d.pair_rows = r; }
-  d.cap_work = d.mode >= 1 ? (int)std::min<long long>((long long)d.S * d.U * (d.U - 1) / 2 + 1, 1 << 22) : 1;  // robot pairs per iteration
-  d.xs = 3 * d.T + 4;
-  const int n = 9 * d.P - 2;
-  d.grad_npl = std::min(d.cap_obs + d.cap_self, 64);   // what a batch of segments really carries (SCN-C: <= 40); more goes through grad_scr.  64: five workgroups per CU (96: four)
-  if (const char* e = tune("GRAD_NPL")) { const int r = atoi(e); if (r >= 8 && r <= 4096) d.grad_npl = std::min(d.cap_obs + d.cap_self, r); }
-  c->lds_grad = grad_lds_doubles(d.grad_npl, d.res) * sizeof(double);
-  const size_t lds_max = 160 * 1024 - 1024;
-  // long trajectories: the dense per-robot system no longer fits LDS -> band storage (decoupled / single-UAV modes)
-  d.xs_band = (xsolve_lds_doubles(n) * sizeof(double) > lds_max || tune("XS_BAND")) ? 1 : 0;
-  c->lds_xs = (d.xs_band ? xsolve_band_lds_doubles(n) : xsolve_lds_doubles(n)) * sizeof(double);
-  c->lds_xs2 = (d.xs_band ? (size_t)(n - 1) * BAND_BS + 5 * (size_t)n : (size_t)n * n + 4 * (size_t)n) * sizeof(double);   // k_xsolve_c2 / k_xsolve_c2_band
-  c->lsl = ls_layout(d.S, d.T, d.P, 120 * 1024);
-  c->lds_ls = c->lsl.total * sizeof(double);
-#ifdef TJ_PHASE_TIMING
-  { int r_ = dalloc(c, &d.dbg, (size_t)K_COUNT * TJ_TIC_BLOCKS * TJ_TIC_SLOTS); if (r_) return r_; }
-#endif
-  if (d.U > 2048) { c->err = "more than 2048 robots are not supported (pair keys pack robot ids into 11 bits; the dense [S][U][U] plane tables are 5.4 GB + 0.7 GB there)"; return TJ_ERR_UNSUPPORTED; }
-  if (d.S > 511) { c->err = "more than 511 segments per robot are not supported by the line-search kernel"; return TJ_ERR_UNSUPPORTED; }
-  if (d.res > GRAD_MAXRES) { c->err = "res > 16 segments per piece is not supported by the gradient kernel"; return TJ_ERR_UNSUPPORTED; }
-  d.seq_tree = (d.mode == TJ_MODE_MULTI_DECOUPLE && seq_lds_bytes(d.U, d.S, true) <= lds_max) ? 1 : 0;
-  if (tune("NO_SEQ_TREE")) d.seq_tree = 0;  // test hook: behave like a fleet too large for the LDS-resident tree
-  c->lds_seq = seq_lds_bytes(d.U, d.S, d.seq_tree != 0);
-  // hundreds of robots: the 512-thread folded k_grad is limited to ~2 workgroups per CU by wave slots; the 192-thread one (5 per CU)
-  // plus a separate compaction launch is faster once there are more pieces than that (SCN-D: k_grad 109 -> 72 + 14 us)
-  c->grad_fold = (d.u1 - d.u0) * d.P <= 512;
-  if (const char* e = tune("GRAD_FOLD")) c->grad_fold = atoi(e) != 0;
-  d.bvh_skip = 0;    // decided when the obstacle set is known (set_obstacles); TJ_BVH_SKIP=0 / 1 forces it (launch-shape switch, same bits)
-  if (const char* e = tune("BVH_SKIP")) d.bvh_skip = atoi(e) != 0;
-  d.pair_prio = 1;
-  d.mid_order = (d.mode >= 1 && d.U >= 192) ? 1 : 0;   // k_mid's grid order (kernels_step.h): config 5 -15 us; small fleets: nothing or slightly worse
-  if (const char* e = tune("MID_ORDER")) d.mid_order = atoi(e) != 0;   // launch-shape switch (same bits)
-  if (const char* e = tune("PAIR_PRIO")) d.pair_prio = atoi(e) != 0;   // launch-shape switch (same bits)
-  d.pair_lpw = 64;
-  if (const char* e = tune("PAIR_LPW")) { const int r = atoi(e); if (r == 8 || r == 16 || r == 32 || r == 64) d.pair_lpw = r; }   // launch-shape switch (same bits)
-  d.pair_pass_on = 1;
-  if (const char* e = tune("PAIR_PASS_ON")) d.pair_pass_on = atoi(e) != 0;
-  // GJK head start for last iteration's slow robot pairs (kernels_pairs.h: spec_pair_body); TJ_PAIR_HEAD_START=0 switches it off (test hook: same bits)
-  d.spec = (d.mode >= 1 && !d.optimal_plane) ? 1 : 0;
-  if (const char* e = tune("PAIR_HEAD_START")) d.spec = d.spec && atoi(e) != 0;
-  // k_ccd's last block finishes with the sequential pair replay + gnorm (kernels_step.h): decoupled mode, when the replay's small
-  // arrays fit k_ccd's static LDS buffer with room for at least 256 acting-pair keys (the value is that capacity)
-  d.seq_fold = 0;
-  if (d.mode == TJ_MODE_MULTI_DECOUPLE || (d.mode == TJ_MODE_MULTI_COUPLED && p->world == 1)) {   // (coupled: one context only -- a sharded one exports its obstacle-CCD exponents from k_ccd_self_seq)
-    const size_t buf = sizeof(double) * (size_t)(CCD_LDS_DOUBLES > PAIR_LDS_DOUBLES ? CCD_LDS_DOUBLES : PAIR_LDS_DOUBLES);
-    int cap = 4096;
-    while (cap >= 256 && seq_fold_lds_bytes(d.U, cap) > buf) cap >>= 1;
-    if (cap >= 256 && (size_t)d.S * pair_units(d.U, d.pair_rows) < 65536) d.seq_fold = cap;   // (the finisher counts the selection blocks in 16 bits)
-  }
-  if (const char* e = tune("SEQ_FOLD")) if (atoi(e) == 0) d.seq_fold = 0;   // launch-shape switch (same bits)
-  c->n_solve_env = 0;
-  if (const char* e = tune("N_SOLVE")) c->n_solve_env = std::max(1, atoi(e));
-  d.spec_budget = SPEC_GJK_BUDGET; d.spec_min = SPEC_GJK_MIN;
-  if (const char* e = tune("HS_BUDGET")) d.spec_budget = std::max(1, atoi(e));   // development hooks (same bits for any value)
-  if (const char* e = tune("HS_MIN")) d.spec_min = std::max(1, atoi(e));
-  d.ls_fast = 1;
-  if (const char* e = tune("LS_FAST")) d.ls_fast = atoi(e) != 0;   // launch-shape switch (same bits): round 0 of k_linesearch in the team shape
-  {   // helper blocks of k_linesearch: one CU each, so as many per robot as the device has compute units to spare (64 robots on 256 CUs: 4)
-    hipDeviceProp_t prop;
-    HIPCHK(c, hipGetDeviceProperties(&prop, p->device));
-    const int owned = std::max(1, d.u1 - d.u0);
-    d.num_cu = prop.multiProcessorCount;
-    // coupled mode: the four evaluation rounds of the Armijo search in one launch where a block per (robot, round) gets a compute unit of its own
-    c->lsc_wide = p->mode == TJ_MODE_MULTI_COUPLED && owned * LSC_ROUNDS <= d.num_cu;
-    // ... and the corner solve inside k_xsolve where every robot's block is resident at once (one block per compute unit: 242 registers x 8 waves), dense storage
-    d.c2_fold = (p->mode == TJ_MODE_MULTI_COUPLED && p->world == 1 && d.U <= d.num_cu && !d.xs_band) ? 1 : 0;
-    if (const char* e = tune("C2_FOLD")) d.c2_fold = d.c2_fold && atoi(e) != 0;   // launch-shape switch (same bits)
-    if (const char* e = tune("LSC_WIDE")) c->lsc_wide = atoi(e) != 0;   // launch-shape switch (same bits)
-    // k_grad's launch order follows the items' last durations where blocks outnumber the compute units (kernels_newton.h: grad_order_body)
-    // -- between one and two blocks per unit, the case it was measured on: SCN-C -1.5 us per iteration, the 64 hard robots -1.4; at five blocks per unit
-    // (256 robots) longest-first ordering bought nothing in k_grad and the run was 1.5 % slower, so larger fleets keep the identity
-    d.grad_bal = (owned * d.P > d.num_cu && owned * d.P < 2 * d.num_cu) ? 1 : 0;
-    // asynchronous Newton solve (dev_common.h, Dev::xs_async): one context, decoupled / single-UAV chain with the swept-hull tail in k_xsolve.  TJ_XS_ASYNC=0: the
-    // solve stays a link of the one-queue chain (launch-shape switch: same bits)
-    d.xs_async = (p->world == 1 && !d.xs_band && (p->mode != TJ_MODE_MULTI_COUPLED ? d.fuse != 0 : (d.c2_fold && d.xf_all))) ? 1 : 0;   // (coupled chain: with the corner solve in k_xsolve and k_ccd's units building the records already;
-                                                                                                                                               //  sharded contexts keep the one-queue chain: tried in round 5, a tj_group of two ranks aborted -- not pursued)
-    if (d.xs_async) {
-      // Liveness: k_xsolve's blocks hold registers and LDS while they sleep on their tickets, and the k_grad blocks that hand the tickets out may still be waiting
-      // for a compute unit.  Safe when the sleepers can never shut k_grad out: at most half as many robots as compute units (half the device stays free whatever
-      // the dispatcher does), or at most one robot per unit AND a k_grad block fits a unit next to one k_xsolve block (a unit with two sleepers then implies a
-      // unit with none).  Larger fleets keep the solve on the chain's queue (1 500 robots: the sleepers filled the device and every wait ran into its 5 ms limit).
-      bool fits = false;
-      {
-        const void* fx = nullptr;
-        switch (9 * d.P - 2) {
-          case 16: fx = (const void*)k_xsolve<16>; break; case 25: fx = (const void*)k_xsolve<25>; break; case 34: fx = (const void*)k_xsolve<34>; break;
-          case 43: fx = (const void*)k_xsolve<43>; break; case 52: fx = (const void*)k_xsolve<52>; break; default: fx = (const void*)k_xsolve<0>; break;
-        }
-        const void* fg = c->grad_fold ? (const void*)k_grad<true> : (const void*)k_grad<false>;
-        hipFuncAttributes ax, ag;
-        if (hipFuncGetAttributes(&ax, fx) == hipSuccess && hipFuncGetAttributes(&ag, fg) == hipSuccess) {
-          auto gran = [](int r) { return (r + 7) / 8 * 8; };
-          const int wx = XS_LOAD_THREADS / 64, wg = (c->grad_fold ? GRAD_FOLD_THREADS : GRAD_THREADS) / 64;
-          const size_t lx = c->lds_xs + ax.sharedSizeBytes, lg = c->lds_grad + (c->grad_fold ? grad_fold_extra_doubles(d.res) * sizeof(double) : 0) + ag.sharedSizeBytes;
-          fits = ((wx + 3) / 4) * gran(ax.numRegs) + ((wg + 3) / 4) * gran(ag.numRegs) <= 512 && lx + lg <= (size_t)160 * 1024 && (wx + 3) / 4 + (wg + 3) / 4 <= 8;
-        } else (void)hipGetLastError();
-      }
-      if (!(2 * owned <= d.num_cu || (owned <= d.num_cu && fits))) d.xs_async = 0;
-    }
-    // rocprofv3's counter collection (--pmc) serialises the dispatches of ALL queues, in an order of its own: a gate held back behind the kernel it waits for would run every
-    // wait into its 2 s limit.  Under it the context keeps everything on the one queue (an explicit TJ_XS_ASYNC=1 / TJ_KEEP_ASYNC=1 overrides).
-    const char* cc_ = getenv("ROCPROF_COUNTER_COLLECTION");
-    const bool counters_on = cc_ && cc_[0] && strcmp(cc_, "0") != 0 && strcasecmp(cc_, "false") != 0;
-    if (counters_on && !tune("XS_ASYNC")) d.xs_async = 0;
-    if (const char* e = tune("XS_ASYNC")) d.xs_async = d.xs_async && atoi(e) != 0;
-    // Hardware queues.  HIP maps a process's streams onto GPU_MAX_HW_QUEUES (4) hardware queues per device and lets further streams SHARE them; a gate kernel that sleeps at the
-    // head of a shared queue keeps back whatever another context put behind it -- possibly the very kernel a gate of THAT context, asleep on a queue of this one, waits for:
-    // measured with three default contexts in one process, two of them ran into the 2 s limit (and healed themselves).  So the contexts of a process that sleep across queues
-    // claim their streams (main + second + third) out of a per-device budget of GPU_MAX_HW_QUEUES - 1 (the null stream has one); a context that does not fit keeps the one-queue
-    // chain (same bits).  An explicit TJ_XS_ASYNC=1 / TJ_KEEP_ASYNC=1 overrides; self-healing stays the net under it.
-    {
-      const bool want_keep = d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !(counters_on && !tune("KEEP_ASYNC")) && !(tune("KEEP_ASYNC") && atoi(tune("KEEP_ASYNC")) == 0);
-      const int need = 1 + (d.xs_async ? 1 : 0) + (want_keep ? 1 : 0);
-      const bool forced = (tune("XS_ASYNC") && atoi(tune("XS_ASYNC")) != 0) || (tune("KEEP_ASYNC") && atoi(tune("KEEP_ASYNC")) != 0);
-      if (need > 1) {
-        std::atomic<int>& g = g_async_queues[std::min(std::max(p->device, 0), 63)];
-        const int had = g.fetch_add(need);
-        if (had + need > hw_queue_budget() && !forced) { g.fetch_sub(need); d.xs_async = 0; c->hwq_refused = true; }
-        else c->xq.hwq_claim = need;
-      }
-    }
-    if (d.xs_async) {
-      const bool ok = hipStreamCreateWithFlags(&c->xq.stream2, hipStreamNonBlocking) == hipSuccess;
-      if (!ok) { (void)hipGetLastError(); c->xq.stream2 = nullptr; }   // (the tickets and flags work on one queue as well)
-      c->xq.xs_two_queues = ok && tune("XS_ONE_QUEUE") == nullptr;
-    }
-    // asynchronous plane refinement ("optimal_plane":1, multi-UAV decoupled mode, one context; TJ_KEEP_ASYNC=0: k_keep stays one launch between k_mid and k_grad -- same bits)
-    d.keep_async = (d.optimal_plane && p->mode == TJ_MODE_MULTI_DECOUPLE && p->world == 1 && !c->hwq_refused) ? 1 : 0;
-    if (counters_on && !tune("KEEP_ASYNC")) d.keep_async = 0;
-    if (const char* e = tune("KEEP_ASYNC")) d.keep_async = d.keep_async && atoi(e) != 0;
-    d.keep_waves = 1024;
-    if (d.keep_async) {
-      if (hipStreamCreateWithFlags(&c->xq.stream3, hipStreamNonBlocking) == hipSuccess) c->xq.keep_two_queues = true;
-      else { (void)hipGetLastError(); c->xq.stream3 = nullptr; d.keep_async = 0; }
-    }
-    if (const char* e = tune("GRAD_BALANCE")) d.grad_bal = (atoi(e) != 0 && owned * d.P <= 65536) ? 1 : 0;   // launch-shape switch (same bits)
-    d.ls_help = (d.ls_fast && p->mode != TJ_MODE_MULTI_COUPLED) ? std::max(1, std::min(LS_HELP_MAX, prop.multiProcessorCount / owned)) : 1;
-    if (const char* e = tune("LS_HELP")) {   // launch-shape switch (same bits); 1 = no helpers.  More blocks per robot than the compute units hold at once would leave helpers waiting for a
-                                                  // unit while every primary runs into its 10 us give-up per super-round: clamped to the units the device has
-      d.ls_help = std::max(1, std::min(LS_HELP_MAX, atoi(e)));
-      d.ls_help = std::min(d.ls_help, std::max(1, prop.multiProcessorCount / owned));
-    }
-    if (const char* e = tune("LS_HELP_LATE")) d.ls_help_late = std::max(0, std::min(4000, atoi(e)));   // test hook (same bits): helper blocks idle that many microseconds before staging
-    if (const char* e = tune("LS_HELP_MUTE")) d.ls_help_mute = atoi(e) != 0;                          // test hook (same bits): the helpers never post, the primaries time out
-    // asynchronous front (dev_common.h, Dev::fa): one context, decoupled mode, the asynchronous solve's second queue, and a k_linesearch grid that is resident all at once
-    // (one block per compute unit at most -- the residency gate's premise).  TJ_FRONT_ASYNC=0: k_linesearch publishes the hull cache and k_front follows it on the chain's queue (same bits)
-    d.fa = (d.xs_async && p->world == 1 && !d.optimal_plane &&
-            (p->mode != TJ_MODE_MULTI_COUPLED ? (d.fuse && owned * d.ls_help <= d.num_cu) : (c->lsc_wide && d.xf_all && owned * LSC_ROUNDS <= d.num_cu))) ? 1 : 0;   // (coupled: the one-launch search, whose last block commits every robot)
-    if (const char* e = tune("FRONT_ASYNC")) d.fa = d.fa && atoi(e) != 0;
-    c->fa_emulate = tune("FRONT_ASYNC_ONE_QUEUE") && atoi(tune("FRONT_ASYNC_ONE_QUEUE")) != 0;   // the asynchronous front's data flow (k_front's units form the records, k_linesearch publishes none) on the chain's queue: counter passes
-    if (d.fa) {
-      // Dev::fa_mid: k_mid may start while k_front still runs only if k_front's whole grid is resident before k_mid's first wave is -- the last k_linesearch block waits
-      // until every k_front block has started, so the grid must fit the device next to that one block: blocks per compute unit by LDS, registers and wave slots
-      const int n_rows = d.S * pair_units(d.U, d.pair_rows);
-      const int n_front = owned * d.S + n_rows + (d.spec ? SPEC_CAP : 0) + (d.grad_bal ? (owned * d.P + 63) / 64 : 0);
-      hipFuncAttributes af;
-      if (hipFuncGetAttributes(&af, (const void*)k_front<1, true>) == hipSuccess) {
-        hipFuncAttributes a3; if (hipFuncGetAttributes(&a3, (const void*)k_front<3, true>) == hipSuccess) { af.numRegs = std::max(af.numRegs, a3.numRegs); af.sharedSizeBytes = std::max(af.sharedSizeBytes, a3.sharedSizeBytes); } else (void)hipGetLastError();
-        const int by_lds = (int)(((size_t)160 * 1024) / std::max<size_t>(af.sharedSizeBytes, 1)), by_regs = 4 * (512 / std::max((af.numRegs + 7) / 8 * 8, 8)), per_cu = std::min(std::min(by_lds, by_regs), 32);
-        c->fa_mid_ok = (long long)n_front <= (long long)(d.num_cu - 1) * per_cu;
-      } else (void)hipGetLastError();
-      if (const char* e = tune("FRONT_ASYNC_MID")) c->fa_mid_ok = c->fa_mid_ok && atoi(e) != 0;   // launch-shape switch (same bits): 0 = k_linesearch waits for k_front's end, k_mid follows plainly
-    }
-  }
-  if (c->lds_grad + grad_fold_extra_doubles(d.res) * sizeof(double) > lds_max || c->lds_xs > lds_max || c->lds_ls > lds_max || c->lds_seq > lds_max) {
-    c->err = "problem does not fit the 160 KB LDS of one CU (segments per robot / fleet size too large for this version)";
-    return TJ_ERR_UNSUPPORTED;
-  }
-  HIPCHK(c, hipFuncSetAttribute((const void*)k_grad<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(c->lds_grad + grad_fold_extra_doubles(d.res) * sizeof(double))));
-  HIPCHK(c, hipFuncSetAttribute((const void*)k_grad<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_grad));
-  if (d.xs_band) HIPCHK(c, hipFuncSetAttribute((const void*)k_xsolve_band, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_xs));
-  else {
-    const void* kx = (const void*)k_xsolve<0>;
-    switch (n) { case 16: kx = (const void*)k_xsolve<16>; break; case 25: kx = (const void*)k_xsolve<25>; break; case 34: kx = (const void*)k_xsolve<34>; break;
-                 case 43: kx = (const void*)k_xsolve<43>; break; case 52: kx = (const void*)k_xsolve<52>; break; }   // 61 rows: the inlined form would spill, the generic kernel calls it out of line
-    HIPCHK(c, hipFuncSetAttribute(kx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_xs));
-  }
-  HIPCHK(c, hipFuncSetAttribute((const void*)k_linesearch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_ls));
-  HIPCHK(c, hipFuncSetAttribute((const void*)k_ls_coupled, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_ls));
-  if (!d.xs_band) HIPCHK(c, hipFuncSetAttribute((const void*)k_xsolve_c2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_xs2));
-  else HIPCHK(c, hipFuncSetAttribute((const void*)k_xsolve_c2_band, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_xs2));
-  HIPCHK(c, hipFuncSetAttribute((const void*)k_ccd_self_seq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_seq));
-
-  HostTables t;
-  build_tables(d.P, d.res, STEP_CAP, t);
-  double *basis, *convert, *mdyn, *kdop, *pow08;
   int r;
-  if ((r = dalloc(c, &basis, t.basis.size())) || (r = dalloc(c, &convert, t.convert.size())) || (r = dalloc(c, &mdyn, 36)) ||
-      (r = dalloc(c, &kdop, 147)) || (r = dalloc(c, &pow08, t.pow08.size()))) return r;
-  if ((r = upload(c, basis, t.basis.data(), t.basis.size() * 8)) || (r = upload(c, convert, t.convert.data(), t.convert.size() * 8)) ||
-      (r = upload(c, mdyn, t.mdyn, 36 * 8)) || (r = upload(c, kdop, t.kdop, 147 * 8)) || (r = upload(c, pow08, t.pow08.data(), t.pow08.size() * 8))) return r;
-  d.basis = basis; d.convert = convert; d.mdyn = mdyn; d.kdop = kdop; d.pow08 = pow08;
-  {   // k_xsolve's overlap-add as a table: per entry of the reduced system the (at most two) piece-block entries that cover it, in piece order; -2: the time-time entry (every piece)
-    const int Pn = d.P, m = 9 * Pn - 3, n = m + 1;
-    std::vector<int> gt((size_t)2 * n * n + 2 * n, -1);
-    auto cover = [&](int g, int& lo, int& hi) { if (g >= 0) { lo = std::max(lo, (g - 17 + 8) / 9); hi = std::min(hi, g / 9); } };
-    for (int idx = 0; idx < n * n; idx++) {
-      const int ra = idx / n, rb = idx % n, ga = ra == m ? -1 : ra + 6, gb = rb == m ? -1 : rb + 6;
-      if (ga < 0 && gb < 0) { gt[2 * (size_t)idx] = -2; continue; }
-      int lo = 0, hi = Pn - 1, k = 0;
-      cover(ga, lo, hi); cover(gb, lo, hi);
-      for (int sp = std::max(lo, 0); sp <= hi; sp++) {
-        const int a = ga < 0 ? 18 : ga - 9 * sp, b = gb < 0 ? 18 : gb - 9 * sp;
-        if (k < 2) gt[2 * (size_t)idx + k] = sp * 361 + a * 19 + b;
-        k++;
-      }
-      if (k > 2) { c->err = "internal: an entry of the reduced system is covered by more than two piece blocks"; return TJ_ERR_INVALID; }
-    }
-    for (int ra = 0; ra < n; ra++) {
-      const int ga = ra == m ? -1 : ra + 6;
-      if (ga < 0) { gt[(size_t)2 * n * n + 2 * ra] = -2; continue; }
-      int lo = 0, hi = Pn - 1, k = 0;
-      cover(ga, lo, hi);
-      for (int sp = std::max(lo, 0); sp <= hi; sp++) { if (k < 2) gt[(size_t)2 * n * n + 2 * ra + k] = sp * 19 + (ga - 9 * sp); k++; }
-      if (k > 2) { c->err = "internal: a row of the reduced system is covered by more than two piece blocks"; return TJ_ERR_INVALID; }
-    }
-    int* gtd = nullptr;
-    if ((r = dalloc(c, &gtd, gt.size())) || (r = upload(c, gtd, gt.data(), gt.size() * sizeof(int)))) return r;
-    d.xs_gather = gtd;
+  if ((r = gather_facts(c, c->facts))) return r;
+  Plan pl = plan_context(p, c->facts, tune);
+  if (!pl.err && pl.h.queues > 1) {   // contexts that sleep across queues claim their streams out of the process's budget (host_plan.h)
+    if (queue_budget(p->device, pl.h.queues, pl.h.forced)) c->xq.hwq_claim = pl.h.queues;
+    else { c->facts.claim_refused = 1; pl = plan_context(p, c->facts, tune); }
   }
-  const size_t U = d.U, S = d.S, P = d.P, T = d.T;
-  if ((r = dalloc(c, &d.spline, U * 3 * T)) || (r = dalloc(c, &d.p_slack, U * 18 * P)) || (r = dalloc(c, &d.p_lambda, U * 18 * P)) ||
-      (r = dalloc(c, &d.t_slack, U * P)) || (r = dalloc(c, &d.t_lambda, U * P)) || (r = dalloc(c, &d.piece_time, U)) ||
-      (r = dalloc(c, &d.oplanes, U * S * d.cap_obs * 4)) || (r = dalloc(c, &d.ocount, U * S)) ||
-      (r = dalloc(c, &d.splanes, U * S * d.cap_self * 4)) || (r = dalloc(c, &d.scount, U * S)) ||
-      (r = dalloc(c, &d.lg, U * P * 19)) || (r = dalloc(c, &d.lh, U * P * 361)) || (r = dalloc(c, &d.xdir, U * d.xs)) ||
-      (r = dalloc(c, &d.k_obs, U)) || (r = dalloc(c, &d.k_self, U)) || (r = dalloc(c, &d.step_out, U)) || (r = dalloc(c, &d.ls_hist, U)) || (r = dalloc(c, &d.grad_cost, (d.u1 - d.u0) * P)) || (r = dalloc(c, &d.grad_perm, (d.u1 - d.u0) * P)) || (r = dalloc(c, &d.ls_tab, U * LS_TAB_STRIDE)) || (r = dalloc(c, &d.ls_word, U)) ||
-      (r = dalloc(c, &d.ccdinfo, U * S * CCD_STRIDE)) || (r = dalloc(c, &d.pair_list, ACT_CAP)) ||
-      (r = dalloc(c, &d.seg_stats, U * S * 6)) || (r = dalloc(c, &d.pair_stats, U * S * 2)) || (r = dalloc(c, &d.blk_stats, U * P + U)) ||
-      (r = dalloc(c, &d.hullinfo, U * S * HULL_STRIDE)) || (r = dalloc(c, &d.hbox, S * 6 * U)) || (r = dalloc(c, &d.cbox, S * 6 * U)) || (r = dalloc(c, &d.pairplane, d.mode >= 1 ? S * U * U * 4 : 1)) ||
-      (r = dalloc(c, &d.pairstamp, d.mode >= 1 ? S * U * U : 1)) || (r = dalloc(c, &d.pairbits, d.mode >= 1 ? S * U * ((U + 63) / 64) : 1)) ||
-      (r = dalloc(c, &d.pair_work, 3 * (size_t)d.cap_work)) || (r = dalloc(c, &d.pair_work_n, (size_t)d.S + 1)) || (r = dalloc(c, &d.pair_ovf, 4)) || (r = dalloc(c, &d.seq_gmem_d, seq_fold_gmem_doubles(d.U))) || (r = dalloc(c, &d.seq_gmem_i, seq_fold_gmem_ints(d.U))) || (r = dalloc(c, &d.spec_n, 2)) || (r = dalloc(c, &d.spec_list, 2 * SPEC_CAP)) || (r = dalloc(c, &d.spec_tag, SPEC_CAP)) || (r = dalloc(c, &d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES)) || (r = dalloc(c, &d.spec_sti, SPEC_CAP * SPEC_STATE_INTS)) || (r = dalloc(c, &d.pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX)) || (r = dalloc(c, &d.ctl, 1)) ||
-      (r = dalloc(c, &d.ocand, U * S * d.cap_obs)) || (r = dalloc(c, &d.ocand_n, U * S)) || (r = dalloc(c, &d.ohull, U * S * 18)) ||
-      (r = dalloc(c, &d.obs_work, 2 * U * S * d.cap_obs)) || (r = dalloc(c, &d.obs_work_n, 1)) ||
-      (r = dalloc(c, &d.oraw, U * S * d.cap_obs * 4)) || (r = dalloc(c, &d.ostamp, U * S * d.cap_obs)) ||
-      (r = dalloc(c, &d.grad_scr, (size_t)(d.u1 - d.u0) * P * 16 * (size_t)(d.cap_obs + d.cap_self))) ||
-      (r = dalloc(c, &d.xs_scr, d.xs_band ? (size_t)(d.u1 - d.u0) * ((size_t)n * n + 4 * n) : 1)) ||
-      (r = dalloc(c, &d.xf_seg, 2 * S * XF_SEG_STRIDE)) || (r = dalloc(c, &d.xs_sync, Dev::xs_sync_ints(U))) || (r = dalloc(c, &d.keep_sync, Dev::keep_sync_ints())) || (r = dalloc(c, &d.fa_sync, Dev::fa_sync_ints(d.U)))) return r;
-  if (d.optimal_plane) {
-    const bool m0 = d.mode == 0;
-    if ((r = dalloc(c, &d.kobs_id, m0 ? U * S * d.cap_obs : 1)) || (r = dalloc(c, &d.kobs_n, U * S)) || (r = dalloc(c, &d.kobs_cd, m0 ? U * S * d.cap_obs * 4 : 1)) ||
-        (r = dalloc(c, &d.kpair_on, m0 ? 1 : S * U * U)) || (r = dalloc(c, &d.kpair_list, m0 ? 1 : S * U * U)) || (r = dalloc(c, &d.kpair_n, 2)) ||
-        (r = dalloc(c, &d.kpair_cd, m0 ? 1 : S * U * U * 4))) return r;
-  }
-  {   // self-healing: what a batch's first state consists of (everything an iteration reads that an earlier iteration wrote and that is not rebuilt or re-stamped anyway)
-    c->heal = !(tune("HEAL") && atoi(tune("HEAL")) == 0);
-    if (const char* e = tune("XS_FAULT")) c->xq.xs_fault = atoi(e);   // test hook: the n-th gate of the asynchronous solve reports a time-out
-    std::vector<std::pair<void*, size_t>> reg = {
-      {d.spline, U * 3 * T * 8}, {d.p_slack, U * 18 * P * 8}, {d.p_lambda, U * 18 * P * 8}, {d.t_slack, U * P * 8}, {d.t_lambda, U * P * 8}, {d.piece_time, U * 8},
-      {d.xdir, U * d.xs * 8}, {d.ls_hist, U * 4}, {d.step_out, U * 8}, {d.seg_stats, U * S * 6 * 8}, {d.pair_stats, U * S * 2 * 8}, {d.blk_stats, (U * P + U) * 8}};
-    if (d.optimal_plane) {
-      const bool m0 = d.mode == 0;
-      if (m0) { reg.push_back({d.kobs_id, U * S * d.cap_obs * 4}); reg.push_back({d.kobs_n, U * S * 4}); reg.push_back({d.kobs_cd, U * S * d.cap_obs * 32}); }
-      else { reg.push_back({d.kpair_on, S * U * U * 4}); reg.push_back({d.kpair_list, S * U * U * 4}); reg.push_back({d.kpair_n, 8}); reg.push_back({d.kpair_cd, S * U * U * 32}); }
-    }
-    std::vector<SnapRegion> tab;
-    for (auto& pr : reg) {
-      char* snap = nullptr;
-      if ((r = dalloc(c, &snap, (pr.second + 15) / 16 * 16))) return r;
-      tab.push_back(SnapRegion{(char*)pr.first, snap, (unsigned long long)pr.second});
-    }
-    c->ck.n = (int)tab.size();
-    if ((r = dalloc(c, &c->ck.tab, tab.size())) || (r = dalloc(c, &c->ck.ctl, 1)) || (r = upload(c, c->ck.tab, tab.data(), tab.size() * sizeof(SnapRegion)))) return r;
-  }
-  if (d.mode == TJ_MODE_MULTI_COUPLED &&
-      ((r = dalloc(c, &d.xL, U * (d.xs_band ? (size_t)(n - 1) * BAND_BS + n : (size_t)n * n))) || (r = dalloc(c, &d.xy, U * (size_t)n)) || (r = dalloc(c, &d.xg, U * (size_t)n)) ||
-       (r = dalloc(c, &d.xcorner, U * 4)) || (r = dalloc(c, &d.k_obs_f, U)) || (r = dalloc(c, &d.ls_e, (size_t)LSC_ROUNDS * U * LS_GROUPS)))) return r;
+  auto stream_for = [&](int wanted, hipStream_t& s) {   // (a stream that cannot be created is not an error: plan_downgrade)
+    if (wanted && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); s = nullptr; }
+    return !wanted || s != nullptr;
+  };
+  if (!pl.err) { const bool s2 = stream_for(pl.d.xs_async, c->xq.stream2), s3 = stream_for(pl.d.keep_async, c->xq.stream3); plan_downgrade(pl, s2, s3); }
+  c->d = pl.d; c->hp = pl.h;
+  c->xq.xs_two_queues = pl.h.xs_two_queues; c->xq.keep_two_queues = pl.h.keep_two_queues; c->xq.xs_fault = pl.h.xs_fault;
+  if (pl.err) { c->err = pl.msg; return pl.err; }
+  if ((r = set_lds_attributes(c)) || (r = upload_tables(c)) || (r = allocate_arrays(c))) return r;
   return TJ_OK;
 }
 
 void tj_destroy(tj_ctx* c) {
   if (!c) return;
-  if (c->xq.hwq_claim) { g_async_queues[std::min(std::max(c->prm.device, 0), 63)].fetch_sub(c->xq.hwq_claim); c->xq.hwq_claim = 0; }
+  release_queues(c);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->xq.stream2) { (void)hipStreamSynchronize(c->xq.stream2); (void)hipStreamDestroy(c->xq.stream2); }
   if (c->xq.stream3) { (void)hipStreamSynchronize(c->xq.stream3); (void)hipStreamDestroy(c->xq.stream3); }
@@ -919,7 +796,7 @@ int set_obstacles(tj_ctx* c, const double* verts, int n, int prim) {
   if ((int)lvl_n.size() > MAX_LEVELS) { c->err = "too many obstacle primitives for MAX_LEVELS"; return TJ_ERR_UNSUPPORTED; }
   QUIESCE(c);
   c->have_cloud = false;
-  d.N = 0; d.nlevels = 0; if (!tune("BVH_SKIP")) d.bvh_skip = 0; d.px = d.py = d.pz = d.tri = nullptr; d.boxes = d.leafbox = nullptr;
+  d.N = 0; d.nlevels = 0; if (!c->hp.bvh_skip_forced) d.bvh_skip = 0; d.px = d.py = d.pz = d.tri = nullptr; d.boxes = d.leafbox = nullptr;
   for (void* p : c->cloud_allocs) hipFree(p);
   c->cloud_allocs.clear();
   c->cloud_order.clear();
@@ -984,7 +861,7 @@ int set_obstacles(tj_ctx* c, const double* verts, int n, int prim) {
     d.nlevels = (int)lvl_n.size();
     // two levels per step at the top of the walk (kernels_sep.h): pays where the pyramid is deep AND the query waves outnumber the resident slots, i.e. where a
     // query's latency is the launch's throughput (256 robots x 1 M primitives: k_front 40.2 -> 36.3 us, k_ccd 34.0 -> 31.0); 64 robots through 1 M points: no change
-    if (!tune("BVH_SKIP")) d.bvh_skip = (d.nlevels >= 5 && (d.u1 - d.u0) * d.S > 3584) ? 1 : 0;
+    if (!c->hp.bvh_skip_forced) d.bvh_skip = (d.nlevels >= 5 && (d.u1 - d.u0) * d.S > 3584) ? 1 : 0;
     for (int i = 0; i < d.nlevels; i++) { d.lvl_off[i] = lvl_off[i]; d.lvl_n[i] = lvl_n[i]; }
     d.N = n;
   }
@@ -1127,7 +1004,7 @@ int tj_set_state(tj_ctx* c, int u, const double* spline, const double* p_slack, 
 namespace {
 // the parts of tj_iterate_async (also used by the lockstep enqueue of the ranks of a group that share a device, tj_group.h)
 int iterate_async_prologue(tj_ctx* c, int n_iters) {
-  if (c->heal && n_iters > 0 && (c->xq.xs_two_queues || c->xq.keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
+  if (c->hp.heal && n_iters > 0 && (c->xq.xs_two_queues || c->xq.keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
     if (c->snap_iters == 0 && !c->heal_busy) { int r = checkpoint_take(c, !c->begin_folded); if (r) return r; }   // (no begin folded: the batch's first launch is k_begin)
     if (!c->heal_busy) c->snap_iters += n_iters;
   }
@@ -1138,7 +1015,7 @@ int iterate_async_prologue(tj_ctx* c, int n_iters) {
 // inside a batch the begin work of iteration i+1 rides on iteration i's k_linesearch (not in coupled mode, whose line search
 // is several kernels -- except where the whole search is ONE launch whose last block commits: lsc_wide, one context)
 bool iterate_async_chain(const tj_ctx* c) {
-  return c->d.mode != TJ_MODE_MULTI_COUPLED || (c->lsc_wide && c->d.u1 - c->d.u0 == c->d.U);
+  return c->d.mode != TJ_MODE_MULTI_COUPLED || (c->hp.lsc_wide && c->d.u1 - c->d.u0 == c->d.U);
 }
 
 // chain position of iteration i of a batch of n (clears begin_folded: the fold it reports is consumed here)
@@ -1407,8 +1284,8 @@ int tj_get_energy(tj_ctx* c, double* energy) {
   DevBuf out;
   { int r = to_dev(c, out, nullptr, (size_t)d.U * 8); if (r) return r; }
   HIPCHK(c, hipMemsetAsync(out.p, 0, (size_t)d.U * 8, c->stream));
-  HIPCHK(c, hipFuncSetAttribute((const void*)k_energy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_ls));
-  hipLaunchKernelGGL(k_energy, dim3(d.u1 - d.u0), dim3(LS_THREADS), c->lds_ls, c->stream, d, c->lsl, (double*)out.p);
+  HIPCHK(c, hipFuncSetAttribute((const void*)k_energy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->hp.lds_ls));
+  hipLaunchKernelGGL(k_energy, dim3(d.u1 - d.u0), dim3(LS_THREADS), c->hp.lds_ls, c->stream, d, c->hp.lsl, (double*)out.p);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(energy, out.p, (size_t)d.U * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2040,6 +1917,21 @@ int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double*
   QUIESCE(c);
   HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * 64, hipMemcpyDeviceToHost));
   return TJ_OK;
+}
+
+// the launch plan as a flat record of ints (host_plan.h: plan_record): a context's own, or -- c == nullptr, no device needed -- the pure planner's on the
+// caller's parameters and PLAN_FACT_INTS device facts.  Returns the number of ints (negated: `cap` is too small), msg: the planner's error text
+int tj_kat_plan(const tj_ctx* c, const tj_params* p, const int* facts, int* out, int cap, char* msg, int msg_cap) {
+  if (!out || (!c && (!p || !facts))) return 0;
+  Plan pl; PlanFacts f;
+  if (c) { pl.d = c->d; pl.h = c->hp; f = c->facts; f.prim = c->d.prim; f.n_obs = c->d.N; }
+  else {
+    memcpy(&f, facts, sizeof(f));
+    if (const char* bad = plan_check_params(p)) { pl.err = TJ_ERR_INVALID; pl.msg = bad; memset(&pl.d, 0, sizeof(pl.d)); pl.h.lsl = LsLayout{}; }
+    else { pl = plan_context(p, f, tune); pl.d.prim = f.prim; pl.d.N = f.n_obs; }
+  }
+  if (msg && msg_cap > 0) { strncpy(msg, pl.msg, (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+  return plan_record(pl, f, out, cap);
 }
 
 int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out) {

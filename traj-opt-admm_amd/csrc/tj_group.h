@@ -310,10 +310,8 @@ int group_select_transport(tj_group* g, int t) {
     // ranks sharing a device: k_linesearch's helper blocks (one compute unit each) only where the ranks run in lockstep (flag: the kernels of the ranks overlap and every
     // helper is resident; measured with 2 x 32 robots on one device: 0.147 -> 0.137 ms) -- under the event transport, which orders whole kernels, the helpers of one rank
     // queue behind the other rank's blocks and the primaries run into their 10 us give-up (0.166 -> 0.279 ms)
-    if (sharers > 1 && !tune("LS_HELP") && c->d.ls_fast && c->d.mode != TJ_MODE_MULTI_COUPLED) {
-      const int owned = std::max(1, c->d.u1 - c->d.u0);
-      c->d.ls_help = t == TJ_TRANSPORT_FLAG ? std::max(1, std::min(LS_HELP_MAX, c->d.num_cu / (owned * sharers))) : 1;
-    }
+    if (sharers > 1 && !c->hp.ls_help_forced && c->d.ls_fast && c->d.mode != TJ_MODE_MULTI_COUPLED)
+      c->d.ls_help = t == TJ_TRANSPORT_FLAG ? plan_ls_help(c->d, c->hp, c->d.num_cu / sharers) : 1;   // (the planner's rule on this rank's share of the compute units)
     int wait_mode = sharers == 1 ? 1 : 0;
     if (const char* e = tune("XCH_POLL")) wait_mode = atoi(e) != 0 ? 1 : 0;
     if (t == TJ_TRANSPORT_EVENT) wait_mode = 2;   // events order the streams
@@ -369,7 +367,7 @@ int tj_group_create(const tj_params* p, int n_ranks, const int* devices, tj_grou
         // a device of their own -- off for those ranks (same bits either way)
       int sharers = 0;
       for (int b = 0; b < n_ranks; b++) sharers += g->dev[b] == g->dev[r] ? 1 : 0;
-      if (sharers > 1) { c->d.ls_help = 1; c->d.grad_bal = 0; c->lsc_wide = false; }   // (ls_help: re-decided per transport, group_select_transport)
+      if (sharers > 1) { c->d.ls_help = 1; c->d.grad_bal = 0; c->hp.lsc_wide = false; }   // (ls_help: re-decided per transport, group_select_transport)
     }
     const int nwhat = c->d.mode == TJ_MODE_MULTI_COUPLED ? 5 : 2;
     for (int w = 0; w < nwhat; w++) {

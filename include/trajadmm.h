@@ -426,6 +426,52 @@ typedef struct tj_obstacle_robot {
 } tj_obstacle_robot;
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);
 int tj_obstacle_record_size(void);   /* sizeof(tj_obstacle_robot) */
+/* ---- tj_flight_profile: where every robot is at the flight times the caller names, how fast it moves there, how far the NEAREST obstacle primitive is --
+ * with no `range`, however far -- and how far the nearest other robot is at the same time (csrc/kernels_flight_profile.h; read-only like tj_audit).  The other
+ * queries answer with one minimum per robot or pair, and only inside `range`; this one is the curve against time: what a plot of clearance and speed, a look
+ * for where a trajectory is tight, or a check of a sampled result file needs.  Every field is a function of the state alone.  Works in all three modes
+ * (single-UAV included), for clouds and meshes.  For every OWNED robot u and every time t = times[k], record out[u * n_times + k]:
+ *   time      The same real time t applies to every robot (equal flight times).  Time, segment boundaries and hover are tj_audit_timed's, unchanged:
+ *             j = the segment with T(j) <= t < T(j + 1), T(j) = (j / res) * piece_time[u] in these very expressions; j == S: the robot has arrived.
+ *             Then its position is hull_entry(S - 1, 5, .), its last control point -- the point tj_audit_timed's hover body is made of --, `segment` is S,
+ *             speed = accel = 0 and HOVER is set.  Otherwise s = clamp01((t - T(j)) / (T(j + 1) - T(j))) is the position in segment j.
+ *   position  per axis b_0 of the segment's raw hull (hull_entry's sums) restricted to [s, s] by blossoming (bez_restrict): five de Casteljau steps
+ *             (1 - s) * x + s * y.  These are the bits tj_obstacle_approach attributes to a window that starts at s.
+ *   dynamics  tj_audit's own nets, per axis v_i = 5 * (P[i+1] - P[i]), i = 0..4, and a_i = 20 * (P[i+2] - 2 * P[i+1] + P[i]), i = 0..3, each evaluated at s
+ *             by the same step (four steps for v, three for a); speed = norm3(v) / (w * pt), accel = norm3(a) / (w * w * pt * pt), w the segment's
+ *             weight, pt = piece_time[u].  At s == 0 these are tj_audit's first terms of the segment bit for bit: (1 - 0) * x + 0 * y is x.
+ *   obstacle  obs_distance = the minimum over ALL primitives of the position's distance: a cloud point p: norm3(position - p); a triangle:
+ *             |gjk({position}, triangle)|, with the limit stated for tj_obstacle_approach's hi.  Equal values go to the smallest caller index (the point
+ *             index of tj_set_cloud / the face index of tj_set_mesh).  There is no `range` argument and no TJ_ERR_CAPACITY for this call, for any obstacle
+ *             set: the walk is a nearest-neighbour descent of the box pyramid with a bounded stack, and it returns the brute-force minimum bit for bit.
+ *             No obstacles: +infinity, index -1.
+ *   robots    robot_distance = the minimum over q != u of norm3(p_u(t) - p_q(t)), every robot at its own segment or hover; equal values go to the smallest
+ *             q.  Single-UAV mode: +infinity, robot -1.
+ * times == NULL, out == NULL, n_times < 1, n_times > TJ_PROFILE_MAX_SAMPLES, uav_num * n_times > TJ_PROFILE_MAX_RECORDS, a NaN, negative or infinite time, a
+ * call before tj_init_state: TJ_ERR_INVALID, and `out` is untouched.  A plain SHARDED multi-UAV context (world > 1) returns TJ_ERR_UNSUPPORTED like
+ * tj_audit_timed: it does not hold the peers' piece_time.  tj_group_flight_profile reads control points and piece_time from the owners and is bitwise one
+ * context's (unverified across distinct devices, like the other group queries); rows of robots a context does not own are all zero.  TWO launches whatever
+ * uav_num, n_times and the number of primitives are; no host loop over samples or robots.  Changes no solver state, statistics or launch count. */
+#define TJ_PROFILE_HOVER        1   /* the robot has arrived: it stays at its last control point */
+#define TJ_PROFILE_OBS_CONTACT  2   /* obs_index >= 0 && obs_distance <= offset */
+#define TJ_PROFILE_PAIR_CONTACT 4   /* robot >= 0 && robot_distance <= offset */
+#define TJ_PROFILE_SPEED        8   /* speed >= vel_limit */
+#define TJ_PROFILE_ACCEL        16  /* accel >= acc_limit */
+#define TJ_PROFILE_MAX_SAMPLES  65536      /* n_times per call */
+#define TJ_PROFILE_MAX_RECORDS  (1 << 24)  /* uav_num * n_times per call */
+typedef struct tj_profile_sample {
+  double time;                 /* the caller's t, echoed */
+  double x, y, z;              /* position of the robot at t */
+  double obs_distance;         /* distance to the NEAREST obstacle primitive, unbounded; +infinity with no obstacles */
+  double robot_distance;       /* distance to the nearest OTHER robot's position at the same t; +infinity in single-UAV mode */
+  double speed, accel;         /* |dp/dt|, |d2p/dt2| at t; 0, 0 while hovering */
+  int obs_index;               /* caller's point index (tj_set_cloud) / face index (tj_set_mesh); -1 with no obstacles */
+  int robot;                   /* the partner; -1 in single-UAV mode */
+  int segment;                 /* the robot's segment at t; S while hovering */
+  int flags;                   /* TJ_PROFILE_* */
+} tj_profile_sample;
+int tj_flight_profile(tj_ctx* c, const double* times, int n_times, tj_profile_sample* out /* [uav_num][n_times] */);
+int tj_flight_profile_record_size(void);   /* sizeof(tj_profile_sample) */
 /* teacher forcing of the CCD / line-search stages: overwrite robot u's search direction record (direction T x 3 column-major) */
 int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_direction, double wolfe, double gn);
 
@@ -582,6 +628,7 @@ int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_r
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);   /* tj_closest_approach of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);   /* tj_pair_approach of every robot by its owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
+int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */
 /* event-timed cost of one exchange of each buffer kind (microseconds, slowest rank's average over `reps`): us[5], kinds 2..4

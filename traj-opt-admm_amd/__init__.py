@@ -35,6 +35,7 @@ EXPORTS = [
     "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
     "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
     "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
+    "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -150,6 +151,44 @@ PAIR_TOL = 1e-10           # TJ_PAIR_TOL: what tol=None selects
 PAIR_MAX_DEPTH = 40        # TJ_PAIR_MAX_DEPTH
 PAIR_FRONTIER = 64         # TJ_PAIR_FRONTIER: what max_windows=None selects
 PAIR_MAX_WINDOWS = 4096    # TJ_PAIR_MAX_WINDOWS
+
+
+class TjProfileSample(C.Structure):
+    """mirror of tj_profile_sample (include/trajadmm.h); tj_flight_profile_record_size() is its sizeof on the C side"""
+    _fields_ = [("time", C.c_double), ("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("obs_distance", C.c_double), ("robot_distance", C.c_double),
+                ("speed", C.c_double), ("accel", C.c_double), ("obs_index", C.c_int), ("robot", C.c_int), ("segment", C.c_int), ("flags", C.c_int)]
+
+
+PROFILE_FLAGS = dict(hover=1, obs_contact=2, pair_contact=4, speed=8, accel=16)
+PROFILE_MAX_SAMPLES = 65536     # TJ_PROFILE_MAX_SAMPLES
+PROFILE_MAX_RECORDS = 1 << 24   # TJ_PROFILE_MAX_RECORDS
+
+
+def profile_grid(piece_time, P, samples=None):
+    """the default time grid of flight_profile: t_k = (k / (K - 1)) * the longest robot's duration, K = samples (None: 101; K == 1: t = 0); a robot's duration is
+    log_data's sum of piece_num times 1.0 * piece_time"""
+    K = 101 if samples is None else int(samples)
+    longest = 0.0
+    for pt in np.asarray(piece_time, dtype=np.float64).ravel():
+        dur = 0.0
+        for _ in range(P):
+            dur += 1.0 * float(pt)
+        longest = max(longest, dur)
+    return np.array([(k / (K - 1)) * longest if K > 1 else 0.0 for k in range(K)], dtype=np.float64)
+
+
+def _flight_profile(call, piece_times, U, P, times, samples):
+    """shared by Solver.flight_profile / Group.flight_profile: call(times, n_times, records) -> dict of numpy arrays [U][K]"""
+    if times is None:
+        times = profile_grid(piece_times(), P, samples)
+    elif samples is not None:
+        raise ValueError("flight_profile: give times or samples, not both")
+    t = np.ascontiguousarray(times, dtype=np.float64).ravel()
+    K = t.size
+    rec = (TjProfileSample * max(U * K, 1))()
+    call(_d(t), C.c_int(K), rec)
+    a = np.frombuffer(rec, dtype=np.dtype(TjProfileSample), count=U * K).reshape(U, K)
+    return {n: np.array(a[n], dtype=np.float64 if ty is C.c_double else np.int32) for n, ty in TjProfileSample._fields_}
 
 
 def merge_pairs(rows, rng, offset):
@@ -660,6 +699,22 @@ class Solver:
         sharded solver (world > 1) answers for its owned robots, the other records are zero."""
         return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_obstacle_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
+    def piece_times(self):
+        """piece_time of every robot as this context holds it"""
+        out = np.zeros(self.U)
+        for u in range(self.U):
+            pt = C.c_double()
+            self._check(self.lib.tj_get_state(self._ctx, C.c_int(u), None, None, None, None, None, C.byref(pt)))
+            out[u] = pt.value
+        return out
+
+    def flight_profile(self, times=None, samples=None):
+        """tj_flight_profile: per robot and flight time the position, the distance and caller's index of the NEAREST obstacle primitive (no range: however far),
+        the distance and index of the nearest other robot at the same time, speed, acceleration, segment (S: arrived) and flags (PROFILE_FLAGS).  times: real
+        times >= 0 [K]; None: profile_grid over the longest robot's duration with K = samples (None: 101).  Dict of numpy arrays [U][K].  Read-only.  All
+        modes; a sharded multi-UAV solver (world > 1) raises (TJ_ERR_UNSUPPORTED): use Group.flight_profile."""
+        return _flight_profile(lambda t, n, rec: self._check(self.lib.tj_flight_profile(self._ctx, t, n, rec)), self.piece_times, self.U, self.P, times, samples)
+
     def build_info(self):
         ms, dev = C.c_double(), C.c_int()
         self._check(self.lib.tj_get_build_info(self._ctx, C.byref(ms), C.byref(dev)))
@@ -787,6 +842,19 @@ class Group:
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""
         return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_group_obstacle_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+
+    def piece_times(self):
+        """piece_time of every robot from the rank that owns it"""
+        out = np.zeros(self.U)
+        for u in range(self.U):
+            pt = C.c_double()
+            self._check(self.lib.tj_group_get_state(self._g, C.c_int(u), None, None, None, None, None, C.byref(pt)))
+            out[u] = pt.value
+        return out
+
+    def flight_profile(self, times=None, samples=None):
+        """tj_group_flight_profile: Solver.flight_profile of every robot from the rank that owns it (bitwise one context's)"""
+        return _flight_profile(lambda t, n, rec: self._check(self.lib.tj_group_flight_profile(self._g, t, n, rec)), self.piece_times, self.U, self.P, times, samples)
 
     def close(self):
         if getattr(self, "_g", None) and self._g.value:

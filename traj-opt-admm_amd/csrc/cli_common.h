@@ -243,4 +243,16 @@ inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   else std::cout << "obstacle fleet hi " << rec[who].hi << " uav " << who << " id " << rec[who].index << " time " << rec[who].time << " contact " << contact << std::endl;
 }
 
+// --flight-profile: one line per robot and sample, robot after robot; `word`: the lines start with "profile " (standard output, next to the other queries' lines)
+inline void print_flight_profile(const std::vector<tj_profile_sample>& rec, int U, int K, std::ostream& os, bool word) {
+  os.precision(17);
+  for (int u = 0; u < U; u++)
+    for (int k = 0; k < K; k++) {
+      const tj_profile_sample& r = rec[(size_t)u * K + k];
+      os << (word ? "profile " : "") << u << " " << r.time << " " << r.x << " " << r.y << " " << r.z << " " << r.obs_distance << " " << r.obs_index << " " << r.robot_distance << " "
+         << r.robot << " " << r.speed << " " << r.accel << " " << r.flags << "\n";
+    }
+  os.flush();
+}
+
 }  // namespace tjcli

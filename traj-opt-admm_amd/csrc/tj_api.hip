@@ -37,6 +37,7 @@
 #include "kernels_closest.h"
 #include "kernels_obstacle_approach.h"
 #include "kernels_pair_approach.h"
+#include "kernels_flight_profile.h"
 #include "host_plan.h"
 
 using namespace tj;
@@ -97,7 +98,7 @@ struct tj_ctx {
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
-  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach): every buffer is allocated by the first call that needs it, and a call
+  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_flight_profile): every buffer is allocated by the first call that needs it, and a call
   // whose allocations failed partway keeps what it got (query_buf).  Each query ends in a stream synchronise, so no two are in flight on one context, and they share: q_ctl, the
   // control block the BVH walk reports its overflow bit to (never the solver's); q_net [U][3][T] and q_pt [U], the staged copy of the control nets and piece times a group hands
   // in; q_order (sorted primitive -> caller's index), which belongs to the obstacle set and goes with it (cloud_allocs).  Per query: its rows / lists / counters and its records.
@@ -110,6 +111,9 @@ struct tj_ctx {
   // largest call so far (pair_cap, pair_mw) and lives in pair_allocs
   PairArgs pair{}; tj_pair_record* pair_out = nullptr;
   std::vector<void*> pair_allocs; int pair_cap = -1, pair_mw = 0;
+  // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
+  ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
+  std::vector<void*> profile_allocs; int profile_cap = 0;
 };
 
 // EVERY environment switch of the library is read through this one function (tj_group.h included): TJ_TUNE="KEY=value,KEY=value" or, equivalently, TJ_KEY=value
@@ -760,6 +764,7 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->allocs) hipFree(p);
   for (void* p : c->cloud_allocs) hipFree(p);
   for (void* p : c->pair_allocs) hipFree(p);
+  for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1293,7 +1298,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }
 
 namespace {
-// ---- the read-only queries: one path for the five (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h) ----
+// ---- the read-only queries: one path for the six (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_flight_profile.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1489,6 +1494,46 @@ int pair_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows
   if (*n > cap && rows) { c->err = "tj_pair_approach: " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
   return TJ_OK;
 }
+
+// tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
+int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
+  if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
+  const Dev& d = c->d;
+  if (n_times > TJ_PROFILE_MAX_SAMPLES || (long long)d.U * n_times > (long long)TJ_PROFILE_MAX_RECORDS) {
+    c->err = "tj_flight_profile: n_times must be 1.." + std::to_string(TJ_PROFILE_MAX_SAMPLES) + " and uav_num * n_times at most " + std::to_string(TJ_PROFILE_MAX_RECORDS);
+    return TJ_ERR_INVALID;
+  }
+  for (int k = 0; k < n_times; k++)
+    if (!(times[k] >= 0.0) || times[k] == INFINITY) { c->err = "tj_flight_profile: times[" + std::to_string(k) + "] is NaN, negative or infinite"; return TJ_ERR_INVALID; }
+  int r;
+  if ((r = query_state(c, "tj_flight_profile", true, net_host && pt_host))) return r;
+  const int owned = d.u1 - d.u0, K = n_times;
+  const size_t recs = (size_t)d.U * K;
+  QUIESCE(c);
+  ProfileArgs& b = c->profile;
+  if (K > c->profile_cap) {   // grow: the context is quiet, nothing reads the old buffers
+    for (void* p : c->profile_allocs) hipFree(p);
+    c->profile_allocs.clear();
+    b.times = nullptr; b.pos = nullptr; c->profile_out = nullptr; c->profile_cap = 0;
+    std::vector<void*>* l = &c->profile_allocs;
+    if ((r = query_buf(c, b.times, (size_t)K, l)) || (r = query_buf(c, b.pos, recs * 3, l)) || (r = query_buf(c, c->profile_out, recs, l))) return r;
+    c->profile_cap = K;
+  }
+  if ((r = ensure_order(c))) return r;
+  ProfileArgs a = b;
+  if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt)) || (r = upload(c, a.times, times, (size_t)K * 8))) return r;
+  a.order = c->q_order; a.K = K;
+  a.cap = d.N > 0 ? 64 + 8 * (d.nlevels - 1) : 1;   // the walk's stack per sample: the top level and eight per level below it (kernels_flight_profile.h)
+  if ((r = query_clear(c, c->profile_out, recs))) return r;
+  // two launches whatever the fleet's size, the number of samples and the number of primitives
+  hipLaunchKernelGGL(k_profile_points, dim3((unsigned)((recs + FP_THREADS - 1) / FP_THREADS)), dim3(FP_THREADS), 0, c->stream, d, a, c->profile_out);
+  if (owned > 0)
+    with_prim(d, [&](auto prim) {
+      hipLaunchKernelGGL(k_profile_nearest<decltype(prim)::value>, dim3((unsigned)(((size_t)owned * K + 7) / 8)), dim3(64), (size_t)8 * a.cap * sizeof(unsigned long long), c->stream, d, a, c->profile_out);
+    });
+  if ((r = query_fetch(c, out, c->profile_out, recs))) return r;
+  return query_finish(c, nullptr);
+}
 }  // namespace
 
 int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) { return audit_run(c, range, nullptr, out, seg_obs, seg_pair); }
@@ -1532,6 +1577,8 @@ int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int
   return query_finish(c, "tj_obstacle_approach");
 }
 int tj_obstacle_record_size(void) { return (int)sizeof(tj_obstacle_robot); }
+int tj_flight_profile(tj_ctx* c, const double* times, int n_times, tj_profile_sample* out) { return profile_run(c, times, n_times, nullptr, nullptr, out); }
+int tj_flight_profile_record_size(void) { return (int)sizeof(tj_profile_sample); }
 
 int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_armijo) {
   if (!c) return TJ_ERR_INVALID;

@@ -690,4 +690,19 @@ int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_de
     return tj_obstacle_approach(c, range, tol, max_depth, max_windows, part); });
 }
 
+// the owners' rows [n_times] per robot; control points and piece_time from the owners, so every rank places the whole fleet as one context would
+int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out) {
+  if (!g || !times || !out || n_times < 1) return TJ_ERR_INVALID;
+  const Dev& d0 = g->ctx[0]->d;
+  if (n_times > TJ_PROFILE_MAX_SAMPLES || (long long)d0.U * n_times > (long long)TJ_PROFILE_MAX_RECORDS) return TJ_ERR_INVALID;   // (before the scratch copy is sized)
+  std::vector<tj_profile_sample> part(g->n > 1 ? (size_t)d0.U * n_times : 0);
+  return group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    if (part.empty()) return profile_run(c, times, n_times, net, pt, out);
+    const int rc = profile_run(c, times, n_times, net, pt, part.data());
+    if (rc < 0) return rc;
+    std::copy(part.begin() + (size_t)c->d.u0 * n_times, part.begin() + (size_t)c->d.u1 * n_times, out + (size_t)c->d.u0 * n_times);
+    return (int)TJ_OK;
+  });
+}
+
 }  // extern "C"

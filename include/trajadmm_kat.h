@@ -30,8 +30,16 @@ int tj_kat_planes(tj_ctx* c, int what, int n, const double* P, const double* Q, 
 /* CCD::GJKCCD / SelfGJKCCD (CCD.h:116,227) on swept hulls, tu[n][2] = (tMax, _tMax): out[n][2] booleans */
 int tj_kat_ccd(tj_ctx* c, int n, const double* P, const double* D, const double* Q, const double* E, const double* q, const double* tu, double d, double* out);
 /* broad phase alone (replaces aabb::Tree::query(AABB, margin), AABB.cc:829-839 / :608-667, on the tree of BVH::InitPointcloud or
- * BVH::InitObstacle): boxes[nq][6] = lo.xyz, hi.xyz; counts[nq]; ids[nq][cap] = indices into the caller's cloud / face list */
+ * BVH::InitObstacle): boxes[nq][6] = lo.xyz, hi.xyz; counts[nq]; ids[nq][cap] = indices into the caller's cloud / face list.
+ * A box whose walk overflows the frontier (FRONT_CAP boxes on one level), or that finds more than cap candidates, makes the call return TJ_ERR_CAPACITY.
+ * That is an error of this call alone: the walk reports it through the read-only queries' control block, the solver's error word stays clear and the
+ * context goes on answering.  Pending work of the context is waited for before the queries are launched. */
 int tj_kat_query(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int* counts, int* ids);
+/* the same in each form of the walk the product kernels instantiate: unroll = 4 (the plane query) or 1 (the CCD query, the audit, the obstacle-approach seeds,
+ * the planner); pre != 0: the lane's top-level box is fetched ahead of the query box and handed to the walk (the plane and CCD queries).  tj_kat_query is
+ * unroll 4, pre 0.  ids come in the walk's own order: positions of the build's sorted order, ascending.  A frontier overflow is TJ_ERR_CAPACITY of this call
+ * alone (reported through the read-only queries' control block): the context stays usable. */
+int tj_kat_query_form(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int unroll, int pre, int* counts, int* ids);
 /* triangle obstacle bodies (tj_set_mesh): P, D [n][6][3] hull and direction hull, tri[n][3][3], t[n] step; out[n][8] =
  * plane ok, cx, cy, cz, d of Separate::opengjk with a 3-vertex body at distance dist | CCD::KDOPDCD(P, tri, dist) |
  * CCD::KDOPDCD({P, P + t D}, tri, off) | CCD::GJKDCD({P, P + t D}, tri, off)  -- the predicates Step::mix_step uses (Step.h:390-404) */

@@ -240,7 +240,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_linalg", "tj_kat_plan"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -638,11 +638,15 @@ class Solver:
         self._check(self.lib.tj_kat_ccd(self._ctx, C.c_int(n), *[_d(x) for x in arrs], C.c_double(d), _d(out)))
         return out
 
-    def kat_query(self, boxes, margin, cap=2048, sort=True):
-        """raw broad-phase candidate SETS of caller-supplied query boxes [nq][6] (lo, hi): list of sorted id arrays"""
+    def kat_query(self, boxes, margin, cap=2048, sort=True, unroll=4, pre=False):
+        """raw broad-phase candidate SETS of caller-supplied query boxes [nq][6] (lo, hi): list of sorted id arrays (sort=False: in the walk's own order).
+        unroll / pre: the form of the walk (tj_kat_query_form: 4 / False is the plane query's walk without a prefetched top box, tj_kat_query)"""
         boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)
         nq = boxes.shape[0]; counts = np.zeros(nq, dtype=np.int32); ids = np.zeros((nq, cap), dtype=np.int32)
-        self._check(self.lib.tj_kat_query(self._ctx, C.c_int(nq), _d(boxes), C.c_double(margin), C.c_int(cap), _i(counts), _i(ids)))
+        if unroll == 4 and not pre:     # (tj_kat_query is tj_kat_query_form at 4 / 0: called by its own name so that both exports stay exercised)
+            self._check(self.lib.tj_kat_query(self._ctx, C.c_int(nq), _d(boxes), C.c_double(margin), C.c_int(cap), _i(counts), _i(ids)))
+        else:
+            self._check(self.lib.tj_kat_query_form(self._ctx, C.c_int(nq), _d(boxes), C.c_double(margin), C.c_int(cap), C.c_int(unroll), C.c_int(bool(pre)), _i(counts), _i(ids)))
         return [np.sort(ids[q, :counts[q]]) if sort else ids[q, :counts[q]].copy() for q in range(nq)]
 
     def kat_tri(self, P, D, tri, t, dist, off):

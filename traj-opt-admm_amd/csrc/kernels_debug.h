@@ -170,23 +170,26 @@ __global__ __launch_bounds__(64) void k_dbg_tri(Dev D, int n, const double* P, c
 }
 
 // broad-phase known answers: one wavefront per caller-supplied query box, raw candidate list (sorted primitive indices,
-// traversal order) of aabb::Tree::query(box, margin) (AABB.cc:608-667) on the static BVH
-template <int PRIM>
+// traversal order) of aabb::Tree::query(box, margin) (AABB.cc:608-667) on the static BVH.  The walk in each of the forms the product kernels instantiate:
+// BQ_UNROLL 4 (k_front) or 1 (k_ccd, the audit, the seeds, the planner); PRE: the lane's top-level box fetched ahead of the query box and handed in (k_front, k_ccd)
+template <int PRIM, int BQ_UNROLL, bool PRE>
 __global__ __launch_bounds__(64) void k_dbg_query(Dev D, int nq, const double* boxes, double m, int cap, int* out_ids, int* out_n) {
   const int b = blockIdx.x;
   if (b >= nq) return;
   __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  TopBox topb{};
+  if constexpr (PRE) topb = bvh_top_box(D);
   QBox q;
   for (int k = 0; k < 3; k++) { q.lo[k] = boxes[6 * (size_t)b + k]; q.hi[k] = boxes[6 * (size_t)b + 3 + k]; }
   int base = 0;
   unsigned long long visits = 0;
-  bvh_query<4, PRIM>(D, q, m, fa, fb, cand, &visits, [&](int pt) {
+  bvh_query<BQ_UNROLL, PRIM>(D, q, m, fa, fb, cand, &visits, [&](int pt) {
     const bool ok = pt >= 0;
     const unsigned long long mask = ballot(ok);
     const int idx = base + prefix_count(mask);
     if (ok && idx < cap) out_ids[(size_t)b * cap + idx] = pt;
     base += __popcll(mask);
-  });
+  }, PRE ? &topb : nullptr);
   if (lane_id() == 0) out_n[b] = base;
 }
 

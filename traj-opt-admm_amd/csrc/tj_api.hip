@@ -1933,23 +1933,42 @@ int tj_kat_ccd(tj_ctx* c, int n, const double* P, const double* D, const double*
   return TJ_OK;
 }
 
-int tj_kat_query(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int* counts, int* ids) {
-  if (!c || nq < 0 || cap < 1 || !boxes || !counts || !ids) return TJ_ERR_INVALID;
-  if (!c->have_cloud) { c->err = "tj_kat_query: set the obstacles first"; return TJ_ERR_INVALID; }
+// The walk reports a frontier overflow to the queries' control block (walk_dev), as every read-only query does: a deliberate overflow here is this call's error
+// and leaves the solver's error word, and with it the context, as it was.  `who`: the entry point the call came in through (the error texts name it).
+static int kat_query_run(tj_ctx* c, const char* who, int nq, const double* boxes, double margin, int cap, int unroll, int pre, int* counts, int* ids) {
+  if (!c || nq < 0 || cap < 1 || !boxes || !counts || !ids || (unroll != 1 && unroll != 4)) return TJ_ERR_INVALID;
+  if (!c->have_cloud) { c->err = std::string(who) + ": set the obstacles first"; return TJ_ERR_INVALID; }
   DevBuf db, di, dn; int r;
   if ((r = to_dev(c, db, boxes, (size_t)nq * 48)) || (r = to_dev(c, di, nullptr, (size_t)nq * cap * 4)) || (r = to_dev(c, dn, nullptr, (size_t)nq * 4))) return r;
-  if (c->d.prim == 3) hipLaunchKernelGGL((k_dbg_query<3>), dim3(std::max(nq, 1)), dim3(64), 0, c->stream, c->d, nq, (const double*)db.p, margin, cap, (int*)di.p, (int*)dn.p);
-  else hipLaunchKernelGGL((k_dbg_query<1>), dim3(std::max(nq, 1)), dim3(64), 0, c->stream, c->d, nq, (const double*)db.p, margin, cap, (int*)di.p, (int*)dn.p);
-  HIPCHK(c, hipGetLastError());
   QUIESCE(c);
+  Dev da;
+  if ((r = walk_dev(c, da))) return r;
+  with_prim(c->d, [&](auto prim) {
+    constexpr int PR = decltype(prim)::value;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(std::max(nq, 1)), dim3(64), 0, c->stream, da, nq, (const double*)db.p, margin, cap, (int*)di.p, (int*)dn.p); };
+    if (unroll == 4) { if (pre) go(k_dbg_query<PR, 4, true>); else go(k_dbg_query<PR, 4, false>); }
+    else { if (pre) go(k_dbg_query<PR, 1, true>); else go(k_dbg_query<PR, 1, false>); }
+  });
+  if ((r = query_finish(c, who))) {
+    if (r == TJ_ERR_CAPACITY)   // (query_finish words it for a trajectory query: a segment and a `range`; here the caller gave boxes and a margin)
+      c->err = std::string(who) + ": the BVH frontier of one of the " + std::to_string(nq) + " query boxes overflowed at margin " + std::to_string(margin) + " (more than " + std::to_string(FRONT_CAP) +
+               " boxes of one level within the margin of the query box): ask with smaller boxes or a smaller margin";
+    return r;
+  }
   if (nq == 0) return TJ_OK;
   HIPCHK(c, hipMemcpy(counts, dn.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(ids, di.p, (size_t)nq * cap * 4, hipMemcpyDeviceToHost));
   for (int q = 0; q < nq; q++) {
-    if (counts[q] > cap) { c->err = "tj_kat_query: a query returned more candidates than cap"; return TJ_ERR_CAPACITY; }
+    if (counts[q] > cap) { c->err = std::string(who) + ": query box " + std::to_string(q) + " returned " + std::to_string(counts[q]) + " candidates, more than cap = " + std::to_string(cap); return TJ_ERR_CAPACITY; }
     for (int i = 0; i < counts[q]; i++) ids[(size_t)q * cap + i] = c->cloud_order[ids[(size_t)q * cap + i]];
   }
   return check_device_errors(c);
+}
+int tj_kat_query_form(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int unroll, int pre, int* counts, int* ids) {
+  return kat_query_run(c, "tj_kat_query_form", nq, boxes, margin, cap, unroll, pre, counts, ids);
+}
+int tj_kat_query(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int* counts, int* ids) {   // the plane query's form, no prefetched top box
+  return kat_query_run(c, "tj_kat_query", nq, boxes, margin, cap, 4, 0, counts, ids);
 }
 
 int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double* tri, const double* t, double dist, double off, double* out) {

@@ -363,6 +363,95 @@ typedef struct tj_pair_record {
 } tj_pair_record;
 int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);
 int tj_pair_record_size(void);   /* sizeof(tj_pair_record) */
+/* ---- tj_path_crossings: where the PATHS of two robots meet in space, whatever the time, and when each of the two is there
+ * (csrc/kernels_path_crossing.h; read-only like tj_pair_approach).  Every other robot-against-robot query pairs the robots at equal segment indices (tj_audit)
+ * or at equal real time (tj_audit_timed, tj_closest_approach, tj_pair_approach, tj_flight_profile): a fleet they all certify may still have two paths through one
+ * point a few tenths of a second apart, safe only while every vehicle keeps its timetable.  Here the two flown curves are compared AS CURVES, with no reference
+ * to time: one row per UNORDERED pair (u, q), u < q, u owned, whose minimum over all x on u's curve and all y on q's of |x - y| may lie below `range`.
+ * A pair with CLEAR is separated in space: no timing error brings the two into contact.  A pair with CONTACT is separated by timing only, and
+ * partner_time - time is the margin of that timing.  For one pair:
+ *   item     (tr, j, [sa, sb], [ra, rb]): a window of segment tr of u and a window of segment j of q, both in the segments' local parameters in [0, 1].
+ *            Windows are dyadic, so halving at 0.5 * (sa + sb) and 0.5 * (ra + rb) is exact, and with max_depth <= 40 no item is ever unsplittable: there
+ *            are no terminal items (as in tj_obstacle_approach).
+ *   nets     a_0..a_5 = u's raw hull of segment tr (hull_entry's sums) restricted to [sa, sb] by blossoming (bez_restrict), b_0..b_5 = q's of segment j
+ *            restricted to [ra, rb]; always from the RAW hulls, never from a parent's net: rounding does not accumulate with depth.  [0, 1] returns the raw
+ *            hull bit for bit.
+ *   lo(W)    |v|, v = gjk(conv{a_i}, conv{b_k}) with u's net as body 1 (the lower robot index goes first: plane_pair's order), where v SEPARATES the two:
+ *            v . (a_i - b_k) > 0 for all 36 vertex pairs, evaluated as (v.x * dx + v.y * dy) + v.z * dz.  Otherwise lo(W) = 0, and the item is never
+ *            dropped, only split (tj_closest_approach's certificate and its reason: the GJK's contact floor).
+ *   hi(W)    the smallest of the four distances norm3(a_i - b_k), i, k in {0, 5}: points of the two curves, at s = sa or sb and partner_s = ra or rb.
+ *            Candidates and bests are ordered by the total order (hi, segment, partner_segment, s, partner_s).
+ *   seeds    for every (tr, j) the pair of full windows [0, 1] x [0, 1] whose raw hull boxes are within `range` of each other on every axis (the box test
+ *            of tj_audit's robot pairs, with its guard: a gap above range * 1.000001 + 1e-9 on an axis skips the seed).
+ *   listed   (u, q) has a row if and only if some seed has lo < range or hi < range.  A pair without a row is certified at least `range` apart in space.
+ *   search   best = the pair's smallest hi < range over the seeds; live = {lo < range and lo < best.hi}.  A round splits every live item into its four
+ *            quadrants (both windows halved), evaluates all children, updates best over the whole round, and keeps the children with lo < best.hi --
+ *            strict, against the round's FINAL best, so that every field (`windows` and `depth` included) is a function of the state alone.
+ *   bracket  lo = min(best.hi, min of lo over the live set), hi = best.hi.
+ *   stop     hi - lo <= tol (CONVERGED) | the live set is empty (CONVERGED) | depth == max_depth | the live set of this pair after a round, or after the
+ *            seeding, holds more than max_windows (TRUNCATED: the record is that of the last completed round -- for the seeds their own bracket with
+ *            depth 0; `windows` counts the work of the overflowing round too).
+ *   record   lo <= the minimum distance of the two paths <= hi.  hi is the distance of u's curve at parameter `s` of `segment` from q's curve at `partner_s` of
+ *            `partner_segment`.  time = ((segment + s) / res) * piece_time[robot] and partner_time = ((partner_segment + partner_s) / res) *
+ *            piece_time[partner] -- tj_obstacle_approach's expression for a time -- say when each robot is at that place.  Listed for its lo only (no sample
+ *            below range): segments -1, parameters and times -1.0, hi == range.  depth: rounds completed.  windows: seeds evaluated + 4 per split item.
+ *   rows     sorted by (robot, partner) ascending; neither the order of evaluation nor that of any atomic append is visible in the output.
+ * ROBOT_END / PARTNER_END: the hi sample is that robot's LAST control point (segment == S - 1, parameter == 1.0).  The robot stays at that point after
+ * arriving (tj_audit_timed's hover), so partner_time - time then UNDERSTATES how long the two are near: the other robot must not pass that place at any
+ * later time either.
+ * *n is the number of listed pairs.  *n > cap: TJ_ERR_CAPACITY, the first `cap` rows in order have been written and *n says what to allocate; cap = 0 with
+ * rows == NULL is a valid count-only call.  range <= 0: offset + 2 * margin; +infinity is valid.  tol < 0: TJ_CROSSING_TOL; 0 is valid.  max_depth < 0:
+ * TJ_CROSSING_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0: TJ_CROSSING_FRONTIER; above TJ_CROSSING_MAX_WINDOWS TJ_ERR_INVALID.  NaN range or tol,
+ * n == NULL, cap < 0, rows == NULL with cap > 0, a call before tj_init_state: TJ_ERR_INVALID.  Single-UAV mode: *n = 0 and TJ_OK.  A plain SHARDED context
+ * (world > 1) returns TJ_ERR_UNSUPPORTED like tj_pair_approach: it does not hold the peers' piece_time.  tj_group_path_crossings computes the rows (u, q > u)
+ * on u's owner with control points and piece_time read from the owners, and is bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, and is a function of cap and max_windows alone (nothing is sized by S^2: the pair's
+ * kernel enumerates its own (tr, j) box tests):
+ *   cap * (2 * max_windows * 48 + 4 * max_windows * 8 + 8 + 80) bytes     (live lists, their children's lo, the slots' pairs and the rows)
+ * plus the bitmask and its offsets, owned * ceil(uav_num / 32) * 8 bytes.  A call whose figure exceeds TJ_CROSSING_MAX_BYTES is refused up front with
+ * TJ_ERR_INVALID: lower cap (rows beyond it are counted, not lost) or max_windows.
+ * At most THREE launches whatever the fleet's size, the number of pairs and the depth (two for a count-only call); no host loop over robots, pairs or
+ * rounds.  Changes no solver state, statistics or launch count.
+ * STATED LIMITS.  (1) A certified lo is the GJK's |v|, up to 1e-10 |v| relative above the hulls' distance (tj_obstacle_approach's limit, unchanged).
+ * (2) Where the paths truly meet no window around the meeting point has a certificate: lo = 0 and hi falls by about half per round, so such a row ends at
+ * max_depth or at hi <= tol, with CONTACT long before.  (3) Paths that run ALONGSIDE each other have a valley instead of a point: the live set grows with
+ * the depth and the row is TRUNCATED with the last bracket, which is still sound.
+ * The defaults are measured (tests/path_crossing_ref.py default_tolerance, the restatement, on the CPU): tol = 0 and max_depth = 40 at the default range on the
+ * final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz, e2e_scn_b_coupled.npz and of e2e_scn_c3.npz with z set to 0 (the fleets are stacked in z; flattened
+ * they cross); per depth the largest hi - lo over the listed pairs:
+ *   depth   0        1        2        3        4        5        6        7        8        9        10       11       12       13       14       15       16       17       18       19       20       21       22       23       24       25       26       27       28       29       30       31       32       33       34       35       36       37       38       39       40
+ *   width   5.07e-2  4.69e-2  4.68e-2  3.94e-2  1.97e-2  1.04e-2  5.66e-3  2.84e-3  1.39e-3  7.06e-4  3.38e-4  1.62e-4  9.10e-5  4.26e-5  2.13e-5  1.14e-5  5.37e-6  2.68e-6  1.33e-6  6.76e-7  3.38e-7  1.76e-7  8.58e-8  4.40e-8  2.17e-8  1.07e-8  5.32e-9  2.76e-9  1.32e-9  6.83e-10 3.32e-10 1.66e-10 8.17e-11 4.20e-11 2.04e-11 1.04e-11 5.38e-12 2.75e-12 1.36e-12 6.63e-13 3.34e-13
+ * and the same over the rows that are NOT in contact (hi > offset: the pairs separated in space, whose bracket closes on a positive distance):
+ *   apart   2.15e-2  3.62e-3  1.36e-3  6.39e-4  5.78e-4  1.01e-4  2.07e-5  8.51e-6  2.15e-6  5.07e-7  1.12e-7  3.27e-8  8.06e-9  1.61e-9  5.09e-10 1.12e-10 3.01e-11 7.21e-12 0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0        0
+ *   state                 listed pairs   rows in contact   largest live set of any pair at any depth
+ *   e2e_scn_b (8 UAVs)    7              0                 6
+ *   e2e_scn_c3 (64 UAVs)  63             0                 53
+ *   e2e_scn_b_coupled     7              0                 7
+ *   e2e_scn_c3_flat       2016           2016              59
+ * A row in contact never closes its bracket where the paths meet (limit 2): its width is hi, halved per round down to 3.34e-13 at depth 40.  The rows that
+ * are not in contact shrink all the way: their last positive width is 7.21e-12 at depth 17, and TJ_CROSSING_TOL is the smallest power of ten >= 10 x that.
+ * TJ_CROSSING_FRONTIER is the next power of two >= 4 x the largest live set (59: stacked neighbours, which run alongside each other, hold up to 53 before their
+ * bracket closes; the flattened fleet's 2016 crossings hold at most 59), and at least 64.  The listed pairs are what `cap` has to hold at the default range: about one per robot
+ * on a fleet stacked in z, every pair where all paths cross. */
+#define TJ_CROSSING_CONTACT     1    /* a sample was found and hi <= offset: the PATHS are within offset in space; the pair's separation rests on timing */
+#define TJ_CROSSING_CLEAR       2    /* lo > offset: no timing error brings these two into contact */
+#define TJ_CROSSING_CONVERGED   4    /* hi - lo <= tol, or nothing was left that could hold a smaller distance */
+#define TJ_CROSSING_TRUNCATED   8    /* the pair's live set outgrew max_windows: the bracket of the last completed round is returned */
+#define TJ_CROSSING_ROBOT_END   16   /* the hi sample is robot's last control point: it stays there after arriving */
+#define TJ_CROSSING_PARTNER_END 32   /* the same for partner */
+#define TJ_CROSSING_MAX_DEPTH 40
+#define TJ_CROSSING_FRONTIER  256
+#define TJ_CROSSING_MAX_WINDOWS 4096
+#define TJ_CROSSING_MAX_BYTES (1ll << 31)
+#define TJ_CROSSING_TOL 1e-10
+typedef struct tj_crossing_record {
+  double lo, hi;                  /* lo <= min distance of robot's path from partner's path <= hi */
+  double s, partner_s;            /* local parameters of the hi sample in `segment` and `partner_segment` */
+  double time, partner_time;      /* when robot / partner is at the hi sample; partner_time - time is the timing margin of the crossing */
+  int robot, partner, segment, partner_segment, depth, flags, windows, reserved;
+} tj_crossing_record;
+int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n);
+int tj_crossing_record_size(void);   /* sizeof(tj_crossing_record) */
 /* ---- tj_obstacle_approach: how close the FLOWN CURVE of every robot comes to an obstacle primitive, when, and to which one, converged to a tolerance the
  * caller names (csrc/kernels_obstacle_approach.h; read-only like tj_audit).  tj_audit's obs_clearance is the distance of a segment's 6-point hull: what the
  * solver constrains and the right certificate for a converged state, but only a lower bound on what the vehicle does, without a time, and on the GJK's
@@ -627,6 +716,7 @@ int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_o
 int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi);   /* tj_audit_timed of every robot by its owner; every robot's control points AND piece_time are read from its owner: bitwise one context's */
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);   /* tj_closest_approach of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);   /* tj_pair_approach of every robot by its owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
+int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n);   /* tj_path_crossings of every pair (u, q > u) by u's owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */

@@ -35,6 +35,7 @@ EXPORTS = [
     "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
     "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
     "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
+    "tj_path_crossings", "tj_crossing_record_size", "tj_group_path_crossings",
     "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
 ]
 
@@ -153,6 +154,20 @@ PAIR_FRONTIER = 64         # TJ_PAIR_FRONTIER: what max_windows=None selects
 PAIR_MAX_WINDOWS = 4096    # TJ_PAIR_MAX_WINDOWS
 
 
+class TjCrossingRecord(C.Structure):
+    """mirror of tj_crossing_record (include/trajadmm.h); tj_crossing_record_size() is its sizeof on the C side"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("s", C.c_double), ("partner_s", C.c_double), ("time", C.c_double), ("partner_time", C.c_double),
+                ("robot", C.c_int), ("partner", C.c_int), ("segment", C.c_int), ("partner_segment", C.c_int), ("depth", C.c_int), ("flags", C.c_int),
+                ("windows", C.c_int), ("reserved", C.c_int)]
+
+
+CROSSING_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8, robot_end=16, partner_end=32)
+CROSSING_TOL = 1e-10           # TJ_CROSSING_TOL: what tol=None selects
+CROSSING_MAX_DEPTH = 40        # TJ_CROSSING_MAX_DEPTH
+CROSSING_FRONTIER = 256        # TJ_CROSSING_FRONTIER: what max_windows=None selects
+CROSSING_MAX_WINDOWS = 4096    # TJ_CROSSING_MAX_WINDOWS
+
+
 class TjProfileSample(C.Structure):
     """mirror of tj_profile_sample (include/trajadmm.h); tj_flight_profile_record_size() is its sizeof on the C side"""
     _fields_ = [("time", C.c_double), ("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("obs_distance", C.c_double), ("robot_distance", C.c_double),
@@ -233,6 +248,21 @@ def _pair_approach(call, params, range, tol, max_depth, max_windows, symmetric):
         return rows
     rng = float(range) if range is not None and range > 0 else params["offset"] + 2 * params["margin"]
     return merge_pairs(rows, rng, params["offset"])
+
+
+def _path_crossings(call, range, tol, max_depth, max_windows):
+    """shared by Solver.path_crossings / Group.path_crossings: call(range, tol, max_depth, max_windows, rows, cap, n).  The count-only call first, then the
+    rows; `gap` = partner_time - time, the timing margin of the crossing (0.0 where the pair is listed for its lo only)."""
+    args = (C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
+            C.c_int(0 if max_windows is None else int(max_windows)))
+    n = C.c_int(0)
+    call(*args, None, C.c_int(0), C.byref(n))
+    rec = (TjCrossingRecord * max(n.value, 1))()
+    if n.value:
+        call(*args, rec, C.c_int(n.value), C.byref(n))
+    rows = _records(TjCrossingRecord, rec[:n.value])
+    rows["gap"] = rows["partner_time"] - rows["time"]
+    return rows
 
 
 class TrajAdmmError(RuntimeError):
@@ -696,6 +726,14 @@ class Solver:
         return _pair_approach(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_pair_approach(self._ctx, r, t, d, w, rows, cap, n)), self.params,
                               range, tol, max_depth, max_windows, symmetric)
 
+    def path_crossings(self, range=None, tol=None, max_depth=None, max_windows=None):
+        """tj_path_crossings: one row per UNORDERED pair robot < partner whose PATHS come within `range` in space, whatever the time (a pair without a row is
+        certified at least `range` apart in space): lo <= the paths' distance <= hi converged to `tol` (None: CROSSING_TOL) by the pair's own branch and
+        bound, `segment` / `s` / `time` and `partner_segment` / `partner_s` / `partner_time` of the hi sample on either path, `gap` = partner_time - time
+        (the timing margin of the crossing), `depth`, `windows`, `flags` (CROSSING_FLAGS).  Dict of numpy arrays [n], sorted by (robot, partner).  Read-only.
+        A sharded solver (world > 1) raises: use Group.path_crossings."""
+        return _path_crossings(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_path_crossings(self._ctx, r, t, d, w, rows, cap, n)), range, tol, max_depth, max_windows)
+
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_obstacle_approach: per robot lo <= closest approach of the FLOWN CURVE to any obstacle primitive <= hi, converged to `tol` (None: OBSTACLE_TOL)
         by a branch and bound over windows of the segments' hulls; `time`, `index` (the caller's point / face index), `segment` of the hi sample (-1 where
@@ -842,6 +880,10 @@ class Group:
         """tj_group_pair_approach: Solver.pair_approach from the ranks that own the robots, in (robot, partner) order (bitwise one context's)"""
         return _pair_approach(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_group_pair_approach(self._g, r, t, d, w, rows, cap, n)), self.params,
                               range, tol, max_depth, max_windows, symmetric)
+
+    def path_crossings(self, range=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_path_crossings: Solver.path_crossings, every pair (u, q > u) from the rank that owns u, in (robot, partner) order (bitwise one context's)"""
+        return _path_crossings(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_group_path_crossings(self._g, r, t, d, w, rows, cap, n)), range, tol, max_depth, max_windows)
 
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""

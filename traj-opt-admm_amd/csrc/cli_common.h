@@ -228,6 +228,29 @@ inline int pair_approach_rows(F&& f, double tol, std::vector<tj_pair_record>& ro
   return n ? f(0.0, tol, -1, 0, rows.data(), n, &n) : rc;
 }
 
+// --path-crossings: one line per listed unordered pair, in the library's (robot, partner) order, and the counts of pairs whose separation rests on timing
+// (contact in space), undecided and separated in space
+inline void print_path_crossings(const std::vector<tj_crossing_record>& rows) {
+  std::cout.precision(17);
+  int contact = 0, clear = 0;
+  for (const tj_crossing_record& r : rows) {
+    std::cout << "crossing uav " << r.robot << " uav " << r.partner << " lo " << r.lo << " hi " << r.hi << " seg " << r.segment << " s " << r.s << " time " << r.time
+              << " seg " << r.partner_segment << " s " << r.partner_s << " time " << r.partner_time << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    contact += r.flags & TJ_CROSSING_CONTACT ? 1 : 0;
+    clear += !(r.flags & TJ_CROSSING_CONTACT) && (r.flags & TJ_CROSSING_CLEAR) ? 1 : 0;
+  }
+  std::cout << "crossing fleet listed " << rows.size() << " timing " << contact << " undecided " << rows.size() - contact - clear << " space " << clear << std::endl;
+}
+// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle)
+template <class F>
+inline int path_crossings_rows(F&& f, double tol, std::vector<tj_crossing_record>& rows) {
+  int n = 0;
+  const int rc = f(0.0, tol, -1, 0, nullptr, 0, &n);
+  if (rc < 0) return rc;
+  rows.resize(n);
+  return n ? f(0.0, tol, -1, 0, rows.data(), n, &n) : rc;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

@@ -37,6 +37,7 @@
 #include "kernels_closest.h"
 #include "kernels_obstacle_approach.h"
 #include "kernels_pair_approach.h"
+#include "kernels_path_crossing.h"
 #include "kernels_flight_profile.h"
 #include "host_plan.h"
 
@@ -98,7 +99,7 @@ struct tj_ctx {
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
-  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_flight_profile): every buffer is allocated by the first call that needs it, and a call
+  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_flight_profile): every buffer is allocated by the first call that needs it, and a call
   // whose allocations failed partway keeps what it got (query_buf).  Each query ends in a stream synchronise, so no two are in flight on one context, and they share: q_ctl, the
   // control block the BVH walk reports its overflow bit to (never the solver's); q_net [U][3][T] and q_pt [U], the staged copy of the control nets and piece times a group hands
   // in; q_order (sorted primitive -> caller's index), which belongs to the obstacle set and goes with it (cloud_allocs).  Per query: its rows / lists / counters and its records.
@@ -111,6 +112,9 @@ struct tj_ctx {
   // largest call so far (pair_cap, pair_mw) and lives in pair_allocs
   PairArgs pair{}; tj_pair_record* pair_out = nullptr;
   std::vector<void*> pair_allocs; int pair_cap = -1, pair_mw = 0;
+  // tj_path_crossings: the same shape, buffers of its own (cross_allocs)
+  CrossArgs cross{}; tj_crossing_record* cross_out = nullptr;
+  std::vector<void*> cross_allocs; int cross_cap = -1, cross_mw = 0;
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -764,6 +768,7 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->allocs) hipFree(p);
   for (void* p : c->cloud_allocs) hipFree(p);
   for (void* p : c->pair_allocs) hipFree(p);
+  for (void* p : c->cross_allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1298,7 +1303,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }
 
 namespace {
-// ---- the read-only queries: one path for the six (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_flight_profile.h) ----
+// ---- the read-only queries: one path for the seven (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_flight_profile.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1495,6 +1500,63 @@ int pair_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows
   return TJ_OK;
 }
 
+// device bytes of tj_path_crossings that depend on the call (include/trajadmm.h states the formula)
+size_t cross_bytes(int cap, int mw) {
+  return (size_t)cap * ((size_t)2 * mw * sizeof(CrossItem) + (size_t)4 * mw * sizeof(double) + 2 * sizeof(int) + sizeof(tj_crossing_record));
+}
+
+// tj_path_crossings (kernels_path_crossing.h): the rows (u, q > u) of the owned robots u
+int cross_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_crossing_record* rows, int cap, int* n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int r;
+  if ((r = query_nan(c, "tj_path_crossings", "range", range)) || (r = query_nan(c, "tj_path_crossings", "tol", tol))) return r;
+  if (max_depth > TJ_CROSSING_MAX_DEPTH) { c->err = "tj_path_crossings: max_depth must be 0.." + std::to_string(TJ_CROSSING_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
+  if (max_windows > TJ_CROSSING_MAX_WINDOWS) { c->err = "tj_path_crossings: max_windows must be 1.." + std::to_string(TJ_CROSSING_MAX_WINDOWS) + " (or <= 0 for the default)"; return TJ_ERR_INVALID; }
+  const Dev& d = c->d;
+  const int mw = max_windows <= 0 ? TJ_CROSSING_FRONTIER : max_windows;
+  if (cross_bytes(cap, mw) > (size_t)TJ_CROSSING_MAX_BYTES) {
+    c->err = "tj_path_crossings: cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw) + " need " + std::to_string(cross_bytes(cap, mw)) + " bytes of device memory, more than TJ_CROSSING_MAX_BYTES (" +
+             std::to_string((long long)TJ_CROSSING_MAX_BYTES) + "): lower cap (rows beyond it are still counted) or max_windows";
+    return TJ_ERR_INVALID;
+  }
+  if ((r = query_state(c, "tj_path_crossings", true, net_host && pt_host))) return r;
+  *n = 0;
+  if (!d.multi()) return TJ_OK;   // one UAV: no pair
+  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
+  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
+  QUIESCE(c);
+  CrossArgs& b = c->cross;
+  if ((r = query_buf(c, b.mask, mask_n)) || (r = query_buf(c, b.wordoff, mask_n)) || (r = query_buf(c, b.n, 1))) return r;
+  if (cap > c->cross_cap || mw > c->cross_mw) {   // grow: the context is quiet, nothing reads the old buffers
+    for (void* p : c->cross_allocs) hipFree(p);
+    c->cross_allocs.clear();
+    b.who = nullptr; b.list = nullptr; b.klo = nullptr; c->cross_out = nullptr;
+    const int gc = std::max(cap, c->cross_cap), gm = std::max(mw, c->cross_mw);
+    c->cross_cap = -1; c->cross_mw = 0;
+    std::vector<void*>* l = &c->cross_allocs;
+    if ((r = query_buf(c, b.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l)) ||
+        (r = query_buf(c, c->cross_out, gc, l))) return r;
+    c->cross_cap = gc; c->cross_mw = gm;
+  }
+  CrossArgs a = b;
+  if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
+  a.range = query_range(d, range); a.tol = tol < 0 ? TJ_CROSSING_TOL : tol;
+  a.max_depth = max_depth < 0 ? TJ_CROSSING_MAX_DEPTH : max_depth; a.max_windows = mw; a.cap = cap;
+  a.words = words;
+  if ((r = query_clear(c, a.mask, mask_n)) || (r = query_clear(c, a.n, 1))) return r;
+  if (owned > 0) {   // two launches for the count, three for the rows, whatever the fleet's size, the number of pairs and the depth
+    PairArgs ix{};   // k_pair_index reads the bitmask and writes its offsets, n and the slots' pairs: the same scan, this query's buffers
+    ix.cap = cap; ix.words = words; ix.mask = a.mask; ix.wordoff = a.wordoff; ix.n = a.n; ix.who = a.who;
+    hipLaunchKernelGGL(k_cross_mark, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, ix);
+    if (cap > 0) hipLaunchKernelGGL(k_cross_refine, dim3(cap), dim3(CX_THREADS), 0, c->stream, d, a, c->cross_out);
+  }
+  if ((r = query_fetch(c, n, a.n, 1)) || (r = query_finish(c, nullptr))) return r;
+  if ((r = query_fetch(c, rows, c->cross_out, std::min(cap, *n))) || (r = query_finish(c, nullptr))) return r;
+  if (*n > cap && rows) { c->err = "tj_path_crossings: " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
 int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
   if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
@@ -1544,6 +1606,8 @@ int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int 
 int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
 int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return pair_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
 int tj_pair_record_size(void) { return (int)sizeof(tj_pair_record); }
+int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) { return cross_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
+int tj_crossing_record_size(void) { return (int)sizeof(tj_crossing_record); }
 
 // tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {

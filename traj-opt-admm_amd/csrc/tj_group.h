@@ -684,6 +684,24 @@ int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth,
   return TJ_OK;
 }
 
+// the rows (u, q > u) by u's owner, the ranks' lists one after the other as above
+int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) {
+  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int total = 0;
+  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    const int room = std::max(0, cap - total);
+    int nr = 0;
+    const int e = cross_run(c, range, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, room, &nr);
+    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
+    total += nr;
+    return (int)TJ_OK;
+  });
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_path_crossings: " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 // from every rank's own state: nothing of another robot is read
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
   return group_query(g, false, false, out, {}, {}, [&](tj_ctx* c, const double*, const double*, tj_obstacle_robot* part) {

@@ -15,6 +15,7 @@ import pytest
 import audit_ref as R
 import audit_timed_ref as T
 import closest_ref as K
+import pair_approach_ref as Q
 from audit_ref import prims
 from conftest import ROOT
 
@@ -114,6 +115,29 @@ def test_beyond_level_six(pkg, scenes):
     assert np.all(a["hi"] <= t6["timed_hi"] + tol + sl)
     for u in range(slv.U):
         assert a["windows"][u] < K.level_window_count(pkg, st, slv.P, slv.res, u, INF, 6), u
+    slv.close()
+
+
+def test_wide_live_sets(pkg, scenes):
+    """a live set wider than the refine workgroup's 128 threads (pair_approach_ref.orbit_state: two robots, the set doubles per round: 32, 64, 128, 256), so
+    that lanes take more than one child per pass; then max_windows one below that size: TRUNCATED with the previous round's record.  With one partner the
+    robot's search is the pair's: the record equals tj_pair_approach's row, which the same round loop produces with 64 threads"""
+    scene, st = Q.orbit_state(pkg, scenes)
+    slv = pkg.Solver(scene, stop=0.0)
+    slv.set_state(st)
+    traces = {}
+    Q.pair_rows(pkg, prims(), st, slv.P, slv.res, INF, slv.params["offset"], 0.0, 4, Q.MAX_WINDOWS, traces=traces)
+    sizes = [t[3] for t in traces[(0, 1)]]
+    print("live set of (0, 1) per depth", sizes)
+    assert sizes[2] <= 128 < sizes[3]
+    T_ = pkg.CLOSEST_FLAGS["truncated"]
+    for cap, depth, truncated in ((sizes[3], 3, False), (sizes[3] - 1, 2, True)):
+        a = check(pkg, slv, INF, 0.0, 3, cap, st)
+        assert np.all(a["depth"] == depth) and np.all((a["flags"] & T_ != 0) == truncated)
+        p = slv.pair_approach(range=INF, tol=0.0, max_depth=3, max_windows=cap)
+        assert list(zip(p["robot"], p["partner"])) == [(0, 1), (1, 0)]
+        for n in ("lo", "hi", "time", "segment", "depth", "flags", "windows"):
+            assert np.array_equal(a[n], p[n]), (cap, n, a[n], p[n])
     slv.close()
 
 

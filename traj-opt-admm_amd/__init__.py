@@ -121,12 +121,27 @@ CLOSEST_MAX_DEPTH = 40     # TJ_CLOSEST_MAX_DEPTH
 CLOSEST_FRONTIER = 4096    # TJ_CLOSEST_FRONTIER
 
 
+def _search_args(range, tol, max_depth, max_windows):
+    """(range, tol, max_depth, max_windows) of the four branch-and-bound queries as the C side takes them; None selects the C side's default"""
+    return (C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
+            C.c_int(0 if max_windows is None else int(max_windows)))
+
+
 def _approach(struct, call, U, range, tol, max_depth, max_windows):
     """shared by closest_approach / obstacle_approach of Solver and Group: call(range, tol, max_depth, max_windows, records) -> dict of numpy arrays [U]"""
     rec = (struct * U)()
-    call(C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
-         C.c_int(0 if max_windows is None else int(max_windows)), rec)
+    call(*_search_args(range, tol, max_depth, max_windows), rec)
     return _records(struct, rec)
+
+
+def _listed_rows(struct, call, args):
+    """shared by pair_approach / path_crossings of Solver and Group: call(*args, rows, cap, n).  The count-only call first, then the rows -> dict of numpy arrays [n]"""
+    n = C.c_int(0)
+    call(*args, None, C.c_int(0), C.byref(n))
+    rec = (struct * max(n.value, 1))()
+    if n.value:
+        call(*args, rec, C.c_int(n.value), C.byref(n))
+    return _records(struct, rec[:n.value])
 
 
 class TjObstacleRobot(C.Structure):
@@ -235,15 +250,8 @@ def merge_pairs(rows, rng, offset):
 
 
 def _pair_approach(call, params, range, tol, max_depth, max_windows, symmetric):
-    """shared by Solver.pair_approach / Group.pair_approach: call(range, tol, max_depth, max_windows, rows, cap, n).  The count-only call first, then the rows."""
-    args = (C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
-            C.c_int(0 if max_windows is None else int(max_windows)))
-    n = C.c_int(0)
-    call(*args, None, C.c_int(0), C.byref(n))
-    rec = (TjPairRecord * max(n.value, 1))()
-    if n.value:
-        call(*args, rec, C.c_int(n.value), C.byref(n))
-    rows = _records(TjPairRecord, rec[:n.value])
+    """shared by Solver.pair_approach / Group.pair_approach: call(range, tol, max_depth, max_windows, rows, cap, n)"""
+    rows = _listed_rows(TjPairRecord, call, _search_args(range, tol, max_depth, max_windows))
     if not symmetric:
         return rows
     rng = float(range) if range is not None and range > 0 else params["offset"] + 2 * params["margin"]
@@ -251,16 +259,9 @@ def _pair_approach(call, params, range, tol, max_depth, max_windows, symmetric):
 
 
 def _path_crossings(call, range, tol, max_depth, max_windows):
-    """shared by Solver.path_crossings / Group.path_crossings: call(range, tol, max_depth, max_windows, rows, cap, n).  The count-only call first, then the
-    rows; `gap` = partner_time - time, the timing margin of the crossing (0.0 where the pair is listed for its lo only)."""
-    args = (C.c_double(0.0 if range is None else float(range)), C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)),
-            C.c_int(0 if max_windows is None else int(max_windows)))
-    n = C.c_int(0)
-    call(*args, None, C.c_int(0), C.byref(n))
-    rec = (TjCrossingRecord * max(n.value, 1))()
-    if n.value:
-        call(*args, rec, C.c_int(n.value), C.byref(n))
-    rows = _records(TjCrossingRecord, rec[:n.value])
+    """shared by Solver.path_crossings / Group.path_crossings: call(range, tol, max_depth, max_windows, rows, cap, n); `gap` = partner_time - time, the timing
+    margin of the crossing (0.0 where the pair is listed for its lo only)."""
+    rows = _listed_rows(TjCrossingRecord, call, _search_args(range, tol, max_depth, max_windows))
     rows["gap"] = rows["partner_time"] - rows["time"]
     return rows
 

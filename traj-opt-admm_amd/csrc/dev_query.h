@@ -2,11 +2,13 @@
 //
 // Every query works per (owned robot, segment) on the segment's 6-point hull (hull_entry's sums: the bits of the hull cache) and its box, and reduces per-lane candidates
 // with a TOTAL order, so that a result is a function of the state alone: no float atomics, no dependence on the order of evaluation.
-//   query_hull     the unit's hull into LDS and its box
+//   hull_box, query_hull   the box of a 6-point hull behind a stride; the unit's hull into LDS and its box
 //   box_near       the box-gap skip: is a 6-point hull's box within `range` of the unit's box on every axis
+//   bez_restrict, hull_restrict   a quintic's Bezier net restricted to a window; a segment's raw hull restricted into a lane's column of a tile
 //   wave_argmin    the smallest (value, key) in lexicographic order over the wave, with whatever travels along
-//   QBest          the record of the two branch-and-bound queries, ordered by (hi, segment, id, parameter): before, wave_best
-//   wave_min / wave_sum, bnb_keep   the small reductions and the bounded append of a branch-and-bound round (kernels_closest.h describes the round)
+//   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
+//   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
+//   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the four branch-and-bound queries, and their four common flag bits
 #pragma once
 #include <limits.h>
 #include "../../include/trajadmm.h"
@@ -21,31 +23,75 @@ struct BodyHullS {
   __device__ __forceinline__ V3 get(int i) const { return V3{p[(3 * i) * st], p[(3 * i + 1) * st], p[(3 * i + 2) * st]}; }
 };
 
+// the box of a 6-point hull behind a stride (min / max: exact)
+__device__ __forceinline__ void hull_box(const double* p, int st, QBox& q) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int i = 0; i < 6; i++) { const double v = p[(3 * i + k) * st]; if (v < lo) lo = v; if (v > hi) hi = v; }
+    q.lo[k] = lo; q.hi[k] = hi;
+  }
+}
+
 // the unit's hull (segment tr of the robot whose control net is `net`) into P[18] and its box; one wave, ends behind a barrier
 __device__ __forceinline__ void query_hull(const Dev& D, const double* net, int tr, double* P, QBox& q) {
   const int lane = lane_id();
   if (lane < 18) P[lane] = hull_entry(D, net, tr, lane / 3, lane % 3);
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    q.lo[k] = lo; q.hi[k] = hi;
-  }
+  hull_box(P, 1, q);
 }
 
 // Boxes further apart than `range` on an axis: the hulls are at least that far apart, and so is whatever lies inside them.  (Rounding is monotonic, so a true gap <= range
 // never compares greater; the guard keeps a pair whose gap is within rounding of `range` in the GJK, whose |v| decides.)  p, st: the other hull, as BodyHullS.
 __device__ __forceinline__ bool box_near(const double* p, int st, const QBox& q, double range) {
+  QBox o;
+  hull_box(p, st, o);
   bool near = true;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int i = 0; i < 6; i++) { const double v = p[(3 * i + k) * st]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    const double gap = fmax(lo - q.hi[k], q.lo[k] - hi);
+    const double gap = fmax(o.lo[k] - q.hi[k], q.lo[k] - o.hi[k]);
     near = near && !(gap > range * 1.000001 + 1e-9);
   }
   return near;
+}
+
+// the Bezier net of a quintic restricted to [sa, sb] of its parameter: o[i] = blossom(sa x (5 - i), sb x i).  Row s of the triangle (s steps at sa) has 6 - s points; 5 - s
+// steps at sb take it to o[5 - s].  sa = 0, sb = 1 returns p bit for bit (1 * x + 0 * y).
+__device__ __forceinline__ void bez_restrict(const double (&p)[6], double sa, double sb, double (&o)[6]) {
+  const double ua = 1 - sa, ub = 1 - sb;
+  double r[6];
+#pragma unroll
+  for (int m = 0; m < 6; m++) r[m] = p[m];
+#pragma unroll
+  for (int s = 0; s <= 5; s++) {
+    double t[6];
+#pragma unroll
+    for (int m = 0; m <= 5 - s; m++) t[m] = r[m];
+#pragma unroll
+    for (int k = 5 - s; k > 0; k--)
+#pragma unroll
+      for (int m = 0; m < k; m++) t[m] = ub * t[m] + sb * t[m + 1];
+    o[5 - s] = t[0];
+#pragma unroll
+    for (int m = 0; m < 5 - s; m++) r[m] = ua * r[m] + sa * r[m + 1];
+  }
+}
+
+
+// segment tr of `net` (hull_entry's sums) restricted to [sa, sb] into a column of stride ST; [0, 1] returns the raw hull bit for bit.  __restrict__: col is a
+// lane's column of an LDS tile and never the net.  A caller that holds the column in a struct hides that from the compiler, which then reloads the control points
+// and the basis behind every axis's stores (165 global loads per pair of hulls instead of 57: a fifth of tj_path_crossings' time where every pair crosses).
+template <int ST>
+__device__ __forceinline__ void hull_restrict(const Dev& D, const double* __restrict__ net, int tr, double sa, double sb, double* __restrict__ col) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double a[6], o[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) a[i] = hull_entry(D, net, tr, i, k);
+    bez_restrict(a, sa, sb, o);
+#pragma unroll
+    for (int i = 0; i < 6; i++) col[(3 * i + k) * ST] = o[i];
+  }
 }
 
 template <class T>
@@ -76,26 +122,127 @@ __device__ __forceinline__ int wave_sum(int v) {
 
 // the best attained distance of a branch and bound: hi at parameter x (a time, or a position in the segment) of segment seg against id (a partner robot, or the caller's index
 // of a primitive).  Nothing found: {range, 0, INT_MAX, INT_MAX}.  The order is total: equal distances go to the smaller (segment, id, parameter).
-struct QBest { double hi, x; int seg, id; };
+struct QBest {
+  double hi, x; int seg, id;
+  __device__ __forceinline__ QBest shuffled(int off) const { return QBest{__shfl_xor(hi, off), __shfl_xor(x, off), __shfl_xor(seg, off), __shfl_xor(id, off)}; }
+};
 __device__ __forceinline__ bool before(const QBest& a, const QBest& b) {
   if (a.hi != b.hi) return a.hi < b.hi;
   if (a.seg != b.seg) return a.seg < b.seg;
   if (a.id != b.id) return a.id < b.id;
   return a.x < b.x;
 }
-__device__ __forceinline__ void wave_best(QBest& m) {
+// the first in the record's total order over the wave (a record states its fields once, in shuffled)
+template <class Best>
+__device__ __forceinline__ void wave_best(Best& m) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    const QBest o{__shfl_xor(m.hi, off), __shfl_xor(m.x, off), __shfl_xor(m.seg, off), __shfl_xor(m.id, off)};
+    const Best o = m.shuffled(off);
     if (before(o, m)) m = o;
   }
 }
+
+// The LDS words of one workgroup's reductions, for the round and for a kernel's own seed passes.  A reduction is two halves around a barrier of the caller's: put_* (wave
+// reduction, lane 0 stores) and the read (every thread folds the waves' words; a second barrier before the words are written again).  `ev` counts evaluated windows:
+// integer adds from init() on, final behind any barrier that follows the last count().  TERM: the search has terminal items (one more word per wave).
+template <int NW, bool TERM> struct BnbTermWords { int wterm[NW]; };
+template <int NW> struct BnbTermWords<NW, false> {};
+template <class Best, int THREADS, bool TERM>
+struct BnbShared : BnbTermWords<THREADS / 64, TERM> {
+  static constexpr int NW = THREADS / 64;
+  Best wbest[NW];
+  double wlo[NW];
+  int kept, ev;
+  __device__ __forceinline__ void init() { if (threadIdx.x == 0) { kept = 0; ev = 0; } __syncthreads(); }
+  __device__ __forceinline__ void put_best(Best& m) { wave_best(m); if (lane_id() == 0) wbest[threadIdx.x >> 6] = m; }
+  __device__ __forceinline__ Best best(Best m) const { for (int k = 0; k < NW; k++) if (before(wbest[k], m)) m = wbest[k]; return m; }
+  __device__ __forceinline__ void put_lo(double& m) { m = wave_min(m); if (lane_id() == 0) wlo[threadIdx.x >> 6] = m; }
+  __device__ __forceinline__ double lo(double m) const { for (int k = 0; k < NW; k++) m = fmin(m, wlo[k]); return m; }
+  __device__ __forceinline__ void count(int k) { atomicAdd(&ev, k); }
+};
 
 // pass 2 of a round keeps an item: one integer atomic on the workgroup's LDS counter, stored while the list has room (the counter goes on: more than maxw = truncated)
 template <class Item>
 __device__ __forceinline__ void bnb_keep(int& kept, Item* nxt, int maxw, const Item& item) {
   const int at = atomicAdd(&kept, 1);
   if (at < maxw) nxt[at] = item;
+}
+
+// ALL ROUNDS of one branch and bound by a workgroup of THREADS threads, from the committed record (best, lo_u, n live items in cur, not truncated) to the one the
+// search ends on; the children evaluated are added to sh.ev, which a kernel reads once, for its record, behind the rounds.
+// cur / nxt: ping-pong lists of maxw items, klo: the children's lo (ARITY * maxw).  One round:
+//   pass 1   lanes take the children strided (i = ARITY * item + child): lo to klo[i], the attained candidates into the lane's best; a total-order reduction gives the
+//            round's best.  The children evaluated go to sh.ev: ARITY * n at once where nothing can be terminal, else one integer add per evaluated child
+//   pass 2   the same children again: those with lo < best.hi -- the round's FINAL best, so the set does not depend on the order of evaluation -- are appended to nxt
+//            (bnb_keep), reducing min lo and "every kept item is terminal"
+//   end      more than maxw kept: TRUNCATED, the committed record stands (`windows` counts the overflowing round's work too); else commit and swap the lists
+// stop: hi - lo <= tol | nothing live | every live item terminal | max_depth | truncated.  Every thread holds the same values on entry and on return.
+// The Search states what differs:
+//   Item, Best (ordered by before), ARITY, TERMINAL (can an item be unsplittable)
+//   none()                 the Best of "nothing found"
+//   terminal(w)            TERMINAL only: w cannot be split; it stays in the set with its lo, and nothing of it is evaluated
+//   eval(w, c, mine)       lo of child c of w; folds the child's attained candidates into mine
+//   child(w, c, lo)        child c of w as an Item (TERMINAL, terminal(w): w itself, marked)
+template <int THREADS, class Search, class Shared>
+__device__ __forceinline__ void bnb_rounds(const Search& s, Shared& sh, double tol, int max_depth, int maxw, typename Search::Item* cur, typename Search::Item* nxt, double* klo,
+                                           typename Search::Best& best, double& lo_u, int& n, int& depth, bool& truncated) {
+  using Item = typename Search::Item;
+  using Best = typename Search::Best;
+  constexpr int ARITY = Search::ARITY;
+  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+  bool terminal = false;   // every live item is
+  while (!truncated && !(best.hi - lo_u <= tol) && n > 0 && !terminal && depth < max_depth) {
+    // ---- pass 1: the children, one per lane ----
+    Best mine = s.none();
+    for (int i = tid; i < ARITY * n; i += THREADS) {
+      const Item w = cur[(unsigned)i / ARITY];
+      const int c = (unsigned)i % ARITY;
+      if constexpr (Search::TERMINAL) { if (s.terminal(w)) { klo[i] = c ? INFINITY : w.lo; continue; } sh.count(1); }
+      klo[i] = s.eval(w, c, mine);
+    }
+    sh.put_best(mine);
+    if (tid == 0) { sh.kept = 0; if constexpr (!Search::TERMINAL) sh.count(ARITY * n); }   // (nothing terminal: every child was evaluated)
+    __syncthreads();   // (also: every klo of the round is written)
+    const Best cand = sh.best(best);
+    // ---- pass 2: keep what can still hold something below the round's best ----
+    double mlo = INFINITY; int allterm = 1;
+    for (int i = tid; i < ARITY * n; i += THREADS) {
+      const double lo = klo[i];
+      if constexpr (!Search::TERMINAL) if (!(lo < cand.hi)) continue;   // (the item is loaded for kept children only)
+      const Item w = cur[(unsigned)i / ARITY];
+      const int c = (unsigned)i % ARITY;
+      if constexpr (Search::TERMINAL) {   // (the item's few words are loaded beside lo: a round of the timed search is latency)
+        if (!(lo < cand.hi)) continue;    // (the second child of a terminal item has lo = INFINITY)
+        allterm &= s.terminal(w) ? 1 : 0;
+      }
+      mlo = fmin(mlo, lo);
+      bnb_keep(sh.kept, nxt, maxw, s.child(w, c, lo));
+    }
+    sh.put_lo(mlo);
+    if constexpr (Search::TERMINAL) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) allterm &= __shfl_xor(allterm, off);
+      if (lane == 0) sh.wterm[wave] = allterm;
+    }
+    __syncthreads();   // (also: the new list is written, `kept` is final)
+    const int m = sh.kept;
+    mlo = sh.lo(mlo);
+    if constexpr (Search::TERMINAL) for (int k = 0; k < Shared::NW; k++) allterm &= sh.wterm[k];
+    __syncthreads();   // everyone has read the round's words before the next round writes them
+    if (m > maxw) { truncated = true; break; }
+    best = cand; lo_u = fmin(best.hi, mlo); n = m; terminal = Search::TERMINAL && m > 0 && allterm; depth++;
+    Item* t = cur; cur = nxt; nxt = t;
+  }
+}
+
+// the four flag bits every branch-and-bound record has (the four headers' values agree); a query's own cases and bits stay at its call
+constexpr int BNB_CONTACT = 1, BNB_CLEAR = 2, BNB_CONVERGED = 4, BNB_TRUNCATED = 8;
+static_assert(TJ_CLOSEST_CONTACT == BNB_CONTACT && TJ_PAIR_CONTACT == BNB_CONTACT && TJ_OBSTACLE_CONTACT == BNB_CONTACT && TJ_CROSSING_CONTACT == BNB_CONTACT, "CONTACT");
+static_assert(TJ_CLOSEST_CLEAR == BNB_CLEAR && TJ_PAIR_CLEAR == BNB_CLEAR && TJ_OBSTACLE_CLEAR == BNB_CLEAR && TJ_CROSSING_CLEAR == BNB_CLEAR, "CLEAR");
+static_assert(TJ_CLOSEST_CONVERGED == BNB_CONVERGED && TJ_PAIR_CONVERGED == BNB_CONVERGED && TJ_OBSTACLE_CONVERGED == BNB_CONVERGED && TJ_CROSSING_CONVERGED == BNB_CONVERGED, "CONVERGED");
+static_assert(TJ_CLOSEST_TRUNCATED == BNB_TRUNCATED && TJ_PAIR_TRUNCATED == BNB_TRUNCATED && TJ_OBSTACLE_TRUNCATED == BNB_TRUNCATED && TJ_CROSSING_TRUNCATED == BNB_TRUNCATED, "TRUNCATED");
+__device__ __forceinline__ int bnb_flags(bool found, double hi, double lo, double tol, int n, bool truncated, double offset) {
+  return (found && hi <= offset ? BNB_CONTACT : 0) | (lo > offset ? BNB_CLEAR : 0) | (hi - lo <= tol || (n == 0 && !truncated) ? BNB_CONVERGED : 0) | (truncated ? BNB_TRUNCATED : 0);
 }
 
 }  // namespace tj

@@ -40,28 +40,6 @@ struct AuditTimedArgs {
   int *row_qlo, *row_qhi;               // [U][S] partner of the row's lo / hi, -1: nothing closer than range
 };
 
-// the Bezier net of a quintic restricted to [sa, sb] of its parameter: o[i] = blossom(sa x (5 - i), sb x i).  Row s of the triangle (s steps at sa) has 6 - s points; 5 - s
-// steps at sb take it to o[5 - s].  sa = 0, sb = 1 returns p bit for bit (1 * x + 0 * y).
-__device__ __forceinline__ void bez_restrict(const double (&p)[6], double sa, double sb, double (&o)[6]) {
-  const double ua = 1 - sa, ub = 1 - sb;
-  double r[6];
-#pragma unroll
-  for (int m = 0; m < 6; m++) r[m] = p[m];
-#pragma unroll
-  for (int s = 0; s <= 5; s++) {
-    double t[6];
-#pragma unroll
-    for (int m = 0; m <= 5 - s; m++) t[m] = r[m];
-#pragma unroll
-    for (int k = 5 - s; k > 0; k--)
-#pragma unroll
-      for (int m = 0; m < k; m++) t[m] = ub * t[m] + sb * t[m + 1];
-    o[5 - s] = t[0];
-#pragma unroll
-    for (int m = 0; m < 5 - s; m++) r[m] = ua * r[m] + sa * r[m + 1];
-  }
-}
-
 __device__ __forceinline__ double clamp01(double x) { return fmin(fmax(x, 0.0), 1.0); }
 
 // the certificate of a GJK result v = (nearest point of body 1) - (nearest point of body 2): v . (a_i - b_j) > 0 for every vertex pair, i.e. v is a separating

@@ -16,6 +16,8 @@
 //   bracket  lo_u = min(best.hi, min lo over live), hi_u = best.hi
 //   stop     hi_u - lo_u <= tol | live empty | every live window terminal | d == max_depth | more than max_windows live (TRUNCATED: the record of the last
 //            completed round is returned; `windows` counts the overflowing round's work too)
+// The round loop itself -- two passes, three barriers, the truncation rule, the ping-pong lists -- is bnb_rounds (dev_query.h), one function for this query,
+// tj_pair_approach, tj_obstacle_approach and tj_path_crossings; this file states the timed-window search it runs (TimedSearch).
 //
 // Four launches whatever the fleet's size and the depth:
 //   k_audit_timed (levels 0), k_audit_timed_reduce   the level-0 bracket per robot: best (hi, segment, partner, time) and the smallest lo
@@ -23,13 +25,10 @@
 //                      lo < best.hi appends it to the robot's list with one integer atomic on the robot's counter (append order is free: nothing
 //                      downstream depends on it; the windows below best.hi are a handful per robot, so there is nothing for a ballot to save).  The
 //                      number of windows evaluated is summed over the wave and added once.
-//   k_closest_refine   one workgroup of CL_THREADS per owned robot runs ALL rounds (closest_rounds, shared with kernels_pair_approach.h).  Lanes take the CHILDREN of the live list strided (item 2 p + c =
-//                      child c of window p): the raw hulls of (u, tr) and (q, j) into the lane's columns of two LDS tiles, timed_window, lo to the robot's
-//                      klo slice.  A total-order reduction (hi, segment, partner, time) over the workgroup gives the round's best; a second pass over the
-//                      same items keeps lo < best.hi and appends to the other half of the ping-pong list (integer LDS counter), reducing min lo and "all
-//                      terminal" on the way.  The lists live in the robot's slice of a global buffer allocated on the first call (40-byte records; a
-//                      live list is a few windows, read once per round: L2 traffic, no LDS staging).  No workgroup waits on another; no polling, no
-//                      cross-queue word, nothing of the iteration's scratch.
+//   k_closest_refine   one workgroup of CL_THREADS per owned robot runs ALL rounds on the robot's slice of a global buffer allocated on the first call (40-byte
+//                      records; a live list is a few windows, read once per round: L2 traffic, no LDS staging).  A child: the raw hulls of (u, tr) and (q, j)
+//                      into the lane's columns of two LDS tiles, timed_window into the third.  No workgroup waits on another; no polling, no cross-queue
+//                      word, nothing of the iteration's scratch.
 // Read-only: the kernels write the query's own buffers only (no tj_stats counter, no launch count).
 #pragma once
 #include "kernels_audit_timed.h"
@@ -72,102 +71,70 @@ __global__ __launch_bounds__(64) void k_closest_seed(Dev D, ClosestArgs A) {
   if (lane == 0 && nev) atomicAdd(&A.count[3 * u + 1], nev);
 }
 
-// ALL rounds of one search by a workgroup of THREADS threads (k_closest_refine: a robot's windows; kernels_pair_approach.h: one pair's): the two-pass round of the header
-// comment on the ping-pong lists cur / nxt (maxw items each) and klo (2 * maxw), from the committed record (best, lo_u, n live windows in cur, not truncated) to the one the
-// search ends on.  Every thread holds the same values on entry and on return.
+// The timed-window search of bnb_rounds (dev_query.h) by a workgroup of THREADS threads (k_closest_refine: a robot's windows; kernels_pair_approach.h: one pair's):
+// a window is halved in time, a child is evaluated by timed_window on the raw hulls in the lane's columns of the kernel's three 18-row tiles.
 template <int THREADS>
-__device__ __forceinline__ void closest_rounds(const Dev& D, const double* net, const double* pt, int u, double range, double tol, int max_depth, int maxw,
-                                               ClosestWin* cur, ClosestWin* nxt, double* klo, QBest& best, double& lo_u, int& n, int& windows, int& depth, bool& truncated) {
-  constexpr int NW = THREADS / 64;
-  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S;
-  __shared__ double tp[18 * THREADS], tq[18 * THREADS], td[18 * THREADS];
-  __shared__ QBest wbest[NW];
-  __shared__ double wlo[NW];
-  __shared__ int wev[NW], wterm[NW], kept;
-  const double res = (double)D.res, ptu = pt[u];
-  const double* nu = net + (size_t)u * 3 * D.T;
-  double* cp = tp + tid; double* cq = tq + tid; double* cd = td + tid;
-  bool terminal = false;   // every live window is
-  while (!truncated && !(best.hi - lo_u <= tol) && n > 0 && !terminal && depth < max_depth) {
-    // ---- pass 1: the children, one per lane ----
-    QBest mine{range, 0.0, INT_MAX, INT_MAX};
-    int nev = 0;
-    for (int i = tid; i < 2 * n; i += THREADS) {
-      const ClosestWin w = cur[i >> 1];
-      const int c = i & 1;
-      const double cm = 0.5 * (w.ca + w.cb);
-      if (w.term || cm == w.ca || cm == w.cb) { klo[i] = c ? INFINITY : w.lo; continue; }
-      const double ca = c ? cm : w.ca, cb = c ? w.cb : cm;
-      const bool hover = w.j >= S;
-      const double ptq = pt[w.q];
-      const double T0u = (w.tr / res) * ptu, T1u = ((w.tr + 1) / res) * ptu, lenu = T1u - T0u;
-      const double Tj = (w.j / res) * ptq, Tj1 = ((w.j + 1) / res) * ptq;
-      for (int e = 0; e < 18; e++) cp[e * THREADS] = hull_entry(D, nu, w.tr, e / 3, e % 3);
-      timed_partner_fill<THREADS>(D, net + (size_t)w.q * 3 * D.T, w.j, hover, cq);
-      const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-      const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
-      double lo, h0, h5; bool sep;
-      timed_window<THREADS, THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
-      if (!sep) lo = 0.0;
-      nev++;
-      klo[i] = lo;
-      const bool first = h0 <= h5;
-      const QBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
-      if (b.hi < range && before(b, mine)) mine = b;
-    }
-    wave_best(mine); nev = wave_sum(nev);
-    if (lane == 0) { wbest[wave] = mine; wev[wave] = nev; }
-    if (tid == 0) kept = 0;
-    __syncthreads();   // (also: every klo of the round is written)
-    QBest cand = best;
-    for (int k = 0; k < NW; k++) { if (before(wbest[k], cand)) cand = wbest[k]; windows += wev[k]; }
-    // ---- pass 2: keep what can still hold something below the round's best ----
-    double mlo = INFINITY; int allterm = 1;
-    for (int i = tid; i < 2 * n; i += THREADS) {
-      const ClosestWin w = cur[i >> 1];
-      const int c = i & 1;
-      const double cm = 0.5 * (w.ca + w.cb), lo = klo[i];
-      const bool term = w.term || cm == w.ca || cm == w.cb;
-      if ((term && c) || !(lo < cand.hi)) continue;
-      mlo = fmin(mlo, lo); allterm &= term ? 1 : 0;
-      bnb_keep(kept, nxt, maxw, term ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0});
-    }
-    mlo = wave_min(mlo);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) allterm &= __shfl_xor(allterm, off);
-    if (lane == 0) { wlo[wave] = mlo; wterm[wave] = allterm; }
-    __syncthreads();   // (also: the new list is written, `kept` is final)
-    const int m = kept;
-    for (int k = 0; k < NW; k++) { mlo = fmin(mlo, wlo[k]); allterm &= wterm[k]; }
-    __syncthreads();   // everyone has read the round's words before the next round writes them
-    if (m > maxw) { truncated = true; break; }
-    best = cand; lo_u = fmin(best.hi, mlo); n = m; terminal = m > 0 && allterm; depth++;
-    ClosestWin* t = cur; cur = nxt; nxt = t;
+struct TimedSearch {
+  using Item = ClosestWin;
+  using Best = QBest;
+  static constexpr int ARITY = 2;
+  static constexpr bool TERMINAL = true;
+  using Shared = BnbShared<QBest, THREADS, true>;
+  const Dev& D; const double* net; const double* pt;
+  const double* nu; double ptu, range;   // u's net and piece time
+  double *cp, *cq, *cd;   // the lane's columns of tp, tq, td
+  __device__ __forceinline__ QBest none() const { return QBest{range, 0.0, INT_MAX, INT_MAX}; }
+  __device__ __forceinline__ bool terminal(const ClosestWin& w) const { const double cm = 0.5 * (w.ca + w.cb); return w.term || cm == w.ca || cm == w.cb; }
+  __device__ __forceinline__ double eval(const ClosestWin& w, int c, QBest& mine) const {
+    const int S = D.S;
+    const double res = (double)D.res;
+    const double cm = 0.5 * (w.ca + w.cb);
+    const double ca = c ? cm : w.ca, cb = c ? w.cb : cm;
+    const bool hover = w.j >= S;
+    const double ptq = pt[w.q];
+    const double T0u = (w.tr / res) * ptu, T1u = ((w.tr + 1) / res) * ptu, lenu = T1u - T0u;
+    const double Tj = (w.j / res) * ptq, Tj1 = ((w.j + 1) / res) * ptq;
+    for (int e = 0; e < 18; e++) cp[e * THREADS] = hull_entry(D, nu, w.tr, e / 3, e % 3);
+    timed_partner_fill<THREADS>(D, net + (size_t)w.q * 3 * D.T, w.j, hover, cq);
+    const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
+    const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+    double lo, h0, h5; bool sep;
+    timed_window<THREADS, THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
+    if (!sep) lo = 0.0;
+    const bool first = h0 <= h5;
+    const QBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};
+    if (b.hi < range && before(b, mine)) mine = b;
+    return lo;
   }
-}
+  __device__ __forceinline__ ClosestWin child(const ClosestWin& w, int c, double lo) const {
+    const double cm = 0.5 * (w.ca + w.cb);
+    return terminal(w) ? ClosestWin{w.ca, w.cb, lo, w.tr, w.q, w.j, 1} : ClosestWin{c ? cm : w.ca, c ? w.cb : cm, lo, w.tr, w.q, w.j, 0};
+  }
+};
 
 __global__ __launch_bounds__(CL_THREADS) void k_closest_refine(Dev D, ClosestArgs A, tj_closest_robot* out) {
   const int tid = threadIdx.x, u = D.u0 + blockIdx.x;
+  __shared__ double tp[18 * CL_THREADS], tq[18 * CL_THREADS], td[18 * CL_THREADS];
+  __shared__ TimedSearch<CL_THREADS>::Shared sh;
   const tj_audit_timed_robot seed = A.seed[u];
   ClosestWin* cur = A.list + (size_t)u * 2 * TJ_CLOSEST_FRONTIER;
+  sh.init();
 
   // the committed record: the level-0 bracket (every thread holds the same values)
   QBest best{seed.timed_hi, seed.timed_time, seed.timed_robot < 0 ? INT_MAX : seed.timed_segment, seed.timed_robot < 0 ? INT_MAX : seed.timed_robot};
   double lo_u = A.count[3 * u + 2] ? 0.0 : fmin(seed.timed_lo, seed.timed_hi);   // min(best.hi, min lo over the live seeds): tj_audit_timed's, unless a live seed counts 0
-  int n = A.count[3 * u], windows = A.count[3 * u + 1], depth = 0;
+  int n = A.count[3 * u], depth = 0;
   bool truncated = n > A.max_windows;
   if (D.multi())
-    closest_rounds<CL_THREADS>(D, A.net, A.pt, u, A.range, A.tol, A.max_depth, A.max_windows, cur, cur + TJ_CLOSEST_FRONTIER, A.klo + (size_t)u * 2 * TJ_CLOSEST_FRONTIER,
-                               best, lo_u, n, windows, depth, truncated);
+    bnb_rounds<CL_THREADS>(TimedSearch<CL_THREADS>{D, A.net, A.pt, A.net + (size_t)u * 3 * D.T, A.pt[u], A.range, tp + tid, tq + tid, td + tid}, sh, A.tol, A.max_depth, A.max_windows,
+                           cur, cur + TJ_CLOSEST_FRONTIER, A.klo + (size_t)u * 2 * TJ_CLOSEST_FRONTIER, best, lo_u, n, depth, truncated);
   if (tid == 0) {
     tj_closest_robot r;
     const bool found = best.id != INT_MAX;
     r.lo = lo_u; r.hi = best.hi; r.time = found ? best.x : -1.0;
     r.robot = found ? best.id : -1; r.segment = found ? best.seg : -1;
-    r.depth = depth; r.windows = windows; r.reserved = 0;
-    r.flags = !D.multi() ? (TJ_CLOSEST_CLEAR | TJ_CLOSEST_CONVERGED)
-                         : ((found && best.hi <= D.offset ? TJ_CLOSEST_CONTACT : 0) | (lo_u > D.offset ? TJ_CLOSEST_CLEAR : 0) |
-                            (best.hi - lo_u <= A.tol || (n == 0 && !truncated) ? TJ_CLOSEST_CONVERGED : 0) | (truncated ? TJ_CLOSEST_TRUNCATED : 0));
+    r.depth = depth; r.windows = A.count[3 * u + 1] + sh.ev; r.reserved = 0;   // the seeding's windows and the rounds'
+    r.flags = !D.multi() ? (TJ_CLOSEST_CLEAR | TJ_CLOSEST_CONVERGED) : bnb_flags(found, best.hi, lo_u, A.tol, n, truncated, D.offset);
     out[u] = r;
   }
 }

@@ -22,12 +22,12 @@
 //                   than one step of the walk), then per candidate and lane the certified lo; an item with lo < best.hi is appended to the robot's list with
 //                   one integer atomic (append order is free: nothing downstream depends on it).  The row's smallest live lo goes to the row, so that the
 //                   seed bracket is exact even where the list overflows.
-//   k_obst_refine   one workgroup of OA_THREADS per owned robot runs ALL rounds over a ping-pong list in global memory (32-byte items + the children's lo):
-//                   lanes take the children strided, restrict the raw hull in registers into their column of one LDS tile, run the per-lane GJK; a
-//                   total-order reduction over the workgroup gives the round's best; a second pass keeps lo < best.hi (integer LDS counter).
+//   k_obst_refine   one workgroup of OA_THREADS per owned robot runs ALL rounds (bnb_rounds, dev_query.h: the round loop of the branch-and-bound queries)
+//                   over a ping-pong list in global memory (32-byte items + the children's lo).  A child (ObstSearch): the raw hull restricted in registers
+//                   into the lane's column of one LDS tile, the per-lane GJK against the item's primitive.
 // No float atomics, no workgroup waits on another, no polling, no cross-queue word, nothing of the iteration's scratch.  Read-only: the kernels write the
-// query's own buffers only; the walk's overflow bit goes to the queries' control block, as k_audit's.  Hull and box, the record QBest with its order and the
-// bounded append are dev_query.h's.
+// query's own buffers only; the walk's overflow bit goes to the queries' control block, as k_audit's.  Hull and box, the restriction, the record QBest with its
+// order, the bounded append and the round loop are dev_query.h's.
 #pragma once
 #include "kernels_closest.h"
 
@@ -120,96 +120,67 @@ __global__ __launch_bounds__(64) void k_obst_append(Dev D, ObstArgs A) {
   if (lane == 0) A.row_lo[(size_t)u * S + tr] = mlo;
 }
 
+// The obstacle search of bnb_rounds (dev_query.h): a window of one segment's parameter is halved, a child is the raw hull restricted to it in the lane's column
+// of the kernel's tile against the sorted primitive of the item.
+template <int PRIM>
+struct ObstSearch {
+  using Item = ObstItem;
+  using Best = QBest;
+  static constexpr int ARITY = 2;
+  static constexpr bool TERMINAL = false;   // dyadic windows, max_depth <= 40: none is ever unsplittable
+  using Shared = BnbShared<QBest, OA_THREADS, false>;
+  const Dev& D; const double* nu; const int* order; double range;
+  double* cd;   // the lane's column of td
+  __device__ __forceinline__ QBest none() const { return QBest{range, 0.0, INT_MAX, INT_MAX}; }
+  __device__ __forceinline__ double eval(const ObstItem& w, int c, QBest& mine) const {
+    const double sm = 0.5 * (w.sa + w.sb), sa = c ? sm : w.sa, sb = c ? w.sb : sm;
+    hull_restrict<OA_THREADS>(D, nu, w.tr, sa, sb, cd);
+    const auto prim = PrimOf<PRIM>::load(D, w.pt);
+    const BodyHullS hull{cd, OA_THREADS};
+    const V3 v = gjk(hull, prim);
+    double lo = norm3(v.x, v.y, v.z);
+    if (!gjk_separates(v, hull, prim)) lo = 0.0;
+    const double h0 = obst_point_dist<PRIM>(hull.get(0), prim), h5 = obst_point_dist<PRIM>(hull.get(5), prim);
+    const bool first = h0 <= h5;
+    const QBest b{first ? h0 : h5, first ? sa : sb, w.tr, order[w.pt]};
+    if (b.hi < range && before(b, mine)) mine = b;
+    return lo;
+  }
+  __device__ __forceinline__ ObstItem child(const ObstItem& w, int c, double lo) const {
+    const double sm = 0.5 * (w.sa + w.sb);
+    return ObstItem{c ? sm : w.sa, c ? w.sb : sm, lo, w.tr, w.pt};
+  }
+};
+
 template <int PRIM>
 __global__ __launch_bounds__(OA_THREADS) void k_obst_refine(Dev D, ObstArgs A, tj_obstacle_robot* out) {
-  constexpr int NW = OA_THREADS / 64;
-  const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, S = D.S, ui = blockIdx.x, u = D.u0 + ui;
+  const int tid = threadIdx.x, S = D.S, ui = blockIdx.x, u = D.u0 + ui;
   __shared__ double td[18 * OA_THREADS];
-  __shared__ QBest wbest[NW];
-  __shared__ double wlo[NW];
-  __shared__ int kept;
-  const double range = A.range, res = (double)D.res, ptu = A.pt[u];
-  const int maxw = A.max_windows;
-  const double* nu = A.net + (size_t)u * 3 * D.T;
-  ObstItem* cur = A.list + (size_t)ui * 2 * A.cap; ObstItem* nxt = cur + A.cap;
-  double* klo = A.klo + (size_t)ui * 2 * A.cap;
-  double* cd = td + tid;
+  __shared__ typename ObstSearch<PRIM>::Shared sh;
+  const double res = (double)D.res, ptu = A.pt[u];
+  ObstItem* cur = A.list + (size_t)ui * 2 * A.cap;
+  sh.init();
 
   // the committed record: the seeds' bracket (every thread holds the same values)
   QBest best = A.best[u];
   double mlo = INFINITY;
   for (int r = tid; r < S; r += OA_THREADS) mlo = fmin(mlo, A.row_lo[(size_t)u * S + r]);
-  mlo = wave_min(mlo);
-  if (lane == 0) wlo[wave] = mlo;
+  sh.put_lo(mlo);
   __syncthreads();
-  for (int k = 0; k < NW; k++) mlo = fmin(mlo, wlo[k]);
+  mlo = sh.lo(mlo);
   __syncthreads();
   double lo_u = fmin(best.hi, mlo);
-  int n = A.count[2 * u], windows = A.count[2 * u + 1], depth = 0;
-  bool truncated = n > maxw;
-  while (!truncated && !(best.hi - lo_u <= A.tol) && n > 0 && depth < A.max_depth) {
-    // ---- pass 1: the children, one per lane ----
-    QBest mine{range, 0.0, INT_MAX, INT_MAX};
-    for (int i = tid; i < 2 * n; i += OA_THREADS) {
-      const ObstItem w = cur[i >> 1];
-      const int c = i & 1;
-      const double sm = 0.5 * (w.sa + w.sb), sa = c ? sm : w.sa, sb = c ? w.sb : sm;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        double a[6], o[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) a[j] = hull_entry(D, nu, w.tr, j, k);
-        bez_restrict(a, sa, sb, o);
-#pragma unroll
-        for (int j = 0; j < 6; j++) cd[(3 * j + k) * OA_THREADS] = o[j];
-      }
-      const auto prim = PrimOf<PRIM>::load(D, w.pt);
-      const BodyHullS hull{cd, OA_THREADS};
-      const V3 v = gjk(hull, prim);
-      double lo = norm3(v.x, v.y, v.z);
-      if (!gjk_separates(v, hull, prim)) lo = 0.0;
-      klo[i] = lo;
-      const double h0 = obst_point_dist<PRIM>(hull.get(0), prim), h5 = obst_point_dist<PRIM>(hull.get(5), prim);
-      const bool first = h0 <= h5;
-      const QBest b{first ? h0 : h5, first ? sa : sb, w.tr, A.order[w.pt]};
-      if (b.hi < range && before(b, mine)) mine = b;
-    }
-    wave_best(mine);
-    if (lane == 0) wbest[wave] = mine;
-    if (tid == 0) kept = 0;
-    __syncthreads();   // (also: every klo of the round is written)
-    QBest cand = best;
-    for (int k = 0; k < NW; k++) if (before(wbest[k], cand)) cand = wbest[k];
-    windows += 2 * n;
-    // ---- pass 2: keep what can still hold something below the round's best ----
-    mlo = INFINITY;
-    for (int i = tid; i < 2 * n; i += OA_THREADS) {
-      const double lo = klo[i];
-      if (!(lo < cand.hi)) continue;
-      const ObstItem w = cur[i >> 1];
-      const int c = i & 1;
-      const double sm = 0.5 * (w.sa + w.sb);
-      mlo = fmin(mlo, lo);
-      bnb_keep(kept, nxt, maxw, ObstItem{c ? sm : w.sa, c ? w.sb : sm, lo, w.tr, w.pt});
-    }
-    mlo = wave_min(mlo);
-    if (lane == 0) wlo[wave] = mlo;
-    __syncthreads();   // (also: the new list is written, `kept` is final)
-    const int m = kept;
-    for (int k = 0; k < NW; k++) mlo = fmin(mlo, wlo[k]);
-    __syncthreads();   // everyone has read the round's words before the next round writes them
-    if (m > maxw) { truncated = true; break; }
-    best = cand; lo_u = fmin(best.hi, mlo); n = m; depth++;
-    ObstItem* t = cur; cur = nxt; nxt = t;
-  }
+  int n = A.count[2 * u], depth = 0;
+  bool truncated = n > A.max_windows;
+  bnb_rounds<OA_THREADS>(ObstSearch<PRIM>{D, A.net + (size_t)u * 3 * D.T, A.order, A.range, td + tid}, sh, A.tol, A.max_depth, A.max_windows,
+                         cur, cur + A.cap, A.klo + (size_t)ui * 2 * A.cap, best, lo_u, n, depth, truncated);
   if (tid == 0) {
     tj_obstacle_robot r;
     const bool found = best.id != INT_MAX;
     r.lo = lo_u; r.hi = best.hi; r.time = found ? ((best.seg + best.x) / res) * ptu : -1.0;   // log_data's sigma * piece_time
     r.index = found ? best.id : -1; r.segment = found ? best.seg : -1;
-    r.depth = depth; r.windows = windows; r.reserved = 0;
-    r.flags = (found && best.hi <= D.offset ? TJ_OBSTACLE_CONTACT : 0) | (lo_u > D.offset || D.N == 0 ? TJ_OBSTACLE_CLEAR : 0) |
-              (best.hi - lo_u <= A.tol || (n == 0 && !truncated) ? TJ_OBSTACLE_CONVERGED : 0) | (truncated ? TJ_OBSTACLE_TRUNCATED : 0);
+    r.depth = depth; r.windows = A.count[2 * u + 1] + sh.ev; r.reserved = 0;   // the seeds evaluated and the rounds' children
+    r.flags = bnb_flags(found, best.hi, lo_u, A.tol, n, truncated, D.offset) | (D.N == 0 ? TJ_OBSTACLE_CLEAR : 0);
     out[u] = r;
   }
 }

@@ -67,6 +67,10 @@ struct CrossQueue {
 // only.  Device half: the regions of `tab` and the control block, copied to an arena of tj_create (in_begin: taken by the next k_begin).  Host half: the flags that describe it.
 struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bool in_begin = false; bool begin_folded = false, maybe_deferred = false; int lsc_base = 0; };
 
+// what a context holds for a row-listing query (tj_pair_approach, tj_path_crossings; listed_run)
+template <class Args, class Rec>
+struct Listed { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; Args sized{}; Rec* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
+
 struct tj_ctx {
   tj_params prm;
   Dev d;
@@ -108,13 +112,10 @@ struct tj_ctx {
   AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr;
   ClosestArgs closest{}; tj_closest_robot* closest_out = nullptr;
   ObstArgs obst{}; tj_obstacle_robot* obst_out = nullptr;
-  // tj_pair_approach: the bitmask, its offsets and n are the fleet's size (allocated once, as above); what is sized by the call's cap and max_windows grows with the
-  // largest call so far (pair_cap, pair_mw) and lives in pair_allocs
-  PairArgs pair{}; tj_pair_record* pair_out = nullptr;
-  std::vector<void*> pair_allocs; int pair_cap = -1, pair_mw = 0;
-  // tj_path_crossings: the same shape, buffers of its own (cross_allocs)
-  CrossArgs cross{}; tj_crossing_record* cross_out = nullptr;
-  std::vector<void*> cross_allocs; int cross_cap = -1, cross_mw = 0;
+  // tj_pair_approach, tj_path_crossings (listed_run): the bitmask, its offsets and n are the fleet's size (allocated once, as above); what is sized by the call's cap and
+  // max_windows (the other buffers of `sized`, and out) grows with the largest call so far (cap, mw) and lives in allocs
+  Listed<PairArgs, tj_pair_record> pair;
+  Listed<CrossArgs, tj_crossing_record> cross;
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -767,8 +768,8 @@ void tj_destroy(tj_ctx* c) {
   if (c->xch_block) (void)hipFree(c->xch_block);
   for (void* p : c->allocs) hipFree(p);
   for (void* p : c->cloud_allocs) hipFree(p);
-  for (void* p : c->pair_allocs) hipFree(p);
-  for (void* p : c->cross_allocs) hipFree(p);
+  for (void* p : c->pair.allocs) hipFree(p);
+  for (void* p : c->cross.allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1302,6 +1303,8 @@ int tj_get_energy(tj_ctx* c, double* energy) {
   return TJ_OK;
 }
 
+}  // extern "C"
+
 namespace {
 // ---- the read-only queries: one path for the seven (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_flight_profile.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
@@ -1320,6 +1323,32 @@ int query_state(tj_ctx* c, const char* name, bool owners, bool handed_in) {
   return TJ_OK;
 }
 double query_range(const Dev& d, double range) { return range > 0 ? range : d.offset + 2 * d.margin; }
+// (range, tol, max_depth, max_windows) of the four branch-and-bound queries, checked (NaN, then the limits) and defaulted in one place from one table: the call's
+// and its group call's name, the limits, the defaults, and the reason clause each limit's message ends on (the two row-listing queries size their lists by the call).
+struct SearchSpec { const char* name; const char* group_name; int depth_limit, window_limit; double tol; int windows; const char* depth_why; const char* windows_why; };
+const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approach", TJ_CLOSEST_MAX_DEPTH, TJ_CLOSEST_FRONTIER, TJ_CLOSEST_TOL, TJ_CLOSEST_FRONTIER,
+                                ": deeper windows cannot be halved in a double", ": the live list's capacity"},
+                 SEARCH_PAIR{"tj_pair_approach", "tj_group_pair_approach", TJ_PAIR_MAX_DEPTH, TJ_PAIR_MAX_WINDOWS, TJ_PAIR_TOL, TJ_PAIR_FRONTIER,
+                             ": deeper windows cannot be halved in a double", ""},
+                 SEARCH_CROSSING{"tj_path_crossings", "tj_group_path_crossings", TJ_CROSSING_MAX_DEPTH, TJ_CROSSING_MAX_WINDOWS, TJ_CROSSING_TOL, TJ_CROSSING_FRONTIER,
+                                 ": deeper windows cannot be halved in a double", ""},
+                 SEARCH_OBSTACLE{"tj_obstacle_approach", "tj_group_obstacle_approach", TJ_OBSTACLE_MAX_DEPTH, TJ_OBSTACLE_FRONTIER, TJ_OBSTACLE_TOL, TJ_OBSTACLE_FRONTIER,
+                                 ": deeper windows are not dyadic in a double", ": the live list's capacity"};
+struct SearchArgs {
+  double range, tol; int max_depth, max_windows;
+  template <class Args> void put(Args& a) const { a.range = range; a.tol = tol; a.max_depth = max_depth; a.max_windows = max_windows; }
+};
+int search_args(tj_ctx* c, const SearchSpec& q, double range, double tol, int max_depth, int max_windows, SearchArgs& a) {
+  int r;
+  if ((r = query_nan(c, q.name, "range", range)) || (r = query_nan(c, q.name, "tol", tol))) return r;
+  if (max_depth > q.depth_limit) { c->err = std::string(q.name) + ": max_depth must be 0.." + std::to_string(q.depth_limit) + " (or negative for the default)" + q.depth_why; return TJ_ERR_INVALID; }
+  if (max_windows > q.window_limit) {
+    c->err = std::string(q.name) + ": max_windows must be 1.." + std::to_string(q.window_limit) + " (or <= 0 for the default)" + q.windows_why;
+    return TJ_ERR_INVALID;
+  }
+  a = SearchArgs{query_range(c->d, range), tol < 0 ? q.tol : tol, max_depth < 0 ? q.depth_limit : max_depth, max_windows <= 0 ? q.windows : max_windows};
+  return TJ_OK;
+}
 // sorted primitive -> index in the caller's obstacle list, made by whichever query needs it first
 int ensure_order(tj_ctx* c) {
   int r;
@@ -1418,10 +1447,8 @@ int audit_timed_run(tj_ctx* c, double range, int levels, const double* net_host,
 int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_closest_robot* out) {
   if (!c || !out) return TJ_ERR_INVALID;
   int r;
-  if ((r = query_nan(c, "tj_closest_approach", "range", range)) || (r = query_nan(c, "tj_closest_approach", "tol", tol))) return r;
-  if (max_depth > TJ_CLOSEST_MAX_DEPTH) { c->err = "tj_closest_approach: max_depth must be 0.." + std::to_string(TJ_CLOSEST_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
-  if (max_windows > TJ_CLOSEST_FRONTIER) { c->err = "tj_closest_approach: max_windows must be 1.." + std::to_string(TJ_CLOSEST_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
-  if ((r = query_state(c, "tj_closest_approach", true, net_host && pt_host))) return r;
+  SearchArgs sa;
+  if ((r = search_args(c, SEARCH_CLOSEST, range, tol, max_depth, max_windows, sa)) || (r = query_state(c, "tj_closest_approach", true, net_host && pt_host))) return r;
   const Dev& d = c->d;
   const int owned = d.u1 - d.u0;
   QUIESCE(c);
@@ -1430,8 +1457,7 @@ int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_wind
   if ((r = timed_setup(c, range, 0, net_host, pt_host, t)) || (r = query_buf(c, b.list, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER)) || (r = query_buf(c, b.klo, (size_t)d.U * 2 * TJ_CLOSEST_FRONTIER)) ||
       (r = query_buf(c, b.count, (size_t)d.U * 3)) || (r = query_buf(c, c->closest_out, d.U))) return r;
   ClosestArgs a = b;
-  a.net = t.net; a.pt = t.pt; a.range = t.range; a.tol = tol < 0 ? TJ_CLOSEST_TOL : tol;
-  a.max_depth = max_depth < 0 ? TJ_CLOSEST_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_CLOSEST_FRONTIER : max_windows;
+  a.net = t.net; a.pt = t.pt; sa.put(a);
   a.seed = c->timed_out;
   if ((r = query_clear(c, c->closest_out, d.U)) || (r = query_clear(c, a.count, (size_t)d.U * 3))) return r;
   if (owned > 0) {   // four launches whatever the fleet's size and the depth
@@ -1443,117 +1469,94 @@ int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_wind
   return query_finish(c, nullptr);
 }
 
-// device bytes of tj_pair_approach that depend on the call (include/trajadmm.h states the formula)
-size_t pair_bytes(const Dev& d, int cap, int mw) {
-  return (size_t)cap * ((size_t)2 * mw * (sizeof(ClosestWin) + sizeof(double)) + (size_t)(2 * d.S + 2) * sizeof(PairSeed) + 4 * sizeof(int) + sizeof(tj_pair_record));
-}
-
-int pair_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_pair_record* rows, int cap, int* n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
-  int r;
-  if ((r = query_nan(c, "tj_pair_approach", "range", range)) || (r = query_nan(c, "tj_pair_approach", "tol", tol))) return r;
-  if (max_depth > TJ_PAIR_MAX_DEPTH) { c->err = "tj_pair_approach: max_depth must be 0.." + std::to_string(TJ_PAIR_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
-  if (max_windows > TJ_PAIR_MAX_WINDOWS) { c->err = "tj_pair_approach: max_windows must be 1.." + std::to_string(TJ_PAIR_MAX_WINDOWS) + " (or <= 0 for the default)"; return TJ_ERR_INVALID; }
-  const Dev& d = c->d;
-  const int mw = max_windows <= 0 ? TJ_PAIR_FRONTIER : max_windows;
-  if (pair_bytes(d, cap, mw) > (size_t)TJ_PAIR_MAX_BYTES) {
-    c->err = "tj_pair_approach: cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw) + " need " + std::to_string(pair_bytes(d, cap, mw)) + " bytes of device memory, more than TJ_PAIR_MAX_BYTES (" +
-             std::to_string((long long)TJ_PAIR_MAX_BYTES) + "): lower cap (rows beyond it are still counted) or max_windows";
-    return TJ_ERR_INVALID;
+// ---- the two row-listing queries: what a query states (its search's table row, its byte budget and formula, its buffers, its launches), and the one path they share ----
+struct PairQuery {
+  using Args = PairArgs; using Rec = tj_pair_record;
+  static constexpr const SearchSpec& spec = SEARCH_PAIR;
+  static constexpr const char* budget = "TJ_PAIR_MAX_BYTES";
+  static constexpr long long max_bytes = TJ_PAIR_MAX_BYTES;
+  static auto& held(tj_ctx* c) { return c->pair; }
+  // device bytes that depend on the call (include/trajadmm.h states the formula)
+  static size_t bytes(const Dev& d, int cap, int mw) {
+    return (size_t)cap * ((size_t)2 * mw * (sizeof(ClosestWin) + sizeof(double)) + (size_t)(2 * d.S + 2) * sizeof(PairSeed) + 4 * sizeof(int) + sizeof(tj_pair_record));
   }
-  if ((r = query_state(c, "tj_pair_approach", true, net_host && pt_host))) return r;
-  *n = 0;
-  if (!d.multi()) return TJ_OK;   // one UAV: no pair
-  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
-  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
-  QUIESCE(c);
-  PairArgs& b = c->pair;
-  if ((r = query_buf(c, b.mask, mask_n)) || (r = query_buf(c, b.wordoff, mask_n)) || (r = query_buf(c, b.n, 1))) return r;
-  if (cap > c->pair_cap || mw > c->pair_mw) {   // grow: the context is quiet, nothing reads the old buffers
-    for (void* p : c->pair_allocs) hipFree(p);
-    c->pair_allocs.clear();
-    b.who = nullptr; b.count = nullptr; b.seeds = nullptr; b.list = nullptr; b.klo = nullptr; c->pair_out = nullptr;
-    const int gc = std::max(cap, c->pair_cap), gm = std::max(mw, c->pair_mw);
-    c->pair_cap = -1; c->pair_mw = 0;
-    std::vector<void*>* l = &c->pair_allocs;
-    if ((r = query_buf(c, b.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.count, (size_t)gc * 2, l)) || (r = query_buf(c, b.seeds, (size_t)gc * (2 * d.S + 2), l)) ||
-        (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, c->pair_out, gc, l))) return r;
-    c->pair_cap = gc; c->pair_mw = gm;
+  static int alloc(tj_ctx* c, Args& b, int gc, int gm, std::vector<void*>* l) {
+    int r;
+    if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.count, (size_t)gc * 2, l)) || (r = query_buf(c, b.seeds, (size_t)gc * (2 * c->d.S + 2), l)) ||
+        (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 2 * gm, l))) return r;
+    return TJ_OK;
   }
-  PairArgs a = b;
-  if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
-  a.range = query_range(d, range); a.tol = tol < 0 ? TJ_PAIR_TOL : tol;
-  a.max_depth = max_depth < 0 ? TJ_PAIR_MAX_DEPTH : max_depth; a.max_windows = mw; a.cap = cap;
-  a.words = words; a.seed_cap = 2 * d.S + 2;
-  if ((r = query_clear(c, a.mask, mask_n)) || (r = query_clear(c, a.n, 1)) || (r = query_clear(c, a.count, (size_t)cap * 2, cap > 0))) return r;
-  if (owned > 0) {   // two launches for the count, four for the rows, whatever the fleet's size, the number of pairs and the depth
-    hipLaunchKernelGGL(k_pair_mark, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
-    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, a);
-    if (cap > 0) {
-      hipLaunchKernelGGL(k_pair_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
-      hipLaunchKernelGGL(k_pair_refine, dim3(cap), dim3(PA_THREADS), 0, c->stream, d, a, c->pair_out);
-    }
+  static int prepare(tj_ctx* c, Args& a) { a.seed_cap = 2 * c->d.S + 2; return query_clear(c, a.count, (size_t)a.ix.cap * 2, a.ix.cap > 0); }
+  // two launches for the count, four for the rows, whatever the fleet's size, the number of pairs and the depth
+  static void mark(tj_ctx* c, const Args& a, int units) { hipLaunchKernelGGL(k_pair_mark, dim3(units), dim3(64), 0, c->stream, c->d, a); }
+  static void rows(tj_ctx* c, const Args& a, int units, Rec* out) {
+    hipLaunchKernelGGL(k_pair_seed, dim3(units), dim3(64), 0, c->stream, c->d, a);
+    hipLaunchKernelGGL(k_pair_refine, dim3(a.ix.cap), dim3(PA_THREADS), 0, c->stream, c->d, a, out);
   }
-  if ((r = query_fetch(c, n, a.n, 1)) || (r = query_finish(c, nullptr))) return r;
-  if ((r = query_fetch(c, rows, c->pair_out, std::min(cap, *n))) || (r = query_finish(c, nullptr))) return r;
-  if (*n > cap && rows) { c->err = "tj_pair_approach: " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
-  return TJ_OK;
-}
-
-// device bytes of tj_path_crossings that depend on the call (include/trajadmm.h states the formula)
-size_t cross_bytes(int cap, int mw) {
-  return (size_t)cap * ((size_t)2 * mw * sizeof(CrossItem) + (size_t)4 * mw * sizeof(double) + 2 * sizeof(int) + sizeof(tj_crossing_record));
-}
-
+};
 // tj_path_crossings (kernels_path_crossing.h): the rows (u, q > u) of the owned robots u
-int cross_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_crossing_record* rows, int cap, int* n) {
+struct CrossQuery {
+  using Args = CrossArgs; using Rec = tj_crossing_record;
+  static constexpr const SearchSpec& spec = SEARCH_CROSSING;
+  static constexpr const char* budget = "TJ_CROSSING_MAX_BYTES";
+  static constexpr long long max_bytes = TJ_CROSSING_MAX_BYTES;
+  static auto& held(tj_ctx* c) { return c->cross; }
+  static size_t bytes(const Dev&, int cap, int mw) { return (size_t)cap * ((size_t)2 * mw * sizeof(CrossItem) + (size_t)4 * mw * sizeof(double) + 2 * sizeof(int) + sizeof(tj_crossing_record)); }
+  static int alloc(tj_ctx* c, Args& b, int gc, int gm, std::vector<void*>* l) {
+    int r;
+    if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l))) return r;
+    return TJ_OK;
+  }
+  static int prepare(tj_ctx*, Args&) { return TJ_OK; }
+  // two launches for the count, three for the rows, whatever the fleet's size, the number of pairs and the depth
+  static void mark(tj_ctx* c, const Args& a, int units) { hipLaunchKernelGGL(k_cross_mark, dim3(units), dim3(64), 0, c->stream, c->d, a); }
+  static void rows(tj_ctx* c, const Args& a, int, Rec* out) { hipLaunchKernelGGL(k_cross_refine, dim3(a.ix.cap), dim3(CX_THREADS), 0, c->stream, c->d, a, out); }
+};
+
+// mark the listed pairs, index them (k_pair_index: pair p is the p-th set bit), and, for a call with room, search each: n first, then min(cap, n) rows
+template <class Q>
+int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, typename Q::Rec* rows, int cap, int* n) {
   if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  const std::string name = Q::spec.name;
   int r;
-  if ((r = query_nan(c, "tj_path_crossings", "range", range)) || (r = query_nan(c, "tj_path_crossings", "tol", tol))) return r;
-  if (max_depth > TJ_CROSSING_MAX_DEPTH) { c->err = "tj_path_crossings: max_depth must be 0.." + std::to_string(TJ_CROSSING_MAX_DEPTH) + " (or negative for the default): deeper windows cannot be halved in a double"; return TJ_ERR_INVALID; }
-  if (max_windows > TJ_CROSSING_MAX_WINDOWS) { c->err = "tj_path_crossings: max_windows must be 1.." + std::to_string(TJ_CROSSING_MAX_WINDOWS) + " (or <= 0 for the default)"; return TJ_ERR_INVALID; }
+  SearchArgs sa;
+  if ((r = search_args(c, Q::spec, range, tol, max_depth, max_windows, sa))) return r;
   const Dev& d = c->d;
-  const int mw = max_windows <= 0 ? TJ_CROSSING_FRONTIER : max_windows;
-  if (cross_bytes(cap, mw) > (size_t)TJ_CROSSING_MAX_BYTES) {
-    c->err = "tj_path_crossings: cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw) + " need " + std::to_string(cross_bytes(cap, mw)) + " bytes of device memory, more than TJ_CROSSING_MAX_BYTES (" +
-             std::to_string((long long)TJ_CROSSING_MAX_BYTES) + "): lower cap (rows beyond it are still counted) or max_windows";
+  const int mw = sa.max_windows;
+  if (Q::bytes(d, cap, mw) > (size_t)Q::max_bytes) {
+    c->err = name + ": cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw) + " need " + std::to_string(Q::bytes(d, cap, mw)) + " bytes of device memory, more than " + Q::budget + " (" +
+             std::to_string(Q::max_bytes) + "): lower cap (rows beyond it are still counted) or max_windows";
     return TJ_ERR_INVALID;
   }
-  if ((r = query_state(c, "tj_path_crossings", true, net_host && pt_host))) return r;
+  if ((r = query_state(c, Q::spec.name, true, net_host && pt_host))) return r;
   *n = 0;
   if (!d.multi()) return TJ_OK;   // one UAV: no pair
   const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
   const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
   QUIESCE(c);
-  CrossArgs& b = c->cross;
-  if ((r = query_buf(c, b.mask, mask_n)) || (r = query_buf(c, b.wordoff, mask_n)) || (r = query_buf(c, b.n, 1))) return r;
-  if (cap > c->cross_cap || mw > c->cross_mw) {   // grow: the context is quiet, nothing reads the old buffers
-    for (void* p : c->cross_allocs) hipFree(p);
-    c->cross_allocs.clear();
-    b.who = nullptr; b.list = nullptr; b.klo = nullptr; c->cross_out = nullptr;
-    const int gc = std::max(cap, c->cross_cap), gm = std::max(mw, c->cross_mw);
-    c->cross_cap = -1; c->cross_mw = 0;
-    std::vector<void*>* l = &c->cross_allocs;
-    if ((r = query_buf(c, b.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l)) ||
-        (r = query_buf(c, c->cross_out, gc, l))) return r;
-    c->cross_cap = gc; c->cross_mw = gm;
+  auto& h = Q::held(c);
+  if ((r = query_buf(c, h.mask, mask_n)) || (r = query_buf(c, h.wordoff, mask_n)) || (r = query_buf(c, h.n, 1))) return r;
+  if (cap > h.cap || mw > h.mw) {   // grow: the context is quiet, nothing reads the old buffers; a failure keeps what it got on the list and starts over next time
+    for (void* p : h.allocs) hipFree(p);
+    h.allocs.clear();
+    const int gc = std::max(cap, h.cap), gm = std::max(mw, h.mw);
+    h.sized = typename Q::Args{}; h.out = nullptr; h.cap = -1; h.mw = 0;
+    if ((r = Q::alloc(c, h.sized, gc, gm, &h.allocs)) || (r = query_buf(c, h.out, gc, &h.allocs))) return r;
+    h.cap = gc; h.mw = gm;
   }
-  CrossArgs a = b;
+  typename Q::Args a = h.sized;
   if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
-  a.range = query_range(d, range); a.tol = tol < 0 ? TJ_CROSSING_TOL : tol;
-  a.max_depth = max_depth < 0 ? TJ_CROSSING_MAX_DEPTH : max_depth; a.max_windows = mw; a.cap = cap;
-  a.words = words;
-  if ((r = query_clear(c, a.mask, mask_n)) || (r = query_clear(c, a.n, 1))) return r;
-  if (owned > 0) {   // two launches for the count, three for the rows, whatever the fleet's size, the number of pairs and the depth
-    PairArgs ix{};   // k_pair_index reads the bitmask and writes its offsets, n and the slots' pairs: the same scan, this query's buffers
-    ix.cap = cap; ix.words = words; ix.mask = a.mask; ix.wordoff = a.wordoff; ix.n = a.n; ix.who = a.who;
-    hipLaunchKernelGGL(k_cross_mark, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
-    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, ix);
-    if (cap > 0) hipLaunchKernelGGL(k_cross_refine, dim3(cap), dim3(CX_THREADS), 0, c->stream, d, a, c->cross_out);
+  sa.put(a);
+  a.ix.cap = cap; a.ix.words = words; a.ix.mask = h.mask; a.ix.wordoff = h.wordoff; a.ix.n = h.n;
+  if ((r = query_clear(c, h.mask, mask_n)) || (r = query_clear(c, h.n, 1)) || (r = Q::prepare(c, a))) return r;
+  if (owned > 0) {
+    Q::mark(c, a, owned * d.S);
+    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, a.ix);
+    if (cap > 0) Q::rows(c, a, owned * d.S, h.out);
   }
-  if ((r = query_fetch(c, n, a.n, 1)) || (r = query_finish(c, nullptr))) return r;
-  if ((r = query_fetch(c, rows, c->cross_out, std::min(cap, *n))) || (r = query_finish(c, nullptr))) return r;
-  if (*n > cap && rows) { c->err = "tj_path_crossings: " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
+  if ((r = query_fetch(c, n, h.n, 1)) || (r = query_finish(c, nullptr))) return r;
+  if ((r = query_fetch(c, rows, h.out, std::min(cap, *n))) || (r = query_finish(c, nullptr))) return r;
+  if (*n > cap && rows) { c->err = name + ": " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
   return TJ_OK;
 }
 
@@ -1598,25 +1601,25 @@ int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_h
 }
 }  // namespace
 
+extern "C" {
+
 int tj_audit(tj_ctx* c, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) { return audit_run(c, range, nullptr, out, seg_obs, seg_pair); }
 int tj_audit_record_size(void) { return (int)sizeof(tj_audit_robot); }
 int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* records, double* seg_lo, double* seg_hi) { return audit_timed_run(c, range, levels, nullptr, nullptr, records, seg_lo, seg_hi); }
 int tj_audit_timed_record_size(void) { return (int)sizeof(tj_audit_timed_robot); }
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records) { return closest_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, records); }
 int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
-int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return pair_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
+int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return listed_run<PairQuery>(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
 int tj_pair_record_size(void) { return (int)sizeof(tj_pair_record); }
-int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) { return cross_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
+int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) { return listed_run<CrossQuery>(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
 int tj_crossing_record_size(void) { return (int)sizeof(tj_crossing_record); }
 
 // tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
   if (!c || !out) return TJ_ERR_INVALID;
   int r;
-  if ((r = query_nan(c, "tj_obstacle_approach", "range", range)) || (r = query_nan(c, "tj_obstacle_approach", "tol", tol))) return r;
-  if (max_depth > TJ_OBSTACLE_MAX_DEPTH) { c->err = "tj_obstacle_approach: max_depth must be 0.." + std::to_string(TJ_OBSTACLE_MAX_DEPTH) + " (or negative for the default): deeper windows are not dyadic in a double"; return TJ_ERR_INVALID; }
-  if (max_windows > TJ_OBSTACLE_FRONTIER) { c->err = "tj_obstacle_approach: max_windows must be 1.." + std::to_string(TJ_OBSTACLE_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
-  if ((r = query_state(c, "tj_obstacle_approach", false, false))) return r;
+  SearchArgs sa;
+  if ((r = search_args(c, SEARCH_OBSTACLE, range, tol, max_depth, max_windows, sa)) || (r = query_state(c, "tj_obstacle_approach", false, false))) return r;
   const Dev& d = c->d;
   const int owned = d.u1 - d.u0;
   const size_t rows = (size_t)d.U * d.S, items = (size_t)(owned > 0 ? owned : 1) * 2 * TJ_OBSTACLE_FRONTIER;
@@ -1627,8 +1630,7 @@ int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int
   ObstArgs a = b;
   Dev da;
   if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = walk_dev(c, da))) return r;
-  a.order = c->q_order; a.range = query_range(d, range); a.tol = tol < 0 ? TJ_OBSTACLE_TOL : tol;
-  a.max_depth = max_depth < 0 ? TJ_OBSTACLE_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_OBSTACLE_FRONTIER : max_windows; a.cap = TJ_OBSTACLE_FRONTIER;
+  a.order = c->q_order; sa.put(a); a.cap = TJ_OBSTACLE_FRONTIER;
   if ((r = query_clear(c, c->obst_out, d.U)) || (r = query_clear(c, a.count, (size_t)d.U * 2))) return r;
   if (owned > 0)   // three launches whatever the fleet's size, the number of primitives and the depth
     with_prim(d, [&](auto prim) {

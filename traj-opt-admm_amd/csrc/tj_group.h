@@ -646,6 +646,25 @@ int group_query(tj_group* g, bool nets, bool pts, Rec* out, GroupRows rows0, Gro
 // a scratch copy of a per-segment array the caller asked for (null: not asked for, nothing to scatter)
 static std::vector<double> group_rows(const tj_group* g, const double* wanted) { return std::vector<double>(g && wanted ? (size_t)g->ctx[0]->d.U * g->ctx[0]->d.S : 0); }
 
+// gather: the rows of a row-listing query (listed_run), rank after rank
+template <class Q>
+int group_listed(tj_group* g, double range, double tol, int max_depth, int max_windows, typename Q::Rec* rows, int cap, int* n) {
+  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int total = 0;
+  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    const int room = std::max(0, cap - total);
+    int nr = 0;
+    const int e = listed_run<Q>(c, range, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, room, &nr);
+    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
+    total += nr;
+    return (int)TJ_OK;
+  });
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, std::string(Q::spec.group_name) + ": " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 extern "C" {
 
 int tj_group_audit(tj_group* g, double range, tj_audit_robot* out, double* seg_obs, double* seg_pair) {
@@ -665,41 +684,13 @@ int tj_group_closest_approach(tj_group* g, double range, double tol, int max_dep
     return closest_run(c, range, tol, max_depth, max_windows, net, pt, part); });
 }
 
-// the ranks' lists one after the other: ownership is by contiguous robot blocks in rank order, so that is the (robot, partner) order.  A rank whose rows do not fit
-// writes the first that do and is counted in full; the ranks behind it only count.
+// the ranks' lists one after the other: ownership is by contiguous robot blocks in rank order, so that is the (robot, partner) order (tj_path_crossings: the rows
+// (u, q > u) by u's owner).  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.
 int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) {
-  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
-  int total = 0;
-  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
-    const int room = std::max(0, cap - total);
-    int nr = 0;
-    const int e = pair_run(c, range, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, room, &nr);
-    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
-    total += nr;
-    return (int)TJ_OK;
-  });
-  if (rc < 0) return rc;
-  *n = total;
-  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_pair_approach: " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
-  return TJ_OK;
+  return group_listed<PairQuery>(g, range, tol, max_depth, max_windows, rows, cap, n);
 }
-
-// the rows (u, q > u) by u's owner, the ranks' lists one after the other as above
 int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) {
-  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
-  int total = 0;
-  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
-    const int room = std::max(0, cap - total);
-    int nr = 0;
-    const int e = cross_run(c, range, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, room, &nr);
-    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
-    total += nr;
-    return (int)TJ_OK;
-  });
-  if (rc < 0) return rc;
-  *n = total;
-  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_path_crossings: " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
-  return TJ_OK;
+  return group_listed<CrossQuery>(g, range, tol, max_depth, max_windows, rows, cap, n);
 }
 
 // from every rank's own state: nothing of another robot is read

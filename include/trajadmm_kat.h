@@ -46,6 +46,11 @@ int tj_kat_query_form(tj_ctx* c, int nq, const double* boxes, double margin, int
 int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double* tri, const double* t, double dist, double off, double* out);
 /* dense LLT failure test + smallest eigenvalue (Eigen LLT / SelfAdjointEigenSolver as used at Gradient_admm.h:38-53): out[nmat][2] */
 int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out);
+/* the per-piece gradient and Hessian blocks of the whole fleet, written from the host: lg[U][P][19], lh[U][P][361] (row-major 19 x 19; local 0..17 = global
+ * coordinates 9 piece .. 9 piece + 17, local 18 = the time variable) -- what tj_get_local_grad reads back and the only input of the Newton solve.  With
+ * tj_run_stage(TJ_STAGE_XSOLVE) and tj_get_direction this feeds the product's own solve kernels any system.  Pending work of the context is waited for, no
+ * kernel is launched.  TJ_ERR_INVALID: a null argument, or a context without cloud / state. */
+int tj_kat_set_local_grad(tj_ctx* c, const double* lg, const double* lh);
 
 /* ---- the launch plan (csrc/host_plan.h) ------------------------------------------------------------
  * A flat record of ints: the device facts the plan was decided on (PlanFacts), then every decision of the plan, the LDS byte counts, the queue

@@ -271,7 +271,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -691,6 +691,14 @@ class Solver:
         out = np.zeros((mats.shape[0], 2))
         self._check(self.lib.tj_kat_linalg(self._ctx, C.c_int(mats.shape[0]), C.c_int(mats.shape[1]), _d(mats), _d(out)))
         return out
+
+    def kat_set_local_grad(self, lg, lh):
+        """the per-piece blocks of the whole fleet from the host (tj_kat_set_local_grad): lg[U][P][19], lh[U][P][19][19] -- what local_grad reads back and
+        run_stage("xsolve") solves"""
+        lg = np.ascontiguousarray(lg, dtype=np.float64); lh = np.ascontiguousarray(lh, dtype=np.float64)
+        if lg.size != self.U * self.P * 19 or lh.size != self.U * self.P * 361:
+            raise ValueError(f"kat_set_local_grad: lg[{self.U}][{self.P}][19] and lh[{self.U}][{self.P}][361] expected")
+        self._check(self.lib.tj_kat_set_local_grad(self._ctx, _d(lg), _d(lh)))
 
     def energy(self):
         """Energy_admm::spline_energy of every owned robot at the current state (planes of the last iteration)"""

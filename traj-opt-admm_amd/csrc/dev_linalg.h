@@ -382,12 +382,15 @@ constexpr int STURM_ROUNDS = 9;   // 64-way multisection: 65^9 > 2^54 subdivisio
                                   // matrix norm, so the result is good to ~1e-16 of the norm; the parity bar is 1e-12 of it)
 
 // Smallest eigenvalue of the symmetric row-major n x n matrix A (lower triangle authoritative;
-// A is destroyed).  d,e,v,p are LDS scratch of length n.  Called by the whole block.
+// A is destroyed).  d,e,v,p are LDS scratch of length n.  Called by the whole block -- or, ONE_WAVE, by the one wave that is left working on the
+// matrix while the block's other waves wait at a barrier of their own (k_xsolve's helpers ahead of the swept-hull tail): its sync points are then
+// wave-local, since an s_barrier here would count as the arrival the waiting waves are held for and let them into the tail, whose staging overwrites A.
+template <bool ONE_WAVE = false>
 __device__ inline double min_eig_lds(double* A, int n, double* d, double* e, double* v, double* p, int tid, int nth) {
   __shared__ double s_scal[4];
   // mirror lower -> upper so that rows can be read contiguously
   for (int idx = tid; idx < n * n; idx += nth) { int i = idx / n, j = idx % n; if (j > i) A[i * n + j] = A[j * n + i]; }
-  __syncthreads();
+  blk_sync<ONE_WAVE>();
   for (int k = 0; k + 2 < n; k++) {
     const int m = n - k - 1;  // size of trailing block, rows/cols k+1..n-1
     if (tid == 0) {
@@ -404,29 +407,29 @@ __device__ inline double min_eig_lds(double* A, int n, double* d, double* e, dou
         s_scal[2] = v0;
       }
     }
-    __syncthreads();
+    blk_sync<ONE_WAVE>();
     const double beta = s_scal[0];
     if (tid == 0) { d[k] = A[k * n + k]; e[k] = s_scal[1]; }
     if (beta != 0) {
       for (int i = tid; i < m; i += nth) v[i] = (i == 0) ? s_scal[2] : A[(k + 1 + i) * n + k];
-      __syncthreads();
+      blk_sync<ONE_WAVE>();
       for (int i = tid; i < m; i += nth) {
         double acc = 0;
         for (int j = 0; j < m; j++) acc += A[(k + 1 + i) * n + (k + 1 + j)] * v[j];
         p[i] = beta * acc;
       }
-      __syncthreads();
+      blk_sync<ONE_WAVE>();
       if (tid == 0) { double kk = 0; for (int i = 0; i < m; i++) kk += v[i] * p[i]; s_scal[3] = 0.5 * beta * kk; }
-      __syncthreads();
+      blk_sync<ONE_WAVE>();
       const double K = s_scal[3];
       for (int i = tid; i < m; i += nth) p[i] = p[i] - K * v[i];  // q
-      __syncthreads();
+      blk_sync<ONE_WAVE>();
       for (int idx = tid; idx < m * m; idx += nth) {
         const int i = idx / m, j = idx % m;
         A[(k + 1 + i) * n + (k + 1 + j)] -= v[i] * p[j] + p[i] * v[j];
       }
     }
-    __syncthreads();
+    blk_sync<ONE_WAVE>();
   }
   if (tid == 0) {
     if (n >= 2) { d[n - 2] = A[(n - 2) * n + (n - 2)]; e[n - 2] = A[(n - 1) * n + (n - 2)]; }
@@ -439,12 +442,12 @@ __device__ inline double min_eig_lds(double* A, int n, double* d, double* e, dou
     }
     s_scal[0] = lo; s_scal[1] = hi;
   }
-  __syncthreads();
+  blk_sync<ONE_WAVE>();
   // multisection on the Sturm count "#eigenvalues < x >= 1"; lanes 0..63 of the first wave
   const SturmScale sc = sturm_scale(s_scal[0], s_scal[1]);
   for (int round = 0; round < STURM_ROUNDS; round++) {
     const double lo = s_scal[0], hi = s_scal[1];
-    __syncthreads();
+    blk_sync<ONE_WAVE>();
     if (tid < 64) {
       const double x = lo + (hi - lo) * (double(tid + 1) / 65.0);
       double p0, p1; bool below;
@@ -460,10 +463,10 @@ __device__ inline double min_eig_lds(double* A, int n, double* d, double* e, dou
         }
       }
     }
-    __syncthreads();
+    blk_sync<ONE_WAVE>();
   }
   const double r = 0.5 * (s_scal[0] + s_scal[1]);
-  __syncthreads();
+  blk_sync<ONE_WAVE>();
   return r;
 }
 

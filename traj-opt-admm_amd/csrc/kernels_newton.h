@@ -679,7 +679,7 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
     if (D.mode == 1) {  // multi: eigen-shift fallback (Optimization3D_multi.h:703-719); single has none
       for (int idx = tid; idx < n * n; idx += XS_THREADS) L[idx] = H[idx];
       blk_sync<true>();
-      const double ev = min_eig_lds(L, n, scr, scr + n, scr + 2 * n, scr + 3 * n, tid, XS_THREADS);
+      const double ev = min_eig_lds<true>(L, n, scr, scr + n, scr + 2 * n, scr + 3 * n, tid, XS_THREADS);   // (wave-local sync points: the helper waves sit at the tail's barrier)
       if (ev < 0) for (int i = tid; i < n; i += XS_THREADS) H[i * n + i] = H[i * n + i] - ev * 1.0 + 0.01 * 1.0;
       blk_sync<true>();
     }
@@ -1043,22 +1043,21 @@ __global__ __launch_bounds__(XB_THREADS) void k_xsolve_band(Dev D) {
   __syncthreads();
   if (!s_ok) {
     if (tid == 0) atomicAdd(&D.ctl->llt_fail_robot, 1ull);
-    double shift = 0;
+    double ev = 0;
     if (D.mode == 1) {   // dense copy in HBM scratch -> smallest eigenvalue -> shift the diagonal (whole block cooperates)
       double* Hd = D.xs_scr + (size_t)blockIdx.x * ((size_t)n * n + 4 * n);
       double* sc = Hd + (size_t)n * n;
       for (int idx = tid; idx < n * n; idx += XB_THREADS) { const int i = idx / n, j = idx % n; Hd[idx] = xb_entry(gh, D.P, i == m ? -1 : i + 6, j == m ? -1 : j + 6); }
       __threadfence_block();
       __syncthreads();
-      const double ev = min_eig_lds(Hd, n, sc, sc + n, sc + 2 * n, sc + 3 * n, tid, XB_THREADS);
-      if (ev < 0) shift = -ev * 1.0 + 0.01 * 1.0;
+      ev = min_eig_lds(Hd, n, sc, sc + n, sc + 2 * n, sc + 3 * n, tid, XB_THREADS);
     }
     __syncthreads();
     assemble();
     __syncthreads();
-    if (shift != 0) {
-      for (int i = tid; i < m; i += XB_THREADS) Bd[i * BS + BS - 1] = Bd[i * BS + BS - 1] + shift;   // h0 - ev*I + 0.01*I, entry by entry like the dense kernel
-      if (tid == 0) Ar[m] = Ar[m] + shift;
+    if (ev < 0) {   // h0 - ev*I + 0.01*I, entry by entry and in the dense kernel's association, (h - ev) + 0.01: a shift summed first rounds differently
+      for (int i = tid; i < m; i += XB_THREADS) Bd[i * BS + BS - 1] = Bd[i * BS + BS - 1] - ev * 1.0 + 0.01 * 1.0;
+      if (tid == 0) Ar[m] = Ar[m] - ev * 1.0 + 0.01 * 1.0;
     }
     __syncthreads();
     if (tid < 64) chol_band_lds(Bd, Ar, n, tid, y);   // like the reference, the second factorisation is not re-checked

@@ -2078,6 +2078,17 @@ int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out) {
   return TJ_OK;
 }
 
+// the counterpart of tj_get_local_grad for the whole fleet: the per-piece blocks k_xsolve / k_xsolve_band read, from the host.  No kernel runs
+int tj_kat_set_local_grad(tj_ctx* c, const double* lg, const double* lh) {
+  if (!c || !lg || !lh) return TJ_ERR_INVALID;
+  if (!ready(c)) return TJ_ERR_INVALID;
+  const Dev& d = c->d;
+  QUIESCE(c);
+  const size_t blocks = (size_t)d.U * d.P;
+  { int ur; if ((ur = upload(c, d.lg, lg, blocks * 19 * 8)) || (ur = upload(c, d.lh, lh, blocks * 361 * 8))) return ur; }
+  return TJ_OK;
+}
+
 #endif  // TJ_KAT
 
 int tj_get_build_info(tj_ctx* c, double* bvh_build_ms, int* built_on_device) {

@@ -398,7 +398,7 @@ int tj_pair_record_size(void);   /* sizeof(tj_pair_record) */
  *   rows     sorted by (robot, partner) ascending; neither the order of evaluation nor that of any atomic append is visible in the output.
  * ROBOT_END / PARTNER_END: the hi sample is that robot's LAST control point (segment == S - 1, parameter == 1.0).  The robot stays at that point after
  * arriving (tj_audit_timed's hover), so partner_time - time then UNDERSTATES how long the two are near: the other robot must not pass that place at any
- * later time either.
+ * later time either.  tj_timing_margin gives the slip such a pair tolerates, with the arrived robot's stay counted.
  * *n is the number of listed pairs.  *n > cap: TJ_ERR_CAPACITY, the first `cap` rows in order have been written and *n says what to allocate; cap = 0 with
  * rows == NULL is a valid count-only call.  range <= 0: offset + 2 * margin; +infinity is valid.  tol < 0: TJ_CROSSING_TOL; 0 is valid.  max_depth < 0:
  * TJ_CROSSING_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0: TJ_CROSSING_FRONTIER; above TJ_CROSSING_MAX_WINDOWS TJ_ERR_INVALID.  NaN range or tol,
@@ -452,6 +452,90 @@ typedef struct tj_crossing_record {
 } tj_crossing_record;
 int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n);
 int tj_crossing_record_size(void);   /* sizeof(tj_crossing_record) */
+/* ---- tj_timing_margin: by how much may one robot run late or early against another before the two come within `dist`
+ * (csrc/kernels_timing_margin.h; read-only like tj_path_crossings).  The timed queries say how close two robots come ON the timetable, tj_path_crossings how
+ * close their paths are whatever the time; its partner_time - time is the timing gap at the spatially closest place, which overstates what the timetable
+ * tolerates: contact begins at distance `dist`, not 0, and a robot that has arrived stays at its goal.  Here the objective is a TIME under a distance
+ * constraint: one row per UNORDERED pair (u, q), u < q, u owned.
+ *   clock    robot r at parameter s of segment g has the clock value T_r(g, s) = ((g + s) / res) * piece_time[r] (the expression used wherever a time is
+ *            formed).  The last control point (g == S - 1, s == 1.0) has the clock set [T, +inf): the robot stays there (tj_audit_timed's hover).  Every other
+ *            point has the one-value set {T}.  (Waiting at the start needs no set: a start's {0} gives the same gaps, every other clock being >= 0.)
+ *   slip     of two points: the distance of their clock sets, max(0, lo_u - hi_q, lo_q - hi_u).
+ *   margin   of the pair: the infimum of the slip over all (x on u's path, y on q's path) with |x - y| <= dist.  0: the two are within dist at equal flight
+ *            times (one passing the other's goal after its arrival included).  +inf, or no row: the paths never come within dist.
+ *   item     tj_path_crossings': (tr, j, [sa, sb], [ra, rb]), dyadic windows, both nets restricted from the RAW hulls by blossoming.
+ *   OUT      lo(W) of tj_path_crossings (the GJK's |v| with its certificate, 0 without one) > dist: the item holds no contact, klo(W) = +inf.
+ *   klo(W)   not OUT: the distance of the windows' clock intervals, max(0, ta_u - tb_q, ta_q - tb_u), ta = T(segment, window's start), tb = T(segment,
+ *            window's end), or +inf where the window ends on the last control point.  The objective is linear in the parameters: exact as the window shrinks.
+ *   corners  the four end-point pairs i, k in {0, 5}: a candidate where norm3(a_i - b_k) <= dist, with the slip of the two corner points.
+ *   same time   only for an item that is not OUT with klo == 0 (its clock intervals overlap): tau = fmax(fmax(ta_u, ta_q), 0.0); each robot's parameter
+ *            x = (tau - T(g, 0)) / (T(g + 1, 0) - T(g, 0)) clamped into the item's own window (tj_flight_profile's expressions); its position is b_0 of the
+ *            raw hull restricted to [x, x].  Within dist: a candidate with slip 0.0 -- stated, not computed -- flagged SAME_TIME.  Without it an equal-time
+ *            contact is never found: dyadic parameters of two robots with different piece_time never give equal clocks.
+ *   order    candidates with slip < max_slip, by the total order (slip, segment, partner_segment, s, partner_s); of a corner and a same-time candidate at the
+ *            same place the corner goes first.
+ *   seeds    every (tr, j) whose raw hull boxes pass tj_audit's box test at dist, full windows, evaluated like a round's children.
+ *   listed   (u, q) has a row if and only if some seed has a candidate, or is not OUT with klo < max_slip.  A pair without a row is certified: no slip below
+ *            max_slip brings the two within dist.
+ *   round    tj_path_crossings': every live item into its four quadrants, all children evaluated, best (the smallest slip) over the whole round, and the
+ *            children with klo < best.hi are kept -- strict, against the round's FINAL best.  Nothing found: hi = max_slip.
+ *   bracket  lo = min(best.hi, min of klo over the live set), hi = best.hi, both in seconds.
+ *   stop     hi - lo <= tol (CONVERGED) | the live set is empty (CONVERGED) | depth == max_depth | more than max_windows live (TRUNCATED: the record of the
+ *            last completed round; `windows` counts the overflowing round's work too).
+ *   record   lo <= the pair's margin <= hi.  `distance` (<= dist) is that of the hi sample: u's curve at `s` of `segment` from q's at `partner_s` of
+ *            `partner_segment`; time = T(segment, s), partner_time = T(partner_segment, partner_s).  No sample found: segments -1, parameters, times and
+ *            distance -1.0, hi == max_slip.  depth: rounds completed.  windows: seeds evaluated + 4 per split item.  Rows sorted by (robot, partner).
+ * *n, cap, the count-only call and TJ_ERR_CAPACITY as in tj_path_crossings.  dist <= 0: offset.  max_slip <= 0: +infinity.  tol < 0:
+ * TJ_MARGIN_TOL_FRACTION * dist / vel_limit -- the margin is resolved to the time a robot at the speed limit needs for 1 % of the contact distance, 5e-4 s at
+ * the shipped parameters: a design condition, stated as such; 0 is valid.  max_depth < 0: TJ_MARGIN_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0:
+ * TJ_MARGIN_FRONTIER; above TJ_MARGIN_MAX_WINDOWS TJ_ERR_INVALID.  NaN dist, max_slip or tol, n == NULL, cap < 0, rows == NULL with cap > 0, a call before
+ * tj_init_state: TJ_ERR_INVALID.  Single-UAV mode: *n = 0 and TJ_OK.  A plain SHARDED context (world > 1) returns TJ_ERR_UNSUPPORTED;
+ * tj_group_timing_margin computes the rows (u, q > u) on u's owner with control points and piece_time read from the owners, and is bitwise one context's.
+ * DEVICE MEMORY grows only and is a function of cap and max_windows alone:
+ *   cap * (2 * max_windows * 48 + 4 * max_windows * 8 + 8 + 88) bytes     (live lists, their children's klo, the slots' pairs and the rows)
+ * plus the bitmask and its offsets, owned * ceil(uav_num / 32) * 8 bytes.  A call whose figure exceeds TJ_MARGIN_MAX_BYTES is refused up front with
+ * TJ_ERR_INVALID.  At most THREE launches whatever the fleet's size, the number of pairs and the depth (two for a count-only call).  Changes no solver
+ * state, statistics or launch count.
+ * STATED LIMITS.  (1) The optimum lies ON the boundary distance == dist, and that boundary is tangent there to the objective's level line, so the live set
+ * grows by about sqrt(2) per round (3 -> 43 -> 1185 items at depths 0, 9 and 19 for two perpendicular straight paths) while the bracket halves: this query
+ * ends at a tolerance in time and does not run to rounding.  (2) Paths that run alongside each other at about dist grow faster and end TRUNCATED; the
+ * bracket returned is still sound.  (3) tj_path_crossings' limit 1, the GJK's 1e-10 relative, applies to the OUT decision.
+ * The defaults are measured (tests/timing_margin_ref.py default_tolerance, the restatement, on the CPU): default dist, max_slip = +inf, the default tol,
+ * max_depth = 40, the live set capped at TJ_MARGIN_MAX_WINDOWS only, on the final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz,
+ * e2e_scn_b_coupled.npz, of e2e_scn_c3.npz with z set to 0 (_flat: the fleet meets at one place at one time) and of that with piece_time[u] *= 1 + 0.03 * u
+ * (_flat_staggered):
+ *   state                       listed pairs   rows with hi == 0   truncated rows   largest live set   largest depth   widest bracket
+ *   e2e_scn_b                   0              0                   0                0                  0               0.00e+00
+ *   e2e_scn_c3                  0              0                   0                0                  0               0.00e+00
+ *   e2e_scn_b_coupled           0              0                   0                0                  0               0.00e+00
+ *   e2e_scn_c3_flat             2016           2016                0                0                  0               0.00e+00
+ *   e2e_scn_c3_flat_staggered   2016           1                   0                2921               12              5.00e-04
+ * The stacked fleets list nothing at dist = offset: they are apart in space.  The flattened fleet meets at one place at one time: every pair is found at slip 0
+ * among the seeds.  Staggered, the slips range from 0 to 10.12 s; no row truncates at TJ_MARGIN_MAX_WINDOWS at the default tolerance, and every bracket
+ * closes below it by depth 12.  At tol = 1e-6 instead, 47 of 119 pairs (every 17th) truncate with brackets up to 3.9e-4 wide (limit 1): the reason the
+ * default is a tolerance in time and not a rounding floor.
+ * TJ_MARGIN_FRONTIER is the next power of two >= 2 x the largest live set, at least 64, capped at TJ_MARGIN_MAX_WINDOWS. */
+#define TJ_MARGIN_CONTACT     1    /* a sample was found and hi <= 0: the two are within dist on the timetable */
+#define TJ_MARGIN_CLEAR       2    /* lo > 0: a positive margin is certified */
+#define TJ_MARGIN_CONVERGED   4    /* hi - lo <= tol, or nothing was left that could hold a smaller slip */
+#define TJ_MARGIN_TRUNCATED   8    /* the pair's live set outgrew max_windows: the bracket of the last completed round is returned */
+#define TJ_MARGIN_ROBOT_END   16   /* the hi sample is robot's last control point */
+#define TJ_MARGIN_PARTNER_END 32   /* the same for partner */
+#define TJ_MARGIN_SAME_TIME   64   /* the hi sample is a same-time candidate: slip 0.0 stated */
+#define TJ_MARGIN_MAX_DEPTH 40
+#define TJ_MARGIN_FRONTIER  4096
+#define TJ_MARGIN_MAX_WINDOWS 4096
+#define TJ_MARGIN_MAX_BYTES (1ll << 31)
+#define TJ_MARGIN_TOL_FRACTION 0.01
+typedef struct tj_margin_record {
+  double lo, hi;                  /* lo <= the slip the pair tolerates before coming within dist <= hi, in seconds */
+  double distance;                /* of the hi sample, <= dist */
+  double s, partner_s;            /* local parameters of the hi sample in `segment` and `partner_segment` */
+  double time, partner_time;      /* the clock values of the hi sample */
+  int robot, partner, segment, partner_segment, depth, flags, windows, reserved;
+} tj_margin_record;
+int tj_timing_margin(tj_ctx* c, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n);
+int tj_margin_record_size(void);   /* sizeof(tj_margin_record) */
 /* ---- tj_obstacle_approach: how close the FLOWN CURVE of every robot comes to an obstacle primitive, when, and to which one, converged to a tolerance the
  * caller names (csrc/kernels_obstacle_approach.h; read-only like tj_audit).  tj_audit's obs_clearance is the distance of a segment's 6-point hull: what the
  * solver constrains and the right certificate for a converged state, but only a lower bound on what the vehicle does, without a time, and on the GJK's
@@ -717,6 +801,7 @@ int tj_group_audit_timed(tj_group* g, double range, int levels, tj_audit_timed_r
 int tj_group_closest_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records);   /* tj_closest_approach of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);   /* tj_pair_approach of every robot by its owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n);   /* tj_path_crossings of every pair (u, q > u) by u's owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
+int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n);   /* tj_timing_margin of every pair (u, q > u) by u's owner, in the same way */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */

@@ -36,6 +36,7 @@ EXPORTS = [
     "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
     "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
     "tj_path_crossings", "tj_crossing_record_size", "tj_group_path_crossings",
+    "tj_timing_margin", "tj_margin_record_size", "tj_group_timing_margin",
     "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
 ]
 
@@ -183,6 +184,20 @@ CROSSING_FRONTIER = 256        # TJ_CROSSING_FRONTIER: what max_windows=None sel
 CROSSING_MAX_WINDOWS = 4096    # TJ_CROSSING_MAX_WINDOWS
 
 
+class TjMarginRecord(C.Structure):
+    """mirror of tj_margin_record (include/trajadmm.h); tj_margin_record_size() is its sizeof on the C side"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("distance", C.c_double), ("s", C.c_double), ("partner_s", C.c_double), ("time", C.c_double),
+                ("partner_time", C.c_double), ("robot", C.c_int), ("partner", C.c_int), ("segment", C.c_int), ("partner_segment", C.c_int), ("depth", C.c_int),
+                ("flags", C.c_int), ("windows", C.c_int), ("reserved", C.c_int)]
+
+
+MARGIN_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8, robot_end=16, partner_end=32, same_time=64)
+MARGIN_TOL_FRACTION = 0.01   # TJ_MARGIN_TOL_FRACTION: tol=None selects this fraction of dist over vel_limit, a time
+MARGIN_MAX_DEPTH = 40        # TJ_MARGIN_MAX_DEPTH
+MARGIN_FRONTIER = 4096       # TJ_MARGIN_FRONTIER: what max_windows=None selects
+MARGIN_MAX_WINDOWS = 4096    # TJ_MARGIN_MAX_WINDOWS
+
+
 class TjProfileSample(C.Structure):
     """mirror of tj_profile_sample (include/trajadmm.h); tj_flight_profile_record_size() is its sizeof on the C side"""
     _fields_ = [("time", C.c_double), ("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("obs_distance", C.c_double), ("robot_distance", C.c_double),
@@ -264,6 +279,12 @@ def _path_crossings(call, range, tol, max_depth, max_windows):
     rows = _listed_rows(TjCrossingRecord, call, _search_args(range, tol, max_depth, max_windows))
     rows["gap"] = rows["partner_time"] - rows["time"]
     return rows
+
+
+def _timing_margin(call, dist, max_slip, tol, max_depth, max_windows):
+    """shared by Solver.timing_margin / Group.timing_margin: call(dist, max_slip, tol, max_depth, max_windows, rows, cap, n)"""
+    d, t, md, mw = _search_args(dist, tol, max_depth, max_windows)
+    return _listed_rows(TjMarginRecord, call, (d, C.c_double(0.0 if max_slip is None else float(max_slip)), t, md, mw))
 
 
 class TrajAdmmError(RuntimeError):
@@ -743,6 +764,15 @@ class Solver:
         A sharded solver (world > 1) raises: use Group.path_crossings."""
         return _path_crossings(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_path_crossings(self._ctx, r, t, d, w, rows, cap, n)), range, tol, max_depth, max_windows)
 
+    def timing_margin(self, dist=None, max_slip=None, tol=None, max_depth=None, max_windows=None):
+        """tj_timing_margin: one row per UNORDERED pair robot < partner that some slip of the timetable below `max_slip` (None: any) may bring within `dist`
+        (None: offset): lo <= the slip the pair tolerates <= hi in seconds, converged to `tol` (None: MARGIN_TOL_FRACTION * dist / vel_limit) by the pair's
+        own branch and bound over two windows; hi == 0: within dist on the timetable.  `distance` of the hi sample, its `segment` / `s` / `time` and
+        `partner_segment` / `partner_s` / `partner_time`, `depth`, `windows`, `flags` (MARGIN_FLAGS).  A pair without a row is certified: no slip below
+        max_slip brings the two within dist.  Dict of numpy arrays [n], sorted by (robot, partner).  Read-only.  A sharded solver (world > 1) raises: use
+        Group.timing_margin."""
+        return _timing_margin(lambda *a: self._check(self.lib.tj_timing_margin(self._ctx, *a)), dist, max_slip, tol, max_depth, max_windows)
+
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_obstacle_approach: per robot lo <= closest approach of the FLOWN CURVE to any obstacle primitive <= hi, converged to `tol` (None: OBSTACLE_TOL)
         by a branch and bound over windows of the segments' hulls; `time`, `index` (the caller's point / face index), `segment` of the hi sample (-1 where
@@ -893,6 +923,10 @@ class Group:
     def path_crossings(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_path_crossings: Solver.path_crossings, every pair (u, q > u) from the rank that owns u, in (robot, partner) order (bitwise one context's)"""
         return _path_crossings(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_group_path_crossings(self._g, r, t, d, w, rows, cap, n)), range, tol, max_depth, max_windows)
+
+    def timing_margin(self, dist=None, max_slip=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_timing_margin: Solver.timing_margin, every pair (u, q > u) from the rank that owns u, in (robot, partner) order (bitwise one context's)"""
+        return _timing_margin(lambda *a: self._check(self.lib.tj_group_timing_margin(self._g, *a)), dist, max_slip, tol, max_depth, max_windows)
 
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""

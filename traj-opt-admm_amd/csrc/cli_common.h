@@ -251,6 +251,31 @@ inline int path_crossings_rows(F&& f, double tol, std::vector<tj_crossing_record
   return n ? f(0.0, tol, -1, 0, rows.data(), n, &n) : rc;
 }
 
+// --timing-margin: one line per listed unordered pair, in the library's (robot, partner) order, and the fleet's line: the pairs within dist on the timetable, the
+// pairs with a certified positive margin, and the smallest hi -- the slip the whole fleet tolerates (inf: no pair listed)
+inline void print_timing_margin(const std::vector<tj_margin_record>& rows) {
+  std::cout.precision(17);
+  int contact = 0, positive = 0;
+  double smallest = INFINITY;
+  for (const tj_margin_record& r : rows) {
+    std::cout << "margin uav " << r.robot << " uav " << r.partner << " lo " << r.lo << " hi " << r.hi << " dist " << r.distance << " seg " << r.segment << " s " << r.s << " time " << r.time
+              << " seg " << r.partner_segment << " s " << r.partner_s << " time " << r.partner_time << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    contact += r.flags & TJ_MARGIN_CONTACT ? 1 : 0;
+    positive += !(r.flags & TJ_MARGIN_CONTACT) && (r.flags & TJ_MARGIN_CLEAR) ? 1 : 0;
+    smallest = std::min(smallest, r.hi);
+  }
+  std::cout << "margin fleet listed " << rows.size() << " contact " << contact << " positive " << positive << " smallest " << smallest << std::endl;
+}
+// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle); default dist and max_slip
+template <class F>
+inline int timing_margin_rows(F&& f, double tol, std::vector<tj_margin_record>& rows) {
+  int n = 0;
+  const int rc = f(0.0, 0.0, tol, -1, 0, nullptr, 0, &n);
+  if (rc < 0) return rc;
+  rows.resize(n);
+  return n ? f(0.0, 0.0, tol, -1, 0, rows.data(), n, &n) : rc;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

@@ -30,7 +30,11 @@
 // partner) -- every pair whose PATHS come within the default range in space, whatever the time: the bracket converged to TOL (default the library's), for each
 // of the two robots segment / parameter / time of the closest sample, rounds, windows evaluated, flag word -- and the counts of pairs separated by timing only
 // (contact in space), undecided and separated in space.
-// --flight-profile K [FILE]: after the --path-crossings lines K lines per robot from tj_flight_profile / tj_group_flight_profile on the grid t_k = (k / (K - 1)) * the
+// --timing-margin [TOL]: after the --path-crossings lines one line per LISTED unordered robot pair from tj_timing_margin / tj_group_timing_margin, sorted by (robot,
+// partner) -- every pair whose paths come within `offset` under some slip of the timetable: the slip's bracket in seconds converged to TOL (default the
+// library's), the distance of the hi sample, for each of the two robots its segment / parameter / clock value, rounds, windows evaluated, flag word -- and the
+// fleet's line: pairs listed, in contact on the timetable, with a certified positive margin, and the smallest hi.
+// --flight-profile K [FILE]: after the --timing-margin lines K lines per robot from tj_flight_profile / tj_group_flight_profile on the grid t_k = (k / (K - 1)) * the
 // longest robot's duration (K == 1: t = 0) -- "profile uav t x y z d_obs idx d_robot partner speed accel flags" at 17 digits: position, distance and index of the
 // NEAREST obstacle primitive (no range), distance and index of the nearest other robot at the same time, speed, acceleration, flag word.  With FILE the lines go
 // there instead, without the leading word (the layout of --sample-traj, extended).  Works in the single-UAV main and with --gpus.
@@ -48,7 +52,7 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--flight-profile K [FILE]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--flight-profile K [FILE]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
@@ -57,6 +61,7 @@ int main(int argc, char** argv) {
   bool obstacle = false; double obstacle_tol = -1;
   bool pairs = false; double pairs_tol = -1;
   bool crossings = false; double crossings_tol = -1;
+  bool margins = false; double margins_tol = -1;
   int profile_samples = 0; std::string profile_file;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
@@ -72,6 +77,7 @@ int main(int argc, char** argv) {
     else if (a == "--obstacle-approach") { obstacle = true; if (i + 1 < argc && argv[i + 1][0] != '-') obstacle_tol = atof(argv[++i]); }
     else if (a == "--pair-approach") { pairs = true; if (i + 1 < argc && argv[i + 1][0] != '-') pairs_tol = atof(argv[++i]); }
     else if (a == "--path-crossings") { crossings = true; if (i + 1 < argc && argv[i + 1][0] != '-') crossings_tol = atof(argv[++i]); }
+    else if (a == "--timing-margin") { margins = true; if (i + 1 < argc && argv[i + 1][0] != '-') margins_tol = atof(argv[++i]); }
     else if (a == "--flight-profile" && i + 1 < argc) { profile_samples = atoi(argv[++i]); if (i + 1 < argc && argv[i + 1][0] != '-') profile_file = argv[++i]; if (profile_samples < 1) { std::cerr << "--flight-profile needs K >= 1" << std::endl; return -1; } }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
@@ -217,6 +223,12 @@ int main(int argc, char** argv) {
       chk(tjcli::path_crossings_rows([&](double r, double t, int d, int w, tj_crossing_record* out, int cap, int* n) {
             return group ? tj_group_path_crossings(grp, r, t, d, w, out, cap, n) : tj_path_crossings(ctx, r, t, d, w, out, cap, n); }, crossings_tol, rows), "tj_path_crossings");
       tjcli::print_path_crossings(rows);
+    }
+    if (margins) {
+      std::vector<tj_margin_record> rows;
+      chk(tjcli::timing_margin_rows([&](double r, double m, double t, int d, int w, tj_margin_record* out, int cap, int* n) {
+            return group ? tj_group_timing_margin(grp, r, m, t, d, w, out, cap, n) : tj_timing_margin(ctx, r, m, t, d, w, out, cap, n); }, margins_tol, rows), "tj_timing_margin");
+      tjcli::print_timing_margin(rows);
     }
     if (profile_samples > 0) {
       // the grid: K equal steps over the longest robot's duration, log_data's sum of piece_num times piece_time

@@ -1,4 +1,4 @@
-// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_flight_profile), each piece defined once.
+// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_flight_profile), each piece defined once.
 //
 // Every query works per (owned robot, segment) on the segment's 6-point hull (hull_entry's sums: the bits of the hull cache) and its box, and reduces per-lane candidates
 // with a TOTAL order, so that a result is a function of the state alone: no float atomics, no dependence on the order of evaluation.
@@ -8,7 +8,7 @@
 //   wave_argmin    the smallest (value, key) in lexicographic order over the wave, with whatever travels along
 //   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
 //   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
-//   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the four branch-and-bound queries, and their four common flag bits
+//   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the five branch-and-bound queries, and their four common flag bits
 #pragma once
 #include <limits.h>
 #include "../../include/trajadmm.h"
@@ -235,12 +235,12 @@ __device__ __forceinline__ void bnb_rounds(const Search& s, Shared& sh, double t
   }
 }
 
-// the four flag bits every branch-and-bound record has (the four headers' values agree); a query's own cases and bits stay at its call
+// the four flag bits every branch-and-bound record has (the five headers' values agree); a query's own cases and bits stay at its call
 constexpr int BNB_CONTACT = 1, BNB_CLEAR = 2, BNB_CONVERGED = 4, BNB_TRUNCATED = 8;
-static_assert(TJ_CLOSEST_CONTACT == BNB_CONTACT && TJ_PAIR_CONTACT == BNB_CONTACT && TJ_OBSTACLE_CONTACT == BNB_CONTACT && TJ_CROSSING_CONTACT == BNB_CONTACT, "CONTACT");
-static_assert(TJ_CLOSEST_CLEAR == BNB_CLEAR && TJ_PAIR_CLEAR == BNB_CLEAR && TJ_OBSTACLE_CLEAR == BNB_CLEAR && TJ_CROSSING_CLEAR == BNB_CLEAR, "CLEAR");
-static_assert(TJ_CLOSEST_CONVERGED == BNB_CONVERGED && TJ_PAIR_CONVERGED == BNB_CONVERGED && TJ_OBSTACLE_CONVERGED == BNB_CONVERGED && TJ_CROSSING_CONVERGED == BNB_CONVERGED, "CONVERGED");
-static_assert(TJ_CLOSEST_TRUNCATED == BNB_TRUNCATED && TJ_PAIR_TRUNCATED == BNB_TRUNCATED && TJ_OBSTACLE_TRUNCATED == BNB_TRUNCATED && TJ_CROSSING_TRUNCATED == BNB_TRUNCATED, "TRUNCATED");
+static_assert(TJ_CLOSEST_CONTACT == BNB_CONTACT && TJ_PAIR_CONTACT == BNB_CONTACT && TJ_OBSTACLE_CONTACT == BNB_CONTACT && TJ_CROSSING_CONTACT == BNB_CONTACT && TJ_MARGIN_CONTACT == BNB_CONTACT, "CONTACT");
+static_assert(TJ_CLOSEST_CLEAR == BNB_CLEAR && TJ_PAIR_CLEAR == BNB_CLEAR && TJ_OBSTACLE_CLEAR == BNB_CLEAR && TJ_CROSSING_CLEAR == BNB_CLEAR && TJ_MARGIN_CLEAR == BNB_CLEAR, "CLEAR");
+static_assert(TJ_CLOSEST_CONVERGED == BNB_CONVERGED && TJ_PAIR_CONVERGED == BNB_CONVERGED && TJ_OBSTACLE_CONVERGED == BNB_CONVERGED && TJ_CROSSING_CONVERGED == BNB_CONVERGED && TJ_MARGIN_CONVERGED == BNB_CONVERGED, "CONVERGED");
+static_assert(TJ_CLOSEST_TRUNCATED == BNB_TRUNCATED && TJ_PAIR_TRUNCATED == BNB_TRUNCATED && TJ_OBSTACLE_TRUNCATED == BNB_TRUNCATED && TJ_CROSSING_TRUNCATED == BNB_TRUNCATED && TJ_MARGIN_TRUNCATED == BNB_TRUNCATED, "TRUNCATED");
 __device__ __forceinline__ int bnb_flags(bool found, double hi, double lo, double tol, int n, bool truncated, double offset) {
   return (found && hi <= offset ? BNB_CONTACT : 0) | (lo > offset ? BNB_CLEAR : 0) | (hi - lo <= tol || (n == 0 && !truncated) ? BNB_CONVERGED : 0) | (truncated ? BNB_TRUNCATED : 0);
 }

@@ -38,6 +38,7 @@
 #include "kernels_obstacle_approach.h"
 #include "kernels_pair_approach.h"
 #include "kernels_path_crossing.h"
+#include "kernels_timing_margin.h"
 #include "kernels_flight_profile.h"
 #include "host_plan.h"
 
@@ -67,7 +68,7 @@ struct CrossQueue {
 // only.  Device half: the regions of `tab` and the control block, copied to an arena of tj_create (in_begin: taken by the next k_begin).  Host half: the flags that describe it.
 struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bool in_begin = false; bool begin_folded = false, maybe_deferred = false; int lsc_base = 0; };
 
-// what a context holds for a row-listing query (tj_pair_approach, tj_path_crossings; listed_run)
+// what a context holds for a row-listing query (tj_pair_approach, tj_path_crossings, tj_timing_margin; listed_run)
 template <class Args, class Rec>
 struct Listed { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; Args sized{}; Rec* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
 
@@ -116,6 +117,7 @@ struct tj_ctx {
   // max_windows (the other buffers of `sized`, and out) grows with the largest call so far (cap, mw) and lives in allocs
   Listed<PairArgs, tj_pair_record> pair;
   Listed<CrossArgs, tj_crossing_record> cross;
+  Listed<MarginArgs, tj_margin_record> margin;
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -770,6 +772,7 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->cloud_allocs) hipFree(p);
   for (void* p : c->pair.allocs) hipFree(p);
   for (void* p : c->cross.allocs) hipFree(p);
+  for (void* p : c->margin.allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1306,7 +1309,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the seven (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_flight_profile.h) ----
+// ---- the read-only queries: one path for the eight (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_flight_profile.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1325,13 +1328,17 @@ int query_state(tj_ctx* c, const char* name, bool owners, bool handed_in) {
 double query_range(const Dev& d, double range) { return range > 0 ? range : d.offset + 2 * d.margin; }
 // (range, tol, max_depth, max_windows) of the four branch-and-bound queries, checked (NaN, then the limits) and defaulted in one place from one table: the call's
 // and its group call's name, the limits, the defaults, and the reason clause each limit's message ends on (the two row-listing queries size their lists by the call).
-struct SearchSpec { const char* name; const char* group_name; int depth_limit, window_limit; double tol; int windows; const char* depth_why; const char* windows_why; };
+// first_is_offset: the first argument is a contact distance and defaults to offset, not to the audit range; tol_fraction > 0: the default tolerance is that fraction of
+// the first argument over vel_limit (a time) instead of `tol`
+struct SearchSpec { const char* name; const char* group_name; int depth_limit, window_limit; double tol; int windows; const char* depth_why; const char* windows_why; bool first_is_offset = false; double tol_fraction = 0.0; };
 const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approach", TJ_CLOSEST_MAX_DEPTH, TJ_CLOSEST_FRONTIER, TJ_CLOSEST_TOL, TJ_CLOSEST_FRONTIER,
                                 ": deeper windows cannot be halved in a double", ": the live list's capacity"},
                  SEARCH_PAIR{"tj_pair_approach", "tj_group_pair_approach", TJ_PAIR_MAX_DEPTH, TJ_PAIR_MAX_WINDOWS, TJ_PAIR_TOL, TJ_PAIR_FRONTIER,
                              ": deeper windows cannot be halved in a double", ""},
                  SEARCH_CROSSING{"tj_path_crossings", "tj_group_path_crossings", TJ_CROSSING_MAX_DEPTH, TJ_CROSSING_MAX_WINDOWS, TJ_CROSSING_TOL, TJ_CROSSING_FRONTIER,
                                  ": deeper windows cannot be halved in a double", ""},
+                 SEARCH_MARGIN{"tj_timing_margin", "tj_group_timing_margin", TJ_MARGIN_MAX_DEPTH, TJ_MARGIN_MAX_WINDOWS, 0.0, TJ_MARGIN_FRONTIER,
+                               ": deeper windows cannot be halved in a double", "", true, TJ_MARGIN_TOL_FRACTION},
                  SEARCH_OBSTACLE{"tj_obstacle_approach", "tj_group_obstacle_approach", TJ_OBSTACLE_MAX_DEPTH, TJ_OBSTACLE_FRONTIER, TJ_OBSTACLE_TOL, TJ_OBSTACLE_FRONTIER,
                                  ": deeper windows are not dyadic in a double", ": the live list's capacity"};
 struct SearchArgs {
@@ -1340,13 +1347,14 @@ struct SearchArgs {
 };
 int search_args(tj_ctx* c, const SearchSpec& q, double range, double tol, int max_depth, int max_windows, SearchArgs& a) {
   int r;
-  if ((r = query_nan(c, q.name, "range", range)) || (r = query_nan(c, q.name, "tol", tol))) return r;
+  if ((r = query_nan(c, q.name, q.first_is_offset ? "dist" : "range", range)) || (r = query_nan(c, q.name, "tol", tol))) return r;
   if (max_depth > q.depth_limit) { c->err = std::string(q.name) + ": max_depth must be 0.." + std::to_string(q.depth_limit) + " (or negative for the default)" + q.depth_why; return TJ_ERR_INVALID; }
   if (max_windows > q.window_limit) {
     c->err = std::string(q.name) + ": max_windows must be 1.." + std::to_string(q.window_limit) + " (or <= 0 for the default)" + q.windows_why;
     return TJ_ERR_INVALID;
   }
-  a = SearchArgs{query_range(c->d, range), tol < 0 ? q.tol : tol, max_depth < 0 ? q.depth_limit : max_depth, max_windows <= 0 ? q.windows : max_windows};
+  const double first = q.first_is_offset ? (range > 0 ? range : c->d.offset) : query_range(c->d, range);
+  a = SearchArgs{first, tol < 0 ? (q.tol_fraction > 0 ? (q.tol_fraction * first) / c->d.vel_limit : q.tol) : tol, max_depth < 0 ? q.depth_limit : max_depth, max_windows <= 0 ? q.windows : max_windows};
   return TJ_OK;
 }
 // sorted primitive -> index in the caller's obstacle list, made by whichever query needs it first
@@ -1469,7 +1477,7 @@ int closest_run(tj_ctx* c, double range, double tol, int max_depth, int max_wind
   return query_finish(c, nullptr);
 }
 
-// ---- the two row-listing queries: what a query states (its search's table row, its byte budget and formula, its buffers, its launches), and the one path they share ----
+// ---- the three row-listing queries: what a query states (its search's table row, its byte budget and formula, its buffers, its launches), and the one path they share ----
 struct PairQuery {
   using Args = PairArgs; using Rec = tj_pair_record;
   static constexpr const SearchSpec& spec = SEARCH_PAIR;
@@ -1486,6 +1494,7 @@ struct PairQuery {
         (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 2 * gm, l))) return r;
     return TJ_OK;
   }
+  static int extra(tj_ctx*, Args&, double) { return TJ_OK; }   // (the query has no argument of its own)
   static int prepare(tj_ctx* c, Args& a) { a.seed_cap = 2 * c->d.S + 2; return query_clear(c, a.count, (size_t)a.ix.cap * 2, a.ix.cap > 0); }
   // two launches for the count, four for the rows, whatever the fleet's size, the number of pairs and the depth
   static void mark(tj_ctx* c, const Args& a, int units) { hipLaunchKernelGGL(k_pair_mark, dim3(units), dim3(64), 0, c->stream, c->d, a); }
@@ -1507,20 +1516,47 @@ struct CrossQuery {
     if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l))) return r;
     return TJ_OK;
   }
+  static int extra(tj_ctx*, Args&, double) { return TJ_OK; }
   static int prepare(tj_ctx*, Args&) { return TJ_OK; }
   // two launches for the count, three for the rows, whatever the fleet's size, the number of pairs and the depth
   static void mark(tj_ctx* c, const Args& a, int units) { hipLaunchKernelGGL(k_cross_mark, dim3(units), dim3(64), 0, c->stream, c->d, a); }
   static void rows(tj_ctx* c, const Args& a, int, Rec* out) { hipLaunchKernelGGL(k_cross_refine, dim3(a.ix.cap), dim3(CX_THREADS), 0, c->stream, c->d, a, out); }
 };
 
-// mark the listed pairs, index them (k_pair_index: pair p is the p-th set bit), and, for a call with room, search each: n first, then min(cap, n) rows
+// tj_timing_margin (kernels_timing_margin.h): the rows (u, q > u) of the owned robots u; the query's own argument is max_slip
+struct MarginQuery {
+  using Args = MarginArgs; using Rec = tj_margin_record;
+  static constexpr const SearchSpec& spec = SEARCH_MARGIN;
+  static constexpr const char* budget = "TJ_MARGIN_MAX_BYTES";
+  static constexpr long long max_bytes = TJ_MARGIN_MAX_BYTES;
+  static auto& held(tj_ctx* c) { return c->margin; }
+  static size_t bytes(const Dev&, int cap, int mw) { return (size_t)cap * ((size_t)2 * mw * sizeof(CrossItem) + (size_t)4 * mw * sizeof(double) + 2 * sizeof(int) + sizeof(tj_margin_record)); }
+  static int alloc(tj_ctx* c, Args& b, int gc, int gm, std::vector<void*>* l) {
+    int r;
+    if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l))) return r;
+    return TJ_OK;
+  }
+  static int extra(tj_ctx* c, Args& a, double max_slip) {
+    const int r = query_nan(c, spec.name, "max_slip", max_slip);
+    a.max_slip = max_slip > 0 ? max_slip : INFINITY;
+    return r;
+  }
+  static int prepare(tj_ctx*, Args&) { return TJ_OK; }
+  // two launches for the count, three for the rows, whatever the fleet's size, the number of pairs and the depth
+  static void mark(tj_ctx* c, const Args& a, int units) { hipLaunchKernelGGL(k_margin_mark, dim3(units), dim3(64), 0, c->stream, c->d, a); }
+  static void rows(tj_ctx* c, const Args& a, int, Rec* out) { hipLaunchKernelGGL(k_margin_refine, dim3(a.ix.cap), dim3(MG_THREADS), 0, c->stream, c->d, a, out); }
+};
+
+// mark the listed pairs, index them (k_pair_index: pair p is the p-th set bit), and, for a call with room, search each: n first, then min(cap, n) rows.  extra: the
+// query's own argument, if it has one (Q::extra checks and stores it)
 template <class Q>
-int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, typename Q::Rec* rows, int cap, int* n) {
+int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, double extra, const double* net_host, const double* pt_host, typename Q::Rec* rows, int cap, int* n) {
   if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
   const std::string name = Q::spec.name;
   int r;
   SearchArgs sa;
-  if ((r = search_args(c, Q::spec, range, tol, max_depth, max_windows, sa))) return r;
+  typename Q::Args own{};   // checked here, with the other arguments; stored into the call's arguments once those exist (below)
+  if ((r = Q::extra(c, own, extra)) || (r = search_args(c, Q::spec, range, tol, max_depth, max_windows, sa))) return r;
   const Dev& d = c->d;
   const int mw = sa.max_windows;
   if (Q::bytes(d, cap, mw) > (size_t)Q::max_bytes) {
@@ -1547,6 +1583,7 @@ int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windo
   typename Q::Args a = h.sized;
   if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
   sa.put(a);
+  Q::extra(c, a, extra);
   a.ix.cap = cap; a.ix.words = words; a.ix.mask = h.mask; a.ix.wordoff = h.wordoff; a.ix.n = h.n;
   if ((r = query_clear(c, h.mask, mask_n)) || (r = query_clear(c, h.n, 1)) || (r = Q::prepare(c, a))) return r;
   if (owned > 0) {
@@ -1609,10 +1646,12 @@ int tj_audit_timed(tj_ctx* c, double range, int levels, tj_audit_timed_robot* re
 int tj_audit_timed_record_size(void) { return (int)sizeof(tj_audit_timed_robot); }
 int tj_closest_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_closest_robot* records) { return closest_run(c, range, tol, max_depth, max_windows, nullptr, nullptr, records); }
 int tj_closest_record_size(void) { return (int)sizeof(tj_closest_robot); }
-int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return listed_run<PairQuery>(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
+int tj_pair_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return listed_run<PairQuery>(c, range, tol, max_depth, max_windows, 0.0, nullptr, nullptr, rows, cap, n); }
 int tj_pair_record_size(void) { return (int)sizeof(tj_pair_record); }
-int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) { return listed_run<CrossQuery>(c, range, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n); }
+int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) { return listed_run<CrossQuery>(c, range, tol, max_depth, max_windows, 0.0, nullptr, nullptr, rows, cap, n); }
 int tj_crossing_record_size(void) { return (int)sizeof(tj_crossing_record); }
+int tj_timing_margin(tj_ctx* c, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n) { return listed_run<MarginQuery>(c, dist, tol, max_depth, max_windows, max_slip, nullptr, nullptr, rows, cap, n); }
+int tj_margin_record_size(void) { return (int)sizeof(tj_margin_record); }
 
 // tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {

@@ -648,13 +648,13 @@ static std::vector<double> group_rows(const tj_group* g, const double* wanted) {
 
 // gather: the rows of a row-listing query (listed_run), rank after rank
 template <class Q>
-int group_listed(tj_group* g, double range, double tol, int max_depth, int max_windows, typename Q::Rec* rows, int cap, int* n) {
+int group_listed(tj_group* g, double range, double tol, int max_depth, int max_windows, double extra, typename Q::Rec* rows, int cap, int* n) {
   if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
   int total = 0;
   const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
     const int room = std::max(0, cap - total);
     int nr = 0;
-    const int e = listed_run<Q>(c, range, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, room, &nr);
+    const int e = listed_run<Q>(c, range, tol, max_depth, max_windows, extra, net, pt, room ? rows + total : nullptr, room, &nr);
     if (e < 0 && e != TJ_ERR_CAPACITY) return e;
     total += nr;
     return (int)TJ_OK;
@@ -687,10 +687,13 @@ int tj_group_closest_approach(tj_group* g, double range, double tol, int max_dep
 // the ranks' lists one after the other: ownership is by contiguous robot blocks in rank order, so that is the (robot, partner) order (tj_path_crossings: the rows
 // (u, q > u) by u's owner).  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.
 int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) {
-  return group_listed<PairQuery>(g, range, tol, max_depth, max_windows, rows, cap, n);
+  return group_listed<PairQuery>(g, range, tol, max_depth, max_windows, 0.0, rows, cap, n);
 }
 int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) {
-  return group_listed<CrossQuery>(g, range, tol, max_depth, max_windows, rows, cap, n);
+  return group_listed<CrossQuery>(g, range, tol, max_depth, max_windows, 0.0, rows, cap, n);
+}
+int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n) {
+  return group_listed<MarginQuery>(g, dist, tol, max_depth, max_windows, max_slip, rows, cap, n);
 }
 
 // from every rank's own state: nothing of another robot is read

@@ -722,7 +722,9 @@ class Solver:
         self._check(self.lib.tj_kat_set_local_grad(self._ctx, _d(lg), _d(lh)))
 
     def energy(self):
-        """Energy_admm::spline_energy of every owned robot at the current state (planes of the last iteration)"""
+        """Energy_admm::spline_energy of every owned robot at the current state (planes of the last iteration).  It is the line search's own evaluation: k_energy
+        stages what k_linesearch stages and calls x_energy_group, the function every Armijo candidate is evaluated with (+inf where a hull point lies behind a
+        plane or a limit is violated); tests/test_gpu_grad.py pins it to a 60-digit restatement of the objective"""
         e = np.zeros(self.U)
         self._check(self.lib.tj_get_energy(self._ctx, _d(e)))
         return e

@@ -144,7 +144,7 @@ def robot_min(d, ids, rng):
 
 
 def limit_terms(pkg, st, P, res, u):
-    """per segment the five speed terms [S][5] and the four acceleration terms [S][4] of robot u (Energy_admm.h:131-165 in kernels_ls.h's association)"""
+    """per segment the five speed terms [S][5] and the four acceleration terms [S][4] of robot u (Energy_admm.h:131-165 in the line search's association: dev_common.h hull_speed / hull_accel, shared by kernels_ls.h and kernels_audit.h)"""
     H = hulls_of(pkg, st["spline"][u:u + 1], P, res)[0]
     pt = st["piece_time"][u]
     sp, ac = np.zeros((P * res, 5)), np.zeros((P * res, 4))

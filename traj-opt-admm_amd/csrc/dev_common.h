@@ -502,6 +502,18 @@ __device__ __forceinline__ double seg_weight(const Dev& D, int tr) {
   return (k + 1) / double(D.res) - k / double(D.res);
 }
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
+// The two quantities bound_energy subtracts from vel_limit / acc_limit (Energy_admm.h:131-165): speed of velocity record b (0..4) and acceleration of record j (0..3)
+// of a segment's 6-point hull Pp, weight w, piece time pt.  ONE association, norm3(5 d) / (w pt) and norm3(20 d2) / (w w pt pt), for the line search (kernels_ls.h) and
+// the audit (kernels_audit.h), whose tests pin it bit for bit.  (k_grad's records, kernels_newton.h, follow Gradient_admm.h's association instead -- on purpose.)
+__device__ __forceinline__ double hull_speed(const double* Pp, int b, double w, double pt) {
+  const double vx = 5 * (Pp[3 * (b + 1)] - Pp[3 * b]), vy = 5 * (Pp[3 * (b + 1) + 1] - Pp[3 * b + 1]), vz = 5 * (Pp[3 * (b + 1) + 2] - Pp[3 * b + 2]);
+  return norm3(vx, vy, vz) / (w * pt);
+}
+__device__ __forceinline__ double hull_accel(const double* Pp, int j, double w, double pt) {
+  const double ax = 20 * (Pp[3 * (j + 2)] - 2 * Pp[3 * (j + 1)] + Pp[3 * j]), ay = 20 * (Pp[3 * (j + 2) + 1] - 2 * Pp[3 * (j + 1) + 1] + Pp[3 * j + 1]),
+               az = 20 * (Pp[3 * (j + 2) + 2] - 2 * Pp[3 * (j + 1) + 2] + Pp[3 * j + 2]);
+  return norm3(ax, ay, az) / (w * w * pt * pt);
+}
 
 // barrier b(d) = -(d-m)^2 ln(d/m) and its derivatives (Energy_admm.h:84-88, Gradient_admm.h:380-384)
 __device__ __forceinline__ double barrier(double w, double d, double m) { return -w * (d - m) * (d - m) * log(d / m); }

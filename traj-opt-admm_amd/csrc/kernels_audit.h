@@ -7,7 +7,7 @@
 //                        (Optimization3D_multi.h:246-259, Step.h:196-208).  Decoupled robots carry their own piece_time, so equal segment
 //                        indices are not equal flight times: this is the solver's own notion of "the pair", not a continuous-time distance (kernels_audit_timed.h is);
 //   speed / acceleration the two quantities bound_energy subtracts from vel_limit / acc_limit (Energy_admm.h:131-165), in the expressions and
-//                        the association of the line search (kernels_ls.h x_energy_group).
+//                        the association of the line search: its own functions (dev_common.h hull_speed / hull_accel).
 //
 //   k_audit         one wave per (owned robot, segment): hull with hull_entry's sums (the bits of the hull cache), BVH walk through
 //                   bvh_query with m = range (a primitive closer than `range` to the hull has its box within `range` of the hull's box, so
@@ -78,20 +78,11 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
     wave_argmin(pd, pq);
   }
 
-  // ---- dynamic limits: the terms of kernels_ls.h x_energy_group (Energy_admm.h:131-165), weight = the segment's table value ----
+  // ---- dynamic limits: the line search's own functions (dev_common.h hull_speed / hull_accel; Energy_admm.h:131-165), weight = the segment's table value ----
   const double w = seg_weight(D, tr), pt = D.piece_time[u];
   double sp = -1.0, ac = -1.0;
-  if (lane < 5) {
-    const int b = lane;
-    const double vx = 5 * (P[3 * (b + 1)] - P[3 * b]), vy = 5 * (P[3 * (b + 1) + 1] - P[3 * b + 1]), vz = 5 * (P[3 * (b + 1) + 2] - P[3 * b + 2]);
-    sp = norm3(vx, vy, vz) / (w * pt);
-  }
-  if (lane < 4) {
-    const int j = lane;
-    const double ax = 20 * (P[3 * (j + 2)] - 2 * P[3 * (j + 1)] + P[3 * j]), ay = 20 * (P[3 * (j + 2) + 1] - 2 * P[3 * (j + 1) + 1] + P[3 * j + 1]),
-                 az = 20 * (P[3 * (j + 2) + 2] - 2 * P[3 * (j + 1) + 2] + P[3 * j + 2]);
-    ac = norm3(ax, ay, az) / (w * w * pt * pt);
-  }
+  if (lane < 5) sp = hull_speed(P, lane, w, pt);
+  if (lane < 4) ac = hull_accel(P, lane, w, pt);
 #pragma unroll
   for (int off = 4; off > 0; off >>= 1) { sp = fmax(sp, __shfl_xor(sp, off)); ac = fmax(ac, __shfl_xor(ac, off)); }
   if (lane == 0) {

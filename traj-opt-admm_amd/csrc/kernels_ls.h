@@ -26,7 +26,7 @@ constexpr int LS_GSIZE = 64;   // one wave per candidate: group-private LDS need
 struct LsLayout {  // offsets in doubles into dynamic LDS
   size_t basis, convert, slack, lambda, tsl, tla, net, dir, gnet, ghull, gcons, res, planes, pltr, hn, hd, wseg, total;
   int plane_cap;
-  int affine;   // hulls of a trial step come from hull(net) + step * hull(dir), both formed once per launch (see x_energy_group)
+  int affine;   // hulls of a trial step come from hull(net) + step * hull(dir), both formed once per launch (see ls_trial_hull)
   int groups;   // Armijo candidates evaluated side by side (one wave each): 8 where the per-candidate hull buffers fit LDS,
                 // fewer for long trajectories (piece_num > 10); the accepted step is the same, only the rounds get shorter
 };
@@ -70,9 +70,6 @@ __host__ __device__ inline LsLayout ls_layout(int S, int T, int P, size_t lds_bu
   return L;
 }
 
-// E(net, pt) for robot u, evaluated by ONE group = one wave (gl = lane within the group).
-// Returns the value in every lane of the group.  Must be called by the whole workgroup (contains a
-// block barrier).
 // one control point coordinate of a segment's hull: row j of the segment's basis times the piece's 6 control points
 __device__ __forceinline__ double ls_hull_entry(const Dev& D, const double* basis, const double* net, int idx) {
   const int tr = idx / 18, e = idx % 18, j = e / 3, a = e % 3;
@@ -84,117 +81,48 @@ __device__ __forceinline__ double ls_hull_entry(const Dev& D, const double* basi
   return acc;
 }
 
-// `trial`: 0 = the hulls are those of `net` itself (E(x)), 1 = a trial step `step` along the direction.  With L.affine the
-// trial hulls are hull(x) + step * hull(d) (the hull map is linear; the two images are formed once per launch by ls_stage)
-// instead of 6 multiply-adds per entry and candidate: the hull pass was 2.9 of the 10.4 us of an evaluation.  The values
-// differ from basis * (x + step d) by rounding (~1e-16 relative) -- far below any Armijo margin seen -- and the hulls that
-// are PUBLISHED for the next iteration are recomputed exactly from the accepted control net.
-__device__ inline double x_energy_group(const Dev& D, int u, const double* sm, const LsLayout& L, const double* net, double pt, double* hulls,
-                                        double* cons, int M, bool planes_in_lds, const int* pref, int gl, int trial, double step) {
-  const int S = D.S, T = D.T;
-  const double* basis = sm + L.basis;
-  const double* wsg = sm + L.wseg;
-  TJ_TIC(D, K_BEGIN, 0);
-  if (L.affine) {
-    const double* hn = sm + L.hn; const double* hd = sm + L.hd;
-    for (int idx = gl; idx < S * 18; idx += LS_GSIZE) hulls[idx] = trial ? hn[idx] + step * hd[idx] : hn[idx];
-  } else {
-    for (int idx = gl; idx < S * 18; idx += LS_GSIZE) hulls[idx] = ls_hull_entry(D, basis, net, idx);
-  }
-  __syncthreads();  // all 8 groups run this function in lock step (uniform trip counts)
-  TJ_TIC(D, K_BEGIN, 1);
-  const double m = D.margin;
-  double part = 0, partb = 0;
-  int bad = 0;
-  // velocity / acceleration barriers (Energy_admm.h:98-170); two loops so that a wave never runs
-  // both formulas
-  for (int it = gl; it < S * 5; it += LS_GSIZE) {
-    const int tr = it / 5, b = it % 5;
-    const double w = wsg[tr];
-    const double* Pp = hulls + tr * 18;
-    const double vx = 5 * (Pp[3 * (b + 1)] - Pp[3 * b]), vy = 5 * (Pp[3 * (b + 1) + 1] - Pp[3 * b + 1]), vz = 5 * (Pp[3 * (b + 1) + 2] - Pp[3 * b + 2]);
-    const double d = D.vel_limit - norm3(vx, vy, vz) / (w * pt);
-    if (d <= 0) bad = 1;
-    else if (d < m) partb += barrier(w, d, m);
-  }
-  for (int it = gl; it < S * 4; it += LS_GSIZE) {
-    const int tr = it / 4, j = it % 4;
-    const double w = wsg[tr];
-    const double* Pp = hulls + tr * 18;
-    const double ax = 20 * (Pp[3 * (j + 2)] - 2 * Pp[3 * (j + 1)] + Pp[3 * j]), ay = 20 * (Pp[3 * (j + 2) + 1] - 2 * Pp[3 * (j + 1) + 1] + Pp[3 * j + 1]),
-                 az = 20 * (Pp[3 * (j + 2) + 2] - 2 * Pp[3 * (j + 1) + 2] + Pp[3 * j + 2]);
-    const double d = D.acc_limit - norm3(ax, ay, az) / (w * w * pt * pt);
-    if (d <= 0) bad = 1;
-    else if (d < m) partb += barrier(w, d, m);
-  }
-  // A violated velocity / acceleration limit already makes the energy +infinity (Energy_admm.h:137-138,154-155): skip the plane
-  // terms and the consensus sums.  In the first iterations every robot backs off 10-20 times on exactly this (measured:
-  // tests/devtools/armijo_hist.py), so most candidates of those rounds end here.  The group = one wave: the decision is uniform.
-  if (__ballot(bad != 0) != 0ull) return INFINITY;
-  TJ_TIC(D, K_BEGIN, 2);
-  // plane barrier (Energy_admm.h:46-96)
-  const double* pl_lds = sm + L.planes;
-  const int* pltr = (const int*)(sm + L.pltr);
-  if (planes_in_lds) {
-    // one (plane, hull point) term per lane and pass: a robot of the headline scene carries ~30 planes, so a lane per PLANE left
-    // half the wave idle while the others took six logarithms one after the other
-    // FOUR passes at a time while every lane has a term in each of them: a pass is a chain of two dependent LDS reads, a dot product and a logarithm (~0.5 us on its
-    // own), and a robot next to an obstacle slab walks 45 of them per candidate (config 5: 28 us per round of eight).  The four terms are formed side by side --
-    // an inactive one is +0.0, which changes no bit of the sum (x + 0.0 == x; the sums start at +0 and every term is positive) -- and added in pass order.
-    int pass = 0;
-    const int full = (6 * M) / LS_GSIZE;
-    for (; pass + 4 <= full; pass += 4) {
-      double t4[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int it = gl + LS_GSIZE * (pass + q);
-        const int ip = it / 6, j = it - 6 * ip, tr = pltr[ip];
-        const double* Pp = hulls + tr * 18 + 3 * j; const double* pl = pl_lds + 4 * ip;
-        const double d = Pp[0] * pl[0] + Pp[1] * pl[1] + Pp[2] * pl[2] + pl[3];
-        if (d <= 0) bad = 1;
-        const double b = barrier(wsg[tr], d, m);
-        t4[q] = (d > 0 && d < m) ? b : 0.0;
-      }
-      part += t4[0]; part += t4[1]; part += t4[2]; part += t4[3];
-    }
-    for (int it = gl + LS_GSIZE * pass; it < 6 * M; it += LS_GSIZE) {
-      const int ip = it / 6, j = it - 6 * ip, tr = pltr[ip];
-      const double* Pp = hulls + tr * 18 + 3 * j; const double* pl = pl_lds + 4 * ip;
-      const double d = Pp[0] * pl[0] + Pp[1] * pl[1] + Pp[2] * pl[2] + pl[3];
-      if (d <= 0) bad = 1;
-      else if (d < m) part += barrier(wsg[tr], d, m);
-    }
-  } else for (int it = gl; it < M; it += LS_GSIZE) {
-    int lo = 0, hi = S;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pref[mid] <= it) lo = mid; else hi = mid; }
-    const int tr = lo;
-    const int k = it - pref[tr], no = pref[512 + tr];
-    const double* pl = k < no ? D.oplanes + (((size_t)u * S + tr) * D.cap_obs + k) * 4 : D.splanes + (((size_t)u * S + tr) * D.cap_self + (k - no)) * 4;
-    const double c0 = pl[0], c1 = pl[1], c2 = pl[2], dk = pl[3];
-    const double w = wsg[tr];
-    const double* Pp = hulls + tr * 18;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-      const double d = Pp[3 * j] * c0 + Pp[3 * j + 1] * c1 + Pp[3 * j + 2] * c2 + dk;
-      if (d <= 0) bad = 1;
-      else if (d < m) part += barrier(w, d, m);
-    }
-  }
-  TJ_TIC(D, K_BEGIN, 3);
-  // fixed butterfly inside the group
-#pragma unroll
-  for (int off = LS_GSIZE / 2; off > 0; off >>= 1) {
-    part += __shfl_xor(part, off, LS_GSIZE);
-    partb += __shfl_xor(partb, off, LS_GSIZE);
-    bad |= __shfl_xor(bad, off, LS_GSIZE);
-  }
-  TJ_TIC(D, K_BEGIN, 4);
-  double e = D.lambda * part + D.lambda * partb;
-  // augmented-Lagrangian terms (Energy_admm.h:24-41).  The 18P entries of C x - z are spread over
-  // the lanes, lane sp then forms the six terms of piece sp (Eigen's reduction order inside each),
-  // and every lane adds the 6P terms in the reference's statement order.  cons is private to this
-  // group = this wave, so ordering points suffice.
-  const int P6 = 6 * D.P;
+// ---- the terms of E(x), each written ONCE: the group shape (x_energy_group) and the team shape (x_energy_team) call these on the same operands ----
+// d of a record: its distance to the limit (velocity / acceleration, Energy_admm.h:131-165) or to the plane (Energy_admm.h:46-96); w: the segment's weight
+__device__ __forceinline__ double ls_vel_dist(const Dev& D, const double* hulls, const double* wsg, int it, double pt, double& w) {
+  const int tr = it / 5, b = it % 5;
+  w = wsg[tr];
+  return D.vel_limit - hull_speed(hulls + tr * 18, b, w, pt);
+}
+__device__ __forceinline__ double ls_acc_dist(const Dev& D, const double* hulls, const double* wsg, int it, double pt, double& w) {
+  const int tr = it / 4, j = it % 4;
+  w = wsg[tr];
+  return D.acc_limit - hull_accel(hulls + tr * 18, j, w, pt);
+}
+__device__ __forceinline__ double ls_plane_dist(const double* Pp, double c0, double c1, double c2, double dk) { return Pp[0] * c0 + Pp[1] * c1 + Pp[2] * c2 + dk; }
+// (plane, hull point) record `it` of the LDS-resident plane list; tr: its segment
+__device__ __forceinline__ double ls_plane_dist_lds(const double* hulls, const double* pl_lds, const int* pltr, int it, int& tr) {
+  const int ip = it / 6, j = it - 6 * ip;
+  tr = pltr[ip];
+  const double* pl = pl_lds + 4 * ip;
+  return ls_plane_dist(hulls + tr * 18 + 3 * j, pl[0], pl[1], pl[2], pl[3]);
+}
+// The barrier term of a record: b(d) inside the margin, +0.0 outside it (x + 0.0 == x bit for bit: the sums start at +0 and every term is positive); a record at or
+// behind its limit (d <= 0) makes the energy +infinity: `bad`.  EAGER: the logarithm is taken whatever d is and the term selected afterwards, so that several
+// records' chains run side by side (the four-pass plane loop); the value is the same.
+template <bool EAGER = false>
+__device__ __forceinline__ double ls_term(double w, double d, double m, int& bad) {
+  if (d <= 0) bad = 1;
+  if (EAGER) { const double b = barrier(w, d, m); return (d > 0 && d < m) ? b : 0.0; }
+  return (d > 0 && d < m) ? barrier(w, d, m) : 0.0;
+}
+// plane `it` of robot u's lists in global memory (obstacle planes of its segment first, then robot-pair planes); tr: its segment, found in the prefix ls_stage left
+__device__ __forceinline__ const double* ls_plane_of(const Dev& D, const int* pref, int u, int it, int& tr) {
+  int lo = 0, hi = D.S;
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pref[mid] <= it) lo = mid; else hi = mid; }
+  tr = lo;
+  const int k = it - pref[tr], no = pref[512 + tr];
+  return k < no ? D.oplanes + (((size_t)u * D.S + tr) * D.cap_obs + k) * 4 : D.splanes + (((size_t)u * D.S + tr) * D.cap_self + (k - no)) * 4;
+}
+// Augmented-Lagrangian terms (Energy_admm.h:24-41), by ONE wave.  The 18P entries of C x - z are spread over the lanes, lane sp then forms the six terms of piece sp
+// (Eigen's reduction order inside each) into cons[18P ..]; whoever adds them -- every lane, in the reference's statement order -- orders them first (the group: an
+// ordering point, cons is private to its wave; the team: its block barrier).
+__device__ __forceinline__ void ls_consensus_terms(const Dev& D, const double* sm, const LsLayout& L, const double* net, double pt, double* cons, int gl) {
+  const int T = D.T, P6 = 6 * D.P;
   const double* cv = sm + L.convert; const double* sl = sm + L.slack; const double* la = sm + L.lambda;
   double* delta = cons; double* terms = cons + 18 * D.P;
   for (int it = gl; it < 18 * D.P; it += LS_GSIZE) {
@@ -224,11 +152,111 @@ __device__ inline double x_energy_group(const Dev& D, int u, const double* sm, c
     }
     t[5] = sm[L.tla + sp] * (pt - sm[L.tsl + sp]);
   }
+}
+// Entry idx of the hulls a candidate is evaluated on: `trial` = 0 those of x itself, 1 = of the trial step `step` along the direction, whose control net is `net`.
+// With L.affine they are hull(x) + step * hull(d) (the hull map is linear; the two images are formed once per launch by ls_stage) instead of 6 multiply-adds per
+// entry and candidate: the hull pass was 2.9 of the 10.4 us of an evaluation.  The values differ from basis * (x + step d) by rounding (~1e-16 relative) -- far below
+// any Armijo margin seen -- and the hulls that are PUBLISHED for the next iteration are recomputed exactly from the accepted control net.
+__device__ __forceinline__ double ls_trial_hull(const Dev& D, const double* sm, const LsLayout& L, const double* net, int idx, int trial, double step) {
+  if (L.affine) { const double* hn = sm + L.hn; const double* hd = sm + L.hd; return trial ? hn[idx] + step * hd[idx] : hn[idx]; }
+  return ls_hull_entry(D, sm + L.basis, net, idx);
+}
+// step * 0.8^k by k multiplications: the rounding of the reference's repeated step *= 0.8 (Optimization3D_multi.h:623,792), not of a power
+__device__ __forceinline__ double ls_step_back(double step, int k) { for (int i = 0; i < k; i++) step *= 0.8; return step; }
+
+// A robot as ls_stage left it in LDS, and one Armijo candidate of it: what an evaluation is a function of.  Small values, handed on by value.
+struct LsRobot {
+  int u, M;          // the robot; the planes it carries
+  bool in_lds;       // ... are LDS resident (L.planes, L.pltr); otherwise they are read from global memory through `pref`
+  double* sm;        // base of the dynamic LDS (offsets: LsLayout)
+  const int* pref;   // plane prefix per segment, [512 + tr]: obstacle planes of segment tr
+};
+struct LsCand { int k; double step, pt; };   // candidate k: x + step d at piece time pt; k = -1: x itself (E(x)), step unused
+__device__ __forceinline__ LsCand ls_cand(int k, double step, double t0, double t_dir) { return LsCand{k, step, k < 0 ? t0 : t0 + step * t_dir}; }
+
+// E of candidate c of robot R, evaluated by ONE group = one wave (group g of the block, gl = lane within it) on the control net the group's buffer holds
+// (ls_eval_candidate forms it).  Returns the value in every lane of the group.  Must be called by the whole workgroup (contains a block barrier).
+__device__ inline double x_energy_group(const Dev& D, const LsLayout& L, const LsRobot R, const LsCand c, int g, int gl) {
+  const int S = D.S, u = R.u, M = R.M;
+  const double* sm = R.sm; const int* pref = R.pref;
+  const double* net = sm + L.gnet + (size_t)g * 3 * D.T;
+  double* hulls = R.sm + L.ghull + (size_t)g * S * 18;
+  double* cons = R.sm + L.gcons + (size_t)g * 24 * D.P;   // per group: delta[18P], then 6 consensus/dual terms per piece
+  const double pt = c.pt;
+  const double* wsg = sm + L.wseg;
+  TJ_TIC(D, K_BEGIN, 0);
+  for (int idx = gl; idx < S * 18; idx += LS_GSIZE) hulls[idx] = ls_trial_hull(D, sm, L, net, idx, c.k >= 0, c.step);
+  __syncthreads();  // all 8 groups run this function in lock step (uniform trip counts)
+  TJ_TIC(D, K_BEGIN, 1);
+  const double m = D.margin;
+  double part = 0, partb = 0, w;
+  int bad = 0, tr;
+  // velocity / acceleration barriers (Energy_admm.h:98-170); two loops so that a wave never runs
+  // both formulas
+  for (int it = gl; it < S * 5; it += LS_GSIZE) { const double d = ls_vel_dist(D, hulls, wsg, it, pt, w); partb += ls_term(w, d, m, bad); }
+  for (int it = gl; it < S * 4; it += LS_GSIZE) { const double d = ls_acc_dist(D, hulls, wsg, it, pt, w); partb += ls_term(w, d, m, bad); }
+  // A violated velocity / acceleration limit already makes the energy +infinity (Energy_admm.h:137-138,154-155): skip the plane
+  // terms and the consensus sums.  In the first iterations every robot backs off 10-20 times on exactly this (measured:
+  // tests/devtools/armijo_hist.py), so most candidates of those rounds end here.  The group = one wave: the decision is uniform.
+  if (__ballot(bad != 0) != 0ull) return INFINITY;
+  TJ_TIC(D, K_BEGIN, 2);
+  // plane barrier (Energy_admm.h:46-96)
+  const double* pl_lds = sm + L.planes;
+  const int* pltr = (const int*)(sm + L.pltr);
+  if (R.in_lds) {
+    // one (plane, hull point) term per lane and pass: a robot of the headline scene carries ~30 planes, so a lane per PLANE left
+    // half the wave idle while the others took six logarithms one after the other
+    // FOUR passes at a time while every lane has a term in each of them: a pass is a chain of two dependent LDS reads, a dot product and a logarithm (~0.5 us on its
+    // own), and a robot next to an obstacle slab walks 45 of them per candidate (config 5: 28 us per round of eight).  The four terms are formed side by side --
+    // an inactive one is +0.0, which changes no bit of the sum (x + 0.0 == x; the sums start at +0 and every term is positive) -- and added in pass order.
+    int pass = 0;
+    const int full = (6 * M) / LS_GSIZE;
+    for (; pass + 4 <= full; pass += 4) {
+      double t4[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const double d = ls_plane_dist_lds(hulls, pl_lds, pltr, gl + LS_GSIZE * (pass + q), tr);
+        t4[q] = ls_term<true>(wsg[tr], d, m, bad);
+      }
+      part += t4[0]; part += t4[1]; part += t4[2]; part += t4[3];
+    }
+    for (int it = gl + LS_GSIZE * pass; it < 6 * M; it += LS_GSIZE) { const double d = ls_plane_dist_lds(hulls, pl_lds, pltr, it, tr); part += ls_term(wsg[tr], d, m, bad); }
+  } else for (int it = gl; it < M; it += LS_GSIZE) {
+    const double* pl = ls_plane_of(D, pref, u, it, tr);
+    const double c0 = pl[0], c1 = pl[1], c2 = pl[2], dk = pl[3];
+    w = wsg[tr];
+#pragma unroll
+    for (int j = 0; j < 6; j++) part += ls_term(w, ls_plane_dist(hulls + tr * 18 + 3 * j, c0, c1, c2, dk), m, bad);
+  }
+  TJ_TIC(D, K_BEGIN, 3);
+  // fixed butterfly inside the group
+#pragma unroll
+  for (int off = LS_GSIZE / 2; off > 0; off >>= 1) {
+    part += __shfl_xor(part, off, LS_GSIZE);
+    partb += __shfl_xor(partb, off, LS_GSIZE);
+    bad |= __shfl_xor(bad, off, LS_GSIZE);
+  }
+  TJ_TIC(D, K_BEGIN, 4);
+  double e = D.lambda * part + D.lambda * partb;
+  // augmented-Lagrangian terms: cons is private to this group = this wave, so ordering points suffice
+  ls_consensus_terms(D, sm, L, net, pt, cons, gl);
   blk_sync<true>();
+  const double* terms = cons + 18 * D.P;
   for (int i = 0; i < 6 * D.P; i++) e += terms[i];
   TJ_TIC(D, K_BEGIN, 5);
   if (bad) e = INFINITY;
   return e;
+}
+// "Group g evaluates candidate c": the group forms the candidate's control net in its buffer and, behind a block barrier, evaluates it.  Whole block; a group
+// with act = false (a round narrower than the block) only keeps the barriers.
+__device__ __forceinline__ double ls_eval_candidate(const Dev& D, const LsLayout& L, const LsRobot R, const LsCand c, int g, int gl, bool act = true) {
+  const double* net = R.sm + L.net; const double* dir = R.sm + L.dir;
+  double* gnet = R.sm + L.gnet + (size_t)g * 3 * D.T;
+  if (act) for (int i = gl; i < 3 * D.T; i += LS_GSIZE) gnet[i] = c.k < 0 ? net[i] : net[i] + c.step * dir[i];
+  __syncthreads();
+  if (act) return x_energy_group(D, L, R, c, g, gl);
+  __syncthreads();   // (x_energy_group's one block barrier)
+  return 0.0;
 }
 
 // ---- the same E(net, pt), evaluated by a TEAM of four waves (round 0 of a robot that accepted the full step last time) ----------
@@ -238,18 +266,26 @@ __device__ inline double x_energy_group(const Dev& D, int u, const double* sm, c
 // plane passes, the order x_energy_group meets them in) is taken by wave u & 3 of the team, which leaves its lane's TERM
 // (0.0 where the record is inactive: x + 0.0 == x bit for bit, the sums start at +0) in terms[u][lane]; wave 3 also forms the
 // consensus / dual terms.  After one block barrier wave 0 of the team adds every lane's terms in unit order -- the very sequence of
-// additions x_energy_group performs in that lane -- and finishes with the same butterfly and the same statement order.  Same
-// operands, same operations, same order: the value is BITWISE x_energy_group's (test: TJ_LS_FAST=0 changes no bit), so it does not
+// additions x_energy_group performs in that lane -- and finishes with the same butterfly and the same statement order.  Both shapes
+// call the SAME functions for every term (ls_vel_dist, ls_acc_dist, ls_plane_dist_lds, ls_term, ls_consensus_terms) on the same
+// operands, in the same order: the value is BITWISE x_energy_group's (test: TJ_LS_FAST=0 changes no bit), so it does not
 // matter which shape evaluated E(x) when a later round compares candidates against it -- which the loops that end by rounding
 // (stages_stack030) rely on.  Both teams run this in lock step (uniform trip counts; a violated limit does not leave early here).
 struct LsTeamUnits { int nv, na, np; __device__ int total() const { return nv + na + np; } };
 __device__ __forceinline__ LsTeamUnits ls_team_units(int S, int M) { return LsTeamUnits{(5 * S + 63) / 64, (4 * S + 63) / 64, (6 * M + 63) / 64}; }
 // abort_word (helper blocks running a super-round ahead of the primary's word, k_linesearch): thread 0 of the block reads the robot's word once,
 // mid-evaluation, and if the search is over by then (LS_WORD_DONE of this epoch) every wave leaves at the barrier -- *s_abort says so, the value is not used.
-__device__ __forceinline__ double x_energy_team(const Dev& D, const double* sm, const LsLayout& L, const double* net, double pt, const double* hulls, double* terms,
-                                                double* cons, int* bad_flag, double* out, int M, int tw, int gl,
+// The team (0 or 1; tw = wave within it) works in the buffers of the groups 4 team .. 4 team + 3: control net and hulls (formed by the caller) in the first group's,
+// the units' terms in the hull buffers of the second and third (2 * S * 18 doubles), the consensus terms in the first's.
+__device__ __forceinline__ double x_energy_team(const Dev& D, const LsLayout& L, const LsRobot R, const LsCand c, int team, int tw, int gl, int* bad_flag, double* out,
                                                 const unsigned long long* abort_word = nullptr, unsigned epoch = 0, int* s_abort = nullptr) {
-  const int S = D.S, T = D.T;
+  const int S = D.S, M = R.M;
+  const double* sm = R.sm;
+  const double* net = sm + L.gnet + (size_t)(4 * team) * 3 * D.T;
+  const double* hulls = sm + L.ghull + (size_t)(4 * team) * S * 18;
+  double* terms = R.sm + L.ghull + (size_t)(4 * team + 1) * S * 18;
+  double* cons = R.sm + L.gcons + (size_t)(4 * team) * 24 * D.P;
+  const double pt = c.pt;
   const double* wsg = sm + L.wseg;
   const double m = D.margin;
   const LsTeamUnits U4 = ls_team_units(S, M);
@@ -259,75 +295,23 @@ __device__ __forceinline__ double x_energy_team(const Dev& D, const double* sm, 
   unsigned long long w_abort = 0;
   for (int unit = tw; unit < U4.total(); unit += 4) {
     if (abort_word && threadIdx.x == 0 && unit + 4 >= U4.total()) w_abort = __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // before this wave's last unit; used at the barrier
-    double term = 0.0;
+    double term = 0.0, w;
     if (unit < U4.nv) {
       const int it = gl + 64 * unit;
-      if (it < S * 5) {
-        const int tr = it / 5, b = it % 5;
-        const double w = wsg[tr];
-        const double* Pp = hulls + tr * 18;
-        const double vx = 5 * (Pp[3 * (b + 1)] - Pp[3 * b]), vy = 5 * (Pp[3 * (b + 1) + 1] - Pp[3 * b + 1]), vz = 5 * (Pp[3 * (b + 1) + 2] - Pp[3 * b + 2]);
-        const double d = D.vel_limit - norm3(vx, vy, vz) / (w * pt);
-        if (d <= 0) bad = 1;
-        else if (d < m) term = barrier(w, d, m);
-      }
+      if (it < S * 5) { const double d = ls_vel_dist(D, hulls, wsg, it, pt, w); term = ls_term(w, d, m, bad); }
     } else if (unit < U4.nv + U4.na) {
       const int it = gl + 64 * (unit - U4.nv);
-      if (it < S * 4) {
-        const int tr = it / 4, j = it % 4;
-        const double w = wsg[tr];
-        const double* Pp = hulls + tr * 18;
-        const double ax = 20 * (Pp[3 * (j + 2)] - 2 * Pp[3 * (j + 1)] + Pp[3 * j]), ay = 20 * (Pp[3 * (j + 2) + 1] - 2 * Pp[3 * (j + 1) + 1] + Pp[3 * j + 1]),
-                     az = 20 * (Pp[3 * (j + 2) + 2] - 2 * Pp[3 * (j + 1) + 2] + Pp[3 * j + 2]);
-        const double d = D.acc_limit - norm3(ax, ay, az) / (w * w * pt * pt);
-        if (d <= 0) bad = 1;
-        else if (d < m) term = barrier(w, d, m);
-      }
+      if (it < S * 4) { const double d = ls_acc_dist(D, hulls, wsg, it, pt, w); term = ls_term(w, d, m, bad); }
     } else {
       const int it = gl + 64 * (unit - U4.nv - U4.na);
-      if (it < 6 * M) {
-        const int ip = it / 6, j = it - 6 * ip, tr = pltr[ip];
-        const double* Pp = hulls + tr * 18 + 3 * j; const double* pl = pl_lds + 4 * ip;
-        const double d = Pp[0] * pl[0] + Pp[1] * pl[1] + Pp[2] * pl[2] + pl[3];
-        if (d <= 0) bad = 1;
-        else if (d < m) term = barrier(wsg[tr], d, m);
-      }
+      int tr;
+      if (it < 6 * M) { const double d = ls_plane_dist_lds(hulls, pl_lds, pltr, it, tr); term = ls_term(wsg[tr], d, m, bad); }
     }
     terms[unit * 64 + gl] = term;
   }
   if (__ballot(bad != 0) != 0ull && gl == 0) *bad_flag = 1;
-  const int P6 = 6 * D.P;
-  double* delta = cons; double* cterms = cons + 18 * D.P;
-  if (tw == 3) {   // augmented-Lagrangian terms, statement for statement as in x_energy_group
-    const double* cv = sm + L.convert; const double* sl = sm + L.slack; const double* la = sm + L.lambda;
-    for (int it = gl; it < 18 * D.P; it += LS_GSIZE) {
-      const int sp = it / 18, r = it % 18, a = r / 6, j = r % 6;
-      const double* C = cv + (size_t)sp * 36 + j * 6;
-      double acc = 0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc += C[k] * net[sp * 3 + k + T * a];
-      delta[it] = acc - sl[sp * 6 + j + P6 * a];
-    }
-    blk_sync<true>();
-    for (int sp = gl; sp < D.P; sp += LS_GSIZE) {
-      const double* dl = delta + 18 * sp;
-      double prod[18];
-#pragma unroll
-      for (int i = 0; i < 18; i++) prod[i] = dl[i] * dl[i];
-      double* t = cterms + 6 * sp;
-      t[0] = D.mu / 2.0 * esum(prod, 18);
-      const double dt = pt - sm[L.tsl + sp];
-      t[1] = D.mu / 2.0 * (dt * dt);
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        double pr[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) pr[j] = la[sp * 6 + j + P6 * a] * dl[j + 6 * a];
-        t[2 + a] = esum(pr, 6);
-      }
-      t[5] = sm[L.tla + sp] * (pt - sm[L.tsl + sp]);
-    }
-  }
+  const double* cterms = cons + 18 * D.P;
+  if (tw == 3) ls_consensus_terms(D, sm, L, net, pt, cons, gl);   // (ordered by the block barrier below)
   if (abort_word && threadIdx.x == 0) *s_abort = (unsigned)(w_abort >> 32) == epoch && (unsigned)w_abort == LS_WORD_DONE;
   __syncthreads();
   double e = 0;
@@ -350,9 +334,9 @@ __device__ __forceinline__ double x_energy_team(const Dev& D, const double* sm, 
 }
 
 // Stage everything an evaluation reuses into LDS: tables, this robot's slack/dual blocks, control net,
-// search direction and (if they fit) its planes with their segment ids.  Returns the plane count M and
-// whether the planes are LDS resident.  Called by the whole block (contains barriers).
-__device__ __forceinline__ int ls_stage(const Dev& D, const LsLayout& L, double* sm, int* pref, int u, int tid, int nth, bool& in_lds_out) {
+// search direction and (if they fit) its planes with their segment ids.  Returns the staged robot (LsRobot: the plane
+// count M, whether the planes are LDS resident).  Called by the whole block (contains barriers).
+__device__ __forceinline__ LsRobot ls_stage(const Dev& D, const LsLayout& L, double* sm, int* pref, int u, int tid, int nth) {
   const int S = D.S, T = D.T, P = D.P, P6 = 6 * D.P;
   double* net = sm + L.net; double* dir = sm + L.dir;
   const double* gspline = D.spline + (size_t)u * 3 * T;
@@ -393,17 +377,14 @@ __device__ __forceinline__ int ls_stage(const Dev& D, const LsLayout& L, double*
   if (in_lds) {
     int* pltr = (int*)(sm + L.pltr);
     for (int it = tid; it < M; it += nth) {
-      int lo = 0, hi = S;
-      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pref[mid] <= it) lo = mid; else hi = mid; }
-      const int tr = lo, k = it - pref[tr], no = pref[512 + tr];
-      const double* pl = k < no ? D.oplanes + (((size_t)u * S + tr) * D.cap_obs + k) * 4 : D.splanes + (((size_t)u * S + tr) * D.cap_self + (k - no)) * 4;
+      int tr;
+      const double* pl = ls_plane_of(D, pref, u, it, tr);
       pltr[it] = tr;
       sm[L.planes + 4 * it] = pl[0]; sm[L.planes + 4 * it + 1] = pl[1]; sm[L.planes + 4 * it + 2] = pl[2]; sm[L.planes + 4 * it + 3] = pl[3];
     }
   }
   __syncthreads();
-  in_lds_out = in_lds;
-  return M;
+  return LsRobot{u, M, in_lds, sm, pref};
 }
 
 // Hull cache of the NEXT iteration's robot-pair stage (layout of k_hullinfo, kernels_pairs.h: hull 18, AABB 6,
@@ -496,10 +477,11 @@ __device__ __forceinline__ void fa_early_begin(const Dev& D) {
   asm volatile("" ::: "memory");
 }
 
-// begin_next = 1: the last block to finish also starts the NEXT iteration (begin_body): the stop test and the counter resets
-// need every block of this kernel to be done, which the ticket establishes; the host then omits the k_begin launch.
-__global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, int begin_next) {
-  if (D.fa_seq > 0) {   // asynchronous front: the early begin (last block of the grid: a helper where there are helpers), then every block counts itself started
+// ---- what k_linesearch and k_ls_coupled open and close with ----
+// Entry.  Asynchronous front: the early begin (by the last block of the grid: a helper where there are helpers), then every block counts itself started.
+// Returns true where the run has converged: the block leaves.
+__device__ __forceinline__ bool ls_enter(const Dev& D, int begin_next) {
+  if (D.fa_seq > 0) {
     if (blockIdx.x == gridDim.x - 1) fa_early_begin(D);
     if (threadIdx.x == 0) __hip_atomic_fetch_add(D.fa_res(blockIdx.x), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     sig_sent();
@@ -507,249 +489,244 @@ __global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, in
   if (TJ_DONE(D)) {
     // converged: the only begin work left for the next iteration is to retire the slack/dual update that k_mid has just paid
     if (begin_next && blockIdx.x == 0 && threadIdx.x == 0) { D.ctl->slack_now = D.ctl->slack_next; D.ctl->slack_next = 0; }
-    return;
+    return true;
   }
-  TJ_TIC_ENTRY(D, K_LINESEARCH);
-  extern __shared__ double sm[];
-  __shared__ int pref[1024];   // plane prefix per segment (S <= 511 checked on the host); [512 + tr]: obstacle planes of segment tr
+  return false;
+}
+// Exit, asynchronous front: the control nets of the robots [ua, ub) are out (written through) and acknowledged -> their commit flags; k_front's units on the other
+// queue wait for them.  Whole block (uniform).
+__device__ __forceinline__ void ls_commit_flags(const Dev& D, int ua, int ub, int tid) {
+  sig_acked();
+  __syncthreads();
+  asm volatile("" ::: "memory");
+  for (int uu = ua + tid; uu < ub; uu += LS_THREADS) __hip_atomic_store(D.fa_commit(uu), D.fa_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  sig_sent();
+}
+// Tail of the launch's last block: it starts the NEXT iteration (begin_body; quiet: see there).
+// Asynchronous front: this launch does not end before the k_front it feeds has -- every block of it has counted itself done behind its acknowledged
+// (write-through) stores; k_mid, next on this queue, then finds everything in memory
+// (Dev::fa_mid: k_mid waits for k_front's end itself; here only until every k_front block has STARTED, i.e. is resident -- k_mid's waves cannot shut one out then)
+__device__ __forceinline__ void ls_begin_next(const Dev& D, int quiet, int tid) {
+  begin_body(D, quiet, D.fa_seq > 0);
+  if (D.fa_seq > 0 && tid < 64) fa_wait16(D, D.fa_mid ? D.fa_fstart(0) : D.fa_fdone(0), (int)((unsigned)D.fa_seq * (unsigned)D.fa_nfront));
+}
+
+// ---- k_linesearch, phase by phase: stage (ls_stage), super-rounds, one-wave rounds, publish the hulls, commit, ticket ----
+// Where a robot's search stands between the phases; handed on by value.
+struct LsSearch {
+  int k_acc;          // the accepted candidate (-1: none yet) ...
+  double step_acc;    // ... and its step
+  int wg;             // the group whose buffers hold the accepted control net (and its hulls)
+  int k_first;        // candidate of group 0 in the next one-wave round: -1 = E(x) is still to be evaluated (it is group 0's job in that round)
+  double e_base;      // E(x), once evaluated
+  double step;        // = step0 * 0.8^k_done, kept across the rounds (each thread for the candidates of its team / group)
+  int k_done;
+  bool commit_late;   // the control net is stored by ls_commit, not at the accepting round
+  bool only_evaluates;   // a helper block: nothing to decide, publish or commit -- on to the ticket
+};
+
+// Rounds in the TEAM shape (x_energy_team): waves 0-3 evaluate one candidate, waves 4-7 the next.
+//  * one block per robot (ls_help = 1: fleets of more robots than compute units): round 0 only -- E(x) and candidate 0 -- for a robot that
+//    accepted the full step in the previous iteration (hist == 0; in the steady phase of a run that is nearly every robot, every iteration).
+//  * SUPER-ROUNDS (ls_help = H > 1: a fleet that leaves compute units idle, 64 robots on 256 CUs): the launch carries H blocks per robot,
+//    each on a CU of its own.  In super-round sr block h evaluates candidates 2 (h + H sr) - 1 and 2 (h + H sr) (candidate -1 = E(x): the
+//    primary's, h = 0, in super-round 0), so one super-round decides 2H candidates in the time of ONE team evaluation (3.8 us where a
+//    one-wave evaluation takes 8 - 10): the early iterations of a run, which back off 7 - 14 times on the velocity limit, take two super-rounds
+//    instead of two or three rounds of eight one-wave evaluations, and no robot waits for a history.  Helpers only EVALUATE: each posts its two
+//    energies (agent-scope stores into Dev::ls_tab; all-ones = not there yet) and then waits for the primary's word -- the next super-round
+//    or the end.  The primary walks the candidates in the reference's order (its own two, then the helpers' as they stand in the table), takes
+//    the first that passes and commits alone; it never depends on a helper: a post that is not there 10 us after its own evaluation (a GPU shared
+//    with another process, helpers not resident) sends it to the one-wave rounds below.  The order of stores that makes this safe:
+//    the primary's DONE word is performed (write-through, waited for) BEFORE any of its commit stores is issued, and a helper reads the word
+//    AFTER its staging loads have returned -- a helper that started late either sees DONE and leaves or has staged the state of before the commit.
+//    E(.) is a pure function of its inputs in either shape (bitwise: TJ_LS_FAST=0 / TJ_LS_HELP=1 change no bit), so it does not matter who evaluated what.
+// h, H: this block among the robot's blocks.  Returns the search as the rounds left it: accepted (k_acc >= 0), or to be continued by the one-wave rounds from k_first.
+__device__ __forceinline__ LsSearch ls_super_rounds(const Dev& D, const LsLayout& L, const LsRobot R, int h, int H, double t0, double t_dir, double wolfe, LsSearch s) {
   __shared__ int s_accept;
   __shared__ int s_bad[2];
-  __shared__ int s_flag;        // super-rounds: 0 = go on, 1 = leave the team loop
-  __shared__ int s_abort;       // super-rounds, helper ahead of the word: the search ended during this evaluation
-  __shared__ double s_accst;    // super-rounds: step of the accepted candidate
-  // ls_help blocks per robot (super-rounds, below): block h of robot ui is blockIdx = ui + h * owned -- the primaries (h = 0) lead the grid
-  // In the steady phase of a run (every robot takes the full step, iteration after iteration) the helpers have nothing to contribute and cost ~1 us per
-  // launch (their tickets, the table's reset): after LS_QUIET_ITERS such iterations in a row they leave at once and the primaries search on their own
-  // (H = 1 below) until a robot backs off again.
-  const int nown = D.u1 - D.u0;
-  const int H = (D.ls_help > 1 && D.ctl->ls_quiet < LS_QUIET_ITERS) ? D.ls_help : 1;
-  const int h = D.ls_help > 1 ? (int)blockIdx.x / nown : 0;
-  if (h > 0 && H == 1) return;   // (no ticket: the primaries count among themselves then)
-  const int tid = threadIdx.x, u = D.u0 + (int)blockIdx.x - h * nown, S = D.S, T = D.T, P = D.P;
+  __shared__ int s_flag;        // 0 = go on, 1 = leave the team loop
+  __shared__ int s_abort;       // helper ahead of the word: the search ended during this evaluation
+  __shared__ double s_accst;    // step of the accepted candidate
+  const int tid = threadIdx.x, gl = tid % LS_GSIZE, u = R.u, S = D.S, T = D.T;
+  double* sm = R.sm;
+  double* net = sm + L.net; double* dir = sm + L.dir; double* res = sm + L.res;
+  const int team = tid >> 8, tw = (tid >> 6) & 3, tl = tid & 255;
+  double* tnet = sm + L.gnet + (size_t)(4 * team) * 3 * T;
+  double* thull = sm + L.ghull + (size_t)(4 * team) * S * 18;
+  const unsigned epoch = (unsigned)D.ctl->epoch;
+  unsigned long long* word = D.ls_word + u;
+  double* tab = D.ls_tab + (size_t)u * LS_TAB_STRIDE;   // three sets of LS_HELP_MAX x 2 slots: super-round sr uses set sr % 3
+  // late-start guard of a helper (see above): the word is read now -- the staging barriers are behind us, every load of ls_stage has returned -- and
+  // looked at before the first post (the round trip hides behind the evaluation)
+  unsigned long long w_guard = 0;
+  asm volatile("" ::: "memory");   // (compiler: the guard load stays behind ls_stage's loads and barriers; hardware: those loads have returned -- their values went through LDS and two s_barriers)
+  if (h > 0 && tid == 0) w_guard = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("" ::: "memory");
+  for (int sr = 0;; sr++) {
+    const int kb = 2 * (h + H * sr) - 1, k = kb + team;   // this block's two candidates of the super-round
+    if (kb + 2 * H >= STEP_CAP) {   // (uniform; never in practice) the tail of a search that ends by rounding belongs to the one-wave rounds and their cap
+      if (h > 0) break;
+      if (tid == 0) { __hip_atomic_store(word, ((unsigned long long)epoch << 32) | LS_WORD_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __builtin_amdgcn_s_waitcnt(0); }
+      s.k_first = kb;
+      break;
+    }
+    for (; s.k_done < k; s.k_done++) s.step *= 0.8;          // same rounding as the reference's repeated step *= 0.8
+    const LsCand c = ls_cand(k, s.step, t0, t_dir);
+    for (int i = tl; i < 3 * T; i += 256) tnet[i] = k < 0 ? net[i] : net[i] + s.step * dir[i];
+    if (tid < 2) s_bad[tid] = 0;
+    if (!L.affine) __syncthreads();   // (the affine form needs nothing of tnet: one barrier for both)
+    for (int idx = tl; idx < S * 18; idx += 256) thull[idx] = ls_trial_hull(D, sm, L, tnet, idx, k >= 0, s.step);
+    __syncthreads();
+    if (sr == 0) TJ_TIC(D, K_LINESEARCH, 3);
+    const bool ahead = h > 0 && sr > 0;   // a helper beyond super-round 0 runs ahead of the primary's decision over the round before (below) and leaves mid-evaluation once the search is over
+    x_energy_team(D, L, R, c, team, tw, gl, &s_bad[team], &res[team], ahead ? word : nullptr, epoch, &s_abort);
+    if (tl == 0) res[LS_GROUPS + team] = s.step;
+    __syncthreads();
+    if (ahead && s_abort) break;
+    if (sr == 0) TJ_TIC(D, K_LINESEARCH, 4);
+    const int set = (sr % 3) * LS_HELP_MAX * 2;
+    if (h > 0) {   // helper: post, then wait for the primary's word
+      if (sr == 0) {
+        if (tid == 0) s_accept = (unsigned)(w_guard >> 32) == epoch && (unsigned)w_guard == LS_WORD_DONE;   // (its own word: s_flag is rewritten below without a barrier in between)
+        __syncthreads();
+        if (s_accept) break;
+      }
+      if (tl == 0) __hip_atomic_store(tab + set + 2 * h + team, res[team], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // The word permits round sr + 1 as soon as the primary's own two candidates of round sr have failed -- before it has read our posts: that
+      // evaluation runs ahead of the decision and is left at its barrier if the search ends meanwhile (x_energy_team: abort_word).
+      if (tid == 0) {
+        unsigned long long w = 0;   // (LS_WORD_DONE > every super-round)
+        const bool ok = poll_until<1>([&] { w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)(w >> 32) == epoch && (unsigned)w > (unsigned)sr; }, WAIT_5MS);
+        if (!ok) atomicAdd(&D.ctl->ls_helper_timeouts, 1);
+        s_flag = !ok || (unsigned)w == LS_WORD_DONE;
+      }
+      __syncthreads();
+      if (s_flag) break;
+      continue;
+    }
+    // primary: the first candidate that passes, in the reference's order
+    if (sr == 0) s.e_base = res[0];
+    if (tid < 64) {
+      int acc_k = -1, giveup = H == 1 ? 1 : 0; double acc_st = 0;
+      for (int c = sr == 0 ? 1 : 0; c < 2 && acc_k < 0; c++) { const double st = res[LS_GROUPS + c]; if (!(s.e_base - 1e-4 * wolfe * st < res[c])) { acc_k = kb + c; acc_st = st; } }
+      if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 0);
+      if (acc_k < 0 && H > 1) {
+        // Our own two failed: PERMIT round sr + 1 at once (word = sr + 1) -- the helpers start it while we look at their posts of this round; if one of those
+        // passes, they leave mid-evaluation.  (The set round sr + 1 posts into was emptied at the end of round sr - 2: long performed, the wait is free.)
+        sig_acked();
+        if (tid == 0) __hip_atomic_store(word, ((unsigned long long)epoch << 32) | (unsigned)(sr + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sig_sent();
+        double v = 0.0;
+        const bool mine = tid >= 2 && tid < 2 * H;
+        auto all_posted = [&] { if (mine) v = __hip_atomic_load(tab + set + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return ballot(mine && (unsigned long long)__double_as_longlong(v) == LS_TAB_EMPTY) == 0ull; };
+        if (!poll_until<0>(all_posted, WAIT_10US)) { giveup = 1; if (tid == 0) atomicAdd(&D.ctl->ls_giveups, 1); }
+        if (!giveup) {
+          double st = res[LS_GROUPS + 1];
+          for (int l = 2; l < 2 * H; l++) {
+            st *= 0.8;
+            const double e = __shfl(v, l);
+            if (acc_k < 0 && !(s.e_base - 1e-4 * wolfe * st < e)) { acc_k = kb + l; acc_st = st; }
+          }
+        }
+      }
+      if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 1);
+      if (H > 1) {
+        if (acc_k < 0 && !giveup) {   // on to the next super-round: empty the set just read -- it is round sr + 3's (not waited for: the permit of round sr + 2 will)
+          if (tid >= 2 && tid < 2 * H) __hip_atomic_store((unsigned long long*)tab + set + tid, LS_TAB_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+          if (tid == 0) __hip_atomic_store(word, ((unsigned long long)epoch << 32) | LS_WORD_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (giveup) __builtin_amdgcn_s_waitcnt(0);   // the one-wave rounds commit on their own: the word is performed before they start
+        }
+      }
+      if (tid == 0) { s_accept = acc_k; s_accst = acc_st; s_flag = giveup; }
+      if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 2);
+    }
+    __syncthreads();
+    if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 3);
+    const int acc = s_accept;
+    if (acc >= 0) {
+      s.k_acc = acc; s.step_acc = s_accst;
+      if (acc - kb < 2) s.wg = 4 * (acc - kb);   // the accepting team's buffers hold the trial net (and its hulls)
+      else {                                     // a helper's candidate: form its net here (same expression, same bits)
+        s.wg = 4;
+        double* wnet = sm + L.gnet + (size_t)4 * 3 * T;
+        for (int i = tid; i < 3 * T; i += LS_THREADS) wnet[i] = net[i] + s.step_acc * dir[i];
+        __syncthreads();
+        if (!L.affine) { double* whl = sm + L.ghull + (size_t)4 * S * 18; for (int idx = tid; idx < S * 18; idx += LS_THREADS) whl[idx] = ls_trial_hull(D, sm, L, wnet, idx, 1, s.step_acc); }   // (affine: published from the net, below)
+      }
+      TJ_TIC(D, K_LS_COUPLED, 4);
+      s.commit_late = true;   // the control net is stored after the hull cache (below): the DONE word has been performed by then
+      __syncthreads();
+      break;
+    }
+    if (s_flag) { s.k_first = kb + 2; break; }   // E(x) is known, the candidates up to kb + 1 have been looked at: one-wave rounds from here
+  }
+  s.only_evaluates = h > 0;   // (a helper has posted what it had to)
+  return s;
+}
+
+// Rounds in the one-wave shape (x_energy_group), G = L.groups candidates each, until a candidate is accepted -- or the step reaches the fixed point of step *= 0.8.
+// narrow: the first round evaluates only E(x) and the full step (see k_linesearch).  Without the asynchronous front the accepted control net is stored here.
+__device__ __forceinline__ LsSearch ls_wave_rounds(const Dev& D, const LsLayout& L, const LsRobot R, bool narrow, int hist, double t0, double t_dir, double wolfe, LsSearch s) {
+  __shared__ int s_accept;
   // G = L.groups candidates per round.  With G < 8 (long trajectories) the waves beyond G shadow the last group: they compute
   // the same candidate into the same buffers (identical values), which keeps every barrier uniform.
-  const int G = L.groups;
+  const int tid = threadIdx.x, T = D.T, G = L.groups;
   const int g = min(tid / LS_GSIZE, G - 1), gl = tid % LS_GSIZE;
   const bool shadow = tid / LS_GSIZE >= G;
-  double* net = sm + L.net; double* dir = sm + L.dir;
-  double* gnet = sm + L.gnet + (size_t)g * 3 * T;
-  double* ghull = sm + L.ghull + (size_t)g * S * 18;
+  double* sm = R.sm;
   double* res = sm + L.res;
-  double* gspline = D.spline + (size_t)u * 3 * T;
-  // scalars of the search first: two dependent global round trips that now overlap the staging below
-  const double wolfe = D.wolfe(D.U - 1);  // reference quirk: the global left by the LAST robot (Optimization3D_multi.h:730,792)
-  const double t_dir = D.tdir(u), t0 = D.piece_time[u];
-  double step0 = D.pow08[min(STEP_CAP, max(D.k_obs[u], D.k_self[u]))];
-  const int hist = D.ls_hist[u];   // exponent this robot accepted in the previous iteration (-1: none yet): the round-0 shape follows it
-  if (h > 0 && D.ls_help_late > 0) {   // test hook (TJ_LS_HELP_LATE): this helper starts its staging late -- typically after the primary has committed
-    const long long t_go = wall_clock64() + 100ll * D.ls_help_late;
-    while (wall_clock64() < t_go) __builtin_amdgcn_s_sleep(32);
-  }
-  bool in_lds;
-  const int M = ls_stage(D, L, sm, pref, u, tid, LS_THREADS, in_lds);
-  TJ_TIC(D, K_LINESEARCH, 2);
-  if (t0 + step0 * t_dir <= 0) step0 = -0.95 * t0 / t_dir;
-
-  double e_base = 0, step_acc = step0, pt_acc = t0;
-  int k_acc = -1, evals = 0, wg = 0;
-  int k_first = -1;   // candidate of group 0 in the next generic round: -1 = E(x) is still to be evaluated (it is group 0's job in that round)
-  // Rounds in the TEAM shape (x_energy_team): waves 0-3 evaluate one candidate, waves 4-7 the next.
-  //  * one block per robot (ls_help = 1: fleets of more robots than compute units): round 0 only -- E(x) and candidate 0 -- for a robot that
-  //    accepted the full step in the previous iteration (hist == 0; in the steady phase of a run that is nearly every robot, every iteration).
-  //  * SUPER-ROUNDS (ls_help = H > 1: a fleet that leaves compute units idle, 64 robots on 256 CUs): the launch carries H blocks per robot,
-  //    each on a CU of its own.  In super-round sr block h evaluates candidates 2 (h + H sr) - 1 and 2 (h + H sr) (candidate -1 = E(x): the
-  //    primary's, h = 0, in super-round 0), so one super-round decides 2H candidates in the time of ONE team evaluation (3.8 us where a
-  //    one-wave evaluation takes 8 - 10): the early iterations of a run, which back off 7 - 14 times on the velocity limit, take two super-rounds
-  //    instead of two or three rounds of eight one-wave evaluations, and no robot waits for a history.  Helpers only EVALUATE: each posts its two
-  //    energies (agent-scope stores into Dev::ls_tab; all-ones = not there yet) and then waits for the primary's word -- the next super-round
-  //    or the end.  The primary walks the candidates in the reference's order (its own two, then the helpers' as they stand in the table), takes
-  //    the first that passes and commits alone; it never depends on a helper: a post that is not there 10 us after its own evaluation (a GPU shared
-  //    with another process, helpers not resident) sends it to the one-wave rounds below.  The order of stores that makes this safe:
-  //    the primary's DONE word is performed (write-through, waited for) BEFORE any of its commit stores is issued, and a helper reads the word
-  //    AFTER its staging loads have returned -- a helper that started late either sees DONE and leaves or has staged the state of before the commit.
-  //    E(.) is a pure function of its inputs in either shape (bitwise: TJ_LS_FAST=0 / TJ_LS_HELP=1 change no bit), so it does not matter who evaluated what.
-  const LsTeamUnits tu = ls_team_units(S, M);
-  const bool team_ok = D.ls_fast && G == LS_GROUPS && in_lds && tu.total() * 64 <= 2 * S * 18;
-  const bool coop = team_ok && H > 1;
-  // A robot with hundreds of planes (next to an obstacle slab; the team shape does not hold its terms) is not a latency chain here but the fp64 issue rate of its compute
-  // unit as well: a round of eight candidates takes it 57 us in the early iterations of config 5 (and ~30 later) where a round of TWO takes 29 (measured: ~20 us is one
-  // wave's chain of 45 passes, ~4.7 us every further candidate on the unit).  In the steady phase of a run -- every robot of the fleet accepted the full step in the previous
-  // iteration -- its FIRST round therefore evaluates only E(x) and the full step, the other waves idle at the barriers; if that fails, full rounds follow.  (Sizing the
-  // first round by the robot's own last exponent while the fleet still backs off was measured too: a wrong guess costs what a right one saves.)  Which candidates share a
-  // round changes no energy and not the order they are looked at in: same step.
-  const bool narrow = !team_ok && G == LS_GROUPS && M >= LS_NARROW_MIN_PLANES && hist == 0 && D.ctl->ls_quiet >= 1 && D.ls_fast;
+  double* gspline = D.spline + (size_t)R.u * 3 * T;
   int W = G;   // candidates of the current round
-  double step = step0; int k_done = 0;                 // step = step0 * 0.8^k_done, kept across the rounds (each thread for the candidates of its team / group)
-  bool commit_late = false;
-  if (h > 0 && (!coop || D.ls_help_mute)) goto ticket;  // (uniform) a helper of a launch that searches in the one-wave shape: nothing to do  (ls_help_mute: test hook -- helpers
-                                                        // that never post; every primary then runs into its 10 us timeout and finishes on its own)
-  if (team_ok && (coop || hist == 0)) {
-    const int team = tid >> 8, tw = (tid >> 6) & 3, tl = tid & 255;
-    double* tnet = sm + L.gnet + (size_t)(4 * team) * 3 * T;
-    double* thull = sm + L.ghull + (size_t)(4 * team) * S * 18;
-    double* tterms = sm + L.ghull + (size_t)(4 * team + 1) * S * 18;   // the buffers of the team's groups 1 and 2: 2 * S * 18 doubles
-    double* tcons = sm + L.gcons + (size_t)(4 * team) * 24 * P;
-    const unsigned epoch = (unsigned)D.ctl->epoch;
-    unsigned long long* word = D.ls_word + u;
-    double* tab = D.ls_tab + (size_t)u * LS_TAB_STRIDE;   // three sets of LS_HELP_MAX x 2 slots: super-round sr uses set sr % 3
-    // late-start guard of a helper (see above): the word is read now -- the staging barriers are behind us, every load of ls_stage has returned -- and
-    // looked at before the first post (the round trip hides behind the evaluation)
-    unsigned long long w_guard = 0;
-    asm volatile("" ::: "memory");   // (compiler: the guard load stays behind ls_stage's loads and barriers; hardware: those loads have returned -- their values went through LDS and two s_barriers)
-    if (h > 0 && tid == 0) w_guard = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("" ::: "memory");
-    for (int sr = 0;; sr++) {
-      const int kb = 2 * (h + H * sr) - 1, k = kb + team;   // this block's two candidates of the super-round
-      if (kb + 2 * H >= STEP_CAP) {   // (uniform; never in practice) the tail of a search that ends by rounding belongs to the one-wave rounds and their cap
-        if (h > 0) break;
-        if (tid == 0) { __hip_atomic_store(word, ((unsigned long long)epoch << 32) | LS_WORD_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __builtin_amdgcn_s_waitcnt(0); }
-        k_first = kb;
-        break;
-      }
-      for (; k_done < k; k_done++) step *= 0.8;          // same rounding as the reference's repeated step *= 0.8
-      const double pt = k < 0 ? t0 : t0 + step * t_dir;
-      for (int i = tl; i < 3 * T; i += 256) tnet[i] = k < 0 ? net[i] : net[i] + step * dir[i];
-      if (tid < 2) s_bad[tid] = 0;
-      if (L.affine) { const double* hn = sm + L.hn; const double* hd = sm + L.hd; for (int idx = tl; idx < S * 18; idx += 256) thull[idx] = k < 0 ? hn[idx] : hn[idx] + step * hd[idx]; }   // (needs nothing of tnet: one barrier for both)
-      else { __syncthreads(); for (int idx = tl; idx < S * 18; idx += 256) thull[idx] = ls_hull_entry(D, sm + L.basis, tnet, idx); }
-      __syncthreads();
-      if (sr == 0) TJ_TIC(D, K_LINESEARCH, 3);
-      const bool ahead = h > 0 && sr > 0;   // a helper beyond super-round 0 runs ahead of the primary's decision over the round before (below) and leaves mid-evaluation once the search is over
-      x_energy_team(D, sm, L, tnet, pt, thull, tterms, tcons, &s_bad[team], &res[team], M, tw, gl, ahead ? word : nullptr, epoch, &s_abort);
-      if (tl == 0) res[LS_GROUPS + team] = step;
-      __syncthreads();
-      if (ahead && s_abort) break;
-      if (sr == 0) TJ_TIC(D, K_LINESEARCH, 4);
-      const int set = (sr % 3) * LS_HELP_MAX * 2;
-      if (h > 0) {   // helper: post, then wait for the primary's word
-        if (sr == 0) {
-          if (tid == 0) s_accept = (unsigned)(w_guard >> 32) == epoch && (unsigned)w_guard == LS_WORD_DONE;   // (its own word: s_flag is rewritten below without a barrier in between)
-          __syncthreads();
-          if (s_accept) break;
-        }
-        if (tl == 0) __hip_atomic_store(tab + set + 2 * h + team, res[team], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // The word permits round sr + 1 as soon as the primary's own two candidates of round sr have failed -- before it has read our posts: that
-        // evaluation runs ahead of the decision and is left at its barrier if the search ends meanwhile (x_energy_team: abort_word).
-        if (tid == 0) {
-          unsigned long long w = 0;   // (LS_WORD_DONE > every super-round)
-          const bool ok = poll_until<1>([&] { w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (unsigned)(w >> 32) == epoch && (unsigned)w > (unsigned)sr; }, WAIT_5MS);
-          if (!ok) atomicAdd(&D.ctl->ls_helper_timeouts, 1);
-          s_flag = !ok || (unsigned)w == LS_WORD_DONE;
-        }
-        __syncthreads();
-        if (s_flag) break;
-        continue;
-      }
-      // primary: the first candidate that passes, in the reference's order
-      if (sr == 0) e_base = res[0];
-      if (tid < 64) {
-        int acc_k = -1, giveup = H == 1 ? 1 : 0; double acc_st = 0;
-        for (int c = sr == 0 ? 1 : 0; c < 2 && acc_k < 0; c++) { const double st = res[LS_GROUPS + c]; if (!(e_base - 1e-4 * wolfe * st < res[c])) { acc_k = kb + c; acc_st = st; } }
-        if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 0);
-        if (acc_k < 0 && H > 1) {
-          // Our own two failed: PERMIT round sr + 1 at once (word = sr + 1) -- the helpers start it while we look at their posts of this round; if one of those
-          // passes, they leave mid-evaluation.  (The set round sr + 1 posts into was emptied at the end of round sr - 2: long performed, the wait is free.)
-          sig_acked();
-          if (tid == 0) __hip_atomic_store(word, ((unsigned long long)epoch << 32) | (unsigned)(sr + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          sig_sent();
-          double v = 0.0;
-          const bool mine = tid >= 2 && tid < 2 * H;
-          auto all_posted = [&] { if (mine) v = __hip_atomic_load(tab + set + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return ballot(mine && (unsigned long long)__double_as_longlong(v) == LS_TAB_EMPTY) == 0ull; };
-          if (!poll_until<0>(all_posted, WAIT_10US)) { giveup = 1; if (tid == 0) atomicAdd(&D.ctl->ls_giveups, 1); }
-          if (!giveup) {
-            double st = res[LS_GROUPS + 1];
-            for (int l = 2; l < 2 * H; l++) {
-              st *= 0.8;
-              const double e = __shfl(v, l);
-              if (acc_k < 0 && !(e_base - 1e-4 * wolfe * st < e)) { acc_k = kb + l; acc_st = st; }
-            }
-          }
-        }
-        if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 1);
-        if (H > 1) {
-          if (acc_k < 0 && !giveup) {   // on to the next super-round: empty the set just read -- it is round sr + 3's (not waited for: the permit of round sr + 2 will)
-            if (tid >= 2 && tid < 2 * H) __hip_atomic_store((unsigned long long*)tab + set + tid, LS_TAB_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } else {
-            if (tid == 0) __hip_atomic_store(word, ((unsigned long long)epoch << 32) | LS_WORD_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (giveup) __builtin_amdgcn_s_waitcnt(0);   // the one-wave rounds commit on their own: the word is performed before they start
-          }
-        }
-        if (tid == 0) { s_accept = acc_k; s_accst = acc_st; s_flag = giveup; }
-        if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 2);
-      }
-      __syncthreads();
-      if (sr == 0) TJ_TIC(D, K_LS_COUPLED, 3);
-      const int acc = s_accept;
-      if (acc >= 0) {
-        k_acc = acc; step_acc = s_accst; pt_acc = t0 + step_acc * t_dir; evals = 2 + k_acc;
-        if (acc - kb < 2) wg = 4 * (acc - kb);   // the accepting team's buffers hold the trial net (and its hulls)
-        else {                                     // a helper's candidate: form its net here (same expression, same bits)
-          wg = 4;
-          double* wnet = sm + L.gnet + (size_t)4 * 3 * T;
-          for (int i = tid; i < 3 * T; i += LS_THREADS) wnet[i] = net[i] + step_acc * dir[i];
-          __syncthreads();
-          if (!L.affine) { double* whl = sm + L.ghull + (size_t)4 * S * 18; for (int idx = tid; idx < S * 18; idx += LS_THREADS) whl[idx] = ls_hull_entry(D, sm + L.basis, wnet, idx); }
-        }
-        TJ_TIC(D, K_LS_COUPLED, 4);
-        commit_late = true;   // the control net is stored after the hull cache (below): the DONE word has been performed by then
-        __syncthreads();
-        break;
-      }
-      if (s_flag) { k_first = kb + 2; break; }   // E(x) is known, the candidates up to kb + 1 have been looked at: one-wave rounds from here
-    }
-    if (h > 0) goto ticket;
-  }
-  for (int round = 0; k_acc < 0; round++, k_first += W) {
-    W = (narrow && round == 0 && k_first < 0) ? hist + 2 : G;
+  for (int round = 0; s.k_acc < 0; round++, s.k_first += W) {
+    W = (narrow && round == 0 && s.k_first < 0) ? hist + 2 : G;
     const bool act = g < W;
     // candidate of this group: -1 = E(x), otherwise trial index k >= 0
-    const int k = k_first + g;
-    if (act) for (; k_done < k; k_done++) step *= 0.8;          // same rounding as the reference's repeated step *= 0.8
-    const double pt = k < 0 ? t0 : t0 + step * t_dir;
-    if (act) for (int i = gl; i < 3 * T; i += LS_GSIZE) gnet[i] = k < 0 ? net[i] : net[i] + step * dir[i];
-    __syncthreads();
+    const int k = s.k_first + g;
+    if (act) for (; s.k_done < k; s.k_done++) s.step *= 0.8;          // same rounding as the reference's repeated step *= 0.8
     if (round == 0) TJ_TIC(D, K_LINESEARCH, 3);
-    double e = 0.0;
-    if (act) e = x_energy_group(D, u, sm, L, gnet, pt, ghull, sm + L.gcons + (size_t)g * 24 * P, M, in_lds, pref, gl, k >= 0, step);
-    else __syncthreads();   // (the function's one block barrier)
+    const double e = ls_eval_candidate(D, L, R, ls_cand(k, s.step, t0, t_dir), g, gl, act);
     if (round == 0) TJ_TIC(D, K_LINESEARCH, 4);
-    if (gl == 0 && !shadow && act) { res[g] = e; res[LS_GROUPS + g] = step; }
+    if (gl == 0 && !shadow && act) { res[g] = e; res[LS_GROUPS + g] = s.step; }
     if (tid == 0) s_accept = -1;
     __syncthreads();
-    if (k_first < 0) e_base = res[0];
+    if (s.k_first < 0) s.e_base = res[0];
     if (tid == 0) {
-      for (int c = (k_first < 0 ? 1 : 0); c < W; c++) {
+      for (int c = (s.k_first < 0 ? 1 : 0); c < W; c++) {
         const double st = res[LS_GROUPS + c];
-        if (!(e_base - 1e-4 * wolfe * st < res[c])) { s_accept = c; break; }
+        if (!(s.e_base - 1e-4 * wolfe * st < res[c])) { s_accept = c; break; }
       }
     }
     __syncthreads();
     const int acc = s_accept;
     if (acc >= 0) {
-      k_acc = k_first + acc;
-      step_acc = res[LS_GROUPS + acc];
-      pt_acc = t0 + step_acc * t_dir;
-      evals = 2 + k_acc;
+      s.k_acc = s.k_first + acc;
+      s.step_acc = res[LS_GROUPS + acc];
       // commit: the accepting group's trial net is the new control net
-      wg = acc;
+      s.wg = acc;
       const double* win = sm + L.gnet + (size_t)acc * 3 * T;
-      if (D.fa_seq > 0) commit_late = true;   // asynchronous front: one commit site (below), written through and followed by the robot's flag
+      if (D.fa_seq > 0) s.commit_late = true;   // asynchronous front: one commit site (below), written through and followed by the robot's flag
       else for (int i = tid; i < 3 * T; i += LS_THREADS) gspline[i] = win[i];
-    } else if (W == G && k_first + G - 1 >= STEP_CAP) {
+    } else if (W == G && s.k_first + G - 1 >= STEP_CAP) {
       // no acceptable step although step *= 0.8 has reached its fixed point (every further candidate is this one again): the
       // reference's loop would never end (Optimization3D_multi.h:792).  Take the last candidate and report.
       if (tid == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP);
-      k_acc = k_first + G - 1;
-      step_acc = res[LS_GROUPS + G - 1];
-      pt_acc = t0 + step_acc * t_dir;
-      evals = 2 + k_acc;
-      wg = G - 1;
+      s.k_acc = s.k_first + G - 1;
+      s.step_acc = res[LS_GROUPS + G - 1];
+      s.wg = G - 1;
       const double* win = sm + L.gnet + (size_t)(G - 1) * 3 * T;
-      if (D.fa_seq > 0) commit_late = true;
+      if (D.fa_seq > 0) s.commit_late = true;
       else for (int i = tid; i < 3 * T; i += LS_THREADS) gspline[i] = win[i];
     }
     __syncthreads();
   }
+  return s;
+}
+
+// The hull cache of the next iteration's robot-pair stage, from the hulls of the accepted candidate (group wg's buffers).
+__device__ __forceinline__ void ls_publish_hulls(const Dev& D, const LsLayout& L, const LsRobot R, int wg) {
+  const int tid = threadIdx.x, u = R.u, S = D.S, T = D.T;
+  double* sm = R.sm;
   if (D.fuse && D.multi() && !D.fa_units) {   // (Dev::fa_units: the next k_front's units form the records themselves, from the committed control net; written through from here
                                                 //  the 40 KB per robot put ~4 us in front of every commit flag -- measured)
     double* wh = sm + L.ghull + (size_t)wg * S * 18;
@@ -760,25 +737,28 @@ __global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, in
     }
     ls_publish_hullinfo(D, u, wh, tid, LS_THREADS);
   }
-  TJ_TIC(D, K_LS_COUPLED, 5);
-  if (commit_late) {   // (uniform) accepted in a team round: commit now -- with helpers about, wave 0's DONE word must have been performed before the first of these stores is issued
+}
+
+// Commit: the accepted control net (where the rounds have not stored it), the robot's commit flag, its record, and the direct exchange of sharded contexts.
+__device__ __forceinline__ void ls_commit(const Dev& D, const LsLayout& L, const LsRobot R, int H, double t0, double t_dir, int begin_next, const LsSearch s) {
+  const int tid = threadIdx.x, u = R.u, T = D.T;
+  const double* win = R.sm + L.gnet + (size_t)s.wg * 3 * T;   // the accepting group's trial net is the new control net
+  double* gspline = D.spline + (size_t)u * 3 * T;
+  if (s.commit_late) {   // (uniform) accepted in a team round: commit now -- with helpers about, wave 0's DONE word must have been performed before the first of these stores is issued
     if (H > 1) { TJ_MARK_(0x2c1); if (tid < 64) __builtin_amdgcn_s_waitcnt(0); __syncthreads(); TJ_MARK_(0x2c2); }   // (s_waitcnt vmcnt(0): wave 0's DONE store has been acknowledged; the barrier hands that to the other waves; the compiler keeps the commit stores below)
-    const double* win = sm + L.gnet + (size_t)wg * 3 * T;
     for (int i = tid; i < 3 * T; i += LS_THREADS) xs_out(D.fa_seq > 0, gspline + i, win[i]);
   }
-  if (D.fa_seq > 0) {   // (uniform) asynchronous front: the control net is out (written through) and acknowledged -> the robot's commit flag; k_front's units on the other queue wait for it
-    sig_acked();
-    __syncthreads();
-    asm volatile("" ::: "memory");
-    if (tid == 0) __hip_atomic_store(D.fa_commit(u), D.fa_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sig_sent();
-  }
+  if (D.fa_seq > 0) ls_commit_flags(D, u, u + 1, tid);   // (uniform) the control net is out: the robot's commit flag
   TJ_TIC(D, K_LINESEARCH, 5);
-  if (tid == 0) { D.piece_time[u] = pt_acc; D.step_out[u] = step_acc; D.ls_hist[u] = k_acc; D.blk_stats[(size_t)D.U * D.P + u] += (unsigned long long)evals; }   // per robot: one writer, no atomic in front of the ticket
+  if (tid == 0) { D.piece_time[u] = t0 + s.step_acc * t_dir; D.step_out[u] = s.step_acc; D.ls_hist[u] = s.k_acc; D.blk_stats[(size_t)D.U * D.P + u] += (unsigned long long)(2 + s.k_acc); }   // per robot: one writer, no atomic in front of the ticket
   // direct exchange (sharded contexts): the committed control net goes straight into every peer's receive buffer -- the next iteration's k_front
   // there waits for it (inside a batch only: the first iteration of a batch is fed by k_begin, which pushes whatever the state is then)
-  if (D.xch && begin_next) xch_push_robot<false>(D, 0, u, 3 * T, sm + L.gnet + (size_t)wg * 3 * T, 3 * T, tid, LS_THREADS);
-ticket:
+  if (D.xch && begin_next) xch_push_robot<false>(D, 0, u, 3 * T, win, 3 * T, tid, LS_THREADS);
+}
+
+// The block's ticket; the last block of the launch starts the next iteration (ls_begin_next).  backed_off: a primary whose robot did not take the full step.
+__device__ __forceinline__ void ls_ticket(const Dev& D, int h, int H, bool backed_off, int begin_next) {
+  const int tid = threadIdx.x, nown = D.u1 - D.u0;
   if (begin_next) {
     if (h > 0) sig_acked();   // a helper's posts are performed before its ticket: begin_body's reset of the table cannot be overtaken by them
     // No fence: nothing another block of THIS kernel writes is read here (gnorm and the counters come from earlier kernels;
@@ -789,21 +769,70 @@ ticket:
     __syncthreads();
     // the ticket also says whether this robot backed off (bit 16 up): the last block knows it of every robot without reading anything another block wrote
     if (tid == 0) {
-      const int add = 1 + ((h == 0 && k_acc != 0) ? 0x10000 : 0), old = atomicAdd(&D.ctl->ticket, add);
+      const int add = 1 + (backed_off ? 0x10000 : 0), old = atomicAdd(&D.ctl->ticket, add);
       s_last = (old & 0xffff) == nown * H - 1 ? 1 + (((old + add) >> 16) != 0) : 0;
     }
     sig_sent();
     __syncthreads();
     if (s_last) {
       if (tid == 0) D.ctl->ticket = 0;
-      begin_body(D, s_last == 1, D.fa_seq > 0);
-      // asynchronous front: this launch does not end before the k_front it feeds has -- every block of it has counted itself done behind its acknowledged
-      // (write-through) stores; k_mid, next on this queue, then finds everything in memory
-      // (Dev::fa_mid: k_mid waits for k_front's end itself; here only until every k_front block has STARTED, i.e. is resident -- k_mid's waves cannot shut one out then)
-      if (D.fa_seq > 0 && tid < 64) fa_wait16(D, D.fa_mid ? D.fa_fstart(0) : D.fa_fdone(0), (int)((unsigned)D.fa_seq * (unsigned)D.fa_nfront));
+      ls_begin_next(D, s_last == 1, tid);
     }
   }
   TJ_TIC(D, K_LINESEARCH, 6);
+}
+
+// begin_next = 1: the last block to finish also starts the NEXT iteration (begin_body): the stop test and the counter resets
+// need every block of this kernel to be done, which the ticket establishes; the host then omits the k_begin launch.
+__global__ __launch_bounds__(LS_THREADS) void k_linesearch(Dev D, LsLayout L, int begin_next) {
+  if (ls_enter(D, begin_next)) return;
+  TJ_TIC_ENTRY(D, K_LINESEARCH);
+  extern __shared__ double sm[];
+  __shared__ int pref[1024];   // plane prefix per segment (S <= 511 checked on the host); [512 + tr]: obstacle planes of segment tr
+  // ls_help blocks per robot (super-rounds, below): block h of robot ui is blockIdx = ui + h * owned -- the primaries (h = 0) lead the grid
+  // In the steady phase of a run (every robot takes the full step, iteration after iteration) the helpers have nothing to contribute and cost ~1 us per
+  // launch (their tickets, the table's reset): after LS_QUIET_ITERS such iterations in a row they leave at once and the primaries search on their own
+  // (H = 1 below) until a robot backs off again.
+  const int nown = D.u1 - D.u0;
+  const int H = (D.ls_help > 1 && D.ctl->ls_quiet < LS_QUIET_ITERS) ? D.ls_help : 1;
+  const int h = D.ls_help > 1 ? (int)blockIdx.x / nown : 0;
+  if (h > 0 && H == 1) return;   // (no ticket: the primaries count among themselves then)
+  const int tid = threadIdx.x, u = D.u0 + (int)blockIdx.x - h * nown, S = D.S, G = L.groups;
+  // scalars of the search first: two dependent global round trips that now overlap the staging below
+  const double wolfe = D.wolfe(D.U - 1);  // reference quirk: the global left by the LAST robot (Optimization3D_multi.h:730,792)
+  const double t_dir = D.tdir(u), t0 = D.piece_time[u];
+  double step0 = D.pow08[min(STEP_CAP, max(D.k_obs[u], D.k_self[u]))];
+  const int hist = D.ls_hist[u];   // exponent this robot accepted in the previous iteration (-1: none yet): the round-0 shape follows it
+  if (h > 0 && D.ls_help_late > 0) {   // test hook (TJ_LS_HELP_LATE): this helper starts its staging late -- typically after the primary has committed
+    const long long t_go = wall_clock64() + 100ll * D.ls_help_late;
+    while (wall_clock64() < t_go) __builtin_amdgcn_s_sleep(32);
+  }
+  const LsRobot R = ls_stage(D, L, sm, pref, u, tid, LS_THREADS);
+  const int M = R.M;
+  TJ_TIC(D, K_LINESEARCH, 2);
+  if (t0 + step0 * t_dir <= 0) step0 = -0.95 * t0 / t_dir;
+
+  const LsTeamUnits tu = ls_team_units(S, M);
+  const bool team_ok = D.ls_fast && G == LS_GROUPS && R.in_lds && tu.total() * 64 <= 2 * S * 18;
+  const bool coop = team_ok && H > 1;
+  // A robot with hundreds of planes (next to an obstacle slab; the team shape does not hold its terms) is not a latency chain here but the fp64 issue rate of its compute
+  // unit as well: a round of eight candidates takes it 57 us in the early iterations of config 5 (and ~30 later) where a round of TWO takes 29 (measured: ~20 us is one
+  // wave's chain of 45 passes, ~4.7 us every further candidate on the unit).  In the steady phase of a run -- every robot of the fleet accepted the full step in the previous
+  // iteration -- its FIRST round therefore evaluates only E(x) and the full step, the other waves idle at the barriers; if that fails, full rounds follow.  (Sizing the
+  // first round by the robot's own last exponent while the fleet still backs off was measured too: a wrong guess costs what a right one saves.)  Which candidates share a
+  // round changes no energy and not the order they are looked at in: same step.
+  const bool narrow = !team_ok && G == LS_GROUPS && M >= LS_NARROW_MIN_PLANES && hist == 0 && D.ctl->ls_quiet >= 1 && D.ls_fast;
+  LsSearch s{-1, step0, 0, -1, 0.0, step0, 0, false, false};
+  // (uniform) a helper of a launch that searches in the one-wave shape has nothing to do  (ls_help_mute: test hook -- helpers that never post; every primary then
+  // runs into its 10 us timeout and finishes on its own)
+  if (h > 0 && (!coop || D.ls_help_mute)) s.only_evaluates = true;
+  else if (team_ok && (coop || hist == 0)) s = ls_super_rounds(D, L, R, h, H, t0, t_dir, wolfe, s);
+  if (s.only_evaluates) { ls_ticket(D, h, H, false, begin_next); return; }   // (uniform) a helper: its ticket, nothing else
+  s = ls_wave_rounds(D, L, R, narrow, hist, t0, t_dir, wolfe, s);   // (no round where the super-rounds accepted)
+  ls_publish_hulls(D, L, R, s.wg);
+  TJ_TIC(D, K_LS_COUPLED, 5);
+  ls_commit(D, L, R, H, t0, t_dir, begin_next, s);
+  ls_ticket(D, h, H, s.k_acc != 0, begin_next);
 }
 
 // Energy_admm::spline_energy (Energy_admm.h:16-44) of the CURRENT state against the plane lists of the last iteration: what the
@@ -812,16 +841,11 @@ ticket:
 __global__ __launch_bounds__(LS_THREADS) void k_energy(Dev D, LsLayout L, double* out) {
   extern __shared__ double sm[];
   __shared__ int pref[1024];
-  const int tid = threadIdx.x, u = D.u0 + blockIdx.x, S = D.S, T = D.T, P = D.P;
+  const int tid = threadIdx.x, u = D.u0 + blockIdx.x;
   const int G = L.groups;
   const int g = min(tid / LS_GSIZE, G - 1), gl = tid % LS_GSIZE;
-  bool in_lds;
-  const int M = ls_stage(D, L, sm, pref, u, tid, LS_THREADS, in_lds);
-  double* net = sm + L.net;
-  double* gnet = sm + L.gnet + (size_t)g * 3 * T;
-  for (int i = gl; i < 3 * T; i += LS_GSIZE) gnet[i] = net[i];
-  __syncthreads();
-  const double e = x_energy_group(D, u, sm, L, gnet, D.piece_time[u], sm + L.ghull + (size_t)g * S * 18, sm + L.gcons + (size_t)g * 24 * P, M, in_lds, pref, gl, 0, 0.0);
+  const LsRobot R = ls_stage(D, L, sm, pref, u, tid, LS_THREADS);
+  const double e = ls_eval_candidate(D, L, R, LsCand{-1, 0.0, D.piece_time[u]}, g, gl);
   if (tid == 0) out[u] = e;
 }
 
@@ -833,6 +857,16 @@ __global__ __launch_bounds__(LS_THREADS) void k_energy(Dev D, LsLayout L, double
 // launch (or k_ls_commit) first forms the totals in robot order -- every block computes the same bits --
 // and returns at once when an earlier round already holds the accepted step.
 __device__ __forceinline__ int lsc_cand_k(int round, int c) { return round == 0 ? c - 1 : (LS_GROUPS - 1) + (round - 1) * LS_GROUPS + c; }
+
+// The coupled commit of robot u (Optimization3D_multi.h:625-636), once for k_ls_commit (a block per robot) and the committing block of k_ls_coupled (every robot):
+// entry i of x_u += step d_u (wt: written through, see xs_out), and the robot's record -- the shared piece_time advances by step * t_direction.
+__device__ __forceinline__ void lsc_commit_entry(const Dev& D, int u, int i, double step, bool wt) {
+  double* gs = D.spline + (size_t)u * 3 * D.T;
+  xs_out(wt, gs + i, gs[i] + step * D.dirp(u)[i]);
+}
+__device__ __forceinline__ void lsc_commit_record(const Dev& D, int u, double t0, double t_dir, double step, int kacc) {
+  D.piece_time[u] = t0 + step * t_dir; D.step_out[u] = step; D.blk_stats[(size_t)D.U * D.P + u] += (unsigned long long)(2 + kacc);
+}
 
 // step after the CCD clamps and the t > 0 guard (Optimization3D_multi.h:586-601); wave 0 computes, all threads get it
 __device__ __forceinline__ double lsc_step0(const Dev& D, int tid, double t0, double t_dir, double* s_val) {
@@ -871,8 +905,7 @@ __device__ __forceinline__ void lsc_decide(const Dev& D, int nrounds, double ste
     blk_sync<true>();
     if (lane < RC) for (int j = 0; j < nu; j++) tot += stage[j * RC + lane];
   }
-  double step = step0;
-  if (lane < RC) { const int k = lsc_cand_k(base + r_l, c); for (int i = 0; i < k; i++) step *= 0.8; }   // same rounding as the reference's repeated step *= 0.8
+  const double step = lane < RC ? ls_step_back(step0, lsc_cand_k(base + r_l, c)) : step0;
   const double e0 = base == 0 ? __shfl(tot, 0) : D.ctl->lsc_e0;
   if (e0_out && lane == 0) *e0_out = e0;
   int found_r = -1, found_c = 0; double found_step = step0;
@@ -892,12 +925,9 @@ __device__ __forceinline__ void lsc_decide(const Dev& D, int nrounds, double ste
 __device__ __forceinline__ void lsc_continue(const Dev& D, const LsLayout& L, double* sm, int* pref, double step0, int tid, int* acc, double* accstep) {
   __shared__ double s_tot[LS_GROUPS], s_e0;
   __shared__ int s_hit;
-  const int S = D.S, T = D.T, P = D.P, G = L.groups;
+  const int G = L.groups;
   const int g = min(tid / LS_GSIZE, G - 1), gl = tid % LS_GSIZE;
   const bool shadow = tid / LS_GSIZE >= G;
-  double* net = sm + L.net; double* dir = sm + L.dir;
-  double* gnet = sm + L.gnet + (size_t)g * 3 * T;
-  double* ghull = sm + L.ghull + (size_t)g * S * 18;
   const double wolfe = D.ctl->wolfe_c;
   if (tid == 0) {   // E(x) summed in robot order: column (round 0, slot 0) of the table (written by other blocks of this launch with agent-scope stores)
     double e0 = 0;
@@ -905,24 +935,17 @@ __device__ __forceinline__ void lsc_continue(const Dev& D, const LsLayout& L, do
     s_e0 = e0;
   }
   int k_first = lsc_cand_k(LSC_ROUNDS - 1, LS_GROUPS - 1) + 1;   // 31
-  double step_first = step0;
-  for (int i = 0; i < k_first; i++) step_first *= 0.8;            // same rounding as the reference's repeated step *= 0.8
+  double step_first = ls_step_back(step0, k_first);
   for (int round = LSC_ROUNDS;; round++, k_first += LS_GROUPS) {
     if (tid < LS_GROUPS) s_tot[tid] = 0.0;
     __syncthreads();
     for (int u = D.u0; u < D.u1; u++) {
-      bool in_lds;
-      const int M = ls_stage(D, L, sm, pref, u, tid, LS_THREADS, in_lds);
+      const LsRobot R = ls_stage(D, L, sm, pref, u, tid, LS_THREADS);
       const double t_dir = D.tdir(u), t0 = D.piece_time[u];
       for (int pass = 0; pass < LS_GROUPS / G; pass++) {
         const int slot = pass * G + g;
-        double step = step_first;
-        for (int i = 0; i < slot; i++) step *= 0.8;
-        const double pt = t0 + step * t_dir;
-        __syncthreads();
-        for (int i = gl; i < 3 * T; i += LS_GSIZE) gnet[i] = net[i] + step * dir[i];
-        __syncthreads();
-        const double e = x_energy_group(D, u, sm, L, gnet, pt, ghull, sm + L.gcons + (size_t)g * 24 * P, M, in_lds, pref, gl, 1, step);
+        __syncthreads();   // the previous pass is through with the group buffers
+        const double e = ls_eval_candidate(D, L, R, ls_cand(k_first + slot, ls_step_back(step_first, slot), t0, t_dir), g, gl);
         if (gl == 0 && !shadow) s_tot[slot] += e;   // one writer per slot, robots in order
       }
       __syncthreads();
@@ -932,14 +955,14 @@ __device__ __forceinline__ void lsc_continue(const Dev& D, const LsLayout& L, do
       for (int c = 0; c < LS_GROUPS; c++) { if (hit < 0 && !(s_e0 - 1e-4 * wolfe * st < s_tot[c])) { hit = c; hst = st; } st *= 0.8; }
       if (hit < 0 && k_first + LS_GROUPS - 1 >= STEP_CAP) {   // the fixed point of step *= 0.8: the reference's loop would never end -- take the last candidate and report
         atomicOr(&D.ctl->error, ERR_LOOP_CAP);
-        hit = LS_GROUPS - 1; hst = step_first; for (int i = 0; i < hit; i++) hst *= 0.8;
+        hit = LS_GROUPS - 1; hst = ls_step_back(step_first, hit);
       }
       s_hit = hit;
       if (hit >= 0) { acc[0] = round; acc[1] = hit; *accstep = hst; }
     }
     __syncthreads();
     if (s_hit >= 0) return;
-    for (int i = 0; i < LS_GROUPS; i++) step_first *= 0.8;
+    step_first = ls_step_back(step_first, LS_GROUPS);
   }
 }
 
@@ -950,21 +973,13 @@ __device__ __forceinline__ void lsc_continue(const Dev& D, const LsLayout& L, do
 // in the decoupled chain -- the host then omits k_begin.
 // base (sharded context, the caller follows the search: Dev::lsc_follow): the launch evaluates the rounds [base + round0, ...) into the table's rows [round0, ...)
 __global__ __launch_bounds__(LS_THREADS) void k_ls_coupled(Dev D, LsLayout L, int round0, int wide, int begin_next, int base = 0) {
-  if (D.fa_seq > 0) {   // asynchronous front (one context, all rounds in this launch): as in k_linesearch -- the early begin by the last block of the grid, then every block counts itself started
-    if (blockIdx.x == gridDim.x - 1) fa_early_begin(D);
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(D.fa_res(blockIdx.x), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sig_sent();
-  }
-  if (TJ_DONE(D)) {
-    if (begin_next && blockIdx.x == 0 && threadIdx.x == 0) { D.ctl->slack_now = D.ctl->slack_next; D.ctl->slack_next = 0; }   // (as k_linesearch: retire the slack update k_mid has just paid)
-    return;
-  }
+  if (ls_enter(D, begin_next)) return;   // (asynchronous front: one context, all rounds in this launch)
   extern __shared__ double sm[];
   __shared__ int pref[1024];
   __shared__ int s_acc[2];
   __shared__ double s_step0, s_accstep;
   const int nown = D.u1 - D.u0, hb = wide > 1 ? (int)blockIdx.x / nown : 0, round = base + round0 + hb;
-  const int tid = threadIdx.x, u = D.u0 + (int)blockIdx.x - hb * nown, S = D.S, T = D.T, P = D.P;
+  const int tid = threadIdx.x, u = D.u0 + (int)blockIdx.x - hb * nown, T = D.T;
   // G = L.groups candidates side by side (8 up to piece_num = 10; 4 or 2 for long trajectories, whose hull buffers are larger): a
   // round's LS_GROUPS candidates then take LS_GROUPS / G passes.  Waves beyond G shadow the last group (same values into the same
   // buffers), which keeps every barrier uniform.
@@ -980,21 +995,12 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_coupled(Dev D, LsLayout L, in
   if (round0 > 0 && one_ctx && D.ctl->lsf_epoch == epoch) return;  // an earlier launch already holds the accepted step
   const double t_dir = D.tdir(u), t0 = D.piece_time[u];
   const double step0 = lsc_step0(D, tid, t0, t_dir, &s_step0);
-  bool in_lds;
-  const int M = ls_stage(D, L, sm, pref, u, tid, LS_THREADS, in_lds);
-  double* net = sm + L.net; double* dir = sm + L.dir;
-  double* gnet = sm + L.gnet + (size_t)g * 3 * T;
-  double* ghull = sm + L.ghull + (size_t)g * S * 18;
+  const LsRobot R = ls_stage(D, L, sm, pref, u, tid, LS_THREADS);
   for (int pass = 0; pass < LS_GROUPS / G; pass++) {
     const int slot = pass * G + g;                      // this group's candidate of the round
     const int k = lsc_cand_k(round, slot);
-    double step = step0;
-    for (int i = 0; i < k; i++) step *= 0.8;
-    const double pt = k < 0 ? t0 : t0 + step * t_dir;
     __syncthreads();                                    // the previous pass is through with the group buffers
-    for (int i = gl; i < 3 * T; i += LS_GSIZE) gnet[i] = k < 0 ? net[i] : net[i] + step * dir[i];
-    __syncthreads();
-    const double e = x_energy_group(D, u, sm, L, gnet, pt, ghull, sm + L.gcons + (size_t)g * 24 * P, M, in_lds, pref, gl, k >= 0, step);
+    const double e = ls_eval_candidate(D, L, R, ls_cand(k, ls_step_back(step0, k), t0, t_dir), g, gl);
     if (gl == 0 && !shadow) {
       double* dst = &D.ls_e[((size_t)u * LSC_ROUNDS + (round - base)) * LS_GROUPS + slot];
       if (one_ctx) __hip_atomic_store(dst, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *dst = e;   // one context: write-through, read by the deciding block of THIS launch
@@ -1017,29 +1023,16 @@ __global__ __launch_bounds__(LS_THREADS) void k_ls_coupled(Dev D, LsLayout L, in
   if (tid == 0 && s_acc[0] >= 0) { D.ctl->lsf_r = s_acc[0]; D.ctl->lsf_c = s_acc[1]; D.ctl->lsf_step = s_accstep; D.ctl->lsf_epoch = epoch; }   // read by LATER kernels only
   if (wide < LSC_ROUNDS) return;
   // Every round has been evaluated and every other block is through (the ticket): this block also COMMITS -- k_ls_commit's work for all robots, 3T values
-  // each; the host omits that launch.  Same expressions as k_ls_commit.
+  // each; the host omits that launch.
   __syncthreads();
   const double step = s_accstep;
   const int kacc = lsc_cand_k(s_acc[0], s_acc[1]);   // (lsc_continue always leaves a decision)
-  for (int idx = tid; idx < nown * 3 * T; idx += LS_THREADS) {
-    const int uu = D.u0 + idx / (3 * T), i = idx % (3 * T);
-    double* gs = D.spline + (size_t)uu * 3 * T;
-    xs_out(D.fa_seq > 0, gs + i, gs[i] + step * D.dirp(uu)[i]);
-  }
-  if (D.fa_seq > 0) {   // (uniform) asynchronous front: every robot's control net is out (written through) and acknowledged -> every robot's commit flag
-    sig_acked();
-    __syncthreads();
-    asm volatile("" ::: "memory");
-    for (int uu = D.u0 + tid; uu < D.u1; uu += LS_THREADS) __hip_atomic_store(D.fa_commit(uu), D.fa_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sig_sent();
-  }
-  for (int uu = D.u0 + tid; uu < D.u1; uu += LS_THREADS) {
-    D.piece_time[uu] = D.piece_time[uu] + step * D.tdir(uu); D.step_out[uu] = step; D.blk_stats[(size_t)D.U * D.P + uu] += (unsigned long long)(2 + kacc);
-  }
+  for (int idx = tid; idx < nown * 3 * T; idx += LS_THREADS) lsc_commit_entry(D, D.u0 + idx / (3 * T), idx % (3 * T), step, D.fa_seq > 0);
+  if (D.fa_seq > 0) ls_commit_flags(D, D.u0, D.u1, tid);   // (uniform) every robot's control net is out: every robot's commit flag
+  for (int uu = D.u0 + tid; uu < D.u1; uu += LS_THREADS) lsc_commit_record(D, uu, D.piece_time[uu], D.tdir(uu), step, kacc);
   if (begin_next) {
     __syncthreads();
-    begin_body(D, 0, D.fa_seq > 0);
-    if (D.fa_seq > 0 && tid < 64) fa_wait16(D, D.fa_mid ? D.fa_fstart(0) : D.fa_fdone(0), (int)((unsigned)D.fa_seq * (unsigned)D.fa_nfront));   // (as k_linesearch's last block)
+    ls_begin_next(D, 0, tid);
   }
 }
 
@@ -1072,14 +1065,11 @@ __global__ __launch_bounds__(64) void k_ls_commit(Dev D, int base = 0) {
       if (tid == 0 && blockIdx.x == 0) D.ctl->lsc_pending = 1;
       return;
     }
-    step = step0;
-    for (int i = 0; i < kacc; i++) step *= 0.8;
+    step = ls_step_back(step0, kacc);
     if (tid == 0 && blockIdx.x == 0) atomicOr(&D.ctl->error, at_end ? ERR_LOOP_CAP : (ERR_LOOP_CAP | ERR_LS_RANGE));
   }
-  double* gspline = D.spline + (size_t)u * 3 * T;
-  const double* dir = D.dirp(u);
-  for (int i = tid; i < 3 * T; i += 64) gspline[i] = gspline[i] + step * dir[i];
-  if (tid == 0) { D.piece_time[u] = t0 + step * t_dir; D.step_out[u] = step; D.blk_stats[(size_t)D.U * D.P + u] += (unsigned long long)(2 + kacc); }
+  for (int i = tid; i < 3 * T; i += 64) lsc_commit_entry(D, u, i, step, false);
+  if (tid == 0) lsc_commit_record(D, u, t0, t_dir, step, kacc);
 }
 
 }  // namespace tj

@@ -55,7 +55,7 @@ def pattern(P):
 
 def assemble(lg, lh):
     """reduced H[n][n], g[n] of one robot from its blocks lg[P][19], lh[P][19][19], with the device's sums in the device's order: 0 + first covering piece +
-    second, the time-time entry over all P pieces in piece order (k_xsolve's gather, xb_entry).  Bit for bit what the kernels factor."""
+    second, the time-time entry over all P pieces in piece order (k_xsolve's gather, xs_entry).  Bit for bit what the kernels factor."""
     lg = np.asarray(lg, dtype=np.float64); lh = np.asarray(lh, dtype=np.float64).reshape(len(lg), 19, 19)
     P = len(lg)
     n = dims(P)[0]

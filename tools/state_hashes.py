@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """State hashes of the standard scenes after a fixed number of iterations (GPU only): run it with two builds of the library (TRAJADMM_LIB=<other .so>) to see whether a
-change moved a bit anywhere.   python tools/state_hashes.py [iterations]      prints: scene, sha256 of the state, error bits, pair planes, energy evaluations, and the
-line search's LDS layout as the context planned it (ls_layout: plane_cap / affine / groups)
+change moved a bit anywhere.   python tools/state_hashes.py [iterations] [plan fields]      prints: scene, sha256 of the state, error bits, pair planes, energy evaluations,
+the line search's LDS layout as the context planned it (ls_layout: plane_cap / affine / groups) and the plan fields asked for (comma separated names of PLAN_FIELDS, e.g.
+xs_async,fuse,c2_fold,xf_all: whether a TJ_* switch of the run took effect on that leg)
 
 The P<n> legs (eight robots, `pieces` = n, res = 8) walk the layouts of the line search (kernels_ls.h ls_layout), each at the smallest `pieces` that has it -- found with
 the planner (tj_kat_plan), not by hand: 7 = eight groups, affine trial hulls, planes in LDS (plane_cap 133); 8 = the same with plane_cap 0 (planes read from global memory);
@@ -12,6 +13,7 @@ ROOT = os.environ.get("GRAFT_REPO_ROOT") or os.path.dirname(os.path.dirname(os.p
 sys.path.insert(0, ROOT)
 pkg = importlib.import_module("traj-opt-admm_amd"); sc = pkg.scenes
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+extra = [k for k in (sys.argv[2].split(",") if len(sys.argv) > 2 else []) if k]
 kat = C.CDLL(pkg.KAT_LIB_PATH)   # the test build next to the library under test (same sources, same context record): only its tj_kat_plan reads the plan
 
 
@@ -20,7 +22,7 @@ def ls_layout(s):
     got = kat.tj_kat_plan(s._ctx, None, None, out.ctypes.data_as(C.POINTER(C.c_int)), C.c_int(out.size), None, C.c_int(0))
     assert got == out.size, got
     plan = dict(zip(pkg.PLAN_FIELDS, (int(x) for x in out[len(pkg.PLAN_FACTS):])))
-    return f"plane_cap {plan['lsl_plane_cap']} affine {plan['lsl_affine']} groups {plan['lsl_groups']}"
+    return f"plane_cap {plan['lsl_plane_cap']} affine {plan['lsl_affine']} groups {plan['lsl_groups']}" + "".join(f" {k} {plan[k]}" for k in extra)
 
 
 def layout_leg(pieces, mode=1):

@@ -400,14 +400,46 @@ __device__ __forceinline__ int prefix_count(unsigned long long m) { return __pop
 // piece, segment -> sub-segment) sit in front of the first load of a block.
 __device__ __forceinline__ int div_small(int a, int b) { return (int)(((float)a + 0.5f) * (1.0f / (float)b)); }
 // hull of segment tr of a T x 3 column-major control net: out[j*3+a] = sum_k basis[j][k] * net[3*piece+k][a]
-// accumulated in k order from zero, as every variant in the reference does (e.g. Energy_admm.h:116-129)
-__device__ __forceinline__ double hull_entry(const Dev& D, const double* net, int tr, int j, int a) {
-  const double* B = D.basis + (size_t)tr * 36 + j * 6;
-  const double* col = net + div_small(tr, D.res) * 3 + D.T * a;
+// accumulated in k order from zero, as every variant in the reference does (e.g. Energy_admm.h:116-129); hull_sum: one such sum, B the basis row, col the piece's 6 coordinates
+__device__ __forceinline__ double hull_sum(const double* B, const double* col) {
   double acc = 0;
 #pragma unroll
   for (int k = 0; k < 6; k++) acc += B[k] * col[k];
   return acc;
+}
+__device__ __forceinline__ double hull_entry(const Dev& D, const double* net, int tr, int j, int a) {
+  return hull_sum(D.basis + (size_t)tr * 36 + j * 6, net + div_small(tr, D.res) * 3 + D.T * a);
+}
+// ---- the swept-hull record of a (robot, segment), its arithmetic written ONCE for its three writers (k_xsolve's tail, ccd_prep_segment, ccd_record_async: each keeps
+// its own thread mapping, loads and stores) -- so every rank and every launch form holds the same bits.  BVH::CCDCollision box (BVH.cpp:195-250), SelfCCDCollision
+// box (:289-330), k-DOP intervals of {P, P + D} (CCD.h:416-533).
+// the third hull sum: basis * (net + dir), the box the reference uses for the cloud query (not P + Dh: the sum is taken per control point first)
+__device__ __forceinline__ double hull_sum_pd(const double* B, const double* net, const double* dir) {
+  double acc = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) acc += B[k] * (net[k] + dir[k]);
+  return acc;
+}
+struct HullTriple { double p, dh, pd; };   // one coordinate of the hull of the net, of the direction, and of net + direction
+__device__ __forceinline__ HullTriple hull_triple(const double* B, const double* net, const double* dir) { return HullTriple{hull_sum(B, net), hull_sum(B, dir), hull_sum_pd(B, net, dir)}; }
+// axis a of the two query boxes: the obstacle box over {P, PD} (lo, hi) and the robot-pair box over {P, P + Dh} (lo2, hi2); ps(j): coordinate a of point j of P + Dh
+struct SweptBoxes { double lo, hi, lo2, hi2; };
+template <class PS>
+__device__ __forceinline__ SweptBoxes swept_boxes(const double* P, const double* PD, int a, PS&& ps) {
+  SweptBoxes b{INFINITY, -INFINITY, INFINITY, -INFINITY};
+  for (int j = 0; j < 6; j++) {
+    double v = P[3 * j + a]; if (v < b.lo) b.lo = v; if (v > b.hi) b.hi = v; if (v < b.lo2) b.lo2 = v; if (v > b.hi2) b.hi2 = v;
+    v = PD[3 * j + a]; if (v < b.lo) b.lo = v; if (v > b.hi) b.hi = v;
+    v = ps(j); if (v < b.lo2) b.lo2 = v; if (v > b.hi2) b.hi2 = v;
+  }
+  return b;
+}
+// [lo, up] widened by the six points q (or q + d) along the k-DOP axis (x, y, z); a fresh interval starts at [+inf, -inf]
+__device__ __forceinline__ void kdop_interval6(double x, double y, double z, const double* q, double& lo, double& up) {
+  for (int i = 0; i < 6; i++) { const double lv = x * q[3 * i] + y * q[3 * i + 1] + z * q[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
+}
+__device__ __forceinline__ void kdop_interval6_sum(double x, double y, double z, const double* q, const double* d, double& lo, double& up) {
+  for (int i = 0; i < 6; i++) { const double lv = x * (q[3 * i] + d[3 * i]) + y * (q[3 * i + 1] + d[3 * i + 1]) + z * (q[3 * i + 2] + d[3 * i + 2]); if (lv < lo) lo = lv; if (lv > up) up = lv; }
 }
 // ---- direct exchange between sharded contexts (Dev::xch): producer side ---------------------------------------------------------------------
 // Ordering without fences: a slice is stored with system-scope (write-through, uncached at the destination) stores, the wave then waits until every one of

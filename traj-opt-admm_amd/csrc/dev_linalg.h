@@ -57,6 +57,9 @@ __device__ __forceinline__ double pivot_rsqrt(double x) {
   e = fma(-(x * r), r, 1.0);
   return fma(0.5 * r, e, r);
 }
+// The reference's PSD repair of one diagonal entry, H - ev*I + 0.01*I taken entry by entry (Gradient_admm.h:49-52, Optimization3D_multi.h:703-719):
+// (h - ev) + 0.01 in this association -- a shift summed first rounds differently.  ev: the smallest eigenvalue, negative.
+__device__ __forceinline__ double psd_shift(double h, double ev) { return h - ev * 1.0 + 0.01 * 1.0; }
 
 // In-place lower Cholesky of the row-major n x n matrix A (lower triangle is read and written).
 // Pattern: half-bandwidth bw (bw >= n-1 means dense) plus a dense last row.  Returns false as soon as

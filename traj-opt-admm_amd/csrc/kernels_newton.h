@@ -9,6 +9,12 @@
 //             removal of the fixed end control points, dense Cholesky in LDS with eigen-shift
 //             fallback, solve, wolfe and |g|.  Replaces spline_descent_direction
 //             (Optimization3D_multi.h:659-752, Optimization3D_admm.h:400-503).
+//             Its storage forms (k_xsolve<N> in registers, k_xsolve<0> in LDS, k_xsolve_band, and the coupled mode's corner
+//             in k_xsolve's fold, k_xsolve_c2 and k_xsolve_c2_band) are built from one statement of each piece:
+//             xs_cover / xs_entry / xs_grad_entry (overlap-add; the host's gather table uses xs_cover too), xs_corner (Schur
+//             corner), xs_backsolve_any (back substitution), xs_direction_store + xs_direction_scalars (direction record and
+//             exchange record), psd_shift (dev_linalg.h) and the swept-hull record's hull_triple / swept_boxes /
+//             kdop_interval6 (dev_common.h, shared with ccd_prep_segment and ccd_record_async of kernels_step.h).
 //
 // GPU shape: one thread owns one lower-triangle Hessian entry (or gradient entry); no atomics, no reduction trees, so a
 // result is a function of the inputs alone (bitwise reproducible, and identical in both launch forms).  Barrier derivatives
@@ -471,7 +477,7 @@ __global__ __launch_bounds__(FOLD ? GRAD_FOLD_THREADS : GRAD_THREADS) void k_gra
   __syncthreads();
   if (s_llt == 0) {
     const double ev = s_ev;
-    if (ev < 0 && tid < 19) H[tid * 19 + tid] = H[tid * 19 + tid] - ev * 1.0 + 0.01 * 1.0;
+    if (ev < 0 && tid < 19) H[tid * 19 + tid] = psd_shift(H[tid * 19 + tid], ev);
   }
   __syncthreads();
   TJ_TIC(D, K_GRAD, 5);
@@ -598,11 +604,122 @@ __device__ __forceinline__ bool xs_factor(double* L, double* x0, int n, int tid,
   return chol_arrow_lds<true, true>(L, n, XS_BAND, tid, XS_THREADS, x0, npiv);
 }
 
+// ---- the pieces of the solve, each written ONCE: k_xsolve<N>, k_xsolve<0>, k_xsolve_band and the two corner kernels call these on the same operands, so their
+// storage forms agree bit for bit by construction (tests: dense against band at P = 2..10, folded against separate corner) ----
+// Overlap-add of the piece blocks (Gradient_admm.h:55-62) in gather form.  Global index of local (sp, a) is 9*sp + a, the piece time is one shared unknown.  Reduced
+// index r = global - 6 for 6 <= global < 3T-6 (the fixed end control points are gone), time -> m; xs_global gives the global index back, -1 = time.  Every reduced
+// entry sums the piece blocks that cover it (at most two; all P for time-time) in piece order from 0, like the reference's += sequence: no read-modify-write.
+struct XsCover { int lo, hi; };   // pieces lo..hi
+__host__ __device__ inline int xs_global(int r, int m) { return r == m ? -1 : r + 6; }
+__host__ __device__ inline XsCover xs_cover(int g, int P) {   // pieces covering coordinate g: 9 sp <= g <= 9 sp + 17 (g >= 6); time: every piece
+  if (g < 0) return XsCover{0, P - 1};
+  const int lo = (g - 17 + 8) / 9, hi = g / 9;
+  return XsCover{lo, hi < P - 1 ? hi : P - 1};
+}
+__host__ __device__ inline XsCover xs_cover(int ga, int gb, int P) {   // ... covering both
+  const XsCover a = xs_cover(ga, P), b = xs_cover(gb, P);
+  return XsCover{a.lo > b.lo ? a.lo : b.lo, a.hi < b.hi ? a.hi : b.hi};
+}
+__host__ __device__ inline int xs_local(int g, int sp) { return g < 0 ? 18 : g - 9 * sp; }   // index of g in piece sp's 19-block (18: the piece time)
+// assembled Hessian entry (ga, gb) / gradient entry ga; src: the P piece blocks, in LDS (lhu / lgu) or global memory (Dev::lh / Dev::lg)
+__device__ __forceinline__ double xs_entry(const double* src, int P, int ga, int gb) {
+  const XsCover c = xs_cover(ga, gb, P);
+  double acc = 0;
+  for (int sp = c.lo; sp <= c.hi; sp++) acc += src[(size_t)sp * 361 + xs_local(ga, sp) * 19 + xs_local(gb, sp)];
+  return acc;
+}
+__device__ __forceinline__ double xs_grad_entry(const double* src, int P, int ga) {
+  const XsCover c = xs_cover(ga, P);
+  double acc = 0;
+  for (int sp = c.lo; sp <= c.hi; sp++) acc += src[sp * 19 + xs_local(ga, sp)];
+  return acc;
+}
+
+// Coupled mode: the Schur corner sum_u (h_t,u - y_u.y_u) and its right-hand side, summed by lanes 0 and 1 (lane 2: G_t) in robot order out of Dev::xcorner -- CHUNK
+// robots per coalesced pass through `stage` (4 * CHUNK doubles), the sums in robot order whatever the chunking, so every block and every form has the same bits --
+// then the corner pivot.  WT: the terms were written through by blocks of this launch (folded corner).  red: 3 doubles.  One wave.
+struct XsCorner { double lc, rhs; };   // reciprocal root of the corner (like the rest of the FAST factor's diagonal), right-hand side
+template <int CHUNK, bool WT>
+__device__ __forceinline__ XsCorner xs_corner(const Dev& D, int tid, double* stage, double* red) {
+  double acc = 0;
+  for (int r0 = 0; r0 < D.U; r0 += CHUNK) {
+    const int nr = min(CHUNK, D.U - r0);
+    blk_sync<true>();
+    for (int i = tid; i < 4 * nr; i += XS_THREADS) stage[i] = WT ? xf_load(D.xcorner + (size_t)r0 * 4 + i) : D.xcorner[(size_t)r0 * 4 + i];
+    blk_sync<true>();
+    if (tid < 3) for (int r = 0; r < nr; r++) acc += stage[4 * r + tid];
+  }
+  blk_sync<true>();
+  if (tid < 3) red[tid] = acc;
+  blk_sync<true>();
+  const double corner = red[0], rhs = red[1];
+  blk_sync<true>();   // (red may be scratch the caller goes on to use)
+  if (!(corner > 0) && tid == 0 && blockIdx.x == 0) atomicOr(&D.ctl->error, ERR_NOT_SPD);
+  return XsCorner{pivot_rsqrt(corner), rhs};
+}
+
+// y <- L^-T y on the dense factor in LDS, by one wave: registers up to n = 64 (NREG > 0: the size is the kernel's template argument, the body inlined), LDS beyond
+template <int NREG>
+__device__ __forceinline__ void xs_backsolve_any(const double* L, int n, double* y, int tid) {
+  if (n <= 64) {
+    double yv = y[min(tid, n - 1)];
+    if constexpr (NREG > 0) yv = backsolve_wave_body<NREG>(L, yv, tid); else yv = xs_backsolve(L, n, yv, tid);
+    blk_sync<true>();
+    if (tid < n) y[tid] = yv;
+    blk_sync<true>();
+  } else chol_arrow_backsolve_lds<true, true>(L, n, XS_BAND, y, tid, XS_THREADS);
+}
+
+// The direction record of robot u, from the solved system y (n unknowns, the last one the piece time) and its right-hand side g0.  One wave; scr: 2n doubles, and
+// 3T + 3 where the exchange record is formed (FINAL).  wt: the stores go out written through (asynchronous solve: kernels on the other queue read the record while this launch runs).
+// entry idx of the T x 3 direction: the fixed end control points (rows 0, 1, T-2, T-1) do not move
+__device__ __forceinline__ double xs_dir_entry(const double* y, int idx, int T) {
+  const int row = idx % T, a = idx / T;
+  return (row >= 2 && row < T - 2) ? y[3 * (row - 2) + a] : 0.0;
+}
+// first half: y <- -y, and the direction
+__device__ __forceinline__ void xs_direction_store(const Dev& D, int u, int tid, int n, double* y, bool wt) {
+  for (int i = tid; i < n; i += XS_THREADS) y[i] = -y[i];
+  blk_sync<true>();
+  double* dir = D.dirp(u);
+  for (int idx = tid; idx < 3 * D.T; idx += XS_THREADS) xs_out(wt, dir + idx, xs_dir_entry(y, idx, D.T));
+}
+// second half: the scalars.  FINAL (decoupled / single UAV): wolfe = -x.g and |g| over all n unknowns, gnorm for a single UAV, and the record pushed to the peers of
+// a sharded context.  Otherwise (coupled) the partial sums of x.g and g.g over this robot's n-1 control-point unknowns and its share of G_t: k_ccd_self_seq completes
+// them in robot order.  WAVE: the sums by esum_wave (the whole wave), else by esum -- two association orders, not interchangeable: each caller keeps its own.
+template <bool FINAL, bool WAVE>
+__device__ __forceinline__ void xs_direction_scalars(const Dev& D, int u, int tid, int n, const double* y, const double* g0, double* scr, bool wt) {
+  const int T = D.T, m = n - 1, cnt = FINAL ? n : m;
+  for (int i = tid; i < cnt; i += XS_THREADS) { scr[i] = y[i] * g0[i]; scr[n + i] = g0[i] * g0[i]; }
+  blk_sync<true>();
+  const double xg = WAVE ? esum_wave(scr, cnt, tid) : esum(scr, cnt), gg = WAVE ? esum_wave(scr + n, cnt, tid) : esum(scr + n, cnt);
+  const double w_ = FINAL ? -xg : xg, g_ = FINAL ? sqrt(gg) : gg;
+  if (tid == 0) {
+    xs_out(wt, &D.wolfe(u), w_);
+    xs_out(wt, &D.gn(u), g_);
+    xs_out(wt, &D.tdir(u), y[m]);   // coupled: the shared t_direction (same bits on every robot)
+    if (!FINAL) xs_out(wt, D.xdir + (size_t)u * D.xs + 3 * T + 3, g0[m]);
+    else if (!D.multi()) xs_out(wt, &D.ctl->gnorm, g_);   // single UAV (Optimization3D_admm.h:499): what k_ccd_self_seq would copy; the chain skips that launch
+  }
+  if (FINAL && D.xch) {   // direct exchange (sharded contexts): the same values straight into every peer's receive buffer
+    blk_sync<true>();
+    for (int idx = tid; idx < 3 * T; idx += XS_THREADS) scr[idx] = xs_dir_entry(y, idx, T);
+    if (tid == 0) { scr[3 * T] = y[m]; scr[3 * T + 1] = w_; scr[3 * T + 2] = g_; }
+    blk_sync<true>();
+    xch_push_robot<true>(D, 1, u, D.xs, scr, 3 * T + 3, tid, XS_THREADS);
+  }
+}
+template <bool FINAL, bool WAVE>
+__device__ __forceinline__ void xs_direction_record(const Dev& D, int u, int tid, int n, double* y, const double* g0, double* scr, bool wt) {
+  xs_direction_store(D, u, tid, n, y, wt);
+  xs_direction_scalars<FINAL, WAVE>(D, u, tid, n, y, g0, scr, wt);
+}
+
 // wave 0 of k_xsolve: factor, solve, direction record (all sync points are wave-local)
 template <int NREG>
 __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, int m, double* H, double* L, double* g0, double* x0, double* scr) {
-  const int T = D.T;
   TJ_TIC(D, K_XSOLVE, 2);
+  const bool wt = D.xs_async != 0;   // asynchronous solve: k_ccd's units (other queue) read the record while this launch is still running
   if (D.coupled()) {
     // Optimization3D_multi::update_spline (Optimization3D_multi.h:519-557): this robot's block of the
     // arrowhead system.  Eliminate the m control-point unknowns; what is left of the last row is the
@@ -613,58 +730,18 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
     blk_sync<true>();
     if (D.c2_fold) {
       // One context, every robot's block resident at once (round 5): the corner terms go out written through, the block counts itself in, waits until all uav_num are there
-      // and finishes the arrowhead solve itself -- k_xsolve_c2's operations on the factor that is still in LDS (that launch re-read 15 KB per robot): the corner summed in
-      // robot order, its pivot, the back substitution, the direction record.  Same operations in the same order, hence the same bits (TJ_C2_FOLD=0: the separate launch).
+      // and finishes the arrowhead solve itself -- k_xsolve_c2's calls on the factor that is still in LDS (that launch re-read 15 KB per robot).  TJ_C2_FOLD=0: the separate launch.
       double* oc = D.xcorner + (size_t)u * 4;
       if (tid == 0) { xf_store(oc, L[m * n + m]); xf_store(oc + 1, x0[m]); xf_store(oc + 2, g0[m]); xf_store(oc + 3, 0.0); }
       sig_acked();
       if (tid == 0) __hip_atomic_fetch_add(&D.ctl->c2_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       sig_sent();
       if (!poll_until<2>([&] { return xf_load_i(&D.ctl->c2_cnt) >= D.U; }, WAIT_5MS)) wait_failed(D, ERR_LOOP_CAP | ERR_PASS_TIMEOUT);
-      double* s_cstage = scr; double* s_red = scr + 64;   // (the scratch of the solve, >= 96 doubles and idle here: static arrays would push the 88-row system over the LDS limit)
-      {
-        double acc = 0;
-        for (int r0 = 0; r0 < D.U; r0 += 16) {   // sixteen robots per pass; the sums run in robot order whatever the chunking
-          const int nr = min(16, D.U - r0);
-          blk_sync<true>();
-          for (int i = tid; i < 4 * nr; i += XS_THREADS) s_cstage[i] = xf_load(D.xcorner + (size_t)r0 * 4 + i);
-          blk_sync<true>();
-          if (tid < 3) for (int r = 0; r < nr; r++) acc += s_cstage[4 * r + tid];
-        }
-        blk_sync<true>();
-        if (tid < 3) s_red[tid] = acc;
-      }
+      const XsCorner c = xs_corner<16, true>(D, tid, scr, scr + 64);   // (the scratch of the solve, >= 96 doubles and idle here: static arrays would push the 88-row system over the LDS limit)
+      if (tid == 0) { L[m * n + m] = c.lc; x0[m] = c.rhs * c.lc; }
       blk_sync<true>();
-      const double corner = s_red[0], rhs = s_red[1];
-      blk_sync<true>();
-      if (!(corner > 0) && tid == 0 && blockIdx.x == 0) atomicOr(&D.ctl->error, ERR_NOT_SPD);
-      const double lc = pivot_rsqrt(corner);
-      double* y = x0;
-      if (tid == 0) { L[m * n + m] = lc; y[m] = rhs * lc; }
-      blk_sync<true>();
-      if (n <= 64) {
-        double yv = y[min(tid, n - 1)];
-        yv = xs_backsolve(L, n, yv, tid);
-        blk_sync<true>();
-        if (tid < n) y[tid] = yv;
-        blk_sync<true>();
-      } else chol_arrow_backsolve_lds<true, true>(L, n, XS_BAND, y, tid, XS_THREADS);
-      for (int i = tid; i < n; i += XS_THREADS) y[i] = -y[i];
-      blk_sync<true>();
-      for (int i = tid; i < m; i += XS_THREADS) { scr[i] = y[i] * g0[i]; scr[n + i] = g0[i] * g0[i]; }
-      blk_sync<true>();
-      const bool wtc = D.xs_async != 0;   // asynchronous solve: k_ccd's units (other queue) read the record while this launch is still running
-      double* dirc = D.dirp(u);
-      for (int idx = tid; idx < 3 * T; idx += XS_THREADS) {
-        const int row = idx % T, a = idx / T;
-        xs_out(wtc, dirc + idx, (row >= 2 && row < T - 2) ? y[3 * (row - 2) + a] : 0.0);
-      }
-      if (tid == 0) {
-        xs_out(wtc, &D.wolfe(u), esum(scr, m));
-        xs_out(wtc, &D.gn(u), esum(scr + n, m));
-        xs_out(wtc, &D.tdir(u), y[m]);
-        xs_out(wtc, D.xdir + (size_t)u * D.xs + 3 * T + 3, g0[m]);
-      }
+      xs_backsolve_any<0>(L, n, x0, tid);   // (the out-of-line back substitution: the inlined body is the decoupled path's)
+      xs_direction_record<false, false>(D, u, tid, n, x0, g0, scr, wt);
       return;
     }
     double* oL = D.xL + (size_t)u * n * n; double* oy = D.xy + (size_t)u * n; double* og = D.xg + (size_t)u * n;
@@ -680,7 +757,7 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
       for (int idx = tid; idx < n * n; idx += XS_THREADS) L[idx] = H[idx];
       blk_sync<true>();
       const double ev = min_eig_lds<true>(L, n, scr, scr + n, scr + 2 * n, scr + 3 * n, tid, XS_THREADS);   // (wave-local sync points: the helper waves sit at the tail's barrier)
-      if (ev < 0) for (int i = tid; i < n; i += XS_THREADS) H[i * n + i] = H[i * n + i] - ev * 1.0 + 0.01 * 1.0;
+      if (ev < 0) for (int i = tid; i < n; i += XS_THREADS) H[i * n + i] = psd_shift(H[i * n + i], ev);
       blk_sync<true>();
     }
     for (int idx = tid; idx < n * n; idx += XS_THREADS) L[idx] = H[idx];
@@ -690,22 +767,9 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
     blk_sync<true>();
   }
   TJ_TIC(D, K_XSOLVE, 3);
-  if (n <= 64) {
-    double yv = x0[min(tid, n - 1)];
-    if constexpr (NREG > 0) yv = backsolve_wave_body<NREG>(L, yv, tid); else yv = xs_backsolve(L, n, yv, tid);
-    blk_sync<true>();
-    if (tid < n) x0[tid] = yv;
-    blk_sync<true>();
-  } else chol_arrow_backsolve_lds<true, true>(L, n, XS_BAND, x0, tid, XS_THREADS);
+  xs_backsolve_any<NREG>(L, n, x0, tid);
   TJ_TIC(D, K_XSOLVE, 4);
-  for (int i = tid; i < n; i += XS_THREADS) { x0[i] = -x0[i]; scr[i] = 0; }
-  blk_sync<true>();
-  const bool wt = D.xs_async != 0;
-  double* dir = D.dirp(u);
-  for (int idx = tid; idx < 3 * T; idx += XS_THREADS) {
-    const int row = idx % T, a = idx / T;
-    xs_out(wt, dir + idx, (row >= 2 && row < T - 2) ? x0[3 * (row - 2) + a] : 0.0);
-  }
+  xs_direction_store(D, u, tid, n, x0, wt);
   if (wt) {
     // asynchronous solve: k_ccd's units of this robot wait for the DIRECTION only -- its flag goes up as soon as those stores are acknowledged; wolfe, |g| and the
     // time direction (read by k_ccd's finisher and by k_linesearch) follow and are counted (xs_done) -- k_ccd does not end before the count is full: its finisher
@@ -714,22 +778,19 @@ __device__ __forceinline__ void xs_wave0(const Dev& D, int u, int tid, int n, in
     if (tid == 0) __hip_atomic_store(D.xs_flag(u), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     sig_sent();
   }
-  for (int i = tid; i < n; i += XS_THREADS) { scr[i] = x0[i] * g0[i]; scr[n + i] = g0[i] * g0[i]; }
-  blk_sync<true>();
-  const double w_ = esum_wave(scr, n, tid), g_ = esum_wave(scr + n, n, tid);
-  if (tid == 0) {
-    xs_out(wt, &D.wolfe(u), -w_);
-    xs_out(wt, &D.gn(u), sqrt(g_));
-    xs_out(wt, &D.tdir(u), x0[m]);
-    if (!D.multi()) xs_out(wt, &D.ctl->gnorm, sqrt(g_));   // single UAV (Optimization3D_admm.h:499): what k_ccd_self_seq would copy; the chain skips that launch
-  }
-  if (D.xch) {   // direct exchange (sharded contexts): the record goes straight into every peer's receive buffer, under the swept-hull tail of this block
-    blk_sync<true>();
-    for (int idx = tid; idx < 3 * T; idx += XS_THREADS) { const int row = idx % T, a = idx / T; scr[idx] = (row >= 2 && row < T - 2) ? x0[3 * (row - 2) + a] : 0.0; }
-    if (tid == 0) { scr[3 * T] = x0[m]; scr[3 * T + 1] = -w_; scr[3 * T + 2] = sqrt(g_); }
-    blk_sync<true>();
-    xch_push_robot<true>(D, 1, u, D.xs, scr, 3 * T + 3, tid, XS_THREADS);
-  }
+  xs_direction_scalars<true, true>(D, u, tid, n, x0, g0, scr, wt);   // (a sharded context's exchange record goes out under the swept-hull tail of this block)
+}
+
+// k_xsolve's swept-hull tail, flat hull-value index idx = 18 * segment + 3 * point + axis: the basis row of the value and the first of its piece's six coordinates in a T x 3 net
+__device__ __forceinline__ const double* xs_hull_basis(const Dev& D, int idx) { return D.basis + (size_t)(idx / 18) * 36 + ((idx % 18) / 3) * 6; }
+__device__ __forceinline__ int xs_hull_row(const Dev& D, int idx) { return div_small(idx / 18, D.res) * 3 + D.T * (idx % 3); }
+// (segment, axis) pair idx = 49 * segment + axis: the interval [lo, up] so far, widened by the six points P + Dh of the segment's hull values (Ph: [S][54]), goes to the record
+__device__ __forceinline__ void xs_swept_interval_out(const Dev& D, int u, const double* Ph, int idx, double lo, double up, bool wt) {
+  const int tr = idx / 49, k = idx % 49;
+  const double* ax = D.kdop + 3 * k;
+  kdop_interval6_sum(ax[0], ax[1], ax[2], Ph + tr * 54, Ph + tr * 54 + 18, lo, up);
+  double* o = D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE;
+  xs_out(wt, o + 48 + k, lo); xs_out(wt, o + 97 + k, up);
 }
 
 // asynchronous solve: the gate in front of k_xsolve on the second queue (one wave, no LDS: it may sit there through the rest of the previous iteration)
@@ -754,13 +815,9 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
   double* x0 = g0 + n;       // [n]
   double* scr = x0 + n;      // [6n]
 
-  // overlap-add of piece blocks; global index of local (sp, a) is 9*sp + a, time is 3T.
-  // Reduced index r = global - 6 for 6 <= global < 3T-6, time -> m.
-  // Gather form of the overlap-add: every reduced entry sums the (at most two, or P for the
-  // time-time entry) piece blocks that cover it, in piece order like the reference's += sequence.
-  // No read-modify-write, so all global loads of a pass are in flight together.
-  // piece blocks first go to LDS with one streaming copy (independent loads, many in flight); the
-  // scatter below then never waits on HBM/L2
+  // The body in order: (1) fetch the gather sources, (2) wait for the piece blocks (asynchronous solve), (3) stream them into LDS with one copy (independent loads,
+  // many in flight: the assembly then never waits on HBM / L2), (4) assemble the reduced system (xs_entry / xs_grad_entry), (5) wave 0 factors, solves and leaves the
+  // direction record (xs_wave0) while the helper waves prepare the swept-hull tail, (6) the tail.
   TJ_TIC(D, K_XSOLVE, 0);
   __shared__ int s_grp;               // arrival counter of the helper waves' private barrier
   if (tid == 0) s_grp = 0;
@@ -800,20 +857,21 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
   }
   __syncthreads();
   TJ_TIC(D, K_XSOLVE, 1);
-  if constexpr (NREG > 0) {   // the same sums in the same order (0 + first covering piece + second), sources from the table
+  // assemble: one thread per entry of the reduced system
+  if constexpr (NREG > 0) {   // xs_entry's sums in its order (0 + first covering piece + second), sources from the table
 #pragma unroll
     for (int k = 0; k < XS_EPT; k++) {
       const int idx = tid + k * XS_LOAD_THREADS;
       if (idx < n * n) {
         double acc = 0;
-        if (gs0[k] == -2) { for (int sp = 0; sp < D.P; sp++) acc += lhu[(size_t)sp * 361 + 18 * 19 + 18]; }
+        if (gs0[k] == -2) acc = xs_entry(lhu, D.P, -1, -1);
         else { if (gs0[k] >= 0) acc += lhu[gs0[k]]; if (gs1[k] >= 0) acc += lhu[gs1[k]]; }
         H[idx] = acc; L[idx] = acc;
       }
     }
     if (tid < n) {
       double acc = 0;
-      if (gv0 == -2) { for (int sp = 0; sp < D.P; sp++) acc += lgu[sp * 19 + 18]; }
+      if (gv0 == -2) acc = xs_grad_entry(lgu, D.P, -1);
       else { if (gv0 >= 0) acc += lgu[gv0]; if (gv1 >= 0) acc += lgu[gv1]; }
       g0[tid] = acc; x0[tid] = acc;
     }
@@ -821,28 +879,15 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
     int ra = tid / n, rb = tid % n;  // (row, column) of entry idx, advanced incrementally
     const int dra = XS_LOAD_THREADS / n, drb = XS_LOAD_THREADS % n;
     for (int idx = tid; idx < n * n; idx += XS_LOAD_THREADS) {
-      const int ga = ra == m ? -1 : ra + 6, gb = rb == m ? -1 : rb + 6;  // -1 = time
-      // pieces covering a coordinate g: 9sp <= g <= 9sp+17
-      int lo = 0, hi = D.P - 1;
-      if (ga >= 0) { lo = max(lo, (ga - 17 + 8) / 9); hi = min(hi, ga / 9); }
-      if (gb >= 0) { lo = max(lo, (gb - 17 + 8) / 9); hi = min(hi, gb / 9); }
-      double acc = 0;
-      for (int sp = max(lo, 0); sp <= hi; sp++) {
-        const int a = ga < 0 ? 18 : ga - 9 * sp, b = gb < 0 ? 18 : gb - 9 * sp;
-        acc += lhu[(size_t)sp * 361 + a * 19 + b];
-      }
+      const double acc = xs_entry(lhu, D.P, xs_global(ra, m), xs_global(rb, m));
       H[idx] = acc; L[idx] = acc;
       ra += dra; rb += drb;
       if (rb >= n) { rb -= n; ra++; }
     }
-  for (int ra = tid; ra < n; ra += XS_LOAD_THREADS) {
-    const int ga = ra == m ? -1 : ra + 6;
-    int lo = 0, hi = D.P - 1;
-    if (ga >= 0) { lo = max(lo, (ga - 17 + 8) / 9); hi = min(hi, ga / 9); }
-    double acc = 0;
-    for (int sp = max(lo, 0); sp <= hi; sp++) acc += lgu[sp * 19 + (ga < 0 ? 18 : ga - 9 * sp)];
-    g0[ra] = acc; x0[ra] = acc;
-  }
+    for (int ra = tid; ra < n; ra += XS_LOAD_THREADS) {
+      const double acc = xs_grad_entry(lgu, D.P, xs_global(ra, m));
+      g0[ra] = acc; x0[ra] = acc;
+    }
   }
   __syncthreads();
   // From here on wave 0 works alone (its sync points are wave-local: blk_sync<true>).  Without the swept-hull tail the other
@@ -879,52 +924,33 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
     int target = 0;
     for (int idx = ht; idx < 3 * T; idx += XS_HELP) netl[idx] = gnet[idx];
     group_barrier(&s_grp, target, XS_HELP / 64);
-    for (int idx = ht; idx < S * 18; idx += XS_HELP) {
-      const int tr = idx / 18, e = idx % 18, j = e / 3, a = e % 3;
-      const double* B = D.basis + (size_t)tr * 36 + j * 6;
-      const int r0 = div_small(tr, D.res) * 3 + T * a;
-      double p = 0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) p += B[k] * netl[r0 + k];
-      php[idx] = p;
-    }
+    for (int idx = ht; idx < S * 18; idx += XS_HELP) php[idx] = hull_sum(xs_hull_basis(D, idx), netl + xs_hull_row(D, idx));
     group_barrier(&s_grp, target, XS_HELP / 64);
 #pragma unroll
     for (int q_ = 0; q_ < XS_KPT; q_++) {
       const int idx = ht + q_ * XS_HELP;
       double up = -INFINITY, lo = INFINITY;
-      if (idx < S * 49) {
-        const int tr = idx / 49, k = idx % 49;
-        const double* q = php + tr * 18;
-        const double x = D.kdop[3 * k], y = D.kdop[3 * k + 1], z = D.kdop[3 * k + 2];
-        for (int i = 0; i < 6; i++) { const double lv = x * q[3 * i] + y * q[3 * i + 1] + z * q[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-      }
+      if (idx < S * 49) { const double* ax = D.kdop + 3 * (idx % 49); kdop_interval6(ax[0], ax[1], ax[2], php + (idx / 49) * 18, lo, up); }
       klo[q_] = lo; kup[q_] = up;
     }
   }
   if (!tail) return;
   __syncthreads();
   TJ_TIC(D, K_XSOLVE, 5);
-  // ---- swept-hull cache of this robot for the two CCD stages (what k_ccd_prep computes; same expressions, same bits) ----
-  // BVH::CCDCollision box (BVH.cpp:195-250), SelfCCDCollision box (:289-330), k-DOP intervals of {P, P + D} (CCD.h:416-533).
+  // ---- swept-hull cache of this robot for the two CCD stages: what k_ccd_prep computes, by the same functions (dev_common.h) ----
   // Flat over the whole block: 54 hull values per segment into LDS (the front of the buffer is free now), then boxes and the
   // 49 x S interval pairs.  Folding this into the solve kernel removes one kernel boundary from the chain.
   {
     for (int idx = tid; idx < 3 * T; idx += XS_LOAD_THREADS) {
-      const int row = idx % T, a = idx / T;
       if (!pre) netl[idx] = gnet[idx];
-      dl[idx] = (row >= 2 && row < T - 2) ? x0[3 * (row - 2) + a] : 0.0;
+      dl[idx] = xs_dir_entry(x0, idx, T);
     }
     __syncthreads();
     double* Ph = sm;   // [S][54]: P[18], Dh[18], PD[18]; PS = P + Dh is formed on the fly
     for (int idx = tid; idx < S * 18; idx += XS_LOAD_THREADS) {
-      const int tr = idx / 18, e = idx % 18, j = e / 3, a = e % 3;
-      const double* B = D.basis + (size_t)tr * 36 + j * 6;
-      const int r0 = div_small(tr, D.res) * 3 + T * a;
-      double p = 0, dh = 0, pd = 0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) { p += B[k] * netl[r0 + k]; dh += B[k] * dl[r0 + k]; pd += B[k] * (netl[r0 + k] + dl[r0 + k]); }
-      Ph[tr * 54 + e] = p; Ph[tr * 54 + 18 + e] = dh; Ph[tr * 54 + 36 + e] = pd;
+      const int tr = idx / 18, e = idx % 18, r0 = xs_hull_row(D, idx);
+      const HullTriple h = hull_triple(xs_hull_basis(D, idx), netl + r0, dl + r0);
+      Ph[tr * 54 + e] = h.p; Ph[tr * 54 + 18 + e] = h.dh; Ph[tr * 54 + 36 + e] = h.pd;
     }
     __syncthreads();
     for (int idx = tid; idx < S * 36; idx += XS_LOAD_THREADS) {   // P, Dh
@@ -934,15 +960,10 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
     for (int idx = tid; idx < S * 3; idx += XS_LOAD_THREADS) {    // obstacle box over {P, PD}, pair box over {P, P + Dh}
       const int tr = idx / 3, a = idx % 3;
       const double* q = Ph + tr * 54;
-      double lo = INFINITY, hi = -INFINITY, lo2 = INFINITY, hi2 = -INFINITY;
-      for (int j = 0; j < 6; j++) {
-        double v = q[3 * j + a]; if (v < lo) lo = v; if (v > hi) hi = v; if (v < lo2) lo2 = v; if (v > hi2) hi2 = v;
-        v = q[36 + 3 * j + a]; if (v < lo) lo = v; if (v > hi) hi = v;
-        v = q[3 * j + a] + q[18 + 3 * j + a]; if (v < lo2) lo2 = v; if (v > hi2) hi2 = v;
-      }
+      const SweptBoxes b = swept_boxes(q, q + 36, a, [&](int j) { return q[3 * j + a] + q[18 + 3 * j + a]; });
       double* o = D.ccdinfo + ((size_t)u * S + tr) * CCD_STRIDE;
-      xs_out(wt, o + 36 + a, lo); xs_out(wt, o + 39 + a, hi); xs_out(wt, o + 42 + a, lo2); xs_out(wt, o + 45 + a, hi2);
-      xs_out(wt, D.cbox + ((size_t)tr * 6 + a) * D.U + u, lo2); xs_out(wt, D.cbox + ((size_t)tr * 6 + 3 + a) * D.U + u, hi2);
+      xs_out(wt, o + 36 + a, b.lo); xs_out(wt, o + 39 + a, b.hi); xs_out(wt, o + 42 + a, b.lo2); xs_out(wt, o + 45 + a, b.hi2);
+      xs_out(wt, D.cbox + ((size_t)tr * 6 + a) * D.U + u, b.lo2); xs_out(wt, D.cbox + ((size_t)tr * 6 + 3 + a) * D.U + u, b.hi2);
     }
     // 49-axis intervals of the swept hull at step 1: min / max over the 6 hull points and the 6 points P + Dh.  With the
     // hull's part already known (helpers), only the second half is left -- min and max do not depend on the order.
@@ -951,26 +972,14 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
 #pragma unroll
         for (int q_ = 0; q_ < XS_KPT; q_++) {
           const int idx = ht + q_ * XS_HELP;
-          if (idx < S * 49) {
-            const int tr = idx / 49, k = idx % 49;
-            const double* q = Ph + tr * 54;
-            const double x = D.kdop[3 * k], y = D.kdop[3 * k + 1], z = D.kdop[3 * k + 2];
-            double up = kup[q_], lo = klo[q_];
-            for (int i = 0; i < 6; i++) { const double lv = x * (q[3 * i] + q[18 + 3 * i]) + y * (q[3 * i + 1] + q[18 + 3 * i + 1]) + z * (q[3 * i + 2] + q[18 + 3 * i + 2]); if (lv < lo) lo = lv; if (lv > up) up = lv; }
-            double* o = D.ccdinfo + ((size_t)u * S + tr) * CCD_STRIDE;
-            xs_out(wt, o + 48 + k, lo); xs_out(wt, o + 97 + k, up);
-          }
+          if (idx < S * 49) xs_swept_interval_out(D, u, Ph, idx, klo[q_], kup[q_], wt);
         }
       }
     } else for (int idx = tid; idx < S * 49; idx += XS_LOAD_THREADS) {
-      const int tr = idx / 49, k = idx % 49;
-      const double* q = Ph + tr * 54;
-      const double x = D.kdop[3 * k], y = D.kdop[3 * k + 1], z = D.kdop[3 * k + 2];
+      const double* ax = D.kdop + 3 * (idx % 49);
       double up = -INFINITY, lo = INFINITY;
-      for (int i = 0; i < 6; i++) { const double lv = x * q[3 * i] + y * q[3 * i + 1] + z * q[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-      for (int i = 0; i < 6; i++) { const double lv = x * (q[3 * i] + q[18 + 3 * i]) + y * (q[3 * i + 1] + q[18 + 3 * i + 1]) + z * (q[3 * i + 2] + q[18 + 3 * i + 2]); if (lv < lo) lo = lv; if (lv > up) up = lv; }
-      double* o = D.ccdinfo + ((size_t)u * S + tr) * CCD_STRIDE;
-      xs_out(wt, o + 48 + k, lo); xs_out(wt, o + 97 + k, up);
+      kdop_interval6(ax[0], ax[1], ax[2], Ph + (idx / 49) * 54, lo, up);
+      xs_swept_interval_out(D, u, Ph, idx, lo, up, wt);
     }
   }
 #ifdef TJ_PHASE_LIGHT
@@ -984,21 +993,13 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
 // ---- long trajectories (Dev::xs_band: piece_num > 10, or TJ_XS_BAND=1 for testing): the same solve on band storage ----------
 // n = 9P-2 grows past what a dense n x n copy in LDS allows (P = 11 already needs 2 x 74 KB), while the system itself is a band
 // of half-width 17 plus one arrow row: n x 18 + n doubles (26 KB at P = 20).  One workgroup per robot; the band entries are
-// gathered straight from the per-piece blocks in HBM (each is the sum of at most two of them, in piece order like the
-// reference's += sequence), wave 0 factors and solves with the band routines of dev_linalg.h -- the same operation order as
-// the dense kernels, hence the same bits (cross-checked at P <= 10 by tests with TJ_XS_BAND=1).  The PSD fallback of the
+// gathered straight from the per-piece blocks in HBM by the dense kernels' xs_entry / xs_grad_entry, wave 0 factors and solves
+// with the band routines of dev_linalg.h -- the same operation order as the dense factorisation, hence the same bits
+// (cross-checked at P <= 10 by tests with TJ_XS_BAND=1).  The PSD fallback of the
 // multi-UAV mode (LLT fails: shift by the smallest eigenvalue, Optimization3D_multi.h:703-719) needs the dense matrix; it is
 // formed in a per-robot HBM scratch (rare path).  Decoupled and single-UAV modes only.
 constexpr int XB_THREADS = 256;
 __host__ __device__ inline size_t xsolve_band_lds_doubles(int n) { return (size_t)(n - 1) * BAND_BS + 3 * (size_t)n + 64; }
-__device__ __forceinline__ double xb_entry(const double* gh, int P, int ga, int gb) {   // assembled Hessian entry; -1 = time
-  int lo = 0, hi = P - 1;
-  if (ga >= 0) { lo = max(lo, (ga - 17 + 8) / 9); hi = min(hi, ga / 9); }
-  if (gb >= 0) { lo = max(lo, (gb - 17 + 8) / 9); hi = min(hi, gb / 9); }
-  double acc = 0;
-  for (int sp = max(lo, 0); sp <= hi; sp++) acc += gh[(size_t)sp * 361 + (ga < 0 ? 18 : ga - 9 * sp) * 19 + (gb < 0 ? 18 : gb - 9 * sp)];
-  return acc;
-}
 __global__ __launch_bounds__(XB_THREADS) void k_xsolve_band(Dev D) {
   if (TJ_DONE(D)) return;
   extern __shared__ double sm[];
@@ -1010,15 +1011,11 @@ __global__ __launch_bounds__(XB_THREADS) void k_xsolve_band(Dev D) {
   auto assemble = [&]() {
     for (int idx = tid; idx < m * BS; idx += XB_THREADS) {
       const int i = idx / BS, c = idx % BS, j = i - (BS - 1) + c;
-      Bd[idx] = j >= 0 ? xb_entry(gh, D.P, i + 6, j + 6) : 0.0;
+      Bd[idx] = j >= 0 ? xs_entry(gh, D.P, i + 6, j + 6) : 0.0;
     }
     for (int j = tid; j < n; j += XB_THREADS) {
-      Ar[j] = xb_entry(gh, D.P, -1, j == m ? -1 : j + 6);
-      const int ga = j == m ? -1 : j + 6;
-      int lo = 0, hi = D.P - 1;
-      if (ga >= 0) { lo = max(lo, (ga - 17 + 8) / 9); hi = min(hi, ga / 9); }
-      double acc = 0;
-      for (int sp = max(lo, 0); sp <= hi; sp++) acc += gg[sp * 19 + (ga < 0 ? 18 : ga - 9 * sp)];
+      Ar[j] = xs_entry(gh, D.P, -1, xs_global(j, m));
+      const double acc = xs_grad_entry(gg, D.P, xs_global(j, m));
       g0[j] = acc; y[j] = acc;
     }
   };
@@ -1047,7 +1044,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_xsolve_band(Dev D) {
     if (D.mode == 1) {   // dense copy in HBM scratch -> smallest eigenvalue -> shift the diagonal (whole block cooperates)
       double* Hd = D.xs_scr + (size_t)blockIdx.x * ((size_t)n * n + 4 * n);
       double* sc = Hd + (size_t)n * n;
-      for (int idx = tid; idx < n * n; idx += XB_THREADS) { const int i = idx / n, j = idx % n; Hd[idx] = xb_entry(gh, D.P, i == m ? -1 : i + 6, j == m ? -1 : j + 6); }
+      for (int idx = tid; idx < n * n; idx += XB_THREADS) Hd[idx] = xs_entry(gh, D.P, xs_global(idx / n, m), xs_global(idx % n, m));
       __threadfence_block();
       __syncthreads();
       ev = min_eig_lds(Hd, n, sc, sc + n, sc + 2 * n, sc + 3 * n, tid, XB_THREADS);
@@ -1055,9 +1052,9 @@ __global__ __launch_bounds__(XB_THREADS) void k_xsolve_band(Dev D) {
     __syncthreads();
     assemble();
     __syncthreads();
-    if (ev < 0) {   // h0 - ev*I + 0.01*I, entry by entry and in the dense kernel's association, (h - ev) + 0.01: a shift summed first rounds differently
-      for (int i = tid; i < m; i += XB_THREADS) Bd[i * BS + BS - 1] = Bd[i * BS + BS - 1] - ev * 1.0 + 0.01 * 1.0;
-      if (tid == 0) Ar[m] = Ar[m] - ev * 1.0 + 0.01 * 1.0;
+    if (ev < 0) {   // the dense kernel's shift, entry by entry on the band's diagonal and the arrow's corner
+      for (int i = tid; i < m; i += XB_THREADS) Bd[i * BS + BS - 1] = psd_shift(Bd[i * BS + BS - 1], ev);
+      if (tid == 0) Ar[m] = psd_shift(Ar[m], ev);
     }
     __syncthreads();
     if (tid < 64) chol_band_lds(Bd, Ar, n, tid, y);   // like the reference, the second factorisation is not re-checked
@@ -1065,24 +1062,7 @@ __global__ __launch_bounds__(XB_THREADS) void k_xsolve_band(Dev D) {
   }
   if (tid >= 64) return;
   chol_band_backsolve_lds(Bd, Ar, n, y, tid);
-  double* scr = Bd;   // the factor is no longer needed: [n] x.g products, [n] g.g products
-  for (int i = tid; i < n; i += 64) y[i] = -y[i];
-  blk_sync<true>();
-  for (int i = tid; i < n; i += 64) { scr[i] = y[i] * g0[i]; scr[n + i] = g0[i] * g0[i]; }
-  blk_sync<true>();
-  double* dir = D.dirp(u);
-  for (int idx = tid; idx < 3 * T; idx += 64) {
-    const int row = idx % T, a = idx / T;
-    dir[idx] = (row >= 2 && row < T - 2) ? y[3 * (row - 2) + a] : 0.0;
-  }
-  if (tid == 0) { D.wolfe(u) = -esum(scr, n); const double gnv = sqrt(esum(scr + n, n)); D.gn(u) = gnv; D.tdir(u) = y[m]; if (!D.multi()) D.ctl->gnorm = gnv; }
-  if (D.xch) {   // direct exchange (sharded contexts), as in k_xsolve
-    double* rec = scr + 2 * n;
-    for (int idx = tid; idx < 3 * T; idx += 64) { const int row = idx % T, a = idx / T; rec[idx] = (row >= 2 && row < T - 2) ? y[3 * (row - 2) + a] : 0.0; }
-    if (tid == 0) { rec[3 * T] = y[m]; rec[3 * T + 1] = -esum(scr, n); rec[3 * T + 2] = sqrt(esum(scr + n, n)); }
-    blk_sync<true>();
-    xch_push_robot<true>(D, 1, u, D.xs, rec, 3 * T + 3, tid, 64);
-  }
+  xs_direction_record<true, false>(D, u, tid, n, y, g0, Bd, false);   // scratch: the factor is no longer needed.  As in k_xsolve, with esum and plain stores (no asynchronous form)
 }
 
 // Coupled mode, second half of the arrowhead solve: one wave per robot.  The Schur corner
@@ -1096,51 +1076,15 @@ __global__ __launch_bounds__(XS_THREADS) void k_xsolve_c2(Dev D) {
   const int tid = threadIdx.x, u = D.u0 + blockIdx.x;
   const int T = D.T, m = 3 * (T - 4), n = m + 1;
   double* L = sm; double* y = L + n * n; double* g0 = y + n; double* scr = g0 + n;  // scr [2n]
-  __shared__ double s_red[3];
+  __shared__ double s_red[3], s_cstage[256];
   const double* gL = D.xL + (size_t)u * n * n;
   for (int idx = tid; idx < n * n; idx += XS_THREADS) L[idx] = gL[idx];
   for (int i = tid; i < n; i += XS_THREADS) { y[i] = D.xy[(size_t)u * n + i]; g0[i] = D.xg[(size_t)u * n + i]; }
-  {  // lane 0: corner, lane 1: rhs, lane 2: G_t -- sequential sums in robot order; the terms of 64 robots come in with one
-     // coalesced pass and are added out of LDS (one lane walking global memory was 64 dependent round trips)
-    __shared__ double s_cstage[256];
-    double acc = 0;
-    for (int r0 = 0; r0 < D.U; r0 += 64) {
-      const int nr = min(64, D.U - r0);
-      blk_sync<true>();
-      for (int i = tid; i < 4 * nr; i += XS_THREADS) s_cstage[i] = D.xcorner[(size_t)r0 * 4 + i];
-      blk_sync<true>();
-      if (tid < 3) for (int r = 0; r < nr; r++) acc += s_cstage[4 * r + tid];
-    }
-    if (tid < 3) s_red[tid] = acc;
-  }
+  const XsCorner c = xs_corner<64, false>(D, tid, s_cstage, s_red);   // (one lane walking global memory was 64 dependent round trips)
+  if (tid == 0) { L[m * n + m] = c.lc; y[m] = c.rhs * c.lc; }
   blk_sync<true>();
-  const double corner = s_red[0], rhs = s_red[1];
-  if (!(corner > 0) && tid == 0 && blockIdx.x == 0) atomicOr(&D.ctl->error, ERR_NOT_SPD);
-  const double lc = pivot_rsqrt(corner);   // reciprocal root, like the rest of the FAST factor's diagonal
-  if (tid == 0) { L[m * n + m] = lc; y[m] = rhs * lc; }
-  blk_sync<true>();
-  if (n <= 64) {   // the unrolled register form of k_xsolve (same operations as the LDS form)
-    double yv = y[min(tid, n - 1)];
-    yv = xs_backsolve(L, n, yv, tid);
-    blk_sync<true>();
-    if (tid < n) y[tid] = yv;
-    blk_sync<true>();
-  } else chol_arrow_backsolve_lds<true, true>(L, n, XS_BAND, y, tid, XS_THREADS);
-  for (int i = tid; i < n; i += XS_THREADS) y[i] = -y[i];
-  blk_sync<true>();
-  for (int i = tid; i < m; i += XS_THREADS) { scr[i] = y[i] * g0[i]; scr[n + i] = g0[i] * g0[i]; }
-  blk_sync<true>();
-  double* dir = D.dirp(u);
-  for (int idx = tid; idx < 3 * T; idx += XS_THREADS) {
-    const int row = idx % T, a = idx / T;
-    dir[idx] = (row >= 2 && row < T - 2) ? y[3 * (row - 2) + a] : 0.0;
-  }
-  if (tid == 0) {
-    D.wolfe(u) = esum(scr, m);          // sum_j x_j g_j over this robot's control-point unknowns
-    D.gn(u) = esum(scr + n, m);         // sum_j g_j^2
-    D.tdir(u) = y[m];                   // shared t_direction (same bits on every robot)
-    D.xdir[(size_t)u * D.xs + 3 * T + 3] = g0[m];  // this robot's share of G_t
-  }
+  xs_backsolve_any<0>(L, n, y, tid);
+  xs_direction_record<false, false>(D, u, tid, n, y, g0, scr, false);
 }
 
 // k_xsolve_c2 for long trajectories (piece_num > 10): the same corner sum, corner pivot and back substitution on the band
@@ -1152,44 +1096,15 @@ __global__ __launch_bounds__(XS_THREADS) void k_xsolve_c2_band(Dev D) {
   const int T = D.T, m = 3 * (T - 4), n = m + 1, BS = BAND_BS;
   const size_t per = (size_t)m * BS + n;
   double* Bd = sm; double* Ar = Bd + (size_t)m * BS; double* y = Ar + n; double* g0 = y + n; double* scr = g0 + n;  // scr [2n]
-  __shared__ double s_red[3];
+  __shared__ double s_red[3], s_cstage[256];
   const double* gL = D.xL + (size_t)u * per;
   for (size_t idx = tid; idx < per; idx += XS_THREADS) Bd[idx] = gL[idx];
   for (int i = tid; i < n; i += XS_THREADS) { y[i] = D.xy[(size_t)u * n + i]; g0[i] = D.xg[(size_t)u * n + i]; }
-  {
-    __shared__ double s_cstage[256];
-    double acc = 0;
-    for (int r0 = 0; r0 < D.U; r0 += 64) {
-      const int nr = min(64, D.U - r0);
-      blk_sync<true>();
-      for (int i = tid; i < 4 * nr; i += XS_THREADS) s_cstage[i] = D.xcorner[(size_t)r0 * 4 + i];
-      blk_sync<true>();
-      if (tid < 3) for (int r = 0; r < nr; r++) acc += s_cstage[4 * r + tid];
-    }
-    if (tid < 3) s_red[tid] = acc;
-  }
-  blk_sync<true>();
-  const double corner = s_red[0], rhs = s_red[1];
-  if (!(corner > 0) && tid == 0 && blockIdx.x == 0) atomicOr(&D.ctl->error, ERR_NOT_SPD);
-  const double lc = pivot_rsqrt(corner);
-  if (tid == 0) { Ar[m] = lc; y[m] = rhs * lc; }
+  const XsCorner c = xs_corner<64, false>(D, tid, s_cstage, s_red);
+  if (tid == 0) { Ar[m] = c.lc; y[m] = c.rhs * c.lc; }
   blk_sync<true>();
   chol_band_backsolve_lds(Bd, Ar, n, y, tid);
-  for (int i = tid; i < n; i += XS_THREADS) y[i] = -y[i];
-  blk_sync<true>();
-  for (int i = tid; i < m; i += XS_THREADS) { scr[i] = y[i] * g0[i]; scr[n + i] = g0[i] * g0[i]; }
-  blk_sync<true>();
-  double* dir = D.dirp(u);
-  for (int idx = tid; idx < 3 * T; idx += XS_THREADS) {
-    const int row = idx % T, a = idx / T;
-    dir[idx] = (row >= 2 && row < T - 2) ? y[3 * (row - 2) + a] : 0.0;
-  }
-  if (tid == 0) {
-    D.wolfe(u) = esum(scr, m);
-    D.gn(u) = esum(scr + n, m);
-    D.tdir(u) = y[m];
-    D.xdir[(size_t)u * D.xs + 3 * T + 3] = g0[m];
-  }
+  xs_direction_record<false, false>(D, u, tid, n, y, g0, scr, false);
 }
 
 }  // namespace tj

@@ -38,23 +38,14 @@ __device__ __forceinline__ void ccd_prep_segment(const Dev& D, const double* net
   double* P = sh; double* Dh = sh + 18; double* PD = sh + 36; double* PS = sh + 54;
   auto ldd = [&](const double* p) { return (XF && sysdir == 1) ? xch_load(p) : ((XF && sysdir == 2) ? xf_load(p) : *p); };
   auto st = [&](double* p, double v) { if constexpr (XF) xf_store(p, v); else *p = v; };
-  if (lane < 18) P[lane] = hull_entry(D, net, tr, lane / 3, lane % 3);
-  else if (lane < 36) {
-    const int j = (lane - 18) / 3, a = (lane - 18) % 3;
-    const double* B = D.basis + (size_t)tr * 36 + j * 6;
-    const double* col = dir + div_small(tr, D.res) * 3 + D.T * a;
-    double acc = 0;
+  const int e = lane % 18, r0 = div_small(tr, D.res) * 3 + D.T * (e % 3);
+  const double* B = D.basis + (size_t)tr * 36 + (e / 3) * 6;
+  if (lane < 18) P[lane] = hull_sum(B, net + r0);
+  else if (lane < 54) {
+    double dk[6];
 #pragma unroll
-    for (int k = 0; k < 6; k++) acc += B[k] * ldd(col + k);   // = hull_entry(D, dir, ...)
-    Dh[lane - 18] = acc;
-  }
-  else if (lane < 54) {  // basis * (bz + bz_d), the box the reference uses for the cloud query
-    const int j = (lane - 36) / 3, a = (lane - 36) % 3;
-    const double* B = D.basis + (size_t)tr * 36 + j * 6;
-    const int r0 = div_small(tr, D.res) * 3 + D.T * a;
-    double acc = 0;
-    for (int k = 0; k < 6; k++) acc += B[k] * (net[r0 + k] + ldd(dir + r0 + k));
-    PD[lane - 36] = acc;
+    for (int k = 0; k < 6; k++) dk[k] = ldd(dir + r0 + k);
+    if (lane < 36) Dh[e] = hull_sum(B, dk); else PD[e] = hull_sum_pd(B, net + r0, dk);
   }
   blk_sync<true>();
   if (lane < 18) PS[lane] = P[lane] + Dh[lane];  // (P + D) used by the pair box and by the k-DOP at step 1
@@ -62,20 +53,15 @@ __device__ __forceinline__ void ccd_prep_segment(const Dev& D, const double* net
   double* o = D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE;
   if (lane < 18) { st(o + lane, P[lane]); st(o + 18 + lane, Dh[lane]); }
   if (lane < 3) {
-    double lo = INFINITY, hi = -INFINITY, lo2 = INFINITY, hi2 = -INFINITY;
-    for (int j = 0; j < 6; j++) {
-      double v = P[3 * j + lane]; if (v < lo) lo = v; if (v > hi) hi = v; if (v < lo2) lo2 = v; if (v > hi2) hi2 = v;
-      v = PD[3 * j + lane]; if (v < lo) lo = v; if (v > hi) hi = v;
-      v = PS[3 * j + lane]; if (v < lo2) lo2 = v; if (v > hi2) hi2 = v;
-    }
-    st(o + 36 + lane, lo); st(o + 39 + lane, hi); st(o + 42 + lane, lo2); st(o + 45 + lane, hi2);
-    st(D.cbox + ((size_t)tr * 6 + lane) * D.U + u, lo2); st(D.cbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, hi2);
+    const SweptBoxes b = swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; });
+    st(o + 36 + lane, b.lo); st(o + 39 + lane, b.hi); st(o + 42 + lane, b.lo2); st(o + 45 + lane, b.hi2);
+    st(D.cbox + ((size_t)tr * 6 + lane) * D.U + u, b.lo2); st(D.cbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, b.hi2);
   }
   if (lane < 49) {
     const double x = D.kdop[3 * lane], y = D.kdop[3 * lane + 1], z = D.kdop[3 * lane + 2];
     double up = -INFINITY, lo = INFINITY;
-    for (int i = 0; i < 6; i++) { const double lv = x * P[3 * i] + y * P[3 * i + 1] + z * P[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-    for (int i = 0; i < 6; i++) { const double lv = x * PS[3 * i] + y * PS[3 * i + 1] + z * PS[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
+    kdop_interval6(x, y, z, P, lo, up);
+    kdop_interval6(x, y, z, PS, lo, up);
     st(o + 48 + lane, lo); st(o + 97 + lane, up);
   }
   blk_sync<true>();  // sh is reused by the caller's next segment
@@ -102,39 +88,21 @@ __device__ __forceinline__ void ccd_record_async(const Dev& D, int u, int tr, in
 #pragma unroll
     for (int k = 0; k < 6; k++) dk[k] = xf_load(dir + r0 + k);
   }
-  {
-    double acc = 0;
-    if (lane < 18) {
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc += bk[k] * nk[k];
-      P[lane] = acc;
-    } else if (lane < 36) {
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc += bk[k] * dk[k];
-      Dh[lane - 18] = acc;
-    } else if (lane < 54) {
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc += bk[k] * (nk[k] + dk[k]);
-      PD[lane - 36] = acc;
-    }
-  }
+  if (lane < 18) P[lane] = hull_sum(bk, nk);
+  else if (lane < 36) Dh[lane - 18] = hull_sum(bk, dk);
+  else if (lane < 54) PD[lane - 36] = hull_sum_pd(bk, nk, dk);
   blk_sync<true>();
   if (lane < 18) { PS[lane] = P[lane] + Dh[lane]; info[lane] = P[lane]; info[18 + lane] = Dh[lane]; }
   blk_sync<true>();
   if (lane < 3) {
-    double lo = INFINITY, hi = -INFINITY, lo2 = INFINITY, hi2 = -INFINITY;
-    for (int j = 0; j < 6; j++) {
-      double v = P[3 * j + lane]; if (v < lo) lo = v; if (v > hi) hi = v; if (v < lo2) lo2 = v; if (v > hi2) hi2 = v;
-      v = PD[3 * j + lane]; if (v < lo) lo = v; if (v > hi) hi = v;
-      v = PS[3 * j + lane]; if (v < lo2) lo2 = v; if (v > hi2) hi2 = v;
-    }
-    info[36 + lane] = lo; info[39 + lane] = hi; info[42 + lane] = lo2; info[45 + lane] = hi2;
-    xf_store(D.cbox + ((size_t)tr * 6 + lane) * D.U + u, lo2); xf_store(D.cbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, hi2);
+    const SweptBoxes b = swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; });
+    info[36 + lane] = b.lo; info[39 + lane] = b.hi; info[42 + lane] = b.lo2; info[45 + lane] = b.hi2;
+    xf_store(D.cbox + ((size_t)tr * 6 + lane) * D.U + u, b.lo2); xf_store(D.cbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, b.hi2);
   }
   if (lane < 49) {
     double up = -INFINITY, lo = INFINITY;
-    for (int i = 0; i < 6; i++) { const double lv = kx * P[3 * i] + ky * P[3 * i + 1] + kz * P[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-    for (int i = 0; i < 6; i++) { const double lv = kx * PS[3 * i] + ky * PS[3 * i + 1] + kz * PS[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
+    kdop_interval6(kx, ky, kz, P, lo, up);
+    kdop_interval6(kx, ky, kz, PS, lo, up);
     info[48 + lane] = lo; info[97 + lane] = up;
   }
   blk_sync<true>();
@@ -697,7 +665,7 @@ __device__ __forceinline__ void slack_body(const Dev& D, int bid, int deferred, 
     for (int idx = tid; idx < n * n; idx += 64) H[idx] = L[idx];  // H now holds the reduced system (n x n)
     __syncthreads();
     const double ev = min_eig_lds(L, n, scr, scr + 19, scr + 38, scr + 57, tid, 64);
-    if (ev < 0 && tid < n) H[tid * n + tid] = H[tid * n + tid] - ev * 1.0 + 0.01 * 1.0;
+    if (ev < 0 && tid < n) H[tid * n + tid] = psd_shift(H[tid * n + tid], ev);
     __syncthreads();
     for (int idx = tid; idx < n * n; idx += 64) L[idx] = H[idx];
     if (tid < n) x0[tid] = g0[tid];

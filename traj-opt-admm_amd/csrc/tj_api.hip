@@ -625,26 +625,19 @@ int set_lds_attributes(tj_ctx* c) {
 const char* build_xs_gather(int Pn, std::vector<int>& gt) {
   const int m = 9 * Pn - 3, n = m + 1;
   gt.assign((size_t)2 * n * n + 2 * n, -1);
-  auto cover = [&](int g, int& lo, int& hi) { if (g >= 0) { lo = std::max(lo, (g - 17 + 8) / 9); hi = std::min(hi, g / 9); } };
-  for (int idx = 0; idx < n * n; idx++) {
-    const int ra = idx / n, rb = idx % n, ga = ra == m ? -1 : ra + 6, gb = rb == m ? -1 : rb + 6;
+  for (int idx = 0; idx < n * n; idx++) {   // the sources xs_entry would sum
+    const int ga = xs_global(idx / n, m), gb = xs_global(idx % n, m);
     if (ga < 0 && gb < 0) { gt[2 * (size_t)idx] = -2; continue; }
-    int lo = 0, hi = Pn - 1, k = 0;
-    cover(ga, lo, hi); cover(gb, lo, hi);
-    for (int sp = std::max(lo, 0); sp <= hi; sp++) {
-      const int a = ga < 0 ? 18 : ga - 9 * sp, b = gb < 0 ? 18 : gb - 9 * sp;
-      if (k < 2) gt[2 * (size_t)idx + k] = sp * 361 + a * 19 + b;
-      k++;
-    }
-    if (k > 2) return "internal: an entry of the reduced system is covered by more than two piece blocks";
+    const XsCover c = xs_cover(ga, gb, Pn);
+    if (c.hi - c.lo > 1) return "internal: an entry of the reduced system is covered by more than two piece blocks";
+    for (int sp = c.lo; sp <= c.hi; sp++) gt[2 * (size_t)idx + (sp - c.lo)] = sp * 361 + xs_local(ga, sp) * 19 + xs_local(gb, sp);
   }
-  for (int ra = 0; ra < n; ra++) {
-    const int ga = ra == m ? -1 : ra + 6;
+  for (int ra = 0; ra < n; ra++) {   // ... and xs_grad_entry
+    const int ga = xs_global(ra, m);
     if (ga < 0) { gt[(size_t)2 * n * n + 2 * ra] = -2; continue; }
-    int lo = 0, hi = Pn - 1, k = 0;
-    cover(ga, lo, hi);
-    for (int sp = std::max(lo, 0); sp <= hi; sp++) { if (k < 2) gt[(size_t)2 * n * n + 2 * ra + k] = sp * 19 + (ga - 9 * sp); k++; }
-    if (k > 2) return "internal: a row of the reduced system is covered by more than two piece blocks";
+    const XsCover c = xs_cover(ga, Pn);
+    if (c.hi - c.lo > 1) return "internal: a row of the reduced system is covered by more than two piece blocks";
+    for (int sp = c.lo; sp <= c.hi; sp++) gt[(size_t)2 * n * n + 2 * ra + (sp - c.lo)] = sp * 19 + xs_local(ga, sp);
   }
   return nullptr;
 }

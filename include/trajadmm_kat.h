@@ -51,6 +51,10 @@ int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out);
  * tj_run_stage(TJ_STAGE_XSOLVE) and tj_get_direction this feeds the product's own solve kernels any system.  Pending work of the context is waited for, no
  * kernel is launched.  TJ_ERR_INVALID: a null argument, or a context without cloud / state. */
 int tj_kat_set_local_grad(tj_ctx* c, const double* lg, const double* lh);
+/* the hull cache of the robot-pair stage as its last writer left it (k_hullinfo, k_front's units or k_linesearch -- which one depends on the schedule):
+ * hullinfo[U][S][122] = hull 18, box lo/hi 6, the 49 k-DOP intervals lo, hi of every (robot, segment) record; hbox[S][6][U] = the boxes again as the
+ * pair tiles read them.  Pending work of the context is waited for, no kernel is launched.  TJ_ERR_INVALID: a null argument, or a context without cloud / state. */
+int tj_kat_get_hull_record(tj_ctx* c, double* hullinfo, double* hbox);
 
 /* ---- the launch plan (csrc/host_plan.h) ------------------------------------------------------------
  * A flat record of ints: the device facts the plan was decided on (PlanFacts), then every decision of the plan, the LDS byte counts, the queue

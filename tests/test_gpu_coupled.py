@@ -277,3 +277,53 @@ def test_coupled_chain_with_cache_units_changes_no_bit(pkg, scenes, monkeypatch)
         assert np.array_equal(sa[n], sc[n]), n
     assert lc - lb == 2 * 12
     a.close(); b.close(); c.close()
+
+
+@pytest.mark.parametrize("mode", [1, 2], ids=["decoupled", "coupled"])
+def test_hull_record_writers_agree_bitwise(pkg, scenes, monkeypatch, mode):
+    """The hull cache of the robot-pair stage (per (robot, segment): hull, box, 49 k-DOP intervals; and the box table) has several writers that must leave the
+    same bits (dev_common.h: hull_record_store and its pieces).  Which one wrote the record a batch leaves behind depends on the schedule:
+      decoupled   the LAST line search of a batch (ls_publish_hullinfo) -- with the asynchronous front and without it (TJ_FRONT_ASYNC=0); the records that
+                  k_front's units leave in the earlier iterations of a batch are overwritten by it and are pinned through the state hashes only;
+      coupled     the line search publishes nothing, so after one more iteration the record of the state after 3 iterations is the one the 4th iteration's
+                  front left: the publishing obstacle units (obs_query_body) in their asynchronous and plain forms, or, with TJ_COUPLED_UNITS=0, k_hullinfo
+                  launched inside the chain.
+    Each is compared with what k_hullinfo writes for the same state through the stage API (set_state, then the stage planes_self, whose first launch it is)."""
+    scene = dict(scenes.crossing(12, 4000, seed=23, name="crossing-U12-hullrec"), mode=mode)
+    for k in ("TJ_FRONT_ASYNC", "TJ_COUPLED_UNITS"):
+        monkeypatch.delenv(k, raising=False)
+
+    def chain(env, plan_want):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        s = pkg.Solver(scene, stop=0.0, kat=True)
+        for k in env:
+            monkeypatch.delenv(k)
+        plan = pkg.plan_record(ctx=s._ctx)[1]
+        for k, v in plan_want.items():
+            assert plan[k] == v, (env, k, plan[k])
+        s.iterate(3)
+        st = s.get_state()
+        if mode == 2:
+            s.iterate(1)
+        rec = s.kat_hull_record()
+        assert s.stats()["error_bits"] == 0
+        return s, st, rec
+
+    runs = [chain({}, {"xf_all": 1} if mode == 2 else {"fuse": 1}), chain({"TJ_FRONT_ASYNC": "0"}, {"fa": 0})]
+    if mode == 2:
+        runs.append(chain({"TJ_COUPLED_UNITS": "0"}, {"xf_all": 0}))
+    s0, st0, _ = runs[0]
+    for _, st, _ in runs[1:]:
+        for n in STATE:
+            assert np.array_equal(st0[n], st[n]), n
+    s0.set_state(st0)
+    s0.run_stage("begin")
+    s0.run_stage("planes_self")
+    info_k, hbox_k = s0.kat_hull_record()
+    assert np.all(np.isfinite(info_k)) and np.any(info_k[:, :, :18] != 0.0)
+    for i, (_, _, (info, hbox)) in enumerate(runs):
+        assert np.array_equal(info, info_k), (i, int(np.sum(info != info_k)))
+        assert np.array_equal(hbox, hbox_k), (i, int(np.sum(hbox != hbox_k)))
+    for s, _, _ in runs:
+        s.close()

@@ -292,7 +292,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad", "tj_kat_get_hull_record"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -625,6 +625,12 @@ class Solver:
         n = a.shape[0]; out = np.zeros((n, 4))
         self._check(self.lib.tj_kat_gjk_wave_split(self._ctx, C.c_int(n), C.c_int(a.shape[1]), _d(a), C.c_int(b.shape[1]), _d(b), C.c_int(k_stop), _d(out)))
         return out[:, :3], out[:, 3].astype(int)
+
+    def kat_hull_record(self):
+        """the hull cache as its last writer left it: (hullinfo [U][S][122], hbox [S][6][U])"""
+        info = np.zeros((self.U, self.S, 122)); hbox = np.zeros((self.S, 6, self.U))
+        self._check(self.lib.tj_kat_get_hull_record(self._ctx, _d(info), _d(hbox)))
+        return info, hbox
 
     def kat_planes(self, what, P, Q, dist):
         P = np.ascontiguousarray(P, dtype=np.float64); Q = np.ascontiguousarray(Q, dtype=np.float64)

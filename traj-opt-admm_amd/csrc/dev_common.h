@@ -275,7 +275,7 @@ struct Dev {
   double *ohull;                  // [U][S][18]
   int *obs_work, *obs_work_n;     // [U*S*cap_obs][2], [1]
   double *oraw; int *ostamp;      // [U][S][cap_obs][4], [U][S][cap_obs]
-  double *hullinfo;               // [U][S][HULL_STRIDE] hull, AABB, k-DOP intervals of the current control net
+  double *hullinfo;               // [U][S][HULL_INFO_STRIDE] hull, AABB, k-DOP intervals of the current control net
   // the same AABBs / the swept pair boxes again, robot-minor [S][6][U] (lo.xyz, hi.xyz): the all-pairs box tests read
   // one component of 64 partners with one coalesced load instead of 64 strided 8-byte loads
   double *hbox, *cbox;
@@ -401,15 +401,20 @@ __device__ __forceinline__ int prefix_count(unsigned long long m) { return __pop
 __device__ __forceinline__ int div_small(int a, int b) { return (int)(((float)a + 0.5f) * (1.0f / (float)b)); }
 // hull of segment tr of a T x 3 column-major control net: out[j*3+a] = sum_k basis[j][k] * net[3*piece+k][a]
 // accumulated in k order from zero, as every variant in the reference does (e.g. Energy_admm.h:116-129); hull_sum: one such sum, B the basis row, col the piece's 6 coordinates
-__device__ __forceinline__ double hull_sum(const double* B, const double* col) {
+// ld: how a net entry is fetched -- plainly, or past the caches (xf_load, xch_load) where the net was written while the launch was running.  A caller that must
+// wait for the net first fetches the basis row into registers before the wait and hands that copy in as B.
+template <class Ld>
+__device__ __forceinline__ double hull_sum(const double* B, const double* col, Ld&& ld) {
   double acc = 0;
 #pragma unroll
-  for (int k = 0; k < 6; k++) acc += B[k] * col[k];
+  for (int k = 0; k < 6; k++) acc += B[k] * ld(col + k);
   return acc;
 }
-__device__ __forceinline__ double hull_entry(const Dev& D, const double* net, int tr, int j, int a) {
-  return hull_sum(D.basis + (size_t)tr * 36 + j * 6, net + div_small(tr, D.res) * 3 + D.T * a);
-}
+__device__ __forceinline__ double hull_sum(const double* B, const double* col) { return hull_sum(B, col, [](const double* p) { return *p; }); }
+// the operands of hull entry (j, a) of segment tr: its basis row and the 6 coordinates a of the segment's piece
+__device__ __forceinline__ const double* hull_row(const Dev& D, int tr, int j) { return D.basis + (size_t)tr * 36 + j * 6; }
+__device__ __forceinline__ const double* hull_col(const Dev& D, const double* net, int tr, int a) { return net + div_small(tr, D.res) * 3 + D.T * a; }
+__device__ __forceinline__ double hull_entry(const Dev& D, const double* net, int tr, int j, int a) { return hull_sum(hull_row(D, tr, j), hull_col(D, net, tr, a)); }
 // ---- the swept-hull record of a (robot, segment), its arithmetic written ONCE for its three writers (k_xsolve's tail, ccd_prep_segment, ccd_record_async: each keeps
 // its own thread mapping, loads and stores) -- so every rank and every launch form holds the same bits.  BVH::CCDCollision box (BVH.cpp:195-250), SelfCCDCollision
 // box (:289-330), k-DOP intervals of {P, P + D} (CCD.h:416-533).
@@ -528,6 +533,42 @@ __device__ __forceinline__ void fa_count(int* w) {
 }
 // a value that a kernel running at the same time on the other queue will read: written through when the solve is asynchronous
 __device__ __forceinline__ void xs_out(bool wt, double* p, double v) { if (wt) xf_store(p, v); else *p = v; }
+
+// ---- the hull record of a (robot, segment) (Dev::hullinfo, Dev::hbox), stated ONCE for its four writers: k_hullinfo, the foreign units (xf_hull_body), the
+// publishing obstacle query (obs_query_body) and k_linesearch (ls_publish_hullinfo, which keeps its own thread mapping) -- tests/test_gpu_coupled.py compares what
+// they leave bit for bit.  Record: hull P[6][3] at 0, box lo[3] at 18, hi[3] at 21, the 49 k-DOP intervals lo at 24, hi at 73 = 122 values in 128 doubles (eight
+// 128-byte lines of its own, see CCD_STRIDE); hbox holds the boxes again as [segment][lo.xyz hi.xyz][robot] for the pair tiles.
+constexpr int HULL_INFO_STRIDE = 128, HULL_BOX = 18, HULL_KLO = 24, HULL_KHI = 73;
+__device__ __forceinline__ double* hull_record(const Dev& D, int u, int tr) { return D.hullinfo + ((size_t)u * D.S + tr) * HULL_INFO_STRIDE; }
+__device__ __forceinline__ void hull_box_axis(const double* P, int a, double& lo, double& hi) {   // coordinate a of the hull's box
+  lo = INFINITY; hi = -INFINITY;
+  for (int j = 0; j < 6; j++) { const double v = P[3 * j + a]; if (v < lo) lo = v; if (v > hi) hi = v; }
+}
+__device__ __forceinline__ void hull_kdop_axis(const Dev& D, const double* P, int ax, double& lo, double& up) {   // the hull's interval on k-DOP axis ax
+  lo = INFINITY; up = -INFINITY;
+  kdop_interval6(D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2], P, lo, up);
+}
+// this lane's share of the record, one wave: hull entry p (lanes 0..17), coordinate `lane` of the box (0..2), interval on axis `lane` (0..48); other lanes' arguments are ignored.
+// WT: written through (the record is read by a kernel, or by later blocks of this one, while the launch runs)
+template <bool WT>
+__device__ __forceinline__ void hull_record_put(const Dev& D, int u, int tr, int lane, double p, double blo, double bhi, double klo, double khi) {
+  auto put = [](double* d, double v) { if constexpr (WT) xf_store(d, v); else *d = v; };
+  double* o = hull_record(D, u, tr);
+  if (lane < 18) put(o + lane, p);
+  if (lane < 3) {
+    put(o + HULL_BOX + lane, blo); put(o + HULL_BOX + 3 + lane, bhi);
+    put(D.hbox + ((size_t)tr * 6 + lane) * D.U + u, blo); put(D.hbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, bhi);
+  }
+  if (lane < 49) { put(o + HULL_KLO + lane, klo); put(o + HULL_KHI + lane, khi); }
+}
+// the record of the hull P (LDS, complete), computed and stored by one wave
+template <bool WT>
+__device__ __forceinline__ void hull_record_store(const Dev& D, int u, int tr, int lane, const double* P) {
+  double blo = 0, bhi = 0, klo = 0, khi = 0;
+  if (lane < 3) hull_box_axis(P, lane, blo, bhi);
+  if (lane < 49) hull_kdop_axis(D, P, lane, klo, khi);
+  hull_record_put<WT>(D, u, tr, lane, P[min(lane, 17)], blo, bhi, klo, khi);
+}
 
 __device__ __forceinline__ double seg_weight(const Dev& D, int tr) {
   int k = tr - D.res * div_small(tr, D.res);

@@ -81,28 +81,13 @@ __global__ __launch_bounds__(64) void k_keep(Dev D, int part) {
   auto publish = [&](size_t s0, int tr, int p0, int q, double cx, double cy, double cz, double d) {
     double* k = D.kpair_cd + 4 * s0;
     k[0] = cx; k[1] = cy; k[2] = cz; k[3] = d;
-    const size_t s1 = ((size_t)tr * U + q) * U + p0;
-    double* q0 = D.pairplane + 4 * s0; double* q1 = D.pairplane + 4 * s1;
-    if (wt) {   // read by k_grad's compaction on another queue, possibly before this launch has ended: written through (same values as below)
-      const bool fin = isfinite(cx) && isfinite(cy) && isfinite(cz) && isfinite(d);
-      xf_store(q0, fin ? cx : 0.0); xf_store(q0 + 1, fin ? cy : 0.0); xf_store(q0 + 2, fin ? cz : 0.0); xf_store(q0 + 3, fin ? d - 0.5 * off : 1e300);
-      xf_store(q1, fin ? -cx : 0.0); xf_store(q1 + 1, fin ? -cy : 0.0); xf_store(q1 + 2, fin ? -cz : 0.0); xf_store(q1 + 3, fin ? -d - 0.5 * off : 1e300);
-      __hip_atomic_store(&D.pairstamp[s0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(&D.pairstamp[s1], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      D.pair_mark(tr, p0, q); D.pair_mark(tr, q, p0);
-      return;
-    }
-    if (!(isfinite(cx) && isfinite(cy) && isfinite(cz) && isfinite(d))) {
-      // The reference's refinement can return NaN (its gradient takes log(dist/m) of a point on the wrong side).  Every consumer
-      // of the reference tests `dist < margin` / `dist <= 0` first, which a NaN fails: such a plane is inert but stays in the
-      // lists.  The kernels here multiply inactive terms by an exact 0 instead of branching, so the plane is published in an
-      // inert finite form (c = 0, d = huge); the table keeps the NaN, from which the next refinement returns at once.
-      q0[0] = 0; q0[1] = 0; q0[2] = 0; q0[3] = 1e300;
-      q1[0] = 0; q1[1] = 0; q1[2] = 0; q1[3] = 1e300;
-    } else {
-    q0[0] = cx; q0[1] = cy; q0[2] = cz; q0[3] = d - 0.5 * off;
-    q1[0] = -cx; q1[1] = -cy; q1[2] = -cz; q1[3] = -d - 0.5 * off;
-    }
-    D.pairstamp[s0] = epoch; D.pairstamp[s1] = epoch; D.pair_mark(tr, p0, q); D.pair_mark(tr, q, p0);
+    // The reference's refinement can return NaN (its gradient takes log(dist/m) of a point on the wrong side).  Every consumer
+    // of the reference tests `dist < margin` / `dist <= 0` first, which a NaN fails: such a plane is inert but stays in the
+    // lists.  The kernels here multiply inactive terms by an exact 0 instead of branching, so the plane is published in an
+    // inert finite form (c = 0, d = huge); the table keeps the NaN, from which the next refinement returns at once.
+    const bool fin = isfinite(cx) && isfinite(cy) && isfinite(cz) && isfinite(d);
+    if (wt) pair_plane_store<true>(D, PairId{tr, p0, q}, cx, cy, cz, d, epoch, fin);   // read by k_grad's compaction on another queue, possibly before this launch has ended: written through (same values)
+    else pair_plane_store<false>(D, PairId{tr, p0, q}, cx, cy, cz, d, epoch, fin);
   };
   // statistics of this mode (tj_stats): newton_iters / pair_solves = Newton rounds / planes refined (Optimal_plane::self_optimal_cd's outer loop),
   // gjk_max_sum = sum over the iterations of the longest refinement of a launch, in rounds -- the unit count of k_keep's critical path
@@ -130,8 +115,8 @@ __global__ __launch_bounds__(64) void k_keep(Dev D, int part) {
       const int tr = D.pair_work[3 * sl], p0 = D.pair_work[3 * sl + 1], q = D.pair_work[3 * sl + 2];
       const size_t s0 = ((size_t)tr * U + p0) * U + q;
       if (D.kpair_on[s0]) continue;
-      const double* A = D.hullinfo + ((size_t)p0 * D.S + tr) * HULL_STRIDE;
-      const double* B = D.hullinfo + ((size_t)q * D.S + tr) * HULL_STRIDE;
+      const double* A = hull_record(D, p0, tr);
+      const double* B = hull_record(D, q, tr);
       double cx, cy, cz, d; bool cp;
       if (!plane_pair(A, B, dist, m, off, false, cx, cy, cz, d, cp)) continue;   // every lane, same arguments: uniform
       if (lane == 0) { D.kpair_on[s0] = 1; D.kpair_list[atomicAdd(D.kpair_n, 1)] = (int)s0; }
@@ -143,8 +128,8 @@ __global__ __launch_bounds__(64) void k_keep(Dev D, int part) {
     for (int w = blockIdx.x; w < nold; w += gridDim.x) {     // part 2 (:310-338)
       const size_t s0 = (size_t)D.kpair_list[w];
       const int tr = (int)(s0 / ((size_t)U * U)), p0 = (int)((s0 / U) % U), q = (int)(s0 % U);
-      const double* A = D.hullinfo + ((size_t)p0 * D.S + tr) * HULL_STRIDE;
-      const double* B = D.hullinfo + ((size_t)q * D.S + tr) * HULL_STRIDE;
+      const double* A = hull_record(D, p0, tr);
+      const double* B = hull_record(D, q, tr);
       const double* k = D.kpair_cd + 4 * s0;
       double cx = k[0], cy = k[1], cz = k[2], d = k[3];
       int rounds = 0;
@@ -162,8 +147,8 @@ __global__ __launch_bounds__(64) void k_keep(Dev D, int part) {
     const int tr = D.pair_work[3 * sl], p0 = D.pair_work[3 * sl + 1], q = D.pair_work[3 * sl + 2];
     const size_t s0 = ((size_t)tr * U + p0) * U + q;
     if (D.kpair_on[s0]) continue;
-    const double* A = D.hullinfo + ((size_t)p0 * D.S + tr) * HULL_STRIDE;
-    const double* B = D.hullinfo + ((size_t)q * D.S + tr) * HULL_STRIDE;
+    const double* A = hull_record(D, p0, tr);
+    const double* B = hull_record(D, q, tr);
     double cx, cy, cz, d; bool cp;
     if (!plane_pair(A, B, dist, m, off, false, cx, cy, cz, d, cp)) continue;
     D.kpair_on[s0] = 1;
@@ -176,8 +161,8 @@ __global__ __launch_bounds__(64) void k_keep(Dev D, int part) {
   for (int w = blockIdx.x * 64 + lane; w < nold; w += gridDim.x * 64) {
     const size_t s0 = (size_t)D.kpair_list[w];
     const int tr = (int)(s0 / ((size_t)U * U)), p0 = (int)((s0 / U) % U), q = (int)(s0 % U);
-    const double* A = D.hullinfo + ((size_t)p0 * D.S + tr) * HULL_STRIDE;
-    const double* B = D.hullinfo + ((size_t)q * D.S + tr) * HULL_STRIDE;
+    const double* A = hull_record(D, p0, tr);
+    const double* B = hull_record(D, q, tr);
     const double* k = D.kpair_cd + 4 * s0;
     double cx = k[0], cy = k[1], cz = k[2], d = k[3];
     capped |= !opt_plane_pair(A, B, m, off, cx, cy, cz, d);

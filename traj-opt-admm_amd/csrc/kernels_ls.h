@@ -390,27 +390,24 @@ __device__ __forceinline__ LsRobot ls_stage(const Dev& D, const LsLayout& L, dou
 // Hull cache of the NEXT iteration's robot-pair stage (layout of k_hullinfo, kernels_pairs.h: hull 18, AABB 6,
 // 49 k-DOP intervals lo/hi), written from the hulls the accepted Armijo candidate was evaluated on -- they ARE the
 // hulls of the control net just committed, so the separate k_hullinfo launch (and its place on the critical path)
-// disappears from the single-GPU iteration graph.  Same expressions as k_hullinfo => identical bits.
-constexpr int LS_HULL_STRIDE = 128;   // = HULL_INFO_STRIDE (kernels_sep.h)
+// disappears from the single-GPU iteration graph.  The record's arithmetic and layout are dev_common.h's (hull_box_axis, hull_kdop_axis: k_hullinfo's bits);
+// the thread mapping is this kernel's own -- a block per robot, its threads over all segments.
 __device__ __forceinline__ void ls_publish_hullinfo(const Dev& D, int u, const double* hulls, int tid, int nth) {
   const int S = D.S;
-  double* o = D.hullinfo + (size_t)u * S * LS_HULL_STRIDE;
-  for (int idx = tid; idx < S * 18; idx += nth) o[(size_t)(idx / 18) * LS_HULL_STRIDE + idx % 18] = hulls[idx];
+  double* o = hull_record(D, u, 0);
+  for (int idx = tid; idx < S * 18; idx += nth) o[(size_t)(idx / 18) * HULL_INFO_STRIDE + idx % 18] = hulls[idx];
   for (int idx = tid; idx < S * 3; idx += nth) {
     const int tr = idx / 3, a = idx % 3;
-    const double* P = hulls + tr * 18;
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + a]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    o[(size_t)tr * LS_HULL_STRIDE + 18 + a] = lo; o[(size_t)tr * LS_HULL_STRIDE + 21 + a] = hi;
+    double lo, hi;
+    hull_box_axis(hulls + tr * 18, a, lo, hi);
+    o[(size_t)tr * HULL_INFO_STRIDE + HULL_BOX + a] = lo; o[(size_t)tr * HULL_INFO_STRIDE + HULL_BOX + 3 + a] = hi;
     D.hbox[((size_t)tr * 6 + a) * D.U + u] = lo; D.hbox[((size_t)tr * 6 + 3 + a) * D.U + u] = hi;
   }
   for (int idx = tid; idx < S * 49; idx += nth) {
     const int tr = idx / 49, ax = idx % 49;
-    const double* P = hulls + tr * 18;
-    const double x = D.kdop[3 * ax], y = D.kdop[3 * ax + 1], z = D.kdop[3 * ax + 2];
-    double up = -INFINITY, lo = INFINITY;
-    for (int i = 0; i < 6; i++) { const double lv = x * P[3 * i] + y * P[3 * i + 1] + z * P[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-    o[(size_t)tr * LS_HULL_STRIDE + 24 + ax] = lo; o[(size_t)tr * LS_HULL_STRIDE + 73 + ax] = up;
+    double lo, up;
+    hull_kdop_axis(D, hulls + tr * 18, ax, lo, up);
+    o[(size_t)tr * HULL_INFO_STRIDE + HULL_KLO + ax] = lo; o[(size_t)tr * HULL_INFO_STRIDE + HULL_KHI + ax] = up;
   }
 }
 

@@ -23,7 +23,6 @@
 namespace tj {
 
 struct QBox { double lo[3], hi[3]; };
-constexpr int HULL_INFO_STRIDE = 128;   // record of Dev::hullinfo (kernels_pairs.h HULL_STRIDE): hull 18, box lo/hi 6, 49 intervals lo/hi 98 = 122 values in a record of 128 doubles (eight 128-byte lines of its own, see CCD_STRIDE)
 
 __device__ __forceinline__ bool box_hit(const float* b, const QBox& q, double m) {
   // query.overlaps(node): reject if node.hi + m < q.lo or node.lo > q.hi + m on any axis
@@ -223,20 +222,6 @@ __device__ int bvh_query(const Dev& D, const QBox& q, double m, int* fa, int* fb
   return found;
 }
 
-// 49-axis intervals of n points stored row-major [n][3] (CCD.h:373-390); lanes 0..48
-__device__ __forceinline__ void kdop_intervals(const Dev& D, const double* pts, int n, double* klo, double* khi) {
-  const int lane = lane_id();
-  if (lane < 49) {
-    const double x = D.kdop[3 * lane], y = D.kdop[3 * lane + 1], z = D.kdop[3 * lane + 2];
-    double up = -INFINITY, lo = INFINITY;
-    for (int i = 0; i < n; i++) {
-      const double lv = x * pts[3 * i] + y * pts[3 * i + 1] + z * pts[3 * i + 2];
-      if (lv < lo) lo = lv;
-      if (lv > up) up = lv;
-    }
-    klo[lane] = lo; khi[lane] = up;
-  }
-}
 // point vs cached hull intervals
 __device__ __forceinline__ bool kdop_point_pass(const Dev& D, const double* klo, const double* khi, const V3& q, double d) {
   for (int k = 0; k < 49; k++) {
@@ -296,12 +281,17 @@ __device__ __forceinline__ bool kdop_cull_wave(const B& body, int n, const V3& a
   return (pass >> lane) & 1ull;
 }
 
-// Separate::opengjk (Separate.h:18-163): plane (c,d) between a 6-point hull and one cloud point
-// plane (c,d) from the GJK witness vector v of hull - point (Separate.h:107-151): rejected if |v| > dist
-__device__ __forceinline__ bool plane_from_witness(const V3& v, const V3& qp, double dist, double offset, double& c0, double& c1, double& c2, double& dd) {
+// witness to plane, first step of every form below: the unit normal c = v / |v| of the GJK witness vector v; false (no plane) if the bodies are farther apart than dist
+__device__ __forceinline__ bool plane_normal(const V3& v, double dist, double& c0, double& c1, double& c2) {
   const double cn = norm3(v.x, v.y, v.z);
   if (cn > dist) return false;
   c0 = v.x / cn; c1 = v.y / cn; c2 = v.z / cn;
+  return true;
+}
+// Separate::opengjk (Separate.h:18-163): plane (c,d) between a 6-point hull and one cloud point
+// plane (c,d) from the GJK witness vector v of hull - point (Separate.h:107-151): rejected if |v| > dist
+__device__ __forceinline__ bool plane_from_witness(const V3& v, const V3& qp, double dist, double offset, double& c0, double& c1, double& c2, double& dd) {
+  if (!plane_normal(v, dist, c0, c1, c2)) return false;
   const double d0 = -c0 * qp.x - c1 * qp.y - c2 * qp.z;
   dd = d0 - offset;
   return true;
@@ -309,9 +299,7 @@ __device__ __forceinline__ bool plane_from_witness(const V3& v, const V3& qp, do
 // the same for a body of B::N vertices: d0 = min_i(-c . B_i), the loop the reference keeps commented out at Separate.h:123-131
 template <class B>
 __device__ __forceinline__ bool plane_from_witness_body(const V3& v, const B& body, double dist, double offset, double& c0, double& c1, double& c2, double& dd) {
-  const double cn = norm3(v.x, v.y, v.z);
-  if (cn > dist) return false;
-  c0 = v.x / cn; c1 = v.y / cn; c2 = v.z / cn;
+  if (!plane_normal(v, dist, c0, c1, c2)) return false;
   const V3 q0 = body.get(0);
   double d0 = -c0 * q0.x - c1 * q0.y - c2 * q0.z;
 #pragma unroll
@@ -347,6 +335,13 @@ __device__ inline bool kdop_hulls_pass(const Dev& D, const double* A, const doub
 // second half of plane_pair: from the GJK witness vector to the plane (separate so that a caller can act between the halves)
 // cr_log out of line: the per-lane pair path lives in k_mid at its 256-register cap, where the inlined double-double pieces spill
 __device__ __noinline__ double cr_log_call(double x) { return cr_log(x); }
+// one barrier term of the offset Newton (Optimal_plane.h:13-71) at signed distance ds < m: its first and second derivative in the offset, before the side's sign.
+// lg = log(ds / m), handed in: the lane path takes it from cr_log_call, the wave path from the inlined cr_log (both round like glibc's log, dev_crmath.h: the offset
+// is then the reference's bit for bit)
+__device__ __forceinline__ void offset_barrier_terms(double ds, double m, double lg, double& g1, double& g2) {
+  g1 = -(2 * (ds - m) * lg + (ds - m) * (ds - m) / ds);
+  g2 = -(2 * lg + 4 * (ds - m) / ds - (ds - m) * (ds - m) / (ds * ds));
+}
 __device__ inline bool plane_pair_finish(const V3& v, const double* A, const double* Bq, double dist, double m, double off, bool refine, double& e0, double& e1c, double& e2c, double& dpl, bool& capped, int* newton_iters = nullptr, int st = 1);
 __device__ inline bool plane_pair(const double* A, const double* Bq, double dist, double m, double off, bool refine, double& e0, double& e1c, double& e2c, double& dpl, bool& capped, int* newton_iters = nullptr, int* gjk_iters = nullptr) {
   const V3 v = gjk(BodyHull{A}, BodyHull{Bq}, gjk_iters);
@@ -355,9 +350,7 @@ __device__ inline bool plane_pair(const double* A, const double* Bq, double dist
 // st: stride between the entries of A / Bq (1: row-major [6][3] in global memory or LDS; the lane-per-pair path of large fleets keeps a transposed tile, BodyHullT)
 __device__ inline bool plane_pair_finish(const V3& v, const double* A, const double* Bq, double dist, double m, double off, bool refine, double& e0, double& e1c, double& e2c, double& dpl, bool& capped, int* newton_iters, int st) {
   capped = false;
-  const double cn = norm3(v.x, v.y, v.z);
-  if (cn > dist) return false;
-  e0 = v.x / cn; e1c = v.y / cn; e2c = v.z / cn;
+  if (!plane_normal(v, dist, e0, e1c, e2c)) return false;
   double d0 = INFINITY, d1 = -INFINITY;
   for (int i = 0; i < 6; i++) { const double t = -(e0 * Bq[(3 * i) * st] + (e1c * Bq[(3 * i + 1) * st] + e2c * Bq[(3 * i + 2) * st])); if (d0 > t) d0 = t; }   // dot_fixed3's order (Eigen unrolled 3-term, Separate.h:268,276)
   for (int i = 0; i < 6; i++) { const double t = -(e0 * A[(3 * i) * st] + (e1c * A[(3 * i + 1) * st] + e2c * A[(3 * i + 2) * st])); if (d1 < t) d1 = t; }
@@ -369,18 +362,16 @@ __device__ inline bool plane_pair_finish(const V3& v, const double* A, const dou
     for (int j = 0; j < 6; j++) {
       const double ds = (A[(3 * j) * st] * e0 + A[(3 * j + 1) * st] * e1c + A[(3 * j + 2) * st] * e2c) + dpl - 0.5 * off;
       if (ds < m) {
-        const double lg = cr_log_call(ds / m);   // rounds like glibc's log (dev_crmath.h): the offset is then the reference's bit for bit
-        const double g1 = -(2 * (ds - m) * lg + (ds - m) * (ds - m) / ds);
-        const double g2 = -(2 * lg + 4 * (ds - m) / ds - (ds - m) * (ds - m) / (ds * ds));
+        double g1, g2;
+        offset_barrier_terms(ds, m, cr_log_call(ds / m), g1, g2);
         grad += g1; hess += g2;
       }
     }
     for (int j = 0; j < 6; j++) {
       const double ds = -(Bq[(3 * j) * st] * e0 + Bq[(3 * j + 1) * st] * e1c + Bq[(3 * j + 2) * st] * e2c) - dpl - 0.5 * off;
       if (ds < m) {
-        const double lg = cr_log_call(ds / m);
-        const double g1 = -(2 * (ds - m) * lg + (ds - m) * (ds - m) / ds);
-        const double g2 = -(2 * lg + 4 * (ds - m) / ds - (ds - m) * (ds - m) / (ds * ds));
+        double g1, g2;
+        offset_barrier_terms(ds, m, cr_log_call(ds / m), g1, g2);
         grad += -g1; hess += g2;
       }
     }
@@ -413,9 +404,7 @@ __device__ __forceinline__ bool plane_pair_wave(const double* A, const double* B
   if (gjk_iters) *gjk_iters = gst.k;
   TJ_ORDER(v.x);
   if (tic) TJ_TIC(*tic, K_SEP_SELF_SOLVE, 3);
-  const double cn = norm3(v.x, v.y, v.z);
-  if (cn > dist) return false;
-  e0 = v.x / cn; e1c = v.y / cn; e2c = v.z / cn;
+  if (!plane_normal(v, dist, e0, e1c, e2c)) return false;
   double d0 = INFINITY, d1 = -INFINITY;
   for (int i = 0; i < 6; i++) { const double t = -dot_fixed3(e0, e1c, e2c, Bq + 3 * i); if (d0 > t) d0 = t; }
   for (int i = 0; i < 6; i++) { const double t = -dot_fixed3(e0, e1c, e2c, A + 3 * i); if (d1 < t) d1 = t; }
@@ -431,11 +420,7 @@ __device__ __forceinline__ bool plane_pair_wave(const double* A, const double* B
     const double ds = lane < 6 ? dp + dpl - 0.5 * off : -dp - dpl - 0.5 * off;
     const bool act = lane < 12 && ds < m;
     double g1 = 0, g2 = 0;
-    if (act) {
-      const double lg = cr_log(ds / m);
-      g1 = -(2 * (ds - m) * lg + (ds - m) * (ds - m) / ds);
-      g2 = -(2 * lg + 4 * (ds - m) / ds - (ds - m) * (ds - m) / (ds * ds));
-    }
+    if (act) offset_barrier_terms(ds, m, cr_log(ds / m), g1, g2);
     const unsigned mask = (unsigned)__ballot(act);
     double grad = 0, hess = 0;
 #pragma unroll
@@ -497,48 +482,32 @@ __device__ __forceinline__ void obs_query_body(const Dev& D, int bid, double* ld
   QBox q;
   const TopBox topb = bvh_top_box(D);   // travels with the segment's record
   if (use_cache && D.multi()) {
-    const double* h = D.hullinfo + ((size_t)u * D.S + tr) * HULL_INFO_STRIDE;
+    const double* h = hull_record(D, u, tr);
     if (lane < 18) P[lane] = h[lane];
-    if (lane < 49) { klo[lane] = h[24 + lane]; khi[lane] = h[73 + lane]; }
+    if (lane < 49) { klo[lane] = h[HULL_KLO + lane]; khi[lane] = h[HULL_KHI + lane]; }
 #pragma unroll
-    for (int k = 0; k < 3; k++) { q.lo[k] = h[18 + k]; q.hi[k] = h[21 + k]; }
+    for (int k = 0; k < 3; k++) { q.lo[k] = h[HULL_BOX + k]; q.hi[k] = h[HULL_BOX + 3 + k]; }
   } else {
     if constexpr (FA) {
       double bk[6] = {0, 0, 0, 0, 0, 0};
       const int e = min(lane, 17);
-      const double* B = D.basis + (size_t)tr * 36 + (e / 3) * 6;
+      const double* B = hull_row(D, tr, e / 3);
 #pragma unroll
       for (int k = 0; k < 6; k++) bk[k] = B[k];
-      const double* col = net + div_small(tr, D.res) * 3 + D.T * (e % 3);
+      const double* col = hull_col(D, net, tr, e % 3);
       fa_wait_flag(D, D.fa_commit(u), D.fa_seq);
       TJ_TIC(D, K_SEP_OBS, 6);
-      if (lane < 18) {
-        double acc = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) acc += bk[k] * xf_load(col + k);   // = hull_entry
-        P[lane] = acc;
-      }
+      if (lane < 18) P[lane] = hull_sum(bk, col, xf_load);
     } else
     if (lane < 18) P[lane] = hull_entry(D, net, tr, lane / 3, lane % 3);
     __syncthreads();
-    kdop_intervals(D, P, 6, klo, khi);
+    if (lane < 49) { double lo, up; hull_kdop_axis(D, P, lane, lo, up); klo[lane] = lo; khi[lane] = up; }
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      double lo = INFINITY, hi = -INFINITY;
-      for (int j = 0; j < 6; j++) { const double v = P[3 * j + k]; if (v < lo) lo = v; if (v > hi) hi = v; }
-      q.lo[k] = lo; q.hi[k] = hi;
-    }
+    for (int k = 0; k < 3; k++) hull_box_axis(P, k, q.lo[k], q.hi[k]);
   }
   __syncthreads();
-  if (publish) {
-    double* o = D.hullinfo + ((size_t)u * D.S + tr) * HULL_INFO_STRIDE;
-    if (lane < 18) xf_store(o + lane, P[lane]);
-    if (lane < 3) {
-      const double lo = lane == 0 ? q.lo[0] : (lane == 1 ? q.lo[1] : q.lo[2]), hi = lane == 0 ? q.hi[0] : (lane == 1 ? q.hi[1] : q.hi[2]);
-      xf_store(o + 18 + lane, lo); xf_store(o + 21 + lane, hi);
-      xf_store(D.hbox + ((size_t)tr * 6 + lane) * D.U + u, lo); xf_store(D.hbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, hi);
-    }
-    if (lane < 49) { xf_store(o + 24 + lane, klo[lane]); xf_store(o + 73 + lane, khi[lane]); }
+  if (publish) {   // the record's values are at hand (every lane holds the box, the intervals are in LDS)
+    hull_record_put<true>(D, u, tr, lane, P[min(lane, 17)], lane == 0 ? q.lo[0] : (lane == 1 ? q.lo[1] : q.lo[2]), lane == 0 ? q.hi[0] : (lane == 1 ? q.hi[1] : q.hi[2]), klo[min(lane, 48)], khi[min(lane, 48)]);
     xf_signal(D, 0, tr);
   }
   TJ_TIC(D, K_SEP_OBS, 1);

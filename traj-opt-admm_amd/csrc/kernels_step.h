@@ -131,31 +131,10 @@ __device__ __forceinline__ void xf_hull_body(const Dev& D, int f) {
     if (D.xch_poll) xch_wait_owner(D, 0, D.owner_of(u));   // (after a timeout the error bit fails the batch; the unit still reports, so that no tile waits in vain)
     const double* rxn = D.rx[0] + (size_t)u * 3 * T;
     if (tr == 0) for (int i = lane; i < 3 * T; i += 64) D.spline[(size_t)u * 3 * T + i] = xch_load(rxn + i);   // read by later kernels only (k_ccd's units)
-    if (lane < 18) {
-      const int j = lane / 3, a = lane % 3;
-      const double* B = D.basis + (size_t)tr * 36 + j * 6;
-      const double* col = rxn + div_small(tr, D.res) * 3 + T * a;
-      double acc = 0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc += B[k] * xch_load(col + k);   // = hull_entry
-      P[lane] = acc;
-    }
+    if (lane < 18) P[lane] = hull_sum(hull_row(D, tr, lane / 3), hull_col(D, rxn, tr, lane % 3), xch_load);
   } else if (lane < 18) P[lane] = hull_entry(D, net, tr, lane / 3, lane % 3);
   blk_sync<true>();
-  double* o = D.hullinfo + ((size_t)u * D.S + tr) * HULL_STRIDE;
-  if (lane < 18) xf_store(o + lane, P[lane]);
-  if (lane < 3) {
-    double lo = INFINITY, hi = -INFINITY;
-    for (int j = 0; j < 6; j++) { const double v = P[3 * j + lane]; if (v < lo) lo = v; if (v > hi) hi = v; }
-    xf_store(o + 18 + lane, lo); xf_store(o + 21 + lane, hi);
-    xf_store(D.hbox + ((size_t)tr * 6 + lane) * D.U + u, lo); xf_store(D.hbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, hi);
-  }
-  if (lane < 49) {
-    const double x = D.kdop[3 * lane], y = D.kdop[3 * lane + 1], z = D.kdop[3 * lane + 2];
-    double up = -INFINITY, lo = INFINITY;
-    for (int i = 0; i < 6; i++) { const double lv = x * P[3 * i] + y * P[3 * i + 1] + z * P[3 * i + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-    xf_store(o + 24 + lane, lo); xf_store(o + 73 + lane, up);
-  }
+  hull_record_store<true>(D, u, tr, lane, P);
   xf_signal(D, 0, tr);
 }
 __device__ __forceinline__ void xf_ccd_body(const Dev& D, int f, double* sh) {

@@ -679,7 +679,7 @@ std::vector<ArrayDecl> device_arrays(Dev& d) {
     arr(d.k_obs, U), arr(d.k_self, U), arr(d.step_out, U, SNAP), arr(d.ls_hist, U, SNAP), arr(d.grad_cost, owned * P), arr(d.grad_perm, owned * P), arr(d.ls_tab, U * LS_TAB_STRIDE), arr(d.ls_word, U),
     arr(d.ccdinfo, U * S * CCD_STRIDE), arr(d.pair_list, ACT_CAP),
     arr(d.seg_stats, U * S * 6, SNAP), arr(d.pair_stats, U * S * 2, SNAP), arr(d.blk_stats, U * P + U, SNAP),
-    arr(d.hullinfo, U * S * HULL_STRIDE), arr(d.hbox, S * 6 * U), arr(d.cbox, S * 6 * U), arr(d.pairplane, multi ? S * U * U * 4 : 1),
+    arr(d.hullinfo, U * S * HULL_INFO_STRIDE), arr(d.hbox, S * 6 * U), arr(d.cbox, S * 6 * U), arr(d.pairplane, multi ? S * U * U * 4 : 1),
     arr(d.pairstamp, multi ? S * U * U : 1), arr(d.pairbits, multi ? S * U * ((U + 63) / 64) : 1),
     arr(d.pair_work, 3 * (size_t)d.cap_work), arr(d.pair_work_n, S + 1), arr(d.pair_ovf, 4), arr(d.seq_gmem_d, seq_fold_gmem_doubles(d.U)), arr(d.seq_gmem_i, seq_fold_gmem_ints(d.U)),
     arr(d.spec_n, 2), arr(d.spec_list, 2 * SPEC_CAP), arr(d.spec_tag, SPEC_CAP), arr(d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES), arr(d.spec_sti, SPEC_CAP * SPEC_STATE_INTS),
@@ -2118,6 +2118,20 @@ int tj_kat_set_local_grad(tj_ctx* c, const double* lg, const double* lh) {
   QUIESCE(c);
   const size_t blocks = (size_t)d.U * d.P;
   { int ur; if ((ur = upload(c, d.lg, lg, blocks * 19 * 8)) || (ur = upload(c, d.lh, lh, blocks * 361 * 8))) return ur; }
+  return TJ_OK;
+}
+
+// the hull cache as the last launch that wrote it left it: the 122 values of every (robot, segment) record and the box table.  No kernel runs
+int tj_kat_get_hull_record(tj_ctx* c, double* hullinfo, double* hbox) {
+  if (!c || !hullinfo || !hbox) return TJ_ERR_INVALID;
+  if (!ready(c)) return TJ_ERR_INVALID;
+  const Dev& d = c->d;
+  QUIESCE(c);
+  const size_t recs = (size_t)d.U * d.S;
+  std::vector<double> h(recs * HULL_INFO_STRIDE);
+  HIPCHK(c, hipMemcpy(h.data(), d.hullinfo, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < recs; r++) memcpy(hullinfo + r * 122, h.data() + r * HULL_INFO_STRIDE, 122 * sizeof(double));
+  HIPCHK(c, hipMemcpy(hbox, d.hbox, (size_t)d.S * 6 * d.U * sizeof(double), hipMemcpyDeviceToHost));
   return TJ_OK;
 }
 

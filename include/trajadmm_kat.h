@@ -55,6 +55,11 @@ int tj_kat_set_local_grad(tj_ctx* c, const double* lg, const double* lh);
  * hullinfo[U][S][122] = hull 18, box lo/hi 6, the 49 k-DOP intervals lo, hi of every (robot, segment) record; hbox[S][6][U] = the boxes again as the
  * pair tiles read them.  Pending work of the context is waited for, no kernel is launched.  TJ_ERR_INVALID: a null argument, or a context without cloud / state. */
 int tj_kat_get_hull_record(tj_ctx* c, double* hullinfo, double* hbox);
+/* the swept-hull cache of the two CCD stages as its last writer left it (k_ccd_prep, k_xsolve's tail or k_ccd's units -- which one depends on the schedule):
+ * ccdinfo[U][S][146] = hull P 18, direction hull D 18, obstacle box lo/hi 6, pair box lo/hi 6, the 49 k-DOP intervals lo, hi of every (robot, segment) record;
+ * cbox[S][6][U] = the pair boxes again as the selection tiles read them.  Pending work of the context is waited for, no kernel is launched.  TJ_ERR_INVALID: a
+ * null argument, or a context without cloud / state. */
+int tj_kat_get_swept_record(tj_ctx* c, double* ccdinfo, double* cbox);
 
 /* ---- the launch plan (csrc/host_plan.h) ------------------------------------------------------------
  * A flat record of ints: the device facts the plan was decided on (PlanFacts), then every decision of the plan, the LDS byte counts, the queue

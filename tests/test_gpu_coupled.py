@@ -327,3 +327,56 @@ def test_hull_record_writers_agree_bitwise(pkg, scenes, monkeypatch, mode):
         assert np.array_equal(hbox, hbox_k), (i, int(np.sum(hbox != hbox_k)))
     for s, _, _ in runs:
         s.close()
+
+
+@pytest.mark.parametrize("mode", [1, 2], ids=["decoupled", "coupled"])
+def test_swept_record_writers_agree_bitwise(pkg, scenes, monkeypatch, mode):
+    """The swept-hull cache of the two CCD stages (per (robot, segment): hull P, direction hull D, obstacle box, pair box, 49 k-DOP intervals; and the pair-box
+    table) has several writers that must leave the same bits (dev_common.h: swept_record_put and its pieces).  The line search does not touch the cache, so after
+    one more iteration it still holds what that iteration's writer made of the state before it and of the direction tj_get_direction then reports:
+      decoupled   the obstacle units of k_ccd behind the asynchronous solve (ccd_record_async), or, with TJ_XS_ASYNC=0, k_xsolve's tail;
+      coupled     the publishing obstacle units of k_ccd (ccd_prep_segment, written through), or, with TJ_COUPLED_UNITS=0, k_ccd_prep launched inside the chain.
+    Each is compared with what k_ccd_prep writes through the stage API for that state and that direction (set_state, set_direction, then the stage ccd_prep)."""
+    scene = dict(scenes.crossing(12, 4000, seed=23, name="crossing-U12-sweptrec"), mode=mode)
+    for k in ("TJ_XS_ASYNC", "TJ_KEEP_ASYNC", "TJ_COUPLED_UNITS"):
+        monkeypatch.delenv(k, raising=False)
+
+    def chain(env, plan_want):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        s = pkg.Solver(scene, stop=0.0, kat=True)
+        for k in env:
+            monkeypatch.delenv(k)
+        plan = pkg.plan_record(ctx=s._ctx)[1]
+        for k, v in plan_want.items():
+            assert plan[k] == v, (env, k, plan[k])
+        s.iterate(3)
+        st = s.get_state()
+        s.iterate(1)
+        rec = s.kat_swept_record()
+        dirs = [s.get_direction(u) for u in range(s.U)]
+        assert s.stats()["error_bits"] == 0
+        return s, st, rec, dirs
+
+    if mode == 1:
+        runs = [chain({}, {"xs_async": 1, "fuse": 1}), chain({"TJ_XS_ASYNC": "0"}, {"xs_async": 0, "fuse": 1})]
+    else:
+        runs = [chain({}, {"xf_all": 1}), chain({"TJ_COUPLED_UNITS": "0"}, {"xf_all": 0})]
+    s0, st0, _, dirs0 = runs[0]
+    for _, st, _, dirs in runs[1:]:
+        for n in STATE:
+            assert np.array_equal(st0[n], st[n]), n
+        for u in range(s0.U):
+            assert np.array_equal(dirs0[u][0], dirs[u][0]), u
+    s0.set_state(st0)
+    for u, (d, t, w, g) in enumerate(dirs0):
+        s0.set_direction(u, d, t, w, g)
+    s0.run_stage("begin")
+    s0.run_stage("ccd_prep")
+    info_k, cbox_k = s0.kat_swept_record()
+    assert np.all(np.isfinite(info_k)) and np.all(np.isfinite(cbox_k)) and np.any(info_k[:, :, pkg.Solver.SWEPT_FIELDS["D"]] != 0.0)
+    for i, (_, _, (info, cbox), _) in enumerate(runs):
+        assert np.array_equal(info, info_k), (i, int(np.sum(info != info_k)))
+        assert np.array_equal(cbox, cbox_k), (i, int(np.sum(cbox != cbox_k)))
+    for s, _, _, _ in runs:
+        s.close()

@@ -292,7 +292,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad", "tj_kat_get_hull_record"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -564,6 +564,12 @@ class Solver:
         out["gnorm"] = float(np.sum(out["gn"]) / self.U) if self.mode == 1 else float(out["gn"][0])
         return out
 
+    def get_direction(self, u):
+        """robot u's direction record as the last Newton solve left it: (direction [3][T], t_direction, wolfe, gn)"""
+        d = np.zeros((3, self.T)); t, w, g = C.c_double(), C.c_double(), C.c_double()
+        self._check(self.lib.tj_get_direction(self._ctx, C.c_int(u), _d(d), C.byref(t), C.byref(w), C.byref(g)))
+        return d, t.value, w.value, g.value
+
     def set_direction(self, u, direction, t_direction, wolfe, gn):
         d = np.ascontiguousarray(direction, dtype=np.float64)
         self._check(self.lib.tj_set_direction(self._ctx, C.c_int(u), _d(d), C.c_double(t_direction), C.c_double(wolfe), C.c_double(gn)))
@@ -631,6 +637,16 @@ class Solver:
         info = np.zeros((self.U, self.S, 122)); hbox = np.zeros((self.S, 6, self.U))
         self._check(self.lib.tj_kat_get_hull_record(self._ctx, _d(info), _d(hbox)))
         return info, hbox
+
+    # the swept-hull record's fields (csrc/dev_common.h: CCD_P .. CCD_KHI, CCD_REC), as slices of a record tj_kat_get_swept_record returns
+    SWEPT_FIELDS = dict(P=slice(0, 18), D=slice(18, 36), obs_box=slice(36, 42), pair_box=slice(42, 48), k_lo=slice(48, 97), k_hi=slice(97, 146))
+    SWEPT_REC = 146
+
+    def kat_swept_record(self):
+        """the swept-hull cache as its last writer left it: (ccdinfo [U][S][SWEPT_REC], cbox [S][6][U])"""
+        info = np.zeros((self.U, self.S, self.SWEPT_REC)); cbox = np.zeros((self.S, 6, self.U))
+        self._check(self.lib.tj_kat_get_swept_record(self._ctx, _d(info), _d(cbox)))
+        return info, cbox
 
     def kat_planes(self, what, P, Q, dist):
         P = np.ascontiguousarray(P, dtype=np.float64); Q = np.ascontiguousarray(Q, dtype=np.float64)

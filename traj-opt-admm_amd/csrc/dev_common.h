@@ -351,7 +351,9 @@ struct Dev {
 // two records, so a record that another block of the SAME launch writes (sharded contexts: foreign units, then pair tiles) cannot sit half-stale in an L2
 // that fetched the neighbouring record earlier in the launch.
 constexpr int CCD_STRIDE = 160;
-constexpr int CCD_REC = 18 + 18 + 6 + 6 + 98;
+// the record's fields (helpers: "the swept-hull record", below): hull P[6][3], direction hull D[6][3], obstacle box lo / hi over {P, PD}, pair box lo / hi over {P, P + D}, interval minima, maxima
+constexpr int CCD_P = 0, CCD_D = CCD_P + 18, CCD_OBOX = CCD_D + 18, CCD_PBOX = CCD_OBOX + 6, CCD_KLO = CCD_PBOX + 6, CCD_KHI = CCD_KLO + 49, CCD_REC = CCD_KHI + 49;
+static_assert(CCD_REC == 146 && CCD_REC <= CCD_STRIDE, "the swept-hull record: 146 values in ten lines of its own");
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
@@ -568,6 +570,40 @@ __device__ __forceinline__ void hull_record_store(const Dev& D, int u, int tr, i
   if (lane < 3) hull_box_axis(P, lane, blo, bhi);
   if (lane < 49) hull_kdop_axis(D, P, lane, klo, khi);
   hull_record_put<WT>(D, u, tr, lane, P[min(lane, 17)], blo, bhi, klo, khi);
+}
+
+// ---- the swept-hull record of a (robot, segment) (Dev::ccdinfo, Dev::cbox; fields CCD_P .. CCD_KHI above), stated ONCE for its writers -- ccd_prep_segment (k_ccd_prep, the
+// publishing and foreign units), ccd_record_async and k_xsolve's tail, which keep their thread mappings, loads and waits -- and its readers (the two CCD stages, the replay);
+// tests/test_gpu_coupled.py compares what the writers leave bit for bit.  cbox holds the pair boxes again as [segment][lo.xyz hi.xyz][robot] for the selection tiles.
+// A writer hands its store in as put(double* dst, double v): plain, written through (xf_store), xs_out(wt, ...), or plain into an LDS copy of the record.
+__device__ __forceinline__ double* swept_record(const Dev& D, int u, int tr) { return D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE; }
+__device__ __forceinline__ BodySwept swept_body(const double* rec, double step) { return BodySwept{rec + CCD_P, rec + CCD_D, step}; }   // conv{P, P + step * D}
+// value e of the 36 hull values [P | D], both hulls' entry e < 18, axis a of the two boxes (the pair box also into the table), the interval on k-DOP axis ax
+template <class Put>
+__device__ __forceinline__ void swept_put_hull_value(double* rec, int e, double v, Put&& put) { put(rec + (e < CCD_D - CCD_P ? CCD_P + e : CCD_D + e - (CCD_D - CCD_P)), v); }
+template <class Put>
+__device__ __forceinline__ void swept_put_hull(double* rec, int e, double p, double dh, Put&& put) { swept_put_hull_value(rec, e, p, put); swept_put_hull_value(rec, CCD_D - CCD_P + e, dh, put); }
+template <class Put, class PutBox>
+__device__ __forceinline__ void swept_put_boxes(const Dev& D, double* rec, int u, int tr, int a, const SweptBoxes& b, Put&& put, PutBox&& put_cbox) {
+  put(rec + CCD_OBOX + a, b.lo); put(rec + CCD_OBOX + 3 + a, b.hi); put(rec + CCD_PBOX + a, b.lo2); put(rec + CCD_PBOX + 3 + a, b.hi2);
+  put_cbox(D.cbox + ((size_t)tr * 6 + a) * D.U + u, b.lo2); put_cbox(D.cbox + ((size_t)tr * 6 + 3 + a) * D.U + u, b.hi2);
+}
+template <class Put>
+__device__ __forceinline__ void swept_put_interval(double* rec, int ax, double lo, double up, Put&& put) { put(rec + CCD_KLO + ax, lo); put(rec + CCD_KHI + ax, up); }
+// one wave, the hulls P, Dh, PD and PS = P + Dh complete in LDS: this lane's share of the record `rec` of (u, tr) -- hull entries (lanes 0..17), box axis (0..2), interval on
+// k-DOP axis `lane` (0..48; axis(): that axis, fetched by the caller where it wants the load) -- and of the box table
+template <class Axis, class Put, class PutBox>
+__device__ __forceinline__ void swept_record_put(const Dev& D, double* rec, int u, int tr, int lane, const double* P, const double* Dh, const double* PD, const double* PS,
+                                                 Axis&& axis, Put&& put, PutBox&& put_cbox) {
+  if (lane < 18) swept_put_hull(rec, lane, P[lane], Dh[lane], put);
+  if (lane < 3) swept_put_boxes(D, rec, u, tr, lane, swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; }), put, put_cbox);
+  if (lane < 49) {
+    const V3 k = axis();
+    double up = -INFINITY, lo = INFINITY;
+    kdop_interval6(k.x, k.y, k.z, P, lo, up);
+    kdop_interval6(k.x, k.y, k.z, PS, lo, up);
+    swept_put_interval(rec, lane, lo, up, put);
+  }
 }
 
 __device__ __forceinline__ double seg_weight(const Dev& D, int tr) {

@@ -50,7 +50,6 @@ struct Plan { int err = TJ_OK; const char* msg = ""; Dev d; HostPlan h; };
 // ---- grid sizes of the iteration's kernels (one wave per block) ----
 struct Grids { int n_rows, n_ccd, n_xf, n_front, n_solve, n_obs_solve, n_mid_slack; };
 inline Grids plan_grids(const Dev& d, int n_solve_env) {
-  const int owned = d.u1 - d.u0;
   const bool multi = d.mode >= 1;
   Grids g;
   // Waves striding over the two device-built work lists.  k_mid holds ~1 wave per SIMD (VGPR bound), i.e. 1024 resident
@@ -62,11 +61,13 @@ inline Grids plan_grids(const Dev& d, int n_solve_env) {
   // 320 slack blocks (1 024: k_mid 31.5 us, 1 536: 28.2, 1 728: 27.6, 2 048: 27.6 before the static assignment; alike after it).
   g.n_solve = (multi && !d.optimal_plane) ? std::min(d.cap_work, n_solve_env > 0 ? n_solve_env : (d.U >= 192 ? 1536 : 1728)) : 0;  // "optimal_plane":1 -- k_keep finds and refines the pair planes
   g.n_obs_solve = d.N > 0 ? 1024 : 0;   // (512: SCN-E's k_mid 43.7 us, 1024: 38.3, 2048: 37.8; SCN-C indifferent)
-  g.n_rows = multi ? d.S * pair_units(d.U, d.pair_rows) : 0;   // one wave per (segment, tile of pair_rows lower robots x 64 partners)
+  // the union kernels: their block layouts (kernels_step.h) say what each grid holds.  n_ccd: obstacle units + pair tiles, without the foreign units and k_ccd's finisher
+  const FrontLayout lf(d); const CcdLayout lc(d);
+  g.n_rows = lc.tiles();
   g.n_xf = d.xf_units();   // sharded contexts: one wave per (foreign robot, segment) at the head of k_front / k_ccd (kernels_step.h); coupled chain: per (robot, segment)
-  g.n_ccd = owned * d.S + g.n_rows;
-  g.n_front = g.n_ccd + g.n_xf + (d.spec ? SPEC_CAP : 0) + (d.grad_bal ? (owned * d.P + 63) / 64 : 0);
-  g.n_mid_slack = owned * d.P;
+  g.n_ccd = lc.total() - lc.xf;
+  g.n_front = lf.total();
+  g.n_mid_slack = MidLayout::slack_blocks(d);
   return g;
 }
 
@@ -133,9 +134,9 @@ inline Plan plan_context(const tj_params* p, const PlanFacts& f, TuneFn tune) {
   if (d.U > 2048) return fail("more than 2048 robots are not supported (pair keys pack robot ids into 11 bits; the dense [S][U][U] plane tables are 5.4 GB + 0.7 GB there)");
   if (d.S > 511) return fail("more than 511 segments per robot are not supported by the line-search kernel");
   if (d.res > GRAD_MAXRES) return fail("res > 16 segments per piece is not supported by the gradient kernel");
-  d.seq_tree = (decoupled && seq_lds_bytes(d.U, d.S, true) <= lds_max) ? 1 : 0;
+  d.seq_tree = (decoupled && SeqLayout(d.U, ACT_CAP, true).lds_bytes() <= lds_max) ? 1 : 0;
   if (tune("NO_SEQ_TREE")) d.seq_tree = 0;  // test hook: behave like a fleet too large for the LDS-resident tree
-  h.lds_seq = seq_lds_bytes(d.U, d.S, d.seq_tree != 0);
+  h.lds_seq = SeqLayout(d.U, ACT_CAP, d.seq_tree != 0).lds_bytes();
   // hundreds of robots: the 512-thread folded k_grad is limited to ~2 workgroups per CU by wave slots; the 192-thread one (5 per CU)
   // plus a separate compaction launch is faster once there are more pieces than that (SCN-D: k_grad 109 -> 72 + 14 us)
   h.grad_fold = flag(tune("GRAD_FOLD"), items <= 512) != 0;
@@ -153,8 +154,8 @@ inline Plan plan_context(const tj_params* p, const PlanFacts& f, TuneFn tune) {
   if (decoupled || (coupled && one)) {   // (coupled: one context only -- a sharded one exports its obstacle-CCD exponents from k_ccd_self_seq)
     const size_t buf = sizeof(double) * (size_t)(CCD_LDS_DOUBLES > PAIR_LDS_DOUBLES ? CCD_LDS_DOUBLES : PAIR_LDS_DOUBLES);
     int cap = 4096;
-    while (cap >= 256 && seq_fold_lds_bytes(d.U, cap) > buf) cap >>= 1;
-    if (cap >= 256 && (size_t)d.S * pair_units(d.U, d.pair_rows) < 65536) d.seq_fold = cap;   // (the finisher counts the selection blocks in 16 bits)
+    while (cap >= 256 && SeqLayout(d.U, cap, true).small_bytes > buf) cap >>= 1;
+    if (cap >= 256 && CcdLayout(d).tiles() < 65536) d.seq_fold = cap;   // (the finisher counts the selection blocks in 16 bits)
   }
   if (!flag(tune("SEQ_FOLD"), 1)) d.seq_fold = 0;   // launch-shape switch (same bits)
   if (const char* e = tune("N_SOLVE")) h.n_solve_env = std::max(1, atoi(e));

@@ -789,8 +789,7 @@ __device__ __forceinline__ void xs_swept_interval_out(const Dev& D, int u, const
   const int tr = idx / 49, k = idx % 49;
   const double* ax = D.kdop + 3 * k;
   kdop_interval6_sum(ax[0], ax[1], ax[2], Ph + tr * 54, Ph + tr * 54 + 18, lo, up);
-  double* o = D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE;
-  xs_out(wt, o + 48 + k, lo); xs_out(wt, o + 97 + k, up);
+  swept_put_interval(swept_record(D, u, tr), k, lo, up, [&](double* p, double v) { xs_out(wt, p, v); });
 }
 
 // asynchronous solve: the gate in front of k_xsolve on the second queue (one wave, no LDS: it may sit there through the rest of the previous iteration)
@@ -953,17 +952,15 @@ __global__ __launch_bounds__(XS_LOAD_THREADS) void k_xsolve(Dev D) {
       Ph[tr * 54 + e] = h.p; Ph[tr * 54 + 18 + e] = h.dh; Ph[tr * 54 + 36 + e] = h.pd;
     }
     __syncthreads();
+    auto put = [&](double* p, double v) { xs_out(wt, p, v); };
     for (int idx = tid; idx < S * 36; idx += XS_LOAD_THREADS) {   // P, Dh
       const int tr = idx / 36, e = idx % 36;
-      xs_out(wt, D.ccdinfo + ((size_t)u * S + tr) * CCD_STRIDE + e, Ph[tr * 54 + e]);
+      swept_put_hull_value(swept_record(D, u, tr), e, Ph[tr * 54 + e], put);
     }
     for (int idx = tid; idx < S * 3; idx += XS_LOAD_THREADS) {    // obstacle box over {P, PD}, pair box over {P, P + Dh}
       const int tr = idx / 3, a = idx % 3;
       const double* q = Ph + tr * 54;
-      const SweptBoxes b = swept_boxes(q, q + 36, a, [&](int j) { return q[3 * j + a] + q[18 + 3 * j + a]; });
-      double* o = D.ccdinfo + ((size_t)u * S + tr) * CCD_STRIDE;
-      xs_out(wt, o + 36 + a, b.lo); xs_out(wt, o + 39 + a, b.hi); xs_out(wt, o + 42 + a, b.lo2); xs_out(wt, o + 45 + a, b.hi2);
-      xs_out(wt, D.cbox + ((size_t)tr * 6 + a) * D.U + u, b.lo2); xs_out(wt, D.cbox + ((size_t)tr * 6 + 3 + a) * D.U + u, b.hi2);
+      swept_put_boxes(D, swept_record(D, u, tr), u, tr, a, swept_boxes(q, q + 36, a, [&](int j) { return q[3 * j + a] + q[18 + 3 * j + a]; }), put, put);
     }
     // 49-axis intervals of the swept hull at step 1: min / max over the 6 hull points and the 6 points P + Dh.  With the
     // hull's part already known (helpers), only the second half is left -- min and max do not depend on the order.

@@ -14,10 +14,18 @@
 //                   swept boxes and k-DOPs overlap and whose swept hulls are within `offset` at FULL step -- no
 //                   other pair can ever act, hulls being nested in the step.  Phase B (one wave, sequential)
 //                   replays the reference's ORDER DEPENDENT joint back-off over those (rare) pairs, segment by
-//                   segment; it also forms gnorm.
+//                   segment (ccd_self_seq_body: the replay only; its arrays are one SeqLayout, carved from LDS by the
+//                   stand-alone kernel and from k_ccd's buffer + global memory by the finisher).
+//   gnorm_form      gnorm (and the coupled mode's wolfe_c) from the per-robot values, the load as an argument: called by
+//                   k_ccd_self_seq and by k_ccd's finisher.
 //   slack_body      update_slack_lambda (Optimization3D_multi.h:344-506): per piece Newton step on
 //                   (z, t_z) with Armijo, then the dual ascent on (Lambda, tau).
-//   k_front / k_mid / k_ccd   union kernels: independent one-wavefront stages sharing a launch (see below).
+//   k_front / k_mid / k_ccd   union kernels: independent one-wavefront stages sharing a launch (see below); which block
+//                   runs which body is a FrontLayout / MidLayout / CcdLayout, built from Dev on both sides of the launch
+//                   (k_ccd decodes its layout's ranges by hand: see ccd_union_body).
+// Stated once, here or in dev_common.h ("The CCD and slack stage's single definitions"): the swept-hull
+// record (CCD_P .. CCD_KHI, swept_record, swept_body, swept_record_put and its pieces), the clamp test swept_within,
+// act_key / act_unkey, gnorm_form, SeqLayout, the three union layouts, slack_dyn_rows / slack_dyn_sum and the SL_* carve.
 #pragma once
 #include "dev_common.h"
 #include "dev_linalg.h"
@@ -50,20 +58,7 @@ __device__ __forceinline__ void ccd_prep_segment(const Dev& D, const double* net
   blk_sync<true>();
   if (lane < 18) PS[lane] = P[lane] + Dh[lane];  // (P + D) used by the pair box and by the k-DOP at step 1
   blk_sync<true>();
-  double* o = D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE;
-  if (lane < 18) { st(o + lane, P[lane]); st(o + 18 + lane, Dh[lane]); }
-  if (lane < 3) {
-    const SweptBoxes b = swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; });
-    st(o + 36 + lane, b.lo); st(o + 39 + lane, b.hi); st(o + 42 + lane, b.lo2); st(o + 45 + lane, b.hi2);
-    st(D.cbox + ((size_t)tr * 6 + lane) * D.U + u, b.lo2); st(D.cbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, b.hi2);
-  }
-  if (lane < 49) {
-    const double x = D.kdop[3 * lane], y = D.kdop[3 * lane + 1], z = D.kdop[3 * lane + 2];
-    double up = -INFINITY, lo = INFINITY;
-    kdop_interval6(x, y, z, P, lo, up);
-    kdop_interval6(x, y, z, PS, lo, up);
-    st(o + 48 + lane, lo); st(o + 97 + lane, up);
-  }
+  swept_record_put(D, swept_record(D, u, tr), u, tr, lane, P, Dh, PD, PS, [&] { return V3{D.kdop[3 * lane], D.kdop[3 * lane + 1], D.kdop[3 * lane + 2]}; }, st, st);
   blk_sync<true>();  // sh is reused by the caller's next segment
 }
 
@@ -92,21 +87,18 @@ __device__ __forceinline__ void ccd_record_async(const Dev& D, int u, int tr, in
   else if (lane < 36) Dh[lane - 18] = hull_sum(bk, dk);
   else if (lane < 54) PD[lane - 36] = hull_sum_pd(bk, nk, dk);
   blk_sync<true>();
-  if (lane < 18) { PS[lane] = P[lane] + Dh[lane]; info[lane] = P[lane]; info[18 + lane] = Dh[lane]; }
+  auto put = [](double* p, double v) { *p = v; };   // the record into the LDS copy; the pieces of swept_record_put in this unit's own order (the hull entries ride with PS, one barrier earlier)
+  if (lane < 18) { PS[lane] = P[lane] + Dh[lane]; swept_put_hull(info, lane, P[lane], Dh[lane], put); }
   blk_sync<true>();
-  if (lane < 3) {
-    const SweptBoxes b = swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; });
-    info[36 + lane] = b.lo; info[39 + lane] = b.hi; info[42 + lane] = b.lo2; info[45 + lane] = b.hi2;
-    xf_store(D.cbox + ((size_t)tr * 6 + lane) * D.U + u, b.lo2); xf_store(D.cbox + ((size_t)tr * 6 + 3 + lane) * D.U + u, b.hi2);
-  }
+  if (lane < 3) swept_put_boxes(D, info, u, tr, lane, swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; }), put, xf_store);
   if (lane < 49) {
     double up = -INFINITY, lo = INFINITY;
     kdop_interval6(kx, ky, kz, P, lo, up);
     kdop_interval6(kx, ky, kz, PS, lo, up);
-    info[48 + lane] = lo; info[97 + lane] = up;
+    swept_put_interval(info, lane, lo, up, put);
   }
   blk_sync<true>();
-  double* o = D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE;
+  double* o = swept_record(D, u, tr);
   for (int i = lane; i < CCD_REC; i += 64) xf_store(o + i, info[i]);
 }
 
@@ -163,7 +155,15 @@ __global__ __launch_bounds__(64) void k_xch_wait(Dev D, int kind) {
   if (!poll_until<4>([&] { if (mine) got = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return ballot(got < need) == 0ull; }, WAIT_2S)) wait_failed(D, ERR_PEER_TIMEOUT);
 }
 
-constexpr int CCD_LDS_DOUBLES = 294 + (2 * FRONT_CAP + 128) / 2;   // info[146] kax[147] | fa fb cand
+// THE clamp test of both CCD stages and the replay: are two bodies within `offset` (off2 = offset^2) of each other?  Wave-cooperative GJK, squared length of the witness
+// vector; written as <= so that a NaN is "not within" at every site (each back-off loop, which asks `while within`, ends on it).  Uniform result.
+template <class A, class B>
+__device__ __forceinline__ bool swept_within(const A& a, const B& b, double off2, int lane) {
+  const V3 v = gjk_wave(a, b, lane);
+  return v.x * v.x + v.y * v.y + v.z * v.z <= off2;
+}
+constexpr int CCD_INFO_DOUBLES = 2 * (CCD_REC + 1);   // the record's LDS copy `info` (ccd_record_async's hull scratch starts behind it, at CCD_REC + 2)
+constexpr int CCD_LDS_DOUBLES = CCD_INFO_DOUBLES + (2 * FRONT_CAP + 128) / 2;   // info | fa fb cand
 // the candidate a lane holds, handed to the whole wave
 __device__ __forceinline__ V3 bcast_v3(const V3& v, int l) { return V3{readlane_f64(v.x, l), readlane_f64(v.y, l), readlane_f64(v.z, l)}; }
 __device__ __forceinline__ BodyPoint bcast_body(const BodyPoint& b, int l) { return BodyPoint{bcast_v3(b.q, l)}; }
@@ -176,13 +176,13 @@ __device__ __forceinline__ void ccd_obs_body(const Dev& D, int bid, double* lds,
   const int u = D.u0 + bid / D.S, tr = bid % D.S;
   const int lane = lane_id();
   double* info = lds;
-  int* fa = (int*)(lds + 294); int* fb = fa + FRONT_CAP; int* cand = fb + FRONT_CAP;
+  int* fa = (int*)(lds + CCD_INFO_DOUBLES); int* fb = fa + FRONT_CAP; int* cand = fb + FRONT_CAP;
   bool kax_ready = false;
   V3 axv{0, 0, 0}; double lo_ax = 0, hi_ax = 0;
-  const double* src = D.ccdinfo + ((size_t)u * D.S + tr) * CCD_STRIDE;
+  const double* src = swept_record(D, u, tr);
   const TopBox topb = bvh_top_box(D);   // travels with the segment's record
   if (D.xs_async) {   // asynchronous Newton solve: the record is built here, once this robot's block (on the other queue) has left its direction
-    ccd_record_async(D, u, tr, lane, info, lds + 148);
+    ccd_record_async(D, u, tr, lane, info, lds + CCD_REC + 2);
     TJ_TIC(D, K_CCD, 4);
     xf_signal(D, 1, tr);   // (its write-through stores acknowledged) -> the pair tiles of the segment
     TJ_TIC(D, K_CCD, 5);
@@ -195,14 +195,14 @@ __device__ __forceinline__ void ccd_obs_body(const Dev& D, int bid, double* lds,
   for (int i = lane; i < CCD_REC; i += 64) info[i] = src[i];
   __syncthreads();
   QBox q;
-  for (int k = 0; k < 3; k++) { q.lo[k] = info[36 + k]; q.hi[k] = info[39 + k]; }
+  for (int k = 0; k < 3; k++) { q.lo[k] = info[CCD_OBOX + k]; q.hi[k] = info[CCD_OBOX + 3 + k]; }
   const double off = D.offset;
   unsigned long long visits = 0;
   int kmax = 0;
   const int found = bvh_query<1, PRIM>(D, q, off, fa, fb, cand, &visits, [&](int pt) {
     if (!kax_ready) {   // wave-uniform: this lane's axis and the swept hull's interval on it
       const int ax = min(lane, 48);
-      axv = V3{D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2]}; lo_ax = info[48 + ax]; hi_ax = info[97 + ax];
+      axv = V3{D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2]}; lo_ax = info[CCD_KLO + ax]; hi_ax = info[CCD_KHI + ax];
       kax_ready = true;
     }
     const int ncand = __popcll(ballot(pt >= 0));   // candidates sit in lanes [0, ncand)
@@ -216,7 +216,7 @@ __device__ __forceinline__ void ccd_obs_body(const Dev& D, int bid, double* lds,
         pm &= pm - 1ull;
         const typename PrimOf<PRIM>::Body qu = bcast_body(qb, l);
         while (k < STEP_CAP) {
-          const V3 v = gjk_wave(BodySwept{info, info + 18, D.pow08[k]}, qu, lane);
+          const V3 v = gjk_wave(swept_body(info, D.pow08[k]), qu, lane);   // swept_within, spelled out: through the helper this body took 8 more registers (k_ccd_lean<3> at its limit)
           if (!(v.x * v.x + v.y * v.y + v.z * v.z <= off * off)) break;
           k++;
         }
@@ -245,7 +245,9 @@ __global__ __launch_bounds__(64) void k_ccd_obs(Dev D) {
 // ONE global list as sortable keys; the replay kernel sorts it, so (segment, p0, p1) is a lexicographic, deterministic order.
 constexpr int ACT_CAP = 4096;                                    // acting pairs of one iteration (all segments)
 constexpr int ROBOT_BITS = 11;                                   // robot ids in packed pair keys: U <= 2048 (with S < 512 a key is 31 bits)
+struct ActPair { int tr, p0, p1; };
 __device__ __forceinline__ int act_key(int tr, int p0, int p1) { return (tr << (2 * ROBOT_BITS)) | (p0 << ROBOT_BITS) | p1; }
+__device__ __forceinline__ ActPair act_unkey(int key) { return ActPair{key >> (2 * ROBOT_BITS), (key >> ROBOT_BITS) & ((1 << ROBOT_BITS) - 1), key & ((1 << ROBOT_BITS) - 1)}; }
 // the survivors of the box + k-DOP filter one after the other by the whole wave (see ccd_obs_body)
 __device__ __forceinline__ int ccd_self_pairs_body(const Dev& D, int bid, double* lds, bool wait_xf = false) {   // returns the acting pairs this tile listed
   int tr, rb, cb;
@@ -257,7 +259,7 @@ __device__ __forceinline__ int ccd_self_pairs_body(const Dev& D, int bid, double
   if (wait_xf || D.xs_async) { xf_wait_seg(D, 1, tr); TJ_TIC(D, K_CCD, 6); }   // (asynchronous Newton solve: the obstacle units of this launch build the records once their robot's direction is there)   // sharded contexts (union kernel): the swept-hull cache of the other ranks' robots is written by units at the head of this launch
   // swept boxes (lanes over partners), then swept 49-axis intervals (lanes over axes): BVH::SelfCCDCollision + CCD::SelfKDOPCCD
   const int m = pair_tile_filter(D.cbox + (size_t)tr * 6 * U, U, rb, D.pair_rows, cb, 0, U,
-                                 [&](int q) { return D.ccdinfo + ((size_t)q * D.S + tr) * CCD_STRIDE; }, 48, 97, off, rowbox, list, lane);
+                                 [&](int q) { return swept_record(D, q, tr); }, CCD_KLO, CCD_KHI, off, rowbox, list, lane);
   if (m == 0) return 0;
   int found = 0;
   // A pair can only ever ACT in the sequential replay if its swept hulls are within `offset` at FULL step: hulls are
@@ -266,10 +268,7 @@ __device__ __forceinline__ int ccd_self_pairs_body(const Dev& D, int bid, double
   // colliding pairs only.
   for (int i = 0; i < m; i++) {   // (uniform)
     const int p0 = list[i] >> 16, p1 = list[i] & 0xffff;
-    const double* a = D.ccdinfo + ((size_t)p0 * D.S + tr) * CCD_STRIDE;
-    const double* b = D.ccdinfo + ((size_t)p1 * D.S + tr) * CCD_STRIDE;
-    const V3 v = gjk_wave(BodySwept{a, a + 18, D.pow08[0]}, BodySwept{b, b + 18, D.pow08[0]}, lane);
-    if (v.x * v.x + v.y * v.y + v.z * v.z <= off * off) {
+    if (swept_within(swept_body(swept_record(D, p0, tr), D.pow08[0]), swept_body(swept_record(D, p1, tr), D.pow08[0]), off * off, lane)) {
       found++;
       if (lane == 0) {
         const int w = atomicAdd(&D.ctl->any_pair, 1);   // any_pair = number of acting pairs this iteration
@@ -296,34 +295,43 @@ __global__ __launch_bounds__(64) void k_ccd_self_pairs(Dev D) {
 // segment) -- tj_iterate reports that as TJ_ERR_UNSUPPORTED instead of silently continuing.
 constexpr int SEQ_ACT_CAP = 256;   // acting pairs of ONE segment
 constexpr int SEQ_STK_CAP = 1024;  // node-pair stack of the tree's self query
-__host__ __device__ inline size_t seq_lds_bytes(int U, int S, bool with_tree) {
-  size_t b = (with_tree ? dyntree_lds_bytes(U) + 6 * (size_t)U * sizeof(double) : 0);
-  b += (size_t)U * sizeof(double);   // gnorm staging
-  b += (2 * (size_t)U + ACT_CAP + 3 * SEQ_ACT_CAP + (with_tree ? 2 * SEQ_STK_CAP : 0)) * sizeof(int);
-  (void)S;
-  return b;
-}
-// where the replay keeps its arrays: the stand-alone kernel carves everything from its dynamic LDS; folded into the tail of
-// k_ccd (below) the small arrays live in that kernel's static buffer and the tree -- touched by lane 0 only, and only when two
-// acting pairs of a segment share a robot -- in global memory
+// where the replay (and gnorm_form's staging) keeps its arrays
 struct SeqMem {
   double *tbox, *tarea, *bx, *gns;   // tree nodes [12U], [2U]; swept boxes of the segment [6U]; gnorm staging [U]
   int *ti, *ks, *seen, *keys, *act0, *act1, *ord, *stk;
   int key_cap;        // acting pairs the sort can hold (a power of two)
   bool lane0_stages;  // bx is global memory: lane 0 copies the boxes itself (no cross-lane traffic through global memory)
 };
-// doubles of k_ccd's static buffer the folded replay needs, and what the tree needs in global memory
-__host__ __device__ inline size_t seq_fold_lds_bytes(int U, int key_cap) { return (size_t)U * sizeof(double) + (2 * (size_t)U + key_cap + 3 * SEQ_ACT_CAP) * sizeof(int); }
-__host__ __device__ inline size_t seq_fold_gmem_doubles(int U) { return 20 * (size_t)U; }
-__host__ __device__ inline size_t seq_fold_gmem_ints(int U) { return 10 * (size_t)U + 2 * SEQ_STK_CAP; }
+// THE description of those arrays: three arenas -- the tree's doubles, the tree's ints (touched by lane 0 only, and only when two acting pairs of a segment share a
+// robot) and the small arrays.  The stand-alone kernel lays the three end to end in its dynamic LDS (lds_bytes); folded into the tail of k_ccd (below) the small
+// arena is that kernel's static buffer (small_bytes must fit it: plan_context chooses key_cap so) and the tree's arenas are global memory (Dev::seq_gmem_d / _i).
+struct SeqLayout {
+  size_t tbox, tarea, bx, tree_doubles;                   // offsets in the tree's doubles, and their number
+  size_t ti, stk, tree_ints;                              // offsets in the tree's ints ([5][2U] parent, left, right, height, particle; node-pair stack), and their number
+  size_t ks, seen, act0, act1, ord, keys, small_bytes;    // small arena: gns [U] doubles at 0, then ints (offsets in ints from the arena's start); its bytes, a multiple of 8
+  int key_cap;
+  __host__ __device__ __forceinline__ SeqLayout(int U, int key_cap_, bool with_tree) : key_cap(key_cap_) {
+    const size_t u = (size_t)U, t = with_tree ? 1 : 0;
+    tbox = 0; tarea = tbox + t * 12 * u; bx = tarea + t * 2 * u; tree_doubles = bx + t * 6 * u;
+    ti = 0; stk = ti + t * 10 * u; tree_ints = stk + t * 2 * SEQ_STK_CAP;
+    ks = 2 * u; seen = ks + u; act0 = seen + u; act1 = act0 + SEQ_ACT_CAP; ord = act1 + SEQ_ACT_CAP; keys = ord + SEQ_ACT_CAP;
+    small_bytes = (keys + (size_t)key_cap) * sizeof(int);
+  }
+  __host__ __device__ size_t lds_bytes() const { return tree_doubles * sizeof(double) + small_bytes + tree_ints * sizeof(int); }
+  __device__ __forceinline__ SeqMem carve(double* tree_d, int* tree_i, double* small, bool lane0_stages) const {
+    int* si = (int*)small;
+    return SeqMem{tree_d + tbox, tree_d + tarea, tree_d + bx, small, tree_i + ti, si + ks, si + seen, si + keys, si + act0, si + act1, si + ord, tree_i + stk, key_cap, lane0_stages};
+  }
+  __device__ __forceinline__ SeqMem carve_lds(double* lds) const { return carve(lds, (int*)((char*)(lds + tree_doubles) + small_bytes), lds + tree_doubles, false); }   // doubles first (alignment)
+};
 
-// FOLD: called by the last block of k_ccd to finish (decoupled mode only); what other blocks of the SAME launch produced --
+// The replay, and nothing else (gnorm: gnorm_form, below).  FOLD: called by k_ccd's finisher; what other blocks of the SAME launch produced --
 // the acting-pair keys and their count -- is read with agent-scope atomic loads (the producers store them that way and wait
-// for the stores before they take their ticket).
+// for the stores before they count themselves in).
 template <bool FOLD>
-__device__ __forceinline__ void ccd_self_seq_body(const Dev& D, const SeqMem& M, bool with_gnorm = true) {
+__device__ __forceinline__ void ccd_self_seq_body(const Dev& D, const SeqMem& M) {
   const int lane = lane_id();
-  double* tbox = M.tbox; double* tarea = M.tarea; double* bx = M.bx; double* gns = M.gns;
+  double* tbox = M.tbox; double* tarea = M.tarea; double* bx = M.bx;
   int* ti = M.ti; int* ks = M.ks; int* seen = M.seen; int* keys = M.keys;
   int* act0 = M.act0; int* act1 = M.act1; int* ord = M.ord; int* stk = M.stk;
   TJ_TIC(D, K_CCD_SELF_SEQ, 0);
@@ -361,10 +369,10 @@ __device__ __forceinline__ void ccd_self_seq_body(const Dev& D, const SeqMem& M,
     int ambiguous = 0, unresolved = 0;
     for (int pos = 0; pos < n_act;) {
       // 1. this segment's acting pairs, lexicographic (p0, p1); does any robot appear twice?
-      const int tr = keys[pos] >> (2 * ROBOT_BITS);
+      const int tr = act_unkey(keys[pos]).tr;
       int m = 0; bool share = false;
-      while (pos < n_act && (keys[pos] >> (2 * ROBOT_BITS)) == tr) {
-        const int p0 = (keys[pos] >> ROBOT_BITS) & ((1 << ROBOT_BITS) - 1), p1 = keys[pos] & ((1 << ROBOT_BITS) - 1);
+      while (pos < n_act && act_unkey(keys[pos]).tr == tr) {
+        const int p0 = act_unkey(keys[pos]).p0, p1 = act_unkey(keys[pos]).p1;
         if (seen[p0] == tr || seen[p1] == tr) share = true;
         blk_sync<true>();
         if (lane == 0) { seen[p0] = tr; seen[p1] = tr; if (m < SEQ_ACT_CAP) { act0[m] = p0; act1[m] = p1; } }
@@ -394,13 +402,12 @@ __device__ __forceinline__ void ccd_self_seq_body(const Dev& D, const SeqMem& M,
       for (int j = 0; j < m; j++) {
         const int i = tree_order ? ord[j] : j;
         const int p0 = act0[i], p1 = act1[i];
-        const double* a = D.ccdinfo + ((size_t)p0 * D.S + tr) * CCD_STRIDE;
-        const double* b = D.ccdinfo + ((size_t)p1 * D.S + tr) * CCD_STRIDE;
+        const double* a = swept_record(D, p0, tr);
+        const double* b = swept_record(D, p1, tr);
         int k0 = ks[shared ? 0 : p0], k1 = ks[shared ? 0 : p1];
         int guard = 0;
         while (guard++ < STEP_CAP) {
-          const V3 v = gjk_wave(BodySwept{a, a + 18, D.pow08[min(k0, STEP_CAP)]}, BodySwept{b, b + 18, D.pow08[min(k1, STEP_CAP)]}, lane);  // the wave is uniform here: solve the pair cooperatively
-          if (!(v.x * v.x + v.y * v.y + v.z * v.z <= off2)) break;
+          if (!swept_within(swept_body(a, D.pow08[min(k0, STEP_CAP)]), swept_body(b, D.pow08[min(k1, STEP_CAP)]), off2, lane)) break;  // the wave is uniform here: solve the pair cooperatively
           k0++; k1++;
         }
         if (guard > STEP_CAP && lane == 0) atomicOr(&D.ctl->error, ERR_LOOP_CAP | ERR_CCD_STUCK);
@@ -418,22 +425,24 @@ __device__ __forceinline__ void ccd_self_seq_body(const Dev& D, const SeqMem& M,
     const int kshared = ks[0];
     __syncthreads();
     for (int i = lane; i < D.U; i += 64) { D.k_self[i] = D.coupled() ? kshared : ks[i]; seen[i] = 0; }
-    if constexpr (!FOLD) if (D.coupled()) for (int i = D.u0 + lane; i < D.u1; i += 64) D.k_obs_f[i] = (double)D.k_obs[i];   // exchange buffer 3 (sharded contexts)
   }
-  if (!with_gnorm) return;
-  // gnorm exactly as the drivers form it (Optimization3D_multi.h:57,72,750; _admm.h:499): a
-  // sequential sum in robot order; the values are first pulled into LDS by all lanes
+}
+// gnorm exactly as the drivers form it (Optimization3D_multi.h:57,72,750; _admm.h:499): a sequential sum in robot order (decoupled: the mean of the robots' |g|; single UAV:
+// the robot's), the values first pulled into LDS (gns [U]) by all lanes.  Coupled mode: gnorm = |G| / uav_num and wolfe_c = -x0.G over the whole arrowhead system
+// (Optimization3D_multi.h:558,580) -- k_xsolve_c2 left per-robot partial sums, the shared-time entries are fetched by the lanes (one round trip per 64 robots) and added
+// by lane 0 in robot order.  One wave.  ld: how a per-robot value is fetched -- plainly, or past the caches where another queue or this launch wrote it.
+template <class Ld>
+__device__ __forceinline__ void gnorm_form(const Dev& D, double* gns, int lane, Ld&& ld) {
   __syncthreads();
-  for (int i = lane; i < D.U; i += 64) gns[i] = D.gn(i);
+  for (int i = lane; i < D.U; i += 64) gns[i] = ld(&D.gn(i));
   __syncthreads();
-  TJ_TIC(D, K_CCD_SELF_SEQ, 3);
   double gt = 0, xg = 0;
-  if constexpr (!FOLD) if (D.coupled()) {   // per-robot terms of G_t and x0.G: fetched by the lanes (one round trip per 64 robots), added by lane 0 in robot order
+  if (D.coupled()) {
     __shared__ double s_cp[2][64];
     for (int u0 = 0; u0 < D.U; u0 += 64) {
       const int nu = min(64, D.U - u0);
       __syncthreads();
-      if (lane < nu) { s_cp[0][lane] = D.xdir[(size_t)(u0 + lane) * D.xs + 3 * D.T + 3]; s_cp[1][lane] = D.wolfe(u0 + lane); }
+      if (lane < nu) { s_cp[0][lane] = ld(D.xdir + (size_t)(u0 + lane) * D.xs + 3 * D.T + 3); s_cp[1][lane] = ld(&D.wolfe(u0 + lane)); }
       __syncthreads();
       if (lane == 0) for (int j = 0; j < nu; j++) { gt += s_cp[0][j]; xg += s_cp[1][j]; }
     }
@@ -441,54 +450,25 @@ __device__ __forceinline__ void ccd_self_seq_body(const Dev& D, const SeqMem& M,
   if (lane == 0) {
     double gsum = 0;
     for (int u = 0; u < D.U; u++) gsum += gns[u];
-    if (!FOLD && D.coupled()) {
-      // gnorm = |G| / uav_num and wolfe = -x0.G over the whole arrowhead system (Optimization3D_multi.h:558,580);
-      // k_xsolve_c2 left per-robot partial sums, the shared-time entries are added here
+    if (D.coupled()) {
       D.ctl->gnorm = sqrt(gsum + gt * gt) / double(D.U);
-      D.ctl->wolfe_c = -(xg + D.tdir(0) * gt);
+      D.ctl->wolfe_c = -(xg + ld(&D.tdir(0)) * gt);
     } else D.ctl->gnorm = (D.mode == 1) ? gsum / double(D.U) : gns[0];
   }
-  TJ_TIC(D, K_CCD_SELF_SEQ, 4);
+  __syncthreads();
 }
 __global__ __launch_bounds__(64) void k_ccd_self_seq(Dev D) {
   if (TJ_DONE(D)) return;
   extern __shared__ double seq_sm[];
-  // doubles first (alignment): tree nodes + the segment's swept boxes + gnorm staging, then the int arrays
-  SeqMem M;
-  M.tbox = seq_sm; M.tarea = M.tbox + (D.seq_tree ? 12 * (size_t)D.U : 0); M.bx = M.tarea + (D.seq_tree ? 2 * (size_t)D.U : 0);
-  M.gns = M.bx + (D.seq_tree ? 6 * (size_t)D.U : 0);               // [U]
-  M.ti = (int*)(M.gns + D.U);                                        // [5][2U] parent, left, right, height, particle
-  M.ks = M.ti + (D.seq_tree ? 10 * (size_t)D.U : 0);                // [U] exponents
-  M.seen = M.ks + D.U;                                               // [U] last segment in which the robot appeared
-  M.keys = M.seen + D.U;                                             // [ACT_CAP] acting pairs, sorted
-  M.act0 = M.keys + ACT_CAP; M.act1 = M.act0 + SEQ_ACT_CAP; M.ord = M.act1 + SEQ_ACT_CAP;
-  M.stk = M.ord + SEQ_ACT_CAP;
-  M.key_cap = ACT_CAP; M.lane0_stages = false;
+  const SeqMem M = SeqLayout(D.U, ACT_CAP, D.seq_tree != 0).carve_lds(seq_sm);
   ccd_self_seq_body<false>(D, M);
+  if (D.coupled()) for (int i = D.u0 + lane_id(); i < D.u1; i += 64) D.k_obs_f[i] = (double)D.k_obs[i];   // exchange buffer 3 (sharded contexts)
+  TJ_TIC(D, K_CCD_SELF_SEQ, 3);
+  gnorm_form(D, M.gns, lane_id(), [](const double* p) { return *p; });
+  TJ_TIC(D, K_CCD_SELF_SEQ, 4);
 }
 
 // ---- slack (z) and dual update -------------------------------------------------------------------
-__device__ inline double z_energy(const Dev& D, const double* cx, double pt, const double* z, double t, const double* lam, double tl) {
-  // Energy_admm::slack_energy / dynamic_energy (Energy_admm.h:172-215)
-  double e = 0;
-  const double s = D.ks / pow5(t) * 0.5;
-  for (int a = 0; a < 3; a++) {
-    double rrow[6], y[6];
-    for (int k = 0; k < 6; k++) rrow[k] = s * z[k + 6 * a];
-    for (int j = 0; j < 6; j++) { double acc = 0; for (int k = 0; k < 6; k++) acc += rrow[k] * D.mdyn[k * 6 + j]; y[j] = acc; }
-    double q = 0; for (int j = 0; j < 6; j++) q += y[j] * z[j + 6 * a];
-    e += q;
-  }
-  e = e + D.kt * pow(t, 1.1);
-  double delta[18], prod[18];
-  for (int i = 0; i < 18; i++) { delta[i] = cx[i] - z[i]; prod[i] = delta[i] * delta[i]; }
-  e += D.mu / 2.0 * esum(prod, 18);
-  e += D.mu / 2.0 * (pt - t) * (pt - t);
-  for (int a = 0; a < 3; a++) { double pr[6]; for (int j = 0; j < 6; j++) pr[j] = lam[j + 6 * a] * delta[j + 6 * a]; e += esum(pr, 6); }
-  e += tl * (pt - t);
-  return e;
-}
-
 // ---- register forms of the slack system's factorisation (EXACT: IEEE sqrt / division, unfused a - l*l -- the same operations
 // in the same order as chol_lds / chol_arrow_backsolve_lds, whose pass/fail decision is pinned to Eigen's unblocked LLT) ----
 template <int N>
@@ -532,26 +512,36 @@ __device__ __noinline__ bool slack_solve_wave(double* L, double* x0, int lane) {
   return true;
 }
 
-// z_energy by one wave: the same sums in the same order, the independent pieces side by side on the lanes.  pw = pow(t, 1.1)
-// (taken by the caller, several arguments per pass on different lanes); w18: LDS scratch [36].  Uniform result.
-__device__ __forceinline__ double z_energy_wave(const Dev& D, const double* md, const double* cx, double pt, const double* z, double t, const double* lam, double tl,
-                                                double pw, double* w18, int lane) {
-  const double s = D.ks / pow5(t) * 0.5;
+// sum over the three axes of (s z_a)^T M z_a (Energy_admm::dynamic_energy's quadratic form, Energy_admm.h:172-215), by one wave, in two steps so that a caller can
+// put other work between them: slack_dyn_rows -- lane (a, j) forms y_j = ((s z_a)^T M)_j of axis a --, then slack_dyn_sum combines the products uniformly in the
+// reference's order.  z [18], md [36]: LDS.  Uniform result.
+__device__ __forceinline__ double slack_dyn_rows(const double* md, const double* z, double s, int lane) {
   const int a = min(lane, 17) / 6, j = min(lane, 17) % 6;
   double y = 0;
 #pragma unroll
-  for (int k = 0; k < 6; k++) y += (s * z[k + 6 * a]) * md[k * 6 + j];      // lane (a, j): y_j of axis a
-  const double delta = cx[min(lane, 17)] - z[min(lane, 17)];
-  blk_sync<true>();
-  if (lane < 18) { w18[lane] = delta * delta; w18[18 + lane] = lam[lane] * delta; }
-  double e = 0;
+  for (int k = 0; k < 6; k++) y += (s * z[k + 6 * a]) * md[k * 6 + j];
+  return y;
+}
+__device__ __forceinline__ double slack_dyn_sum(double y, const double* z) {
+  double dyn = 0;
 #pragma unroll
   for (int ax = 0; ax < 3; ax++) {
     double q = 0;
 #pragma unroll
     for (int jj = 0; jj < 6; jj++) q += readlane_f64(y, 6 * ax + jj) * z[jj + 6 * ax];
-    e += q;
+    dyn += q;
   }
+  return dyn;
+}
+// Energy_admm::slack_energy / dynamic_energy (Energy_admm.h:172-215) by one wave: the reference's sums in its order, the independent pieces side by side on the lanes.
+// pw = pow(t, 1.1) (taken by the caller, several arguments per pass on different lanes); w18: LDS scratch [36].  Uniform result.
+__device__ __forceinline__ double z_energy_wave(const Dev& D, const double* md, const double* cx, double pt, const double* z, double t, const double* lam, double tl,
+                                                double pw, double* w18, int lane) {
+  const double y = slack_dyn_rows(md, z, D.ks / pow5(t) * 0.5, lane);
+  const double delta = cx[min(lane, 17)] - z[min(lane, 17)];
+  blk_sync<true>();
+  if (lane < 18) { w18[lane] = delta * delta; w18[18 + lane] = lam[lane] * delta; }
+  double e = slack_dyn_sum(y, z);
   e = e + D.kt * pw;
   blk_sync<true>();
   e += D.mu / 2.0 * esum_wave(w18, 18, lane);
@@ -569,13 +559,15 @@ __device__ __forceinline__ double z_energy_wave(const Dev& D, const double* md, 
 // per lane, v_readlane broadcasts: the LDS form pays three barriers per pivot) -> Armijo search with the objective evaluated by
 // the whole wave (z_energy_wave) and every pow() of a pass taken on different lanes at once (the scalar loop on one lane was
 // a third of the 27 us this body took; it is the whole of k_mid for one or a few robots).
-constexpr int SLACK_LDS_DOUBLES = 5 * 18 + 19 + 2 * 361 + 2 * 19 + 4 * 19 + 36 + 36;   // 1017
+// slack_body's LDS, one statement: every array starts where its predecessor ends, and SLACK_LDS_DOUBLES is where the last one does
+constexpr int SL_CX = 0, SL_Z = SL_CX + 18, SL_LAM = SL_Z + 18, SL_ZT = SL_LAM + 18, SL_DIRZ = SL_ZT + 18, SL_G = SL_DIRZ + 18, SL_H = SL_G + 19, SL_L = SL_H + 361, SL_G0 = SL_L + 361,
+              SL_X0 = SL_G0 + 19, SL_SCR = SL_X0 + 19, SL_MD = SL_SCR + 4 * 19, SL_W18 = SL_MD + 36, SLACK_LDS_DOUBLES = SL_W18 + 36;   // 1017
 __device__ __forceinline__ void slack_body(const Dev& D, int bid, int deferred, double* lds) {   // lds: SLACK_LDS_DOUBLES doubles the KERNEL owns (k_mid overlays them with the pair tile)
   const int tid = threadIdx.x;
   const int u = D.u0 + bid / D.P, sp = bid % D.P;
   const int P6 = 6 * D.P, T = D.T;
-  double* cx = lds; double* z = cx + 18; double* lam = z + 18; double* zt = lam + 18; double* dirz = zt + 18; double* g = dirz + 18; double* H = g + 19; double* L = H + 361;
-  double* g0 = L + 361; double* x0 = g0 + 19; double* scr = x0 + 19; double* md = scr + 4 * 19; double* w18 = md + 36;
+  double* cx = lds + SL_CX; double* z = lds + SL_Z; double* lam = lds + SL_LAM; double* zt = lds + SL_ZT; double* dirz = lds + SL_DIRZ; double* g = lds + SL_G; double* H = lds + SL_H;
+  double* L = lds + SL_L; double* g0 = lds + SL_G0; double* x0 = lds + SL_X0; double* scr = lds + SL_SCR; double* md = lds + SL_MD; double* w18 = lds + SL_W18;
   const double* net = D.spline + (size_t)u * 3 * T;
   const double* C = D.convert + (size_t)sp * 36;
   const double pt = D.piece_time[u];
@@ -608,20 +600,8 @@ __device__ __forceinline__ void slack_body(const Dev& D, int bid, int deferred, 
     H[tid * 19 + 18] = pg; H[18 * 19 + tid] = pg;
     for (int b = 0; b < 6; b++) H[tid * 19 + 3 * b + a] = sc * md[k * 6 + b] + (k == b ? D.mu : 0.0);
   }
-  {  // time entries: the quadratic form z^T M z per axis on lanes (a, j) like z_energy_wave, combined uniformly
-    const double s = sc * 0.5;
-    const int a = min(tid, 17) / 6, j = min(tid, 17) % 6;
-    double y = 0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) y += (s * z[k + 6 * a]) * md[k * 6 + j];
-    double dyn = 0;
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) {
-      double q = 0;
-#pragma unroll
-      for (int jj = 0; jj < 6; jj++) q += readlane_f64(y, 6 * ax + jj) * z[jj + 6 * ax];
-      dyn += q;
-    }
+  {  // time entries, from the dynamic energy's quadratic form
+    const double dyn = slack_dyn_sum(slack_dyn_rows(md, z, sc * 0.5, tid), z);
     double g_t = -5 * dyn / t;
     g_t += D.kt * 1.1 * pw01;
     double h_t = 30 * dyn / (t * t);
@@ -713,6 +693,48 @@ __global__ __launch_bounds__(64) void k_slack(Dev D, int deferred) {
 // FA (asynchronous front, dev_common.h Dev::fa_seq): this launch runs on the second queue NEXT TO the previous iteration's k_linesearch (behind k_fa_gate).  Stop flag
 // and epoch come from fa_early_begin's record -- the control block still belongs to the running iteration --, units wait for their robots' commit flags, every
 // store a later kernel reads is written through, and each block counts itself done behind them (the last k_linesearch block waits for that count).
+// ---- which block runs which body: one layout per union kernel, built from Dev on both sides of the launch.  The kernel picks its body through it, plan_grids and
+// launch_kernel (host_plan.h, tj_api.hip) take the grid from it (k_ccd decodes the same ranges by hand, see ccd_union_body).  Fields are the ENDS of the ranges in grid order; total() is the grid.
+__host__ __device__ __forceinline__ int owned_segments(const Dev& d) { return (d.u1 - d.u0) * d.S; }                                   // obstacle units of k_front / k_ccd: one per owned (robot, segment)
+// the pair tiles are the LAST range of k_front and k_ccd: one wave per (segment, tile of pair_rows lower robots x 64 partners).  Their number takes integer divisions
+// (pair_units) that no block needs to pick its body, so a layout keeps the operands and forms tiles() / total() where they are asked for: the host and k_ccd's finisher
+// (computed in CcdLayout's constructor, the divisions stood in front of every block's dispatch)
+struct PairTiles {
+  int S, U, rows;   // S = 0: no robot pairs
+  __host__ __device__ __forceinline__ explicit PairTiles(const Dev& d) : S(d.multi() ? d.S : 0), U(d.U), rows(d.pair_rows) {}
+  __host__ __device__ __forceinline__ int count() const { return S ? S * pair_units(U, rows) : 0; }
+};
+struct FrontLayout {   // order blocks | foreign units | head starts | obstacle units | pair tiles
+  int ord, xf, spec, obs; PairTiles pt;
+  __host__ __device__ __forceinline__ int total() const { return obs + pt.count(); }
+  __host__ __device__ __forceinline__ explicit FrontLayout(const Dev& d) : pt(d) {
+    ord = d.grad_bal ? ((d.u1 - d.u0) * d.P + 63) / 64 : 0;   // launch order of this iteration's k_grad (kernels_newton.h; ~3 us each -- as the LAST blocks they started when the first query blocks retired and ended 1 us after everything else)
+    xf = ord + d.xf_units();                                  // sharded contexts: hull cache of the other ranks' robots, AHEAD of everything that reads it (head starts, pair tiles)
+    spec = xf + (d.spec ? SPEC_CAP : 0);                      // GJK head starts of last iteration's slow pairs: they are the longest blocks
+    obs = spec + owned_segments(d);
+  }
+};
+struct MidLayout {   // [watcher] | slack | pair waves | obstacle solves -- or, Dev::mid_order, [watcher] | pair waves | obstacle solves | slack (see k_mid)
+  enum Body { SLACK, PAIR, OBS };
+  __host__ __device__ __forceinline__ static int slack_blocks(const Dev& d) { return (d.u1 - d.u0) * d.P; }   // one per owned (robot, piece)
+  int watcher, slack0, n_slack, pair0, n_pair, obs0, n_obs, total;   // watcher: 1 if block 0 is the asynchronous front's watcher; the bodies' first blocks count from behind it
+  __host__ __device__ __forceinline__ MidLayout(const Dev& d, int n_pair_waves, int n_obs_waves, bool with_watcher, bool slack_last) {   // slack_last: Dev::mid_order
+    watcher = with_watcher ? 1 : 0; n_slack = slack_blocks(d); n_pair = n_pair_waves; n_obs = n_obs_waves;
+    pair0 = slack_last ? 0 : n_slack; obs0 = pair0 + n_pair; slack0 = slack_last ? obs0 + n_obs : 0;
+    total = watcher + n_slack + n_pair + n_obs;
+  }
+  __host__ __device__ __forceinline__ Body body(int b) const { return (unsigned)(b - slack0) < (unsigned)n_slack ? SLACK : ((unsigned)(b - pair0) < (unsigned)n_pair ? PAIR : OBS); }   // b: block index behind the watcher
+};
+struct CcdLayout {   // [finisher] | foreign units | obstacle units | pair tiles
+  int fin, xf, obs; PairTiles pt;
+  __host__ __device__ __forceinline__ explicit CcdLayout(const Dev& d) : pt(d) {
+    fin = d.seq_fold ? 1 : 0;        // the replay folded in: block 0 is the finisher and has no other work
+    xf = fin + d.xf_units();         // sharded contexts: swept-hull cache of the other ranks' robots (coupled chain: of every robot), ahead of what reads it
+    obs = xf + owned_segments(d);
+  }
+  __host__ __device__ __forceinline__ int tiles() const { return pt.count(); }
+  __host__ __device__ __forceinline__ int total() const { return obs + tiles(); }
+};
 template <int PRIM, bool FA = false>
 __global__ __launch_bounds__(64) void k_front(Dev D) {
   if (D.keep_seq > 0 && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(D.keep_go(), D.keep_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // opens the gate of the asynchronous plane refinement
@@ -722,22 +744,17 @@ __global__ __launch_bounds__(64) void k_front(Dev D) {
     fa_epoch = xf_load_i(D.fa_rec() + 1);
     if (xf_load_i(D.fa_rec() + 2) | (D.ctl->error & ERR_XS_TIMEOUT)) { fa_count(D.fa_fdone(blockIdx.x)); return; }   // (the begun iteration's stop test has fired, or a cross-queue wait has run out: the batch is being abandoned)
   } else if (TJ_DONE(D)) return;
-  const int n_obs = (D.u1 - D.u0) * D.S;
   TJ_TIC(D, K_FRONT, 0);
   __shared__ double lds[OBS_LDS_DOUBLES > PAIR_LDS_DOUBLES ? OBS_LDS_DOUBLES : PAIR_LDS_DOUBLES];   // one buffer for whichever body this block runs
   static_assert(sizeof(lds) >= GRAD_ORDER_CHUNK * sizeof(int), "grad_order_body stages its costs in this buffer");
-  const int n_spec = D.spec ? SPEC_CAP : 0;   // GJK head starts of last iteration's slow pairs lead the grid: they are the longest blocks
-  const int n_ord = D.grad_bal ? ((D.u1 - D.u0) * D.P + 63) / 64 : 0;   // the first blocks of the grid: launch order of this iteration's k_grad (kernels_newton.h; ~3 us each --
-                                                                        // as the LAST blocks they started when the first query blocks retired and ended 1 us after everything else)
-  const int n_xf = D.xf_units();   // sharded contexts: hull cache of the other ranks' robots (coupled chain: of every robot), AHEAD of everything that reads it (head starts, pair tiles)
+  const FrontLayout L(D);
   const int bx = (int)blockIdx.x;
-  const int b = bx - n_ord - n_xf - n_spec;
   const bool pub = D.xf_all != 0 || (D.fa_units != 0 && D.multi());   // the query forms its hull itself and publishes the record (coupled chain; Dev::fa_units: the k_linesearch before this launch published none)
-  if (bx < n_ord) grad_order_body<FA>(D, bx, (int*)lds);
-  else if (bx < n_ord + n_xf) xf_hull_body(D, bx - n_ord);
-  else if (b < 0) spec_pair_body<FA>(D, bx - n_ord - n_xf, lds, fa_epoch);
-  else if (b < n_obs) obs_query_body<PRIM, FA>(D, b, lds, !pub, pub);
-  else sep_self_rows_body<FA>(D, b - n_obs, lds, D.xf != 0 || D.fa_units != 0);
+  if (bx < L.ord) grad_order_body<FA>(D, bx, (int*)lds);
+  else if (bx < L.xf) xf_hull_body(D, bx - L.ord);
+  else if (bx < L.spec) spec_pair_body<FA>(D, bx - L.xf, lds, fa_epoch);
+  else if (bx < L.obs) obs_query_body<PRIM, FA>(D, bx - L.spec, lds, !pub, pub);
+  else sep_self_rows_body<FA>(D, bx - L.obs, lds, D.xf != 0 || D.fa_units != 0);
   TJ_TIC(D, K_FRONT, 1);
   if constexpr (FA) fa_count(D.fa_fdone(blockIdx.x));
 }
@@ -751,11 +768,23 @@ __global__ __launch_bounds__(64) void k_fa_gate(Dev D, int want) { fa_wait16(D, 
 // FA (asynchronous front, Dev::fa_mid): this launch started while the iteration's k_front was still running on the other queue.  Block 0 is the WATCHER: it polls k_front's
 // done counters (every block of it counts itself behind its acknowledged write-through stores) and then raises the 64 go words; a pair / obstacle solve wave sleeps on
 // one of them before it touches anything k_front leaves, and reads that past the caches.  The slack blocks start at once.
+// block b (counted from behind the watcher) of k_mid runs its body.  SLACK_LAST: the grid order, a compile-time copy of Dev::mid_order -- k_mid instantiates the dispatch once per
+// order, so that each order's block arithmetic folds into the body it selects as it did when the two orders were written out (k_mid sits 20 registers under its limit)
+template <int PRIM, bool FA, bool SLACK_LAST>
+__device__ __forceinline__ void mid_dispatch(const Dev& D, int b, int n_pair_waves, int n_obs_waves, double* mid_lds) {
+  const MidLayout L(D, n_pair_waves, n_obs_waves, FA, SLACK_LAST);
+  const MidLayout::Body body = L.body(b);
+  if (body == MidLayout::SLACK) { if (D.ctl->slack_now) slack_body(D, b - L.slack0, 1, mid_lds); TJ_TIC(D, K_MID, 1); return; }
+  if (TJ_DONE(D)) return;
+  if (body == MidLayout::PAIR) sep_self_solve_body<FA>(D, b - L.pair0, n_pair_waves, D.spec != 0, mid_lds);   // (FA: waits for k_front's end itself -- a dedicated wave after its early solve)
+  else { if constexpr (FA) { fa_wait_flag(D, D.fa_go(b), D.fa_seq); if constexpr (!SLACK_LAST) TJ_TIC(D, K_MID, 4); } obs_solve_body<PRIM, FA>(D, b - L.obs0, n_obs_waves); }
+  TJ_TIC(D, K_MID, 1);
+}
 template <int PRIM, bool FA = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_mid(Dev D, int n_pair_waves, int n_obs_waves) {
-  const int n_slack = (D.u1 - D.u0) * D.P;
+  constexpr int watcher = FA ? 1 : 0;   // MidLayout::watcher
   if constexpr (FA) {
-    if (blockIdx.x == 0) {
+    if ((int)blockIdx.x < watcher) {
       fa_wait16(D, D.fa_fdone(0), (int)((unsigned)D.fa_seq * (unsigned)D.fa_nfront));
       sig_acked();   // (nothing of its own to acknowledge: the watcher only relays k_front's count)
       xf_store_i(D.fa_go(threadIdx.x), D.fa_seq);
@@ -763,7 +792,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       return;
     }
   }
-  const int b = (int)blockIdx.x - (FA ? 1 : 0);
+  const int b = (int)blockIdx.x - watcher;
   TJ_TIC(D, K_MID, 0);
 #ifdef TJ_PHASE_TIMING
   if (threadIdx.x == 0 && blockIdx.x < TJ_TIC_BLOCKS) {   // where the block runs: HW_ID (wave, SIMD, CU, SE) and XCC_ID
@@ -772,34 +801,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   }
 #endif
   __shared__ double mid_lds[SLACK_LDS_DOUBLES > PAIR_TILE_DOUBLES ? SLACK_LDS_DOUBLES : PAIR_TILE_DOUBLES];   // one buffer for whichever body this block runs: the slack system, or the pair tile
-  if (D.mid_order) {
-    // Hundreds of robots (TJ_MID_ORDER): pair waves | obstacle solves | slack.  Blocks b and b + 1024 share a SIMD (two waves per SIMD, 1 024 SIMDs); with the slack
-    // blocks leading, every producer wave of the one-pair-per-lane path had a slack wave as its mate and both took 80 - 100 us where they take 12 + 30 alone (phase
-    // stamps + HW_ID, round 5).  With the pair waves leading, a producer's mate is a consumer that spins until pairs are passed on, the obstacle solves fill the
-    // remaining slots and the slack waves follow as those retire: config 5's k_mid 76.5 -> 61 us.  Small fleets keep slack first (their k_mid is its slowest pair).
-    const int s0 = n_pair_waves + n_obs_waves;
-    if (b >= s0) { if (D.ctl->slack_now) slack_body(D, b - s0, 1, mid_lds); TJ_TIC(D, K_MID, 1); return; }
-    if (TJ_DONE(D)) return;
-    if (b < n_pair_waves) sep_self_solve_body<FA>(D, b, n_pair_waves, D.spec != 0, mid_lds);   // (FA: waits for k_front's end itself -- a dedicated wave after its early solve)
-    else { if constexpr (FA) fa_wait_flag(D, D.fa_go(b), D.fa_seq); obs_solve_body<PRIM, FA>(D, b - n_pair_waves, n_obs_waves); }
-    TJ_TIC(D, K_MID, 1);
-    return;
-  }
-  if (b < n_slack) { if (D.ctl->slack_now) slack_body(D, b, 1, mid_lds); TJ_TIC(D, K_MID, 1); return; }   // long single-wave tasks first
-  else if (TJ_DONE(D)) return;
-  if (b < n_slack + n_pair_waves) sep_self_solve_body<FA>(D, b - n_slack, n_pair_waves, D.spec != 0, mid_lds);   // (FA: waits for k_front's end itself -- a dedicated wave after its early solve)
-  else { if constexpr (FA) { fa_wait_flag(D, D.fa_go(b), D.fa_seq); TJ_TIC(D, K_MID, 4); } obs_solve_body<PRIM, FA>(D, b - n_slack - n_pair_waves, n_obs_waves); }
-  TJ_TIC(D, K_MID, 1);
+  // Small fleets: slack first (long single-wave tasks; their k_mid is its slowest pair).
+  // Hundreds of robots (Dev::mid_order, TJ_MID_ORDER): pair waves | obstacle solves | slack.  Blocks b and b + 1024 share a SIMD (two waves per SIMD, 1 024 SIMDs); with the slack
+  // blocks leading, every producer wave of the one-pair-per-lane path had a slack wave as its mate and both took 80 - 100 us where they take 12 + 30 alone (phase
+  // stamps + HW_ID, round 5).  With the pair waves leading, a producer's mate is a consumer that spins until pairs are passed on, the obstacle solves fill the
+  // remaining slots and the slack waves follow as those retire: config 5's k_mid 76.5 -> 61 us.
+  if (D.mid_order) mid_dispatch<PRIM, FA, true>(D, b, n_pair_waves, n_obs_waves, mid_lds);
+  else mid_dispatch<PRIM, FA, false>(D, b, n_pair_waves, n_obs_waves, mid_lds);
 }
 template <int PRIM>
 __device__ __forceinline__ void ccd_union_body(const Dev& D) {
-  const int n_obs = (D.u1 - D.u0) * D.S;
   __shared__ double lds[CCD_LDS_DOUBLES > PAIR_LDS_DOUBLES ? CCD_LDS_DOUBLES : PAIR_LDS_DOUBLES];
   int found = 0;
   TJ_TIC(D, K_CCD, 0);
-  // with the replay folded in (below) the grid has one block more: block 0 is the finisher and has no other work
-  const int fin = D.seq_fold ? 1 : 0;
-  const int n_xf = D.xf_units();   // sharded contexts: swept-hull cache of the other ranks' robots (coupled chain: of every robot), ahead of what reads it
+  // CcdLayout's ranges, decoded by hand: [finisher] | foreign units | obstacle units | pair tiles.  Picked through the layout, k_ccd ran 1 us (SCN-C) to 2 us (SCN-D) longer
+  // per launch with the same bodies, registers and LDS; the host takes the grid from the layout.
+  const int n_obs = owned_segments(D);
+  const int fin = D.seq_fold ? 1 : 0;   // with the replay folded in (below) the grid has one block more: block 0 is the finisher and has no other work
+  const int n_xf = D.xf_units();        // sharded contexts: swept-hull cache of the other ranks' robots (coupled chain: of every robot), ahead of what reads it
   const int b = (int)blockIdx.x - fin - n_xf;
   if ((int)blockIdx.x >= fin && b < 0) xf_ccd_body(D, (int)blockIdx.x - fin, lds);
   else if (b >= 0 && b < n_obs) ccd_obs_body<PRIM>(D, b, lds, D.xf_all != 0);
@@ -816,7 +835,7 @@ __device__ __forceinline__ void ccd_union_body(const Dev& D) {
   // in.  Their sum also tells it whether any pair acts: none, almost always, and then it is done (k_begin has zeroed k_self).
   if (!D.seq_fold) return;
   const int lane = lane_id();
-  const int n_t = (int)gridDim.x - 1 - n_xf - n_obs;   // selection blocks
+  const int n_t = (int)gridDim.x - 1 - n_xf - n_obs;   // selection blocks = CcdLayout::tiles(), counted back from the grid the host took from the layout
   if (b >= n_obs) {
     sig_acked();
     if (lane == 0) atomicAdd(&D.ctl->ccd_sub[(b - n_obs) & 15], 1 + (found ? 0x10000 : 0));
@@ -824,44 +843,11 @@ __device__ __forceinline__ void ccd_union_body(const Dev& D) {
   }
   if (blockIdx.x != 0) return;
   __syncthreads();
-  SeqMem M;
-  M.gns = lds;                                   // [U]
-  M.ks = (int*)(lds + D.U); M.seen = M.ks + D.U;  // [U], [U]
-  M.act0 = M.seen + D.U; M.act1 = M.act0 + SEQ_ACT_CAP; M.ord = M.act1 + SEQ_ACT_CAP;
-  M.keys = M.ord + SEQ_ACT_CAP; M.key_cap = D.seq_fold;   // Dev::seq_fold = the key capacity that fits the buffer (a power of two)
-  M.tbox = D.seq_gmem_d; M.tarea = M.tbox + 12 * (size_t)D.U; M.bx = M.tarea + 2 * (size_t)D.U;
-  M.ti = D.seq_gmem_i; M.stk = M.ti + 10 * (size_t)D.U;
-  M.lane0_stages = true;
-  {   // gnorm: the sequential sum in robot order (Optimization3D_multi.h:57,72,750)
-    if (D.xs_async) xs_wait(D, D.xs_done(), D.u1 - D.u0);   // asynchronous Newton solve: every robot's |g| is in
-    if (D.xf) xf_wait_seg(D, 1, 0);   // sharded contexts: the other ranks' |g| values are put in place by this launch's foreign units of segment 0
-    for (int i = lane; i < D.U; i += 64) M.gns[i] = (D.xf || D.xs_async) ? xf_load(&D.gn(i)) : D.gn(i);
-    __syncthreads();
-    if (!D.coupled()) { if (lane == 0) { double gsum = 0; for (int u = 0; u < D.U; u++) gsum += M.gns[u]; D.ctl->gnorm = gsum / double(D.U); } }
-    else {
-      // coupled mode (one context; round 5: the replay is folded here too): gnorm = |G| / uav_num and wolfe = -x0.G over the whole arrowhead system
-      // (Optimization3D_multi.h:558,580) from k_xsolve_c2's per-robot partial sums, the shared-time entries added in robot order -- what k_ccd_self_seq forms
-      __shared__ double s_cp[2][64];
-      double gt = 0, xg = 0;
-      for (int u0 = 0; u0 < D.U; u0 += 64) {
-        const int nu = min(64, D.U - u0);
-        __syncthreads();
-        if (lane < nu) {
-          const double* pg = D.xdir + (size_t)(u0 + lane) * D.xs + 3 * D.T + 3;
-          s_cp[0][lane] = D.xs_async ? xf_load(pg) : *pg; s_cp[1][lane] = D.xs_async ? xf_load(&D.wolfe(u0 + lane)) : D.wolfe(u0 + lane);   // (asynchronous solve: records of two robots share cache lines)
-        }
-        __syncthreads();
-        if (lane == 0) for (int j = 0; j < nu; j++) { gt += s_cp[0][j]; xg += s_cp[1][j]; }
-      }
-      if (lane == 0) {
-        double gsum = 0;
-        for (int u = 0; u < D.U; u++) gsum += M.gns[u];
-        D.ctl->gnorm = sqrt(gsum + gt * gt) / double(D.U);
-        D.ctl->wolfe_c = -(xg + (D.xs_async ? xf_load(&D.tdir(0)) : D.tdir(0)) * gt);
-      }
-    }
-    __syncthreads();
-  }
+  const SeqMem M = SeqLayout(D.U, D.seq_fold, true).carve(D.seq_gmem_d, D.seq_gmem_i, lds, true);   // Dev::seq_fold = the key capacity that fits the buffer (a power of two)
+  if (D.xs_async) xs_wait(D, D.xs_done(), D.u1 - D.u0);   // asynchronous Newton solve: every robot's |g| is in
+  if (D.xf) xf_wait_seg(D, 1, 0);   // sharded contexts: the other ranks' |g| values are put in place by this launch's foreign units of segment 0
+  const bool past = D.xf || D.xs_async;   // (asynchronous solve: records of two robots share cache lines)
+  gnorm_form(D, M.gns, lane, [&](const double* p) { return past ? xf_load(p) : *p; });
   int any_act = 0, v = 0;
   // 5 ms + 1 us per block of the launch (asynchronous solve: the tiles themselves wait for units that wait for the other queue -- 2 s, like them)
   if (poll_until<8>([&] { v = sum16(D.ctl->ccd_sub, 1); return (v & 0xffff) == n_t; }, D.xs_async ? WAIT_2S : WAIT_5MS + WAIT_SLACK * gridDim.x)) {
@@ -871,7 +857,7 @@ __device__ __forceinline__ void ccd_union_body(const Dev& D) {
     // time-out: late blocks may still be adding (the next begin_body zeroes the words anyway).
     if (lane < 16) { const int mine = xf_load_i(&D.ctl->ccd_sub[lane]); if (mine) atomicSub(&D.ctl->ccd_sub[lane], mine); }
   } else wait_failed(D, ERR_LOOP_CAP | ERR_PASS_TIMEOUT);
-  if (any_act > 0) ccd_self_seq_body<true>(D, M, false);   // (reads the pairs' count and keys with agent-scope loads)
+  if (any_act > 0) ccd_self_seq_body<true>(D, M);   // (reads the pairs' count and keys with agent-scope loads)
   TJ_TIC(D, K_CCD, 2);
 }
 // The union kernel behind K_CCD.  Compiled for 3 waves per SIMD (168 VGPRs): with the wave-cooperative GJK (ccd_obs_body) it fits

@@ -236,9 +236,8 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
   const int owned = d.u1 - d.u0;
   const bool multi = d.mode >= 1, coupled = d.mode == 2;
   const Grids g = plan_grids(d, c->hp.n_solve_env);   // (of d as this launch sees it: the per-launch flags above count)
-  const int n_solve = g.n_solve, n_obs_solve = g.n_obs_solve, n_rows = g.n_rows, n_xf = g.n_xf, n_ccd = g.n_ccd, n_front = g.n_front;
+  const int n_solve = g.n_solve, n_obs_solve = g.n_obs_solve, n_rows = g.n_rows, n_front = g.n_front;
   const bool chained = sched != Sched::Stage;          // an iteration chain (one context, or the phases of a sharded schedule) as opposed to the stage API
-  const int n_mid = g.n_mid_slack + n_solve + n_obs_solve;
   d_.fa_nfront = n_front; d_.fa_nls = coupled ? owned * LSC_ROUNDS : owned * d.ls_help;
   switch (kid) {
     case K_BEGIN: if (chain_pos & 1) return false;
@@ -276,10 +275,10 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
       if (sched == Sched::Chain && c->xq.fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
         c->xq.fa_mid_now = false;
         d_.fa_seq = c->xq.fa_seq; d_.fa_mid = 1;
-        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value, true>), dim3(1 + n_mid), dim3(64), 0, s, d, n_solve, n_obs_solve); });
+        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value, true>), dim3(MidLayout(d, n_solve, n_obs_solve, true, d.mid_order != 0).total), dim3(64), 0, s, d, n_solve, n_obs_solve); });
         return true;
       }
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value>), dim3(n_mid), dim3(64), 0, s, d, n_solve, n_obs_solve); });
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value>), dim3(MidLayout(d, n_solve, n_obs_solve, false, d.mid_order != 0).total), dim3(64), 0, s, d, n_solve, n_obs_solve); });
       return true;
     case K_SEP_SELF_SOLVE: if (sched == Sched::Chain || !n_solve) return false; TJ_LAUNCH(k_sep_self_solve, dim3(n_solve), dim3(64), 0, s, d); return true;
     case K_KEEP:  // "optimal_plane":1 only; single UAV: a wave per segment, multi UAV: lanes over the switched-on pair slots
@@ -317,10 +316,7 @@ bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos
     case K_CCD: if (!chained) return false;
       if (d.xf) { if (c->xf_used[1]) (void)hipMemsetAsync(d.xf_seg + (size_t)d.S * XF_SEG_STRIDE, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[1] = true; }
       if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 1);   // ranks sharing a device: the wait for the peers' direction records is a launch of its own
-      {
-        const int n = n_ccd + n_xf + (d.seq_fold ? 1 : 0);   // + the finisher of the folded pair replay (kernels_step.h)
-        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_lean<decltype(prim)::value>), dim3(n), dim3(64), 0, s, d); });
-      }
+      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_lean<decltype(prim)::value>), dim3(CcdLayout(d).total()), dim3(64), 0, s, d); });   // (its layout counts the foreign units and the finisher of the folded pair replay)
       return true;
     case K_CCD_OBS: if (sched == Sched::Chain) return false;
       with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_obs<decltype(prim)::value>), dim3(owned * d.S), dim3(64), 0, s, d); });
@@ -681,7 +677,7 @@ std::vector<ArrayDecl> device_arrays(Dev& d) {
     arr(d.seg_stats, U * S * 6, SNAP), arr(d.pair_stats, U * S * 2, SNAP), arr(d.blk_stats, U * P + U, SNAP),
     arr(d.hullinfo, U * S * HULL_INFO_STRIDE), arr(d.hbox, S * 6 * U), arr(d.cbox, S * 6 * U), arr(d.pairplane, multi ? S * U * U * 4 : 1),
     arr(d.pairstamp, multi ? S * U * U : 1), arr(d.pairbits, multi ? S * U * ((U + 63) / 64) : 1),
-    arr(d.pair_work, 3 * (size_t)d.cap_work), arr(d.pair_work_n, S + 1), arr(d.pair_ovf, 4), arr(d.seq_gmem_d, seq_fold_gmem_doubles(d.U)), arr(d.seq_gmem_i, seq_fold_gmem_ints(d.U)),
+    arr(d.pair_work, 3 * (size_t)d.cap_work), arr(d.pair_work_n, S + 1), arr(d.pair_ovf, 4), arr(d.seq_gmem_d, SeqLayout(d.U, ACT_CAP, true).tree_doubles), arr(d.seq_gmem_i, SeqLayout(d.U, ACT_CAP, true).tree_ints),
     arr(d.spec_n, 2), arr(d.spec_list, 2 * SPEC_CAP), arr(d.spec_tag, SPEC_CAP), arr(d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES), arr(d.spec_sti, SPEC_CAP * SPEC_STATE_INTS),
     arr(d.pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX), arr(d.ctl, 1),
     arr(d.ocand, U * S * co), arr(d.ocand_n, U * S), arr(d.ohull, U * S * 18),
@@ -2132,6 +2128,20 @@ int tj_kat_get_hull_record(tj_ctx* c, double* hullinfo, double* hbox) {
   HIPCHK(c, hipMemcpy(h.data(), d.hullinfo, h.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t r = 0; r < recs; r++) memcpy(hullinfo + r * 122, h.data() + r * HULL_INFO_STRIDE, 122 * sizeof(double));
   HIPCHK(c, hipMemcpy(hbox, d.hbox, (size_t)d.S * 6 * d.U * sizeof(double), hipMemcpyDeviceToHost));
+  return TJ_OK;
+}
+
+// the swept-hull cache likewise: the CCD_REC values of every (robot, segment) record and the pair-box table.  No kernel runs
+int tj_kat_get_swept_record(tj_ctx* c, double* ccdinfo, double* cbox) {
+  if (!c || !ccdinfo || !cbox) return TJ_ERR_INVALID;
+  if (!ready(c)) return TJ_ERR_INVALID;
+  const Dev& d = c->d;
+  QUIESCE(c);
+  const size_t recs = (size_t)d.U * d.S;
+  std::vector<double> h(recs * CCD_STRIDE);
+  HIPCHK(c, hipMemcpy(h.data(), d.ccdinfo, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < recs; r++) memcpy(ccdinfo + r * CCD_REC, h.data() + r * CCD_STRIDE, CCD_REC * sizeof(double));
+  HIPCHK(c, hipMemcpy(cbox, d.cbox, (size_t)d.S * 6 * d.U * sizeof(double), hipMemcpyDeviceToHost));
   return TJ_OK;
 }
 

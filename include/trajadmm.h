@@ -599,6 +599,83 @@ typedef struct tj_obstacle_robot {
 } tj_obstacle_robot;
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);
 int tj_obstacle_record_size(void);   /* sizeof(tj_obstacle_robot) */
+/* ---- tj_peak_dynamics: how fast every robot's FLOWN CURVE really gets -- peak speed, acceleration and jerk, converged, each with its flight time -- how long
+ * its path is, and by how much its timetable could be compressed (csrc/kernels_peak_dynamics.h; read-only like tj_audit).  tj_audit's speed / accel are maxima
+ * over the control vectors of each segment's derivative nets: what bound_energy constrains, but only an upper bound on what the vehicle does, without a time --
+ * TJ_AUDIT_SPEED can be set for a curve that never reaches the limit (an init file, tj_plan_init's output).  Here that bound drives a maximising branch and
+ * bound over windows of one segment's parameter.  Nothing of another robot is read: all three modes, single-UAV included.  For every OWNED robot u:
+ *   nets     P[0..5] = the raw hull of segment tr (hull_entry's sums); per axis v_i = 5 * (P[i+1] - P[i]), i = 0..4 (degree 4), a_i = 20 * (P[i+2] - 2 * P[i+1]
+ *            + P[i]), i = 0..3 (degree 3) -- hull_speed's and hull_accel's expressions -- and j_i = 60 * (P[i+3] - 3 * P[i+2] + 3 * P[i+1] - P[i]), i = 0..2
+ *            (degree 2), all left to right.  A control vector c of a net counts as norm3(c) / den with den = w * pt (speed), w * w * pt * pt (acceleration),
+ *            w * w * w * pt * pt * pt (jerk), left to right, w = the segment's weight, pt = piece_time[u]: tj_audit's association, so depth 0 gives its bits.
+ *   window   W = [sa, sb], dyadic in the segment's local parameter (as in tj_obstacle_approach: halving at 0.5 * (sa + sb) is exact, max_depth <= 40).  The
+ *            derivative net ITSELF is restricted to W by blossoming (bez_restrict_n: bez_restrict's steps for degree 4, 3, 2), always from the RAW derivative
+ *            net, never from a parent's and never by differencing a restricted position net: rounding does not grow with depth and no window-width factor
+ *            appears.  [0, 1] returns the raw net bit for bit.
+ *   bounds   for the restricted net c_0..c_n: ub(W) = max_i norm3(c_i) / den (the curve lies in the hull of its net); at(W) = the larger of norm3(c_0) / den
+ *            and norm3(c_n) / den -- values of the curve at s = sa and s = sb: attained; c_0's on equality.  Attained candidates are ordered: larger value,
+ *            then smaller segment, then smaller s.  The real time of (tr, s) is ((tr + s) / res) * piece_time[u], tj_obstacle_approach's expression.
+ *   search   one per robot and quantity.  Seeds: every segment at [0, 1]; best = the first attained candidate in that order; live = {W : ub(W) > best.value},
+ *            strict.  Round d = 1, 2, ..: every live item is halved, both children are evaluated, best is updated over the round's children, then live = the
+ *            children with ub > best.value -- the round's FINAL best, so nothing (`windows` and `depth` included) depends on the order of evaluation.
+ *   bracket  lo = best.value, hi = max(best.value, max of ub over the live set): lo <= the curve's peak <= hi, lo attained at `time` in `segment`.
+ *   stop     hi - lo <= tol * hi (relative: the three quantities have different units; CONVERGED) | the live set is empty (CONVERGED) | d == max_depth |
+ *            the live set holds more than max_windows (TRUNCATED: the record of the last completed round -- for an overflow at seeding the seeds' own bracket
+ *            with depth 0; `windows` counts the overflowing round's work too).
+ *   length   real time cancels.  Level L (0 <= L <= TJ_PEAK_MAX_LENGTH_LEVELS): per segment the 2^L windows [j * h, (j + 1) * h], h = 1.0 / 2^L, each the raw v
+ *            net restricted: len_lo(W) = h * norm3(m), m = (c_0 + c_1 + c_2 + c_3 + c_4) / 5 per axis -- the chord: the integral of a Bezier net is its mean --
+ *            and len_hi(W) = (h * (norm3(c_0) + norm3(c_1) + norm3(c_2) + norm3(c_3) + norm3(c_4))) / 5 -- the control polygon; sums left to right.  A
+ *            segment's windows are summed in the balanced binary tree over adjacent pairs, the segments one after the other, tr = 0..S-1.
+ *            length_lo <= path length <= length_hi.
+ *   duration = tj_audit's: piece_num * piece_time as its sum.  time_scale = fmax(speed.hi / vel_limit, sqrt(accel.hi / acc_limit)): multiplying the robot's
+ *   piece_time by any factor >= time_scale keeps both peaks certified at or below their limits; a value < 1 is headroom.
+ * STATED LIMIT: hi is sound up to the rounding of at most eight convex-combination steps ((1 - s) * x + s * y: relative 3 eps of the larger operand each),
+ * norm3 and the division: hi >= true peak - 32 eps * (the robot's depth-0 hi of that quantity), eps = 2^-53.  The CPU test measures the excess on the four end
+ * states and tiny()'s initial states against mpmath: at most 1.72e-16 = 1.5 eps of the depth-0 hi (at tol = 0, where hi == lo is the peak's own rounded value);
+ * the test allows 64 eps.
+ * tol < 0: TJ_PEAK_TOL; 0 is valid.  max_depth < 0: TJ_PEAK_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0: TJ_PEAK_FRONTIER; above it TJ_ERR_INVALID.
+ * length_levels < 0: TJ_PEAK_LENGTH_LEVELS; above TJ_PEAK_MAX_LENGTH_LEVELS TJ_ERR_INVALID.  A NaN tol, records == NULL, a call before tj_init_state:
+ * TJ_ERR_INVALID, records untouched.  A plain SHARDED context (world > 1) answers for its owned robots; records of other ranks' robots are all zero.
+ * tj_group_peak_dynamics assembles the owners' records: bitwise one context's.  TWO launches whatever the fleet's size, the piece count and the depth; no host
+ * loop over rounds or robots.  Changes no solver state, statistics or launch count.
+ * The defaults are measured (tests/peak_dynamics_ref.py default_tolerance, the restatement, on the CPU): tol = 0 and max_depth = 40 on the final states of
+ * tests/golden/e2e_scn_a.npz, e2e_scn_b.npz, e2e_scn_c3.npz and e2e_scn_b_coupled.npz; per depth the largest (hi - lo) / hi over robots and quantities, and
+ * the largest live set:
+ *   depth   0        1        2        3        4        5        6        7        8        9        10       11       12       13       14       15
+ *   width   1.49e-2  7.88e-3  3.04e-4  5.04e-5  2.64e-5  9.48e-6  4.74e-6  1.73e-6  2.47e-7  1.11e-7  2.56e-8  6.72e-9  1.81e-9  4.56e-10 1.14e-10 2.78e-11
+ *   live    3        2        2        2        2        2        2        2        2        2        2        2        2        2        2        2
+ *   depth   16       17       18       19       20       21       22       23       24       25       26       27       28       29       30       31
+ *   width   6.77e-12 1.72e-12 4.29e-13 1.10e-13 2.70e-14 7.12e-15 1.84e-15 6.89e-16 4.56e-16 3.44e-16 2.30e-16 2.28e-16 2.28e-16 1.15e-16 1.15e-16 0
+ *   live    2        2        2        2        2        1        2        2        2        2        2        4        1        1        1        0
+ * At depth 31 every live set has emptied (hi == lo): the floor is the last positive width, 1.15e-16 at depth 30, and TJ_PEAK_TOL is the smallest power of ten
+ * >= 10 x that.  The largest live set is 4 items; TJ_PEAK_FRONTIER is the next power of two >= 4 x that, and at least 1024 (above every seed count in use: a
+ * robot has piece_num * res seeds).  The largest (length_hi - length_lo) / length_hi per level on the same states:
+ *   level   0        1        2        3        4        5        6
+ *   width   1.69e-4  4.30e-5  1.08e-5  2.70e-6  6.76e-7  1.69e-7  4.23e-8
+ * (a quarter per level); TJ_PEAK_LENGTH_LEVELS is the first below 1e-6 -- a micrometre per metre is beyond any use of a path length. */
+#define TJ_PEAK_CONVERGED 4   /* hi - lo <= tol * hi, or nothing was left that could hold a larger value */
+#define TJ_PEAK_TRUNCATED 8   /* the live set outgrew max_windows: the bracket of the last completed round is returned */
+#define TJ_PEAK_MAX_DEPTH 40
+#define TJ_PEAK_FRONTIER  1024   /* measured maximum of the live set: 4 */
+#define TJ_PEAK_TOL 1e-14
+#define TJ_PEAK_MAX_LENGTH_LEVELS 12
+#define TJ_PEAK_LENGTH_LEVELS 4
+#define TJ_DYN_SPEED    1   /* speed.lo >= vel_limit: the limit IS reached, at speed.time */
+#define TJ_DYN_SPEED_OK 2   /* speed.hi < vel_limit: certified */
+#define TJ_DYN_ACCEL    4   /* accel.lo >= acc_limit: the limit IS reached, at accel.time */
+#define TJ_DYN_ACCEL_OK 8   /* accel.hi < acc_limit: certified */
+typedef struct tj_peak {
+  double lo, hi, time;     /* lo <= the quantity's peak over u's flight <= hi; lo is attained at `time` */
+  int segment, depth;      /* the segment of the lo sample; rounds of halving completed */
+  int windows, flags;      /* windows evaluated (seeds + 2 per halved item); TJ_PEAK_CONVERGED | TJ_PEAK_TRUNCATED */
+} tj_peak;
+typedef struct tj_dynamics_robot {
+  tj_peak speed, accel, jerk;
+  double length_lo, length_hi, duration, time_scale;
+  int length_levels, flags;   /* the level the length bracket was formed at; TJ_DYN_* */
+} tj_dynamics_robot;
+int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);
+int tj_dynamics_record_size(void);   /* sizeof(tj_dynamics_robot) */
 /* ---- tj_flight_profile: where every robot is at the flight times the caller names, how fast it moves there, how far the NEAREST obstacle primitive is --
  * with no `range`, however far -- and how far the nearest other robot is at the same time (csrc/kernels_flight_profile.h; read-only like tj_audit).  The other
  * queries answer with one minimum per robot or pair, and only inside `range`; this one is the curve against time: what a plot of clearance and speed, a look
@@ -803,6 +880,7 @@ int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth,
 int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n);   /* tj_path_crossings of every pair (u, q > u) by u's owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n);   /* tj_timing_margin of every pair (u, q > u) by u's owner, in the same way */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
+int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);   /* tj_peak_dynamics of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */

@@ -38,6 +38,7 @@ EXPORTS = [
     "tj_path_crossings", "tj_crossing_record_size", "tj_group_path_crossings",
     "tj_timing_margin", "tj_margin_record_size", "tj_group_timing_margin",
     "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
+    "tj_peak_dynamics", "tj_dynamics_record_size", "tj_group_peak_dynamics",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -69,9 +70,9 @@ class TjAuditRobot(C.Structure):
 AUDIT_FLAGS = dict(obs_contact=1, pair_contact=2, speed=4, accel=8)
 
 
-def _records(struct, rec):
-    """an array of C records -> dict of numpy arrays, one per field (`reserved` is dropped)"""
-    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in struct._fields_ if n != "reserved"}
+def _records(struct, rec, only=None):
+    """an array of C records -> dict of numpy arrays, one per field (`reserved` is dropped; only: the fields wanted)"""
+    return {n: np.array([getattr(r, n) for r in rec], dtype=np.float64 if t is C.c_double else np.int32) for n, t in struct._fields_ if n != "reserved" and (only is None or n in only)}
 
 
 def _audit(call, U, S, range, per_segment):
@@ -155,6 +156,40 @@ OBSTACLE_FLAGS = dict(contact=1, clear=2, converged=4, truncated=8)
 OBSTACLE_TOL = 1e-11        # TJ_OBSTACLE_TOL: what tol=None selects
 OBSTACLE_MAX_DEPTH = 40     # TJ_OBSTACLE_MAX_DEPTH
 OBSTACLE_FRONTIER = 4096    # TJ_OBSTACLE_FRONTIER
+
+
+class TjPeak(C.Structure):
+    """mirror of tj_peak (include/trajadmm.h)"""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("time", C.c_double), ("segment", C.c_int), ("depth", C.c_int), ("windows", C.c_int), ("flags", C.c_int)]
+
+
+class TjDynamicsRobot(C.Structure):
+    """mirror of tj_dynamics_robot (include/trajadmm.h); tj_dynamics_record_size() is its sizeof on the C side"""
+    _fields_ = [("speed", TjPeak), ("accel", TjPeak), ("jerk", TjPeak), ("length_lo", C.c_double), ("length_hi", C.c_double), ("duration", C.c_double),
+                ("time_scale", C.c_double), ("length_levels", C.c_int), ("flags", C.c_int)]
+
+
+PEAK_FLAGS = dict(converged=4, truncated=8)                        # the flags of a TjPeak
+PEAK_DYN_FLAGS = dict(speed=1, speed_ok=2, accel=4, accel_ok=8)    # the flags of a TjDynamicsRobot
+PEAK_TOL = 1e-14            # TJ_PEAK_TOL: what tol=None selects (relative)
+PEAK_MAX_DEPTH = 40         # TJ_PEAK_MAX_DEPTH
+PEAK_FRONTIER = 1024        # TJ_PEAK_FRONTIER
+PEAK_LENGTH_LEVELS = 4      # TJ_PEAK_LENGTH_LEVELS: what length_levels=None selects
+PEAK_MAX_LENGTH_LEVELS = 12 # TJ_PEAK_MAX_LENGTH_LEVELS
+
+
+def _peak_dynamics(call, U, tol, max_depth, max_windows, length_levels):
+    """shared by Solver.peak_dynamics / Group.peak_dynamics: call(tol, max_depth, max_windows, length_levels, records) -> dict of numpy arrays [U]; a peak's fields
+    under `speed_lo`, `speed_hi`, `speed_time`, `speed_segment`, `speed_depth`, `speed_windows`, `speed_flags` (and accel_, jerk_)"""
+    rec = (TjDynamicsRobot * U)()
+    call(C.c_double(-1.0 if tol is None else float(tol)), C.c_int(-1 if max_depth is None else int(max_depth)), C.c_int(0 if max_windows is None else int(max_windows)),
+         C.c_int(-1 if length_levels is None else int(length_levels)), rec)
+    out = {}
+    for q in ("speed", "accel", "jerk"):
+        for n, v in _records(TjPeak, [getattr(r, q) for r in rec]).items():
+            out[q + "_" + n] = v
+    out.update(_records(TjDynamicsRobot, rec, ("length_lo", "length_hi", "duration", "time_scale", "length_levels", "flags")))
+    return out
 
 
 class TjPairRecord(C.Structure):
@@ -804,6 +839,14 @@ class Solver:
         sharded solver (world > 1) answers for its owned robots, the other records are zero."""
         return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_obstacle_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
+    def peak_dynamics(self, tol=None, max_depth=None, max_windows=None, length_levels=None):
+        """tj_peak_dynamics: per robot the FLOWN CURVE's peak speed, acceleration and jerk as brackets lo <= peak <= hi converged to the relative `tol` (None:
+        PEAK_TOL) -- `speed_lo`, `speed_hi`, `speed_time` / `speed_segment` of the lo sample, `speed_depth`, `speed_windows`, `speed_flags` (PEAK_FLAGS), the same
+        under accel_ and jerk_ --, the path length's bracket `length_lo` / `length_hi` at `length_levels` (None: PEAK_LENGTH_LEVELS), `duration`, `time_scale`
+        (the smallest factor on piece_time that keeps both limits certified; < 1: headroom) and `flags` (PEAK_DYN_FLAGS).  Dict of numpy arrays [U].  Read-only.
+        All modes; a sharded solver (world > 1) answers for its owned robots, the other records are zero."""
+        return _peak_dynamics(lambda *a: self._check(self.lib.tj_peak_dynamics(self._ctx, *a)), self.U, tol, max_depth, max_windows, length_levels)
+
     def piece_times(self):
         """piece_time of every robot as this context holds it"""
         out = np.zeros(self.U)
@@ -964,6 +1007,10 @@ class Group:
             self._check(self.lib.tj_group_get_state(self._g, C.c_int(u), None, None, None, None, None, C.byref(pt)))
             out[u] = pt.value
         return out
+
+    def peak_dynamics(self, tol=None, max_depth=None, max_windows=None, length_levels=None):
+        """tj_group_peak_dynamics: Solver.peak_dynamics of every robot from the rank that owns it (bitwise one context's)"""
+        return _peak_dynamics(lambda *a: self._check(self.lib.tj_group_peak_dynamics(self._g, *a)), self.U, tol, max_depth, max_windows, length_levels)
 
     def flight_profile(self, times=None, samples=None):
         """tj_group_flight_profile: Solver.flight_profile of every robot from the rank that owns it (bitwise one context's)"""

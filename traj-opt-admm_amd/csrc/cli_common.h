@@ -291,6 +291,24 @@ inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   else std::cout << "obstacle fleet hi " << rec[who].hi << " uav " << who << " id " << rec[who].index << " time " << rec[who].time << " contact " << contact << std::endl;
 }
 
+// --peak-dynamics: one line per robot and the fleet's summary (the robot with the largest time_scale), in the style of --obstacle-approach
+inline void print_peak_dynamics(const std::vector<tj_dynamics_robot>& rec) {
+  std::cout.precision(17);
+  size_t who = 0;
+  auto peak = [](const char* name, const tj_peak& p) {
+    std::cout << " " << name << " lo " << p.lo << " hi " << p.hi << " seg " << p.segment << " time " << p.time << " depth " << p.depth << " windows " << p.windows << " flags " << p.flags;
+  };
+  for (size_t u = 0; u < rec.size(); u++) {
+    const tj_dynamics_robot& r = rec[u];
+    std::cout << "dynamics uav " << u;
+    peak("speed", r.speed); peak("accel", r.accel); peak("jerk", r.jerk);
+    std::cout << " length lo " << r.length_lo << " hi " << r.length_hi << " levels " << r.length_levels << " duration " << r.duration << " time_scale " << r.time_scale
+              << " flags " << r.flags << std::endl;
+    if (r.time_scale > rec[who].time_scale) who = u;
+  }
+  if (!rec.empty()) std::cout << "dynamics fleet time_scale " << rec[who].time_scale << " uav " << who << std::endl;
+}
+
 // --flight-profile: one line per robot and sample, robot after robot; `word`: the lines start with "profile " (standard output, next to the other queries' lines)
 inline void print_flight_profile(const std::vector<tj_profile_sample>& rec, int U, int K, std::ostream& os, bool word) {
   os.precision(17);

@@ -38,6 +38,9 @@
 // longest robot's duration (K == 1: t = 0) -- "profile uav t x y z d_obs idx d_robot partner speed accel flags" at 17 digits: position, distance and index of the
 // NEAREST obstacle primitive (no range), distance and index of the nearest other robot at the same time, speed, acceleration, flag word.  With FILE the lines go
 // there instead, without the leading word (the layout of --sample-traj, extended).  Works in the single-UAV main and with --gpus.
+// --peak-dynamics [TOL]: after the --flight-profile lines one line per robot from tj_peak_dynamics / tj_group_peak_dynamics -- the flown curve's peak speed, acceleration
+// and jerk converged to the relative TOL (default the library's), each with its time, the path length's bracket, duration, time_scale, flag word -- and a fleet line with
+// the largest time_scale and its robot.  Works in the single-UAV main and with --gpus.
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
 #include <chrono>
@@ -52,7 +55,7 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--flight-profile K [FILE]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
@@ -63,6 +66,7 @@ int main(int argc, char** argv) {
   bool crossings = false; double crossings_tol = -1;
   bool margins = false; double margins_tol = -1;
   int profile_samples = 0; std::string profile_file;
+  bool dynamics = false; double dynamics_tol = -1;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -79,6 +83,7 @@ int main(int argc, char** argv) {
     else if (a == "--path-crossings") { crossings = true; if (i + 1 < argc && argv[i + 1][0] != '-') crossings_tol = atof(argv[++i]); }
     else if (a == "--timing-margin") { margins = true; if (i + 1 < argc && argv[i + 1][0] != '-') margins_tol = atof(argv[++i]); }
     else if (a == "--flight-profile" && i + 1 < argc) { profile_samples = atoi(argv[++i]); if (i + 1 < argc && argv[i + 1][0] != '-') profile_file = argv[++i]; if (profile_samples < 1) { std::cerr << "--flight-profile needs K >= 1" << std::endl; return -1; } }
+    else if (a == "--peak-dynamics") { dynamics = true; if (i + 1 < argc && argv[i + 1][0] != '-') dynamics_tol = atof(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -247,6 +252,11 @@ int main(int argc, char** argv) {
       std::ofstream pf;
       if (!profile_file.empty()) pf.open(profile_file);
       tjcli::print_flight_profile(rec, U, K, profile_file.empty() ? std::cout : pf, profile_file.empty());
+    }
+    if (dynamics) {
+      std::vector<tj_dynamics_robot> rec(U);
+      chk(group ? tj_group_peak_dynamics(grp, dynamics_tol, -1, 0, -1, rec.data()) : tj_peak_dynamics(ctx, dynamics_tol, -1, 0, -1, rec.data()), "tj_peak_dynamics");
+      tjcli::print_peak_dynamics(rec);
     }
     if (!dump.empty()) {
       std::ofstream df(dump);

@@ -1,10 +1,10 @@
-// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_flight_profile), each piece defined once.
+// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_flight_profile, tj_peak_dynamics), each piece defined once.
 //
 // Every query works per (owned robot, segment) on the segment's 6-point hull (hull_entry's sums: the bits of the hull cache) and its box, and reduces per-lane candidates
 // with a TOTAL order, so that a result is a function of the state alone: no float atomics, no dependence on the order of evaluation.
 //   hull_box, query_hull   the box of a 6-point hull behind a stride; the unit's hull into LDS and its box
 //   box_near       the box-gap skip: is a 6-point hull's box within `range` of the unit's box on every axis
-//   bez_restrict, hull_restrict   a quintic's Bezier net restricted to a window; a segment's raw hull restricted into a lane's column of a tile
+//   bez_restrict, bez_restrict_n, hull_restrict   a quintic's Bezier net restricted to a window, the same for any degree; a segment's raw hull restricted into a lane's column of a tile
 //   wave_argmin    the smallest (value, key) in lexicographic order over the wave, with whatever travels along
 //   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
 //   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
@@ -77,6 +77,28 @@ __device__ __forceinline__ void bez_restrict(const double (&p)[6], double sa, do
   }
 }
 
+// the same for a net of N points (degree N - 1: the derivative nets of tj_peak_dynamics, N = 5, 4, 3): o[i] = blossom(sa x (N - 1 - i), sb x i), the steps and their order as
+// above (N = 6 gives bez_restrict's bits); sa = 0, sb = 1 returns p bit for bit
+template <int N>
+__device__ __forceinline__ void bez_restrict_n(const double (&p)[N], double sa, double sb, double (&o)[N]) {
+  const double ua = 1 - sa, ub = 1 - sb;
+  double r[N];
+#pragma unroll
+  for (int m = 0; m < N; m++) r[m] = p[m];
+#pragma unroll
+  for (int s = 0; s < N; s++) {
+    double t[N];
+#pragma unroll
+    for (int m = 0; m < N - s; m++) t[m] = r[m];
+#pragma unroll
+    for (int k = N - 1 - s; k > 0; k--)
+#pragma unroll
+      for (int m = 0; m < k; m++) t[m] = ub * t[m] + sb * t[m + 1];
+    o[N - 1 - s] = t[0];
+#pragma unroll
+    for (int m = 0; m < N - 1 - s; m++) r[m] = ua * r[m] + sa * r[m + 1];
+  }
+}
 
 // segment tr of `net` (hull_entry's sums) restricted to [sa, sb] into a column of stride ST; [0, 1] returns the raw hull bit for bit.  __restrict__: col is a
 // lane's column of an LDS tile and never the net.  A caller that holds the column in a struct hides that from the compiler, which then reloads the control points

@@ -36,6 +36,7 @@
 #include "kernels_audit_timed.h"
 #include "kernels_closest.h"
 #include "kernels_obstacle_approach.h"
+#include "kernels_peak_dynamics.h"
 #include "kernels_pair_approach.h"
 #include "kernels_path_crossing.h"
 #include "kernels_timing_margin.h"
@@ -104,7 +105,7 @@ struct tj_ctx {
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
-  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_flight_profile): every buffer is allocated by the first call that needs it, and a call
+  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_flight_profile, tj_peak_dynamics): every buffer is allocated by the first call that needs it, and a call
   // whose allocations failed partway keeps what it got (query_buf).  Each query ends in a stream synchronise, so no two are in flight on one context, and they share: q_ctl, the
   // control block the BVH walk reports its overflow bit to (never the solver's); q_net [U][3][T] and q_pt [U], the staged copy of the control nets and piece times a group hands
   // in; q_order (sorted primitive -> caller's index), which belongs to the obstacle set and goes with it (cloud_allocs).  Per query: its rows / lists / counters and its records.
@@ -113,6 +114,7 @@ struct tj_ctx {
   AuditTimedArgs timed{}; tj_audit_timed_robot* timed_out = nullptr;
   ClosestArgs closest{}; tj_closest_robot* closest_out = nullptr;
   ObstArgs obst{}; tj_obstacle_robot* obst_out = nullptr;
+  PeakArgs peak{}; tj_dynamics_robot* peak_out = nullptr;   // tj_peak_dynamics
   // tj_pair_approach, tj_path_crossings (listed_run): the bitmask, its offsets and n are the fleet's size (allocated once, as above); what is sized by the call's cap and
   // max_windows (the other buffers of `sized`, and out) grows with the largest call so far (cap, mw) and lives in allocs
   Listed<PairArgs, tj_pair_record> pair;
@@ -1298,7 +1300,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the eight (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_flight_profile.h) ----
+// ---- the read-only queries: one path for the nine (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1671,6 +1673,35 @@ int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int
   return query_finish(c, "tj_obstacle_approach");
 }
 int tj_obstacle_record_size(void) { return (int)sizeof(tj_obstacle_robot); }
+
+// tj_peak_dynamics: every owned robot from the context's own state, like tj_obstacle_approach.  Argument checks in the queries' precedence: null -> NaN -> limits -> no state
+int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* out) {
+  if (!c || !out) return TJ_ERR_INVALID;
+  int r;
+  if ((r = query_nan(c, "tj_peak_dynamics", "tol", tol))) return r;
+  if (max_depth > TJ_PEAK_MAX_DEPTH) { c->err = "tj_peak_dynamics: max_depth must be 0.." + std::to_string(TJ_PEAK_MAX_DEPTH) + " (or negative for the default): deeper windows are not dyadic in a double"; return TJ_ERR_INVALID; }
+  if (max_windows > TJ_PEAK_FRONTIER) { c->err = "tj_peak_dynamics: max_windows must be 1.." + std::to_string(TJ_PEAK_FRONTIER) + " (or <= 0 for the default): the live list's capacity"; return TJ_ERR_INVALID; }
+  if (length_levels > TJ_PEAK_MAX_LENGTH_LEVELS) { c->err = "tj_peak_dynamics: length_levels must be 0.." + std::to_string(TJ_PEAK_MAX_LENGTH_LEVELS) + " (or negative for the default)"; return TJ_ERR_INVALID; }
+  if ((r = query_state(c, "tj_peak_dynamics", false, false))) return r;
+  const Dev& d = c->d;
+  const int owned = d.u1 - d.u0, kw = std::max(2 * TJ_PEAK_FRONTIER, d.S);
+  const size_t lists = (size_t)(owned > 0 ? owned : 1) * 3;
+  QUIESCE(c);
+  PeakArgs& b = c->peak;
+  if ((r = query_buf(c, b.list, lists * 2 * TJ_PEAK_FRONTIER)) || (r = query_buf(c, b.kub, lists * kw)) || (r = query_buf(c, c->peak_out, d.U))) return r;
+  PeakArgs a = b;
+  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt))) return r;
+  a.tol = tol < 0 ? TJ_PEAK_TOL : tol; a.max_depth = max_depth < 0 ? TJ_PEAK_MAX_DEPTH : max_depth; a.max_windows = max_windows <= 0 ? TJ_PEAK_FRONTIER : max_windows;
+  a.levels = length_levels < 0 ? TJ_PEAK_LENGTH_LEVELS : length_levels; a.cap = TJ_PEAK_FRONTIER; a.kw = kw;
+  if ((r = query_clear(c, c->peak_out, d.U))) return r;
+  if (owned > 0) {   // two launches whatever the fleet's size, the piece count and the depth
+    hipLaunchKernelGGL(k_peak_dynamics, dim3(owned, 4), dim3(64), 0, c->stream, d, a, c->peak_out);
+    hipLaunchKernelGGL(k_peak_finish, dim3((owned + 63) / 64), dim3(64), 0, c->stream, d, c->peak_out);
+  }
+  if ((r = query_fetch(c, out, c->peak_out, d.U))) return r;
+  return query_finish(c, nullptr);
+}
+int tj_dynamics_record_size(void) { return (int)sizeof(tj_dynamics_robot); }
 int tj_flight_profile(tj_ctx* c, const double* times, int n_times, tj_profile_sample* out) { return profile_run(c, times, n_times, nullptr, nullptr, out); }
 int tj_flight_profile_record_size(void) { return (int)sizeof(tj_profile_sample); }
 

@@ -702,6 +702,11 @@ int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_de
     return tj_obstacle_approach(c, range, tol, max_depth, max_windows, part); });
 }
 
+int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* out) {
+  return group_query(g, false, false, out, {}, {}, [&](tj_ctx* c, const double*, const double*, tj_dynamics_robot* part) {
+    return tj_peak_dynamics(c, tol, max_depth, max_windows, length_levels, part); });
+}
+
 // the owners' rows [n_times] per robot; control points and piece_time from the owners, so every rank places the whole fleet as one context would
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out) {
   if (!g || !times || !out || n_times < 1) return TJ_ERR_INVALID;

@@ -44,6 +44,11 @@ int tj_kat_query_form(tj_ctx* c, int nq, const double* boxes, double margin, int
  * plane ok, cx, cy, cz, d of Separate::opengjk with a 3-vertex body at distance dist | CCD::KDOPDCD(P, tri, dist) |
  * CCD::KDOPDCD({P, P + t D}, tri, off) | CCD::GJKDCD({P, P + t D}, tri, off)  -- the predicates Step::mix_step uses (Step.h:390-404) */
 int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double* tri, const double* t, double dist, double off, double* out);
+/* the obstacle 49-axis cull in the form the obstacle walks run it (kdop_cull_wave: one wave per case, lanes over the axes, up to 64 candidates on the lanes):
+ * prim 1 points / 3 triangles; P[n][6][3] hull; swept != 0: the intervals of conv{P, P + t D} (D[n][6][3], t[n]; both may be NULL otherwise);
+ * bodies[n][per][prim][3], per <= 64; nc[n] = candidates of case i that take part (lanes [0, nc[i]); NULL: all per); out[n][per] = pass, 0 beyond nc[i].
+ * tj_kat_planes' what 2 and tj_kat_tri's two k-DOP outputs are this call with one candidate per case. */
+int tj_kat_kdop_wave(tj_ctx* c, int prim, int swept, int n, int per, const double* P, const double* D, const double* t, const double* bodies, const int* nc, double d, double* out);
 /* dense LLT failure test + smallest eigenvalue (Eigen LLT / SelfAdjointEigenSolver as used at Gradient_admm.h:38-53): out[nmat][2] */
 int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out);
 /* the per-piece gradient and Hessian blocks of the whole fleet, written from the host: lg[U][P][19], lh[U][P][361] (row-major 19 x 19; local 0..17 = global

@@ -87,7 +87,7 @@ def cap(d, ids, rng):
 
 def brute_obs(pr, H, prims_xyz, rng, prefilter=True):
     """prims_xyz [N][3] points or [N][3][3] triangles -> (d[U][S], id[U][S]); id -1 and d = rng where nothing is closer.
-    prefilter=True: only primitives whose point / box is within rng of the hull's box (the device's comparison, kernels_sep.h box_hit);
+    prefilter=True: only primitives whose point / box is within rng of the hull's box (the device's comparison, kernels_sep.h box_near);
     prefilter=False: every primitive against every hull."""
     prims_xyz = np.asarray(prims_xyz, dtype=np.float64)
     if not prefilter:

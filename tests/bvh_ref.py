@@ -6,7 +6,7 @@
   candidates   what a query returns with sort=False: the walk ends in the fp64 leaf test `x + m < q.lo[k]` / `x > q.hi[k] + m` on the primitive itself (a
                point, or the fp64 min / max of a triangle's three vertices), frontiers are compacted in ascending order and leaves are taken slot by slot,
                then by lane -- so the sequence is the passing positions of the sorted order, ascending, mapped through `order`.  No tolerance anywhere.
-  frontiers    hit boxes per level by box_hit's expression on the float32 boxes widened to double: what the walk's frontier holds (FRONT_CAP).
+  frontiers    hit boxes per level by box_near's expression on the float32 boxes widened to double: what the walk's frontier holds (FRONT_CAP).
   walk         the level-by-level walk over the restated pyramid (tests/test_bvh_ref.py: it must give the brute-force set).
   cloud, queries, touching, case
                the inputs of tests/test_gpu_bvh_walk.py; tests/test_bvh_ref.py checks on the CPU that they do not let a test pass on nothing.
@@ -117,7 +117,7 @@ def candidate_lists(b, boxes, m):
 
 
 def frontiers(levels, q, m):
-    """hit boxes per level (level 0 first) by box_hit's expression"""
+    """hit boxes per level (level 0 first) by box_near's expression"""
     q = np.asarray(q, dtype=np.float64)
     return [len(_passing(np.ascontiguousarray(lo.astype(np.float64).T), np.ascontiguousarray(hi.astype(np.float64).T), q, float(m))) for lo, hi in levels]
 

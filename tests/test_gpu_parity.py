@@ -119,6 +119,44 @@ def test_device_planes_kdop_ccd_vs_reference(katsolver):
     assert np.array_equal(out[:, 1], g["self_gjk_ccd"].astype(float))
 
 
+def _kdop_cull_restated(axes, hull_pts, bodies, d):
+    """the obstacle 49-axis test written out again: hull_pts[n][m][3] (the 6 hull points, or the 12 of a swept hull), bodies[n][64][v][3] -> pass[n][64].
+    Projections as (x*px + y*py) + z*pz, min / max over the vertices, and the comparison of the product's kdop_apart."""
+    proj = lambda X: (X[..., None, 0] * axes[:, 0] + X[..., None, 1] * axes[:, 1]) + X[..., None, 2] * axes[:, 2]     # [..., vertex, axis]
+    h = proj(hull_pts); lo_ax, hi_ax = h.min(axis=1)[:, None, :], h.max(axis=1)[:, None, :]                          # [n][1][49]
+    b = proj(bodies); lo, up = b.min(axis=2), b.max(axis=2)                                                          # [n][64][49]
+    return ~((up < lo_ax - d) | (hi_ax < lo - d)).any(axis=2)
+
+
+@pytest.mark.parametrize("fixture", ["kdop_dcd", "kdop_dcd_tri", "kdop_ccd_tri"])
+def test_device_obstacle_kdop_cull_in_its_product_form(pkg, katsolver, fixture):
+    """CCD::KDOPDCD on the reference's cases through kdop_cull_wave, the form obs_query_body and ccd_obs_body run: one wave per case, 64 candidates on its
+    lanes.  Candidate j of case i is the fixture's body shifted by (j - i % 64) * 0.01 along a seeded unit direction, so lane i % 64 holds the reference's
+    case and the lanes around it move through the verdict's boundary."""
+    if fixture == "kdop_dcd":
+        g = gold("prims_kat.npz"); body = g["q"][:, None, :]; d = 0.2; swept = {}
+    else:
+        g = gold("tri_kat.npz"); body = g["tri"]
+        d, swept = (0.2, {}) if fixture == "kdop_dcd_tri" else (0.1, dict(D=g["D"], t=g["t"]))
+    P = g["P"].reshape(-1, 6, 3); n = len(P); lane = np.arange(n) % 64
+    dirs = np.random.default_rng(20260).normal(size=(n, 3)); dirs /= np.linalg.norm(dirs, axis=1)[:, None]
+    shift = (np.arange(64)[None, :] - lane[:, None]) * 0.01                                                # [n][64]
+    bodies = body[:, None, :, :] + (shift[:, :, None] * dirs[:, None, :])[:, :, None, :]                   # [n][64][v][3]
+    assert np.array_equal(bodies[np.arange(n), lane], body)
+    hull_pts = np.concatenate([P, P + g["t"][:, None, None] * g["D"].reshape(-1, 6, 3)], axis=1) if swept else P
+    want = _kdop_cull_restated(pkg.host_tables(3, 8)[3], hull_pts, bodies, d)
+    both = (want.any(axis=1) & ~want.all(axis=1)).sum()
+    assert both >= 200, f"only {both} of {n} waves hold both verdicts"                                     # a condition on the inputs, not a measurement
+    got = katsolver.kat_kdop_wave(P, bodies, d, **swept)
+    print(f"{fixture}: {both} of {n} waves hold both verdicts, {want.mean():.0%} of the candidates pass")
+    assert np.array_equal(got[np.arange(n), lane], g[fixture].astype(float))                               # the reference's verdict, on its lane
+    assert np.array_equal(got, want.astype(float))                                                         # all 64 verdicts of every wave
+    part = katsolver.kat_kdop_wave(P, bodies, d, nc=lane + 1, **swept)
+    have = np.arange(64)[None, :] <= lane[:, None]
+    assert np.array_equal(part[have], got[have])                                                           # a wave's verdicts do not depend on how many candidates it holds
+    assert not part[~have].any()
+
+
 def test_device_llt_and_min_eigenvalue(katsolver):
     g = gold("prims_kat.npz")
     out = katsolver.kat_linalg(g["llt_mats"])

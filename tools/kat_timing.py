@@ -19,4 +19,6 @@ P, Q = p["P"][ok][:64], p["Q"][ok][:64]
 print("plane_pair (gjk+newton) 64 cases: %.1f" % t(lambda: s.kat_planes(1, P, Q, 0.3)), " same case x64: %.1f" % t(lambda: s.kat_planes(1, P[:1].repeat(64, 0), Q[:1].repeat(64, 0), 0.3)))
 print("plane_obs 64 cases: %.1f" % t(lambda: s.kat_planes(0, p["P"][:64], p["q"][:64], 0.2)))
 print("kdop hull/hull 64 cases: %.1f" % t(lambda: s.kat_planes(3, P, Q, 0.3)))
-print("empty-ish (kdop point): %.1f" % t(lambda: s.kat_planes(2, p["P"][:64], p["q"][:64], 0.2)))
+print("kdop hull/point, 64 waves of one candidate: %.1f" % t(lambda: s.kat_planes(2, p["P"][:64], p["q"][:64], 0.2)))
+cand = p["q"][:64, None, None, :] + 0.01 * np.arange(64)[None, :, None, None]
+print("kdop hull/point, 64 waves of 64 candidates (kdop_cull_wave as the walks run it): %.1f" % t(lambda: s.kat_kdop_wave(p["P"][:64], cand, 0.2)))

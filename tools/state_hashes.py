@@ -8,7 +8,8 @@ The P<n> legs (eight robots, `pieces` = n, res = 8) walk the layouts of the line
 the planner (tj_kat_plan), not by hand: 7 = eight groups, affine trial hulls, planes in LDS (plane_cap 133); 8 = the same with plane_cap 0 (planes read from global memory);
 10 = eight groups, hulls from the basis; 11 = four groups; 19 = two groups; 27 = one group; P20c = two groups in the coupled mode (a round in four passes).
 fleet256 (the scene of test_passing_long_pair_solves_on_changes_no_bit) is the one leg in the one-pair-per-lane regime of the pair solve, with its passed-on consumers:
-pair_solves / iterations must exceed 4096 there."""
+pair_solves / iterations must exceed 4096 there.
+H8tri / H8tri-c: H8's cloud as obstacle triangles (BASELINE config 5's geometry), decoupled and coupled -- the PRIM == 3 paths of the walk, the cull and the solve."""
 import sys, os, importlib, hashlib, ctypes as C
 import numpy as np
 ROOT = os.environ.get("GRAFT_REPO_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,7 +34,8 @@ def layout_leg(pieces, mode=1):
 
 for name, mk, kw in (("A", sc.scn_a, {}), ("B", sc.scn_b, {}), ("C", sc.scn_c, {}), ("H8", lambda: sc.hard(8, 8000), {}), ("Bc", lambda: dict(sc.scn_b(), mode=2), {}), ("Cc", lambda: dict(sc.scn_c(), mode=2), {}),
                      ("B-optplane", sc.scn_b, {"optimal_plane": 1}), ("fleet100", lambda: sc.crossing(100, 20000, seed=121), {}), ("fleet256", lambda: sc.crossing(256, 20000, seed=31), {}), ("P7", lambda: sc.crossing(8, 8000, seed=5, pieces=7), {}),
-                     ("P8", layout_leg(8), {}), ("P10", layout_leg(10), {}), ("P11", layout_leg(11), {}), ("P19", layout_leg(19), {}), ("P27", layout_leg(27), {}), ("P20c", layout_leg(20, mode=2), {})):
+                     ("P8", layout_leg(8), {}), ("P10", layout_leg(10), {}), ("P11", layout_leg(11), {}), ("P19", layout_leg(19), {}), ("P27", layout_leg(27), {}), ("P20c", layout_leg(20, mode=2), {}),
+                     ("H8tri", lambda: sc.triangulate(sc.hard(8, 8000), size=0.025), {}), ("H8tri-c", lambda: dict(sc.triangulate(sc.hard(8, 8000), size=0.025), mode=2), {})):
     s = pkg.Solver(mk(), stop=0.0, **kw)
     for b in (1, n // 2, n - 1 - n // 2):
         s.iterate_async(b); s.sync()

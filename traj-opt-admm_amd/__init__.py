@@ -327,7 +327,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_kdop_wave", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -762,6 +762,19 @@ class Solver:
         arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in (P, D, tri, t)]
         n = arrs[0].shape[0]; out = np.zeros((n, 8))
         self._check(self.lib.tj_kat_tri(self._ctx, C.c_int(n), *[_d(x) for x in arrs], C.c_double(dist), C.c_double(off), _d(out)))
+        return out
+
+    def kat_kdop_wave(self, P, bodies, d, D=None, t=None, nc=None):
+        """the obstacle 49-axis cull as the walks run it, one wave per case: P[n][6][3], bodies[n][per][prim][3] (prim 1 or 3, per <= 64) -> pass[n][per];
+        D, t: the swept hull conv{P, P + t D}; nc[n]: only the first nc[i] candidates of case i take part"""
+        P = np.ascontiguousarray(P, dtype=np.float64); bodies = np.ascontiguousarray(bodies, dtype=np.float64)
+        n, per, prim = bodies.shape[:3]
+        swept = D is not None
+        D = np.ascontiguousarray(D, dtype=np.float64) if swept else None; t = np.ascontiguousarray(t, dtype=np.float64) if swept else None
+        nc = None if nc is None else np.ascontiguousarray(nc, dtype=np.int32)
+        out = np.zeros((n, per))
+        self._check(self.lib.tj_kat_kdop_wave(self._ctx, C.c_int(prim), C.c_int(swept), C.c_int(n), C.c_int(per), _d(P), _d(D) if swept else None, _d(t) if swept else None,
+                                              _d(bodies), None if nc is None else _i(nc), C.c_double(d), _d(out)))
         return out
 
     def kat_linalg(self, mats):

@@ -588,6 +588,12 @@ __device__ __forceinline__ void swept_put_boxes(const Dev& D, double* rec, int u
   put(rec + CCD_OBOX + a, b.lo); put(rec + CCD_OBOX + 3 + a, b.hi); put(rec + CCD_PBOX + a, b.lo2); put(rec + CCD_PBOX + 3 + a, b.hi2);
   put_cbox(D.cbox + ((size_t)tr * 6 + a) * D.U + u, b.lo2); put_cbox(D.cbox + ((size_t)tr * 6 + 3 + a) * D.U + u, b.hi2);
 }
+// the swept hull's interval on the k-DOP axis k: over P and PS = P + step * D (CCD::KDOPCCD, CCD.h:415-533)
+__device__ __forceinline__ void swept_kdop_axis(const V3& k, const double* P, const double* PS, double& lo, double& up) {
+  lo = INFINITY; up = -INFINITY;
+  kdop_interval6(k.x, k.y, k.z, P, lo, up);
+  kdop_interval6(k.x, k.y, k.z, PS, lo, up);
+}
 template <class Put>
 __device__ __forceinline__ void swept_put_interval(double* rec, int ax, double lo, double up, Put&& put) { put(rec + CCD_KLO + ax, lo); put(rec + CCD_KHI + ax, up); }
 // one wave, the hulls P, Dh, PD and PS = P + Dh complete in LDS: this lane's share of the record `rec` of (u, tr) -- hull entries (lanes 0..17), box axis (0..2), interval on
@@ -598,10 +604,8 @@ __device__ __forceinline__ void swept_record_put(const Dev& D, double* rec, int 
   if (lane < 18) swept_put_hull(rec, lane, P[lane], Dh[lane], put);
   if (lane < 3) swept_put_boxes(D, rec, u, tr, lane, swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; }), put, put_cbox);
   if (lane < 49) {
-    const V3 k = axis();
-    double up = -INFINITY, lo = INFINITY;
-    kdop_interval6(k.x, k.y, k.z, P, lo, up);
-    kdop_interval6(k.x, k.y, k.z, PS, lo, up);
+    double lo, up;
+    swept_kdop_axis(axis(), P, PS, lo, up);
     swept_put_interval(rec, lane, lo, up, put);
   }
 }

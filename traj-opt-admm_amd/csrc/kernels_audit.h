@@ -37,7 +37,7 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
   const int lane = lane_id(), S = D.S;
   const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
   __shared__ double P[18], tile[18 * 64];
-  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  __shared__ int walk[WalkScratch::INTS];
   QBox q;
   query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
   const double range = A.range;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void k_audit(Dev D, AuditArgs A) {
 
   // ---- obstacles: every primitive whose box is within `range` of the hull's box, one per lane ----
   double od = range; int oi = INT_MAX;
-  bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
+  bvh_query<1, PRIM>(D, q, range, WalkScratch::carve(walk), nullptr, [&](int pt) {
     if (pt >= 0) {
       const V3 v = gjk(BodyHull{P}, PrimOf<PRIM>::load(D, pt));
       const double d = norm3(v.x, v.y, v.z);

@@ -1,5 +1,5 @@
 // kernels_debug.h -- known-answer entry points: run the SAME device functions the hot-path kernels
-// use (gjk, plane_obstacle, plane_pair, k-DOP tests, swept-hull CCD predicates, chol / min-eig) on
+// use (gjk, plane_from_witness_body, plane_pair, the k-DOP cull and comparison, swept-hull CCD predicates, chol / min-eig) on
 // caller-supplied batches, one case per lane (or per workgroup for the LDS linear algebra), so the
 // parity tests can compare them bit-for-bit against vectors produced by the reference
 // (tests/golden/gjk_kat.npz, prims_kat.npz).
@@ -71,33 +71,30 @@ __global__ __launch_bounds__(64) void k_dbg_pair_wave(Dev D, int n, const double
   if (threadIdx.x == 0) { double* o = out + (size_t)i * 5; o[0] = ok; o[1] = e0; o[2] = e1; o[3] = e2; o[4] = dpl; }
 }
 
-// what: 0 plane_obstacle(P,q) -> out[5] = ok,c,d ; 1 plane_pair(P,Q) with Newton refine -> ok,c,d ;
-//       2 k-DOP hull/point ; 3 k-DOP hull/hull   (out[0] = pass)
+// what: 0 hull / point plane as obs_solve_body's batch path forms it -> out[5] = ok,c,d ; 1 plane_pair(P,Q) with Newton refine -> ok,c,d ;
+//       3 k-DOP hull/hull: both hulls' intervals by hull_kdop_axis and kdop_apart, the arithmetic of pair_tile_filter (out[0] = pass)   (2, hull / point: k_dbg_kdop_wave)
 __global__ __launch_bounds__(64) void k_dbg_planes(Dev D, int what, int n, const double* P, const double* Q, double dist, double* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double* p = P + (size_t)i * 18;
   double* o = out + (size_t)i * 5;
   if (what == 0) {
-    const V3 q{Q[3 * i], Q[3 * i + 1], Q[3 * i + 2]};
+    const BodyPoint q{V3{Q[3 * i], Q[3 * i + 1], Q[3 * i + 2]}};
     double c0 = 0, c1 = 0, c2 = 0, dd = 0;
-    const bool ok = plane_obstacle(p, q, dist, D.offset, c0, c1, c2, dd);
+    const bool ok = plane_from_witness_body(gjk(BodyHull{p}, q), q, dist, D.offset, c0, c1, c2, dd);
     o[0] = ok; o[1] = c0; o[2] = c1; o[3] = c2; o[4] = dd;
   } else if (what == 1) {
     double e0 = 0, e1 = 0, e2 = 0, dpl = 0; bool capped;
     const bool ok = plane_pair(p, Q + (size_t)i * 18, dist, D.margin, D.offset, true, e0, e1, e2, dpl, capped);
     o[0] = ok; o[1] = e0; o[2] = e1; o[3] = e2; o[4] = dpl;
-  } else if (what == 2) {
-    double klo[49], khi[49];
-    for (int k = 0; k < 49; k++) {
-      const double x = D.kdop[3 * k], y = D.kdop[3 * k + 1], z = D.kdop[3 * k + 2];
-      double up = -INFINITY, lo = INFINITY;
-      for (int j = 0; j < 6; j++) { const double lv = x * p[3 * j] + y * p[3 * j + 1] + z * p[3 * j + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-      klo[k] = lo; khi[k] = up;
-    }
-    o[0] = kdop_point_pass(D, klo, khi, V3{Q[3 * i], Q[3 * i + 1], Q[3 * i + 2]}, dist);
   } else if (what == 3) {
-    o[0] = kdop_hulls_pass(D, p, Q + (size_t)i * 18, dist);
+    bool sep = false;
+    for (int k = 0; k < 49; k++) {
+      double alo, ahi, blo, bhi;
+      hull_kdop_axis(D, p, k, alo, ahi); hull_kdop_axis(D, Q + (size_t)i * 18, k, blo, bhi);
+      sep = sep | kdop_apart(alo, ahi, blo, bhi, dist);
+    }
+    o[0] = !sep;
   } else if (what == 5) {  // Optimal_plane::optimal_cd: o[1..4] = (c, d) in/out, o[0] = finished within the iteration caps
     double cx = o[1], cy = o[2], cz = o[3], d = o[4];
     o[0] = opt_plane_obstacle(p, Q[3 * i], Q[3 * i + 1], Q[3 * i + 2], D.margin, D.offset, cx, cy, cz, d);
@@ -132,7 +129,7 @@ __global__ __launch_bounds__(64) void k_dbg_ccd(int n, const double* P, const do
 }
 
 // triangle obstacle bodies (BASELINE config 5), one case per lane: out[i][8] = plane ok, c, d (hull P vs triangle, distance
-// dist) | k-DOP pass hull/triangle at dist | k-DOP pass swept hull {P, P + t D}/triangle at off | GJK CCD hit at off
+// dist) | o[5], o[6]: the two k-DOP verdicts, left to k_dbg_kdop_wave | GJK CCD hit at off
 __global__ __launch_bounds__(64) void k_dbg_tri(Dev D, int n, const double* P, const double* Dd, const double* tri, const double* t, double dist, double off, double* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -142,22 +139,33 @@ __global__ __launch_bounds__(64) void k_dbg_tri(Dev D, int n, const double* P, c
   double c0 = 0, c1 = 0, c2 = 0, pd = 0;
   const bool ok = plane_from_witness_body(gjk(BodyHull{p}, tb), tb, dist, D.offset, c0, c1, c2, pd);
   o[0] = ok; o[1] = c0; o[2] = c1; o[3] = c2; o[4] = pd;
-  double klo[49], khi[49];
-  for (int pass = 0; pass < 2; pass++) {
-    for (int k = 0; k < 49; k++) {
-      const double x = D.kdop[3 * k], y = D.kdop[3 * k + 1], z = D.kdop[3 * k + 2];
-      double up = -INFINITY, lo = INFINITY;
-      for (int j = 0; j < 6; j++) { const double lv = x * p[3 * j] + y * p[3 * j + 1] + z * p[3 * j + 2]; if (lv < lo) lo = lv; if (lv > up) up = lv; }
-      if (pass) for (int j = 0; j < 6; j++) {
-        const double lv = x * (p[3 * j] + t[i] * dd[3 * j]) + y * (p[3 * j + 1] + t[i] * dd[3 * j + 1]) + z * (p[3 * j + 2] + t[i] * dd[3 * j + 2]);
-        if (lv < lo) lo = lv; if (lv > up) up = lv;
-      }
-      klo[k] = lo; khi[k] = up;
-    }
-    o[5 + pass] = kdop_body_pass(D.kdop, klo, khi, tb, pass ? off : dist);
-  }
   const V3 v = gjk(BodySwept{p, dd, t[i]}, tb);
   o[7] = (v.x * v.x + v.y * v.y + v.z * v.z <= off * off);
+}
+
+// The obstacle k-DOP cull in the product's form, one wave per case: kdop_cull_wave (lanes over the axes, candidates by readlane) on the hull's intervals from
+// hull_kdop_axis -- SWEPT: of conv{P, P + t D} from swept_kdop_axis, the swept record's --, `per` candidates (bodies[n][per][PRIM][3]) of which the first nc[i]
+// (nc == nullptr: all) sit on the lanes; out[(i * per + j) * ostride] = candidate j's verdict
+template <int PRIM, bool SWEPT>
+__global__ __launch_bounds__(64) void k_dbg_kdop_wave(Dev D, int n, const double* P, const double* Dd, const double* t, const double* bodies, int per, const int* nc, double d, double* out, int ostride) {
+  const int i = blockIdx.x, lane = lane_id();
+  if (i >= n) return;
+  __shared__ double H[18], PS[18];
+  if (lane < 18) {
+    H[lane] = P[(size_t)i * 18 + lane];
+    if constexpr (SWEPT) PS[lane] = H[lane] + t[i] * Dd[(size_t)i * 18 + lane];
+  }
+  __syncthreads();
+  const int ax = min(lane, 48);
+  const V3 axv{D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2]};
+  double lo, hi;
+  if constexpr (SWEPT) swept_kdop_axis(axv, H, PS, lo, hi); else hull_kdop_axis(D, H, ax, lo, hi);
+  const int m = nc ? min(nc[i], per) : per;
+  const double* b = bodies + ((size_t)i * per + min(lane, per - 1)) * 3 * PRIM;
+  typename PrimOf<PRIM>::Body qb;
+  if constexpr (PRIM == 1) qb = BodyPoint{V3{b[0], b[1], b[2]}}; else qb = BodyTri{V3{b[0], b[1], b[2]}, V3{b[3], b[4], b[5]}, V3{b[6], b[7], b[8]}};
+  const bool pass = kdop_cull_wave(qb, m, axv, lo, hi, d, lane);
+  if (lane < m) out[((size_t)i * per + lane) * ostride] = pass;
 }
 
 // broad-phase known answers: one wavefront per caller-supplied query box, raw candidate list (sorted primitive indices,
@@ -167,14 +175,14 @@ template <int PRIM, int BQ_UNROLL, bool PRE>
 __global__ __launch_bounds__(64) void k_dbg_query(Dev D, int nq, const double* boxes, double m, int cap, int* out_ids, int* out_n) {
   const int b = blockIdx.x;
   if (b >= nq) return;
-  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  __shared__ int walk[WalkScratch::INTS];
   TopBox topb{};
   if constexpr (PRE) topb = bvh_top_box(D);
   QBox q;
   for (int k = 0; k < 3; k++) { q.lo[k] = boxes[6 * (size_t)b + k]; q.hi[k] = boxes[6 * (size_t)b + 3 + k]; }
   int base = 0;
   unsigned long long visits = 0;
-  bvh_query<BQ_UNROLL, PRIM>(D, q, m, fa, fb, cand, &visits, [&](int pt) {
+  bvh_query<BQ_UNROLL, PRIM>(D, q, m, WalkScratch::carve(walk), &visits, [&](int pt) {
     const bool ok = pt >= 0;
     const unsigned long long mask = ballot(ok);
     const int idx = base + prefix_count(mask);

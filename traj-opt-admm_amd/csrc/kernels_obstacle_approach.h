@@ -64,13 +64,13 @@ __global__ __launch_bounds__(64) void k_obst_seed(Dev D, ObstArgs A) {
   const int lane = lane_id(), S = D.S;
   const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
   __shared__ double P[18];
-  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  __shared__ int walk[WalkScratch::INTS];
   QBox q;
   query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
   const double range = A.range;
   QBest mine{range, 0.0, INT_MAX, INT_MAX};
   int nev = 0;
-  bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
+  bvh_query<1, PRIM>(D, q, range, WalkScratch::carve(walk), nullptr, [&](int pt) {
     if (pt >= 0) {
       const auto prim = PrimOf<PRIM>::load(D, pt);
       const double h0 = obst_point_dist<PRIM>(V3{P[0], P[1], P[2]}, prim), h5 = obst_point_dist<PRIM>(V3{P[15], P[16], P[17]}, prim);
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(64) void k_obst_append(Dev D, ObstArgs A) {
   const int lane = lane_id(), S = D.S;
   const int ui = blockIdx.x / S, tr = blockIdx.x - ui * S, u = D.u0 + ui;
   __shared__ double P[18];
-  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  __shared__ int walk[WalkScratch::INTS];
   QBox q;
   query_hull(D, A.net + (size_t)u * 3 * D.T, tr, P, q);
   const double range = A.range;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64) void k_obst_append(Dev D, ObstArgs A) {
   if (tr == 0 && lane == 0) A.best[u] = best;
   ObstItem* list = A.list + (size_t)ui * 2 * A.cap;
   double mlo = INFINITY;
-  bvh_query<1, PRIM>(D, q, range, fa, fb, cand, nullptr, [&](int pt) {
+  bvh_query<1, PRIM>(D, q, range, WalkScratch::carve(walk), nullptr, [&](int pt) {
     if (pt >= 0) {
       const auto prim = PrimOf<PRIM>::load(D, pt);
       const BodyHull hull{P};

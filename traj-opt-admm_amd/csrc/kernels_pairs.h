@@ -106,8 +106,8 @@ __device__ __forceinline__ int pair_work_slot(const Dev& D, const int* pre, int 
 // intervals).  Box test: lanes over the 64 partners (their boxes in registers, loaded once), loop over the R rows (boxes
 // broadcast from LDS); hits are appended to list[] as (p0 << 16 | p1) in (p0, p1) order.  Then, per box survivor, lanes over the
 // 49 axes against both robots' interval records; the records of FOUR pairs are fetched together -- the loop is a chain of
-// memory latencies, not of arithmetic -- and the list is compacted in place.  Same comparisons as the one-pair-at-a-time
-// forms (CCD.h:535-587), hence the same decisions.  Returns the number of pairs left in list[].
+// memory latencies, not of arithmetic -- and the list is compacted in place.  The two comparisons are kernels_sep.h's box_near and
+// kdop_apart, the ones of the one-pair-at-a-time forms (CCD.h:535-587), hence the same decisions.  Returns the number of pairs left in list[].
 //   segbox  [6][U] lo.xyz, hi.xyz of every robot for this segment      rec(q) -> robot q's record, intervals lo at LO, hi at HI
 //   [own0, own1): robots of this rank -- a pair is skipped unless it touches one (sharded contexts; pass 0, U otherwise)
 template <bool FA = false, class RecOf>   // FA (asynchronous front): boxes and records were written (through) by blocks of a kernel that runs at the same time -- read past the caches
@@ -126,9 +126,8 @@ __device__ __forceinline__ int pair_tile_filter(const double* segbox, int U, int
   for (int r = 0; r < R; r++) {
     const int p0 = rb + r;
     if (p0 >= U - 1) break;   // uniform
-    bool hit = p1 < U && p1 > p0 && (own1p || (p0 >= own0 && p0 < own1));
-#pragma unroll
-    for (int k = 0; k < 3; k++) hit = hit & !((bv[3 + k] + d < rowbox[6 * r + k]) | (bv[k] > rowbox[6 * r + 3 + k] + d));
+    const bool listed = p1 < U && p1 > p0 && (own1p || (p0 >= own0 && p0 < own1));
+    const bool hit = listed & box_near(bv, bv + 3, rowbox + 6 * r, rowbox + 6 * r + 3, d);
     const unsigned long long mask = ballot(hit);
     if (hit) list[n + prefix_count(mask)] = (p0 << 16) | p1;
     n += __popcll(mask);
@@ -150,7 +149,7 @@ __device__ __forceinline__ int pair_tile_filter(const double* segbox, int U, int
 #pragma unroll
     for (int c = 0; c < PT_FLIGHT; c++) {
       if (base + c >= n) break;
-      const bool sep = lane < 49 && (bhi[c] < alo[c] - d || ahi[c] < blo[c] - d);
+      const bool sep = lane < 49 && kdop_apart(alo[c], ahi[c], blo[c], bhi[c], d);
       if (ballot(sep) == 0ull) {
         if (lane == 0) list[m] = pr[c];
         m++;
@@ -705,8 +704,9 @@ __device__ __forceinline__ void compact_segment(const Dev& D, int u, int tr, int
     int base = 0;
     for (int s0 = 0; s0 < n; s0 += 64) {
       const int sl = s0 + lane, slc = min(sl, n - 1);
-      const int stamp = D.ostamp[seg * D.cap_obs + slc];
-      const double* p = D.oraw + (seg * D.cap_obs + slc) * 4;
+      const size_t slot = obs_plane_slot(D, seg, slc);
+      const int stamp = D.ostamp[slot];
+      const double* p = D.oraw + slot * 4;
       const double o0 = p[0], o1 = p[1], o2 = p[2], o3 = p[3];   // (issued with the stamp; the 64 candidate slots fetched with the first trip, whatever the count, measured slower)
       const bool ok = sl < n && stamp == epoch;
       const unsigned long long mask = ballot(ok);

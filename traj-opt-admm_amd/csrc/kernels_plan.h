@@ -29,7 +29,7 @@ template <int PRIM>
 __global__ __launch_bounds__(64) void k_edge_hit(Dev D, int n, const double* pieces, const int* owner, int n_prior, const double* prior, double d, int* hit) {
   const int e = blockIdx.x, lane = lane_id();
   if (e >= n) return;
-  __shared__ int fa[FRONT_CAP], fb[FRONT_CAP], cand[128];
+  __shared__ int walk[WalkScratch::INTS];
   const double* E = pieces + 6 * (size_t)e;
   const BodyEdge eb{V3{E[0], E[1], E[2]}, V3{E[3], E[4], E[5]}};
   bool h = false;
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(64) void k_edge_hit(Dev D, int n, const double* pie
 #pragma unroll
   for (int k = 0; k < 3; k++) { q.lo[k] = fmin(E[k], E[3 + k]); q.hi[k] = fmax(E[k], E[3 + k]); }
   unsigned long long visits = 0;
-  bvh_query<1, PRIM>(D, q, d, fa, fb, cand, &visits, [&](int pt) {
+  bvh_query<1, PRIM>(D, q, d, WalkScratch::carve(walk), &visits, [&](int pt) {
     if (pt >= 0) {
       const V3 v = gjk(eb, PrimOf<PRIM>::load(D, pt));
       h |= (v.x * v.x + v.y * v.y + v.z * v.z <= d * d);

@@ -24,12 +24,19 @@ namespace tj {
 
 struct QBox { double lo[3], hi[3]; };
 
-__device__ __forceinline__ bool box_hit(const float* b, const QBox& q, double m) {
-  // query.overlaps(node): reject if node.hi + m < q.lo or node.lo > q.hi + m on any axis
+// THE box predicate of the walk, the leaves and the pair tiles: the box [lo, hi] is within m of the query box [qlo, qhi] -- rejected if hi + m < qlo or
+// lo > qhi + m on any axis (query.overlaps(node), AABB.cc:141: touching counts).  fp64 bounds; an fp32 box (rounded outward) converts at the call.
+// box_near_axis is the predicate on one axis, for a caller that forms its bounds axis by axis (the triangle leaf).
+__device__ __forceinline__ bool box_near_axis(double lo, double hi, double qlo, double qhi, double m) { return !((hi + m < qlo) | (lo > qhi + m)); }
+__device__ __forceinline__ bool box_near(const double* lo, const double* hi, const double* qlo, const double* qhi, double m) {
   bool hit = true;
 #pragma unroll
-  for (int k = 0; k < 3; k++) hit = hit && !((double)b[3 + k] + m < q.lo[k] || (double)b[k] > q.hi[k] + m);
+  for (int k = 0; k < 3; k++) hit = hit & box_near_axis(lo[k], hi[k], qlo[k], qhi[k], m);
   return hit;
+}
+__device__ __forceinline__ bool box_near(const float* b, const QBox& q, double m) {   // b: lo.xyz, hi.xyz
+  const double d[6] = {(double)b[0], (double)b[1], (double)b[2], (double)b[3], (double)b[4], (double)b[5]};
+  return box_near(d, d + 3, q.lo, q.hi, m);
 }
 
 // ---- obstacle primitives as GJK bodies ----
@@ -63,8 +70,55 @@ __device__ __forceinline__ TopBox bvh_top_box(const Dev& D) {
   for (int k = 0; k < 6; k++) t.b[k] = p[k];
   return t;
 }
+// The walk's LDS scratch, one wave's: the two frontiers and the candidate buffer (CAND = 128: the leaves flush at 64, and a chunk's up to 64 hits land behind
+// up to 63 kept ones).  A kernel declares INTS ints (or counts DOUBLES into a buffer of doubles it carves) and hands carve() of them to bvh_query.
+struct WalkScratch {
+  static constexpr int CAND = 128, INTS = 2 * FRONT_CAP + CAND, DOUBLES = INTS / 2;
+  int *fa, *fb, *cand;
+  static __device__ __forceinline__ WalkScratch carve(void* p) { int* a = (int*)p; return WalkScratch{a, a + FRONT_CAP, a + 2 * FRONT_CAP}; }
+};
+// Lanes over a chunk of the frontier, FAN children per node (8: one level down; 64: the grandchildren, a level pair in one step): 64 / FAN frontier nodes
+// per chunk, lane -> (the chunk's slot in the frontier, the child of that slot's node).  The leaves are the children of the last frontier at FAN 8.
+template <int FAN> __device__ __forceinline__ int walk_slot(int base, int c, int lane) { return base + (64 / FAN) * c + lane / FAN; }
+template <int FAN> __device__ __forceinline__ int walk_child(int node, int lane) { return node * FAN + lane % FAN; }
+// ONE step of the walk: frontier cur[0, count) -> the survivors among its nodes' FAN-children on level lv, into nxt in frontier order; returns their number.
+// Each step is a dependent global load (~0.7 us).  BQ_UNROLL chunks are therefore fetched together: all box loads of the group are issued first (branch-free,
+// clamped addresses), then the chunks are tested and compacted one by one in frontier order (the order of the survivors, and with it of the candidate
+// list, is unchanged).  More than FRONT_CAP survivors: ERR_FRONT_OVERFLOW, the step ends with what it has.
+template <int FAN, int BQ_UNROLL>
+__device__ __forceinline__ int walk_step(const Dev& D, const QBox& q, double m, int lv, const int* cur, int* nxt, int count, unsigned long long& nv) {
+  constexpr int NODES = 64 / FAN;
+  const int lane = lane_id(), nl = D.lvl_n[lv];
+  const float* lvl = D.boxes + (size_t)D.lvl_off[lv] * 6;
+  int ncount = 0; bool overflow = false;
+  for (int base = 0; base < count && !overflow; base += NODES * BQ_UNROLL) {
+    int child[BQ_UNROLL]; bool live[BQ_UNROLL]; float bx[BQ_UNROLL][6];
+#pragma unroll
+    for (int c = 0; c < BQ_UNROLL; c++) {
+      const int slot = walk_slot<FAN>(base, c, lane);
+      child[c] = walk_child<FAN>(cur[min(slot, count - 1)], lane);
+      live[c] = slot < count && child[c] < nl;
+      const float* b = lvl + (size_t)min(child[c], nl - 1) * 6;
+#pragma unroll
+      for (int k = 0; k < 6; k++) bx[c][k] = b[k];
+    }
+#pragma unroll
+    for (int c = 0; c < BQ_UNROLL; c++) {
+      if (base + NODES * c >= count) break;
+      const bool hit = live[c] & box_near(bx[c], q, m);
+      const unsigned long long mask = ballot(hit);
+      const int tot = __popcll(mask);
+      if (ncount + tot > FRONT_CAP) { if (lane == 0) atomicOr(&D.ctl->error, ERR_FRONT_OVERFLOW); overflow = true; break; }
+      if (hit) nxt[ncount + prefix_count(mask)] = child[c];
+      ncount += tot;
+      nv += FAN * min(NODES, count - (base + NODES * c));
+    }
+  }
+  __syncthreads();
+  return ncount;
+}
 template <int BQ_UNROLL, int PRIM, class F>
-__device__ int bvh_query(const Dev& D, const QBox& q, double m, int* fa, int* fb, int* cand, unsigned long long* visits, F&& process, const TopBox* pre = nullptr) {
+__device__ int bvh_query(const Dev& D, const QBox& q, double m, const WalkScratch& ws, unsigned long long* visits, F&& process, const TopBox* pre = nullptr) {
   const int lane = lane_id();
   if (D.N == 0) return 0;
   int top = D.nlevels - 1;
@@ -73,103 +127,36 @@ __device__ int bvh_query(const Dev& D, const QBox& q, double m, int* fa, int* fb
   {
     const int n = D.lvl_n[top];
     bool hit = false;
-    if (lane < n) hit = pre ? box_hit(pre->b, q, m) : box_hit(D.boxes + (size_t)(D.lvl_off[top] + lane) * 6, q, m);
+    if (lane < n) hit = box_near(pre ? pre->b : D.boxes + (size_t)(D.lvl_off[top] + lane) * 6, q, m);
     const unsigned long long mask = ballot(hit);
-    if (hit) fa[prefix_count(mask)] = lane;
+    if (hit) ws.fa[prefix_count(mask)] = lane;
     count = __popcll(mask);
     nv += n;
   }
   if (count == 0) { if (visits) *visits += nv; return 0; }   // wave-uniform: nothing of the obstacle set is near this box (the common case)
   __syncthreads();
-  int* cur = fa; int* nxt = fb;
+  int* cur = ws.fa; int* nxt = ws.fb; int* const cand = ws.cand;
+  auto step = [&](int ncount) { int* t = cur; cur = nxt; nxt = t; count = ncount; };
   // DOUBLE STEPS while the frontier is small (the top of a deep pyramid: 1 M primitives are five levels): the 64 GRANDchildren of a frontier node are tested by
   // the 64 lanes at once -- one dependent round trip per two levels instead of two.  A box contains its children's boxes (unions, rounded outward monotonically),
   // so a grandchild that is hit has a hit parent: the survivors at level lv - 1 are the same nodes in the same (ascending) order as after two single steps.
   while (top >= 2 && count <= BVH_SKIP_MAX && D.bvh_skip) {
-    const int lv = top - 2, nl = D.lvl_n[lv];
-    const float* lvl = D.boxes + (size_t)D.lvl_off[lv] * 6;
-    int ncount = 0; bool overflow = false;
-    for (int base = 0; base < count && !overflow; base += BQ_UNROLL) {
-      int gc[BQ_UNROLL]; bool live[BQ_UNROLL]; float bx[BQ_UNROLL][6];
-#pragma unroll
-      for (int c = 0; c < BQ_UNROLL; c++) {
-        const int node = cur[min(base + c, count - 1)];
-        gc[c] = node * 64 + lane;
-        live[c] = base + c < count && gc[c] < nl;
-        const float* b = lvl + (size_t)min(gc[c], nl - 1) * 6;
-#pragma unroll
-        for (int k = 0; k < 6; k++) bx[c][k] = b[k];
-      }
-#pragma unroll
-      for (int c = 0; c < BQ_UNROLL; c++) {
-        if (base + c >= count) break;
-        bool hit = live[c];
-#pragma unroll
-        for (int k = 0; k < 3; k++) hit = hit & !(((double)bx[c][3 + k] + m < q.lo[k]) | ((double)bx[c][k] > q.hi[k] + m));
-        const unsigned long long mask = ballot(hit);
-        const int tot = __popcll(mask);
-        if (ncount + tot > FRONT_CAP) { if (lane == 0) atomicOr(&D.ctl->error, ERR_FRONT_OVERFLOW); overflow = true; break; }
-        if (hit) nxt[ncount + prefix_count(mask)] = gc[c];
-        ncount += tot;
-        nv += 64;
-      }
-    }
-    __syncthreads();
-    int* t = cur; cur = nxt; nxt = t;
-    count = ncount;
+    step(walk_step<64, BQ_UNROLL>(D, q, m, top - 2, cur, nxt, count, nv));
     top -= 2;
     if (count == 0) break;
   }
-  // Each step of the walk is a dependent global load (~0.7 us).  BQ_UNROLL chunks of 8 frontier nodes are therefore
-  // fetched together: all box loads of the group are issued first (branch-free, clamped addresses), then the chunks are
-  // tested and compacted one by one in frontier order (the order of the survivors, and with it of the candidate list,
-  // is unchanged).
-  for (int lv = top - 1; lv >= 0; lv--) {
-    int ncount = 0;
-    const int nl = D.lvl_n[lv];
-    const float* lvl = D.boxes + (size_t)D.lvl_off[lv] * 6;
-    bool overflow = false;
-    for (int base = 0; base < count && !overflow; base += 8 * BQ_UNROLL) {
-      int child[BQ_UNROLL]; bool live[BQ_UNROLL]; float bx[BQ_UNROLL][6];
-#pragma unroll
-      for (int c = 0; c < BQ_UNROLL; c++) {
-        const int slot = base + 8 * c + (lane >> 3);
-        const int node = cur[min(slot, count - 1)];
-        child[c] = node * 8 + (lane & 7);
-        live[c] = slot < count && child[c] < nl;
-        const float* b = lvl + (size_t)min(child[c], nl - 1) * 6;
-#pragma unroll
-        for (int k = 0; k < 6; k++) bx[c][k] = b[k];
-      }
-#pragma unroll
-      for (int c = 0; c < BQ_UNROLL; c++) {
-        if (base + 8 * c >= count) break;
-        bool hit = live[c];
-#pragma unroll
-        for (int k = 0; k < 3; k++) hit = hit & !(((double)bx[c][3 + k] + m < q.lo[k]) | ((double)bx[c][k] > q.hi[k] + m));
-        const unsigned long long mask = ballot(hit);
-        const int tot = __popcll(mask);
-        if (ncount + tot > FRONT_CAP) { if (lane == 0) atomicOr(&D.ctl->error, ERR_FRONT_OVERFLOW); overflow = true; break; }
-        if (hit) nxt[ncount + prefix_count(mask)] = child[c];
-        ncount += tot;
-        nv += 8 * min(8, count - (base + 8 * c));
-      }
-    }
-    __syncthreads();
-    int* t = cur; cur = nxt; nxt = t;
-    count = ncount;
-  }
+  for (int lv = top - 1; lv >= 0; lv--) step(walk_step<8, BQ_UNROLL>(D, q, m, lv, cur, nxt, count, nv));
   if constexpr (BQ_UNROLL == 4) TJ_TIC(D, K_SEP_OBS, 2);   // timing build: the plane query's walk is done, leaves next
   int nc = 0, found = 0;
   for (int base = 0; base < count; base += 8 * BQ_UNROLL) {
-    int pts[BQ_UNROLL]; bool live[BQ_UNROLL]; double px[BQ_UNROLL], py[BQ_UNROLL], pz[BQ_UNROLL]; float lb[BQ_UNROLL][6];
+    int pts[BQ_UNROLL]; bool live[BQ_UNROLL]; double pp[BQ_UNROLL][3]; float lb[BQ_UNROLL][6];
 #pragma unroll
     for (int c = 0; c < BQ_UNROLL; c++) {  // leaf boxes -> primitives: again all loads of the group first
-      const int slot = base + 8 * c + (lane >> 3);
-      const int pt = cur[min(slot, count - 1)] * 8 + (lane & 7);
+      const int slot = walk_slot<8>(base, c, lane);
+      const int pt = walk_child<8>(cur[min(slot, count - 1)], lane);
       pts[c] = pt; live[c] = slot < count && pt < D.N;
       const int pc = min(pt, D.N - 1);
-      if constexpr (PRIM == 1) { px[c] = D.px[pc]; py[c] = D.py[pc]; pz[c] = D.pz[pc]; }
+      if constexpr (PRIM == 1) { pp[c][0] = D.px[pc]; pp[c][1] = D.py[pc]; pp[c][2] = D.pz[pc]; }
       else {
 #pragma unroll
         for (int k = 0; k < 6; k++) lb[c][k] = D.leafbox[(size_t)pc * 6 + k];
@@ -179,24 +166,19 @@ __device__ int bvh_query(const Dev& D, const QBox& q, double m, int* fa, int* fb
     for (int c = 0; c < BQ_UNROLL; c++) {
       if (base + 8 * c >= count) break;
       bool hit;
-      if constexpr (PRIM == 1) {
-        const double x = px[c], y = py[c], z = pz[c];
-        hit = live[c] & !((x + m < q.lo[0]) | (x > q.hi[0] + m)) & !((y + m < q.lo[1]) | (y > q.hi[1] + m)) & !((z + m < q.lo[2]) | (z > q.hi[2] + m));
-      } else {
+      if constexpr (PRIM == 1) hit = live[c] & box_near(pp[c], pp[c], q.lo, q.hi, m);   // a point is its own box
+      else {
         // fp32 pre-filter (conservative), then the exact box of the three vertices in fp64 (BVH::InitObstacle, BVH.cpp:26-46)
-        bool pre = live[c];
-#pragma unroll
-        for (int k = 0; k < 3; k++) pre = pre & !(((double)lb[c][3 + k] + m < q.lo[k]) | ((double)lb[c][k] > q.hi[k] + m));
         hit = false;
-        if (pre) {
+        if (live[c] & box_near(lb[c], q, m)) {
           const double* t = D.tri + (size_t)pts[c] * 9;
           hit = true;
 #pragma unroll
-          for (int k = 0; k < 3; k++) {
+          for (int k = 0; k < 3; k++) {   // (axis by axis: with the three axes' bounds formed first, k_ccd_obs<3> took 3 more registers and k_ccd_lean<3> 2)
             double lo = INFINITY, hi = -INFINITY;
 #pragma unroll
             for (int j = 0; j < 3; j++) { const double lv = t[3 * j + k]; if (lv < lo) lo = lv; if (lv > hi) hi = lv; }
-            hit = hit & !((hi + m < q.lo[k]) | (lo > q.hi[k] + m));
+            hit = hit & box_near_axis(lo, hi, q.lo[k], q.hi[k], m);
           }
         }
       }
@@ -222,47 +204,15 @@ __device__ int bvh_query(const Dev& D, const QBox& q, double m, int* fa, int* fb
   return found;
 }
 
-// point vs cached hull intervals
-__device__ __forceinline__ bool kdop_point_pass(const Dev& D, const double* klo, const double* khi, const V3& q, double d) {
-  for (int k = 0; k < 49; k++) {
-    const double lv = D.kdop[3 * k] * q.x + D.kdop[3 * k + 1] * q.y + D.kdop[3 * k + 2] * q.z;
-    if (lv < klo[k] - d || khi[k] < lv - d) return false;
-  }
-  return true;
-}
+// THE comparison of the 49-axis test (CCD::KDOPDCD CCD.h:354-413, SelfKDOPDCD :535-587, and their swept forms): the intervals [alo, ahi] and [blo, bhi] of two
+// bodies on one axis are more than d apart.  Two bodies pass the test if no axis says so.
+__device__ __forceinline__ bool kdop_apart(double alo, double ahi, double blo, double bhi, double d) { return (bhi < alo - d) | (ahi < blo - d); }
 
-// obstacle primitive (1 or 3 vertices) vs cached hull intervals: CCD::KDOPDCD / KDOPCCD with the body-2 loop over
-// _position.rows() (CCD.h:391-400; for one vertex it is kdop_point_pass)
-// One candidate per LANE.  The axes come from LDS (kax, staged by stage_kdop_axes) and all 49 are evaluated without an early
-// exit: with the axes in global memory and a `return false` per axis the loop was a chain of up to 49 dependent memory
-// round trips -- 118 us for a segment under an obstacle slab (40 candidates), the whole tail of k_front at 256 robots.
-// Same comparisons, hence the same decision.
-__device__ __forceinline__ void stage_kdop_axes(const Dev& D, double* kax, int lane) {
-  for (int i = lane; i < 147; i += 64) kax[i] = D.kdop[i];
-  __syncthreads();
-}
-template <class B>
-__device__ __forceinline__ bool kdop_body_pass(const double* kax, const double* klo, const double* khi, const B& body, double d) {
-  bool sep = false;
-  for (int k = 0; k < 49; k++) {
-    const double x = kax[3 * k], y = kax[3 * k + 1], z = kax[3 * k + 2];
-    double up = -INFINITY, lo = INFINITY;
-#pragma unroll
-    for (int i = 0; i < B::N; i++) {
-      const V3 p = body.get(i);
-      const double lv = x * p.x + y * p.y + z * p.z;
-      if (lv < lo) lo = lv;
-      if (lv > up) up = lv;
-    }
-    sep = sep | (up < klo[k] - d) | (khi[k] < lo - d);
-  }
-  return !sep;
-}
-
-// The same cull for up to 64 candidates held one per LANE (lanes [0, n)), done by the whole wave: lanes over the 49 AXES
-// (axis and the hull's interval in registers), candidates one after the other with their vertices broadcast by v_readlane.
-// ~20 instructions per point candidate instead of a 49-step loop per lane; returns this lane's verdict.  Same products and
-// sums as kdop_body_pass, hence the same decision.  axv = this lane's axis (x, y, z), lo_ax / hi_ax = hull interval on it.
+// The obstacle cull for up to 64 candidates held one per LANE (lanes [0, n)), done by the whole wave: lanes over the 49 AXES
+// (axis and the hull's interval in registers), candidates one after the other with their vertices broadcast by v_readlane: the body-2 loop over
+// _position.rows() of CCD::KDOPDCD (CCD.h:391-400), all axes without an early exit.  ~20 instructions per point candidate instead of a 49-step loop of
+// dependent memory round trips per lane (118 us for a segment under an obstacle slab, once the whole tail of k_front at 256 robots); returns this lane's
+// verdict.  axv = this lane's axis (x, y, z), lo_ax / hi_ax = hull interval on it.
 template <class B>
 __device__ __forceinline__ bool kdop_cull_wave(const B& body, int n, const V3& axv, double lo_ax, double hi_ax, double d, int lane) {
   unsigned long long pass = 0ull;
@@ -275,11 +225,28 @@ __device__ __forceinline__ bool kdop_cull_wave(const B& body, int n, const V3& a
       if (lv < lo) lo = lv;
       if (lv > up) up = lv;
     }
-    const bool sep = lane < 49 && ((up < lo_ax - d) | (hi_ax < lo - d));
+    const bool sep = lane < 49 && kdop_apart(lo_ax, hi_ax, lo, up, d);
     if (ballot(sep) == 0ull) pass |= 1ull << i;
   }
   return (pass >> lane) & 1ull;
 }
+// The cull as the two obstacle walks call it from bvh_query's process(pt) (obs_query_body: hull intervals at offset + margin; ccd_obs_body: swept intervals at
+// offset): this lane's axis and the hull's interval on it (klo / khi: the 49 intervals, LDS), fetched at the first candidate (wave-uniform) and kept in registers
+// from then on; cull() loads the lane's candidate into qb and returns its verdict (false for a lane without one).  Candidates sit in lanes [0, ncand).
+struct KdopLane {
+  V3 axv{0, 0, 0}; double lo = 0, hi = 0; bool ready = false;
+  template <int PRIM>
+  __device__ __forceinline__ bool cull(const Dev& D, const double* klo, const double* khi, int pt, double d, int lane, typename PrimOf<PRIM>::Body& qb) {
+    if (!ready) {
+      const int ax = min(lane, 48);
+      axv = V3{D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2]}; lo = klo[ax]; hi = khi[ax];
+      ready = true;
+    }
+    const int ncand = __popcll(ballot(pt >= 0));
+    qb = PrimOf<PRIM>::load(D, max(pt, 0));
+    return kdop_cull_wave(qb, ncand, axv, lo, hi, d, lane) && pt >= 0;
+  }
+};
 
 // witness to plane, first step of every form below: the unit normal c = v / |v| of the GJK witness vector v; false (no plane) if the bodies are farther apart than dist
 __device__ __forceinline__ bool plane_normal(const V3& v, double dist, double& c0, double& c1, double& c2) {
@@ -288,15 +255,9 @@ __device__ __forceinline__ bool plane_normal(const V3& v, double dist, double& c
   c0 = v.x / cn; c1 = v.y / cn; c2 = v.z / cn;
   return true;
 }
-// Separate::opengjk (Separate.h:18-163): plane (c,d) between a 6-point hull and one cloud point
-// plane (c,d) from the GJK witness vector v of hull - point (Separate.h:107-151): rejected if |v| > dist
-__device__ __forceinline__ bool plane_from_witness(const V3& v, const V3& qp, double dist, double offset, double& c0, double& c1, double& c2, double& dd) {
-  if (!plane_normal(v, dist, c0, c1, c2)) return false;
-  const double d0 = -c0 * qp.x - c1 * qp.y - c2 * qp.z;
-  dd = d0 - offset;
-  return true;
-}
-// the same for a body of B::N vertices: d0 = min_i(-c . B_i), the loop the reference keeps commented out at Separate.h:123-131
+// Separate::opengjk (Separate.h:18-163): plane (c,d) between a 6-point hull and an obstacle body of B::N vertices, from the GJK witness vector v of
+// hull - body (Separate.h:107-151): rejected if |v| > dist; d0 = min_i(-c . B_i), the loop the reference keeps commented out at Separate.h:123-131 (one
+// vertex, a cloud point: d0 = -c . q)
 template <class B>
 __device__ __forceinline__ bool plane_from_witness_body(const V3& v, const B& body, double dist, double offset, double& c0, double& c1, double& c2, double& dd) {
   if (!plane_normal(v, dist, c0, c1, c2)) return false;
@@ -307,26 +268,14 @@ __device__ __forceinline__ bool plane_from_witness_body(const V3& v, const B& bo
   dd = d0 - offset;
   return true;
 }
-__device__ __forceinline__ bool plane_obstacle(const double* P, const V3& qp, double dist, double offset, double& c0, double& c1, double& c2, double& dd) {
-  return plane_from_witness(gjk(BodyHull{P}, BodyPoint{qp}), qp, dist, offset, c0, c1, c2, dd);
-}
 
-__device__ __forceinline__ double dot_fixed3(double c0, double c1, double c2, const double* r) { return c0 * r[0] + (c1 * r[1] + c2 * r[2]); }  // Eigen unrolled 3-term order (Separate.h:268,276)
-
-// 49-axis test between two 6-point hulls (CCD::SelfKDOPDCD, CCD.h:535-587)
-__device__ inline bool kdop_hulls_pass(const Dev& D, const double* A, const double* Bq, double dist) {
-  for (int k = 0; k < 49; k++) {
-    const double x = D.kdop[3 * k], y = D.kdop[3 * k + 1], z = D.kdop[3 * k + 2];
-    double upA = -INFINITY, loA = INFINITY, upB = -INFINITY, loB = INFINITY;
-    for (int i = 0; i < 6; i++) {
-      const double la = x * A[3 * i] + y * A[3 * i + 1] + z * A[3 * i + 2];
-      if (la < loA) loA = la; if (la > upA) upA = la;
-      const double lb = x * Bq[3 * i] + y * Bq[3 * i + 1] + z * Bq[3 * i + 2];
-      if (lb < loB) loB = lb; if (lb > upB) upB = lb;
-    }
-    if (upB < loA - dist || upA < loB - dist) return false;
-  }
-  return true;
+__device__ __forceinline__ double dot_fixed3(double c0, double c1, double c2, const double* r, int st = 1) { return c0 * r[0] + (c1 * r[st] + c2 * r[2 * st]); }  // Eigen unrolled 3-term order (Separate.h:268,276); st: stride between r's entries
+// the offset of the plane midway between two hulls along the unit normal c (Separate.h:262-280): d = (min over B of -c . B_i + max over A of -c . A_i) / 2
+__device__ __forceinline__ double pair_midplane(double c0, double c1, double c2, const double* A, const double* Bq, int st) {
+  double d0 = INFINITY, d1 = -INFINITY;
+  for (int i = 0; i < 6; i++) { const double t = -dot_fixed3(c0, c1, c2, Bq + 3 * i * st, st); if (d0 > t) d0 = t; }
+  for (int i = 0; i < 6; i++) { const double t = -dot_fixed3(c0, c1, c2, A + 3 * i * st, st); if (d1 < t) d1 = t; }
+  return 0.5 * (d0 + d1);
 }
 
 // Separate::selfgjk (Separate.h:165-304) + Optimal_plane::optimal_d (Optimal_plane.h:13-71).
@@ -351,10 +300,7 @@ __device__ inline bool plane_pair(const double* A, const double* Bq, double dist
 __device__ inline bool plane_pair_finish(const V3& v, const double* A, const double* Bq, double dist, double m, double off, bool refine, double& e0, double& e1c, double& e2c, double& dpl, bool& capped, int* newton_iters, int st) {
   capped = false;
   if (!plane_normal(v, dist, e0, e1c, e2c)) return false;
-  double d0 = INFINITY, d1 = -INFINITY;
-  for (int i = 0; i < 6; i++) { const double t = -(e0 * Bq[(3 * i) * st] + (e1c * Bq[(3 * i + 1) * st] + e2c * Bq[(3 * i + 2) * st])); if (d0 > t) d0 = t; }   // dot_fixed3's order (Eigen unrolled 3-term, Separate.h:268,276)
-  for (int i = 0; i < 6; i++) { const double t = -(e0 * A[(3 * i) * st] + (e1c * A[(3 * i + 1) * st] + e2c * A[(3 * i + 2) * st])); if (d1 < t) d1 = t; }
-  dpl = 0.5 * (d0 + d1);
+  dpl = pair_midplane(e0, e1c, e2c, A, Bq, st);
   if (!refine) return true;
   int it = 0;
   for (; it < NEWTON_CAP; it++) {  // Newton on the offset until |grad| < 1e-2
@@ -405,10 +351,7 @@ __device__ __forceinline__ bool plane_pair_wave(const double* A, const double* B
   TJ_ORDER(v.x);
   if (tic) TJ_TIC(*tic, K_SEP_SELF_SOLVE, 3);
   if (!plane_normal(v, dist, e0, e1c, e2c)) return false;
-  double d0 = INFINITY, d1 = -INFINITY;
-  for (int i = 0; i < 6; i++) { const double t = -dot_fixed3(e0, e1c, e2c, Bq + 3 * i); if (d0 > t) d0 = t; }
-  for (int i = 0; i < 6; i++) { const double t = -dot_fixed3(e0, e1c, e2c, A + 3 * i); if (d1 < t) d1 = t; }
-  dpl = 0.5 * (d0 + d1);
+  dpl = pair_midplane(e0, e1c, e2c, A, Bq, 1);
   TJ_ORDER(dpl);
   if (tic) TJ_TIC(*tic, K_SEP_SELF_SOLVE, 4);
   const int j = lane < 6 ? lane : (lane < 12 ? lane - 6 : 0);
@@ -459,7 +402,20 @@ __device__ inline bool plane_pair_wave(const double* A, const double* Bq, double
 constexpr int OBS_SINGLE_MAX = 16;  // candidates of a segment that still get a wave each
 // LDS of one unit, carved from a buffer the KERNEL owns: the union kernels run a different body per block, and function-local
 // __shared__ arrays of exclusive branches are not overlaid by the compiler (their sizes add up, and with them go residency).
-constexpr int OBS_LDS_DOUBLES = 264 + (2 * FRONT_CAP + 128) / 2;   // P[18] klo[49] khi[49] kax[147] | fa fb cand
+constexpr int OBS_P = 0, OBS_KLO = OBS_P + 18, OBS_KHI = OBS_KLO + 49, OBS_WALK = OBS_KHI + 49, OBS_LDS_DOUBLES = OBS_WALK + WalkScratch::DOUBLES;   // hull | its 49 intervals lo, hi | the walk's scratch: 1204
+// A work item of the solve stage, two ints of Dev::obs_work: (segment, slot).  slot >= 0: the segment's candidate `slot`, for a whole wave; slot < 0: a batch of up to
+// 64 candidates, one per lane, starting at candidate -(slot + 1).
+struct ObsItem { int seg, first; bool batch; };
+__device__ __forceinline__ int obs_item_slot(bool batched, int i) { return batched ? -(i * 64) - 1 : i; }   // item i of its segment
+__device__ __forceinline__ ObsItem obs_item(int seg, int slot) { return ObsItem{seg, slot < 0 ? -(slot + 1) : slot, slot < 0}; }
+// The plane slot of candidate i of a segment (Dev::oraw, Dev::ostamp): the solve wave leaves plane and epoch stamp there, the compaction (kernels_pairs.h)
+// takes the slots stamped with this epoch in slot order.
+__device__ __forceinline__ size_t obs_plane_slot(const Dev& D, size_t seg, int i) { return seg * D.cap_obs + i; }
+__device__ __forceinline__ void obs_plane_store(const Dev& D, size_t sl, double c0, double c1, double c2, double dd, int epoch) {
+  double* o = D.oraw + sl * 4;
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = dd;
+  D.ostamp[sl] = epoch;
+}
 // use_cache: the hull cache (hullinfo: hull, box, 49 intervals -- the same expressions, written by k_linesearch / k_hullinfo) is
 // valid for this robot; taking the record from there is ONE memory latency where recomputing costs two plus the projections.
 // True in the iteration chains of the multi-robot modes, false in the stage API (the cache is rebuilt after this stage there).
@@ -473,10 +429,8 @@ __device__ __forceinline__ void obs_query_body(const Dev& D, int bid, double* ld
   const int u = D.u0 + bid / D.S, tr = bid % D.S;
   const int lane = lane_id();
   auto sti = [&](int* p, int v) { if constexpr (FA) xf_store_i(p, v); else *p = v; };
-  double* P = lds; double* klo = P + 18; double* khi = klo + 49;
-  int* fa = (int*)(lds + 264); int* fb = fa + FRONT_CAP; int* cand = fb + FRONT_CAP;
-  bool kax_ready = false;
-  V3 axv{0, 0, 0}; double lo_ax = 0, hi_ax = 0;
+  double* P = lds + OBS_P; double* klo = lds + OBS_KLO; double* khi = lds + OBS_KHI;
+  KdopLane kl;
   const double* net = D.spline + (size_t)u * 3 * D.T;
   TJ_TIC(D, K_SEP_OBS, 0);
   QBox q;
@@ -516,14 +470,9 @@ __device__ __forceinline__ void obs_query_body(const Dev& D, int bid, double* ld
   int* list = D.ocand + seg * D.cap_obs;
   int base = 0;
   unsigned long long visits = 0;
-  const int found = bvh_query<4, PRIM>(D, q, dist, fa, fb, cand, &visits, [&](int pt) {
-    if (!kax_ready) {   // wave-uniform: this lane's axis and the hull's interval on it, kept in registers from the first candidate on
-      const int ax = min(lane, 48);
-      axv = V3{D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2]}; lo_ax = klo[ax]; hi_ax = khi[ax];
-      kax_ready = true;
-    }
-    const int ncand = __popcll(ballot(pt >= 0));   // candidates sit in lanes [0, ncand)
-    const bool ok = kdop_cull_wave(PrimOf<PRIM>::load(D, max(pt, 0)), ncand, axv, lo_ax, hi_ax, dist, lane) && pt >= 0;
+  const int found = bvh_query<4, PRIM>(D, q, dist, WalkScratch::carve(lds + OBS_WALK), &visits, [&](int pt) {
+    typename PrimOf<PRIM>::Body qb;
+    const bool ok = kl.template cull<PRIM>(D, klo, khi, pt, dist, lane, qb);
     const unsigned long long mask = ballot(ok);
     const int idx = base + prefix_count(mask);
     if (ok) {
@@ -537,7 +486,7 @@ __device__ __forceinline__ void obs_query_body(const Dev& D, int bid, double* ld
   if (cnt > 0 && lane < 18) { if constexpr (FA) xf_store(D.ohull + seg * 18 + lane, P[lane]); else D.ohull[seg * 18 + lane] = P[lane]; }   // read by the solve waves of this segment's candidates only
   // Work items: a segment with few candidates hands each one to its own wave (cooperative GJK, lowest latency); a
   // segment in a dense part of the cloud hands them over in batches of up to 64, one candidate per lane (per-lane GJK,
-  // highest throughput).  slot >= 0: single candidate; slot < 0: batch starting at candidate -(slot + 1).
+  // highest throughput): ObsItem.
   const bool batched = cnt > OBS_SINGLE_MAX;
   const int items = batched ? (cnt + 63) / 64 : cnt;
   int w0 = 0;
@@ -548,7 +497,7 @@ __device__ __forceinline__ void obs_query_body(const Dev& D, int bid, double* ld
     atomicAdd(&st[0], visits); atomicAdd(&st[1], (unsigned long long)found);
   }
   w0 = __shfl(w0, 0);
-  for (int i = lane; i < items; i += 64) { sti(D.obs_work + 2 * (size_t)(w0 + i), (int)seg); sti(D.obs_work + 2 * (size_t)(w0 + i) + 1, batched ? -(i * 64) - 1 : i); }
+  for (int i = lane; i < items; i += 64) { sti(D.obs_work + 2 * (size_t)(w0 + i), (int)seg); sti(D.obs_work + 2 * (size_t)(w0 + i) + 1, obs_item_slot(batched, i)); }
   TJ_TIC(D, K_SEP_OBS, 5);
 }
 
@@ -563,25 +512,19 @@ __device__ __forceinline__ void obs_solve_body(const Dev& D, int bid, int nwaves
   const double dist = D.offset + D.margin;
   const int epoch = D.ctl->epoch;
   for (int w = bid; w < n; w += nwaves) {
-    const int seg = ldi(D.obs_work + 2 * (size_t)w), slot = ldi(D.obs_work + 2 * (size_t)w + 1);
+    const ObsItem it = obs_item(ldi(D.obs_work + 2 * (size_t)w), ldi(D.obs_work + 2 * (size_t)w + 1));
     __syncthreads();
-    if (lane < 18) { if constexpr (FA) P[lane] = xf_load(D.ohull + (size_t)seg * 18 + lane); else P[lane] = D.ohull[(size_t)seg * 18 + lane]; }
+    if (lane < 18) { if constexpr (FA) P[lane] = xf_load(D.ohull + (size_t)it.seg * 18 + lane); else P[lane] = D.ohull[(size_t)it.seg * 18 + lane]; }
     __syncthreads();
-    const bool batch = slot < 0;
-    const int first = batch ? -(slot + 1) : slot;
-    const int mine = batch ? first + lane : first;                     // candidate of this lane
-    const bool live = !batch || mine < ldi(D.ocand_n + seg);
-    const int pt = ldi(D.ocand + (size_t)seg * D.cap_obs + (live ? mine : first));
+    const int mine = it.batch ? it.first + lane : it.first;            // candidate of this lane
+    const bool live = !it.batch || mine < ldi(D.ocand_n + it.seg);
+    const int pt = ldi(D.ocand + (size_t)it.seg * D.cap_obs + (live ? mine : it.first));
     const typename PrimOf<PRIM>::Body qb = PrimOf<PRIM>::load(D, pt);
     V3 v;
-    if (batch) v = gjk(BodyHull{P}, qb);                               // one candidate per lane
+    if (it.batch) v = gjk(BodyHull{P}, qb);                            // one candidate per lane
     else v = gjk_wave(BodyHull{P}, qb, lane);                          // one candidate for the whole wave
     double c0, c1, c2, dd;
-    if (plane_from_witness_body(v, qb, dist, D.offset, c0, c1, c2, dd) && live && (batch || lane == 0)) {
-      double* o = D.oraw + ((size_t)seg * D.cap_obs + mine) * 4;
-      o[0] = c0; o[1] = c1; o[2] = c2; o[3] = dd;
-      D.ostamp[(size_t)seg * D.cap_obs + mine] = epoch;
-    }
+    if (plane_from_witness_body(v, qb, dist, D.offset, c0, c1, c2, dd) && live && (it.batch || lane == 0)) obs_plane_store(D, obs_plane_slot(D, it.seg, mine), c0, c1, c2, dd, epoch);
   }
 }
 

@@ -92,9 +92,8 @@ __device__ __forceinline__ void ccd_record_async(const Dev& D, int u, int tr, in
   blk_sync<true>();
   if (lane < 3) swept_put_boxes(D, info, u, tr, lane, swept_boxes(P, PD, lane, [&](int j) { return PS[3 * j + lane]; }), put, xf_store);
   if (lane < 49) {
-    double up = -INFINITY, lo = INFINITY;
-    kdop_interval6(kx, ky, kz, P, lo, up);
-    kdop_interval6(kx, ky, kz, PS, lo, up);
+    double lo, up;
+    swept_kdop_axis(V3{kx, ky, kz}, P, PS, lo, up);
     swept_put_interval(info, lane, lo, up, put);
   }
   blk_sync<true>();
@@ -163,7 +162,7 @@ __device__ __forceinline__ bool swept_within(const A& a, const B& b, double off2
   return v.x * v.x + v.y * v.y + v.z * v.z <= off2;
 }
 constexpr int CCD_INFO_DOUBLES = 2 * (CCD_REC + 1);   // the record's LDS copy `info` (ccd_record_async's hull scratch starts behind it, at CCD_REC + 2)
-constexpr int CCD_LDS_DOUBLES = CCD_INFO_DOUBLES + (2 * FRONT_CAP + 128) / 2;   // info | fa fb cand
+constexpr int CCD_LDS_DOUBLES = CCD_INFO_DOUBLES + WalkScratch::DOUBLES;   // info | the walk's scratch
 // the candidate a lane holds, handed to the whole wave
 __device__ __forceinline__ V3 bcast_v3(const V3& v, int l) { return V3{readlane_f64(v.x, l), readlane_f64(v.y, l), readlane_f64(v.z, l)}; }
 __device__ __forceinline__ BodyPoint bcast_body(const BodyPoint& b, int l) { return BodyPoint{bcast_v3(b.q, l)}; }
@@ -176,9 +175,7 @@ __device__ __forceinline__ void ccd_obs_body(const Dev& D, int bid, double* lds,
   const int u = D.u0 + bid / D.S, tr = bid % D.S;
   const int lane = lane_id();
   double* info = lds;
-  int* fa = (int*)(lds + CCD_INFO_DOUBLES); int* fb = fa + FRONT_CAP; int* cand = fb + FRONT_CAP;
-  bool kax_ready = false;
-  V3 axv{0, 0, 0}; double lo_ax = 0, hi_ax = 0;
+  KdopLane kl;
   const double* src = swept_record(D, u, tr);
   const TopBox topb = bvh_top_box(D);   // travels with the segment's record
   if (D.xs_async) {   // asynchronous Newton solve: the record is built here, once this robot's block (on the other queue) has left its direction
@@ -199,16 +196,9 @@ __device__ __forceinline__ void ccd_obs_body(const Dev& D, int bid, double* lds,
   const double off = D.offset;
   unsigned long long visits = 0;
   int kmax = 0;
-  const int found = bvh_query<1, PRIM>(D, q, off, fa, fb, cand, &visits, [&](int pt) {
-    if (!kax_ready) {   // wave-uniform: this lane's axis and the swept hull's interval on it
-      const int ax = min(lane, 48);
-      axv = V3{D.kdop[3 * ax], D.kdop[3 * ax + 1], D.kdop[3 * ax + 2]}; lo_ax = info[CCD_KLO + ax]; hi_ax = info[CCD_KHI + ax];
-      kax_ready = true;
-    }
-    const int ncand = __popcll(ballot(pt >= 0));   // candidates sit in lanes [0, ncand)
-    const typename PrimOf<PRIM>::Body qb = PrimOf<PRIM>::load(D, max(pt, 0));
-    const bool pass = kdop_cull_wave(qb, ncand, axv, lo_ax, hi_ax, off, lane);
-    unsigned long long pm = ballot(pass && pt >= 0);
+  const int found = bvh_query<1, PRIM>(D, q, off, WalkScratch::carve(lds + CCD_INFO_DOUBLES), &visits, [&](int pt) {
+    typename PrimOf<PRIM>::Body qb;
+    unsigned long long pm = ballot(kl.template cull<PRIM>(D, info + CCD_KLO, info + CCD_KHI, pt, off, lane, qb));
     if (pm) {
       int k = max(kmax, __builtin_amdgcn_readfirstlane(atomicAdd(&D.k_obs[u], 0)));   // any earlier value is a valid lower bound (uniform)
       while (pm) {

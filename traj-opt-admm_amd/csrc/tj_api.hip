@@ -1782,6 +1782,7 @@ int tj_kat_planes(tj_ctx* c, int what, int n, const double* P, const double* Q, 
   HIPCHK(c, hipMemsetAsync(dout.p, 0, std::max<size_t>((size_t)n * 40, 8), c->stream));
   if (what >= 5 && n > 0) { int ur = upload(c, dout.p, out, (size_t)n * 40); if (ur) return ur; }  // in/out: the plane to refine
   if (what == 7) hipLaunchKernelGGL(k_dbg_optpair_wave, dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)dp.p, (const double*)dq.p, (double*)dout.p);
+  else if (what == 2) hipLaunchKernelGGL((k_dbg_kdop_wave<1, false>), dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)dp.p, nullptr, nullptr, (const double*)dq.p, 1, nullptr, dist, (double*)dout.p, 5);
   else if (what == 4) hipLaunchKernelGGL(k_dbg_pair_wave, dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)dp.p, (const double*)dq.p, dist, (double*)dout.p);
   else hipLaunchKernelGGL(k_dbg_planes, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d, what, n, (const double*)dp.p, (const double*)dq.p, dist, (double*)dout.p);
   HIPCHK(c, hipGetLastError());
@@ -2104,9 +2105,31 @@ int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double*
   for (int i = 0; i < 4; i++) if ((r = to_dev(c, b[i], src[i], sz[i]))) return r;
   if ((r = to_dev(c, dout, nullptr, (size_t)n * 64))) return r;
   hipLaunchKernelGGL(k_dbg_tri, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[2].p, (const double*)b[3].p, dist, off, (double*)dout.p);
+  // the two k-DOP verdicts, out[.][5] and out[.][6]: one wave per case, the triangle on lane 0
+  hipLaunchKernelGGL((k_dbg_kdop_wave<3, false>), dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, nullptr, nullptr, (const double*)b[2].p, 1, nullptr, dist, (double*)dout.p + 5, 8);
+  hipLaunchKernelGGL((k_dbg_kdop_wave<3, true>), dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[3].p, (const double*)b[2].p, 1, nullptr, off, (double*)dout.p + 6, 8);
   HIPCHK(c, hipGetLastError());
   QUIESCE(c);
   HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * 64, hipMemcpyDeviceToHost));
+  return TJ_OK;
+}
+
+int tj_kat_kdop_wave(tj_ctx* c, int prim, int swept, int n, int per, const double* P, const double* D, const double* t, const double* bodies, const int* nc, double d, double* out) {
+  if (!c || n < 0 || per < 1 || per > 64 || (prim != 1 && prim != 3) || !P || !bodies || !out || (swept && (!D || !t))) return TJ_ERR_INVALID;
+  DevBuf b[5], dout; int r;
+  const void* src[5] = {P, swept ? D : nullptr, swept ? t : nullptr, bodies, nc};
+  const size_t sz[5] = {(size_t)n * 144, swept ? (size_t)n * 144 : 0, swept ? (size_t)n * 8 : 0, (size_t)n * per * prim * 24, nc ? (size_t)n * 4 : 0};
+  for (int i = 0; i < 5; i++) if (src[i] && (r = to_dev(c, b[i], src[i], sz[i]))) return r;
+  if ((r = to_dev(c, dout, nullptr, (size_t)n * per * 8))) return r;
+  HIPCHK(c, hipMemsetAsync(dout.p, 0, std::max<size_t>((size_t)n * per * 8, 8), c->stream));
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[2].p, (const double*)b[3].p, per, (const int*)b[4].p, d, (double*)dout.p, 1);
+  };
+  if (prim == 1) { if (swept) go(k_dbg_kdop_wave<1, true>); else go(k_dbg_kdop_wave<1, false>); }
+  else { if (swept) go(k_dbg_kdop_wave<3, true>); else go(k_dbg_kdop_wave<3, false>); }
+  HIPCHK(c, hipGetLastError());
+  QUIESCE(c);
+  HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * per * 8, hipMemcpyDeviceToHost));
   return TJ_OK;
 }
 

@@ -536,6 +536,94 @@ typedef struct tj_margin_record {
 } tj_margin_record;
 int tj_timing_margin(tj_ctx* c, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n);
 int tj_margin_record_size(void);   /* sizeof(tj_margin_record) */
+/* ---- tj_proximity_windows: FROM WHEN TO WHEN is each pair of robots within `dist` of each other at equal flight times
+ * (csrc/kernels_proximity.h; read-only like tj_pair_approach).  tj_pair_approach returns one minimum per pair, tj_timing_margin one tolerable slip,
+ * tj_flight_profile samples that certify nothing between them.  Here the whole time axis of a pair is classified against the level `dist` and everything
+ * that is not certified outside is returned as time intervals: at dist = offset the conflict intervals of a state that is not yet collision-free, at a
+ * radio range or a downwash radius the fleet's time-varying link graph, each edge with certified on and off times.  Rows are for one DIRECTED pair (u, q),
+ * u owned, q != u, over u's flight (tj_pair_approach's convention: the two directions end at different times).  Time, hover after arrival, hull formation,
+ * the cuts at q's segment boundaries and arrival, the restriction of both RAW hulls and the box prefilter are tj_audit_timed's and tj_closest_approach's,
+ * unchanged.  For one directed pair:
+ *   window   W = [ca, cb] in one segment of u and one segment of q (or q's hover), d_0..d_5 its difference net.  lo(W): the GJK's |v| with its certificate
+ *            `sep` (v . d_i > 0 for all six points), 0 without one.  h0, h5 = norm3(d_0), norm3(d_5): the separations attained at ca and cb.
+ *            ub(W) = the largest norm3(d_i), i = 0..5: the curve lies in the net's hull and a norm is convex, so no separation on W is larger.
+ *   class    OUT: sep and lo > dist.  IN: ub <= dist.  MIXED: everything else.  (In this order.)
+ *   seeds    the level-0 windows tj_audit_timed evaluates for u against this q that pass the box prefilter at range = dist; a window the prefilter skips is OUT.
+ *   listed   (u, q) is listed if and only if some seed is not OUT.  A pair that is not listed is certified farther than dist apart over u's whole flight.
+ *   search   kept = the IN seeds, live = the MIXED seeds.  One round: a live window with cb - ca <= tol, or whose midpoint cm = 0.5 * (ca + cb) does not lie
+ *            strictly between its ends, is appended to kept as an EDGE leaf with its h0 and h5; every other live window is halved at cm and both children are
+ *            evaluated from the RAW hulls: OUT children are dropped, IN children appended to kept with h0 and h5, MIXED children form the next live set.
+ *   stop     the live set is empty | depth == max_depth | the live set or the kept list after a round, or after the seeding, holds more than max_windows
+ *            (TRUNCATED: kept and live are those of the last completed round -- the appends of the overflowing round do not count, `windows` counts its work
+ *            too, as the siblings do).  Whatever is live at the end joins the leaves as EDGE leaves (so a pair has at most 2 * max_windows leaves).
+ *   merge    the pair's leaves ordered by ca (distinct: a pair's windows are disjoint).  Two consecutive leaves are adjacent exactly when prev.cb == next.ca
+ *            on doubles: the cut and midpoint expressions are shared, so the ends agree bit for bit.  A row is a maximal chain of adjacent leaves.
+ *   sure     every time of an IN leaf; of an EDGE leaf ca if h0 <= dist and cb if h5 <= dist: times at which the pair IS within dist.
+ *   row      t_first_lo = the chain's start, t_last_hi = its end; t_first_hi = the earliest sure time, t_last_lo = the latest (both -1.0 without one);
+ *            within_lo = the sum of the IN leaves' cb - ca in time order, left to right; closest, closest_time = the smallest attained end sample of the
+ *            chain in the order (value, time) -- not converged: tj_pair_approach converges it; leaves = the chain's length; depth = the rounds the pair
+ *            completed; windows = the pair's work, seeds evaluated + 2 per halved window, repeated on each of the pair's rows.
+ * Every field is a function of the state alone.  Outside every row's [t_first_lo, t_last_hi] the separation of the pair is certified above dist over u's
+ * flight; the pair first comes within dist in [t_first_lo, t_first_hi] and is last within dist in [t_last_lo, t_last_hi].  A listed pair may end with no
+ * row (every child turned OUT).  Rows are sorted by (robot, partner, t_first_lo); neither the order of evaluation nor that of any atomic append is visible.
+ * CAPACITY.  *n_pairs = the listed pairs, *n = the rows; listed pairs need `cap` slots and rows `cap` entries.  n_pairs > cap: TJ_ERR_CAPACITY and
+ * *n = -1 (rows are known only for pairs that were refined; nothing is written).  n_pairs <= cap < *n: TJ_ERR_CAPACITY with the exact *n, the first `cap`
+ * rows in order have been written.  cap = 0 with rows == NULL is the count-only call: TJ_OK, *n_pairs, and *n = -1 unless nothing is listed (two launches).
+ * dist <= 0: offset.  +infinity is valid: every pair is IN for its whole flight, one row with AT_START | AT_END.  tol < 0:
+ * TJ_PROXIMITY_TOL_FRACTION * dist / vel_limit -- tj_timing_margin's design condition, stated as such: the time a robot at the speed limit needs for 1 % of
+ * dist, 5e-4 s at the shipped parameters (offset in place of an infinite dist); 0 is valid.  max_depth < 0: TJ_PROXIMITY_MAX_DEPTH; above it TJ_ERR_INVALID.
+ * max_windows <= 0: TJ_PROXIMITY_FRONTIER; above TJ_PROXIMITY_MAX_WINDOWS TJ_ERR_INVALID.  NaN dist or tol, n == NULL, n_pairs == NULL, cap < 0,
+ * rows == NULL with cap > 0, a call before tj_init_state: TJ_ERR_INVALID, the outputs untouched.  Single-UAV mode: 0 pairs, 0 rows and TJ_OK.  A plain
+ * SHARDED context (world > 1) returns TJ_ERR_UNSUPPORTED like tj_pair_approach; tj_group_proximity_windows reads every robot's control points and piece_time
+ * from its owner and returns the owners' rows one after the other, bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, and is a function of cap and max_windows (S = piece_num * res segments):
+ *   cap * (2 * max_windows * 48 + 2 * (2 * max_windows + 2 * S + 2) * 40 + (2 * S + 2) * 48 + 32 + 80) bytes
+ *   (live lists; the kept list and the sorted leaves; the pairs' level-0 seeds; the slots' pairs, counters and totals; the rows)
+ * plus the bitmask and its offsets, owned * ceil(uav_num / 32) * 8 bytes.  A call whose figure exceeds TJ_PROXIMITY_MAX_BYTES is refused up front with
+ * TJ_ERR_INVALID: lower cap or max_windows.  At the defaults a pair slot costs 141 680 bytes at S = 40.
+ * At most FIVE launches whatever the fleet's size, the number of pairs and the depth (two for the count-only call); no host loop over robots, pairs or
+ * rounds.  Changes no solver state, statistics or launch count.
+ * STATED LIMITS.  (1) A certified lo is the GJK's |v|, up to 1e-10 |v| relative above the hull's distance (the siblings' limit, unchanged): it applies to
+ * the OUT decision.  (2) Separation gaps shorter than a leaf are not resolved: an EDGE leaf, and a chain across it, may hold instants at which the pair is
+ * farther than dist apart.  UNCERTAIN rows are grazes at the resolution tol: the pair may or may not come within dist inside the row.
+ * The defaults are measured (tests/proximity_ref.py default_tolerance, the restatement, on the CPU): the default tol, max_depth = 40, the lists capped at
+ * TJ_PROXIMITY_MAX_WINDOWS only, on the final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz, e2e_scn_b_coupled.npz, of e2e_scn_c3.npz with z set to 0
+ * (_flat) and of that with piece_time[u] *= 1 + 0.03 * u (_flat_staggered), at dist = offset = 0.1 and dist = 1.0 (widest bracket: the larger of
+ * t_first_hi - t_first_lo and t_last_hi - t_last_lo over the CERTAIN rows):
+ *   state                       dist   listed pairs   rows   uncertain   truncated   largest live set   largest kept list   largest depth   widest bracket
+ *   e2e_scn_b                   0.1    0              0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b                   1.0    38             38     0           0           2                  27                  7               4.49e-03
+ *   e2e_scn_c3                  0.1    0              0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_c3                  1.0    372            372    0           0           2                  80                  7               4.49e-03
+ *   e2e_scn_b_coupled           0.1    0              0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b_coupled           1.0    38             38     0           0           2                  19                  7               4.49e-03
+ *   e2e_scn_c3_flat             0.1    4032           4032   0           0           2                  29                  11              2.81e-04
+ *   e2e_scn_c3_flat             1.0    4032           4032   0           0           2                  80                  7               4.49e-03
+ *   e2e_scn_c3_flat_staggered   0.1    2              2      0           0           2                  17                  12              3.34e-04
+ *   e2e_scn_c3_flat_staggered   1.0    704            782    0           0           3                  88                  9               4.98e-03
+ * A level set is crossed at isolated times, so the live set stays at two or three windows; what grows is the kept list, by the IN windows of long stays
+ * within dist (up to the 2 * S + 2 seeds of a pair that flies alongside).  TJ_PROXIMITY_FRONTIER is the next power of two >= 4 x the larger of the two list
+ * maxima (88), and at least 64. */
+#define TJ_PROXIMITY_CERTAIN   1    /* a sure time exists: the pair IS within dist in [t_first_hi, t_last_lo]'s ends */
+#define TJ_PROXIMITY_UNCERTAIN 2    /* no sure time: t_first_hi == t_last_lo == -1.0, a graze at the resolution tol */
+#define TJ_PROXIMITY_AT_START  4    /* the chain starts at time 0: nothing lies before it */
+#define TJ_PROXIMITY_AT_END    8    /* the chain ends at the end of robot's flight */
+#define TJ_PROXIMITY_RESOLVED  16   /* CERTAIN and both brackets are at most tol wide (a side closed by AT_START / AT_END counts as resolved) */
+#define TJ_PROXIMITY_TRUNCATED 32   /* the pair's live set or kept list outgrew max_windows: the leaves of the last completed round are returned */
+#define TJ_PROXIMITY_MAX_DEPTH 40
+#define TJ_PROXIMITY_FRONTIER  512
+#define TJ_PROXIMITY_MAX_WINDOWS 4096
+#define TJ_PROXIMITY_MAX_BYTES (1ll << 31)
+#define TJ_PROXIMITY_TOL_FRACTION 0.01
+typedef struct tj_proximity_row {
+  double t_first_lo, t_first_hi;   /* the pair first comes within dist in [t_first_lo, t_first_hi] */
+  double t_last_lo,  t_last_hi;    /* ... and is last within dist in [t_last_lo, t_last_hi] */
+  double within_lo;                /* seconds CERTIFIED within dist inside the row (sum of the IN leaves) */
+  double closest, closest_time;    /* smallest attained sample of the row and its time (not converged: tj_pair_approach converges it) */
+  int robot, partner, leaves, depth, flags, windows;
+} tj_proximity_row;
+int tj_proximity_windows(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n);
+int tj_proximity_row_size(void);   /* sizeof(tj_proximity_row) */
 /* ---- tj_obstacle_approach: how close the FLOWN CURVE of every robot comes to an obstacle primitive, when, and to which one, converged to a tolerance the
  * caller names (csrc/kernels_obstacle_approach.h; read-only like tj_audit).  tj_audit's obs_clearance is the distance of a segment's 6-point hull: what the
  * solver constrains and the right certificate for a converged state, but only a lower bound on what the vehicle does, without a time, and on the GJK's
@@ -879,6 +967,7 @@ int tj_group_closest_approach(tj_group* g, double range, double tol, int max_dep
 int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n);   /* tj_pair_approach of every robot by its owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n);   /* tj_path_crossings of every pair (u, q > u) by u's owner, the ranks' rows one after the other: (robot, partner) order, bitwise one context's */
 int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n);   /* tj_timing_margin of every pair (u, q > u) by u's owner, in the same way */
+int tj_group_proximity_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n);   /* tj_proximity_windows of every robot by its owner, the ranks' rows one after the other: (robot, partner, t_first_lo) order, bitwise one context's; every rank gets `cap` pair slots and the rows' remaining room */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);   /* tj_peak_dynamics of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */

@@ -37,6 +37,7 @@ EXPORTS = [
     "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
     "tj_path_crossings", "tj_crossing_record_size", "tj_group_path_crossings",
     "tj_timing_margin", "tj_margin_record_size", "tj_group_timing_margin",
+    "tj_proximity_windows", "tj_proximity_row_size", "tj_group_proximity_windows",
     "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
     "tj_peak_dynamics", "tj_dynamics_record_size", "tj_group_peak_dynamics",
 ]
@@ -233,6 +234,20 @@ MARGIN_FRONTIER = 4096       # TJ_MARGIN_FRONTIER: what max_windows=None selects
 MARGIN_MAX_WINDOWS = 4096    # TJ_MARGIN_MAX_WINDOWS
 
 
+class TjProximityRow(C.Structure):
+    """mirror of tj_proximity_row (include/trajadmm.h); tj_proximity_row_size() is its sizeof on the C side"""
+    _fields_ = [("t_first_lo", C.c_double), ("t_first_hi", C.c_double), ("t_last_lo", C.c_double), ("t_last_hi", C.c_double), ("within_lo", C.c_double),
+                ("closest", C.c_double), ("closest_time", C.c_double), ("robot", C.c_int), ("partner", C.c_int), ("leaves", C.c_int), ("depth", C.c_int),
+                ("flags", C.c_int), ("windows", C.c_int)]
+
+
+PROXIMITY_FLAGS = dict(certain=1, uncertain=2, at_start=4, at_end=8, resolved=16, truncated=32)
+PROXIMITY_TOL_FRACTION = 0.01   # TJ_PROXIMITY_TOL_FRACTION: tol=None selects this fraction of dist over vel_limit, a time
+PROXIMITY_MAX_DEPTH = 40        # TJ_PROXIMITY_MAX_DEPTH
+PROXIMITY_FRONTIER = 512        # TJ_PROXIMITY_FRONTIER: what max_windows=None selects
+PROXIMITY_MAX_WINDOWS = 4096    # TJ_PROXIMITY_MAX_WINDOWS
+
+
 class TjProfileSample(C.Structure):
     """mirror of tj_profile_sample (include/trajadmm.h); tj_flight_profile_record_size() is its sizeof on the C side"""
     _fields_ = [("time", C.c_double), ("x", C.c_double), ("y", C.c_double), ("z", C.c_double), ("obs_distance", C.c_double), ("robot_distance", C.c_double),
@@ -320,6 +335,26 @@ def _timing_margin(call, dist, max_slip, tol, max_depth, max_windows):
     """shared by Solver.timing_margin / Group.timing_margin: call(dist, max_slip, tol, max_depth, max_windows, rows, cap, n)"""
     d, t, md, mw = _search_args(dist, tol, max_depth, max_windows)
     return _listed_rows(TjMarginRecord, call, (d, C.c_double(0.0 if max_slip is None else float(max_slip)), t, md, mw))
+
+
+def _proximity_windows(call, check, dist, tol, max_depth, max_windows):
+    """shared by Solver.proximity_windows / Group.proximity_windows: call(dist, tol, max_depth, max_windows, rows, cap, n_pairs, n) -> the C side's return value,
+    check(rc) raises on an error.  The count-only call sizes cap by the listed pairs; more rows than that (TJ_ERR_CAPACITY with the exact n) take one more call"""
+    args = _search_args(dist, tol, max_depth, max_windows)
+    pairs, n = C.c_int(0), C.c_int(0)
+    check(call(*args, None, C.c_int(0), C.byref(pairs), C.byref(n)))
+    cap = pairs.value
+    rec = (TjProximityRow * max(cap, 1))()
+    if cap:
+        rc = call(*args, rec, C.c_int(cap), C.byref(pairs), C.byref(n))
+        if rc == -3 and n.value > cap:
+            cap = n.value
+            rec = (TjProximityRow * cap)()
+            rc = call(*args, rec, C.c_int(cap), C.byref(pairs), C.byref(n))
+        check(rc)
+    out = _records(TjProximityRow, rec[:max(n.value, 0)])
+    out["n_pairs"] = pairs.value
+    return out
 
 
 class TrajAdmmError(RuntimeError):
@@ -845,6 +880,15 @@ class Solver:
         Group.timing_margin."""
         return _timing_margin(lambda *a: self._check(self.lib.tj_timing_margin(self._ctx, *a)), dist, max_slip, tol, max_depth, max_windows)
 
+    def proximity_windows(self, dist=None, tol=None, max_depth=None, max_windows=None):
+        """tj_proximity_windows: WHEN is each DIRECTED pair (robot, partner) within `dist` (None: offset) at equal flight times over robot's flight.  One row per
+        maximal run of time that is not certified farther apart: the pair first comes within dist in [`t_first_lo`, `t_first_hi`] and is last within it in
+        [`t_last_lo`, `t_last_hi`], resolved to `tol` (None: PROXIMITY_TOL_FRACTION * dist / vel_limit); `within_lo` seconds certified within, `closest` /
+        `closest_time` the smallest attained sample, `leaves`, `depth`, `windows`, `flags` (PROXIMITY_FLAGS).  Outside every row the pair is certified above
+        dist.  Dict of numpy arrays [n] sorted by (robot, partner, t_first_lo), plus `n_pairs` (the listed pairs).  Read-only.  A sharded solver (world > 1)
+        raises: use Group.proximity_windows."""
+        return _proximity_windows(lambda *a: self.lib.tj_proximity_windows(self._ctx, *a), self._check, dist, tol, max_depth, max_windows)
+
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_obstacle_approach: per robot lo <= closest approach of the FLOWN CURVE to any obstacle primitive <= hi, converged to `tol` (None: OBSTACLE_TOL)
         by a branch and bound over windows of the segments' hulls; `time`, `index` (the caller's point / face index), `segment` of the hi sample (-1 where
@@ -1003,6 +1047,10 @@ class Group:
     def path_crossings(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_path_crossings: Solver.path_crossings, every pair (u, q > u) from the rank that owns u, in (robot, partner) order (bitwise one context's)"""
         return _path_crossings(lambda r, t, d, w, rows, cap, n: self._check(self.lib.tj_group_path_crossings(self._g, r, t, d, w, rows, cap, n)), range, tol, max_depth, max_windows)
+
+    def proximity_windows(self, dist=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_proximity_windows: Solver.proximity_windows from the ranks that own the robots, in (robot, partner, t_first_lo) order (bitwise one context's)"""
+        return _proximity_windows(lambda *a: self.lib.tj_group_proximity_windows(self._g, *a), self._check, dist, tol, max_depth, max_windows)
 
     def timing_margin(self, dist=None, max_slip=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_timing_margin: Solver.timing_margin, every pair (u, q > u) from the rank that owns u, in (robot, partner) order (bitwise one context's)"""

@@ -276,6 +276,37 @@ inline int timing_margin_rows(F&& f, double tol, std::vector<tj_margin_record>& 
   return n ? f(0.0, 0.0, tol, -1, 0, rows.data(), n, &n) : rc;
 }
 
+// --proximity-windows: one line per row, in the library's (robot, partner, t_first_lo) order, and the fleet's line: listed pairs, rows, the rows with a sure time,
+// the grazes, and the seconds certified within dist summed over the rows
+inline void print_proximity_windows(const std::vector<tj_proximity_row>& rows, int n_pairs) {
+  std::cout.precision(17);
+  int certain = 0, uncertain = 0;
+  double within = 0.0;
+  for (const tj_proximity_row& r : rows) {
+    std::cout << "proximity uav " << r.robot << " uav " << r.partner << " first " << r.t_first_lo << " " << r.t_first_hi << " last " << r.t_last_lo << " " << r.t_last_hi << " within " << r.within_lo
+              << " closest " << r.closest << " time " << r.closest_time << " leaves " << r.leaves << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    certain += r.flags & TJ_PROXIMITY_CERTAIN ? 1 : 0;
+    uncertain += r.flags & TJ_PROXIMITY_UNCERTAIN ? 1 : 0;
+    within += r.within_lo;
+  }
+  std::cout << "proximity fleet listed " << n_pairs << " rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
+}
+// the count-only call, then the rows with a slot per listed pair, once more if the rows are more than that (f: the context's or the group's entry point, bound to its handle)
+template <class F>
+inline int proximity_windows_rows(F&& f, double dist, std::vector<tj_proximity_row>& rows, int& n_pairs) {
+  int n = 0;
+  int rc = f(dist, -1.0, -1, 0, nullptr, 0, &n_pairs, &n);
+  if (rc < 0 || n_pairs == 0) return rc;
+  rows.resize(n_pairs);
+  rc = f(dist, -1.0, -1, 0, rows.data(), n_pairs, &n_pairs, &n);
+  if (rc == TJ_ERR_CAPACITY && n > (int)rows.size()) {
+    rows.resize(n);
+    rc = f(dist, -1.0, -1, 0, rows.data(), n, &n_pairs, &n);
+  }
+  rows.resize(rc < 0 || n < 0 ? 0 : n);
+  return rc;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

@@ -34,7 +34,11 @@
 // partner) -- every pair whose paths come within `offset` under some slip of the timetable: the slip's bracket in seconds converged to TOL (default the
 // library's), the distance of the hi sample, for each of the two robots its segment / parameter / clock value, rounds, windows evaluated, flag word -- and the
 // fleet's line: pairs listed, in contact on the timetable, with a certified positive margin, and the smallest hi.
-// --flight-profile K [FILE]: after the --timing-margin lines K lines per robot from tj_flight_profile / tj_group_flight_profile on the grid t_k = (k / (K - 1)) * the
+// --proximity-windows [DIST]: after the --timing-margin lines one line per row of tj_proximity_windows / tj_group_proximity_windows, sorted by (robot, partner, start) --
+// every time interval in which a directed robot pair is not certified farther than DIST apart (default `offset`) at equal flight times: the brackets of the first
+// and the last time within DIST, the seconds certified within, the smallest attained sample and its time, leaves, rounds, windows evaluated, flag word -- and the
+// fleet's line: listed pairs, rows, rows with a sure time, grazes, seconds certified within.
+// --flight-profile K [FILE]: after the --proximity-windows lines K lines per robot from tj_flight_profile / tj_group_flight_profile on the grid t_k = (k / (K - 1)) * the
 // longest robot's duration (K == 1: t = 0) -- "profile uav t x y z d_obs idx d_robot partner speed accel flags" at 17 digits: position, distance and index of the
 // NEAREST obstacle primitive (no range), distance and index of the nearest other robot at the same time, speed, acceleration, flag word.  With FILE the lines go
 // there instead, without the leading word (the layout of --sample-traj, extended).  Works in the single-UAV main and with --gpus.
@@ -55,7 +59,7 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
@@ -65,6 +69,7 @@ int main(int argc, char** argv) {
   bool pairs = false; double pairs_tol = -1;
   bool crossings = false; double crossings_tol = -1;
   bool margins = false; double margins_tol = -1;
+  bool proximity = false; double proximity_dist = 0;
   int profile_samples = 0; std::string profile_file;
   bool dynamics = false; double dynamics_tol = -1;
   std::vector<int> devices;   // empty: one context on device 0
@@ -82,6 +87,7 @@ int main(int argc, char** argv) {
     else if (a == "--pair-approach") { pairs = true; if (i + 1 < argc && argv[i + 1][0] != '-') pairs_tol = atof(argv[++i]); }
     else if (a == "--path-crossings") { crossings = true; if (i + 1 < argc && argv[i + 1][0] != '-') crossings_tol = atof(argv[++i]); }
     else if (a == "--timing-margin") { margins = true; if (i + 1 < argc && argv[i + 1][0] != '-') margins_tol = atof(argv[++i]); }
+    else if (a == "--proximity-windows") { proximity = true; if (i + 1 < argc && argv[i + 1][0] != '-') proximity_dist = atof(argv[++i]); }
     else if (a == "--flight-profile" && i + 1 < argc) { profile_samples = atoi(argv[++i]); if (i + 1 < argc && argv[i + 1][0] != '-') profile_file = argv[++i]; if (profile_samples < 1) { std::cerr << "--flight-profile needs K >= 1" << std::endl; return -1; } }
     else if (a == "--peak-dynamics") { dynamics = true; if (i + 1 < argc && argv[i + 1][0] != '-') dynamics_tol = atof(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
@@ -234,6 +240,13 @@ int main(int argc, char** argv) {
       chk(tjcli::timing_margin_rows([&](double r, double m, double t, int d, int w, tj_margin_record* out, int cap, int* n) {
             return group ? tj_group_timing_margin(grp, r, m, t, d, w, out, cap, n) : tj_timing_margin(ctx, r, m, t, d, w, out, cap, n); }, margins_tol, rows), "tj_timing_margin");
       tjcli::print_timing_margin(rows);
+    }
+    if (proximity) {
+      std::vector<tj_proximity_row> rows;
+      int n_pairs = 0;
+      chk(tjcli::proximity_windows_rows([&](double r, double t, int d, int w, tj_proximity_row* out, int cap, int* np, int* n) {
+            return group ? tj_group_proximity_windows(grp, r, t, d, w, out, cap, np, n) : tj_proximity_windows(ctx, r, t, d, w, out, cap, np, n); }, proximity_dist, rows, n_pairs), "tj_proximity_windows");
+      tjcli::print_proximity_windows(rows, n_pairs);
     }
     if (profile_samples > 0) {
       // the grid: K equal steps over the longest robot's duration, log_data's sum of piece_num times piece_time

@@ -40,6 +40,7 @@
 #include "kernels_pair_approach.h"
 #include "kernels_path_crossing.h"
 #include "kernels_timing_margin.h"
+#include "kernels_proximity.h"
 #include "kernels_flight_profile.h"
 #include "host_plan.h"
 
@@ -72,6 +73,9 @@ struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bo
 // what a context holds for a row-listing query (tj_pair_approach, tj_path_crossings, tj_timing_margin; listed_run)
 template <class Args, class Rec>
 struct Listed { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; Args sized{}; Rec* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
+
+// what a context holds for tj_proximity_windows (proximity_run): as Listed, with the row total; the sized buffers grow with the largest cap and max_windows so far
+struct ProxHeld { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; int* n_rows = nullptr; ProxArgs sized{}; tj_proximity_row* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
 
 struct tj_ctx {
   tj_params prm;
@@ -120,6 +124,7 @@ struct tj_ctx {
   Listed<PairArgs, tj_pair_record> pair;
   Listed<CrossArgs, tj_crossing_record> cross;
   Listed<MarginArgs, tj_margin_record> margin;
+  ProxHeld prox;   // tj_proximity_windows
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -764,6 +769,7 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->pair.allocs) hipFree(p);
   for (void* p : c->cross.allocs) hipFree(p);
   for (void* p : c->margin.allocs) hipFree(p);
+  for (void* p : c->prox.allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1300,7 +1306,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the nine (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
+// ---- the read-only queries: one path for the ten (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1330,6 +1336,8 @@ const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approac
                                  ": deeper windows cannot be halved in a double", ""},
                  SEARCH_MARGIN{"tj_timing_margin", "tj_group_timing_margin", TJ_MARGIN_MAX_DEPTH, TJ_MARGIN_MAX_WINDOWS, 0.0, TJ_MARGIN_FRONTIER,
                                ": deeper windows cannot be halved in a double", "", true, TJ_MARGIN_TOL_FRACTION},
+                 SEARCH_PROXIMITY{"tj_proximity_windows", "tj_group_proximity_windows", TJ_PROXIMITY_MAX_DEPTH, TJ_PROXIMITY_MAX_WINDOWS, 0.0, TJ_PROXIMITY_FRONTIER,
+                                  ": deeper windows cannot be halved in a double", "", true, TJ_PROXIMITY_TOL_FRACTION},
                  SEARCH_OBSTACLE{"tj_obstacle_approach", "tj_group_obstacle_approach", TJ_OBSTACLE_MAX_DEPTH, TJ_OBSTACLE_FRONTIER, TJ_OBSTACLE_TOL, TJ_OBSTACLE_FRONTIER,
                                  ": deeper windows are not dyadic in a double", ": the live list's capacity"};
 struct SearchArgs {
@@ -1588,6 +1596,81 @@ int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windo
   return TJ_OK;
 }
 
+// tj_proximity_windows (kernels_proximity.h): the rows of the directed pairs (u, q), u owned.  pair_cap: the slots of listed pairs, row_cap <= pair_cap: the caller's
+// rows (the public call gives both its cap; a group gives every rank the whole cap in slots and what is left of it in rows).  n_pairs first, then the row total, then
+// min(row_cap, n) rows.  Five launches for the rows, two for the count.
+size_t proximity_bytes(const Dev& d, int cap, int mw) {
+  const size_t seeds = (size_t)2 * d.S + 2;
+  return (size_t)cap * ((size_t)2 * mw * sizeof(ProxWin) + 2 * ((size_t)2 * mw + seeds) * sizeof(ProxLeaf) + seeds * sizeof(ProxSeed) + 8 * sizeof(int) + sizeof(tj_proximity_row));
+}
+int proximity_run(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, const double* net_host, const double* pt_host, tj_proximity_row* rows, int pair_cap, int row_cap,
+                  int* n_pairs, int* n) {
+  if (!c || !n || !n_pairs || pair_cap < 0 || row_cap < 0 || row_cap > pair_cap || (row_cap > 0 && !rows)) return TJ_ERR_INVALID;
+  const SearchSpec& spec = SEARCH_PROXIMITY;
+  const std::string name = spec.name;
+  int r;
+  SearchArgs sa;
+  if ((r = search_args(c, spec, dist, tol, max_depth, max_windows, sa))) return r;
+  const Dev& d = c->d;
+  if (tol < 0 && sa.range == INFINITY) sa.tol = (spec.tol_fraction * d.offset) / d.vel_limit;   // (no time resolves 1 % of an infinite distance: offset's)
+  const int mw = sa.max_windows, cap = pair_cap;
+  if (proximity_bytes(d, cap, mw) > (size_t)TJ_PROXIMITY_MAX_BYTES) {
+    c->err = name + ": cap " + std::to_string(cap) + " pairs at max_windows " + std::to_string(mw) + " need " + std::to_string(proximity_bytes(d, cap, mw)) +
+             " bytes of device memory, more than TJ_PROXIMITY_MAX_BYTES (" + std::to_string(TJ_PROXIMITY_MAX_BYTES) + "): lower cap or max_windows";
+    return TJ_ERR_INVALID;
+  }
+  if ((r = query_state(c, spec.name, true, net_host && pt_host))) return r;
+  *n_pairs = 0; *n = 0;
+  if (!d.multi()) return TJ_OK;   // one UAV: no pair
+  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
+  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
+  QUIESCE(c);
+  ProxHeld& h = c->prox;
+  if ((r = query_buf(c, h.mask, mask_n)) || (r = query_buf(c, h.wordoff, mask_n)) || (r = query_buf(c, h.n, 1)) || (r = query_buf(c, h.n_rows, 1))) return r;
+  const int seed_cap = 2 * d.S + 2;
+  if (cap > h.cap || mw > h.mw) {   // grow: the context is quiet, nothing reads the old buffers; a failure keeps what it got on the list and starts over next time
+    for (void* p : h.allocs) hipFree(p);
+    h.allocs.clear();
+    const int gc = std::max(cap, h.cap), gm = std::max(mw, h.mw);
+    h.sized = ProxArgs{}; h.out = nullptr; h.cap = -1; h.mw = 0;
+    ProxArgs& b = h.sized;
+    std::vector<void*>* l = &h.allocs;
+    const size_t leaves = (size_t)gc * ((size_t)2 * gm + seed_cap);
+    if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.count, (size_t)gc * 2, l)) || (r = query_buf(c, b.seeds, (size_t)gc * seed_cap, l)) ||
+        (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.leaf, leaves, l)) || (r = query_buf(c, b.sorted, leaves, l)) ||
+        (r = query_buf(c, b.info, (size_t)gc * 4, l)) || (r = query_buf(c, h.out, gc, l))) return r;
+    h.cap = gc; h.mw = gm;
+  }
+  ProxArgs a = h.sized;
+  if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
+  sa.put(a);
+  a.seed_cap = seed_cap; a.leaf_cap = 2 * mw + seed_cap; a.row_cap = row_cap; a.n_rows = h.n_rows;
+  a.ix.cap = cap; a.ix.words = words; a.ix.mask = h.mask; a.ix.wordoff = h.wordoff; a.ix.n = h.n;
+  if ((r = query_clear(c, h.mask, mask_n)) || (r = query_clear(c, h.n, 1)) || (r = query_clear(c, h.n_rows, 1)) || (r = query_clear(c, a.count, (size_t)cap * 2, cap > 0))) return r;
+  if (owned > 0) {
+    hipLaunchKernelGGL(k_prox_mark, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, a.ix);
+    if (cap > 0) {
+      hipLaunchKernelGGL(k_prox_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
+      hipLaunchKernelGGL(k_prox_refine, dim3(cap), dim3(PX_THREADS), 0, c->stream, d, a);
+      hipLaunchKernelGGL(k_prox_place, dim3(cap), dim3(PX_THREADS), 0, c->stream, d, a, h.out);
+    }
+  }
+  int np = 0, nr = 0;
+  if ((r = query_fetch(c, &np, h.n, 1)) || (r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, nullptr))) return r;
+  *n_pairs = np;
+  if (np > cap) {   // rows are known only for pairs that were refined
+    *n = -1;
+    if (cap == 0 && !rows) return TJ_OK;   // the count-only call
+    c->err = name + ": " + std::to_string(np) + " pairs are listed, the caller's slots hold " + std::to_string(cap) + ": nothing was written";
+    return TJ_ERR_CAPACITY;
+  }
+  *n = nr;
+  if ((r = query_fetch(c, rows, h.out, std::min(row_cap, nr))) || (r = query_finish(c, nullptr))) return r;
+  if (nr > row_cap) { c->err = name + ": " + std::to_string(nr) + " rows, the caller's hold " + std::to_string(row_cap) + ": the first " + std::to_string(row_cap) + " were written"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
 int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
   if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
@@ -1643,6 +1726,8 @@ int tj_path_crossings(tj_ctx* c, double range, double tol, int max_depth, int ma
 int tj_crossing_record_size(void) { return (int)sizeof(tj_crossing_record); }
 int tj_timing_margin(tj_ctx* c, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n) { return listed_run<MarginQuery>(c, dist, tol, max_depth, max_windows, max_slip, nullptr, nullptr, rows, cap, n); }
 int tj_margin_record_size(void) { return (int)sizeof(tj_margin_record); }
+int tj_proximity_windows(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n) { return proximity_run(c, dist, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, cap, n_pairs, n); }
+int tj_proximity_row_size(void) { return (int)sizeof(tj_proximity_row); }
 
 // tj_obstacle_approach: every owned robot from the context's own state (a sharded context's own robots are current; nothing of another robot is read)
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {

@@ -696,6 +696,30 @@ int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol
   return group_listed<MarginQuery>(g, dist, tol, max_depth, max_windows, max_slip, rows, cap, n);
 }
 
+// tj_proximity_windows, rank after rank: every rank gets the whole `cap` in pair slots and what is left of it in rows.  More pairs than `cap` over the ranks together, as
+// one context counts them: *n = -1.  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.
+int tj_group_proximity_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n) {
+  if (!g || !n || !n_pairs || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int pairs = 0, total = 0;
+  bool unknown = false;
+  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    const int room = unknown ? 0 : std::max(0, cap - total);
+    int np = 0, nr = 0;
+    const int e = proximity_run(c, dist, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, cap, room, &np, &nr);
+    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
+    pairs += np;
+    if (nr < 0) unknown = true; else total += nr;
+    return (int)TJ_OK;
+  });
+  if (rc < 0) return rc;
+  *n_pairs = pairs;
+  *n = unknown || pairs > cap ? -1 : total;
+  if (cap == 0 && !rows) return TJ_OK;   // the count-only call
+  if (*n < 0) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_proximity_windows: " + std::to_string(pairs) + " pairs are listed, the caller's slots hold " + std::to_string(cap));
+  if (total > cap) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_proximity_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 // from every rank's own state: nothing of another robot is read
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* out) {
   return group_query(g, false, false, out, {}, {}, [&](tj_ctx* c, const double*, const double*, tj_obstacle_robot* part) {

@@ -75,6 +75,18 @@ int tj_kat_get_swept_record(tj_ctx* c, double* ccdinfo, double* cbox);
  * Returns the number of ints written, 0 for bad arguments, -needed if cap is too small. */
 int tj_kat_plan(const tj_ctx* c, const tj_params* p, const int* facts, int* out, int cap, char* msg, int msg_cap);
 
+/* ---- the launch sequence (csrc/host_launch.h) ------------------------------------------------------
+ * What the schedules enqueue for a list of calls (kid, sched, chain_pos) -- sched: 0 stage, 1 chain, 2 phase --, as flat records of ints; nothing is launched.
+ * Per call: exists, number of records, the host state (SchedState) after the call, then the Launch records: kernel id (K_COUNT and up: the three gates, k_xch_wait,
+ * the counter clear), form, primitive kind, queue, grid, block, dynamic LDS bytes, four scalar arguments, the eleven Dev fields the launch overrides (the Python
+ * package names the entries: SCHED_STATE, LAUNCH_FIELDS).
+ *   c != NULL: that context's own Dev, plan and state; its state is written to state[] and stays as it is (p, facts, lsc_follow are ignored).  One entry is read
+ *              from state[] instead: xs_same_queue_now, which tj_profile_kernels sets around its run only -- nonzero asks for that run's sequence.
+ *   c == NULL: the planner's Dev and plan on the caller's parameters and facts[] (as tj_kat_plan), Dev::lsc_follow = lsc_follow, from the start state in state[];
+ *              needs no device.
+ * Returns the number of ints written, 0 for bad arguments or a shape the planner refuses, -needed if cap is too small. */
+int tj_kat_launches(const tj_ctx* c, const tj_params* p, const int* facts, int lsc_follow, int* state, const int* calls, int n_calls, int* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -362,7 +362,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_kdop_wave", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_kdop_wave", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_launches", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -434,6 +434,41 @@ def plan_record(params=None, facts=None, ctx=None):
         raise TrajAdmmError(f"tj_kat_plan returned {n}, the package knows {out.size} entries")
     v = [int(x) for x in out]
     return dict(zip(PLAN_FACTS, v)), dict(zip(PLAN_FIELDS, v[len(PLAN_FACTS):])), msg.value.decode()
+
+
+# the launch sequence's records (tj_kat_launches, csrc/host_launch.h): SchedState, Launch, the ids beyond the K_* kernels, the schedules
+SCHED_STATE = ("xs_seq", "xs_seq_gated", "keep_seq", "fa_seq", "fa_armed", "fa_mid_now", "hull_from_units", "xs_two_queues", "keep_two_queues", "xs_same_queue_now", "xs_fault",
+               "xf_used0", "xf_used1", "ccd_valid", "ck_in_begin", "xch_wait_kernel", "lsc_base")
+LAUNCH_FIELDS = ("kid", "form", "prim", "queue", "grid", "block", "lds", "arg0", "arg1", "arg2", "arg3",
+                 "xs_async", "keep_async", "fa", "xs_seq", "keep_seq", "fa_seq", "fa_mid", "fa_units", "fa_nfront", "fa_nls", "c2_fold")
+KERNELS = ("k_begin", "k_hullinfo", "k_front", "k_obs_query", "k_sep_self_rows", "k_mid", "k_obs_solve", "k_sep_self_solve", "k_keep", "k_sep_self_compact", "k_grad", "k_xsolve",
+           "k_xsolve_c2", "k_ccd_prep", "k_ccd", "k_ccd_obs", "k_ccd_self_pairs", "k_ccd_self_seq", "k_linesearch", "k_ls_coupled", "k_ls_commit", "k_slack")   # tj_kernel_name, in id order
+LAUNCH_EXTRA = ("k_xs_gate", "k_keep_gate", "k_fa_gate", "k_xch_wait", "xf_seg_clear")   # kid = len(KERNELS) + index; the last one is a memset, not a kernel
+SCHED_STAGE, SCHED_CHAIN, SCHED_PHASE = 0, 1, 2
+
+
+def launch_records(calls, state=None, params=None, facts=None, follow=0, ctx=None):
+    """What the schedules enqueue for calls = [(kid, sched, chain_pos), ...] (tj_kat_launches; nothing is launched): (start state, [(exists, state after, [launch, ...]), ...]), states
+    and launches as lists of ints in the order of SCHED_STATE / LAUNCH_FIELDS.  ctx: a context's own Dev, plan and state; else -- no GPU needed -- the planner's on a TjParams and a
+    dict of PLAN_FACTS, from the start state given.  With ctx, of `state` only xs_same_queue_now is read (nonzero: the sequence of tj_profile_kernels)"""
+    lib = load_library(kat=True)
+    ns, nl = len(SCHED_STATE), len(LAUNCH_FIELDS)
+    f = np.array([facts[k] for k in PLAN_FACTS] if facts else [0] * len(PLAN_FACTS), dtype=np.int32)
+    st = np.array(list(state) if state is not None else [0] * ns, dtype=np.int32)
+    cl = np.array(calls, dtype=np.int32).reshape(-1, 3)
+    out = np.zeros(len(cl) * (2 + ns + 8 * nl) + 1, dtype=np.int32)
+    n = lib.tj_kat_launches(ctx, C.byref(params) if params is not None else None, _i(f), C.c_int(follow), _i(st), _i(cl), C.c_int(len(cl)), _i(out), C.c_int(out.size))
+    if n <= 0 and len(cl):
+        raise TrajAdmmError(f"tj_kat_launches returned {n}")
+    v, res, at = [int(x) for x in out[:n]], [], 0
+    for _ in range(len(cl)):
+        k = v[at + 1]
+        body = at + 2 + ns
+        res.append((v[at], v[at + 2:body], [v[body + i * nl:body + (i + 1) * nl] for i in range(k)]))
+        at = body + k * nl
+    if at != n:
+        raise TrajAdmmError(f"tj_kat_launches wrote {n} ints, the package read {at}")
+    return [int(x) for x in st], res
 
 
 class Solver:

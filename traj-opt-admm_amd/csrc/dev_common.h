@@ -104,6 +104,10 @@ enum { K_BEGIN = 0, K_HULLINFO, K_FRONT, K_SEP_OBS /* k_obs_query */, K_SEP_SELF
        K_CCD_PREP, K_CCD, K_CCD_OBS, K_CCD_SELF_PAIRS, K_CCD_SELF_SEQ, K_LINESEARCH,
        K_LS_COUPLED, K_LS_COMMIT,   // coupled mode only
        K_SLACK, K_COUNT };
+constexpr const char* kKernelNames[] = {"k_begin", "k_hullinfo", "k_front", "k_obs_query", "k_sep_self_rows", "k_mid", "k_obs_solve", "k_sep_self_solve", "k_keep", "k_sep_self_compact",
+                                        "k_grad", "k_xsolve", "k_xsolve_c2", "k_ccd_prep", "k_ccd", "k_ccd_obs", "k_ccd_self_pairs", "k_ccd_self_seq",
+                                        "k_linesearch", "k_ls_coupled", "k_ls_commit", "k_slack"};   // tj_kernel_name
+static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == K_COUNT, "one name per kernel id");
 constexpr int LS_HELP_MAX = 8;                 // k_linesearch: at most this many blocks per robot (16 candidates per super-round)
 constexpr int LS_TAB_STRIDE = 3 * LS_HELP_MAX * 2;   // Dev::ls_tab per robot: three rotating sets (super-round % 3) of LS_HELP_MAX blocks x 2 candidates
 constexpr unsigned LS_WORD_DONE = 0x7fffffffu;

@@ -5,7 +5,7 @@
 // a shape this version cannot run -- the error.  It makes no HIP runtime call and reads every switch of the plan in exactly one place, so it runs (and is tested)
 // without a device.  tj_create plans, claims its queues, plans AGAIN with PlanFacts::claim_refused set if the claim was refused, and creates its streams; a stream
 // that cannot be created downgrades the plan through plan_downgrade.  Two helpers live here because more than one place needs the same arithmetic: plan_grids
-// (the grid sizes of the union kernels: the residency rule of Dev::fa_mid and launch_kernel) and plan_ls_help (tj_group.h re-decides it for ranks sharing a device).
+// (the grid sizes of the union kernels: the residency rule of Dev::fa_mid and sequence_kernel, host_launch.h) and plan_ls_help (tj_group.h re-decides it for ranks sharing a device).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -28,7 +28,7 @@ struct PlanFacts {
 };
 constexpr int PLAN_FACT_INTS = sizeof(PlanFacts) / sizeof(int);
 
-// ---- the host-side half of the plan (tj_ctx::hp: kept as made; CrossQueue owns the live copies of xs_two_queues / keep_two_queues / xs_fault, hwq_refused is a record only) ----
+// ---- the host-side half of the plan (tj_ctx::hp: kept as made; SchedState, host_launch.h, owns the live copies of xs_two_queues / keep_two_queues / xs_fault, hwq_refused is a record only) ----
 struct HostPlan {
   size_t lds_grad = 0, lds_xs = 0, lds_xs2 = 0, lds_ls = 0, lds_seq = 0;
   LsLayout lsl;
@@ -39,7 +39,7 @@ struct HostPlan {
   int fa_mid_front = 0;      // the k_front grid the residency rule of fa_mid_ok was decided for (0: not asked)
   bool hwq_refused = false;  // no room in the queue budget
   int queues = 1; bool forced = false;                 // streams the context wants (main + second + third) / an explicit TJ_XS_ASYNC=1 / TJ_KEEP_ASYNC=1 bypasses the budget
-  bool xs_two_queues = false, keep_two_queues = false; // CrossQueue: stream2 / stream3 in use
+  bool xs_two_queues = false, keep_two_queues = false; // SchedState: stream2 / stream3 in use
   bool heal = true; int xs_fault = 0;                  // TJ_HEAL=0: self-healing off / test hook TJ_XS_FAULT: the n-th gate reports a time-out
   bool bvh_skip_forced = false, ls_help_forced = false; int ls_help_asked = 0;   // TJ_BVH_SKIP / TJ_LS_HELP are set (set_obstacles / tj_group.h decide otherwise)
   size_t lds_grad_of(bool fold, int res) const { return lds_grad + (fold ? grad_fold_extra_doubles(res) * sizeof(double) : 0); }   // dynamic LDS of k_grad<fold>

@@ -43,6 +43,7 @@
 #include "kernels_proximity.h"
 #include "kernels_flight_profile.h"
 #include "host_plan.h"
+#include "host_launch.h"
 
 using namespace tj;
 
@@ -58,17 +59,14 @@ static bool queue_budget(int device, int n, bool forced = true) {
 }
 
 // The cross-queue schedule of one context: the asynchronous Newton solve (Dev::xs_async) and front (Dev::fa) on stream2, the asynchronous plane refinement (Dev::keep_async) on
-// stream3.  Each pairing has a host counter that must match a monotonic word on the device: xs_seq <-> Dev::xs_go (k_grad opens the gate of its k_xsolve; xs_seq_gated: the last
-// pairing a gate was launched for), keep_seq <-> Dev::keep_go (k_front opens the refinement's gate), fa_seq <-> Dev::fa_sync (k_linesearch(i) <-> k_front(i + 1)).  restart_pairings resets both.
+// stream3: the streams and the queue claim.  The pairing counters and flags that the launch sequence advances are SchedState's (host_launch.h, tj_ctx::ss).
 struct CrossQueue {
-  hipStream_t stream2 = nullptr, stream3 = nullptr; int xs_seq = 0, xs_seq_gated = 0, keep_seq = 0, fa_seq = 0;
-  bool xs_two_queues = false, keep_two_queues = false, xs_same_queue_now = false;   // stream2 / stream3 in use (heal_check latches both off for good) / tj_profile_kernels: one queue
-  bool fa_armed = false, fa_mid_now = false, hull_from_units = false;   // the last k_linesearch enqueued belongs to pairing fa_seq (the next k_front goes to stream2 behind k_fa_gate) / the k_mid about to be enqueued waits for k_front itself (Dev::fa_mid) / the last k_linesearch published no hull cache (the next k_front forms the records)
-  int hwq_claim = 0, xs_fault = 0;   // hardware queues claimed out of the process's budget for contexts that sleep across queues (tj_create) / test hook TJ_XS_FAULT: the n-th gate reports a time-out
+  hipStream_t stream2 = nullptr, stream3 = nullptr;
+  int hwq_claim = 0;   // hardware queues claimed out of the process's budget for contexts that sleep across queues (tj_create)
 };
 // The checkpoint a batch can be restored from (heal_check; the careful re-run of a coupled sharded group, tj_group_iterate), touched by checkpoint_take / _restore / _drop
-// only.  Device half: the regions of `tab` and the control block, copied to an arena of tj_create (in_begin: taken by the next k_begin).  Host half: the flags that describe it.
-struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bool in_begin = false; bool begin_folded = false, maybe_deferred = false; int lsc_base = 0; };
+// only.  Device half: the regions of `tab` and the control block, copied to an arena of tj_create (SchedState::ck_in_begin: taken by the next k_begin).  Host half: the flags that describe it.
+struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bool begin_folded = false, maybe_deferred = false; int lsc_base = 0; };
 
 // what a context holds for a row-listing query (tj_pair_approach, tj_path_crossings, tj_timing_margin; listed_run)
 template <class Args, class Rec>
@@ -87,22 +85,19 @@ struct tj_ctx {
   std::string err;
   bool have_cloud = false, have_state = false;
   CrossQueue xq;
+  SchedState ss;   // the host state of the launch sequence (host_launch.h): pairing counters, queue flags, cache flags
   HostPlan hp; PlanFacts facts{};   // the host half of the launch plan (host_plan.h; Dev holds the rest) and the device facts it was decided on.  The plan AS MADE by tj_create: the live
-                                    // queue state is xq's (xs_two_queues, keep_two_queues, xs_fault start as planned; heal_check clears them there only)
+                                    // queue state is ss's (xs_two_queues, keep_two_queues, xs_fault start as planned; heal_check clears them there only)
   // Self-healing (heal_check): a wait between the queues that runs out (ERR_XS_TIMEOUT -- in practice a GPU shared with another process) must not fail a run.  snap_iters:
   // iterations enqueued since the first tj_iterate_async after a host look took the checkpoint.  TJ_HEAL=0: off (the bit is reported as TJ_ERR_NO_PROGRESS, as in round 5).
   bool heal_busy = false; long long snap_iters = 0; int async_fallbacks = 0; Checkpoint ck;
   bool hull_valid = false;   // Dev::fuse: the hull cache matches the control points (else k_hullinfo runs before the next iteration)
-  bool ccd_valid = false;    // Dev::fuse: the swept-hull cache of the owned robots matches their direction records (k_xsolve's tail wrote it; tj_set_direction / tj_set_state clear it)
   long long launches = 0;    // kernels enqueued by the iteration schedules so far (tj_launch_count)
   bool begin_folded = false; // the last k_linesearch enqueued has already begun the next iteration (begin_next): the next phase 0 / iteration launches no k_begin
   // direct exchange between sharded contexts (Dev::xch): this rank's receive block (uncached), the peers' blocks as mapped here, the device table
   void* xch_block = nullptr; size_t xch_bytes = 0; bool xch_ipc_exported = false;
   std::vector<void*> xch_ipc_opened;
   XchPeers* xch_table = nullptr;
-  bool xf_used[2] = {false, false};   // the cache units of k_front [0] / k_ccd [1] have counted themselves done since the last begin: a repeat of that launch before the next begin first zeroes the counters
-  bool xch_wait_kernel = false;   // direct exchange, wait mode 0: a one-wave k_xch_wait launch in front of k_front / k_ccd
-  int lsc_base = 0;          // coupled mode, sharded context that follows the Armijo search (Dev::lsc_follow): first round of the table the next phases 4 / 5 evaluate and decide (0 at every iteration's start)
   // cloud-dependent allocations (rebuilt by tj_set_cloud)
   std::vector<void*> cloud_allocs;
   std::vector<int> cloud_order;   // sorted position -> index in the caller's cloud (ids of tj_get/set_obs_cache)
@@ -208,171 +203,67 @@ int query_fetch(tj_ctx* c, T* host, const T* dev, size_t n) {
   return TJ_OK;
 }
 
-// every kernel the iteration schedules enqueue is counted (tj_launch_count: launches per iteration of a schedule, bench.py / tests)
+// ---- the iteration's launches: what is enqueued is decided by sequence_kernel (host_launch.h); issue() enqueues one record and is the only place that names a
+// kernel of the iteration.  Every kernel it enqueues is counted (tj_launch_count: launches per iteration of a schedule, bench.py / tests); the counter clears are not.
 #define TJ_LAUNCH(...) do { c->launches++; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
-// ---- kernels of one iteration, in stream order (also the unit of tj_profile_kernels) ----
-const char* const kKernelNames[K_COUNT] = {"k_begin", "k_hullinfo", "k_front", "k_obs_query", "k_sep_self_rows", "k_mid", "k_obs_solve", "k_sep_self_solve", "k_keep", "k_sep_self_compact",
-                                           "k_grad", "k_xsolve", "k_xsolve_c2", "k_ccd_prep", "k_ccd", "k_ccd_obs", "k_ccd_self_pairs", "k_ccd_self_seq",
-                                           "k_linesearch", "k_ls_coupled", "k_ls_commit", "k_slack"};
-
-// the schedule a launch belongs to:
-//   Stage: the stage API (tj_run_stage) and the host's one-off launches -- every stage as its own kernels.
-//   Chain: the single-context iteration, a linear chain on one queue in which independent stages share a launch (union kernels
-//          k_front / k_mid / k_ccd instead of their constituents), the slack/dual update is the deferred one inside k_mid, and --
-//          except in coupled mode -- the hull cache comes from k_linesearch (Dev::fuse); the asynchronous schedules (second and
-//          third queue) belong to it alone.
-//   Phase: the phases of a sharded iteration (enqueue_body): union kernels as well, on the context's queue only.
-enum class Sched { Stage, Chain, Phase };
-
-// launch exactly one kernel (returns false for kernels that do not exist in this mode / schedule).
-// chain_pos (chains only): 0 = an iteration on its own (k_begin launched, k_linesearch plain); bit 1 = this iteration's
-// begin work was done by the previous iteration's k_linesearch (no k_begin launch); bit 2 = this iteration's k_linesearch also
-// does the next iteration's begin work.
-bool launch_kernel(tj_ctx* c, int kid, hipStream_t s, Sched sched, int chain_pos = 0) {
-  Dev d_ = c->d;
-  if (sched != Sched::Chain) d_.xs_async = 0;   // the asynchronous solve's tickets and flags belong to the single-GPU chain (begin -> k_grad -> k_xsolve -> k_ccd, every iteration); stage API and phases: plain
-  d_.xs_seq = 0; d_.keep_seq = 0;
-  const bool keep2q = sched == Sched::Chain && c->xq.keep_two_queues && !c->xq.xs_same_queue_now;
-  if (!keep2q) d_.keep_async = 0;
-  if (kid == K_GRAD && d_.xs_async && c->xq.xs_two_queues && !c->xq.xs_same_queue_now) d_.xs_seq = ++c->xq.xs_seq;   // this k_grad opens the gate of its k_xsolve
-  d_.fa_seq = 0; d_.fa_mid = 0; d_.fa_units = 0;
-  if (sched != Sched::Chain) d_.fa = 0;   // (the context switch belongs to the single-GPU chain like xs_async; fa contexts are never sharded, and the stage API rebuilds the hull cache itself)
-  const bool fa2q = sched == Sched::Chain && d_.fa && c->xq.xs_two_queues && !c->xq.xs_same_queue_now;
-  const Dev& d = d_;
-  const int owned = d.u1 - d.u0;
-  const bool multi = d.mode >= 1, coupled = d.mode == 2;
-  const Grids g = plan_grids(d, c->hp.n_solve_env);   // (of d as this launch sees it: the per-launch flags above count)
-  const int n_solve = g.n_solve, n_obs_solve = g.n_obs_solve, n_rows = g.n_rows, n_front = g.n_front;
-  const bool chained = sched != Sched::Stage;          // an iteration chain (one context, or the phases of a sharded schedule) as opposed to the stage API
-  d_.fa_nfront = n_front; d_.fa_nls = coupled ? owned * LSC_ROUNDS : owned * d.ls_help;
-  switch (kid) {
-    case K_BEGIN: if (chain_pos & 1) return false;
-      if (c->ck.in_begin) { c->ck.in_begin = false; TJ_LAUNCH(k_begin, dim3(1 + 128), dim3(256), 0, s, d, c->ck.tab, c->ck.n, c->ck.ctl); }   // (checkpoint_take: the device half rides in this launch)
-      else TJ_LAUNCH(k_begin, dim3(1), dim3(256), 0, s, d, nullptr, 0, nullptr);
-      c->xf_used[0] = c->xf_used[1] = false; return true;
-    case K_HULLINFO: if ((chained && (d.fuse || d.xf_all)) || !multi) return false; TJ_LAUNCH(k_hullinfo, dim3(d.U * d.S), dim3(64), 0, s, d); return true;  // unfused sharded phases (coupled mode): always (all robots, after the gather)
-    case K_FRONT: if (!chained) return false;
-      if (d.xf) { if (c->xf_used[0]) (void)hipMemsetAsync(d.xf_seg, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[0] = true; }
-      if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 0);   // ranks sharing a device: the wait for the peers' control points is a launch of its own
-      if (keep2q) d_.keep_seq = ++c->xq.keep_seq;   // this k_front opens the gate of the iteration's plane refinement (third queue)
-      if (c->xq.fa_armed && fa2q && (chain_pos & 1)) {   // asynchronous front: on the second queue, next to the k_linesearch just enqueued (pairing fa_seq), behind the residency gate
-        c->xq.fa_armed = false;
-        d_.fa_seq = c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->hp.fa_mid_ok ? 1 : 0; c->xq.fa_mid_now = c->hp.fa_mid_ok;
-        TJ_LAUNCH(k_fa_gate, dim3(1), dim3(64), 0, c->xq.stream2, d, (int)((unsigned)c->xq.fa_seq * (unsigned)d.fa_nls));
-        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_front<decltype(prim)::value, true>), dim3(n_front), dim3(64), 0, c->xq.stream2, d); });
-        return true;
-      }
-      d_.fa_units = (sched == Sched::Chain && c->xq.hull_from_units) ? 1 : 0;   // (the k_linesearch before it published no hull cache: one-queue emulation of the asynchronous front)
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_front<decltype(prim)::value>), dim3(n_front), dim3(64), 0, s, d); });
-      if (keep2q) {
-        d_.keep_seq = 0;
-        TJ_LAUNCH(k_keep_gate, dim3(1), dim3(64), 0, c->xq.stream3, d, c->xq.keep_seq);
-        TJ_LAUNCH(k_keep, dim3(d.keep_waves), dim3(64), 0, c->xq.stream3, d, 2);
-      }
-      return true;
-    case K_SEP_OBS: if (chained) return false;  // stage API only
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_obs_query<decltype(prim)::value>), dim3(owned * d.S), dim3(64), 0, s, d); });
-      return true;
-    case K_OBS_SOLVE: if (sched == Sched::Chain || !n_obs_solve) return false;
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_obs_solve<decltype(prim)::value>), dim3(n_obs_solve), dim3(64), 0, s, d); });
-      return true;
-    case K_SEP_SELF_ROWS: if (chained || !multi) return false; TJ_LAUNCH(k_sep_self_rows, dim3(n_rows), dim3(64), 0, s, d); return true;
-    case K_MID: if (!chained) return false;
-      if (sched == Sched::Chain && c->xq.fa_mid_now) {   // asynchronous front, small grids: this launch starts while the iteration's k_front (pairing fa_seq) still runs -- its solve waves wait for it themselves (+ the watcher block)
-        c->xq.fa_mid_now = false;
-        d_.fa_seq = c->xq.fa_seq; d_.fa_mid = 1;
-        with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value, true>), dim3(MidLayout(d, n_solve, n_obs_solve, true, d.mid_order != 0).total), dim3(64), 0, s, d, n_solve, n_obs_solve); });
-        return true;
-      }
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_mid<decltype(prim)::value>), dim3(MidLayout(d, n_solve, n_obs_solve, false, d.mid_order != 0).total), dim3(64), 0, s, d, n_solve, n_obs_solve); });
-      return true;
-    case K_SEP_SELF_SOLVE: if (sched == Sched::Chain || !n_solve) return false; TJ_LAUNCH(k_sep_self_solve, dim3(n_solve), dim3(64), 0, s, d); return true;
-    case K_KEEP:  // "optimal_plane":1 only; single UAV: a wave per segment, multi UAV: lanes over the switched-on pair slots
-      if (!d.optimal_plane || (multi ? false : d.N == 0)) return false;
-      TJ_LAUNCH(k_keep, dim3(multi ? 1024 : owned * d.S), dim3(64), 0, s, d, keep2q ? 1 : 0); return true;   // (asynchronous refinement: the new pairs only)
-    case K_SEP_SELF_COMPACT: if (chained && c->hp.grad_fold) return false;   // iteration chains (single GPU and sharded phases): folded into k_grad
-      TJ_LAUNCH(k_sep_self_compact, dim3(owned * d.S), dim3(64), 0, s, d); return true;
-    case K_GRAD:
-      if (chained && c->hp.grad_fold) TJ_LAUNCH((k_grad<true>), dim3(owned * d.P), dim3(GRAD_FOLD_THREADS), c->hp.lds_grad_of(true, d.res), s, d);
-      else TJ_LAUNCH((k_grad<false>), dim3(owned * d.P), dim3(GRAD_THREADS), c->hp.lds_grad, s, d);
-      return true;
-    case K_XSOLVE: {
-      Dev dx = d;
-      if (!chained) dx.c2_fold = 0;   // (the stage API's solve is followed by k_xsolve_c2)
-      const Dev& d = dx;
-      if (c->xq.xs_seq_gated != c->xq.xs_seq) {   // asynchronous solve: on the second queue, behind a gate that this iteration's k_grad opens (profiling: it simply follows k_grad on this queue)
-        c->xq.xs_seq_gated = c->xq.xs_seq;
-        s = c->xq.stream2;
-        TJ_LAUNCH(k_xs_gate, dim3(1), dim3(64), 0, s, d, c->xq.xs_seq, (c->xq.xs_fault > 0 && c->xq.xs_seq == c->xq.xs_fault) ? 1 : 0);
-      }
-      if (d.xs_band) TJ_LAUNCH(k_xsolve_band, dim3(owned), dim3(XB_THREADS), c->hp.lds_xs, s, d);
-      else with_xsolve(d.P, [&](auto n) { TJ_LAUNCH((k_xsolve<decltype(n)::value>), dim3(owned), dim3(XS_LOAD_THREADS), c->hp.lds_xs, s, d); });
-      if (chained && d.fuse && !d.xs_band) c->ccd_valid = true;   // its tail has left the owned robots' swept-hull cache
-      return true;
-    }
-    case K_XSOLVE_C2:
-      if (coupled && chained && d.c2_fold) return false;   // k_xsolve has finished the arrowhead solve itself
-      if (coupled) { if (d.xs_band) TJ_LAUNCH(k_xsolve_c2_band, dim3(owned), dim3(XS_THREADS), c->hp.lds_xs2, s, d); else TJ_LAUNCH(k_xsolve_c2, dim3(owned), dim3(XS_THREADS), c->hp.lds_xs2, s, d); }
-      return coupled;
-    case K_CCD_PREP: if (chained && d.xf_all) return false;                                // coupled chain: k_ccd's units build every robot's record
-      if (chained && d.fuse && !d.xs_band && c->ccd_valid) return false;  // fused chains: k_xsolve's tail leaves the swept-hull cache
-      if (chained && d.xf) { if (owned > 0) TJ_LAUNCH(k_ccd_prep, dim3(owned * d.S), dim3(64), 0, s, d, d.u0); }   // (the other ranks' robots: k_ccd's foreign units)
-      else TJ_LAUNCH(k_ccd_prep, dim3(d.U * d.S), dim3(64), 0, s, d, 0);
-      return true;
-    case K_CCD: if (!chained) return false;
-      if (d.xf) { if (c->xf_used[1]) (void)hipMemsetAsync(d.xf_seg + (size_t)d.S * XF_SEG_STRIDE, 0, (size_t)d.S * XF_SEG_STRIDE * sizeof(int), s); c->xf_used[1] = true; }
-      if (d.xch && c->xch_wait_kernel) TJ_LAUNCH(k_xch_wait, dim3(1), dim3(64), 0, s, d, 1);   // ranks sharing a device: the wait for the peers' direction records is a launch of its own
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_lean<decltype(prim)::value>), dim3(CcdLayout(d).total()), dim3(64), 0, s, d); });   // (its layout counts the foreign units and the finisher of the folded pair replay)
-      return true;
-    case K_CCD_OBS: if (sched == Sched::Chain) return false;
-      with_prim(d, [&](auto prim) { TJ_LAUNCH((k_ccd_obs<decltype(prim)::value>), dim3(owned * d.S), dim3(64), 0, s, d); });
-      return true;
-    case K_CCD_SELF_PAIRS: if (sched == Sched::Chain || !multi) return false; TJ_LAUNCH(k_ccd_self_pairs, dim3(n_rows), dim3(64), 0, s, d); return true;
-    case K_CCD_SELF_SEQ:
-      if (chained && d.seq_fold) return false;   // the last block of k_ccd has done it
-      if (!multi && sched == Sched::Chain) return false;   // single UAV: no pairs to replay, and k_xsolve has left gnorm = |g| itself -- one launch less in the chain
-      TJ_LAUNCH(k_ccd_self_seq, dim3(1), dim3(64), c->hp.lds_seq, s, d); return true;
-    case K_LINESEARCH: if (!coupled) { c->xq.hull_from_units = false;
-      if (fa2q && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->hp.fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; c->xq.hull_from_units = true; }
-      else if (sched == Sched::Chain && d_.fa && c->hp.fa_emulate && (chain_pos & 2)) { d_.fa_units = 1; c->xq.hull_from_units = true; }   // the next iteration of the batch follows: its k_front runs next to this launch
-      TJ_LAUNCH(k_linesearch, dim3(owned * d.ls_help), dim3(LS_THREADS), c->hp.lds_ls, s, d, c->hp.lsl, (chain_pos & 2) ? 1 : 0); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // (its last block runs begin_body)
-      return !coupled;
-    // coupled mode ("decouple":0): evaluation rounds of the summed-energy Armijo search, commit
-    case K_LS_COUPLED:
-      if (coupled) {
-        const int base = (owned != d.U && d.lsc_follow) ? c->lsc_base : 0;   // (a followed search of a sharded context: the rounds beyond the first table)
-        c->xq.hull_from_units = false;
-        if (fa2q && c->hp.lsc_wide && owned == d.U && (chain_pos & 2)) { d_.fa_seq = ++c->xq.fa_seq; d_.fa_units = 1; d_.fa_mid = c->hp.fa_mid_ok ? 1 : 0; c->xq.fa_armed = true; }   // asynchronous front: the next k_front runs next to this launch
-        if (c->hp.lsc_wide) { TJ_LAUNCH(k_ls_coupled, dim3(owned * LSC_ROUNDS), dim3(LS_THREADS), c->hp.lds_ls, s, d, c->hp.lsl, 0, LSC_ROUNDS, (chain_pos & 2) ? 1 : 0, base); if (chain_pos & 2) c->xf_used[0] = c->xf_used[1] = false; }   // all rounds at once, one block per (robot, round)
-        else for (int r = 0; r < LSC_ROUNDS; r++) TJ_LAUNCH(k_ls_coupled, dim3(owned), dim3(LS_THREADS), c->hp.lds_ls, s, d, c->hp.lsl, r, 1, 0, base);
-      }
-      return coupled;
-    case K_LS_COMMIT: if (coupled && !(c->hp.lsc_wide && owned == d.U)) TJ_LAUNCH(k_ls_commit, dim3(owned), dim3(64), 0, s, d, (owned != d.U && d.lsc_follow) ? c->lsc_base : 0); return coupled;   // (one context, all rounds in one launch: its last block commits)
-    case K_SLACK: if (sched == Sched::Chain) return false; TJ_LAUNCH(k_slack, dim3(owned * d.P), dim3(64), 0, s, d, 0); return true;
+void issue(tj_ctx* c, const Launch& l) {
+  const hipStream_t s = l.queue == 1 ? c->xq.stream2 : (l.queue == 2 ? c->xq.stream3 : c->stream);
+  if (l.kid == L_XF_CLEAR) { (void)hipMemsetAsync(c->d.xf_seg + (size_t)l.arg[0] * c->d.S * XF_SEG_STRIDE, 0, (size_t)c->d.S * XF_SEG_STRIDE * sizeof(int), s); return; }
+  Dev d = c->d; apply_patch(d, l.patch);
+  const dim3 grid(l.grid), block(l.block); const size_t lds = (size_t)l.lds; const int* a = l.arg;
+  c->launches++;
+  switch (l.kid) {
+    case K_BEGIN: if (l.form) hipLaunchKernelGGL(k_begin, grid, block, lds, s, d, c->ck.tab, c->ck.n, c->ck.ctl); else hipLaunchKernelGGL(k_begin, grid, block, lds, s, d, nullptr, 0, nullptr); break;
+    case K_HULLINFO: hipLaunchKernelGGL(k_hullinfo, grid, block, lds, s, d); break;
+    case K_FRONT: with_prim(d, [&](auto prim) { if (l.form) hipLaunchKernelGGL((k_front<decltype(prim)::value, true>), grid, block, lds, s, d); else hipLaunchKernelGGL((k_front<decltype(prim)::value>), grid, block, lds, s, d); }); break;
+    case K_SEP_OBS: with_prim(d, [&](auto prim) { hipLaunchKernelGGL((k_obs_query<decltype(prim)::value>), grid, block, lds, s, d); }); break;
+    case K_OBS_SOLVE: with_prim(d, [&](auto prim) { hipLaunchKernelGGL((k_obs_solve<decltype(prim)::value>), grid, block, lds, s, d); }); break;
+    case K_SEP_SELF_ROWS: hipLaunchKernelGGL(k_sep_self_rows, grid, block, lds, s, d); break;
+    case K_MID: with_prim(d, [&](auto prim) { if (l.form) hipLaunchKernelGGL((k_mid<decltype(prim)::value, true>), grid, block, lds, s, d, a[0], a[1]); else hipLaunchKernelGGL((k_mid<decltype(prim)::value>), grid, block, lds, s, d, a[0], a[1]); }); break;
+    case K_SEP_SELF_SOLVE: hipLaunchKernelGGL(k_sep_self_solve, grid, block, lds, s, d); break;
+    case K_KEEP: hipLaunchKernelGGL(k_keep, grid, block, lds, s, d, a[0]); break;
+    case K_SEP_SELF_COMPACT: hipLaunchKernelGGL(k_sep_self_compact, grid, block, lds, s, d); break;
+    case K_GRAD: if (l.form) hipLaunchKernelGGL((k_grad<true>), grid, block, lds, s, d); else hipLaunchKernelGGL((k_grad<false>), grid, block, lds, s, d); break;
+    case K_XSOLVE:
+      if (l.form == FORM_BAND) hipLaunchKernelGGL(k_xsolve_band, grid, block, lds, s, d);
+      else with_xsolve(d.P, [&](auto n) { hipLaunchKernelGGL((k_xsolve<decltype(n)::value>), grid, block, lds, s, d); });
+      break;
+    case K_XSOLVE_C2: if (l.form == FORM_BAND) hipLaunchKernelGGL(k_xsolve_c2_band, grid, block, lds, s, d); else hipLaunchKernelGGL(k_xsolve_c2, grid, block, lds, s, d); break;
+    case K_CCD_PREP: hipLaunchKernelGGL(k_ccd_prep, grid, block, lds, s, d, a[0]); break;
+    case K_CCD: with_prim(d, [&](auto prim) { hipLaunchKernelGGL((k_ccd_lean<decltype(prim)::value>), grid, block, lds, s, d); }); break;
+    case K_CCD_OBS: with_prim(d, [&](auto prim) { hipLaunchKernelGGL((k_ccd_obs<decltype(prim)::value>), grid, block, lds, s, d); }); break;
+    case K_CCD_SELF_PAIRS: hipLaunchKernelGGL(k_ccd_self_pairs, grid, block, lds, s, d); break;
+    case K_CCD_SELF_SEQ: hipLaunchKernelGGL(k_ccd_self_seq, grid, block, lds, s, d); break;
+    case K_LINESEARCH: hipLaunchKernelGGL(k_linesearch, grid, block, lds, s, d, c->hp.lsl, a[0]); break;
+    case K_LS_COUPLED: hipLaunchKernelGGL(k_ls_coupled, grid, block, lds, s, d, c->hp.lsl, a[0], a[1], a[2], a[3]); break;
+    case K_LS_COMMIT: hipLaunchKernelGGL(k_ls_commit, grid, block, lds, s, d, a[0]); break;
+    case K_SLACK: hipLaunchKernelGGL(k_slack, grid, block, lds, s, d, a[0]); break;
+    case L_XS_GATE: hipLaunchKernelGGL(k_xs_gate, grid, block, lds, s, d, a[0], a[1]); break;
+    case L_KEEP_GATE: hipLaunchKernelGGL(k_keep_gate, grid, block, lds, s, d, a[0]); break;
+    case L_FA_GATE: hipLaunchKernelGGL(k_fa_gate, grid, block, lds, s, d, a[0]); break;
+    case L_XCH_WAIT: hipLaunchKernelGGL(k_xch_wait, grid, block, lds, s, d, a[0]); break;
   }
-  return false;
 }
-
-// enqueue one stage (= one or more kernels) on a stream
-int enqueue_stage(tj_ctx* c, int stage, hipStream_t s = nullptr) {
-  if (!s) s = c->stream;
-  switch (stage) {
-    case TJ_STAGE_BEGIN: launch_kernel(c, K_BEGIN, s, Sched::Stage); break;
-    case TJ_STAGE_PLANES_OBS: launch_kernel(c, K_SEP_OBS, s, Sched::Stage); launch_kernel(c, K_OBS_SOLVE, s, Sched::Stage); if (c->d.mode == 0) launch_kernel(c, K_KEEP, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_COMPACT, s, Sched::Stage); break;
-    case TJ_STAGE_PLANES_SELF: launch_kernel(c, K_HULLINFO, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_ROWS, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_SOLVE, s, Sched::Stage); launch_kernel(c, K_KEEP, s, Sched::Stage); launch_kernel(c, K_SEP_SELF_COMPACT, s, Sched::Stage); break;
-    case TJ_STAGE_GRAD: launch_kernel(c, K_GRAD, s, Sched::Stage); break;
-    case TJ_STAGE_XSOLVE: launch_kernel(c, K_XSOLVE, s, Sched::Stage); launch_kernel(c, K_XSOLVE_C2, s, Sched::Stage); break;
-    case TJ_STAGE_CCD_PREP: launch_kernel(c, K_CCD_PREP, s, Sched::Stage); break;
-    case TJ_STAGE_CCD_OBS: launch_kernel(c, K_CCD_OBS, s, Sched::Stage); break;
-    case TJ_STAGE_CCD_SELF: launch_kernel(c, K_CCD_SELF_PAIRS, s, Sched::Stage); launch_kernel(c, K_CCD_SELF_SEQ, s, Sched::Stage); break;
-    case TJ_STAGE_LINESEARCH: launch_kernel(c, K_LINESEARCH, s, Sched::Stage); launch_kernel(c, K_LS_COUPLED, s, Sched::Stage); launch_kernel(c, K_LS_COMMIT, s, Sched::Stage); break;
-    case TJ_STAGE_SLACK: launch_kernel(c, K_SLACK, s, Sched::Stage); break;
-    case TJ_STAGE_END: hipLaunchKernelGGL(k_end, dim3(1), dim3(1), 0, s, c->d); break;
-    default: c->err = "unknown stage"; return TJ_ERR_INVALID;
-  }
+// sequence, then issue: one kernel id (returns whether it exists in this schedule) / a list of them
+bool enqueue_kernel(tj_ctx* c, Sched sched, int chain_pos, int kid) {
+  LaunchList l;
+  const bool exists = sequence_kernel(c->d, c->hp, c->ss, sched, chain_pos, kid, l);
+  for (int i = 0; i < l.n; i++) issue(c, l.v[i]);
+  return exists;
+}
+int enqueue_list(tj_ctx* c, Sched sched, int chain_pos, const KernelList& list) {
+  LaunchList l;
+  sequence_list(c->d, c->hp, c->ss, sched, chain_pos, list, l);
+  for (int i = 0; i < l.n; i++) issue(c, l.v[i]);
   HIPCHK(c, hipGetLastError());
   return TJ_OK;
+}
+
+// enqueue one stage (= one or more kernels)
+int enqueue_stage(tj_ctx* c, int stage) {
+  if (stage == TJ_STAGE_END) { hipLaunchKernelGGL(k_end, dim3(1), dim3(1), 0, c->stream, c->d); HIPCHK(c, hipGetLastError()); return TJ_OK; }
+  if (stage < 0 || stage > TJ_STAGE_END) { c->err = "unknown stage"; return TJ_ERR_INVALID; }
+  return enqueue_list(c, Sched::Stage, 0, kStageKernels[stage]);
 }
 
 // One iteration of the single-GPU schedule (Sched::Chain): a LINEAR chain on one stream / hardware queue
@@ -386,11 +277,14 @@ int enqueue_stage(tj_ctx* c, int stage, hipStream_t s = nullptr) {
 // same chain measured 4 us slower per iteration.
 // (k0, k1: only kernels [k0, k1) of the stream order -- the lockstep enqueue of ranks that share a device, tj_group.h)
 int enqueue_iteration(tj_ctx* c, int chain_pos = 0, int k0 = 0, int k1 = K_COUNT) {
-  for (int k = k0; k < k1; k++) launch_kernel(c, k, c->stream, Sched::Chain, chain_pos);
+  LaunchList l;
+  for (int k = k0; k < k1; k++) sequence_kernel(c->d, c->hp, c->ss, Sched::Chain, chain_pos, k, l);
+  for (int i = 0; i < l.n; i++) issue(c, l.v[i]);
   HIPCHK(c, hipGetLastError());
   c->maybe_deferred = true;
   return TJ_OK;
 }
+
 
 int ensure_hull_cache(tj_ctx* c);
 
@@ -427,14 +321,14 @@ int flush_deferred(tj_ctx* c) {
 // xs_go / keep_go and their counters go on counting (nothing is in flight: they still match); the words in front of xs_go and fa_sync restart (begin_body zeroes keep_sync's counters).
 int restart_pairings(tj_ctx* c, bool keep_go) {
   HIPCHK(c, hipMemsetAsync(c->d.xs_sync, 0, (keep_go ? (size_t)(c->d.xs_go() - c->d.xs_sync) : Dev::xs_sync_ints(c->d.U)) * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d.fa_sync, 0, Dev::fa_sync_ints(c->d.U) * sizeof(int), c->stream)); c->xq.fa_seq = 0; c->xq.fa_armed = c->xq.fa_mid_now = false;
-  if (!keep_go) { HIPCHK(c, hipMemsetAsync(c->d.keep_sync, 0, Dev::keep_sync_ints() * sizeof(int), c->stream)); c->xq.xs_seq = c->xq.xs_seq_gated = c->xq.keep_seq = 0; }
+  HIPCHK(c, hipMemsetAsync(c->d.fa_sync, 0, Dev::fa_sync_ints(c->d.U) * sizeof(int), c->stream)); c->ss.fa_seq = 0; c->ss.fa_armed = c->ss.fa_mid_now = false;
+  if (!keep_go) { HIPCHK(c, hipMemsetAsync(c->d.keep_sync, 0, Dev::keep_sync_ints() * sizeof(int), c->stream)); c->ss.xs_seq = c->ss.xs_seq_gated = c->ss.keep_seq = 0; }
   return TJ_OK;
 }
 // Checkpoint take: the host half now, the device half in the next k_begin (in_begin: the batch starts with one -- no begin folded) or in a k_snapshot launch now.
 int checkpoint_take(tj_ctx* c, bool in_begin) {
   Checkpoint& k = c->ck;
-  k.in_begin = in_begin; k.begin_folded = c->begin_folded; k.maybe_deferred = c->maybe_deferred; k.lsc_base = c->lsc_base;
+  c->ss.ck_in_begin = in_begin; k.begin_folded = c->begin_folded; k.maybe_deferred = c->maybe_deferred; k.lsc_base = c->ss.lsc_base;
   if (!in_begin) { hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(k.n, 1)), dim3(256), 0, c->stream, k.tab, k.n, 0, c->d.ctl, k.ctl); HIPCHK(c, hipGetLastError()); }
   return TJ_OK;
 }
@@ -443,10 +337,10 @@ int checkpoint_take(tj_ctx* c, bool in_begin) {
 int checkpoint_restore(tj_ctx* c) {
   const Checkpoint& k = c->ck;
   hipLaunchKernelGGL(k_snapshot, dim3(64, std::max(k.n, 1)), dim3(256), 0, c->stream, k.tab, k.n, 1, c->d.ctl, k.ctl); HIPCHK(c, hipGetLastError());
-  c->begin_folded = k.begin_folded; c->maybe_deferred = k.maybe_deferred; c->lsc_base = k.lsc_base; c->hull_valid = c->ccd_valid = c->xf_used[0] = c->xf_used[1] = false;
+  c->begin_folded = k.begin_folded; c->maybe_deferred = k.maybe_deferred; c->ss.lsc_base = k.lsc_base; c->hull_valid = c->ss.ccd_valid = c->ss.xf_used[0] = c->ss.xf_used[1] = false;
   return c->begin_folded ? flush_deferred(c) : TJ_OK;
 }
-void checkpoint_drop(tj_ctx* c) { c->ck.in_begin = false; }
+void checkpoint_drop(tj_ctx* c) { c->ss.ck_in_begin = 0; }
 
 // Self-healing (tj_ctx): the batch enqueued since the checkpoint is through.  No incident: drop the checkpoint.  ERR_XS_TIMEOUT: latch one queue (release the queue
 // claim, clear the two-queue flags, restart the pairings), restore the checkpoint, enqueue the same iterations again and drain.
@@ -458,7 +352,7 @@ int heal_check(tj_ctx* c, int err_known) {
   struct Busy { tj_ctx* c; ~Busy() { c->heal_busy = false; } } busy{c}; c->heal_busy = true;   // (reset on every exit)
   c->async_fallbacks++;
   release_queues(c);   // (the budget is free for another context)
-  c->xq.xs_two_queues = c->xq.keep_two_queues = false; c->xq.xs_fault = 0;   // (the tickets / flags of the asynchronous solve work on one queue as well: TJ_XS_ONE_QUEUE's schedule)
+  c->ss.xs_two_queues = c->ss.keep_two_queues = false; c->ss.xs_fault = 0;   // (the tickets / flags of the asynchronous solve work on one queue as well: TJ_XS_ONE_QUEUE's schedule)
   int r = restart_pairings(c, false);
   if (r || (r = checkpoint_restore(c))) return r;
   checkpoint_drop(c);   // (the run enqueued again stays on one queue: nothing of it is healed)
@@ -468,31 +362,12 @@ int heal_check(tj_ctx* c, int err_known) {
   return TJ_OK;
 }
 
-// Phase `which` of a sharded iteration (Sched::Phase), split at the all-gathers.  The phases are linear chains on the context's stream as well and reuse the union kernels where the
-// stages they join fall into the same phase (k_mid, k_ccd); the slack/dual update is the deferred one inside k_mid.
-//   phase 0: begin (stop test)                                                            -> all-gather control points
-//   phase 1: hull cache (ALL robots), k_front {obstacle query | pair rows}, k_mid, compaction, gradient, Newton solve -> all-gather directions
-//   phase 2: swept-hull cache (ALL robots), k_ccd, sequential pair clamp + gnorm, line search
+// Phase `which` of a sharded iteration (Sched::Phase), split at the all-gathers (kPhaseKernels, host_launch.h).  The phases are linear chains on the context's stream as well and
+// reuse the union kernels where the stages they join fall into the same phase (k_mid, k_ccd); the slack/dual update is the deferred one inside k_mid.
 int enqueue_body(tj_ctx* c, int which, int chain_pos = 0) {
-  hipStream_t m = c->stream;
-  // decoupled / single: 3 phases.  coupled ("decouple":0): 6 phases -- the arrowhead system, the shared CCD step and the
-  // Armijo test on the summed energy each need something from every robot (tj_iterate_phase, trajadmm.h)
-  static const int ph0[] = {K_BEGIN}, ph1[] = {K_HULLINFO, K_FRONT, K_MID, K_KEEP, K_SEP_SELF_COMPACT, K_GRAD, K_XSOLVE},
-                   ph2[] = {K_CCD_PREP, K_CCD, K_CCD_SELF_SEQ, K_LINESEARCH},
-                   pc2[] = {K_XSOLVE_C2}, pc3[] = {K_CCD_PREP, K_CCD, K_CCD_SELF_SEQ}, pc4[] = {K_LS_COUPLED}, pc5[] = {K_LS_COMMIT};
   const bool cpl = c->d.mode == TJ_MODE_MULTI_COUPLED;
-  const int* list = nullptr; int n = 0;
-  switch (which) {
-    case 0: list = ph0; n = 1; break;
-    case 1: list = ph1; n = 7; break;
-    case 2: if (cpl) { list = pc2; n = 1; } else { list = ph2; n = 4; } break;
-    case 3: list = pc3; n = 3; break;
-    case 4: list = pc4; n = 1; break;
-    case 5: list = pc5; n = 1; break;
-  }
   if (which == 1 && c->d.fuse) { int hr = ensure_hull_cache(c); if (hr) return hr; }   // fused phases: k_linesearch keeps the owned robots' hull cache; after a host write it is rebuilt once
-  for (int i = 0; i < n; i++) launch_kernel(c, list[i], m, Sched::Phase, chain_pos);
-  HIPCHK(c, hipGetLastError());
+  if (int r = enqueue_list(c, Sched::Phase, chain_pos, kPhaseKernels[cpl ? 1 : 0][which])) return r;
   // this iteration's slack/dual update is owed to the next k_mid (or the flush) -- in a followed coupled search only once the search is over (tj_coupled_search_pending says so):
   // a flush between two tables of candidates would pay the update on the uncommitted control net
   if (which == (cpl ? 5 : 2) && !(cpl && c->d.lsc_follow && c->d.u1 - c->d.u0 != c->d.U)) c->maybe_deferred = true;
@@ -532,9 +407,9 @@ int check_device_errors(tj_ctx* c, Ctl* out = nullptr) {
 // control points were set from the host the cache is rebuilt once here.
 int ensure_hull_cache(tj_ctx* c) {
   if (!c->d.fuse || c->hull_valid) return TJ_OK;
-  launch_kernel(c, K_HULLINFO, c->stream, Sched::Stage);
+  enqueue_kernel(c, Sched::Stage, 0, K_HULLINFO);
   HIPCHK(c, hipGetLastError());
-  c->hull_valid = true; c->xq.hull_from_units = false;
+  c->hull_valid = true; c->ss.hull_from_units = false;
   return TJ_OK;
 }
 
@@ -750,7 +625,7 @@ int tj_create(const tj_params* p, tj_ctx** out) {
   };
   if (!pl.err) { const bool s2 = stream_for(pl.d.xs_async, c->xq.stream2), s3 = stream_for(pl.d.keep_async, c->xq.stream3); plan_downgrade(pl, s2, s3); }
   c->d = pl.d; c->hp = pl.h;
-  c->xq.xs_two_queues = pl.h.xs_two_queues; c->xq.keep_two_queues = pl.h.keep_two_queues; c->xq.xs_fault = pl.h.xs_fault;
+  c->ss.xs_two_queues = pl.h.xs_two_queues; c->ss.keep_two_queues = pl.h.keep_two_queues; c->ss.xs_fault = pl.h.xs_fault;
   if (pl.err) { c->err = pl.msg; return pl.err; }
   if ((r = set_lds_attributes(c)) || (r = upload_tables(c)) || (r = allocate_arrays(c))) return r;
   return TJ_OK;
@@ -949,7 +824,7 @@ int tj_init_state(tj_ctx* c, const double* wp, double pt0) {
   memset(&h, 0, sizeof(h));
   h.gnorm = 1.0;  // Main/multiPathPlanning3D.cpp:594
   if ((r = upload(c, d.ctl, &h, sizeof(h)))) return r;
-  c->hull_valid = false; c->ccd_valid = false;
+  c->hull_valid = false; c->ss.ccd_valid = false;
   HIPCHK(c, hipMemsetAsync(d.xdir, 0, (size_t)U * d.xs * 8, c->stream));
   HIPCHK(c, hipMemsetAsync(d.ocount, 0, (size_t)U * d.S * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(d.scount, 0, (size_t)U * d.S * 4, c->stream));
@@ -1007,7 +882,7 @@ int tj_set_state(tj_ctx* c, int u, const double* spline, const double* p_slack, 
   if (t_slack && (r = upload(c, d.t_slack + (size_t)u * d.P, t_slack, d.P * 8))) return r;
   if (t_lambda && (r = upload(c, d.t_lambda + (size_t)u * d.P, t_lambda, d.P * 8))) return r;
   if ((r = upload(c, d.piece_time + u, &piece_time, 8))) return r;
-  c->hull_valid = false; c->ccd_valid = false;
+  c->hull_valid = false; c->ss.ccd_valid = false;
   c->have_state = true;
   return TJ_OK;
 }
@@ -1015,7 +890,7 @@ int tj_set_state(tj_ctx* c, int u, const double* spline, const double* p_slack, 
 namespace {
 // the parts of tj_iterate_async (also used by the lockstep enqueue of the ranks of a group that share a device, tj_group.h)
 int iterate_async_prologue(tj_ctx* c, int n_iters) {
-  if (c->hp.heal && n_iters > 0 && (c->xq.xs_two_queues || c->xq.keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
+  if (c->hp.heal && n_iters > 0 && (c->ss.xs_two_queues || c->ss.keep_two_queues)) {   // self-healing: the state this batch starts from (one launch), unless iterations the host has not looked at yet are already outstanding
     if (c->snap_iters == 0 && !c->heal_busy) { int r = checkpoint_take(c, !c->begin_folded); if (r) return r; }   // (no begin folded: the batch's first launch is k_begin)
     if (!c->heal_busy) c->snap_iters += n_iters;
   }
@@ -1023,15 +898,10 @@ int iterate_async_prologue(tj_ctx* c, int n_iters) {
   return TJ_OK;
 }
 
-// inside a batch the begin work of iteration i+1 rides on iteration i's k_linesearch (not in coupled mode, whose line search
-// is several kernels -- except where the whole search is ONE launch whose last block commits: lsc_wide, one context)
-bool iterate_async_chain(const tj_ctx* c) {
-  return c->d.mode != TJ_MODE_MULTI_COUPLED || (c->hp.lsc_wide && c->d.u1 - c->d.u0 == c->d.U);
-}
-
-// chain position of iteration i of a batch of n (clears begin_folded: the fold it reports is consumed here)
-int iterate_async_pos(tj_ctx* c, bool chain, int i, int n) {
-  const int pos = chain ? (((i > 0 || c->begin_folded) ? 1 : 0) | (i + 1 < n ? 2 : 0)) : 0;
+// chain position of iteration i of a batch of n: inside a batch the begin work of iteration i+1 rides on iteration i's line search (chain_position, host_launch.h).
+// Clears begin_folded: the fold it reports is consumed here
+int iterate_async_pos(tj_ctx* c, int i, int n) {
+  const int pos = chain_position(c->d, c->hp, true, i > 0 || c->begin_folded, i + 1 < n);
   c->begin_folded = false;
   return pos;
 }
@@ -1041,9 +911,8 @@ int tj_iterate_async(tj_ctx* c, int n_iters) {
   if (!c || n_iters < 0) return TJ_ERR_INVALID;
   if (!ready(c)) return TJ_ERR_INVALID;
   { int r = iterate_async_prologue(c, n_iters); if (r) return r; }
-  const bool chain = iterate_async_chain(c);
   for (int i = 0; i < n_iters; i++)
-    if (int r = enqueue_iteration(c, iterate_async_pos(c, chain, i, n_iters))) return r;
+    if (int r = enqueue_iteration(c, iterate_async_pos(c, i, n_iters))) return r;
   return TJ_OK;
 }
 
@@ -1072,18 +941,18 @@ int tj_profile_kernels(tj_ctx* c, int n_iters, double* ms, int* launches) {
   std::vector<hipEvent_t> ev((size_t)n_iters * (K_COUNT + 1));
   for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
   std::vector<int> ran(K_COUNT, 0);
-  c->xq.xs_same_queue_now = true;   // per-kernel events on one queue: the asynchronous solve follows k_grad there (its own time is then what the events show)
+  c->ss.xs_same_queue_now = true;   // per-kernel events on one queue: the asynchronous solve follows k_grad there (its own time is then what the events show)
   for (int it = 0; it < n_iters; it++) {
     hipEvent_t* e = &ev[(size_t)it * (K_COUNT + 1)];
     HIPCHK(c, hipEventRecord(e[0], c->stream));
-    const int pos = (c->d.mode != TJ_MODE_MULTI_COUPLED) ? ((it > 0 ? 1 : 0) | (it + 1 < n_iters ? 2 : 0)) : 0;
+    const int pos = chain_position(c->d, c->hp, false, it > 0, it + 1 < n_iters);   // (the flush above has taken a folded begin back; the one-launch coupled search is profiled with a k_begin per iteration)
     for (int k = 0; k < K_COUNT; k++) {
-      if (launch_kernel(c, k, c->stream, Sched::Chain, pos)) ran[k]++;
+      if (enqueue_kernel(c, Sched::Chain, pos, k)) ran[k]++;
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipEventRecord(e[k + 1], c->stream));
     }
   }
-  c->xq.xs_same_queue_now = false;
+  c->ss.xs_same_queue_now = false;
   if (n_iters > 0) c->maybe_deferred = true;  // the last iteration's slack/dual update is still owed (paid by the flush below)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < K_COUNT; k++) ms[k] = 0;
@@ -1136,12 +1005,10 @@ int tj_iterate_phase_chained(tj_ctx* c, int phase, int more) {
   // Decoupled / single-UAV schedules fold the next iteration's begin into the last phase's k_linesearch when the caller says one follows
   // (more != 0): that iteration's phase 0 then launches nothing.  A begin that was folded for an iteration the caller never enqueues is
   // taken back by the next flush (tj_sync, any state access).
-  int pos = 0;
-  if (c->d.mode != TJ_MODE_MULTI_COUPLED && c->d.fuse) {
-    if (phase == 0) { pos = c->begin_folded ? 1 : 0; c->begin_folded = false; }
-    if (phase == 2 && more) { pos = 2; c->begin_folded = true; }
-  }
-  if (phase == 0) c->lsc_base = 0;
+  int pos = 0;   // (coupled mode commits in a phase of its own: no fold, chain_position's wide_coupled = false)
+  if (phase == 0) { pos = chain_position(c->d, c->hp, false, c->begin_folded, false); if (c->d.mode != TJ_MODE_MULTI_COUPLED) c->begin_folded = false; }
+  if (phase == 2 && more) { pos = chain_position(c->d, c->hp, false, false, true); if (pos) c->begin_folded = true; }
+  if (phase == 0) c->ss.lsc_base = 0;
   return enqueue_body(c, phase, pos);
 }
 
@@ -1152,7 +1019,7 @@ int tj_iterate_phase_chained(tj_ctx* c, int phase, int more) {
 int tj_set_coupled_follow(tj_ctx* c, int on) {
   if (!c) return TJ_ERR_INVALID;
   if (c->d.mode != TJ_MODE_MULTI_COUPLED) { c->err = "tj_set_coupled_follow: coupled mode only"; return TJ_ERR_INVALID; }
-  c->d.lsc_follow = on ? 1 : 0; c->lsc_base = 0;
+  c->d.lsc_follow = on ? 1 : 0; c->ss.lsc_base = 0;
   return TJ_OK;
 }
 int tj_coupled_search_pending(tj_ctx* c, int* pending) {
@@ -1163,7 +1030,7 @@ int tj_coupled_search_pending(tj_ctx* c, int* pending) {
   int p = 0;
   HIPCHK(c, hipMemcpy(&p, &c->d.ctl->lsc_pending, sizeof(int), hipMemcpyDeviceToHost));
   *pending = p ? 1 : 0;
-  c->lsc_base = p ? c->lsc_base + LSC_ROUNDS : 0;
+  c->ss.lsc_base = p ? c->ss.lsc_base + LSC_ROUNDS : 0;
   if (!p) c->maybe_deferred = true;   // the step is committed: the iteration's slack/dual update is owed from here on
   return TJ_OK;
 }
@@ -1274,7 +1141,7 @@ int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_directi
   std::vector<double> rec(d.xs, 0.0);
   memcpy(rec.data(), direction, 3 * d.T * 8);
   rec[3 * d.T] = t_direction; rec[3 * d.T + 1] = wolfe; rec[3 * d.T + 2] = gn;
-  c->ccd_valid = false;   // the swept-hull cache no longer matches: the next chained CCD stage rebuilds it (k_ccd_prep)
+  c->ss.ccd_valid = false;   // the swept-hull cache no longer matches: the next chained CCD stage rebuilds it (k_ccd_prep)
   return upload(c, d.xdir + (size_t)u * d.xs, rec.data(), d.xs * 8);
 }
 
@@ -2233,6 +2100,39 @@ int tj_kat_plan(const tj_ctx* c, const tj_params* p, const int* facts, int* out,
   return plan_record(pl, f, out, cap);
 }
 
+// the launch sequence as flat records of ints (host_launch.h: sequence_kernel), call by call: a context's own Dev, plan and state (its state is copied to `state`
+// first, but for xs_same_queue_now, and not advanced), or -- c == nullptr, no device needed -- the planner's Dev and plan on the caller's parameters and facts, from the start state in `state`.
+// calls: n_calls x (kid, sched, chain_pos).  out, per call: exists, number of records, the SchedState after it, the Launch records.  Returns the ints written
+// (negated: `cap` is too small; 0: bad arguments or a shape the planner refuses)
+int tj_kat_launches(const tj_ctx* c, const tj_params* p, const int* facts, int lsc_follow, int* state, const int* calls, int n_calls, int* out, int cap) {
+  if (!out || !state || n_calls < 0 || (n_calls > 0 && !calls) || (!c && (!p || !facts))) return 0;
+  Dev d; HostPlan h; SchedState st;
+  if (c) {   // (xs_same_queue_now comes FROM state[]: tj_profile_kernels sets it around its run only, so the caller says which run it asks about)
+    SchedState in; memcpy(&in, state, sizeof(in));
+    d = c->d; h = c->hp; st = c->ss; st.xs_same_queue_now = in.xs_same_queue_now ? 1 : 0; memcpy(state, &st, sizeof(st));
+  }
+  else {
+    PlanFacts f; memcpy(&f, facts, sizeof(f));
+    if (plan_check_params(p)) return 0;
+    const Plan pl = plan_context(p, f, tune);
+    if (pl.err) return 0;
+    d = pl.d; d.prim = f.prim; d.N = f.n_obs; d.lsc_follow = lsc_follow ? 1 : 0; h = pl.h; memcpy(&st, state, sizeof(st));
+  }
+  int n = 0;
+  for (int i = 0; i < n_calls; i++) {
+    const int kid = calls[3 * i], sched = calls[3 * i + 1];
+    if (kid < 0 || kid >= K_COUNT || sched < 0 || sched > 2) return 0;
+    LaunchList l;
+    const bool exists = sequence_kernel(d, h, st, (Sched)sched, calls[3 * i + 2], kid, l);
+    const int need = 2 + SCHED_STATE_INTS + l.n * LAUNCH_INTS;
+    if (n + need > cap) return -(n + need);
+    out[n] = exists ? 1 : 0; out[n + 1] = l.n;
+    memcpy(out + n + 2, &st, sizeof(st)); memcpy(out + n + 2 + SCHED_STATE_INTS, l.v, (size_t)l.n * sizeof(Launch));
+    n += need;
+  }
+  return n;
+}
+
 int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out) {
   if (!c || nmat < 0 || n < 1 || n > 64 || !mats || !out) return TJ_ERR_INVALID;
   DevBuf dm, dout; int r;
@@ -2410,7 +2310,7 @@ int tj_xch_enable(tj_ctx* c, int on, int wait_mode) {
   Dev& d = c->d;
   if (on && (!d.xp || !c->xch_block)) { c->err = "tj_xch_enable: tj_xch_attach has not been called"; return TJ_ERR_INVALID; }
   QUIESCE(c);
-  d.xch = on ? 1 : 0; d.xch_poll = (on && wait_mode == 1) ? 1 : 0; c->xch_wait_kernel = on && wait_mode == 0;
+  d.xch = on ? 1 : 0; d.xch_poll = (on && wait_mode == 1) ? 1 : 0; c->ss.xch_wait_kernel = on && wait_mode == 0;
   return TJ_OK;
 }
 

@@ -258,13 +258,11 @@ int group_rank_loop(tj_group* g, int r, int n_iters, bool careful = false, long*
 // waits for the direction records, k_linesearch pushes the control points of the next iteration) -- every wait stands behind its producers in whatever queue they share.
 // Same kernels and chain positions per rank as tj_iterate_async; only the host's interleaving differs.
 int group_direct_lockstep(tj_group* g, int n_iters, std::vector<int>& rc) {
-  std::vector<bool> chain(g->n);
   for (int r = 0; r < g->n; r++) {
     tj_ctx* c = g->ctx[r];
     if (hipSetDevice(g->dev[r]) != hipSuccess) { c->err = "hipSetDevice failed"; return rc[r] = TJ_ERR_DEVICE; }
     if (!ready(c)) return rc[r] = TJ_ERR_INVALID;
     if ((rc[r] = iterate_async_prologue(c, n_iters))) return rc[r];
-    chain[r] = iterate_async_chain(c);
   }
   for (int i = 0; i < n_iters; i++) {
     std::vector<int> pos(g->n);
@@ -273,7 +271,7 @@ int group_direct_lockstep(tj_group* g, int n_iters, std::vector<int>& rc) {
       for (int r = 0; r < g->n; r++) {
         tj_ctx* c = g->ctx[r];
         if (hipSetDevice(g->dev[r]) != hipSuccess) { c->err = "hipSetDevice failed"; return rc[r] = TJ_ERR_DEVICE; }
-        if (part == 0) pos[r] = iterate_async_pos(c, chain[r], i, n_iters);
+        if (part == 0) pos[r] = iterate_async_pos(c, i, n_iters);
         if ((rc[r] = enqueue_iteration(c, pos[r], cut[part], cut[part + 1]))) return rc[r];
       }
   }

@@ -687,6 +687,113 @@ typedef struct tj_obstacle_robot {
 } tj_obstacle_robot;
 int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);
 int tj_obstacle_record_size(void);   /* sizeof(tj_obstacle_robot) */
+/* ---- tj_obstacle_windows: FROM WHEN TO WHEN is the flown curve of every robot within `dist` of the obstacle set, as certified time intervals
+ * (csrc/kernels_obstacle_windows.h; read-only like tj_obstacle_approach).  tj_audit gives a hull clearance without a time, tj_obstacle_approach one converged
+ * minimum per robot (one time, one primitive), tj_flight_profile samples that certify nothing between them.  A state that is not yet collision-free -- an init
+ * file, tj_plan_init's output, a state from tj_set_state, a run stopped early -- is in conflict with the obstacles over intervals, often several per robot: at
+ * dist = offset these are the stretches of each flight to re-plan, at a sensor or safety radius the certified stretches in which the vehicle flies near
+ * structure.  The obstacle-side counterpart of tj_proximity_windows: the union of ALL primitives is classified against the level `dist`.  Works in all three
+ * modes (single-UAV included), for clouds and meshes.  For every OWNED robot u:
+ *   window   W = (segment tr, [sa, sb] in [0, 1] of the segment's local parameter), dyadic (halving at 0.5 * (sa + sb) is exact; with max_depth <= 40 no window
+ *            is ever unsplittable).  The real time of parameter s of segment tr is ((tr + s) / res) * piece_time[u] -- tj_obstacle_approach's expression, used
+ *            wherever a time is formed.  The position on the flight g = tr + s is exact in a double (9 + 40 bits).
+ *   net      b_0..b_5 = the segment's RAW hull restricted to [sa, sb] (bez_restrict), never a parent's net; [0, 1] returns the raw hull bit for bit.
+ *   C(W)     the candidates: the primitives whose box is within dist of the box of the net on every axis, touching counts (the walk's leaf predicate in
+ *            fp64; the 49-axis cull is not used).  A primitive within dist of any point of the curve on W is in C(W), so a primitive
+ *            outside it is farther than dist from the curve on W.
+ *   per p    of C(W): lo_p = the GJK's |v| (hull = body 1, primitive = body 2) where v separates the two (tj_obstacle_approach's certificate), 0 without it;
+ *            ub_p = the largest distance of b_0..b_5 from p (the curve lies in the net's hull and the distance to a convex primitive is convex, so the
+ *            distance to p on W is never larger); h0_p, h5_p = the distances of b_0 and b_5 from p, attained at sa and sb.  A point's distance from a cloud
+ *            point is norm3(b - p), from a triangle |gjk({b}, triangle)| (tj_obstacle_approach's hi: an upper bound of the distance, so ub_p stays one).
+ *   class    OUT: every candidate has lo_p > dist (an empty C(W) is OUT).  Else IN: some candidate has ub_p <= dist.  Else MIXED.
+ *   h0, h5   of W: the smallest h0_p (h5_p) over C(W) with its primitive, ordered by (value, caller's index); +infinity and -1 for an empty set.  h0 <= dist
+ *            if and only if some primitive of the whole set is within dist of the curve at sa; then h0 is the nearest primitive's distance.
+ *   search   per (robot, segment), independent of every other segment.  Seed: the window [0, 1]; OUT: the segment contributes nothing, IN: it is a leaf,
+ *            MIXED: it is the live set.  Round d = 1, 2, ..: the live windows in ascending sa; one whose time width ((sb - sa) / res) * piece_time[u] <= tol
+ *            becomes an EDGE leaf with its h0 and h5; every other is halved and both children are evaluated, left then right: OUT children are dropped, IN
+ *            children appended to the leaves with h0 and h5, MIXED children form the next live set.
+ *   stop     the live set is empty | d == max_depth | the live set or the leaf list after a round holds more than max_windows (TRUNCATED: the lists are
+ *            those of the last completed round, `windows` counts the overflowing round's work too).  Whatever is live at the end joins the leaves as EDGE
+ *            leaves (so a segment has at most 2 * max_windows leaves).
+ *   merge    per robot the leaves of its segments in (segment, sa) order: distinct and disjoint.  Two consecutive leaves are adjacent exactly when
+ *            prev.tr + prev.sb == next.tr + next.sa on doubles (a chain crosses a segment boundary).  A row is a maximal chain of adjacent leaves.
+ *   sure     every time of an IN leaf; of an EDGE leaf sa if h0 <= dist and sb if h5 <= dist: times at which the curve IS within dist of a primitive.
+ *   row      t_first_lo = the chain's start, t_last_hi = its end; t_first_hi = the earliest sure time, t_last_lo = the latest (both -1.0 without one);
+ *            within_lo = the sum of the IN leaves' time widths ((sb - sa) / res) * piece_time[u], left to right; closest, closest_time, index = the
+ *            smallest attained end sample (h0 at sa, h5 at sb) of the chain in the order (value, time, index), index = the caller's index of its primitive
+ *            (-1, closest = +infinity, closest_time = -1.0 where no end sample has a candidate) -- not converged: tj_obstacle_approach converges it;
+ *            segment_first, segment_last = the segments of the chain's ends; leaves = the chain's length; depth = the most rounds completed by any segment
+ *            with a leaf in the chain; windows = the ROBOT's work, seeds evaluated + 2 per halved window over all its segments, repeated on each of its rows.
+ *   flags    CERTAIN (a sure time exists) or UNCERTAIN, AT_START (the chain starts at g == 0), AT_END (it ends at g == S), RESOLVED (CERTAIN, and
+ *            t_first_hi - t_first_lo <= tol or AT_START, and t_last_hi - t_last_lo <= tol or AT_END), TRUNCATED (a segment of the chain was truncated).
+ * Every field is a function of the state alone.  Outside every row of robot u the flown curve is certified farther than dist from every primitive.  Rows are
+ * sorted by (robot, t_first_lo); no order of evaluation or of any append is visible.
+ * dist <= 0: offset; +infinity is valid (every primitive is a candidate of every window: for small sets, tj_audit's remark).  tol < 0:
+ * TJ_OBSWIN_TOL_FRACTION * dist / vel_limit -- tj_proximity_windows' design condition, stated as such: the time a robot at the speed limit needs for 1 % of
+ * dist (offset in place of an infinite dist); 0 is valid.  max_depth < 0: TJ_OBSWIN_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0:
+ * TJ_OBSWIN_FRONTIER; above TJ_OBSWIN_MAX_WINDOWS (it bounds the in-kernel rank sort) TJ_ERR_INVALID.  *n = the rows.  *n > cap: TJ_ERR_CAPACITY with the
+ * exact *n, the first `cap` rows in order have been written.  cap == 0 with rows == NULL is the count-only call (two launches).  n == NULL, cap < 0, rows ==
+ * NULL with cap > 0, NaN dist or tol, a call before tj_init_state: TJ_ERR_INVALID, the outputs untouched (precedence: null, NaN, limits, no state).  No
+ * obstacles (tj_set_cloud with n = 0 included): 0 rows and TJ_OK.  A walk frontier beyond its capacity (more than FRONT_CAP boxes of 8 primitives within dist of one
+ * window's box: lower dist): TJ_ERR_CAPACITY, never fewer rows; no count is known then, *n is left UNTOUCHED and nothing is written -- that, *n <= cap or unchanged,
+ * tells it from the rows' TJ_ERR_CAPACITY, which always comes with *n > cap; tj_last_error names the cause.  A plain SHARDED
+ * context (world > 1) answers for its owned robots, as tj_obstacle_approach does: nothing of another robot is read.  tj_group_obstacle_windows returns the
+ * owners' rows one after the other, bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, and is a function of owned x S x max_windows (S = piece_num * res segments):
+ *   owned * S * (4 * max_windows * 48 + 16) + owned * 8 + cap * 88 bytes
+ *   (per segment the two live lists, which hold the sorted leaves afterwards, and 2 * max_windows leaves, 48 bytes a window; its four counters; the robots'
+ *   row counts and work; the rows).  A call whose figure exceeds TJ_OBSWIN_MAX_BYTES is refused up front with TJ_ERR_INVALID: lower max_windows or cap.
+ * At most THREE launches whatever the fleet's size, the number of primitives and the depth (two for the count-only call); no host loop over robots,
+ * segments or rounds.  Changes no solver state, statistics or launch count.
+ * STATED LIMITS.  (1) A certified lo_p is the GJK's |v|, up to 1e-10 |v| relative above the hull's distance (the siblings' limit): it applies to the OUT
+ * decision.  (2) IN needs ONE primitive that covers the whole window; a window covered only by several primitives together is halved until one does, or ends
+ * as an EDGE leaf.  (3) Gaps shorter than a leaf are not resolved; UNCERTAIN rows are grazes at the resolution tol.
+ * The defaults are measured (tests/obstacle_windows_ref.py default_tolerance, the restatement, on the CPU): the default tol, max_depth = 40, the lists capped
+ * at TJ_OBSWIN_MAX_WINDOWS only, on the final states of tests/golden/e2e_scn_a.npz, e2e_scn_b.npz, e2e_scn_c3.npz, e2e_scn_b_coupled.npz and on the same
+ * runs' iteration-0 states (_init), with their scenes' clouds cropped as obstacle_approach_ref.default_tolerance crops them, at dist = offset = 0.1 and
+ * dist = offset + 2 * margin (widest bracket: the larger of t_first_hi - t_first_lo and t_last_hi - t_last_lo over the CERTAIN rows):
+ *   state                    dist   rows   uncertain   truncated   largest live set   largest leaf list   largest depth   widest bracket
+ *   e2e_scn_a                0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_a                0.3    2      0           0           1                  6                   8               7.63e-04
+ *   e2e_scn_a_init           0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_a_init           0.3    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b                0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b                0.3    48     0           0           3                  17                  9               1.12e-03
+ *   e2e_scn_b_init           0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b_init           0.3    52     0           0           4                  25                  12              1.22e-03
+ *   e2e_scn_c3               0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_c3               0.3    19     0           0           4                  16                  9               1.12e-03
+ *   e2e_scn_c3_init          0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_c3_init          0.3    7      0           0           2                  13                  12              1.22e-03
+ *   e2e_scn_b_coupled        0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b_coupled        0.3    47     0           0           3                  16                  9               1.12e-03
+ *   e2e_scn_b_coupled_init   0.1    0      0           0           0                  0                   0               0.00e+00
+ *   e2e_scn_b_coupled_init   0.3    52     0           0           4                  25                  12              1.22e-03
+ * A level set is crossed at isolated times, so the live set of a segment stays at a few windows; what grows is its leaf list, by the IN windows of a
+ * stay within dist that is resolved to tol at both ends.  The iteration-0 states of these scenes are clear of their clouds at offset, as their end states are.
+ * TJ_OBSWIN_FRONTIER is the next power of two >= 4 x the larger of the two list maxima (25), and at least 64. */
+#define TJ_OBSWIN_CERTAIN   1    /* a sure time exists: the curve IS within dist of a primitive at t_first_hi and at t_last_lo */
+#define TJ_OBSWIN_UNCERTAIN 2    /* no sure time: t_first_hi == t_last_lo == -1.0, a graze at the resolution tol */
+#define TJ_OBSWIN_AT_START  4    /* the chain starts at time 0: nothing lies before it */
+#define TJ_OBSWIN_AT_END    8    /* the chain ends at the end of the robot's flight */
+#define TJ_OBSWIN_RESOLVED  16   /* CERTAIN and both brackets are at most tol wide (a side closed by AT_START / AT_END counts as resolved) */
+#define TJ_OBSWIN_TRUNCATED 32   /* a segment of the chain outgrew max_windows: its leaves of the last completed round are returned */
+#define TJ_OBSWIN_MAX_DEPTH 40
+#define TJ_OBSWIN_FRONTIER  128
+#define TJ_OBSWIN_MAX_WINDOWS 1024
+#define TJ_OBSWIN_MAX_BYTES (1ll << 31)
+#define TJ_OBSWIN_TOL_FRACTION 0.01
+typedef struct tj_obswin_row {
+  double t_first_lo, t_first_hi;   /* the curve first comes within dist of the obstacles in [t_first_lo, t_first_hi] */
+  double t_last_lo,  t_last_hi;    /* ... and is last within dist in [t_last_lo, t_last_hi] */
+  double within_lo;                /* seconds CERTIFIED within dist inside the row (sum of the IN leaves) */
+  double closest, closest_time;    /* smallest attained end sample of the row and its time (not converged: tj_obstacle_approach converges it) */
+  int robot, index;                /* index: the primitive of `closest` (caller's index), -1 without one */
+  int segment_first, segment_last; /* the segments of the chain's ends */
+  int leaves, depth, flags, windows;
+} tj_obswin_row;
+int tj_obstacle_windows(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n);
+int tj_obswin_row_size(void);   /* sizeof(tj_obswin_row) */
 /* ---- tj_peak_dynamics: how fast every robot's FLOWN CURVE really gets -- peak speed, acceleration and jerk, converged, each with its flight time -- how long
  * its path is, and by how much its timetable could be compressed (csrc/kernels_peak_dynamics.h; read-only like tj_audit).  tj_audit's speed / accel are maxima
  * over the control vectors of each segment's derivative nets: what bound_energy constrains, but only an upper bound on what the vehicle does, without a time --
@@ -969,6 +1076,7 @@ int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth
 int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n);   /* tj_timing_margin of every pair (u, q > u) by u's owner, in the same way */
 int tj_group_proximity_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n);   /* tj_proximity_windows of every robot by its owner, the ranks' rows one after the other: (robot, partner, t_first_lo) order, bitwise one context's; every rank gets `cap` pair slots and the rows' remaining room */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
+int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n);   /* tj_obstacle_windows of every robot by its owner, from the owner's own state, the ranks' rows one after the other: (robot, t_first_lo) order, bitwise one context's */
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);   /* tj_peak_dynamics of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */

@@ -1,4 +1,4 @@
-"""The clock of the query timing scripts (audit_timing.py, closest_timing.py, obstacle_approach_timing.py): the 64-UAV SCN-C state after a number of iterations, and a
+"""The clock of the query timing scripts (audit_timing.py, closest_timing.py, obstacle_approach_timing.py, obstacle_windows_timing.py): the 64-UAV SCN-C state after a number of iterations, and a
 hipEvent pair on the context's stream around a whole call (memsets, kernels, copies).  Run the scripts from the repository root on the GPU."""
 import ctypes as C, importlib, os, sys
 import numpy as np

@@ -34,6 +34,7 @@ EXPORTS = [
     "tj_audit_timed", "tj_audit_timed_record_size", "tj_group_audit_timed",
     "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
     "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
+    "tj_obstacle_windows", "tj_obswin_row_size", "tj_group_obstacle_windows",
     "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
     "tj_path_crossings", "tj_crossing_record_size", "tj_group_path_crossings",
     "tj_timing_margin", "tj_margin_record_size", "tj_group_timing_margin",
@@ -246,6 +247,20 @@ PROXIMITY_TOL_FRACTION = 0.01   # TJ_PROXIMITY_TOL_FRACTION: tol=None selects th
 PROXIMITY_MAX_DEPTH = 40        # TJ_PROXIMITY_MAX_DEPTH
 PROXIMITY_FRONTIER = 512        # TJ_PROXIMITY_FRONTIER: what max_windows=None selects
 PROXIMITY_MAX_WINDOWS = 4096    # TJ_PROXIMITY_MAX_WINDOWS
+
+
+class TjObswinRow(C.Structure):
+    """mirror of tj_obswin_row (include/trajadmm.h); tj_obswin_row_size() is its sizeof on the C side"""
+    _fields_ = [("t_first_lo", C.c_double), ("t_first_hi", C.c_double), ("t_last_lo", C.c_double), ("t_last_hi", C.c_double), ("within_lo", C.c_double),
+                ("closest", C.c_double), ("closest_time", C.c_double), ("robot", C.c_int), ("index", C.c_int), ("segment_first", C.c_int), ("segment_last", C.c_int),
+                ("leaves", C.c_int), ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int)]
+
+
+OBSWIN_FLAGS = dict(certain=1, uncertain=2, at_start=4, at_end=8, resolved=16, truncated=32)
+OBSWIN_TOL_FRACTION = 0.01   # TJ_OBSWIN_TOL_FRACTION: tol=None selects this fraction of dist over vel_limit, a time
+OBSWIN_MAX_DEPTH = 40        # TJ_OBSWIN_MAX_DEPTH
+OBSWIN_FRONTIER = 128        # TJ_OBSWIN_FRONTIER: what max_windows=None selects
+OBSWIN_MAX_WINDOWS = 1024    # TJ_OBSWIN_MAX_WINDOWS
 
 
 class TjProfileSample(C.Structure):
@@ -931,6 +946,15 @@ class Solver:
         sharded solver (world > 1) answers for its owned robots, the other records are zero."""
         return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_obstacle_approach(self._ctx, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
 
+    def obstacle_windows(self, dist=None, tol=None, max_depth=None, max_windows=None):
+        """tj_obstacle_windows: WHEN is each robot's FLOWN CURVE within `dist` (None: offset) of the obstacle set.  One row per certified time interval: the
+        curve first comes within dist in [`t_first_lo`, `t_first_hi`] and is last within it in [`t_last_lo`, `t_last_hi`], resolved to `tol` (None:
+        OBSWIN_TOL_FRACTION * dist / vel_limit); `within_lo` seconds certified within, `closest` / `closest_time` / `index` the smallest attained end sample
+        and its primitive (the caller's index), `segment_first`, `segment_last`, `leaves`, `depth`, `windows`, `flags` (OBSWIN_FLAGS).  Outside every row of a
+        robot its curve is certified farther than dist from every primitive.  Dict of numpy arrays [n] in (robot, t_first_lo) order.  Read-only.  All modes; a
+        sharded solver (world > 1) answers for its owned robots."""
+        return _listed_rows(TjObswinRow, lambda *a: self._check(self.lib.tj_obstacle_windows(self._ctx, *a)), _search_args(dist, tol, max_depth, max_windows))
+
     def peak_dynamics(self, tol=None, max_depth=None, max_windows=None, length_levels=None):
         """tj_peak_dynamics: per robot the FLOWN CURVE's peak speed, acceleration and jerk as brackets lo <= peak <= hi converged to the relative `tol` (None:
         PEAK_TOL) -- `speed_lo`, `speed_hi`, `speed_time` / `speed_segment` of the lo sample, `speed_depth`, `speed_windows`, `speed_flags` (PEAK_FLAGS), the same
@@ -1094,6 +1118,10 @@ class Group:
     def obstacle_approach(self, range=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_obstacle_approach: Solver.obstacle_approach of every robot from the rank that owns it (bitwise one context's)"""
         return _approach(TjObstacleRobot, lambda r, t, d, w, rec: self._check(self.lib.tj_group_obstacle_approach(self._g, r, t, d, w, rec)), self.U, range, tol, max_depth, max_windows)
+
+    def obstacle_windows(self, dist=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_obstacle_windows: Solver.obstacle_windows of every robot from the rank that owns it, in (robot, t_first_lo) order (bitwise one context's)"""
+        return _listed_rows(TjObswinRow, lambda *a: self._check(self.lib.tj_group_obstacle_windows(self._g, *a)), _search_args(dist, tol, max_depth, max_windows))
 
     def piece_times(self):
         """piece_time of every robot from the rank that owns it"""

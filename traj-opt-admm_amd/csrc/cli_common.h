@@ -307,6 +307,32 @@ inline int proximity_windows_rows(F&& f, double dist, std::vector<tj_proximity_r
   return rc;
 }
 
+// --obstacle-windows: one line per row, in the library's (robot, t_first_lo) order, and the fleet's line: rows, the rows with a sure time, the grazes, and the
+// seconds certified within dist summed over the rows
+inline void print_obstacle_windows(const std::vector<tj_obswin_row>& rows) {
+  std::cout.precision(17);
+  int certain = 0, uncertain = 0;
+  double within = 0.0;
+  for (const tj_obswin_row& r : rows) {
+    std::cout << "obswin uav " << r.robot << " first " << r.t_first_lo << " " << r.t_first_hi << " last " << r.t_last_lo << " " << r.t_last_hi << " within " << r.within_lo
+              << " closest " << r.closest << " time " << r.closest_time << " id " << r.index << " seg " << r.segment_first << " " << r.segment_last << " leaves " << r.leaves
+              << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    certain += r.flags & TJ_OBSWIN_CERTAIN ? 1 : 0;
+    uncertain += r.flags & TJ_OBSWIN_UNCERTAIN ? 1 : 0;
+    within += r.within_lo;
+  }
+  std::cout << "obswin fleet rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
+}
+// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle)
+template <class F>
+inline int obstacle_windows_rows(F&& f, double dist, std::vector<tj_obswin_row>& rows) {
+  int n = 0;
+  const int rc = f(dist, -1.0, -1, 0, nullptr, 0, &n);
+  if (rc < 0) return rc;
+  rows.resize(n);
+  return n ? f(dist, -1.0, -1, 0, rows.data(), n, &n) : rc;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

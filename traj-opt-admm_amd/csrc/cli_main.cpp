@@ -23,7 +23,11 @@
 // --obstacle-approach [TOL]: after the --closest-approach lines one line per robot from tj_obstacle_approach / tj_group_obstacle_approach -- the flown curve's closest
 // approach to an obstacle primitive converged to TOL (default the library's; default range), the primitive / segment / time, rounds, items evaluated, flag word -- and a
 // fleet summary (smallest hi, who, which primitive, when, any contact).  Works in the single-UAV main too.
-// --pair-approach [TOL]: after the --obstacle-approach lines one line per LISTED directed robot pair from tj_pair_approach / tj_group_pair_approach, sorted by (robot,
+// --obstacle-windows [DIST]: after the --obstacle-approach lines one line per row of tj_obstacle_windows / tj_group_obstacle_windows, sorted by (robot, start) -- every
+// time interval in which a robot's flown curve is not certified farther than DIST (default `offset`) from the obstacles: the brackets of the first and the last
+// time within DIST, the seconds certified within, the smallest attained sample with its time and primitive, the segments of the ends, leaves, rounds, windows
+// evaluated, flag word -- and the fleet's line: rows, rows with a sure time, grazes, seconds certified within.  Works in the single-UAV main too.
+// --pair-approach [TOL]: after the --obstacle-windows lines one line per LISTED directed robot pair from tj_pair_approach / tj_group_pair_approach, sorted by (robot,
 // partner) -- every pair that comes within the default range at equal flight times, its closest approach converged to TOL (default the library's), segment / time,
 // rounds, windows evaluated, flag word -- and the counts of pairs in contact, undecided and clear.
 // --path-crossings [TOL]: after the --pair-approach lines one line per LISTED unordered robot pair from tj_path_crossings / tj_group_path_crossings, sorted by (robot,
@@ -59,13 +63,14 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
   bool audit_timed = false; int audit_levels = -1;
   bool closest = false; double closest_tol = -1;
   bool obstacle = false; double obstacle_tol = -1;
+  bool obswin = false; double obswin_dist = 0;
   bool pairs = false; double pairs_tol = -1;
   bool crossings = false; double crossings_tol = -1;
   bool margins = false; double margins_tol = -1;
@@ -84,6 +89,7 @@ int main(int argc, char** argv) {
     else if (a == "--audit-timed") { audit_timed = true; if (i + 1 < argc && argv[i + 1][0] != '-') audit_levels = atoi(argv[++i]); }
     else if (a == "--closest-approach") { closest = true; if (i + 1 < argc && argv[i + 1][0] != '-') closest_tol = atof(argv[++i]); }
     else if (a == "--obstacle-approach") { obstacle = true; if (i + 1 < argc && argv[i + 1][0] != '-') obstacle_tol = atof(argv[++i]); }
+    else if (a == "--obstacle-windows") { obswin = true; if (i + 1 < argc && argv[i + 1][0] != '-') obswin_dist = atof(argv[++i]); }
     else if (a == "--pair-approach") { pairs = true; if (i + 1 < argc && argv[i + 1][0] != '-') pairs_tol = atof(argv[++i]); }
     else if (a == "--path-crossings") { crossings = true; if (i + 1 < argc && argv[i + 1][0] != '-') crossings_tol = atof(argv[++i]); }
     else if (a == "--timing-margin") { margins = true; if (i + 1 < argc && argv[i + 1][0] != '-') margins_tol = atof(argv[++i]); }
@@ -222,6 +228,12 @@ int main(int argc, char** argv) {
       std::vector<tj_obstacle_robot> rec(U);
       chk(group ? tj_group_obstacle_approach(grp, 0.0, obstacle_tol, -1, 0, rec.data()) : tj_obstacle_approach(ctx, 0.0, obstacle_tol, -1, 0, rec.data()), "tj_obstacle_approach");
       tjcli::print_obstacle_approach(rec);
+    }
+    if (obswin) {
+      std::vector<tj_obswin_row> rows;
+      chk(tjcli::obstacle_windows_rows([&](double r, double t, int d, int w, tj_obswin_row* out, int cap, int* n) {
+            return group ? tj_group_obstacle_windows(grp, r, t, d, w, out, cap, n) : tj_obstacle_windows(ctx, r, t, d, w, out, cap, n); }, obswin_dist, rows), "tj_obstacle_windows");
+      tjcli::print_obstacle_windows(rows);
     }
     if (pairs) {
       std::vector<tj_pair_record> rows;

@@ -1,4 +1,4 @@
-// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_proximity_windows, tj_flight_profile, tj_peak_dynamics), each piece defined once.
+// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_obstacle_windows, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_proximity_windows, tj_flight_profile, tj_peak_dynamics), each piece defined once.
 //
 // Every query works per (owned robot, segment) on the segment's 6-point hull (hull_entry's sums: the bits of the hull cache) and its box, and reduces per-lane candidates
 // with a TOTAL order, so that a result is a function of the state alone: no float atomics, no dependence on the order of evaluation.

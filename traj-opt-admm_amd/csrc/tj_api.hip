@@ -36,6 +36,7 @@
 #include "kernels_audit_timed.h"
 #include "kernels_closest.h"
 #include "kernels_obstacle_approach.h"
+#include "kernels_obstacle_windows.h"
 #include "kernels_peak_dynamics.h"
 #include "kernels_pair_approach.h"
 #include "kernels_path_crossing.h"
@@ -75,6 +76,9 @@ struct Listed { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullp
 // what a context holds for tj_proximity_windows (proximity_run): as Listed, with the row total; the sized buffers grow with the largest cap and max_windows so far
 struct ProxHeld { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; int* n_rows = nullptr; ProxArgs sized{}; tj_proximity_row* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
 
+// what a context holds for tj_obstacle_windows (obswin_run): the per-segment lists grow with the largest max_windows so far, the rows with the largest cap
+struct ObwinHeld { ObwinArgs sized{}; int* n_rows = nullptr; tj_obswin_row* out = nullptr; std::vector<void*> allocs, out_allocs; int mw = 0, cap = 0; };
+
 struct tj_ctx {
   tj_params prm;
   Dev d;
@@ -104,7 +108,7 @@ struct tj_ctx {
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
-  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_pair_approach, tj_path_crossings, tj_flight_profile, tj_peak_dynamics): every buffer is allocated by the first call that needs it, and a call
+  // The read-only queries (dev_query.h; tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_obstacle_windows, tj_pair_approach, tj_path_crossings, tj_flight_profile, tj_peak_dynamics): every buffer is allocated by the first call that needs it, and a call
   // whose allocations failed partway keeps what it got (query_buf).  Each query ends in a stream synchronise, so no two are in flight on one context, and they share: q_ctl, the
   // control block the BVH walk reports its overflow bit to (never the solver's); q_net [U][3][T] and q_pt [U], the staged copy of the control nets and piece times a group hands
   // in; q_order (sorted primitive -> caller's index), which belongs to the obstacle set and goes with it (cloud_allocs).  Per query: its rows / lists / counters and its records.
@@ -120,6 +124,7 @@ struct tj_ctx {
   Listed<CrossArgs, tj_crossing_record> cross;
   Listed<MarginArgs, tj_margin_record> margin;
   ProxHeld prox;   // tj_proximity_windows
+  ObwinHeld obwin; // tj_obstacle_windows
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -645,6 +650,8 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->cross.allocs) hipFree(p);
   for (void* p : c->margin.allocs) hipFree(p);
   for (void* p : c->prox.allocs) hipFree(p);
+  for (void* p : c->obwin.allocs) hipFree(p);
+  for (void* p : c->obwin.out_allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1173,7 +1180,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the ten (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
+// ---- the read-only queries: one path for the eleven (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1206,7 +1213,9 @@ const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approac
                  SEARCH_PROXIMITY{"tj_proximity_windows", "tj_group_proximity_windows", TJ_PROXIMITY_MAX_DEPTH, TJ_PROXIMITY_MAX_WINDOWS, 0.0, TJ_PROXIMITY_FRONTIER,
                                   ": deeper windows cannot be halved in a double", "", true, TJ_PROXIMITY_TOL_FRACTION},
                  SEARCH_OBSTACLE{"tj_obstacle_approach", "tj_group_obstacle_approach", TJ_OBSTACLE_MAX_DEPTH, TJ_OBSTACLE_FRONTIER, TJ_OBSTACLE_TOL, TJ_OBSTACLE_FRONTIER,
-                                 ": deeper windows are not dyadic in a double", ": the live list's capacity"};
+                                 ": deeper windows are not dyadic in a double", ": the live list's capacity"},
+                 SEARCH_OBSWIN{"tj_obstacle_windows", "tj_group_obstacle_windows", TJ_OBSWIN_MAX_DEPTH, TJ_OBSWIN_MAX_WINDOWS, 0.0, TJ_OBSWIN_FRONTIER,
+                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_OBSWIN_TOL_FRACTION};
 struct SearchArgs {
   double range, tol; int max_depth, max_windows;
   template <class Args> void put(Args& a) const { a.range = range; a.tol = tol; a.max_depth = max_depth; a.max_windows = max_windows; }
@@ -1538,6 +1547,67 @@ int proximity_run(tj_ctx* c, double dist, double tol, int max_depth, int max_win
   return TJ_OK;
 }
 
+// tj_obstacle_windows (kernels_obstacle_windows.h): the rows of the owned robots from the context's own state (nothing of another robot is read, so a sharded context
+// answers for its own and a group calls this rank after rank).  *n = the rows; min(cap, *n) of them are written.  TJ_ERR_CAPACITY has two causes: more rows than cap
+// (*n is set, and exceeds cap) and a walk frontier overflow (*n is left untouched: no count is known).  Three launches for the rows, two for the count.
+size_t obswin_bytes(const Dev& d, int owned, int cap, int mw) {
+  return (size_t)owned * d.S * ((size_t)4 * mw * sizeof(ObwinLeaf) + 4 * sizeof(int)) + (size_t)owned * 2 * sizeof(int) + (size_t)cap * sizeof(tj_obswin_row);
+}
+int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  const SearchSpec& spec = SEARCH_OBSWIN;
+  const std::string name = spec.name;
+  int r;
+  SearchArgs sa;
+  if ((r = search_args(c, spec, dist, tol, max_depth, max_windows, sa))) return r;
+  const Dev& d = c->d;
+  if (tol < 0 && sa.range == INFINITY) sa.tol = (spec.tol_fraction * d.offset) / d.vel_limit;   // (no time resolves 1 % of an infinite distance: offset's)
+  const int mw = sa.max_windows, owned = d.u1 - d.u0;
+  if (obswin_bytes(d, owned, cap, mw) > (size_t)TJ_OBSWIN_MAX_BYTES) {
+    c->err = name + ": " + std::to_string(owned) + " robots of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap) + " need " +
+             std::to_string(obswin_bytes(d, owned, cap, mw)) + " bytes of device memory, more than TJ_OBSWIN_MAX_BYTES (" + std::to_string(TJ_OBSWIN_MAX_BYTES) + "): lower max_windows or cap";
+    return TJ_ERR_INVALID;
+  }
+  if ((r = query_state(c, spec.name, false, false))) return r;
+  if (d.N == 0 || owned <= 0) { *n = 0; return TJ_OK; }   // no obstacles: nothing is within any distance of them
+  QUIESCE(c);
+  ObwinHeld& h = c->obwin;
+  const size_t units = (size_t)owned * d.S;
+  if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.sized.info, units * 4)) || (r = query_buf(c, h.sized.robot, (size_t)owned * 2)) || (r = ensure_order(c))) return r;
+  if (mw > h.mw) {   // grow: the context is quiet, nothing reads the old buffers; a failure keeps what it got on the list and starts over next time
+    for (void* p : h.allocs) hipFree(p);
+    h.allocs.clear();
+    h.sized.list = nullptr; h.sized.leaf = nullptr; h.mw = 0;
+    if ((r = query_buf(c, h.sized.list, units * 2 * mw, &h.allocs)) || (r = query_buf(c, h.sized.leaf, units * 2 * mw, &h.allocs))) return r;
+    h.mw = mw;
+  }
+  if (cap > h.cap) {
+    for (void* p : h.out_allocs) hipFree(p);
+    h.out_allocs.clear();
+    h.out = nullptr; h.cap = 0;
+    if ((r = query_buf(c, h.out, cap, &h.out_allocs))) return r;
+    h.cap = cap;
+  }
+  ObwinArgs a = h.sized;
+  Dev da;
+  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = walk_dev(c, da))) return r;
+  a.order = c->q_order; sa.put(a); a.row_cap = cap; a.n_rows = h.n_rows;
+  if ((r = query_clear(c, h.n_rows, 1))) return r;
+  with_prim(d, [&](auto prim) { hipLaunchKernelGGL(k_obwin_refine<decltype(prim)::value>, dim3((unsigned)units), dim3(OW_THREADS), 0, c->stream, da, a); });
+  hipLaunchKernelGGL(k_obwin_count, dim3(owned), dim3(OW_THREADS), 0, c->stream, da, a);
+  if (cap > 0) hipLaunchKernelGGL(k_obwin_place, dim3(owned), dim3(OW_THREADS), 0, c->stream, da, a, h.out);
+  int nr = 0;
+  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, spec.name))) {   // (a walk overflow ends here: no count is known, *n stays untouched)
+    if (r == TJ_ERR_CAPACITY)   // (query_finish words it for a `range`; this query's first argument is `dist`)
+      c->err = name + ": the BVH frontier of a window overflowed at this dist (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one window's box): lower `dist`";
+    return r;
+  }
+  *n = nr;
+  if (std::min(cap, nr) > 0 && ((r = query_fetch(c, rows, h.out, std::min(cap, nr))) || (r = query_finish(c, nullptr)))) return r;
+  if (nr > cap && !(cap == 0 && !rows)) { c->err = name + ": " + std::to_string(nr) + " rows, the caller's hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
 int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
   if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
@@ -1625,6 +1695,8 @@ int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int
   return query_finish(c, "tj_obstacle_approach");
 }
 int tj_obstacle_record_size(void) { return (int)sizeof(tj_obstacle_robot); }
+int tj_obstacle_windows(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) { return obswin_run(c, dist, tol, max_depth, max_windows, rows, cap, n); }
+int tj_obswin_row_size(void) { return (int)sizeof(tj_obswin_row); }
 
 // tj_peak_dynamics: every owned robot from the context's own state, like tj_obstacle_approach.  Argument checks in the queries' precedence: null -> NaN -> limits -> no state
 int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* out) {

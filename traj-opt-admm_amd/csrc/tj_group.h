@@ -724,6 +724,26 @@ int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_de
     return tj_obstacle_approach(c, range, tol, max_depth, max_windows, part); });
 }
 
+// tj_obstacle_windows, rank after rank, each from its own state (ownership is by contiguous robot blocks in rank order: that is the (robot, t_first_lo) order).  A rank
+// whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.  Only THAT capacity error is carried on (obswin_run set its
+// count above the room it was given); a walk frontier overflow leaves the count untouched and ends the group's call with the rank's TJ_ERR_CAPACITY, *n untouched.
+int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) {
+  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  int total = 0;
+  const int rc = group_each(g, false, false, [&](int, tj_ctx* c, const double*, const double*) {
+    const int room = std::max(0, cap - total);
+    int nr = 0;
+    const int e = obswin_run(c, dist, tol, max_depth, max_windows, room ? rows + total : nullptr, room, &nr);
+    if (e < 0 && !(e == TJ_ERR_CAPACITY && nr > room)) return e;
+    total += nr;
+    return (int)TJ_OK;
+  });
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_obstacle_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* out) {
   return group_query(g, false, false, out, {}, {}, [&](tj_ctx* c, const double*, const double*, tj_dynamics_robot* part) {
     return tj_peak_dynamics(c, tol, max_depth, max_windows, length_levels, part); });

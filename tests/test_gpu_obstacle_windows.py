@@ -93,6 +93,27 @@ def test_constructed_states(pkg, scenes, name):
     slv.close()
 
 
+def test_a_segment_with_a_second_block_of_leaves(pkg, scenes):
+    """k_obwin_place indexes a segment's chain heads in blocks of 64 leaves; no other state of this file gives a segment more than 25.  The straight flight
+    x = -5 + 2 t with tol = 0 and max_depth = 40, segment 25 (x in [1.25, 1.5]).  Points 77 and 78 at x = 1.3 and 1.325 with dist = 0.05 - 1e-11 are within
+    dist over x in [1.25 + 1e-11, 1.375 - 1e-11]: one crossing just behind the segment's start and one just before its midpoint, so nearly every halving
+    leaves an IN child behind and the chain has 68 leaves.  Point 79 at x = 1.45 adds a second chain, whose head is leaf 68.  Asserted on the restatement,
+    so that the case cannot stop reaching the path: more than 64 leaves in one segment, a chain across leaf 64, a chain head in the second block."""
+    dist = 0.05 - 1e-11
+    scene, st = W.two_point_state(pkg, scenes, 0.025)
+    scene["cloud"][79] = (1.45, 0.0, 0.0)
+    slv = loaded(pkg, scene, st)
+    ref = ref_for(pkg, slv, scene, st)
+    found = ref.search(0, 25, dist, 0.0, 40, pkg.OBSWIN_FRONTIER)
+    lv = found["leaves"]
+    heads = [k for k in range(1, len(lv)) if lv[k - 1][1] != lv[k][0]]
+    assert len(lv) > 64 and lv[63][1] == lv[64][0] and any(k > 64 for k in heads) and not found["truncated"]
+    a = check(pkg, slv, ref, dist, 0.0, 40)
+    assert list(a["leaves"]) == [heads[0], len(lv) - heads[0]] and list(a["segment_first"]) == list(a["segment_last"]) == [25, 25]
+    assert np.all(a["flags"] == pkg.OBSWIN_FLAGS["certain"]) and np.all(a["depth"] == 40)
+    slv.close()
+
+
 @pytest.mark.parametrize("P,res", [(12, 8), (2, 16)])
 def test_segment_counts_and_resolutions(pkg, scenes, P, res):
     scene = dict(scenes.hard(4, 3000, pieces=P))

@@ -218,14 +218,15 @@ inline void print_pair_approach(const std::vector<tj_pair_record>& rows) {
   }
   std::cout << "pair fleet listed " << rows.size() << " contact " << contact << " undecided " << rows.size() - contact - clear << " clear " << clear << std::endl;
 }
-// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle)
-template <class F>
-inline int pair_approach_rows(F&& f, double tol, std::vector<tj_pair_record>& rows) {
+// a row-listing query: the count-only call, then the rows.  f(rows or null, cap, &n): the context's or the group's entry point, bound to its handle and to the
+// query's leading arguments (tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_obstacle_windows)
+template <class Rec, class F>
+inline int listed_rows(F&& f, std::vector<Rec>& rows) {
   int n = 0;
-  const int rc = f(0.0, tol, -1, 0, nullptr, 0, &n);
+  const int rc = f(nullptr, 0, &n);
   if (rc < 0) return rc;
   rows.resize(n);
-  return n ? f(0.0, tol, -1, 0, rows.data(), n, &n) : rc;
+  return n ? f(rows.data(), n, &n) : rc;
 }
 
 // --path-crossings: one line per listed unordered pair, in the library's (robot, partner) order, and the counts of pairs whose separation rests on timing
@@ -240,15 +241,6 @@ inline void print_path_crossings(const std::vector<tj_crossing_record>& rows) {
     clear += !(r.flags & TJ_CROSSING_CONTACT) && (r.flags & TJ_CROSSING_CLEAR) ? 1 : 0;
   }
   std::cout << "crossing fleet listed " << rows.size() << " timing " << contact << " undecided " << rows.size() - contact - clear << " space " << clear << std::endl;
-}
-// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle)
-template <class F>
-inline int path_crossings_rows(F&& f, double tol, std::vector<tj_crossing_record>& rows) {
-  int n = 0;
-  const int rc = f(0.0, tol, -1, 0, nullptr, 0, &n);
-  if (rc < 0) return rc;
-  rows.resize(n);
-  return n ? f(0.0, tol, -1, 0, rows.data(), n, &n) : rc;
 }
 
 // --timing-margin: one line per listed unordered pair, in the library's (robot, partner) order, and the fleet's line: the pairs within dist on the timetable, the
@@ -265,15 +257,6 @@ inline void print_timing_margin(const std::vector<tj_margin_record>& rows) {
     smallest = std::min(smallest, r.hi);
   }
   std::cout << "margin fleet listed " << rows.size() << " contact " << contact << " positive " << positive << " smallest " << smallest << std::endl;
-}
-// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle); default dist and max_slip
-template <class F>
-inline int timing_margin_rows(F&& f, double tol, std::vector<tj_margin_record>& rows) {
-  int n = 0;
-  const int rc = f(0.0, 0.0, tol, -1, 0, nullptr, 0, &n);
-  if (rc < 0) return rc;
-  rows.resize(n);
-  return n ? f(0.0, 0.0, tol, -1, 0, rows.data(), n, &n) : rc;
 }
 
 // --proximity-windows: one line per row, in the library's (robot, partner, t_first_lo) order, and the fleet's line: listed pairs, rows, the rows with a sure time,
@@ -322,15 +305,6 @@ inline void print_obstacle_windows(const std::vector<tj_obswin_row>& rows) {
     within += r.within_lo;
   }
   std::cout << "obswin fleet rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
-}
-// the count-only call, then the rows (f: the context's or the group's entry point, bound to its handle)
-template <class F>
-inline int obstacle_windows_rows(F&& f, double dist, std::vector<tj_obswin_row>& rows) {
-  int n = 0;
-  const int rc = f(dist, -1.0, -1, 0, nullptr, 0, &n);
-  if (rc < 0) return rc;
-  rows.resize(n);
-  return n ? f(dist, -1.0, -1, 0, rows.data(), n, &n) : rc;
 }
 
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach

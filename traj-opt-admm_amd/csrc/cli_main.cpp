@@ -231,26 +231,26 @@ int main(int argc, char** argv) {
     }
     if (obswin) {
       std::vector<tj_obswin_row> rows;
-      chk(tjcli::obstacle_windows_rows([&](double r, double t, int d, int w, tj_obswin_row* out, int cap, int* n) {
-            return group ? tj_group_obstacle_windows(grp, r, t, d, w, out, cap, n) : tj_obstacle_windows(ctx, r, t, d, w, out, cap, n); }, obswin_dist, rows), "tj_obstacle_windows");
+      chk(tjcli::listed_rows([&](tj_obswin_row* out, int cap, int* n) {
+            return group ? tj_group_obstacle_windows(grp, obswin_dist, -1.0, -1, 0, out, cap, n) : tj_obstacle_windows(ctx, obswin_dist, -1.0, -1, 0, out, cap, n); }, rows), "tj_obstacle_windows");
       tjcli::print_obstacle_windows(rows);
     }
     if (pairs) {
       std::vector<tj_pair_record> rows;
-      chk(tjcli::pair_approach_rows([&](double r, double t, int d, int w, tj_pair_record* out, int cap, int* n) {
-            return group ? tj_group_pair_approach(grp, r, t, d, w, out, cap, n) : tj_pair_approach(ctx, r, t, d, w, out, cap, n); }, pairs_tol, rows), "tj_pair_approach");
+      chk(tjcli::listed_rows([&](tj_pair_record* out, int cap, int* n) {
+            return group ? tj_group_pair_approach(grp, 0.0, pairs_tol, -1, 0, out, cap, n) : tj_pair_approach(ctx, 0.0, pairs_tol, -1, 0, out, cap, n); }, rows), "tj_pair_approach");
       tjcli::print_pair_approach(rows);
     }
     if (crossings) {
       std::vector<tj_crossing_record> rows;
-      chk(tjcli::path_crossings_rows([&](double r, double t, int d, int w, tj_crossing_record* out, int cap, int* n) {
-            return group ? tj_group_path_crossings(grp, r, t, d, w, out, cap, n) : tj_path_crossings(ctx, r, t, d, w, out, cap, n); }, crossings_tol, rows), "tj_path_crossings");
+      chk(tjcli::listed_rows([&](tj_crossing_record* out, int cap, int* n) {
+            return group ? tj_group_path_crossings(grp, 0.0, crossings_tol, -1, 0, out, cap, n) : tj_path_crossings(ctx, 0.0, crossings_tol, -1, 0, out, cap, n); }, rows), "tj_path_crossings");
       tjcli::print_path_crossings(rows);
     }
     if (margins) {
       std::vector<tj_margin_record> rows;
-      chk(tjcli::timing_margin_rows([&](double r, double m, double t, int d, int w, tj_margin_record* out, int cap, int* n) {
-            return group ? tj_group_timing_margin(grp, r, m, t, d, w, out, cap, n) : tj_timing_margin(ctx, r, m, t, d, w, out, cap, n); }, margins_tol, rows), "tj_timing_margin");
+      chk(tjcli::listed_rows([&](tj_margin_record* out, int cap, int* n) {   // (default dist and max_slip)
+            return group ? tj_group_timing_margin(grp, 0.0, 0.0, margins_tol, -1, 0, out, cap, n) : tj_timing_margin(ctx, 0.0, 0.0, margins_tol, -1, 0, out, cap, n); }, rows), "tj_timing_margin");
       tjcli::print_timing_margin(rows);
     }
     if (proximity) {

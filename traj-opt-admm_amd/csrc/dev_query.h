@@ -9,6 +9,8 @@
 //   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
 //   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
 //   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the five branch-and-bound queries, and their four common flag bits
+//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain   THE MERGE HALF of the two window queries (tj_proximity_windows, tj_obstacle_windows): the classes and
+//                  the six flag bits, the leaves' rank sort with the interior chain heads, a head's row index, and the fold of a chain into a row's common fields and flags
 #pragma once
 #include <limits.h>
 #include "../../include/trajadmm.h"
@@ -266,5 +268,71 @@ static_assert(TJ_CLOSEST_TRUNCATED == BNB_TRUNCATED && TJ_PAIR_TRUNCATED == BNB_
 __device__ __forceinline__ int bnb_flags(bool found, double hi, double lo, double tol, int n, bool truncated, double offset) {
   return (found && hi <= offset ? BNB_CONTACT : 0) | (lo > offset ? BNB_CLEAR : 0) | (hi - lo <= tol || (n == 0 && !truncated) ? BNB_CONVERGED : 0) | (truncated ? BNB_TRUNCATED : 0);
 }
+
+// ---- the merge half of the window queries (kernels_proximity.h, kernels_obstacle_windows.h): both classify windows against a level, keep leaves, sort them, merge adjacent
+// leaves into chains and write a row per chain.  How a window is evaluated, the round loop, what a leaf's times are and where a chain goes on stay with each query. ----
+constexpr int WIN_OUT = 0, WIN_IN = 1, WIN_MIXED = 2;   // a window's class against the level
+constexpr int WIN_CERTAIN = 1, WIN_UNCERTAIN = 2, WIN_AT_START = 4, WIN_AT_END = 8, WIN_RESOLVED = 16, WIN_TRUNCATED = 32;   // a row's flag bits (the two headers' values agree)
+static_assert(TJ_PROXIMITY_CERTAIN == WIN_CERTAIN && TJ_OBSWIN_CERTAIN == WIN_CERTAIN && TJ_PROXIMITY_UNCERTAIN == WIN_UNCERTAIN && TJ_OBSWIN_UNCERTAIN == WIN_UNCERTAIN, "CERTAIN, UNCERTAIN");
+static_assert(TJ_PROXIMITY_AT_START == WIN_AT_START && TJ_OBSWIN_AT_START == WIN_AT_START && TJ_PROXIMITY_AT_END == WIN_AT_END && TJ_OBSWIN_AT_END == WIN_AT_END, "AT_START, AT_END");
+static_assert(TJ_PROXIMITY_RESOLVED == WIN_RESOLVED && TJ_OBSWIN_RESOLVED == WIN_RESOLVED && TJ_PROXIMITY_TRUNCATED == WIN_TRUNCATED && TJ_OBSWIN_TRUNCATED == WIN_TRUNCATED, "RESOLVED, TRUNCATED");
+
+// is leaf i of m sorted leaves a chain head: it does not begin (member A) where the leaf before it ends (member B).  first: what the caller knows of leaf 0
+template <auto A, auto B, class Leaf>
+__device__ __forceinline__ bool win_head(const Leaf* sorted, int i, int m, bool first) { return i < m && (i == 0 ? first : sorted[i - 1].*B != sorted[i].*A); }
+// one wave: leaf[0..m) by the start key A into sorted (rank sort: the keys are distinct, so a leaf's rank is the number of smaller keys and the order of the appends vanishes
+// here), behind a barrier; returns the chain heads BEHIND leaf 0, in every lane (whether leaf 0 starts a chain is the caller's to say)
+template <auto A, auto B, class Leaf>
+__device__ __forceinline__ int win_sort(const Leaf* leaf, Leaf* sorted, int m) {
+  const int lane = lane_id();
+  for (int i = lane; i < m; i += 64) {
+    const Leaf x = leaf[i];
+    int rank = 0;
+    for (int k = 0; k < m; k++) rank += leaf[k].*A < x.*A ? 1 : 0;
+    sorted[rank] = x;
+  }
+  __syncthreads();
+  int heads = 0;
+  for (int i = 1 + lane; i < m; i += 64) heads += win_head<A, B>(sorted, i, m, false) ? 1 : 0;
+  return wave_sum(heads);
+}
+
+// one wave: the rows of the slots before `slot` (counts[stride * k]: slot k's row count), in every lane
+__device__ __forceinline__ int win_rows_before(const int* counts, int stride, int slot) {
+  int off = 0;
+  for (int k = lane_id(); k < slot; k += 64) off += counts[stride * k];
+  return wave_sum(off);
+}
+// one step over a block of 64 leaves, every lane of the wave: a head's row index is base + the heads in the lanes below it; base moves behind the block's heads
+__device__ __forceinline__ int win_row_index(bool head, int& base) {
+  const unsigned long long mask = ballot(head);
+  const int r = base + prefix_count(mask);
+  base += __popcll(mask);
+  return r;
+}
+
+// The fold of one chain, leaf after leaf in time order, into what a row of either query states.  A leaf is its times [ta, tb], its width in time, IN or not, and the
+// separations attained at its ends (h0, h5) with the ids they were found against.  closest: the smallest of them in the total order (value, time, id); a row without an id
+// leaves i0 / i5 at INT_MAX, where no id is ever smaller, so its ties end at the time.
+struct WinChain {
+  double first_hi = -1.0, last_lo = -1.0, within = 0.0, best = INFINITY, best_t = INFINITY; int best_i = INT_MAX; bool sure = false;
+  __device__ __forceinline__ void add(double dist, double ta, double tb, double width, bool in, double h0, double h5, int i0 = INT_MAX, int i5 = INT_MAX) {
+    const bool s0 = in || h0 <= dist, s5 = in || h5 <= dist;
+    if (!sure && (s0 || s5)) { first_hi = s0 ? ta : tb; sure = true; }
+    if (s0) last_lo = ta;
+    if (s5) last_lo = tb;
+    if (in) within += width;   // (summed in time order)
+    if (h0 < best || (h0 == best && (ta < best_t || (ta == best_t && i0 < best_i)))) { best = h0; best_t = ta; best_i = i0; }
+    if (h5 < best || (h5 == best && (tb < best_t || (tb == best_t && i5 < best_i)))) { best = h5; best_t = tb; best_i = i5; }
+  }
+  // the row's common fields and its flags, for a chain from t_first_lo to t_last_hi; closest_time and what else a query's row has stay at its call
+  template <class Row>
+  __device__ __forceinline__ void finish(Row& row, double t_first_lo, double t_last_hi, bool at_start, bool at_end, bool truncated, double tol) const {
+    row.t_first_lo = t_first_lo; row.t_first_hi = first_hi; row.t_last_lo = last_lo; row.t_last_hi = t_last_hi; row.within_lo = within; row.closest = best;
+    int flags = (sure ? WIN_CERTAIN : WIN_UNCERTAIN) | (at_start ? WIN_AT_START : 0) | (at_end ? WIN_AT_END : 0) | (truncated ? WIN_TRUNCATED : 0);
+    if (sure && (at_start || first_hi - t_first_lo <= tol) && (at_end || t_last_hi - last_lo <= tol)) flags |= WIN_RESOLVED;
+    row.flags = flags;
+  }
+};
 
 }  // namespace tj

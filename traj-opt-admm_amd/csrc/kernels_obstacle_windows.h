@@ -19,13 +19,16 @@
 //                   time to process(pt), which forms the candidate's four values per lane and accumulates per lane any_in, all_out and the two (value, index)
 //                   minima (the candidate buffer flushes at 64: process runs several times per walk); behind the walk one ballot each and two total-order
 //                   reductions.  The windows of a round are taken one after the other by the whole wave, so the lists are appended by lane 0 alone, counted in
-//                   LDS.  Then the leaves are sorted by sa (rank sort: the keys are distinct) into the live lists' room and the segment's leaf count, work, depth,
-//                   truncation and interior chain heads are stored.
+//                   LDS.  Then the leaves are sorted by sa (win_sort) into the live lists' room and the segment's leaf count, work, depth, truncation and interior
+//                   chain heads are stored.
 //   k_obwin_count   one wave per owned robot: the chain heads over its segments' leaves in order (a segment's first leaf continues the chain of the segment
 //                   before it or starts one) = the robot's row count, and its work; the counts are added up with one integer atomic per robot.
-//   k_obwin_place   one wave per owned robot: the exclusive scan of the row counts over the robots before it gives its first row; the chain heads of a block of 64
-//                   leaves get their row index from a ballot's prefix count, and the lane of a head walks its chain left to right (within_lo is summed in time
-//                   order), across segment boundaries, and writes the row where it belongs.  Rows beyond the caller's capacity are counted, not written.
+//   k_obwin_place   one wave per owned robot: win_rows_before over the robots before it gives its first row; the chain heads of a block of 64 leaves get their row
+//                   index from win_row_index, and the lane of a head folds its chain left to right (WinChain), across segment boundaries, and writes the row where
+//                   it belongs.  Rows beyond the caller's capacity are counted, not written.
+// THE MERGE HALF is dev_query.h's, shared with kernels_proximity.h: the classes and flag bits (WIN_*), the rank sort with the interior heads, the row indexing, the
+// chain fold with the flag rule.  This file's own: a leaf's times and width are formed from (segment, sa, sb) (obwin_time; ((sb - sa) / res) * ptu), whether a segment's
+// first leaf is a head and where a chain goes on behind a segment's last leaf (obwin_first_is_head), and the row's index, segments and closest_time = -1 without a sample.
 // bvh_query and walk_step contain __syncthreads(): the refine kernel is ONE wave per block, every lane reaches every call, and the trip counts of the loop over
 // live windows and of the round loop are read from LDS behind a barrier (or loaded from one address by every lane), never taken from a lane's own arithmetic.
 // Every loop is bounded by max_depth <= 40 and max_windows.  No polling, no workgroup waits on another, no cross-queue word, no float atomics, no ticket between
@@ -37,9 +40,6 @@
 namespace tj {
 
 constexpr int OW_THREADS = 64;    // one wave per (robot, segment): the walk is one wave's
-constexpr int OW_OUT = 0, OW_IN = 1, OW_MIXED = 2;
-constexpr int OW_CERTAIN = TJ_OBSWIN_CERTAIN, OW_UNCERTAIN = TJ_OBSWIN_UNCERTAIN, OW_AT_START = TJ_OBSWIN_AT_START, OW_AT_END = TJ_OBSWIN_AT_END,
-              OW_RESOLVED = TJ_OBSWIN_RESOLVED, OW_TRUNCATED = TJ_OBSWIN_TRUNCATED;
 
 struct ObwinLeaf { double sa, sb, h0, h5; int i0, i5, in, pad; };   // a live window (MIXED) or a kept one (IN, or an EDGE leaf): [sa, sb], h0 / h5 with their primitives
 
@@ -94,12 +94,12 @@ __device__ __forceinline__ int obwin_eval(const Dev& D, const ObwinArgs& A, cons
       if (h5 < b5 || (h5 == b5 && id < k5)) { b5 = h5; k5 = id; }
     }
   });
-  if (ballot(!all_out) == 0ull) return OW_OUT;   // (wave-uniform; a lane without a candidate has nothing against OUT)
+  if (ballot(!all_out) == 0ull) return WIN_OUT;   // (wave-uniform; a lane without a candidate has nothing against OUT)
   const bool in = ballot(any_in) != 0ull;
   wave_argmin(b0, k0);
   wave_argmin(b5, k5);
   w = ObwinLeaf{sa, sb, b0, b5, k0, k5, in ? 1 : 0, 0};
-  return in ? OW_IN : OW_MIXED;
+  return in ? WIN_IN : WIN_MIXED;
 }
 
 template <int PRIM>
@@ -124,9 +124,9 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_refine(Dev D, ObwinArgs A)
     ObwinLeaf w;
     const int cls = obwin_eval<PRIM>(D, A, net, tr, 0.0, 1.0, P, ws, w);
     if (lane == 0) {
-      s_leaf = cls == OW_IN ? 1 : 0; s_live = cls == OW_MIXED ? 1 : 0; s_next = 0; s_work = 1;
-      if (cls == OW_IN) leaf[0] = w;
-      if (cls == OW_MIXED) cur[0] = w;
+      s_leaf = cls == WIN_IN ? 1 : 0; s_live = cls == WIN_MIXED ? 1 : 0; s_next = 0; s_work = 1;
+      if (cls == WIN_IN) leaf[0] = w;
+      if (cls == WIN_MIXED) cur[0] = w;
     }
   }
   __syncthreads();
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_refine(Dev D, ObwinArgs A)
         const int cls = obwin_eval<PRIM>(D, A, net, tr, c ? sm : w.sa, c ? w.sb : sm, P, ws, k);
         if (lane == 0) {
           s_work++;
-          if (cls == OW_IN) { const int at = s_leaf++; if (at < maxw) leaf[at] = k; }
-          if (cls == OW_MIXED) { const int at = s_next++; if (at < maxw) nxt[at] = k; }
+          if (cls == WIN_IN) { const int at = s_leaf++; if (at < maxw) leaf[at] = k; }
+          if (cls == WIN_MIXED) { const int at = s_next++; if (at < maxw) nxt[at] = k; }
         }
       }
     }
@@ -167,17 +167,8 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_refine(Dev D, ObwinArgs A)
   const int m = kept + n;   // <= 2 * max_windows
   __syncthreads();
 
-  // ---- by sa: the keys are distinct, so a leaf's rank is the number of smaller keys (the live lists' room is free now) ----
-  for (int i = lane; i < m; i += OW_THREADS) {
-    const ObwinLeaf x = leaf[i];
-    int rank = 0;
-    for (int k = 0; k < m; k++) rank += leaf[k].sa < x.sa ? 1 : 0;
-    sorted[rank] = x;
-  }
-  __syncthreads();
-  int heads = 0;
-  for (int i = 1 + lane; i < m; i += OW_THREADS) heads += sorted[i - 1].sb != sorted[i].sa ? 1 : 0;
-  heads = wave_sum(heads);
+  // ---- by sa into the live lists' room, which is free now, and the chain heads behind the first leaf ----
+  const int heads = win_sort<&ObwinLeaf::sa, &ObwinLeaf::sb>(leaf, sorted, m);
   if (lane == 0) {
     int* info = A.info + unit * 4;
     info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = heads;
@@ -212,13 +203,10 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_count(Dev D, ObwinArgs A) 
 // the rows of robot slot ui at their final place: behind the rows of the robots before it, chain after chain in time order
 __global__ __launch_bounds__(OW_THREADS) void k_obwin_place(Dev D, ObwinArgs A, tj_obswin_row* out) {
   const int ui = blockIdx.x, lane = lane_id(), S = D.S, u = D.u0 + ui;
-  int off = 0;
-  for (int k = lane; k < ui; k += OW_THREADS) off += A.robot[2 * k];
-  off = wave_sum(off);
+  int base = win_rows_before(A.robot, 2, ui);   // the robot's first row
   const int windows = A.robot[2 * ui + 1];
   const double dist = A.range, tol = A.tol, ptu = A.pt[u], res = (double)D.res;
   const size_t per = (size_t)2 * A.max_windows;
-  int base = off;
   for (int tr = 0; tr < S; tr++) {
     const size_t unit = (size_t)ui * S + tr;
     const int m = A.info[unit * 4];   // (one address for the wave)
@@ -227,28 +215,21 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_place(Dev D, ObwinArgs A, 
     const bool first_head = obwin_first_is_head(A, S, ui, tr);
     for (int i0 = 0; i0 < m; i0 += OW_THREADS) {
       const int i = i0 + lane;
-      const bool head = i < m && (i == 0 ? first_head : sorted[i - 1].sb != sorted[i].sa);
-      const unsigned long long mask = ballot(head);
-      const int r = base + prefix_count(mask);
-      base += __popcll(mask);
+      const bool head = win_head<&ObwinLeaf::sa, &ObwinLeaf::sb>(sorted, i, m, first_head);
+      const int r = win_row_index(head, base);
       if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
         // the chain from leaf i of segment tr on, left to right, into the segments behind where it goes on
         tj_obswin_row row;
-        double first_hi = -1.0, last_lo = -1.0, within = 0.0, best = INFINITY, best_t = INFINITY, end_g = 0.0, end_t = 0.0;
-        int best_i = INT_MAX, t = tr, k = i, mt = m, leaves = 0, dmax = 0;
-        bool sure = false, trunc = false;
+        WinChain ch;
+        double end_g = 0.0, end_t = 0.0;
+        int t = tr, k = i, mt = m, leaves = 0, dmax = 0;
+        bool trunc = false;
         const ObwinLeaf* sl = sorted;
         for (;;) {
           if (k == 0 || leaves == 0) { const int dt = A.info[((size_t)ui * S + t) * 4 + 2]; dmax = max(dmax, dt & 0xffff); trunc = trunc || (dt >> 16) != 0; }
           const ObwinLeaf x = sl[k];
           const double ta = obwin_time(D, ptu, t, x.sa), tb = obwin_time(D, ptu, t, x.sb);
-          const bool s0 = x.in || x.h0 <= dist, s5 = x.in || x.h5 <= dist;
-          if (!sure && (s0 || s5)) { first_hi = s0 ? ta : tb; sure = true; }
-          if (s0) last_lo = ta;
-          if (s5) last_lo = tb;
-          if (x.in) within += ((x.sb - x.sa) / res) * ptu;
-          if (x.h0 < best || (x.h0 == best && (ta < best_t || (ta == best_t && x.i0 < best_i)))) { best = x.h0; best_t = ta; best_i = x.i0; }
-          if (x.h5 < best || (x.h5 == best && (tb < best_t || (tb == best_t && x.i5 < best_i)))) { best = x.h5; best_t = tb; best_i = x.i5; }
+          ch.add(dist, ta, tb, ((x.sb - x.sa) / res) * ptu, x.in, x.h0, x.h5, x.i0, x.i5);
           end_g = obwin_pos(t, x.sb); end_t = tb;
           leaves++;
           if (k + 1 < mt) {
@@ -263,15 +244,11 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_place(Dev D, ObwinArgs A, 
             t++; k = 0; mt = m2; sl = s2;
           }
         }
-        const bool found = best_i != INT_MAX;
-        row.t_first_lo = obwin_time(D, ptu, tr, sorted[i].sa); row.t_first_hi = first_hi; row.t_last_lo = last_lo; row.t_last_hi = end_t;
-        row.within_lo = within; row.closest = best; row.closest_time = found ? best_t : -1.0;
-        row.robot = u; row.index = found ? best_i : -1; row.segment_first = tr; row.segment_last = t;
+        const bool found = ch.best_i != INT_MAX;
+        ch.finish(row, obwin_time(D, ptu, tr, sorted[i].sa), end_t, obwin_pos(tr, sorted[i].sa) == 0.0, end_g == (double)S, trunc, tol);
+        row.closest_time = found ? ch.best_t : -1.0;
+        row.robot = u; row.index = found ? ch.best_i : -1; row.segment_first = tr; row.segment_last = t;
         row.leaves = leaves; row.depth = dmax; row.windows = windows;
-        const bool at_start = obwin_pos(tr, sorted[i].sa) == 0.0, at_end = end_g == (double)S;
-        int flags = (sure ? OW_CERTAIN : OW_UNCERTAIN) | (at_start ? OW_AT_START : 0) | (at_end ? OW_AT_END : 0) | (trunc ? OW_TRUNCATED : 0);
-        if (sure && (at_start || first_hi - row.t_first_lo <= tol) && (at_end || end_t - last_lo <= tol)) flags |= OW_RESOLVED;
-        row.flags = flags;
         out[r] = row;
       }
     }

@@ -19,13 +19,15 @@
 //   k_prox_seed     the walk again (the same bits).  A window of a listed pair whose slot is below cap is counted in the pair's `windows`; IN and MIXED windows are
 //                   appended to the PAIR's seed list with their class, h0 and h5 (bnb_keep on the pair's counter; at most 2 S + 2 windows at level 0).
 //   k_prox_refine   one wave per pair slot.  ALL rounds in the kernel on the pair's slices of global buffers (a ping-pong live list and the kept list, both counted in
-//                   LDS as bnb_keep does), then the live windows join the kept list as EDGE leaves, the leaves are sorted by ca (rank sort: the keys are distinct, so
-//                   the order of the appends vanishes here) and the chain heads counted: the pair's row count.
-//   k_prox_place    one wave per pair slot: the exclusive scan of the row counts gives the pair's first row; the chain heads of a block of 64 leaves get their row
-//                   index from a ballot's prefix count, and the lane of a head walks its chain left to right (within_lo is summed in time order) and writes the row
-//                   where it belongs.  Rows beyond the caller's capacity are counted, not written.
-// The classifying round loop is this file's (bnb_rounds prunes against a best and does not fit); the bounded append is dev_query.h's.  LDS per wave: k_pair_refine's
-// three 18-row tiles of 64 columns (27 KB), so the per-lane GJK's registers set the occupancy.
+//                   LDS as bnb_keep does), then the live windows join the kept list as EDGE leaves, the leaves are sorted by ca (win_sort: the order of the appends
+//                   vanishes here) and the chain heads counted: the pair's row count (leaf 0 is a head: a pair's chains do not go on anywhere).
+//   k_prox_place    one wave per pair slot: win_rows_before gives the pair's first row; the chain heads of a block of 64 leaves get their row index from
+//                   win_row_index, and the lane of a head folds its chain left to right (WinChain) and writes the row where it belongs.  Rows beyond the caller's
+//                   capacity are counted, not written.
+// The classifying round loop is this file's (bnb_rounds prunes against a best and does not fit).  The bounded append and THE MERGE HALF are dev_query.h's, shared with
+// kernels_obstacle_windows.h: the classes and flag bits (WIN_*), the rank sort with the interior heads, the row indexing, the chain fold with the flag rule.  This
+// file's own: a leaf's times are its [ca, cb] and its width cb - ca, the next leaf is the next of the pair's list, a row has a partner and no index (the closest
+// sample's ties end at the time).  LDS per wave: k_pair_refine's three 18-row tiles of 64 columns (27 KB), so the per-lane GJK's registers set the occupancy.
 // Read-only: the kernels write the query's own buffers only (no tj_stats counter, no launch count).  No float atomics, no polling, no workgroup waits on another.
 #pragma once
 #include "kernels_pair_approach.h"
@@ -33,9 +35,6 @@
 namespace tj {
 
 constexpr int PX_THREADS = 64;    // one wave per pair
-constexpr int PX_OUT = 0, PX_IN = 1, PX_MIXED = 2;
-constexpr int PX_CERTAIN = TJ_PROXIMITY_CERTAIN, PX_UNCERTAIN = TJ_PROXIMITY_UNCERTAIN, PX_AT_START = TJ_PROXIMITY_AT_START, PX_AT_END = TJ_PROXIMITY_AT_END,
-              PX_RESOLVED = TJ_PROXIMITY_RESOLVED, PX_TRUNCATED = TJ_PROXIMITY_TRUNCATED;
 
 struct ProxSeed { double ca, cb, h0, h5; int tr, j, cls, pad; };   // a level-0 window of a listed pair that is not OUT
 struct ProxWin { double ca, cb, h0, h5; int tr, j; };              // a live (MIXED) window: [ca, cb] in segment tr of u and segment j of q (j == S: q hovers)
@@ -67,7 +66,7 @@ __device__ __forceinline__ double prox_ub(const double* cd) {
   for (int i = 0; i < 6; i++) m = fmax(m, norm3(cd[(3 * i) * ST], cd[(3 * i + 1) * ST], cd[(3 * i + 2) * ST]));
   return m;
 }
-__device__ __forceinline__ int prox_class(bool sep, double lo, double ub, double dist) { return sep && lo > dist ? PX_OUT : (ub <= dist ? PX_IN : PX_MIXED); }
+__device__ __forceinline__ int prox_class(bool sep, double lo, double ub, double dist) { return sep && lo > dist ? WIN_OUT : (ub <= dist ? WIN_IN : WIN_MIXED); }
 
 __global__ __launch_bounds__(64) void k_prox_mark(Dev D, ProxArgs A) {
   const int lane = lane_id(), S = D.S;
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(64) void k_prox_seed(Dev D, ProxArgs A) {
     if (slot >= A.ix.cap) return;
     atomicAdd(&A.count[2 * slot + 1], 1);
     const int cls = prox_class(sep, lo, prox_ub<64>(cd), dist);
-    if (cls != PX_OUT) bnb_keep(A.count[2 * slot], A.seeds + (size_t)slot * A.seed_cap, A.seed_cap, ProxSeed{ca, cb, h0, h5, tr, j, cls, 0});
+    if (cls != WIN_OUT) bnb_keep(A.count[2 * slot], A.seeds + (size_t)slot * A.seed_cap, A.seed_cap, ProxSeed{ca, cb, h0, h5, tr, j, cls, 0});
   });
 }
 
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(PX_THREADS) void k_prox_refine(Dev D, ProxArgs A) {
   // ---- the seeds: IN to the kept list (it holds every seed), MIXED to the live list ----
   for (int i = tid; i < ns; i += PX_THREADS) {
     const ProxSeed s = seeds[i];
-    if (s.cls == PX_IN) bnb_keep(s_kept, leaf, A.leaf_cap, ProxLeaf{s.ca, s.cb, s.h0, s.h5, 1, 0});
+    if (s.cls == WIN_IN) bnb_keep(s_kept, leaf, A.leaf_cap, ProxLeaf{s.ca, s.cb, s.h0, s.h5, 1, 0});
     else bnb_keep(s_live, cur, maxw, ProxWin{s.ca, s.cb, s.h0, s.h5, s.tr, s.j});
   }
   __syncthreads();
@@ -171,8 +170,8 @@ __global__ __launch_bounds__(PX_THREADS) void k_prox_refine(Dev D, ProxArgs A) {
       double h0, h5;
       const int cls = prox_eval(D, nu, ptu, nq, ptq, w.tr, w.j, ca, cb, dist, tp + tid, tq + tid, td + tid, h0, h5);
       atomicAdd(&s_ev, 1);
-      if (cls == PX_IN) bnb_keep(s_kept, leaf, maxw, ProxLeaf{ca, cb, h0, h5, 1, 0});
-      else if (cls == PX_MIXED) bnb_keep(s_live, nxt, maxw, ProxWin{ca, cb, h0, h5, w.tr, w.j});
+      if (cls == WIN_IN) bnb_keep(s_kept, leaf, maxw, ProxLeaf{ca, cb, h0, h5, 1, 0});
+      else if (cls == WIN_MIXED) bnb_keep(s_live, nxt, maxw, ProxWin{ca, cb, h0, h5, w.tr, w.j});
     }
     __syncthreads();   // the lists are written, the counters final
     const int k2 = s_kept, n2 = s_live;
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(PX_THREADS) void k_prox_refine(Dev D, ProxArgs A) {
     __syncthreads();
     for (int i = tid; i < ns; i += PX_THREADS) {
       const ProxSeed s = seeds[i];
-      if (s.cls == PX_MIXED) bnb_keep(s_kept, leaf, A.leaf_cap, ProxLeaf{s.ca, s.cb, s.h0, s.h5, 0, 0});
+      if (s.cls == WIN_MIXED) bnb_keep(s_kept, leaf, A.leaf_cap, ProxLeaf{s.ca, s.cb, s.h0, s.h5, 0, 0});
     }
     __syncthreads();
     kept = s_kept;
@@ -205,17 +204,8 @@ __global__ __launch_bounds__(PX_THREADS) void k_prox_refine(Dev D, ProxArgs A) {
   }
   const int m = kept;   // <= leaf_cap: at most 2 * max_windows from the rounds, at most seed_cap from the seeds alone
 
-  // ---- by ca: the keys are distinct, so a leaf's rank is the number of smaller keys ----
-  for (int i = tid; i < m; i += PX_THREADS) {
-    const ProxLeaf x = leaf[i];
-    int rank = 0;
-    for (int k = 0; k < m; k++) rank += leaf[k].ca < x.ca ? 1 : 0;
-    sorted[rank] = x;
-  }
-  __syncthreads();
-  int heads = 0;
-  for (int i = tid; i < m; i += PX_THREADS) heads += (i == 0 || sorted[i - 1].cb != sorted[i].ca) ? 1 : 0;
-  heads = wave_sum(heads);
+  // ---- by ca, and the chain heads: leaf 0 is one ----
+  const int heads = win_sort<&ProxLeaf::ca, &ProxLeaf::cb>(leaf, sorted, m) + (m > 0 ? 1 : 0);
   if (tid == 0) {
     A.info[4 * p] = heads; A.info[4 * p + 1] = m; A.info[4 * p + 2] = depth | (truncated ? 1 << 16 : 0);
     A.info[4 * p + 3] = A.count[2 * p + 1] + s_ev;   // the seeding's windows and the rounds'
@@ -227,48 +217,34 @@ __global__ __launch_bounds__(PX_THREADS) void k_prox_place(Dev D, ProxArgs A, tj
   const int p = blockIdx.x, lane = lane_id();
   const int np = min(*A.ix.n, A.ix.cap);
   if (p >= np) return;
-  int off = 0;
-  for (int k = lane; k < p; k += PX_THREADS) off += A.info[4 * k];
-  off = wave_sum(off);
+  int base = win_rows_before(A.info, 4, p);   // the pair's first row
   const int heads = A.info[4 * p], m = A.info[4 * p + 1], dt = A.info[4 * p + 2], windows = A.info[4 * p + 3];
-  if (p == np - 1 && lane == 0) *A.n_rows = off + heads;
+  if (p == np - 1 && lane == 0) *A.n_rows = base + heads;
   const int u = A.ix.who[2 * p], q = A.ix.who[2 * p + 1];
   const double dist = A.range, tol = A.tol;
   const double t_end = ((D.S - 1 + 1) / (double)D.res) * A.pt[u];   // the end of u's last segment, in the walk's expression
   const ProxLeaf* sorted = A.sorted + (size_t)p * A.leaf_cap;
-  int base = off;
   for (int i0 = 0; i0 < m; i0 += PX_THREADS) {
     const int i = i0 + lane;
-    const bool head = i < m && (i == 0 || sorted[i - 1].cb != sorted[i].ca);
-    const unsigned long long mask = __ballot(head);
-    const int r = base + __popcll(mask & ((1ull << lane) - 1ull));
-    base += __popcll(mask);
+    const bool head = win_head<&ProxLeaf::ca, &ProxLeaf::cb>(sorted, i, m, true);
+    const int r = win_row_index(head, base);
     if (!head || r >= A.row_cap) continue;
     // the chain from leaf i on, left to right
     tj_proximity_row row;
-    double first_hi = -1.0, last_lo = -1.0, within = 0.0, best = INFINITY, best_t = INFINITY, end = 0.0;
-    bool sure = false;
+    WinChain ch;
+    double end = 0.0;
     int k = i;
     for (;;) {
       const ProxLeaf x = sorted[k];
-      const bool s0 = x.in || x.h0 <= dist, s5 = x.in || x.h5 <= dist;
-      if (!sure && (s0 || s5)) { first_hi = s0 ? x.ca : x.cb; sure = true; }
-      if (s0) last_lo = x.ca;
-      if (s5) last_lo = x.cb;
-      if (x.in) within += x.cb - x.ca;
-      if (x.h0 < best || (x.h0 == best && x.ca < best_t)) { best = x.h0; best_t = x.ca; }
-      if (x.h5 < best || (x.h5 == best && x.cb < best_t)) { best = x.h5; best_t = x.cb; }
+      ch.add(dist, x.ca, x.cb, x.cb - x.ca, x.in, x.h0, x.h5);
       end = x.cb;
       k++;
       if (k >= m || sorted[k].ca != end) break;
     }
-    row.t_first_lo = sorted[i].ca; row.t_first_hi = first_hi; row.t_last_lo = last_lo; row.t_last_hi = end;
-    row.within_lo = within; row.closest = best; row.closest_time = best_t;
+    const double t0 = sorted[i].ca;
+    ch.finish(row, t0, end, t0 == 0.0, end == t_end, (dt >> 16) != 0, tol);
+    row.closest_time = ch.best_t;
     row.robot = u; row.partner = q; row.leaves = k - i; row.depth = dt & 0xffff; row.windows = windows;
-    const bool at_start = row.t_first_lo == 0.0, at_end = end == t_end;
-    int flags = (sure ? PX_CERTAIN : PX_UNCERTAIN) | (at_start ? PX_AT_START : 0) | (at_end ? PX_AT_END : 0) | (dt >> 16 ? PX_TRUNCATED : 0);
-    if (sure && (at_start || first_hi - row.t_first_lo <= tol) && (at_end || end - last_lo <= tol)) flags |= PX_RESOLVED;
-    row.flags = flags;
     out[r] = row;
   }
 }

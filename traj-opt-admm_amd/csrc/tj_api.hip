@@ -73,8 +73,8 @@ struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bo
 template <class Args, class Rec>
 struct Listed { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; Args sized{}; Rec* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
 
-// what a context holds for tj_proximity_windows (proximity_run): as Listed, with the row total; the sized buffers grow with the largest cap and max_windows so far
-struct ProxHeld { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullptr; int* n_rows = nullptr; ProxArgs sized{}; tj_proximity_row* out = nullptr; std::vector<void*> allocs; int cap = -1, mw = 0; };
+// what a context holds for tj_proximity_windows (proximity_run): as Listed, with the row total
+struct ProxHeld : Listed<ProxArgs, tj_proximity_row> { int* n_rows = nullptr; };
 
 // what a context holds for tj_obstacle_windows (obswin_run): the per-segment lists grow with the largest max_windows so far, the rows with the largest cap
 struct ObwinHeld { ObwinArgs sized{}; int* n_rows = nullptr; tj_obswin_row* out = nullptr; std::vector<void*> allocs, out_allocs; int mw = 0, cap = 0; };
@@ -1200,8 +1200,8 @@ double query_range(const Dev& d, double range) { return range > 0 ? range : d.of
 // (range, tol, max_depth, max_windows) of the four branch-and-bound queries, checked (NaN, then the limits) and defaulted in one place from one table: the call's
 // and its group call's name, the limits, the defaults, and the reason clause each limit's message ends on (the two row-listing queries size their lists by the call).
 // first_is_offset: the first argument is a contact distance and defaults to offset, not to the audit range; tol_fraction > 0: the default tolerance is that fraction of
-// the first argument over vel_limit (a time) instead of `tol`
-struct SearchSpec { const char* name; const char* group_name; int depth_limit, window_limit; double tol; int windows; const char* depth_why; const char* windows_why; bool first_is_offset = false; double tol_fraction = 0.0; };
+// the first argument over vel_limit (a time) instead of `tol`; inf_as_offset: of offset where the first argument is infinite (no time resolves 1 % of an infinite distance)
+struct SearchSpec { const char* name; const char* group_name; int depth_limit, window_limit; double tol; int windows; const char* depth_why; const char* windows_why; bool first_is_offset = false; double tol_fraction = 0.0; bool inf_as_offset = false; };
 const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approach", TJ_CLOSEST_MAX_DEPTH, TJ_CLOSEST_FRONTIER, TJ_CLOSEST_TOL, TJ_CLOSEST_FRONTIER,
                                 ": deeper windows cannot be halved in a double", ": the live list's capacity"},
                  SEARCH_PAIR{"tj_pair_approach", "tj_group_pair_approach", TJ_PAIR_MAX_DEPTH, TJ_PAIR_MAX_WINDOWS, TJ_PAIR_TOL, TJ_PAIR_FRONTIER,
@@ -1211,11 +1211,11 @@ const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approac
                  SEARCH_MARGIN{"tj_timing_margin", "tj_group_timing_margin", TJ_MARGIN_MAX_DEPTH, TJ_MARGIN_MAX_WINDOWS, 0.0, TJ_MARGIN_FRONTIER,
                                ": deeper windows cannot be halved in a double", "", true, TJ_MARGIN_TOL_FRACTION},
                  SEARCH_PROXIMITY{"tj_proximity_windows", "tj_group_proximity_windows", TJ_PROXIMITY_MAX_DEPTH, TJ_PROXIMITY_MAX_WINDOWS, 0.0, TJ_PROXIMITY_FRONTIER,
-                                  ": deeper windows cannot be halved in a double", "", true, TJ_PROXIMITY_TOL_FRACTION},
+                                  ": deeper windows cannot be halved in a double", "", true, TJ_PROXIMITY_TOL_FRACTION, true},
                  SEARCH_OBSTACLE{"tj_obstacle_approach", "tj_group_obstacle_approach", TJ_OBSTACLE_MAX_DEPTH, TJ_OBSTACLE_FRONTIER, TJ_OBSTACLE_TOL, TJ_OBSTACLE_FRONTIER,
                                  ": deeper windows are not dyadic in a double", ": the live list's capacity"},
                  SEARCH_OBSWIN{"tj_obstacle_windows", "tj_group_obstacle_windows", TJ_OBSWIN_MAX_DEPTH, TJ_OBSWIN_MAX_WINDOWS, 0.0, TJ_OBSWIN_FRONTIER,
-                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_OBSWIN_TOL_FRACTION};
+                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_OBSWIN_TOL_FRACTION, true};
 struct SearchArgs {
   double range, tol; int max_depth, max_windows;
   template <class Args> void put(Args& a) const { a.range = range; a.tol = tol; a.max_depth = max_depth; a.max_windows = max_windows; }
@@ -1229,7 +1229,7 @@ int search_args(tj_ctx* c, const SearchSpec& q, double range, double tol, int ma
     return TJ_ERR_INVALID;
   }
   const double first = q.first_is_offset ? (range > 0 ? range : c->d.offset) : query_range(c->d, range);
-  a = SearchArgs{first, tol < 0 ? (q.tol_fraction > 0 ? (q.tol_fraction * first) / c->d.vel_limit : q.tol) : tol, max_depth < 0 ? q.depth_limit : max_depth, max_windows <= 0 ? q.windows : max_windows};
+  a = SearchArgs{first, tol < 0 ? (q.tol_fraction > 0 ? (q.tol_fraction * (q.inf_as_offset && first == INFINITY ? c->d.offset : first)) / c->d.vel_limit : q.tol) : tol, max_depth < 0 ? q.depth_limit : max_depth, max_windows <= 0 ? q.windows : max_windows};
   return TJ_OK;
 }
 // sorted primitive -> index in the caller's obstacle list, made by whichever query needs it first
@@ -1263,6 +1263,54 @@ int query_finish(tj_ctx* c, const char* walk) {
   if (walk) HIPCHK(c, hipMemcpyAsync(&err, &c->q_ctl->error, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (err & ERR_FRONT_OVERFLOW) { c->err = std::string(walk) + ": the BVH frontier of a segment overflowed at this range (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one hull): lower `range`"; return TJ_ERR_CAPACITY; }
+  return TJ_OK;
+}
+
+// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, profile_run) ----
+// the refusal of a call whose buffers would exceed its query's byte budget, up front, nothing allocated.  what: the call's sizes in its words; advice: what to lower
+int query_budget(tj_ctx* c, const std::string& what, size_t bytes, const char* budget, long long max_bytes, const char* advice) {
+  if (bytes <= (size_t)max_bytes) return TJ_OK;
+  c->err = what + " need " + std::to_string(bytes) + " bytes of device memory, more than " + budget + " (" + std::to_string(max_bytes) + "): " + advice;
+  return TJ_ERR_INVALID;
+}
+// grow the buffers on `list`: the context is quiet, nothing reads the old ones.  They are freed, reset() puts the holder back to "nothing held" -- a failure keeps what
+// it got on the list and starts over next time -- and alloc() -> rc allocates at the new sizes, which the caller records once this returns TJ_OK
+template <class Reset, class Alloc>
+int query_grow(std::vector<void*>& list, Reset&& reset, Alloc&& alloc) {
+  for (void* p : list) hipFree(p);
+  list.clear();
+  reset();
+  return alloc();
+}
+// the same for a Listed: grown to the largest cap and max_windows so far; alloc(sized, gc, gm, list) -> rc allocates everything but the rows
+template <class Held, class Alloc>
+int listed_grow(tj_ctx* c, Held& h, int cap, int mw, Alloc&& alloc) {
+  if (cap <= h.cap && mw <= h.mw) return TJ_OK;
+  const int gc = std::max(cap, h.cap), gm = std::max(mw, h.mw);
+  const int r = query_grow(h.allocs, [&] { h.sized = {}; h.out = nullptr; h.cap = -1; h.mw = 0; }, [&] { const int e = alloc(h.sized, gc, gm, &h.allocs); return e ? e : query_buf(c, h.out, gc, &h.allocs); });
+  if (!r) { h.cap = gc; h.mw = gm; }
+  return r;
+}
+// the pair index of a call (kernels_pair_approach.h): the bitmask, its offsets and n are the fleet's size (allocated once) and cleared; ix gets their fields and the call's slots
+template <class Held>
+int pair_index_begin(tj_ctx* c, Held& h, int cap, PairIndex& ix) {
+  const Dev& d = c->d;
+  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
+  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
+  int r;
+  if ((r = query_buf(c, h.mask, mask_n)) || (r = query_buf(c, h.wordoff, mask_n)) || (r = query_buf(c, h.n, 1))) return r;
+  ix.cap = cap; ix.words = words; ix.mask = h.mask; ix.wordoff = h.wordoff; ix.n = h.n;
+  return (r = query_clear(c, h.mask, mask_n)) ? r : query_clear(c, h.n, 1);
+}
+// behind a query's marking launch: pair p is the p-th set bit
+void pair_index_launch(tj_ctx* c, const PairIndex& ix) { hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, c->d, ix); }
+// the end of a row-listing call whose total is known: min(cap, total) rows to the caller, then the capacity error in the call's words (what: "pairs are listed, the
+// caller's rows hold" or "rows, the caller's hold").  silent: a count-only call, to which more rows than room are no error
+template <class Rec>
+int rows_finish(tj_ctx* c, const std::string& name, Rec* rows, const Rec* dev, int cap, int total, const char* what, bool silent) {
+  int r;
+  if (std::min(cap, total) > 0 && ((r = query_fetch(c, rows, dev, std::min(cap, total))) || (r = query_finish(c, nullptr)))) return r;
+  if (total > cap && !silent) { c->err = name + ": " + std::to_string(total) + " " + what + " " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
   return TJ_OK;
 }
 
@@ -1386,7 +1434,8 @@ struct CrossQuery {
   static constexpr long long max_bytes = TJ_CROSSING_MAX_BYTES;
   static auto& held(tj_ctx* c) { return c->cross; }
   static size_t bytes(const Dev&, int cap, int mw) { return (size_t)cap * ((size_t)2 * mw * sizeof(CrossItem) + (size_t)4 * mw * sizeof(double) + 2 * sizeof(int) + sizeof(tj_crossing_record)); }
-  static int alloc(tj_ctx* c, Args& b, int gc, int gm, std::vector<void*>* l) {
+  template <class A>   // (MarginQuery's lists are the same)
+  static int alloc(tj_ctx* c, A& b, int gc, int gm, std::vector<void*>* l) {
     int r;
     if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l))) return r;
     return TJ_OK;
@@ -1406,11 +1455,7 @@ struct MarginQuery {
   static constexpr long long max_bytes = TJ_MARGIN_MAX_BYTES;
   static auto& held(tj_ctx* c) { return c->margin; }
   static size_t bytes(const Dev&, int cap, int mw) { return (size_t)cap * ((size_t)2 * mw * sizeof(CrossItem) + (size_t)4 * mw * sizeof(double) + 2 * sizeof(int) + sizeof(tj_margin_record)); }
-  static int alloc(tj_ctx* c, Args& b, int gc, int gm, std::vector<void*>* l) {
-    int r;
-    if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.klo, (size_t)gc * 4 * gm, l))) return r;
-    return TJ_OK;
-  }
+  static int alloc(tj_ctx* c, Args& b, int gc, int gm, std::vector<void*>* l) { return CrossQuery::alloc(c, b, gc, gm, l); }   // (the same lists)
   static int extra(tj_ctx* c, Args& a, double max_slip) {
     const int r = query_nan(c, spec.name, "max_slip", max_slip);
     a.max_slip = max_slip > 0 ? max_slip : INFINITY;
@@ -1434,42 +1479,27 @@ int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windo
   if ((r = Q::extra(c, own, extra)) || (r = search_args(c, Q::spec, range, tol, max_depth, max_windows, sa))) return r;
   const Dev& d = c->d;
   const int mw = sa.max_windows;
-  if (Q::bytes(d, cap, mw) > (size_t)Q::max_bytes) {
-    c->err = name + ": cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw) + " need " + std::to_string(Q::bytes(d, cap, mw)) + " bytes of device memory, more than " + Q::budget + " (" +
-             std::to_string(Q::max_bytes) + "): lower cap (rows beyond it are still counted) or max_windows";
-    return TJ_ERR_INVALID;
-  }
-  if ((r = query_state(c, Q::spec.name, true, net_host && pt_host))) return r;
+  if ((r = query_budget(c, name + ": cap " + std::to_string(cap) + " rows at max_windows " + std::to_string(mw), Q::bytes(d, cap, mw), Q::budget, Q::max_bytes,
+                        "lower cap (rows beyond it are still counted) or max_windows")) ||
+      (r = query_state(c, Q::spec.name, true, net_host && pt_host))) return r;
   *n = 0;
   if (!d.multi()) return TJ_OK;   // one UAV: no pair
-  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
-  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
+  const int owned = d.u1 - d.u0;
   QUIESCE(c);
   auto& h = Q::held(c);
-  if ((r = query_buf(c, h.mask, mask_n)) || (r = query_buf(c, h.wordoff, mask_n)) || (r = query_buf(c, h.n, 1))) return r;
-  if (cap > h.cap || mw > h.mw) {   // grow: the context is quiet, nothing reads the old buffers; a failure keeps what it got on the list and starts over next time
-    for (void* p : h.allocs) hipFree(p);
-    h.allocs.clear();
-    const int gc = std::max(cap, h.cap), gm = std::max(mw, h.mw);
-    h.sized = typename Q::Args{}; h.out = nullptr; h.cap = -1; h.mw = 0;
-    if ((r = Q::alloc(c, h.sized, gc, gm, &h.allocs)) || (r = query_buf(c, h.out, gc, &h.allocs))) return r;
-    h.cap = gc; h.mw = gm;
-  }
+  if ((r = listed_grow(c, h, cap, mw, [&](typename Q::Args& b, int gc, int gm, std::vector<void*>* l) { return Q::alloc(c, b, gc, gm, l); }))) return r;
   typename Q::Args a = h.sized;
   if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
   sa.put(a);
   Q::extra(c, a, extra);
-  a.ix.cap = cap; a.ix.words = words; a.ix.mask = h.mask; a.ix.wordoff = h.wordoff; a.ix.n = h.n;
-  if ((r = query_clear(c, h.mask, mask_n)) || (r = query_clear(c, h.n, 1)) || (r = Q::prepare(c, a))) return r;
+  if ((r = pair_index_begin(c, h, cap, a.ix)) || (r = Q::prepare(c, a))) return r;
   if (owned > 0) {
     Q::mark(c, a, owned * d.S);
-    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, a.ix);
+    pair_index_launch(c, a.ix);
     if (cap > 0) Q::rows(c, a, owned * d.S, h.out);
   }
   if ((r = query_fetch(c, n, h.n, 1)) || (r = query_finish(c, nullptr))) return r;
-  if ((r = query_fetch(c, rows, h.out, std::min(cap, *n))) || (r = query_finish(c, nullptr))) return r;
-  if (*n > cap && rows) { c->err = name + ": " + std::to_string(*n) + " pairs are listed, the caller's rows hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
-  return TJ_OK;
+  return rows_finish(c, name, rows, h.out, cap, *n, "pairs are listed, the caller's rows hold", !rows);
 }
 
 // tj_proximity_windows (kernels_proximity.h): the rows of the directed pairs (u, q), u owned.  pair_cap: the slots of listed pairs, row_cap <= pair_cap: the caller's
@@ -1488,44 +1518,31 @@ int proximity_run(tj_ctx* c, double dist, double tol, int max_depth, int max_win
   SearchArgs sa;
   if ((r = search_args(c, spec, dist, tol, max_depth, max_windows, sa))) return r;
   const Dev& d = c->d;
-  if (tol < 0 && sa.range == INFINITY) sa.tol = (spec.tol_fraction * d.offset) / d.vel_limit;   // (no time resolves 1 % of an infinite distance: offset's)
   const int mw = sa.max_windows, cap = pair_cap;
-  if (proximity_bytes(d, cap, mw) > (size_t)TJ_PROXIMITY_MAX_BYTES) {
-    c->err = name + ": cap " + std::to_string(cap) + " pairs at max_windows " + std::to_string(mw) + " need " + std::to_string(proximity_bytes(d, cap, mw)) +
-             " bytes of device memory, more than TJ_PROXIMITY_MAX_BYTES (" + std::to_string(TJ_PROXIMITY_MAX_BYTES) + "): lower cap or max_windows";
-    return TJ_ERR_INVALID;
-  }
-  if ((r = query_state(c, spec.name, true, net_host && pt_host))) return r;
+  if ((r = query_budget(c, name + ": cap " + std::to_string(cap) + " pairs at max_windows " + std::to_string(mw), proximity_bytes(d, cap, mw), "TJ_PROXIMITY_MAX_BYTES", TJ_PROXIMITY_MAX_BYTES,
+                        "lower cap or max_windows")) ||
+      (r = query_state(c, spec.name, true, net_host && pt_host))) return r;
   *n_pairs = 0; *n = 0;
   if (!d.multi()) return TJ_OK;   // one UAV: no pair
-  const int owned = d.u1 - d.u0, words = (d.U + 31) / 32;
-  const size_t mask_n = (size_t)(owned > 0 ? owned : 1) * words;
+  const int owned = d.u1 - d.u0, seed_cap = 2 * d.S + 2;
   QUIESCE(c);
   ProxHeld& h = c->prox;
-  if ((r = query_buf(c, h.mask, mask_n)) || (r = query_buf(c, h.wordoff, mask_n)) || (r = query_buf(c, h.n, 1)) || (r = query_buf(c, h.n_rows, 1))) return r;
-  const int seed_cap = 2 * d.S + 2;
-  if (cap > h.cap || mw > h.mw) {   // grow: the context is quiet, nothing reads the old buffers; a failure keeps what it got on the list and starts over next time
-    for (void* p : h.allocs) hipFree(p);
-    h.allocs.clear();
-    const int gc = std::max(cap, h.cap), gm = std::max(mw, h.mw);
-    h.sized = ProxArgs{}; h.out = nullptr; h.cap = -1; h.mw = 0;
-    ProxArgs& b = h.sized;
-    std::vector<void*>* l = &h.allocs;
-    const size_t leaves = (size_t)gc * ((size_t)2 * gm + seed_cap);
-    if ((r = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (r = query_buf(c, b.count, (size_t)gc * 2, l)) || (r = query_buf(c, b.seeds, (size_t)gc * seed_cap, l)) ||
-        (r = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (r = query_buf(c, b.leaf, leaves, l)) || (r = query_buf(c, b.sorted, leaves, l)) ||
-        (r = query_buf(c, b.info, (size_t)gc * 4, l)) || (r = query_buf(c, h.out, gc, l))) return r;
-    h.cap = gc; h.mw = gm;
-  }
+  if ((r = query_buf(c, h.n_rows, 1)) ||
+      (r = listed_grow(c, h, cap, mw, [&](ProxArgs& b, int gc, int gm, std::vector<void*>* l) {
+         const size_t leaves = (size_t)gc * ((size_t)2 * gm + seed_cap);
+         int e;   // (the first failure, or TJ_OK)
+         (e = query_buf(c, b.ix.who, (size_t)gc * 2, l)) || (e = query_buf(c, b.count, (size_t)gc * 2, l)) || (e = query_buf(c, b.seeds, (size_t)gc * seed_cap, l)) ||
+             (e = query_buf(c, b.list, (size_t)gc * 2 * gm, l)) || (e = query_buf(c, b.leaf, leaves, l)) || (e = query_buf(c, b.sorted, leaves, l)) || (e = query_buf(c, b.info, (size_t)gc * 4, l));
+         return e;
+       }))) return r;
   ProxArgs a = h.sized;
   if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt))) return r;
   sa.put(a);
   a.seed_cap = seed_cap; a.leaf_cap = 2 * mw + seed_cap; a.row_cap = row_cap; a.n_rows = h.n_rows;
-  a.ix.cap = cap; a.ix.words = words; a.ix.mask = h.mask; a.ix.wordoff = h.wordoff; a.ix.n = h.n;
-  if ((r = query_clear(c, h.mask, mask_n)) || (r = query_clear(c, h.n, 1)) || (r = query_clear(c, h.n_rows, 1)) || (r = query_clear(c, a.count, (size_t)cap * 2, cap > 0))) return r;
+  if ((r = pair_index_begin(c, h, cap, a.ix)) || (r = query_clear(c, h.n_rows, 1)) || (r = query_clear(c, a.count, (size_t)cap * 2, cap > 0))) return r;
   if (owned > 0) {
     hipLaunchKernelGGL(k_prox_mark, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
-    hipLaunchKernelGGL(k_pair_index, dim3(1), dim3(PA_INDEX), 0, c->stream, d, a.ix);
+    pair_index_launch(c, a.ix);
     if (cap > 0) {
       hipLaunchKernelGGL(k_prox_seed, dim3(owned * d.S), dim3(64), 0, c->stream, d, a);
       hipLaunchKernelGGL(k_prox_refine, dim3(cap), dim3(PX_THREADS), 0, c->stream, d, a);
@@ -1542,9 +1559,7 @@ int proximity_run(tj_ctx* c, double dist, double tol, int max_depth, int max_win
     return TJ_ERR_CAPACITY;
   }
   *n = nr;
-  if ((r = query_fetch(c, rows, h.out, std::min(row_cap, nr))) || (r = query_finish(c, nullptr))) return r;
-  if (nr > row_cap) { c->err = name + ": " + std::to_string(nr) + " rows, the caller's hold " + std::to_string(row_cap) + ": the first " + std::to_string(row_cap) + " were written"; return TJ_ERR_CAPACITY; }
-  return TJ_OK;
+  return rows_finish(c, name, rows, h.out, row_cap, nr, "rows, the caller's hold", false);
 }
 
 // tj_obstacle_windows (kernels_obstacle_windows.h): the rows of the owned robots from the context's own state (nothing of another robot is read, so a sharded context
@@ -1561,31 +1576,22 @@ int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_window
   SearchArgs sa;
   if ((r = search_args(c, spec, dist, tol, max_depth, max_windows, sa))) return r;
   const Dev& d = c->d;
-  if (tol < 0 && sa.range == INFINITY) sa.tol = (spec.tol_fraction * d.offset) / d.vel_limit;   // (no time resolves 1 % of an infinite distance: offset's)
   const int mw = sa.max_windows, owned = d.u1 - d.u0;
-  if (obswin_bytes(d, owned, cap, mw) > (size_t)TJ_OBSWIN_MAX_BYTES) {
-    c->err = name + ": " + std::to_string(owned) + " robots of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap) + " need " +
-             std::to_string(obswin_bytes(d, owned, cap, mw)) + " bytes of device memory, more than TJ_OBSWIN_MAX_BYTES (" + std::to_string(TJ_OBSWIN_MAX_BYTES) + "): lower max_windows or cap";
-    return TJ_ERR_INVALID;
-  }
-  if ((r = query_state(c, spec.name, false, false))) return r;
+  if ((r = query_budget(c, name + ": " + std::to_string(owned) + " robots of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
+                        obswin_bytes(d, owned, cap, mw), "TJ_OBSWIN_MAX_BYTES", TJ_OBSWIN_MAX_BYTES, "lower max_windows or cap")) ||
+      (r = query_state(c, spec.name, false, false))) return r;
   if (d.N == 0 || owned <= 0) { *n = 0; return TJ_OK; }   // no obstacles: nothing is within any distance of them
   QUIESCE(c);
   ObwinHeld& h = c->obwin;
   const size_t units = (size_t)owned * d.S;
   if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.sized.info, units * 4)) || (r = query_buf(c, h.sized.robot, (size_t)owned * 2)) || (r = ensure_order(c))) return r;
-  if (mw > h.mw) {   // grow: the context is quiet, nothing reads the old buffers; a failure keeps what it got on the list and starts over next time
-    for (void* p : h.allocs) hipFree(p);
-    h.allocs.clear();
-    h.sized.list = nullptr; h.sized.leaf = nullptr; h.mw = 0;
-    if ((r = query_buf(c, h.sized.list, units * 2 * mw, &h.allocs)) || (r = query_buf(c, h.sized.leaf, units * 2 * mw, &h.allocs))) return r;
+  if (mw > h.mw) {
+    if ((r = query_grow(h.allocs, [&] { h.sized.list = nullptr; h.sized.leaf = nullptr; h.mw = 0; },
+                        [&] { const int e = query_buf(c, h.sized.list, units * 2 * mw, &h.allocs); return e ? e : query_buf(c, h.sized.leaf, units * 2 * mw, &h.allocs); }))) return r;
     h.mw = mw;
   }
   if (cap > h.cap) {
-    for (void* p : h.out_allocs) hipFree(p);
-    h.out_allocs.clear();
-    h.out = nullptr; h.cap = 0;
-    if ((r = query_buf(c, h.out, cap, &h.out_allocs))) return r;
+    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
     h.cap = cap;
   }
   ObwinArgs a = h.sized;
@@ -1603,9 +1609,7 @@ int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_window
     return r;
   }
   *n = nr;
-  if (std::min(cap, nr) > 0 && ((r = query_fetch(c, rows, h.out, std::min(cap, nr))) || (r = query_finish(c, nullptr)))) return r;
-  if (nr > cap && !(cap == 0 && !rows)) { c->err = name + ": " + std::to_string(nr) + " rows, the caller's hold " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
-  return TJ_OK;
+  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
 }
 
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
@@ -1624,12 +1628,13 @@ int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_h
   const size_t recs = (size_t)d.U * K;
   QUIESCE(c);
   ProfileArgs& b = c->profile;
-  if (K > c->profile_cap) {   // grow: the context is quiet, nothing reads the old buffers
-    for (void* p : c->profile_allocs) hipFree(p);
-    c->profile_allocs.clear();
-    b.times = nullptr; b.pos = nullptr; c->profile_out = nullptr; c->profile_cap = 0;
+  if (K > c->profile_cap) {
     std::vector<void*>* l = &c->profile_allocs;
-    if ((r = query_buf(c, b.times, (size_t)K, l)) || (r = query_buf(c, b.pos, recs * 3, l)) || (r = query_buf(c, c->profile_out, recs, l))) return r;
+    if ((r = query_grow(*l, [&] { b.times = nullptr; b.pos = nullptr; c->profile_out = nullptr; c->profile_cap = 0; }, [&] {
+           int e;   // (the first failure, or TJ_OK)
+           (e = query_buf(c, b.times, (size_t)K, l)) || (e = query_buf(c, b.pos, recs * 3, l)) || (e = query_buf(c, c->profile_out, recs, l));
+           return e;
+         }))) return r;
     c->profile_cap = K;
   }
   if ((r = ensure_order(c))) return r;

@@ -644,19 +644,30 @@ int group_query(tj_group* g, bool nets, bool pts, Rec* out, GroupRows rows0, Gro
 // a scratch copy of a per-segment array the caller asked for (null: not asked for, nothing to scatter)
 static std::vector<double> group_rows(const tj_group* g, const double* wanted) { return std::vector<double>(g && wanted ? (size_t)g->ctx[0]->d.U * g->ctx[0]->d.S : 0); }
 
-// gather: the rows of a row-listing query (listed_run), rank after rank
-template <class Q>
-int group_listed(tj_group* g, double range, double tol, int max_depth, int max_windows, double extra, typename Q::Rec* rows, int cap, int* n) {
-  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
-  int total = 0;
-  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
-    const int room = std::max(0, cap - total);
+// gather: the rows of a row-listing query, rank after rank.  run(ctx, net, pt, rows or null, room, &count) -> rc is the rank's call with what is left of the caller's rows; it
+// leaves in count the rank's rows (negative: not known).  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.
+// Only THAT capacity error is carried on (the rank set its count above the room it was given, or below zero); any other error ends the group's call with the rank's code.
+// state: the ranks read other robots, so the owners' nets and piece times are handed in.  total: the rows of all ranks; unknown: some rank could not count its rows.
+template <class Rec, class Run>
+int group_gather(tj_group* g, bool state, Rec* rows, int cap, int& total, bool& unknown, Run&& run) {
+  if (!g || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  total = 0; unknown = false;
+  return group_each(g, state, state, [&](int, tj_ctx* c, const double* net, const double* pt) {
+    const int room = unknown ? 0 : std::max(0, cap - total);
     int nr = 0;
-    const int e = listed_run<Q>(c, range, tol, max_depth, max_windows, extra, net, pt, room ? rows + total : nullptr, room, &nr);
-    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
-    total += nr;
+    const int e = run(c, net, pt, room ? rows + total : nullptr, room, &nr);
+    if (e < 0 && !(e == TJ_ERR_CAPACITY && (nr > room || nr < 0))) return e;
+    if (nr < 0) unknown = true; else total += nr;
     return (int)TJ_OK;
   });
+}
+// the rows of a query of listed_run
+template <class Q>
+int group_listed(tj_group* g, double range, double tol, int max_depth, int max_windows, double extra, typename Q::Rec* rows, int cap, int* n) {
+  if (!n) return TJ_ERR_INVALID;
+  int total; bool unknown;
+  const int rc = group_gather(g, true, rows, cap, total, unknown, [&](tj_ctx* c, const double* net, const double* pt, typename Q::Rec* out, int room, int* nr) {
+    return listed_run<Q>(c, range, tol, max_depth, max_windows, extra, net, pt, out, room, nr); });
   if (rc < 0) return rc;
   *n = total;
   if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, std::string(Q::spec.group_name) + ": " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
@@ -684,31 +695,20 @@ int tj_group_closest_approach(tj_group* g, double range, double tol, int max_dep
 
 // the ranks' lists one after the other: ownership is by contiguous robot blocks in rank order, so that is the (robot, partner) order (tj_path_crossings: the rows
 // (u, q > u) by u's owner).  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.
-int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) {
-  return group_listed<PairQuery>(g, range, tol, max_depth, max_windows, 0.0, rows, cap, n);
-}
-int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) {
-  return group_listed<CrossQuery>(g, range, tol, max_depth, max_windows, 0.0, rows, cap, n);
-}
-int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n) {
-  return group_listed<MarginQuery>(g, dist, tol, max_depth, max_windows, max_slip, rows, cap, n);
-}
+int tj_group_pair_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_pair_record* rows, int cap, int* n) { return group_listed<PairQuery>(g, range, tol, max_depth, max_windows, 0.0, rows, cap, n); }
+int tj_group_path_crossings(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_crossing_record* rows, int cap, int* n) { return group_listed<CrossQuery>(g, range, tol, max_depth, max_windows, 0.0, rows, cap, n); }
+int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol, int max_depth, int max_windows, tj_margin_record* rows, int cap, int* n) { return group_listed<MarginQuery>(g, dist, tol, max_depth, max_windows, max_slip, rows, cap, n); }
 
 // tj_proximity_windows, rank after rank: every rank gets the whole `cap` in pair slots and what is left of it in rows.  More pairs than `cap` over the ranks together, as
 // one context counts them: *n = -1.  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.
 int tj_group_proximity_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n) {
-  if (!g || !n || !n_pairs || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
-  int pairs = 0, total = 0;
-  bool unknown = false;
-  const int rc = group_each(g, true, true, [&](int, tj_ctx* c, const double* net, const double* pt) {
-    const int room = unknown ? 0 : std::max(0, cap - total);
-    int np = 0, nr = 0;
-    const int e = proximity_run(c, dist, tol, max_depth, max_windows, net, pt, room ? rows + total : nullptr, cap, room, &np, &nr);
-    if (e < 0 && e != TJ_ERR_CAPACITY) return e;
+  if (!n || !n_pairs) return TJ_ERR_INVALID;
+  int pairs = 0, total; bool unknown;
+  const int rc = group_gather(g, true, rows, cap, total, unknown, [&](tj_ctx* c, const double* net, const double* pt, tj_proximity_row* out, int room, int* nr) {
+    int np = 0;
+    const int e = proximity_run(c, dist, tol, max_depth, max_windows, net, pt, out, cap, room, &np, nr);
     pairs += np;
-    if (nr < 0) unknown = true; else total += nr;
-    return (int)TJ_OK;
-  });
+    return e; });
   if (rc < 0) return rc;
   *n_pairs = pairs;
   *n = unknown || pairs > cap ? -1 : total;
@@ -725,19 +725,13 @@ int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_de
 }
 
 // tj_obstacle_windows, rank after rank, each from its own state (ownership is by contiguous robot blocks in rank order: that is the (robot, t_first_lo) order).  A rank
-// whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count.  Only THAT capacity error is carried on (obswin_run set its
-// count above the room it was given); a walk frontier overflow leaves the count untouched and ends the group's call with the rank's TJ_ERR_CAPACITY, *n untouched.
+// whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count (group_gather).  A walk frontier overflow leaves the rank's
+// count untouched and so ends the group's call with the rank's TJ_ERR_CAPACITY, *n untouched.
 int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) {
-  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
-  int total = 0;
-  const int rc = group_each(g, false, false, [&](int, tj_ctx* c, const double*, const double*) {
-    const int room = std::max(0, cap - total);
-    int nr = 0;
-    const int e = obswin_run(c, dist, tol, max_depth, max_windows, room ? rows + total : nullptr, room, &nr);
-    if (e < 0 && !(e == TJ_ERR_CAPACITY && nr > room)) return e;
-    total += nr;
-    return (int)TJ_OK;
-  });
+  if (!n) return TJ_ERR_INVALID;
+  int total; bool unknown;
+  const int rc = group_gather(g, false, rows, cap, total, unknown, [&](tj_ctx* c, const double*, const double*, tj_obswin_row* out, int room, int* nr) {
+    return obswin_run(c, dist, tol, max_depth, max_windows, out, room, nr); });
   if (rc < 0) return rc;
   *n = total;
   if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_obstacle_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));

@@ -11,6 +11,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 pkg = importlib.import_module("traj-opt-admm_amd")
 from conftest import canon  # noqa: E402
 from oracle.pyoracle import Engine  # noqa: E402
+from query_kit import STATE  # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "hard"
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 6
@@ -18,7 +19,6 @@ sc = {"hard": lambda: pkg.scenes.hard(4, 4000), "scn_b": pkg.scenes.scn_b, "tiny
 o = Engine("port", sc); o.set_optimal_plane(True)
 s = pkg.Solver(sc, stop=0.0, optimal_plane=1)
 free = pkg.Solver(sc, stop=0.0, optimal_plane=1)
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 for it in range(iters):
     s.set_state(o.get_state()); s.set_pair_cache(*o.get_pair_cache())
     cd, pd = s.stage_planes()

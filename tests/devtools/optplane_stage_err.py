@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 pkg = importlib.import_module("traj-opt-admm_amd")
 import test_gpu_optplane as T
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
+from query_kit import STATE
 for name in ("tiny_multi", "tiny_multi_coupled"):
     g = np.load(os.path.join(ROOT, "tests", "golden", f"optplane_stages_{name}.npz"))
     scene = T._scene(pkg.scenes, name)

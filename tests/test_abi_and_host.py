@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from query_kit import reference_config
 
 
 def _header_functions(name="trajadmm.h"):
@@ -110,9 +111,7 @@ def test_cli_usage_and_config_errors(name, tmp_path):
     (tmp_path / "Config_File" / "3D.json").write_text('{"auto":0,"init":1,"gui":0}')
     r = subprocess.run([exe, "x.obj"], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 1 and "missing key" in r.stderr             # all 16 keys are mandatory
-    shipped = '{"auto":0,"init":1,"gui":1,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,' \
-              '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}'
-    (tmp_path / "Config_File" / "3D.json").write_text(shipped)
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config(gui=1))   # the shipped file
     r = subprocess.run([exe, "x.obj"], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 1 and "gui:1" in r.stderr                   # unsupported branch is rejected, not ignored
 

@@ -19,14 +19,10 @@ import audit_ref as R
 import audit_timed_ref as T
 import closest_ref as K
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 OFFSET = 0.1
 STATES = ["chase", "crossing", "hover", "hard"]
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

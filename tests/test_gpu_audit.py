@@ -6,20 +6,17 @@ every other robot -- no box filter, nothing sampled (tests/test_audit_ref.py sho
 limits are compared with == on the doubles: same inputs, same expressions (no FMA contraction on either side).  The truth tests compare with an
 exact distance that shares nothing with GJK, at the bars measured in tests/test_audit_ref.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import audit_ref as R
-from conftest import ROOT
 from audit_ref import brute_obs, brute_pair, hulls_of, limits_of, norm3, prims, robot_min
 from test_audit_ref import GJK_BAR
+from query_kit import STATE, CliCase, assert_group_equals, assert_read_only, close_to_six_digits, group_pair, one_queue, raw_context
 from test_oracle_params import PARAM_SETS
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 DEFAULT_RANGE = 0.1 + 2 * 0.1   # offset + 2 * margin at the shipped values, in the library's association (0.30000000000000004)
 
 
@@ -127,45 +124,15 @@ def test_start_in_collision_is_reported(pkg, scenes):
 @pytest.mark.parametrize("queues", ["default", "one"])
 def test_audit_is_read_only(pkg, scenes, monkeypatch, queues):
     if queues == "one":
-        monkeypatch.setenv("TJ_XS_ASYNC", "0"); monkeypatch.setenv("TJ_FRONT_ASYNC", "0")
-    scene = scenes.hard()
-
-    def run(audited):   # one context at a time: a second live context may find the process's hardware-queue budget taken and keep the one-queue chain (tj_create)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the audit drains the queues itself
-                s.iterate_async(2)
-                if audited:
-                    s.audit(range=1.0, per_segment=True)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if audited:
-                    s.audit(); s.audit(range=1.0)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.close()
-        return out
-
-    (sa, ta, la), (sb, tb, lb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-    assert ta == tb
-    assert la == lb
+        one_queue(monkeypatch)
+    assert_read_only(pkg, scenes.hard(), lambda s: s.audit(range=1.0, per_segment=True), lambda s: (s.audit(), s.audit(range=1.0)))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 def test_sharded_audit_equals_one_context(pkg, scenes, mode):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0, 0], stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for rng in (None, 1.0):
-            x, y = one.audit(range=rng, per_segment=True), grp.audit(range=rng, per_segment=True)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, rng, k)
+    one, grp = group_pair(pkg, scene, 2)
+    assert_group_equals(one, grp, lambda s, rng: s.audit(range=rng, per_segment=True), ((None,), (1.0,)))
     grp.close(); one.close()
     one = pkg.Solver(scene, stop=0.0)   # (a fresh one: the sharded context below is at the initial state)
     half = pkg.Solver(scene, stop=0.0, rank=1, world=2)   # a sharded context reports its own robots and zeroes the others
@@ -176,20 +143,14 @@ def test_sharded_audit_equals_one_context(pkg, scenes, mode):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec = (pkg.TjAuditRobot * 3)()
-    assert lib.tj_audit(ctx, C.c_double(0.0), rec, None, None) == -1          # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    assert lib.tj_audit(ctx, C.c_double(0.0), None, None, None) == -1         # NULL out
-    assert lib.tj_audit(ctx, C.c_double(0.0), rec, None, None) == 0           # no obstacles set: valid, nothing within range
-    assert all(r.obs_index == -1 and abs(r.obs_clearance - 0.3) < 1e-15 for r in rec)
-    assert lib.tj_audit(None, C.c_double(0.0), rec, None, None) == -1
-    lib.tj_destroy(ctx)
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec = (pkg.TjAuditRobot * 3)()
+        assert lib.tj_audit(ctx, C.c_double(0.0), rec, None, None) == -1          # before tj_init_state
+        init()
+        assert lib.tj_audit(ctx, C.c_double(0.0), None, None, None) == -1         # NULL out
+        assert lib.tj_audit(ctx, C.c_double(0.0), rec, None, None) == 0           # no obstacles set: valid, nothing within range
+        assert all(r.obs_index == -1 and abs(r.obs_clearance - 0.3) < 1e-15 for r in rec)
+        assert lib.tj_audit(None, C.c_double(0.0), rec, None, None) == -1
 
 
 # ---- sizes, tables, flags, ties, truth, errors (the shapes the tests above never reach) ----------------------------------------------------
@@ -520,52 +481,30 @@ def parse_audit_lines(stdout):
     return out
 
 
-def load_dump(path, st):
-    """--dump-state file -> the solver state `st` with its control points and piece_time replaced (17 digits: the exact doubles)"""
-    lines = open(path).read().strip().split("\n")
-    U, P = int(lines[0].split()[1]), int(lines[0].split()[3])
-    T = 3 * P + 3
-    out = {k: v.copy() for k, v in st.items()}
-    for u in range(U):
-        blk = lines[1 + u * (T + 1):1 + (u + 1) * (T + 1)]
-        assert blk[0].split()[:2] == ["uav", str(u)]
-        out["piece_time"][u] = float(blk[0].split()[3])
-        out["spline"][u] = np.array([[float(x) for x in l.split()] for l in blk[1:]]).T
-    return out
-
-
 @pytest.mark.parametrize("multi", [False, True])
 def test_command_line_audit(pkg, scenes, tmp_path, multi):
     """--audit and --audit 1.0 on both mains (and through a two-rank group on the multi-UAV one): every printed field equals the library's audit
     of the dumped state -- doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly"""
     import torch
     scene = scenes.tiny(mode=1) if multi else scenes.tiny(0, n_points=3000)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D" if multi else "admmPathPlanning3D")
+    cli = CliCase(pkg, scenes, tmp_path, scene, "multiPathPlanning3D" if multi else "admmPathPlanning3D")
     two = ["--gpus", "2"] if torch.cuda.device_count() >= 2 else ["--devices", "0,0"]   # two ranks either way: tj_group_audit
-    slv = pkg.Solver(scene, stop=0.0)
     dumps = []
     for audit_args, rng in ((["--audit"], None), (["--audit", "1.0"], 1.0)):
         for extra in ([], two) if multi else ([],):
-            r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + audit_args + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-            assert r.returncode in (0, 2), r.stderr          # 2: not converged after 6 iterations, the audit is printed all the same
-            got = parse_audit_lines(r.stdout)
-            assert len(got) == scene["U"], r.stdout[-2000:]
+            lines = cli.run(audit_args + extra)
+            got = parse_audit_lines("\n".join(lines))
+            assert len(got) == scene["U"], lines[-40:]
             dumps.append(open(tmp_path / "state.txt").read())
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.audit(range=rng)
+            cli.load()
+            a = cli.slv.audit(range=rng)
             for u, rec in enumerate(got):
                 for n, v in rec.items():
                     if isinstance(v, int):
                         assert v == a[n][u], (audit_args, extra, u, n, v, a[n][u])
                     else:
-                        assert abs(v - a[n][u]) <= 1e-6 * abs(a[n][u]), (audit_args, extra, u, n, v, a[n][u])
+                        assert close_to_six_digits(v, a[n][u]), (audit_args, extra, u, n, v, a[n][u])
             if not multi:
                 assert all(rec["pair_robot"] == -1 and rec["pair_clearance"] == (DEFAULT_RANGE if rng is None else rng) for rec in got)
     assert len(set(dumps)) == 1                                # the audit and the group change nothing of the run
-    slv.close()
+    cli.close()

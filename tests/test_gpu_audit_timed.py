@@ -6,7 +6,6 @@ holds: same inputs, same expressions, no FMA contraction on either side.  The re
 (tests/test_audit_timed_ref.py)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +14,9 @@ import audit_ref as R
 import audit_timed_ref as T
 from audit_ref import prims
 from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_only_adds, assert_read_only, close_to_six_digits, group_pair, one_queue, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 DEFAULT_RANGE = 0.1 + 2 * 0.1
 
 
@@ -164,46 +163,17 @@ def test_segment_counts_and_resolutions(pkg, scenes, P, res):
 @pytest.mark.parametrize("queues", ["default", "one"])
 def test_audit_timed_is_read_only(pkg, scenes, monkeypatch, queues):
     if queues == "one":
-        monkeypatch.setenv("TJ_XS_ASYNC", "0"); monkeypatch.setenv("TJ_FRONT_ASYNC", "0")
-    scene = scenes.hard()
-
-    def run(audited):   # one context at a time: a second live context may find the process's hardware-queue budget taken and keep the one-queue chain (tj_create)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the audit drains the queues itself
-                s.iterate_async(2)
-                if audited:
-                    s.audit_timed(range=1.0, levels=6, per_segment=True)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if audited:
-                    s.audit_timed(); s.audit_timed(range=1.0, levels=0)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.close()
-        return out
-
-    (sa, ta, la), (sb, tb, lb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-    assert ta == tb
-    assert la == lb
+        one_queue(monkeypatch)
+    assert_read_only(pkg, scenes.hard(), lambda s: s.audit_timed(range=1.0, levels=6, per_segment=True),
+                     lambda s: (s.audit_timed(), s.audit_timed(range=1.0, levels=0)))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for rng, levels in ((None, None), (1.0, 4)):
-            x, y = one.audit_timed(range=rng, levels=levels, per_segment=True), grp.audit_timed(range=rng, levels=levels, per_segment=True)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, rng, levels, k)
+    one, grp = group_pair(pkg, scene, ranks)
+    assert_group_equals(one, grp, lambda s, rng, levels: s.audit_timed(range=rng, levels=levels, per_segment=True), ((None, None), (1.0, 4)))
     grp.close(); one.close()
     half = pkg.Solver(scene, stop=0.0, rank=1, world=2)   # a plain sharded context does not hold the other ranks' piece_time: it says so
     with pytest.raises(pkg.TrajAdmmError) as ei:
@@ -214,21 +184,15 @@ def test_group_equals_one_context(pkg, scenes, mode, ranks):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec = (pkg.TjAuditTimedRobot * 3)()
-    call = lambda r, l, out=rec: lib.tj_audit_timed(ctx, C.c_double(r), C.c_int(l), out, None, None)
-    assert call(0.0, -1) == -1                                   # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    assert call(0.0, 7) == -1 and call(float("nan"), -1) == -1 and call(0.0, -1, None) == -1
-    assert lib.tj_audit_timed(None, C.c_double(0.0), C.c_int(-1), rec, None, None) == -1
-    assert call(0.0, -1) == 0 and all(r.levels == pkg.AUDIT_TIMED_LEVELS for r in rec)   # still usable; no obstacles set: valid
-    assert call(0.0, 6) == 0 and all(r.levels == 6 for r in rec)
-    lib.tj_destroy(ctx)
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec = (pkg.TjAuditTimedRobot * 3)()
+        call = lambda r, l, out=rec: lib.tj_audit_timed(ctx, C.c_double(r), C.c_int(l), out, None, None)
+        assert call(0.0, -1) == -1                                   # before tj_init_state
+        init()
+        assert call(0.0, 7) == -1 and call(float("nan"), -1) == -1 and call(0.0, -1, None) == -1
+        assert lib.tj_audit_timed(None, C.c_double(0.0), C.c_int(-1), rec, None, None) == -1
+        assert call(0.0, -1) == 0 and all(r.levels == pkg.AUDIT_TIMED_LEVELS for r in rec)   # still usable; no obstacles set: valid
+        assert call(0.0, 6) == 0 and all(r.levels == 6 for r in rec)
 
 
 def parse_timed_lines(stdout):
@@ -247,40 +211,21 @@ def test_command_line(pkg, scenes, tmp_path):
     """--audit-timed and --audit-timed 4 on the multi-UAV main (one context and a two-rank group): every printed field equals the library's answer on
     the dumped state -- doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly; the lines come
     after the --audit lines, and without the flag the output is what it was (every line but the wall-clock ones)"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain, audited = run([]), run(["--audit"])
+    cli = CliCase(pkg, scenes, tmp_path)
+    audited = cli.run(["--audit"])
     for args, levels in ((["--audit-timed"], None), (["--audit-timed", "4"], 4)):
-        for extra in ([], ["--devices", "0,0"]):
-            lines = run(["--audit"] + args + extra)
+        for extra, lines in cli.queried(["--audit"] + args, "audit-timed ", against=audited):   # everything else is the --audit run's output
             got = parse_timed_lines("\n".join(lines))
-            assert len(got) == scene["U"]
-            rest = [l for l in lines if not l.startswith("audit-timed ") and not l.startswith("devices:")]
-            assert rest == audited                                              # everything else is the --audit run's output
+            assert len(got) == cli.scene["U"]
             first = min(i for i, l in enumerate(lines) if l.startswith("audit-timed "))
             assert all(not l.startswith("audit uav ") for l in lines[first:])   # after the --audit lines
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.audit_timed(levels=levels)
+            a = cli.slv.audit_timed(levels=levels)
             for u, rec in enumerate(got):
                 for n, v in rec.items():
                     if isinstance(v, int):
                         assert v == a[n][u], (args, extra, u, n, v, a[n][u])
                     else:
-                        assert abs(v - a[n][u]) <= 1e-6 * abs(a[n][u]), (args, extra, u, n, v, a[n][u])
-    assert [l for l in audited if not l.startswith("audit uav ")] == plain
-    assert [l for l in run(["--audit-timed"]) if not l.startswith("audit-timed ")] == plain
-    slv.close()
+                        assert close_to_six_digits(v, a[n][u]), (args, extra, u, n, v, a[n][u])
+    assert_only_adds(audited, "audit uav ", cli.plain)
+    assert_only_adds(cli.run(["--audit-timed"]), "audit-timed ", cli.plain)
+    cli.close()

@@ -7,7 +7,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,9 +17,9 @@ import closest_ref as K
 import pair_approach_ref as Q
 from audit_ref import prims
 from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_read_only, assert_sharded_refuses, close_to_six_digits, group_pair, one_queue, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 
 
@@ -193,73 +192,31 @@ def test_truncation(pkg, scenes, name):
 @pytest.mark.parametrize("queues", ["default", "one"])
 def test_closest_approach_is_read_only(pkg, scenes, monkeypatch, queues):
     if queues == "one":
-        monkeypatch.setenv("TJ_XS_ASYNC", "0"); monkeypatch.setenv("TJ_FRONT_ASYNC", "0")
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the call drains the queues itself
-                s.iterate_async(2)
-                if asked:
-                    s.closest_approach(range=INF, tol=0.0)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if asked:
-                    s.closest_approach(); s.closest_approach(range=1.0, max_depth=2, max_windows=1)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    (sa, ta, la, na), (sb, tb, lb, nb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-        assert np.array_equal(na[n], nb[n]), n
-    assert ta == tb
-    assert la == lb
+        one_queue(monkeypatch)
+    assert_read_only(pkg, scenes.hard(), lambda s: s.closest_approach(range=INF, tol=0.0),
+                     lambda s: (s.closest_approach(), s.closest_approach(range=1.0, max_depth=2, max_windows=1)))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for rng, tol in ((None, None), (INF, 0.0)):
-            x, y = one.closest_approach(range=rng, tol=tol), grp.closest_approach(range=rng, tol=tol)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, rng, tol, k)
+    one, grp = group_pair(pkg, scene, ranks)
+    assert_group_equals(one, grp, lambda s, rng, tol: s.closest_approach(range=rng, tol=tol), ((None, None), (INF, 0.0)))
     grp.close(); one.close()
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec = (pkg.TjClosestRobot * 3)()
-    call = lambda r, t, d, w, out=rec: lib.tj_closest_approach(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out)
-    assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    nan = float("nan")
-    assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
-    assert call(0.0, -1.0, -1, 0, None) == -1
-    assert call(0.0, -1.0, 40, 4096) == 0 and call(0.0, 0.0, -1, 0) == 0     # still usable; the limits themselves are valid
-    lib.tj_destroy(ctx)
-    half = pkg.Solver(scenes.hard(), stop=0.0, rank=1, world=2)
-    with pytest.raises(pkg.TrajAdmmError) as ei:
-        half.closest_approach()
-    assert "-5" in str(ei.value) and "tj_group_closest_approach" in str(ei.value)
-    half.close()
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec = (pkg.TjClosestRobot * 3)()
+        call = lambda r, t, d, w, out=rec: lib.tj_closest_approach(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out)
+        assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
+        init()
+        nan = float("nan")
+        assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
+        assert call(0.0, -1.0, -1, 0, None) == -1
+        assert call(0.0, -1.0, 40, 4096) == 0 and call(0.0, 0.0, -1, 0) == 0     # still usable; the limits themselves are valid
+    assert_sharded_refuses(pkg, scenes, lambda half: half.closest_approach(), "tj_group_closest_approach")
     one = pkg.Solver(scenes.tiny(mode=0), stop=0.0)
     one.iterate(2)
     F = pkg.CLOSEST_FLAGS
@@ -272,36 +229,17 @@ def test_bad_arguments(pkg, scenes):
 def test_command_line(pkg, scenes, tmp_path):
     """--closest-approach and --closest-approach 1e-6 (one context and a two-rank group): every printed field equals the library's answer on the dumped state --
     doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly; the summary line names the smallest hi"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
     names = ("lo", "hi", "robot", "segment", "time", "depth", "windows", "flags")
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run([])
     for args, tol in ((["--closest-approach"], None), (["--closest-approach", "1e-6"], 1e-6)):
-        for extra in ([], ["--devices", "0,0"]):
-            lines = run(args + extra)
-            assert [l for l in lines if not l.startswith("closest ") and not l.startswith("devices:")] == plain
+        for extra, lines in cli.queried(args, "closest "):
             got = [l.split() for l in lines if l.startswith("closest uav ")]
-            assert len(got) == scene["U"] and all(len(w) == 19 and int(w[2]) == u for u, w in enumerate(got))
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.closest_approach(tol=tol)
+            assert len(got) == cli.scene["U"] and all(len(w) == 19 and int(w[2]) == u for u, w in enumerate(got))
+            a = cli.slv.closest_approach(tol=tol)
             for u, w in enumerate(got):
                 for k, n in enumerate(names):
                     if n in ("lo", "hi", "time"):
-                        assert abs(float(w[4 + 2 * k]) - a[n][u]) <= 1e-6 * abs(a[n][u]), (args, extra, u, n, w)
+                        assert close_to_six_digits(w[4 + 2 * k], a[n][u]), (args, extra, u, n, w)
                     else:
                         assert int(w[4 + 2 * k]) == a[n][u], (args, extra, u, n, w)
             fleet = [l.split() for l in lines if l.startswith("closest fleet ")]
@@ -310,8 +248,8 @@ def test_command_line(pkg, scenes, tmp_path):
             if m.any():
                 who = int(np.flatnonzero(m)[np.argmin(a["hi"][m])])
                 f = fleet[0]
-                assert abs(float(f[3]) - a["hi"][who]) <= 1e-6 * a["hi"][who] and int(f[5]) == who and int(f[7]) == a["robot"][who]
+                assert close_to_six_digits(f[3], a["hi"][who]) and int(f[5]) == who and int(f[7]) == a["robot"][who]
                 assert int(f[11]) == int(np.any(a["flags"] & pkg.CLOSEST_FLAGS["contact"]))
             else:
                 assert fleet[0][2] == "none"
-    slv.close()
+    cli.close()

@@ -6,9 +6,9 @@ import numpy as np
 import pytest
 
 from conftest import canon, check_scene_matches_fixture, gold, maxdiff, rel, scene_by_name
+from query_kit import STATE
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 def test_coupled_stages_teacher_forced_vs_reference(pkg, scenes):

@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, maxdiff, rel
+from query_kit import STATE, reference_config
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 def _oracle_run(scene, n):
@@ -150,9 +150,7 @@ def test_cli_drop_in(pkg, scenes, tmp_path, multi):
     mesh = "x.obj"
     scenes.write_reference_files(scene, str(tmp_path), mesh)
     os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config())
     exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D" if multi else "admmPathPlanning3D")
     r = subprocess.run([exe, mesh, "--dump-state", "state.txt", "--max-iter", "300"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
@@ -182,9 +180,7 @@ def test_cli_coupled_mode_and_log_data(pkg, scenes, tmp_path):
     mesh = "y.obj"
     scenes.write_reference_files(scene, str(tmp_path), mesh)
     os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":0,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config(decouple=0))
     exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
     r = subprocess.run([exe, mesh, "--dump-state", "state.txt", "--sample-traj", "traj.txt", "--max-iter", "300"], cwd=tmp_path,
                        capture_output=True, text=True, timeout=300)

@@ -6,7 +6,6 @@ against the flown curve on the CPU (tests/test_flight_profile_ref.py)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,9 +15,9 @@ import audit_timed_ref as T
 import flight_profile_ref as F
 from audit_ref import prims
 from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_read_only, assert_sharded_refuses, group_pair, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 
 
@@ -198,58 +197,25 @@ def test_partner_scan_wider_than_a_wave(pkg, scenes):
 
 def test_flight_profile_is_read_only(pkg, scenes):
     """state, tj_get_stats and tj_launch_count are unchanged by calls; 3 iterations after them give the bits of 3 iterations without them"""
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        s.iterate(2)
-        before = s.get_state(), s.stats(), s.launch_count()
-        if asked:
-            s.flight_profile(); s.flight_profile(samples=7); s.flight_profile(times=[0.0, 3.0])
-        s.iterate_async(2)
-        if asked:
-            s.flight_profile(samples=9)   # right behind iterate_async: the call drains the queues itself
-        else:
-            s.sync()
-        out = before + (s.get_state(), s.stats(), s.launch_count())
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    a, b = run(True), run(False)
-    for x, y in zip(a, b):
-        if isinstance(x, dict) and "spline" in x:
-            for n in STATE:
-                assert np.array_equal(x[n], y[n]), n
-        else:
-            assert x == y
+    assert_read_only(pkg, scenes.hard(), lambda s: s.flight_profile(samples=9),
+                     lambda s: (s.flight_profile(), s.flight_profile(samples=7), s.flight_profile(times=[0.0, 3.0])))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        times = F.sample_times(one.get_state(), one.P, one.res, 65)
-        x, y = one.flight_profile(times=times), grp.flight_profile(times=times)
-        for k in x:
-            assert np.array_equal(x[k], y[k]), (it, k)
-        x, y = one.flight_profile(samples=9), grp.flight_profile(samples=9)
-        for k in x:
-            assert np.array_equal(x[k], y[k]), (it, k)
+    one, grp = group_pair(pkg, scene, ranks)
+
+    def ask(s, how):   # 65 times chosen on the state the one context holds now, or the default grid of 9
+        return s.flight_profile(samples=9) if how == "grid" else s.flight_profile(times=F.sample_times(one.get_state(), one.P, one.res, 65))
+
+    assert_group_equals(one, grp, ask, (("times",), ("grid",)))
     grp.close(); one.close()
 
 
 def test_sharded_context_is_unsupported_and_single_uav_has_no_partner(pkg, scenes):
-    half = pkg.Solver(scenes.hard(), stop=0.0, rank=1, world=2)
-    with pytest.raises(pkg.TrajAdmmError, match="error -5"):
-        half.flight_profile(samples=3)
-    half.close()
+    assert_sharded_refuses(pkg, scenes, lambda half: half.flight_profile(samples=3), "tj_group_flight_profile")
     scene = scenes.tiny(mode=0)
     slv = pkg.Solver(scene, stop=0.0)
     a = check(pkg, slv, scene, np.array([0.0, 1.0, 1e4]))
@@ -259,33 +225,27 @@ def test_sharded_context_is_unsupported_and_single_uav_has_no_partner(pkg, scene
 
 def test_bad_arguments(pkg, scenes):
     """every invalid argument returns TJ_ERR_INVALID and leaves `out` untouched"""
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec = (pkg.TjProfileSample * (3 * 4))()
-    C.memset(rec, 0xAB, C.sizeof(rec))
-    mark = bytes(rec)
     dp = C.POINTER(C.c_double)
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec = (pkg.TjProfileSample * (3 * 4))()
+        C.memset(rec, 0xAB, C.sizeof(rec))
+        mark = bytes(rec)
 
-    def call(times, n=None, out=rec):
-        t = None if times is None else np.ascontiguousarray(times, dtype=np.float64)
-        return lib.tj_flight_profile(ctx, None if t is None else t.ctypes.data_as(dp), C.c_int(len(times) if n is None else n), out)
+        def call(times, n=None, out=rec):
+            t = None if times is None else np.ascontiguousarray(times, dtype=np.float64)
+            return lib.tj_flight_profile(ctx, None if t is None else t.ctypes.data_as(dp), C.c_int(len(times) if n is None else n), out)
 
-    assert call([0.0, 1.0]) == -1 and bytes(rec) == mark                                  # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(dp), C.c_double(20.0)) == 0
-    nan = float("nan")
-    for bad in ([nan], [0.0, nan], [-1e-300], [1.0, -2.0], [INF], [0.0, -INF]):
-        assert call(bad) == -1, bad
-    assert call(None, 2) == -1 and call([0.0], 1, None) == -1 and call([0.0], 0) == -1 and call([0.0], -3) == -1
-    big = np.zeros(pkg.PROFILE_MAX_SAMPLES + 1)
-    assert call(big) == -1
-    assert bytes(rec) == mark
-    assert call([0.0, 1.0, 2.0, 1e300]) == 0 and bytes(rec) != mark                       # valid: no obstacle set at all, +infinity and -1
-    assert all(rec[i].obs_index == -1 and rec[i].obs_distance == INF for i in range(12))
-    lib.tj_destroy(ctx)
+        assert call([0.0, 1.0]) == -1 and bytes(rec) == mark                                  # before tj_init_state
+        init()
+        nan = float("nan")
+        for bad in ([nan], [0.0, nan], [-1e-300], [1.0, -2.0], [INF], [0.0, -INF]):
+            assert call(bad) == -1, bad
+        assert call(None, 2) == -1 and call([0.0], 1, None) == -1 and call([0.0], 0) == -1 and call([0.0], -3) == -1
+        big = np.zeros(pkg.PROFILE_MAX_SAMPLES + 1)
+        assert call(big) == -1
+        assert bytes(rec) == mark
+        assert call([0.0, 1.0, 2.0, 1e300]) == 0 and bytes(rec) != mark                       # valid: no obstacle set at all, +infinity and -1
+        assert all(rec[i].obs_index == -1 and rec[i].obs_distance == INF for i in range(12))
     # uav_num * n_times above the limit, n_times itself within it
     tp2 = pkg.TjParams()
     lib.tj_default_params(C.byref(tp2), 1, 257, 2)
@@ -315,36 +275,26 @@ def test_command_line(pkg, scenes, tmp_path):
     """--flight-profile 5 (one context and a two-rank group; to standard output and to a file): 5 lines per robot whose numbers are
     Solver.flight_profile(samples=5)'s on the dumped state -- times, positions, robot distances and dynamics to 1e-12, obstacle distances to 1e-6 (the CLI
     read the scene through the x0.2 / x5 file round trip), integers exactly; all other output is unchanged"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
+    U = cli.scene["U"]
+    plain = cli.run(["--obstacle-approach"])
+    flags = ["--obstacle-approach", "--flight-profile", "5"]
 
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
+    def runs():   # one context and a two-rank group to standard output, then one context to a file
+        for extra, lines in cli.queried(flags, "profile ", against=plain):
+            yield extra, lines, False
+        yield next(cli.queried(flags + ["prof.txt"], "profile ", against=plain)) + (True,)
 
-    plain = run(["--obstacle-approach"])
-    for extra, to_file in (([], False), (["--devices", "0,0"], False), ([], True)):
-        lines = run(["--obstacle-approach", "--flight-profile", "5"] + (["prof.txt"] if to_file else []) + extra)
-        assert [l for l in lines if not l.startswith("profile ") and not l.startswith("devices:")] == plain
+    for extra, lines, to_file in runs():
         if to_file:
             assert not [l for l in lines if l.startswith("profile ")]
             got = [l.split() for l in open(tmp_path / "prof.txt").read().split("\n") if l]
         else:
             at = [i for i, l in enumerate(lines) if l.startswith("obstacle ") or l.startswith("profile ")]
-            assert [lines[i].split()[0] for i in at] == ["obstacle"] * (scene["U"] + 1) + ["profile"] * (5 * scene["U"])      # after the query lines
+            assert [lines[i].split()[0] for i in at] == ["obstacle"] * (U + 1) + ["profile"] * (5 * U)      # after the query lines
             got = [l.split()[1:] for l in lines if l.startswith("profile ")]
-        assert len(got) == 5 * scene["U"] and all(len(w) == 12 for w in got)
-        slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-        a = slv.flight_profile(samples=5)
+        assert len(got) == 5 * U and all(len(w) == 12 for w in got)
+        a = cli.slv.flight_profile(samples=5)
         names = ("time", "x", "y", "z", "obs_distance", "obs_index", "robot_distance", "robot", "speed", "accel", "flags")
         for r, w in enumerate(got):
             u, k = divmod(r, 5)
@@ -355,4 +305,4 @@ def test_command_line(pkg, scenes, tmp_path):
                     assert int(s) == v, (extra, u, k, n, w)
                 else:
                     assert abs(float(s) - v) <= (1e-6 if n == "obs_distance" else 1e-12) * max(1.0, abs(v)), (extra, u, k, n, w)
-    slv.close()
+    cli.close()

@@ -7,8 +7,9 @@ import os
 import numpy as np
 import pytest
 
+from query_kit import STATE, reference_config
+
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 @pytest.mark.parametrize("mode,ranks", [(1, 2), (1, 3), (2, 2), (2, 4)])
@@ -163,9 +164,7 @@ def test_cli_devices_flag_gives_the_one_device_trajectory(scenes, tmp_path):
     mesh = "x.obj"
     scenes.write_reference_files(scene, str(tmp_path), mesh)
     os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config())
     exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
     out = []
     for extra, name in (([], "a.txt"), (["--devices", "0,0,0"], "b.txt")):

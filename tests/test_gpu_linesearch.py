@@ -43,9 +43,9 @@ from mpmath import mp, mpf
 
 import grad_ref as G
 import ls_ref as L
+from query_kit import STATE
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 SWITCHES = ("TJ_LS_HELP", "TJ_LS_FAST", "TJ_LS_HELP_MUTE", "TJ_LS_HELP_LATE", "TJ_LSC_WIDE")
 CASES = [(r[0], slot) for r in L.ROWS for slot in r[3]]
 

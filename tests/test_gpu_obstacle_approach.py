@@ -7,7 +7,6 @@ compared with == on doubles and ints, `windows` and `depth` included.  The resta
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,9 +15,9 @@ import audit_ref as R
 import obstacle_approach_ref as O
 from audit_ref import prims
 from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_read_only, close_to_six_digits, group_pair, one_queue, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 
 
@@ -188,49 +187,17 @@ def test_constructed_states(pkg, scenes):
 @pytest.mark.parametrize("queues", ["default", "one"])
 def test_obstacle_approach_is_read_only(pkg, scenes, monkeypatch, queues):
     if queues == "one":
-        monkeypatch.setenv("TJ_XS_ASYNC", "0"); monkeypatch.setenv("TJ_FRONT_ASYNC", "0")
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the call drains the queues itself
-                s.iterate_async(2)
-                if asked:
-                    s.obstacle_approach(range=1.0, tol=0.0)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if asked:
-                    s.obstacle_approach(); s.obstacle_approach(range=1.0, max_depth=2, max_windows=1)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    (sa, ta, la, na), (sb, tb, lb, nb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-        assert np.array_equal(na[n], nb[n]), n
-    assert ta == tb
-    assert la == lb
+        one_queue(monkeypatch)
+    assert_read_only(pkg, scenes.hard(), lambda s: s.obstacle_approach(range=1.0, tol=0.0),
+                     lambda s: (s.obstacle_approach(), s.obstacle_approach(range=1.0, max_depth=2, max_windows=1)))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for rng, tol in ((None, None), (1.0, 0.0)):
-            x, y = one.obstacle_approach(range=rng, tol=tol), grp.obstacle_approach(range=rng, tol=tol)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, rng, tol, k)
+    one, grp = group_pair(pkg, scene, ranks)
+    assert_group_equals(one, grp, lambda s, rng, tol: s.obstacle_approach(range=rng, tol=tol), ((None, None), (1.0, 0.0)))
     grp.close(); one.close()
 
 
@@ -249,68 +216,45 @@ def test_sharded_context_answers_for_its_own_robots(pkg, scenes):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec = (pkg.TjObstacleRobot * 3)()
-    call = lambda r, t, d, w, out=rec: lib.tj_obstacle_approach(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out)
-    assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    nan = float("nan")
-    assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, pkg.OBSTACLE_FRONTIER + 1) == -1
-    assert call(0.0, -1.0, -1, 0, None) == -1
-    # the limits themselves are valid; no obstacle set at all: the sentinel for every robot
-    F = pkg.OBSTACLE_FLAGS
-    for args, r in (((0.0, -1.0, 40, pkg.OBSTACLE_FRONTIER), 0.1 + 2 * 0.1), ((0.05, 0.0, -1, 0), 0.05), ((INF, -1.0, 0, 1), INF)):
-        assert call(*args) == 0
-        for u in range(3):
-            got = {n: getattr(rec[u], n) for n in O.FIELDS}
-            assert got == O.sentinel(r) and got["flags"] == F["clear"] | F["converged"], (args, u, got)
-    cloud = np.zeros((0, 3))
-    assert lib.tj_set_cloud(ctx, cloud.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(0)) == 0       # tj_set_cloud with n = 0: the same
-    assert call(0.0, -1.0, -1, 0) == 0 and {n: getattr(rec[1], n) for n in O.FIELDS} == O.sentinel(0.1 + 2 * 0.1)
-    lib.tj_destroy(ctx)
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec = (pkg.TjObstacleRobot * 3)()
+        call = lambda r, t, d, w, out=rec: lib.tj_obstacle_approach(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out)
+        assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
+        init()
+        nan = float("nan")
+        assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, pkg.OBSTACLE_FRONTIER + 1) == -1
+        assert call(0.0, -1.0, -1, 0, None) == -1
+        # the limits themselves are valid; no obstacle set at all: the sentinel for every robot
+        F = pkg.OBSTACLE_FLAGS
+        for args, r in (((0.0, -1.0, 40, pkg.OBSTACLE_FRONTIER), 0.1 + 2 * 0.1), ((0.05, 0.0, -1, 0), 0.05), ((INF, -1.0, 0, 1), INF)):
+            assert call(*args) == 0
+            for u in range(3):
+                got = {n: getattr(rec[u], n) for n in O.FIELDS}
+                assert got == O.sentinel(r) and got["flags"] == F["clear"] | F["converged"], (args, u, got)
+        cloud = np.zeros((0, 3))
+        assert lib.tj_set_cloud(ctx, cloud.ctypes.data_as(C.POINTER(C.c_double)), C.c_int(0)) == 0       # tj_set_cloud with n = 0: the same
+        assert call(0.0, -1.0, -1, 0) == 0 and {n: getattr(rec[1], n) for n in O.FIELDS} == O.sentinel(0.1 + 2 * 0.1)
 
 
 def test_command_line(pkg, scenes, tmp_path):
     """--obstacle-approach and --obstacle-approach 1e-6 (one context and a two-rank group): every printed field equals the library's answer on the dumped state --
     doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly; the summary line names the smallest hi;
     all other output is unchanged"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
+    U = cli.scene["U"]
     names = ("lo", "hi", "index", "segment", "time", "depth", "windows", "flags")
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run(["--closest-approach"])
+    plain = cli.run(["--closest-approach"])
     for args, tol in ((["--obstacle-approach"], None), (["--obstacle-approach", "1e-6"], 1e-6)):
-        for extra in ([], ["--devices", "0,0"]):
-            lines = run(["--closest-approach"] + args + extra)
-            assert [l for l in lines if not l.startswith("obstacle ") and not l.startswith("devices:")] == plain
+        for extra, lines in cli.queried(["--closest-approach"] + args, "obstacle ", against=plain):
             at = [i for i, l in enumerate(lines) if l.startswith("closest ") or l.startswith("obstacle ")]
-            assert [lines[i].split()[0] for i in at] == ["closest"] * (scene["U"] + 1) + ["obstacle"] * (scene["U"] + 1)      # after the `closest` lines
+            assert [lines[i].split()[0] for i in at] == ["closest"] * (U + 1) + ["obstacle"] * (U + 1)      # after the `closest` lines
             got = [l.split() for l in lines if l.startswith("obstacle uav ")]
-            assert len(got) == scene["U"] and all(len(w) == 19 and int(w[2]) == u for u, w in enumerate(got))
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.obstacle_approach(tol=tol)
+            assert len(got) == U and all(len(w) == 19 and int(w[2]) == u for u, w in enumerate(got))
+            a = cli.slv.obstacle_approach(tol=tol)
             for u, w in enumerate(got):
                 for k, n in enumerate(names):
                     if n in ("lo", "hi", "time"):
-                        assert abs(float(w[4 + 2 * k]) - a[n][u]) <= 1e-6 * abs(a[n][u]), (args, extra, u, n, w)
+                        assert close_to_six_digits(w[4 + 2 * k], a[n][u]), (args, extra, u, n, w)
                     else:
                         assert int(w[4 + 2 * k]) == a[n][u], (args, extra, u, n, w)
             fleet = [l.split() for l in lines if l.startswith("obstacle fleet ")]
@@ -319,8 +263,8 @@ def test_command_line(pkg, scenes, tmp_path):
             if m.any():
                 who = int(np.flatnonzero(m)[np.argmin(a["hi"][m])])
                 f = fleet[0]
-                assert abs(float(f[3]) - a["hi"][who]) <= 1e-6 * a["hi"][who] and int(f[5]) == who and int(f[7]) == a["index"][who]
+                assert close_to_six_digits(f[3], a["hi"][who]) and int(f[5]) == who and int(f[7]) == a["index"][who]
                 assert int(f[11]) == int(np.any(a["flags"] & pkg.OBSTACLE_FLAGS["contact"]))
             else:
                 assert fleet[0][2] == "none"
-    slv.close()
+    cli.close()

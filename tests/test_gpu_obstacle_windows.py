@@ -6,8 +6,6 @@ merge of the leaves into rows across segment boundaries, the row order).  Every 
 `leaves` and `index` included, and so is the number of rows.  The restatement itself is held against the flown curve on the CPU
 (tests/test_obstacle_windows_ref.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,10 +14,9 @@ import audit_ref as R
 import obstacle_approach_ref as O
 import obstacle_windows_ref as W
 from audit_ref import prims
-from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_read_only, close_to_six_digits, group_pair, loaded, one_queue, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 
 
@@ -40,14 +37,6 @@ def check(pkg, slv, ref, dist=None, tol=None, max_depth=None, max_windows=None, 
     key = list(zip(a["robot"], a["t_first_lo"]))
     assert key == sorted(key)
     return a
-
-
-def loaded(pkg, scene, st, params=None):
-    slv = pkg.Solver(scene, params, stop=0.0) if params else pkg.Solver(scene, stop=0.0)
-    full = slv.get_state()
-    full["spline"], full["piece_time"] = np.array(st["spline"]), np.array(st["piece_time"])
-    slv.set_state(full)
-    return slv
 
 
 def test_row_size(pkg):
@@ -262,52 +251,18 @@ def test_walk_overflow_is_an_error_for_a_context_and_for_a_group(pkg, scenes):
 @pytest.mark.parametrize("queues", ["default", "one"])
 def test_obstacle_windows_is_read_only(pkg, scenes, monkeypatch, queues):
     if queues == "one":
-        monkeypatch.setenv("TJ_XS_ASYNC", "0"); monkeypatch.setenv("TJ_FRONT_ASYNC", "0")
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the call drains the queues itself
-                s.iterate_async(2)
-                if asked:
-                    s.obstacle_windows(dist=1.0, tol=0.0, max_depth=4)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if asked:
-                    s.obstacle_windows(); s.obstacle_windows(dist=0.3, max_depth=2, max_windows=1)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    (sa, ta, la, na), (sb, tb, lb, nb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-        assert np.array_equal(na[n], nb[n]), n
-    assert ta == tb
-    assert la == lb
+        one_queue(monkeypatch)
+    assert_read_only(pkg, scenes.hard(), lambda s: s.obstacle_windows(dist=1.0, tol=0.0, max_depth=4),
+                     lambda s: (s.obstacle_windows(), s.obstacle_windows(dist=0.3, max_depth=2, max_windows=1)))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    n = 0
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for dist, tol in ((None, None), (0.3, None), (0.3, 0.0)):
-            x, y = one.obstacle_windows(dist=dist, tol=tol, max_depth=6), grp.obstacle_windows(dist=dist, tol=tol, max_depth=6)
-            assert set(x) == set(y)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, dist, tol, k)
-            n = len(x["robot"])
+    one, grp = group_pair(pkg, scene, ranks)
+    x = assert_group_equals(one, grp, lambda s, dist, tol: s.obstacle_windows(dist=dist, tol=tol, max_depth=6), ((None, None), (0.3, None), (0.3, 0.0)))
+    n = len(x["robot"])
     assert n > 2
     rec, got = (pkg.TjObswinRow * n)(), C.c_int(0)                                          # a cap that ends inside the rows: the exact total, the first rows
     rc = grp.lib.tj_group_obstacle_windows(grp._g, C.c_double(0.3), C.c_double(0.0), C.c_int(6), C.c_int(0), rec, C.c_int(n - 2), C.byref(got))
@@ -331,73 +286,48 @@ def test_sharded_context_answers_for_its_own_robots(pkg, scenes):
 
 def test_bad_arguments(pkg, scenes):
     """the precedence: null, then NaN, then limits, then no state; the outputs stay untouched"""
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec, got = (pkg.TjObswinRow * 12)(), C.c_int(-7)
-    rec[0].robot = -99
-    nan = float("nan")
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec, got = (pkg.TjObswinRow * 12)(), C.c_int(-7)
+        rec[0].robot = -99
+        nan = float("nan")
 
-    def call(d, t, depth, w, out=rec, cap=12, n=C.byref(got)):
-        rc = lib.tj_obstacle_windows(ctx, C.c_double(d), C.c_double(t), C.c_int(depth), C.c_int(w), out, C.c_int(cap), n)
-        if rc == -1:
-            assert (got.value, rec[0].robot) == (-7, -99)                                  # the outputs are untouched
-        return rc, lib.tj_last_error(ctx)
+        def call(d, t, depth, w, out=rec, cap=12, n=C.byref(got)):
+            rc = lib.tj_obstacle_windows(ctx, C.c_double(d), C.c_double(t), C.c_int(depth), C.c_int(w), out, C.c_int(cap), n)
+            if rc == -1:
+                assert (got.value, rec[0].robot) == (-7, -99)                                  # the outputs are untouched
+            return rc, lib.tj_last_error(ctx)
 
-    rc, msg = call(0.0, -1.0, -1, 0)                                                       # before tj_init_state
-    assert rc == -1 and b"tj_init_state" in msg
-    rc, msg = call(nan, -1.0, 41, 0)                                                       # NaN before the limits, the limits before the missing state
-    assert rc == -1 and b"NaN" in msg
-    rc, msg = call(0.0, -1.0, 41, 0)
-    assert rc == -1 and b"max_depth" in msg
-    assert call(nan, -1.0, -1, 0, n=None)[0] == -1 and call(0.0, -1.0, -1, 0, cap=-1)[0] == -1 and call(0.0, -1.0, -1, 0, out=None)[0] == -1
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    assert call(nan, -1.0, -1, 0)[0] == -1 and call(0.0, nan, -1, 0)[0] == -1 and call(0.0, -1.0, 41, 0)[0] == -1 and call(0.0, -1.0, -1, pkg.OBSWIN_MAX_WINDOWS + 1)[0] == -1
-    rc, msg = call(0.0, -1.0, -1, pkg.OBSWIN_MAX_WINDOWS, cap=1 << 25)                     # refused up front, nothing allocated
-    assert rc == -1 and b"TJ_OBSWIN_MAX_BYTES" in msg
-    for args in ((0.0, -1.0, 40, pkg.OBSWIN_MAX_WINDOWS), (0.05, 0.0, -1, 0), (INF, -1.0, 0, 1)):   # the limits themselves are valid; no obstacle set at all: 0 rows
-        got.value = -7
-        assert call(*args)[0] == 0 and got.value == 0 and rec[0].robot == -99
-    lib.tj_destroy(ctx)
+        rc, msg = call(0.0, -1.0, -1, 0)                                                       # before tj_init_state
+        assert rc == -1 and b"tj_init_state" in msg
+        rc, msg = call(nan, -1.0, 41, 0)                                                       # NaN before the limits, the limits before the missing state
+        assert rc == -1 and b"NaN" in msg
+        rc, msg = call(0.0, -1.0, 41, 0)
+        assert rc == -1 and b"max_depth" in msg
+        assert call(nan, -1.0, -1, 0, n=None)[0] == -1 and call(0.0, -1.0, -1, 0, cap=-1)[0] == -1 and call(0.0, -1.0, -1, 0, out=None)[0] == -1
+        init()
+        assert call(nan, -1.0, -1, 0)[0] == -1 and call(0.0, nan, -1, 0)[0] == -1 and call(0.0, -1.0, 41, 0)[0] == -1 and call(0.0, -1.0, -1, pkg.OBSWIN_MAX_WINDOWS + 1)[0] == -1
+        rc, msg = call(0.0, -1.0, -1, pkg.OBSWIN_MAX_WINDOWS, cap=1 << 25)                     # refused up front, nothing allocated
+        assert rc == -1 and b"TJ_OBSWIN_MAX_BYTES" in msg
+        for args in ((0.0, -1.0, 40, pkg.OBSWIN_MAX_WINDOWS), (0.05, 0.0, -1, 0), (INF, -1.0, 0, 1)):   # the limits themselves are valid; no obstacle set at all: 0 rows
+            got.value = -7
+            assert call(*args)[0] == 0 and got.value == 0 and rec[0].robot == -99
 
 
 def test_command_line(pkg, scenes, tmp_path):
     """--obstacle-windows 0.3 (one context and a two-rank group): the printed rows are the library's on the dumped state, in its order -- doubles to 6
     significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly -- and the fleet's line counts them"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
     doubles = ("t_first_lo", "t_first_hi", "t_last_lo", "t_last_hi", "within_lo", "closest", "closest_time")
     ints = ("index", "segment_first", "segment_last", "leaves", "depth", "windows", "flags")
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run([])
-    for extra in ([], ["--devices", "0,0"]):
-        lines = run(["--obstacle-windows", "0.3"] + extra)
-        assert [l for l in lines if not l.startswith("obswin ") and not l.startswith("devices:")] == plain
+    for extra, lines in cli.queried(["--obstacle-windows", "0.3"], "obswin "):
         got = [l.split() for l in lines if l.startswith("obswin uav ")]
-        slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-        a = slv.obstacle_windows(dist=0.3)
+        a = cli.slv.obstacle_windows(dist=0.3)
         assert len(got) == len(a["robot"]) > 0 and all(len(w) == 28 for w in got)
         for k, w in enumerate(got):
             assert int(w[2]) == a["robot"][k]
             for n, i in zip(doubles, (4, 5, 7, 8, 10, 12, 14)):
-                assert abs(float(w[i]) - a[n][k]) <= 1e-6 * abs(a[n][k]), (extra, k, n, w)
+                assert close_to_six_digits(w[i], a[n][k]), (extra, k, n, w)
             assert [int(w[i]) for i in (16, 18, 19, 21, 23, 25, 27)] == [a[n][k] for n in ints], (extra, k, w)
         fleet = [l.split() for l in lines if l.startswith("obswin fleet ")]
         assert len(fleet) == 1 and int(fleet[0][3]) == len(a["robot"])
-    slv.close()
+    cli.close()

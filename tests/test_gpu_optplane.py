@@ -13,9 +13,9 @@ import numpy as np
 import pytest
 
 from conftest import canon, check_scene_matches_fixture, gold, maxdiff, rel
+from query_kit import STATE, reference_config
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 # Round 3 made the plane refinements BIT-IDENTICAL to the reference (dev_crmath.h: log / sin / cos rounded like glibc's); the tests assert
@@ -250,9 +250,7 @@ def test_cli_optimal_plane_1(pkg, scenes, tmp_path, multi):
     mesh = "x.obj"
     scenes.write_reference_files(scene, str(tmp_path), mesh)
     os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":1,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config(optimal_plane=1))
     exe = os.path.join(root, "traj-opt-admm_amd", "multiPathPlanning3D" if multi else "admmPathPlanning3D")
     r = subprocess.run([exe, mesh, "--max-iter", "300"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr

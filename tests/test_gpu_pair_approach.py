@@ -5,8 +5,6 @@ pair, the listed rule, the row order).  Every field of every row is compared wit
 of rows: the bar tests/test_gpu_closest.py holds.  The restatement itself is held against the flown curves on the CPU (tests/test_pair_approach_ref.py)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +13,10 @@ import audit_ref as R
 import audit_timed_ref as T
 import pair_approach_ref as Q
 from audit_ref import prims
-from conftest import ROOT
+from query_kit import (CliCase, assert_group_equals, assert_read_only, assert_sharded_refuses, close_to_six_digits, group_pair, loaded, one_queue,
+                       raw_context)
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 
 
@@ -37,12 +35,6 @@ def check(pkg, slv, rng=None, tol=None, max_depth=None, max_windows=None, st=Non
         assert np.array_equal(a[n], ref[n]), (rng, tol, max_depth, max_windows, n, a[n], ref[n])
     assert list(zip(a["robot"], a["partner"])) == sorted(zip(a["robot"], a["partner"]))
     return a
-
-
-def loaded(pkg, scene, st):
-    slv = pkg.Solver(scene, stop=0.0)
-    slv.set_state(st)
-    return slv
 
 
 @pytest.mark.parametrize("name", ["hard", "tiny", "tiny_coupled"])
@@ -200,50 +192,17 @@ def test_triangle_scene(pkg, scenes):
 @pytest.mark.parametrize("queues", ["default", "one"])
 def test_pair_approach_is_read_only(pkg, scenes, monkeypatch, queues):
     if queues == "one":
-        monkeypatch.setenv("TJ_XS_ASYNC", "0"); monkeypatch.setenv("TJ_FRONT_ASYNC", "0")
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the call drains the queues itself
-                s.iterate_async(2)
-                if asked:
-                    s.pair_approach(range=INF, tol=0.0)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if asked:
-                    s.pair_approach(); s.pair_approach(range=1.0, max_depth=2, max_windows=1)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    (sa, ta, la, na), (sb, tb, lb, nb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-        assert np.array_equal(na[n], nb[n]), n
-    assert ta == tb
-    assert la == lb
+        one_queue(monkeypatch)
+    assert_read_only(pkg, scenes.hard(), lambda s: s.pair_approach(range=INF, tol=0.0),
+                     lambda s: (s.pair_approach(), s.pair_approach(range=1.0, max_depth=2, max_windows=1)))
 
 
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for rng, tol in ((None, None), (INF, 0.0)):
-            x, y = one.pair_approach(range=rng, tol=tol), grp.pair_approach(range=rng, tol=tol)
-            assert set(x) == set(y)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, rng, tol, k)
+    one, grp = group_pair(pkg, scene, ranks)
+    x = assert_group_equals(one, grp, lambda s, rng, tol: s.pair_approach(range=rng, tol=tol), ((None, None), (INF, 0.0)))
     n = len(x["robot"])
     rec, got = (pkg.TjPairRecord * n)(), C.c_int(0)                       # a cap that ends inside a later rank's rows
     rc = grp.lib.tj_group_pair_approach(grp._g, C.c_double(INF), C.c_double(0.0), C.c_int(-1), C.c_int(0), rec, C.c_int(n - 2), C.byref(got))
@@ -252,27 +211,17 @@ def test_group_equals_one_context(pkg, scenes, mode, ranks):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec, got = (pkg.TjPairRecord * 6)(), C.c_int(0)
-    call = lambda r, t, d, w, out=rec, cap=6, n=C.byref(got): lib.tj_pair_approach(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out, C.c_int(cap), n)
-    assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    nan = float("nan")
-    assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
-    assert call(0.0, -1.0, -1, 0, n=None) == -1 and call(0.0, -1.0, -1, 0, cap=-1) == -1 and call(0.0, -1.0, -1, 0, out=None) == -1
-    assert call(0.0, -1.0, -1, 4096, cap=1 << 20) == -1 and b"TJ_PAIR_MAX_BYTES" in lib.tj_last_error(ctx)      # refused up front, nothing allocated
-    assert call(INF, -1.0, 40, 4096) == 0 and got.value == 6 and call(0.0, 0.0, -1, 0) == 0                                  # still usable; the limits themselves are valid
-    lib.tj_destroy(ctx)
-    half = pkg.Solver(scenes.hard(), stop=0.0, rank=1, world=2)
-    with pytest.raises(pkg.TrajAdmmError) as ei:
-        half.pair_approach()
-    assert "-5" in str(ei.value) and "tj_group_pair_approach" in str(ei.value)
-    half.close()
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec, got = (pkg.TjPairRecord * 6)(), C.c_int(0)
+        call = lambda r, t, d, w, out=rec, cap=6, n=C.byref(got): lib.tj_pair_approach(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out, C.c_int(cap), n)
+        assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
+        init()
+        nan = float("nan")
+        assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
+        assert call(0.0, -1.0, -1, 0, n=None) == -1 and call(0.0, -1.0, -1, 0, cap=-1) == -1 and call(0.0, -1.0, -1, 0, out=None) == -1
+        assert call(0.0, -1.0, -1, 4096, cap=1 << 20) == -1 and b"TJ_PAIR_MAX_BYTES" in lib.tj_last_error(ctx)      # refused up front, nothing allocated
+        assert call(INF, -1.0, 40, 4096) == 0 and got.value == 6 and call(0.0, 0.0, -1, 0) == 0                                  # still usable; the limits themselves are valid
+    assert_sharded_refuses(pkg, scenes, lambda half: half.pair_approach(), "tj_group_pair_approach")
     one = pkg.Solver(scenes.tiny(mode=0), stop=0.0)
     one.iterate(2)
     for rng in (None, INF):
@@ -284,41 +233,22 @@ def test_bad_arguments(pkg, scenes):
 def test_command_line(pkg, scenes, tmp_path):
     """--pair-approach and --pair-approach 1e-6 (one context and a two-rank group): the printed rows are the library's on the dumped state, in its order --
     doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly -- and the summary line counts them"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
     names = ("lo", "hi", "segment", "time", "depth", "windows", "flags")
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run([])
     for args, tol in ((["--pair-approach"], None), (["--pair-approach", "1e-6"], 1e-6)):
-        for extra in ([], ["--devices", "0,0"]):
-            lines = run(args + extra)
-            assert [l for l in lines if not l.startswith("pair ") and not l.startswith("devices:")] == plain
+        for extra, lines in cli.queried(args, "pair "):
             got = [l.split() for l in lines if l.startswith("pair uav ")]
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.pair_approach(tol=tol)
+            a = cli.slv.pair_approach(tol=tol)
             assert len(got) == len(a["robot"]) and all(len(w) == 19 for w in got)
             for k, w in enumerate(got):
                 assert (int(w[2]), int(w[4])) == (a["robot"][k], a["partner"][k])
                 for i, n in enumerate(names):
                     if n in ("lo", "hi", "time"):
-                        assert abs(float(w[6 + 2 * i]) - a[n][k]) <= 1e-6 * abs(a[n][k]), (args, extra, k, n, w)
+                        assert close_to_six_digits(w[6 + 2 * i], a[n][k]), (args, extra, k, n, w)
                     else:
                         assert int(w[6 + 2 * i]) == a[n][k], (args, extra, k, n, w)
             fleet = [l.split() for l in lines if l.startswith("pair fleet ")]
             assert len(fleet) == 1
             contact = int(np.sum(a["flags"] & 1 != 0)); clear = int(np.sum((a["flags"] & 3) == 2))
             assert [int(fleet[0][i]) for i in (3, 5, 7, 9)] == [len(a["robot"]), contact, len(a["robot"]) - contact - clear, clear]
-    slv.close()
+    cli.close()

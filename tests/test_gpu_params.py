@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import TOL_GNORM_FULL, TOL_STATE_FULL, check_scene_matches_fixture, gold, observe_iteration, rel, scene_by_name
+from query_kit import STATE
 from test_gpu_coupled import _coupled_teacher_forced
 from test_gpu_optplane import _persistent_plane_stage, assert_bits
 from test_gpu_parity import _teacher_forced
@@ -20,7 +21,6 @@ from test_planner import _wall_scene
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 @pytest.mark.parametrize("name,tag", STAGE_FIXTURES)

@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import backoff_exponent, observe_iteration, TOL_STATE_FULL, TOL_GNORM_FULL, canon, check_scene_matches_fixture, gold, maxdiff, rel, scene_by_name
+from query_kit import STATE
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,6 @@ import ctypes as C
 import faulthandler
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,9 +18,9 @@ import audit_ref as R
 import path_crossing_ref as X
 from audit_ref import prims
 from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_read_only, assert_sharded_refuses, close_to_six_digits, group_pair, loaded, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 NAMES = X.FIELDS + ("gap",)
 
@@ -50,12 +49,6 @@ def check(pkg, slv, rng=None, tol=None, max_depth=None, max_windows=None, st=Non
     assert np.array_equal(a["gap"], want["partner_time"] - want["time"])
     assert list(zip(a["robot"], a["partner"])) == sorted(zip(a["robot"], a["partner"])) and np.all(a["robot"] < a["partner"])
     return a
-
-
-def loaded(pkg, scene, st):
-    slv = pkg.Solver(scene, stop=0.0)
-    slv.set_state(st)
-    return slv
 
 
 def test_record_size_and_constants(pkg):
@@ -184,17 +177,14 @@ def test_capacity(pkg, scenes):
 
 @pytest.mark.parametrize("ranks", [1, 2, 3])
 def test_group_equals_one_context(pkg, scenes, ranks):
-    scene = scenes.hard()
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for rng, tol, depth in ((None, None, None), (INF, 0.0, 6)):
-            x, y = one.path_crossings(range=rng, tol=tol, max_depth=depth), grp.path_crossings(range=rng, tol=tol, max_depth=depth)
-            assert set(x) == set(y) == set(NAMES)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, rng, tol, k)
+    one, grp = group_pair(pkg, scenes.hard(), ranks)
+
+    def ask(s, rng, tol, depth):
+        a = s.path_crossings(range=rng, tol=tol, max_depth=depth)
+        assert set(a) == set(NAMES)
+        return a
+
+    x = assert_group_equals(one, grp, ask, ((None, None, None), (INF, 0.0, 6)))
     n = len(x["robot"])
     assert n == 6
     rec, got = (pkg.TjCrossingRecord * n)(), C.c_int(0)                   # a cap that ends inside a later rank's rows
@@ -204,27 +194,17 @@ def test_group_equals_one_context(pkg, scenes, ranks):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec, got = (pkg.TjCrossingRecord * 3)(), C.c_int(0)
-    call = lambda r, t, d, w, out=rec, cap=3, n=C.byref(got): lib.tj_path_crossings(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out, C.c_int(cap), n)
-    assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    nan = float("nan")
-    assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
-    assert call(0.0, -1.0, -1, 0, n=None) == -1 and call(0.0, -1.0, -1, 0, cap=-1) == -1 and call(0.0, -1.0, -1, 0, out=None) == -1
-    assert call(0.0, -1.0, -1, 4096, cap=1 << 20) == -1 and b"TJ_CROSSING_MAX_BYTES" in lib.tj_last_error(ctx)      # refused up front, nothing allocated
-    assert call(INF, -1.0, 40, 4096) == 0 and got.value == 3 and call(0.0, 0.0, -1, 0) == 0                          # still usable; the limits themselves are valid
-    lib.tj_destroy(ctx)
-    half = pkg.Solver(scenes.hard(), stop=0.0, rank=1, world=2)           # a plain sharded context
-    with pytest.raises(pkg.TrajAdmmError) as ei:
-        half.path_crossings()
-    assert "-5" in str(ei.value) and "tj_group_path_crossings" in str(ei.value)
-    half.close()
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec, got = (pkg.TjCrossingRecord * 3)(), C.c_int(0)
+        call = lambda r, t, d, w, out=rec, cap=3, n=C.byref(got): lib.tj_path_crossings(ctx, C.c_double(r), C.c_double(t), C.c_int(d), C.c_int(w), out, C.c_int(cap), n)
+        assert call(0.0, -1.0, -1, 0) == -1                                   # before tj_init_state
+        init()
+        nan = float("nan")
+        assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
+        assert call(0.0, -1.0, -1, 0, n=None) == -1 and call(0.0, -1.0, -1, 0, cap=-1) == -1 and call(0.0, -1.0, -1, 0, out=None) == -1
+        assert call(0.0, -1.0, -1, 4096, cap=1 << 20) == -1 and b"TJ_CROSSING_MAX_BYTES" in lib.tj_last_error(ctx)      # refused up front, nothing allocated
+        assert call(INF, -1.0, 40, 4096) == 0 and got.value == 3 and call(0.0, 0.0, -1, 0) == 0                          # still usable; the limits themselves are valid
+    assert_sharded_refuses(pkg, scenes, lambda half: half.path_crossings(), "tj_group_path_crossings")
     one = pkg.Solver(scenes.tiny(mode=0), stop=0.0)                       # single-UAV mode
     one.iterate(2)
     for rng in (None, INF):
@@ -236,74 +216,42 @@ def test_bad_arguments(pkg, scenes):
 def test_path_crossings_is_read_only(pkg, scenes):
     """state, statistics and launch count are untouched; the other queries answer the same before and after; an iteration after the call gives the bits of
     an iteration without it"""
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        s.iterate(2)
-        before = (s.get_state(), s.stats(), s.launch_count(), s.audit(), s.pair_approach(), s.flight_profile(samples=5))
-        if asked:
-            s.path_crossings(); s.path_crossings(range=INF, tol=0.0, max_depth=3); s.path_crossings(range=1.0, max_depth=2, max_windows=1)
-        after = (s.get_state(), s.stats(), s.launch_count(), s.audit(), s.pair_approach(), s.flight_profile(samples=5))
-        s.iterate_async(2)
-        if asked:
-            s.path_crossings()                                            # right behind iterate_async: the call drains the queues itself
-        else:
-            s.sync()
-        s.iterate(1)
-        out = (s.get_state(), s.stats(), s.launch_count())
-        s.close()
-        return before, after, out
+    def held(s):
+        return s.get_state(), s.stats(), s.launch_count(), s.audit(), s.pair_approach(), s.flight_profile(samples=5)
 
     def same(x, y):
         if isinstance(x, dict):
             return set(x) == set(y) and all(np.array_equal(x[k], y[k]) for k in x)
         return x == y
 
-    (b1, a1, o1), (b2, a2, o2) = run(True), run(False)
-    assert all(same(x, y) for x, y in zip(b1, a1)) and all(same(x, y) for x, y in zip(a1, a2))
-    assert all(same(x, y) for x, y in zip(o1, o2))
+    def ask_sync(s):
+        before = held(s)
+        s.path_crossings(); s.path_crossings(range=INF, tol=0.0, max_depth=3); s.path_crossings(range=1.0, max_depth=2, max_windows=1)
+        assert all(same(x, y) for x, y in zip(before, held(s)))
+
+    assert_read_only(pkg, scenes.hard(), lambda s: s.path_crossings(), ask_sync)
 
 
 def test_command_line(pkg, scenes, tmp_path):
     """--path-crossings and --path-crossings 1e-6 (one context and a two-rank group): the printed rows are the library's on the dumped state, in its order --
     doubles to 6 significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly -- and the summary line counts them"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
     # crossing uav U uav Q lo . hi . seg . s . time . seg . s . time . depth . windows . flags .
     names = ("lo", "hi", "segment", "s", "time", "partner_segment", "partner_s", "partner_time", "depth", "windows", "flags")
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run([])
     for args, tol in ((["--path-crossings"], None), (["--path-crossings", "1e-6"], 1e-6)):
-        for extra in ([], ["--devices", "0,0"]):
-            lines = run(args + extra)
-            assert [l for l in lines if not l.startswith("crossing ") and not l.startswith("devices:")] == plain
+        for extra, lines in cli.queried(args, "crossing "):
             got = [l.split() for l in lines if l.startswith("crossing uav ")]
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.path_crossings(tol=tol)
+            a = cli.slv.path_crossings(tol=tol)
             assert len(got) == len(a["robot"]) > 0 and all(len(w) == 27 for w in got)
             for k, w in enumerate(got):
                 assert (int(w[2]), int(w[4])) == (a["robot"][k], a["partner"][k])
                 for i, n in enumerate(names):
                     if n in X.DOUBLES:
-                        assert abs(float(w[6 + 2 * i]) - a[n][k]) <= 1e-6 * abs(a[n][k]), (args, extra, k, n, w)
+                        assert close_to_six_digits(w[6 + 2 * i], a[n][k]), (args, extra, k, n, w)
                     else:
                         assert int(w[6 + 2 * i]) == a[n][k], (args, extra, k, n, w)
             fleet = [l.split() for l in lines if l.startswith("crossing fleet ")]
             assert len(fleet) == 1
             contact = int(np.sum(a["flags"] & 1 != 0)); clear = int(np.sum((a["flags"] & 3) == 2))
             assert [int(fleet[0][i]) for i in (3, 5, 7, 9)] == [len(a["robot"]), contact, len(a["robot"]) - contact - clear, clear]
-    slv.close()
+    cli.close()

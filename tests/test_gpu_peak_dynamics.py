@@ -4,18 +4,15 @@ Expected values come from tests/peak_dynamics_ref.py: the Python restatement of 
 level-synchronous maximising search and the length tree written out).  Every field of every record is compared with == on doubles and ints, `windows` and
 `depth` included.  The restatement itself is held against mpmath on the CPU (tests/test_peak_dynamics_ref.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import audit_ref as R
 import peak_dynamics_ref as D
-from conftest import ROOT
+from query_kit import CliCase, assert_group_equals, assert_read_only, close_to_six_digits, group_pair, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 def ref_for(pkg, slv, st=None):
@@ -188,33 +185,8 @@ def test_constructed_states(pkg, scenes):
 
 
 def test_peak_dynamics_is_read_only(pkg, scenes):
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the call drains the queues itself
-                s.iterate_async(2)
-                if asked:
-                    s.peak_dynamics(tol=0.0)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if asked:
-                    s.peak_dynamics(); s.peak_dynamics(max_depth=2, max_windows=1, length_levels=7)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    (sa, ta, la, na), (sb, tb, lb, nb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-        assert np.array_equal(na[n], nb[n]), n
-    assert ta == tb
-    assert la == lb
+    assert_read_only(pkg, scenes.hard(), lambda s: s.peak_dynamics(tol=0.0),
+                     lambda s: (s.peak_dynamics(), s.peak_dynamics(max_depth=2, max_windows=1, length_levels=7)))
 
 
 def test_interleaved_with_the_other_queries(pkg, scenes):
@@ -235,15 +207,8 @@ def test_interleaved_with_the_other_queries(pkg, scenes):
 @pytest.mark.parametrize("mode,ranks", [(1, 1), (1, 2), (1, 3), (2, 2)])
 def test_group_equals_one_context(pkg, scenes, mode, ranks):
     scene = dict(scenes.hard(), mode=mode)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0] * ranks, stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for tol, levels in ((None, None), (0.0, 7)):
-            x, y = one.peak_dynamics(tol=tol, length_levels=levels), grp.peak_dynamics(tol=tol, length_levels=levels)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, tol, levels, k)
+    one, grp = group_pair(pkg, scene, ranks)
+    assert_group_equals(one, grp, lambda s, tol, levels: s.peak_dynamics(tol=tol, length_levels=levels), ((None, None), (0.0, 7)))
     grp.close(); one.close()
 
 
@@ -262,66 +227,41 @@ def test_sharded_context_answers_for_its_own_robots(pkg, scenes):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec = (pkg.TjDynamicsRobot * 3)()
-    C.memset(rec, 0x5a, C.sizeof(rec))
-    before = bytes(rec)
-    call = lambda t, d, w, l, out=rec: lib.tj_peak_dynamics(ctx, C.c_double(t), C.c_int(d), C.c_int(w), C.c_int(l), out)
-    assert call(-1.0, -1, 0, -1) == -1                                   # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    assert call(float("nan"), -1, 0, -1) == -1 and call(-1.0, 41, 0, -1) == -1 and call(-1.0, -1, pkg.PEAK_FRONTIER + 1, -1) == -1 and call(-1.0, -1, 0, 13) == -1
-    assert call(-1.0, -1, 0, -1, None) == -1
-    assert bytes(rec) == before                                           # records untouched
-    for args in ((-1.0, 40, pkg.PEAK_FRONTIER, 12), (0.0, 0, 1, 0), (-1.0, -1, 0, -1)):   # the limits themselves are valid
-        assert call(*args) == 0
-        assert rec[0].length_levels == (args[3] if args[3] >= 0 else pkg.PEAK_LENGTH_LEVELS) and rec[2].speed.windows >= 40
-    lib.tj_destroy(ctx)
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec = (pkg.TjDynamicsRobot * 3)()
+        C.memset(rec, 0x5a, C.sizeof(rec))
+        before = bytes(rec)
+        call = lambda t, d, w, l, out=rec: lib.tj_peak_dynamics(ctx, C.c_double(t), C.c_int(d), C.c_int(w), C.c_int(l), out)
+        assert call(-1.0, -1, 0, -1) == -1                                   # before tj_init_state
+        init()
+        assert call(float("nan"), -1, 0, -1) == -1 and call(-1.0, 41, 0, -1) == -1 and call(-1.0, -1, pkg.PEAK_FRONTIER + 1, -1) == -1 and call(-1.0, -1, 0, 13) == -1
+        assert call(-1.0, -1, 0, -1, None) == -1
+        assert bytes(rec) == before                                           # records untouched
+        for args in ((-1.0, 40, pkg.PEAK_FRONTIER, 12), (0.0, 0, 1, 0), (-1.0, -1, 0, -1)):   # the limits themselves are valid
+            assert call(*args) == 0
+            assert rec[0].length_levels == (args[3] if args[3] >= 0 else pkg.PEAK_LENGTH_LEVELS) and rec[2].speed.windows >= 40
 
 
 def test_command_line(pkg, scenes, tmp_path):
     """--peak-dynamics and --peak-dynamics 1e-6 (one context and a two-rank group): every printed field equals the library's answer on the dumped state -- doubles to
     6 significant digits (the CLI read the scene through the file round trip), integers exactly; the fleet line names the largest time_scale; other output unchanged"""
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run([])
+    cli = CliCase(pkg, scenes, tmp_path)
     for args, tol in ((["--peak-dynamics"], None), (["--peak-dynamics", "1e-6"], 1e-6)):
-        for extra in ([], ["--devices", "0,0"]):
-            lines = run(args + extra)
-            assert [l for l in lines if not l.startswith("dynamics ") and not l.startswith("devices:")] == plain
+        for extra, lines in cli.queried(args, "dynamics "):
             words = [l.split() for l in lines if l.startswith("dynamics uav ")]
-            assert len(words) == scene["U"] and all(int(w[2]) == u for u, w in enumerate(words))
-            slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-            a = slv.peak_dynamics(tol=tol)
+            assert len(words) == cli.scene["U"] and all(int(w[2]) == u for u, w in enumerate(words))
+            a = cli.slv.peak_dynamics(tol=tol)
             for u, w in enumerate(words):
                 at = {q: w.index(q) for q in ("speed", "accel", "jerk", "length")}
                 for q in D.QUANTITIES:
                     f = dict(zip(w[at[q] + 1:at[q] + 15:2], w[at[q] + 2:at[q] + 15:2]))
                     for n, key in (("lo", "lo"), ("hi", "hi"), ("time", "time")):
-                        assert abs(float(f[key]) - a[q + "_" + n][u]) <= 1e-6 * abs(a[q + "_" + n][u]) + 1e-12, (args, extra, u, q, n, w)
+                        assert close_to_six_digits(f[key], a[q + "_" + n][u], floor=1e-12), (args, extra, u, q, n, w)
                     assert int(f["seg"]) == a[q + "_segment"][u] and int(f["flags"]) == a[q + "_flags"][u]
                 f = dict(zip(w[at["length"] + 1::2], w[at["length"] + 2::2]))
                 for key, n in (("lo", "length_lo"), ("hi", "length_hi"), ("duration", "duration"), ("time_scale", "time_scale")):
-                    assert abs(float(f[key]) - a[n][u]) <= 1e-6 * abs(a[n][u]), (args, extra, u, n, w)
+                    assert close_to_six_digits(f[key], a[n][u]), (args, extra, u, n, w)
                 assert int(f["levels"]) == a["length_levels"][u] and int(f["flags"]) == a["flags"][u]
             fleet = [l.split() for l in lines if l.startswith("dynamics fleet ")]
-            assert len(fleet) == 1 and int(fleet[0][5]) == int(np.argmax(a["time_scale"])) and abs(float(fleet[0][3]) - a["time_scale"].max()) <= 1e-6 * a["time_scale"].max()
-    slv.close()
+            assert len(fleet) == 1 and int(fleet[0][5]) == int(np.argmax(a["time_scale"])) and close_to_six_digits(fleet[0][3], a["time_scale"].max())
+    cli.close()

@@ -14,9 +14,9 @@ import audit_timed_ref as T
 import proximity_ref as X
 import timing_margin_ref as M
 from audit_ref import prims
+from query_kit import CliCase, assert_group_equals, assert_read_only, assert_sharded_refuses, close_to_six_digits, group_pair, loaded, raw_context
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 INF = float("inf")
 # tests/test_proximity_ref.py::test_truncation chooses these on the CPU: (dist, max_windows) at which some rows of the flattened fleet truncate and not all
 TRUNCATING = ((0.1, 16), (1.0, 32))
@@ -40,12 +40,6 @@ def check(pkg, slv, dist=None, tol=None, max_depth=None, max_windows=None, st=No
     key = list(zip(a["robot"], a["partner"], a["t_first_lo"]))
     assert key == sorted(key)
     return a
-
-
-def loaded(pkg, scene, st):
-    slv = pkg.Solver(scene, stop=0.0)
-    slv.set_state(st)
-    return slv
 
 
 @pytest.mark.parametrize("name", ["hard", "tiny", "tiny_coupled"])
@@ -163,29 +157,23 @@ def test_truncation(pkg, scenes, dist, max_windows):
 
 
 def test_bad_arguments(pkg, scenes):
-    lib = pkg.load_library()
-    tp = pkg.TjParams()
-    lib.tj_default_params(C.byref(tp), 1, 3, 5)
-    ctx = C.c_void_p()
-    assert lib.tj_create(C.byref(tp), C.byref(ctx)) == 0
-    rec, pairs, got = (pkg.TjProximityRow * 12)(), C.c_int(-7), C.c_int(-7)
-    rec[0].robot = -99
+    with raw_context(pkg, scenes) as (lib, ctx, init):
+        rec, pairs, got = (pkg.TjProximityRow * 12)(), C.c_int(-7), C.c_int(-7)
+        rec[0].robot = -99
 
-    def call(d, t, depth, w, out=rec, cap=12, np_=C.byref(pairs), n=C.byref(got)):
-        rc = _call(lib, ctx, d, t, depth, w, out, cap, np_, n)
-        if rc == -1:
-            assert (pairs.value, got.value, rec[0].robot) == (-7, -7, -99)              # the outputs are untouched
-        return rc
+        def call(d, t, depth, w, out=rec, cap=12, np_=C.byref(pairs), n=C.byref(got)):
+            rc = _call(lib, ctx, d, t, depth, w, out, cap, np_, n)
+            if rc == -1:
+                assert (pairs.value, got.value, rec[0].robot) == (-7, -7, -99)              # the outputs are untouched
+            return rc
 
-    assert call(0.0, -1.0, -1, 0) == -1                                                 # before tj_init_state
-    wp = np.ascontiguousarray(scenes.tiny(mode=1)["waypoints"])
-    assert lib.tj_init_state(ctx, wp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(20.0)) == 0
-    nan = float("nan")
-    assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
-    assert call(0.0, -1.0, -1, 0, n=None) == -1 and call(0.0, -1.0, -1, 0, np_=None) == -1 and call(0.0, -1.0, -1, 0, cap=-1) == -1 and call(0.0, -1.0, -1, 0, out=None) == -1
-    assert call(0.0, -1.0, -1, 4096, cap=1 << 20) == -1 and b"TJ_PROXIMITY_MAX_BYTES" in lib.tj_last_error(ctx)   # refused up front, nothing allocated
-    assert call(INF, -1.0, 40, 4096) == 0 and (pairs.value, got.value) == (6, 6) and call(0.0, 0.0, -1, 0) == 0       # still usable; the limits themselves are valid
-    lib.tj_destroy(ctx)
+        assert call(0.0, -1.0, -1, 0) == -1                                                 # before tj_init_state
+        init()
+        nan = float("nan")
+        assert call(nan, -1.0, -1, 0) == -1 and call(0.0, nan, -1, 0) == -1 and call(0.0, -1.0, 41, 0) == -1 and call(0.0, -1.0, -1, 4097) == -1
+        assert call(0.0, -1.0, -1, 0, n=None) == -1 and call(0.0, -1.0, -1, 0, np_=None) == -1 and call(0.0, -1.0, -1, 0, cap=-1) == -1 and call(0.0, -1.0, -1, 0, out=None) == -1
+        assert call(0.0, -1.0, -1, 4096, cap=1 << 20) == -1 and b"TJ_PROXIMITY_MAX_BYTES" in lib.tj_last_error(ctx)   # refused up front, nothing allocated
+        assert call(INF, -1.0, 40, 4096) == 0 and (pairs.value, got.value) == (6, 6) and call(0.0, 0.0, -1, 0) == 0       # still usable; the limits themselves are valid
     one = pkg.Solver(scenes.tiny(mode=0), stop=0.0)
     one.iterate(2)
     for dist in (None, INF):
@@ -195,96 +183,37 @@ def test_bad_arguments(pkg, scenes):
 
 
 def test_proximity_windows_is_read_only(pkg, scenes):
-    scene = scenes.hard()
-
-    def run(asked):   # one context at a time (tests/test_gpu_audit_timed.py)
-        s = pkg.Solver(scene, stop=0.0)
-        for k in range(3):
-            if k == 1:   # right behind iterate_async: the call drains the queues itself
-                s.iterate_async(2)
-                if asked:
-                    s.proximity_windows(dist=INF, tol=0.0)
-                else:
-                    s.sync()
-            else:
-                s.iterate(2)
-                if asked:
-                    s.proximity_windows(); s.proximity_windows(dist=1.0, max_depth=2, max_windows=1)
-        out = s.get_state(), s.stats(), s.launch_count()
-        s.iterate(3)
-        out += (s.get_state(),)
-        s.close()
-        return out
-
-    (sa, ta, la, na), (sb, tb, lb, nb) = run(True), run(False)
-    for n in STATE:
-        assert np.array_equal(sa[n], sb[n]), n
-        assert np.array_equal(na[n], nb[n]), n
-    assert ta == tb
-    assert la == lb
+    assert_read_only(pkg, scenes.hard(), lambda s: s.proximity_windows(dist=INF, tol=0.0),
+                     lambda s: (s.proximity_windows(), s.proximity_windows(dist=1.0, max_depth=2, max_windows=1)))
 
 
 def test_group_equals_one_context(pkg, scenes):
     """two ranks on one device (tests/test_gpu_group.py's way of building a group): bitwise one context's answer; a plain sharded context refuses"""
     scene = dict(scenes.hard(), mode=1)
-    one = pkg.Solver(scene, stop=0.0)
-    grp = pkg.Group(scene, [0, 0], stop=0.0)
-    for it in (0, 3):
-        if it:
-            one.iterate(it); grp.iterate(it)
-        for dist, tol in ((None, None), (1.0, None), (INF, 0.0)):
-            x, y = one.proximity_windows(dist=dist, tol=tol), grp.proximity_windows(dist=dist, tol=tol)
-            assert set(x) == set(y)
-            for k in x:
-                assert np.array_equal(x[k], y[k]), (it, dist, tol, k)
+    one, grp = group_pair(pkg, scene, 2)
+    x = assert_group_equals(one, grp, lambda s, dist, tol: s.proximity_windows(dist=dist, tol=tol), ((None, None), (1.0, None), (INF, 0.0)))
     n = len(x["robot"])
     rec, pairs, got = (pkg.TjProximityRow * n)(), C.c_int(0), C.c_int(0)             # a cap that ends inside the second rank's rows
     rc = _call(grp.lib, grp._g, INF, 0.0, -1, 0, rec, n - 2, C.byref(pairs), C.byref(got), fn="tj_group_proximity_windows")
     assert (rc, pairs.value, got.value) == (-3, n, -1)
     grp.close(); one.close()
-    half = pkg.Solver(scenes.hard(), stop=0.0, rank=1, world=2)
-    with pytest.raises(pkg.TrajAdmmError) as ei:
-        half.proximity_windows()
-    assert "-5" in str(ei.value) and "tj_group_proximity_windows" in str(ei.value)
-    half.close()
+    assert_sharded_refuses(pkg, scenes, lambda half: half.proximity_windows(), "tj_group_proximity_windows")
 
 
 def test_command_line(pkg, scenes, tmp_path):
     """--proximity-windows 1.0 (one context and a two-rank group): the printed rows are the library's on the dumped state, in its order -- doubles to 6
     significant digits (the CLI read the scene through the x0.2 / x5 file round trip), integers exactly -- and the fleet's line counts them"""
-    import os
-    import subprocess
-    from conftest import ROOT
-    from test_gpu_audit import load_dump
-    scene = scenes.tiny(mode=1)
-    mesh = "x.obj"
-    scenes.write_reference_files(scene, str(tmp_path), mesh)
-    os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
-    exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
-    slv = pkg.Solver(scene, stop=0.0)
+    cli = CliCase(pkg, scenes, tmp_path)
     doubles = ("t_first_lo", "t_first_hi", "t_last_lo", "t_last_hi", "within_lo", "closest", "closest_time")
-
-    def run(extra):
-        r = subprocess.run([exe, mesh, "--max-iter", "6", "--dump-state", "state.txt"] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        assert r.returncode in (0, 2), r.stderr
-        return [l for l in r.stdout.split("\n") if not l.startswith("time:")]
-
-    plain = run([])
-    for extra in ([], ["--devices", "0,0"]):
-        lines = run(["--proximity-windows", "1.0"] + extra)
-        assert [l for l in lines if not l.startswith("proximity ") and not l.startswith("devices:")] == plain
+    for extra, lines in cli.queried(["--proximity-windows", "1.0"], "proximity "):
         got = [l.split() for l in lines if l.startswith("proximity uav ")]
-        slv.set_state(load_dump(tmp_path / "state.txt", slv.get_state()))
-        a = slv.proximity_windows(dist=1.0)
+        a = cli.slv.proximity_windows(dist=1.0)
         assert len(got) == len(a["robot"]) > 0 and all(len(w) == 25 for w in got)
         for k, w in enumerate(got):
             assert (int(w[2]), int(w[4])) == (a["robot"][k], a["partner"][k])
             for n, i in zip(doubles, (6, 7, 9, 10, 12, 14, 16)):
-                assert abs(float(w[i]) - a[n][k]) <= 1e-6 * abs(a[n][k]), (extra, k, n, w)
+                assert close_to_six_digits(w[i], a[n][k]), (extra, k, n, w)
             assert [int(w[i]) for i in (18, 20, 22, 24)] == [a[n][k] for n in ("leaves", "depth", "windows", "flags")], (extra, k, w)
         fleet = [l.split() for l in lines if l.startswith("proximity fleet ")]
         assert len(fleet) == 1 and [int(fleet[0][i]) for i in (3, 5)] == [a["n_pairs"], len(a["robot"])]
-    slv.close()
+    cli.close()

@@ -47,10 +47,10 @@ import numpy as np
 import pytest
 from mpmath import mp, mpf
 
+from query_kit import STATE
 import slack_ref as S
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 TAGS = [sh[0] for sh in S.SHAPES]
 
 

@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import observe_iteration, TOL_STATE_FULL, TOL_GNORM_FULL, canon, gold, maxdiff
+from query_kit import STATE, reference_config
 
 pytestmark = pytest.mark.gpu
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 @pytest.fixture(scope="module")
@@ -192,9 +192,7 @@ def test_cli_triangle_front_end(pkg, scenes, tmp_path):
     mesh = "t.obj"
     scenes.write_reference_files(scene, str(tmp_path), mesh)
     os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":1,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config())
     exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
     r = subprocess.run([exe, mesh, "--triangles", "--dump-state", "state.txt", "--max-iter", "300"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr

@@ -9,9 +9,9 @@ from mpmath import mp, mpf
 
 import grad_ref as G
 import ls_ref as L
+from query_kit import STATE
 
 ROWS = [r[0] for r in L.ROWS]
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 def port_steps(inp):

@@ -17,15 +17,11 @@ import pytest
 import audit_ref as R
 import obstacle_approach_ref as O
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 OFFSET = 0.1
 INF = float("inf")
 STATES = ["tiny0", "tiny1", "hard0", "hard3", "tiny_tri"]
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

@@ -6,6 +6,7 @@ import pytest
 
 from conftest import backoff_exponent, canon, check_scene_matches_fixture, gold, maxdiff, rel, scene_by_name
 from oracle.pyoracle import Engine, Prims
+from query_kit import STATE
 
 
 @pytest.mark.parametrize("P", [2, 5])
@@ -332,7 +333,6 @@ def test_headline_scene_free_running_within_reference_envelope(scenes):
 
 
 # ---- coupled mode ("decouple":0): Optimization3D_multi::optimization, one shared piece_time ----------------
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 def test_coupled_stages_teacher_forced(scenes):

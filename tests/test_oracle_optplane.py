@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import canon, check_scene_matches_fixture, gold, rel
+from query_kit import STATE
 
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 
 
 def _scene(scenes, name):

@@ -20,7 +20,6 @@ PARAMS_A = dict(res=8, lam=20.0, margin=0.14, offset=0.06, mu=0.25, vel_limit=1.
 PARAMS_B = dict(res=8, lam=4.0, margin=0.06, offset=0.115, mu=0.05, vel_limit=0.9, acc_limit=0.8, kt=0.4, piece_time0=20.0, stop=1e-2)
 PARAM_SETS = {"A": PARAMS_A, "B": PARAMS_B}
 PARAM_FIELDS = ("lam", "margin", "offset", "mu", "vel_limit", "acc_limit", "ks", "kt", "piece_time0", "res")
-STATE = ("spline", "p_slack", "p_lambda", "t_slack", "t_lambda", "piece_time")
 STAGE_FIXTURES = [(name, tag) for tag in ("A", "B") for name in ("hard", "hard_single", "hard_coupled")]
 TWINS = ["swap_margin_offset", "swap_vel_acc", "lam_mu_inverse", "kt_one"] + \
         [f"scale_{k}" for k in ("lam", "margin", "offset", "mu", "vel_limit", "acc_limit", "kt")]

@@ -19,15 +19,11 @@ import audit_timed_ref as T
 import closest_ref as K
 import pair_approach_ref as Q
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 LD = np.longdouble
 OFFSET, DEFAULT = 0.1, 0.1 + 2 * 0.1
 STATES = [("e2e_scn_b", DEFAULT), ("e2e_scn_c3", DEFAULT), ("e2e_scn_b_coupled", DEFAULT), ("chase", np.inf), ("crossing", np.inf), ("hover", np.inf)]
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

@@ -21,6 +21,7 @@ import audit_timed_ref as T
 import pair_approach_ref as Q
 import path_crossing_ref as X
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 OFFSET, DEFAULT = 0.1, 0.1 + 2 * 0.1
 INF = float("inf")
@@ -28,11 +29,6 @@ INF = float("inf")
 CASES = [("tiny", INF, None), ("hard", INF, None), ("hard", DEFAULT, None),
          ("e2e_scn_b", DEFAULT, [(0, 1), (1, 2), (3, 4), (0, 7)]), ("e2e_scn_c3", DEFAULT, [(0, 1), (1, 2), (20, 21), (62, 63)]),
          ("e2e_scn_b_coupled", DEFAULT, [(0, 1), (1, 2), (3, 4), (0, 7)]), ("e2e_scn_c3_flat", DEFAULT, [(0, 1), (0, 32), (5, 40), (17, 50)])]
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,17 +22,13 @@ import audit_ref as R
 import audit_timed_ref as T
 import peak_dynamics_ref as D
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 EPS = 2.0 ** -53
 MEASURED_EXCESS = 1.72e-16                  # the largest (truth - hi) / hi0 seen (tiny(mode=1)'s initial state, tol = 0)
 MARGIN = max(16 * MEASURED_EXCESS, 64 * EPS)
 STATES = ["e2e_scn_a", "e2e_scn_b", "e2e_scn_c3", "e2e_scn_b_coupled", "tiny0", "tiny1"]
 VEL, ACC = 2.0, 2.0
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import check_scene_matches_fixture, gold
+from query_kit import reference_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,9 +102,7 @@ def test_cli_init_2_plans_and_writes_the_init_file(pkg, scenes, tmp_path):
         for a, b in zip(starts, goals):
             f.write(" ".join("%.17g" % v for v in list(a) + list(b)) + "\n")
     os.makedirs(tmp_path / "Config_File", exist_ok=True)
-    (tmp_path / "Config_File" / "3D.json").write_text(
-        '{"auto":0,"init":2,"gui":0,"optimal_plane":0,"decouple":1,"res":8,"vel_limit":2,"acc_limit":2,"lambda":1e1,'
-        '"epsilon":1e-1,"margin":1e-1,"offset":1e-1,"stop":1e-2,"exit":0,"init_ob":1,"mu":0.1}')
+    (tmp_path / "Config_File" / "3D.json").write_text(reference_config(init=2))
     exe = os.path.join(ROOT, "traj-opt-admm_amd", "multiPathPlanning3D")
     r = subprocess.run([exe, mesh, "--max-iter", "400"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr + r.stdout[-500:]

@@ -20,6 +20,7 @@ import audit_timed_ref as T
 import proximity_ref as X
 import timing_margin_ref as M
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 OFFSET, VEL = 0.1, 2.0
 INF = float("inf")
@@ -30,11 +31,6 @@ BUILT = [("chase", 0.1), ("chase", 1.0), ("crossing", 2.5), ("crossing", 2.2), (
 # (chosen here, on the CPU: 8 truncates 3810 of 4032 rows, 16 truncates 518, at depths 2 .. 10; tests/test_gpu_proximity.py uses it on robots 0..7, where it
 # truncates 32 of 56 rows, and adds (1.0, 32), which overflows among the seeds for 50 of 56)
 TRUNC_DIST, TRUNC_WINDOWS = 0.1, 16
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

@@ -23,6 +23,7 @@ import pair_approach_ref as Q
 import path_crossing_ref as X
 import timing_margin_ref as M
 from conftest import ROOT
+from query_kit import pkg_module as _pkg
 
 OFFSET, VEL = 0.1, 2.0
 INF = float("inf")
@@ -30,11 +31,6 @@ TOL = M.default_tol(OFFSET, VEL)
 # (state, dist, pairs or None = all)
 CASES = [("tiny", 0.1, None), ("tiny", 0.3, None), ("hard", 0.1, None), ("hard", 0.3, None),
          ("e2e_scn_c3_flat_staggered", 0.1, [(0, 1), (0, 32), (5, 40), (17, 50), (62, 63)])]
-
-
-def _pkg():
-    import importlib
-    return importlib.import_module("traj-opt-admm_amd")
 
 
 @functools.lru_cache(maxsize=None)

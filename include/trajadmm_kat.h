@@ -87,6 +87,15 @@ int tj_kat_plan(const tj_ctx* c, const tj_params* p, const int* facts, int* out,
  * Returns the number of ints written, 0 for bad arguments or a shape the planner refuses, -needed if cap is too small. */
 int tj_kat_launches(const tj_ctx* c, const tj_params* p, const int* facts, int lsc_follow, int* state, const int* calls, int n_calls, int* out, int cap);
 
+/* ---- the device arrays of a context (csrc/tj_api.hip: device_arrays) --------------------------------
+ * The declaration table every allocation, checkpoint region, reset and host copy takes its sizes from, as four ints per array -- element count, element size in
+ * bytes, 1 if the array is part of the checkpoint, what tj_init_state fills it with (0 nothing, 1 zero bytes, 2 one bytes) -- in declaration order, and the arrays'
+ * names (the members of Dev) as one comma-joined string in names[].
+ *   c != NULL: that context's own table (p and facts are ignored).
+ *   c == NULL: the table of the planner's Dev on the caller's parameters and facts[] (as tj_kat_plan); needs no device.
+ * Returns the number of arrays, 0 for bad arguments or a shape the planner refuses, -count if cap (ints) or names_cap (chars) is too small. */
+int tj_kat_arrays(const tj_ctx* c, const tj_params* p, const int* facts, int* out, int cap, char* names, int names_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -377,7 +377,7 @@ class TrajAdmmError(RuntimeError):
 
 
 # the known-answer hooks (include/trajadmm_kat.h) live in a TEST build of the same translation unit, never in the product library
-KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_kdop_wave", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_launches", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record"]
+KAT_EXPORTS = ["tj_kat_gjk", "tj_kat_gjk_wave", "tj_kat_gjk_wave_split", "tj_kat_planes", "tj_kat_ccd", "tj_kat_tri", "tj_kat_kdop_wave", "tj_kat_query", "tj_kat_query_form", "tj_kat_linalg", "tj_kat_plan", "tj_kat_launches", "tj_kat_set_local_grad", "tj_kat_get_hull_record", "tj_kat_get_swept_record", "tj_kat_arrays"]
 KAT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtrajadmm_kat.so")
 _lib = None
 _kat_lib = None
@@ -449,6 +449,22 @@ def plan_record(params=None, facts=None, ctx=None):
         raise TrajAdmmError(f"tj_kat_plan returned {n}, the package knows {out.size} entries")
     v = [int(x) for x in out]
     return dict(zip(PLAN_FACTS, v)), dict(zip(PLAN_FIELDS, v[len(PLAN_FACTS):])), msg.value.decode()
+
+
+# the declaration table of a context's device arrays (tj_kat_arrays, csrc/tj_api.hip: device_arrays): per array its name and these
+ARRAY_FIELDS = ("n", "elem", "snap", "reset")   # element count, element size, part of the checkpoint, what tj_init_state fills it with (0 nothing, 1 zero bytes, 2 one bytes)
+
+
+def arrays_record(params=None, facts=None, ctx=None):
+    """[(name, n, elem, snap, reset), ...] of a context (ctx: its tj_ctx pointer) or -- no GPU needed -- of the planner's Dev on a TjParams and a dict of PLAN_FACTS."""
+    lib = load_library(kat=True)
+    f = np.array([facts[k] for k in PLAN_FACTS] if facts else [0] * len(PLAN_FACTS), dtype=np.int32)
+    out = np.zeros(4 * 256, dtype=np.int32)
+    names = C.create_string_buffer(8192)
+    n = lib.tj_kat_arrays(ctx, C.byref(params) if params is not None else None, _i(f), _i(out), C.c_int(out.size), names, C.c_int(8192))
+    if n <= 0:
+        raise TrajAdmmError(f"tj_kat_arrays returned {n}")
+    return [(name,) + tuple(int(x) for x in out[4 * i:4 * i + 4]) for i, name in enumerate(names.value.decode().split(","))]
 
 
 # the launch sequence's records (tj_kat_launches, csrc/host_launch.h): SchedState, Launch, the ids beyond the K_* kernels, the schedules
@@ -733,24 +749,30 @@ class Solver:
         return g.value, w.value
 
     # ---- known-answer hooks (device primitives on caller batches) -------------------------------
-    def kat_gjk(self, a, b):
+    def _kat_gjk(self, fn, a, b, k, *extra):
+        """the three GJK hooks: bodies a[n][n1][3], b[n][n2][3] in, (n, k) out"""
         a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-        n = a.shape[0]; v = np.zeros((n, 3))
-        self._check(self.lib.tj_kat_gjk(self._ctx, C.c_int(n), C.c_int(a.shape[1]), _d(a), C.c_int(b.shape[1]), _d(b), _d(v)))
-        return v
+        n = a.shape[0]; out = np.zeros((n, k))
+        self._check(fn(self._ctx, C.c_int(n), C.c_int(a.shape[1]), _d(a), C.c_int(b.shape[1]), _d(b), *extra, _d(out)))
+        return out
+
+    def kat_gjk(self, a, b):
+        return self._kat_gjk(self.lib.tj_kat_gjk, a, b, 3)
 
     def kat_gjk_wave(self, a, b):
-        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-        n = a.shape[0]; v = np.zeros((n, 3))
-        self._check(self.lib.tj_kat_gjk_wave(self._ctx, C.c_int(n), C.c_int(a.shape[1]), _d(a), C.c_int(b.shape[1]), _d(b), _d(v)))
-        return v
+        return self._kat_gjk(self.lib.tj_kat_gjk_wave, a, b, 3)
 
     def kat_gjk_wave_split(self, a, b, k_stop):
         """gjk_wave interrupted after k_stop iterations and continued from the state it left in memory: (witness vectors, iterations)"""
-        a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-        n = a.shape[0]; out = np.zeros((n, 4))
-        self._check(self.lib.tj_kat_gjk_wave_split(self._ctx, C.c_int(n), C.c_int(a.shape[1]), _d(a), C.c_int(b.shape[1]), _d(b), C.c_int(k_stop), _d(out)))
+        out = self._kat_gjk(self.lib.tj_kat_gjk_wave_split, a, b, 4, C.c_int(k_stop))
         return out[:, :3], out[:, 3].astype(int)
+
+    def _kat_rows(self, fn, arrays, k, head=(), mid=(), tail=()):
+        """the hooks that take a list of float64 arrays of n cases each and give (n, k): fn(ctx, *head, n, *mid, *arrays, *tail, out)"""
+        arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in arrays]
+        n = arrs[0].shape[0]; out = np.zeros((n, k))
+        self._check(fn(self._ctx, *head, C.c_int(n), *mid, *[_d(x) for x in arrs], *tail, _d(out)))
+        return out
 
     def kat_hull_record(self):
         """the hull cache as its last writer left it: (hullinfo [U][S][122], hbox [S][6][U])"""
@@ -769,10 +791,7 @@ class Solver:
         return info, cbox
 
     def kat_planes(self, what, P, Q, dist):
-        P = np.ascontiguousarray(P, dtype=np.float64); Q = np.ascontiguousarray(Q, dtype=np.float64)
-        n = P.shape[0]; out = np.zeros((n, 5))
-        self._check(self.lib.tj_kat_planes(self._ctx, C.c_int(what), C.c_int(n), _d(P), _d(Q), C.c_double(dist), _d(out)))
-        return out
+        return self._kat_rows(self.lib.tj_kat_planes, (P, Q), 5, head=(C.c_int(what),), tail=(C.c_double(dist),))
 
     def kat_refine_planes(self, what, P, Q, cd):
         """what 5: Optimal_plane::optimal_cd (Q = points), 6: self_optimal_cd (Q = hulls); cd[n][4] = planes to refine.
@@ -827,10 +846,7 @@ class Solver:
         return wp[:, :n.value].copy()
 
     def kat_ccd(self, P, D, Q, E, q, tu, d):
-        arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in (P, D, Q, E, q, tu)]
-        n = arrs[0].shape[0]; out = np.zeros((n, 2))
-        self._check(self.lib.tj_kat_ccd(self._ctx, C.c_int(n), *[_d(x) for x in arrs], C.c_double(d), _d(out)))
-        return out
+        return self._kat_rows(self.lib.tj_kat_ccd, (P, D, Q, E, q, tu), 2, tail=(C.c_double(d),))
 
     def kat_query(self, boxes, margin, cap=2048, sort=True, unroll=4, pre=False):
         """raw broad-phase candidate SETS of caller-supplied query boxes [nq][6] (lo, hi): list of sorted id arrays (sort=False: in the walk's own order).
@@ -844,10 +860,7 @@ class Solver:
         return [np.sort(ids[q, :counts[q]]) if sort else ids[q, :counts[q]].copy() for q in range(nq)]
 
     def kat_tri(self, P, D, tri, t, dist, off):
-        arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in (P, D, tri, t)]
-        n = arrs[0].shape[0]; out = np.zeros((n, 8))
-        self._check(self.lib.tj_kat_tri(self._ctx, C.c_int(n), *[_d(x) for x in arrs], C.c_double(dist), C.c_double(off), _d(out)))
-        return out
+        return self._kat_rows(self.lib.tj_kat_tri, (P, D, tri, t), 8, tail=(C.c_double(dist), C.c_double(off)))
 
     def kat_kdop_wave(self, P, bodies, d, D=None, t=None, nc=None):
         """the obstacle 49-axis cull as the walks run it, one wave per case: P[n][6][3], bodies[n][per][prim][3] (prim 1 or 3, per <= 64) -> pass[n][per];
@@ -863,10 +876,7 @@ class Solver:
         return out
 
     def kat_linalg(self, mats):
-        mats = np.ascontiguousarray(mats, dtype=np.float64)
-        out = np.zeros((mats.shape[0], 2))
-        self._check(self.lib.tj_kat_linalg(self._ctx, C.c_int(mats.shape[0]), C.c_int(mats.shape[1]), _d(mats), _d(out)))
-        return out
+        return self._kat_rows(self.lib.tj_kat_linalg, (mats,), 2, mid=(C.c_int(np.shape(mats)[1]),))
 
     def kat_set_local_grad(self, lg, lh):
         """the per-piece blocks of the whole fleet from the host (tj_kat_set_local_grad): lg[U][P][19], lh[U][P][19][19] -- what local_grad reads back and

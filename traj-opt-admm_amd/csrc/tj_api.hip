@@ -68,6 +68,12 @@ struct CrossQueue {
 // The checkpoint a batch can be restored from (heal_check; the careful re-run of a coupled sharded group, tj_group_iterate), touched by checkpoint_take / _restore / _drop
 // only.  Device half: the regions of `tab` and the control block, copied to an arena of tj_create (SchedState::ck_in_begin: taken by the next k_begin).  Host half: the flags that describe it.
 struct Checkpoint { SnapRegion* tab = nullptr; int n = 0; Ctl* ctl = nullptr; bool begin_folded = false, maybe_deferred = false; int lsc_base = 0; };
+// One device array of a context, declared once (device_arrays): its name, where its pointer lives, its element count and size, whether it is part of the checkpoint, and
+// what tj_init_state fills it with (0: nothing).  tj_create allocates from the table, builds the checkpoint's region table from it and keeps it (tj_ctx::arrays); tj_init_state
+// resets from it; every host copy or clear of a context array takes its bounds from it (array_clear, fetch, store, array_count).  No extent is written a second time.
+constexpr int SNAP = 1;   // self-healing: what a batch's first state consists of (everything an iteration reads that an earlier iteration wrote and that is not rebuilt or re-stamped anyway)
+constexpr int ZERO = 2, ONES = 4;   // tj_init_state: all-zero bytes / all-one bytes (ls_hist: -1, no line search yet; ls_tab: LS_TAB_EMPTY)
+struct ArrayDecl { const char* name; void** slot; size_t n, elem; bool snap; int reset; };
 
 // what a context holds for a row-listing query (tj_pair_approach, tj_path_crossings, tj_timing_margin; listed_run)
 template <class Args, class Rec>
@@ -86,6 +92,7 @@ struct tj_ctx {
   bool own_stream = true;
   bool maybe_deferred = false;                    // an iteration chain ran since the last flush
   std::vector<void*> allocs;
+  std::vector<ArrayDecl> arrays;   // the declaration table (device_arrays): the slots point into d, which does not move
   std::string err;
   bool have_cloud = false, have_state = false;
   CrossQueue xq;
@@ -104,7 +111,7 @@ struct tj_ctx {
   XchPeers* xch_table = nullptr;
   // cloud-dependent allocations (rebuilt by tj_set_cloud)
   std::vector<void*> cloud_allocs;
-  std::vector<int> cloud_order;   // sorted position -> index in the caller's cloud (ids of tj_get/set_obs_cache)
+  std::vector<int> cloud_order, cloud_rank;   // sorted position -> index in the caller's cloud, and its inverse (ids_to_caller, ids_to_sorted)
   double cloud_lo[3] = {0, 0, 0}, cloud_hi[3] = {0, 0, 0};   // bounding box of the cloud (planner bounds, Main/multiPathPlanning3D.cpp:211-218)
   double bvh_build_ms = 0;   // device time of the last BVH build (tj_get_build_info)
   int bvh_on_device = 0;
@@ -178,6 +185,36 @@ int upload(tj_ctx* c, const void* dst, const void* src, size_t bytes) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return TJ_OK;
 }
+
+// ---- host access to the context's device arrays: the bounds come from the declaration table (tj_ctx::arrays), never from the caller ----
+// elements [off, off + n) of array `dev` lie inside what the table declares for it; else TJ_ERR_DEVICE, the array named.  a: its declaration
+template <class T>
+int array_range(tj_ctx* c, const T* dev, size_t off, size_t n, const ArrayDecl** a = nullptr) {
+  const ArrayDecl* e = nullptr;
+  for (const ArrayDecl& x : c->arrays) if (*x.slot == (const void*)dev) e = &x;
+  if (a) *a = e;
+  if (e && e->elem == sizeof(T) && off <= e->n && n <= e->n - off) return TJ_OK;
+  c->err = std::string("device array ") + (e ? e->name : "(not declared)") + ": elements [" + std::to_string(off) + ", " + std::to_string(off + n) + ") of " + std::to_string(sizeof(T)) + " bytes are outside its extent";
+  return TJ_ERR_DEVICE;
+}
+template <class T>
+size_t array_count(tj_ctx* c, const T* dev) { const ArrayDecl* a; return array_range(c, dev, 0, 0, &a) ? 0 : a->n; }
+// the whole array to zero bytes, on the context's stream
+template <class T>
+int array_clear(tj_ctx* c, T* dev) {
+  if (int r = array_range(c, dev, 0, 0)) return r;
+  HIPCHK(c, hipMemsetAsync(dev, 0, array_count(c, dev) * sizeof(T), c->stream));
+  return TJ_OK;
+}
+// elements [off, off + n) to the host, blocking (the caller has drained the context: QUIESCE) / from the host (upload: on the context's stream, waited for)
+template <class T>
+int fetch(tj_ctx* c, T* host, const T* dev, size_t off, size_t n) {
+  if (int r = array_range(c, dev, off, n)) return r;
+  HIPCHK(c, hipMemcpy(host, dev + off, n * sizeof(T), hipMemcpyDeviceToHost));
+  return TJ_OK;
+}
+template <class T>
+int store(tj_ctx* c, T* dev, size_t off, const T* host, size_t n) { const int r = array_range(c, dev, off, n); return r ? r : upload(c, dev + off, host, n * sizeof(T)); }
 
 // ---- the templates of the read-only queries' host path (further down, with the rest of it) ----
 // a buffer of the queries: allocated once; what an earlier call got before an allocation failed is kept, only the missing ones are retried
@@ -361,7 +398,7 @@ int heal_check(tj_ctx* c, int err_known) {
   int r = restart_pairings(c, false);
   if (r || (r = checkpoint_restore(c))) return r;
   checkpoint_drop(c);   // (the run enqueued again stays on one queue: nothing of it is healed)
-  HIPCHK(c, hipMemsetAsync(c->d.xf_seg, 0, (size_t)2 * c->d.S * XF_SEG_STRIDE * sizeof(int), c->stream)); HIPCHK(c, hipMemsetAsync(c->d.spec_n, 0, 8, c->stream));   // (spec_n: head-start lists of the abandoned iterations, launch shape only)
+  if ((r = array_clear(c, c->d.xf_seg)) || (r = array_clear(c, c->d.spec_n))) return r;   // (spec_n: head-start lists of the abandoned iterations, launch shape only)
   if ((r = tj_iterate_async(c, (int)n))) return r;
   QUIESCE_NOHEAL(c);
   return TJ_OK;
@@ -422,6 +459,23 @@ bool ready(tj_ctx* c) {
   if (!c->have_cloud) { c->err = "tj_set_cloud has not been called"; return false; }
   if (!c->have_state) { c->err = "tj_init_state has not been called"; return false; }
   return true;
+}
+
+// Obstacle ids: the device holds positions of the build's sorted order, the caller speaks of indices into its own cloud / face list.  To the caller's (cloud_order), in place ...
+void ids_to_caller(const tj_ctx* c, int* ids, size_t n) { for (size_t i = 0; i < n; i++) ids[i] = c->cloud_order[ids[i]]; }
+// ... and back, through the inverse that the first call after set_obstacles makes; false: an id outside the caller's list
+bool ids_to_sorted(tj_ctx* c, const int* ids, size_t n, int* sorted) {
+  std::vector<int>& rank = c->cloud_rank;
+  if (rank.size() != c->cloud_order.size()) { rank.resize(c->cloud_order.size()); for (size_t i = 0; i < rank.size(); i++) rank[c->cloud_order[i]] = (int)i; }
+  for (size_t i = 0; i < n; i++) { if (ids[i] < 0 || (size_t)ids[i] >= rank.size()) return false; sorted[i] = rank[ids[i]]; }
+  return true;
+}
+// the id list of (robot, segment) s, cap_obs slots each: its count n, and min(n, cap) ids in the caller's numbering
+int fetch_ids(tj_ctx* c, const int* count, const int* list, size_t s, int cap, int* ids, int& n) {
+  int r = fetch(c, &n, count, s, 1);
+  if (r || std::min(n, cap) <= 0 || !ids) return r;
+  if (!(r = fetch(c, ids, list, s * c->d.cap_obs, std::min(n, cap)))) ids_to_caller(c, ids, std::min(n, cap));
+  return r;
 }
 
 }  // namespace
@@ -545,48 +599,50 @@ int upload_tables(tj_ctx* c) {
   return TJ_OK;
 }
 
-// One device array of a context: where its pointer lives, its element count and size, and whether it is part of the checkpoint.  tj_create allocates from this
-// list and builds the checkpoint's region table from it, so no size is written twice.
-struct ArrayDecl { void** slot; size_t n, elem; bool snap; };
+// The declaration table (ArrayDecl, at the top): one ARR per array, flags SNAP | ZERO | ONES.  What tj_init_state fills is what the mains start from: epochs and tags
+// restart (ostamp, pairstamp, pairbits, ls_word, pair_ovf_list, spec_tag), counts and statistics are empty, the persistent plane tables are off.  The payload behind a
+// zeroed count (oplanes, kobs_id, kobs_cd, kpair_list, kpair_cd, ...) and what every iteration rebuilds before reading it (lg, lh, hullinfo, ccdinfo, ...) is left alone.
 template <class T>
-ArrayDecl arr(T*& p, size_t n, bool snap = false) { return ArrayDecl{(void**)&p, n, sizeof(T), snap}; }
-constexpr bool SNAP = true;   // self-healing: what a batch's first state consists of (everything an iteration reads that an earlier iteration wrote and that is not rebuilt or re-stamped anyway)
+ArrayDecl arr(const char* name, T*& p, size_t n, int flags = 0) { return ArrayDecl{name, (void**)&p, n, sizeof(T), (flags & SNAP) != 0, flags & (ZERO | ONES)}; }
+#define ARR(member, ...) arr(#member, d.member, __VA_ARGS__)
 
 std::vector<ArrayDecl> device_arrays(Dev& d) {
   const size_t U = d.U, S = d.S, P = d.P, T = d.T, owned = d.u1 - d.u0, n = 9 * P - 2, co = d.cap_obs, cs = d.cap_self;
   const bool multi = d.mode >= 1;
   std::vector<ArrayDecl> a = {
-    arr(d.spline, U * 3 * T, SNAP), arr(d.p_slack, U * 18 * P, SNAP), arr(d.p_lambda, U * 18 * P, SNAP), arr(d.t_slack, U * P, SNAP), arr(d.t_lambda, U * P, SNAP), arr(d.piece_time, U, SNAP),
-    arr(d.oplanes, U * S * co * 4), arr(d.ocount, U * S), arr(d.splanes, U * S * cs * 4), arr(d.scount, U * S),
-    arr(d.lg, U * P * 19), arr(d.lh, U * P * 361), arr(d.xdir, U * d.xs, SNAP),
-    arr(d.k_obs, U), arr(d.k_self, U), arr(d.step_out, U, SNAP), arr(d.ls_hist, U, SNAP), arr(d.grad_cost, owned * P), arr(d.grad_perm, owned * P), arr(d.ls_tab, U * LS_TAB_STRIDE), arr(d.ls_word, U),
-    arr(d.ccdinfo, U * S * CCD_STRIDE), arr(d.pair_list, ACT_CAP),
-    arr(d.seg_stats, U * S * 6, SNAP), arr(d.pair_stats, U * S * 2, SNAP), arr(d.blk_stats, U * P + U, SNAP),
-    arr(d.hullinfo, U * S * HULL_INFO_STRIDE), arr(d.hbox, S * 6 * U), arr(d.cbox, S * 6 * U), arr(d.pairplane, multi ? S * U * U * 4 : 1),
-    arr(d.pairstamp, multi ? S * U * U : 1), arr(d.pairbits, multi ? S * U * ((U + 63) / 64) : 1),
-    arr(d.pair_work, 3 * (size_t)d.cap_work), arr(d.pair_work_n, S + 1), arr(d.pair_ovf, 4), arr(d.seq_gmem_d, SeqLayout(d.U, ACT_CAP, true).tree_doubles), arr(d.seq_gmem_i, SeqLayout(d.U, ACT_CAP, true).tree_ints),
-    arr(d.spec_n, 2), arr(d.spec_list, 2 * SPEC_CAP), arr(d.spec_tag, SPEC_CAP), arr(d.spec_state, SPEC_CAP * SPEC_STATE_DOUBLES), arr(d.spec_sti, SPEC_CAP * SPEC_STATE_INTS),
-    arr(d.pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX), arr(d.ctl, 1),
-    arr(d.ocand, U * S * co), arr(d.ocand_n, U * S), arr(d.ohull, U * S * 18),
-    arr(d.obs_work, 2 * U * S * co), arr(d.obs_work_n, 1), arr(d.oraw, U * S * co * 4), arr(d.ostamp, U * S * co),
-    arr(d.grad_scr, owned * P * 16 * (co + cs)), arr(d.xs_scr, d.xs_band ? owned * (n * n + 4 * n) : 1),
-    arr(d.xf_seg, 2 * S * XF_SEG_STRIDE), arr(d.xs_sync, Dev::xs_sync_ints(d.U)), arr(d.keep_sync, Dev::keep_sync_ints()), arr(d.fa_sync, Dev::fa_sync_ints(d.U))};
+    ARR(spline, U * 3 * T, SNAP), ARR(p_slack, U * 18 * P, SNAP), ARR(p_lambda, U * 18 * P, SNAP), ARR(t_slack, U * P, SNAP), ARR(t_lambda, U * P, SNAP), ARR(piece_time, U, SNAP),
+    ARR(oplanes, U * S * co * 4), ARR(ocount, U * S, ZERO), ARR(splanes, U * S * cs * 4), ARR(scount, U * S, ZERO),
+    ARR(lg, U * P * 19), ARR(lh, U * P * 361), ARR(xdir, U * d.xs, SNAP | ZERO),
+    ARR(k_obs, U), ARR(k_self, U), ARR(step_out, U, SNAP), ARR(ls_hist, U, SNAP | ONES), ARR(grad_cost, owned * P, ZERO), ARR(grad_perm, owned * P), ARR(ls_tab, U * LS_TAB_STRIDE, ONES), ARR(ls_word, U, ZERO),
+    ARR(ccdinfo, U * S * CCD_STRIDE), ARR(pair_list, ACT_CAP),
+    ARR(seg_stats, U * S * 6, SNAP | ZERO), ARR(pair_stats, U * S * 2, SNAP | ZERO), ARR(blk_stats, U * P + U, SNAP | ZERO),
+    ARR(hullinfo, U * S * HULL_INFO_STRIDE), ARR(hbox, S * 6 * U), ARR(cbox, S * 6 * U), ARR(pairplane, multi ? S * U * U * 4 : 1),
+    ARR(pairstamp, multi ? S * U * U : 1, ZERO), ARR(pairbits, multi ? S * U * ((U + 63) / 64) : 1, ZERO),
+    ARR(pair_work, 3 * (size_t)d.cap_work), ARR(pair_work_n, S + 1), ARR(pair_ovf, 4, ZERO), ARR(seq_gmem_d, SeqLayout(d.U, ACT_CAP, true).tree_doubles), ARR(seq_gmem_i, SeqLayout(d.U, ACT_CAP, true).tree_ints),
+    ARR(spec_n, 2, ZERO), ARR(spec_list, 2 * SPEC_CAP), ARR(spec_tag, SPEC_CAP, ZERO), ARR(spec_state, SPEC_CAP * SPEC_STATE_DOUBLES), ARR(spec_sti, SPEC_CAP * SPEC_STATE_INTS),
+    ARR(pair_ovf_list, (size_t)d.cap_work + PAIR_CONSUMERS_MAX, ZERO), ARR(ctl, 1),
+    ARR(ocand, U * S * co), ARR(ocand_n, U * S, ZERO), ARR(ohull, U * S * 18),
+    ARR(obs_work, 2 * U * S * co), ARR(obs_work_n, 1), ARR(oraw, U * S * co * 4), ARR(ostamp, U * S * co, ZERO),
+    ARR(grad_scr, owned * P * 16 * (co + cs)), ARR(xs_scr, d.xs_band ? owned * (n * n + 4 * n) : 1),
+    ARR(xf_seg, 2 * S * XF_SEG_STRIDE, ZERO), ARR(xs_sync, Dev::xs_sync_ints(d.U)), ARR(keep_sync, Dev::keep_sync_ints()), ARR(fa_sync, Dev::fa_sync_ints(d.U))};
 #ifdef TJ_PHASE_TIMING
-  a.push_back(arr(d.dbg, (size_t)K_COUNT * TJ_TIC_BLOCKS * TJ_TIC_SLOTS));
+  a.push_back(ARR(dbg, (size_t)K_COUNT * TJ_TIC_BLOCKS * TJ_TIC_SLOTS));
 #endif
   if (d.optimal_plane) {   // the planes that persist across iterations: obstacle lists (single UAV) or the dense pair table
     const bool m0 = d.mode == 0;
-    a.insert(a.end(), {arr(d.kobs_id, m0 ? U * S * co : 1, m0), arr(d.kobs_n, U * S, m0), arr(d.kobs_cd, m0 ? U * S * co * 4 : 1, m0),
-                       arr(d.kpair_on, m0 ? 1 : S * U * U, !m0), arr(d.kpair_list, m0 ? 1 : S * U * U, !m0), arr(d.kpair_n, 2, !m0), arr(d.kpair_cd, m0 ? 1 : S * U * U * 4, !m0)});
+    const int s0 = m0 ? SNAP : 0, s1 = m0 ? 0 : SNAP;
+    a.insert(a.end(), {ARR(kobs_id, m0 ? U * S * co : 1, s0), ARR(kobs_n, U * S, s0 | ZERO), ARR(kobs_cd, m0 ? U * S * co * 4 : 1, s0),
+                       ARR(kpair_on, m0 ? 1 : S * U * U, s1 | ZERO), ARR(kpair_list, m0 ? 1 : S * U * U, s1), ARR(kpair_n, 2, s1 | ZERO), ARR(kpair_cd, m0 ? 1 : S * U * U * 4, s1)});
   }
   if (d.mode == TJ_MODE_MULTI_COUPLED)
-    a.insert(a.end(), {arr(d.xL, U * (d.xs_band ? (n - 1) * BAND_BS + n : n * n)), arr(d.xy, U * n), arr(d.xg, U * n), arr(d.xcorner, U * 4), arr(d.k_obs_f, U), arr(d.ls_e, (size_t)LSC_ROUNDS * U * LS_GROUPS)});
+    a.insert(a.end(), {ARR(xL, U * (d.xs_band ? (n - 1) * BAND_BS + n : n * n)), ARR(xy, U * n), ARR(xg, U * n), ARR(xcorner, U * 4), ARR(k_obs_f, U), ARR(ls_e, (size_t)LSC_ROUNDS * U * LS_GROUPS)});
   return a;
 }
+#undef ARR
 
-// allocate the arrays and, for those of the checkpoint, an arena each and the region table k_snapshot walks
+// build the table, allocate the arrays and, for those of the checkpoint, an arena each and the region table k_snapshot walks
 int allocate_arrays(tj_ctx* c) {
-  const std::vector<ArrayDecl> arrays = device_arrays(c->d);
+  const std::vector<ArrayDecl>& arrays = c->arrays = device_arrays(c->d);
   int r;
   for (const ArrayDecl& a : arrays) if ((r = dalloc_bytes(c, a.slot, std::max<size_t>(a.n, 1) * a.elem))) return r;
   std::vector<SnapRegion> tab;
@@ -692,7 +748,7 @@ int set_obstacles(tj_ctx* c, const double* verts, int n, int prim) {
   d.N = 0; d.nlevels = 0; if (!c->hp.bvh_skip_forced) d.bvh_skip = 0; d.px = d.py = d.pz = d.tri = nullptr; d.boxes = d.leafbox = nullptr;
   for (void* p : c->cloud_allocs) hipFree(p);
   c->cloud_allocs.clear();
-  c->cloud_order.clear();
+  c->cloud_order.clear(); c->cloud_rank.clear();
   c->q_order = nullptr;
   if (n > 0) {
     for (int k = 0; k < 3; k++) { c->cloud_lo[k] = INFINITY; c->cloud_hi[k] = -INFINITY; }
@@ -819,76 +875,51 @@ int tj_init_state(tj_ctx* c, const double* wp, double pt0) {
   }
   QUIESCE(c);
   int r;
-  if ((r = upload(c, d.spline, spline.data(), spline.size() * 8)) || (r = upload(c, d.p_slack, p_slack.data(), p_slack.size() * 8)) ||
-      (r = upload(c, d.p_lambda, zeros.data(), zeros.size() * 8)) || (r = upload(c, d.t_slack, ts.data(), ts.size() * 8)) ||
-      (r = upload(c, d.t_lambda, tz.data(), tz.size() * 8)) || (r = upload(c, d.piece_time, ptv.data(), ptv.size() * 8))) return r;
-  // direct exchange: the push / arrival counts restart (the caller has every rank drained before any rank calls this, and a barrier after:
-  // tj_group_init_state does; processes use their collective's barrier)
+  // 1. the state
+  if ((r = store(c, d.spline, 0, spline.data(), spline.size())) || (r = store(c, d.p_slack, 0, p_slack.data(), p_slack.size())) ||
+      (r = store(c, d.p_lambda, 0, zeros.data(), zeros.size())) || (r = store(c, d.t_slack, 0, ts.data(), ts.size())) ||
+      (r = store(c, d.t_lambda, 0, tz.data(), tz.size())) || (r = store(c, d.piece_time, 0, ptv.data(), ptv.size()))) return r;
+  // 2. every array the table says is filled (device_arrays: ZERO, ONES).  The conditions this loop no longer states: xf_seg was cleared with Dev::xf only (without it nothing
+  // reads the counters), pairstamp and pairbits in the multi-UAV modes and kpair_on outside mode 0 only (else each is the one-element placeholder, which nothing reads);
+  // the optimal_plane tables are declared, and so filled, with optimal_plane only, as before
+  for (const ArrayDecl& a : c->arrays)
+    if (a.reset) HIPCHK(c, hipMemsetAsync(*a.slot, a.reset == ONES ? 0xff : 0, a.n * a.elem, c->stream));
+  // 3. what is not a plain fill (the two stores come last: each waits for the stream, and so for every fill above)
+  // direct exchange (the counters live in the exchange block, not in a context array): the push / arrival counts restart (the caller has every rank drained before any
+  // rank calls this, and a barrier after: tj_group_init_state does; processes use their collective's barrier)
   if (c->xch_block) HIPCHK(c, hipMemsetAsync(d.xcnt, 0, 2 * XCH_MAX * sizeof(unsigned long long), c->stream));
-  if (d.xf) HIPCHK(c, hipMemsetAsync(d.xf_seg, 0, (size_t)2 * d.S * XF_SEG_STRIDE * sizeof(int), c->stream));
   if ((r = restart_pairings(c, true))) return r;
-  Ctl h;
-  memset(&h, 0, sizeof(h));
-  h.gnorm = 1.0;  // Main/multiPathPlanning3D.cpp:594
-  if ((r = upload(c, d.ctl, &h, sizeof(h)))) return r;
+  Ctl h; memset(&h, 0, sizeof(h)); h.gnorm = 1.0;  // Main/multiPathPlanning3D.cpp:594
+  if ((r = store(c, d.ctl, 0, &h, 1))) return r;
+  std::vector<int> idp(array_count(c, d.grad_perm));   // k_grad's launch order: no history, identity
+  for (size_t i = 0; i < idp.size(); i++) idp[i] = (int)i;
+  if ((r = store(c, d.grad_perm, 0, idp.data(), idp.size()))) return r;
   c->hull_valid = false; c->ss.ccd_valid = false;
-  HIPCHK(c, hipMemsetAsync(d.xdir, 0, (size_t)U * d.xs * 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.ocount, 0, (size_t)U * d.S * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.scount, 0, (size_t)U * d.S * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.ocand_n, 0, (size_t)U * d.S * 4, c->stream));
-  if (d.optimal_plane) {  // the mains start with empty persistent tables (Main/admmPathPlanning3D.cpp:343-351, Main/multiPathPlanning3D.cpp:450-464)
-    HIPCHK(c, hipMemsetAsync(d.kobs_n, 0, (size_t)U * d.S * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(d.kpair_n, 0, 8, c->stream));
-    if (d.mode != 0) HIPCHK(c, hipMemsetAsync(d.kpair_on, 0, (size_t)d.S * U * U * 4, c->stream));
-  }
-  HIPCHK(c, hipMemsetAsync(d.ostamp, 0, (size_t)U * d.S * d.cap_obs * 4, c->stream));  // epochs restart at 1
-  HIPCHK(c, hipMemsetAsync(d.seg_stats, 0, (size_t)U * d.S * 6 * 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.pair_stats, 0, (size_t)U * d.S * 2 * 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.blk_stats, 0, ((size_t)U * d.P + U) * 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.ls_hist, 0xff, (size_t)U * 4, c->stream));   // -1: no line search yet
-  HIPCHK(c, hipMemsetAsync(d.ls_tab, 0xff, (size_t)U * LS_TAB_STRIDE * 8, c->stream));   // LS_TAB_EMPTY
-  HIPCHK(c, hipMemsetAsync(d.ls_word, 0, (size_t)U * 8, c->stream));                        // (the words carry the epoch, which restarts at 1)
-  {   // k_grad's launch order: no history, identity
-    std::vector<int> idp((size_t)(d.u1 - d.u0) * d.P);
-    for (size_t i = 0; i < idp.size(); i++) idp[i] = (int)i;
-    HIPCHK(c, hipMemsetAsync(d.grad_cost, 0, idp.size() * 4, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.grad_perm, idp.data(), idp.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  if (d.mode >= 1) HIPCHK(c, hipMemsetAsync(d.pairstamp, 0, (size_t)d.S * U * U * 4, c->stream));  // epochs restart at 1
-  if (d.mode >= 1) HIPCHK(c, hipMemsetAsync(d.pairbits, 0, (size_t)d.S * U * ((U + 63) / 64) * 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.pair_ovf_list, 0, ((size_t)d.cap_work + PAIR_CONSUMERS_MAX) * 8, c->stream));                  // (entries are tagged with the epoch)
-  HIPCHK(c, hipMemsetAsync(d.pair_ovf, 0, 16, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.spec_n, 0, 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(d.spec_tag, 0, SPEC_CAP * 8, c->stream));                                                          // (tags carry the epoch)
   c->have_state = true;
   return TJ_OK;
 }
 
+// the six state arrays and their doubles per robot, in the argument order of tj_get_state / tj_set_state
+struct StateArrays {
+  struct { double* dev; size_t per; } v[6];
+  explicit StateArrays(const Dev& d) : v{{d.spline, (size_t)3 * d.T}, {d.p_slack, (size_t)18 * d.P}, {d.p_lambda, (size_t)18 * d.P}, {d.t_slack, (size_t)d.P}, {d.t_lambda, (size_t)d.P}, {d.piece_time, 1}} {}
+};
+
 int tj_get_state(tj_ctx* c, int u, double* spline, double* p_slack, double* p_lambda, double* t_slack, double* t_lambda, double* piece_time) {
   if (!c || u < 0 || u >= c->d.U) return TJ_ERR_INVALID;
-  const Dev& d = c->d;
   QUIESCE(c);
-  if (spline) HIPCHK(c, hipMemcpy(spline, d.spline + (size_t)u * 3 * d.T, 3 * d.T * 8, hipMemcpyDeviceToHost));
-  if (p_slack) HIPCHK(c, hipMemcpy(p_slack, d.p_slack + (size_t)u * 18 * d.P, 18 * d.P * 8, hipMemcpyDeviceToHost));
-  if (p_lambda) HIPCHK(c, hipMemcpy(p_lambda, d.p_lambda + (size_t)u * 18 * d.P, 18 * d.P * 8, hipMemcpyDeviceToHost));
-  if (t_slack) HIPCHK(c, hipMemcpy(t_slack, d.t_slack + (size_t)u * d.P, d.P * 8, hipMemcpyDeviceToHost));
-  if (t_lambda) HIPCHK(c, hipMemcpy(t_lambda, d.t_lambda + (size_t)u * d.P, d.P * 8, hipMemcpyDeviceToHost));
-  if (piece_time) HIPCHK(c, hipMemcpy(piece_time, d.piece_time + u, 8, hipMemcpyDeviceToHost));
+  double* const host[6] = {spline, p_slack, p_lambda, t_slack, t_lambda, piece_time};
+  const StateArrays st(c->d);
+  for (int i = 0; i < 6; i++) if (host[i]) { int r = fetch(c, host[i], st.v[i].dev, u * st.v[i].per, st.v[i].per); if (r) return r; }
   return TJ_OK;
 }
 
 int tj_set_state(tj_ctx* c, int u, const double* spline, const double* p_slack, const double* p_lambda, const double* t_slack, const double* t_lambda, double piece_time) {
   if (!c || u < 0 || u >= c->d.U) return TJ_ERR_INVALID;
-  const Dev& d = c->d;
   QUIESCE(c);
-  int r;
-  if (spline && (r = upload(c, d.spline + (size_t)u * 3 * d.T, spline, 3 * d.T * 8))) return r;
-  if (p_slack && (r = upload(c, d.p_slack + (size_t)u * 18 * d.P, p_slack, 18 * d.P * 8))) return r;
-  if (p_lambda && (r = upload(c, d.p_lambda + (size_t)u * 18 * d.P, p_lambda, 18 * d.P * 8))) return r;
-  if (t_slack && (r = upload(c, d.t_slack + (size_t)u * d.P, t_slack, d.P * 8))) return r;
-  if (t_lambda && (r = upload(c, d.t_lambda + (size_t)u * d.P, t_lambda, d.P * 8))) return r;
-  if ((r = upload(c, d.piece_time + u, &piece_time, 8))) return r;
+  const double* const host[6] = {spline, p_slack, p_lambda, t_slack, t_lambda, &piece_time};
+  const StateArrays st(c->d);
+  for (int i = 0; i < 6; i++) if (host[i]) { int r = store(c, st.v[i].dev, u * st.v[i].per, host[i], st.v[i].per); if (r) return r; }
   c->hull_valid = false; c->ss.ccd_valid = false;
   c->have_state = true;
   return TJ_OK;
@@ -1067,19 +1098,19 @@ int tj_get_planes(tj_ctx* c, int u, int* counts_obs, int* counts_self, double* p
   const Dev& d = c->d;
   QUIESCE(c);
   std::vector<int> co(d.S), cs(d.S, 0);
-  HIPCHK(c, hipMemcpy(co.data(), d.ocount + (size_t)u * d.S, d.S * 4, hipMemcpyDeviceToHost));
-  if (d.mode >= 1) HIPCHK(c, hipMemcpy(cs.data(), d.scount + (size_t)u * d.S, d.S * 4, hipMemcpyDeviceToHost));
+  int r;
+  if ((r = fetch(c, co.data(), d.ocount, (size_t)u * d.S, d.S)) || (d.mode >= 1 && (r = fetch(c, cs.data(), d.scount, (size_t)u * d.S, d.S)))) return r;
   int total = 0;
   for (int tr = 0; tr < d.S; tr++) total += co[tr] + cs[tr];
-  if (counts_obs) memcpy(counts_obs, co.data(), d.S * 4);
-  if (counts_self) memcpy(counts_self, cs.data(), d.S * 4);
+  if (counts_obs) memcpy(counts_obs, co.data(), d.S * sizeof(int));
+  if (counts_self) memcpy(counts_self, cs.data(), d.S * sizeof(int));
   if (planes) {
     if (cap < total) { c->err = "tj_get_planes: buffer too small"; return TJ_ERR_INVALID; }
     size_t w = 0;
     for (int tr = 0; tr < d.S; tr++) {
-      if (co[tr]) HIPCHK(c, hipMemcpy(planes + 4 * w, d.oplanes + ((size_t)u * d.S + tr) * d.cap_obs * 4, (size_t)co[tr] * 32, hipMemcpyDeviceToHost));
+      if (co[tr] && (r = fetch(c, planes + 4 * w, d.oplanes, ((size_t)u * d.S + tr) * d.cap_obs * 4, (size_t)co[tr] * 4))) return r;
       w += co[tr];
-      if (cs[tr]) HIPCHK(c, hipMemcpy(planes + 4 * w, d.splanes + ((size_t)u * d.S + tr) * d.cap_self * 4, (size_t)cs[tr] * 32, hipMemcpyDeviceToHost));
+      if (cs[tr] && (r = fetch(c, planes + 4 * w, d.splanes, ((size_t)u * d.S + tr) * d.cap_self * 4, (size_t)cs[tr] * 4))) return r;
       w += cs[tr];
     }
   }
@@ -1091,17 +1122,11 @@ int tj_get_candidates(tj_ctx* c, int u, int seg, int cap, int* ids, int* n_broad
   const Dev& d = c->d;
   QUIESCE(c);
   const size_t s = (size_t)u * d.S + seg;
-  int n = 0;
-  HIPCHK(c, hipMemcpy(&n, d.ocand_n + s, 4, hipMemcpyDeviceToHost));
-  const int m = std::min(n, cap);
-  if (m > 0 && ids) {
-    std::vector<int> tmp(m);
-    HIPCHK(c, hipMemcpy(tmp.data(), d.ocand + s * d.cap_obs, (size_t)m * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < m; i++) ids[i] = c->cloud_order[tmp[i]];
-  }
+  int n = 0, r;
+  if ((r = fetch_ids(c, d.ocand_n, d.ocand, s, cap, ids, n))) return r;
   if (n_broad) {
     unsigned long long st[6];
-    HIPCHK(c, hipMemcpy(st, d.seg_stats + s * 6, sizeof(st), hipMemcpyDeviceToHost));
+    if ((r = fetch(c, st, d.seg_stats, s * 6, 6))) return r;
     *n_broad = (int)st[1];
   }
   return n;
@@ -1115,10 +1140,10 @@ int tj_set_planes(tj_ctx* c, int u, const int* counts, const double* planes) {
   std::vector<int> zero(d.S, 0);
   for (int tr = 0; tr < d.S; tr++) {
     if (counts[tr] > d.cap_obs) { c->err = "tj_set_planes: more planes than cap_obs"; return TJ_ERR_CAPACITY; }
-    if (counts[tr]) { int ur = upload(c, d.oplanes + ((size_t)u * d.S + tr) * d.cap_obs * 4, planes + 4 * w, (size_t)counts[tr] * 32); if (ur) return ur; }
+    if (counts[tr]) { int ur = store(c, d.oplanes, ((size_t)u * d.S + tr) * d.cap_obs * 4, planes + 4 * w, (size_t)counts[tr] * 4); if (ur) return ur; }
     w += counts[tr];
   }
-  { int ur; if ((ur = upload(c, d.ocount + (size_t)u * d.S, counts, d.S * 4)) || (ur = upload(c, d.scount + (size_t)u * d.S, zero.data(), d.S * 4))) return ur; }
+  { int ur; if ((ur = store(c, d.ocount, (size_t)u * d.S, counts, d.S)) || (ur = store(c, d.scount, (size_t)u * d.S, zero.data(), d.S))) return ur; }
   return TJ_OK;
 }
 
@@ -1127,14 +1152,14 @@ int tj_get_direction(tj_ctx* c, int u, double* direction, double* t_direction, d
   const Dev& d = c->d;
   QUIESCE(c);
   std::vector<double> rec(d.xs);
-  HIPCHK(c, hipMemcpy(rec.data(), d.xdir + (size_t)u * d.xs, d.xs * 8, hipMemcpyDeviceToHost));
-  if (direction) memcpy(direction, rec.data(), 3 * d.T * 8);
+  if (int r = fetch(c, rec.data(), d.xdir, (size_t)u * d.xs, d.xs)) return r;
+  if (direction) memcpy(direction, rec.data(), 3 * d.T * sizeof(double));
   if (t_direction) *t_direction = rec[3 * d.T];
   if (wolfe) *wolfe = rec[3 * d.T + 1];
   if (gn) *gn = rec[3 * d.T + 2];
   if (d.mode == TJ_MODE_MULTI_COUPLED) {  // one Newton system for all robots: report its global wolfe and gnorm
     Ctl h;
-    HIPCHK(c, hipMemcpy(&h, d.ctl, sizeof(Ctl), hipMemcpyDeviceToHost));
+    if (int r = fetch(c, &h, d.ctl, 0, 1)) return r;
     if (wolfe) *wolfe = h.wolfe_c;
     if (gn) *gn = h.gnorm;
   }
@@ -1146,19 +1171,18 @@ int tj_set_direction(tj_ctx* c, int u, const double* direction, double t_directi
   const Dev& d = c->d;
   QUIESCE(c);
   std::vector<double> rec(d.xs, 0.0);
-  memcpy(rec.data(), direction, 3 * d.T * 8);
+  memcpy(rec.data(), direction, 3 * d.T * sizeof(double));
   rec[3 * d.T] = t_direction; rec[3 * d.T + 1] = wolfe; rec[3 * d.T + 2] = gn;
   c->ss.ccd_valid = false;   // the swept-hull cache no longer matches: the next chained CCD stage rebuilds it (k_ccd_prep)
-  return upload(c, d.xdir + (size_t)u * d.xs, rec.data(), d.xs * 8);
+  return store(c, d.xdir, (size_t)u * d.xs, rec.data(), d.xs);
 }
 
 int tj_get_local_grad(tj_ctx* c, int u, int piece, double* g19, double* h361) {
   if (!c || u < 0 || u >= c->d.U || piece < 0 || piece >= c->d.P) return TJ_ERR_INVALID;
   const Dev& d = c->d;
   QUIESCE(c);
-  if (g19) HIPCHK(c, hipMemcpy(g19, d.lg + ((size_t)u * d.P + piece) * 19, 19 * 8, hipMemcpyDeviceToHost));
-  if (h361) HIPCHK(c, hipMemcpy(h361, d.lh + ((size_t)u * d.P + piece) * 361, 361 * 8, hipMemcpyDeviceToHost));
-  return TJ_OK;
+  const int r = g19 ? fetch(c, g19, d.lg, ((size_t)u * d.P + piece) * 19, 19) : TJ_OK;
+  return (r || !h361) ? r : fetch(c, h361, d.lh, ((size_t)u * d.P + piece) * 361, 361);
 }
 
 int tj_get_energy(tj_ctx* c, double* energy) {
@@ -1738,89 +1762,14 @@ int tj_get_steps(tj_ctx* c, double* step_self, double* step_obs, double* step_ar
   if (!c) return TJ_ERR_INVALID;
   const Dev& d = c->d;
   QUIESCE(c);
-  std::vector<int> ko(d.U), ks(d.U);
-  HIPCHK(c, hipMemcpy(ko.data(), d.k_obs, d.U * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(ks.data(), d.k_self, d.U * 4, hipMemcpyDeviceToHost));
+  std::vector<int> ko(array_count(c, d.k_obs)), ks(array_count(c, d.k_self));
+  int r;
+  if ((r = fetch(c, ko.data(), d.k_obs, 0, ko.size())) || (r = fetch(c, ks.data(), d.k_self, 0, ks.size()))) return r;
   auto p = [](int k) { double s = 1.0; for (int i = 0; i < k; i++) s *= 0.8; return s; };
   for (int u = 0; u < d.U; u++) { if (step_self) step_self[u] = p(ks[u]); if (step_obs) step_obs[u] = p(ko[u]); }
-  if (step_armijo) HIPCHK(c, hipMemcpy(step_armijo, d.step_out, d.U * 8, hipMemcpyDeviceToHost));
+  if (step_armijo && (r = fetch(c, step_armijo, d.step_out, 0, array_count(c, d.step_out)))) return r;
   return TJ_OK;
 }
-
-#ifdef TJ_KAT
-// ---- known-answer hooks ------------------------------------------------------------------------
-
-int tj_kat_gjk(tj_ctx* c, int n, int n1, const double* a, int n2, const double* b, double* v) {
-  if (!c || n < 0 || !a || !b || !v) return TJ_ERR_INVALID;
-  DevBuf da, db, dv; int r;
-  if ((r = to_dev(c, da, a, (size_t)n * n1 * 24)) || (r = to_dev(c, db, b, (size_t)n * n2 * 24)) || (r = to_dev(c, dv, nullptr, (size_t)n * 24))) return r;
-  dim3 g((n + 63) / 64), t(64);
-  const double *A = (const double*)da.p, *B = (const double*)db.p; double* V = (double*)dv.p;
-  if (n1 == 6 && n2 == 1) hipLaunchKernelGGL((k_dbg_gjk<6, 1>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 6 && n2 == 6) hipLaunchKernelGGL((k_dbg_gjk<6, 6>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 12 && n2 == 1) hipLaunchKernelGGL((k_dbg_gjk<12, 1>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 12 && n2 == 12) hipLaunchKernelGGL((k_dbg_gjk<12, 12>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 6 && n2 == 3) hipLaunchKernelGGL((k_dbg_gjk<6, 3>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 12 && n2 == 3) hipLaunchKernelGGL((k_dbg_gjk<12, 3>), g, t, 0, c->stream, n, A, B, V);
-  else { c->err = "tj_kat_gjk: body sizes must be 6v1, 6v3, 6v6, 12v1, 12v3 or 12v12"; return TJ_ERR_INVALID; }
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(v, dv.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-int tj_kat_gjk_wave(tj_ctx* c, int n, int n1, const double* a, int n2, const double* b, double* v) {
-  if (!c || n < 0 || !a || !b || !v) return TJ_ERR_INVALID;
-  DevBuf da, db, dv; int r;
-  if ((r = to_dev(c, da, a, (size_t)n * n1 * 24)) || (r = to_dev(c, db, b, (size_t)n * n2 * 24)) || (r = to_dev(c, dv, nullptr, (size_t)n * 24))) return r;
-  dim3 g(std::max(n, 1)), t(64);
-  const double *A = (const double*)da.p, *B = (const double*)db.p; double* V = (double*)dv.p;
-  if (n1 == 6 && n2 == 6) hipLaunchKernelGGL((k_dbg_gjk_wave<6, 6>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 12 && n2 == 12) hipLaunchKernelGGL((k_dbg_gjk_wave<12, 12>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 6 && n2 == 1) hipLaunchKernelGGL((k_dbg_gjk_wave<6, 1>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 12 && n2 == 1) hipLaunchKernelGGL((k_dbg_gjk_wave<12, 1>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 6 && n2 == 3) hipLaunchKernelGGL((k_dbg_gjk_wave<6, 3>), g, t, 0, c->stream, n, A, B, V);
-  else if (n1 == 12 && n2 == 3) hipLaunchKernelGGL((k_dbg_gjk_wave<12, 3>), g, t, 0, c->stream, n, A, B, V);
-  else { c->err = "tj_kat_gjk_wave: body sizes must be 6v1, 6v3, 6v6, 12v1, 12v3 or 12v12"; return TJ_ERR_INVALID; }
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(v, dv.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-int tj_kat_gjk_wave_split(tj_ctx* c, int n, int n1, const double* a, int n2, const double* b, int k_stop, double* v_iters) {
-  if (!c || n < 0 || !a || !b || !v_iters || k_stop < 1) return TJ_ERR_INVALID;
-  DevBuf da, db, ds, dv; int r;
-  if ((r = to_dev(c, da, a, (size_t)n * n1 * 24)) || (r = to_dev(c, db, b, (size_t)n * n2 * 24)) || (r = to_dev(c, ds, nullptr, (size_t)n * 256)) || (r = to_dev(c, dv, nullptr, (size_t)n * 32))) return r;
-  dim3 g(std::max(n, 1)), t(64);
-  const double *A = (const double*)da.p, *B = (const double*)db.p; double* S = (double*)ds.p; double* V = (double*)dv.p;
-  if (n1 == 6 && n2 == 6) hipLaunchKernelGGL((k_dbg_gjk_wave_split<6, 6>), g, t, 0, c->stream, n, A, B, k_stop, S, V);
-  else if (n1 == 12 && n2 == 12) hipLaunchKernelGGL((k_dbg_gjk_wave_split<12, 12>), g, t, 0, c->stream, n, A, B, k_stop, S, V);
-  else { c->err = "tj_kat_gjk_wave_split: body sizes must be 6v6 or 12v12"; return TJ_ERR_INVALID; }
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(v_iters, dv.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-int tj_kat_planes(tj_ctx* c, int what, int n, const double* P, const double* Q, double dist, double* out) {
-  if (!c || n < 0 || what < 0 || what > 7 || !P || !Q || !out) return TJ_ERR_INVALID;
-  const size_t qbytes = (what == 0 || what == 2 || what == 5) ? (size_t)n * 24 : (size_t)n * 144;  // what 1, 3, 4, 6: hull vs hull
-  DevBuf dp, dq, dout; int r;
-  if ((r = to_dev(c, dp, P, (size_t)n * 144)) || (r = to_dev(c, dq, Q, qbytes)) || (r = to_dev(c, dout, nullptr, (size_t)n * 40))) return r;
-  HIPCHK(c, hipMemsetAsync(dout.p, 0, std::max<size_t>((size_t)n * 40, 8), c->stream));
-  if (what >= 5 && n > 0) { int ur = upload(c, dout.p, out, (size_t)n * 40); if (ur) return ur; }  // in/out: the plane to refine
-  if (what == 7) hipLaunchKernelGGL(k_dbg_optpair_wave, dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)dp.p, (const double*)dq.p, (double*)dout.p);
-  else if (what == 2) hipLaunchKernelGGL((k_dbg_kdop_wave<1, false>), dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)dp.p, nullptr, nullptr, (const double*)dq.p, 1, nullptr, dist, (double*)dout.p, 5);
-  else if (what == 4) hipLaunchKernelGGL(k_dbg_pair_wave, dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)dp.p, (const double*)dq.p, dist, (double*)dout.p);
-  else hipLaunchKernelGGL(k_dbg_planes, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d, what, n, (const double*)dp.p, (const double*)dq.p, dist, (double*)dout.p);
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * 40, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-#endif  // TJ_KAT
 
 // ---- "optimal_plane":1 : host access to the persistent plane tables (teacher-forced parity tests, checkpointing) ----
 int tj_get_obs_cache(tj_ctx* c, int u, int seg, int cap, int* ids, double* cd) {
@@ -1829,15 +1778,9 @@ int tj_get_obs_cache(tj_ctx* c, int u, int seg, int cap, int* ids, double* cd) {
   if (!d.optimal_plane || d.mode != 0) { c->err = "tj_get_obs_cache: needs optimal_plane and TJ_MODE_SINGLE"; return TJ_ERR_INVALID; }
   QUIESCE(c);
   const size_t s = (size_t)u * d.S + seg;
-  int n = 0;
-  HIPCHK(c, hipMemcpy(&n, d.kobs_n + s, 4, hipMemcpyDeviceToHost));
-  const int m = std::min(n, cap);
-  if (m > 0 && ids) {
-    std::vector<int> tmp(m);
-    HIPCHK(c, hipMemcpy(tmp.data(), d.kobs_id + s * d.cap_obs, (size_t)m * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < m; i++) ids[i] = c->cloud_order[tmp[i]];
-  }
-  if (m > 0 && cd) HIPCHK(c, hipMemcpy(cd, d.kobs_cd + s * d.cap_obs * 4, (size_t)m * 32, hipMemcpyDeviceToHost));
+  int n = 0, r;
+  if ((r = fetch_ids(c, d.kobs_n, d.kobs_id, s, cap, ids, n))) return r;
+  if (std::min(n, cap) > 0 && cd && (r = fetch(c, cd, d.kobs_cd, s * d.cap_obs * 4, (size_t)std::min(n, cap) * 4))) return r;
   return n;
 }
 int tj_set_obs_cache(tj_ctx* c, int u, int seg, int n, const int* ids, const double* cd) {
@@ -1846,16 +1789,11 @@ int tj_set_obs_cache(tj_ctx* c, int u, int seg, int n, const int* ids, const dou
   if (!d.optimal_plane || d.mode != 0) { c->err = "tj_set_obs_cache: needs optimal_plane and TJ_MODE_SINGLE"; return TJ_ERR_INVALID; }
   if (n > d.cap_obs) { c->err = "tj_set_obs_cache: more planes than cap_obs"; return TJ_ERR_CAPACITY; }
   QUIESCE(c);
-  std::vector<int> inv(c->cloud_order.size());
-  for (size_t i = 0; i < inv.size(); i++) inv[c->cloud_order[i]] = (int)i;
   std::vector<int> tmp(std::max(n, 1));
-  for (int i = 0; i < n; i++) {
-    if (ids[i] < 0 || ids[i] >= d.N) { c->err = "tj_set_obs_cache: obstacle id out of range"; return TJ_ERR_INVALID; }
-    tmp[i] = inv[ids[i]];
-  }
+  if (!ids_to_sorted(c, ids, n, tmp.data())) { c->err = "tj_set_obs_cache: obstacle id out of range"; return TJ_ERR_INVALID; }
   const size_t s = (size_t)u * d.S + seg;
   int r;
-  if ((r = upload(c, d.kobs_id + s * d.cap_obs, tmp.data(), (size_t)n * 4)) || (r = upload(c, d.kobs_cd + s * d.cap_obs * 4, cd, (size_t)n * 32)) || (r = upload(c, d.kobs_n + s, &n, 4))) return r;
+  if ((r = store(c, d.kobs_id, s * d.cap_obs, tmp.data(), n)) || (r = store(c, d.kobs_cd, s * d.cap_obs * 4, cd, (size_t)n * 4)) || (r = store(c, d.kobs_n, s, &n, 1))) return r;
   return TJ_OK;
 }
 int tj_get_pair_cache(tj_ctx* c, int* flags, double* cd) {
@@ -1863,9 +1801,9 @@ int tj_get_pair_cache(tj_ctx* c, int* flags, double* cd) {
   const Dev& d = c->d;
   if (!d.optimal_plane || d.mode == 0) { c->err = "tj_get_pair_cache: needs optimal_plane and a multi-UAV mode"; return TJ_ERR_INVALID; }
   QUIESCE(c);
-  const size_t n = (size_t)d.S * d.U * d.U;
-  HIPCHK(c, hipMemcpy(flags, d.kpair_on, n * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(cd, d.kpair_cd, n * 32, hipMemcpyDeviceToHost));
+  const size_t n = array_count(c, d.kpair_on);   // [S][U][U]
+  int r;
+  if ((r = fetch(c, flags, d.kpair_on, 0, n)) || (r = fetch(c, cd, d.kpair_cd, 0, 4 * n))) return r;
   for (size_t i = 0; i < n; i++) if (!flags[i]) cd[4 * i] = cd[4 * i + 1] = cd[4 * i + 2] = cd[4 * i + 3] = 0.0;
   return TJ_OK;
 }
@@ -1874,7 +1812,7 @@ int tj_set_pair_cache(tj_ctx* c, const int* flags, const double* cd) {
   const Dev& d = c->d;
   if (!d.optimal_plane || d.mode == 0) { c->err = "tj_set_pair_cache: needs optimal_plane and a multi-UAV mode"; return TJ_ERR_INVALID; }
   QUIESCE(c);
-  const size_t n = (size_t)d.S * d.U * d.U;
+  const size_t n = array_count(c, d.kpair_on);   // [S][U][U]
   std::vector<int> on(n, 0), list;
   for (int tr = 0; tr < d.S; tr++) for (int a = 0; a < d.U; a++) for (int b = a + 1; b < d.U; b++) {
     const size_t i = ((size_t)tr * d.U + a) * d.U + b;
@@ -1883,7 +1821,7 @@ int tj_set_pair_cache(tj_ctx* c, const int* flags, const double* cd) {
   }
   const int cnt = (int)list.size();
   int r;
-  if ((r = upload(c, d.kpair_on, on.data(), n * 4)) || (r = upload(c, d.kpair_cd, cd, n * 32)) || (r = upload(c, d.kpair_list, list.data(), (size_t)cnt * 4)) || (r = upload(c, d.kpair_n, &cnt, 4))) return r;  // [1] is re-snapshot by the next k_begin
+  if ((r = store(c, d.kpair_on, 0, on.data(), n)) || (r = store(c, d.kpair_cd, 0, cd, 4 * n)) || (r = store(c, d.kpair_list, 0, list.data(), cnt)) || (r = store(c, d.kpair_n, 0, &cnt, 1))) return r;  // [1] is re-snapshot by the next k_begin
   return TJ_OK;
 }
 
@@ -2072,197 +2010,6 @@ int tj_plan_init(tj_ctx* c, int n_robots, const double* starts, const double* go
   return TJ_OK;
 }
 
-#ifdef TJ_KAT
-int tj_kat_ccd(tj_ctx* c, int n, const double* P, const double* D, const double* Q, const double* E, const double* q, const double* tu, double d, double* out) {
-  if (!c || n < 0 || !P || !D || !Q || !E || !q || !tu || !out) return TJ_ERR_INVALID;
-  DevBuf b[6], dout; int r;
-  const void* src[6] = {P, D, Q, E, q, tu};
-  const size_t sz[6] = {(size_t)n * 144, (size_t)n * 144, (size_t)n * 144, (size_t)n * 144, (size_t)n * 24, (size_t)n * 16};
-  for (int i = 0; i < 6; i++) if ((r = to_dev(c, b[i], src[i], sz[i]))) return r;
-  if ((r = to_dev(c, dout, nullptr, (size_t)n * 16))) return r;
-  hipLaunchKernelGGL(k_dbg_ccd, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[2].p,
-                     (const double*)b[3].p, (const double*)b[4].p, (const double*)b[5].p, d, (double*)dout.p);
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-// The walk reports a frontier overflow to the queries' control block (walk_dev), as every read-only query does: a deliberate overflow here is this call's error
-// and leaves the solver's error word, and with it the context, as it was.  `who`: the entry point the call came in through (the error texts name it).
-static int kat_query_run(tj_ctx* c, const char* who, int nq, const double* boxes, double margin, int cap, int unroll, int pre, int* counts, int* ids) {
-  if (!c || nq < 0 || cap < 1 || !boxes || !counts || !ids || (unroll != 1 && unroll != 4)) return TJ_ERR_INVALID;
-  if (!c->have_cloud) { c->err = std::string(who) + ": set the obstacles first"; return TJ_ERR_INVALID; }
-  DevBuf db, di, dn; int r;
-  if ((r = to_dev(c, db, boxes, (size_t)nq * 48)) || (r = to_dev(c, di, nullptr, (size_t)nq * cap * 4)) || (r = to_dev(c, dn, nullptr, (size_t)nq * 4))) return r;
-  QUIESCE(c);
-  Dev da;
-  if ((r = walk_dev(c, da))) return r;
-  with_prim(c->d, [&](auto prim) {
-    constexpr int PR = decltype(prim)::value;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(std::max(nq, 1)), dim3(64), 0, c->stream, da, nq, (const double*)db.p, margin, cap, (int*)di.p, (int*)dn.p); };
-    if (unroll == 4) { if (pre) go(k_dbg_query<PR, 4, true>); else go(k_dbg_query<PR, 4, false>); }
-    else { if (pre) go(k_dbg_query<PR, 1, true>); else go(k_dbg_query<PR, 1, false>); }
-  });
-  if ((r = query_finish(c, who))) {
-    if (r == TJ_ERR_CAPACITY)   // (query_finish words it for a trajectory query: a segment and a `range`; here the caller gave boxes and a margin)
-      c->err = std::string(who) + ": the BVH frontier of one of the " + std::to_string(nq) + " query boxes overflowed at margin " + std::to_string(margin) + " (more than " + std::to_string(FRONT_CAP) +
-               " boxes of one level within the margin of the query box): ask with smaller boxes or a smaller margin";
-    return r;
-  }
-  if (nq == 0) return TJ_OK;
-  HIPCHK(c, hipMemcpy(counts, dn.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(ids, di.p, (size_t)nq * cap * 4, hipMemcpyDeviceToHost));
-  for (int q = 0; q < nq; q++) {
-    if (counts[q] > cap) { c->err = std::string(who) + ": query box " + std::to_string(q) + " returned " + std::to_string(counts[q]) + " candidates, more than cap = " + std::to_string(cap); return TJ_ERR_CAPACITY; }
-    for (int i = 0; i < counts[q]; i++) ids[(size_t)q * cap + i] = c->cloud_order[ids[(size_t)q * cap + i]];
-  }
-  return check_device_errors(c);
-}
-int tj_kat_query_form(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int unroll, int pre, int* counts, int* ids) {
-  return kat_query_run(c, "tj_kat_query_form", nq, boxes, margin, cap, unroll, pre, counts, ids);
-}
-int tj_kat_query(tj_ctx* c, int nq, const double* boxes, double margin, int cap, int* counts, int* ids) {   // the plane query's form, no prefetched top box
-  return kat_query_run(c, "tj_kat_query", nq, boxes, margin, cap, 4, 0, counts, ids);
-}
-
-int tj_kat_tri(tj_ctx* c, int n, const double* P, const double* D, const double* tri, const double* t, double dist, double off, double* out) {
-  if (!c || n < 0 || !P || !D || !tri || !t || !out) return TJ_ERR_INVALID;
-  DevBuf b[4], dout; int r;
-  const void* src[4] = {P, D, tri, t};
-  const size_t sz[4] = {(size_t)n * 144, (size_t)n * 144, (size_t)n * 72, (size_t)n * 8};
-  for (int i = 0; i < 4; i++) if ((r = to_dev(c, b[i], src[i], sz[i]))) return r;
-  if ((r = to_dev(c, dout, nullptr, (size_t)n * 64))) return r;
-  hipLaunchKernelGGL(k_dbg_tri, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[2].p, (const double*)b[3].p, dist, off, (double*)dout.p);
-  // the two k-DOP verdicts, out[.][5] and out[.][6]: one wave per case, the triangle on lane 0
-  hipLaunchKernelGGL((k_dbg_kdop_wave<3, false>), dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, nullptr, nullptr, (const double*)b[2].p, 1, nullptr, dist, (double*)dout.p + 5, 8);
-  hipLaunchKernelGGL((k_dbg_kdop_wave<3, true>), dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[3].p, (const double*)b[2].p, 1, nullptr, off, (double*)dout.p + 6, 8);
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * 64, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-int tj_kat_kdop_wave(tj_ctx* c, int prim, int swept, int n, int per, const double* P, const double* D, const double* t, const double* bodies, const int* nc, double d, double* out) {
-  if (!c || n < 0 || per < 1 || per > 64 || (prim != 1 && prim != 3) || !P || !bodies || !out || (swept && (!D || !t))) return TJ_ERR_INVALID;
-  DevBuf b[5], dout; int r;
-  const void* src[5] = {P, swept ? D : nullptr, swept ? t : nullptr, bodies, nc};
-  const size_t sz[5] = {(size_t)n * 144, swept ? (size_t)n * 144 : 0, swept ? (size_t)n * 8 : 0, (size_t)n * per * prim * 24, nc ? (size_t)n * 4 : 0};
-  for (int i = 0; i < 5; i++) if (src[i] && (r = to_dev(c, b[i], src[i], sz[i]))) return r;
-  if ((r = to_dev(c, dout, nullptr, (size_t)n * per * 8))) return r;
-  HIPCHK(c, hipMemsetAsync(dout.p, 0, std::max<size_t>((size_t)n * per * 8, 8), c->stream));
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(std::max(n, 1)), dim3(64), 0, c->stream, c->d, n, (const double*)b[0].p, (const double*)b[1].p, (const double*)b[2].p, (const double*)b[3].p, per, (const int*)b[4].p, d, (double*)dout.p, 1);
-  };
-  if (prim == 1) { if (swept) go(k_dbg_kdop_wave<1, true>); else go(k_dbg_kdop_wave<1, false>); }
-  else { if (swept) go(k_dbg_kdop_wave<3, true>); else go(k_dbg_kdop_wave<3, false>); }
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(out, dout.p, (size_t)n * per * 8, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-// the launch plan as a flat record of ints (host_plan.h: plan_record): a context's own, or -- c == nullptr, no device needed -- the pure planner's on the
-// caller's parameters and PLAN_FACT_INTS device facts.  Returns the number of ints (negated: `cap` is too small), msg: the planner's error text
-int tj_kat_plan(const tj_ctx* c, const tj_params* p, const int* facts, int* out, int cap, char* msg, int msg_cap) {
-  if (!out || (!c && (!p || !facts))) return 0;
-  Plan pl; PlanFacts f;
-  if (c) { pl.d = c->d; pl.h = c->hp; f = c->facts; f.prim = c->d.prim; f.n_obs = c->d.N; }
-  else {
-    memcpy(&f, facts, sizeof(f));
-    if (const char* bad = plan_check_params(p)) { pl.err = TJ_ERR_INVALID; pl.msg = bad; memset(&pl.d, 0, sizeof(pl.d)); pl.h.lsl = LsLayout{}; }
-    else { pl = plan_context(p, f, tune); pl.d.prim = f.prim; pl.d.N = f.n_obs; }
-  }
-  if (msg && msg_cap > 0) { strncpy(msg, pl.msg, (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
-  return plan_record(pl, f, out, cap);
-}
-
-// the launch sequence as flat records of ints (host_launch.h: sequence_kernel), call by call: a context's own Dev, plan and state (its state is copied to `state`
-// first, but for xs_same_queue_now, and not advanced), or -- c == nullptr, no device needed -- the planner's Dev and plan on the caller's parameters and facts, from the start state in `state`.
-// calls: n_calls x (kid, sched, chain_pos).  out, per call: exists, number of records, the SchedState after it, the Launch records.  Returns the ints written
-// (negated: `cap` is too small; 0: bad arguments or a shape the planner refuses)
-int tj_kat_launches(const tj_ctx* c, const tj_params* p, const int* facts, int lsc_follow, int* state, const int* calls, int n_calls, int* out, int cap) {
-  if (!out || !state || n_calls < 0 || (n_calls > 0 && !calls) || (!c && (!p || !facts))) return 0;
-  Dev d; HostPlan h; SchedState st;
-  if (c) {   // (xs_same_queue_now comes FROM state[]: tj_profile_kernels sets it around its run only, so the caller says which run it asks about)
-    SchedState in; memcpy(&in, state, sizeof(in));
-    d = c->d; h = c->hp; st = c->ss; st.xs_same_queue_now = in.xs_same_queue_now ? 1 : 0; memcpy(state, &st, sizeof(st));
-  }
-  else {
-    PlanFacts f; memcpy(&f, facts, sizeof(f));
-    if (plan_check_params(p)) return 0;
-    const Plan pl = plan_context(p, f, tune);
-    if (pl.err) return 0;
-    d = pl.d; d.prim = f.prim; d.N = f.n_obs; d.lsc_follow = lsc_follow ? 1 : 0; h = pl.h; memcpy(&st, state, sizeof(st));
-  }
-  int n = 0;
-  for (int i = 0; i < n_calls; i++) {
-    const int kid = calls[3 * i], sched = calls[3 * i + 1];
-    if (kid < 0 || kid >= K_COUNT || sched < 0 || sched > 2) return 0;
-    LaunchList l;
-    const bool exists = sequence_kernel(d, h, st, (Sched)sched, calls[3 * i + 2], kid, l);
-    const int need = 2 + SCHED_STATE_INTS + l.n * LAUNCH_INTS;
-    if (n + need > cap) return -(n + need);
-    out[n] = exists ? 1 : 0; out[n + 1] = l.n;
-    memcpy(out + n + 2, &st, sizeof(st)); memcpy(out + n + 2 + SCHED_STATE_INTS, l.v, (size_t)l.n * sizeof(Launch));
-    n += need;
-  }
-  return n;
-}
-
-int tj_kat_linalg(tj_ctx* c, int nmat, int n, const double* mats, double* out) {
-  if (!c || nmat < 0 || n < 1 || n > 64 || !mats || !out) return TJ_ERR_INVALID;
-  DevBuf dm, dout; int r;
-  if ((r = to_dev(c, dm, mats, (size_t)nmat * n * n * 8)) || (r = to_dev(c, dout, nullptr, (size_t)nmat * 16))) return r;
-  const size_t lds = (2 * (size_t)n * n + 4 * n) * 8;
-  hipLaunchKernelGGL(k_dbg_linalg, dim3(nmat), dim3(64), lds, c->stream, nmat, n, (const double*)dm.p, (double*)dout.p);
-  HIPCHK(c, hipGetLastError());
-  QUIESCE(c);
-  HIPCHK(c, hipMemcpy(out, dout.p, (size_t)nmat * 16, hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-// the counterpart of tj_get_local_grad for the whole fleet: the per-piece blocks k_xsolve / k_xsolve_band read, from the host.  No kernel runs
-int tj_kat_set_local_grad(tj_ctx* c, const double* lg, const double* lh) {
-  if (!c || !lg || !lh) return TJ_ERR_INVALID;
-  if (!ready(c)) return TJ_ERR_INVALID;
-  const Dev& d = c->d;
-  QUIESCE(c);
-  const size_t blocks = (size_t)d.U * d.P;
-  { int ur; if ((ur = upload(c, d.lg, lg, blocks * 19 * 8)) || (ur = upload(c, d.lh, lh, blocks * 361 * 8))) return ur; }
-  return TJ_OK;
-}
-
-// the hull cache as the last launch that wrote it left it: the 122 values of every (robot, segment) record and the box table.  No kernel runs
-int tj_kat_get_hull_record(tj_ctx* c, double* hullinfo, double* hbox) {
-  if (!c || !hullinfo || !hbox) return TJ_ERR_INVALID;
-  if (!ready(c)) return TJ_ERR_INVALID;
-  const Dev& d = c->d;
-  QUIESCE(c);
-  const size_t recs = (size_t)d.U * d.S;
-  std::vector<double> h(recs * HULL_INFO_STRIDE);
-  HIPCHK(c, hipMemcpy(h.data(), d.hullinfo, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < recs; r++) memcpy(hullinfo + r * 122, h.data() + r * HULL_INFO_STRIDE, 122 * sizeof(double));
-  HIPCHK(c, hipMemcpy(hbox, d.hbox, (size_t)d.S * 6 * d.U * sizeof(double), hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-// the swept-hull cache likewise: the CCD_REC values of every (robot, segment) record and the pair-box table.  No kernel runs
-int tj_kat_get_swept_record(tj_ctx* c, double* ccdinfo, double* cbox) {
-  if (!c || !ccdinfo || !cbox) return TJ_ERR_INVALID;
-  if (!ready(c)) return TJ_ERR_INVALID;
-  const Dev& d = c->d;
-  QUIESCE(c);
-  const size_t recs = (size_t)d.U * d.S;
-  std::vector<double> h(recs * CCD_STRIDE);
-  HIPCHK(c, hipMemcpy(h.data(), d.ccdinfo, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < recs; r++) memcpy(ccdinfo + r * CCD_REC, h.data() + r * CCD_STRIDE, CCD_REC * sizeof(double));
-  HIPCHK(c, hipMemcpy(cbox, d.cbox, (size_t)d.S * 6 * d.U * sizeof(double), hipMemcpyDeviceToHost));
-  return TJ_OK;
-}
-
-#endif  // TJ_KAT
-
 int tj_get_build_info(tj_ctx* c, double* bvh_build_ms, int* built_on_device) {
   if (!c) return TJ_ERR_INVALID;
   if (bvh_build_ms) *bvh_build_ms = c->bvh_build_ms;
@@ -2274,20 +2021,17 @@ int tj_get_stats(tj_ctx* c, tj_stats* s) {
   if (!c || !s) return TJ_ERR_INVALID;
   Ctl h;
   QUIESCE(c);
-  HIPCHK(c, hipMemcpy(&h, c->d.ctl, sizeof(Ctl), hipMemcpyDeviceToHost));
   const Dev& d = c->d;
-  std::vector<unsigned long long> seg((size_t)d.U * d.S * 6);
-  HIPCHK(c, hipMemcpy(seg.data(), d.seg_stats, seg.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<unsigned long long> seg(array_count(c, d.seg_stats)), ps(array_count(c, d.pair_stats)), bs(array_count(c, d.blk_stats));
+  int r;
+  if ((r = fetch(c, &h, d.ctl, 0, 1)) || (r = fetch(c, seg.data(), d.seg_stats, 0, seg.size())) || (r = fetch(c, ps.data(), d.pair_stats, 0, ps.size())) ||
+      (r = fetch(c, bs.data(), d.blk_stats, 0, bs.size()))) return r;
   unsigned long long tot[6] = {0, 0, 0, 0, 0, 0};
   for (size_t i = 0; i < seg.size(); i++) tot[i % 6] += seg[i];
   s->iters = (unsigned long long)(h.iter + h.pending);
   s->nodes_dcd = tot[0]; s->cand_dcd = tot[1]; s->nodes_ccd = tot[2]; s->cand_ccd = tot[3]; s->planes_obs = tot[4]; s->planes_self = tot[5];
-  std::vector<unsigned long long> ps((size_t)d.U * d.S * 2);
-  HIPCHK(c, hipMemcpy(ps.data(), d.pair_stats, ps.size() * 8, hipMemcpyDeviceToHost));
   unsigned long long pt[2] = {0, 0};
   for (size_t i = 0; i < ps.size(); i++) pt[i % 2] += ps[i];
-  std::vector<unsigned long long> bs((size_t)d.U * d.P + d.U);
-  HIPCHK(c, hipMemcpy(bs.data(), d.blk_stats, bs.size() * 8, hipMemcpyDeviceToHost));
   unsigned long long fails = 0, evals = 0;
   for (size_t i = 0; i < (size_t)d.U * d.P; i++) fails += bs[i];
   for (size_t i = (size_t)d.U * d.P; i < bs.size(); i++) evals += bs[i];
@@ -2391,4 +2135,7 @@ int tj_xch_enable(tj_ctx* c, int on, int wait_mode) {
   return TJ_OK;
 }
 
+#ifdef TJ_KAT
+#include "tj_kat.h"   // the known-answer hooks: test build only
+#endif
 #include "tj_group.h"

@@ -794,6 +794,138 @@ typedef struct tj_obswin_row {
 } tj_obswin_row;
 int tj_obstacle_windows(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n);
 int tj_obswin_row_size(void);   /* sizeof(tj_obswin_row) */
+/* ---- tj_sight_windows: FROM WHEN TO WHEN does the straight line between two robots at equal flight times, or between a robot and a fixed station, pass within
+ * `dist` of the obstacle set, as certified time intervals (csrc/kernels_sight_windows.h; read-only like tj_obstacle_windows).  The robot-robot queries look at
+ * no obstacle and the obstacle queries at one robot; a planner that assigns radio or optical links, relays or tethers asks about the LINK: during which intervals
+ * is the segment between the two ends blocked, or closer to structure than a Fresnel or tether clearance?  tj_flight_profile's samples certify nothing between
+ * them, and a thin pillar crosses a link in milliseconds.  Works in all three modes (single-UAV: station links only), for clouds and meshes.
+ * links [n_links][2]: link k = (a, b); a is a robot, b a robot other than a, or -1 - s for station s of stations [n_stations][3].  A link is directed: it is
+ * looked at over a's flight, time 0 to (S / res) * piece_time[a] (tj_proximity_windows' convention: the two ends arrive at different times).  A partner that
+ * has arrived hovers at its last control point; a station is six copies of its point and has no cuts.  Duplicate links are allowed and answered per index.
+ * For every link k = (a, b) with a OWNED, and every segment tr of a:
+ *   seeds    the segment's window of time [(tr / res) * pt_a, ((tr + 1) / res) * pt_a] cut at b's segment boundaries (j / res) * pt_b and at b's arrival
+ *            (tj_audit_timed's cuts at level 0, the same expressions: adjacent windows share an end bit for bit).  A station: the one window.
+ *   window   W = [ca, cb] lies in segment tr of a and in ONE segment j of b (j == S: b hovers).  a_0..a_5 = a's RAW hull of tr restricted to
+ *            [sa, sb] = clamp01((ca - T0) / (T1 - T0)), .. and b_0..b_5 = b's raw hull of j restricted likewise to [ra, rb] (tj_proximity_windows' expressions,
+ *            never a parent's net; a hover body and a station are not restricted).  L(W) = {a_0..a_5, b_0..b_5}: at every time of W the link joins a point of
+ *            conv{a_i} to a point of conv{b_i}, so it lies in conv L(W).
+ *   C(W)     the candidates: the primitives whose box is within dist of the box of the 12 points on every axis, touching counts (the walk's leaf predicate in
+ *            fp64; the 49-axis cull is not used).  A primitive outside C(W) is farther than dist from the link on all of W.
+ *   lo_p     |v|, v = gjk(L(W), p) (the 12 points = body 1), where v separates the two over all 12 points (tj_obstacle_approach's certificate); 0 without it.
+ *   sample   (x, y, p), the attained distance of ONE point of the link with ends x, y from p: e = y - x; proj(z) = 0 if e.e == 0, else
+ *            clamp01(((z - x) . e) / (e . e)).  A cloud point: lambda = proj(p).  A triangle: lambda = 0.5, then TJ_SIGHT_PROJECTIONS times z = x + lambda e,
+ *            w = z - gjk({z}, triangle) (the GJK's witness on the triangle), lambda = proj(w).  Value: the distance of x + lambda e from p (norm3 for a cloud
+ *            point, |gjk({.}, triangle)| for a triangle: tj_obstacle_approach's hi).  Any lambda in [0, 1] is a point of the link, so the value is an upper
+ *            bound of the link's distance (exact for a cloud point); the projections only decide how soon a window is decided.
+ *   h0_p, h5_p  = sample(a_0, b_0, p) with its lambda0_p: attained at ca; sample(a_5, b_5, p) with lambda5_p: attained at cb.
+ *   ub_p     for lambda of {lambda0_p, lambda5_p}: the largest distance of a_i + lambda (b_i - a_i), i = 0..5, from p.  Both nets are over the same window of
+ *            time, so these six points are the Bezier net of the point that rides the link at the FIXED lambda; the distance to a convex primitive is convex, so
+ *            that point, and with it the link, is within this value of p on all of W.  ub_p is the smaller of the two; the term i = 0 at lambda0_p is h0_p
+ *            itself (i = 5 at lambda5_p: h5_p), so a lambda whose sample is above dist cannot bring ub_p to dist and is not looked at.
+ *   class    OUT: every candidate has lo_p > dist (an empty C(W) is OUT).  Else IN: some candidate has ub_p <= dist.  Else MIXED.
+ *   h0, h5   of W: the smallest h0_p (h5_p) over C(W) with its primitive, ordered by (value, caller's index).
+ *   search   per (link, segment of a), independent of every other.  The seeds in time order: IN seeds are leaves, MIXED seeds the live set.  Round d = 1, 2, ..:
+ *            the live windows in ascending ca; one with cb - ca <= tol, or whose midpoint 0.5 * (ca + cb) is not strictly inside, becomes an EDGE leaf with its
+ *            h0 and h5; every other is halved there and both children are evaluated from the raw hulls, left then right: OUT children are dropped, IN children
+ *            appended to the leaves, MIXED children form the next live set.
+ *   stop     the live set is empty | d == max_depth | the live set or the leaf list after a round holds more than max_windows (TRUNCATED: the lists are those
+ *            of the last completed round, `windows` counts the overflowing round's work too).  More than max_windows MIXED or IN seeds: TRUNCATED at depth 0.
+ *            Whatever is live at the end joins the leaves as EDGE leaves (a segment has at most max(2 * max_windows, S + 1) leaves).
+ *   merge    per link the leaves of a's segments in ca order: distinct and disjoint.  Two consecutive leaves are adjacent exactly when prev.cb == next.ca on
+ *            doubles (the segment ends and the cuts share their expressions, so a chain crosses segment boundaries).  A row is a maximal chain.
+ *   sure     every time of an IN leaf; of an EDGE leaf ca if h0 <= dist and cb if h5 <= dist: times at which the link IS within dist of a primitive.
+ *   row      t_first_lo = the chain's start, t_last_hi = its end; t_first_hi = the earliest sure time, t_last_lo = the latest (both -1.0 without one);
+ *            within_lo = the sum of the IN leaves' cb - ca, left to right; closest, closest_time, index = the smallest attained end sample of the chain in the
+ *            order (value, time, index), index = the caller's index of its primitive (-1, closest = +infinity, closest_time = -1.0 where no end sample has a
+ *            candidate) -- not converged; link = k, robot = a, partner = b as given; leaves = the chain's length; depth = the most rounds completed by any
+ *            segment with a leaf in the chain; windows = the LINK's work, seeds + 2 per halved window over all segments of a, repeated on each of its rows.
+ *   flags    CERTAIN (a sure time exists) or UNCERTAIN, AT_START (t_first_lo == 0), AT_END (t_last_hi == (S / res) * pt_a), RESOLVED (CERTAIN, and
+ *            t_first_hi - t_first_lo <= tol or AT_START, and t_last_hi - t_last_lo <= tol or AT_END), TRUNCATED (a segment of the chain was truncated).
+ * Every field is a function of the state and the arguments alone.  Outside every row of link k the link is certified farther than dist from every primitive
+ * over a's flight.  Rows are sorted by (link, t_first_lo); no order of evaluation or of any append is visible.
+ * dist <= 0: offset; +infinity is valid.  tol < 0: TJ_SIGHT_TOL_FRACTION * dist / vel_limit -- every point of a link moves at most at the speed limit of its
+ * ends, so the siblings' design condition carries over: the time such a point needs for 1 % of dist (offset in place of an infinite dist); 0 is valid.
+ * max_depth < 0: TJ_SIGHT_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0: TJ_SIGHT_FRONTIER; above TJ_SIGHT_MAX_WINDOWS (it bounds the in-kernel rank
+ * sort) TJ_ERR_INVALID.  *n = the rows.  *n > cap: TJ_ERR_CAPACITY with the exact *n, the first `cap` rows in order have been written.  cap == 0 with rows ==
+ * NULL is the count-only call (two launches).  TJ_ERR_INVALID with the outputs untouched (precedence: null, NaN, limits, no state): n == NULL, cap < 0, rows ==
+ * NULL with cap > 0, n_links < 0, links == NULL with n_links > 0, n_stations < 0, stations == NULL with n_stations > 0; a NaN dist, tol or station coordinate; a
+ * link whose a is no robot, whose b == a or whose b is neither a robot nor a station; a call before tj_init_state.  n_links == 0 or no obstacles (tj_set_cloud
+ * with n = 0 included): 0 rows and TJ_OK.  A walk frontier beyond its capacity (more than FRONT_CAP boxes of 8 primitives within dist of one window's box: lower
+ * dist): TJ_ERR_CAPACITY, never fewer rows; no count is known then, *n is left UNTOUCHED and nothing is written; tj_last_error names the cause.  A plain SHARDED
+ * context (world > 1) holds neither the other ranks' piece_time nor their current nets: TJ_ERR_UNSUPPORTED, tj_last_error names tj_group_sight_windows, which
+ * answers each link on the rank that owns a with nets and piece_time from the owners, in (link, t_first_lo) order, bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, and is a function of n_links x S x max_windows (S = piece_num * res segments):
+ *   n_links * S * (2 * (2 * max_windows + S + 1) * 48 + 16) + n_links * 16 + n_stations * 24 + cap * 88 bytes
+ *   (per link and segment the live lists, which hold the seeds before and the sorted leaves afterwards, and the leaf list, 48 bytes a window, each with room for
+ *   a segment whose S + 1 seeds are all there is; its four counters; the links with their row counts and work; the stations; the rows).  A call whose figure
+ *   exceeds TJ_SIGHT_MAX_BYTES is refused up front with TJ_ERR_INVALID: lower max_windows, cap or the number of links.
+ * At most THREE launches whatever the number of links, the number of primitives and the depth (two for the count-only call); no host loop over links,
+ * segments or rounds.  Changes no solver state, statistics or launch count.
+ * STATED LIMITS.  (1) A certified lo_p is the GJK's |v|, up to 1e-10 |v| relative above the hull's distance (the siblings' limit): it applies to the OUT
+ * decision.  (2) conv L(W) holds more than the link's sweep (a link between distant ends has a long box: every primitive near it is a candidate of every
+ * window), and IN needs ONE primitive and ONE fixed lambda that cover the whole window; anything else is halved until one does, or ends as an EDGE leaf.
+ * (3) For a triangle the sample is an upper bound reached by TJ_SIGHT_PROJECTIONS alternating projections, not the link's distance.  (4) Gaps shorter than a
+ * leaf are not resolved; UNCERTAIN rows are grazes at the resolution tol.
+ * The defaults are measured (tests/sight_windows_ref.py default_tolerance, the restatement, on the CPU; nothing here is timed): the default tol, max_depth = 40,
+ * the lists capped at TJ_SIGHT_MAX_WINDOWS only, on the final states of tests/golden/e2e_scn_b.npz, e2e_scn_c3.npz, e2e_scn_b_coupled.npz and on the same runs'
+ * iteration-0 states (_init), with their scenes' clouds cropped as obstacle_approach_ref.default_tolerance crops them; the links (u, (u + 1) % U) and
+ * (u, U - 1 - u) for every u and every robot to one station at the cropped cloud's centroid, 1.0 above its top; dist = offset = 0.1 and offset + 2 * margin
+ * (widest bracket: the larger of t_first_hi - t_first_lo and t_last_hi - t_last_lo over the CERTAIN rows):
+ *   state                    dist   rows   uncertain   truncated   largest live set   largest leaf list   largest depth   widest bracket
+ *   e2e_scn_b                0.1    90     0           0           6                  20                  11              2.81e-04
+ *   e2e_scn_b                0.3    72     0           0           4                  17                  9               1.12e-03
+ *   e2e_scn_b_init           0.1    98     0           0           8                  25                  14              3.05e-04
+ *   e2e_scn_b_init           0.3    80     0           0           4                  27                  12              1.22e-03
+ *   e2e_scn_c3               0.1    126    0           0           4                  20                  11              2.81e-04
+ *   e2e_scn_c3               0.3    85     0           0           4                  17                  9               1.12e-03
+ *   e2e_scn_c3_init          0.1    125    0           0           4                  20                  14              3.05e-04
+ *   e2e_scn_c3_init          0.3    73     0           0           2                  13                  12              1.22e-03
+ *   e2e_scn_b_coupled        0.1    89     0           0           6                  21                  11              2.81e-04
+ *   e2e_scn_b_coupled        0.3    72     0           0           4                  17                  9               1.12e-03
+ *   e2e_scn_b_coupled_init   0.1    98     0           0           8                  25                  14              3.05e-04
+ *   e2e_scn_b_coupled_init   0.3    80     0           0           4                  27                  12              1.22e-03
+ * The same clouds with every point a triangle (the point and two vertices 0.02 along x and along y), per number of projections K: rows / UNCERTAIN rows /
+ * largest leaf list:
+ *   state                    dist   K = 1        K = 2        K = 3        K = 4        K = 5        K = 6
+ *   e2e_scn_b                0.1    81/0/126     81/0/32      81/0/19      81/0/19      81/0/19      81/0/19
+ *   e2e_scn_b                0.3    66/0/22      66/0/20      66/0/20      66/0/20      66/0/20      66/0/20
+ *   e2e_scn_b_init           0.1    85/4/570     84/0/197     84/0/25      84/0/25      84/0/25      84/0/25
+ *   e2e_scn_b_init           0.3    68/1/92      68/0/25      68/0/25      68/0/25      68/0/25      68/0/25
+ *   e2e_scn_c3               0.1    90/0/49      90/0/15      90/0/15      90/0/15      90/0/15      90/0/15
+ *   e2e_scn_c3               0.3    80/0/16      80/0/16      80/0/16      80/0/16      80/0/16      80/0/16
+ *   e2e_scn_c3_init          0.1    90/0/253     90/0/20      90/0/20      90/0/20      90/0/20      90/0/20
+ *   e2e_scn_c3_init          0.3    71/0/14      71/0/14      71/0/14      71/0/14      71/0/14      71/0/14
+ *   e2e_scn_b_coupled        0.1    83/0/127     83/0/33      83/0/21      83/0/21      83/0/21      83/0/21
+ *   e2e_scn_b_coupled        0.3    67/0/22      67/0/20      67/0/20      67/0/20      67/0/20      67/0/20
+ *   e2e_scn_b_coupled_init   0.1    85/4/570     84/0/197     84/0/25      84/0/25      84/0/25      84/0/25
+ *   e2e_scn_b_coupled_init   0.3    68/1/92      68/0/25      68/0/25      68/0/25      68/0/25      68/0/25
+ * (K = 7 and 8, measured too, repeat K = 6.)  With one projection the iteration-0 states of e2e_scn_b even end TRUNCATED at TJ_SIGHT_MAX_WINDOWS: a sample far from
+ * the link's nearest point leaves whole stretches undecided.  TJ_SIGHT_PROJECTIONS is the smallest K at which no state's triple differs from that of K + 1 and of K + 2 (3).  TJ_SIGHT_FRONTIER is the next power of two >= 4 x
+ * the larger of the two list maxima over the cloud states and the triangulated states at TJ_SIGHT_PROJECTIONS (27), and at least 64. */
+#define TJ_SIGHT_CERTAIN   1    /* a sure time exists: the link IS within dist of a primitive at t_first_hi and at t_last_lo */
+#define TJ_SIGHT_UNCERTAIN 2    /* no sure time: t_first_hi == t_last_lo == -1.0, a graze at the resolution tol */
+#define TJ_SIGHT_AT_START  4    /* the chain starts at time 0: nothing lies before it */
+#define TJ_SIGHT_AT_END    8    /* the chain ends at the end of robot a's flight */
+#define TJ_SIGHT_RESOLVED  16   /* CERTAIN and both brackets are at most tol wide (a side closed by AT_START / AT_END counts as resolved) */
+#define TJ_SIGHT_TRUNCATED 32   /* a segment of the chain outgrew max_windows: its leaves of the last completed round are returned */
+#define TJ_SIGHT_MAX_DEPTH 40
+#define TJ_SIGHT_FRONTIER  128
+#define TJ_SIGHT_MAX_WINDOWS 1024
+#define TJ_SIGHT_MAX_BYTES (1ll << 31)
+#define TJ_SIGHT_TOL_FRACTION 0.01
+#define TJ_SIGHT_PROJECTIONS 3
+typedef struct tj_sight_row {
+  double t_first_lo, t_first_hi;   /* the link first comes within dist of the obstacles in [t_first_lo, t_first_hi] */
+  double t_last_lo,  t_last_hi;    /* ... and is last within dist in [t_last_lo, t_last_hi] */
+  double within_lo;                /* seconds CERTIFIED within dist inside the row (sum of the IN leaves) */
+  double closest, closest_time;    /* smallest attained end sample of the row and its time (not converged) */
+  int link, robot, partner;        /* the caller's index of the link, its robot a and its b as given (a robot, or -1 - station) */
+  int index;                       /* the primitive of `closest` (caller's index), -1 without one */
+  int leaves, depth, flags, windows;
+} tj_sight_row;
+int tj_sight_windows(tj_ctx* c, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows,
+                     tj_sight_row* rows, int cap, int* n);
+int tj_sight_row_size(void);   /* sizeof(tj_sight_row) */
 /* ---- tj_peak_dynamics: how fast every robot's FLOWN CURVE really gets -- peak speed, acceleration and jerk, converged, each with its flight time -- how long
  * its path is, and by how much its timetable could be compressed (csrc/kernels_peak_dynamics.h; read-only like tj_audit).  tj_audit's speed / accel are maxima
  * over the control vectors of each segment's derivative nets: what bound_energy constrains, but only an upper bound on what the vehicle does, without a time --
@@ -1077,6 +1209,7 @@ int tj_group_timing_margin(tj_group* g, double dist, double max_slip, double tol
 int tj_group_proximity_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_proximity_row* rows, int cap, int* n_pairs, int* n);   /* tj_proximity_windows of every robot by its owner, the ranks' rows one after the other: (robot, partner, t_first_lo) order, bitwise one context's; every rank gets `cap` pair slots and the rows' remaining room */
 int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_depth, int max_windows, tj_obstacle_robot* records);   /* tj_obstacle_approach of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n);   /* tj_obstacle_windows of every robot by its owner, from the owner's own state, the ranks' rows one after the other: (robot, t_first_lo) order, bitwise one context's */
+int tj_group_sight_windows(tj_group* g, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows, tj_sight_row* rows, int cap, int* n);   /* tj_sight_windows of every link by the rank that owns its robot a, nets and piece_time from the owners: (link, t_first_lo) order, bitwise one context's */
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);   /* tj_peak_dynamics of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */

@@ -35,6 +35,7 @@ EXPORTS = [
     "tj_closest_approach", "tj_closest_record_size", "tj_group_closest_approach",
     "tj_obstacle_approach", "tj_obstacle_record_size", "tj_group_obstacle_approach",
     "tj_obstacle_windows", "tj_obswin_row_size", "tj_group_obstacle_windows",
+    "tj_sight_windows", "tj_sight_row_size", "tj_group_sight_windows",
     "tj_pair_approach", "tj_pair_record_size", "tj_group_pair_approach",
     "tj_path_crossings", "tj_crossing_record_size", "tj_group_path_crossings",
     "tj_timing_margin", "tj_margin_record_size", "tj_group_timing_margin",
@@ -261,6 +262,33 @@ OBSWIN_TOL_FRACTION = 0.01   # TJ_OBSWIN_TOL_FRACTION: tol=None selects this fra
 OBSWIN_MAX_DEPTH = 40        # TJ_OBSWIN_MAX_DEPTH
 OBSWIN_FRONTIER = 128        # TJ_OBSWIN_FRONTIER: what max_windows=None selects
 OBSWIN_MAX_WINDOWS = 1024    # TJ_OBSWIN_MAX_WINDOWS
+
+
+class TjSightRow(C.Structure):
+    """mirror of tj_sight_row (include/trajadmm.h); tj_sight_row_size() is its sizeof on the C side"""
+    _fields_ = [("t_first_lo", C.c_double), ("t_first_hi", C.c_double), ("t_last_lo", C.c_double), ("t_last_hi", C.c_double), ("within_lo", C.c_double),
+                ("closest", C.c_double), ("closest_time", C.c_double), ("link", C.c_int), ("robot", C.c_int), ("partner", C.c_int), ("index", C.c_int),
+                ("leaves", C.c_int), ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int)]
+
+
+SIGHT_FLAGS = dict(certain=1, uncertain=2, at_start=4, at_end=8, resolved=16, truncated=32)
+SIGHT_TOL_FRACTION = 0.01   # TJ_SIGHT_TOL_FRACTION: tol=None selects this fraction of dist over vel_limit, a time
+SIGHT_MAX_DEPTH = 40        # TJ_SIGHT_MAX_DEPTH
+SIGHT_FRONTIER = 128        # TJ_SIGHT_FRONTIER: what max_windows=None selects
+SIGHT_MAX_WINDOWS = 1024    # TJ_SIGHT_MAX_WINDOWS
+SIGHT_PROJECTIONS = 3       # TJ_SIGHT_PROJECTIONS: the alternating projections of a triangle's sample
+
+
+def sight_links(U, n_stations):
+    """what links=None selects: every directed robot pair in (a, b) order, then per robot every station (-1 - s)"""
+    return [(a, b) for a in range(U) for b in range(U) if b != a] + [(a, -1 - s) for a in range(U) for s in range(n_stations)]
+
+
+def _sight_windows(call, U, links, stations, dist, tol, max_depth, max_windows):
+    """shared by Solver.sight_windows / Group.sight_windows: call(links, n_links, stations, n_stations, dist, tol, max_depth, max_windows, rows, cap, n)"""
+    st = np.zeros((0, 3)) if stations is None else np.ascontiguousarray(stations, dtype=np.float64).reshape(-1, 3)
+    lk = np.ascontiguousarray(sight_links(U, len(st)) if links is None else links, dtype=np.int32).reshape(-1, 2)
+    return _listed_rows(TjSightRow, call, (lk.ctypes.data_as(_ip), C.c_int(len(lk)), _d(st), C.c_int(len(st))) + _search_args(dist, tol, max_depth, max_windows))
 
 
 class TjProfileSample(C.Structure):
@@ -965,6 +993,14 @@ class Solver:
         sharded solver (world > 1) answers for its owned robots."""
         return _listed_rows(TjObswinRow, lambda *a: self._check(self.lib.tj_obstacle_windows(self._ctx, *a)), _search_args(dist, tol, max_depth, max_windows))
 
+    def sight_windows(self, links=None, stations=None, dist=None, tol=None, max_depth=None, max_windows=None):
+        """tj_sight_windows: WHEN does the straight line of each link pass within `dist` (None: offset) of the obstacle set.  links [n][2]: (a, b), a a robot, b
+        another robot or -1 - s for row s of stations [m][3] (None: sight_links, every directed pair, then per robot every station); a link is looked at over
+        a's flight, b hovers once it has arrived.  One row per certified time interval, with obstacle_windows' fields and `link` (the index into links),
+        `robot` = a, `partner` = b; `flags` (SIGHT_FLAGS).  Outside every row of a link it is certified farther than dist from every primitive.  Dict of numpy
+        arrays [n] in (link, t_first_lo) order.  Read-only.  All modes (single-UAV: station links); a sharded solver (world > 1) is refused: Group.sight_windows."""
+        return _sight_windows(lambda *a: self._check(self.lib.tj_sight_windows(self._ctx, *a)), self.U, links, stations, dist, tol, max_depth, max_windows)
+
     def peak_dynamics(self, tol=None, max_depth=None, max_windows=None, length_levels=None):
         """tj_peak_dynamics: per robot the FLOWN CURVE's peak speed, acceleration and jerk as brackets lo <= peak <= hi converged to the relative `tol` (None:
         PEAK_TOL) -- `speed_lo`, `speed_hi`, `speed_time` / `speed_segment` of the lo sample, `speed_depth`, `speed_windows`, `speed_flags` (PEAK_FLAGS), the same
@@ -1141,6 +1177,10 @@ class Group:
             self._check(self.lib.tj_group_get_state(self._g, C.c_int(u), None, None, None, None, None, C.byref(pt)))
             out[u] = pt.value
         return out
+
+    def sight_windows(self, links=None, stations=None, dist=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_sight_windows: Solver.sight_windows, each link answered by the rank that owns its robot a, in (link, t_first_lo) order (bitwise one context's)"""
+        return _sight_windows(lambda *a: self._check(self.lib.tj_group_sight_windows(self._g, *a)), self.U, links, stations, dist, tol, max_depth, max_windows)
 
     def peak_dynamics(self, tol=None, max_depth=None, max_windows=None, length_levels=None):
         """tj_group_peak_dynamics: Solver.peak_dynamics of every robot from the rank that owns it (bitwise one context's)"""

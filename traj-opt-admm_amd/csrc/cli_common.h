@@ -307,6 +307,28 @@ inline void print_obstacle_windows(const std::vector<tj_obswin_row>& rows) {
   std::cout << "obswin fleet rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
 }
 
+// --sight-windows: one line per row, in the library's (link, t_first_lo) order, and the fleet's line: links, rows, the rows with a sure time, the grazes, and the
+// seconds certified within dist summed over the rows.  The links: every directed robot pair in (a, b) order, then per robot every station of --sight-station.
+inline std::vector<int> sight_links(int U, int n_stations) {
+  std::vector<int> links;
+  for (int a = 0; a < U; a++) for (int b = 0; b < U; b++) if (b != a) { links.push_back(a); links.push_back(b); }
+  for (int a = 0; a < U; a++) for (int s = 0; s < n_stations; s++) { links.push_back(a); links.push_back(-1 - s); }
+  return links;
+}
+inline void print_sight_windows(const std::vector<tj_sight_row>& rows, int n_links) {
+  std::cout.precision(17);
+  int certain = 0, uncertain = 0;
+  double within = 0.0;
+  for (const tj_sight_row& r : rows) {
+    std::cout << "sight link " << r.link << " uav " << r.robot << " to " << r.partner << " first " << r.t_first_lo << " " << r.t_first_hi << " last " << r.t_last_lo << " " << r.t_last_hi << " within " << r.within_lo
+              << " closest " << r.closest << " time " << r.closest_time << " id " << r.index << " leaves " << r.leaves << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    certain += r.flags & TJ_SIGHT_CERTAIN ? 1 : 0;
+    uncertain += r.flags & TJ_SIGHT_UNCERTAIN ? 1 : 0;
+    within += r.within_lo;
+  }
+  std::cout << "sight fleet " << n_links << " rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
+}
+
 // --obstacle-approach: one line per robot and the fleet's summary (the robot with the smallest attained distance), in the style of --closest-approach
 inline void print_obstacle_approach(const std::vector<tj_obstacle_robot>& rec) {
   std::cout.precision(17);

@@ -63,7 +63,7 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--sight-windows [DIST]] [--sight-station X Y Z].. [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
@@ -71,6 +71,7 @@ int main(int argc, char** argv) {
   bool closest = false; double closest_tol = -1;
   bool obstacle = false; double obstacle_tol = -1;
   bool obswin = false; double obswin_dist = 0;
+  bool sight = false; double sight_dist = 0; std::vector<double> sight_stations;   // (stations in solver units)
   bool pairs = false; double pairs_tol = -1;
   bool crossings = false; double crossings_tol = -1;
   bool margins = false; double margins_tol = -1;
@@ -90,6 +91,8 @@ int main(int argc, char** argv) {
     else if (a == "--closest-approach") { closest = true; if (i + 1 < argc && argv[i + 1][0] != '-') closest_tol = atof(argv[++i]); }
     else if (a == "--obstacle-approach") { obstacle = true; if (i + 1 < argc && argv[i + 1][0] != '-') obstacle_tol = atof(argv[++i]); }
     else if (a == "--obstacle-windows") { obswin = true; if (i + 1 < argc && argv[i + 1][0] != '-') obswin_dist = atof(argv[++i]); }
+    else if (a == "--sight-windows") { sight = true; if (i + 1 < argc && argv[i + 1][0] != '-') sight_dist = atof(argv[++i]); }
+    else if (a == "--sight-station" && i + 3 < argc) { for (int k = 0; k < 3; k++) sight_stations.push_back(atof(argv[++i])); }
     else if (a == "--pair-approach") { pairs = true; if (i + 1 < argc && argv[i + 1][0] != '-') pairs_tol = atof(argv[++i]); }
     else if (a == "--path-crossings") { crossings = true; if (i + 1 < argc && argv[i + 1][0] != '-') crossings_tol = atof(argv[++i]); }
     else if (a == "--timing-margin") { margins = true; if (i + 1 < argc && argv[i + 1][0] != '-') margins_tol = atof(argv[++i]); }
@@ -234,6 +237,16 @@ int main(int argc, char** argv) {
       chk(tjcli::listed_rows([&](tj_obswin_row* out, int cap, int* n) {
             return group ? tj_group_obstacle_windows(grp, obswin_dist, -1.0, -1, 0, out, cap, n) : tj_obstacle_windows(ctx, obswin_dist, -1.0, -1, 0, out, cap, n); }, rows), "tj_obstacle_windows");
       tjcli::print_obstacle_windows(rows);
+    }
+    if (sight) {
+      const int n_stations = (int)sight_stations.size() / 3;
+      const std::vector<int> links = tjcli::sight_links(U, n_stations);
+      const int n_links = (int)links.size() / 2;
+      std::vector<tj_sight_row> rows;
+      chk(tjcli::listed_rows([&](tj_sight_row* out, int cap, int* n) {
+            return group ? tj_group_sight_windows(grp, links.data(), n_links, sight_stations.data(), n_stations, sight_dist, -1.0, -1, 0, out, cap, n)
+                         : tj_sight_windows(ctx, links.data(), n_links, sight_stations.data(), n_stations, sight_dist, -1.0, -1, 0, out, cap, n); }, rows), "tj_sight_windows");
+      tjcli::print_sight_windows(rows, n_links);
     }
     if (pairs) {
       std::vector<tj_pair_record> rows;

@@ -50,6 +50,11 @@ struct BodyHull {  // 6 control points of one Bezier segment, row-major [6][3] (
   static constexpr int N = 6;
   __device__ __forceinline__ V3 get(int i) const { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 };
+struct BodyHull12 {  // two 6-point nets, row-major [12][3] (LDS): the hull of a link between two segments (kernels_sight_windows.h)
+  const double* p;
+  static constexpr int N = 12;
+  __device__ __forceinline__ V3 get(int i) const { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+};
 template <int STRIDE>
 struct BodyHullT {  // the same, one hull per LANE in a transposed LDS tile: entry e of this lane's hull at p[e * STRIDE] (p already points at the lane's column)
   const double* p;

@@ -70,6 +70,27 @@ __device__ __forceinline__ int timed_first_segment(double t0, double ptq, double
   return j;
 }
 
+// THE CUTS of a window [t0, t1] of u's time at q's segment boundaries and arrival, in time order: f(j, hover, ca, cb) once per piece [ca, cb], which lies in segment j of q
+// (j == S, hover: q has arrived).  The one loop of timed_walk and of kernels_sight_windows.h's seeds: adjacent pieces share an end bit for bit.
+template <class F>
+__device__ __forceinline__ void timed_cuts(double t0, double t1, double ptq, double res, int S, F&& f) {
+  int j = timed_first_segment(t0, ptq, res, S);
+  do {
+    const bool hover = j >= S;
+    const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
+    f(j, hover, fmax(t0, Tj), hover ? t1 : fmin(t1, Tj1));
+    j++;
+  } while (j <= S && (j / res) * ptq < t1);
+}
+
+// where a window [ca, cb] lies in segment tr of u (sa, sb) and in segment j of q (ra, rb), each in its segment's own parameter: what both raw hulls are restricted to
+struct TimedSpan { double sa, sb, ra, rb; };
+__device__ __forceinline__ TimedSpan timed_span(double res, double ptu, double ptq, int tr, int j, double ca, double cb) {
+  const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
+  const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq, lenq = Tj1 - Tj;
+  return TimedSpan{clamp01((ca - T0u) / lenu), clamp01((cb - T0u) / lenu), clamp01((ca - Tj) / lenq), clamp01((cb - Tj) / lenq)};
+}
+
 // q's raw hull of segment j (hover: six times its last control point) into a lane's column of a tile of stride ST
 template <int ST>
 __device__ __forceinline__ void timed_partner_fill(const Dev& D, const double* nq, int j, bool hover, double* cq) {
@@ -122,27 +143,20 @@ __device__ __forceinline__ void timed_walk(const Dev& D, const double* net, cons
   const int lane = lane_id(), S = D.S, U = D.U;
   const double res = (double)D.res, ptu = pt[u];
   const int N = 1 << L, per = 64 >> L, w = lane & (N - 1), ql = lane >> L;
-  const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
   const double t0 = ((tr + w / (double)N) / res) * ptu, t1 = ((tr + (w + 1) / (double)N) / res) * ptu;   // (the last sub-window ends at T1u bit for bit)
   for (int base = 0; base < U; base += per) {
     const int q = base + ql;
     if (q >= U || q == u) continue;
     const double ptq = pt[q];
     const double* nq = net + (size_t)q * 3 * D.T;
-    int j = timed_first_segment(t0, ptq, res, S);
-    do {
-      const bool hover = j >= S;
-      const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
-      const double ca = fmax(t0, Tj), cb = hover ? t1 : fmin(t1, Tj1);
+    timed_cuts(t0, t1, ptq, res, S, [&](int j, bool hover, double ca, double cb) {
       if (timed_partner_hull(D, nq, j, hover, cq, box, range)) {
-        const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-        const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+        const TimedSpan sp = timed_span(res, ptu, ptq, tr, j, ca, cb);
         double lo, h0, h5; bool sep = true;
-        timed_window<1, 64>(P, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, CERT ? &sep : nullptr);
+        timed_window<1, 64>(P, cq, cd, hover, sp.sa, sp.sb, sp.ra, sp.rb, lo, h0, h5, CERT ? &sep : nullptr);
         f(q, w, j, ca, cb, lo, h0, h5, sep);
       }
-      j++;
-    } while (j <= S && (j / res) * ptq < t1);
+    });
   }
 }
 

@@ -92,14 +92,11 @@ struct TimedSearch {
     const double ca = c ? cm : w.ca, cb = c ? w.cb : cm;
     const bool hover = w.j >= S;
     const double ptq = pt[w.q];
-    const double T0u = (w.tr / res) * ptu, T1u = ((w.tr + 1) / res) * ptu, lenu = T1u - T0u;
-    const double Tj = (w.j / res) * ptq, Tj1 = ((w.j + 1) / res) * ptq;
     for (int e = 0; e < 18; e++) cp[e * THREADS] = hull_entry(D, nu, w.tr, e / 3, e % 3);
     timed_partner_fill<THREADS>(D, net + (size_t)w.q * 3 * D.T, w.j, hover, cq);
-    const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-    const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+    const TimedSpan sp = timed_span(res, ptu, ptq, w.tr, w.j, ca, cb);
     double lo, h0, h5; bool sep;
-    timed_window<THREADS, THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
+    timed_window<THREADS, THREADS>(cp, cq, cd, hover, sp.sa, sp.sb, sp.ra, sp.rb, lo, h0, h5, &sep);
     if (!sep) lo = 0.0;
     const bool first = h0 <= h5;
     const QBest b{first ? h0 : h5, first ? ca : cb, w.tr, w.q};

@@ -107,14 +107,11 @@ __device__ __forceinline__ int prox_eval(const Dev& D, const double* nu, double 
   const int S = D.S;
   const double res = (double)D.res;
   const bool hover = j >= S;
-  const double T0u = (tr / res) * ptu, T1u = ((tr + 1) / res) * ptu, lenu = T1u - T0u;
-  const double Tj = (j / res) * ptq, Tj1 = ((j + 1) / res) * ptq;
   for (int e = 0; e < 18; e++) cp[e * PX_THREADS] = hull_entry(D, nu, tr, e / 3, e % 3);
   timed_partner_fill<PX_THREADS>(D, nq, j, hover, cq);
-  const double sa = clamp01((ca - T0u) / lenu), sb = clamp01((cb - T0u) / lenu);
-  const double lenq = Tj1 - Tj, ra = clamp01((ca - Tj) / lenq), rb = clamp01((cb - Tj) / lenq);
+  const TimedSpan sp = timed_span(res, ptu, ptq, tr, j, ca, cb);
   double lo; bool sep;
-  timed_window<PX_THREADS, PX_THREADS>(cp, cq, cd, hover, sa, sb, ra, rb, lo, h0, h5, &sep);
+  timed_window<PX_THREADS, PX_THREADS>(cp, cq, cd, hover, sp.sa, sp.sb, sp.ra, sp.rb, lo, h0, h5, &sep);
   return prox_class(sep, lo, prox_ub<PX_THREADS>(cd), dist);
 }
 

@@ -43,6 +43,7 @@
 #include "kernels_timing_margin.h"
 #include "kernels_proximity.h"
 #include "kernels_flight_profile.h"
+#include "kernels_sight_windows.h"
 #include "host_plan.h"
 #include "host_launch.h"
 
@@ -84,6 +85,10 @@ struct ProxHeld : Listed<ProxArgs, tj_proximity_row> { int* n_rows = nullptr; };
 
 // what a context holds for tj_obstacle_windows (obswin_run): the per-segment lists grow with the largest max_windows so far, the rows with the largest cap
 struct ObwinHeld { ObwinArgs sized{}; int* n_rows = nullptr; tj_obswin_row* out = nullptr; std::vector<void*> allocs, out_allocs; int mw = 0, cap = 0; };
+
+// what a context holds for tj_sight_windows (sight_run): the lists grow with the largest n_links x S x leaf_cap so far, the counters with the largest n_links x S, the links and stations with their counts, the
+// rows with the largest cap
+struct SightHeld { SightArgs sized{}; int* links = nullptr; double* stations = nullptr; int* n_rows = nullptr; tj_sight_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t items = 0, units = 0; int n_links = 0, n_stations = 0, cap = 0; };
 
 struct tj_ctx {
   tj_params prm;
@@ -132,6 +137,7 @@ struct tj_ctx {
   Listed<MarginArgs, tj_margin_record> margin;
   ProxHeld prox;   // tj_proximity_windows
   ObwinHeld obwin; // tj_obstacle_windows
+  SightHeld sight; // tj_sight_windows
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -708,6 +714,8 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->prox.allocs) hipFree(p);
   for (void* p : c->obwin.allocs) hipFree(p);
   for (void* p : c->obwin.out_allocs) hipFree(p);
+  for (void* p : c->sight.allocs) hipFree(p);
+  for (void* p : c->sight.out_allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1204,7 +1212,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the eleven (the kernels: kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
+// ---- the read-only queries: one path for the twelve (the kernels: kernels_sight_windows.h, kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1239,7 +1247,9 @@ const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approac
                  SEARCH_OBSTACLE{"tj_obstacle_approach", "tj_group_obstacle_approach", TJ_OBSTACLE_MAX_DEPTH, TJ_OBSTACLE_FRONTIER, TJ_OBSTACLE_TOL, TJ_OBSTACLE_FRONTIER,
                                  ": deeper windows are not dyadic in a double", ": the live list's capacity"},
                  SEARCH_OBSWIN{"tj_obstacle_windows", "tj_group_obstacle_windows", TJ_OBSWIN_MAX_DEPTH, TJ_OBSWIN_MAX_WINDOWS, 0.0, TJ_OBSWIN_FRONTIER,
-                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_OBSWIN_TOL_FRACTION, true};
+                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_OBSWIN_TOL_FRACTION, true},
+                 SEARCH_SIGHT{"tj_sight_windows", "tj_group_sight_windows", TJ_SIGHT_MAX_DEPTH, TJ_SIGHT_MAX_WINDOWS, 0.0, TJ_SIGHT_FRONTIER,
+                              ": deeper windows cannot be halved in a double", ": the in-kernel rank sort's bound", true, TJ_SIGHT_TOL_FRACTION, true};
 struct SearchArgs {
   double range, tol; int max_depth, max_windows;
   template <class Args> void put(Args& a) const { a.range = range; a.tol = tol; a.max_depth = max_depth; a.max_windows = max_windows; }
@@ -1290,7 +1300,7 @@ int query_finish(tj_ctx* c, const char* walk) {
   return TJ_OK;
 }
 
-// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, profile_run) ----
+// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, profile_run) ----
 // the refusal of a call whose buffers would exceed its query's byte budget, up front, nothing allocated.  what: the call's sizes in its words; advice: what to lower
 int query_budget(tj_ctx* c, const std::string& what, size_t bytes, const char* budget, long long max_bytes, const char* advice) {
   if (bytes <= (size_t)max_bytes) return TJ_OK;
@@ -1636,6 +1646,73 @@ int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_window
   return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
 }
 
+// tj_sight_windows (kernels_sight_windows.h): the rows of the links (a, b) whose a is owned, `link` = the caller's index; a link of another rank's robot has no row here
+// (a group asks every rank for the whole list and places the rows by link).  The other end's net and piece_time are read, so a sharded context needs them handed in.
+// *n = the rows; min(cap, *n) of them are written.  TJ_ERR_CAPACITY has two causes, as in obswin_run: more rows than cap (*n is set, and exceeds cap) and a walk frontier
+// overflow (*n is left untouched).  Three launches for the rows, two for the count.
+size_t sight_bytes(const Dev& d, int n_links, int n_stations, int cap, int mw) {
+  return (size_t)n_links * d.S * ((size_t)2 * (2 * mw + d.S + 1) * sizeof(SightLeaf) + 4 * sizeof(int)) + (size_t)n_links * 4 * sizeof(int) + (size_t)n_stations * 3 * sizeof(double) + (size_t)cap * sizeof(tj_sight_row);
+}
+int sight_run(tj_ctx* c, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows,
+              const double* net_host, const double* pt_host, tj_sight_row* rows, int cap, int* n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !rows) || n_links < 0 || (n_links > 0 && !links) || n_stations < 0 || (n_stations > 0 && !stations)) return TJ_ERR_INVALID;
+  const SearchSpec& spec = SEARCH_SIGHT;
+  const std::string name = spec.name;
+  int r;
+  for (int k = 0; k < 3 * n_stations; k++) if ((r = query_nan(c, spec.name, "a station coordinate", stations[k]))) return r;
+  SearchArgs sa;
+  if ((r = search_args(c, spec, dist, tol, max_depth, max_windows, sa))) return r;
+  const Dev& d = c->d;
+  for (int k = 0; k < n_links; k++) {
+    const int a = links[2 * k], b = links[2 * k + 1];
+    if (a < 0 || a >= d.U || b == a || b >= d.U || b < -n_stations) {
+      c->err = name + ": link " + std::to_string(k) + " = (" + std::to_string(a) + ", " + std::to_string(b) + "): a must be a robot, b another robot or -1 - s for one of the " + std::to_string(n_stations) + " stations";
+      return TJ_ERR_INVALID;
+    }
+  }
+  const int mw = sa.max_windows, leaf_cap = 2 * mw + d.S + 1;
+  if ((r = query_budget(c, name + ": " + std::to_string(n_links) + " links of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
+                        sight_bytes(d, n_links, n_stations, cap, mw), "TJ_SIGHT_MAX_BYTES", TJ_SIGHT_MAX_BYTES, "lower max_windows, cap or the number of links")) ||
+      (r = query_state(c, spec.name, true, net_host && pt_host))) return r;
+  if (d.N == 0 || n_links == 0) { *n = 0; return TJ_OK; }   // no obstacles: no link is within any distance of them
+  QUIESCE(c);
+  SightHeld& h = c->sight;
+  const size_t units = (size_t)n_links * d.S, items = units * leaf_cap;
+  if ((r = query_buf(c, h.n_rows, 1)) || (r = ensure_order(c))) return r;
+  if (items > h.items || units > h.units || n_links > h.n_links || n_stations > h.n_stations) {
+    const size_t gi = std::max(items, h.items), gu = std::max(units, h.units);
+    const int gl = std::max(n_links, h.n_links), gs = std::max(n_stations, h.n_stations);
+    if ((r = query_grow(h.allocs, [&] { h.sized = {}; h.links = nullptr; h.stations = nullptr; h.items = 0; h.units = 0; h.n_links = 0; h.n_stations = 0; }, [&] {
+           int e;   // (the first failure, or TJ_OK)
+           (e = query_buf(c, h.sized.list, gi, &h.allocs)) || (e = query_buf(c, h.sized.leaf, gi, &h.allocs)) || (e = query_buf(c, h.sized.info, gu * 4, &h.allocs)) ||
+               (e = query_buf(c, h.sized.link, (size_t)gl * 2, &h.allocs)) || (e = query_buf(c, h.links, (size_t)gl * 2, &h.allocs)) || (e = query_buf(c, h.stations, (size_t)gs * 3, &h.allocs));
+           return e;
+         }))) return r;
+    h.items = gi; h.units = gu; h.n_links = gl; h.n_stations = gs;
+  }
+  if (cap > h.cap) {
+    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
+    h.cap = cap;
+  }
+  SightArgs a = h.sized;
+  Dev da;
+  if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt)) || (r = walk_dev(c, da)) || (r = upload(c, h.links, links, (size_t)n_links * 2 * sizeof(int))) ||
+      (r = upload(c, h.stations, stations, (size_t)n_stations * 3 * sizeof(double)))) return r;
+  a.order = c->q_order; a.links = h.links; a.stations = h.stations; sa.put(a); a.leaf_cap = leaf_cap; a.row_cap = cap; a.n_rows = h.n_rows;
+  if ((r = query_clear(c, h.n_rows, 1))) return r;
+  with_prim(d, [&](auto prim) { hipLaunchKernelGGL(k_sight_refine<decltype(prim)::value>, dim3((unsigned)units), dim3(SW_THREADS), 0, c->stream, da, a); });
+  hipLaunchKernelGGL(k_sight_count, dim3(n_links), dim3(SW_THREADS), 0, c->stream, da, a);
+  if (cap > 0) hipLaunchKernelGGL(k_sight_place, dim3(n_links), dim3(SW_THREADS), 0, c->stream, da, a, h.out);
+  int nr = 0;
+  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, spec.name))) {   // (a walk overflow ends here: no count is known, *n stays untouched)
+    if (r == TJ_ERR_CAPACITY)   // (query_finish words it for a `range`; this query's first argument is `dist`)
+      c->err = name + ": the BVH frontier of a window overflowed at this dist (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one window's box): lower `dist`";
+    return r;
+  }
+  *n = nr;
+  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+}
+
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
 int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
   if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
@@ -1726,6 +1803,10 @@ int tj_obstacle_approach(tj_ctx* c, double range, double tol, int max_depth, int
 int tj_obstacle_record_size(void) { return (int)sizeof(tj_obstacle_robot); }
 int tj_obstacle_windows(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) { return obswin_run(c, dist, tol, max_depth, max_windows, rows, cap, n); }
 int tj_obswin_row_size(void) { return (int)sizeof(tj_obswin_row); }
+int tj_sight_windows(tj_ctx* c, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows, tj_sight_row* rows, int cap, int* n) {
+  return sight_run(c, links, n_links, stations, n_stations, dist, tol, max_depth, max_windows, nullptr, nullptr, rows, cap, n);
+}
+int tj_sight_row_size(void) { return (int)sizeof(tj_sight_row); }
 
 // tj_peak_dynamics: every owned robot from the context's own state, like tj_obstacle_approach.  Argument checks in the queries' precedence: null -> NaN -> limits -> no state
 int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* out) {

@@ -738,6 +738,36 @@ int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_dept
   return TJ_OK;
 }
 
+// tj_sight_windows, rank after rank with nets and piece_time from the owners: every rank gets the whole link list and answers the links whose robot a it owns, with
+// room for the first `cap` of its rows; the host then places the rows link after link -- each link's rows come from one rank, in time order -- which is one
+// context's (link, t_first_lo) order.  A rank whose rows exceed `cap` is counted in full.  A walk frontier overflow leaves the rank's count untouched and so ends the
+// group's call with the rank's TJ_ERR_CAPACITY, *n untouched.
+int tj_group_sight_windows(tj_group* g, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows, tj_sight_row* rows, int cap, int* n) {
+  if (!g || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  std::vector<std::vector<tj_sight_row>> part(g->n);
+  std::vector<int> count(g->n, 0);
+  const int rc = group_each(g, true, true, [&](int r, tj_ctx* c, const double* net, const double* pt) {
+    part[r].resize(cap);
+    int nr = -1;
+    const int e = sight_run(c, links, n_links, stations, n_stations, dist, tol, max_depth, max_windows, net, pt, cap ? part[r].data() : nullptr, cap, &nr);
+    if (e < 0 && !(e == TJ_ERR_CAPACITY && nr > cap)) return e;
+    count[r] = nr;
+    return (int)TJ_OK;
+  });
+  if (rc < 0) return rc;
+  int total = 0, written = 0;
+  for (int r = 0; r < g->n; r++) total += count[r];
+  std::vector<int> at(g->n, 0);
+  for (int k = 0; k < n_links && written < cap; k++)
+    for (int r = 0; r < g->n; r++) {
+      if (links[2 * k] < g->ctx[r]->d.u0 || links[2 * k] >= g->ctx[r]->d.u1) continue;
+      while (written < cap && at[r] < std::min(count[r], cap) && part[r][at[r]].link == k) rows[written++] = part[r][at[r]++];
+    }
+  *n = total;
+  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_sight_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* out) {
   return group_query(g, false, false, out, {}, {}, [&](tj_ctx* c, const double*, const double*, tj_dynamics_robot* part) {
     return tj_peak_dynamics(c, tol, max_depth, max_windows, length_levels, part); });

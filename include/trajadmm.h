@@ -1003,6 +1003,110 @@ typedef struct tj_dynamics_robot {
 } tj_dynamics_robot;
 int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);
 int tj_dynamics_record_size(void);   /* sizeof(tj_dynamics_robot) */
+/* ---- tj_dynamics_windows: FROM WHEN TO WHEN is every robot's flown curve over (or under) a level of speed, acceleration or jerk, as certified time intervals
+ * (csrc/kernels_dynamics_windows.h; read-only like tj_peak_dynamics).  tj_peak_dynamics names one peak per robot and quantity and time_scale; a state that is not
+ * yet inside its limits -- an init file, tj_plan_init's output, a run stopped early, a timetable about to be compressed by a factor below time_scale -- exceeds a
+ * limit over stretches, often several per flight, and re-timing or re-planning needs each with certified start and end times.  tj_flight_profile samples, and
+ * samples certify nothing between them; tj_audit's speed / accel are control-vector maxima without a time.  The opposite sense, "when is the robot slower than a
+ * level", gives hover and loiter stretches and hand-over points.  The interval counterpart of tj_peak_dynamics, as tj_obstacle_windows is tj_obstacle_approach's.
+ * Nothing of another robot is read: all three modes, single-UAV included.  A gate k is (quantity q, sense, level); for every OWNED robot u and every gate:
+ *   window   W = (segment tr, [sa, sb] in [0, 1] of the segment's local parameter), dyadic, as in tj_obstacle_windows; the real time of parameter s of segment
+ *            tr is ((tr + s) / res) * piece_time[u], used wherever a time is formed.  The position on the flight tr + s is exact in a double (9 + 40 bits).
+ *   net      c_0..c_n = tj_peak_dynamics' net: the raw derivative net of degree n = 4 (speed), 3 (acceleration), 2 (jerk) restricted to W by bez_restrict_n,
+ *            always from the RAW net.  A vector c counts as norm3(c) / den, den in tj_peak_dynamics' association.
+ *   bounds   ub(W) = max_i norm3(c_i) / den (at [0, 1] tj_audit's and tj_peak_dynamics' depth-0 bits).  lb(W): d = c_0 + c_1 + .. + c_n per axis, left to
+ *            right; lb = (min_i dot3(c_i, d) / norm3(d)) / den where norm3(d) > 0 and the minimum is positive, else 0; dot3(c, d) = (c.x * d.x + c.y * d.y) +
+ *            c.z * d.z.  The derivative lies in the hull of its net and |x| >= x . d / |d|, so lb <= the value on W <= ub.  h0, h5 = norm3(c_0) / den,
+ *            norm3(c_n) / den: the values AT sa and sb, attained.
+ *   class    ABOVE (within = value >= level): OUT if ub < level, else IN if lb >= level, else MIXED.  BELOW (within = value <= level): OUT if lb > level, else IN
+ *            if ub <= level, else MIXED.  With sigma = -1 (ABOVE) / +1 (BELOW), g = sigma * value and L = sigma * level (negation is exact), "within" is
+ *            g <= L for both senses, and the smallest g is the extreme value: the merge below is tj_obstacle_windows' with L as its dist and g as its distance.
+ *   search   ONE per (robot, gate) over the whole flight.  Seeds: every segment at [0, 1]: IN to the leaves, MIXED to the live set, OUT dropped; seeding is
+ *            never truncated.  Round d = 1, 2, ..: a live window whose time width ((sb - sa) / res) * piece_time[u] <= tol becomes an EDGE leaf with its h0 and
+ *            h5; every other is halved at 0.5 * (sa + sb) and both children are evaluated from the raw net: OUT dropped, IN to the leaves, MIXED to the next
+ *            live set.
+ *   stop     the live set is empty | d == max_depth | after a round the live set holds more than max_windows or the leaves more than S + max_windows
+ *            (TRUNCATED: the lists of the last completed round stand, `windows` counts the overflowing round's work too).  What is live at the end joins the
+ *            leaves as EDGE leaves.
+ *   merge    the leaves by flight position tr + sa: distinct and disjoint.  Two consecutive leaves are adjacent exactly when prev.tr + prev.sb == next.tr +
+ *            next.sa on doubles (a chain crosses segment boundaries with no special case).  A row is a maximal chain.
+ *   row      brackets, sure times, within_lo and flags by tj_obstacle_windows' rules word for word (a sure time: every time of an IN leaf; of an EDGE leaf sa
+ *            if h0 is within the level and sb if h5 is).  extreme, extreme_time = ABOVE the largest, BELOW the smallest attained end sample of the chain and
+ *            its time (equal values: the earlier time) -- not converged: tj_peak_dynamics converges the peak.  robot, gate (the index in `gates`), quantity,
+ *            sense; segment_first, segment_last = the segments of the chain's ends; leaves = the chain's length; depth = the completed rounds of the (robot,
+ *            gate) search; windows = its work, seeds + 2 per halved window; both repeated on each of its rows.
+ *   flags    CERTAIN or UNCERTAIN, AT_START, AT_END, RESOLVED, TRUNCATED (the search of the row's robot and gate was truncated): tj_obstacle_windows' meanings.
+ * Every field is a function of the state and the arguments alone; no order of evaluation or of any append is visible.  Rows are sorted by (robot, gate,
+ * t_first_lo).  Outside every row of a gate the robot is certified on the other side of the level, up to the stated limits.
+ * gates == NULL with n_gates == 0 selects the two default gates: (SPEED, ABOVE, vel_limit) and (ACCEL, ABOVE, acc_limit).  A non-null `gates` with n_gates == 0
+ * is an empty list: 0 rows.  n_gates <= TJ_DYNWIN_MAX_GATES.  A NaN level, a quantity or a sense out of range: TJ_ERR_INVALID.  Any other level is valid:
+ * level <= 0 ABOVE (and +infinity BELOW) gives the whole flight in one AT_START | AT_END row per robot, +infinity ABOVE none.  tol < 0:
+ * (TJ_DYNWIN_TOL_FRACTION * vel_limit) / acc_limit -- a design condition, stated as such: the time in which a vehicle at the acceleration limit changes its speed
+ * by 1 % of the speed limit, 0.01 s at the shipped parameters; 0 is valid.  max_depth < 0: TJ_DYNWIN_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0:
+ * TJ_DYNWIN_FRONTIER; above TJ_DYNWIN_MAX_WINDOWS (it bounds the in-kernel rank sort) TJ_ERR_INVALID.  *n = the rows.  *n > cap: TJ_ERR_CAPACITY with the exact
+ * *n, the first `cap` rows in order have been written.  cap == 0 with rows == NULL is the count-only call (one launch).  n == NULL, cap < 0, rows == NULL with
+ * cap > 0, n_gates < 0, gates == NULL with n_gates > 0, a NaN tol or level, a call before tj_init_state: TJ_ERR_INVALID, the outputs untouched (precedence: null,
+ * NaN, limits, no state).  A plain SHARDED context (world > 1) answers for its owned robots, as tj_peak_dynamics does.  tj_group_dynamics_windows returns the
+ * owners' rows one after the other, bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, and is a function of owned x n_gates x (S, max_windows) (S = piece_num * res):
+ *   owned * n_gates * ((3 * S + 4 * max_windows) * 56 + 16) + cap * 96 bytes
+ *   (per (robot, gate) the two live lists of S + max_windows windows, which hold the sorted leaves afterwards, and S + 2 * max_windows leaves, 56 bytes a
+ *   window; its four counters; the rows).  A call whose figure exceeds TJ_DYNWIN_MAX_BYTES is refused up front with TJ_ERR_INVALID: lower max_windows, cap or the
+ *   number of gates.
+ * TWO launches whatever the fleet's size, the number of gates and the depth (one for the count-only call); no host loop over robots, gates or rounds.  Changes
+ * no solver state, statistics or launch count.
+ * STATED LIMITS.  (1) ub and lb are sound up to rounding, in tj_peak_dynamics' terms: the roundings of the blossoming, norm3, the sum, the dot products and the
+ * divisions, a small multiple of eps = 2^-53 of the robot's depth-0 ub of that quantity.  The CPU test measures, against the polynomial's real roots in mpmath,
+ * the largest excess by which the truth contradicts a certified class (an OUT window or a gap holding a within time, an IN leaf holding an outside time), on
+ * the four end states and tiny()'s initial states at the measurement's gates: no truly-within time outside a row (0), and 1.54 eps of the depth-0 ub inside
+ * an IN leaf (a level the quantity touches: BELOW at 1.0 of the state's own jerk bound); the test allows the next power of two >= 16 x that, 32 eps.  (2) A quantity that EQUALS the level over an interval (a constant-speed line at exactly that speed; a hover at
+ * level 0 BELOW is IN: ub = 0 <= 0) is resolved only down to tol, or ends TRUNCATED.  (3) Gaps shorter than a leaf are not resolved; UNCERTAIN rows are grazes at
+ * the resolution tol.
+ * The defaults are measured (tests/dynamics_windows_ref.py default_tolerance, the restatement, on the CPU; tools/dynamics_windows_measure.py prints the tables):
+ * the default tol (0.01 s), max_depth = 40, the lists capped at TJ_DYNWIN_MAX_WINDOWS only, on the final states of tests/golden/e2e_scn_a.npz, e2e_scn_b.npz,
+ * e2e_scn_c3.npz, e2e_scn_b_coupled.npz and on the same runs' iteration-0 states (_init); gates: all three quantities, both senses, levels 1.0 / 0.9 / 0.5 of
+ * the limit (jerk: of the state's own largest depth-0 ub).  Per state the sums over its 18 gates of rows, UNCERTAIN rows and TRUNCATED rows, and the maxima of
+ * the live set after a round >= 1, the leaf list, the depth and the widest bracket of a CERTAIN row:
+ *   state                    rows   uncertain   truncated   largest live set   largest leaf list   largest depth   widest bracket
+ *   e2e_scn_a                33     0           0           8                  47                  5               6.10e-03
+ *   e2e_scn_a_init           26     0           0           12                 86                  9               9.77e-03
+ *   e2e_scn_b                281    0           0           8                  58                  6               8.98e-03
+ *   e2e_scn_b_init           105    0           0           2                  48                  9               9.77e-03
+ *   e2e_scn_c3               2241   0           0           8                  62                  6               8.98e-03
+ *   e2e_scn_c3_init          851    0           0           5                  70                  9               9.77e-03
+ *   e2e_scn_b_coupled        281    0           0           8                  58                  6               8.98e-03
+ *   e2e_scn_b_coupled_init   105    0           0           2                  48                  9               9.77e-03
+ * A level set is crossed at isolated times, so the live set of a search stays at a few windows per crossing; what grows is the leaf list, by the IN windows of
+ * a stay within the level.  TJ_DYNWIN_FRONTIER is the next power of two >= 4 x the largest live set, and at least 64. */
+#define TJ_DYNWIN_SPEED 0
+#define TJ_DYNWIN_ACCEL 1
+#define TJ_DYNWIN_JERK  2
+#define TJ_DYNWIN_ABOVE 0   /* within = value >= level */
+#define TJ_DYNWIN_BELOW 1   /* within = value <= level */
+#define TJ_DYNWIN_CERTAIN   1    /* a sure time exists: the quantity IS within the level at t_first_hi and at t_last_lo */
+#define TJ_DYNWIN_UNCERTAIN 2    /* no sure time: t_first_hi == t_last_lo == -1.0, a graze at the resolution tol */
+#define TJ_DYNWIN_AT_START  4    /* the chain starts at time 0: nothing lies before it */
+#define TJ_DYNWIN_AT_END    8    /* the chain ends at the end of the robot's flight */
+#define TJ_DYNWIN_RESOLVED  16   /* CERTAIN and both brackets are at most tol wide (a side closed by AT_START / AT_END counts as resolved) */
+#define TJ_DYNWIN_TRUNCATED 32   /* the search of this robot and gate outgrew its lists: the leaves of the last completed round are returned */
+#define TJ_DYNWIN_MAX_GATES 16
+#define TJ_DYNWIN_MAX_DEPTH 40
+#define TJ_DYNWIN_FRONTIER  64
+#define TJ_DYNWIN_MAX_WINDOWS 1024
+#define TJ_DYNWIN_MAX_BYTES (1ll << 31)
+#define TJ_DYNWIN_TOL_FRACTION 0.01
+typedef struct tj_dyn_gate { double level; int quantity, sense; } tj_dyn_gate;   /* TJ_DYNWIN_SPEED | ACCEL | JERK, TJ_DYNWIN_ABOVE | BELOW */
+typedef struct tj_dynwin_row {
+  double t_first_lo, t_first_hi;   /* the quantity first comes within the level in [t_first_lo, t_first_hi] */
+  double t_last_lo,  t_last_hi;    /* ... and is last within it in [t_last_lo, t_last_hi] */
+  double within_lo;                /* seconds CERTIFIED within the level inside the row (sum of the IN leaves) */
+  double extreme, extreme_time;    /* ABOVE: the largest attained end sample of the chain, BELOW: the smallest; not converged: tj_peak_dynamics converges the peak */
+  int robot, gate, quantity, sense;
+  int segment_first, segment_last; /* the segments of the chain's ends */
+  int leaves, depth, flags, windows;
+} tj_dynwin_row;
+int tj_dynamics_windows(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n);
+int tj_dynwin_row_size(void);   /* sizeof(tj_dynwin_row) */
 /* ---- tj_flight_profile: where every robot is at the flight times the caller names, how fast it moves there, how far the NEAREST obstacle primitive is --
  * with no `range`, however far -- and how far the nearest other robot is at the same time (csrc/kernels_flight_profile.h; read-only like tj_audit).  The other
  * queries answer with one minimum per robot or pair, and only inside `range`; this one is the curve against time: what a plot of clearance and speed, a look
@@ -1211,6 +1315,7 @@ int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_de
 int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n);   /* tj_obstacle_windows of every robot by its owner, from the owner's own state, the ranks' rows one after the other: (robot, t_first_lo) order, bitwise one context's */
 int tj_group_sight_windows(tj_group* g, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows, tj_sight_row* rows, int cap, int* n);   /* tj_sight_windows of every link by the rank that owns its robot a, nets and piece_time from the owners: (link, t_first_lo) order, bitwise one context's */
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);   /* tj_peak_dynamics of every robot by its owner, from the owner's own state: bitwise one context's */
+int tj_group_dynamics_windows(tj_group* g, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n);   /* tj_dynamics_windows of every robot by its owner, from the owner's own state, the ranks' rows one after the other: (robot, gate, t_first_lo) order, bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */

@@ -42,6 +42,7 @@ EXPORTS = [
     "tj_proximity_windows", "tj_proximity_row_size", "tj_group_proximity_windows",
     "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
     "tj_peak_dynamics", "tj_dynamics_record_size", "tj_group_peak_dynamics",
+    "tj_dynamics_windows", "tj_dynwin_row_size", "tj_group_dynamics_windows",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -289,6 +290,41 @@ def _sight_windows(call, U, links, stations, dist, tol, max_depth, max_windows):
     st = np.zeros((0, 3)) if stations is None else np.ascontiguousarray(stations, dtype=np.float64).reshape(-1, 3)
     lk = np.ascontiguousarray(sight_links(U, len(st)) if links is None else links, dtype=np.int32).reshape(-1, 2)
     return _listed_rows(TjSightRow, call, (lk.ctypes.data_as(_ip), C.c_int(len(lk)), _d(st), C.c_int(len(st))) + _search_args(dist, tol, max_depth, max_windows))
+
+
+class TjDynGate(C.Structure):
+    """mirror of tj_dyn_gate (include/trajadmm.h)"""
+    _fields_ = [("level", C.c_double), ("quantity", C.c_int), ("sense", C.c_int)]
+
+
+class TjDynwinRow(C.Structure):
+    """mirror of tj_dynwin_row (include/trajadmm.h); tj_dynwin_row_size() is its sizeof on the C side"""
+    _fields_ = [("t_first_lo", C.c_double), ("t_first_hi", C.c_double), ("t_last_lo", C.c_double), ("t_last_hi", C.c_double), ("within_lo", C.c_double),
+                ("extreme", C.c_double), ("extreme_time", C.c_double), ("robot", C.c_int), ("gate", C.c_int), ("quantity", C.c_int), ("sense", C.c_int),
+                ("segment_first", C.c_int), ("segment_last", C.c_int), ("leaves", C.c_int), ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int)]
+
+
+DYNWIN_FLAGS = dict(certain=1, uncertain=2, at_start=4, at_end=8, resolved=16, truncated=32)
+DYNWIN_QUANTITIES = dict(speed=0, accel=1, jerk=2)   # TJ_DYNWIN_SPEED, TJ_DYNWIN_ACCEL, TJ_DYNWIN_JERK
+DYNWIN_SENSES = dict(above=0, below=1)               # TJ_DYNWIN_ABOVE (within = value >= level), TJ_DYNWIN_BELOW (within = value <= level)
+DYNWIN_TOL_FRACTION = 0.01   # TJ_DYNWIN_TOL_FRACTION: tol=None selects this fraction of vel_limit over acc_limit, a time
+DYNWIN_MAX_GATES = 16        # TJ_DYNWIN_MAX_GATES
+DYNWIN_MAX_DEPTH = 40        # TJ_DYNWIN_MAX_DEPTH
+DYNWIN_FRONTIER = 64         # TJ_DYNWIN_FRONTIER: what max_windows=None selects
+DYNWIN_MAX_WINDOWS = 1024    # TJ_DYNWIN_MAX_WINDOWS
+
+
+def dynwin_gates(gates):
+    """a list of (quantity, sense, level), quantity / sense by name (DYNWIN_QUANTITIES / DYNWIN_SENSES) or number -> a list of (int, int, float)"""
+    return [(DYNWIN_QUANTITIES[q] if isinstance(q, str) else int(q), DYNWIN_SENSES[s] if isinstance(s, str) else int(s), float(level)) for q, s, level in gates]
+
+
+def _dynamics_windows(call, gates, tol, max_depth, max_windows):
+    """shared by Solver.dynamics_windows / Group.dynamics_windows: call(gates, n_gates, tol, max_depth, max_windows, rows, cap, n); gates=None: a null list, the
+    two default gates; an empty list: no gate"""
+    gl = None if gates is None else dynwin_gates(gates)
+    arr = None if gl is None else (TjDynGate * max(len(gl), 1))(*[TjDynGate(level, q, s) for q, s, level in gl])
+    return _listed_rows(TjDynwinRow, call, (arr, C.c_int(0 if gl is None else len(gl))) + _search_args(None, tol, max_depth, max_windows)[1:])
 
 
 class TjProfileSample(C.Structure):
@@ -1009,6 +1045,16 @@ class Solver:
         All modes; a sharded solver (world > 1) answers for its owned robots, the other records are zero."""
         return _peak_dynamics(lambda *a: self._check(self.lib.tj_peak_dynamics(self._ctx, *a)), self.U, tol, max_depth, max_windows, length_levels)
 
+    def dynamics_windows(self, gates=None, tol=None, max_depth=None, max_windows=None):
+        """tj_dynamics_windows: per (owned robot, gate) the certified time intervals of the flight in which the flown curve's speed, acceleration or jerk is over
+        (`above`) or under (`below`) a level.  gates: a list of (quantity, sense, level), names (DYNWIN_QUANTITIES, DYNWIN_SENSES) or numbers; None: speed above
+        vel_limit and acceleration above acc_limit.  A row: brackets `t_first_lo` <= first time within <= `t_first_hi` and `t_last_lo` <= last <= `t_last_hi`
+        (-1 without a sure time), resolved to `tol` seconds (None: DYNWIN_TOL_FRACTION * vel_limit / acc_limit); `within_lo` seconds certified within, `extreme`
+        / `extreme_time` the largest (above) or smallest (below) attained end sample, `robot`, `gate`, `quantity`, `sense`, `segment_first`, `segment_last`,
+        `leaves`, `depth`, `windows`, `flags` (DYNWIN_FLAGS).  Outside every row of a gate the robot is certified on the other side of the level.  Dict of numpy
+        arrays [n] in (robot, gate, t_first_lo) order.  Read-only.  All modes; a sharded solver (world > 1) answers for its owned robots."""
+        return _dynamics_windows(lambda *a: self._check(self.lib.tj_dynamics_windows(self._ctx, *a)), gates, tol, max_depth, max_windows)
+
     def piece_times(self):
         """piece_time of every robot as this context holds it"""
         out = np.zeros(self.U)
@@ -1185,6 +1231,10 @@ class Group:
     def peak_dynamics(self, tol=None, max_depth=None, max_windows=None, length_levels=None):
         """tj_group_peak_dynamics: Solver.peak_dynamics of every robot from the rank that owns it (bitwise one context's)"""
         return _peak_dynamics(lambda *a: self._check(self.lib.tj_group_peak_dynamics(self._g, *a)), self.U, tol, max_depth, max_windows, length_levels)
+
+    def dynamics_windows(self, gates=None, tol=None, max_depth=None, max_windows=None):
+        """tj_group_dynamics_windows: Solver.dynamics_windows of every robot from the rank that owns it, in (robot, gate, t_first_lo) order (bitwise one context's)"""
+        return _dynamics_windows(lambda *a: self._check(self.lib.tj_group_dynamics_windows(self._g, *a)), gates, tol, max_depth, max_windows)
 
     def flight_profile(self, times=None, samples=None):
         """tj_group_flight_profile: Solver.flight_profile of every robot from the rank that owns it (bitwise one context's)"""

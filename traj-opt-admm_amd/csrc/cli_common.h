@@ -307,6 +307,23 @@ inline void print_obstacle_windows(const std::vector<tj_obswin_row>& rows) {
   std::cout << "obswin fleet rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
 }
 
+// --dynamics-windows: one line per row, in the library's (robot, gate, t_first_lo) order, and the fleet's line: rows, the rows with a sure time, the grazes, and the
+// seconds certified within the level summed over the rows
+inline void print_dynamics_windows(const std::vector<tj_dynwin_row>& rows) {
+  std::cout.precision(17);
+  int certain = 0, uncertain = 0;
+  double within = 0.0;
+  for (const tj_dynwin_row& r : rows) {
+    std::cout << "dynwin uav " << r.robot << " gate " << r.gate << " quantity " << r.quantity << " sense " << r.sense << " first " << r.t_first_lo << " " << r.t_first_hi << " last " << r.t_last_lo << " "
+              << r.t_last_hi << " within " << r.within_lo << " extreme " << r.extreme << " time " << r.extreme_time << " seg " << r.segment_first << " " << r.segment_last << " leaves " << r.leaves
+              << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    certain += r.flags & TJ_DYNWIN_CERTAIN ? 1 : 0;
+    uncertain += r.flags & TJ_DYNWIN_UNCERTAIN ? 1 : 0;
+    within += r.within_lo;
+  }
+  std::cout << "dynwin fleet rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
+}
+
 // --sight-windows: one line per row, in the library's (link, t_first_lo) order, and the fleet's line: links, rows, the rows with a sure time, the grazes, and the
 // seconds certified within dist summed over the rows.  The links: every directed robot pair in (a, b) order, then per robot every station of --sight-station.
 inline std::vector<int> sight_links(int U, int n_stations) {

@@ -49,6 +49,10 @@
 // --peak-dynamics [TOL]: after the --flight-profile lines one line per robot from tj_peak_dynamics / tj_group_peak_dynamics -- the flown curve's peak speed, acceleration
 // and jerk converged to the relative TOL (default the library's), each with its time, the path length's bracket, duration, time_scale, flag word -- and a fleet line with
 // the largest time_scale and its robot.  Works in the single-UAV main and with --gpus.
+// --dynamics-windows [FRACTION]: after the --peak-dynamics lines one line per row from tj_dynamics_windows / tj_group_dynamics_windows at the two default gates scaled --
+// speed ABOVE FRACTION * vel_limit and acceleration ABOVE FRACTION * acc_limit, FRACTION default 1 -- "dynwin uav gate quantity sense first lo hi last lo hi within
+// extreme time seg a b leaves depth windows flags" at 17 digits, and the fleet's line: rows, rows with a sure time, grazes, seconds certified over the level.
+// Works in the single-UAV main and with --gpus.
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
 #include <chrono>
@@ -63,7 +67,7 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--sight-windows [DIST]] [--sight-station X Y Z].. [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--sight-windows [DIST]] [--sight-station X Y Z].. [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--dynamics-windows [FRACTION]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
@@ -78,6 +82,7 @@ int main(int argc, char** argv) {
   bool proximity = false; double proximity_dist = 0;
   int profile_samples = 0; std::string profile_file;
   bool dynamics = false; double dynamics_tol = -1;
+  bool dynwin = false; double dynwin_fraction = 1;
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -99,6 +104,7 @@ int main(int argc, char** argv) {
     else if (a == "--proximity-windows") { proximity = true; if (i + 1 < argc && argv[i + 1][0] != '-') proximity_dist = atof(argv[++i]); }
     else if (a == "--flight-profile" && i + 1 < argc) { profile_samples = atoi(argv[++i]); if (i + 1 < argc && argv[i + 1][0] != '-') profile_file = argv[++i]; if (profile_samples < 1) { std::cerr << "--flight-profile needs K >= 1" << std::endl; return -1; } }
     else if (a == "--peak-dynamics") { dynamics = true; if (i + 1 < argc && argv[i + 1][0] != '-') dynamics_tol = atof(argv[++i]); }
+    else if (a == "--dynamics-windows") { dynwin = true; if (i + 1 < argc && argv[i + 1][0] != '-') dynwin_fraction = atof(argv[++i]); }
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -295,6 +301,13 @@ int main(int argc, char** argv) {
       std::vector<tj_dynamics_robot> rec(U);
       chk(group ? tj_group_peak_dynamics(grp, dynamics_tol, -1, 0, -1, rec.data()) : tj_peak_dynamics(ctx, dynamics_tol, -1, 0, -1, rec.data()), "tj_peak_dynamics");
       tjcli::print_peak_dynamics(rec);
+    }
+    if (dynwin) {
+      const tj_dyn_gate gates[2] = {{dynwin_fraction * vel, TJ_DYNWIN_SPEED, TJ_DYNWIN_ABOVE}, {dynwin_fraction * acc, TJ_DYNWIN_ACCEL, TJ_DYNWIN_ABOVE}};
+      std::vector<tj_dynwin_row> rows;
+      chk(tjcli::listed_rows([&](tj_dynwin_row* out, int cap, int* n) {
+            return group ? tj_group_dynamics_windows(grp, gates, 2, -1.0, -1, 0, out, cap, n) : tj_dynamics_windows(ctx, gates, 2, -1.0, -1, 0, out, cap, n); }, rows), "tj_dynamics_windows");
+      tjcli::print_dynamics_windows(rows);
     }
     if (!dump.empty()) {
       std::ofstream df(dump);

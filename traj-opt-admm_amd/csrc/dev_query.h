@@ -1,4 +1,4 @@
-// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_obstacle_windows, tj_sight_windows, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_proximity_windows, tj_flight_profile, tj_peak_dynamics), each piece defined once.
+// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_obstacle_windows, tj_sight_windows, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_proximity_windows, tj_flight_profile, tj_peak_dynamics, tj_dynamics_windows), each piece defined once.
 //
 // Every query works per (owned robot, segment) on the segment's 6-point hull (hull_entry's sums: the bits of the hull cache) and its box, and reduces per-lane candidates
 // with a TOTAL order, so that a result is a function of the state alone: no float atomics, no dependence on the order of evaluation.
@@ -9,7 +9,7 @@
 //   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
 //   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
 //   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the five branch-and-bound queries, and their four common flag bits
-//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain   THE MERGE HALF of the three window queries (tj_proximity_windows, tj_obstacle_windows, tj_sight_windows): the classes and
+//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain   THE MERGE HALF of the four window queries (tj_proximity_windows, tj_obstacle_windows, tj_sight_windows, tj_dynamics_windows): the classes and
 //                  the six flag bits, the leaves' rank sort with the interior chain heads, a head's row index, and the fold of a chain into a row's common fields and flags
 #pragma once
 #include <limits.h>
@@ -269,7 +269,7 @@ __device__ __forceinline__ int bnb_flags(bool found, double hi, double lo, doubl
   return (found && hi <= offset ? BNB_CONTACT : 0) | (lo > offset ? BNB_CLEAR : 0) | (hi - lo <= tol || (n == 0 && !truncated) ? BNB_CONVERGED : 0) | (truncated ? BNB_TRUNCATED : 0);
 }
 
-// ---- the merge half of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h): all classify windows against a level, keep leaves, sort them, merge adjacent
+// ---- the merge half of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h, kernels_dynamics_windows.h): all classify windows against a level, keep leaves, sort them, merge adjacent
 // leaves into chains and write a row per chain.  How a window is evaluated, the round loop, what a leaf's times are and where a chain goes on stay with each query. ----
 constexpr int WIN_OUT = 0, WIN_IN = 1, WIN_MIXED = 2;   // a window's class against the level
 constexpr int WIN_CERTAIN = 1, WIN_UNCERTAIN = 2, WIN_AT_START = 4, WIN_AT_END = 8, WIN_RESOLVED = 16, WIN_TRUNCATED = 32;   // a row's flag bits (the two headers' values agree)
@@ -277,6 +277,7 @@ static_assert(TJ_PROXIMITY_CERTAIN == WIN_CERTAIN && TJ_OBSWIN_CERTAIN == WIN_CE
 static_assert(TJ_PROXIMITY_AT_START == WIN_AT_START && TJ_OBSWIN_AT_START == WIN_AT_START && TJ_PROXIMITY_AT_END == WIN_AT_END && TJ_OBSWIN_AT_END == WIN_AT_END, "AT_START, AT_END");
 static_assert(TJ_PROXIMITY_RESOLVED == WIN_RESOLVED && TJ_OBSWIN_RESOLVED == WIN_RESOLVED && TJ_PROXIMITY_TRUNCATED == WIN_TRUNCATED && TJ_OBSWIN_TRUNCATED == WIN_TRUNCATED, "RESOLVED, TRUNCATED");
 static_assert(TJ_SIGHT_CERTAIN == WIN_CERTAIN && TJ_SIGHT_UNCERTAIN == WIN_UNCERTAIN && TJ_SIGHT_AT_START == WIN_AT_START && TJ_SIGHT_AT_END == WIN_AT_END && TJ_SIGHT_RESOLVED == WIN_RESOLVED && TJ_SIGHT_TRUNCATED == WIN_TRUNCATED, "tj_sight_windows' flags");
+static_assert(TJ_DYNWIN_CERTAIN == WIN_CERTAIN && TJ_DYNWIN_UNCERTAIN == WIN_UNCERTAIN && TJ_DYNWIN_AT_START == WIN_AT_START && TJ_DYNWIN_AT_END == WIN_AT_END && TJ_DYNWIN_RESOLVED == WIN_RESOLVED && TJ_DYNWIN_TRUNCATED == WIN_TRUNCATED, "tj_dynamics_windows' flags");
 
 // is leaf i of m sorted leaves a chain head: it does not begin (member A) where the leaf before it ends (member B).  first: what the caller knows of leaf 0
 template <auto A, auto B, class Leaf>

@@ -1,0 +1,222 @@
+// kernels_dynamics_windows.h -- tj_dynamics_windows: WHEN is every robot's flown curve over (or under) a level of speed, acceleration or jerk, as certified time intervals.
+//
+// tj_peak_dynamics names one peak per robot and quantity; a state that is not yet inside its limits exceeds them over stretches, often several per flight.  This is the
+// interval counterpart, the fourth of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h): windows of a segment's parameter are
+// classified against a level and only what is not certified on the far side is kept.  The derivative nets and their blossoming are kernels_peak_dynamics.h's, unchanged
+// (peak_raw, peak_den, peak_net, bez_restrict_n); the merge half is dev_query.h's (WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain).  The definition
+// (include/trajadmm.h), per slot = (owned robot u, gate k) with the gate's quantity (degree n = 4, 3, 2), sense and level:
+//   net      c_0..c_n = the raw derivative net of segment tr restricted to [sa, sb] (always from the RAW net); a vector counts as norm3(c) / den (peak_den)
+//   bounds   ub = max_i norm3(c_i) / den; lb = (min_i dot3(c_i, d) / norm3(d)) / den with d = c_0 + .. + c_n per axis, left to right, where norm3(d) > 0 and the
+//            minimum is positive, else 0 (the derivative lies in the net's hull and |x| >= x . d / |d|); h0, h5 = norm3(c_0) / den, norm3(c_n) / den, attained at sa, sb
+//   class    ABOVE: OUT ub < level | IN lb >= level | MIXED; BELOW: OUT lb > level | IN ub <= level | MIXED.  With sigma = -1 (ABOVE) / +1 (BELOW), g = sigma * value and
+//            L = sigma * level, "within" is g <= L: a leaf carries sigma * h0 / sigma * h5 and WinChain::add takes L as the siblings' dist
+//   search   ONE per slot over the whole flight.  Seeds: every segment at [0, 1]: IN to the leaves, MIXED to the live set (never truncated: the lists have room for S).
+//            Round: a live window whose time width <= tol becomes an EDGE leaf, every other is halved and both children are evaluated.  Stop: live empty | max_depth |
+//            after a round more than max_windows live or more than S + max_windows leaves (TRUNCATED: the lists of the last completed round).  What is live at the
+//            end joins the leaves as EDGE leaves.
+//   merge    the slot's leaves by flight position tr + sa (exact in a double: 9 + 40 bits); adjacent iff prev.gb == next.ga; a row per maximal chain
+//
+// An evaluation costs a few dozen flops where the siblings walk a BVH per evaluation, so the WINDOWS are spread over the lanes: every lane halves its own live window
+// and evaluates both children in registers.  TWO launches whatever the fleet, the gates and the depth (a count-only call, cap == 0, ends after the first):
+//   k_dynwin_refine  grid (owned x n_gates), ONE wave per block, which dispatches on its gate's quantity to a body templated on the degree (the branch is the block's).
+//                    Seeds and the live windows of a round are strided over the lanes; appends go to the slot's ping-pong live lists and its kept list in global
+//                    memory through LDS integer counters (k_prox_refine's way: the order of the appends vanishes in the rank sort, and a truncated round is dropped
+//                    whole).  Behind the rounds win_sort into the live lists' room, which is free then, and the slot's row count (the interior heads + 1 where it
+//                    has a leaf), work, depth and truncation bit; ONE integer atomicAdd of the row count into n_rows.
+//   k_dynwin_place   one wave per slot: win_rows_before over the slots before it gives its first row; blocks of 64 leaves through win_head / win_row_index; the lane
+//                    of a head folds its chain left to right (WinChain) and writes the row at its final place.  Rows beyond the caller's capacity are counted only.
+// The trip counts of the round loop and of the loop over live windows are read from LDS behind a barrier, never taken from a lane's own arithmetic; every loop is
+// bounded by max_depth <= 40 and the list capacities.  No float atomics, no polling, no workgroup waits on another, nothing of the iteration's scratch, no tj_stats
+// counter, no launch count.  Read-only: the kernels write the query's own buffers only.
+#pragma once
+#include "kernels_peak_dynamics.h"
+
+namespace tj {
+
+static_assert(sizeof(tj_dyn_gate) == 16 && sizeof(tj_dynwin_row) == 96, "the records' layout (include/trajadmm.h)");
+
+constexpr int DW_THREADS = 64;   // one wave per slot
+
+// a live window (MIXED) or a kept one (IN, or an EDGE leaf): [sa, sb] of segment tr; ga / gb = tr + sa / tr + sb, the position on the flight (the sort's and the chain's
+// keys); g0 / g5 = sigma * the value attained at sa / sb
+struct DynLeaf { double sa, sb, ga, gb, g0, g5; int tr, in; };
+
+struct DynwinArgs {
+  const double* net;        // [U][3][T]
+  const double* pt;         // [U]
+  const tj_dyn_gate* gates; // [n_gates], the levels resolved
+  double tol;
+  int max_depth, max_windows, n_gates;
+  int row_cap;              // the caller's rows
+  DynLeaf* list;            // [slots][2][S + max_windows] ping-pong live lists; behind the rounds the slot's leaves by flight position
+  DynLeaf* leaf;            // [slots][S + 2 * max_windows] the kept list, in the order of the appends
+  int* info;                // [slots][4] leaves, work, depth (+ 1 << 16: truncated), rows
+  int* n_rows;              // [1]
+};
+
+__device__ __forceinline__ size_t dynwin_live_cap(int S, int maxw) { return (size_t)S + maxw; }
+__device__ __forceinline__ size_t dynwin_leaf_cap(int S, int maxw) { return (size_t)S + 2 * (size_t)maxw; }
+__device__ __forceinline__ double dynwin_time(const Dev& D, double ptu, double g) { return (g / (double)D.res) * ptu; }   // ((tr + s) / res) * piece_time: the siblings' expression
+
+// ONE evaluation, in a lane's registers: the class of [sa, sb] of segment tr against the gate, and the window with its attained ends
+template <int DEG>
+__device__ __forceinline__ int dynwin_eval(const Dev& D, const double* __restrict__ nu, double ptu, int tr, double sa, double sb, int sense, double level, DynLeaf& w) {
+  double o[3][DEG + 1];
+  peak_net<DEG>(D, nu, tr, sa, sb, o);
+  const double den = peak_den<DEG>(seg_weight(D, tr), ptu);
+  double ub = -INFINITY, v0 = 0.0, vn = 0.0;
+#pragma unroll
+  for (int i = 0; i <= DEG; i++) {
+    const double v = norm3(o[0][i], o[1][i], o[2][i]) / den;
+    ub = fmax(ub, v);
+    if (i == 0) v0 = v;
+    if (i == DEG) vn = v;
+  }
+  double d[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    d[k] = o[k][0];
+#pragma unroll
+    for (int i = 1; i <= DEG; i++) d[k] = d[k] + o[k][i];
+  }
+  const double nd = norm3(d[0], d[1], d[2]);
+  double m = INFINITY;
+#pragma unroll
+  for (int i = 0; i <= DEG; i++) m = fmin(m, o[0][i] * d[0] + o[1][i] * d[1] + o[2][i] * d[2]);
+  const double lb = nd > 0.0 && m > 0.0 ? (m / nd) / den : 0.0;
+  int cls;
+  if (sense == TJ_DYNWIN_ABOVE) cls = ub < level ? WIN_OUT : (lb >= level ? WIN_IN : WIN_MIXED);
+  else cls = lb > level ? WIN_OUT : (ub <= level ? WIN_IN : WIN_MIXED);
+  const double sigma = sense == TJ_DYNWIN_ABOVE ? -1.0 : 1.0;
+  w = DynLeaf{sa, sb, (double)tr + sa, (double)tr + sb, sigma * v0, sigma * vn, tr, cls == WIN_IN ? 1 : 0};
+  return cls;
+}
+
+// the appends of one evaluated window: IN to the kept list, MIXED to the next live list (a counter goes on past its list: that is how a round is found truncated)
+__device__ __forceinline__ void dynwin_put(int cls, const DynLeaf& w, DynLeaf* leaf, int& s_leaf, int leaf_room, DynLeaf* nxt, int& s_next, int live_room) {
+  if (cls == WIN_IN) { const int at = atomicAdd(&s_leaf, 1); if (at < leaf_room) leaf[at] = w; }
+  if (cls == WIN_MIXED) { const int at = atomicAdd(&s_next, 1); if (at < live_room) nxt[at] = w; }
+}
+
+// the seed, ALL rounds, the sort and the slot's counts by one wave (the workgroup); s_*: the workgroup's LDS counters
+template <int DEG>
+__device__ void dynwin_search(const Dev& D, const DynwinArgs& A, size_t slot, int u, int sense, double level, int& s_leaf, int& s_next, int& s_work) {
+  const int lane = lane_id(), S = D.S, maxw = A.max_windows;
+  const double* nu = A.net + (size_t)u * 3 * D.T;
+  const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
+  const size_t lc = dynwin_live_cap(S, maxw);
+  const int kept_room = S + maxw;   // the kept leaves of a completed round
+  DynLeaf* cur = A.list + slot * 2 * lc;
+  DynLeaf* nxt = cur + lc;
+  DynLeaf* leaf = A.leaf + slot * dynwin_leaf_cap(S, maxw);
+  DynLeaf* const sorted = cur;
+
+  // ---- the seeds: every segment at [0, 1], strided over the lanes (at most S appends: both lists have room) ----
+  if (lane == 0) { s_leaf = 0; s_next = 0; s_work = S; }
+  __syncthreads();
+  for (int tr = lane; tr < S; tr += DW_THREADS) {
+    DynLeaf w;
+    const int cls = dynwin_eval<DEG>(D, nu, ptu, tr, 0.0, 1.0, sense, level, w);
+    dynwin_put(cls, w, leaf, s_leaf, S, cur, s_next, S);
+  }
+  __syncthreads();
+  int kept = s_leaf, n = s_next, depth = 0;   // (LDS words behind a barrier: the same in every lane)
+  bool truncated = false;
+
+  // ---- the rounds: every lane halves its own live windows ----
+  while (n > 0 && depth < A.max_depth) {
+    __syncthreads();   // everyone has read the counters before lane 0 writes them
+    if (lane == 0) s_next = 0;   // (s_leaf goes on from the committed count)
+    __syncthreads();
+    for (int i = lane; i < n; i += DW_THREADS) {
+      const DynLeaf w = cur[i];
+      if (((w.sb - w.sa) / res) * ptu <= tol) {
+        const int at = atomicAdd(&s_leaf, 1);
+        if (at < kept_room) { DynLeaf e = w; e.in = 0; leaf[at] = e; }
+        continue;
+      }
+      atomicAdd(&s_work, 2);
+      const double sm = 0.5 * (w.sa + w.sb);
+      DynLeaf k;
+      int cls = dynwin_eval<DEG>(D, nu, ptu, w.tr, w.sa, sm, sense, level, k);
+      dynwin_put(cls, k, leaf, s_leaf, kept_room, nxt, s_next, maxw);
+      cls = dynwin_eval<DEG>(D, nu, ptu, w.tr, sm, w.sb, sense, level, k);
+      dynwin_put(cls, k, leaf, s_leaf, kept_room, nxt, s_next, maxw);
+    }
+    __syncthreads();   // the lists are written, the counters final
+    const int k2 = s_leaf, n2 = s_next;
+    if (k2 > kept_room || n2 > maxw) { truncated = true; break; }   // the committed lists stand: the appends of this round do not count
+    kept = k2; n = n2; depth++;
+    DynLeaf* t = cur; cur = nxt; nxt = t;
+  }
+
+  // ---- the live windows of the last completed round become EDGE leaves ----
+  __syncthreads();
+  for (int i = lane; i < n; i += DW_THREADS) { DynLeaf e = cur[i]; e.in = 0; leaf[kept + i] = e; }
+  const int m = kept + n;   // <= S at depth 0, <= S + 2 * max_windows behind a round
+  __syncthreads();
+
+  // ---- by flight position into the live lists' room, which is free now, and the slot's rows ----
+  const int heads = win_sort<&DynLeaf::ga, &DynLeaf::gb>(leaf, sorted, m);
+  if (lane == 0) {
+    int* info = A.info + slot * 4;
+    const int rows = m > 0 ? heads + 1 : 0;
+    info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = rows;
+    if (rows) atomicAdd(A.n_rows, rows);
+  }
+}
+
+__global__ __launch_bounds__(DW_THREADS) void k_dynwin_refine(Dev D, DynwinArgs A) {
+  const int ui = blockIdx.x / A.n_gates, k = blockIdx.x - ui * A.n_gates, u = D.u0 + ui;
+  __shared__ int s_leaf, s_next, s_work;
+  const tj_dyn_gate g = A.gates[k];   // (the gate is the block's: every branch below is taken by the whole workgroup)
+  if (g.quantity == TJ_DYNWIN_SPEED) dynwin_search<4>(D, A, blockIdx.x, u, g.sense, g.level, s_leaf, s_next, s_work);
+  else if (g.quantity == TJ_DYNWIN_ACCEL) dynwin_search<3>(D, A, blockIdx.x, u, g.sense, g.level, s_leaf, s_next, s_work);
+  else dynwin_search<2>(D, A, blockIdx.x, u, g.sense, g.level, s_leaf, s_next, s_work);
+}
+
+// what WinChain::finish states of a row (it writes a member called `closest`: sigma * closest is the row's `extreme`)
+struct DynRowFold { double t_first_lo, t_first_hi, t_last_lo, t_last_hi, within_lo, closest; int flags; };
+
+// the rows of a slot at their final place: behind the rows of the slots before it, chain after chain in time order
+__global__ __launch_bounds__(DW_THREADS) void k_dynwin_place(Dev D, DynwinArgs A, tj_dynwin_row* out) {
+  const int slot = blockIdx.x, lane = lane_id(), S = D.S;
+  const int ui = slot / A.n_gates, k = slot - ui * A.n_gates, u = D.u0 + ui;
+  int base = win_rows_before(A.info + 3, 4, slot);   // the slot's first row
+  const int* info = A.info + (size_t)slot * 4;
+  const int m = info[0], windows = info[1], depth = info[2] & 0xffff;
+  const bool trunc = (info[2] >> 16) != 0;
+  const tj_dyn_gate g = A.gates[k];
+  const double sigma = g.sense == TJ_DYNWIN_ABOVE ? -1.0 : 1.0, L = sigma * g.level;
+  const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
+  const DynLeaf* sorted = A.list + (size_t)slot * 2 * dynwin_live_cap(S, A.max_windows);
+  for (int i0 = 0; i0 < m; i0 += DW_THREADS) {
+    const int i = i0 + lane;
+    const bool head = win_head<&DynLeaf::ga, &DynLeaf::gb>(sorted, i, m, true);
+    const int r = win_row_index(head, base);
+    if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
+      WinChain ch;
+      int j = i, leaves = 0;
+      DynLeaf x;
+      for (;;) {
+        x = sorted[j];
+        ch.add(L, dynwin_time(D, ptu, x.ga), dynwin_time(D, ptu, x.gb), ((x.sb - x.sa) / res) * ptu, x.in != 0, x.g0, x.g5);
+        leaves++;
+        if (j + 1 >= m || sorted[j + 1].ga != x.gb) break;
+        j++;
+      }
+      const DynLeaf first = sorted[i];
+      DynRowFold f;
+      ch.finish(f, dynwin_time(D, ptu, first.ga), dynwin_time(D, ptu, x.gb), first.ga == 0.0, x.gb == (double)S, trunc, tol);
+      tj_dynwin_row row;
+      row.t_first_lo = f.t_first_lo; row.t_first_hi = f.t_first_hi; row.t_last_lo = f.t_last_lo; row.t_last_hi = f.t_last_hi; row.within_lo = f.within_lo;
+      row.extreme = sigma * f.closest; row.extreme_time = ch.best_t;
+      row.robot = u; row.gate = k; row.quantity = g.quantity; row.sense = g.sense;
+      row.segment_first = first.tr; row.segment_last = x.tr;
+      row.leaves = leaves; row.depth = depth; row.flags = f.flags; row.windows = windows;
+      out[r] = row;
+    }
+  }
+}
+
+}  // namespace tj

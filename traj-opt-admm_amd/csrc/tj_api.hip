@@ -38,6 +38,7 @@
 #include "kernels_obstacle_approach.h"
 #include "kernels_obstacle_windows.h"
 #include "kernels_peak_dynamics.h"
+#include "kernels_dynamics_windows.h"
 #include "kernels_pair_approach.h"
 #include "kernels_path_crossing.h"
 #include "kernels_timing_margin.h"
@@ -90,6 +91,9 @@ struct ObwinHeld { ObwinArgs sized{}; int* n_rows = nullptr; tj_obswin_row* out 
 // rows with the largest cap
 struct SightHeld { SightArgs sized{}; int* links = nullptr; double* stations = nullptr; int* n_rows = nullptr; tj_sight_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t items = 0, units = 0; int n_links = 0, n_stations = 0, cap = 0; };
 
+// what a context holds for tj_dynamics_windows (dynwin_run): the per-slot lists grow with the largest slots x (3 S + 4 max_windows) so far, the rows with the largest cap
+struct DynwinHeld { DynwinArgs sized{}; tj_dyn_gate* gates = nullptr; int* n_rows = nullptr; tj_dynwin_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t slots = 0, live = 0, leaf = 0; int cap = 0; };
+
 struct tj_ctx {
   tj_params prm;
   Dev d;
@@ -138,6 +142,7 @@ struct tj_ctx {
   ProxHeld prox;   // tj_proximity_windows
   ObwinHeld obwin; // tj_obstacle_windows
   SightHeld sight; // tj_sight_windows
+  DynwinHeld dynwin; // tj_dynamics_windows
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -716,6 +721,8 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->obwin.out_allocs) hipFree(p);
   for (void* p : c->sight.allocs) hipFree(p);
   for (void* p : c->sight.out_allocs) hipFree(p);
+  for (void* p : c->dynwin.allocs) hipFree(p);
+  for (void* p : c->dynwin.out_allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1212,7 +1219,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the twelve (the kernels: kernels_sight_windows.h, kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
+// ---- the read-only queries: one path for the thirteen (the kernels: kernels_dynamics_windows.h, kernels_sight_windows.h, kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1249,7 +1256,9 @@ const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approac
                  SEARCH_OBSWIN{"tj_obstacle_windows", "tj_group_obstacle_windows", TJ_OBSWIN_MAX_DEPTH, TJ_OBSWIN_MAX_WINDOWS, 0.0, TJ_OBSWIN_FRONTIER,
                                ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_OBSWIN_TOL_FRACTION, true},
                  SEARCH_SIGHT{"tj_sight_windows", "tj_group_sight_windows", TJ_SIGHT_MAX_DEPTH, TJ_SIGHT_MAX_WINDOWS, 0.0, TJ_SIGHT_FRONTIER,
-                              ": deeper windows cannot be halved in a double", ": the in-kernel rank sort's bound", true, TJ_SIGHT_TOL_FRACTION, true};
+                              ": deeper windows cannot be halved in a double", ": the in-kernel rank sort's bound", true, TJ_SIGHT_TOL_FRACTION, true},
+                 SEARCH_DYNWIN{"tj_dynamics_windows", "tj_group_dynamics_windows", TJ_DYNWIN_MAX_DEPTH, TJ_DYNWIN_MAX_WINDOWS, 0.0, TJ_DYNWIN_FRONTIER,
+                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound"};
 struct SearchArgs {
   double range, tol; int max_depth, max_windows;
   template <class Args> void put(Args& a) const { a.range = range; a.tol = tol; a.max_depth = max_depth; a.max_windows = max_windows; }
@@ -1300,7 +1309,7 @@ int query_finish(tj_ctx* c, const char* walk) {
   return TJ_OK;
 }
 
-// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, profile_run) ----
+// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, dynwin_run, profile_run) ----
 // the refusal of a call whose buffers would exceed its query's byte budget, up front, nothing allocated.  what: the call's sizes in its words; advice: what to lower
 int query_budget(tj_ctx* c, const std::string& what, size_t bytes, const char* budget, long long max_bytes, const char* advice) {
   if (bytes <= (size_t)max_bytes) return TJ_OK;
@@ -1713,6 +1722,67 @@ int sight_run(tj_ctx* c, const int* links, int n_links, const double* stations, 
   return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
 }
 
+// tj_dynamics_windows (kernels_dynamics_windows.h): the rows of the owned robots from the context's own state, gate after gate (nothing of another robot is read, so
+// a sharded context answers for its own and a group calls this rank after rank).  *n = the rows; min(cap, *n) of them are written.  Two launches for the rows, one
+// for the count.  gates == null with n_gates == 0: the two default gates.
+size_t dynwin_bytes(const Dev& d, size_t slots, int cap, int mw) {
+  return slots * (((size_t)3 * d.S + (size_t)4 * mw) * sizeof(DynLeaf) + 4 * sizeof(int)) + (size_t)cap * sizeof(tj_dynwin_row);
+}
+int dynwin_run(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !rows) || n_gates < 0 || (n_gates > 0 && !gates)) return TJ_ERR_INVALID;
+  const SearchSpec& spec = SEARCH_DYNWIN;
+  const std::string name = spec.name;
+  const Dev& d = c->d;
+  int r;
+  if ((r = query_nan(c, spec.name, "tol", tol))) return r;
+  for (int k = 0; k < n_gates; k++) if ((r = query_nan(c, spec.name, "a gate's level", gates[k].level))) return r;
+  if (n_gates > TJ_DYNWIN_MAX_GATES) { c->err = name + ": n_gates must be 0.." + std::to_string(TJ_DYNWIN_MAX_GATES); return TJ_ERR_INVALID; }
+  for (int k = 0; k < n_gates; k++)
+    if (gates[k].quantity < TJ_DYNWIN_SPEED || gates[k].quantity > TJ_DYNWIN_JERK || gates[k].sense < TJ_DYNWIN_ABOVE || gates[k].sense > TJ_DYNWIN_BELOW) {
+      c->err = name + ": gate " + std::to_string(k) + ": quantity must be TJ_DYNWIN_SPEED, ACCEL or JERK and sense TJ_DYNWIN_ABOVE or BELOW";
+      return TJ_ERR_INVALID;
+    }
+  SearchArgs sa;
+  if ((r = search_args(c, spec, 0.0, tol, max_depth, max_windows, sa))) return r;
+  // the default tolerance, a design condition: the time in which a vehicle at the acceleration limit changes its speed by 1 % of the speed limit
+  if (tol < 0) sa.tol = (TJ_DYNWIN_TOL_FRACTION * d.vel_limit) / d.acc_limit;
+  std::vector<tj_dyn_gate> gl(gates, gates + n_gates);
+  if (!gates) gl = {tj_dyn_gate{d.vel_limit, TJ_DYNWIN_SPEED, TJ_DYNWIN_ABOVE}, tj_dyn_gate{d.acc_limit, TJ_DYNWIN_ACCEL, TJ_DYNWIN_ABOVE}};
+  const int ng = (int)gl.size(), mw = sa.max_windows, owned = d.u1 - d.u0;
+  const size_t slots = (size_t)std::max(owned, 0) * ng;
+  if ((r = query_budget(c, name + ": " + std::to_string(owned) + " robots x " + std::to_string(ng) + " gates of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
+                        dynwin_bytes(d, slots, cap, mw), "TJ_DYNWIN_MAX_BYTES", TJ_DYNWIN_MAX_BYTES, "lower max_windows, cap or the number of gates")) ||
+      (r = query_state(c, spec.name, false, false))) return r;
+  if (slots == 0) { *n = 0; return TJ_OK; }
+  QUIESCE(c);
+  DynwinHeld& h = c->dynwin;
+  const size_t live = slots * 2 * ((size_t)d.S + mw), leaf = slots * ((size_t)d.S + 2 * (size_t)mw);
+  if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.gates, TJ_DYNWIN_MAX_GATES))) return r;
+  if (slots > h.slots || live > h.live || leaf > h.leaf) {
+    const size_t gs = std::max(slots, h.slots), gv = std::max(live, h.live), gf = std::max(leaf, h.leaf);
+    if ((r = query_grow(h.allocs, [&] { h.sized = {}; h.slots = 0; h.live = 0; h.leaf = 0; }, [&] {
+           int e;   // (the first failure, or TJ_OK)
+           (e = query_buf(c, h.sized.list, gv, &h.allocs)) || (e = query_buf(c, h.sized.leaf, gf, &h.allocs)) || (e = query_buf(c, h.sized.info, gs * 4, &h.allocs));
+           return e;
+         }))) return r;
+    h.slots = gs; h.live = gv; h.leaf = gf;
+  }
+  if (cap > h.cap) {
+    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
+    h.cap = cap;
+  }
+  DynwinArgs a = h.sized;
+  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = upload(c, h.gates, gl.data(), (size_t)ng * sizeof(tj_dyn_gate)))) return r;
+  a.gates = h.gates; a.tol = sa.tol; a.max_depth = sa.max_depth; a.max_windows = mw; a.n_gates = ng; a.row_cap = cap; a.n_rows = h.n_rows;
+  if ((r = query_clear(c, h.n_rows, 1))) return r;
+  hipLaunchKernelGGL(k_dynwin_refine, dim3((unsigned)slots), dim3(DW_THREADS), 0, c->stream, d, a);
+  if (cap > 0) hipLaunchKernelGGL(k_dynwin_place, dim3((unsigned)slots), dim3(DW_THREADS), 0, c->stream, d, a, h.out);
+  int nr = 0;
+  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, nullptr))) return r;
+  *n = nr;
+  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+}
+
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
 int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
   if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
@@ -1836,6 +1906,8 @@ int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int 
   return query_finish(c, nullptr);
 }
 int tj_dynamics_record_size(void) { return (int)sizeof(tj_dynamics_robot); }
+int tj_dynamics_windows(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n) { return dynwin_run(c, gates, n_gates, tol, max_depth, max_windows, rows, cap, n); }
+int tj_dynwin_row_size(void) { return (int)sizeof(tj_dynwin_row); }
 int tj_flight_profile(tj_ctx* c, const double* times, int n_times, tj_profile_sample* out) { return profile_run(c, times, n_times, nullptr, nullptr, out); }
 int tj_flight_profile_record_size(void) { return (int)sizeof(tj_profile_sample); }
 

@@ -773,6 +773,19 @@ int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windo
     return tj_peak_dynamics(c, tol, max_depth, max_windows, length_levels, part); });
 }
 
+// tj_dynamics_windows, rank after rank, each from its own state, without gathered nets (ownership is by contiguous robot blocks in rank order: that is the (robot,
+// gate, t_first_lo) order).  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count (group_gather).
+int tj_group_dynamics_windows(tj_group* g, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n) {
+  if (!n) return TJ_ERR_INVALID;
+  int total; bool unknown;
+  const int rc = group_gather(g, false, rows, cap, total, unknown, [&](tj_ctx* c, const double*, const double*, tj_dynwin_row* out, int room, int* nr) {
+    return dynwin_run(c, gates, n_gates, tol, max_depth, max_windows, out, room, nr); });
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_dynamics_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 // the owners' rows [n_times] per robot; control points and piece_time from the owners, so every rank places the whole fleet as one context would
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out) {
   if (!g || !times || !out || n_times < 1) return TJ_ERR_INVALID;

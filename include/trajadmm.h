@@ -1107,6 +1107,117 @@ typedef struct tj_dynwin_row {
 } tj_dynwin_row;
 int tj_dynamics_windows(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n);
 int tj_dynwin_row_size(void);   /* sizeof(tj_dynwin_row) */
+/* ---- tj_zone_windows: FROM WHEN TO WHEN is every robot's flown curve inside (or outside) a volume the CALLER names at query time, as certified time intervals
+ * (csrc/kernels_zone_windows.h; read-only like tj_dynamics_windows).  The window queries answer against the obstacle set (tj_obstacle_windows, tj_sight_windows), the
+ * other robots (tj_proximity_windows) and the robot's own dynamics (tj_dynamics_windows): all fixed by the scene or the state.  A geofence the fleet must stay inside,
+ * a no-fly box, an altitude band, the coverage ball of a ground station or a charging pad, a camera's work volume are none of these: they are no obstacles, never
+ * enter the BVH or the optimiser, and change per question.  Sampling tj_flight_profile and testing points certifies nothing between the samples.  Nothing of another
+ * robot is read: all three modes, single-UAV included.
+ *   shapes   a table shapes[n_shapes][4] of doubles; a zone names rows first .. first + count - 1 of it.
+ *   zone     TJ_ZONE_PLANES: the convex polytope that intersects the `count` half-spaces n_j . x <= d_j, a row is (nx, ny, nz, d), 1 <= count <=
+ *            TJ_ZONEWIN_MAX_PLANES (an axis-aligned box is 6 rows, an altitude band 2, a one-sided fence 1).  Gauge g(x) = max_j (dot3(n_j, x) - d_j), faces left to
+ *            right, dot3(n, x) = (n.x * x.x + n.y * x.y) + n.z * x.z; face(x) = the smallest j attaining it.  The library does NOT normalise: with unit normals g is
+ *            metres, the signed distance inside the zone and next to a face, and a LOWER bound of the distance beyond an edge or a corner.
+ *            TJ_ZONE_BALL: count == 1, the row is (cx, cy, cz, r).  Gauge g(x) = norm3(x - c) - r, the signed distance; face = -1.
+ *   sense    TJ_ZONE_INSIDE: within means g <= level.  TJ_ZONE_OUTSIDE: within means g >= level.
+ *   level    0 is the zone itself; -m with INSIDE is "inside with margin m"; -offset with OUTSIDE is "outside the fence, or within offset of it".
+ * For every OWNED robot u and every zone k ONE search over the whole flight, tj_dynamics_windows' search word for word:
+ *   window   W = (segment tr, [sa, sb] in [0, 1] of the segment's local parameter), dyadic; the real time of parameter s of segment tr is ((tr + s) / res) *
+ *            piece_time[u], used wherever a time is formed.
+ *   net      b_0..b_5 = the segment's raw 6-point hull (hull_entry's sums) restricted to W by bez_restrict, always from the RAW hull: [0, 1] returns it bit for bit.
+ *   PLANES   f_ij = dot3(n_j, b_i) - d_j.  lb = max_j min_i f_ij, ub = max_j max_i f_ij; g0 = max_j f_0j and g5 = max_j f_5j, each with its face (the smallest j):
+ *            attained at sa and sb.  Every f_j is affine, so on the hull it lies between its extremes over the net; a maximum of affine functions is then bounded by
+ *            the maxima on both sides: lb <= g on W <= ub, and both tend to g as the window shrinks.
+ *   BALL     e_i = b_i - c.  ub = max_i norm3(e_i) - r.  With d = e_0 + .. + e_5 per axis, left to right, lb = (min_i dot3(e_i, d) / norm3(d)) - r where norm3(d) > 0
+ *            and the minimum is positive, else 0 - r: tj_dynamics_windows' projection bound on e (|x| >= x . d / |d| on the hull).  g0 = norm3(e_0) - r, g5 =
+ *            norm3(e_5) - r.
+ *   class    INSIDE: OUT if lb > level, IN if ub <= level, else MIXED.  OUTSIDE: OUT if ub < level, IN if lb >= level, else MIXED.  With sigma = +1 (INSIDE) / -1
+ *            (OUTSIDE) a leaf carries sigma * g0 and sigma * g5 and the merge takes sigma * level as tj_obstacle_windows' dist (negation is exact): tj_dynamics_windows'
+ *            BELOW / ABOVE.  "within" is sigma * g <= sigma * level for both senses, and the smallest sigma * g is the extreme sample.
+ *   search   seeds: every segment at [0, 1]: IN to the leaves, MIXED to the live set, OUT dropped; seeding is never truncated.  Round d = 1, 2, ..: a live window whose
+ *            time width ((sb - sa) / res) * piece_time[u] <= tol becomes an EDGE leaf with its g0 and g5; every other is halved at 0.5 * (sa + sb) and both children are
+ *            evaluated from the raw hull.  Stop: the live set is empty | d == max_depth | after a round the live set holds more than max_windows or the leaves more
+ *            than S + max_windows (TRUNCATED: the lists of the last completed round stand, `windows` counts the overflowing round's work too).  What is live at the
+ *            end joins the leaves as EDGE leaves.
+ *   merge    the leaves by flight position tr + sa; two consecutive leaves are adjacent exactly when prev.tr + prev.sb == next.tr + next.sa on doubles; a row is a
+ *            maximal chain.
+ *   row      brackets, sure times, within_lo and flags by tj_obstacle_windows' rules word for word (a sure time: every time of an IN leaf; of an EDGE leaf sa if g0 is
+ *            within the level and sb if g5 is).  extreme, extreme_time, face = INSIDE the smallest, OUTSIDE the largest attained end sample of the gauge over the
+ *            chain, its time and its face (equal values: the earlier time, then the smaller face) -- not converged.  robot, zone (the index in `zones`), sense;
+ *            segment_first, segment_last, leaves, depth, windows as tj_dynamics_windows'.
+ *   flags    CERTAIN or UNCERTAIN, AT_START, AT_END, RESOLVED, TRUNCATED: tj_obstacle_windows' meanings.
+ * Every field is a function of the state and the arguments alone.  Rows are sorted by (robot, zone, t_first_lo).  Outside every row of a zone the robot is certified on
+ * the other side of the level, up to the stated limits.
+ * n_zones <= TJ_ZONEWIN_MAX_ZONES; n_zones == 0 gives 0 rows: there is no default zone.  tol < 0: (TJ_ZONEWIN_TOL_FRACTION * offset) / vel_limit -- a design
+ * condition, stated as such: the time to fly 1 % of the contact distance at the speed limit, tj_obstacle_windows' at its default dist; 0 is valid.  max_depth < 0:
+ * TJ_ZONEWIN_MAX_DEPTH; above it TJ_ERR_INVALID.  max_windows <= 0: TJ_ZONEWIN_FRONTIER; above TJ_ZONEWIN_MAX_WINDOWS (it bounds the in-kernel rank sort)
+ * TJ_ERR_INVALID.  *n = the rows.  *n > cap: TJ_ERR_CAPACITY with the exact *n, the first `cap` rows in order have been written.  cap == 0 with rows == NULL is the
+ * count-only call (one launch).  TJ_ERR_INVALID with the outputs untouched: n == NULL, cap < 0, rows == NULL with cap > 0, n_zones < 0 or n_shapes < 0, zones == NULL
+ * with n_zones > 0, shapes == NULL with n_shapes > 0; a NaN tol, a non-finite level or shape value; n_zones above the limit, a kind or a sense
+ * out of range, first / count outside the table or count outside the kind's range, an all-zero normal, r < 0, max_depth, max_windows; a call before tj_init_state
+ * (precedence: null, NaN / non-finite, limits, no state).  A plain SHARDED context (world > 1) answers for its owned robots.  tj_group_zone_windows returns the owners'
+ * rows one after the other, bitwise one context's.
+ * DEVICE MEMORY is allocated by the first call that needs it, grows only, is freed by tj_destroy, and is a function of owned x n_zones x (S, max_windows):
+ *   owned * n_zones * ((3 * S + 4 * max_windows) * 56 + 16) + cap * 96 bytes
+ *   (per slot the two live lists of S + max_windows windows and S + 2 * max_windows leaves, 56 bytes a window; its four counters; the rows), and the zone list and
+ *   the shape table, copied per call (at most 64 zones of 32 rows).  A call whose figure exceeds TJ_ZONEWIN_MAX_BYTES is refused up front with TJ_ERR_INVALID: lower
+ *   max_windows, cap or the number of zones.
+ * TWO launches whatever the fleet's size, the number of zones and the depth (one for the count-only call).  Changes no solver state, statistics or launch count.
+ * STATED LIMITS.  (1) ub and lb are sound up to rounding: the roundings of the blossoming, dot3, norm3, the sum and the division, a small multiple of eps = 2^-53 of the
+ * slot's scale -- the depth-0 largest |n_j| * |b_i| + |d_j| (PLANES), |e_i| + r (BALL).  The CPU test measures, against the real roots in mpmath of each face's
+ * quintic f_j(x(s)) - level and of the degree-10 |x(s) - c|^2 - (r + level)^2, the largest excess by which the truth contradicts a certified class (a within time in
+ * an OUT window or in a gap between rows, an outside time in an IN leaf): no truly-within time outside a row (0), and 0.283 eps of the slot's scale inside an IN leaf (e2e_scn_c3; 0 on the other states); the test allows the next power of two >= 16 x that, 8 eps.  (2) A gauge that EQUALS the level over an interval -- a flight at constant
+ * altitude on a band's plane, a start or a goal on a face -- is resolved only down to tol, or ends TRUNCATED.  (3) Gaps shorter than a leaf are not resolved;
+ * UNCERTAIN rows are grazes at the resolution tol.
+ * The defaults are measured (tests/zone_windows_ref.py default_tolerance, the restatement, on the CPU; tools/zone_windows_measure.py prints the tables): the default
+ * tol, max_depth = 40, the lists capped at TJ_ZONEWIN_MAX_WINDOWS only, on the final states of tests/golden/e2e_scn_a.npz, e2e_scn_b.npz, e2e_scn_c3.npz,
+ * e2e_scn_b_coupled.npz and on the same runs' iteration-0 states (_init).  The zone set is built from each state: a box over the middle third of the fleet's bounding
+ * box, the bounding box shrunk by offset (the fence), an altitude band of height 2 * offset through the mean z, a 32-face prism (30 sides around the vertical axis
+ * through the bounding box's centre at the apothem of a quarter of its horizontal diagonal, floor and ceiling the box's), a ball at the fleet's centroid with a quarter
+ * of the bounding box's diagonal as its radius; each in both senses at levels 0 and -offset: 20 zones.  Per state the sums over its zones of rows, UNCERTAIN rows and
+ * TRUNCATED rows, and the maxima of the live set after a round >= 1, the leaf list, the depth and the widest bracket of a CERTAIN row:
+ *   state                    rows   uncertain   truncated   largest live set   largest leaf list   largest depth   widest bracket
+ *   e2e_scn_a                22     4           0           4                  72                  9               3.81e-04
+ *   e2e_scn_a_init           17     0           0           2                  40                  14              3.05e-04
+ *   e2e_scn_b                154    0           0           2                  52                  11              2.81e-04
+ *   e2e_scn_b_init           157    0           0           14                 107                 14              3.05e-04
+ *   e2e_scn_c3               1256   0           0           4                  52                  11              5.61e-04
+ *   e2e_scn_c3_init          1284   6           0           73                 252                 14              3.05e-04
+ *   e2e_scn_b_coupled        154    0           0           2                  52                  11              2.81e-04
+ *   e2e_scn_b_coupled_init   157    0           0           14                 107                 14              3.05e-04
+ * A level set is crossed at isolated times, so the live set of most searches stays at a few windows per crossing; the zones are built from the state's own bounding
+ * box, so the topmost robot of an initial state flies at constant altitude ON the prism's ceiling (stated limit (2): e2e_scn_c3_init's robot 63 at z = 18.27, the
+ * live set of 73 and the 6 UNCERTAIN rows; no other search of that state holds more than 4 windows).  TJ_ZONEWIN_FRONTIER is the next
+ * power of two >= 4 x the largest live set (73), and at least 64: 512. */
+#define TJ_ZONE_PLANES 0    /* the intersection of `count` half-spaces n_j . x <= d_j */
+#define TJ_ZONE_BALL   1    /* |x - c| <= r */
+#define TJ_ZONE_INSIDE  0   /* within = gauge <= level */
+#define TJ_ZONE_OUTSIDE 1   /* within = gauge >= level */
+#define TJ_ZONEWIN_CERTAIN   1    /* a sure time exists: the robot IS within the level at t_first_hi and at t_last_lo */
+#define TJ_ZONEWIN_UNCERTAIN 2    /* no sure time: t_first_hi == t_last_lo == -1.0, a graze at the resolution tol */
+#define TJ_ZONEWIN_AT_START  4    /* the chain starts at time 0: nothing lies before it */
+#define TJ_ZONEWIN_AT_END    8    /* the chain ends at the end of the robot's flight */
+#define TJ_ZONEWIN_RESOLVED  16   /* CERTAIN and both brackets are at most tol wide (a side closed by AT_START / AT_END counts as resolved) */
+#define TJ_ZONEWIN_TRUNCATED 32   /* the search of this robot and zone outgrew its lists: the leaves of the last completed round are returned */
+#define TJ_ZONEWIN_MAX_ZONES 64
+#define TJ_ZONEWIN_MAX_PLANES 32
+#define TJ_ZONEWIN_MAX_DEPTH 40
+#define TJ_ZONEWIN_FRONTIER  512
+#define TJ_ZONEWIN_MAX_WINDOWS 1024
+#define TJ_ZONEWIN_MAX_BYTES (1ll << 31)
+#define TJ_ZONEWIN_TOL_FRACTION 0.01
+typedef struct tj_zone { double level; int kind, sense, first, count; } tj_zone;   /* TJ_ZONE_PLANES | BALL, TJ_ZONE_INSIDE | OUTSIDE, rows first .. first + count - 1 of the shape table */
+typedef struct tj_zonewin_row {
+  double t_first_lo, t_first_hi;   /* the robot first comes within the level in [t_first_lo, t_first_hi] */
+  double t_last_lo,  t_last_hi;    /* ... and is last within it in [t_last_lo, t_last_hi] */
+  double within_lo;                /* seconds CERTIFIED within the level inside the row (sum of the IN leaves) */
+  double extreme, extreme_time;    /* INSIDE: the smallest attained end sample of the gauge (deepest), OUTSIDE: the largest; not converged */
+  int robot, zone, sense, face;    /* face: of the extreme sample; -1 for a ball */
+  int segment_first, segment_last; /* the segments of the chain's ends */
+  int leaves, depth, flags, windows;
+} tj_zonewin_row;
+int tj_zone_windows(tj_ctx* c, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n);
+int tj_zonewin_row_size(void);   /* sizeof(tj_zonewin_row) */
 /* ---- tj_flight_profile: where every robot is at the flight times the caller names, how fast it moves there, how far the NEAREST obstacle primitive is --
  * with no `range`, however far -- and how far the nearest other robot is at the same time (csrc/kernels_flight_profile.h; read-only like tj_audit).  The other
  * queries answer with one minimum per robot or pair, and only inside `range`; this one is the curve against time: what a plot of clearance and speed, a look
@@ -1316,6 +1427,7 @@ int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_dept
 int tj_group_sight_windows(tj_group* g, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows, tj_sight_row* rows, int cap, int* n);   /* tj_sight_windows of every link by the rank that owns its robot a, nets and piece_time from the owners: (link, t_first_lo) order, bitwise one context's */
 int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windows, int length_levels, tj_dynamics_robot* records);   /* tj_peak_dynamics of every robot by its owner, from the owner's own state: bitwise one context's */
 int tj_group_dynamics_windows(tj_group* g, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n);   /* tj_dynamics_windows of every robot by its owner, from the owner's own state, the ranks' rows one after the other: (robot, gate, t_first_lo) order, bitwise one context's */
+int tj_group_zone_windows(tj_group* g, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n);   /* tj_zone_windows of every robot by its owner, from the owner's own state, the ranks' rows one after the other: (robot, zone, t_first_lo) order, bitwise one context's */
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out);   /* tj_flight_profile of every robot by its owner; control points and piece_time from the owners: bitwise one context's */
 const char* tj_group_transport(tj_group* g);          /* "flag", "event" or "rccl" */
 int tj_group_set_transport(tj_group* g, const char* name);   /* between batches; restarts the exchange sequence numbers */

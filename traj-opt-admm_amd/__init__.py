@@ -43,6 +43,7 @@ EXPORTS = [
     "tj_flight_profile", "tj_flight_profile_record_size", "tj_group_flight_profile",
     "tj_peak_dynamics", "tj_dynamics_record_size", "tj_group_peak_dynamics",
     "tj_dynamics_windows", "tj_dynwin_row_size", "tj_group_dynamics_windows",
+    "tj_zone_windows", "tj_zonewin_row_size", "tj_group_zone_windows",
 ]
 
 STAGES = dict(begin=0, planes_obs=1, planes_self=2, grad=3, xsolve=4, ccd_prep=5, ccd_obs=6, ccd_self=7, linesearch=8, slack=9, end=10)
@@ -325,6 +326,72 @@ def _dynamics_windows(call, gates, tol, max_depth, max_windows):
     gl = None if gates is None else dynwin_gates(gates)
     arr = None if gl is None else (TjDynGate * max(len(gl), 1))(*[TjDynGate(level, q, s) for q, s, level in gl])
     return _listed_rows(TjDynwinRow, call, (arr, C.c_int(0 if gl is None else len(gl))) + _search_args(None, tol, max_depth, max_windows)[1:])
+
+
+class TjZone(C.Structure):
+    """mirror of tj_zone (include/trajadmm.h)"""
+    _fields_ = [("level", C.c_double), ("kind", C.c_int), ("sense", C.c_int), ("first", C.c_int), ("count", C.c_int)]
+
+
+class TjZonewinRow(C.Structure):
+    """mirror of tj_zonewin_row (include/trajadmm.h); tj_zonewin_row_size() is its sizeof on the C side"""
+    _fields_ = [("t_first_lo", C.c_double), ("t_first_hi", C.c_double), ("t_last_lo", C.c_double), ("t_last_hi", C.c_double), ("within_lo", C.c_double),
+                ("extreme", C.c_double), ("extreme_time", C.c_double), ("robot", C.c_int), ("zone", C.c_int), ("sense", C.c_int), ("face", C.c_int),
+                ("segment_first", C.c_int), ("segment_last", C.c_int), ("leaves", C.c_int), ("depth", C.c_int), ("flags", C.c_int), ("windows", C.c_int)]
+
+
+ZONEWIN_FLAGS = dict(certain=1, uncertain=2, at_start=4, at_end=8, resolved=16, truncated=32)
+ZONE_KINDS = dict(planes=0, ball=1)        # TJ_ZONE_PLANES (half-spaces n . x <= d), TJ_ZONE_BALL (|x - c| <= r)
+ZONE_SENSES = dict(inside=0, outside=1)    # TJ_ZONE_INSIDE (within = gauge <= level), TJ_ZONE_OUTSIDE (within = gauge >= level)
+ZONEWIN_TOL_FRACTION = 0.01   # TJ_ZONEWIN_TOL_FRACTION: tol=None selects this fraction of offset over vel_limit, a time
+ZONEWIN_MAX_ZONES = 64        # TJ_ZONEWIN_MAX_ZONES
+ZONEWIN_MAX_PLANES = 32       # TJ_ZONEWIN_MAX_PLANES
+ZONEWIN_MAX_DEPTH = 40        # TJ_ZONEWIN_MAX_DEPTH
+ZONEWIN_FRONTIER = 512        # TJ_ZONEWIN_FRONTIER: what max_windows=None selects
+ZONEWIN_MAX_WINDOWS = 1024    # TJ_ZONEWIN_MAX_WINDOWS
+
+
+def zone_planes(rows, sense="inside", level=0.0):
+    """the convex polytope of the half-spaces n . x <= d: rows [count][4] of (nx, ny, nz, d), not normalised by the library -> a zone (kind, sense, level, rows)"""
+    rows = np.array(rows, dtype=np.float64).reshape(-1, 4)
+    return ZONE_KINDS["planes"], ZONE_SENSES[sense] if isinstance(sense, str) else int(sense), float(level), rows
+
+
+def zone_box(lo, hi, sense="inside", level=0.0):
+    """the axis-aligned box lo <= x <= hi: 6 unit faces in the order -x, +x, -y, +y, -z, +z"""
+    rows = []
+    for a in range(3):
+        n = [0.0, 0.0, 0.0]
+        n[a] = -1.0
+        rows.append(n + [-float(lo[a])])
+        n = [0.0, 0.0, 0.0]
+        n[a] = 1.0
+        rows.append(n + [float(hi[a])])
+    return zone_planes(rows, sense, level)
+
+
+def zone_ball(center, r, sense="inside", level=0.0):
+    """the ball |x - center| <= r"""
+    return ZONE_KINDS["ball"], ZONE_SENSES[sense] if isinstance(sense, str) else int(sense), float(level), np.array([[center[0], center[1], center[2], r]], dtype=np.float64)
+
+
+def zonewin_pack(zones):
+    """zones as zone_planes / zone_box / zone_ball return them -> (a ctypes array of TjZone, the shape table [n_shapes][4] as a C-contiguous numpy array): every
+    zone's rows one after the other, `first` the offset of its first"""
+    arr = (TjZone * max(len(zones), 1))()
+    table, first = [], 0
+    for k, (kind, sense, level, rows) in enumerate(zones):
+        arr[k] = TjZone(float(level), int(kind), int(sense), first, len(rows))
+        table.append(np.asarray(rows, dtype=np.float64).reshape(-1, 4))
+        first += len(rows)
+    return arr, np.ascontiguousarray(np.concatenate(table) if table else np.zeros((0, 4)))
+
+
+def _zone_windows(call, zones, tol, max_depth, max_windows):
+    """shared by Solver.zone_windows / Group.zone_windows: call(zones, n_zones, shapes, n_shapes, tol, max_depth, max_windows, rows, cap, n)"""
+    arr, table = zonewin_pack(list(zones))
+    return _listed_rows(TjZonewinRow, call, (arr, C.c_int(len(zones)), table.ctypes.data_as(C.POINTER(C.c_double)) if len(table) else None, C.c_int(len(table))) +
+                        _search_args(None, tol, max_depth, max_windows)[1:])
 
 
 class TjProfileSample(C.Structure):
@@ -1055,6 +1122,16 @@ class Solver:
         arrays [n] in (robot, gate, t_first_lo) order.  Read-only.  All modes; a sharded solver (world > 1) answers for its owned robots."""
         return _dynamics_windows(lambda *a: self._check(self.lib.tj_dynamics_windows(self._ctx, *a)), gates, tol, max_depth, max_windows)
 
+    def zone_windows(self, zones, tol=None, max_depth=None, max_windows=None):
+        """tj_zone_windows: per (owned robot, zone) the certified time intervals of the flight in which the flown curve is inside (or outside) a volume named here.
+        zones: a list of zone_box(lo, hi) / zone_ball(center, r) / zone_planes(rows), each with sense="inside" | "outside" and a level (0: the zone itself, -m
+        inside: with margin m).  A row: brackets `t_first_lo` <= first time within <= `t_first_hi` and `t_last_lo` <= last <= `t_last_hi` (-1 without a sure time),
+        resolved to `tol` seconds (None: ZONEWIN_TOL_FRACTION * offset / vel_limit); `within_lo` seconds certified within, `extreme` / `extreme_time` / `face` the
+        smallest (inside) or largest (outside) attained end sample of the gauge, its time and face (-1 for a ball), `robot`, `zone`, `sense`, `segment_first`,
+        `segment_last`, `leaves`, `depth`, `windows`, `flags` (ZONEWIN_FLAGS).  Outside every row of a zone the robot is certified on the other side of the level.
+        Dict of numpy arrays [n] in (robot, zone, t_first_lo) order.  Read-only.  All modes; a sharded solver (world > 1) answers for its owned robots."""
+        return _zone_windows(lambda *a: self._check(self.lib.tj_zone_windows(self._ctx, *a)), zones, tol, max_depth, max_windows)
+
     def piece_times(self):
         """piece_time of every robot as this context holds it"""
         out = np.zeros(self.U)
@@ -1235,6 +1312,10 @@ class Group:
     def dynamics_windows(self, gates=None, tol=None, max_depth=None, max_windows=None):
         """tj_group_dynamics_windows: Solver.dynamics_windows of every robot from the rank that owns it, in (robot, gate, t_first_lo) order (bitwise one context's)"""
         return _dynamics_windows(lambda *a: self._check(self.lib.tj_group_dynamics_windows(self._g, *a)), gates, tol, max_depth, max_windows)
+
+    def zone_windows(self, zones, tol=None, max_depth=None, max_windows=None):
+        """tj_group_zone_windows: Solver.zone_windows of every robot from the rank that owns it, in (robot, zone, t_first_lo) order (bitwise one context's)"""
+        return _zone_windows(lambda *a: self._check(self.lib.tj_group_zone_windows(self._g, *a)), zones, tol, max_depth, max_windows)
 
     def flight_profile(self, times=None, samples=None):
         """tj_group_flight_profile: Solver.flight_profile of every robot from the rank that owns it (bitwise one context's)"""

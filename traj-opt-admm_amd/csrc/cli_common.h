@@ -324,6 +324,40 @@ inline void print_dynamics_windows(const std::vector<tj_dynwin_row>& rows) {
   std::cout << "dynwin fleet rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
 }
 
+// --zone-windows: one line per row, in the library's (robot, zone, t_first_lo) order, and the fleet's line: zones, rows, the rows with a sure time, the grazes, and the
+// seconds certified within the level summed over the rows.  The zones: every --zone-box (6 unit faces in the order -x, +x, -y, +y, -z, +z) and --zone-ball in the
+// order given, each with the sense in force where it stands (--zone-outside) and the one LEVEL.
+struct ZoneList {
+  std::vector<tj_zone> zones; std::vector<double> shapes; int sense = TJ_ZONE_INSIDE;
+  void box(const double* v) {
+    zones.push_back(tj_zone{0.0, TJ_ZONE_PLANES, sense, (int)shapes.size() / 4, 6});
+    for (int a = 0; a < 3; a++)
+      for (int side = 0; side < 2; side++) {
+        double row[4] = {0.0, 0.0, 0.0, side ? v[3 + a] : -v[a]};
+        row[a] = side ? 1.0 : -1.0;
+        shapes.insert(shapes.end(), row, row + 4);
+      }
+  }
+  void ball(const double* v) {
+    zones.push_back(tj_zone{0.0, TJ_ZONE_BALL, sense, (int)shapes.size() / 4, 1});
+    shapes.insert(shapes.end(), v, v + 4);
+  }
+};
+inline void print_zone_windows(const std::vector<tj_zonewin_row>& rows, int n_zones) {
+  std::cout.precision(17);
+  int certain = 0, uncertain = 0;
+  double within = 0.0;
+  for (const tj_zonewin_row& r : rows) {
+    std::cout << "zonewin uav " << r.robot << " zone " << r.zone << " sense " << r.sense << " face " << r.face << " first " << r.t_first_lo << " " << r.t_first_hi << " last " << r.t_last_lo << " "
+              << r.t_last_hi << " within " << r.within_lo << " extreme " << r.extreme << " time " << r.extreme_time << " seg " << r.segment_first << " " << r.segment_last << " leaves " << r.leaves
+              << " depth " << r.depth << " windows " << r.windows << " flags " << r.flags << std::endl;
+    certain += r.flags & TJ_ZONEWIN_CERTAIN ? 1 : 0;
+    uncertain += r.flags & TJ_ZONEWIN_UNCERTAIN ? 1 : 0;
+    within += r.within_lo;
+  }
+  std::cout << "zonewin fleet zones " << n_zones << " rows " << rows.size() << " certain " << certain << " uncertain " << uncertain << " within " << within << std::endl;
+}
+
 // --sight-windows: one line per row, in the library's (link, t_first_lo) order, and the fleet's line: links, rows, the rows with a sure time, the grazes, and the
 // seconds certified within dist summed over the rows.  The links: every directed robot pair in (a, b) order, then per robot every station of --sight-station.
 inline std::vector<int> sight_links(int U, int n_stations) {

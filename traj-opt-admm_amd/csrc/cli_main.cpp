@@ -53,8 +53,14 @@
 // speed ABOVE FRACTION * vel_limit and acceleration ABOVE FRACTION * acc_limit, FRACTION default 1 -- "dynwin uav gate quantity sense first lo hi last lo hi within
 // extreme time seg a b leaves depth windows flags" at 17 digits, and the fleet's line: rows, rows with a sure time, grazes, seconds certified over the level.
 // Works in the single-UAV main and with --gpus.
+// --zone-windows [LEVEL] with repeatable --zone-box X0 Y0 Z0 X1 Y1 Z1, --zone-ball X Y Z R and --zone-outside (applies to the zones after it): after the
+// --dynamics-windows lines one line per row from tj_zone_windows / tj_group_zone_windows -- the time intervals in which a robot is inside (or outside) each zone at
+// LEVEL (default 0, the zone itself), zones in solver units in the order given -- "zonewin uav zone sense face first lo hi last lo hi within extreme time seg a b
+// leaves depth windows flags" at 17 digits, and the fleet's line: zones, rows, rows with a sure time, grazes, seconds certified within.  Works in the single-UAV main
+// and with --gpus.
 // --gpus N / --devices a,b,.. (multi-UAV main only): the robots are sharded over N devices by the library (tj_group, trajadmm.h);
 // the trajectory is bitwise the one-device one.
+#include <cctype>
 #include <chrono>
 #include <sstream>
 #include "../../include/trajadmm.h"
@@ -67,7 +73,7 @@ static const bool kMulti = false;
 #endif
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--sight-windows [DIST]] [--sight-station X Y Z].. [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--dynamics-windows [FRACTION]] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
+  if (argc < 2) { std::cerr << "Syntax: " << argv[0] << " <mesh file> [--max-iter N] [--batch N] [--dump-state FILE] [--sample-traj FILE] [--triangles] [--audit [RANGE]] [--audit-timed [LEVELS]] [--closest-approach [TOL]] [--obstacle-approach [TOL]] [--obstacle-windows [DIST]] [--sight-windows [DIST]] [--sight-station X Y Z].. [--pair-approach [TOL]] [--path-crossings [TOL]] [--timing-margin [TOL]] [--proximity-windows [DIST]] [--flight-profile K [FILE]] [--peak-dynamics [TOL]] [--dynamics-windows [FRACTION]] [--zone-windows [LEVEL]] [--zone-box X0 Y0 Z0 X1 Y1 Z1].. [--zone-ball X Y Z R].. [--zone-outside] [--gpus N | --devices a,b,..]" << std::endl; return -1; }
   const std::string mesh = argv[1];
   long max_iter = 1000000; int batch = 8; std::string dump, sample_file; bool triangles = false;
   bool audit = false; double audit_range = 0;
@@ -83,6 +89,7 @@ int main(int argc, char** argv) {
   int profile_samples = 0; std::string profile_file;
   bool dynamics = false; double dynamics_tol = -1;
   bool dynwin = false; double dynwin_fraction = 1;
+  bool zonewin = false; double zonewin_level = 0; tjcli::ZoneList zone_list;   // (zones in solver units)
   std::vector<int> devices;   // empty: one context on device 0
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -105,6 +112,10 @@ int main(int argc, char** argv) {
     else if (a == "--flight-profile" && i + 1 < argc) { profile_samples = atoi(argv[++i]); if (i + 1 < argc && argv[i + 1][0] != '-') profile_file = argv[++i]; if (profile_samples < 1) { std::cerr << "--flight-profile needs K >= 1" << std::endl; return -1; } }
     else if (a == "--peak-dynamics") { dynamics = true; if (i + 1 < argc && argv[i + 1][0] != '-') dynamics_tol = atof(argv[++i]); }
     else if (a == "--dynamics-windows") { dynwin = true; if (i + 1 < argc && argv[i + 1][0] != '-') dynwin_fraction = atof(argv[++i]); }
+    else if (a == "--zone-windows") { zonewin = true; if (i + 1 < argc && (argv[i + 1][0] != '-' || isdigit((unsigned char)argv[i + 1][1]) || argv[i + 1][1] == '.')) zonewin_level = atof(argv[++i]); }
+    else if (a == "--zone-box" && i + 6 < argc) { double v[6]; for (int k = 0; k < 6; k++) v[k] = atof(argv[++i]); zone_list.box(v); }
+    else if (a == "--zone-ball" && i + 4 < argc) { double v[4]; for (int k = 0; k < 4; k++) v[k] = atof(argv[++i]); zone_list.ball(v); }
+    else if (a == "--zone-outside") zone_list.sense = TJ_ZONE_OUTSIDE;
     else if (a == "--gpus" && i + 1 < argc) { const int n = atoi(argv[++i]); devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
     else if (a == "--devices" && i + 1 < argc) { devices.clear(); std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) devices.push_back(atoi(t.c_str())); }
     else { std::cerr << "unknown argument " << a << std::endl; return -1; }
@@ -308,6 +319,15 @@ int main(int argc, char** argv) {
       chk(tjcli::listed_rows([&](tj_dynwin_row* out, int cap, int* n) {
             return group ? tj_group_dynamics_windows(grp, gates, 2, -1.0, -1, 0, out, cap, n) : tj_dynamics_windows(ctx, gates, 2, -1.0, -1, 0, out, cap, n); }, rows), "tj_dynamics_windows");
       tjcli::print_dynamics_windows(rows);
+    }
+    if (zonewin) {
+      for (tj_zone& z : zone_list.zones) z.level = zonewin_level;
+      const int nz = (int)zone_list.zones.size(), ns = (int)zone_list.shapes.size() / 4;
+      std::vector<tj_zonewin_row> rows;
+      chk(tjcli::listed_rows([&](tj_zonewin_row* out, int cap, int* n) {
+            return group ? tj_group_zone_windows(grp, zone_list.zones.data(), nz, zone_list.shapes.data(), ns, -1.0, -1, 0, out, cap, n)
+                         : tj_zone_windows(ctx, zone_list.zones.data(), nz, zone_list.shapes.data(), ns, -1.0, -1, 0, out, cap, n); }, rows), "tj_zone_windows");
+      tjcli::print_zone_windows(rows, nz);
     }
     if (!dump.empty()) {
       std::ofstream df(dump);

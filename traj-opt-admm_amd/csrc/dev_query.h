@@ -1,4 +1,4 @@
-// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_obstacle_windows, tj_sight_windows, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_proximity_windows, tj_flight_profile, tj_peak_dynamics, tj_dynamics_windows), each piece defined once.
+// dev_query.h -- what the read-only queries on the held state share (tj_audit, tj_audit_timed, tj_closest_approach, tj_obstacle_approach, tj_obstacle_windows, tj_sight_windows, tj_pair_approach, tj_path_crossings, tj_timing_margin, tj_proximity_windows, tj_flight_profile, tj_peak_dynamics, tj_dynamics_windows, tj_zone_windows), each piece defined once.
 //
 // Every query works per (owned robot, segment) on the segment's 6-point hull (hull_entry's sums: the bits of the hull cache) and its box, and reduces per-lane candidates
 // with a TOTAL order, so that a result is a function of the state alone: no float atomics, no dependence on the order of evaluation.
@@ -9,8 +9,9 @@
 //   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
 //   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
 //   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the five branch-and-bound queries, and their four common flag bits
-//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain   THE MERGE HALF of the four window queries (tj_proximity_windows, tj_obstacle_windows, tj_sight_windows, tj_dynamics_windows): the classes and
+//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain   THE MERGE HALF of the five window queries (tj_proximity_windows, tj_obstacle_windows, tj_sight_windows, tj_dynamics_windows, tj_zone_windows): the classes and
 //                  the six flag bits, the leaves' rank sort with the interior chain heads, a head's row index, and the fold of a chain into a row's common fields and flags
+//   win_lane_search, win_put, win_live_cap, win_leaf_cap   THE LANE-PER-WINDOW SEARCH of tj_dynamics_windows and tj_zone_windows: one search per slot by one wave, a template on the evaluation
 #pragma once
 #include <limits.h>
 #include "../../include/trajadmm.h"
@@ -269,7 +270,7 @@ __device__ __forceinline__ int bnb_flags(bool found, double hi, double lo, doubl
   return (found && hi <= offset ? BNB_CONTACT : 0) | (lo > offset ? BNB_CLEAR : 0) | (hi - lo <= tol || (n == 0 && !truncated) ? BNB_CONVERGED : 0) | (truncated ? BNB_TRUNCATED : 0);
 }
 
-// ---- the merge half of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h, kernels_dynamics_windows.h): all classify windows against a level, keep leaves, sort them, merge adjacent
+// ---- the merge half of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h, kernels_dynamics_windows.h, kernels_zone_windows.h): all classify windows against a level, keep leaves, sort them, merge adjacent
 // leaves into chains and write a row per chain.  How a window is evaluated, the round loop, what a leaf's times are and where a chain goes on stay with each query. ----
 constexpr int WIN_OUT = 0, WIN_IN = 1, WIN_MIXED = 2;   // a window's class against the level
 constexpr int WIN_CERTAIN = 1, WIN_UNCERTAIN = 2, WIN_AT_START = 4, WIN_AT_END = 8, WIN_RESOLVED = 16, WIN_TRUNCATED = 32;   // a row's flag bits (the two headers' values agree)
@@ -278,6 +279,7 @@ static_assert(TJ_PROXIMITY_AT_START == WIN_AT_START && TJ_OBSWIN_AT_START == WIN
 static_assert(TJ_PROXIMITY_RESOLVED == WIN_RESOLVED && TJ_OBSWIN_RESOLVED == WIN_RESOLVED && TJ_PROXIMITY_TRUNCATED == WIN_TRUNCATED && TJ_OBSWIN_TRUNCATED == WIN_TRUNCATED, "RESOLVED, TRUNCATED");
 static_assert(TJ_SIGHT_CERTAIN == WIN_CERTAIN && TJ_SIGHT_UNCERTAIN == WIN_UNCERTAIN && TJ_SIGHT_AT_START == WIN_AT_START && TJ_SIGHT_AT_END == WIN_AT_END && TJ_SIGHT_RESOLVED == WIN_RESOLVED && TJ_SIGHT_TRUNCATED == WIN_TRUNCATED, "tj_sight_windows' flags");
 static_assert(TJ_DYNWIN_CERTAIN == WIN_CERTAIN && TJ_DYNWIN_UNCERTAIN == WIN_UNCERTAIN && TJ_DYNWIN_AT_START == WIN_AT_START && TJ_DYNWIN_AT_END == WIN_AT_END && TJ_DYNWIN_RESOLVED == WIN_RESOLVED && TJ_DYNWIN_TRUNCATED == WIN_TRUNCATED, "tj_dynamics_windows' flags");
+static_assert(TJ_ZONEWIN_CERTAIN == WIN_CERTAIN && TJ_ZONEWIN_UNCERTAIN == WIN_UNCERTAIN && TJ_ZONEWIN_AT_START == WIN_AT_START && TJ_ZONEWIN_AT_END == WIN_AT_END && TJ_ZONEWIN_RESOLVED == WIN_RESOLVED && TJ_ZONEWIN_TRUNCATED == WIN_TRUNCATED, "tj_zone_windows' flags");
 
 // is leaf i of m sorted leaves a chain head: it does not begin (member A) where the leaf before it ends (member B).  first: what the caller knows of leaf 0
 template <auto A, auto B, class Leaf>
@@ -336,5 +338,88 @@ struct WinChain {
     row.flags = flags;
   }
 };
+
+// ---- THE LANE-PER-WINDOW SEARCH of the queries whose evaluation is a few dozen flops (kernels_dynamics_windows.h, kernels_zone_windows.h): one search per slot over the
+// whole flight by one wave, the windows spread over the lanes.  A query states its evaluation, its leaf and where its slot's lists are; the seeds, the rounds, the bounded
+// appends through LDS counters, a truncated round dropped whole, the EDGE leaves, the sort and the info record are here.
+//   Leaf     sa, sb (the window of segment tr), ga, gb = tr + sa, tr + sb (the position on the flight: the sort's and the chain's keys), tr, in, and what the query adds
+//   eval     (tr, sa, sb, Leaf& w) -> WIN_OUT | WIN_IN | WIN_MIXED, and the window with its attained ends, in a lane's registers
+//   list     the slot's [2][S + max_windows] ping-pong live lists; behind the rounds the slot's leaves by flight position
+//   leaf     the slot's [S + 2 * max_windows] kept list, in the order of the appends
+//   info     the slot's [4]: leaves, work, depth (+ 1 << 16: truncated), rows; ONE integer atomicAdd of the rows into n_rows
+constexpr int WIN_LANES = 64;   // one wave per slot
+__device__ __forceinline__ size_t win_live_cap(int S, int maxw) { return (size_t)S + maxw; }
+__device__ __forceinline__ size_t win_leaf_cap(int S, int maxw) { return (size_t)S + 2 * (size_t)maxw; }
+
+// the appends of one evaluated window: IN to the kept list, MIXED to the next live list (a counter goes on past its list: that is how a round is found truncated)
+template <class Leaf>
+__device__ __forceinline__ void win_put(int cls, const Leaf& w, Leaf* leaf, int& s_leaf, int leaf_room, Leaf* nxt, int& s_next, int live_room) {
+  if (cls == WIN_IN) { const int at = atomicAdd(&s_leaf, 1); if (at < leaf_room) leaf[at] = w; }
+  if (cls == WIN_MIXED) { const int at = atomicAdd(&s_next, 1); if (at < live_room) nxt[at] = w; }
+}
+
+// the seed, ALL rounds, the sort and the slot's counts by one wave (the workgroup); s_*: the workgroup's LDS counters
+template <class Leaf, class Eval>
+__device__ __forceinline__ void win_lane_search(int S, double res, double ptu, double tol, int max_depth, int maxw, Leaf* list, Leaf* leaf, int* info, int* n_rows,
+                                                int& s_leaf, int& s_next, int& s_work, const Eval& eval) {
+  const int lane = lane_id();
+  const int kept_room = S + maxw;   // the kept leaves of a completed round
+  Leaf* cur = list;
+  Leaf* nxt = cur + win_live_cap(S, maxw);
+  Leaf* const sorted = cur;
+
+  // ---- the seeds: every segment at [0, 1], strided over the lanes (at most S appends: both lists have room) ----
+  if (lane == 0) { s_leaf = 0; s_next = 0; s_work = S; }
+  __syncthreads();
+  for (int tr = lane; tr < S; tr += WIN_LANES) {
+    Leaf w;
+    const int cls = eval(tr, 0.0, 1.0, w);
+    win_put(cls, w, leaf, s_leaf, S, cur, s_next, S);
+  }
+  __syncthreads();
+  int kept = s_leaf, n = s_next, depth = 0;   // (LDS words behind a barrier: the same in every lane)
+  bool truncated = false;
+
+  // ---- the rounds: every lane halves its own live windows ----
+  while (n > 0 && depth < max_depth) {
+    __syncthreads();   // everyone has read the counters before lane 0 writes them
+    if (lane == 0) s_next = 0;   // (s_leaf goes on from the committed count)
+    __syncthreads();
+    for (int i = lane; i < n; i += WIN_LANES) {
+      const Leaf w = cur[i];
+      if (((w.sb - w.sa) / res) * ptu <= tol) {
+        const int at = atomicAdd(&s_leaf, 1);
+        if (at < kept_room) { Leaf e = w; e.in = 0; leaf[at] = e; }
+        continue;
+      }
+      atomicAdd(&s_work, 2);
+      const double sm = 0.5 * (w.sa + w.sb);
+      Leaf k;
+      int cls = eval(w.tr, w.sa, sm, k);
+      win_put(cls, k, leaf, s_leaf, kept_room, nxt, s_next, maxw);
+      cls = eval(w.tr, sm, w.sb, k);
+      win_put(cls, k, leaf, s_leaf, kept_room, nxt, s_next, maxw);
+    }
+    __syncthreads();   // the lists are written, the counters final
+    const int k2 = s_leaf, n2 = s_next;
+    if (k2 > kept_room || n2 > maxw) { truncated = true; break; }   // the committed lists stand: the appends of this round do not count
+    kept = k2; n = n2; depth++;
+    Leaf* t = cur; cur = nxt; nxt = t;
+  }
+
+  // ---- the live windows of the last completed round become EDGE leaves ----
+  __syncthreads();
+  for (int i = lane; i < n; i += WIN_LANES) { Leaf e = cur[i]; e.in = 0; leaf[kept + i] = e; }
+  const int m = kept + n;   // <= S at depth 0, <= S + 2 * max_windows behind a round
+  __syncthreads();
+
+  // ---- by flight position into the live lists' room, which is free now, and the slot's rows ----
+  const int heads = win_sort<&Leaf::ga, &Leaf::gb>(leaf, sorted, m);
+  if (lane == 0) {
+    const int rows = m > 0 ? heads + 1 : 0;
+    info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = rows;
+    if (rows) atomicAdd(n_rows, rows);
+  }
+}
 
 }  // namespace tj

@@ -3,7 +3,8 @@
 // tj_peak_dynamics names one peak per robot and quantity; a state that is not yet inside its limits exceeds them over stretches, often several per flight.  This is the
 // interval counterpart, the fourth of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h): windows of a segment's parameter are
 // classified against a level and only what is not certified on the far side is kept.  The derivative nets and their blossoming are kernels_peak_dynamics.h's, unchanged
-// (peak_raw, peak_den, peak_net, bez_restrict_n); the merge half is dev_query.h's (WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain).  The definition
+// (peak_raw, peak_den, peak_net, bez_restrict_n); the search loop and the merge half are dev_query.h's (win_lane_search; WIN_*, win_sort, win_head, win_rows_before,
+// win_row_index, WinChain).  The definition
 // (include/trajadmm.h), per slot = (owned robot u, gate k) with the gate's quantity (degree n = 4, 3, 2), sense and level:
 //   net      c_0..c_n = the raw derivative net of segment tr restricted to [sa, sb] (always from the RAW net); a vector counts as norm3(c) / den (peak_den)
 //   bounds   ub = max_i norm3(c_i) / den; lb = (min_i dot3(c_i, d) / norm3(d)) / den with d = c_0 + .. + c_n per axis, left to right, where norm3(d) > 0 and the
@@ -35,7 +36,7 @@ namespace tj {
 
 static_assert(sizeof(tj_dyn_gate) == 16 && sizeof(tj_dynwin_row) == 96, "the records' layout (include/trajadmm.h)");
 
-constexpr int DW_THREADS = 64;   // one wave per slot
+constexpr int DW_THREADS = WIN_LANES;   // one wave per slot
 
 // a live window (MIXED) or a kept one (IN, or an EDGE leaf): [sa, sb] of segment tr; ga / gb = tr + sa / tr + sb, the position on the flight (the sort's and the chain's
 // keys); g0 / g5 = sigma * the value attained at sa / sb
@@ -54,8 +55,6 @@ struct DynwinArgs {
   int* n_rows;              // [1]
 };
 
-__device__ __forceinline__ size_t dynwin_live_cap(int S, int maxw) { return (size_t)S + maxw; }
-__device__ __forceinline__ size_t dynwin_leaf_cap(int S, int maxw) { return (size_t)S + 2 * (size_t)maxw; }
 __device__ __forceinline__ double dynwin_time(const Dev& D, double ptu, double g) { return (g / (double)D.res) * ptu; }   // ((tr + s) / res) * piece_time: the siblings' expression
 
 // ONE evaluation, in a lane's registers: the class of [sa, sb] of segment tr against the gate, and the window with its attained ends
@@ -92,78 +91,15 @@ __device__ __forceinline__ int dynwin_eval(const Dev& D, const double* __restric
   return cls;
 }
 
-// the appends of one evaluated window: IN to the kept list, MIXED to the next live list (a counter goes on past its list: that is how a round is found truncated)
-__device__ __forceinline__ void dynwin_put(int cls, const DynLeaf& w, DynLeaf* leaf, int& s_leaf, int leaf_room, DynLeaf* nxt, int& s_next, int live_room) {
-  if (cls == WIN_IN) { const int at = atomicAdd(&s_leaf, 1); if (at < leaf_room) leaf[at] = w; }
-  if (cls == WIN_MIXED) { const int at = atomicAdd(&s_next, 1); if (at < live_room) nxt[at] = w; }
-}
-
-// the seed, ALL rounds, the sort and the slot's counts by one wave (the workgroup); s_*: the workgroup's LDS counters
+// the seed, ALL rounds, the sort and the slot's counts by one wave (the workgroup): dev_query.h's win_lane_search with dynwin_eval as its evaluation; s_*: the
+// workgroup's LDS counters
 template <int DEG>
 __device__ void dynwin_search(const Dev& D, const DynwinArgs& A, size_t slot, int u, int sense, double level, int& s_leaf, int& s_next, int& s_work) {
-  const int lane = lane_id(), S = D.S, maxw = A.max_windows;
+  const int S = D.S, maxw = A.max_windows;
   const double* nu = A.net + (size_t)u * 3 * D.T;
-  const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
-  const size_t lc = dynwin_live_cap(S, maxw);
-  const int kept_room = S + maxw;   // the kept leaves of a completed round
-  DynLeaf* cur = A.list + slot * 2 * lc;
-  DynLeaf* nxt = cur + lc;
-  DynLeaf* leaf = A.leaf + slot * dynwin_leaf_cap(S, maxw);
-  DynLeaf* const sorted = cur;
-
-  // ---- the seeds: every segment at [0, 1], strided over the lanes (at most S appends: both lists have room) ----
-  if (lane == 0) { s_leaf = 0; s_next = 0; s_work = S; }
-  __syncthreads();
-  for (int tr = lane; tr < S; tr += DW_THREADS) {
-    DynLeaf w;
-    const int cls = dynwin_eval<DEG>(D, nu, ptu, tr, 0.0, 1.0, sense, level, w);
-    dynwin_put(cls, w, leaf, s_leaf, S, cur, s_next, S);
-  }
-  __syncthreads();
-  int kept = s_leaf, n = s_next, depth = 0;   // (LDS words behind a barrier: the same in every lane)
-  bool truncated = false;
-
-  // ---- the rounds: every lane halves its own live windows ----
-  while (n > 0 && depth < A.max_depth) {
-    __syncthreads();   // everyone has read the counters before lane 0 writes them
-    if (lane == 0) s_next = 0;   // (s_leaf goes on from the committed count)
-    __syncthreads();
-    for (int i = lane; i < n; i += DW_THREADS) {
-      const DynLeaf w = cur[i];
-      if (((w.sb - w.sa) / res) * ptu <= tol) {
-        const int at = atomicAdd(&s_leaf, 1);
-        if (at < kept_room) { DynLeaf e = w; e.in = 0; leaf[at] = e; }
-        continue;
-      }
-      atomicAdd(&s_work, 2);
-      const double sm = 0.5 * (w.sa + w.sb);
-      DynLeaf k;
-      int cls = dynwin_eval<DEG>(D, nu, ptu, w.tr, w.sa, sm, sense, level, k);
-      dynwin_put(cls, k, leaf, s_leaf, kept_room, nxt, s_next, maxw);
-      cls = dynwin_eval<DEG>(D, nu, ptu, w.tr, sm, w.sb, sense, level, k);
-      dynwin_put(cls, k, leaf, s_leaf, kept_room, nxt, s_next, maxw);
-    }
-    __syncthreads();   // the lists are written, the counters final
-    const int k2 = s_leaf, n2 = s_next;
-    if (k2 > kept_room || n2 > maxw) { truncated = true; break; }   // the committed lists stand: the appends of this round do not count
-    kept = k2; n = n2; depth++;
-    DynLeaf* t = cur; cur = nxt; nxt = t;
-  }
-
-  // ---- the live windows of the last completed round become EDGE leaves ----
-  __syncthreads();
-  for (int i = lane; i < n; i += DW_THREADS) { DynLeaf e = cur[i]; e.in = 0; leaf[kept + i] = e; }
-  const int m = kept + n;   // <= S at depth 0, <= S + 2 * max_windows behind a round
-  __syncthreads();
-
-  // ---- by flight position into the live lists' room, which is free now, and the slot's rows ----
-  const int heads = win_sort<&DynLeaf::ga, &DynLeaf::gb>(leaf, sorted, m);
-  if (lane == 0) {
-    int* info = A.info + slot * 4;
-    const int rows = m > 0 ? heads + 1 : 0;
-    info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = rows;
-    if (rows) atomicAdd(A.n_rows, rows);
-  }
+  const double ptu = A.pt[u];
+  win_lane_search(S, (double)D.res, ptu, A.tol, A.max_depth, maxw, A.list + slot * 2 * win_live_cap(S, maxw), A.leaf + slot * win_leaf_cap(S, maxw), A.info + slot * 4, A.n_rows,
+                  s_leaf, s_next, s_work, [&](int tr, double sa, double sb, DynLeaf& w) { return dynwin_eval<DEG>(D, nu, ptu, tr, sa, sb, sense, level, w); });
 }
 
 __global__ __launch_bounds__(DW_THREADS) void k_dynwin_refine(Dev D, DynwinArgs A) {
@@ -189,7 +125,7 @@ __global__ __launch_bounds__(DW_THREADS) void k_dynwin_place(Dev D, DynwinArgs A
   const tj_dyn_gate g = A.gates[k];
   const double sigma = g.sense == TJ_DYNWIN_ABOVE ? -1.0 : 1.0, L = sigma * g.level;
   const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
-  const DynLeaf* sorted = A.list + (size_t)slot * 2 * dynwin_live_cap(S, A.max_windows);
+  const DynLeaf* sorted = A.list + (size_t)slot * 2 * win_live_cap(S, A.max_windows);
   for (int i0 = 0; i0 < m; i0 += DW_THREADS) {
     const int i = i0 + lane;
     const bool head = win_head<&DynLeaf::ga, &DynLeaf::gb>(sorted, i, m, true);

@@ -39,6 +39,7 @@
 #include "kernels_obstacle_windows.h"
 #include "kernels_peak_dynamics.h"
 #include "kernels_dynamics_windows.h"
+#include "kernels_zone_windows.h"
 #include "kernels_pair_approach.h"
 #include "kernels_path_crossing.h"
 #include "kernels_timing_margin.h"
@@ -94,6 +95,10 @@ struct SightHeld { SightArgs sized{}; int* links = nullptr; double* stations = n
 // what a context holds for tj_dynamics_windows (dynwin_run): the per-slot lists grow with the largest slots x (3 S + 4 max_windows) so far, the rows with the largest cap
 struct DynwinHeld { DynwinArgs sized{}; tj_dyn_gate* gates = nullptr; int* n_rows = nullptr; tj_dynwin_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t slots = 0, live = 0, leaf = 0; int cap = 0; };
 
+// what a context holds for tj_zone_windows (zonewin_run): the per-slot lists grow with the largest slots x (3 S + 4 max_windows) so far, the rows with the largest cap; the
+// zone list and the shape table have their largest size from the start
+struct ZonewinHeld { ZonewinArgs sized{}; tj_zone* zones = nullptr; double* shapes = nullptr; int* n_rows = nullptr; tj_zonewin_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t slots = 0, live = 0, leaf = 0; int cap = 0; };
+
 struct tj_ctx {
   tj_params prm;
   Dev d;
@@ -143,6 +148,7 @@ struct tj_ctx {
   ObwinHeld obwin; // tj_obstacle_windows
   SightHeld sight; // tj_sight_windows
   DynwinHeld dynwin; // tj_dynamics_windows
+  ZonewinHeld zonewin; // tj_zone_windows
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -723,6 +729,8 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->sight.out_allocs) hipFree(p);
   for (void* p : c->dynwin.allocs) hipFree(p);
   for (void* p : c->dynwin.out_allocs) hipFree(p);
+  for (void* p : c->zonewin.allocs) hipFree(p);
+  for (void* p : c->zonewin.out_allocs) hipFree(p);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1219,7 +1227,7 @@ int tj_get_energy(tj_ctx* c, double* energy) {
 }  // extern "C"
 
 namespace {
-// ---- the read-only queries: one path for the thirteen (the kernels: kernels_dynamics_windows.h, kernels_sight_windows.h, kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
+// ---- the read-only queries: one path for the fourteen (the kernels: kernels_zone_windows.h, kernels_dynamics_windows.h, kernels_sight_windows.h, kernels_audit.h, kernels_audit_timed.h, kernels_closest.h, kernels_obstacle_approach.h, kernels_obstacle_windows.h, kernels_pair_approach.h, kernels_path_crossing.h, kernels_timing_margin.h, kernels_proximity.h, kernels_flight_profile.h, kernels_peak_dynamics.h) ----
 // The `*_run` functions serve the public call and the group's (tj_group.h).  net_host [U][3][T] / pt_host [U]: every robot's control points / piece_time as a group read them from
 // the owners, or null = the context's own.  Argument checks in one precedence: null -> NaN -> limits -> no state -> sharded.
 int query_nan(tj_ctx* c, const char* name, const char* what, double v) {
@@ -1258,7 +1266,9 @@ const SearchSpec SEARCH_CLOSEST{"tj_closest_approach", "tj_group_closest_approac
                  SEARCH_SIGHT{"tj_sight_windows", "tj_group_sight_windows", TJ_SIGHT_MAX_DEPTH, TJ_SIGHT_MAX_WINDOWS, 0.0, TJ_SIGHT_FRONTIER,
                               ": deeper windows cannot be halved in a double", ": the in-kernel rank sort's bound", true, TJ_SIGHT_TOL_FRACTION, true},
                  SEARCH_DYNWIN{"tj_dynamics_windows", "tj_group_dynamics_windows", TJ_DYNWIN_MAX_DEPTH, TJ_DYNWIN_MAX_WINDOWS, 0.0, TJ_DYNWIN_FRONTIER,
-                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound"};
+                               ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound"},
+                 SEARCH_ZONEWIN{"tj_zone_windows", "tj_group_zone_windows", TJ_ZONEWIN_MAX_DEPTH, TJ_ZONEWIN_MAX_WINDOWS, 0.0, TJ_ZONEWIN_FRONTIER,
+                                ": deeper windows are not dyadic in a double", ": the in-kernel rank sort's bound", true, TJ_ZONEWIN_TOL_FRACTION};
 struct SearchArgs {
   double range, tol; int max_depth, max_windows;
   template <class Args> void put(Args& a) const { a.range = range; a.tol = tol; a.max_depth = max_depth; a.max_windows = max_windows; }
@@ -1309,7 +1319,7 @@ int query_finish(tj_ctx* c, const char* walk) {
   return TJ_OK;
 }
 
-// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, dynwin_run, profile_run) ----
+// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, dynwin_run, zonewin_run, profile_run) ----
 // the refusal of a call whose buffers would exceed its query's byte budget, up front, nothing allocated.  what: the call's sizes in its words; advice: what to lower
 int query_budget(tj_ctx* c, const std::string& what, size_t bytes, const char* budget, long long max_bytes, const char* advice) {
   if (bytes <= (size_t)max_bytes) return TJ_OK;
@@ -1783,6 +1793,75 @@ int dynwin_run(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int
   return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
 }
 
+// tj_zone_windows (kernels_zone_windows.h): the rows of the owned robots from the context's own state, zone after zone (nothing of another robot is read, so a
+// sharded context answers for its own and a group calls this rank after rank).  *n = the rows; min(cap, *n) of them are written.  Two launches for the rows, one
+// for the count.  The zone list and the shape rows the zones name are copied per call.
+size_t zonewin_bytes(const Dev& d, size_t slots, int cap, int mw) {
+  return slots * (((size_t)3 * d.S + (size_t)4 * mw) * sizeof(ZoneLeaf) + 4 * sizeof(int)) + (size_t)cap * sizeof(tj_zonewin_row);
+}
+int zonewin_run(tj_ctx* c, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !rows) || n_zones < 0 || n_shapes < 0 || (n_zones > 0 && !zones) || (n_shapes > 0 && !shapes)) return TJ_ERR_INVALID;
+  const SearchSpec& spec = SEARCH_ZONEWIN;
+  const std::string name = spec.name;
+  const Dev& d = c->d;
+  int r;
+  if ((r = query_nan(c, spec.name, "tol", tol))) return r;
+  for (int k = 0; k < n_zones; k++) if (!std::isfinite(zones[k].level)) { c->err = name + ": zone " + std::to_string(k) + ": the level is NaN or infinite"; return TJ_ERR_INVALID; }
+  for (size_t e = 0; e < (size_t)4 * n_shapes; e++) if (!std::isfinite(shapes[e])) { c->err = name + ": row " + std::to_string(e / 4) + " of the shape table holds a NaN or an infinite value"; return TJ_ERR_INVALID; }
+  if (n_zones > TJ_ZONEWIN_MAX_ZONES) { c->err = name + ": n_zones must be 0.." + std::to_string(TJ_ZONEWIN_MAX_ZONES); return TJ_ERR_INVALID; }
+  std::vector<tj_zone> zl(zones, zones + n_zones);      // the zones with `first` pointing into the packed rows
+  std::vector<double> packed;                           // the rows the zones name, zone after zone: at most 64 x 32
+  for (int k = 0; k < n_zones; k++) {
+    const tj_zone& z = zones[k];
+    const std::string zk = name + ": zone " + std::to_string(k) + ": ";
+    if (z.kind < TJ_ZONE_PLANES || z.kind > TJ_ZONE_BALL || z.sense < TJ_ZONE_INSIDE || z.sense > TJ_ZONE_OUTSIDE) { c->err = zk + "kind must be TJ_ZONE_PLANES or BALL and sense TJ_ZONE_INSIDE or OUTSIDE"; return TJ_ERR_INVALID; }
+    if (z.count < 1 || z.count > (z.kind == TJ_ZONE_BALL ? 1 : TJ_ZONEWIN_MAX_PLANES)) { c->err = zk + "count must be 1.." + std::to_string(TJ_ZONEWIN_MAX_PLANES) + " for planes and 1 for a ball"; return TJ_ERR_INVALID; }
+    if (z.first < 0 || z.first > n_shapes - z.count) { c->err = zk + "rows first .. first + count - 1 must lie inside the shape table of " + std::to_string(n_shapes) + " rows"; return TJ_ERR_INVALID; }
+    for (int j = 0; j < z.count; j++) {
+      const double* row = shapes + (size_t)4 * (z.first + j);
+      if (z.kind == TJ_ZONE_PLANES && row[0] == 0.0 && row[1] == 0.0 && row[2] == 0.0) { c->err = zk + "face " + std::to_string(j) + " has an all-zero normal"; return TJ_ERR_INVALID; }
+      if (z.kind == TJ_ZONE_BALL && row[3] < 0.0) { c->err = zk + "the radius r must be >= 0"; return TJ_ERR_INVALID; }
+    }
+    zl[k].first = (int)(packed.size() / 4);
+    packed.insert(packed.end(), shapes + (size_t)4 * z.first, shapes + (size_t)4 * (z.first + z.count));
+  }
+  SearchArgs sa;
+  if ((r = search_args(c, spec, 0.0, tol, max_depth, max_windows, sa))) return r;   // (the default tolerance: TJ_ZONEWIN_TOL_FRACTION of offset over vel_limit, a design condition)
+  const int nz = n_zones, mw = sa.max_windows, owned = d.u1 - d.u0;
+  const size_t slots = (size_t)std::max(owned, 0) * nz;
+  if ((r = query_budget(c, name + ": " + std::to_string(owned) + " robots x " + std::to_string(nz) + " zones of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
+                        zonewin_bytes(d, slots, cap, mw), "TJ_ZONEWIN_MAX_BYTES", TJ_ZONEWIN_MAX_BYTES, "lower max_windows, cap or the number of zones")) ||
+      (r = query_state(c, spec.name, false, false))) return r;
+  if (slots == 0) { *n = 0; return TJ_OK; }
+  QUIESCE(c);
+  ZonewinHeld& h = c->zonewin;
+  const size_t live = slots * 2 * ((size_t)d.S + mw), leaf = slots * ((size_t)d.S + 2 * (size_t)mw);
+  if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.zones, TJ_ZONEWIN_MAX_ZONES)) || (r = query_buf(c, h.shapes, (size_t)4 * TJ_ZONEWIN_MAX_ZONES * TJ_ZONEWIN_MAX_PLANES))) return r;
+  if (slots > h.slots || live > h.live || leaf > h.leaf) {
+    const size_t gs = std::max(slots, h.slots), gv = std::max(live, h.live), gf = std::max(leaf, h.leaf);
+    if ((r = query_grow(h.allocs, [&] { h.sized = {}; h.slots = 0; h.live = 0; h.leaf = 0; }, [&] {
+           int e;   // (the first failure, or TJ_OK)
+           (e = query_buf(c, h.sized.list, gv, &h.allocs)) || (e = query_buf(c, h.sized.leaf, gf, &h.allocs)) || (e = query_buf(c, h.sized.info, gs * 4, &h.allocs));
+           return e;
+         }))) return r;
+    h.slots = gs; h.live = gv; h.leaf = gf;
+  }
+  if (cap > h.cap) {
+    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
+    h.cap = cap;
+  }
+  ZonewinArgs a = h.sized;
+  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = upload(c, h.zones, zl.data(), (size_t)nz * sizeof(tj_zone))) || (r = upload(c, h.shapes, packed.data(), packed.size() * sizeof(double)))) return r;
+  a.zones = h.zones; a.shapes = h.shapes; a.tol = sa.tol; a.max_depth = sa.max_depth; a.max_windows = mw; a.n_zones = nz; a.row_cap = cap; a.n_rows = h.n_rows;
+  if ((r = query_clear(c, h.n_rows, 1))) return r;
+  hipLaunchKernelGGL(k_zonewin_refine, dim3((unsigned)slots), dim3(ZW_THREADS), 0, c->stream, d, a);
+  if (cap > 0) hipLaunchKernelGGL(k_zonewin_place, dim3((unsigned)slots), dim3(ZW_THREADS), 0, c->stream, d, a, h.out);
+  int nr = 0;
+  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, nullptr))) return r;
+  *n = nr;
+  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+}
+
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in
 int profile_run(tj_ctx* c, const double* times, int n_times, const double* net_host, const double* pt_host, tj_profile_sample* out) {
   if (!c || !times || !out || n_times < 1) return TJ_ERR_INVALID;
@@ -1908,6 +1987,8 @@ int tj_peak_dynamics(tj_ctx* c, double tol, int max_depth, int max_windows, int 
 int tj_dynamics_record_size(void) { return (int)sizeof(tj_dynamics_robot); }
 int tj_dynamics_windows(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n) { return dynwin_run(c, gates, n_gates, tol, max_depth, max_windows, rows, cap, n); }
 int tj_dynwin_row_size(void) { return (int)sizeof(tj_dynwin_row); }
+int tj_zone_windows(tj_ctx* c, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n) { return zonewin_run(c, zones, n_zones, shapes, n_shapes, tol, max_depth, max_windows, rows, cap, n); }
+int tj_zonewin_row_size(void) { return (int)sizeof(tj_zonewin_row); }
 int tj_flight_profile(tj_ctx* c, const double* times, int n_times, tj_profile_sample* out) { return profile_run(c, times, n_times, nullptr, nullptr, out); }
 int tj_flight_profile_record_size(void) { return (int)sizeof(tj_profile_sample); }
 

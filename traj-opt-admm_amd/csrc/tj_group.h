@@ -786,6 +786,18 @@ int tj_group_dynamics_windows(tj_group* g, const tj_dyn_gate* gates, int n_gates
   return TJ_OK;
 }
 
+// tj_zone_windows, rank after rank, each from its own state, without gathered nets: tj_group_dynamics_windows' way, in (robot, zone, t_first_lo) order
+int tj_group_zone_windows(tj_group* g, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n) {
+  if (!n) return TJ_ERR_INVALID;
+  int total; bool unknown;
+  const int rc = group_gather(g, false, rows, cap, total, unknown, [&](tj_ctx* c, const double*, const double*, tj_zonewin_row* out, int room, int* nr) {
+    return zonewin_run(c, zones, n_zones, shapes, n_shapes, tol, max_depth, max_windows, out, room, nr); });
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_zone_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
+  return TJ_OK;
+}
+
 // the owners' rows [n_times] per robot; control points and piece_time from the owners, so every rank places the whole fleet as one context would
 int tj_group_flight_profile(tj_group* g, const double* times, int n_times, tj_profile_sample* out) {
   if (!g || !times || !out || n_times < 1) return TJ_ERR_INVALID;

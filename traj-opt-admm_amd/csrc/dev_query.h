@@ -9,9 +9,13 @@
 //   QBest          the record of the timed and the obstacle branch and bound, ordered by (hi, segment, id, parameter): before, shuffled
 //   wave_best / wave_min / wave_sum, BnbShared   the reductions over a wave, and over a workgroup through its LDS words
 //   bnb_keep, bnb_rounds, bnb_flags   the bounded append, THE ROUND LOOP of the five branch-and-bound queries, and their four common flag bits
-//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain   THE MERGE HALF of the five window queries (tj_proximity_windows, tj_obstacle_windows, tj_sight_windows, tj_dynamics_windows, tj_zone_windows): the classes and
-//                  the six flag bits, the leaves' rank sort with the interior chain heads, a head's row index, and the fold of a chain into a row's common fields and flags
-//   win_lane_search, win_put, win_live_cap, win_leaf_cap   THE LANE-PER-WINDOW SEARCH of tj_dynamics_windows and tj_zone_windows: one search per slot by one wave, a template on the evaluation
+//   WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain, WinRowFold, win_time   THE MERGE HALF of the five window queries (tj_proximity_windows, tj_obstacle_windows, tj_sight_windows, tj_dynamics_windows, tj_zone_windows): the classes and
+//                  the six flag bits, the leaves' rank sort with the interior chain heads, a head's row index, the fold of a chain into a row's common fields and flags, and a flight position's time
+//   WinSlotArgs, win_lane_search, win_put, win_live_cap, win_leaf_cap, win_slot_place   THE SLOT QUERIES tj_dynamics_windows and tj_zone_windows: one lane-per-window search per slot by one wave, a template
+//                  on the evaluation, and the slot's rows at their final place, a template on the row writer
+//   win_wave_rounds, win_seg_first_is_head, win_seg_count, win_seg_place   THE WAVE-COOPERATIVE QUERIES tj_obstacle_windows and tj_sight_windows: the rounds of one (owner, segment) unit whose evaluation is the whole
+//                  wave's, a template on the evaluation, and the owner's row count and rows with the chains that cross segment boundaries, templates on how a key maps to position and time
+//                  (tj_proximity_windows uses the merge half only: its refine is lane-per-child with live and leaf types of its own and a seed kernel)
 #pragma once
 #include <limits.h>
 #include "../../include/trajadmm.h"
@@ -339,14 +343,27 @@ struct WinChain {
   }
 };
 
+// what WinChain::finish states of a row whose own fields are named otherwise (finish writes a member called `closest`: sigma * closest is such a row's `extreme`)
+struct WinRowFold {
+  double t_first_lo, t_first_hi, t_last_lo, t_last_hi, within_lo, closest; int flags;
+  // into a row of a slot query: the times, the flags, extreme = sigma * closest at the chain's best_t
+  template <class Row>
+  __device__ __forceinline__ void put(Row& row, double sigma, const WinChain& ch) const {
+    row.t_first_lo = t_first_lo; row.t_first_hi = t_first_hi; row.t_last_lo = t_last_lo; row.t_last_hi = t_last_hi; row.within_lo = within_lo;
+    row.extreme = sigma * closest; row.extreme_time = ch.best_t; row.flags = flags;
+  }
+};
+
+// the time of the flight position g = tr + s: ((tr + s) / res) * piece_time, every window query's expression
+__device__ __forceinline__ double win_time(double res, double ptu, double g) { return (g / res) * ptu; }
+
 // ---- THE LANE-PER-WINDOW SEARCH of the queries whose evaluation is a few dozen flops (kernels_dynamics_windows.h, kernels_zone_windows.h): one search per slot over the
 // whole flight by one wave, the windows spread over the lanes.  A query states its evaluation, its leaf and where its slot's lists are; the seeds, the rounds, the bounded
 // appends through LDS counters, a truncated round dropped whole, the EDGE leaves, the sort and the info record are here.
-//   Leaf     sa, sb (the window of segment tr), ga, gb = tr + sa, tr + sb (the position on the flight: the sort's and the chain's keys), tr, in, and what the query adds
+//   Leaf     sa, sb (the window of segment tr), ga, gb = tr + sa, tr + sb (the position on the flight: the sort's and the chain's keys), tr, in, g0, g5 (sigma * the value
+//            attained at sa, sb) and what the query adds
 //   eval     (tr, sa, sb, Leaf& w) -> WIN_OUT | WIN_IN | WIN_MIXED, and the window with its attained ends, in a lane's registers
-//   list     the slot's [2][S + max_windows] ping-pong live lists; behind the rounds the slot's leaves by flight position
-//   leaf     the slot's [S + 2 * max_windows] kept list, in the order of the appends
-//   info     the slot's [4]: leaves, work, depth (+ 1 << 16: truncated), rows; ONE integer atomicAdd of the rows into n_rows
+//   WinSlotArgs   what the kernels of a slot query are handed whatever the query; a query derives its own from it (its gates, its zones and shapes)
 constexpr int WIN_LANES = 64;   // one wave per slot
 __device__ __forceinline__ size_t win_live_cap(int S, int maxw) { return (size_t)S + maxw; }
 __device__ __forceinline__ size_t win_leaf_cap(int S, int maxw) { return (size_t)S + 2 * (size_t)maxw; }
@@ -358,10 +375,29 @@ __device__ __forceinline__ void win_put(int cls, const Leaf& w, Leaf* leaf, int&
   if (cls == WIN_MIXED) { const int at = atomicAdd(&s_next, 1); if (at < live_room) nxt[at] = w; }
 }
 
-// the seed, ALL rounds, the sort and the slot's counts by one wave (the workgroup); s_*: the workgroup's LDS counters
+// what the kernels of a slot query are handed whatever the query; slot = (owned robot, the query's k-th gate or zone), robot-major
+template <class L>
+struct WinSlotArgs {
+  using Leaf = L;
+  const double* net;        // [U][3][T]
+  const double* pt;         // [U]
+  double tol;
+  int max_depth, max_windows;
+  int row_cap;              // the caller's rows
+  Leaf* list;               // [slots][2][S + max_windows] ping-pong live lists; behind the rounds the slot's leaves by flight position
+  Leaf* leaf;               // [slots][S + 2 * max_windows] the kept list, in the order of the appends
+  int* info;                // [slots][4] leaves, work, depth (+ 1 << 16: truncated), rows; ONE integer atomicAdd of the rows into n_rows
+  int* n_rows;              // [1]
+};
+
+// the seed, ALL rounds, the sort and the slot's counts of robot u's slot by one wave (the workgroup); s_*: the workgroup's LDS counters
 template <class Leaf, class Eval>
-__device__ __forceinline__ void win_lane_search(int S, double res, double ptu, double tol, int max_depth, int maxw, Leaf* list, Leaf* leaf, int* info, int* n_rows,
-                                                int& s_leaf, int& s_next, int& s_work, const Eval& eval) {
+__device__ __forceinline__ void win_lane_search(const Dev& D, const WinSlotArgs<Leaf>& A, size_t slot, int u, int& s_leaf, int& s_next, int& s_work, const Eval& eval) {
+  const int S = D.S, maxw = A.max_windows, max_depth = A.max_depth;
+  const double res = (double)D.res, ptu = A.pt[u], tol = A.tol;
+  Leaf* const list = A.list + slot * 2 * win_live_cap(S, maxw);
+  Leaf* const leaf = A.leaf + slot * win_leaf_cap(S, maxw);
+  int* const info = A.info + slot * 4;
   const int lane = lane_id();
   const int kept_room = S + maxw;   // the kept leaves of a completed round
   Leaf* cur = list;
@@ -418,7 +454,192 @@ __device__ __forceinline__ void win_lane_search(int S, double res, double ptu, d
   if (lane == 0) {
     const int rows = m > 0 ? heads + 1 : 0;
     info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = rows;
+    if (rows) atomicAdd(A.n_rows, rows);
+  }
+}
+
+// the rows of robot u's slot at their final place: behind the rows of the slots before it, chain after chain in time order, by one wave.  L: sigma * the slot's level,
+// what WinChain::add takes as the siblings' dist.  ids(leaf, i0, i5): the two ids a leaf carries (a query without ids leaves them at WinChain::add's INT_MAX);
+// write(r, fold, chain, first, last, leaves, depth, windows): the query's own row r from the fold of the chain first..last
+template <class Leaf, class Ids, class Write>
+__device__ __forceinline__ void win_slot_place(const Dev& D, const WinSlotArgs<Leaf>& A, int slot, int u, double L, const Ids& ids, const Write& write) {
+  const int lane = lane_id(), S = D.S;
+  int base = win_rows_before(A.info + 3, 4, slot);   // the slot's first row
+  const int* info = A.info + (size_t)slot * 4;
+  const int m = info[0], windows = info[1], depth = info[2] & 0xffff;
+  const bool trunc = (info[2] >> 16) != 0;
+  const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
+  const Leaf* sorted = A.list + (size_t)slot * 2 * win_live_cap(S, A.max_windows);
+  for (int i0 = 0; i0 < m; i0 += WIN_LANES) {
+    const int i = i0 + lane;
+    const bool head = win_head<&Leaf::ga, &Leaf::gb>(sorted, i, m, true);
+    const int r = win_row_index(head, base);
+    if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
+      WinChain ch;
+      int j = i, leaves = 0;
+      Leaf x;
+      for (;;) {
+        x = sorted[j];
+        int k0 = INT_MAX, k5 = INT_MAX;
+        ids(x, k0, k5);
+        ch.add(L, win_time(res, ptu, x.ga), win_time(res, ptu, x.gb), ((x.sb - x.sa) / res) * ptu, x.in != 0, x.g0, x.g5, k0, k5);
+        leaves++;
+        if (j + 1 >= m || sorted[j + 1].ga != x.gb) break;
+        j++;
+      }
+      const Leaf first = sorted[i];
+      WinRowFold f;
+      ch.finish(f, win_time(res, ptu, first.ga), win_time(res, ptu, x.gb), first.ga == 0.0, x.gb == (double)S, trunc, tol);
+      write(r, f, ch, first, x, leaves, depth, windows);
+    }
+  }
+}
+
+// ---- THE WAVE-COOPERATIVE QUERIES, whose evaluation walks the BVH and is the whole wave's (kernels_obstacle_windows.h, kernels_sight_windows.h): one 64-thread block per
+// unit = (owner, segment) -- the owner a robot or a link -- refines the unit's windows one after the other, lane 0 alone appends, counted in LDS; then one wave per owner
+// counts and places the owner's rows, whose chains cross segment boundaries.  A query states its evaluation, its seeds, its keys and its row.
+//   Leaf     the key members A, B (the window's ends: the sort's and, within a segment, the chain's keys), h0, h5, i0, i5, in, and what the query adds
+//   list     [units][per]: the unit's ping-pong live lists of maxw each at its head; behind the rounds the segment's leaves by key A
+//   leaf     [units][per]: the kept list, in the order of the appends
+//   info     [units][4]: leaves, work, depth (+ 1 << 16: truncated), chain heads behind the first leaf
+//   owner    [owners][2]: rows, work; ONE integer atomicAdd of an owner's rows into n_rows
+//   Keys     pos(t, key): the flight position compared ACROSS a segment boundary (within a segment the raw keys are compared); time(t, key), width(t, a, b): what
+//            WinChain::add receives of a leaf of segment t
+
+// ALL ROUNDS of one unit behind its seeds, the EDGE leaves, the sort and the unit's info record, by one wave (the workgroup).  kept, n: the seeds' leaves and live windows
+// (LDS words read behind a barrier: the same in every lane); truncated: among the seeds alone, no round then.  narrow(w): the window is narrow enough to become an EDGE
+// leaf; eval(w, a, b, kid) -> the class of the child [a, b] of w, and kid.  eval contains barriers: every lane reaches every call, and the trip counts of the loop over
+// live windows and of the round loop are read from LDS behind a barrier (or loaded from one address by every lane), never taken from a lane's own arithmetic.
+template <auto A, auto B, class Leaf, class Narrow, class Eval>
+__device__ __forceinline__ void win_wave_rounds(Leaf* cur, Leaf* nxt, Leaf* leaf, int kept, int n, bool truncated, int maxw, int max_depth, int& s_leaf, int& s_next, int& s_work, int* info,
+                                                const Narrow& narrow, const Eval& eval) {
+  const int lane = lane_id();
+  Leaf* const sorted = cur;
+  int depth = 0;
+
+  // ---- the rounds ----
+  while (!truncated && n > 0 && depth < max_depth) {
+    __syncthreads();   // everyone has read the counters before lane 0 writes them
+    if (lane == 0) s_next = 0;   // (s_leaf goes on from the committed count)
+    for (int i = 0; i < n; i++) {
+      const Leaf w = cur[i];   // (one address for the wave)
+      if (narrow(w)) {
+        if (lane == 0) { const int at = s_leaf++; if (at < maxw) { Leaf e = w; e.in = 0; leaf[at] = e; } }
+        continue;
+      }
+      const double mid = 0.5 * (w.*A + w.*B);
+      for (int c = 0; c < 2; c++) {
+        Leaf kid;
+        const int cls = eval(w, c ? mid : w.*A, c ? w.*B : mid, kid);
+        if (lane == 0) {
+          s_work++;
+          if (cls == WIN_IN) { const int at = s_leaf++; if (at < maxw) leaf[at] = kid; }
+          if (cls == WIN_MIXED) { const int at = s_next++; if (at < maxw) nxt[at] = kid; }
+        }
+      }
+    }
+    __syncthreads();   // the lists are written, the counters final
+    const int k2 = s_leaf, n2 = s_next;
+    if (k2 > maxw || n2 > maxw) { truncated = true; break; }   // the committed lists stand: the appends of this round do not count
+    kept = k2; n = n2; depth++;
+    Leaf* t = cur; cur = nxt; nxt = t;
+  }
+
+  // ---- the live windows of the last completed round become EDGE leaves ----
+  __syncthreads();
+  for (int i = lane; i < n; i += WIN_LANES) { Leaf e = cur[i]; e.in = 0; leaf[kept + i] = e; }
+  const int m = kept + n;   // <= 2 * max_windows behind a round; the seeds alone: what the caller's lists hold
+  __syncthreads();
+
+  // ---- by key A into the live lists' room, which is free now, and the chain heads behind the first leaf ----
+  const int heads = win_sort<A, B>(leaf, sorted, m);
+  if (lane == 0) { info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = heads; }
+}
+
+// does the first leaf of segment tr of owner o start a chain (it does not where the last leaf of segment tr - 1 ends where it begins)
+template <auto A, auto B, class Leaf, class Keys>
+__device__ __forceinline__ bool win_seg_first_is_head(const Leaf* list, const int* info, size_t per, int S, int o, int tr, const Keys& key) {
+  if (tr == 0) return true;
+  const size_t prev = (size_t)o * S + tr - 1;
+  const int mp = info[prev * 4];
+  if (mp == 0) return true;
+  return key.pos(tr - 1, list[prev * per + mp - 1].*B) != key.pos(tr, list[(prev + 1) * per].*A);
+}
+
+// one wave per owner: the chain heads over its segments' leaves in order (a segment's first leaf continues the chain of the segment before it or starts one) = the
+// owner's row count, and its work; the counts are added up with one integer atomic per owner
+template <auto A, auto B, class Leaf, class Keys>
+__device__ __forceinline__ void win_seg_count(const Leaf* list, const int* info, size_t per, int S, int o, int* owner, int* n_rows, const Keys& key) {
+  const int lane = lane_id();
+  int rows = 0, work = 0;
+  for (int tr = lane; tr < S; tr += WIN_LANES) {
+    const int* unit = info + ((size_t)o * S + tr) * 4;
+    work += unit[1];
+    if (unit[0] > 0) rows += unit[3] + (win_seg_first_is_head<A, B>(list, info, per, S, o, tr, key) ? 1 : 0);
+  }
+  rows = wave_sum(rows); work = wave_sum(work);
+  if (lane == 0) {
+    owner[2 * o] = rows; owner[2 * o + 1] = work;
     if (rows) atomicAdd(n_rows, rows);
+  }
+}
+
+// one wave per owner: its rows at their final place, behind the rows of the owners before it, chain after chain in time order.  The chain heads of a block of 64 leaves
+// get their row index from win_row_index, and the lane of a head folds its chain left to right (WinChain), across segment boundaries, and writes the row where it
+// belongs; rows beyond row_cap are counted, not written.  pos_end: the flight's last position, as key.pos gives it.  The row's common fields and flags, closest_time
+// and index (-1 without a sample), leaves, depth and windows are set here; own(row, first segment, last segment) sets what else the query's row has.
+template <auto A, auto B, class Leaf, class Keys, class Row, class Own>
+__device__ __forceinline__ void win_seg_place(const Leaf* list, const int* info, size_t per, int S, int o, const int* owner, int row_cap, double dist, double tol, double pos_end,
+                                              const Keys& key, Row* out, const Own& own) {
+  const int lane = lane_id();
+  int base = win_rows_before(owner, 2, o);   // the owner's first row
+  const int windows = owner[2 * o + 1];
+  for (int tr = 0; tr < S; tr++) {
+    const size_t unit = (size_t)o * S + tr;
+    const int m = info[unit * 4];   // (one address for the wave)
+    if (m == 0) continue;
+    const Leaf* sorted = list + unit * per;
+    const bool first_head = win_seg_first_is_head<A, B>(list, info, per, S, o, tr, key);
+    for (int i0 = 0; i0 < m; i0 += WIN_LANES) {
+      const int i = i0 + lane;
+      const bool head = win_head<A, B>(sorted, i, m, first_head);
+      const int r = win_row_index(head, base);
+      if (head && r < row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
+        // the chain from leaf i of segment tr on, left to right, into the segments behind where it goes on
+        Row row;
+        WinChain ch;
+        double end_g = 0.0, end_t = 0.0;
+        int t = tr, k = i, mt = m, leaves = 0, dmax = 0;
+        bool trunc = false;
+        const Leaf* sl = sorted;
+        for (;;) {
+          if (k == 0 || leaves == 0) { const int dt = info[((size_t)o * S + t) * 4 + 2]; dmax = max(dmax, dt & 0xffff); trunc = trunc || (dt >> 16) != 0; }
+          const Leaf x = sl[k];
+          const double ta = key.time(t, x.*A), tb = key.time(t, x.*B);
+          ch.add(dist, ta, tb, key.width(t, x.*A, x.*B), x.in, x.h0, x.h5, x.i0, x.i5);
+          end_g = key.pos(t, x.*B); end_t = tb;
+          leaves++;
+          if (k + 1 < mt) {
+            if (sl[k + 1].*A != x.*B) break;   // (within a segment: the raw keys)
+            k++;
+          } else {
+            if (t + 1 >= S) break;
+            const int m2 = info[((size_t)o * S + t + 1) * 4];
+            if (m2 == 0) break;
+            const Leaf* s2 = list + ((size_t)o * S + t + 1) * per;
+            if (end_g != key.pos(t + 1, s2[0].*A)) break;
+            t++; k = 0; mt = m2; sl = s2;
+          }
+        }
+        const bool found = ch.best_i != INT_MAX;
+        ch.finish(row, key.time(tr, sorted[i].*A), end_t, key.pos(tr, sorted[i].*A) == 0.0, end_g == pos_end, trunc, tol);
+        row.closest_time = found ? ch.best_t : -1.0;
+        row.index = found ? ch.best_i : -1;
+        row.leaves = leaves; row.depth = dmax; row.windows = windows;
+        own(row, tr, t);
+        out[r] = row;
+      }
+    }
   }
 }
 

@@ -3,8 +3,8 @@
 // tj_peak_dynamics names one peak per robot and quantity; a state that is not yet inside its limits exceeds them over stretches, often several per flight.  This is the
 // interval counterpart, the fourth of the window queries (kernels_proximity.h, kernels_obstacle_windows.h, kernels_sight_windows.h): windows of a segment's parameter are
 // classified against a level and only what is not certified on the far side is kept.  The derivative nets and their blossoming are kernels_peak_dynamics.h's, unchanged
-// (peak_raw, peak_den, peak_net, bez_restrict_n); the search loop and the merge half are dev_query.h's (win_lane_search; WIN_*, win_sort, win_head, win_rows_before,
-// win_row_index, WinChain).  The definition
+// (peak_raw, peak_den, peak_net, bez_restrict_n); the search loop, the placing of a slot's rows and the merge half are dev_query.h's (WinSlotArgs, win_lane_search,
+// win_slot_place; WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain, WinRowFold, win_time).  This file's own: the evaluation (dynwin_eval), the gates and the row.  The definition
 // (include/trajadmm.h), per slot = (owned robot u, gate k) with the gate's quantity (degree n = 4, 3, 2), sense and level:
 //   net      c_0..c_n = the raw derivative net of segment tr restricted to [sa, sb] (always from the RAW net); a vector counts as norm3(c) / den (peak_den)
 //   bounds   ub = max_i norm3(c_i) / den; lb = (min_i dot3(c_i, d) / norm3(d)) / den with d = c_0 + .. + c_n per axis, left to right, where norm3(d) > 0 and the
@@ -24,7 +24,7 @@
 //                    memory through LDS integer counters (k_prox_refine's way: the order of the appends vanishes in the rank sort, and a truncated round is dropped
 //                    whole).  Behind the rounds win_sort into the live lists' room, which is free then, and the slot's row count (the interior heads + 1 where it
 //                    has a leaf), work, depth and truncation bit; ONE integer atomicAdd of the row count into n_rows.
-//   k_dynwin_place   one wave per slot: win_rows_before over the slots before it gives its first row; blocks of 64 leaves through win_head / win_row_index; the lane
+//   k_dynwin_place   one wave per slot (win_slot_place): win_rows_before over the slots before it gives its first row; blocks of 64 leaves through win_head / win_row_index; the lane
 //                    of a head folds its chain left to right (WinChain) and writes the row at its final place.  Rows beyond the caller's capacity are counted only.
 // The trip counts of the round loop and of the loop over live windows are read from LDS behind a barrier, never taken from a lane's own arithmetic; every loop is
 // bounded by max_depth <= 40 and the list capacities.  No float atomics, no polling, no workgroup waits on another, nothing of the iteration's scratch, no tj_stats
@@ -42,20 +42,11 @@ constexpr int DW_THREADS = WIN_LANES;   // one wave per slot
 // keys); g0 / g5 = sigma * the value attained at sa / sb
 struct DynLeaf { double sa, sb, ga, gb, g0, g5; int tr, in; };
 
-struct DynwinArgs {
-  const double* net;        // [U][3][T]
-  const double* pt;         // [U]
+// dev_query.h's WinSlotArgs and the gates
+struct DynwinArgs : WinSlotArgs<DynLeaf> {
   const tj_dyn_gate* gates; // [n_gates], the levels resolved
-  double tol;
-  int max_depth, max_windows, n_gates;
-  int row_cap;              // the caller's rows
-  DynLeaf* list;            // [slots][2][S + max_windows] ping-pong live lists; behind the rounds the slot's leaves by flight position
-  DynLeaf* leaf;            // [slots][S + 2 * max_windows] the kept list, in the order of the appends
-  int* info;                // [slots][4] leaves, work, depth (+ 1 << 16: truncated), rows
-  int* n_rows;              // [1]
+  int n_gates;
 };
-
-__device__ __forceinline__ double dynwin_time(const Dev& D, double ptu, double g) { return (g / (double)D.res) * ptu; }   // ((tr + s) / res) * piece_time: the siblings' expression
 
 // ONE evaluation, in a lane's registers: the class of [sa, sb] of segment tr against the gate, and the window with its attained ends
 template <int DEG>
@@ -91,68 +82,35 @@ __device__ __forceinline__ int dynwin_eval(const Dev& D, const double* __restric
   return cls;
 }
 
-// the seed, ALL rounds, the sort and the slot's counts by one wave (the workgroup): dev_query.h's win_lane_search with dynwin_eval as its evaluation; s_*: the
-// workgroup's LDS counters
-template <int DEG>
-__device__ void dynwin_search(const Dev& D, const DynwinArgs& A, size_t slot, int u, int sense, double level, int& s_leaf, int& s_next, int& s_work) {
-  const int S = D.S, maxw = A.max_windows;
-  const double* nu = A.net + (size_t)u * 3 * D.T;
-  const double ptu = A.pt[u];
-  win_lane_search(S, (double)D.res, ptu, A.tol, A.max_depth, maxw, A.list + slot * 2 * win_live_cap(S, maxw), A.leaf + slot * win_leaf_cap(S, maxw), A.info + slot * 4, A.n_rows,
-                  s_leaf, s_next, s_work, [&](int tr, double sa, double sb, DynLeaf& w) { return dynwin_eval<DEG>(D, nu, ptu, tr, sa, sb, sense, level, w); });
-}
-
+// the slot's search: dev_query.h's win_lane_search with dynwin_eval at the gate's degree as its evaluation
 __global__ __launch_bounds__(DW_THREADS) void k_dynwin_refine(Dev D, DynwinArgs A) {
   const int ui = blockIdx.x / A.n_gates, k = blockIdx.x - ui * A.n_gates, u = D.u0 + ui;
   __shared__ int s_leaf, s_next, s_work;
   const tj_dyn_gate g = A.gates[k];   // (the gate is the block's: every branch below is taken by the whole workgroup)
-  if (g.quantity == TJ_DYNWIN_SPEED) dynwin_search<4>(D, A, blockIdx.x, u, g.sense, g.level, s_leaf, s_next, s_work);
-  else if (g.quantity == TJ_DYNWIN_ACCEL) dynwin_search<3>(D, A, blockIdx.x, u, g.sense, g.level, s_leaf, s_next, s_work);
-  else dynwin_search<2>(D, A, blockIdx.x, u, g.sense, g.level, s_leaf, s_next, s_work);
+  const double* nu = A.net + (size_t)u * 3 * D.T;
+  const double ptu = A.pt[u];
+  const auto search = [&](auto deg) {
+    win_lane_search(D, A, blockIdx.x, u, s_leaf, s_next, s_work, [&](int tr, double sa, double sb, DynLeaf& w) { return dynwin_eval<decltype(deg)::value>(D, nu, ptu, tr, sa, sb, g.sense, g.level, w); });
+  };
+  if (g.quantity == TJ_DYNWIN_SPEED) search(std::integral_constant<int, 4>{});
+  else if (g.quantity == TJ_DYNWIN_ACCEL) search(std::integral_constant<int, 3>{});
+  else search(std::integral_constant<int, 2>{});
 }
 
-// what WinChain::finish states of a row (it writes a member called `closest`: sigma * closest is the row's `extreme`)
-struct DynRowFold { double t_first_lo, t_first_hi, t_last_lo, t_last_hi, within_lo, closest; int flags; };
-
-// the rows of a slot at their final place: behind the rows of the slots before it, chain after chain in time order
+// the rows of a slot at their final place (win_slot_place): the slot's robot and gate, and the row's own fields
 __global__ __launch_bounds__(DW_THREADS) void k_dynwin_place(Dev D, DynwinArgs A, tj_dynwin_row* out) {
-  const int slot = blockIdx.x, lane = lane_id(), S = D.S;
-  const int ui = slot / A.n_gates, k = slot - ui * A.n_gates, u = D.u0 + ui;
-  int base = win_rows_before(A.info + 3, 4, slot);   // the slot's first row
-  const int* info = A.info + (size_t)slot * 4;
-  const int m = info[0], windows = info[1], depth = info[2] & 0xffff;
-  const bool trunc = (info[2] >> 16) != 0;
+  const int slot = blockIdx.x, ui = slot / A.n_gates, k = slot - ui * A.n_gates, u = D.u0 + ui;
   const tj_dyn_gate g = A.gates[k];
-  const double sigma = g.sense == TJ_DYNWIN_ABOVE ? -1.0 : 1.0, L = sigma * g.level;
-  const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
-  const DynLeaf* sorted = A.list + (size_t)slot * 2 * win_live_cap(S, A.max_windows);
-  for (int i0 = 0; i0 < m; i0 += DW_THREADS) {
-    const int i = i0 + lane;
-    const bool head = win_head<&DynLeaf::ga, &DynLeaf::gb>(sorted, i, m, true);
-    const int r = win_row_index(head, base);
-    if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
-      WinChain ch;
-      int j = i, leaves = 0;
-      DynLeaf x;
-      for (;;) {
-        x = sorted[j];
-        ch.add(L, dynwin_time(D, ptu, x.ga), dynwin_time(D, ptu, x.gb), ((x.sb - x.sa) / res) * ptu, x.in != 0, x.g0, x.g5);
-        leaves++;
-        if (j + 1 >= m || sorted[j + 1].ga != x.gb) break;
-        j++;
-      }
-      const DynLeaf first = sorted[i];
-      DynRowFold f;
-      ch.finish(f, dynwin_time(D, ptu, first.ga), dynwin_time(D, ptu, x.gb), first.ga == 0.0, x.gb == (double)S, trunc, tol);
-      tj_dynwin_row row;
-      row.t_first_lo = f.t_first_lo; row.t_first_hi = f.t_first_hi; row.t_last_lo = f.t_last_lo; row.t_last_hi = f.t_last_hi; row.within_lo = f.within_lo;
-      row.extreme = sigma * f.closest; row.extreme_time = ch.best_t;
-      row.robot = u; row.gate = k; row.quantity = g.quantity; row.sense = g.sense;
-      row.segment_first = first.tr; row.segment_last = x.tr;
-      row.leaves = leaves; row.depth = depth; row.flags = f.flags; row.windows = windows;
-      out[r] = row;
-    }
-  }
+  const double sigma = g.sense == TJ_DYNWIN_ABOVE ? -1.0 : 1.0;
+  win_slot_place(D, A, slot, u, sigma * g.level, [](const DynLeaf&, int&, int&) {},
+                 [&](int r, const WinRowFold& f, const WinChain& ch, const DynLeaf& first, const DynLeaf& last, int leaves, int depth, int windows) {
+                   tj_dynwin_row row;
+                   f.put(row, sigma, ch);
+                   row.robot = u; row.gate = k; row.quantity = g.quantity; row.sense = g.sense;
+                   row.segment_first = first.tr; row.segment_last = last.tr;
+                   row.leaves = leaves; row.depth = depth; row.windows = windows;
+                   out[r] = row;
+                 });
 }
 
 }  // namespace tj

@@ -27,8 +27,10 @@
 //                   index from win_row_index, and the lane of a head folds its chain left to right (WinChain), across segment boundaries, and writes the row where
 //                   it belongs.  Rows beyond the caller's capacity are counted, not written.
 // THE MERGE HALF is dev_query.h's, shared with kernels_proximity.h: the classes and flag bits (WIN_*), the rank sort with the interior heads, the row indexing, the
-// chain fold with the flag rule.  This file's own: a leaf's times and width are formed from (segment, sa, sb) (obwin_time; ((sb - sa) / res) * ptu), whether a segment's
-// first leaf is a head and where a chain goes on behind a segment's last leaf (obwin_first_is_head), and the row's index, segments and closest_time = -1 without a sample.
+// chain fold with the flag rule.  THE PROTOCOL around it is dev_query.h's too, shared with kernels_sight_windows.h: the rounds behind the seed, the EDGE leaves, the sort and
+// the unit's record (win_wave_rounds), whether a segment's first leaf is a head (win_seg_first_is_head), the count (win_seg_count) and the placing with the chain walk across
+// segment boundaries, closest_time = -1 and index = -1 without a sample (win_seg_place).  This file's own: the evaluation (obwin_eval), the seed, how a leaf's (segment, sa, sb)
+// map to position, time and width (ObwinKeys), and the row's robot and segments.
 // bvh_query and walk_step contain __syncthreads(): the refine kernel is ONE wave per block, every lane reaches every call, and the trip counts of the loop over
 // live windows and of the round loop are read from LDS behind a barrier (or loaded from one address by every lane), never taken from a lane's own arithmetic.
 // Every loop is bounded by max_depth <= 40 and max_windows.  No polling, no workgroup waits on another, no cross-queue word, no float atomics, no ticket between
@@ -57,9 +59,14 @@ struct ObwinArgs {
   int* n_rows;         // [1]
 };
 
-// tr + s: the position on the flight, exact in a double (9 + 40 bits); two leaves are adjacent exactly when these agree
-__device__ __forceinline__ double obwin_pos(int tr, double s) { return (double)tr + s; }
-__device__ __forceinline__ double obwin_time(const Dev& D, double ptu, int tr, double s) { return (obwin_pos(tr, s) / (double)D.res) * ptu; }
+// how a leaf's keys (sa, sb of segment t) map to the flight: tr + s, the position, exact in a double (9 + 40 bits) -- two leaves are adjacent exactly when these agree --
+// and its time ((tr + s) / res) * piece_time; a leaf's width in time is formed from its own keys
+struct ObwinKeys {
+  double res, ptu;
+  __device__ __forceinline__ double pos(int t, double s) const { return (double)t + s; }
+  __device__ __forceinline__ double time(int t, double s) const { return win_time(res, ptu, pos(t, s)); }
+  __device__ __forceinline__ double width(int, double sa, double sb) const { return ((sb - sa) / res) * ptu; }
+};
 
 // ONE evaluation, by the whole wave: the class of [sa, sb] of segment tr, and (not OUT) the window with its h0, h5.  P: the wave's 18 doubles.
 template <int PRIM>
@@ -117,7 +124,6 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_refine(Dev D, ObwinArgs A)
   ObwinLeaf* cur = A.list + unit * 2 * maxw;
   ObwinLeaf* nxt = cur + maxw;
   ObwinLeaf* leaf = A.leaf + unit * 2 * maxw;
-  ObwinLeaf* const sorted = cur;
 
   // ---- the seed: the whole segment ----
   {
@@ -130,129 +136,23 @@ __global__ __launch_bounds__(OW_THREADS) void k_obwin_refine(Dev D, ObwinArgs A)
     }
   }
   __syncthreads();
-  int kept = s_leaf, n = s_live, depth = 0;   // (LDS words behind a barrier: the same in every lane)
-  bool truncated = false;
+  const int kept = s_leaf, n = s_live;   // (LDS words behind a barrier: the same in every lane)
 
-  // ---- the rounds ----
-  while (n > 0 && depth < A.max_depth) {
-    __syncthreads();   // everyone has read the counters before lane 0 writes them
-    if (lane == 0) s_next = 0;   // (s_leaf goes on from the committed count)
-    for (int i = 0; i < n; i++) {
-      const ObwinLeaf w = cur[i];   // (one address for the wave)
-      if (((w.sb - w.sa) / res) * ptu <= tol) {
-        if (lane == 0) { const int at = s_leaf++; if (at < maxw) { ObwinLeaf e = w; e.in = 0; leaf[at] = e; } }
-        continue;
-      }
-      const double sm = 0.5 * (w.sa + w.sb);
-      for (int c = 0; c < 2; c++) {
-        ObwinLeaf k;
-        const int cls = obwin_eval<PRIM>(D, A, net, tr, c ? sm : w.sa, c ? w.sb : sm, P, ws, k);
-        if (lane == 0) {
-          s_work++;
-          if (cls == WIN_IN) { const int at = s_leaf++; if (at < maxw) leaf[at] = k; }
-          if (cls == WIN_MIXED) { const int at = s_next++; if (at < maxw) nxt[at] = k; }
-        }
-      }
-    }
-    __syncthreads();   // the lists are written, the counters final
-    const int k2 = s_leaf, n2 = s_next;
-    if (k2 > maxw || n2 > maxw) { truncated = true; break; }   // the committed lists stand: the appends of this round do not count
-    kept = k2; n = n2; depth++;
-    ObwinLeaf* t = cur; cur = nxt; nxt = t;
-  }
-
-  // ---- the live windows of the last completed round become EDGE leaves ----
-  __syncthreads();
-  for (int i = lane; i < n; i += OW_THREADS) { ObwinLeaf e = cur[i]; e.in = 0; leaf[kept + i] = e; }
-  const int m = kept + n;   // <= 2 * max_windows
-  __syncthreads();
-
-  // ---- by sa into the live lists' room, which is free now, and the chain heads behind the first leaf ----
-  const int heads = win_sort<&ObwinLeaf::sa, &ObwinLeaf::sb>(leaf, sorted, m);
-  if (lane == 0) {
-    int* info = A.info + unit * 4;
-    info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = heads;
-  }
-}
-
-// does the first leaf of segment tr of robot slot ui start a chain (it does not where the last leaf of segment tr - 1 ends where it begins)
-__device__ __forceinline__ bool obwin_first_is_head(const ObwinArgs& A, int S, int ui, int tr) {
-  if (tr == 0) return true;
-  const size_t prev = (size_t)ui * S + tr - 1;
-  const int mp = A.info[prev * 4];
-  if (mp == 0) return true;
-  const size_t w = (size_t)2 * A.max_windows;
-  return obwin_pos(tr - 1, A.list[prev * w + mp - 1].sb) != obwin_pos(tr, A.list[(prev + 1) * w].sa);
+  // ---- the rounds, the EDGE leaves, the sort by sa and the unit's record ----
+  win_wave_rounds<&ObwinLeaf::sa, &ObwinLeaf::sb>(cur, nxt, leaf, kept, n, false, maxw, A.max_depth, s_leaf, s_next, s_work, A.info + unit * 4,
+      [&](const ObwinLeaf& w) { return ((w.sb - w.sa) / res) * ptu <= tol; },
+      [&](const ObwinLeaf&, double sa, double sb, ObwinLeaf& kid) { return obwin_eval<PRIM>(D, A, net, tr, sa, sb, P, ws, kid); });
 }
 
 __global__ __launch_bounds__(OW_THREADS) void k_obwin_count(Dev D, ObwinArgs A) {
-  const int ui = blockIdx.x, lane = lane_id(), S = D.S;
-  int rows = 0, work = 0;
-  for (int tr = lane; tr < S; tr += OW_THREADS) {
-    const int* info = A.info + ((size_t)ui * S + tr) * 4;
-    work += info[1];
-    if (info[0] > 0) rows += info[3] + (obwin_first_is_head(A, S, ui, tr) ? 1 : 0);
-  }
-  rows = wave_sum(rows); work = wave_sum(work);
-  if (lane == 0) {
-    A.robot[2 * ui] = rows; A.robot[2 * ui + 1] = work;
-    if (rows) atomicAdd(A.n_rows, rows);
-  }
+  win_seg_count<&ObwinLeaf::sa, &ObwinLeaf::sb>(A.list, A.info, (size_t)2 * A.max_windows, D.S, blockIdx.x, A.robot, A.n_rows, ObwinKeys{});
 }
 
-// the rows of robot slot ui at their final place: behind the rows of the robots before it, chain after chain in time order
+// the rows of robot slot ui at their final place (win_seg_place); the row's own: robot and the chain's segments
 __global__ __launch_bounds__(OW_THREADS) void k_obwin_place(Dev D, ObwinArgs A, tj_obswin_row* out) {
-  const int ui = blockIdx.x, lane = lane_id(), S = D.S, u = D.u0 + ui;
-  int base = win_rows_before(A.robot, 2, ui);   // the robot's first row
-  const int windows = A.robot[2 * ui + 1];
-  const double dist = A.range, tol = A.tol, ptu = A.pt[u], res = (double)D.res;
-  const size_t per = (size_t)2 * A.max_windows;
-  for (int tr = 0; tr < S; tr++) {
-    const size_t unit = (size_t)ui * S + tr;
-    const int m = A.info[unit * 4];   // (one address for the wave)
-    if (m == 0) continue;
-    const ObwinLeaf* sorted = A.list + unit * per;
-    const bool first_head = obwin_first_is_head(A, S, ui, tr);
-    for (int i0 = 0; i0 < m; i0 += OW_THREADS) {
-      const int i = i0 + lane;
-      const bool head = win_head<&ObwinLeaf::sa, &ObwinLeaf::sb>(sorted, i, m, first_head);
-      const int r = win_row_index(head, base);
-      if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
-        // the chain from leaf i of segment tr on, left to right, into the segments behind where it goes on
-        tj_obswin_row row;
-        WinChain ch;
-        double end_g = 0.0, end_t = 0.0;
-        int t = tr, k = i, mt = m, leaves = 0, dmax = 0;
-        bool trunc = false;
-        const ObwinLeaf* sl = sorted;
-        for (;;) {
-          if (k == 0 || leaves == 0) { const int dt = A.info[((size_t)ui * S + t) * 4 + 2]; dmax = max(dmax, dt & 0xffff); trunc = trunc || (dt >> 16) != 0; }
-          const ObwinLeaf x = sl[k];
-          const double ta = obwin_time(D, ptu, t, x.sa), tb = obwin_time(D, ptu, t, x.sb);
-          ch.add(dist, ta, tb, ((x.sb - x.sa) / res) * ptu, x.in, x.h0, x.h5, x.i0, x.i5);
-          end_g = obwin_pos(t, x.sb); end_t = tb;
-          leaves++;
-          if (k + 1 < mt) {
-            if (sl[k + 1].sa != x.sb) break;
-            k++;
-          } else {
-            if (t + 1 >= S) break;
-            const int m2 = A.info[((size_t)ui * S + t + 1) * 4];
-            if (m2 == 0) break;
-            const ObwinLeaf* s2 = A.list + ((size_t)ui * S + t + 1) * per;
-            if (end_g != obwin_pos(t + 1, s2[0].sa)) break;
-            t++; k = 0; mt = m2; sl = s2;
-          }
-        }
-        const bool found = ch.best_i != INT_MAX;
-        ch.finish(row, obwin_time(D, ptu, tr, sorted[i].sa), end_t, obwin_pos(tr, sorted[i].sa) == 0.0, end_g == (double)S, trunc, tol);
-        row.closest_time = found ? ch.best_t : -1.0;
-        row.robot = u; row.index = found ? ch.best_i : -1; row.segment_first = tr; row.segment_last = t;
-        row.leaves = leaves; row.depth = dmax; row.windows = windows;
-        out[r] = row;
-      }
-    }
-  }
+  const int ui = blockIdx.x, u = D.u0 + ui;
+  win_seg_place<&ObwinLeaf::sa, &ObwinLeaf::sb>(A.list, A.info, (size_t)2 * A.max_windows, D.S, ui, A.robot, A.row_cap, A.range, A.tol, (double)D.S, ObwinKeys{(double)D.res, A.pt[u]}, out,
+      [&](tj_obswin_row& row, int first, int last) { row.robot = u; row.segment_first = first; row.segment_last = last; });
 }
 
 }  // namespace tj

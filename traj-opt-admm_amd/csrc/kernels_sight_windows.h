@@ -4,7 +4,9 @@
 // The robot-robot queries look at two robots and no obstacle, the obstacle queries at one robot and the obstacles.  This one classifies windows of a LINK's time axis
 // against the UNION of all primitives: time, hover, the cuts at the partner's segment boundaries and the restriction of both RAW hulls are kernels_audit_timed.h's
 // (timed_cuts, timed_span, timed_partner_fill: the expressions of tj_proximity_windows), the BVH walk with its fp64 leaf predicate, the certified GJK bound and the
-// attained point distance kernels_obstacle_windows.h's (bvh_query, gjk / gjk_separates, obst_point_dist), the merge half dev_query.h's.  The definition
+// attained point distance kernels_obstacle_windows.h's (bvh_query, gjk / gjk_separates, obst_point_dist), the merge half and the protocol around it dev_query.h's (win_wave_rounds,
+// win_seg_count, win_seg_place: tj_obstacle_windows' rounds, count and placing, stated once).  This file's own: the evaluation (sight_eval, sight_candidate, sight_sample), the
+// seeds with their truncation test, the keys (SightKeys: a leaf's keys are times already) and the row's link, robot and partner.  The definition
 // (include/trajadmm.h), per link k = (a, b) and segment tr of a:
 //   window   W = [ca, cb] in segment tr of a and in ONE segment j of b (j == S: b hovers; a station: six times its point, no cuts)
 //   body     L(W) = a_0..a_5, b_0..b_5: both raw hulls restricted to W.  The link at any time of W joins a point of conv{a_i} to a point of conv{b_i}: it lies in conv L
@@ -181,7 +183,6 @@ __global__ __launch_bounds__(SW_THREADS) void k_sight_refine(Dev D, SightArgs A)
   SightLeaf* cur = A.list + unit * A.leaf_cap;
   SightLeaf* nxt = cur + maxw;
   SightLeaf* leaf = A.leaf + unit * A.leaf_cap;
-  SightLeaf* const sorted = cur;
 
   // ---- the seeds: segment tr's window of time cut at b's segment boundaries and arrival (a station: no cuts), listed by lane 0 at the head of the live list ----
   if (lane == 0) {
@@ -203,130 +204,33 @@ __global__ __launch_bounds__(SW_THREADS) void k_sight_refine(Dev D, SightArgs A)
     }
   }
   __syncthreads();
-  int kept = s_leaf, n = s_live, depth = 0;   // (LDS words behind a barrier: the same in every lane)
-  bool truncated = n > maxw || kept > maxw;   // the seeds alone: no round, every seed that is not OUT is a leaf
+  const int kept = s_leaf, n = s_live;   // (LDS words behind a barrier: the same in every lane)
+  const bool truncated = n > maxw || kept > maxw;   // the seeds alone: no round, every seed that is not OUT is a leaf (at most S + 1: leaf_cap has room)
 
-  // ---- the rounds ----
-  while (!truncated && n > 0 && depth < A.max_depth) {
-    __syncthreads();   // everyone has read the counters before lane 0 writes them
-    if (lane == 0) s_next = 0;   // (s_leaf goes on from the committed count)
-    for (int i = 0; i < n; i++) {
-      const SightLeaf w = cur[i];   // (one address for the wave)
-      if (prox_is_leaf(w.ca, w.cb, tol)) {
-        if (lane == 0) { const int at = s_leaf++; if (at < maxw) { SightLeaf e = w; e.in = 0; leaf[at] = e; } }
-        continue;
-      }
-      const double cm = 0.5 * (w.ca + w.cb);
-      for (int c = 0; c < 2; c++) {
-        SightLeaf kid;
-        const int cls = sight_eval<PRIM>(D, A, E, tr, w.j, c ? cm : w.ca, c ? w.cb : cm, L, ws, kid);
-        if (lane == 0) {
-          s_work++;
-          if (cls == WIN_IN) { const int at = s_leaf++; if (at < maxw) leaf[at] = kid; }
-          if (cls == WIN_MIXED) { const int at = s_next++; if (at < maxw) nxt[at] = kid; }
-        }
-      }
-    }
-    __syncthreads();   // the lists are written, the counters final
-    const int k2 = s_leaf, n2 = s_next;
-    if (k2 > maxw || n2 > maxw) { truncated = true; break; }   // the committed lists stand: the appends of this round do not count
-    kept = k2; n = n2; depth++;
-    SightLeaf* t = cur; cur = nxt; nxt = t;
-  }
-
-  // ---- the live windows of the last completed round become EDGE leaves ----
-  __syncthreads();
-  for (int i = lane; i < n; i += SW_THREADS) { SightLeaf e = cur[i]; e.in = 0; leaf[kept + i] = e; }
-  const int m = kept + n;   // <= leaf_cap: at most 2 * max_windows from the rounds, at most S + 1 from the seeds alone
-  __syncthreads();
-
-  // ---- by ca into the live lists' room, which is free now, and the chain heads behind the first leaf ----
-  const int heads = win_sort<&SightLeaf::ca, &SightLeaf::cb>(leaf, sorted, m);
-  if (lane == 0) {
-    int* info = A.info + unit * 4;
-    info[0] = m; info[1] = s_work; info[2] = depth | (truncated ? 1 << 16 : 0); info[3] = heads;
-  }
+  // ---- the rounds, the EDGE leaves, the sort by ca and the unit's record ----
+  win_wave_rounds<&SightLeaf::ca, &SightLeaf::cb>(cur, nxt, leaf, kept, n, truncated, maxw, A.max_depth, s_leaf, s_next, s_work, A.info + unit * 4,
+      [&](const SightLeaf& w) { return prox_is_leaf(w.ca, w.cb, tol); },
+      [&](const SightLeaf& w, double ca, double cb, SightLeaf& kid) { return sight_eval<PRIM>(D, A, E, tr, w.j, ca, cb, L, ws, kid); });
 }
 
-// does the first leaf of segment tr of link k start a chain (it does not where the last leaf of segment tr - 1 ends where it begins)
-__device__ __forceinline__ bool sight_first_is_head(const SightArgs& A, int S, int k, int tr) {
-  if (tr == 0) return true;
-  const size_t prev = (size_t)k * S + tr - 1;
-  const int mp = A.info[prev * 4];
-  if (mp == 0) return true;
-  return A.list[prev * A.leaf_cap + mp - 1].cb != A.list[(prev + 1) * A.leaf_cap].ca;
-}
+// a leaf's keys are times already: the position compared across a segment boundary, the time and the width follow from them alone
+struct SightKeys {
+  __device__ __forceinline__ double pos(int, double c) const { return c; }
+  __device__ __forceinline__ double time(int, double c) const { return c; }
+  __device__ __forceinline__ double width(int, double ca, double cb) const { return cb - ca; }
+};
 
 __global__ __launch_bounds__(SW_THREADS) void k_sight_count(Dev D, SightArgs A) {
-  const int k = blockIdx.x, lane = lane_id(), S = D.S;
-  int rows = 0, work = 0;
-  for (int tr = lane; tr < S; tr += SW_THREADS) {
-    const int* info = A.info + ((size_t)k * S + tr) * 4;
-    work += info[1];
-    if (info[0] > 0) rows += info[3] + (sight_first_is_head(A, S, k, tr) ? 1 : 0);
-  }
-  rows = wave_sum(rows); work = wave_sum(work);
-  if (lane == 0) {
-    A.link[2 * k] = rows; A.link[2 * k + 1] = work;
-    if (rows) atomicAdd(A.n_rows, rows);
-  }
+  win_seg_count<&SightLeaf::ca, &SightLeaf::cb>(A.list, A.info, (size_t)A.leaf_cap, D.S, blockIdx.x, A.link, A.n_rows, SightKeys{});
 }
 
-// the rows of link k at their final place: behind the rows of the links before it, chain after chain in time order
+// the rows of link k at their final place (win_seg_place); the row's own: the link and its two ends
 __global__ __launch_bounds__(SW_THREADS) void k_sight_place(Dev D, SightArgs A, tj_sight_row* out) {
-  const int k = blockIdx.x, lane = lane_id(), S = D.S;
-  int base = win_rows_before(A.link, 2, k);   // the link's first row
-  const int windows = A.link[2 * k + 1], a = A.links[2 * k], b = A.links[2 * k + 1];
-  if (a < D.u0 || a >= D.u1) return;   // (another rank's link: no leaves)
-  const double dist = A.range, tol = A.tol;
+  const int k = blockIdx.x, S = D.S, a = A.links[2 * k], b = A.links[2 * k + 1];
+  if (a < D.u0 || a >= D.u1) return;   // (another rank's link: no leaves; the whole block leaves)
   const double t_end = ((S - 1 + 1) / (double)D.res) * A.pt[a];   // the end of a's last segment, in the seeds' expression
-  const size_t per = (size_t)A.leaf_cap;
-  for (int tr = 0; tr < S; tr++) {
-    const size_t unit = (size_t)k * S + tr;
-    const int m = A.info[unit * 4];   // (one address for the wave)
-    if (m == 0) continue;
-    const SightLeaf* sorted = A.list + unit * per;
-    const bool first_head = sight_first_is_head(A, S, k, tr);
-    for (int i0 = 0; i0 < m; i0 += SW_THREADS) {
-      const int i = i0 + lane;
-      const bool head = win_head<&SightLeaf::ca, &SightLeaf::cb>(sorted, i, m, first_head);
-      const int r = win_row_index(head, base);
-      if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
-        // the chain from leaf i of segment tr on, left to right, into the segments behind where it goes on
-        tj_sight_row row;
-        WinChain ch;
-        double end = 0.0;
-        int t = tr, at = i, mt = m, leaves = 0, dmax = 0;
-        bool trunc = false;
-        const SightLeaf* sl = sorted;
-        for (;;) {
-          if (at == 0 || leaves == 0) { const int dt = A.info[((size_t)k * S + t) * 4 + 2]; dmax = max(dmax, dt & 0xffff); trunc = trunc || (dt >> 16) != 0; }
-          const SightLeaf x = sl[at];
-          ch.add(dist, x.ca, x.cb, x.cb - x.ca, x.in, x.h0, x.h5, x.i0, x.i5);
-          end = x.cb;
-          leaves++;
-          if (at + 1 < mt) {
-            if (sl[at + 1].ca != end) break;
-            at++;
-          } else {
-            if (t + 1 >= S) break;
-            const int m2 = A.info[((size_t)k * S + t + 1) * 4];
-            if (m2 == 0) break;
-            const SightLeaf* s2 = A.list + ((size_t)k * S + t + 1) * per;
-            if (s2[0].ca != end) break;
-            t++; at = 0; mt = m2; sl = s2;
-          }
-        }
-        const bool found = ch.best_i != INT_MAX;
-        const double t0 = sorted[i].ca;
-        ch.finish(row, t0, end, t0 == 0.0, end == t_end, trunc, tol);
-        row.closest_time = found ? ch.best_t : -1.0;
-        row.link = k; row.robot = a; row.partner = b; row.index = found ? ch.best_i : -1;
-        row.leaves = leaves; row.depth = dmax; row.windows = windows;
-        out[r] = row;
-      }
-    }
-  }
+  win_seg_place<&SightLeaf::ca, &SightLeaf::cb>(A.list, A.info, (size_t)A.leaf_cap, S, k, A.link, A.row_cap, A.range, A.tol, t_end, SightKeys{}, out,
+      [&](tj_sight_row& row, int, int) { row.link = k; row.robot = a; row.partner = b; });
 }
 
 }  // namespace tj

@@ -3,8 +3,9 @@
 // The siblings answer against what the scene or the state fixes: the obstacle set (kernels_obstacle_windows.h, kernels_sight_windows.h), the other robots
 // (kernels_proximity.h), the robot's own dynamics (kernels_dynamics_windows.h).  A geofence, a no-fly box, an altitude band, a station's coverage ball are none of these:
 // they never enter the BVH or the optimiser and change per question.  The fifth of the window queries: the raw position hull and its blossoming are dev_query.h's
-// (hull_entry's sums, bez_restrict), the search loop is dev_query.h's win_lane_search -- tj_dynamics_windows' search word for word -- and so is the merge half (WIN_*,
-// win_sort, win_head, win_rows_before, win_row_index, WinChain with a leaf's faces in its id slots).  Only the evaluation is new.  The definition (include/trajadmm.h), per
+// (hull_entry's sums, bez_restrict), the search loop and the placing of a slot's rows are dev_query.h's (WinSlotArgs, win_lane_search, win_slot_place: tj_dynamics_windows' word
+// for word) and so is the merge half (WIN_*, win_sort, win_head, win_rows_before, win_row_index, WinChain with a leaf's faces in its id slots, WinRowFold, win_time).  This
+// file's own: the evaluation (zonewin_eval), the zones with their staging in LDS, and the row.  The definition (include/trajadmm.h), per
 // slot = (owned robot u, zone k):
 //   net      b_0..b_5 = the raw hull of segment tr restricted to [sa, sb] (always from the RAW hull; [0, 1] returns it bit for bit)
 //   PLANES   f_ij = dot3(n_j, b_i) - d_j over the zone's rows (n_j, d_j); lb = max_j min_i f_ij, ub = max_j max_i f_ij; g0 = max_j f_0j, g5 = max_j f_5j, each with its
@@ -20,7 +21,7 @@
 //   k_zonewin_refine  grid (owned x n_zones), ONE wave per block.  The block's zone and its rows of the shape table are staged in LDS once; the block dispatches once on
 //                     the zone's kind to a body templated on it (the branch is the block's).  Seeds and live windows are strided over the lanes, each lane halves its
 //                     own window and evaluates both children in registers: the 18 net values stay in registers while the face loop, rolled, reads a row from LDS.
-//   k_zonewin_place   one wave per slot: win_rows_before over the slots before it gives its first row; blocks of 64 leaves through win_head / win_row_index; the lane
+//   k_zonewin_place   one wave per slot (win_slot_place): win_rows_before over the slots before it gives its first row; blocks of 64 leaves through win_head / win_row_index; the lane
 //                     of a head folds its chain left to right (WinChain) and writes the row at its final place.  Rows beyond the caller's capacity are counted only.
 // The trip counts of the round loop, of the loop over live windows and of the face loop are read from LDS behind a barrier; every loop is bounded by max_depth <= 40,
 // the list capacities and TJ_ZONEWIN_MAX_PLANES.  No float atomics, no polling, no workgroup waits on another, nothing of the iteration's scratch, no tj_stats counter,
@@ -40,22 +41,14 @@ constexpr int ZW_THREADS = WIN_LANES;   // one wave per slot
 struct ZoneLeaf { double sa, sb, ga, gb, g0, g5; int tr; int in : 8, f0 : 12, f5 : 12; };
 static_assert(sizeof(ZoneLeaf) == 56 && TJ_ZONEWIN_MAX_PLANES < 2048, "a leaf's faces fit their bit-fields");
 
-struct ZonewinArgs {
-  const double* net;        // [U][3][T]
-  const double* pt;         // [U]
+// dev_query.h's WinSlotArgs, the zones and their rows
+struct ZonewinArgs : WinSlotArgs<ZoneLeaf> {
   const tj_zone* zones;     // [n_zones], checked on the host: first / count inside the table
   const double* shapes;     // [n_shapes][4]
-  double tol;
-  int max_depth, max_windows, n_zones;
-  int row_cap;              // the caller's rows
-  ZoneLeaf* list;           // [slots][2][S + max_windows] ping-pong live lists; behind the rounds the slot's leaves by flight position
-  ZoneLeaf* leaf;           // [slots][S + 2 * max_windows] the kept list, in the order of the appends
-  int* info;                // [slots][4] leaves, work, depth (+ 1 << 16: truncated), rows
-  int* n_rows;              // [1]
+  int n_zones;
 };
 
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
-__device__ __forceinline__ double zonewin_time(const Dev& D, double ptu, double g) { return (g / (double)D.res) * ptu; }   // ((tr + s) / res) * piece_time: the siblings' expression
 
 // ONE evaluation, in a lane's registers: the class of [sa, sb] of segment tr against the zone, and the window with its attained ends.  rows: the zone's rows in LDS
 template <int KIND>
@@ -122,15 +115,7 @@ __device__ __forceinline__ int zonewin_eval(const Dev& D, const double* __restri
   return cls;
 }
 
-// the slot's search: dev_query.h's win_lane_search with zonewin_eval as its evaluation; s_*: the workgroup's LDS counters
-template <int KIND>
-__device__ void zonewin_search(const Dev& D, const ZonewinArgs& A, size_t slot, int u, const double* rows, int count, int sense, double level, int& s_leaf, int& s_next, int& s_work) {
-  const int S = D.S, maxw = A.max_windows;
-  const double* nu = A.net + (size_t)u * 3 * D.T;
-  win_lane_search(S, (double)D.res, A.pt[u], A.tol, A.max_depth, maxw, A.list + slot * 2 * win_live_cap(S, maxw), A.leaf + slot * win_leaf_cap(S, maxw), A.info + slot * 4, A.n_rows,
-                  s_leaf, s_next, s_work, [&](int tr, double sa, double sb, ZoneLeaf& w) { return zonewin_eval<KIND>(D, nu, tr, sa, sb, rows, count, sense, level, w); });
-}
-
+// the slot's search: dev_query.h's win_lane_search with zonewin_eval at the zone's kind as its evaluation
 __global__ __launch_bounds__(ZW_THREADS) void k_zonewin_refine(Dev D, ZonewinArgs A) {
   const int ui = blockIdx.x / A.n_zones, k = blockIdx.x - ui * A.n_zones, u = D.u0 + ui, lane = lane_id();
   __shared__ int s_leaf, s_next, s_work;
@@ -144,52 +129,28 @@ __global__ __launch_bounds__(ZW_THREADS) void k_zonewin_refine(Dev D, ZonewinArg
   __syncthreads();
   const int kind = s_zone[0], sense = s_zone[1], n = s_zone[2];   // (LDS words behind a barrier: the branch and the face loop's trip count are the block's)
   const double level = s_level;
-  if (kind == TJ_ZONE_PLANES) zonewin_search<TJ_ZONE_PLANES>(D, A, blockIdx.x, u, s_rows, n, sense, level, s_leaf, s_next, s_work);
-  else zonewin_search<TJ_ZONE_BALL>(D, A, blockIdx.x, u, s_rows, n, sense, level, s_leaf, s_next, s_work);
+  const double* nu = A.net + (size_t)u * 3 * D.T;
+  const auto search = [&](auto kd) {
+    win_lane_search(D, A, blockIdx.x, u, s_leaf, s_next, s_work, [&](int tr, double sa, double sb, ZoneLeaf& w) { return zonewin_eval<decltype(kd)::value>(D, nu, tr, sa, sb, s_rows, n, sense, level, w); });
+  };
+  if (kind == TJ_ZONE_PLANES) search(std::integral_constant<int, TJ_ZONE_PLANES>{});
+  else search(std::integral_constant<int, TJ_ZONE_BALL>{});
 }
 
-// what WinChain::finish states of a row (it writes a member called `closest`: sigma * closest is the row's `extreme`)
-struct ZoneRowFold { double t_first_lo, t_first_hi, t_last_lo, t_last_hi, within_lo, closest; int flags; };
-
-// the rows of a slot at their final place: behind the rows of the slots before it, chain after chain in time order
+// the rows of a slot at their final place (win_slot_place): the slot's robot and zone, a leaf's faces as the chain's ids, and the row's own fields
 __global__ __launch_bounds__(ZW_THREADS) void k_zonewin_place(Dev D, ZonewinArgs A, tj_zonewin_row* out) {
-  const int slot = blockIdx.x, lane = lane_id(), S = D.S;
-  const int ui = slot / A.n_zones, k = slot - ui * A.n_zones, u = D.u0 + ui;
-  int base = win_rows_before(A.info + 3, 4, slot);   // the slot's first row
-  const int* info = A.info + (size_t)slot * 4;
-  const int m = info[0], windows = info[1], depth = info[2] & 0xffff;
-  const bool trunc = (info[2] >> 16) != 0;
+  const int slot = blockIdx.x, ui = slot / A.n_zones, k = slot - ui * A.n_zones, u = D.u0 + ui;
   const tj_zone z = A.zones[k];
-  const double sigma = z.sense == TJ_ZONE_INSIDE ? 1.0 : -1.0, L = sigma * z.level;
-  const double tol = A.tol, ptu = A.pt[u], res = (double)D.res;
-  const ZoneLeaf* sorted = A.list + (size_t)slot * 2 * win_live_cap(S, A.max_windows);
-  for (int i0 = 0; i0 < m; i0 += ZW_THREADS) {
-    const int i = i0 + lane;
-    const bool head = win_head<&ZoneLeaf::ga, &ZoneLeaf::gb>(sorted, i, m, true);
-    const int r = win_row_index(head, base);
-    if (head && r < A.row_cap) {   // (no lane leaves the block loop early: every lane reaches the next ballot)
-      WinChain ch;
-      int j = i, leaves = 0;
-      ZoneLeaf x;
-      for (;;) {
-        x = sorted[j];
-        ch.add(L, zonewin_time(D, ptu, x.ga), zonewin_time(D, ptu, x.gb), ((x.sb - x.sa) / res) * ptu, x.in != 0, x.g0, x.g5, x.f0, x.f5);
-        leaves++;
-        if (j + 1 >= m || sorted[j + 1].ga != x.gb) break;
-        j++;
-      }
-      const ZoneLeaf first = sorted[i];
-      ZoneRowFold f;
-      ch.finish(f, zonewin_time(D, ptu, first.ga), zonewin_time(D, ptu, x.gb), first.ga == 0.0, x.gb == (double)S, trunc, tol);
-      tj_zonewin_row row;
-      row.t_first_lo = f.t_first_lo; row.t_first_hi = f.t_first_hi; row.t_last_lo = f.t_last_lo; row.t_last_hi = f.t_last_hi; row.within_lo = f.within_lo;
-      row.extreme = sigma * f.closest; row.extreme_time = ch.best_t;
-      row.robot = u; row.zone = k; row.sense = z.sense; row.face = ch.best_i;
-      row.segment_first = first.tr; row.segment_last = x.tr;
-      row.leaves = leaves; row.depth = depth; row.flags = f.flags; row.windows = windows;
-      out[r] = row;
-    }
-  }
+  const double sigma = z.sense == TJ_ZONE_INSIDE ? 1.0 : -1.0;
+  win_slot_place(D, A, slot, u, sigma * z.level, [](const ZoneLeaf& x, int& f0, int& f5) { f0 = x.f0; f5 = x.f5; },
+                 [&](int r, const WinRowFold& f, const WinChain& ch, const ZoneLeaf& first, const ZoneLeaf& last, int leaves, int depth, int windows) {
+                   tj_zonewin_row row;
+                   f.put(row, sigma, ch);
+                   row.robot = u; row.zone = k; row.sense = z.sense; row.face = ch.best_i;
+                   row.segment_first = first.tr; row.segment_last = last.tr;
+                   row.leaves = leaves; row.depth = depth; row.windows = windows;
+                   out[r] = row;
+                 });
 }
 
 }  // namespace tj

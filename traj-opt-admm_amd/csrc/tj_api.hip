@@ -85,19 +85,19 @@ struct Listed { unsigned* mask = nullptr; int* wordoff = nullptr; int* n = nullp
 // what a context holds for tj_proximity_windows (proximity_run): as Listed, with the row total
 struct ProxHeld : Listed<ProxArgs, tj_proximity_row> { int* n_rows = nullptr; };
 
-// what a context holds for tj_obstacle_windows (obswin_run): the per-segment lists grow with the largest max_windows so far, the rows with the largest cap
-struct ObwinHeld { ObwinArgs sized{}; int* n_rows = nullptr; tj_obswin_row* out = nullptr; std::vector<void*> allocs, out_allocs; int mw = 0, cap = 0; };
+// the rows of a window query whose row total is counted on the device (obswin_run, sight_run, slot_run): the count, and the rows grown to the largest cap so far
+template <class Row>
+struct RowsHeld { int* n_rows = nullptr; Row* out = nullptr; std::vector<void*> out_allocs; int cap = 0; };
 
-// what a context holds for tj_sight_windows (sight_run): the lists grow with the largest n_links x S x leaf_cap so far, the counters with the largest n_links x S, the links and stations with their counts, the
-// rows with the largest cap
-struct SightHeld { SightArgs sized{}; int* links = nullptr; double* stations = nullptr; int* n_rows = nullptr; tj_sight_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t items = 0, units = 0; int n_links = 0, n_stations = 0, cap = 0; };
+// what a context holds for tj_obstacle_windows (obswin_run): the per-segment lists grow with the largest max_windows so far
+struct ObwinHeld : RowsHeld<tj_obswin_row> { ObwinArgs sized{}; std::vector<void*> allocs; int mw = 0; };
 
-// what a context holds for tj_dynamics_windows (dynwin_run): the per-slot lists grow with the largest slots x (3 S + 4 max_windows) so far, the rows with the largest cap
-struct DynwinHeld { DynwinArgs sized{}; tj_dyn_gate* gates = nullptr; int* n_rows = nullptr; tj_dynwin_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t slots = 0, live = 0, leaf = 0; int cap = 0; };
+// what a context holds for tj_sight_windows (sight_run): the lists grow with the largest n_links x S x leaf_cap so far, the counters with the largest n_links x S, the links and stations with their counts
+struct SightHeld : RowsHeld<tj_sight_row> { SightArgs sized{}; int* links = nullptr; double* stations = nullptr; std::vector<void*> allocs; size_t items = 0, units = 0; int n_links = 0, n_stations = 0; };
 
-// what a context holds for tj_zone_windows (zonewin_run): the per-slot lists grow with the largest slots x (3 S + 4 max_windows) so far, the rows with the largest cap; the
-// zone list and the shape table have their largest size from the start
-struct ZonewinHeld { ZonewinArgs sized{}; tj_zone* zones = nullptr; double* shapes = nullptr; int* n_rows = nullptr; tj_zonewin_row* out = nullptr; std::vector<void*> allocs, out_allocs; size_t slots = 0, live = 0, leaf = 0; int cap = 0; };
+// what a context holds for a slot query (tj_dynamics_windows, tj_zone_windows; slot_run): the per-slot lists grow with the largest slots x (3 S + 4 max_windows) so far
+template <class Args, class Row>
+struct SlotHeld : RowsHeld<Row> { Args sized{}; std::vector<void*> allocs; size_t slots = 0, live = 0, leaf = 0; };
 
 struct tj_ctx {
   tj_params prm;
@@ -147,8 +147,8 @@ struct tj_ctx {
   ProxHeld prox;   // tj_proximity_windows
   ObwinHeld obwin; // tj_obstacle_windows
   SightHeld sight; // tj_sight_windows
-  DynwinHeld dynwin; // tj_dynamics_windows
-  ZonewinHeld zonewin; // tj_zone_windows
+  SlotHeld<DynwinArgs, tj_dynwin_row> dynwin; tj_dyn_gate* dynwin_gates = nullptr;   // tj_dynamics_windows, and the gates of a call (their largest size from the start)
+  SlotHeld<ZonewinArgs, tj_zonewin_row> zonewin; tj_zone* zonewin_zones = nullptr; double* zonewin_shapes = nullptr;   // tj_zone_windows, and the zone list and shape table of a call (the same)
   // tj_flight_profile: times [K], positions [K][U][3] and records [U][K] grow with the largest n_times so far (profile_cap) and live in profile_allocs
   ProfileArgs profile{}; tj_profile_sample* profile_out = nullptr;
   std::vector<void*> profile_allocs; int profile_cap = 0;
@@ -723,14 +723,8 @@ void tj_destroy(tj_ctx* c) {
   for (void* p : c->cross.allocs) hipFree(p);
   for (void* p : c->margin.allocs) hipFree(p);
   for (void* p : c->prox.allocs) hipFree(p);
-  for (void* p : c->obwin.allocs) hipFree(p);
-  for (void* p : c->obwin.out_allocs) hipFree(p);
-  for (void* p : c->sight.allocs) hipFree(p);
-  for (void* p : c->sight.out_allocs) hipFree(p);
-  for (void* p : c->dynwin.allocs) hipFree(p);
-  for (void* p : c->dynwin.out_allocs) hipFree(p);
-  for (void* p : c->zonewin.allocs) hipFree(p);
-  for (void* p : c->zonewin.out_allocs) hipFree(p);
+  const auto free_windows = [](auto& h) { for (void* p : h.allocs) hipFree(p); for (void* p : h.out_allocs) hipFree(p); };   // a window query's lists, and its rows (RowsHeld)
+  free_windows(c->obwin); free_windows(c->sight); free_windows(c->dynwin); free_windows(c->zonewin);
   for (void* p : c->profile_allocs) hipFree(p);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -1319,7 +1313,8 @@ int query_finish(tj_ctx* c, const char* walk) {
   return TJ_OK;
 }
 
-// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, dynwin_run, zonewin_run, profile_run) ----
+// ---- what the row-listing and the sampling queries share on the host (listed_run, proximity_run, obswin_run, sight_run, slot_run of dynwin_run and zonewin_run, profile_run) ----
+// rows_finish ends every row-listing call; rows_args_ok, rows_begin and rows_end are the window queries' whose device counts the rows (proximity_run keeps its own tail: its *n = -1 rule)
 // the refusal of a call whose buffers would exceed its query's byte budget, up front, nothing allocated.  what: the call's sizes in its words; advice: what to lower
 int query_budget(tj_ctx* c, const std::string& what, size_t bytes, const char* budget, long long max_bytes, const char* advice) {
   if (bytes <= (size_t)max_bytes) return TJ_OK;
@@ -1365,6 +1360,35 @@ int rows_finish(tj_ctx* c, const std::string& name, Rec* rows, const Rec* dev, i
   if (std::min(cap, total) > 0 && ((r = query_fetch(c, rows, dev, std::min(cap, total))) || (r = query_finish(c, nullptr)))) return r;
   if (total > cap && !silent) { c->err = name + ": " + std::to_string(total) + " " + what + " " + std::to_string(cap) + ": the first " + std::to_string(cap) + " were written"; return TJ_ERR_CAPACITY; }
   return TJ_OK;
+}
+
+// the first line of every row-listing call: a context, somewhere to put the count, and rows where there is room for any
+template <class Rec>
+bool rows_args_ok(const tj_ctx* c, const int* n, const Rec* rows, int cap) { return c && n && cap >= 0 && !(cap > 0 && !rows); }
+// a RowsHeld before its call's launches: the device's row count, and the rows grown to the largest cap so far.  (Clearing the count stays with the caller, right before its launches.)
+template <class Row>
+int rows_begin(tj_ctx* c, RowsHeld<Row>& h, int cap) {
+  int r = query_buf(c, h.n_rows, 1);
+  if (!r && cap > h.cap) {
+    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
+    h.cap = cap;
+  }
+  return r;
+}
+// a RowsHeld behind its call's launches: the count is fetched and the call waited for, *n = the rows, min(cap, *n) of them go to the caller; more rows than cap are
+// TJ_ERR_CAPACITY unless the call only counts (cap == 0 without rows).  walked: the query walked the BVH, and a frontier overflow ends the call here, worded for `dist`
+// (query_finish words it for a `range`), *n untouched: no count is known
+template <class Row>
+int rows_end(tj_ctx* c, const SearchSpec& spec, RowsHeld<Row>& h, Row* rows, int cap, int* n, bool walked) {
+  const std::string name = spec.name;
+  int r, nr = 0;
+  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, walked ? spec.name : nullptr))) {
+    if (walked && r == TJ_ERR_CAPACITY)
+      c->err = name + ": the BVH frontier of a window overflowed at this dist (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one window's box): lower `dist`";
+    return r;
+  }
+  *n = nr;
+  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
 }
 
 int audit_run(tj_ctx* c, double range, const double* net_host, tj_audit_robot* out, double* seg_obs, double* seg_pair) {
@@ -1524,7 +1548,7 @@ struct MarginQuery {
 // query's own argument, if it has one (Q::extra checks and stores it)
 template <class Q>
 int listed_run(tj_ctx* c, double range, double tol, int max_depth, int max_windows, double extra, const double* net_host, const double* pt_host, typename Q::Rec* rows, int cap, int* n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  if (!rows_args_ok(c, n, rows, cap)) return TJ_ERR_INVALID;
   const std::string name = Q::spec.name;
   int r;
   SearchArgs sa;
@@ -1622,7 +1646,7 @@ size_t obswin_bytes(const Dev& d, int owned, int cap, int mw) {
   return (size_t)owned * d.S * ((size_t)4 * mw * sizeof(ObwinLeaf) + 4 * sizeof(int)) + (size_t)owned * 2 * sizeof(int) + (size_t)cap * sizeof(tj_obswin_row);
 }
 int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !rows)) return TJ_ERR_INVALID;
+  if (!rows_args_ok(c, n, rows, cap)) return TJ_ERR_INVALID;
   const SearchSpec& spec = SEARCH_OBSWIN;
   const std::string name = spec.name;
   int r;
@@ -1637,15 +1661,11 @@ int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_window
   QUIESCE(c);
   ObwinHeld& h = c->obwin;
   const size_t units = (size_t)owned * d.S;
-  if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.sized.info, units * 4)) || (r = query_buf(c, h.sized.robot, (size_t)owned * 2)) || (r = ensure_order(c))) return r;
+  if ((r = rows_begin(c, h, cap)) || (r = query_buf(c, h.sized.info, units * 4)) || (r = query_buf(c, h.sized.robot, (size_t)owned * 2)) || (r = ensure_order(c))) return r;
   if (mw > h.mw) {
     if ((r = query_grow(h.allocs, [&] { h.sized.list = nullptr; h.sized.leaf = nullptr; h.mw = 0; },
                         [&] { const int e = query_buf(c, h.sized.list, units * 2 * mw, &h.allocs); return e ? e : query_buf(c, h.sized.leaf, units * 2 * mw, &h.allocs); }))) return r;
     h.mw = mw;
-  }
-  if (cap > h.cap) {
-    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
-    h.cap = cap;
   }
   ObwinArgs a = h.sized;
   Dev da;
@@ -1655,14 +1675,7 @@ int obswin_run(tj_ctx* c, double dist, double tol, int max_depth, int max_window
   with_prim(d, [&](auto prim) { hipLaunchKernelGGL(k_obwin_refine<decltype(prim)::value>, dim3((unsigned)units), dim3(OW_THREADS), 0, c->stream, da, a); });
   hipLaunchKernelGGL(k_obwin_count, dim3(owned), dim3(OW_THREADS), 0, c->stream, da, a);
   if (cap > 0) hipLaunchKernelGGL(k_obwin_place, dim3(owned), dim3(OW_THREADS), 0, c->stream, da, a, h.out);
-  int nr = 0;
-  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, spec.name))) {   // (a walk overflow ends here: no count is known, *n stays untouched)
-    if (r == TJ_ERR_CAPACITY)   // (query_finish words it for a `range`; this query's first argument is `dist`)
-      c->err = name + ": the BVH frontier of a window overflowed at this dist (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one window's box): lower `dist`";
-    return r;
-  }
-  *n = nr;
-  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+  return rows_end(c, spec, h, rows, cap, n, true);   // (a walk overflow ends there: *n stays untouched)
 }
 
 // tj_sight_windows (kernels_sight_windows.h): the rows of the links (a, b) whose a is owned, `link` = the caller's index; a link of another rank's robot has no row here
@@ -1674,7 +1687,7 @@ size_t sight_bytes(const Dev& d, int n_links, int n_stations, int cap, int mw) {
 }
 int sight_run(tj_ctx* c, const int* links, int n_links, const double* stations, int n_stations, double dist, double tol, int max_depth, int max_windows,
               const double* net_host, const double* pt_host, tj_sight_row* rows, int cap, int* n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !rows) || n_links < 0 || (n_links > 0 && !links) || n_stations < 0 || (n_stations > 0 && !stations)) return TJ_ERR_INVALID;
+  if (!rows_args_ok(c, n, rows, cap) || n_links < 0 || (n_links > 0 && !links) || n_stations < 0 || (n_stations > 0 && !stations)) return TJ_ERR_INVALID;
   const SearchSpec& spec = SEARCH_SIGHT;
   const std::string name = spec.name;
   int r;
@@ -1697,7 +1710,7 @@ int sight_run(tj_ctx* c, const int* links, int n_links, const double* stations, 
   QUIESCE(c);
   SightHeld& h = c->sight;
   const size_t units = (size_t)n_links * d.S, items = units * leaf_cap;
-  if ((r = query_buf(c, h.n_rows, 1)) || (r = ensure_order(c))) return r;
+  if ((r = rows_begin(c, h, cap)) || (r = ensure_order(c))) return r;
   if (items > h.items || units > h.units || n_links > h.n_links || n_stations > h.n_stations) {
     const size_t gi = std::max(items, h.items), gu = std::max(units, h.units);
     const int gl = std::max(n_links, h.n_links), gs = std::max(n_stations, h.n_stations);
@@ -1709,10 +1722,6 @@ int sight_run(tj_ctx* c, const int* links, int n_links, const double* stations, 
          }))) return r;
     h.items = gi; h.units = gu; h.n_links = gl; h.n_stations = gs;
   }
-  if (cap > h.cap) {
-    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
-    h.cap = cap;
-  }
   SightArgs a = h.sized;
   Dev da;
   if ((r = query_inputs(c, net_host, pt_host, a.net, a.pt)) || (r = walk_dev(c, da)) || (r = upload(c, h.links, links, (size_t)n_links * 2 * sizeof(int))) ||
@@ -1722,24 +1731,54 @@ int sight_run(tj_ctx* c, const int* links, int n_links, const double* stations, 
   with_prim(d, [&](auto prim) { hipLaunchKernelGGL(k_sight_refine<decltype(prim)::value>, dim3((unsigned)units), dim3(SW_THREADS), 0, c->stream, da, a); });
   hipLaunchKernelGGL(k_sight_count, dim3(n_links), dim3(SW_THREADS), 0, c->stream, da, a);
   if (cap > 0) hipLaunchKernelGGL(k_sight_place, dim3(n_links), dim3(SW_THREADS), 0, c->stream, da, a, h.out);
-  int nr = 0;
-  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, spec.name))) {   // (a walk overflow ends here: no count is known, *n stays untouched)
-    if (r == TJ_ERR_CAPACITY)   // (query_finish words it for a `range`; this query's first argument is `dist`)
-      c->err = name + ": the BVH frontier of a window overflowed at this dist (more than " + std::to_string(FRONT_CAP) + " boxes of 8 primitives near one window's box): lower `dist`";
-    return r;
-  }
-  *n = nr;
-  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+  return rows_end(c, spec, h, rows, cap, n, true);   // (a walk overflow ends there: *n stays untouched)
 }
 
-// tj_dynamics_windows (kernels_dynamics_windows.h): the rows of the owned robots from the context's own state, gate after gate (nothing of another robot is read, so
-// a sharded context answers for its own and a group calls this rank after rank).  *n = the rows; min(cap, *n) of them are written.  Two launches for the rows, one
-// for the count.  gates == null with n_gates == 0: the two default gates.
-size_t dynwin_bytes(const Dev& d, size_t slots, int cap, int mw) {
-  return slots * (((size_t)3 * d.S + (size_t)4 * mw) * sizeof(DynLeaf) + 4 * sizeof(int)) + (size_t)cap * sizeof(tj_dynwin_row);
+// ---- the slot queries tj_dynamics_windows and tj_zone_windows (dev_query.h: WinSlotArgs, win_lane_search, win_slot_place): the rows of the owned robots from the
+// context's own state, slot after slot = (robot, the call's k-th gate or zone); nothing of another robot is read, so a sharded context answers for its own and a group
+// calls it rank after rank.  *n = the rows; min(cap, *n) of them are written.  Two launches for the rows, one for the count. ----
+template <class Leaf, class Row>
+size_t slot_bytes(const Dev& d, size_t slots, int cap, int mw) {
+  return slots * (((size_t)3 * d.S + (size_t)4 * mw) * sizeof(Leaf) + 4 * sizeof(int)) + (size_t)cap * sizeof(Row);
 }
+// What a slot query's *_run hands on once its own arguments are checked, defaulted and packed.  sa: tol, max_depth, max_windows; per_robot of `noun` ("gates",
+// "zones"): the slots of a robot; budget, max_bytes, advice: query_budget's.  own(a) -> rc: the call's uploads and the members `a` has beyond WinSlotArgs.
+template <class Args, class Row, class Own>
+int slot_run(tj_ctx* c, const SearchSpec& spec, const SearchArgs& sa, SlotHeld<Args, Row>& h, int per_robot, const char* noun, const char* budget, long long max_bytes, const char* advice,
+             Own&& own, void (*refine)(Dev, Args), void (*place)(Dev, Args, Row*), Row* rows, int cap, int* n) {
+  const std::string name = spec.name;
+  const Dev& d = c->d;
+  const int mw = sa.max_windows, owned = d.u1 - d.u0;
+  const size_t slots = (size_t)std::max(owned, 0) * per_robot;
+  int r;
+  if ((r = query_budget(c, name + ": " + std::to_string(owned) + " robots x " + std::to_string(per_robot) + " " + noun + " of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
+                        slot_bytes<typename Args::Leaf, Row>(d, slots, cap, mw), budget, max_bytes, advice)) ||
+      (r = query_state(c, spec.name, false, false))) return r;
+  if (slots == 0) { *n = 0; return TJ_OK; }
+  QUIESCE(c);
+  const size_t live = slots * 2 * ((size_t)d.S + mw), leaf = slots * ((size_t)d.S + 2 * (size_t)mw);
+  if ((r = rows_begin(c, h, cap))) return r;
+  if (slots > h.slots || live > h.live || leaf > h.leaf) {
+    const size_t gs = std::max(slots, h.slots), gv = std::max(live, h.live), gf = std::max(leaf, h.leaf);
+    if ((r = query_grow(h.allocs, [&] { h.sized = {}; h.slots = 0; h.live = 0; h.leaf = 0; }, [&] {
+           int e;   // (the first failure, or TJ_OK)
+           (e = query_buf(c, h.sized.list, gv, &h.allocs)) || (e = query_buf(c, h.sized.leaf, gf, &h.allocs)) || (e = query_buf(c, h.sized.info, gs * 4, &h.allocs));
+           return e;
+         }))) return r;
+    h.slots = gs; h.live = gv; h.leaf = gf;
+  }
+  Args a = h.sized;
+  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = own(a))) return r;
+  a.tol = sa.tol; a.max_depth = sa.max_depth; a.max_windows = mw; a.row_cap = cap; a.n_rows = h.n_rows;
+  if ((r = query_clear(c, h.n_rows, 1))) return r;
+  hipLaunchKernelGGL(refine, dim3((unsigned)slots), dim3(WIN_LANES), 0, c->stream, d, a);
+  if (cap > 0) hipLaunchKernelGGL(place, dim3((unsigned)slots), dim3(WIN_LANES), 0, c->stream, d, a, h.out);
+  return rows_end(c, spec, h, rows, cap, n, false);
+}
+
+// tj_dynamics_windows (kernels_dynamics_windows.h): slot_run over (robot, gate).  gates == null with n_gates == 0: the two default gates.
 int dynwin_run(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !rows) || n_gates < 0 || (n_gates > 0 && !gates)) return TJ_ERR_INVALID;
+  if (!rows_args_ok(c, n, rows, cap) || n_gates < 0 || (n_gates > 0 && !gates)) return TJ_ERR_INVALID;
   const SearchSpec& spec = SEARCH_DYNWIN;
   const std::string name = spec.name;
   const Dev& d = c->d;
@@ -1758,49 +1797,18 @@ int dynwin_run(tj_ctx* c, const tj_dyn_gate* gates, int n_gates, double tol, int
   if (tol < 0) sa.tol = (TJ_DYNWIN_TOL_FRACTION * d.vel_limit) / d.acc_limit;
   std::vector<tj_dyn_gate> gl(gates, gates + n_gates);
   if (!gates) gl = {tj_dyn_gate{d.vel_limit, TJ_DYNWIN_SPEED, TJ_DYNWIN_ABOVE}, tj_dyn_gate{d.acc_limit, TJ_DYNWIN_ACCEL, TJ_DYNWIN_ABOVE}};
-  const int ng = (int)gl.size(), mw = sa.max_windows, owned = d.u1 - d.u0;
-  const size_t slots = (size_t)std::max(owned, 0) * ng;
-  if ((r = query_budget(c, name + ": " + std::to_string(owned) + " robots x " + std::to_string(ng) + " gates of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
-                        dynwin_bytes(d, slots, cap, mw), "TJ_DYNWIN_MAX_BYTES", TJ_DYNWIN_MAX_BYTES, "lower max_windows, cap or the number of gates")) ||
-      (r = query_state(c, spec.name, false, false))) return r;
-  if (slots == 0) { *n = 0; return TJ_OK; }
-  QUIESCE(c);
-  DynwinHeld& h = c->dynwin;
-  const size_t live = slots * 2 * ((size_t)d.S + mw), leaf = slots * ((size_t)d.S + 2 * (size_t)mw);
-  if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.gates, TJ_DYNWIN_MAX_GATES))) return r;
-  if (slots > h.slots || live > h.live || leaf > h.leaf) {
-    const size_t gs = std::max(slots, h.slots), gv = std::max(live, h.live), gf = std::max(leaf, h.leaf);
-    if ((r = query_grow(h.allocs, [&] { h.sized = {}; h.slots = 0; h.live = 0; h.leaf = 0; }, [&] {
-           int e;   // (the first failure, or TJ_OK)
-           (e = query_buf(c, h.sized.list, gv, &h.allocs)) || (e = query_buf(c, h.sized.leaf, gf, &h.allocs)) || (e = query_buf(c, h.sized.info, gs * 4, &h.allocs));
-           return e;
-         }))) return r;
-    h.slots = gs; h.live = gv; h.leaf = gf;
-  }
-  if (cap > h.cap) {
-    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
-    h.cap = cap;
-  }
-  DynwinArgs a = h.sized;
-  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = upload(c, h.gates, gl.data(), (size_t)ng * sizeof(tj_dyn_gate)))) return r;
-  a.gates = h.gates; a.tol = sa.tol; a.max_depth = sa.max_depth; a.max_windows = mw; a.n_gates = ng; a.row_cap = cap; a.n_rows = h.n_rows;
-  if ((r = query_clear(c, h.n_rows, 1))) return r;
-  hipLaunchKernelGGL(k_dynwin_refine, dim3((unsigned)slots), dim3(DW_THREADS), 0, c->stream, d, a);
-  if (cap > 0) hipLaunchKernelGGL(k_dynwin_place, dim3((unsigned)slots), dim3(DW_THREADS), 0, c->stream, d, a, h.out);
-  int nr = 0;
-  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, nullptr))) return r;
-  *n = nr;
-  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+  const int ng = (int)gl.size();
+  return slot_run(c, spec, sa, c->dynwin, ng, "gates", "TJ_DYNWIN_MAX_BYTES", TJ_DYNWIN_MAX_BYTES, "lower max_windows, cap or the number of gates", [&](DynwinArgs& a) {
+    int e;   // (the first failure, or TJ_OK)
+    (e = query_buf(c, c->dynwin_gates, TJ_DYNWIN_MAX_GATES)) || (e = upload(c, c->dynwin_gates, gl.data(), (size_t)ng * sizeof(tj_dyn_gate)));
+    a.gates = c->dynwin_gates; a.n_gates = ng;
+    return e;
+  }, k_dynwin_refine, k_dynwin_place, rows, cap, n);
 }
 
-// tj_zone_windows (kernels_zone_windows.h): the rows of the owned robots from the context's own state, zone after zone (nothing of another robot is read, so a
-// sharded context answers for its own and a group calls this rank after rank).  *n = the rows; min(cap, *n) of them are written.  Two launches for the rows, one
-// for the count.  The zone list and the shape rows the zones name are copied per call.
-size_t zonewin_bytes(const Dev& d, size_t slots, int cap, int mw) {
-  return slots * (((size_t)3 * d.S + (size_t)4 * mw) * sizeof(ZoneLeaf) + 4 * sizeof(int)) + (size_t)cap * sizeof(tj_zonewin_row);
-}
+// tj_zone_windows (kernels_zone_windows.h): slot_run over (robot, zone).  The zone list and the shape rows the zones name are copied per call.
 int zonewin_run(tj_ctx* c, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !rows) || n_zones < 0 || n_shapes < 0 || (n_zones > 0 && !zones) || (n_shapes > 0 && !shapes)) return TJ_ERR_INVALID;
+  if (!rows_args_ok(c, n, rows, cap) || n_zones < 0 || n_shapes < 0 || (n_zones > 0 && !zones) || (n_shapes > 0 && !shapes)) return TJ_ERR_INVALID;
   const SearchSpec& spec = SEARCH_ZONEWIN;
   const std::string name = spec.name;
   const Dev& d = c->d;
@@ -1827,39 +1835,13 @@ int zonewin_run(tj_ctx* c, const tj_zone* zones, int n_zones, const double* shap
   }
   SearchArgs sa;
   if ((r = search_args(c, spec, 0.0, tol, max_depth, max_windows, sa))) return r;   // (the default tolerance: TJ_ZONEWIN_TOL_FRACTION of offset over vel_limit, a design condition)
-  const int nz = n_zones, mw = sa.max_windows, owned = d.u1 - d.u0;
-  const size_t slots = (size_t)std::max(owned, 0) * nz;
-  if ((r = query_budget(c, name + ": " + std::to_string(owned) + " robots x " + std::to_string(nz) + " zones of " + std::to_string(d.S) + " segments at max_windows " + std::to_string(mw) + " and cap " + std::to_string(cap),
-                        zonewin_bytes(d, slots, cap, mw), "TJ_ZONEWIN_MAX_BYTES", TJ_ZONEWIN_MAX_BYTES, "lower max_windows, cap or the number of zones")) ||
-      (r = query_state(c, spec.name, false, false))) return r;
-  if (slots == 0) { *n = 0; return TJ_OK; }
-  QUIESCE(c);
-  ZonewinHeld& h = c->zonewin;
-  const size_t live = slots * 2 * ((size_t)d.S + mw), leaf = slots * ((size_t)d.S + 2 * (size_t)mw);
-  if ((r = query_buf(c, h.n_rows, 1)) || (r = query_buf(c, h.zones, TJ_ZONEWIN_MAX_ZONES)) || (r = query_buf(c, h.shapes, (size_t)4 * TJ_ZONEWIN_MAX_ZONES * TJ_ZONEWIN_MAX_PLANES))) return r;
-  if (slots > h.slots || live > h.live || leaf > h.leaf) {
-    const size_t gs = std::max(slots, h.slots), gv = std::max(live, h.live), gf = std::max(leaf, h.leaf);
-    if ((r = query_grow(h.allocs, [&] { h.sized = {}; h.slots = 0; h.live = 0; h.leaf = 0; }, [&] {
-           int e;   // (the first failure, or TJ_OK)
-           (e = query_buf(c, h.sized.list, gv, &h.allocs)) || (e = query_buf(c, h.sized.leaf, gf, &h.allocs)) || (e = query_buf(c, h.sized.info, gs * 4, &h.allocs));
-           return e;
-         }))) return r;
-    h.slots = gs; h.live = gv; h.leaf = gf;
-  }
-  if (cap > h.cap) {
-    if ((r = query_grow(h.out_allocs, [&] { h.out = nullptr; h.cap = 0; }, [&] { return query_buf(c, h.out, cap, &h.out_allocs); }))) return r;
-    h.cap = cap;
-  }
-  ZonewinArgs a = h.sized;
-  if ((r = query_inputs(c, nullptr, nullptr, a.net, a.pt)) || (r = upload(c, h.zones, zl.data(), (size_t)nz * sizeof(tj_zone))) || (r = upload(c, h.shapes, packed.data(), packed.size() * sizeof(double)))) return r;
-  a.zones = h.zones; a.shapes = h.shapes; a.tol = sa.tol; a.max_depth = sa.max_depth; a.max_windows = mw; a.n_zones = nz; a.row_cap = cap; a.n_rows = h.n_rows;
-  if ((r = query_clear(c, h.n_rows, 1))) return r;
-  hipLaunchKernelGGL(k_zonewin_refine, dim3((unsigned)slots), dim3(ZW_THREADS), 0, c->stream, d, a);
-  if (cap > 0) hipLaunchKernelGGL(k_zonewin_place, dim3((unsigned)slots), dim3(ZW_THREADS), 0, c->stream, d, a, h.out);
-  int nr = 0;
-  if ((r = query_fetch(c, &nr, h.n_rows, 1)) || (r = query_finish(c, nullptr))) return r;
-  *n = nr;
-  return rows_finish(c, name, rows, h.out, cap, nr, "rows, the caller's hold", cap == 0 && !rows);
+  return slot_run(c, spec, sa, c->zonewin, n_zones, "zones", "TJ_ZONEWIN_MAX_BYTES", TJ_ZONEWIN_MAX_BYTES, "lower max_windows, cap or the number of zones", [&](ZonewinArgs& a) {
+    int e;   // (the first failure, or TJ_OK)
+    (e = query_buf(c, c->zonewin_zones, TJ_ZONEWIN_MAX_ZONES)) || (e = query_buf(c, c->zonewin_shapes, (size_t)4 * TJ_ZONEWIN_MAX_ZONES * TJ_ZONEWIN_MAX_PLANES)) ||
+        (e = upload(c, c->zonewin_zones, zl.data(), (size_t)n_zones * sizeof(tj_zone))) || (e = upload(c, c->zonewin_shapes, packed.data(), packed.size() * sizeof(double)));
+    a.zones = c->zonewin_zones; a.shapes = c->zonewin_shapes; a.n_zones = n_zones;
+    return e;
+  }, k_zonewin_refine, k_zonewin_place, rows, cap, n);
 }
 
 // tj_flight_profile (kernels_flight_profile.h): the records [U][n_times] of the owned robots; positions of ALL robots from the nets and piece times handed in

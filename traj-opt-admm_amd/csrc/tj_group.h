@@ -661,17 +661,23 @@ int group_gather(tj_group* g, bool state, Rec* rows, int cap, int& total, bool& 
     return (int)TJ_OK;
   });
 }
+// group_gather and its end, for a call whose ranks' rows simply follow one another: *n = the rows of all ranks, and more rows than cap are the group's TJ_ERR_CAPACITY in
+// the call's words (what: the window queries' "rows, the caller's hold", or listed_run's) unless the call only counts (no rows)
+template <class Rec, class Run>
+int group_row_list(tj_group* g, bool state, const char* group_name, Rec* rows, int cap, int* n, Run&& run, const char* what = "rows, the caller's hold") {
+  if (!n) return TJ_ERR_INVALID;
+  int total; bool unknown;
+  const int rc = group_gather(g, state, rows, cap, total, unknown, run);
+  if (rc < 0) return rc;
+  *n = total;
+  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, std::string(group_name) + ": " + std::to_string(total) + " " + what + " " + std::to_string(cap));
+  return TJ_OK;
+}
 // the rows of a query of listed_run
 template <class Q>
 int group_listed(tj_group* g, double range, double tol, int max_depth, int max_windows, double extra, typename Q::Rec* rows, int cap, int* n) {
-  if (!n) return TJ_ERR_INVALID;
-  int total; bool unknown;
-  const int rc = group_gather(g, true, rows, cap, total, unknown, [&](tj_ctx* c, const double* net, const double* pt, typename Q::Rec* out, int room, int* nr) {
-    return listed_run<Q>(c, range, tol, max_depth, max_windows, extra, net, pt, out, room, nr); });
-  if (rc < 0) return rc;
-  *n = total;
-  if (total > cap && rows) return group_fail(g, TJ_ERR_CAPACITY, std::string(Q::spec.group_name) + ": " + std::to_string(total) + " pairs are listed, the caller's rows hold " + std::to_string(cap));
-  return TJ_OK;
+  return group_row_list(g, true, Q::spec.group_name, rows, cap, n, [&](tj_ctx* c, const double* net, const double* pt, typename Q::Rec* out, int room, int* nr) {
+    return listed_run<Q>(c, range, tol, max_depth, max_windows, extra, net, pt, out, room, nr); }, "pairs are listed, the caller's rows hold");
 }
 
 extern "C" {
@@ -728,14 +734,8 @@ int tj_group_obstacle_approach(tj_group* g, double range, double tol, int max_de
 // whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count (group_gather).  A walk frontier overflow leaves the rank's
 // count untouched and so ends the group's call with the rank's TJ_ERR_CAPACITY, *n untouched.
 int tj_group_obstacle_windows(tj_group* g, double dist, double tol, int max_depth, int max_windows, tj_obswin_row* rows, int cap, int* n) {
-  if (!n) return TJ_ERR_INVALID;
-  int total; bool unknown;
-  const int rc = group_gather(g, false, rows, cap, total, unknown, [&](tj_ctx* c, const double*, const double*, tj_obswin_row* out, int room, int* nr) {
+  return group_row_list(g, false, "tj_group_obstacle_windows", rows, cap, n, [&](tj_ctx* c, const double*, const double*, tj_obswin_row* out, int room, int* nr) {
     return obswin_run(c, dist, tol, max_depth, max_windows, out, room, nr); });
-  if (rc < 0) return rc;
-  *n = total;
-  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_obstacle_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
-  return TJ_OK;
 }
 
 // tj_sight_windows, rank after rank with nets and piece_time from the owners: every rank gets the whole link list and answers the links whose robot a it owns, with
@@ -776,26 +776,14 @@ int tj_group_peak_dynamics(tj_group* g, double tol, int max_depth, int max_windo
 // tj_dynamics_windows, rank after rank, each from its own state, without gathered nets (ownership is by contiguous robot blocks in rank order: that is the (robot,
 // gate, t_first_lo) order).  A rank whose rows do not fit writes the first that do and is counted in full; the ranks behind it only count (group_gather).
 int tj_group_dynamics_windows(tj_group* g, const tj_dyn_gate* gates, int n_gates, double tol, int max_depth, int max_windows, tj_dynwin_row* rows, int cap, int* n) {
-  if (!n) return TJ_ERR_INVALID;
-  int total; bool unknown;
-  const int rc = group_gather(g, false, rows, cap, total, unknown, [&](tj_ctx* c, const double*, const double*, tj_dynwin_row* out, int room, int* nr) {
+  return group_row_list(g, false, "tj_group_dynamics_windows", rows, cap, n, [&](tj_ctx* c, const double*, const double*, tj_dynwin_row* out, int room, int* nr) {
     return dynwin_run(c, gates, n_gates, tol, max_depth, max_windows, out, room, nr); });
-  if (rc < 0) return rc;
-  *n = total;
-  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_dynamics_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
-  return TJ_OK;
 }
 
 // tj_zone_windows, rank after rank, each from its own state, without gathered nets: tj_group_dynamics_windows' way, in (robot, zone, t_first_lo) order
 int tj_group_zone_windows(tj_group* g, const tj_zone* zones, int n_zones, const double* shapes, int n_shapes, double tol, int max_depth, int max_windows, tj_zonewin_row* rows, int cap, int* n) {
-  if (!n) return TJ_ERR_INVALID;
-  int total; bool unknown;
-  const int rc = group_gather(g, false, rows, cap, total, unknown, [&](tj_ctx* c, const double*, const double*, tj_zonewin_row* out, int room, int* nr) {
+  return group_row_list(g, false, "tj_group_zone_windows", rows, cap, n, [&](tj_ctx* c, const double*, const double*, tj_zonewin_row* out, int room, int* nr) {
     return zonewin_run(c, zones, n_zones, shapes, n_shapes, tol, max_depth, max_windows, out, room, nr); });
-  if (rc < 0) return rc;
-  *n = total;
-  if (total > cap && !(cap == 0 && !rows)) return group_fail(g, TJ_ERR_CAPACITY, "tj_group_zone_windows: " + std::to_string(total) + " rows, the caller's hold " + std::to_string(cap));
-  return TJ_OK;
 }
 
 // the owners' rows [n_times] per robot; control points and piece_time from the owners, so every rank places the whole fleet as one context would
